@@ -75,7 +75,12 @@ def parse_args():
     ap.add_argument("--lz4-priority", action="store_true", help="development: the compress stream gets the high priority")
     ap.add_argument("--cu-split", default="", help="development: 'E,C' = the encode stream may use the first E CUs of the mask "
                                                    "order, the compress stream the last C (hipExtStreamCreateWithCUMask)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed (a fixed, seeded sample) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -221,6 +226,70 @@ def one_step(ctx, shards, S, blocksize, streams=None, lookahead=1):
         cmp_(shards[k])
         if k + lookahead < n:
             enc(shards[k + lookahead])
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# --dump-outputs (outside the timed region)
+# ---------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT = 64_000_000     # bytes of all .npy files together
+DUMP_VARIANTS = 1 << 16     # sampled variants (start / stop / ref / alt)
+
+
+def dump_outputs(shards, out_dir, seed=2504):
+    """What the last timed step handed its caller, as float arrays in out_dir/<name>.npy:
+        chunk_offsets   every shard's chunk offsets (n_chunks + 1 per shard, shards in order)            float64
+        chunk_sample    (shard, chunk) of a seeded sample of chunks                                       float64 [k, 2]
+        chunk_bytes     the framed bytes of those chunks, concatenated                                    float32
+        genotypes       the int8 matrix bytes each sampled chunk decodes to (CPU oracle)                  float32 [k, chunk bytes]
+        variant_sample  (shard, variant) of a seeded sample of variants                                   float64 [m, 2]
+        start, stop     their positions                                                                   float64 [m]
+        ref, alt        their allele codes                                                                float32 [m]
+    Which chunks and variants are sampled depends on the arguments alone (k from the largest a chunk can frame to), so two
+    builds run with the same arguments dump the same positions."""
+    import numpy as np
+    import torch
+    from oracle import oracle
+    rng = np.random.default_rng(seed)
+    out = {"chunk_offsets": np.concatenate([sh.off.cpu().numpy() for sh in shards]).astype(np.float64)}
+
+    v_first = np.cumsum([0] + [sh.V for sh in shards])
+    flat = np.sort(rng.choice(v_first[-1], min(int(v_first[-1]), DUMP_VARIANTS), replace=False))
+    si = np.searchsorted(v_first, flat, side="right") - 1
+    out["variant_sample"] = np.stack([si, flat - v_first[si]], axis=1).astype(np.float64)
+    cols = {k: [] for k in ("start", "stop", "ref", "alt")}
+    for s, sh in enumerate(shards):
+        idx = torch.from_numpy(flat[si == s] - v_first[s]).to(sh.off.device)
+        for k in cols:
+            cols[k].append(getattr(sh.res, k)[idx].cpu().numpy())
+    for k in ("start", "stop"):
+        out[k] = np.concatenate(cols[k]).view(np.uint32).astype(np.float64)
+    for k in ("ref", "alt"):
+        out[k] = np.concatenate(cols[k]).astype(np.float32)
+
+    # a chunk frames to at most chunk_nbytes + 32 bytes (bench's dst holds n_chunks of those); 4 bytes per byte as float32
+    chunk_nbytes = shards[0].chunk_nbytes
+    room = DUMP_LIMIT - sum(a.nbytes + 128 for a in out.values()) - 3 * 128
+    k = min(sum(sh.n_chunks for sh in shards), room // (4 * (2 * chunk_nbytes + 32) + 16))
+    if k < 1:
+        raise SystemExit(f"--dump-outputs: one chunk of {chunk_nbytes} B does not fit in {DUMP_LIMIT} B")
+    c_first = np.cumsum([0] + [sh.n_chunks for sh in shards])
+    flat = np.sort(rng.choice(c_first[-1], k, replace=False))
+    si = np.searchsorted(c_first, flat, side="right") - 1
+    out["chunk_sample"] = np.stack([si, flat - c_first[si]], axis=1).astype(np.float64)
+    framed, geno = [], []
+    for s, c in zip(si, flat - c_first[si]):
+        off = shards[s].off[c:c + 2].cpu().numpy()
+        framed.append(shards[s].dst[int(off[0]):int(off[1])].cpu().numpy())
+        geno.append(oracle.blosc_decompress(framed[-1]).view(np.int8))
+    out["chunk_bytes"] = np.concatenate(framed).astype(np.float32)
+    out["genotypes"] = np.stack(geno).astype(np.float32)
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    total = sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in out)
+    assert total <= DUMP_LIMIT, total
+    return {"dir": out_dir, "bytes": total, "chunks_sampled": int(k), "variants_sampled": int(len(out["start"]))}
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -798,6 +867,10 @@ def main():
     stages = ctx.profile_read()
     ctx.profile(False)
     frame_stream(False)
+    # the buffers still hold the last timed step's outputs (the gate only reads them; the later legs free them)
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(shards, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"))
 
     dev_for_reduce = "cuda" if backend == "nccl" else "cpu"
     dt_max, total_variants = sharding.reduce_job(dist if use_dist else None, dt, my_variants, device=dev_for_reduce)
@@ -921,6 +994,7 @@ def main():
         "roofline": roof,
         "per_rank": per_rank if world > 1 else None,
         "correctness": check,
+        "dumped_outputs": dumped,
         "stages_ms_per_step": {k: v["ms"] for k, v in stages_serial.items()},
         "stages_ms_per_step_timed_region": {k: v["ms"] / args.steps for k, v in stages.items()},
     }

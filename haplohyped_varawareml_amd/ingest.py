@@ -100,7 +100,8 @@ class Ingest:
         instead of inside the first input (include/hhgt_ingest.h)"""
         self.L = _L()
         self.ctx = ctx
-        self._hold_lock = threading.Lock()
+        self._hold_lock = threading.Condition()
+        self._n_held = 0             # holds not yet released: hhgt_ingest_close frees their buffers
         self.h = None
         device_inflate = normalize_device_inflate(device_inflate)
         o = IngestOpts(int(sc), int(vc), int(typesize), int(blocksize), int(fmt), int(bool(sites_only)),
@@ -165,12 +166,22 @@ class Ingest:
         the next event (hhgt_ingest_hold)"""
         t = C.c_int(-1)
         check(self.L.hhgt_ingest_hold(self.h, C.byref(t)))
+        with self._hold_lock:
+            self._n_held += 1
         return int(t.value)
 
     def release(self, token):
         with self._hold_lock:        # (a writer thread may release while another thread closes the engine)
+            self._n_held -= 1
+            self._hold_lock.notify_all()
             if getattr(self, "h", None):
                 check(self.L.hhgt_ingest_release(self.h, int(token)))
+
+    def wait_released(self):
+        """blocks until every hold() has been released: close() frees the held buffers, which a writer thread may still
+        be reading"""
+        with self._hold_lock:
+            self._hold_lock.wait_for(lambda: self._n_held == 0)
 
     def close(self):
         with self._hold_lock:

@@ -329,6 +329,8 @@ def _stream_files(ctx, jobs, stats, sc, vc, block_bytes, n_threads, sites_only, 
                 fs.is_bgzf = bool(ev.stats["is_bgzf"])
                 if on_end:
                     on_end(ev.input, fs)
+        if hold_columns:
+            ing.wait_released()      # the consumer's writer thread may still be writing held chunks: closing the engine frees them
     return stats
 
 

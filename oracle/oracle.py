@@ -1,6 +1,6 @@
 """ctypes wrapper over oracle/liboracle.so — CPU ORACLE, test infrastructure only.
 
-May be imported ONLY by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.
+May be imported ONLY by tests/, __graft_entry__.smoke() and bench.py (cpu_baseline leg, correctness gate, --dump-outputs).
 The product package (haplohyped_varawareml_amd) never imports this module.
 """
 import ctypes as C

@@ -144,6 +144,39 @@ def test_stream_files_callbacks(ctx, tmp_path):
     assert stats[0].samples == synth.sample_names(S) and seen["raw"] == 3 * 2 * 64 * 1024 * 2
 
 
+def test_stream_files_closes_after_held_columns_are_released(ctx, tmp_path, monkeypatch):
+    """hold_columns: closing the engine frees the held chunk bytes, so stream_files returns only after every release has
+    come back — the converter's .h5 writer thread releases a batch once it is on file, which may be after the last event"""
+    import threading
+    import time
+    S, V = 70, 2500
+    tab = synth.variant_table(8, V, S)
+    text, _ = synth.render_fixed_numpy("chr8", tab, S, seed=8)
+    p = str(tmp_path / "a.vcf.gz")
+    write_bgzf(p, text, level=1)
+    log, writers = [], []
+    close = Ingest.close
+
+    def logged_close(self):
+        log.append("close")
+        close(self)
+    monkeypatch.setattr(Ingest, "close", logged_close)
+
+    def write_later(release):       # a writer thread still busy with its batch when the engine has no events left
+        time.sleep(0.2)
+        log.append("release")
+        release()
+
+    def on_columns(i, g, n, framed, release):
+        writers.append(threading.Thread(target=write_later, args=(release,)))
+        writers[-1].start()
+
+    stream_files(ctx, [(p, "chr8")], sc=64, vc=1024, block_bytes=1 << 20, on_columns=on_columns, hold_columns=True)
+    for t in writers:
+        t.join()
+    assert writers and log.index("close") == len(writers), log
+
+
 def test_errors_surface(ctx, tmp_path):
     S, V = 20, 3000
     tab = synth.variant_table(5, V, S)
