@@ -35,6 +35,11 @@ class Window(C.Structure):     # hhgt_window
                 ("var_hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class BlockSel(C.Structure):   # hhgt_block_sel
+    _fields_ = [("src_ptr", C.c_uint64), ("src_bytes", C.c_uint64), ("dst_off", C.c_uint64), ("block", C.c_uint32),
+                ("lo", C.c_uint32), ("hi", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class EncodeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "n_lines", "n_records", "n_kept", "n_drop_region", "n_drop_filter", "n_haploid_padded",
@@ -111,6 +116,7 @@ def load():
     L.hhgt_compress_bound.argtypes = [u64, u64, i32, i32]
     L.hhgt_compress_chunks.argtypes = [vp, vp, u64, u64, i32, i32, i32, vp, u64, vp, C.POINTER(u64), vp]
     L.hhgt_decompress_chunks.argtypes = [vp, vp, vp, u64, u64, i32, i32, vp, C.POINTER(u64), vp]
+    L.hhgt_decompress_blocks.argtypes = [vp, vp, C.c_uint32, u64, i32, i32, vp, C.POINTER(u64), vp]
     L.hhgt_bgzf_scan.argtypes = [vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.hhgt_inflate_members.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, vp, vp, C.POINTER(u64), vp]
     L.hhgt_onehot_windows.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp, vp]

@@ -1114,3 +1114,33 @@ extern "C" int hhgt_decompress_chunks(hhgt_ctx *c, const void *d_src, const uint
     }
     return HHGT_OK;
 }
+
+extern "C" int hhgt_decompress_blocks(hhgt_ctx *c, const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chunk_nbytes,
+                                      int typesize, int blocksize, void *d_dst, uint64_t *n_bad, void *stream)
+{
+    if (!c || (n_sel && (!d_sel || !d_dst))) {
+        hhgt_set_error("decompress_blocks: null %s", !c ? "context" : !d_sel ? "selection array" : "destination");
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
+    if (n_bad) *n_bad = 0;
+    if (n_sel == 0) return HHGT_OK;
+    blocksize = effective_blocksize(chunk_nbytes, typesize, blocksize);
+    TRY(c->dec_bad.ensure(8));
+    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
+    {
+        StageTimer t(c, st, HHGT_STAGE_DECODE);
+        TRY(launch_decode_sel(d_sel, n_sel, chunk_nbytes, typesize, blocksize, static_cast<uint8_t *>(d_dst),
+                              c->dec_bad.as<unsigned long long>(), st));
+        t.stop();
+    }
+    if (n_bad) {
+        uint64_t nb = 0;
+        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_bad = nb;
+    }
+    return HHGT_OK;
+}

@@ -5,6 +5,9 @@
 // the encode -> compress -> decode round-trip property used by the full-size parity tests.
 // Workgroup = one block; wave j decodes stream j in place: compressed bytes staged at the end of its LDS
 // plane buffer, decoded bytes written from the start; the workgroup then un-shuffles the planes straight into HBM with 16 B stores.
+// k_decode_blocks decodes whole chunks; k_decode_sel (hhgt_decompress_blocks) decodes one selected block per workgroup
+// and writes only a byte range of it — the read of a hyperslab.  Both run the same header check, stream walk, in-place
+// LZ4 decode and un-shuffle (the __device__ functions below).
 #include "common.h"
 
 #define BLOSC_DOSHUFFLE 0x1u
@@ -133,78 +136,72 @@ __device__ __forceinline__ bool lz4_wave_decode(const uint8_t *cin, uint32_t csi
     return op == n;
 }
 
-// grid = n_chunks * nblocks; block = 64 * nwaves; dynamic LDS = nwaves * sstride + 16
-__global__ __launch_bounds__(1024) void k_decode_blocks(const uint8_t *__restrict__ src,
-                                                        const unsigned long long *__restrict__ chunk_off,
-                                                        uint32_t nblocks, uint64_t chunk_nbytes, uint32_t typesize,
-                                                        uint32_t blocksize, uint32_t sstride,
-                                                        uint8_t *__restrict__ dst, unsigned long long *n_bad)
+// ---- the decoder body, shared by k_decode_blocks (whole chunks) and k_decode_sel (block ranges) -----------------------
+
+// what the header of one framed chunk says, once validated against the dataset's parameters
+struct BloscHdr {
+    uint32_t hl;          // header bytes: 16 (Blosc1) or 32 (Blosc2 extended header)
+    uint32_t flags;
+    uint32_t doshuffle;   // byte-shuffled
+    uint32_t dont_split;  // one stream per block
+};
+
+// validates the header of the chunk ck[0, avail) (either format); false = bad chunk.  Every thread computes the same.
+__device__ __forceinline__ bool blosc_header(const uint8_t *ck, uint32_t avail, uint64_t chunk_nbytes, uint32_t typesize,
+                                             uint32_t blocksize, BloscHdr &h)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    __shared__ uint32_t s_bad;
+    h.hl = 16;
+    h.flags = 0;
+    h.doshuffle = 0;
+    h.dont_split = 1;
+    if (avail < 16u) return false;
+    bool bad = false;
+    const uint32_t version = ck[0];
+    const uint32_t flags = ck[2];
+    const uint32_t ts = ck[3], nbytes = ld32u(ck + 4), bs = ld32u(ck + 8), cbytes = ld32u(ck + 12);
+    const bool extended = (flags & BLOSC_DOSHUFFLE) && (flags & BLOSC_DOBITSHUFFLE);
+    h.flags = flags;
+    h.doshuffle = (flags & BLOSC_DOSHUFFLE) ? 1u : 0u;
+    if (extended) {
+        h.hl = 32;
+        bad = version < 3u || avail < 32u;
+        h.doshuffle = 0;
+        if (!bad)
+            for (int k = 0; k < 6; ++k) {
+                uint32_t f = ck[16 + k];
+                if (f == 1u) h.doshuffle = 1u;
+                else if (f != 0u) bad = true;
+            }
+    } else if (flags & BLOSC_DOBITSHUFFLE)
+        bad = true;
+    h.dont_split = (flags & BLOSC_DONT_SPLIT) ? 1u : 0u;
+    bad = bad || ts != typesize || nbytes != (uint32_t)chunk_nbytes || cbytes != avail;
+    if (flags & BLOSC_MEMCPYED) bad = bad || avail != chunk_nbytes + h.hl;
+    else bad = bad || bs != blocksize || ((flags >> 5) & 7u) != 1u;
+    return !bad;
+}
+
+// streams of a block of bsize bytes (the short last block of a chunk is always one stream)
+__device__ __forceinline__ uint32_t block_streams(const BloscHdr &h, uint32_t bsize, uint32_t blocksize, uint32_t typesize)
+{
+    return (!h.dont_split && bsize == blocksize) ? typesize : 1u;
+}
+
+// block b of a valid, compressed chunk -> its byte planes in LDS: wave j decodes stream j in place (plane j at
+// smem + j * sstride when the block is split, the whole block at smem otherwise).  Workgroup-cooperative, holds a barrier;
+// returns false (the same in every thread) when the block's stream table or a stream is corrupt.
+__device__ __forceinline__ bool decode_block_lds(const uint8_t *ck, uint32_t avail, uint32_t hl, uint32_t b, uint32_t bsize,
+                                                 uint32_t nstreams, uint32_t sstride, uint8_t *smem, uint32_t *s_bad)
+{
     const uint32_t nwaves = blockDim.x >> 6;
     const uint32_t wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;  // SGPR: stream sizes and LDS bases follow
-    const uint64_t chunk = blockIdx.x / nblocks;
-    const uint32_t b = blockIdx.x - (uint32_t)(chunk * nblocks);
-    const uint8_t *ck = src + chunk_off[chunk];
-    const uint32_t avail = (uint32_t)(chunk_off[chunk + 1] - chunk_off[chunk]);
-    if (threadIdx.x == 0) s_bad = 0;
-    __syncthreads();
-    bool bad = avail < 16u;
-    uint32_t flags = 0, hl = 16, doshuffle = 0, dont_split = 1;
-    if (!bad) {
-        const uint32_t version = ck[0];
-        flags = ck[2];
-        const uint32_t ts = ck[3], nbytes = ld32u(ck + 4), bs = ld32u(ck + 8), cbytes = ld32u(ck + 12);
-        const bool extended = (flags & BLOSC_DOSHUFFLE) && (flags & BLOSC_DOBITSHUFFLE);
-        doshuffle = (flags & BLOSC_DOSHUFFLE) ? 1u : 0u;
-        if (extended) {
-            hl = 32;
-            bad = bad || version < 3u || avail < 32u;
-            doshuffle = 0;
-            if (!bad)
-                for (int k = 0; k < 6; ++k) {
-                    uint32_t f = ck[16 + k];
-                    if (f == 1u) doshuffle = 1u;
-                    else if (f != 0u) bad = true;
-                }
-        } else if (flags & BLOSC_DOBITSHUFFLE)
-            bad = true;
-        dont_split = (flags & BLOSC_DONT_SPLIT) ? 1u : 0u;
-        bad = bad || ts != typesize || nbytes != (uint32_t)chunk_nbytes || cbytes != avail;
-        if (!(flags & BLOSC_MEMCPYED)) bad = bad || bs != blocksize || ((flags >> 5) & 7u) != 1u;
-    }
-    const uint64_t boff = (uint64_t)b * blocksize;
-    const uint32_t bsize = (uint32_t)(chunk_nbytes - boff < blocksize ? chunk_nbytes - boff : blocksize);
-    uint8_t *out_blk = dst + chunk * chunk_nbytes + boff;
-    if (!bad && (flags & BLOSC_MEMCPYED)) {
-        if (avail != chunk_nbytes + hl) bad = true;
-        else
-            for (uint32_t i = threadIdx.x; i < bsize; i += blockDim.x) out_blk[i] = ck[hl + boff + i];
-        if (bad && threadIdx.x == 0 && b == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
-    if (bad) {
-        if (threadIdx.x == 0 && b == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
-    const bool leftover = bsize != blocksize;
-    const uint32_t nstreams = (!dont_split && !leftover) ? typesize : 1u;
-    if (nstreams > nwaves) {  // header asks for a split this launch was not sized for
-        if (threadIdx.x == 0 && b == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
-    const uint32_t nelem = bsize / typesize;
     const uint32_t neblock = bsize / nstreams;
-    const uint32_t pstride = nstreams > 1u ? sstride : nelem;
-    uint8_t *planes = smem;
     // bytes of LDS the stream of this wave owns: its plane, or the whole area when the block is one stream
     const uint32_t cap = nstreams > 1u ? sstride : nwaves * sstride;
     // stream table of this block: walk the csize words (nstreams <= 16, serial by every thread)
-    const uint32_t bstart = ld32u(ck + hl + 4u * b);
-    uint32_t sp = bstart, my_sp = 0, my_cs = 0;
-    bool sbad = false;
-    for (uint32_t j = 0; j < nstreams; ++j) {
+    bool sbad = hl + 4u * b + 4u > avail;
+    uint32_t sp = sbad ? 0u : ld32u(ck + hl + 4u * b), my_sp = 0, my_cs = 0;
+    for (uint32_t j = 0; j < nstreams && !sbad; ++j) {
         if (sp + 4u > avail) {
             sbad = true;
             break;
@@ -221,7 +218,7 @@ __global__ __launch_bounds__(1024) void k_decode_blocks(const uint8_t *__restric
         sp += 4u + cs;
     }
     if (!sbad && wave < nstreams) {
-        uint8_t *plane = planes + (size_t)wave * pstride;
+        uint8_t *plane = smem + (size_t)wave * sstride;   // (one stream: wave 0 only)
         if (my_cs == neblock) {
             for (uint32_t k = lane; k < neblock; k += 64u) plane[k] = ck[my_sp + k];
         } else {
@@ -240,18 +237,23 @@ __global__ __launch_bounds__(1024) void k_decode_blocks(const uint8_t *__restric
             if (sbad || !lz4_wave_decode(cin, my_cs, plane, neblock)) sbad = true;
         }
     }
-    if (sbad) atomicOr(&s_bad, 1u);
+    if (sbad) atomicOr(s_bad, 1u);
     __syncthreads();
-    if (s_bad) {
-        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
-    // un-shuffle planes -> HBM
+    return *s_bad == 0u;
+}
+
+// decoded bytes [lo, hi) of the block whose planes decode_block_lds left in LDS -> out[0, hi - lo) (HBM), un-shuffled.
+// 16-byte stores when lo, hi and out are 16-byte aligned (the whole block of k_decode_blocks), a byte loop otherwise.
+__device__ __forceinline__ void unshuffle_range(const uint8_t *planes, uint32_t doshuffle, uint32_t typesize, uint32_t nstreams,
+                                                uint32_t bsize, uint32_t sstride, uint32_t lo, uint32_t hi, uint8_t *out)
+{
+    const uint32_t nelem = bsize / typesize;
+    const uint32_t pstride = nstreams > 1u ? sstride : nelem;
     if (!doshuffle || typesize == 1u) {
-        for (uint32_t i = threadIdx.x; i < bsize; i += blockDim.x) out_blk[i] = planes[i];
-    } else if (typesize == 2u && nstreams == 2u && (bsize & 15u) == 0u &&
-               ((reinterpret_cast<uintptr_t>(out_blk) & 15u) == 0)) {
-        for (uint32_t i = threadIdx.x * 16u; i < bsize; i += blockDim.x * 16u) {
+        for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) out[i - lo] = planes[i];
+    } else if (typesize == 2u && nstreams == 2u && ((lo | hi) & 15u) == 0u &&
+               ((reinterpret_cast<uintptr_t>(out) & 15u) == 0)) {
+        for (uint32_t i = lo + threadIdx.x * 16u; i < hi; i += blockDim.x * 16u) {
             uint2 a = *reinterpret_cast<const uint2 *>(planes + (i >> 1));
             uint2 c = *reinterpret_cast<const uint2 *>(planes + pstride + (i >> 1));
             uint4 v;
@@ -259,41 +261,134 @@ __global__ __launch_bounds__(1024) void k_decode_blocks(const uint8_t *__restric
             v.y = __builtin_amdgcn_perm(c.x, a.x, 0x07030602u);
             v.z = __builtin_amdgcn_perm(c.y, a.y, 0x05010400u);
             v.w = __builtin_amdgcn_perm(c.y, a.y, 0x07030602u);
-            *reinterpret_cast<uint4 *>(out_blk + i) = v;
+            *reinterpret_cast<uint4 *>(out + (i - lo)) = v;
         }
     } else {
         const uint32_t body = nelem * typesize;
-        for (uint32_t i = threadIdx.x; i < bsize; i += blockDim.x) {
+        for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
             uint8_t v;
             if (i < body) {
                 uint32_t e = i / typesize, j = i - e * typesize;
                 v = planes[j * pstride + e];
             } else
                 v = planes[(typesize - 1u) * pstride + nelem + (i - body)];
-            out_blk[i] = v;
+            out[i - lo] = v;
         }
     }
+}
+
+// grid = n_chunks * nblocks; block = 64 * nwaves; dynamic LDS = nwaves * sstride + 16
+__global__ __launch_bounds__(1024) void k_decode_blocks(const uint8_t *__restrict__ src,
+                                                        const unsigned long long *__restrict__ chunk_off,
+                                                        uint32_t nblocks, uint64_t chunk_nbytes, uint32_t typesize,
+                                                        uint32_t blocksize, uint32_t sstride,
+                                                        uint8_t *__restrict__ dst, unsigned long long *n_bad)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ uint32_t s_bad;
+    const uint32_t nwaves = blockDim.x >> 6;
+    const uint64_t chunk = blockIdx.x / nblocks;
+    const uint32_t b = blockIdx.x - (uint32_t)(chunk * nblocks);
+    const uint8_t *ck = src + chunk_off[chunk];
+    const uint32_t avail = (uint32_t)(chunk_off[chunk + 1] - chunk_off[chunk]);
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();
+    BloscHdr h;
+    const bool ok = blosc_header(ck, avail, chunk_nbytes, typesize, blocksize, h);
+    const uint64_t boff = (uint64_t)b * blocksize;
+    const uint32_t bsize = (uint32_t)(chunk_nbytes - boff < blocksize ? chunk_nbytes - boff : blocksize);
+    uint8_t *out_blk = dst + chunk * chunk_nbytes + boff;
+    // a bad header counts once per chunk, a corrupt block once per block
+    if (!ok) {
+        if (threadIdx.x == 0 && b == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    if (h.flags & BLOSC_MEMCPYED) {
+        for (uint32_t i = threadIdx.x; i < bsize; i += blockDim.x) out_blk[i] = ck[h.hl + boff + i];
+        return;
+    }
+    const uint32_t nstreams = block_streams(h, bsize, blocksize, typesize);
+    if (nstreams > nwaves) {  // header asks for a split this launch was not sized for
+        if (threadIdx.x == 0 && b == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    if (!decode_block_lds(ck, avail, h.hl, b, bsize, nstreams, sstride, smem, &s_bad)) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    unshuffle_range(smem, h.doshuffle, typesize, nstreams, bsize, sstride, 0u, bsize, out_blk);
+}
+
+// grid = n_sel, one selection per workgroup; block and dynamic LDS as k_decode_blocks.  Selection i: decoded bytes
+// [lo, hi) of Blosc block `block` of the chunk at src_ptr -> dst + dst_off.  A bad selection counts once.
+__global__ __launch_bounds__(1024) void k_decode_sel(const hhgt_block_sel *__restrict__ sel, uint64_t chunk_nbytes,
+                                                     uint32_t typesize, uint32_t blocksize, uint32_t sstride,
+                                                     uint8_t *__restrict__ dst, unsigned long long *n_bad)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ uint32_t s_bad;
+    const uint32_t nwaves = blockDim.x >> 6;
+    const hhgt_block_sel *s = sel + blockIdx.x;
+    const uint8_t *ck = reinterpret_cast<const uint8_t *>(s->src_ptr);
+    const uint64_t src_bytes = s->src_bytes;
+    const uint32_t b = s->block, lo = s->lo, hi = s->hi;
+    uint8_t *out = dst + s->dst_off;
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();
+    const uint32_t avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
+    BloscHdr h;
+    bool ok = blosc_header(ck, avail, chunk_nbytes, typesize, blocksize, h);
+    const uint32_t nblocks = (uint32_t)((chunk_nbytes + blocksize - 1) / blocksize);
+    ok = ok && b < nblocks;
+    const uint64_t boff = (uint64_t)b * blocksize;
+    const uint32_t bsize = ok ? (uint32_t)(chunk_nbytes - boff < blocksize ? chunk_nbytes - boff : blocksize) : 0u;
+    ok = ok && lo < hi && hi <= bsize;
+    if (!ok) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    if (h.flags & BLOSC_MEMCPYED) {
+        const uint8_t *from = ck + h.hl + boff;
+        for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) out[i - lo] = from[i];
+        return;
+    }
+    const uint32_t nstreams = block_streams(h, bsize, blocksize, typesize);
+    if (nstreams > nwaves || !decode_block_lds(ck, avail, h.hl, b, bsize, nstreams, sstride, smem, &s_bad)) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    unshuffle_range(smem, h.doshuffle, typesize, nstreams, bsize, sstride, lo, hi, out);
+}
+
+// launch shape shared by both kernels: waves per workgroup, the per-stream LDS stride, dynamic LDS bytes
+static int decode_geometry(int typesize, int blocksize, uint32_t *nwaves, uint32_t *sstride, size_t *lds)
+{
+    const uint32_t split = (typesize >= 2 && typesize <= 16 && blocksize / typesize >= 128) ? 1u : 0u;
+    *nwaves = split ? (uint32_t)typesize : 1u;
+    const uint32_t max_stream = split ? (uint32_t)blocksize / (uint32_t)typesize : (uint32_t)blocksize;
+    // per-stream buffer = decoded plane + in-place margin ((n >> 8) + 32) + alignment slack (4) + read-ahead (24)
+    uint32_t ss = (max_stream + (max_stream >> 8) + 60u + 15u) & ~15u;
+    {   // a block decoded as ONE stream (no-split header, or the short last block of a chunk) owns the whole area
+        const uint32_t whole = (uint32_t)blocksize + ((uint32_t)blocksize >> 8) + 60u;
+        if (whole > ss * *nwaves) ss = ((whole + *nwaves - 1) / *nwaves + 15u) & ~15u;
+    }
+    *sstride = ss;
+    *lds = (size_t)*nwaves * ss + 16u;
+    if (*lds > 160 * 1024 - 64) {
+        hhgt_set_error("decode: block of %d bytes x typesize %d does not fit LDS", blocksize, typesize);
+        return HHGT_ERR_ARG;
+    }
+    return HHGT_OK;
 }
 
 int launch_decode(const uint8_t *d_src, const uint64_t *d_chunk_off, uint64_t n_chunks, uint64_t chunk_nbytes,
                   int typesize, int blocksize, uint8_t *d_dst, unsigned long long *d_bad, hipStream_t st)
 {
     if (n_chunks == 0) return HHGT_OK;
-    const uint32_t split = (typesize >= 2 && typesize <= 16 && blocksize / typesize >= 128) ? 1u : 0u;
-    const uint32_t nwaves = split ? (uint32_t)typesize : 1u;
+    uint32_t nwaves, sstride;
+    size_t lds;
+    if (int rc = decode_geometry(typesize, blocksize, &nwaves, &sstride, &lds)) return rc;
     const uint32_t nblocks = (uint32_t)((chunk_nbytes + blocksize - 1) / blocksize);
-    const uint32_t max_stream = split ? (uint32_t)blocksize / (uint32_t)typesize : (uint32_t)blocksize;
-    // per-stream buffer = decoded plane + in-place margin ((n >> 8) + 32) + alignment slack (4) + read-ahead (24)
-    uint32_t sstride = (max_stream + (max_stream >> 8) + 60u + 15u) & ~15u;
-    {   // a block decoded as ONE stream (no-split header, or the short last block of a chunk) owns the whole area
-        const uint32_t whole = (uint32_t)blocksize + ((uint32_t)blocksize >> 8) + 60u;
-        if (whole > sstride * nwaves) sstride = ((whole + nwaves - 1) / nwaves + 15u) & ~15u;
-    }
-    const size_t lds = (size_t)nwaves * sstride + 16u;
-    if (lds > 160 * 1024 - 64) {
-        hhgt_set_error("decode: block of %d bytes x typesize %d does not fit LDS", blocksize, typesize);
-        return HHGT_ERR_ARG;
-    }
     static size_t attr_lds = 64 * 1024;  // dynamic LDS above 64 KiB needs an explicit opt-in
     if (lds > attr_lds) {
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_decode_blocks),
@@ -308,6 +403,29 @@ int launch_decode(const uint8_t *d_src, const uint64_t *d_chunk_off, uint64_t n_
     hipLaunchKernelGGL(k_decode_blocks, dim3((uint32_t)grid), dim3(64u * nwaves), lds, st, d_src,
                        reinterpret_cast<const unsigned long long *>(d_chunk_off), nblocks, chunk_nbytes,
                        (uint32_t)typesize, (uint32_t)blocksize, sstride, d_dst, d_bad);
+    HIP_TRY(hipGetLastError());
+    return HHGT_OK;
+}
+
+int launch_decode_sel(const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chunk_nbytes, int typesize, int blocksize,
+                      uint8_t *d_dst, unsigned long long *d_bad, hipStream_t st)
+{
+    if (n_sel == 0) return HHGT_OK;
+    uint32_t nwaves, sstride;
+    size_t lds;
+    if (int rc = decode_geometry(typesize, blocksize, &nwaves, &sstride, &lds)) return rc;
+    static size_t attr_lds = 64 * 1024;
+    if (lds > attr_lds) {
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_decode_sel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_lds = lds;
+    }
+    if (n_sel > 0x7fffffffu) {
+        hhgt_set_error("decode: too many selections");
+        return HHGT_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_decode_sel, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, chunk_nbytes, (uint32_t)typesize,
+                       (uint32_t)blocksize, sstride, d_dst, d_bad);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

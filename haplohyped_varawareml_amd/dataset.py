@@ -24,7 +24,6 @@ tensors with a numpy restatement of the rules above.
 import ctypes as C
 import json
 import os
-from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -146,7 +145,6 @@ class RandomHaplotypeDataset(Dataset):
         self.set_random_seed(seed)
         self.num_samples = len(self.bed)
         self._groups = {}
-        self._rows = OrderedDict()
         self.last_items = []
 
     def read_samples(self, samples_file):
@@ -168,46 +166,46 @@ class RandomHaplotypeDataset(Dataset):
                                        d_ref=torch.from_numpy(ref).to(d), d_alt=torch.from_numpy(alt).to(d))
         return self._groups[group]
 
-    def _donor_row(self, group, donor):
-        key = (group, donor)
-        if key not in self._rows:
-            row = torch.from_numpy(self.store.sample_row(group, donor)).to(self.ctx.device).contiguous()
-            self._rows[key] = row
-            while len(self._rows) > 64:
-                self._rows.popitem(last=False)
-        self._rows.move_to_end(key)
-        return self._rows[key]
-
     def __getitem__(self, idx):
         L, B = self.seq_length, self.batch_size
-        items = (_lib.Window * B)()
-        keep = []
-        self.last_items = []
+        # the batch's draws first, in the reference's order per item (region, donor, chromosome; :59-61) ...
+        draws = []
         for b in range(B):
             region_idx = np.random.randint(0, self.num_samples)          # :59
             donor_idx = np.random.randint(0, len(self.donor_ids))         # :60
             np.random.randint(0, len(self.chromosomes))                   # :61 (drawn, see module docstring)
+            draws.append((region_idx, donor_idx))
+        # ... then every item's window of variants, read in one GenotypeStore.read_windows call
+        items = (_lib.Window * B)()
+        self.last_items = []
+        reqs, req_of = [], {}
+        for b, (region_idx, donor_idx) in enumerate(draws):
             chrom, start, end = self.bed[region_idx]
             donor_id = self.donor_ids[donor_idx]
             new_start, _ = calculate_midpoint_region(start, end, L)       # :68
             digits = chrom[3:] if chrom.startswith("chr") else chrom
             group = f"chr_{digits}"
-            w = items[b]
-            ref = self.reference_genome.device_bases(chrom) if chrom in self.reference_genome.contigs else None
-            w.ref_ptr = ref.data_ptr() if ref is not None else 0
-            w.ref_len = ref.numel() if ref is not None else 0
-            w.win_start = new_start
             lo = hi = 0
             if group in self.store.meta["groups"] and donor_id in self.store.samples:
                 g = self._group(group)
                 lo = int(np.searchsorted(g["start"], new_start, side="left"))
                 hi = int(np.searchsorted(g["start"], new_start + L, side="left"))
-                row = self._donor_row(group, donor_id)
-                keep.append(row)
-                w.var_start_ptr, w.var_ref_ptr, w.var_alt_ptr = g["d_start"].data_ptr(), g["d_ref"].data_ptr(), g["d_alt"].data_ptr()
-                w.geno_ptr, w.geno_first = row.data_ptr(), 0
-            w.var_lo, w.var_hi = lo, hi
+                req_of[b] = len(reqs)
+                reqs.append((group, donor_id, lo, hi))
             self.last_items.append(dict(chrom=chrom, group=group, donor=donor_id, start=new_start, var_lo=lo, var_hi=hi))
+        rows = self.store.read_windows(reqs)
+        for b, it in enumerate(self.last_items):
+            w = items[b]
+            chrom = it["chrom"]
+            ref = self.reference_genome.device_bases(chrom) if chrom in self.reference_genome.contigs else None
+            w.ref_ptr = ref.data_ptr() if ref is not None else 0
+            w.ref_len = ref.numel() if ref is not None else 0
+            w.win_start = it["start"]
+            if b in req_of:
+                g = self._groups[it["group"]]
+                w.var_start_ptr, w.var_ref_ptr, w.var_alt_ptr = g["d_start"].data_ptr(), g["d_ref"].data_ptr(), g["d_alt"].data_ptr()
+                w.geno_ptr, w.geno_first = rows[req_of[b]].data_ptr(), it["var_lo"]
+            w.var_lo, w.var_hi = it["var_lo"], it["var_hi"]
         d = self.ctx.device
         with torch.cuda.device(d):
             d_items = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(d)
@@ -217,12 +215,11 @@ class RandomHaplotypeDataset(Dataset):
                                                         self.lut.ctypes.data, self.n_channels,
                                                         C.c_void_p(hap1.data_ptr()), C.c_void_p(hap2.data_ptr()),
                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-            torch.cuda.current_stream().synchronize()     # d_items / keep stay alive until the kernels are done
+            torch.cuda.current_stream().synchronize()     # d_items / rows stay alive until the kernels are done
         return hap1, hap2
 
     def close(self):
         self.reference_genome.close()
-        self._rows.clear()
         self._groups.clear()
         if self._own_ctx:
             self.ctx.close()

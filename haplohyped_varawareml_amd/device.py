@@ -19,6 +19,12 @@ DEFAULT_TYPESIZE = 2
 DEFAULT_BLOCKSIZE = 8192
 
 
+# hhgt_block_sel as a numpy record (the layout of _lib.BlockSel)
+SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("dst_off", np.uint64), ("block", np.uint32),
+                      ("lo", np.uint32), ("hi", np.uint32), ("reserved", np.uint32)])
+assert SEL_DTYPE.itemsize == C.sizeof(_lib.BlockSel) == 40
+
+
 def make_ring_layout(n_samples, ring_cols, sc=DEFAULT_SC, vc=DEFAULT_VC):
     """ring of `ring_cols` chunk columns (streaming: kept indices wrap, see include/hhgt.h)"""
     return Layout(int(n_samples), int(sc), int(vc), int(ring_cols), int(ring_cols) * int(vc))
@@ -354,6 +360,25 @@ class Context:
             check(self.lib.hhgt_decompress_chunks(self.h, _ptr(src), _ptr(chunk_off), int(n_chunks),
                                                   int(chunk_nbytes), typesize, blocksize, _ptr(dst),
                                                   C.byref(bad), _stream()))
+        return dst, int(bad.value)
+
+    def decompress_blocks(self, sel, chunk_nbytes, typesize=DEFAULT_TYPESIZE, blocksize=None, dst=None):
+        """gather decode (hhgt_decompress_blocks): sel is a numpy structured array of SEL_DTYPE (device chunk addresses,
+        block, decoded byte range [lo, hi), dst_off), uploaded in one copy.  dst: uint8 tensor (default: just large
+        enough for the selections).  -> (dst, n_bad)"""
+        if blocksize is None:
+            blocksize = min(int(chunk_nbytes), DEFAULT_BLOCKSIZE)
+            blocksize -= blocksize % typesize
+        sel = np.ascontiguousarray(sel, dtype=SEL_DTYPE)
+        n = len(sel)
+        with torch.cuda.device(self.device):
+            if dst is None:
+                size = int((sel["dst_off"] + sel["hi"] - sel["lo"]).max()) if n else 0
+                dst = torch.empty(size, dtype=torch.uint8, device=self.device)
+            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
+            bad = C.c_uint64(0)
+            check(self.lib.hhgt_decompress_blocks(self.h, _ptr(d_sel), n, int(chunk_nbytes), typesize, blocksize,
+                                                  _ptr(dst), C.byref(bad), _stream()))
         return dst, int(bad.value)
 
     # ---- BGZF on the device (SURVEY §8 f-4) -------------------------------------------------------

@@ -14,6 +14,7 @@ group = "chr_{N}" (the reference's group naming, vcf_to_h5.py:132).
 """
 import json
 import os
+from collections import OrderedDict
 
 import numpy as np
 
@@ -21,6 +22,40 @@ import numpy as np
 SNP_DTYPE = np.dtype([("chrom", "S5"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
                       ("alt", "S10"), ("phase1", np.int8), ("phase2", np.int8)])
 assert SNP_DTYPE.itemsize == 35
+
+# default budget of GenotypeStore's device cache of compressed chunks: a 2504-sample cohort's chunk of 64 x 8192 calls
+# compresses to ~0.1-0.2 MiB, so this holds about one chr1-sized group of such a cohort (the cache only grows with use)
+DEFAULT_CACHE_BYTES = 256 << 20
+
+# one selection of the window planner: request q, chunk (vcol, scol), Blosc block, decoded bytes [lo, hi) of the block,
+# and where they go in the output
+PLAN_DTYPE = np.dtype([("req", np.int64), ("vcol", np.int64), ("scol", np.int64), ("block", np.uint32),
+                       ("lo", np.uint32), ("hi", np.uint32), ("dst_off", np.uint64)])
+
+
+def plan_windows(requests, sc, vc, blocksize):
+    """(sample, v_lo, v_hi) requests -> (selections PLAN_DTYPE, out_off int64 [n + 1]).  Chunks are (sc, vc, 2) int8,
+    sample-major: byte 2v of sample row r = s % sc of chunk column v // vc is chunk byte r*vc*2 + 2*(v % vc) of chunk
+    (v // vc, s // sc).  Each range is split at chunk and block boundaries; request q's rows land at
+    [out_off[q], out_off[q + 1]) of the output, the requests end to end.  Empty requests give no selection."""
+    sc, vc, bs = int(sc), int(vc), int(blocksize)
+    out_off = np.zeros(len(requests) + 1, np.int64)
+    rows = []
+    for q, (s, v_lo, v_hi) in enumerate(requests):
+        s, v_lo, v_hi = int(s), int(v_lo), int(v_hi)
+        out_off[q + 1] = out_off[q] + 2 * max(v_hi - v_lo, 0)
+        if v_hi <= v_lo:
+            continue
+        scol, r = divmod(s, sc)
+        for vcol in range(v_lo // vc, (v_hi - 1) // vc + 1):
+            a, b = max(v_lo, vcol * vc), min(v_hi, (vcol + 1) * vc)
+            c0 = r * vc * 2 + 2 * (a - vcol * vc)
+            c1 = c0 + 2 * (b - a)
+            dst = int(out_off[q]) + 2 * (a - v_lo)
+            for blk in range(c0 // bs, (c1 - 1) // bs + 1):
+                x0, x1 = max(c0, blk * bs), min(c1, (blk + 1) * bs)
+                rows.append((q, vcol, scol, blk, x0 - blk * bs, x1 - blk * bs, dst + x0 - c0))
+    return np.array(rows, dtype=PLAN_DTYPE), out_off
 
 
 class StoreWriter:
@@ -95,12 +130,20 @@ class StoreWriter:
 class GenotypeStore:
     """Reader.  Opens either the working store directory or the HDF5 file the converter exports
     (`OUT/{cohort}.h5`: read natively through h5file.H5Reader — metadata and raw chunks only).  Decoding runs on the
-    GPU (hhgt_decompress_chunks); there is no CPU decode path in the product."""
+    GPU (hhgt_decompress_blocks: only the Blosc blocks a read touches); there is no CPU decode path in the product."""
 
-    def __init__(self, path, ctx=None):
+    def __init__(self, path, ctx=None, cache_bytes=DEFAULT_CACHE_BYTES):
+        """cache_bytes: budget of the device-side cache of compressed chunks (read_windows), least recently used first out"""
         self.path = path
         self._ctx = ctx
         self._h5 = None
+        self._files = {}                 # group -> (offsets, memmap of chunks.bin): directory store
+        self.cache_bytes = int(cache_bytes)
+        self._cache = OrderedDict()      # (group, chunk id) -> device uint8 tensor of the framed chunk
+        self._cache_used = 0
+        # host counters of read_windows: chunks and compressed bytes read from the file, Blosc blocks decoded and their
+        # decoded size (the kernel decodes a block whole and writes the selected range of it)
+        self.stats = dict(chunks_read=0, compressed_bytes_read=0, blocks_decoded=0, bytes_decoded=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -144,6 +187,9 @@ class GenotypeStore:
         self._h5 = r
 
     def close(self):
+        self._cache.clear()
+        self._cache_used = 0
+        self._files.clear()
         if self._h5 is not None:
             self._h5.close()
             self._h5 = None
@@ -168,54 +214,132 @@ class GenotypeStore:
         return (np.load(os.path.join(d, "start.npy")), np.load(os.path.join(d, "ref.npy")),
                 np.load(os.path.join(d, "alt.npy")), json.load(open(os.path.join(d, "chrom_runs.json"))))
 
+    def _chunk_id(self, group, vcol, scol):
+        return vcol * self.meta["groups"][group]["n_scol"] + scol       # vcol-major, then scol (module docstring)
+
+    def _read_chunk(self, group, vcol, scol):
+        """framed chunk (vcol, scol) of a group, as host uint8 (the .h5 through H5Reader, the directory store through a
+        memmap of chunks.bin and the group's offsets, both opened once per group)"""
+        if self._h5 is not None:
+            sc, vc = self.meta["sc"], self.meta["vc"]
+            return self._h5.read_chunk(self._h5_info[group], (scol * sc, vcol * vc, 0))
+        if group not in self._files:
+            d = os.path.join(self.path, group)
+            self._files[group] = (np.load(os.path.join(d, "offsets.npy")),
+                                  np.memmap(os.path.join(d, "chunks.bin"), dtype=np.uint8, mode="r"))
+        off, mm = self._files[group]
+        i = self._chunk_id(group, vcol, scol)
+        return np.asarray(mm[int(off[i]):int(off[i + 1])])
+
     def _chunk_row(self, group, scol):
         """framed chunks (vcol = 0 .. n_vcol-1) of sample-chunk row `scol`, as a list of uint8 arrays"""
-        g = self.meta["groups"][group]
+        return [self._read_chunk(group, v, scol) for v in range(self.meta["groups"][group]["n_vcol"])]
+
+    def _sample_index(self, sample):
+        s = self._idx[sample] if isinstance(sample, str) else int(sample)
+        if not 0 <= s < len(self.samples):
+            raise IndexError(f"sample {sample} out of range (0..{len(self.samples) - 1})")
+        return s
+
+    def _blocksize(self):
+        """the Blosc block size the chunks were written with, clamped to the chunk as c-blosc (and the decoder) clamp it"""
+        ts, nbytes = self.meta["typesize"], self.meta["sc"] * self.meta["vc"] * 2
+        bs = int(self.meta["blocksize"])
+        if bs > nbytes:
+            bs = nbytes - (nbytes % ts if ts > 1 and nbytes >= ts else 0)
+        return max(bs, 1)
+
+    def read_windows(self, requests):
+        """genotypes of (group, sample, v_lo, v_hi) requests: -> one int8 device tensor [v_hi - v_lo, 2] per request (views
+        into one buffer, the requests' rows end to end).  Only the Blosc blocks the ranges touch are decoded, in one
+        hhgt_decompress_blocks launch; only the chunks they lie in are read, the missing ones uploaded in one copy and
+        kept in the device-side chunk cache.  Nothing is copied back to the host."""
+        import torch
+        from .device import SEL_DTYPE
+        ctx = self._context()
         sc, vc = self.meta["sc"], self.meta["vc"]
-        if self._h5 is not None:
-            info = self._h5_info[group]
-            return [self._h5.read_chunk(info, (scol * sc, v * vc, 0)) for v in range(g["n_vcol"])]
-        off = np.load(os.path.join(self.path, group, "offsets.npy"))
-        mm = np.memmap(os.path.join(self.path, group, "chunks.bin"), dtype=np.uint8, mode="r")
-        ids = [v * g["n_scol"] + scol for v in range(g["n_vcol"])]
-        return [np.asarray(mm[int(off[i]):int(off[i + 1])]) for i in ids]
+        norm = []
+        for group, sample, v_lo, v_hi in requests:
+            n_var = self.meta["groups"][group]["n_variants"]
+            v_lo, v_hi = int(v_lo), int(v_hi)
+            if not 0 <= v_lo <= v_hi <= n_var:
+                raise IndexError(f"variants [{v_lo}, {v_hi}) outside {group} (0..{n_var})")
+            norm.append((group, self._sample_index(sample), v_lo, v_hi))
+        sel, out_off = plan_windows([r[1:] for r in norm], sc, vc, self._blocksize())
+        keys = [(norm[q][0], self._chunk_id(norm[q][0], int(vcol), int(scol)))
+                for q, vcol, scol in zip(sel["req"], sel["vcol"], sel["scol"])]
+        # chunks: cache hits, then the misses read on the host and uploaded in one copy
+        chunks, missing = {}, {}
+        for k, vcol, scol in zip(keys, sel["vcol"], sel["scol"]):
+            if k in chunks or k in missing:
+                continue
+            if k in self._cache:
+                self._cache.move_to_end(k)
+                chunks[k] = self._cache[k]
+            else:
+                missing[k] = self._read_chunk(k[0], int(vcol), int(scol))
+        if missing:
+            # one host-to-device copy of all misses; then every cached chunk gets its own allocation (a device copy), so
+            # evicting a chunk frees its bytes and the cache holds no more than its budget
+            host = np.concatenate(list(missing.values()))
+            dev = torch.from_numpy(host).to(ctx.device)
+            pos = 0
+            for k, a in missing.items():
+                chunks[k] = dev if len(missing) == 1 else dev[pos:pos + a.size].clone()
+                pos += a.size
+                self._cache[k] = chunks[k]
+                self._cache_used += a.size
+            del dev
+            self.stats["chunks_read"] += len(missing)
+            self.stats["compressed_bytes_read"] += int(host.size)
+        # (an evicted chunk of this call stays alive in `chunks` until the launch is done: decompress_blocks syncs)
+        while self._cache_used > self.cache_bytes and self._cache:
+            _, t = self._cache.popitem(last=False)
+            self._cache_used -= t.numel()
+        dsel = np.zeros(len(sel), dtype=SEL_DTYPE)
+        dsel["src_ptr"] = [chunks[k].data_ptr() for k in keys]
+        dsel["src_bytes"] = [chunks[k].numel() for k in keys]
+        for f in ("dst_off", "block", "lo", "hi"):
+            dsel[f] = sel[f]
+        total = int(out_off[-1])
+        out = torch.empty(max(total, 16), dtype=torch.uint8, device=ctx.device)
+        if len(sel):
+            chunk_nbytes, bs = sc * vc * 2, self._blocksize()
+            _, bad = ctx.decompress_blocks(dsel, chunk_nbytes, typesize=self.meta["typesize"], blocksize=bs, dst=out)
+            if bad:
+                raise RuntimeError(f"{bad} corrupt chunk(s) in {', '.join(sorted({r[0] for r in norm}))}")
+            self.stats["blocks_decoded"] += len(sel)
+            self.stats["bytes_decoded"] += int(np.minimum(bs, chunk_nbytes - sel["block"].astype(np.int64) * bs).sum())
+        g8 = out.view(torch.int8)
+        return [g8[int(out_off[q]):int(out_off[q + 1])].view(-1, 2) for q in range(len(norm))]
 
     def sample_row(self, group, sample):
-        """int8 [n_variants, 2] for one sample: decodes the sample's chunk row on the GPU."""
-        import torch
+        """int8 [n_variants, 2] for one sample: decodes the sample's blocks on the GPU (read_windows)."""
         g = self.meta["groups"][group]
-        s = self._idx[sample] if isinstance(sample, str) else int(sample)
-        sc, vc = self.meta["sc"], self.meta["vc"]
-        scol, sin = divmod(s, sc)
         if g["n_vcol"] == 0:
             return np.zeros((0, 2), np.int8)
-        parts = self._chunk_row(group, scol)
-        rel = [0]
-        for part in parts:
-            rel.append(rel[-1] + part.size)
-        ctx = self._context()
-        src = torch.from_numpy(np.concatenate(parts) if parts else np.zeros(0, np.uint8)).to(ctx.device)
-        d_off = torch.tensor(rel, dtype=torch.int64, device=ctx.device)
-        chunk_nbytes = sc * vc * 2
-        out, bad = ctx.decompress(src, d_off, len(parts), chunk_nbytes, typesize=self.meta["typesize"],
-                                  blocksize=self.meta["blocksize"])
-        if bad:
-            raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
-        rows = out.view(torch.int8).view(len(parts), sc, vc, 2)[:, sin].reshape(-1, 2)
-        return rows[: g["n_variants"]].cpu().numpy()
+        return self.read_windows([(group, sample, 0, g["n_variants"])])[0].cpu().numpy()
 
-    def snp_records(self, group, sample):
-        """the reference's per-donor compound records (vcf_to_h5.py:119-129), synthesised on demand"""
-        start, ref, alt, runs = self.variants(group)
-        ph = self.sample_row(group, sample)
-        rec = np.zeros(len(start), dtype=SNP_DTYPE)
-        bounds = [r[0] for r in runs] + [len(start)]
+    def snp_records(self, group, sample, v_lo=0, v_hi=None, tables=None):
+        """the reference's per-donor compound records (vcf_to_h5.py:119-129), synthesised on demand; v_lo / v_hi: those
+        of the group's variants [v_lo, v_hi) only (a windowed read); tables: variants(group), when the caller has it"""
+        start, ref, alt, runs = tables if tables is not None else self.variants(group)
+        n = len(start)
+        v_hi = n if v_hi is None else v_hi
+        if v_lo == 0 and v_hi == n:
+            ph = self.sample_row(group, sample)
+        else:
+            ph = self.read_windows([(group, sample, v_lo, v_hi)])[0].cpu().numpy()
+        rec = np.zeros(v_hi - v_lo, dtype=SNP_DTYPE)
+        bounds = [r[0] for r in runs] + [n]
         for (a, name), b in zip(runs, bounds[1:]):
-            rec["chrom"][a:b] = name.encode()[:5]
-        rec["start"] = start
-        rec["stop"] = start + 1
-        rec["ref"] = ref.view("S1")
-        rec["alt"] = alt.view("S1")
+            a, b = max(a, v_lo), min(b, v_hi)
+            if a < b:
+                rec["chrom"][a - v_lo:b - v_lo] = name.encode()[:5]
+        rec["start"] = start[v_lo:v_hi]
+        rec["stop"] = start[v_lo:v_hi] + 1
+        rec["ref"] = ref[v_lo:v_hi].view("S1")
+        rec["alt"] = alt[v_lo:v_hi].view("S1")
         rec["phase1"] = ph[:, 0]
         rec["phase2"] = ph[:, 1]
         return rec

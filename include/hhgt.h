@@ -220,6 +220,24 @@ int hhgt_decompress_chunks(hhgt_ctx *ctx, const void *d_src, const uint64_t *d_c
                            uint64_t n_chunks, uint64_t chunk_nbytes, int typesize, int blocksize,
                            void *d_dst, uint64_t *n_bad, void *stream);
 
+/* Gather form (read of a hyperslab; the reference's reader can only read a whole dataset, src/utils/h5_reader.py:37-41):
+ * selection i names one Blosc block of one framed chunk (either header format) and the decoded bytes [lo, hi) of that
+ * block (after un-shuffle); they are written to d_dst + dst_off.  Chunks are named by device address, so they may sit in
+ * any allocation.  d_sel: device array of n_sel selections; one workgroup decodes one selection.  typesize / blocksize /
+ * chunk_nbytes as in hhgt_decompress_chunks.  *n_bad (host, optional, syncs) = the number of bad selections: invalid
+ * chunk header, block at or past the chunk's block count, lo >= hi or hi past the end of the block, corrupt stream.  A
+ * bad selection's destination bytes are unspecified; every other selection is exact. */
+typedef struct {
+    uint64_t src_ptr;    /* device address of one framed chunk (either header format)                  */
+    uint64_t src_bytes;  /* its stored size                                                            */
+    uint64_t dst_off;    /* byte of d_dst that receives decoded byte lo of the block                   */
+    uint32_t block;      /* Blosc block of the chunk                                                   */
+    uint32_t lo, hi;     /* decoded bytes [lo, hi) of that block (after un-shuffle), lo < hi <= size   */
+    uint32_t reserved;   /* 0 */
+} hhgt_block_sel;
+int hhgt_decompress_blocks(hhgt_ctx *ctx, const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chunk_nbytes,
+                           int typesize, int blocksize, void *d_dst, uint64_t *n_bad, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values
