@@ -360,6 +360,158 @@ __global__ __launch_bounds__(1024) void k_decode_sel(const hhgt_block_sel *__res
     unshuffle_range(smem, h.doshuffle, typesize, nstreams, bsize, sstride, lo, hi, out);
 }
 
+// ---- allele counts straight out of LDS (hhgt_count_alleles) ------------------------------------------------------------
+
+// adds the counters of 4 calls to 4 packed byte counters: a, b hold the two alleles of the calls, one call per byte.  After
+// 64 rows no byte exceeds 128, so the packed adds never carry into the next byte.
+__device__ __forceinline__ void count4(uint32_t a, uint32_t b, uint32_t &an, uint32_t &ac, uint32_t &het, uint32_t &hom)
+{
+    const uint32_t H = 0x80808080u, L7 = 0x7F7F7F7Fu;
+    const uint32_t pa = ~a & H, pb = ~b & H;               // 0x80 where the allele is >= 0
+    const uint32_t xa = a ^ 0x01010101u, xb = b ^ 0x01010101u;
+    const uint32_t ea = ~(((xa & L7) + L7) | xa) & H;      // 0x80 where the allele is 1 (zero-byte test without carries)
+    const uint32_t eb = ~(((xb & L7) + L7) | xb) & H;
+    const uint32_t d = a ^ b;
+    const uint32_t ne = (((d & L7) + L7) | d) & H;         // 0x80 where the alleles differ
+    an += (pa >> 7) + (pb >> 7);
+    ac += (ea >> 7) + (eb >> 7);
+    het += (pa & pb & ne) >> 7;
+    hom += (ea & eb) >> 7;
+}
+
+// byte p of a decoded block that is cut into streams of neblock bytes, stream j at base + j * sstride (typesize 2: at
+// most two streams; one stream, or a memcpyed block in global memory, has neblock = the block size)
+__device__ __forceinline__ uint32_t stream_byte(const uint8_t *base, uint32_t p, uint32_t neblock, uint32_t sstride)
+{
+    return base[p < neblock ? p : sstride + (p - neblock)];
+}
+
+// grid = n_sel, one selection per workgroup; block = 64 * nwaves (decode_geometry, typesize 2); dynamic LDS = the larger
+// of decode_geometry's and 64 * blockDim + 16.  Thread t counts variants [g, g + 16) of the block for g = 16 (t + k
+// blockDim), k = 0, 1 (blockDim * 32 >= blocksize / 2 for every block size served), in registers, over every selected
+// row: decode_block_lds leaves the row's two byte planes in LDS, the thread reads its 16 calls of each with one 16-byte
+// load (shuffled, split blocks; any other block layout through stream_byte).  Then the counters go through LDS once,
+// variant-major, and out with one agent-scope add per (variant, counter) and consecutive lanes on consecutive words.
+__global__ __launch_bounds__(128) void k_count_alleles(const hhgt_count_sel *__restrict__ sel, uint32_t sc, uint32_t vc,
+                                                       uint32_t blocksize, uint32_t sstride, uint32_t *__restrict__ counts,
+                                                       uint64_t n_out, unsigned long long *n_bad)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ uint32_t s_bad;
+    const uint32_t nwaves = blockDim.x >> 6;
+    const hhgt_count_sel *s = sel + blockIdx.x;
+    const uint8_t *ck = reinterpret_cast<const uint8_t *>(s->src_ptr);
+    const uint64_t src_bytes = s->src_bytes, mask = s->row_mask, out_row = s->out_row;
+    const uint32_t part = s->part, lo = s->lo, hi = s->hi;
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();
+    const uint32_t avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
+    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
+    const uint32_t vb = blocksize >> 1, parts = vc * 2u / blocksize;
+    BloscHdr h;
+    bool ok = blosc_header(ck, avail, chunk_nbytes, 2u, blocksize, h);
+    ok = ok && part < parts && lo < hi && hi <= vb && (sc >= 64u || (mask >> sc) == 0ull) && out_row <= n_out &&
+         hi - lo <= n_out - out_row;
+    const uint32_t nstreams = block_streams(h, blocksize, blocksize, 2u);   // (every block of such a chunk is whole)
+    ok = ok && nstreams <= nwaves;
+    if (!ok) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    const bool memcpyed = (h.flags & BLOSC_MEMCPYED) != 0u;
+    // the fast form: both planes of a shuffled block split into two streams, 16-byte aligned
+    const bool planes16 = !memcpyed && h.doshuffle && nstreams == 2u && (vb & 15u) == 0u;
+    const uint32_t neblock = memcpyed ? blocksize : blocksize / nstreams;
+    uint32_t acc[2][4][4];   // [k][counter][word]: byte j of word w = variant g + 4 w + j
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int w = 0; w < 4; ++w) acc[k][c][w] = 0u;
+    uint32_t mlo = uni((uint32_t)mask), mhi = uni((uint32_t)(mask >> 32));
+    bool bad = false;
+    while ((mlo | mhi) != 0u) {
+        const uint32_t r = mlo ? (uint32_t)__builtin_ctz(mlo) : 32u + (uint32_t)__builtin_ctz(mhi);
+        if (mlo) mlo &= mlo - 1u;
+        else mhi &= mhi - 1u;
+        const uint32_t b = r * parts + part;
+        const uint8_t *base = smem;
+        if (memcpyed) {
+            base = ck + h.hl + (uint64_t)b * blocksize;
+        } else if (!decode_block_lds(ck, avail, h.hl, b, blocksize, nstreams, sstride, smem, &s_bad)) {
+            bad = true;
+            break;
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
+            if (planes16) {
+                if (g < vb) {
+                    const uint4 A = *reinterpret_cast<const uint4 *>(smem + g);
+                    const uint4 B = *reinterpret_cast<const uint4 *>(smem + sstride + g);
+                    count4(A.x, B.x, acc[k][0][0], acc[k][1][0], acc[k][2][0], acc[k][3][0]);
+                    count4(A.y, B.y, acc[k][0][1], acc[k][1][1], acc[k][2][1], acc[k][3][1]);
+                    count4(A.z, B.z, acc[k][0][2], acc[k][1][2], acc[k][2][2], acc[k][3][2]);
+                    count4(A.w, B.w, acc[k][0][3], acc[k][1][3], acc[k][2][3], acc[k][3][3]);
+                }
+            } else {
+                // allele j of variant v: byte j * vb + v of a shuffled block, byte 2 v + j of an interleaved one
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t a = 0xF7F7F7F7u, c = 0xF7F7F7F7u;   // -9 beyond the block: counts nothing
+#pragma unroll 1
+                    for (uint32_t j = 0; j < 4u; ++j) {
+                        const uint32_t v = g + 4u * (uint32_t)w + j;
+                        if (v < vb) {
+                            const uint32_t p0 = h.doshuffle && !memcpyed ? v : 2u * v;
+                            const uint32_t p1 = h.doshuffle && !memcpyed ? vb + v : 2u * v + 1u;
+                            const uint32_t sh = 8u * j;
+                            a = (a & ~(0xFFu << sh)) | (stream_byte(base, p0, neblock, sstride) << sh);
+                            c = (c & ~(0xFFu << sh)) | (stream_byte(base, p1, neblock, sstride) << sh);
+                        }
+                    }
+                    count4(a, c, acc[k][0][w], acc[k][1][w], acc[k][2][w], acc[k][3][w]);
+                }
+            }
+        }
+        if (!memcpyed) __syncthreads();   // the planes are read before the next row is decoded over them
+    }
+    if (bad) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    // flush, in two passes of 16 * blockDim variants: the packed counters -> LDS as [variant][AN, AC, HET, HOM] bytes (the
+    // order of d_counts), then word i of the pass -> d_counts, skipping zeros
+    uint32_t *out = counts + out_row * 4u;           // variant v of the block, v in [lo, hi): out + 4 (v - lo)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t pass0 = 16u * blockDim.x * (uint32_t)k, pass1 = pass0 + 16u * blockDim.x;
+        const uint32_t v0 = lo > pass0 ? lo : pass0, v1 = hi < pass1 ? hi : pass1;
+        if (v0 >= v1) continue;   // (uniform)
+        uint32_t wd[16];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t an = acc[k][0][w], ac = acc[k][1][w], het = acc[k][2][w], hom = acc[k][3][w];
+            const uint32_t p01 = __builtin_amdgcn_perm(ac, an, 0x05010400u), q01 = __builtin_amdgcn_perm(hom, het, 0x05010400u);
+            const uint32_t p23 = __builtin_amdgcn_perm(ac, an, 0x07030602u), q23 = __builtin_amdgcn_perm(hom, het, 0x07030602u);
+            wd[4 * w + 0] = __builtin_amdgcn_perm(q01, p01, 0x05040100u);
+            wd[4 * w + 1] = __builtin_amdgcn_perm(q01, p01, 0x07060302u);
+            wd[4 * w + 2] = __builtin_amdgcn_perm(q23, p23, 0x05040100u);
+            wd[4 * w + 3] = __builtin_amdgcn_perm(q23, p23, 0x07060302u);
+        }
+        __syncthreads();   // LDS is free: the last row's planes (or the previous pass) have been read
+        uint4 *dst = reinterpret_cast<uint4 *>(smem + 64u * threadIdx.x);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) dst[q] = make_uint4(wd[4 * q], wd[4 * q + 1], wd[4 * q + 2], wd[4 * q + 3]);
+        __syncthreads();
+        for (uint32_t i = 4u * (v0 - pass0) + threadIdx.x; i < 4u * (v1 - pass0); i += blockDim.x) {
+            const uint32_t x = smem[i];
+            if (x) __hip_atomic_fetch_add(out + (4u * (pass0 - lo) + i), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 // launch shape shared by both kernels: waves per workgroup, the per-stream LDS stride, dynamic LDS bytes
 static int decode_geometry(int typesize, int blocksize, uint32_t *nwaves, uint32_t *sstride, size_t *lds)
 {
@@ -426,6 +578,25 @@ int launch_decode_sel(const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chun
     }
     hipLaunchKernelGGL(k_decode_sel, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, chunk_nbytes, (uint32_t)typesize,
                        (uint32_t)blocksize, sstride, d_dst, d_bad);
+    HIP_TRY(hipGetLastError());
+    return HHGT_OK;
+}
+
+int launch_count_alleles(const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
+                         uint32_t *d_counts, uint64_t n_out, unsigned long long *d_bad, hipStream_t st)
+{
+    if (n_sel == 0) return HHGT_OK;
+    uint32_t nwaves, sstride;
+    size_t lds;
+    if (int rc = decode_geometry(2, blocksize, &nwaves, &sstride, &lds)) return rc;
+    const size_t flush = 64u * 64u * nwaves + 16u;   // one pass of the flush: 16 variants x 4 counter bytes per thread
+    if (lds < flush) lds = flush;                     // (blocksize <= 8192: at most 8.4 KiB, no opt-in needed)
+    if (n_sel > 0x7fffffffu) {
+        hhgt_set_error("count_alleles: too many selections");
+        return HHGT_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_count_alleles, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
+                       sstride, d_counts, n_out, d_bad);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

@@ -24,6 +24,12 @@ SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("dst_of
                       ("lo", np.uint32), ("hi", np.uint32), ("reserved", np.uint32)])
 assert SEL_DTYPE.itemsize == C.sizeof(_lib.BlockSel) == 40
 
+# hhgt_count_sel as a numpy record (the layout of _lib.CountSel)
+COUNT_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("row_mask", np.uint64),
+                            ("out_row", np.uint64), ("part", np.uint32), ("lo", np.uint32), ("hi", np.uint32),
+                            ("reserved", np.uint32)])
+assert COUNT_SEL_DTYPE.itemsize == C.sizeof(_lib.CountSel) == 48
+
 
 def make_ring_layout(n_samples, ring_cols, sc=DEFAULT_SC, vc=DEFAULT_VC):
     """ring of `ring_cols` chunk columns (streaming: kept indices wrap, see include/hhgt.h)"""
@@ -380,6 +386,29 @@ class Context:
             check(self.lib.hhgt_decompress_blocks(self.h, _ptr(d_sel), n, int(chunk_nbytes), typesize, blocksize,
                                                   _ptr(dst), C.byref(bad), _stream()))
         return dst, int(bad.value)
+
+    def count_alleles(self, sel, sc, vc, n_out=None, typesize=DEFAULT_TYPESIZE, blocksize=None, counts=None):
+        """per-variant allele counts (hhgt_count_alleles): sel is a numpy structured array of COUNT_SEL_DTYPE (device
+        chunk addresses, block `part` of the rows, row mask, variants [lo, hi), out_row), uploaded in one copy.  The
+        counts are ADDED to `counts`, an int32 tensor [n_out, 4] (the kernel's uint32 words; AN, AC, HET, HOM_ALT; default:
+        zeros just large enough for the selections), so calls may accumulate into one buffer.  -> (counts, n_bad)"""
+        if blocksize is None:
+            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
+        sel = np.ascontiguousarray(sel, dtype=COUNT_SEL_DTYPE)
+        n = len(sel)
+        with torch.cuda.device(self.device):
+            if counts is None:
+                if n_out is None:
+                    n_out = int((sel["out_row"] + sel["hi"] - sel["lo"]).max()) if n else 0
+                counts = torch.zeros((int(n_out), 4), dtype=torch.int32, device=self.device)
+            if (counts.dtype not in (torch.int32, torch.uint32) or counts.dim() != 2 or counts.shape[1] != 4
+                    or not counts.is_contiguous()):
+                raise ValueError("counts: a contiguous int32 tensor [n_out, 4]")
+            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
+            bad = C.c_uint64(0)
+            check(self.lib.hhgt_count_alleles(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize,
+                                              _ptr(counts), counts.shape[0], C.byref(bad), _stream()))
+        return counts, int(bad.value)
 
     # ---- BGZF on the device (SURVEY §8 f-4) -------------------------------------------------------
     def inflate_bgzf(self, raw, return_status=False, check_crc=True):

@@ -58,6 +58,53 @@ def plan_windows(requests, sc, vc, blocksize):
     return np.array(rows, dtype=PLAN_DTYPE), out_off
 
 
+# columns of GenotypeStore.allele_counts (and of hhgt_count_alleles' counters)
+AN, AC, HET, HOM_ALT = 0, 1, 2, 3
+
+# one selection of the count planner: chunk (vcol, scol), Blosc block `part` of its rows, the rows counted (bit r = row r),
+# variants [lo, hi) of that block, and the output row of variant lo
+COUNT_PLAN_DTYPE = np.dtype([("vcol", np.int64), ("scol", np.int64), ("part", np.uint32), ("row_mask", np.uint64),
+                             ("lo", np.uint32), ("hi", np.uint32), ("out_row", np.int64)])
+
+
+def plan_counts(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize=None):
+    """the selections of an allele count (hhgt_count_alleles) over the samples `sample_idx` (indices; each counted once,
+    however often it is named) and the variants [v_lo, v_hi) of a group of n_samples x n_variants stored in chunks of
+    sc x vc: per chunk row, the selected rows as a 64-bit mask; the variant range cut at chunk columns and at Blosc
+    blocks (a row of vc variants is vc * 2 / blocksize blocks of blocksize / 2 variants: its two halves with 8 KiB blocks
+    and vc = 8192).  Padded rows (samples >= n_samples) and padded variants (>= n_variants) are never selected.  Chunk
+    columns come in order, within one the chunk rows, within a chunk its blocks, so the selections of a chunk are adjacent.
+    An empty sample list or range gives no selection."""
+    sc, vc, n_samples, n_variants = int(sc), int(vc), int(n_samples), int(n_variants)
+    v_lo, v_hi = int(v_lo), int(v_hi)
+    bs = min(vc * 2, 8192) if blocksize is None else int(blocksize)
+    if not 1 <= sc <= 64 or bs % 2 or (vc * 2) % bs:
+        raise ValueError(f"plan_counts: chunks of {sc} x {vc} in blocks of {bs} bytes (1..64 rows, whole blocks per row)")
+    if not 0 <= v_lo <= v_hi <= n_variants:
+        raise IndexError(f"variants [{v_lo}, {v_hi}) outside 0..{n_variants}")
+    s = np.unique(np.asarray(sample_idx, dtype=np.int64).reshape(-1))
+    if s.size and (s[0] < 0 or s[-1] >= n_samples):
+        raise IndexError(f"sample index outside 0..{n_samples - 1}")
+    if s.size == 0 or v_hi == v_lo:
+        return np.zeros(0, COUNT_PLAN_DTYPE)
+    masks = np.zeros(-(-n_samples // sc), np.uint64)
+    np.bitwise_or.at(masks, s // sc, np.left_shift(np.uint64(1), (s % sc).astype(np.uint64)))
+    scols = np.nonzero(masks)[0]
+    vb = bs // 2
+    seg = np.arange(v_lo // vb, (v_hi - 1) // vb + 1, dtype=np.int64)        # blocks of vb variants touched, in order
+    a, b = np.maximum(v_lo, seg * vb), np.minimum(v_hi, (seg + 1) * vb)
+    out = np.zeros(seg.size * scols.size, COUNT_PLAN_DTYPE)
+    rep = lambda x: np.repeat(x, scols.size)
+    out["vcol"] = rep(seg * vb // vc)
+    out["part"] = rep((seg * vb % vc) // vb)
+    out["lo"] = rep(a - seg * vb)
+    out["hi"] = rep(b - seg * vb)
+    out["out_row"] = rep(a - v_lo)
+    out["scol"] = np.tile(scols, seg.size)
+    out["row_mask"] = np.tile(masks[scols], seg.size)
+    return out[np.lexsort((out["part"], out["scol"], out["vcol"]))]
+
+
 class StoreWriter:
     def __init__(self, path, samples, sc, vc, typesize=2, cohort_name="", donor_ids=None, chunk_format="blosc2"):
         self.path = path
@@ -144,6 +191,8 @@ class GenotypeStore:
         # host counters of read_windows: chunks and compressed bytes read from the file, Blosc blocks decoded and their
         # decoded size (the kernel decodes a block whole and writes the selected range of it)
         self.stats = dict(chunks_read=0, compressed_bytes_read=0, blocks_decoded=0, bytes_decoded=0)
+        # and of allele_counts: Blosc blocks it decoded, compressed bytes it read from the file (cache hits not included)
+        self.stats.update(count_blocks=0, count_compressed_bytes_read=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -312,6 +361,85 @@ class GenotypeStore:
             self.stats["bytes_decoded"] += int(np.minimum(bs, chunk_nbytes - sel["block"].astype(np.int64) * bs).sum())
         g8 = out.view(torch.int8)
         return [g8[int(out_off[q]):int(out_off[q + 1])].view(-1, 2) for q in range(len(norm))]
+
+    def allele_counts(self, group, samples=None, v_lo=0, v_hi=None, slab_bytes=None):
+        """per-variant allele counts of the variants [v_lo, v_hi) of a group over `samples` (names or indices, each counted
+        once; None = every sample): an int32 device tensor [v_hi - v_lo, 4], columns AN, AC, HET, HOM_ALT (module
+        constants) — called alleles, alleles equal to 1, heterozygous calls (two called, different alleles), calls 1/1.
+        Missing alleles are 2 * n_samples - AN.  hhgt_count_alleles decodes the selected rows' Blosc blocks and counts in
+        LDS; no genotype is written anywhere.  Chunks already in the read cache are used as they are, the rest read from the
+        file and uploaded in slabs of at most slab_bytes (default: the cache budget; a chunk larger than that goes alone),
+        each freed after its launch: the scan neither adds chunks to the cache nor evicts any."""
+        import torch
+        from .device import COUNT_SEL_DTYPE
+        ctx = self._context()
+        sc, vc = self.meta["sc"], self.meta["vc"]
+        g = self.meta["groups"][group]
+        n_var = g["n_variants"]
+        v_hi = n_var if v_hi is None else int(v_hi)
+        v_lo = int(v_lo)
+        if not 0 <= v_lo <= v_hi <= n_var:
+            raise IndexError(f"variants [{v_lo}, {v_hi}) outside {group} (0..{n_var})")
+        idx = (np.arange(len(self.samples)) if samples is None else
+               np.array([self._sample_index(x) for x in samples], dtype=np.int64))
+        bs = self._blocksize()
+        plan = plan_counts(idx, len(self.samples), sc, vc, n_var, v_lo, v_hi, blocksize=bs)
+        counts = torch.zeros((v_hi - v_lo, 4), dtype=torch.int32, device=ctx.device)
+        if not len(plan):
+            return counts
+        budget = self.cache_bytes if slab_bytes is None else int(slab_bytes)
+        keys = [(group, self._chunk_id(group, int(v), int(c))) for v, c in zip(plan["vcol"], plan["scol"])]
+        blocks = np.array([bin(int(m)).count("1") for m in plan["row_mask"]], np.int64)
+
+        def launch(chunks, rows):
+            dsel = np.zeros(len(rows), COUNT_SEL_DTYPE)
+            dsel["src_ptr"] = [chunks[keys[i]].data_ptr() for i in rows]
+            dsel["src_bytes"] = [chunks[keys[i]].numel() for i in rows]
+            for f in ("row_mask", "out_row", "part", "lo", "hi"):
+                dsel[f] = plan[f][rows]
+            _, bad = ctx.count_alleles(dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, counts=counts)
+            if bad:
+                raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
+            self.stats["count_blocks"] += int(blocks[rows].sum())
+
+        # selections in plan order (chunk columns in order), cut into slabs; a slab's missing chunks go up in one copy
+        slab, rows, host, size = {}, [], [], 0
+        for i, k in enumerate(keys):
+            if k not in slab:
+                if k in self._cache:
+                    slab[k] = self._cache[k]
+                else:
+                    a = self._read_chunk(group, int(plan["vcol"][i]), int(plan["scol"][i]))
+                    if host and size + a.size > budget:
+                        self._count_slab(slab, host, rows, launch)
+                        slab, rows, host, size = {}, [], [], 0
+                    slab[k] = None
+                    host.append((k, a))
+                    size += a.size
+            rows.append(i)
+        self._count_slab(slab, host, rows, launch)
+        return counts
+
+    def _count_slab(self, slab, host, rows, launch):
+        """uploads the chunks read for one slab of allele_counts in one copy, then runs its selections"""
+        import torch
+        if host:
+            cat = np.concatenate([a for _, a in host])
+            dev = torch.from_numpy(cat).to(self._context().device)
+            pos = 0
+            for k, a in host:
+                slab[k] = dev[pos:pos + a.size]
+                pos += a.size
+            self.stats["count_compressed_bytes_read"] += int(cat.size)
+        if rows:
+            launch(slab, rows)          # (synchronises: the slab's memory is free to go when this returns)
+
+    def allele_frequencies(self, group, samples=None, v_lo=0, v_hi=None, slab_bytes=None):
+        """AC / AN of allele_counts (same arguments): a float32 device tensor [v_hi - v_lo], NaN where AN == 0"""
+        import torch
+        c = self.allele_counts(group, samples, v_lo, v_hi, slab_bytes)
+        an = c[:, AN].to(torch.float32)
+        return torch.where(an > 0, c[:, AC].to(torch.float32) / an, torch.full_like(an, float("nan")))
 
     def sample_row(self, group, sample):
         """int8 [n_variants, 2] for one sample: decodes the sample's blocks on the GPU (read_windows)."""

@@ -238,6 +238,36 @@ typedef struct {
 int hhgt_decompress_blocks(hhgt_ctx *ctx, const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chunk_nbytes,
                            int typesize, int blocksize, void *d_dst, uint64_t *n_bad, void *stream);
 
+/* Per-variant allele counts straight out of the compressed genotype chunks (sc x vc x 2 int8, typesize 2, the values
+ * cpp/parse_vcf.cpp produces: 0, 1, >= 2, -9 for missing or the haploid pad).  The decoded genotypes never reach
+ * memory: one workgroup decodes the selected sample rows of one Blosc block column of a chunk (the same decoder as
+ * hhgt_decompress_blocks) and adds, for every counted variant, over the selected rows r with alleles (a, b):
+ *     d_counts[v][0] AN       [a >= 0] + [b >= 0]
+ *     d_counts[v][1] AC       [a == 1] + [b == 1]
+ *     d_counts[v][2] HET      [a >= 0 && b >= 0 && a != b]
+ *     d_counts[v][3] HOM_ALT  [a == 1 && b == 1]
+ * Selection i names one framed chunk (device address, either header format), one block `part` of its rows (a row of vc
+ * variants is vc * 2 / blocksize blocks of blocksize / 2 variants each: the halves of a row for vc = 8192 and 8 KiB
+ * blocks), the rows to count (bit r of row_mask = row r of the chunk, r < sc), and the variants [lo, hi) of that block;
+ * variant lo goes to row out_row of d_counts [n_out][4].  The call ADDS to d_counts (integer agent-scope atomics, one
+ * per counted variant and counter and selection: exact, independent of order), so a host may split a count over
+ * selections, calls and streams.  Serves typesize 2, (vc * 2) % blocksize == 0, blocksize <= 8192 and 1 <= sc <= 64;
+ * other geometries return HHGT_ERR_ARG.  *n_bad (host, optional, syncs) = the number of bad selections, counted as
+ * hhgt_decompress_blocks counts them: invalid chunk header, part past the row's blocks, lo >= hi or hi past the block,
+ * a row bit >= sc, out_row + (hi - lo) > n_out, a corrupt stream; a bad selection adds unspecified counts (a broken
+ * header or bad bounds: none). */
+typedef struct {
+    uint64_t src_ptr;    /* device address of one framed chunk (either header format)                  */
+    uint64_t src_bytes;  /* its stored size                                                            */
+    uint64_t row_mask;   /* sample rows of the chunk to count: bit r = row r                           */
+    uint64_t out_row;    /* row of d_counts that receives variant lo                                   */
+    uint32_t part;       /* Blosc block of each row (0 .. vc * 2 / blocksize - 1)                      */
+    uint32_t lo, hi;     /* variants [lo, hi) of that block, lo < hi <= blocksize / 2                  */
+    uint32_t reserved;   /* 0 */
+} hhgt_count_sel;
+int hhgt_count_alleles(hhgt_ctx *ctx, const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
+                       int typesize, int blocksize, uint32_t *d_counts, uint64_t n_out, uint64_t *n_bad, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values
