@@ -209,7 +209,6 @@ __global__ __launch_bounds__(256) void k_index_hop(const uint8_t *__restrict__ t
     // A batch reads 256 bytes of a head where the one-line path reads 1 KiB — and a record that is too short for its S
     // samples but ends inside that KiB is recognised there (its newline is IN the head).  So a candidate that came out of
     // a batch and turns out not to be a newline sends the wave back to the head it came from, once, with the wide window.
-    uint64_t len_other = 0, srch_soff = 0;   // bytes of the sample columns of the last record whose FORMAT was not "GT"; start of the one being searched
     uint64_t head_p = 0;       // the (verified) newline in front of the line whose head produced `cand`
     bool cand_batch = false;   // ... and that head was read by a batch
     bool rehead = false;
@@ -276,7 +275,6 @@ __global__ __launch_bounds__(256) void k_index_hop(const uint8_t *__restrict__ t
                 }
                 exp_head = expected;
                 exp_batch = true;
-                srch_soff = 0ull;
                 if (expected >= endw) {
                     stop = true;
                     continue;
@@ -355,7 +353,6 @@ __global__ __launch_bounds__(256) void k_index_hop(const uint8_t *__restrict__ t
             if (c15 == 0x0Au && c14 != '\r') {
                 found = true;
                 p = cand;
-                srch_soff = 0ull;
             } else if (cand_batch) {
                 // the head this candidate came from, once more and 1 KiB wide (no newline is recorded: head_p already is)
                 cand_batch = false;
@@ -431,10 +428,6 @@ __global__ __launch_bounds__(256) void k_index_hop(const uint8_t *__restrict__ t
             pos = a0 + (uint64_t)U * 1024u;
             continue;
         }
-        if (WALK && srch_soff != 0ull) {   // the sample columns of a record with another FORMAT: as long as the next one's, maybe
-            len_other = p - srch_soff;
-            srch_soff = 0ull;
-        }
         }
         if (!rehead) {
             if (p >= endw) break;
@@ -484,19 +477,14 @@ __global__ __launch_bounds__(256) void k_index_hop(const uint8_t *__restrict__ t
                                 est_len = cand - p;
                                 head_p = p;
                                 cand_batch = false;
-                            } else if (!gt && len_other != 0ull && soff + len_other <= last_term) {
-                                // another FORMAT ("GT:DP" ...): no width to compute — but such records often repeat the width
-                                // of the last one of their kind (fixed-width sub-fields): the newline is tried there, the
-                                // search from the bound stays the fallback, the encoders read every byte of a kept record
-                                cand = soff + len_other;
-                                fb = lo;
-                                have_cand = true;
-                                head_p = p;
-                                cand_batch = false;
-                                srch_soff = soff;
                             } else {
+                                // another FORMAT ("GT:DP", "GT:AD:DP:GQ:PL" ...; or a GT line that would end past the text):
+                                // no width to compute, so the first newline behind the bound is the record's.  (The walk once
+                                // tried the width of the last record of that kind first and took a newline found there on
+                                // trust: a shorter record followed by lines that happened to end at that byte was merged with
+                                // them and valid text flagged — tests/test_gpu_index_walk.py
+                                // test_width_of_the_last_other_format_record_is_not_trusted.)
                                 pos = lo;
-                                srch_soff = gt ? 0ull : soff;
                             }
                             hopped = true;
                         }

@@ -108,7 +108,10 @@ typedef struct {
  * outputs are undefined (the reference raises RuntimeError / asserts).
  * Records of >= 760 samples: the line index does not look at every byte (hhgt_set_index_mode); a pass that comes back
  * MALFORMED is run once more with every byte scanned before this call reports anything, so the outcome is the plain
- * scan's (round 4; the asynchronous forms below make one pass and report it).
+ * scan's (round 4).  The asynchronous forms below make one pass and report it: on valid text that pass fails only on the
+ * two shapes of DESIGN.md §4 — a record shorter than 2 S + 17 bytes whose newline lies beyond the 1 KiB head the walk
+ * reads, and a FORMAT == "GT" record some bytes short of S diploid calls followed by a line that ends exactly where its
+ * newline was predicted — and never returns a different matrix.
  */
 int hhgt_encode_text(hhgt_ctx *ctx, const void *d_text, uint64_t nbytes, const char *region,
                      const hhgt_layout *lay, uint64_t v_base, void *d_G, uint32_t *d_start,

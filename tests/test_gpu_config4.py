@@ -8,7 +8,7 @@ import torch
 
 from oracle import oracle
 from haplohyped_varawareml_amd import device as dev, synth
-from tests.gpu_util import assert_same_as_oracle, gpu_encode
+from tests.gpu_util import assert_one_pass, assert_same_as_oracle, gpu_encode
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +33,7 @@ def test_medium_vs_oracle(ctx):
     assert g["n_kept"] == len(kept) and g["stats"]["n_drop_filter"] == V - len(kept)
     assert g["stats"]["n_general_lines"] == int(t["with_dp"][kept].sum())     # only GT:DP lines leave the tile kernel
     assert (g["G"] == -9).any() and g["G"].max() == 1
+    assert_one_pass(ctx, text, S, o, region="chr4")     # GT:DP records among GT ones: one pass as the engine runs it
 
 
 def test_full_size_500k_x_5000_properties(ctx):

@@ -1,11 +1,15 @@
 """-m gpu: randomised VCF text (deterministic seeds) through the HIP path vs the oracle: odd GT strings,
 multi-digit alleles, missing sub-fields, FORMAT with GT in any position, long INFO, CRLF, blank lines,
-header lines in the middle, contig changes, sample counts around the tile edges."""
+header lines in the middle, contig changes, sample counts around the tile edges.  At cohort widths (S >= 760) the same
+text goes through one pass of the line index (tests/gpu_util.gpu_encode_one_pass), with and without the shapes DESIGN.md
+lets one pass flag."""
+import os
+
 import numpy as np
 import pytest
 
 from oracle import oracle
-from tests.gpu_util import assert_same_as_oracle, gpu_encode
+from tests.gpu_util import assert_one_pass, assert_same_as_oracle, gpu_encode
 
 pytestmark = pytest.mark.gpu
 
@@ -16,17 +20,19 @@ ALT_POOL = ["A", "C", "G", "T", "A", "C", "G", "T", "AT", "A,C", "*", "<DEL>", "
 REF_POOL = ["A", "C", "G", "T", "N", "AC", "a"]
 
 
-def make_text(rng, S, n_lines, fixed_share):
+def make_text(rng, S, n_lines, fixed_share, flaggable=True):
+    """flaggable=False: no blank and no late '##' lines — behind a GT record with short calls ("0", "", "1|") such a line
+    can end exactly where the walk predicts the record's newline, a shape one pass may flag"""
     names = [f"s{i}" for i in range(S)]
     out = ["##fileformat=VCFv4.2", "#" + "\t".join(["CHROM", "POS", "ID", "REF", "ALT", "QUAL", "FILTER", "INFO", "FORMAT"] + names)]
     pos = 100
     contig = "chrA"
     for i in range(n_lines):
         r = rng.random()
-        if r < 0.02:
+        if r < 0.02 and flaggable:
             out.append("")                       # blank line
             continue
-        if r < 0.03:
+        if r < 0.03 and flaggable:
             out.append("##late header line")
             continue
         if r < 0.06:
@@ -74,3 +80,42 @@ def test_random_text_matches_oracle(ctx, seed):
         for (a, name), b in zip(runs, bounds[1:]):
             got[a:b] = [name] * (b - a)
         assert got == o["chrom"]
+
+
+WIDE_SEEDS = int(os.environ.get("HHGT_FUZZ_SEEDS", "12"))
+
+
+def wide_case(seed, flaggable):
+    rng = np.random.default_rng(7000 + seed)
+    S = int(rng.choice([760, 761, 800, 1023, 1100, 2049, 2504]))
+    return S, make_text(rng, S, int(rng.integers(40, 160)), fixed_share=float(rng.choice([0.0, 0.5, 0.9])), flaggable=flaggable)
+
+
+@pytest.mark.parametrize("seed", range(WIDE_SEEDS))
+def test_wide_random_text_one_pass(ctx, seed):
+    """cohort widths without the flaggable shapes: every one pass (hop and walk, int8 and planes form) equals the oracle"""
+    S, text = wide_case(seed, flaggable=False)
+    for region in ("", "chrA", "chrB:1000-900000"):
+        assert_one_pass(ctx, text, S, oracle.vcf_encode(text, S, region=region), region=region)
+
+
+def test_wide_random_text_one_pass_flaggable(ctx):
+    """... and with blank / late '##' lines: the oracle's result or "Error parsing VCF file", never another matrix.  The
+    number of flagged seeds is printed and bounded, so that a drift toward flagging everything shows"""
+    flagged = []
+    for seed in range(WIDE_SEEDS):
+        S, text = wide_case(seed, flaggable=True)
+        n = 0
+        for region in ("", "chrA"):
+            try:
+                o = oracle.vcf_encode(text, S, region=region)
+            except Exception:
+                o = None
+            try:
+                n += assert_one_pass(ctx, text, S, o, region=region, flaggable=True)
+            except AssertionError as e:
+                raise AssertionError(f"seed {seed}, S {S}, region {region!r}: {e}") from e
+        if n:
+            flagged.append(seed)
+    print(f"one pass flagged {len(flagged)} of {WIDE_SEEDS} seeds: {flagged}")
+    assert len(flagged) <= WIDE_SEEDS // 4, flagged

@@ -8,7 +8,7 @@ import pytest
 from oracle import oracle
 from haplohyped_varawareml_amd import synth
 from haplohyped_varawareml_amd._lib import HhgtError
-from tests.gpu_util import assert_same_as_oracle, gpu_encode
+from tests.gpu_util import assert_one_pass, assert_same_as_oracle, gpu_encode
 
 pytestmark = pytest.mark.gpu
 
@@ -21,17 +21,29 @@ def index_mode(ctx, request):
     ctx.set_index_mode(-1)
 
 
+def one_pass(ctx, text, S, want, index_mode, region="chr5", flaggable=False):
+    """the one-pass leg (tests/gpu_util.assert_one_pass) in this case's index mode, int8 and planes form; want None: the
+    oracle rejects the text, so must every pass"""
+    try:
+        return assert_one_pass(ctx, text, S, want, region=region, flaggable=flaggable or want is None,
+                               forms=[(index_mode, False), (index_mode, True)])
+    finally:
+        ctx.set_index_mode(index_mode)
+
+
 def shard(S, V, seed=5, contig="chr5"):
     text, _ = synth.render_fixed_numpy(contig, synth.variant_table(seed, V, S), S, seed=seed)
     return bytes(text)
 
 
 @pytest.mark.parametrize("S,V", [(800, 700), (1100, 500), (2100, 300), (2504, 257)])   # k_index_hop<3> / <5>
-def test_fixed_width_matches_oracle(ctx, S, V):
+def test_fixed_width_matches_oracle(ctx, S, V, index_mode):
     text = shard(S, V)
     g = gpu_encode(ctx, text, S, region="chr5")
     assert g["n_kept"] == V
-    assert_same_as_oracle(g, oracle.vcf_encode(text, S, region="chr5"))
+    o = oracle.vcf_encode(text, S, region="chr5")
+    assert_same_as_oracle(g, o)
+    one_pass(ctx, text, S, o, index_mode)
 
 
 def body_lines(text):
@@ -41,19 +53,23 @@ def body_lines(text):
 
 
 @pytest.mark.parametrize("S", [800, 2100])
-def test_no_final_newline_and_crlf(ctx, S):
+def test_no_final_newline_and_crlf(ctx, S, index_mode):
     text = shard(S, 40)
     for t in (text[:-1], text.replace(b"\n", b"\r\n")):
-        assert_same_as_oracle(gpu_encode(ctx, t, S, region="chr5"), oracle.vcf_encode(t, S, region="chr5"))
+        o = oracle.vcf_encode(t, S, region="chr5")
+        assert_same_as_oracle(gpu_encode(ctx, t, S, region="chr5"), o)
+        one_pass(ctx, t, S, o, index_mode)
 
 
 @pytest.mark.parametrize("S", [800, 2100])
-def test_header_and_empty_lines_between_records(ctx, S):
+def test_header_and_empty_lines_between_records(ctx, S, index_mode):
     """'#' lines and empty lines are short: the index must not hop behind them, wherever they stand"""
     hdr, rec = body_lines(shard(S, 30))
     mixed = hdr + rec[:5] + [b"##comment in the middle"] + rec[5:9] + [b"#x", b"#y"] + rec[9:20] + hdr[-1:] + rec[20:]
     t = b"\n".join(mixed) + b"\n"
-    assert_same_as_oracle(gpu_encode(ctx, t, S, region="chr5"), oracle.vcf_encode(t, S, region="chr5"))
+    o = oracle.vcf_encode(t, S, region="chr5")
+    assert_same_as_oracle(gpu_encode(ctx, t, S, region="chr5"), o)
+    one_pass(ctx, t, S, o, index_mode)
     # empty lines: whatever the encoder says about them, it says the same with and without the hop (oracle: ignored or
     # an error) — compare the outcome
     t2 = b"\n".join(hdr + rec[:3] + [b""] + rec[3:]) + b"\n\n"
@@ -66,10 +82,11 @@ def test_header_and_empty_lines_between_records(ctx, S):
             gpu_encode(ctx, t2, S, region="chr5")
     else:
         assert_same_as_oracle(gpu_encode(ctx, t2, S, region="chr5"), want)
+    one_pass(ctx, t2, S, want, index_mode)      # (full-length GT records in front of the empty lines: nothing to flag)
 
 
 @pytest.mark.parametrize("S", [800, 2100])
-def test_variable_width_lines(ctx, S):
+def test_variable_width_lines(ctx, S, index_mode):
     """general-path lines of every length from the shortest a record with S samples can have (haploid calls: the newline
     sits right behind the bound) to long multi-digit / annotated ones, across range borders"""
     rng = np.random.default_rng(S)
@@ -97,11 +114,13 @@ def test_variable_width_lines(ctx, S):
     t = hdr + b"\n".join(lines) + b"\n"
     g = gpu_encode(ctx, t, S, region="5")
     assert g["n_kept"] == 260
-    assert_same_as_oracle(g, oracle.vcf_encode(t, S, region="5"))
+    o = oracle.vcf_encode(t, S, region="5")
+    assert_same_as_oracle(g, o)
+    one_pass(ctx, t, S, o, index_mode, region="5")
 
 
 @pytest.mark.parametrize("S", [800, 2100])
-def test_truncated_file_is_reported(ctx, S):
+def test_truncated_file_is_reported(ctx, S, index_mode):
     """a file cut off in mid-line ends in a line shorter than the bound: it reaches the parser and is reported"""
     text = shard(S, 50)
     cut = text[:len(text) - (2 * S + 300)]           # the last line keeps less than half of its sample columns
@@ -109,10 +128,11 @@ def test_truncated_file_is_reported(ctx, S):
         gpu_encode(ctx, cut, S, region="chr5")
     with pytest.raises(Exception):
         oracle.vcf_encode(cut, S, region="chr5")
+    one_pass(ctx, cut, S, None, index_mode)
 
 
 @pytest.mark.parametrize("S", [800, 2100])
-def test_short_line_in_mid_file_is_reported(ctx, S):
+def test_short_line_in_mid_file_is_reported(ctx, S, index_mode):
     """a kept record with fewer sample columns than the header declares: its newline lies inside a hop, the line merges
     with the next one, and the general encoder reports the newline it finds inside the sample columns"""
     hdr, rec = body_lines(shard(S, 40))
@@ -120,6 +140,7 @@ def test_short_line_in_mid_file_is_reported(ctx, S):
     t = b"\n".join(hdr + rec[:10] + [short] + rec[11:]) + b"\n"
     with pytest.raises(HhgtError, match="Error parsing VCF file"):
         gpu_encode(ctx, t, S, region="chr5")
+    one_pass(ctx, t, S, None, index_mode)
 
 
 @pytest.mark.parametrize("S", [800, 2100])
@@ -152,6 +173,8 @@ def test_line_with_empty_sample_columns(ctx, S, index_mode):
     else:
         with pytest.raises(HhgtError, match="Error parsing VCF file"):
             pend.wait()
+    flagged = one_pass(ctx, t, S, o, index_mode, flaggable=True)      # a documented shape: the oracle's result or flagged
+    assert flagged == (0 if index_mode == 2 and len(empty) < 1000 else 2)
 
 
 def _as_indel(line):
@@ -162,7 +185,7 @@ def _as_indel(line):
 
 @pytest.mark.parametrize("S", [1000, 2100])
 @pytest.mark.parametrize("how", ["indel", "other_contig"])
-def test_short_line_that_the_filter_drops_is_reported(ctx, S, how):
+def test_short_line_that_the_filter_drops_is_reported(ctx, S, how, index_mode):
     """A record with too few sample columns that the isSNP / region filter DROPS: nobody reads its sample columns, and at
     cohort widths its newline lies in the part the hopping index jumps over — the valid record behind it used to vanish
     with it, unreported (round 2's review).  k_parse_fixed now looks at the skipped bytes of every dropped record: the
@@ -192,10 +215,11 @@ def test_short_line_that_the_filter_drops_is_reported(ctx, S, how):
             gpu_encode(ctx, t, S, region="chr5")
     else:
         assert_same_as_oracle(gpu_encode(ctx, t, S, region="chr5"), want)
+    assert one_pass(ctx, t, S, want, index_mode, flaggable=True) == 2     # a documented shape: both forms flag it
 
 
 @pytest.mark.parametrize("S", [1000, 2100])
-def test_full_length_dropped_lines_are_not_reported(ctx, S):
+def test_full_length_dropped_lines_are_not_reported(ctx, S, index_mode):
     """... and dropped records of full length (indels, another contig) between kept ones change nothing"""
     hdr, rec = body_lines(shard(S, 40))
     mixed = list(rec)
@@ -205,4 +229,6 @@ def test_full_length_dropped_lines_are_not_reported(ctx, S):
     t = b"\n".join(hdr + mixed) + b"\n"
     g = gpu_encode(ctx, t, S, region="chr5")
     assert g["n_kept"] == 35
-    assert_same_as_oracle(g, oracle.vcf_encode(t, S, region="chr5"))
+    o = oracle.vcf_encode(t, S, region="chr5")
+    assert_same_as_oracle(g, o)
+    one_pass(ctx, t, S, o, index_mode)

@@ -260,6 +260,37 @@ def test_randomized_engine_matches_oracle(ctx, tmp_path, seed):
             check_against_oracle(res[n], text, S, region, sc, vc)
 
 
+@pytest.mark.parametrize("seed", list(range(int(os.environ.get("HHGT_FUZZ_SEEDS", "3")))))
+def test_gatk_shaped_cohort_engine_matches_oracle(ctx, tmp_path, seed):
+    """GATK-shaped text at cohort widths (tests/gatk_text.py: GT:AD:DP:GQ:PL records whose width varies by kilobytes, the
+    line index walks them) through the engine — one pass per text block, no retry — BGZF and plain sources, text blocks
+    that records straddle, vc 512 (int8 ring) and 4096 / 8192 (bit-plane ring): every chunk against the oracle"""
+    from tests.gatk_text import gatk_text
+    rng = np.random.default_rng(5000 + seed)
+    sc = int(rng.choice([64, 128]))
+    vc = [512, 4096, 8192][seed % 3]
+    jobs, expect = [], []
+    for k in range(2):
+        S = int(rng.choice([760, 1200, 2504]))
+        contig = f"chr{int(rng.integers(1, 23))}"
+        text, _ = gatk_text(rng, S, int(rng.choice([6, 12])) << 20, contig=contig)
+        src = str(tmp_path / (f"in{k}.vcf" + (".gz" if k == 0 else "")))
+        if k == 0:
+            write_bgzf(src, text, level=1)
+        else:
+            open(src, "wb").write(text)
+        region = contig if k == 0 or seed % 2 else ""
+        jobs.append((src, region))
+        expect.append((text, S, region))
+    line_max = max(max(len(x) for x in t.split(b"\n")) for t, _, _ in expect)
+    bb = int(max(int(rng.choice([1 << 20, 3 << 20])), 2 * line_max + (1 << 16)))
+    res = run_engine(ctx, jobs, sc=sc, vc=vc, fmt=dev.BLOSC2 if seed % 2 else dev.BLOSC1, block_bytes=bb,
+                     n_threads=int(rng.integers(1, 5)))
+    for n, (text, S, region) in enumerate(expect):
+        check_against_oracle(res[n], text, S, region, sc, vc)
+        assert res[n]["stats"]["n_blocks"] >= 2
+
+
 @pytest.mark.parametrize("shape", ["fixed", "mixed"])
 def test_planes_geometry_matches_oracle(ctx, tmp_path, shape, fixture_text):
     """default-like chunk geometry (vc a multiple of 4096, 8 KiB blocks, typesize 2): the engine keeps the ring as BIT PLANES

@@ -193,6 +193,30 @@ def test_converter_two_workers_one_gpu(tmp_path, golden_dir, fixture_golden):
     assert np.array_equal(rec["phase1"], o7["G"][2, :, 0]) and np.array_equal(rec["phase2"], o7["G"][2, :, 1])
 
 
+def test_converter_on_gatk_shaped_cohort(ctx, tmp_path):
+    """VCFtoHDF5Converter on a GATK-shaped file (GT:AD:DP:GQ:PL columns whose width varies by kilobytes) of 800 samples:
+    the line index walks it in one pass per block, and the stored genotypes are the oracle's"""
+    from haplohyped_varawareml_amd.store import GenotypeStore
+    from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
+    from tests.gatk_text import gatk_text
+    S = 800
+    names = synth.sample_names(S)
+    text, _ = gatk_text(np.random.default_rng(11), S, 12 << 20, contig="chr3", names=names)
+    vcf_dir = tmp_path / "vcf"
+    vcf_dir.mkdir()
+    write_bgzf(str(vcf_dir / "chr3.filtered.vcf.gz"), text)
+    sl = tmp_path / "samples.txt"
+    sl.write_text("\n".join(names))
+    conv = VCFtoHDF5Converter("c", str(vcf_dir), str(tmp_path / "out"), str(sl), 2, 1, n_gpus=1, donor_records=False,
+                              keep_store=True)
+    conv.run()
+    o = oracle.vcf_encode(text, S, region="chr3")
+    st = GenotypeStore(conv.store_path, ctx=ctx)
+    assert st.meta["groups"]["chr_3"]["n_variants"] == o["n_kept"]
+    for s in (0, 1, 399, 799):
+        assert np.array_equal(st.sample_row("chr_3", names[s]), o["G"][s]), names[s]
+
+
 def test_header_only_chromosome(ctx, tmp_path, fixture_golden):
     """a chromosome file with a header and no record: an empty group that neither the store nor the .h5 trips over"""
     from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
