@@ -115,7 +115,7 @@ extern "C" void hhgt_ctx_destroy(hhgt_ctx *c)
                       &c->counters, &c->cursor, &c->result, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n};
     for (DevBuf *b : bufs) b->release();
     for (auto &w : c->cw) {
-        DevBuf *wb[] = {&w.lz_scratch, &w.lz_csize, &w.lz_flags, &w.fr_bsize, &w.fr_csize, &w.fr_flags, &w.fr_state};
+        DevBuf *wb[] = {&w.lz_scratch, &w.lz_csize, &w.lz_flags, &w.fr_bsize, &w.fr_csize, &w.fr_flags};
         for (DevBuf *b : wb) b->release();
         if (w.lz_done) hipEventDestroy(w.lz_done);
         if (w.fr_done) hipEventDestroy(w.fr_done);
@@ -372,14 +372,6 @@ static int encode_stage_index(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes,
     return HHGT_OK;
 }
 
-// HHGT_ENC_STRIDE=0: GT:DP-style records of one column width go to the variable-width kernel like every other record that is not
-// "a|b\t" x S (round 3); default: the bit-plane tile kernel decodes them at their stride
-static bool stride_env()
-{
-    static const bool on = !(getenv("HHGT_ENC_STRIDE") && atoi(getenv("HHGT_ENC_STRIDE")) == 0);
-    return on;
-}
-
 // stages 2..: everything behind the index, sized by max_lines, counts and append position read on the device
 static int encode_stage_rest(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes, uint32_t n_regions, uint32_t max_lines,
                              const RegionFilter &rf, const LayoutDev &L, const uint64_t *d_cursor, void *d_G, void *d_P, uint32_t *d_start, uint32_t *d_stop,
@@ -415,7 +407,7 @@ static int encode_stage_rest(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes, 
                                 c->l_flags.as<uint32_t>(), c->l_kidx.as<uint32_t>(), c->l_crun.as<uint32_t>(),
                                 c->k_soff.as<uint32_t>(), c->k_lend.as<uint32_t>(), c->k_meta.as<uint32_t>(),
                                 c->redo_list.as<uint32_t>(), c->redo_flag.as<uint32_t>(), c->run_first.as<uint64_t>(), c->run_names.as<uint8_t>(),
-                                MAX_CHROM_RUNS, d_cursor, L.v_capacity, L.ring, d_start, d_stop, d_ref, d_alt, cnt, d_P != nullptr && stride_env(), st));
+                                MAX_CHROM_RUNS, d_cursor, L.v_capacity, L.ring, d_start, d_stop, d_ref, d_alt, cnt, d_P != nullptr, st));
         t.stop();
     }
     if (L.S > 0) {
@@ -826,14 +818,6 @@ static int compress_impl(hhgt_ctx *c, const void *d_src, const void *d_planes, P
     TRY(w.fr_bsize.ensure((size_t)n_chunks * nblocks * 4));
     TRY(w.fr_csize.ensure(((size_t)n_chunks + 1) * 8));
     TRY(w.fr_flags.ensure((size_t)n_chunks * 4));
-    {   // k_frame_fused's state words carry the tag of their launch: zeroed when (re)allocated and when the tag wraps
-        const size_t cap0 = w.fr_state.cap;
-        TRY(w.fr_state.ensure(frame_state_bytes(n_chunks)));
-        if (w.fr_state.cap != cap0 || ++w.fr_tag >= (1u << 20)) {
-            HIP_TRY(hipMemsetAsync(w.fr_state.p, 0, w.fr_state.cap, fst));
-            w.fr_tag = 1;
-        }
-    }
     if (w.fr_pending) {
         HIP_TRY(hipStreamWaitEvent(st, w.fr_done, 0));
         w.fr_pending = false;
@@ -841,8 +825,8 @@ static int compress_impl(hhgt_ctx *c, const void *d_src, const void *d_planes, P
     {
         StageTimer t(c, st, HHGT_STAGE_LZ4);
         if (!w.lz_flags.p) {
-            TRY(w.lz_flags.ensure(8));
-            HIP_TRY(hipMemsetAsync(w.lz_flags.p, 0, 8, st));
+            TRY(w.lz_flags.ensure(4));
+            HIP_TRY(hipMemsetAsync(w.lz_flags.p, 0, 4, st));
         }
         if (++w.lz_tag == 0) w.lz_tag = 1;
         TRY(launch_lz4_blocks(static_cast<const uint8_t *>(d_src), static_cast<const uint8_t *>(d_planes), pg, n_chunks, chunk_nbytes, typesize,
@@ -861,7 +845,7 @@ static int compress_impl(hhgt_ctx *c, const void *d_src, const void *d_planes, P
         TRY(launch_frame(w.lz_scratch.as<uint8_t>(), slot, w.lz_csize.as<uint32_t>(),
                          static_cast<const uint8_t *>(d_src), static_cast<const uint8_t *>(d_planes), pg, n_chunks, chunk_nbytes, typesize,
                          blocksize, format, w.fr_bsize.as<uint32_t>(), w.fr_csize.as<uint64_t>(), static_cast<uint8_t *>(d_dst),
-                         dst_cap, d_chunk_off, w.fr_flags.as<uint32_t>(), w.fr_state.p, w.fr_tag, fst));
+                         dst_cap, d_chunk_off, w.fr_flags.as<uint32_t>(), fst));
         t.stop();
     }
     if (fst != st) {
@@ -944,12 +928,6 @@ extern "C" int hhgt_reserve(hhgt_ctx *c, uint64_t text_bytes, uint32_t max_lines
         TRY(w.fr_bsize.ensure((size_t)n_chunks * nblocks * 4));
         TRY(w.fr_csize.ensure(((size_t)n_chunks + 1) * 8));
         TRY(w.fr_flags.ensure((size_t)n_chunks * 4));
-        const size_t cap0 = w.fr_state.cap;
-        TRY(w.fr_state.ensure(frame_state_bytes(n_chunks)));
-        if (w.fr_state.cap != cap0) {
-            HIP_TRY(hipMemset(w.fr_state.p, 0, w.fr_state.cap));
-            w.fr_tag = 0;
-        }
     }
     return HHGT_OK;
 }

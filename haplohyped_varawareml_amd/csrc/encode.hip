@@ -6,8 +6,8 @@
 // (and htslib's vcf_parse_format GT tokeniser behind it) by ONE pass over the sample columns of all
 // kept lines that emits every sample at once as G[s, v', 2].
 //
-// k_encode_tiles<TV> (fixed-width lines "a|b\t" x S — the 1000G shape): a 256-thread workgroup owns a
-//   TV-variant x 256-sample tile (TV = 64 by default: 32 KiB of LDS, four workgroups per CU).  Wave w reads
+// k_encode_tiles (fixed-width lines "a|b\t" x S — the 1000G shape): a 256-thread workgroup owns a
+//   TV-variant x 256-sample tile (TV = 64: 32 KiB of LDS, four workgroups per CU).  Wave w reads
 //   TV/4 lines; lane l reads 16 contiguous bytes (4 samples) of each line, so every wave-load is a coalesced
 //   1 KiB run of raw GT bytes.  Each lane packs its 4 samples x TV/4 variants in registers, the tile is
 //   transposed through an XOR-swizzled LDS image (conflict-free ds_write_b128 / ds_read_b128) and leaves as
@@ -16,7 +16,6 @@
 // k_encode_general (anything else: GT:DP columns, multi-digit alleles, haploid calls ...): one wave
 //   per line, tab-rank by ballot/prefix over 1 KiB pieces, htslib GT rule per field.
 #include "common.h"
-#include <stdlib.h>
 
 // -------------------------------------------------------------------------------------------------
 // one "a|b\t" field in a dword (little endian: a, sep, b, terminator) -> h0 | h1 << 8 ; bit 31 = not
@@ -46,14 +45,14 @@ typedef uint32_t u32x4_al __attribute__((ext_vector_type(4)));
 #define TILE_G 16  // lines whose 16-byte loads are in flight together per wave (1 KiB each)
 #endif
 
-// TV = variants per tile (128 or 64).  LDS = 256 rows x 2*TV bytes (64 / 32 KiB): TV = 64 lets four
-// workgroups share a CU, so the load, transpose and store phases of different tiles overlap.
-template <int TV>
-__global__ __launch_bounds__(256, TV == 128 ? 2 : 4) void k_encode_tiles(
+// TV = variants per tile.  LDS = 256 rows x 2*TV bytes = 32 KiB: four workgroups share a CU, so the load, transpose and
+// store phases of different tiles overlap (TV = 128, 64 KiB and two workgroups per CU, was the other width built).
+__global__ __launch_bounds__(256, 4) void k_encode_tiles(
     const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ k_soff,
     const uint32_t *__restrict__ k_meta, const uint64_t *__restrict__ d_cursor, LayoutDev lay, int8_t *__restrict__ G,
     uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag, DevCounters *cnt)
 {
+    constexpr int TV = 64;
     const uint64_t v_base = *d_cursor;   // append position: device-resident, so a chain of calls needs no host round trip
     constexpr int LW = TV / 4;        // lines per wave
     constexpr int SLOTS = TV / 8;     // 16-byte slots per LDS row
@@ -547,25 +546,18 @@ __global__ __launch_bounds__(64 * PT_NW, PT_WGS) void k_encode_planes(const uint
                                                           const uint64_t *__restrict__ d_cursor, LayoutDev lay,
                                                           uint8_t *__restrict__ P, int8_t *__restrict__ G,
                                                           uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag,
-                                                          DevCounters *cnt, uint32_t tiles_v, uint32_t tiles_s, uint32_t map)
+                                                          DevCounters *cnt, uint32_t tiles_v, uint32_t tiles_s)
 {
     HHGT_WAVE_PRIO();
     __shared__ __attribute__((aligned(16))) uint32_t img[1024 * PT_ROWDW];   // 32 KiB
     const uint64_t v_base = *d_cursor;
     const uint32_t n_kept = (uint32_t)cnt->n_kept;
-    // which tile: (variant tile, sample band) from the linear workgroup id
-    uint32_t tile_v, band;
-    if (map == 0u) {          // variant tile fastest (round 3a's 2-D grid)
-        tile_v = blockIdx.x % tiles_v;
-        band = blockIdx.x / tiles_v;
-    } else if (map == 1u) {   // sample band fastest: workgroups that run together read neighbouring KiB of the same lines
-        band = blockIdx.x % tiles_s;
-        tile_v = blockIdx.x / tiles_s;
-    } else {                  // ... and the bands of one variant tile stay on one XCD (workgroup id mod 8), so the cache lines
-        const uint32_t x = blockIdx.x & 7u, q = blockIdx.x >> 3;   // two neighbouring bands share are fetched by one L2
-        band = q % tiles_s;
-        tile_v = (q / tiles_s) * 8u + x;
-    }
+    // which tile: (variant tile, sample band) from the linear workgroup id.  Sample band fastest, so workgroups that run
+    // together read neighbouring KiB of the same lines, and the bands of one variant tile stay on one XCD (workgroup id
+    // mod 8), so the cache lines two neighbouring bands share are fetched by one L2
+    const uint32_t x = blockIdx.x & 7u, q = blockIdx.x >> 3;
+    const uint32_t band = q % tiles_s;
+    const uint32_t tile_v = (q / tiles_s) * 8u + x;
     if (tile_v >= tiles_v) return;
     if (band + 1u == tiles_s)
         encode_planes_tile<true>(text, n, k_soff, k_meta, v_base, n_kept, lay, P, G, redo_list, redo_flag, cnt, img, tile_v, band);
@@ -925,20 +917,11 @@ int launch_encode_tiles(const uint8_t *d_text, uint64_t n, const uint32_t *k_sof
                         uint32_t *redo_list, uint32_t *redo_flag, DevCounters *d_cnt, hipStream_t st)
 {
     if (n_lines_bound == 0 || lay.S == 0) return HHGT_OK;
-    static const int tv = getenv("HHGT_TILE_V") ? atoi(getenv("HHGT_TILE_V")) : 64;
-    // development: extra (unused) dynamic LDS per workgroup = fewer workgroups per CU (co-residency experiments)
-    static const int enc_lds_pad = getenv("HHGT_ENC_LDS_PAD") ? atoi(getenv("HHGT_ENC_LDS_PAD")) : 0;
-    uint32_t tiles_s = (lay.S + TILE_S - 1) / TILE_S;
-    if (tv == 128) {
-        // the append position is only known on the device: one tile more than the lines need covers any phase
-        uint64_t tiles_v = (127 + (uint64_t)n_lines_bound + 127) / 128;
-        hipLaunchKernelGGL(k_encode_tiles<128>, dim3((uint32_t)tiles_v, tiles_s), dim3(256), 0, st, d_text, n, k_soff,
-                           k_meta, d_cursor, lay, d_G, redo_list, redo_flag, d_cnt);
-    } else {
-        uint64_t tiles_v = (63 + (uint64_t)n_lines_bound + 63) / 64;
-        hipLaunchKernelGGL(k_encode_tiles<64>, dim3((uint32_t)tiles_v, tiles_s), dim3(256), enc_lds_pad, st, d_text, n, k_soff,
-                           k_meta, d_cursor, lay, d_G, redo_list, redo_flag, d_cnt);
-    }
+    const uint32_t tiles_s = (lay.S + TILE_S - 1) / TILE_S;
+    // the append position is only known on the device: one tile more than the lines need covers any phase
+    const uint64_t tiles_v = (63 + (uint64_t)n_lines_bound + 63) / 64;
+    hipLaunchKernelGGL(k_encode_tiles, dim3((uint32_t)tiles_v, tiles_s), dim3(256), 0, st, d_text, n, k_soff, k_meta, d_cursor, lay,
+                       d_G, redo_list, redo_flag, d_cnt);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }
@@ -966,11 +949,11 @@ int launch_encode_planes(const uint8_t *d_text, uint64_t n, const uint32_t *k_so
     const uint32_t tiles_s = (lay.S + TILE_S - 1) / TILE_S;
     // the append position is only known on the device: one tile more than the lines need covers any phase
     const uint64_t tiles_v = ((uint64_t)(PT_V - 1) + (uint64_t)n_lines_bound + (PT_V - 1)) / PT_V;
-    // measured (tools/dev/enc_map.sh, encode stage of the bench): 7.6 ms variant tile fastest, 7.4 ms band fastest / XCD-aware
-    static const uint32_t map = getenv("HHGT_ENC_MAP") ? (uint32_t)atoi(getenv("HHGT_ENC_MAP")) : 2u;
-    const uint64_t n_wg = map == 2u ? (tiles_v + 7ull) / 8ull * 8ull * tiles_s : tiles_v * tiles_s;
+    // (measured, encode stage of the bench: 7.6 ms variant tile fastest, 7.4 ms band fastest / XCD-aware)
+    // the XCD-aware order deals variant tiles out in groups of 8: the grid is rounded up to whole groups
+    const uint64_t n_wg = (tiles_v + 7ull) / 8ull * 8ull * tiles_s;
     hipLaunchKernelGGL(k_encode_planes, dim3((uint32_t)n_wg), dim3(64 * PT_NW), 0, st, d_text, n, k_soff, k_meta, d_cursor, lay,
-                       d_P, d_G, redo_list, redo_flag, d_cnt, (uint32_t)tiles_v, tiles_s, map);
+                       d_P, d_G, redo_list, redo_flag, d_cnt, (uint32_t)tiles_v, tiles_s);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

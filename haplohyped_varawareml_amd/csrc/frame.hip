@@ -13,7 +13,6 @@
 // k_frame_write : one workgroup per block; dword-wide funnel-shift copy of the stream bytes from the
 //                 LZ4 scratch slots to their final (byte-aligned) position.
 #include "common.h"
-#include <stdlib.h>
 
 #define BLOSC_DOSHUFFLE 0x1u
 #define BLOSC_MEMCPYED 0x2u
@@ -286,144 +285,10 @@ __global__ __launch_bounds__(256) void k_frame_write(FrameParams P, const uint8_
     frame_block(P, scratch, csize, src, dst, chunk, b, gb, coff, cend, memcpyed, memcpyed ? 0u : bstart[chunk * P.nblocks + b], planes, pg);
 }
 
-// ---------------------------------------------------------------------------------------------
-// k_frame_fused (round 4): the three kernels above in ONE launch.  FR_SPLIT workgroups per chunk; each sums the sizes of
-// its chunk's blocks (bstarts: an exclusive scan over at most FR_MAXB blocks, kept in LDS), the first of them chains the
-// chunk totals into chunk offsets by a decoupled look-back over one 64-bit state word per chunk (status | launch tag |
-// value: the word carries its own data, so no fence is needed beside agent-scope atomic loads / stores), the others wait
-// for that word; then every wave copies its share of the blocks to their final place.  Chunk ids are handed out by a
-// ticket in start order, so a workgroup only ever waits for workgroups that already run.  The LZ4 kernels are complete
-// when this starts (stream order): nobody waits for data, only for the offsets of at most a few chunks in front.
-#define FR_MAXB 1024u
-#define FR_ST_AGG 1ull
-#define FR_ST_INC 2ull
-#define FR_VAL_BITS 42
-#define FR_TAG_BITS 20
-struct FrameState {
-    unsigned long long ticket;
-    unsigned long long pad_[7];
-    unsigned long long st[1];   // [n_chunks]
-};
-
-__device__ __forceinline__ unsigned long long fr_word(unsigned long long status, uint32_t tag, unsigned long long v)
-{
-    return (status << 62) | ((unsigned long long)tag << FR_VAL_BITS) | v;
-}
-
-__global__ __launch_bounds__(256) void k_frame_fused(FrameParams P, const uint8_t *__restrict__ scratch, const uint32_t *__restrict__ csize,
-                                                     const uint8_t *__restrict__ src, FrameState *__restrict__ fs, uint32_t tag,
-                                                     uint32_t fr_split, unsigned long long *__restrict__ chunk_off, uint8_t *__restrict__ dst,
-                                                     uint64_t dst_cap, uint64_t n_chunks, const uint8_t *__restrict__ planes, PlanesGeom pg)
-{
-    __shared__ uint32_t s_bstart[FR_MAXB];
-    __shared__ uint32_t sm[8];
-    __shared__ unsigned long long s_tk, s_coff;
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    if (threadIdx.x == 0) {
-        const unsigned long long t = atomicAdd(&fs->ticket, 1ull);
-        if (t + 1ull == n_chunks * fr_split) fs->ticket = 0ull;   // the last one to start: every other ticket is drawn, the next launch starts at 0
-        s_tk = t;
-    }
-    __syncthreads();
-    const uint64_t chunk = s_tk / fr_split;
-    const uint32_t q = (uint32_t)(s_tk - chunk * fr_split);
-    // ---- block sizes of the chunk -> bstarts, chunk size (every workgroup of the chunk: 256 loads)
-    uint32_t carry = P.hl + 4u * P.nblocks;
-    for (uint32_t b0 = 0; b0 < P.nblocks; b0 += 256u) {
-        const uint32_t b = b0 + threadIdx.x;
-        uint32_t sz = 0;
-        if (b < P.nblocks) {
-            const uint64_t boff = (uint64_t)b * P.blocksize;
-            const bool leftover = P.chunk_nbytes - boff < P.blocksize;
-            const uint32_t ns = (P.split && !leftover) ? P.typesize : 1u;
-            const uint32_t *cs = csize + (chunk * P.nblocks + b) * P.nwaves;
-            for (uint32_t j = 0; j < ns; ++j) sz += 4u + cs[j];
-        }
-        const uint32_t inc = frame_wave_incl_scan(sz);
-        if (lane == 63) sm[w] = inc;
-        __syncthreads();
-        uint32_t base = 0, tot = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t x = sm[i];
-            if ((uint32_t)i < w) base += x;
-            tot += x;
-        }
-        __syncthreads();
-        if (b < P.nblocks) s_bstart[b] = carry + base + inc - sz;
-        carry += tot;
-    }
-    unsigned long long cb = carry;
-    const uint32_t memcpyed = cb > P.chunk_nbytes + P.hl ? 1u : 0u;
-    if (memcpyed) cb = P.chunk_nbytes + P.hl;
-    // ---- chunk offset
-    unsigned long long *st = fs->st;
-    if (w == 0) {
-        unsigned long long coff = 0;
-        if (q == 0) {
-            if (chunk != 0) {
-                if (lane == 0) __hip_atomic_store(&st[chunk], fr_word(FR_ST_AGG, tag, cb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                // look back: 64 chunks per step, the nearest inclusive word ends it
-                long long hi = (long long)chunk - 1;
-                for (;;) {
-                    const long long i = hi - (long long)lane;
-                    unsigned long long x = 0;
-                    bool ok = false;
-                    for (;;) {   // until every word down to the nearest inclusive one (or 64 of them) is of this launch
-                        x = i >= 0 ? __hip_atomic_load(&st[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : fr_word(FR_ST_INC, tag, 0ull);
-                        const uint32_t xt = (uint32_t)(x >> FR_VAL_BITS) & ((1u << FR_TAG_BITS) - 1u);
-                        ok = xt == tag && (x >> 62) != 0ull;
-                        const unsigned long long incm = __builtin_amdgcn_ballot_w64(ok && (x >> 62) == FR_ST_INC);
-                        const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
-                        // lanes in front of (= nearer than) the first inclusive one must all be there
-                        const unsigned long long need = incm ? ((incm & (0ull - incm)) << 1) - 1ull : ~0ull;
-                        if ((okm & need) == need) {
-                            const bool mine = ((need >> lane) & 1ull) != 0ull;
-                            unsigned long long v = mine ? (x & ((1ull << FR_VAL_BITS) - 1ull)) : 0ull;
-#pragma unroll
-                            for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-                            coff += (unsigned long long)__shfl(v, 0, 64);
-                            ok = incm != 0ull;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(2);
-                    }
-                    if (ok) break;
-                    hi -= 64;
-                }
-            }
-            if (lane == 0) {
-                __hip_atomic_store(&st[chunk], fr_word(FR_ST_INC, tag, coff + cb), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                chunk_off[chunk] = coff;
-                if (chunk + 1 == n_chunks) chunk_off[n_chunks] = coff + cb;
-            }
-        } else {
-            for (;;) {
-                const unsigned long long x = __hip_atomic_load(&st[chunk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const uint32_t xt = (uint32_t)(x >> FR_VAL_BITS) & ((1u << FR_TAG_BITS) - 1u);
-                if (xt == tag && (x >> 62) == FR_ST_INC) {
-                    coff = (x & ((1ull << FR_VAL_BITS) - 1ull)) - cb;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
-        if (lane == 0) s_coff = coff;
-    }
-    __syncthreads();
-    const unsigned long long coff = s_coff, cend = coff + cb;
-    if (cend > dst_cap) return;   // capacity error is reported by the host from chunk_off[n]
-    // ---- this workgroup's share of the blocks, a wave per block
-    const uint32_t per = (P.nblocks + fr_split - 1u) / fr_split;
-    const uint32_t b_end = (q + 1u) * per < P.nblocks ? (q + 1u) * per : P.nblocks;
-    for (uint32_t b = q * per + w; b < b_end; b += 4u)
-        frame_block(P, scratch, csize, src, dst, chunk, b, chunk * P.nblocks + b, coff, cend, memcpyed, memcpyed ? 0u : s_bstart[b], planes, pg);
-}
-
 int launch_frame(const uint8_t *d_scratch, size_t slot_bytes, const uint32_t *d_csize, const uint8_t *d_src, const uint8_t *d_planes,
                  PlanesGeom pg, uint64_t n_chunks, uint64_t chunk_nbytes, int typesize, int blocksize, int format,
                  uint32_t *d_bstart, uint64_t *d_chunk_csize, uint8_t *d_dst, uint64_t dst_cap,
-                 uint64_t *d_chunk_off, uint32_t *d_chunk_flags, void *d_state, uint32_t tag, hipStream_t st)
+                 uint64_t *d_chunk_off, uint32_t *d_chunk_flags, hipStream_t st)
 {
     if (n_chunks == 0) return HHGT_OK;
     FrameParams P;
@@ -436,21 +301,8 @@ int launch_frame(const uint8_t *d_scratch, size_t slot_bytes, const uint32_t *d_
     P.hl = format == HHGT_BLOSC2 ? 32u : 16u;
     P.chunk_nbytes = chunk_nbytes;
     P.slot_bytes = slot_bytes;
-    // HHGT_FRAME_FUSED=1: the one-launch form (k_frame_fused) — same bytes (tests/test_gpu_frame_fused.py), built and measured
-    // in round 4: framing 2.97 against 1.83 ms per 3 M x 2504 step (a ticket per workgroup on one word, a look-back chain and
-    // 8 blocks per wave against one) — so the three launches stay the default
-    static const bool fused_env = getenv("HHGT_FRAME_FUSED") && atoi(getenv("HHGT_FRAME_FUSED")) != 0;
-    if (fused_env && d_state && P.nblocks <= FR_MAXB && n_chunks < (1ull << 30) &&
-        n_chunks * (chunk_nbytes + 32) < (1ull << FR_VAL_BITS)) {
-        // workgroups per chunk: about 8 blocks per wave
-        uint32_t split = (P.nblocks + 31u) / 32u;
-        split = split < 1u ? 1u : (split > 8u ? 8u : split);
-        hipLaunchKernelGGL(k_frame_fused, dim3((uint32_t)(n_chunks * split)), dim3(256), 0, st, P, d_scratch, d_csize, d_src,
-                           static_cast<FrameState *>(d_state), tag, split, reinterpret_cast<unsigned long long *>(d_chunk_off), d_dst, dst_cap,
-                           n_chunks, d_planes, pg);
-        HIP_TRY(hipGetLastError());
-        return HHGT_OK;
-    }
+    // (a one-launch form — a ticket per workgroup, a decoupled look-back over the chunk totals, 8 blocks per wave — was built
+    // and measured in round 4: framing 2.97 against 1.83 ms per 3 M x 2504 step; removed, git history has it)
     hipLaunchKernelGGL(k_frame_sizes, dim3((uint32_t)n_chunks), dim3(256), 0, st, P, d_csize, d_bstart,
                        reinterpret_cast<unsigned long long *>(d_chunk_csize), d_chunk_flags);
     hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(256), 0, st,
@@ -463,5 +315,3 @@ int launch_frame(const uint8_t *d_scratch, size_t slot_bytes, const uint32_t *d_
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }
-
-size_t frame_state_bytes(uint64_t n_chunks) { return sizeof(FrameState) + (size_t)n_chunks * 8u; }

@@ -875,13 +875,12 @@ int launch_index_newlines(const uint8_t *d_text, uint64_t n, uint32_t *d_slots, 
         // 4.4 for 16 and for "as many as make all waves of the launch resident at once" (11 on chr1) — longer walks per wave
         // cost more than a second, part-filled round of waves; fewer than 4 and the plain scan up to a range's first newline
         // (half a line per wave) starts to show
-        static const int hop_k_env = getenv("HHGT_INDEX_HOP_K") ? atoi(getenv("HHGT_INDEX_HOP_K")) : 0;   // development
         const bool walk = mode >= 2 && S > 0;
         // The walk costs one dependent 1 KiB load per line, so a wave is a latency chain and every wave pays a plain scan up
         // to the first newline of its range (half a line, in U KiB windows): as few waves as still fill the chip once —
         // 8 workgroups of 4 waves on each of 256 CUs — at least the hop's 6 regions, at most 64 (the per-lane counters).
         const uint32_t k_walk = (n_regions + 8191u) / 8192u;
-        uint32_t K = hop_k_env > 0 ? (uint32_t)hop_k_env : (walk ? (k_walk < 6u ? 6u : k_walk) : 6u);
+        uint32_t K = walk ? (k_walk < 6u ? 6u : k_walk) : 6u;
         K = K > 64u ? 64u : K;
 #define HOP_LAUNCH(U, W)                                                                                                      \
     hipLaunchKernelGGL((k_index_hop<U, W>), dim3(((n_regions + K - 1) / K + 3) / 4), dim3(256), 0, st, d_text, n, d_slots, d_counts, \

@@ -15,12 +15,9 @@
 //            most recent occurrence and the offset-1 run; the greedy left-to-right choice of non-overlapping
 //            matches is the only serial part and runs on the scalar unit; the chosen sequences are queued in LDS
 //            and laid out (DPP prefix sum) and written one per lane, 48-64 at a time.
-//            lz4_wave_compress (v1: one match per round trip) is kept as a second instantiation for A/B runs
-//            (HHGT_LZ4_ALGO=1).
 // Algorithmic bytes = blocksize read + compressed bytes written per block; measured: the kernel is bound by
 // instruction issue, not by HBM.
 #include "common.h"
-#include <stdio.h>
 #include <stdlib.h>
 
 #define LZ_MINMATCH 4u
@@ -66,88 +63,6 @@ __device__ __forceinline__ uint32_t emit_len(uint8_t *out, uint32_t q, uint32_t 
     uint32_t nb = rem / 255u + 1u;
     for (uint32_t j = lane; j < nb; j += 64u) out[q + j] = (j == nb - 1u) ? (uint8_t)(rem % 255u) : (uint8_t)255u;
     return q + nb;
-}
-
-// Greedy LZ4 of in[0, n) (LDS, 4-byte aligned, >= 8 readable bytes past n) by one wave.
-// Returns the compressed size (wave-uniform).  out has lz4_slot_bytes(n) capacity.
-__device__ __forceinline__ uint32_t lz4_wave_compress(const uint8_t *in, uint32_t n, uint16_t *tab, uint32_t hashlog,
-                                      uint8_t *__restrict__ out)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t i = lane; i < (1u << hashlog) / 2u; i += 64u) reinterpret_cast<uint32_t *>(tab)[i] = 0u;
-    uint32_t op = 0, anchor = 0;
-    if (n > LZ_MFLIMIT) {
-        const uint32_t mflimit = n - LZ_MFLIMIT, matchlimit = n - LZ_LASTLITERALS;
-        const uint32_t hshift = 32u - hashlog;
-        uint32_t p = 0;
-        while (p <= mflimit) {
-            const uint32_t i = p + lane;
-            const bool valid = i <= mflimit;
-            const uint32_t d = valid ? lds_load4(in, i) : 0u;
-            const uint32_t h = (d * 2654435761u) >> hshift;
-            uint32_t cand = valid ? (uint32_t)tab[h] : 0u;
-            if (valid) tab[h] = (uint16_t)i;
-            const uint32_t r = lds_load4(in, cand);
-            const bool ok = valid && cand < i && r == d;
-            unsigned long long m = __ballot(ok);
-            const uint32_t wend = p + 64u;
-            while (m) {
-                const uint32_t sl = (uint32_t)__ffsll((long long)m) - 1u;
-                uint32_t pos = p + sl;
-                uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)cand, (int)sl);
-                // forward extension, 64 bytes per step
-                uint32_t ml = LZ_MINMATCH;
-                for (;;) {
-                    const uint32_t k = ml + lane;
-                    const bool eq = (pos + k < matchlimit) && in[pos + k] == in[c + k];
-                    const unsigned long long ne = __ballot(!eq);
-                    if (ne == 0ull) {
-                        ml += 64u;
-                        continue;
-                    }
-                    ml += (uint32_t)__ffsll((long long)ne) - 1u;
-                    break;
-                }
-                // backward extension over pending literals (at most 64 bytes)
-                {
-                    const uint32_t kk = lane + 1u;
-                    const bool eq = (pos >= anchor + kk) && (c >= kk) && in[pos - kk] == in[c - kk];
-                    const unsigned long long ne = __ballot(!eq);
-                    const uint32_t nb = ne ? (uint32_t)__ffsll((long long)ne) - 1u : 64u;
-                    pos -= nb;
-                    c -= nb;
-                    ml += nb;
-                }
-                // ---- emit sequence: token | literal-length ext | literals | offset | match-length ext
-                const uint32_t ll = pos - anchor, mlc = ml - LZ_MINMATCH;
-                if (lane == 0) out[op] = (uint8_t)(((ll < 15u ? ll : 15u) << 4) | (mlc < 15u ? mlc : 15u));
-                uint32_t q = op + 1u;
-                if (ll >= 15u) q = emit_len(out, q, ll - 15u, lane);
-                for (uint32_t k = lane; k < ll; k += 64u) out[q + k] = in[anchor + k];
-                q += ll;
-                const uint32_t off = pos - c;
-                if (lane == 0) out[q] = (uint8_t)(off & 0xFFu);
-                if (lane == 1) out[q + 1u] = (uint8_t)(off >> 8);
-                q += 2u;
-                if (mlc >= 15u) q = emit_len(out, q, mlc - 15u, lane);
-                op = q;
-                anchor = pos + ml;
-                if (anchor >= wend) m = 0ull;
-                else m &= ~((1ull << (anchor - p)) - 1ull);
-            }
-            p = anchor > wend ? anchor : wend;
-        }
-    }
-    // last literals
-    {
-        const uint32_t ll = n - anchor;
-        if (lane == 0) out[op] = (uint8_t)((ll < 15u ? ll : 15u) << 4);
-        uint32_t q = op + 1u;
-        if (ll >= 15u) q = emit_len(out, q, ll - 15u, lane);
-        for (uint32_t k = lane; k < ll; k += 64u) out[q + k] = in[anchor + k];
-        op = q + ll;
-    }
-    return op;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -650,7 +565,8 @@ __device__ __forceinline__ uint32_t lz4_wave_compress_v6(const uint8_t *in, uint
 // dynamic LDS: [data: nwaves * sstride + 16][tables: nwaves << (hashlog + 1)]
 // MW = minimum waves per SIMD the register allocator must leave room for (0: no constraint, workgroups of up
 // to 16 waves for typesize 16).  The common genotype case (typesize 2 -> 2-wave workgroups) is latency bound,
-// so it is compiled for 8 resident waves per SIMD (<= 64 VGPRs).
+// so it is compiled for 7 resident waves per SIMD (8 at the fastest effort, <= 64 VGPRs).
+// ALGO = the effort of lz4_wave_compress_v6: 5 run candidate only, 6 hash + run candidates, 7 plus the long-run candidate.
 // PLANES: the blocks exist as bit planes (phase A generates the bytes); a template parameter so that the int8
 // instantiations keep their registers (the default one sits at the 72-register line of 7 waves per SIMD)
 template <int MW, int ALGO, bool PLANES>
@@ -663,9 +579,9 @@ __global__ __launch_bounds__(MW ? 128 : 1024, MW ? MW : 1) void k_lz4_blocks(con
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t nwaves = blockDim.x >> 6;
-    // scan mode: the bit-plane coders say whether they left anything (lz4bits.hip: the word holds this call's tag if so)
+    // scan mode: the bit-plane coder says whether it left anything (lz4bits.hip: the word holds this call's tag if so)
     if (mark_flag && __builtin_nontemporal_load(mark_flag) != tag) return;
-    // algo bit 8: scan mode — only the streams the bit-plane encoders (lz4bits.hip) left marked (csize == 0xFFFFFFFF) are
+    // algo bit 8: scan mode — only the streams the bit-plane coder (lz4bits.hip) left marked (csize == 0xFFFFFFFF) are
     // coded: the (small, fixed) grid scans the stream sizes, 64 blocks per load, and works on the blocks that still hold one
     const bool only_marked = (algo & 0x100u) != 0u;
     for (uint32_t b0 = only_marked ? blockIdx.x * 64u : blockIdx.x; b0 < (only_marked ? n_total : blockIdx.x + 1u);
@@ -766,8 +682,7 @@ __global__ __launch_bounds__(MW ? 128 : 1024, MW ? MW : 1) void k_lz4_blocks(con
         // sequence queue: 64 entries per wave, 8-aligned after the tables (offset arithmetic keeps the LDS address space)
         const uint32_t qoff = (nwaves * sstride + 16u + nwaves * ((2u << hashlog) + 4u) + 7u) & ~7u;
         uint2 *queue = reinterpret_cast<uint2 *>(smem + qoff) + wave * 64u;
-        uint32_t cs = ALGO == 1   ? lz4_wave_compress(in, neblock, tb, hashlog, out)
-                      : ALGO == 5 ? lz4_wave_compress_v6<true, false>(in, neblock, tb, hashlog, out, queue)
+        uint32_t cs = ALGO == 5   ? lz4_wave_compress_v6<true, false>(in, neblock, tb, hashlog, out, queue)
                       : ALGO == 7 ? lz4_wave_compress_v6<false, true>(in, neblock, tb, hashlog, out, queue)
                                   : lz4_wave_compress_v6<false, false>(in, neblock, tb, hashlog, out, queue);
         (void)algo;
@@ -788,14 +703,14 @@ int launch_lz4_blocks(const uint8_t *d_src, const uint8_t *d_planes, PlanesGeom 
                       int blocksize, uint8_t *d_scratch, size_t slot_bytes, uint32_t *d_csize, int clevel, uint32_t *d_flags, uint32_t tag,
                       hipStream_t st)
 {
-    const uint32_t *mark_flag = nullptr;   // scan mode: where the last bit-plane coder of this call says whether it left marks
     if (d_planes && (typesize != 2 || blocksize != 8192 || chunk_nbytes % 8192 || (reinterpret_cast<uintptr_t>(d_planes) & 15u))) {
         hhgt_set_error("lz4: bit planes stand for typesize 2, 8 KiB blocks, chunks of whole blocks, 16-byte aligned");
         return HHGT_ERR_ARG;
     }
     const int fast = clevel <= 2 ? 1 : (clevel >= 7 ? 2 : 0);
     // the bit-plane encoder (lz4bits.hip) takes the case the path is built for — typesize 2, 8 KiB blocks, default
-    // effort — and marks the streams it cannot code (a byte > 1, very dense planes); this kernel then only runs those.
+    // effort — and marks the streams it cannot code (calls beyond 0 / 1 / missing, with int8 input any byte > 1, very dense
+    // planes); this kernel then only runs those.
     // HHGT_LZ4_BITPLANES=0 keeps everything on the byte-wise encoder.
     static const bool bp_env = !(getenv("HHGT_LZ4_BITPLANES") && atoi(getenv("HHGT_LZ4_BITPLANES")) == 0);
     const bool bitplanes = bp_env && typesize == 2 && blocksize == 8192 && chunk_nbytes % 8192 == 0 &&
@@ -808,11 +723,9 @@ int launch_lz4_blocks(const uint8_t *d_src, const uint8_t *d_planes, PlanesGeom 
         static const int lazy_env = getenv("HHGT_LZ4_LAZY") ? atoi(getenv("HHGT_LZ4_LAZY")) : -1;
         int depth = depth_env >= 0 ? depth_env : (clevel <= 2 ? 0 : clevel <= 4 ? 1 : clevel <= 6 ? 2 : clevel == 7 ? 4 : clevel == 8 ? 8 : 12);
         if ((lazy_env < 0 ? clevel >= 9 && depth == 12 : lazy_env != 0) && (depth == 2 || depth == 12)) depth |= 0x100;
-        bool exc_ran = false;
         const int rc = launch_lz4_bitplanes(d_planes ? d_planes : d_src, d_planes != nullptr, pg, n_chunks * (chunk_nbytes / 8192), d_scratch,
-                                            slot_bytes, d_csize, depth, d_flags, tag, &exc_ran, st);
+                                            slot_bytes, d_csize, depth, d_flags, tag, st);
         if (rc != HHGT_OK) return rc;
-        if (d_flags) mark_flag = d_flags + (exc_ran ? 1 : 0);
     }
     const uint32_t split = (typesize >= 2 && typesize <= 16 && blocksize / typesize >= 128) ? 1u : 0u;
     const uint32_t nwaves = split ? (uint32_t)typesize : 1u;
@@ -830,40 +743,33 @@ int launch_lz4_blocks(const uint8_t *d_src, const uint8_t *d_planes, PlanesGeom 
     // hash table size: the kernel is latency/issue bound, so resident waves matter more than table
     // reach.  Take the largest table (<= 4096 entries) that does not cost a resident workgroup
     // relative to the smallest one (512 entries); 160 KiB LDS and 32 waves per CU.
-    static const int hl_env = getenv("HHGT_LZ4_HASHLOG") ? atoi(getenv("HHGT_LZ4_HASHLOG")) : 0;
     auto occ = [&](uint32_t hl) {
         size_t l = data_bytes + (size_t)nwaves * ((2u << hl) + 4u) + 8u + (size_t)nwaves * 512u;
         size_t by_lds = (160 * 1024) / l, by_waves = 32 / nwaves;
         return by_lds < by_waves ? by_lds : by_waves;
     };
     uint32_t hashlog = 12;
-    // (HHGT_LZ4_MINWAVES=8 HHGT_LZ4_HASHLOG=7 gives 16 workgroups per CU: LZ4 alone 35.3 -> 34.5 ms, but the whole
-    //  two-stream step does not move (53.3 ms) because the index kernel then finds no room beside it; on genotype
+    // (8 waves per SIMD with a 128-entry table gave 16 workgroups per CU: LZ4 alone 35.3 -> 34.5 ms, but the whole
+    //  two-stream step did not move (53.3 ms) because the index kernel then found no room beside it; on genotype
     //  planes the ratio is the same 4.326 with 64 .. 512 table entries)
     while (hashlog > 9 && occ(hashlog) < occ(9)) --hashlog;
-    if (hl_env >= 6 && hl_env <= 13) hashlog = (uint32_t)hl_env;
-    // HHGT_LZ4_LDSPAD: extra dynamic LDS per workgroup — an experiment knob that caps how many LZ4 workgroups
-    // share a CU, leaving LDS for the HBM-bound kernels of the other stream
-    static const size_t lds_pad = getenv("HHGT_LZ4_LDSPAD") ? (size_t)atoi(getenv("HHGT_LZ4_LDSPAD")) : 0;
-    const size_t lds = data_bytes + (size_t)nwaves * ((2u << hashlog) + 4u) + 8u + (size_t)nwaves * 512u + lds_pad;
+    const size_t lds = data_bytes + (size_t)nwaves * ((2u << hashlog) + 4u) + 8u + (size_t)nwaves * 512u;
     if (lds > 160 * 1024 - 64) {
         hhgt_set_error("lz4: block of %d bytes x typesize %d does not fit LDS", blocksize, typesize);
         return HHGT_ERR_ARG;
     }
     static size_t attr_lds = 64 * 1024;  // dynamic LDS above 64 KiB needs an explicit opt-in
     if (lds > attr_lds) {
-        const void *fns[] = {reinterpret_cast<const void *>(k_lz4_blocks<0, 1, false>), reinterpret_cast<const void *>(k_lz4_blocks<0, 5, false>),
-                             reinterpret_cast<const void *>(k_lz4_blocks<8, 5, false>), reinterpret_cast<const void *>(k_lz4_blocks<0, 6, false>),
-                             reinterpret_cast<const void *>(k_lz4_blocks<7, 6, false>), reinterpret_cast<const void *>(k_lz4_blocks<8, 6, false>),
+        const void *fns[] = {reinterpret_cast<const void *>(k_lz4_blocks<0, 5, false>), reinterpret_cast<const void *>(k_lz4_blocks<8, 5, false>),
+                             reinterpret_cast<const void *>(k_lz4_blocks<0, 6, false>), reinterpret_cast<const void *>(k_lz4_blocks<7, 6, false>),
                              reinterpret_cast<const void *>(k_lz4_blocks<0, 7, false>), reinterpret_cast<const void *>(k_lz4_blocks<7, 7, false>),
                              reinterpret_cast<const void *>(k_lz4_blocks<8, 5, true>), reinterpret_cast<const void *>(k_lz4_blocks<7, 6, true>),
                              reinterpret_cast<const void *>(k_lz4_blocks<7, 7, true>)};
         for (const void *f : fns) HIP_TRY(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_lds = lds;
     }
-    // HHGT_LZ4_ALGO: 6 = window-parallel encoder with batched emission (default), 1 = the simple first version (A/B)
-    static const uint32_t algo_env = getenv("HHGT_LZ4_ALGO") ? (uint32_t)atoi(getenv("HHGT_LZ4_ALGO")) : 6u;
-    const uint32_t algo = algo_env | (bitplanes ? 0x100u : 0u);
+    const uint32_t algo = 6u | (bitplanes ? 0x100u : 0u);
+    const uint32_t *mark_flag = bitplanes ? d_flags : nullptr;   // scan mode: where the bit-plane coder says whether it left marks
     uint64_t grid = n_chunks * nblocks;
     if (grid == 0) return HHGT_OK;
     // scan mode: a fixed grid (enough workgroups to fill the chip) scans the stream sizes, 64 blocks per workgroup and step
@@ -871,16 +777,6 @@ int launch_lz4_blocks(const uint8_t *d_src, const uint8_t *d_planes, PlanesGeom 
     if (grid > 0x7fffffffull) {
         hhgt_set_error("lz4: too many blocks");
         return HHGT_ERR_ARG;
-    }
-    static const int mw_env = getenv("HHGT_LZ4_MINWAVES") ? atoi(getenv("HHGT_LZ4_MINWAVES")) : 7;
-    const int mw = nwaves <= 2 ? mw_env : 0;
-    static const bool dbg = getenv("HHGT_LZ4_DEBUG") != nullptr;
-    if (dbg) {  // development: what the runtime thinks fits on a CU
-        int n7 = -1, n8 = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n7, k_lz4_blocks<7, 6, false>, (int)(64u * nwaves), lds);
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n8, k_lz4_blocks<8, 6, false>, (int)(64u * nwaves), lds);
-        fprintf(stderr, "[hhgt lz4] nwaves=%u hashlog=%u lds=%zu B/workgroup, workgroups per CU: <7,6> %d  <8,6> %d\n", nwaves, hashlog,
-                lds, n7, n8);
     }
 #define LZ_LAUNCH2(MWV, ALG, PL)                                                                                      \
     hipLaunchKernelGGL((k_lz4_blocks<MWV, ALG, PL>), dim3((uint32_t)grid), dim3(64u * nwaves), lds, st, d_src, nblocks, \
@@ -893,13 +789,11 @@ int launch_lz4_blocks(const uint8_t *d_src, const uint8_t *d_planes, PlanesGeom 
         if (fast == 1) LZ_LAUNCH2(8, 5, true);
         else if (fast == 2) LZ_LAUNCH2(7, 7, true);
         else LZ_LAUNCH2(7, 6, true);
-    } else if ((algo & 0xFFu) == 1u) LZ_LAUNCH(0, 1);
-    else if (fast == 1 && nwaves <= 2) LZ_LAUNCH(8, 5);
+    } else if (fast == 1 && nwaves <= 2) LZ_LAUNCH(8, 5);
     else if (fast == 1) LZ_LAUNCH(0, 5);
     else if (fast == 2 && nwaves <= 2) LZ_LAUNCH(7, 7);
     else if (fast == 2) LZ_LAUNCH(0, 7);
-    else if (mw == 8) LZ_LAUNCH(8, 6);
-    else if (mw == 7) LZ_LAUNCH(7, 6);
+    else if (nwaves <= 2) LZ_LAUNCH(7, 6);
     else LZ_LAUNCH(0, 6);
 #undef LZ_LAUNCH2
 #undef LZ_LAUNCH

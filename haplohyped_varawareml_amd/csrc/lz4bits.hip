@@ -33,17 +33,12 @@
 //
 // tools/sim/gapenc_ref.c states the same algorithm on the CPU, decision for decision; the kernel's streams are
 // compared with it byte for byte (tests/test_gpu_lz4_bitplanes.py) and decoded by liblz4 / the oracle like every
-// other stream.  Planes with a byte > 1 (missing calls, -9) or more than 636 ones are left to the byte-wise
-// encoder (csize = MARK; lz4.hip's kernel then runs in "marked streams only" mode).
+// other stream.  Planes of bit-plane input that hold missing calls are coded by the exception-aware path of
+// k_lz4_bitplanes_uni.  Planes neither path can code (a call beyond 0 / 1 / missing, int8 input with a byte > 1, too
+// many ones) are left to the byte-wise encoder (csize = MARK; lz4.hip's kernel then runs in "marked streams only" mode).
 #include "common.h"
 
 #define BP_N 4096
-#ifndef BP_SELECT_SCALAR
-#define BP_SELECT_SCALAR 0   // which ones of a window the parse visits: 0 pointer doubling through LDS; 1 walked on the scalar unit
-                             // (built again in round 4, leaner than round 2's: one v_readlane + ~6 scalar instructions per coded
-                             // one, no LDS — byte-identical streams, LZ4 stage 14.0 against 12.1 ms: a taken branch and a
-                             // vector -> scalar hand-over per hop are a longer chain than twelve LDS round trips per window)
-#endif
 #ifndef BP_MAXONES
 #define BP_MAXONES 636
 #endif
@@ -51,10 +46,10 @@
 #define BP_STAGE 576    // staging area; with the queue below the workgroup stays under 11 KiB of LDS = 14 workgroups per CU
 #endif
 #ifndef BP_WAVES
-#define BP_WAVES 7       // waves per SIMD the plain instantiations are compiled for (LDS must allow 2 x BP_WAVES workgroups per CU)
+#define BP_WAVES 7       // waves per SIMD the kernels are compiled for (LDS must allow 2 x BP_WAVES workgroups per CU)
 #endif
 #define BP_QCAP 100     // queued coded ones a wave can hold (a window adds at most 64 to fewer than 64)
-// the exception-aware instantiation carries a second bit map and the ones' classes (624 bytes per wave): its list and its staging
+// the exception-aware path carries a second bit map and the ones' classes (624 bytes per wave): its list and its staging
 // area are smaller by as much, so that it too stays under 11 KiB per workgroup = 14 workgroups per CU, 7 waves per SIMD (round 4;
 // it ran at 13 / 6 before, and this kernel's time is 1 / occupancy)
 #ifndef BP_MAXONES_EXC
@@ -62,9 +57,6 @@
 #endif
 #ifndef BP_STAGE_EXC
 #define BP_STAGE_EXC 448
-#endif
-#ifndef BP_WAVES_EXC
-#define BP_WAVES_EXC 7
 #endif
 template <bool EXC> struct BpCfg {
     static constexpr uint32_t MAXONES = EXC ? BP_MAXONES_EXC : BP_MAXONES;
@@ -332,10 +324,9 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     return BpOut{prev_end, gop, sop};
 }
 
-// One plane, from its bit map(s) in registers to its stream (or its mark): everything behind the loads.  FLAG: which word of
-// `flags` says "this call left a mark" for the launch that scans next; WRITE_MARK: the mark is written here (the scanning
-// exception-aware launch finds it in place already).
-template <int DEPTH, bool EXC, bool LAZY, int FLAG, bool WRITE_MARK, typename LDS>
+// One plane, from its bit map(s) in registers to its stream (or its mark): everything behind the loads.  A plane left to the
+// byte-wise kernel gets csize = MARK, and flags[0] = tag says "this call left a mark" to that kernel's scan.
+template <int DEPTH, bool EXC, bool LAZY, typename LDS>
 __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi, uint32_t xlo, uint32_t xhi, bool nonbinary, uint32_t bid,
                                               uint32_t wave, uint32_t lane, uint8_t *__restrict__ scratch, uint64_t slot_bytes,
                                               uint32_t *__restrict__ csize, uint32_t *__restrict__ flags, uint32_t tag)
@@ -360,8 +351,8 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
     const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     if (nonbinary || m > BpCfg<EXC>::MAXONES) {
         // (the flag: read first — the line sits in the L2 and after the first few marking waves of an XCD it holds the tag)
-        if (lane == 0 && flags && flags[FLAG] != tag) flags[FLAG] = tag;
-        if (lane == 0 && WRITE_MARK) csize[sidx] = 0xFFFFFFFFu;   // left to the next coder (the scanning exception-aware launch finds the mark there already)
+        if (lane == 0 && flags && flags[0] != tag) flags[0] = tag;
+        if (lane == 0) csize[sidx] = 0xFFFFFFFFu;   // left to the byte-wise kernel
         return;
     }
     BP_MARK("scan_done");
@@ -593,7 +584,8 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
         BP_MARK("nxt_done");
         // ---- which ones of the window are coded: follow nxt from `cur` by pointer doubling.  (Measured against the plain
         //      walk on the scalar unit — one v_readlane + 5 scalar instructions per coded one, half the vector instructions:
-        //      14.8 against 13.0 ms per step.  A wave's dependent chain is what counts, not its instruction total.)
+        //      14.8 against 13.0 ms per step; rebuilt leaner in round 4, one v_readlane + ~6 scalar instructions and no LDS:
+        //      LZ4 stage 14.0 against 12.1 ms.  A wave's dependent chain is what counts, not its instruction total.)
         bool sel = false;
         if (BP_SKIP >= 3) {
             sink += nxt + E;
@@ -602,20 +594,6 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
         if (cur < jw + 64) {   // (wave-uniform) otherwise the whole window lies inside an earlier match
             const uint32_t e0 = (uint32_t)(cur - jw);
             uint32_t jump = valid ? (nxt - (uint32_t)jw < 64u ? nxt - (uint32_t)jw : 64u) : 64u;   // nxt > j: always forward
-#if BP_SELECT_SCALAR
-            // the chain walked on the scalar side — one v_readlane and a handful of scalar instructions per coded one — instead
-            // of six rounds of flag write -> flag read -> ds_bpermute (measured slower, see BP_SELECT_SCALAR)
-            unsigned long long SEL = 0ull;
-            uint32_t c = e0, last = e0;
-            do {
-                SEL |= 1ull << c;
-                last = c;
-                c = (uint32_t)__builtin_amdgcn_readlane((int)jump, (int)c);
-            } while (c < 64u);
-            sel = __builtin_amdgcn_inverse_ballot_w64(SEL) && valid;
-            // the coded one whose successor lies outside the window hands over to the next window
-            if ((int)(jw + (int)last) < (int)m) cur = (int)__builtin_amdgcn_readlane((int)nxt, (int)last);
-#else
             const uint32_t p0 = jump;
             flag[lane] = lane == e0 ? 1u : 0u;
             flag[lane == 0u ? 64u : 69u] = 0u;
@@ -633,7 +611,6 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
             const unsigned long long ex = __builtin_amdgcn_ballot_w64(sel && p0 == 64u);
             // the coded one whose successor lies outside the window hands over to the next window
             if (ex != 0ull) cur = (int)__builtin_amdgcn_readlane((int)nxt, (int)(__ffsll((long long)ex) - 1));
-#endif
         }
         BP_MARK("sel_done");
         if (BP_SKIP >= 2) {
@@ -743,76 +720,23 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
     if (lane == 0) csize[sidx] = op;
 }
 
-// grid = number of 8 KiB blocks; 128 threads: wave w codes byte plane w of the block
+// int8 input (the matrix itself): grid = number of 8 KiB blocks; 128 threads: wave w codes byte plane w of the block
 // DEPTH = candidates tried per one along the hash chain (1: the table's entry only; 0: no hash matches at all,
 // offset-1 runs only — the fastest level)
-// PLANES: src is the bit-plane form of the matrix (include/hhgt.h, tile-major: common.h; written by k_encode_planes): the
-// wave's bit map is 16 pieces of 32 bytes it gathers as they are (one load instruction: lane l takes 8 bytes of tile
-// l / 4), and a set EXC bit is what "a byte > 1" was.  The pieces of four neighbouring sample rows share a 128-byte
-// line, so the blocks are dealt to the workgroups in an XCD-aware order: of 64 consecutive workgroups the eight that land
-// on one XCD (round robin) take eight consecutive blocks — one L2 fetches each line once.
-// EXC (with PLANES): the exception-aware instantiation — planes whose bytes are 0, 1 or 0xF7 (missing calls; config 4).
-// On a fixed grid every wave scans the stream sizes of its plane, 64 blocks per load, and codes the streams the plain
-// instantiation left marked (csize = 0xFFFFFFFF; a list of marked blocks built by atomic adds on one counter cost more than
-// the coding itself when every plane is marked: 6 ms for config 4's 537 k blocks); the bit map is the map of NONZERO bytes, a second map says which of them are 0xF7, every one
-// carries that bit as its class, and two ones only agree if their classes do (tools/sim/gapenc_ref.c states the rules).
-// Streams it cannot code either (a call beyond 0 / 1 / missing, too many nonzero bytes) stay marked for the byte-wise kernel.
-template <int DEPTH, bool PLANES, bool EXC, bool LAZY = false>
-__global__ __launch_bounds__(128, EXC ? BP_WAVES_EXC : BP_WAVES) void k_lz4_bitplanes(const uint8_t *__restrict__ src, PlanesGeom pg, uint32_t n_blocks,
-                                                          uint8_t *__restrict__ scratch, uint64_t slot_bytes, uint32_t *__restrict__ csize,
-                                                          uint32_t *__restrict__ flags, uint32_t tag)
+template <int DEPTH, bool LAZY = false>
+__global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes(const uint8_t *__restrict__ src, PlanesGeom pg, uint32_t n_blocks,
+                                                                  uint8_t *__restrict__ scratch, uint64_t slot_bytes, uint32_t *__restrict__ csize,
+                                                                  uint32_t *__restrict__ flags, uint32_t tag)
 {
-    static_assert(!EXC || PLANES, "the exception-aware coder reads bit planes");
-    // flags (may be null): flags[0] == tag <=> the plain instantiation of THIS call left a stream marked, flags[1] == tag <=> the
-    // exception-aware one did.  The scanning launches behind (this kernel with EXC, lz4.hip's kernel in scan mode) look at the
-    // word first and are gone if nobody marked anything — on the headline cohort that is every call, and the two scans were
-    // 48 us of each shard's chain (r04b_bench_kernel_stats.csv).  A tag per call instead of a flag somebody has to clear.
-    if (EXC && flags && __builtin_nontemporal_load(flags) != tag) return;
     constexpr bool CHAIN = DEPTH > 1;
-    __shared__ BpLds<CHAIN, EXC> lds[2];
+    __shared__ BpLds<CHAIN, false> lds[2];
     __shared__ uint32_t nonbin[2][2];
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
-    // (EXC: the two waves of a workgroup are independent; each walks the marked streams of its plane)
-    for (uint32_t b0 = EXC ? blockIdx.x * 64u : 0u; b0 < (EXC ? n_blocks : 1u); b0 += EXC ? gridDim.x * 64u : 1u) {
-    unsigned long long todo = 1ull;
-    if (EXC) {   // which of the 64 blocks from b0 on still have this wave's stream marked
-        const uint32_t bb = b0 + lane;
-        todo = __builtin_amdgcn_ballot_w64(bb < n_blocks && csize[(uint64_t)bb * 2u + wave] == 0xFFFFFFFFu);
-    }
-    while (todo != 0ull) {   // (wave-uniform)
-    {
-    const uint32_t bid = EXC ? b0 + (uint32_t)__builtin_ctzll(todo)
-                             : PLANES ? ((blockIdx.x & ~63u) | ((blockIdx.x & 7u) << 3) | ((blockIdx.x >> 3) & 7u)) : blockIdx.x;
-    todo &= todo - 1ull;
-    if (PLANES && !EXC && bid >= n_blocks) return;   // (the grid is rounded up to whole groups of 64)
-    uint32_t xlo = 0, xhi = 0;   // EXC: the lane's 64 positions of the missing-call map
-    uint32_t wlo, whi;
-    bool nonbinary;
-    if (PLANES) {
-        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-        uint64_t col;
-        uint32_t row, bi;
-        planes_block(pg, bid, &col, &row, &bi);
-        const u32x2 *pl = reinterpret_cast<const u32x2 *>(src + planes_piece(pg, col, bi * 16u + (lane >> 2), wave, row)) + (lane & 3u);
-        const u32x2 one = *pl, exc = *(pl + (uint64_t)pg.S_pad * 8ull);   // EXC: two kind-planes (S_pad * 32 bytes each) further
-        wlo = one.x;
-        whi = one.y;
-        lds[wave].bm[2u * lane] = wlo;
-        lds[wave].bm[2u * lane + 1u] = whi;
-        if (lane < 4u) lds[wave].bm[128u + lane] = 0u;
-        if (EXC) {
-            // (ONE, EXC) = (0, 1): a call beyond 0 / 1 / missing, its byte lives in the int8 matrix — not this coder's
-            nonbinary = __builtin_amdgcn_ballot_w64(((exc.x & ~one.x) | (exc.y & ~one.y)) != 0u) != 0ull;
-            xlo = exc.x;
-            xhi = exc.y;
-            lds[wave].xm[2u * lane] = xlo;
-            lds[wave].xm[2u * lane + 1u] = xhi;
-            if (lane < 4u) lds[wave].xm[128u + lane] = 0u;
-            if (lane < 24u) lds[wave].cls[lane] = 0u;
-        } else {
-            nonbinary = __builtin_amdgcn_ballot_w64((exc.x | exc.y) != 0u) != 0ull;
-        }
-    } else {
+    const uint32_t bid = blockIdx.x;
+    // (a one-trip loop: it keeps the compiler's schedule of this kernel as it was when the body sat in the loop of the removed
+    // exception-aware form; without it phase A is scheduled differently — 66 instead of 64 VGPRs at most depths, 7 instead
+    // of 8 waves per SIMD at depth 0)
+    for (int once = 0; once < 1; ++once) {
     const uint8_t *blk = src + (uint64_t)bid * 8192u;
 
     // ---- phase A: wave r packs the bits of block bytes [4096 r, 4096 r + 4096) for BOTH planes (byte-shuffle fused:
@@ -855,27 +779,30 @@ __global__ __launch_bounds__(128, EXC ? BP_WAVES_EXC : BP_WAVES) void k_lz4_bitp
         if (lane < 4u) lds[wave].bm[128u + lane] = 0u;
     }
     __syncthreads();
-    wlo = lds[wave].bm[2u * lane];
-    whi = lds[wave].bm[2u * lane + 1u];
-    nonbinary = (nonbin[0][wave] | nonbin[1][wave]) != 0u;
-    }
+    const uint32_t wlo = lds[wave].bm[2u * lane], whi = lds[wave].bm[2u * lane + 1u];
+    const bool nonbinary = (nonbin[0][wave] | nonbin[1][wave]) != 0u;
     BP_MARK("A_done");
     if (BP_SKIP >= 5) {
         if (lane == 0) csize[(uint64_t)bid * 2u + wave] = lds[wave].bm[5] & 1u;
-        continue;
+        return;
     }
 
-    bp_code_plane<DEPTH, EXC, LAZY, EXC ? 1 : 0, !EXC>(lds[wave], wlo, whi, xlo, xhi, nonbinary, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
-    }
-    }
+    bp_code_plane<DEPTH, false, LAZY>(lds[wave], wlo, whi, 0u, 0u, nonbinary, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
     }
 }
 
-// The plain and the exception-aware coder in ONE launch over bit planes (round 4): a wave looks at its plane's missing-call map
-// and takes the one or the other path (wave-uniform; both are the instantiations above, inlined).  What it replaces is the plain
-// launch marking every plane that holds a missing call for a second, scanning launch — on config 4, where every plane does,
-// 0.4 ms of reading all planes for nothing.  Planes neither can code (a call beyond 0 / 1 / missing, too many nonzero bytes) are
-// marked for the byte-wise kernel as before (flags[0]).
+// Bit-plane input (include/hhgt.h, tile-major: common.h; written by k_encode_planes): the wave's bit map is 16 pieces of
+// 32 bytes it gathers as they are (one load instruction: lane l takes 8 bytes of tile l / 4).  The pieces of four
+// neighbouring sample rows share a 128-byte line, so the blocks are dealt to the workgroups in an XCD-aware order: of 64
+// consecutive workgroups the eight that land on one XCD (round robin) take eight consecutive blocks — one L2 fetches each
+// line once (the grid is rounded up to whole groups of 64).
+// The plain and the exception-aware coder in ONE launch (round 4): a wave looks at its plane's missing-call map and takes the
+// one or the other path (wave-uniform; both are bp_code_plane, inlined).  The exception-aware path codes planes whose bytes
+// are 0, 1 or 0xF7 (missing calls; config 4): the bit map is the map of NONZERO bytes, a second map says which of them are
+// 0xF7, every one carries that bit as its class, and two ones only agree if their classes do (tools/sim/gapenc_ref.c states
+// the rules).  What this replaced was a plain launch marking every plane that holds a missing call for a second, scanning
+// launch — on config 4, where every plane does, 0.4 ms of reading all planes for nothing.  Planes neither path can code (a
+// call beyond 0 / 1 / missing, too many nonzero bytes) are marked for the byte-wise kernel (flags[0]).
 template <int DEPTH, bool LAZY>
 __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8_t *__restrict__ src, PlanesGeom pg, uint32_t n_blocks,
                                                                       uint8_t *__restrict__ scratch, uint64_t slot_bytes,
@@ -888,7 +815,7 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8
     };
     __shared__ BpBoth lds[2];
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
-    const uint32_t bid = (blockIdx.x & ~63u) | ((blockIdx.x & 7u) << 3) | ((blockIdx.x >> 3) & 7u);   // (XCD-aware order, as above)
+    const uint32_t bid = (blockIdx.x & ~63u) | ((blockIdx.x & 7u) << 3) | ((blockIdx.x >> 3) & 7u);   // (XCD-aware order)
     if (bid >= n_blocks) return;
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     uint64_t col;
@@ -901,7 +828,7 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8
         S.bm[2u * lane] = one.x;
         S.bm[2u * lane + 1u] = one.y;
         if (lane < 4u) S.bm[128u + lane] = 0u;
-        bp_code_plane<DEPTH, false, LAZY, 0, true>(S, one.x, one.y, 0u, 0u, false, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
+        bp_code_plane<DEPTH, false, LAZY>(S, one.x, one.y, 0u, 0u, false, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
     } else {
         BpLds<CHAIN, true> &S = lds[wave].x;
         // (ONE, EXC) = (0, 1): a call beyond 0 / 1 / missing, its byte lives in the int8 matrix — not this coder's
@@ -913,15 +840,14 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8
         S.xm[2u * lane + 1u] = exc.y;
         if (lane < 4u) S.xm[128u + lane] = 0u;
         if (lane < 24u) S.cls[lane] = 0u;
-        bp_code_plane<DEPTH, true, LAZY, 0, true>(S, one.x, one.y, exc.x, exc.y, nonbinary, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
+        bp_code_plane<DEPTH, true, LAZY>(S, one.x, one.y, exc.x, exc.y, nonbinary, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
     }
 }
 
 // depth: candidates per one; + 0x100: with the lazy rule (instantiated for 12 candidates — clevel 9 — and, for measurements, 2)
 int launch_lz4_bitplanes(const uint8_t *d_src, bool planes, PlanesGeom pg, uint64_t n_blocks, uint8_t *d_scratch, size_t slot_bytes, uint32_t *d_csize,
-                         int depth, uint32_t *d_flags, uint32_t tag, bool *exc_ran, hipStream_t st)
+                         int depth, uint32_t *d_flags, uint32_t tag, hipStream_t st)
 {
-    if (exc_ran) *exc_ran = false;
     const bool lazy = (depth & 0x100) != 0;
     depth &= 0xFF;
     if (n_blocks == 0) return HHGT_OK;
@@ -929,33 +855,14 @@ int launch_lz4_bitplanes(const uint8_t *d_src, bool planes, PlanesGeom pg, uint6
         hhgt_set_error("lz4: too many blocks");
         return HHGT_ERR_ARG;
     }
-    // development: extra (unused) dynamic LDS per workgroup caps how many workgroups a CU holds, which leaves LDS and
-    // wave slots to a kernel running beside this one on another stream
-    static const int lds_pad = getenv("HHGT_LZ4_LDS_PAD") ? atoi(getenv("HHGT_LZ4_LDS_PAD")) : 0;
-    // the exception-aware instantiation scans for the streams the plain one marked, on a grid that fills the chip
-    // (HHGT_LZ4_EXC=0: every marked stream goes to the byte-wise kernel, as before round 3)
-    static const bool exc_env = !(getenv("HHGT_LZ4_EXC") && atoi(getenv("HHGT_LZ4_EXC")) == 0);
-    // planes: one launch in which every wave takes the plain or the exception-aware path by its plane's missing-call map
-    // (HHGT_LZ4_UNI=0: the plain launch marks, the exception-aware one scans for the marks — rounds 3 and 4a-c)
-    static const bool uni_env = exc_env && !(getenv("HHGT_LZ4_UNI") && atoi(getenv("HHGT_LZ4_UNI")) == 0);
-    const uint32_t exc_grid = (uint32_t)((n_blocks + 63) / 64 < 256u * 14u ? (n_blocks + 63) / 64 : 256u * 14u);
-#define BP_LAUNCH2(D, PL, LZ)                                                                                               \
-    hipLaunchKernelGGL((k_lz4_bitplanes<D, PL, false, LZ>), dim3(PL ? (uint32_t)((n_blocks + 63) / 64 * 64) : (uint32_t)n_blocks), dim3(128), lds_pad, st, \
-                       d_src, pg, (uint32_t)n_blocks, d_scratch, (uint64_t)slot_bytes, d_csize, d_flags, tag)
 #define BP_LAUNCH(D, LZ)                                                                                                    \
     do {                                                                                                                    \
-        if (planes && uni_env) {                                                                                            \
-            hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((uint32_t)((n_blocks + 63) / 64 * 64)), dim3(128), lds_pad, st, d_src, pg, \
+        if (planes)                                                                                                         \
+            hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((uint32_t)((n_blocks + 63) / 64 * 64)), dim3(128), 0, st, d_src, pg, \
                                (uint32_t)n_blocks, d_scratch, (uint64_t)slot_bytes, d_csize, d_flags, tag);                 \
-        } else if (planes) {                                                                                                \
-            BP_LAUNCH2(D, true, LZ);                                                                                        \
-            if (exc_env) {                                                                                                  \
-                hipLaunchKernelGGL((k_lz4_bitplanes<D, true, true, LZ>), dim3(exc_grid), dim3(128), 0, st, d_src, pg, (uint32_t)n_blocks, d_scratch, \
-                                   (uint64_t)slot_bytes, d_csize, d_flags, tag);                                            \
-                if (exc_ran) *exc_ran = true;                                                                               \
-            }                                                                                                               \
-        } else                                                                                                              \
-            BP_LAUNCH2(D, false, LZ);                                                                                       \
+        else                                                                                                                \
+            hipLaunchKernelGGL((k_lz4_bitplanes<D, LZ>), dim3((uint32_t)n_blocks), dim3(128), 0, st, d_src, pg, (uint32_t)n_blocks, \
+                               d_scratch, (uint64_t)slot_bytes, d_csize, d_flags, tag);                                     \
     } while (0)
     if (lazy && depth == 2) BP_LAUNCH(2, true);
     else if (lazy) BP_LAUNCH(12, true);
@@ -967,7 +874,6 @@ int launch_lz4_bitplanes(const uint8_t *d_src, bool planes, PlanesGeom pg, uint6
     else if (depth <= 12) BP_LAUNCH(12, false);
     else BP_LAUNCH(16, false);
 #undef BP_LAUNCH
-#undef BP_LAUNCH2
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

@@ -34,12 +34,20 @@ def roundtrip(ctx, data, chunk_nbytes, typesize, blocksize, fmt):
     return chunks
 
 
-@pytest.mark.parametrize("typesize,blocksize,nbytes", BLOSC_CASES)
+# framing shapes beyond the oracle's table: one 8 KiB block per chunk, and 700 chunks (the chunk-offset scan runs several
+# passes) with incompressible chunks between compressible ones (a memcpyed chunk changes the offsets of all behind it)
+MANY_CHUNKS = {(2, 8192, 16384): (700, [3, 4, 17, 399, 699])}
+
+
+@pytest.mark.parametrize("typesize,blocksize,nbytes", BLOSC_CASES + [(2, 8192, 8192), (2, 8192, 16384)])
 @pytest.mark.parametrize("fmt", [dev.BLOSC1, dev.BLOSC2])
 def test_chunk_shapes(ctx, typesize, blocksize, nbytes, fmt):
-    n_chunks = 3
+    n_chunks, noise = MANY_CHUNKS.get((typesize, blocksize, nbytes), (3, []))
     data = genotype_like(1, n_chunks * nbytes // 2 + 1, nbytes).reshape(-1).view(np.uint8)[:n_chunks * nbytes].copy()
-    roundtrip(ctx, data, nbytes, typesize, blocksize, fmt)
+    data.reshape(n_chunks, nbytes)[noise] = np.random.default_rng(nbytes).integers(0, 256, (len(noise), nbytes), dtype=np.uint8)
+    chunks = roundtrip(ctx, data, nbytes, typesize, blocksize, fmt)
+    if noise:
+        assert [i for i, ck in enumerate(chunks) if ck[2] & 0x2] == noise
 
 
 @pytest.mark.parametrize("name,data", [c for c in cases() if c[1].size >= 16])
