@@ -768,6 +768,17 @@ static int effective_blocksize(uint64_t chunk_nbytes, int typesize, int blocksiz
     return blocksize > 0 ? blocksize : 1;
 }
 
+// the decoders hold a whole Blosc block in LDS: blocks of at most 64 KiB (c-blosc's automatic blocksizes are larger)
+static int check_decode_block(int typesize, int blocksize)
+{
+    if (blocksize > 65536) {
+        hhgt_set_error("decode: block of %d bytes x typesize %d does not fit LDS (blocks of at most 65536 bytes)",
+                       blocksize, typesize);
+        return HHGT_ERR_ARG;
+    }
+    return HHGT_OK;
+}
+
 static void codec_geometry(uint64_t chunk_nbytes, int typesize, int blocksize, uint32_t *nblocks, uint32_t *nwaves,
                            size_t *slot_bytes)
 {
@@ -1072,6 +1083,7 @@ extern "C" int hhgt_decompress_chunks(hhgt_ctx *c, const void *d_src, const uint
     if (!c || !d_src || !d_dst || !d_chunk_off) return HHGT_ERR_ARG;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
+    TRY(check_decode_block(typesize, blocksize));
     TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
     if (n_bad) *n_bad = 0;
     if (n_chunks == 0) return HHGT_OK;
@@ -1102,6 +1114,7 @@ extern "C" int hhgt_decompress_blocks(hhgt_ctx *c, const hhgt_block_sel *d_sel, 
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
+    TRY(check_decode_block(typesize, blocksize));
     TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
     if (n_bad) *n_bad = 0;
     if (n_sel == 0) return HHGT_OK;

@@ -249,8 +249,16 @@ __device__ __forceinline__ void unshuffle_range(const uint8_t *planes, uint32_t 
 {
     const uint32_t nelem = bsize / typesize;
     const uint32_t pstride = nstreams > 1u ? sstride : nelem;
-    if (!doshuffle || typesize == 1u) {
+    if ((!doshuffle || typesize == 1u) && nstreams == 1u) {
         for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) out[i - lo] = planes[i];
+    } else if (!doshuffle) {
+        // split but not shuffled (c-blosc 1.21 writes this for shuffle 0): stream j holds bytes [j neblock, (j + 1)
+        // neblock) of the block and sits at planes + j * sstride
+        const uint32_t neblock = bsize / nstreams;
+        for (uint32_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+            const uint32_t j = i / neblock;
+            out[i - lo] = planes[j * sstride + (i - j * neblock)];
+        }
     } else if (typesize == 2u && nstreams == 2u && ((lo | hi) & 15u) == 0u &&
                ((reinterpret_cast<uintptr_t>(out) & 15u) == 0)) {
         for (uint32_t i = lo + threadIdx.x * 16u; i < hi; i += blockDim.x * 16u) {
@@ -515,7 +523,9 @@ __global__ __launch_bounds__(128) void k_count_alleles(const hhgt_count_sel *__r
 // launch shape shared by both kernels: waves per workgroup, the per-stream LDS stride, dynamic LDS bytes
 static int decode_geometry(int typesize, int blocksize, uint32_t *nwaves, uint32_t *sstride, size_t *lds)
 {
-    const uint32_t split = (typesize >= 2 && typesize <= 16 && blocksize / typesize >= 128) ? 1u : 0u;
+    // one wave per stream of a split header: typesize 2..16 always, also for blocks of fewer than 128 elements, which
+    // our encoder and c-blosc store unsplit but another writer may split (the split is the header's word, not ours)
+    const uint32_t split = (typesize >= 2 && typesize <= 16) ? 1u : 0u;
     *nwaves = split ? (uint32_t)typesize : 1u;
     const uint32_t max_stream = split ? (uint32_t)blocksize / (uint32_t)typesize : (uint32_t)blocksize;
     // per-stream buffer = decoded plane + in-place margin ((n >> 8) + 32) + alignment slack (4) + read-ahead (24)

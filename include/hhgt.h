@@ -217,8 +217,12 @@ int hhgt_compress_chunks(hhgt_ctx *ctx, const void *d_src, uint64_t n_chunks, ui
 
 /* Inverse (read side, src/utils/h5_reader.py:37-41): decodes n_chunks framed chunks (either header
  * format) into d_dst, chunk i at d_dst + i*chunk_nbytes.  typesize/blocksize are the dataset's
- * (the headers are validated against them).  Sets *n_bad (host, optional, syncs) to
- * the number of chunks that failed validation. */
+ * (the headers are validated against them).  Sets *n_bad (host, optional, syncs) to the number of
+ * failures: 1 per chunk whose header is refused, 1 per Blosc block whose stream table or LZ4 stream is
+ * corrupt (a chunk with k corrupt blocks counts k; its other blocks and every other chunk are exact).
+ * Accepted: LZ4 / LZ4HC streams (codec 1), byte shuffle or none, split or unsplit blocks, memcpyed chunks.
+ * Refused: bitshuffle, any other codec (blosclz, zlib, zstd, ...), a header whose typesize, nbytes,
+ * blocksize or cbytes differ from the call's; blocks over 64 KiB (they do not fit LDS) fail the call. */
 int hhgt_decompress_chunks(hhgt_ctx *ctx, const void *d_src, const uint64_t *d_chunk_off,
                            uint64_t n_chunks, uint64_t chunk_nbytes, int typesize, int blocksize,
                            void *d_dst, uint64_t *n_bad, void *stream);

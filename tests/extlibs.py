@@ -85,10 +85,60 @@ def blosc1_decompress(chunk, nbytes):
     return out[:n]
 
 
-def blosc1_compress(buf, typesize, blocksize=0, clevel=5, shuffle=1, cname=b"lz4"):
+def blosc1_compress(buf, typesize, blocksize=0, clevel=5, shuffle=1, cname=b"lz4", tight=False):
+    """tight: a destination of nbytes + 16 (BLOSC_MAX_OVERHEAD), c-blosc's own sizing, under which it stores
+    incompressible input as a memcpyed chunk"""
     buf = np.ascontiguousarray(buf, dtype=np.uint8)
-    out = np.empty(buf.size + 16 + 4096, np.uint8)
+    out = np.empty(buf.size + 16 + (0 if tight else 4096), np.uint8)
     n = _blosc.blosc_compress_ctx(clevel, shuffle, typesize, buf.size, buf.ctypes.data, out.ctypes.data, out.size,
                                   cname, blocksize, 1)
     assert n > 0
     return out[:n].copy()
+
+
+if _lz4 is not None:
+    _lz4.LZ4_compress_HC.restype = C.c_int
+    _lz4.LZ4_compress_HC.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    _lz4.LZ4_compress_fast.restype = C.c_int
+    _lz4.LZ4_compress_fast.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+if _blosc is not None:
+    _blosc.blosc_set_splitmode.restype = None
+    _blosc.blosc_set_splitmode.argtypes = [C.c_int]
+
+# c-blosc 1.x split modes (blosc.h)
+BLOSC_ALWAYS_SPLIT, BLOSC_NEVER_SPLIT, BLOSC_AUTO_SPLIT, BLOSC_FORWARD_COMPAT_SPLIT = 1, 2, 3, 4
+
+
+def _lz4_call(fn, buf, arg):
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    cap = _lz4.LZ4_compressBound(buf.size)
+    out = np.empty(max(cap, 1), np.uint8)
+    n = fn(buf.ctypes.data, out.ctypes.data, buf.size, cap, arg)
+    assert n > 0
+    return out[:n].copy()
+
+
+def lz4_compress_hc(buf, level):
+    """liblz4's LZ4HC at `level` (1..12): the block coder behind c-blosc's lz4hc"""
+    return _lz4_call(_lz4.LZ4_compress_HC, buf, level)
+
+
+def lz4_compress_fast(buf, accel):
+    """liblz4's fast coder with acceleration `accel` (1 = LZ4_compress_default)"""
+    return _lz4_call(_lz4.LZ4_compress_fast, buf, accel)
+
+
+class splitmode:
+    """with splitmode(BLOSC_NEVER_SPLIT): c-blosc's block splitting for the compressions inside; process-global state, so
+    FORWARD_COMPAT (c-blosc 1.21's default, which other tests rely on) is restored on the way out, also after an error"""
+
+    def __init__(self, mode):
+        self.mode = mode
+
+    def __enter__(self):
+        _blosc.blosc_set_splitmode(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        _blosc.blosc_set_splitmode(BLOSC_FORWARD_COMPAT_SPLIT)
+        return False
