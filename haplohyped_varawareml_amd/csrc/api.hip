@@ -468,7 +468,8 @@ extern "C" int hhgt_encode_result_status(const hhgt_encode_result *r)
         return HHGT_ERR_CAPACITY;
     }
     if (r->stats.n_chrom_runs > MAX_CHROM_RUNS) {
-        hhgt_set_error("encode: %llu CHROM runs in one text block (limit %u): the input is not sorted by contig",
+        hhgt_set_error("encode: %llu CHROM runs in one text block, more than the limit of %u (a run starts at every change of CHROM "
+                       "and behind every empty or header line)",
                        (unsigned long long)r->stats.n_chrom_runs, MAX_CHROM_RUNS);
         return HHGT_ERR_CAPACITY;
     }

@@ -160,8 +160,8 @@ struct Batch {
 
 struct VarSlot {
     PinnedBuf start, ref, alt;
-    uint64_t run_first[HHGT_RESULT_RUNS];
-    char run_names[HHGT_RESULT_RUNS][32];
+    uint64_t run_first[MAX_CHROM_RUNS];
+    char run_names[MAX_CHROM_RUNS][32];
 };
 struct DstSlot {
     DevBuf d, off;          // framed bytes, chunk_off (device)
@@ -240,6 +240,9 @@ struct hhgt_ingest {
     uint64_t n_begun = 0;
     struct Res {
         hhgt_encode_result *rec = nullptr;   // pinned
+        // the block's whole CHROM run table (MAX_CHROM_RUNS entries; the record holds the first HHGT_RESULT_RUNS): copied out of
+        // the context's scratch on the main stream right behind the encode, before the next block's encode overwrites it
+        DevBuf run_first, run_names;
         hipEvent_t ev = nullptr;
         int text_idx = -1;
         InState *st = nullptr;
@@ -1136,10 +1139,21 @@ bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
         fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
         return false;
     }
-    G_TRY(hhgt_encode_result_status(&rec));
-    if (rec.stats.n_chrom_runs > HHGT_RESULT_RUNS) {
-        fail(g, HHGT_ERR_CAPACITY, "more than 16 CHROM runs in one text block: the input is not sorted by contig");
-        return false;
+    G_TRY(hhgt_encode_result_status(&rec));   // (more than MAX_CHROM_RUNS runs: HHGT_ERR_CAPACITY)
+    const uint32_t n_runs = (uint32_t)rec.stats.n_chrom_runs;
+    const uint64_t *run_first = rec.run_first;
+    const char *run_names = &rec.run_names[0][0];
+    std::vector<uint64_t> more_first;
+    std::vector<char> more_names;
+    if (n_runs > HHGT_RESULT_RUNS) {
+        // every empty or header line and every CHROM change inside the block starts a run (the ones with no kept record
+        // included): the rest of the table is in the copy queued behind the block's encode
+        more_first.resize(n_runs);
+        more_names.resize((size_t)n_runs * 32);
+        G_HIP(hipMemcpy(more_first.data(), r.run_first.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost));
+        G_HIP(hipMemcpy(more_names.data(), r.run_names.p, (size_t)n_runs * 32, hipMemcpyDeviceToHost));
+        run_first = more_first.data();
+        run_names = more_names.data();
     }
     in->st.n_lines += rec.stats.n_lines;
     in->st.n_records += rec.stats.n_records;
@@ -1161,7 +1175,7 @@ bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
     r.text_idx = -1;
     X->host_cursor = b;
     in->st.n_kept = b;
-    if (b > a || rec.stats.n_chrom_runs) {
+    if (b > a || n_runs) {
         Batch v;
         v.kind = B_VARIANTS;
         v.in = in;
@@ -1179,11 +1193,12 @@ bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
             G_HIP(hipGetLastError());
         }
         trace("drv:tables_queued", (long long)(b - a));
-        for (uint64_t i = 0; i < rec.stats.n_chrom_runs; ++i) {
-            const std::string name(rec.run_names[i], strnlen(rec.run_names[i], 31));
-            if (name == in->last_run) continue;   // the block continues the previous block's contig
+        for (uint32_t i = 0; i < n_runs; ++i) {
+            const char *nm = run_names + (size_t)i * 32;
+            const std::string name(nm, strnlen(nm, 31));
+            if (name == in->last_run) continue;   // the block continues the previous block's (or this block's last) contig
             in->last_run = name;
-            vs.run_first[v.n_runs] = a + rec.run_first[i];
+            vs.run_first[v.n_runs] = a + run_first[i];
             memset(vs.run_names[v.n_runs], 0, 32);
             memcpy(vs.run_names[v.n_runs], name.data(), name.size());
             ++v.n_runs;
@@ -1245,12 +1260,13 @@ void driver_main(hhgt_ingest *g)
             trace("drv:encode_launch", ti, (long long)tb.nbytes);
             G_HIP(hipStreamWaitEvent(g->s_main, tb.ready, 0));
             // Bound on the block's line count (sizes the workspaces and every grid behind the index): a record of a
-            // file with S sample columns has at least 2 S + 17 bytes, so apart from the header lines of the first
+            // file with S sample columns has at least 2 S + 17 bytes (a sites-only file's eight columns: 16), so apart from the header lines of the first
             // block more lines than that can only be blank or cut-off lines — which are a parse error anyway
             // (reported as such by harvest).  The unconditional bound, 1024 lines per 16 KiB region, would size the
             // grids for lines of 16 bytes: 10 M empty workgroups per 1 GiB block.
             const uint64_t n_regions = (tb.nbytes + 1 + INDEX_REGION - 1) / INDEX_REGION;
-            uint64_t max_lines = tb.nbytes / (2 * in->S_file + 17) + (tb.first ? in->header_lines : 0) + 64;
+            const uint64_t min_record = in->S_file ? 2 * (uint64_t)in->S_file + 17 : 16;
+            uint64_t max_lines = tb.nbytes / min_record + (tb.first ? in->header_lines : 0) + 64;
             if (max_lines > n_regions * INDEX_CAP) max_lines = n_regions * INDEX_CAP;
             if (X->planes)
                 G_TRY(hhgt_encode_text_planes_async(g->ctx, tb.d, tb.nbytes, in->region.c_str(), &X->lay, X->cursor.as<uint64_t>(),
@@ -1262,6 +1278,8 @@ void driver_main(hhgt_ingest *g)
                                              (uint32_t)(max_lines > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : max_lines), X->G.p,
                                              X->t_start.as<uint32_t>(), nullptr, X->t_ref.as<uint8_t>(), X->t_alt.as<uint8_t>(), r.rec,
                                              g->s_main));
+            G_HIP(hipMemcpyAsync(r.run_first.p, g->ctx->run_first.p, MAX_CHROM_RUNS * 8, hipMemcpyDeviceToDevice, g->s_main));
+            G_HIP(hipMemcpyAsync(r.run_names.p, g->ctx->run_names.p, MAX_CHROM_RUNS * 32, hipMemcpyDeviceToDevice, g->s_main));
             G_HIP(hipEventRecord(r.ev, g->s_main));
             r.text_idx = ti;
             pending.push_back(next_res);
@@ -1425,6 +1443,8 @@ extern "C" int hhgt_ingest_open(hhgt_ctx *ctx, const hhgt_ingest_opts *opts, hhg
     for (int i = 0; i < N_RES && rc == HHGT_OK; ++i) {
         hip(hipHostMalloc(reinterpret_cast<void **>(&g->res[i].rec), sizeof(hhgt_encode_result), hipHostMallocDefault), "hipHostMalloc");
         hip(hipEventCreateWithFlags(&g->res[i].ev, wait_event_flags()), "event");
+        if (rc == HHGT_OK) rc = g->res[i].run_first.ensure(MAX_CHROM_RUNS * 8);
+        if (rc == HHGT_OK) rc = g->res[i].run_names.ensure(MAX_CHROM_RUNS * 32);
     }
     for (int i = 0; i < N_VAR; ++i) g->free_var.push(i);
     for (int i = 0; i < N_DST; ++i) g->free_dst.push(i);
@@ -1706,6 +1726,8 @@ extern "C" void hhgt_ingest_close(hhgt_ingest *g)
         for (DevBuf *b : {&x.G, &x.P, &x.t_start, &x.t_ref, &x.t_alt, &x.cursor}) b->release();
     for (auto &r : g->res) {
         if (r.rec) hipHostFree(r.rec);
+        r.run_first.release();
+        r.run_names.release();
         if (r.ev) hipEventDestroy(r.ev);
     }
     for (auto &v : g->var) {

@@ -94,7 +94,8 @@ def header_samples(text):
 
 
 def vcf_encode(text, n_samples, region="", cap=None, want_chrom=False, keep_multiallelic=False):
-    """-> dict(G int8 [S, n_kept, 2], start, stop, ref, alt, chrom?, stats).  keep_multiallelic: the labelled
+    """-> dict(G int8 [S, n_kept, 2], start, stop, ref, alt, chrom?, stats).  want_chrom="bytes": chrom as uint8 [n_kept, 32]
+    instead of a list of str.  keep_multiallelic: the labelled
     non-reference filter mode of include/hhgt.h (multi-allelic SNP sites kept)"""
     t = _as_u8(text)
     if cap is None:
@@ -117,7 +118,9 @@ def vcf_encode(text, n_samples, region="", cap=None, want_chrom=False, keep_mult
         raise RuntimeError(f"oracle_vcf_encode failed rc={n} stats={st.asdict()}")
     out = dict(G=np.ascontiguousarray(G[:n_samples, :n]), start=start[:n], stop=stop[:n], ref=ref[:n],
                alt=alt[:n], stats=st.asdict(), n_kept=int(n))
-    if want_chrom:
+    if want_chrom == "bytes":
+        out["chrom"] = chrom[:n]          # uint8 [n_kept, 32], NUL padded (millions of records: no per-record str)
+    elif want_chrom:
         out["chrom"] = [bytes(r).rstrip(b"\0").decode() for r in chrom[:n]]
     return out
 

@@ -45,11 +45,12 @@ def split_chunks(dst, chunk_off, total):
     return [d[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
 
 
-def gpu_encode_one_pass(ctx, text, n_samples, region="", mode=2, planes=False, sc=dev.DEFAULT_SC, vc=dev.DEFAULT_VC, cap=None):
+def gpu_encode_one_pass(ctx, text, n_samples, region="", mode=2, planes=False, sc=dev.DEFAULT_SC, vc=dev.DEFAULT_VC, cap=None,
+                        max_lines=None):
     """One pass of the line index `mode` (hhgt_set_index_mode) and the encoders, the way the ingest engine, the converter
     and bench.py run them: hhgt_encode_text_async, or (planes=True, vc % 4096 == 0) hhgt_encode_text_planes_async followed
     by hhgt_planes_expand.  No retry: a MALFORMED pass raises its HhgtError, where gpu_encode would scan every byte once
-    more.  -> the same dict as gpu_encode"""
+    more.  max_lines: the caller's bound (default: every line of the text).  -> the same dict as gpu_encode"""
     import torch
     t = text if torch.is_tensor(text) else to_dev(text)
     S = n_samples
@@ -65,7 +66,8 @@ def gpu_encode_one_pass(ctx, text, n_samples, region="", mode=2, planes=False, s
     res = dev.EncodeResult(z(max(dev.layout_bytes(lay), 16), torch.uint8), lay, z(n_cap, torch.int32), z(n_cap, torch.int32),
                            z(n_cap, torch.uint8), z(n_cap, torch.uint8), 0, {}, [], P)
     cursor = z(1, torch.int64)
-    max_lines = int((t == 0x0A).sum().item()) + 2          # the caller's bound: every line of the text (blank ones included)
+    if max_lines is None:
+        max_lines = int((t == 0x0A).sum().item()) + 2      # the caller's bound: every line of the text (blank ones included)
     ctx.set_index_mode(mode)
     try:
         if planes:
