@@ -105,8 +105,8 @@ struct LayoutDev {
 // ---- bit-plane form of the matrix (include/hhgt.h "Bit-plane form"): tile-major ----------------------------------------
 // A chunk column (Vc variants x S_pad padded sample rows) is cut into tiles of PL_TILE variants; a tile holds, per kind-plane
 // kp (0: ONE hap 0, 1: ONE hap 1, 2: EXC hap 0, 3: EXC hap 1) and sample row r, one 32-byte piece (bit i = variant i of the
-// tile): P[column slot][tile][kp][row][32 B].  The encoder's workgroup (256 rows x one tile) therefore writes four
-// contiguous 8 KiB runs — the first version of this path wrote row-major planes, 32-byte pieces 2 KiB apart, and spent
+// tile): P[column slot][tile][kp][row][32 B].  The encoder's workgroup (252 rows x one tile) therefore writes four
+// contiguous 8064-byte runs — the first version of this path wrote row-major planes, 32-byte pieces 2 KiB apart, and spent
 // 40 % of its time on those partial-line writes — and a compressor wave gathers the 16 pieces of its 4096-variant plane.
 #define PL_TILE 256u
 struct PlanesGeom {

@@ -191,18 +191,22 @@ __global__ __launch_bounds__(256, 4) void k_encode_tiles(
 // two BITS per allele instead of a byte (include/hhgt.h "Bit-plane form"): ONE (allele 1, or missing) and EXC (anything
 // but 0 / 1), so what crosses HBM between the two halves of the path is S/2 bytes per variant each way instead of 2 S.
 //
-// A 256-thread workgroup owns one plane tile (PL_TILE = 256 variants) of 256 samples; wave w reads lines [64 w, 64 w + 64)
-// of the tile in groups of lines (1 KiB each, 16 B per lane = 4 samples) whose loads are in flight together; where a
-// group's line starts come from: pl_load_step.  Packing is SWAR on the field dword "a|b\t": (x & 0x00010001) holds the
+// A 256-thread workgroup owns one plane tile (PL_TILE = 256 variants) of a band of PT_S = 252 samples; wave w reads lines
+// [64 w, 64 w + 64) of the tile in groups of lines whose loads are in flight together (one 16-byte-aligned 1 KiB window per
+// line: pl_load_window; lanes 0..62 own 4 samples each, lane 63 loads but owns nothing); where a group's line starts come
+// from: pl_load_step.  Each lane's four fields are rebuilt from its chunk and its neighbour's just before packing
+// (pl_funnel).  Packing is SWAR on the field dword "a|b\t": (x & 0x00010001) holds the
 // two allele bits, shifted by the line number they accumulate into a register whose low half is haplotype 0 and whose
 // high half is haplotype 1 over 16 lines; one xor/or chain per line tells whether all four fields of the lane were
 // "[01]|[01]\t" (pl_pack_group: what happens otherwise).  Per 32 lines a lane holds one dword per (sample, plane, kind):
-// 16 ds_write_b32 into a 32 KiB image [kind][plane][sample][32 B]; after one barrier the image leaves as four contiguous
-// 8 KiB runs — the planes are TILE-MAJOR in HBM (common.h) for exactly that.  The tile that straddles the append position
-// merges with the bits the previous call wrote.
-// HBM roofline: algorithmic bytes per variant = 4 S read + S/2 written.  What bounds it in practice: the 16-byte loads
-// start at the byte where a line's sample columns start, and a wave-load whose lanes are not dword-aligned is worth
-// ~20 % less (tools/micro/strided_read.hip: 6.4 -> 5.1 TB/s).
+// 16 ds_write_b32 into a 32 KiB image [kind][plane][sample][32 B] (rows 0..251 are the band's); after one barrier the
+// image leaves as four contiguous 8064-byte runs — the planes are TILE-MAJOR in HBM (common.h) for exactly that.  The tile
+// that straddles the append position merges with the bits the previous call wrote.
+// HBM roofline: algorithmic bytes per variant = 4 S read + S/2 written.  Why 252 samples and not 256: a band's fields are
+// 1008 bytes, so with any start phase they fit one 16-byte-aligned 1 KiB window, one load instruction per line and wave
+// with every lane aligned.  Lanes that load at the (arbitrary) byte where the sample columns start run ~20 % slower
+// (tools/micro/strided_read.hip: 6.4 -> 5.1 TB/s), and a 256-sample band needs a 65th aligned chunk per line.
+#define PT_S 252           // samples per band: 63 owner lanes x 4 (TILE_S stays k_encode_tiles')
 #define PT_V 256           // = PL_TILE
 #define PT_ROWDW (PT_V / 32)                    // dwords per image row
 #ifndef PT_NW
@@ -243,48 +247,74 @@ __device__ __forceinline__ PlStep pl_load_step(const uint32_t *__restrict__ k_so
     return t;
 }
 
-// the 16 bytes (four sample fields) of one line that this lane owns
+// Lane `lane`'s 16-byte chunk of the aligned 1 KiB window that covers the band's fields of one line: the band's fields
+// start at F = soff + 4 s0 (s0 = 252 b, so F = soff + 1008 b and F's phase against 16 bytes is the line's, whatever the
+// band), the window at F minus that phase (the text itself starts on a 16-byte boundary: api.hip checks).  The window may
+// reach up to 12 bytes past the line's end (the band behind it has fewer than 4 samples) or into the bytes in front of F
+// (band 0): none of those bytes is a field this lane owns, and the window has to stay inside the text only.  EDGE (k_encode_planes: the
+// last band, and any band of a tile whose last line's window could end past the text) reads a window that would end past
+// the text's end byte by byte, and what lies past the end reads as a tab; every other tile reads flat.
 template <bool EDGE>
-__device__ __forceinline__ uint4 pl_load_line(const uint8_t *__restrict__ text, uint64_t n, uint32_t soff, uint32_t ls, uint32_t nval,
-                                              uint32_t last_q)
+__device__ __forceinline__ uint4 pl_load_window(const uint8_t *__restrict__ text, uint64_t n, uint32_t soff, uint32_t s0, uint32_t lane)
 {
-    uint4 v = make_uint4(FILL_FIELD, FILL_FIELD, FILL_FIELD, FILL_FIELD);
-    const uint64_t off = (uint64_t)soff + 4ull * ls;
-    if (!EDGE) {
-        // Every lane owns four samples in front of the line's last one: the 16 bytes lie inside the line.  (They start
-        // wherever the line's sample columns start; in isolation a wave-load whose lanes are not dword-aligned runs at ~80 % of
-        // an aligned one — tools/micro/strided_read.hip.  Two aligned forms were built and measured in round 3, both correct,
-        // neither faster: aligned chunks + the neighbour lane's data by wavefront shift (the 65th chunk needs its own load per
-        // line), and two aligned loads per lane with a deferred funnel shift (0.61 against 0.56 ms per chr1-sized shard;
-        // both in git history: round 3).)
-        u32x4_unaligned t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(text + off));
-        v = make_uint4(t.x, t.y, t.z, t.w);
-    } else {
-        if (nval == 4u && off + 16ull <= n) {
-            u32x4_unaligned t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(text + off));
-            v = make_uint4(t.x, t.y, t.z, t.w);
-        } else if (nval) {
-            uint32_t d[4];
+    const uint64_t F = (uint64_t)soff + 4ull * s0;
+    const uint64_t A = F & ~15ull;
+    const uint64_t off = A + 16ull * lane;
+    if (!EDGE || A + 1024ull <= n) {   // (wave-uniform)
+        const u32x4_al t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_al *>(text + off));
+        return make_uint4(t.x, t.y, t.z, t.w);
+    }
+    uint32_t d[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t x = FILL_FIELD;
-                if ((uint32_t)q < nval) {
+    for (int q = 0; q < 4; ++q) {
+        uint32_t x = 0;
 #pragma unroll
-                    for (int bb = 0; bb < 4; ++bb) {
-                        uint64_t idx = off + (uint64_t)(q * 4 + bb);
-                        uint32_t c = idx < n ? text[idx] : (uint32_t)'\t';
-                        x = (x & ~(0xFFu << (bb * 8))) | (c << (bb * 8));
-                    }
-                }
-                d[q] = x;
-            }
-            v = make_uint4(d[0], d[1], d[2], d[3]);
+        for (int bb = 0; bb < 4; ++bb) {
+            const uint64_t idx = off + (uint64_t)(q * 4 + bb);
+            x |= (idx < n ? (uint32_t)text[idx] : (uint32_t)'\t') << (bb * 8);
         }
-        // the last sample of a line is terminated by the line end (LF_FAST pinned where it ends)
-        if (last_q == 0u) v.x = (v.x & 0x00FFFFFFu) | 0x09000000u;
-        if (last_q == 1u) v.y = (v.y & 0x00FFFFFFu) | 0x09000000u;
-        if (last_q == 2u) v.z = (v.z & 0x00FFFFFFu) | 0x09000000u;
-        if (last_q == 3u) v.w = (v.w & 0x00FFFFFFu) | 0x09000000u;
+        d[q] = x;
+    }
+    return make_uint4(d[0], d[1], d[2], d[3]);
+}
+
+// The lane's four fields from its window chunk c and lane + 1's: bytes [d, d + 16) of the 32 (d = the line's phase,
+// wave-uniform).  Four DPP moves (wave_shl:1; lane 63 gets zeros — it owns nothing), dwords d >> 2 .. (d >> 2) + 4 of the
+// eight by two v_cndmask stages on the bits of d >> 2 (as lane masks: a uniform select of an array element becomes a
+// scratch round trip), v_alignbyte by d & 3.
+__device__ __forceinline__ uint4 pl_funnel(const uint4 c, const uint32_t d)
+{
+    const uint32_t w[8] = {c.x, c.y, c.z, c.w,
+                           (uint32_t)__builtin_amdgcn_mov_dpp((int)c.x, 0x130, 0xf, 0xf, true),
+                           (uint32_t)__builtin_amdgcn_mov_dpp((int)c.y, 0x130, 0xf, 0xf, true),
+                           (uint32_t)__builtin_amdgcn_mov_dpp((int)c.z, 0x130, 0xf, 0xf, true),
+                           (uint32_t)__builtin_amdgcn_mov_dpp((int)c.w, 0x130, 0xf, 0xf, true)};
+    const bool k2 = __builtin_amdgcn_inverse_ballot_w64((d & 8u) ? ~0ull : 0ull);
+    const bool k1 = __builtin_amdgcn_inverse_ballot_w64((d & 4u) ? ~0ull : 0ull);
+    uint32_t t[6], u[5];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) t[i] = k2 ? w[i + 2] : w[i];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) u[i] = k1 ? t[i + 1] : t[i];
+    const uint32_t r = d & 3u;
+    return make_uint4(__builtin_amdgcn_alignbyte(u[1], u[0], r), __builtin_amdgcn_alignbyte(u[2], u[1], r),
+                      __builtin_amdgcn_alignbyte(u[3], u[2], r), __builtin_amdgcn_alignbyte(u[4], u[3], r));
+}
+
+// the band that holds the last sample: fields the lane does not own read "0|0\t", and the last sample of the line is
+// terminated by the line end (LF_FAST pinned where it ends).  rel = (S - 1) - (the lane's first sample): field q is
+// owned if q < rel, the last sample's if q == rel.
+template <bool EDGE>
+__device__ __forceinline__ uint4 pl_edge_fields(uint4 v, int rel)
+{
+    if (EDGE) {
+        uint32_t x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t keep = rel > q ? 0xFFFFFFFFu : (rel == q ? 0x00FFFFFFu : 0u);
+            x[q] = (x[q] & keep) | (FILL_FIELD & ~keep);
+        }
+        v = make_uint4(x[0], x[1], x[2], x[3]);
     }
     return v;
 }
@@ -293,9 +323,10 @@ struct __attribute__((packed)) PlU32 {
     uint32_t v;
 };
 
+// the raw window chunks of PT_G lines (the funnel waits for pl_pack_group: the chunks in flight stay 4 registers per line)
 template <bool EDGE>
-__device__ __forceinline__ void pl_load_group(PlGroup &gr, const uint8_t *__restrict__ text, uint64_t n, const PlStep &stp, const int j0,
-                                              uint32_t ls, uint32_t nval, uint32_t last_q)
+__device__ __forceinline__ void pl_load_group(PlGroup &gr, const uint8_t *__restrict__ text, uint64_t n, const PlStep &stp,
+                                              const int j0, uint32_t s0, uint32_t lane)
 {
     uint32_t lv = 0, lst = 0;
 #pragma unroll
@@ -305,7 +336,7 @@ __device__ __forceinline__ void pl_load_group(PlGroup &gr, const uint8_t *__rest
         uint4 v = make_uint4(FILL_FIELD, FILL_FIELD, FILL_FIELD, FILL_FIELD);
         if (meta & LF_FAST) {   // (wave-uniform)
             lv |= 1u << j;
-            v = pl_load_line<EDGE>(text, n, soff, ls, nval, last_q);
+            v = pl_load_window<EDGE>(text, n, soff, s0, lane);
         } else if ((meta >> 20) & 15u)
             lst |= 1u << j;   // decoded by the second level below, at its stride
         gr.raw[j] = v;
@@ -325,14 +356,18 @@ __device__ __forceinline__ void pl_load_group(PlGroup &gr, const uint8_t *__rest
 // what lets four workgroups share a CU.
 template <bool EDGE>
 __device__ __forceinline__ void pl_pack_group(const PlGroup &gr, const int sh, uint32_t (&one)[4], uint32_t (&exc)[4], long long kbase,
-                                              const uint8_t *__restrict__ text, uint64_t n, const PlStep &stp, const int j0, uint32_t ls,
-                                              uint32_t nval, uint32_t last_q, uint32_t *__restrict__ redo_list,
+                                              const uint8_t *__restrict__ text, uint64_t n, const PlStep &stp, const int j0,
+                                              uint32_t s0, uint32_t ls, uint32_t nval, uint32_t *__restrict__ redo_list,
                                               uint32_t *__restrict__ redo_flag, DevCounters *cnt, uint32_t lane, uint32_t S_all)
 {
+    const int rel = lane == 63u ? -1 : (int)(S_all - 1u) - (int)ls;   // (EDGE: pl_edge_fields)
     uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, bad = 0;
 #pragma unroll
     for (int j = 0; j < PT_G; ++j) {
-        const uint4 x = gr.raw[j];
+        // the line's phase (a line that was not loaded holds "0|0\t" in every dword: phase 0 keeps it so)
+        const uint32_t soff = (uint32_t)__builtin_amdgcn_readlane((int)stp.soff, j0 + j);
+        const uint32_t d = ((gr.lvalid >> j) & 1u) ? soff & 15u : 0u;
+        const uint4 x = pl_edge_fields<EDGE>(pl_funnel(gr.raw[j], d), rel);
         a0 |= (x.x & 0x00010001u) << (sh + j);
         a1 |= (x.y & 0x00010001u) << (sh + j);
         a2 |= (x.z & 0x00010001u) << (sh + j);
@@ -340,7 +375,8 @@ __device__ __forceinline__ void pl_pack_group(const PlGroup &gr, const int sh, u
         bad |= ((x.x ^ PT_C) | (x.y ^ PT_C)) | ((x.z ^ PT_C) | (x.w ^ PT_C));
     }
     bad |= gr.lstride ? 2u : 0u;   // a record decoded at its stride is the second level's (as data, not as a branch: the branch cost 86 spilled registers)
-    if (__builtin_amdgcn_ballot_w64((bad & 0xFFFEFFFEu) != 0u) == 0ull) {
+    // (lane 63 owns nothing: what it holds is the next band's, or past the line)
+    if ((__builtin_amdgcn_ballot_w64((bad & 0xFFFEFFFEu) != 0u) & 0x7FFFFFFFFFFFFFFFull) == 0ull) {
         one[0] |= a0, one[1] |= a1, one[2] |= a2, one[3] |= a3;
         return;
     }
@@ -367,7 +403,7 @@ __device__ __forceinline__ void pl_pack_group(const PlGroup &gr, const int sh, u
         hard |= off;                                                                                                   \
     } while (0)
         if (meta & LF_FAST) {   // (wave-uniform)
-            const uint4 v = pl_load_line<EDGE>(text, n, soff, ls, nval, last_q);
+            const uint4 v = pl_edge_fields<EDGE>(pl_funnel(pl_load_window<EDGE>(text, n, soff, s0, lane), soff & 15u), rel);
             PL_CLASSIFY(v.x, 0);
             PL_CLASSIFY(v.y, 1);
             PL_CLASSIFY(v.z, 2);
@@ -412,7 +448,7 @@ __device__ __forceinline__ void pl_pack_group(const PlGroup &gr, const int sh, u
 #undef PL_STRIDED
         }
 #undef PL_CLASSIFY
-        const unsigned long long bm = __builtin_amdgcn_ballot_w64(hard != 0u);
+        const unsigned long long bm = __builtin_amdgcn_ballot_w64(hard != 0u) & 0x7FFFFFFFFFFFFFFFull;
         if (bm != 0ull && lane == 0) {
             const uint32_t k = (uint32_t)(kbase + j);
             if (atomicExch(&redo_flag[k], 1u) == 0u) {
@@ -433,13 +469,12 @@ __device__ __forceinline__ void encode_planes_tile(const uint8_t *__restrict__ t
     const uint64_t gv0 = (v_base / PT_V + tile_v) * (uint64_t)PT_V;   // first global column of the tile
     const long long k0 = (long long)gv0 - (long long)v_base;              // batch-local kept index of it
     if (k0 >= (long long)n_kept || (!lay.ring && gv0 >= lay.v_capacity)) return;
-    const uint32_t s0 = band * TILE_S;
+    const uint32_t s0 = band * PT_S;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t S = lay.S;
     const uint32_t ls = s0 + 4u * lane;
-    const uint32_t nval = ls >= S ? 0u : (S - ls >= 4u ? 4u : S - ls);
-    const uint32_t last_q = (S - 1u >= ls && S - 1u < ls + 4u) ? S - 1u - ls : 4u;
+    const uint32_t nval = (lane == 63u || ls >= S) ? 0u : (S - ls >= 4u ? 4u : S - ls);
     const long long kw = k0 + (long long)(w * PT_LW);
 
     constexpr int NG = 32 / PT_G;   // load groups per 32 lines
@@ -453,33 +488,35 @@ __device__ __forceinline__ void encode_planes_tile(const uint8_t *__restrict__ t
         // PT_SCHED(): the instruction scheduler may not move anything across — it would otherwise hoist the loads of all
         // four groups of a step to its top (128 registers of text in flight per lane, and spills)
 #define PT_SCHED() __builtin_amdgcn_sched_barrier(0)
-#if PT_DB
-        PlGroup A, B;
-        pl_load_group<EDGE>(A, text, n, stp, 0, ls, nval, last_q);
+        // (the careful path of EDGE tiles does not fit the registers next to a second group in flight: they load one group
+        // at a time)
+        if (PT_DB && !EDGE) {
+            PlGroup A, B;
+            pl_load_group<EDGE>(A, text, n, stp, 0, s0, lane);
 #pragma unroll
-        for (int g = 0; g < NG; g += 2) {
-            pl_load_group<EDGE>(B, text, n, stp, (g + 1) * PT_G, ls, nval, last_q);
-            PT_SCHED();
-            pl_pack_group<EDGE>(A, (g * PT_G) & 15, o[(g * PT_G) >> 4], e[(g * PT_G) >> 4], kb + g * PT_G, text, n, stp, g * PT_G, ls, nval,
-                                last_q, redo_list, redo_flag, cnt, lane, S);
-            PT_SCHED();
-            if (g + 2 < NG) pl_load_group<EDGE>(A, text, n, stp, (g + 2) * PT_G, ls, nval, last_q);
-            PT_SCHED();
-            pl_pack_group<EDGE>(B, ((g + 1) * PT_G) & 15, o[((g + 1) * PT_G) >> 4], e[((g + 1) * PT_G) >> 4], kb + (g + 1) * PT_G, text, n,
-                                stp, (g + 1) * PT_G, ls, nval, last_q, redo_list, redo_flag, cnt, lane, S);
-            PT_SCHED();
-        }
-#else
+            for (int g = 0; g < NG; g += 2) {
+                pl_load_group<EDGE>(B, text, n, stp, (g + 1) * PT_G, s0, lane);
+                PT_SCHED();
+                pl_pack_group<EDGE>(A, (g * PT_G) & 15, o[(g * PT_G) >> 4], e[(g * PT_G) >> 4], kb + g * PT_G, text, n, stp, g * PT_G, s0, ls,
+                                    nval, redo_list, redo_flag, cnt, lane, S);
+                PT_SCHED();
+                if (g + 2 < NG) pl_load_group<EDGE>(A, text, n, stp, (g + 2) * PT_G, s0, lane);
+                PT_SCHED();
+                pl_pack_group<EDGE>(B, ((g + 1) * PT_G) & 15, o[((g + 1) * PT_G) >> 4], e[((g + 1) * PT_G) >> 4], kb + (g + 1) * PT_G, text, n,
+                                    stp, (g + 1) * PT_G, s0, ls, nval, redo_list, redo_flag, cnt, lane, S);
+                PT_SCHED();
+            }
+        } else {
 #pragma unroll
-        for (int g = 0; g < NG; ++g) {
-            PlGroup A;
-            pl_load_group<EDGE>(A, text, n, stp, g * PT_G, ls, nval, last_q);
-            PT_SCHED();
-            pl_pack_group<EDGE>(A, (g * PT_G) & 15, o[(g * PT_G) >> 4], e[(g * PT_G) >> 4], kb + g * PT_G, text, n, stp, g * PT_G, ls, nval,
-                                last_q, redo_list, redo_flag, cnt, lane, S);
-            PT_SCHED();
+            for (int g = 0; g < NG; ++g) {
+                PlGroup A;
+                pl_load_group<EDGE>(A, text, n, stp, g * PT_G, s0, lane);
+                PT_SCHED();
+                pl_pack_group<EDGE>(A, (g * PT_G) & 15, o[(g * PT_G) >> 4], e[(g * PT_G) >> 4], kb + g * PT_G, text, n, stp, g * PT_G, s0, ls,
+                                    nval, redo_list, redo_flag, cnt, lane, S);
+                PT_SCHED();
+            }
         }
-#endif
         // image row (kind * 2 + plane) * 256 + sample, 8 dwords; dword c of a row sits at c ^ ((lane >> 1) & 7)
         const uint32_t c = (w * (uint32_t)(PT_LW / 32) + (uint32_t)gp) ^ ((lane >> 1) & 7u);
 #pragma unroll
@@ -492,7 +529,8 @@ __device__ __forceinline__ void encode_planes_tile(const uint8_t *__restrict__ t
         }
     }
     __syncthreads();
-    // image -> HBM: per kind-plane the 256 rows are one contiguous 8 KiB run of the tile (tile-major planes, common.h)
+    // image -> HBM: per kind-plane the band's 252 rows are one contiguous 8064-byte run of the tile (tile-major planes,
+    // common.h); rows 252..255 (lane 63's) are not the band's
     uint64_t vcol = gv0 / lay.Vc;
     const uint64_t vin = gv0 - vcol * lay.Vc;
     if (lay.ring) vcol %= lay.ring;
@@ -504,7 +542,7 @@ __device__ __forceinline__ void encode_planes_tile(const uint8_t *__restrict__ t
         const uint32_t pi = (uint32_t)it * (64u * PT_NW) + threadIdx.x;   // 16-byte piece: kp * 512 + row * 2 + half
         const uint32_t kp = pi >> 9, row = (pi >> 1) & 255u, half = pi & 1u;
         const uint32_t s = s0 + row;
-        if (s >= S) continue;
+        if (row >= PT_S || s >= S) continue;
         const uint32_t sw = (row >> 3) & 7u;   // the writer's (lane >> 1) & 7: row = 4 lane + q
         const uint4 t = reinterpret_cast<const uint4 *>(img)[(kp * 256u + row) * 2u + (half ^ (sw >> 2))];
         uint32_t d0 = t.x, d1 = t.y, d2 = t.z, d3 = t.w;
@@ -537,10 +575,12 @@ __device__ __forceinline__ void encode_planes_tile(const uint8_t *__restrict__ t
     }
 }
 
-// The band of sample columns that holds the last sample (and lanes past it) reads with care (EDGE); every other band reads
-// 16 bytes flat.  One launch, a workgroup-uniform branch: since the medium path is a rolled loop both bodies fit the same
-// 125 registers, and the last band's tiles fill the tail of the grid instead of being an under-filled launch of their own
-// (round 3 first split them: 1.2 of 7.8 ms per step).
+// The band of sample columns that holds the last sample (and lanes past it) reads with care (EDGE), and so does every band
+// of a tile whose last line's window could end past the text (the text's last lines, in front of a last band of 1..3
+// samples): kept lines are in text order, so no line of the tile starts behind its last one.  Every other tile reads flat.
+// One launch, a workgroup-uniform branch: since the medium path is a rolled loop both bodies fit the same registers, and
+// the last band's tiles fill the tail of the grid instead of being an under-filled launch of their own (round 3 first split
+// them: 1.2 of 7.8 ms per step).
 __global__ __launch_bounds__(64 * PT_NW, PT_WGS) void k_encode_planes(const uint8_t *__restrict__ text, uint64_t n,
                                                           const uint32_t *__restrict__ k_soff, const uint32_t *__restrict__ k_meta,
                                                           const uint64_t *__restrict__ d_cursor, LayoutDev lay,
@@ -559,7 +599,13 @@ __global__ __launch_bounds__(64 * PT_NW, PT_WGS) void k_encode_planes(const uint
     const uint32_t band = q % tiles_s;
     const uint32_t tile_v = (q / tiles_s) * 8u + x;
     if (tile_v >= tiles_v) return;
-    if (band + 1u == tiles_s)
+    bool edge = band + 1u == tiles_s;
+    if (!edge) {
+        const long long k0 = (long long)((v_base / PT_V + tile_v) * (uint64_t)PT_V) - (long long)v_base;
+        const long long kl = k0 + (PT_V - 1) < (long long)n_kept - 1 ? k0 + (PT_V - 1) : (long long)n_kept - 1;
+        if (kl >= 0) edge = (uint64_t)k_soff[kl] + 4ull * PT_S * band + 1024ull > n;
+    }
+    if (edge)
         encode_planes_tile<true>(text, n, k_soff, k_meta, v_base, n_kept, lay, P, G, redo_list, redo_flag, cnt, img, tile_v, band);
     else
         encode_planes_tile<false>(text, n, k_soff, k_meta, v_base, n_kept, lay, P, G, redo_list, redo_flag, cnt, img, tile_v, band);
@@ -946,7 +992,7 @@ int launch_encode_planes(const uint8_t *d_text, uint64_t n, const uint32_t *k_so
                          uint32_t *redo_list, uint32_t *redo_flag, DevCounters *d_cnt, hipStream_t st)
 {
     if (n_lines_bound == 0 || lay.S == 0) return HHGT_OK;
-    const uint32_t tiles_s = (lay.S + TILE_S - 1) / TILE_S;
+    const uint32_t tiles_s = (lay.S + PT_S - 1) / PT_S;
     // the append position is only known on the device: one tile more than the lines need covers any phase
     const uint64_t tiles_v = ((uint64_t)(PT_V - 1) + (uint64_t)n_lines_bound + (PT_V - 1)) / PT_V;
     // (measured, encode stage of the bench: 7.6 ms variant tile fastest, 7.4 ms band fastest / XCD-aware)
