@@ -9,8 +9,9 @@ is quoted on; ~30 GB of text, fits one MI355X):
     hhgt_pad_tail_planes_cursor
     hhgt_compress_planes (byte-shuffle + LZ4 -> Blosc2-framed chunks that decode to the int8 matrix)
 Inputs (raw VCF text) are generated ON the GPU (csrc/synth.hip) before the timed region; nothing in the
-step waits on the host.  `value` is this kernel-only leg.  Outside the timed region and
-outside `value`, rank 0 at N = 1 also reports
+step waits on the host.  `value` is this kernel-only leg.  A plain run does only what `value` needs:
+it sets up, warms up, times the steps, writes --dump-outputs and prints the line.  With --full, outside the timed region
+and outside `value`, the line also carries the roofline, and rank 0 at N = 1 reports
     correctness  every shard's chunks decoded on the GPU and compared with G, sampled variants against the
                  generator's rule, two chunks decoded by the CPU oracle — a mismatch fails the run (rc 1)
     host_fed     §8d (ii): the same text in pinned host memory through the ingest engine (PCIe-inclusive)
@@ -18,14 +19,16 @@ outside `value`, rank 0 at N = 1 also reports
                  design) and device inflater
     cpu_baseline the oracle on the host cores: matrix-shaped on 1 core and on all granted cores, and
                  reference-shaped (one rescan of the text per sample)
+    other_configs  the C2 and C4 shapes of BASELINE.json through the same path, with their own checks
+The --no-* switches leave parts of a --full run out.
 
 Multi-GPU: one process per GPU (torch.distributed / RCCL only for the barrier and the max-over-ranks
 time); shards are independent, there is no data-path collective.  `--gpus N` without a launcher starts the
 N ranks itself (before this process touches a GPU); under torchrun the given environment is used.  Default
 "strong": the 22 shards of ONE cohort are dealt to the ranks longest-processing-time-first, as the north star's
-per-chromosome sharding does (`value` = 3 M variants x steps over the slowest rank's time); the trivially linear
-weak form (every rank its own cohort) is measured in the same run and reported as the secondary field `weak`.
-The end-to-end legs run on EVERY rank at once, each over its own share of the 22 BGZF files with its share of the
+per-chromosome sharding does (`value` = 3 M variants x steps over the slowest rank's time); with --full the trivially
+linear weak form (every rank its own cohort) is measured in the same run and reported as the secondary field `weak`.
+The end-to-end legs (--full) run on EVERY rank at once, each over its own share of the 22 BGZF files with its share of the
 host CPUs (sharding.pin_rank: the CPUs of its GPU's NUMA node, divided among the ranks), and are reported as the
 aggregate.
 """
@@ -52,6 +55,10 @@ def parse_args():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong",
                     help="strong (default): the 22 shards of ONE cohort are dealt to the ranks, longest first — the north star's "
                          "per-chromosome sharding; weak: every rank encodes a cohort of its own")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the roofline, the correctness gate, "
+                         "the host-fed / end-to-end legs, weak scaling (N > 1), the CPU baselines and the C2 / C4 legs (the "
+                         "--no-* switches leave parts of it out)")
     ap.add_argument("--no-weak", action="store_true", help="N > 1, --scaling strong: skip the secondary weak-scaling measurement")
     ap.add_argument("--vc", type=int, default=8192, help="variants per chunk (chunk = 64 x vc x 2 bytes)")
     ap.add_argument("--blocksize", type=int, default=8192, help="Blosc2 block bytes")
@@ -765,6 +772,93 @@ def config_leg(ctx, which, variants=None, steps=3, check=True, streams=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# roofline (--full): the dominant stage of the single-stream pass, priced at SURVEY.md §8d's bytes of this rank
+# ---------------------------------------------------------------------------------------------------------------
+def roofline(args, shards, stages, stages_serial, streams, dt_max, g_bytes, comp_bytes):
+    """stages_serial: the un-timed single-stream pass (picks the dominant stage, gives its whole-chip launch time);
+    stages: the timed region (the launch time `achieved` is priced at); dt_max: the job's time of the timed steps"""
+    import glob
+    S = args.samples
+    text_bytes = sum(sh.nbytes for sh in shards)
+    my_variants = sum(sh.V for sh in shards)
+    alg = {
+        "index": text_bytes, "fixed": 0, "encode": sum(sh.V * 4 * S for sh in shards) + g_bytes,
+        "lz4": g_bytes + comp_bytes, "frame": 2 * comp_bytes,
+    }
+    planes = args.intermediate == "planes"
+    p_bytes = sum(sh.res.P.numel() for sh in shards) if planes else 0
+    # what the kernels of this build actually move (planes step: the matrix crosses HBM as 2 bits per allele)
+    moved = {"encode": sum(sh.V * 4 * S for sh in shards) + (p_bytes if planes else g_bytes),
+             "lz4": (p_bytes if planes else g_bytes) + comp_bytes}
+    # dominant kernel stage = largest share of device time
+    dom = max((k for k in stages_serial if k in alg), key=lambda k: stages_serial[k]["ms"])
+    dom_ms_per_launch = stages[dom]["ms"] / max(stages[dom]["launches"], 1)
+    dom_bytes_per_launch = alg[dom] / max(len(shards), 1)                     # one launch per shard per step
+    achieved = dom_bytes_per_launch / (dom_ms_per_launch * 1e-3) / 1e9
+    # HBM traffic of the dominant kernel: NOT measured in this run — per-variant bytes of the newest committed PMC
+    # passes (FETCH_SIZE / WRITE_SIZE collected in separate rocprofv3 runs on a 300 k-variant workload and corrected
+    # as tools/summarize_profiles.py does: fetch bytes = FETCH_SIZE x 2 on gfx950), scaled to this launch size
+    traffic, traffic_source = None, None
+    pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_summary.json")))   # newest build last (r01, r01b, r02 ...)
+    if pmcs:
+        try:
+            per_variant = json.load(open(pmcs[-1])).get(dom, {}).get("hbm_bytes_per_variant")
+            if per_variant and S == 2504:
+                traffic = per_variant * my_variants / max(len(shards), 1)
+                traffic_source = (f"{os.path.basename(pmcs[-1])}: {per_variant:.0f} B/variant from separate --pmc passes "
+                                  f"(300 k variants), scaled to this launch; not collected in this run")
+        except Exception:
+            traffic = None
+    # whole path against SURVEY.md §8d's definition: B = B_enc + B_cmp (unfused: V (F + 6 S) + V' 2 S (1 + 1/r)) per
+    # step, over the step time, over the HBM peak
+    b_whole = text_bytes + g_bytes + g_bytes + comp_bytes
+    step_s = dt_max / args.steps
+    moved_per_launch = moved.get(dom, alg[dom]) / max(len(shards), 1)
+    roof = {"bound": "hbm", "kernel": {"lz4": "k_lz4_bitplanes_uni" if planes else "k_lz4_bitplanes", "encode": "k_encode_planes" if planes else "k_encode_tiles", "index": "k_index_hop",
+                                       "frame": "k_frame_write"}.get(dom, dom),
+            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+            # what this build's kernel really moves per launch (planes in, streams out) over the same launch time: the figure
+            # above prices the launch at SURVEY 8d's bytes (the int8 matrix), as the contract asks
+            "achieved_moved": moved_per_launch / (dom_ms_per_launch * 1e-3) / 1e9,
+            "frac_moved": moved_per_launch / (dom_ms_per_launch * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "traffic": traffic, "traffic_source": traffic_source,
+            "bytes_per_launch": dom_bytes_per_launch, "ms_per_launch": dom_ms_per_launch,
+            "bytes_definition": "SURVEY 8d per-variant figure x variants per launch (lz4: 2 S read + 2 S / r written; encode: 4 S + 2 S)",
+            "moved_bytes_per_launch": moved_per_launch,
+            "whole_path": {"bytes_per_step": b_whole, "GBps": b_whole / step_s / 1e9, "frac": b_whole / step_s / 1e9 / HBM_PEAK_GBS,
+                           "definition": "SURVEY 8d: V (F + 6 S) + V' 2 S (1 + 1/r) over the step time over 8 TB/s"}}
+    if dom == "lz4" and streams is not None and not args.cu_split and not args.lz4_priority:
+        # the timed region runs this kernel on the library's compress stream = 3/4 of the CUs (hhgt_stream_create):
+        # longer launches, shorter step.  The same kernel on the whole chip: the single-stream pass in front of the
+        # timed region.
+        ser = stages_serial[dom]["ms"] / max(stages_serial[dom]["launches"], 1)
+        cus = os.environ.get("HHGT_COMPRESS_CUS")
+        roof["cu_mask"] = ("compress stream restricted to " + (cus if cus and cus != "0" else "3/4 of the") + " CUs" if cus != "0"
+                           else "none (HHGT_COMPRESS_CUS=0)")
+        roof["whole_chip"] = {"ms_per_launch": ser, "achieved": dom_bytes_per_launch / (ser * 1e-3) / 1e9,
+                              "frac": dom_bytes_per_launch / (ser * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                              "source": "un-timed single-stream pass of the same run, default stream (every CU)"}
+    if dom == "lz4":
+        # the contract's roofline is HBM or MFMA; this kernel is bound by neither (DESIGN.md §3.1)
+        sq = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_lz4_sq.txt")))
+        mix = ""
+        try:   # instruction mix per 4 KiB plane from the newest committed SQ-counter pass (a separate rocprofv3 --pmc run)
+            line = next(l for l in open(sq[-1]) if l.startswith(("k_lz4_bitplanes_uni<2, false>", "k_lz4_bitplanes<2, true, false")))
+            w = json.loads(line[line.index("{"):])
+            mix = (f"{w['SQ_INSTS_VALU'] / 1e3:.2f} k vector + {w['SQ_INSTS_SALU'] / 1e3:.2f} k scalar + {w['SQ_INSTS_LDS'] / 1e3:.2f} k LDS "
+                   f"instructions per 4 KiB plane at 7 waves per SIMD ({os.path.basename(sq[-1])}); ")
+        except Exception:
+            pass
+        roof["bound_note"] = ("'hbm' is the contract's vocabulary (HBM or MFMA): this kernel is bound by neither — see limiter; "
+                              "achieved_moved / frac_moved price the launch at the bytes it really moves")
+        roof["limiter"] = ("the sum of a wave's DEPENDENT latencies (vector -> vector, ~220 LDS round trips per plane, scalar <-> vector "
+                           "hand-overs, branches) at 7 waves per SIMD: " + mix + "stage time follows occupancy, not the instruction "
+                           "count (measurements: DESIGN.md 3.2; round 4: a scalar-side selection walk with a third fewer vector "
+                           "instructions per window was 16 % slower); HBM at a sixth of its peak under this kernel")
+    return roof
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -847,7 +941,9 @@ def main():
     frame_stream(False)
     ctx.profile(True)
     # one un-timed single-stream pass: clean per-stage device times (with two streams the event pairs of the
-    # non-dominant stages also contain the time they spend queued behind the other stream's kernels)
+    # non-dominant stages also contain the time they spend queued behind the other stream's kernels).  Every run makes
+    # these two passes, not only --full: the timed steps have always followed them (without them, --warmup 0 timed
+    # 0.7 % slower), and they take about 45 ms.
     one_step(ctx, shards, S, args.blocksize, None)   # (the stream pair's warm-up leaves the default stream cold: this pass read 40 % high once)
     torch.cuda.synchronize()
     ctx.profile_reset()
@@ -884,91 +980,18 @@ def main():
 
     failed = None
     check = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         try:
             check = correctness_gate(ctx, shards, S, args.blocksize)
         except Exception as e:      # reported in the line, and the run exits non-zero
             failed = f"{type(e).__name__}: {e}"
             check = {"ok": False, "error": failed}
 
-    # sizes for the roofline (algorithmic bytes), this rank
+    # this rank's matrix and framed bytes (the compression ratio; with --full, the roofline's algorithmic bytes)
     comp_bytes = sum(int(sh.off[-1].item()) for sh in shards)
     g_bytes = sum(sh.V * 2 * S for sh in shards)                             # V' * 2S (every synthetic record is kept)
-    alg = {
-        "index": text_bytes, "fixed": 0, "encode": sum(sh.V * 4 * S for sh in shards) + g_bytes,
-        "lz4": g_bytes + comp_bytes, "frame": 2 * comp_bytes,
-    }
     planes = args.intermediate == "planes"
-    p_bytes = sum(sh.res.P.numel() for sh in shards) if planes else 0
-    # what the kernels of this build actually move (planes step: the matrix crosses HBM as 2 bits per allele)
-    moved = {"encode": sum(sh.V * 4 * S for sh in shards) + (p_bytes if planes else g_bytes),
-             "lz4": (p_bytes if planes else g_bytes) + comp_bytes}
-    # dominant kernel stage = largest share of device time
-    dom = max((k for k in stages_serial if k in alg), key=lambda k: stages_serial[k]["ms"])
-    dom_ms_per_launch = stages[dom]["ms"] / max(stages[dom]["launches"], 1)
-    dom_bytes_per_launch = alg[dom] / max(len(shards), 1)                     # one launch per shard per step
-    achieved = dom_bytes_per_launch / (dom_ms_per_launch * 1e-3) / 1e9
-    # HBM traffic of the dominant kernel: NOT measured in this run — per-variant bytes of the newest committed PMC
-    # passes (FETCH_SIZE / WRITE_SIZE collected in separate rocprofv3 runs on a 300 k-variant workload and corrected
-    # as MI355X_MICROARCH.md prescribes), scaled to this launch size
-    traffic, traffic_source = None, None
-    import glob
-    pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_summary.json")))   # newest build last (r01, r01b, r02 ...)
-    if pmcs:
-        try:
-            per_variant = json.load(open(pmcs[-1])).get(dom, {}).get("hbm_bytes_per_variant")
-            if per_variant and S == 2504:
-                traffic = per_variant * my_variants / max(len(shards), 1)
-                traffic_source = (f"{os.path.basename(pmcs[-1])}: {per_variant:.0f} B/variant from separate --pmc passes "
-                                  f"(300 k variants), scaled to this launch; not collected in this run")
-        except Exception:
-            traffic = None
-    # whole path against SURVEY.md §8d's definition: B = B_enc + B_cmp (unfused: V (F + 6 S) + V' 2 S (1 + 1/r)) per
-    # step, over the step time, over the HBM peak
-    b_whole = text_bytes + g_bytes + g_bytes + comp_bytes
-    step_s = dt_max / args.steps
-    moved_per_launch = moved.get(dom, alg[dom]) / max(len(shards), 1)
-    roof = {"bound": "hbm", "kernel": {"lz4": "k_lz4_bitplanes_uni" if planes else "k_lz4_bitplanes", "encode": "k_encode_planes" if planes else "k_encode_tiles", "index": "k_index_hop",
-                                       "frame": "k_frame_write"}.get(dom, dom),
-            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            # what this build's kernel really moves per launch (planes in, streams out) over the same launch time: the figure
-            # above prices the launch at SURVEY 8d's bytes (the int8 matrix), as the contract asks
-            "achieved_moved": moved_per_launch / (dom_ms_per_launch * 1e-3) / 1e9,
-            "frac_moved": moved_per_launch / (dom_ms_per_launch * 1e-3) / 1e9 / HBM_PEAK_GBS,
-            "traffic": traffic, "traffic_source": traffic_source,
-            "bytes_per_launch": dom_bytes_per_launch, "ms_per_launch": dom_ms_per_launch,
-            "bytes_definition": "SURVEY 8d per-variant figure x variants per launch (lz4: 2 S read + 2 S / r written; encode: 4 S + 2 S)",
-            "moved_bytes_per_launch": moved_per_launch,
-            "whole_path": {"bytes_per_step": b_whole, "GBps": b_whole / step_s / 1e9, "frac": b_whole / step_s / 1e9 / HBM_PEAK_GBS,
-                           "definition": "SURVEY 8d: V (F + 6 S) + V' 2 S (1 + 1/r) over the step time over 8 TB/s"}}
-    if dom == "lz4" and streams is not None and not args.cu_split and not args.lz4_priority:
-        # the timed region runs this kernel on the library's compress stream = 3/4 of the CUs (hhgt_stream_create):
-        # longer launches, shorter step.  The same kernel on the whole chip: the single-stream pass in front of the
-        # timed region.
-        ser = stages_serial[dom]["ms"] / max(stages_serial[dom]["launches"], 1)
-        cus = os.environ.get("HHGT_COMPRESS_CUS")
-        roof["cu_mask"] = ("compress stream restricted to " + (cus if cus and cus != "0" else "3/4 of the") + " CUs" if cus != "0"
-                           else "none (HHGT_COMPRESS_CUS=0)")
-        roof["whole_chip"] = {"ms_per_launch": ser, "achieved": dom_bytes_per_launch / (ser * 1e-3) / 1e9,
-                              "frac": dom_bytes_per_launch / (ser * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                              "source": "un-timed single-stream pass of the same run, default stream (every CU)"}
-    if dom == "lz4":
-        # the contract's roofline is HBM or MFMA; this kernel is bound by neither
-        sq = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_pmc_lz4_sq.txt")))
-        mix = ""
-        try:   # instruction mix per 4 KiB plane from the newest committed SQ-counter pass (a separate rocprofv3 --pmc run)
-            line = next(l for l in open(sq[-1]) if l.startswith(("k_lz4_bitplanes_uni<2, false>", "k_lz4_bitplanes<2, true, false")))
-            w = json.loads(line[line.index("{"):])
-            mix = (f"{w['SQ_INSTS_VALU'] / 1e3:.2f} k vector + {w['SQ_INSTS_SALU'] / 1e3:.2f} k scalar + {w['SQ_INSTS_LDS'] / 1e3:.2f} k LDS "
-                   f"instructions per 4 KiB plane at 7 waves per SIMD ({os.path.basename(sq[-1])}); ")
-        except Exception:
-            pass
-        roof["bound_note"] = ("'hbm' is the contract's vocabulary (HBM or MFMA): this kernel is bound by neither — see limiter; "
-                              "achieved_moved / frac_moved price the launch at the bytes it really moves")
-        roof["limiter"] = ("the sum of a wave's DEPENDENT latencies (vector -> vector, ~220 LDS round trips per plane, scalar <-> vector "
-                           "hand-overs, branches) at 7 waves per SIMD: " + mix + "stage time follows occupancy, not the instruction "
-                           "count (measurements: DESIGN.md 3.2; round 4: a scalar-side selection walk with a third fewer vector "
-                           "instructions per window was 16 % slower); HBM at a sixth of its peak under this kernel")
+    roof = roofline(args, shards, stages, stages_serial, streams, dt_max, g_bytes, comp_bytes) if args.full else None
 
     out = {
         "metric": "variants/sec encode+compress, 3M-variant x 2.5k-sample VCF",
@@ -999,9 +1022,9 @@ def main():
         "stages_ms_per_step_timed_region": {k: v["ms"] / args.steps for k, v in stages.items()},
     }
     dist_or_none = dist if use_dist else None
-    # what follows is collective: a rank whose gate failed takes everybody out of it
-    any_failed = sharding.reduce_job(dist_or_none, 1.0 if failed else 0.0, 0.0, device=dev_for_reduce)[0] > 0
-    if not any_failed and not args.no_legs:
+    # what follows (--full) is collective: a rank whose gate failed takes everybody out of it
+    go_on = args.full and not sharding.reduce_job(dist_or_none, 1.0 if failed else 0.0, 0.0, device=dev_for_reduce)[0] > 0
+    if go_on and not args.no_legs:
         try:
             e2e_chroms = None if args.legs_chroms == "all" else {int(x) for x in args.legs_chroms.split(",") if x}
             fed_chroms = {int(x) for x in args.fed_chroms.split(",") if x}
@@ -1010,7 +1033,7 @@ def main():
         except Exception as e:
             failed = f"ingest legs: {type(e).__name__}: {e}"
             out["host_fed"] = out["e2e"] = {"error": failed}
-    if not any_failed and world > 1 and args.scaling == "strong" and not args.no_weak:
+    if go_on and world > 1 and args.scaling == "strong" and not args.no_weak:
         # secondary: weak scaling — every rank its own 3 M-variant cohort (trivially linear; here so that both shapes
         # come from one run)
         for sh in shards:
@@ -1030,7 +1053,7 @@ def main():
                        "note": "every rank encodes its own cohort (different seeds): per-GPU work fixed"}
         del wshards
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not failed:
+    if args.full and rank == 0 and world == 1 and not failed:
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(shards, S, args.cpu_seconds)
         if not args.no_other_configs and not failed:

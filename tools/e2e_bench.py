@@ -2,7 +2,7 @@
 """End-to-end (inflate- and PCIe-inclusive) rate of the native ingest engine (csrc/ingest.hip): synthetic
 per-chromosome shards of the 3 M x 2504 cohort as files in /dev/shm (BGZF at --level, plain gzip or uncompressed)
 or as text in pinned host memory -> framed chunks back on the host.  Reported next to the HBM-resident number of
-bench.py (which runs the same legs on a bounded sample by default); never bench.py's `value`."""
+bench.py (whose --full run runs the same legs); never bench.py's `value`."""
 import argparse
 import json
 import os

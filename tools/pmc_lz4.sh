@@ -8,9 +8,9 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 R=/root/repo
 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_SMEM SQ_WAVES \
-  --kernel-include-regex k_lz4 --kernel-trace -d $out/a -o a --output-format csv -- python3 $R/bench.py --variants 300000 --steps 1 --warmup 0 --no-overlap --no-cpu-baseline > $out/a.log 2>&1
+  --kernel-include-regex k_lz4 --kernel-trace -d $out/a -o a --output-format csv -- python3 $R/bench.py --full --variants 300000 --steps 1 --warmup 0 --no-overlap --no-cpu-baseline > $out/a.log 2>&1
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM \
-  --kernel-include-regex k_lz4 --kernel-trace -d $out/b -o b --output-format csv -- python3 $R/bench.py --variants 300000 --steps 1 --warmup 0 --no-overlap --no-cpu-baseline > $out/b.log 2>&1
+  --kernel-include-regex k_lz4 --kernel-trace -d $out/b -o b --output-format csv -- python3 $R/bench.py --full --variants 300000 --steps 1 --warmup 0 --no-overlap --no-cpu-baseline > $out/b.log 2>&1
 python3 - <<PY
 import csv, glob, collections
 for s in "ab":
