@@ -104,11 +104,13 @@ class ReferenceGenome:
     def device_bases(self, chrom):
         if chrom not in self._dev:
             if self._store is not None:
-                # one-hot rows -> base letters, on the device (columns are in the store's sorted order)
+                # one-hot rows -> base letters, on the device (columns are in the store's sorted order); an all-zero
+                # row is a base without a column of its own (N in a store written without an N column)
                 m = self._store.contig_meta(chrom)
                 rows = self._store.get_sequence_device(chrom, 0, m["length"])
-                letters = torch.tensor([ord(c) for c in m["columns"]], dtype=torch.uint8, device=rows.device)
-                self._dev[chrom] = letters[rows.argmax(dim=1)].contiguous()
+                letters = torch.tensor([ord(c) for c in m["columns"]] + [ord("N")], dtype=torch.uint8, device=rows.device)
+                col = torch.where(rows.ne(0).any(dim=1), rows.argmax(dim=1), len(m["columns"]))
+                self._dev[chrom] = letters[col].contiguous()
             else:
                 self._dev[chrom] = torch.from_numpy(self.contigs[chrom]).to(self.device)
         return self._dev[chrom]

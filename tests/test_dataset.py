@@ -192,3 +192,117 @@ def test_dataset_reads_fasta_encoder_store(ctx, tmp_path, golden_dir, fixture_te
         want = np.zeros((rows, 5), np.uint8)
         want[np.arange(rows), np.array([b"ACGNT".index(c) for c in up[:rows].tobytes()])] = 1
         assert np.array_equal(first, want)
+
+
+# ---- a normalised VCF: multi-allelic sites split into biallelic records at one POS ---------------------------------
+NORM_SAMPLES, NORM_RECORDS, NORM_REF_LEN, NORM_SPAN = 64, 5000, 1_900_000, 2_000_000
+
+
+def normalised_vcf(rng, ref):
+    """64 samples x 5000 SNP records on chr5, sites spread over [1, 2 Mbp] (past the reference's 1.9 Mbp), 2-3 records
+    at a third of the sites with the reference base as REF and distinct ALTs; GT phased, unphased, missing and allele 2"""
+    names = [f"S{i:02d}" for i in range(NORM_SAMPLES)]
+    sites = np.unique(np.concatenate([[7, 8], rng.integers(1, NORM_SPAN + 1, 3500)]))
+    runs = rng.choice([1, 2, 3], sites.size, p=[0.65, 0.2, 0.15])
+    pos = np.repeat(sites, runs)[:NORM_RECORDS]
+    assert pos.size == NORM_RECORDS
+    gts = np.array(["0|0", "0|1", "1|0", "1|1", "0/1", ".|.", "2|0", "1|2"])
+    g = gts[rng.choice(gts.size, (NORM_RECORDS, NORM_SAMPLES), p=[0.3, 0.2, 0.2, 0.15, 0.05, 0.04, 0.03, 0.03])]
+    lines = ["##fileformat=VCFv4.2", f"##contig=<ID=chr5,length={NORM_SPAN + 1000}>",
+             '##FORMAT=<ID=GT,Number=1,Type=String,Description="Genotype">',
+             "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(names)]
+    prev, used = -1, set()
+    for j, p in enumerate(pos.tolist()):
+        r = chr(ref[p - 1]).upper() if p <= NORM_REF_LEN else "ACGT"[p % 4]
+        r = r if r in "ACGT" else "A"
+        if p != prev:
+            prev, used = p, {r}
+        alt = next(a for a in "ACGT"[j % 4:] + "ACGT" if a not in used)
+        used.add(alt)
+        lines.append(f"chr5\t{p}\t.\t{r}\t{alt}\t.\tPASS\t.\tGT\t" + "\t".join(g[j]))
+    return ("\n".join(lines) + "\n").encode(), names
+
+
+def write_fasta(path, name, seq, width=60):
+    """FASTA of a uint8 array, 60 bases a line, built with numpy"""
+    full = seq.size // width * width
+    body = np.hstack([seq[:full].reshape(-1, width), np.full((full // width, 1), 10, np.uint8)]).reshape(-1)
+    tail = seq[full:].tobytes() + (b"\n" if seq.size > full else b"")
+    with open(path, "wb") as f:
+        f.write(b">" + name.encode() + b" test\n" + body.tobytes() + tail)
+
+
+@pytest.fixture(scope="module")
+def normalised_cohort(ctx, tmp_path_factory):
+    """the normalised VCF converted to a cohort store, its reference as FASTA (an N block at the contig start, lower
+    case, N and IUPAC codes inside) and a BED file with rows near the start (window start clamped to 0), in the middle,
+    across the reference's end and wholly past it"""
+    from haplohyped_varawareml_amd.reader import write_bgzf
+    from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
+    d = tmp_path_factory.mktemp("normalised")
+    rng = np.random.default_rng(55)
+    ref = np.frombuffer(b"ACGTACGTacgtNR", np.uint8)[rng.integers(0, 14, NORM_REF_LEN)]
+    ref[:500] = ord("N")
+    text, names = normalised_vcf(rng, ref)
+    (d / "vcf").mkdir()
+    write_bgzf(str(d / "vcf" / "chr5.filtered.vcf.gz"), text)
+    (d / "samples.txt").write_text("\n".join(names) + "\n")
+    store = VCFtoHDF5Converter("norm", str(d / "vcf"), str(d / "out"), str(d / "samples.txt"), 2, 1).run()
+    write_fasta(d / "ref.fa", "chr5", ref)
+    (d / "regions.bed").write_text("chr5\t100\t200\nchr5\t1000000\t1000100\nchr5\t1899000\t1899500\n"
+                                   "chr5\t1950000\t1950100\n")
+    return dict(dir=d, store=store, text=text, names=names, ref=ref, samples=str(d / "samples.txt"),
+                bed=str(d / "regions.bed"), fasta=str(d / "ref.fa"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seq_length,draws", [(1_048_576, 3), (1000, 6)])
+def test_dataset_normalised_vcf(ctx, normalised_cohort, seq_length, draws):
+    """records that share a POS (the last one in the file wins), > 2048 records in a 1 Mbp window, windows clamped to the
+    contig start and windows past the reference's end, against numpy_expected fed from the oracle"""
+    from haplohyped_varawareml_amd.dataset import RandomHaplotypeDataset
+    from oracle import oracle
+    nc = normalised_cohort
+    o = oracle.vcf_encode(nc["text"], NORM_SAMPLES, region="chr5")
+    assert o["n_kept"] == NORM_RECORDS and int((np.diff(o["start"].astype(np.int64)) == 0).sum()) > 1000
+    ds = RandomHaplotypeDataset(nc["bed"], nc["store"], nc["fasta"], nc["samples"], seed=3, batch_size=4,
+                                seq_length=seq_length, ctx=ctx)
+    seen = []
+    for _ in range(draws):
+        h1, h2 = ds[0]
+        e1, e2 = numpy_expected(ds.last_items, seq_length, None, nc["text"], nc["names"], {"chr5": nc["ref"]})
+        assert np.array_equal(h1.cpu().numpy(), e1) and np.array_equal(h2.cpu().numpy(), e2)
+        seen += ds.last_items
+    assert any(it["start"] == 0 for it in seen)
+    assert any(it["start"] + seq_length > NORM_REF_LEN for it in seen)
+    if seq_length > 2048 * NORM_SPAN // NORM_RECORDS:
+        assert max(it["var_hi"] - it["var_lo"] for it in seen) > 2048
+    ds.close()
+
+
+@pytest.mark.gpu
+def test_dataset_acgt_store_reads_like_the_fasta(ctx, normalised_cohort):
+    """a reference store written with encode_spec="ACGT" has no N column: its N bases are all-zero rows, which the
+    dataset must read back as N (not as the first column, A), exactly as when it reads the FASTA itself"""
+    from haplohyped_varawareml_amd import fasta_encoder
+    from haplohyped_varawareml_amd.dataset import RandomHaplotypeDataset
+    nc = normalised_cohort
+    rg = fasta_encoder.ReferenceGenome(fasta_file=nc["fasta"], encode_spec="ACGT", output_dir=str(nc["dir"] / "acgt"),
+                                       ctx=ctx)
+    h5 = fasta_encoder.HDF5Handler.save_to_hdf5(rg.load_genome_parallel(), str(nc["dir"] / "acgt.h5"))
+    up = np.frombuffer(nc["ref"].tobytes().upper(), np.uint8)
+    want_bases = np.where(np.isin(up, np.frombuffer(b"ACGT", np.uint8)), up, ord("N"))
+    for spec in (None, "ACGT"):
+        got = {}
+        for ref_file in (nc["fasta"], h5):
+            ds = RandomHaplotypeDataset(nc["bed"], nc["store"], ref_file, nc["samples"], encode_spec=spec, seed=11,
+                                        batch_size=4, seq_length=1000, ctx=ctx)
+            got[ref_file] = [tuple(t.cpu() for t in ds[0]) + (ds.last_items,) for _ in range(2)]
+            bases = ds.reference_genome.host_bases("chr5")
+            ds.close()
+        for a, b in zip(got[nc["fasta"]], got[h5]):
+            assert a[2] == b[2]
+            # the windows hold N bases: the N channel (default spec) or all-zero rows ("ACGT")
+            assert bool((a[0][..., 4] == 1).any()) if spec is None else bool((a[0].sum(-1) == 0).any())
+            assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+        assert np.array_equal(bases, want_bases)        # the store's bases, upper case, N for every other letter

@@ -51,3 +51,23 @@ def test_encode_and_store_roundtrip(ctx, tmp_path):
             got = rg.get_sequence(name, a, b)
             assert got.dtype == np.int8 and np.array_equal(got.view(np.uint8), exp[a:min(b, len(s))])
         assert np.array_equal(rg.get_sequence(name, 0, len(s)).sum(axis=1), np.ones(len(s)))
+
+
+@pytest.mark.gpu
+def test_load_chromosome_past_one_kernel_pass(ctx, tmp_path):
+    """a 70 Mbp contig is one hhgt_onehot_bases_u8 call of 350 MB, more than five grid passes of 2^26 bytes: the rows
+    that straddle each pass boundary (2^26 is not a multiple of 5), read back through the store"""
+    from haplohyped_varawareml_amd.fasta_encoder import ReferenceGenome
+    from tests.test_dataset import write_fasta
+    n, step = 70_000_003, 1 << 26
+    rng = np.random.default_rng(70)
+    seq = np.frombuffer(b"ACGTACGTACGTacgtNnR", np.uint8)[rng.integers(0, 19, n)]
+    write_fasta(tmp_path / "big.fa", "chr2", seq)
+    rg = ReferenceGenome(fasta_file=str(tmp_path / "big.fa"), output_dir=str(tmp_path / "store"), ctx=ctx)
+    rg.load_chromosome("chr2")
+    cols = rg.columns()
+    windows = [(t * step // 5 - 3000, t * step // 5 + 3000) for t in range(1, -(-n * 5 // step))]
+    assert len(windows) == 5
+    for a, b in windows + [(0, 4000), (n - 4000, n + 10)]:
+        got = rg.get_sequence("chr2", a, b)
+        assert np.array_equal(got.view(np.uint8), expected_onehot(seq[a:b].tobytes(), cols)), (a, b)
