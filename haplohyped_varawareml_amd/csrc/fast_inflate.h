@@ -352,10 +352,12 @@ static int inflate_impl(const uint8_t *in, size_t in_len, uint8_t *out, size_t o
                     refill(b);
                     const uint32_t e = cltab[b.buf & 127u];
                     const uint32_t l = e & 0xFFu;
-                    if (((e >> 8) & 0xFFu) == X_BAD || l == 0 || b.cnt < l + 7) return -9;
+                    const int sym = (int)(e >> 16);
+                    // the code and its own extra bits only: an 18 (7 extra bits) is not always followed by 7 more bits
+                    const uint32_t xb = sym < 16 ? 0u : (sym == 16 ? 2u : (sym == 17 ? 3u : 7u));
+                    if (((e >> 8) & 0xFFu) == X_BAD || l == 0 || b.cnt < l + xb) return -9;
                     b.buf >>= l;
                     b.cnt -= l;
-                    const int sym = (int)(e >> 16);
                     if (sym < 16) {
                         lens[n++] = (uint8_t)sym;
                     } else {

@@ -23,9 +23,13 @@ struct HuffLane {      // lane L (1..15): canonical-code data of code length L; 
     uint32_t first, cnt, offs;
 };
 
-// lens[0, nsym) (LDS) -> per-length lane data + syms[] (LDS) = symbols sorted by (length, value).  false: over-subscribed.
+// lens[0, nsym) (LDS) -> per-length lane data + syms[] (LDS) = symbols sorted by (length, value).
+// false: an over-subscribed code, or an incomplete one where zlib's inflate_table rejects it — every incomplete code
+// except one code of length 1 (`single`: the literal/length and distance alphabets) and no code at all (`empty`:
+// distances; a block without matches).  Wave-uniform arithmetic on the per-length counts only.
 template <int MAXLEN>
-__device__ __forceinline__ bool huff_build(const uint8_t *lens, uint32_t nsym, uint16_t *syms, HuffLane &t, uint32_t lane)
+__device__ __forceinline__ bool huff_build(const uint8_t *lens, uint32_t nsym, uint16_t *syms, HuffLane &t, uint32_t lane,
+                                           bool single, bool empty)
 {
     uint32_t tot[MAXLEN + 1];
 #pragma unroll
@@ -54,6 +58,8 @@ __device__ __forceinline__ bool huff_build(const uint8_t *lens, uint32_t nsym, u
         }
         off += tot[L];
     }
+    // code space taken, in units of 2^-MAXLEN (the first code of the longest length + the codes of that length)
+    if (code + tot[MAXLEN] != (1u << MAXLEN) && !(single && off == 1u && tot[1] == 1u) && !(empty && off == 0u)) ok = false;
     for (uint32_t base = 0; base < nsym; base += 64u) {
         const uint32_t s = base + lane;
         const uint32_t l = s < nsym ? lens[s] : 0u;
@@ -229,9 +235,10 @@ __global__ __launch_bounds__(256, INF_WGS) void k_inflate_members(const uint8_t 
         HuffLane LL, DD;
         if (btype == 1u) {  // fixed code (RFC 1951 3.2.6)
             for (uint32_t s = lane; s < 288u; s += 64u) lens[s] = s < 144u ? 8 : (s < 256u ? 9 : (s < 280u ? 7 : 8));
-            if (lane < 32u) lens[288u + lane] = lane < 30u ? 5 : 0;
-            huff_build<15>(lens, 288u, ll_syms, LL, lane);
-            huff_build<15>(lens + 288, 32u, dd_syms, DD, lane);
+            // all 32 distance codes are in the fixed code (a complete one); 30 and 31 are rejected where they are decoded
+            if (lane < 32u) lens[288u + lane] = 5;
+            huff_build<15>(lens, 288u, ll_syms, LL, lane, false, false);
+            huff_build<15>(lens + 288, 32u, dd_syms, DD, lane, false, false);
         } else {  // dynamic code (3.2.7)
             refill();
             const uint32_t hlit = take(5) + 257u, hdist = take(5) + 1u, hclen = take(4) + 4u;
@@ -246,7 +253,7 @@ __global__ __launch_bounds__(256, INF_WGS) void k_inflate_members(const uint8_t 
                 if (lane == 0u) lens[clc_order(i)] = (uint8_t)l;
             }
             HuffLane CL;
-            if (!huff_build<7>(lens, 19u, dd_syms, CL, lane)) {
+            if (!huff_build<7>(lens, 19u, dd_syms, CL, lane, false, false)) {
                 err = INF_BAD_TABLE;
                 break;
             }
@@ -313,7 +320,8 @@ __global__ __launch_bounds__(256, INF_WGS) void k_inflate_members(const uint8_t 
                 err = INF_BAD_TABLE;
                 break;
             }
-            if (!huff_build<15>(lens, hlit, ll_syms, LL, lane) || !huff_build<15>(lens + 288, hdist, dd_syms, DD, lane)) {
+            if (!huff_build<15>(lens, hlit, ll_syms, LL, lane, true, false) ||
+                !huff_build<15>(lens + 288, hdist, dd_syms, DD, lane, true, true)) {
                 err = INF_BAD_TABLE;
                 break;
             }

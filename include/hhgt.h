@@ -363,11 +363,12 @@ int hhgt_onehot_bases_u8(hhgt_ctx *ctx, const uint8_t *d_bases, uint64_t n, cons
  * end of the buffer is left for the next call).  HHGT_ERR_MALFORMED if a header is not a BGZF member.
  *
  * hhgt_inflate_members (device): inflates member i from d_src + d_comp_off[i] to d_dst + d_out_off[i]
- * (d_out_off = exclusive prefix sum of isize, computed by the caller).  d_src must be 4-byte aligned and
- * src_bytes a multiple of 4 (pad the upload).  d_status[i] = 0 on success, else a non-zero code
- * (1 block type, 2 stored block, 3 code table, 4 invalid code, 5 distance, 6 output overrun, 7 input overrun,
- * 8 size != ISIZE, 9 CRC-32 of the text != d_crc32[i] — checked by a second kernel when d_crc32 is given, as htslib's
- * bgzf.c does).  *n_bad (host, optional, syncs) = number of members with a non-zero status.
+ * (d_out_off = exclusive prefix sum of isize, computed by the caller; slices may also leave gaps, which stay untouched).
+ * d_src must be 4-byte aligned and src_bytes a multiple of 4 (pad the upload).  d_status[i] = 0 on success, else a
+ * non-zero code (1 block type, 2 stored block, 3 code table: over-subscribed, or incomplete where zlib rejects it,
+ * 4 invalid code, 5 distance, 6 output overrun, 7 input overrun, 8 size != ISIZE, 9 CRC-32 of the text != d_crc32[i] —
+ * checked by a second kernel when d_crc32 is given, as htslib's bgzf.c does).  *n_bad (host, optional, syncs) = number
+ * of members with a non-zero status.
  * ------------------------------------------------------------------------------------------- */
 int hhgt_bgzf_scan(const void *host, uint64_t nbytes, uint64_t max_members, uint64_t *comp_off, uint32_t *comp_len,
                    uint32_t *isize, uint32_t *crc32 /* optional */, uint64_t *n_members, uint64_t *consumed);

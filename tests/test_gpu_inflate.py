@@ -197,6 +197,18 @@ def test_fuzzed_members_terminate_and_stay_in_bounds(ctx):
 def test_converter_with_device_inflate_writes_the_same_h5(ctx, tmp_path, golden_dir, monkeypatch):
     """vcf_to_h5 with HHGT_DEVICE_INFLATE=1: BGZF shards go through the device inflater, the plain-gzip fixture keeps the
     host reader; the cohort file is byte-identical to the one written with the host inflater"""
+    _converter_writes_the_same_h5(tmp_path, golden_dir, monkeypatch, write_bgzf)
+
+
+def test_converter_with_device_inflate_writes_the_same_h5_from_libdeflate(ctx, tmp_path, golden_dir, monkeypatch):
+    """the same with the BGZF shard written as bgzip writes it when it links libdeflate"""
+    from tests import extlibs
+    if not extlibs.have_libdeflate():
+        pytest.skip("libdeflate is not loadable on this box")
+    _converter_writes_the_same_h5(tmp_path, golden_dir, monkeypatch, extlibs.write_bgzf_libdeflate)
+
+
+def _converter_writes_the_same_h5(tmp_path, golden_dir, monkeypatch, write):
     import os
     import shutil
     from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
@@ -204,7 +216,7 @@ def test_converter_with_device_inflate_writes_the_same_h5(ctx, tmp_path, golden_
     vcf_dir.mkdir()
     shutil.copy(os.path.join(golden_dir, "chr22.filtered.vcf.gz"), vcf_dir / "chr22.filtered.vcf.gz")
     names = [l.strip() for l in open(os.path.join(golden_dir, "ipscs_samples_test.txt")) if l.strip()]
-    write_bgzf(str(vcf_dir / "chr4.filtered.vcf.gz"), synth.render_mixed("chr4", 5000, len(names), seed=4, names=names))
+    write(str(vcf_dir / "chr4.filtered.vcf.gz"), synth.render_mixed("chr4", 5000, len(names), seed=4, names=names))
     files = {}
     for mode in ("0", "1"):
         monkeypatch.setenv("HHGT_DEVICE_INFLATE", mode)

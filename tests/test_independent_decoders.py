@@ -1,5 +1,5 @@
 """Which independent decoders ran beside the oracle's own.  The parity tests always decode with the oracle
-(oracle/codec_oracle.c) and, where the base image offers them, ALSO with liblz4, c-blosc and libhdf5 — base-image
+(oracle/codec_oracle.c) and, where the base image offers them, ALSO with liblz4, c-blosc, libdeflate and libhdf5 — base-image
 libraries, neither reference code nor part of this repository.  Those legs are `if present:` branches inside the tests; this
 module makes their presence a visible test outcome in both suites (a skip with its reason instead of a silent pass), and
 tests/conftest.py prints presence and call counts in the header and the summary of every run."""
@@ -7,7 +7,7 @@ import pytest
 
 from tests import extlibs
 
-LEGS = ["liblz4", "c-blosc", "libhdf5"]
+LEGS = ["liblz4", "c-blosc", "libdeflate", "libhdf5"]
 
 
 def _check(leg):
