@@ -26,6 +26,7 @@
 #include <deque>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <thread>
 
 namespace {
@@ -129,7 +130,7 @@ struct TextBuf {   // device-resident text block
     hipEvent_t ready = nullptr, carry_done = nullptr;
     uint64_t nbytes = 0;
     Input *in = nullptr;
-    bool first = false, last = false, end_of_inputs = false;
+    bool first = false, last = false;
     // device-side inflate: per-member status and the count of failures (checked at harvest)
     DevBuf status, bad;
     unsigned long long *h_bad = nullptr;   // pinned
@@ -217,14 +218,18 @@ struct hhgt_ingest {
         std::unique_ptr<uint64_t[]> c_off;
         std::unique_ptr<uint32_t[]> c_len, isz, crc;
         size_t cap = 0;
-        void ensure(size_t n)
+        bool ensure(size_t n)
         {
-            if (n <= cap) return;
-            cap = n + n / 4;
-            c_off.reset(new uint64_t[cap]);
-            c_len.reset(new uint32_t[cap]);
-            isz.reset(new uint32_t[cap]);
-            crc.reset(new uint32_t[cap]);
+            if (n <= cap) return true;
+            cap = 0;
+            const size_t want = n + n / 4;
+            c_off.reset(new (std::nothrow) uint64_t[want]);
+            c_len.reset(new (std::nothrow) uint32_t[want]);
+            isz.reset(new (std::nothrow) uint32_t[want]);
+            crc.reset(new (std::nothrow) uint32_t[want]);
+            if (!c_off || !c_len || !isz || !crc) return false;
+            cap = want;
+            return true;
         }
     } mtab;
     DevBuf crc_x2n;
@@ -297,7 +302,8 @@ void trace(const char *tag, long long a = 0, long long b = 0)
     g_trace.push_back({now_s(), tag, a, b});
 }
 
-void fail(hhgt_ingest *g, int code, const char *msg)
+// records the first error and stops every stage.  Always false, so that an error exit reads `return fail(...)`
+bool fail(hhgt_ingest *g, int code, const char *msg)
 {
     {
         std::lock_guard<std::mutex> lk(g->err_mu);
@@ -316,14 +322,14 @@ void fail(hhgt_ingest *g, int code, const char *msg)
     g->q_ship.close();
     g->q_out.close();
     g->in_cv.notify_all();
+    return false;
 }
 
 #define G_TRY(expr)                                  \
     do {                                             \
         int _rc = (expr);                            \
         if (_rc != HHGT_OK) {                        \
-            fail(g, _rc, hhgt_last_error());         \
-            return false;                            \
+            return fail(g, _rc, hhgt_last_error());  \
         }                                            \
     } while (0)
 #define G_HIP(expr)                                                                                 \
@@ -331,8 +337,7 @@ void fail(hhgt_ingest *g, int code, const char *msg)
         hipError_t _e = (expr);                                                                     \
         if (_e != hipSuccess) {                                                                     \
             hhgt_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            fail(g, HHGT_ERR_HIP, hhgt_last_error());                                               \
-            return false;                                                                           \
+            return fail(g, HHGT_ERR_HIP, hhgt_last_error());                                        \
         }                                                                                           \
     } while (0)
 
@@ -400,6 +405,58 @@ bool wants_device_inflate(int mode, const char *path)
 // ---------------------------------------------------------------------------------------------------------------
 // source thread
 // ---------------------------------------------------------------------------------------------------------------
+// What an early return in this section must not leak.  Each holder's own code is the only place its resource is released.
+struct Fd {
+    int fd = -1;
+    ~Fd() { if (fd >= 0) close(fd); }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    ~Event() { if (e) hipEventDestroy(e); }
+};
+struct Inflater {   // host zlib, raw DEFLATE: one BGZF member per call
+    z_stream zs;
+    Inflater()
+    {
+        memset(&zs, 0, sizeof(zs));
+        inflateInit2(&zs, -15);
+    }
+    ~Inflater() { inflateEnd(&zs); }
+    bool member(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out)
+    {
+        if (inflateReset(&zs) != Z_OK) return false;
+        zs.next_in = const_cast<Bytef *>(src);
+        zs.avail_in = n_in;
+        zs.next_out = dst;
+        zs.avail_out = n_out;
+        return inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0;
+    }
+};
+struct ReaderBlock {   // a pinned block of the reader: it goes back to the reader once its copy has left it (`copied`)
+    hhgt_reader *rd = nullptr;
+    int tok = -1;
+    hipEvent_t copied = nullptr;
+    void release()
+    {
+        if (tok < 0) return;
+        hipEventSynchronize(copied);
+        hhgt_reader_release(rd, tok);
+        tok = -1;
+    }
+    void hold(int t, hipEvent_t ev)   // in place of the block held so far
+    {
+        release();
+        tok = t;
+        copied = ev;
+    }
+    ~ReaderBlock() { release(); }
+};
+
+uint64_t block_bytes(const hhgt_ingest *g, uint64_t dflt)
+{
+    return g->o.block_bytes ? g->o.block_bytes : dflt;
+}
+
 bool push_text(hhgt_ingest *g, int ti)
 {
     trace("src:push_text", ti, (long long)g->text[(size_t)ti].nbytes);
@@ -421,16 +478,43 @@ bool take_text(hhgt_ingest *g, int *ti, size_t need)
         G_HIP(hipMalloc(reinterpret_cast<void **>(&tb.d), need + 256));
         tb.cap = need + 256;
     }
-    tb.first = tb.last = tb.end_of_inputs = false;
-    tb.n_members = 0;
     return true;
+}
+
+// The one hand-off to the driver.  The work that fills the buffer is queued, tb.ready is recorded behind it; every field of the
+// buffer that the driver reads is set here, whatever the buffer's last use left in it.
+bool hand_off(hhgt_ingest *g, int ti, Input *in, uint64_t nbytes, bool first, bool last, uint64_t n_members = 0,
+              uint64_t first_member = 0)
+{
+    TextBuf &tb = g->text[(size_t)ti];
+    tb.nbytes = nbytes;
+    tb.in = in;
+    tb.first = first;
+    tb.last = last;
+    tb.n_members = n_members;
+    tb.first_member = first_member;
+    return push_text(g, ti);
+}
+
+// n bytes of text in host memory -> a text buffer -> the driver.  n = 0: nothing to copy, the (empty) block goes down the pipe
+// all the same.  `copied`: an event of the caller's to record behind the copy, or null
+bool upload_text(hhgt_ingest *g, Input *in, const void *src, uint64_t n, bool first, bool last, hipEvent_t copied)
+{
+    int ti;
+    if (!take_text(g, &ti, (size_t)n + 64)) return false;
+    TextBuf &tb = g->text[(size_t)ti];
+    // (a device-inflated input before this one may still have a carry copy out of this buffer queued on its own stream)
+    if ((n && g->last_carry && hipStreamWaitEvent(g->s_copy, g->last_carry, 0) != hipSuccess) ||
+        (n && hipMemcpyAsync(tb.d, src, n, hipMemcpyHostToDevice, g->s_copy) != hipSuccess) ||
+        hipEventRecord(tb.ready, g->s_copy) != hipSuccess || (copied && hipEventRecord(copied, g->s_copy) != hipSuccess))
+        return fail(g, HHGT_ERR_HIP, "ingest: upload of a text block failed");
+    return hand_off(g, ti, in, n, first, last);
 }
 
 bool open_reader(hhgt_ingest *g, Input *in)
 {
     if (in->rd || in->kind != 0) return true;
-    const uint64_t bb = g->o.block_bytes ? g->o.block_bytes : (64ull << 20);
-    G_TRY(hhgt_reader_open(in->path.c_str(), bb, g->o.n_threads, 6, &in->rd));
+    G_TRY(hhgt_reader_open(in->path.c_str(), block_bytes(g, 64ull << 20), g->o.n_threads, 6, &in->rd));
     in->is_bgzf = hhgt_reader_is_bgzf(in->rd) != 0;
     return true;
 }
@@ -441,8 +525,7 @@ bool set_header(hhgt_ingest *g, Input *in, const uint8_t *p, size_t n, bool at_e
     uint64_t S = 0;
     if (!parse_header_text(p, n, &hb, &S, at_eof)) {
         hhgt_set_error("%s: no #CHROM header line in the first block of the VCF", in->kind ? "<memory>" : in->path.c_str());
-        fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
-        return false;
+        return fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
     }
     in->header.assign(reinterpret_cast<const char *>(p), hb);
     in->header_lines = 0;
@@ -454,95 +537,41 @@ bool set_header(hhgt_ingest *g, Input *in, const uint8_t *p, size_t n, bool at_e
 }
 
 // host reader (BGZF / gzip / plain file): pinned ring -> device text buffers
-bool run_reader_input(hhgt_ingest *g, Input *in)
+bool feed_from_reader(hhgt_ingest *g, Input *in)
 {
-    if (!open_reader(g, in)) return false;
-    hipEvent_t cev[2] = {nullptr, nullptr};
-    G_HIP(hipEventCreateWithFlags(&cev[0], wait_event_flags()));
-    G_HIP(hipEventCreateWithFlags(&cev[1], wait_event_flags()));
-    int prev_tok = -1, k = 0;
-    bool first = true, ok = true;
-    for (;;) {
+    Event cev[2];
+    G_HIP(hipEventCreateWithFlags(&cev[0].e, wait_event_flags()));
+    G_HIP(hipEventCreateWithFlags(&cev[1].e, wait_event_flags()));
+    ReaderBlock prev{in->rd};   // (declared behind the events: it waits on one of them before they are destroyed)
+    bool first = true;
+    for (int k = 0;; ++k) {
         const void *ptr = nullptr;
         uint64_t n = 0;
         int tok = -1, last = 0;
         const int rc = hhgt_reader_acquire(in->rd, &ptr, &n, &tok, &last);
-        if (rc != HHGT_OK) {
-            fail(g, rc, hhgt_last_error());
-            ok = false;
-            break;
+        if (rc != HHGT_OK) return fail(g, rc, hhgt_last_error());
+        if (n == 0 && first) {
+            hhgt_set_error("%s: empty file (no VCF header)", in->path.c_str());
+            return fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
         }
-        if (n == 0) {
-            if (first) {
-                hhgt_set_error("%s: empty file (no VCF header)", in->path.c_str());
-                fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
-                ok = false;
-                break;
-            }
-            // The reader may end a stream with an EMPTY last block (a gzip stream whose text fills a block exactly before
-            // zlib reports the end).  Blocks were already sent without `last`, so an empty one with last = true still has to go
-            // down the pipe: the harvest of THAT block pads and frames the open chunk column and sends INPUT_END — without it
-            // up to vc - 1 variants' genotypes would silently be missing behind their variant-table rows.
-            int ti;
-            if (!take_text(g, &ti, 64)) {
-                ok = false;
-                break;
-            }
-            TextBuf &tb = g->text[(size_t)ti];
-            if (hipEventRecord(tb.ready, g->s_copy) != hipSuccess) {
-                fail(g, HHGT_ERR_HIP, "ingest: event record failed");
-                ok = false;
-                break;
-            }
-            tb.nbytes = 0;
-            tb.in = in;
-            tb.first = false;
-            tb.last = true;
-            if (!push_text(g, ti)) ok = false;
-            break;
-        }
-        if (first && !set_header(g, in, static_cast<const uint8_t *>(ptr), (size_t)n, last != 0)) {
-            ok = false;
-            break;
-        }
-        int ti;
-        if (!take_text(g, &ti, (size_t)n + 64)) {
-            ok = false;
-            break;
-        }
-        TextBuf &tb = g->text[(size_t)ti];
-        // (a device-inflated input before this one may still have a carry copy out of this buffer queued on its own stream)
-        if ((g->last_carry && hipStreamWaitEvent(g->s_copy, g->last_carry, 0) != hipSuccess) ||
-            hipMemcpyAsync(tb.d, ptr, n, hipMemcpyHostToDevice, g->s_copy) != hipSuccess ||
-            hipEventRecord(tb.ready, g->s_copy) != hipSuccess || hipEventRecord(cev[k & 1], g->s_copy) != hipSuccess) {
-            fail(g, HHGT_ERR_HIP, "ingest: upload of a text block failed");
-            ok = false;
-            break;
-        }
-        tb.nbytes = n;
-        tb.in = in;
-        tb.first = first;
-        tb.last = last != 0;
+        // The reader may end a stream with an EMPTY last block (a gzip stream whose text fills a block exactly before
+        // zlib reports the end).  Blocks were already sent without `last`, so an empty one with last = true still has to go
+        // down the pipe: the harvest of THAT block pads and frames the open chunk column and sends INPUT_END — without it
+        // up to vc - 1 variants' genotypes would silently be missing behind their variant-table rows.
+        if (n == 0) return upload_text(g, in, nullptr, 0, false, true, nullptr);
+        if (first && !set_header(g, in, static_cast<const uint8_t *>(ptr), (size_t)n, last != 0)) return false;
+        if (!upload_text(g, in, ptr, n, first, last != 0, cev[k & 1].e)) return false;
         first = false;
-        if (!push_text(g, ti)) {
-            ok = false;
-            break;
-        }
         // the previous pinned block goes back to the reader once its copy has left it
-        if (prev_tok >= 0) {
-            hipEventSynchronize(cev[(k + 1) & 1]);
-            hhgt_reader_release(in->rd, prev_tok);
-        }
-        prev_tok = tok;
-        ++k;
-        if (last) break;
+        prev.hold(tok, cev[k & 1].e);
+        if (last) return true;
     }
-    if (prev_tok >= 0) {
-        hipEventSynchronize(cev[(k + 1) & 1]);
-        hhgt_reader_release(in->rd, prev_tok);
-    }
-    hipEventDestroy(cev[0]);
-    hipEventDestroy(cev[1]);
+}
+
+bool run_reader_input(hhgt_ingest *g, Input *in)
+{
+    if (!open_reader(g, in)) return false;
+    const bool ok = feed_from_reader(g, in);
     uint64_t fb = 0, tbytes = 0;
     hhgt_reader_stats(in->rd, &fb, &tbytes);
     in->st.file_bytes = fb;
@@ -554,40 +583,22 @@ bool run_reader_input(hhgt_ingest *g, Input *in)
 // text already in host memory: cut at line ends, upload
 bool run_memory_input(hhgt_ingest *g, Input *in)
 {
-    const uint64_t bb = g->o.block_bytes ? g->o.block_bytes : (64ull << 20);
+    const uint64_t bb = block_bytes(g, 64ull << 20);
     const uint8_t *p = in->mem;
     const uint64_t N = in->mem_bytes;
-    if (N == 0) {
-        fail(g, HHGT_ERR_MALFORMED, "<memory>: empty text (no VCF header)");
-        return false;
-    }
+    if (N == 0) return fail(g, HHGT_ERR_MALFORMED, "<memory>: empty text (no VCF header)");
     if (!set_header(g, in, p, (size_t)(N < bb ? N : bb), N <= bb)) return false;
     in->st.file_bytes = N;
     uint64_t pos = 0;
-    bool first = true;
     while (pos < N) {
         uint64_t n = N - pos < bb ? N - pos : bb;
         const bool last = pos + n >= N;
         if (!last) {
             const void *nl = memrchr(p + pos, '\n', (size_t)n);
-            if (!nl) {
-                fail(g, HHGT_ERR_IO, "a line is longer than the text block size");
-                return false;
-            }
+            if (!nl) return fail(g, HHGT_ERR_IO, "a line is longer than the text block size");
             n = (uint64_t)((const uint8_t *)nl - (p + pos)) + 1;
         }
-        int ti;
-        if (!take_text(g, &ti, (size_t)n + 64)) return false;
-        TextBuf &tb = g->text[(size_t)ti];
-        if (g->last_carry) G_HIP(hipStreamWaitEvent(g->s_copy, g->last_carry, 0));   // (see run_reader_input)
-        G_HIP(hipMemcpyAsync(tb.d, p + pos, n, hipMemcpyHostToDevice, g->s_copy));
-        G_HIP(hipEventRecord(tb.ready, g->s_copy));
-        tb.nbytes = n;
-        tb.in = in;
-        tb.first = first;
-        tb.last = last;
-        first = false;
-        if (!push_text(g, ti)) return false;
+        if (!upload_text(g, in, p + pos, n, pos == 0, last, nullptr)) return false;
         pos += n;
     }
     return true;
@@ -600,6 +611,17 @@ __global__ void k_count_bad_members(const uint32_t *__restrict__ st, uint64_t n,
     if ((threadIdx.x & 63u) == 0u && m) atomicAdd(out, (unsigned long long)__popcll(m));
 }
 
+bool pread_all(int fd, uint8_t *dst, size_t n, uint64_t off)
+{
+    size_t got = 0;
+    while (got < n) {
+        const ssize_t k = pread(fd, dst + got, n - got, (off_t)(off + got));
+        if (k <= 0) return false;
+        got += (size_t)k;
+    }
+    return true;
+}
+
 // BGZF file inflated on the device: the host walks the member headers and decides the block cuts, the compressed
 // members cross PCIe, one wave per member writes the text (csrc/inflate.hip).
 // Per block the source thread: pread()s the next stretch of the file straight into a pinned staging slot (no mapping:
@@ -608,225 +630,203 @@ __global__ void k_count_bad_members(const uint32_t *__restrict__ st, uint64_t n,
 // writes the member tables behind the compressed bytes and queues upload + carry copy + inflate kernels.  The first
 // blocks of an input are small (the GPU starts after ~1 ms of host work), later ones grow to block_bytes (a launch
 // wants >= 10 k members to fill the chip).
-bool run_device_inflate_input(hhgt_ingest *g, Input *in)
-{
-    const uint64_t bb = g->o.block_bytes ? g->o.block_bytes : (512ull << 20);
-    int fd = open(in->path.c_str(), O_RDONLY);
-    struct stat st;
-    if (fd < 0 || fstat(fd, &st) != 0) {
-        if (fd >= 0) close(fd);
-        hhgt_set_error("cannot open %s", in->path.c_str());
-        fail(g, HHGT_ERR_IO, hhgt_last_error());
-        return false;
-    }
-    const uint64_t flen = (uint64_t)st.st_size;
-    in->st.file_bytes = flen;
-    in->is_bgzf = true;
-    bool ok = true;
-    trace("src:file_open", (long long)flen);
-    z_stream zs;
-    memset(&zs, 0, sizeof(zs));
-    inflateInit2(&zs, -15);
-    std::vector<uint8_t> scratch(65536);
-    uint64_t *c_off = nullptr;
-    uint32_t *c_len = nullptr, *isz = nullptr, *crc = nullptr;
-    auto host_inflate = [&](const uint8_t *base, size_t m, uint8_t *dst) -> bool {
-        if (inflateReset(&zs) != Z_OK) return false;
-        zs.next_in = const_cast<Bytef *>(base + c_off[m]);
-        zs.avail_in = c_len[m];
-        zs.next_out = dst;
-        zs.avail_out = isz[m];
-        return inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0;
-    };
-    auto pread_all = [&](uint8_t *dst, size_t n, uint64_t off) -> bool {
-        size_t got = 0;
-        while (got < n) {
-            const ssize_t k = pread(fd, dst + got, n - got, (off_t)(off + got));
-            if (k <= 0) return false;
-            got += (size_t)k;
-        }
-        return true;
-    };
+// One DeviceInflate per input; a block passes through its steps in the order they stand here (run_device_inflate_input).
+struct DeviceInflate {
+    hhgt_ingest *g;
+    Input *in;
+    Fd file;
+    Inflater z;
+    std::vector<uint8_t> scratch = std::vector<uint8_t>(65536);   // one inflated member
+    uint64_t bb = 0, flen = 0;
     uint64_t fpos = 0;          // file offset of the first member not yet in a block
     uint64_t carry = 0;         // bytes of the previous block behind its last newline
     int prev_ti = -1;
     uint64_t prev_cut = 0;
     bool first = true;
     double ratio = 24.0;        // text bytes per file byte, refined as blocks go by
-    // text budget of the first block: small when nothing is in flight (the GPU starts after ~1 ms of host work instead
-    // of ~5), full size when earlier inputs still keep the device busy (a small launch fills a fraction of the chip)
-    const bool idle = g->free_text.size() == g->text.size() && g->q_text.size() == 0;
-    uint64_t budget = idle ? (bb < (96ull << 20) ? bb : (96ull << 20)) : bb;
-    uint64_t member_index = 0;
-    if (flen == 0) {
-        fail(g, HHGT_ERR_MALFORMED, "empty file (no VCF header)");
-        ok = false;
+    uint64_t budget = 0, member_index = 0;
+    // the block on its way through the steps; each value is set by one step for the steps behind it
+    Staging *stg = nullptr;
+    uint64_t want = 0, nm64 = 0;               // file bytes read into the staging slot, whole members among them
+    size_t nm = 0;                             // members that go into this block
+    uint64_t total = 0, consumed = 0, tail = 0;   // their text bytes and file bytes; text behind the block's last newline
+    bool last = false;
+    int ti = -1;
+    size_t comp_bytes = 0, o_coff = 0, o_ooff = 0, o_clen = 0, o_isz = 0, o_crc = 0, stg_bytes = 0;   // staging layout
+
+    bool host_inflate(size_t m, uint8_t *dst)
+    {
+        return z.member(stg->h.p + g->mtab.c_off[m], g->mtab.c_len[m], dst, g->mtab.isz[m]);
     }
-    while (ok && fpos < flen) {
-        Staging &sg = g->stg[g->stg_next];
+    bool line_too_long() { return fail(g, HHGT_ERR_IO, "a line is longer than the text block: raise block_bytes"); }
+
+    bool open_file()
+    {
+        bb = block_bytes(g, 512ull << 20);
+        file.fd = open(in->path.c_str(), O_RDONLY);
+        struct stat st;
+        if (file.fd < 0 || fstat(file.fd, &st) != 0) {
+            hhgt_set_error("cannot open %s", in->path.c_str());
+            return fail(g, HHGT_ERR_IO, hhgt_last_error());
+        }
+        flen = (uint64_t)st.st_size;
+        in->st.file_bytes = flen;
+        in->is_bgzf = true;
+        trace("src:file_open", (long long)flen);
+        // text budget of the first block: small when nothing is in flight (the GPU starts after ~1 ms of host work instead
+        // of ~5), full size when earlier inputs still keep the device busy (a small launch fills a fraction of the chip)
+        const bool idle = g->free_text.size() == g->text.size() && g->q_text.size() == 0;
+        budget = idle ? (bb < (96ull << 20) ? bb : (96ull << 20)) : bb;
+        if (flen == 0) return fail(g, HHGT_ERR_MALFORMED, "empty file (no VCF header)");
+        return true;
+    }
+
+    // the next stretch of the file -> the next staging slot
+    bool read_stretch()
+    {
+        stg = &g->stg[g->stg_next];
+        Staging &sg = *stg;
         g->stg_next = (g->stg_next + 1) % N_STG;
         if (sg.used) hipEventSynchronize(sg.done);   // the inflate that read this staging slot two blocks ago
         trace("src:staging_free");
         // stretch of the file to look at: what the budget should need, plus slack; at least one whole member
-        uint64_t want = (uint64_t)((double)budget / ratio * 1.15) + (256u << 10);
+        want = (uint64_t)((double)budget / ratio * 1.15) + (256u << 10);
         if (want > flen - fpos) want = flen - fpos;
         const size_t tab_room = (size_t)(want / 26 + 2) * 28 + 64;   // tables live behind the compressed bytes (a member is >= 26 bytes)
-        if (sg.h.ensure((size_t)want + 64 + tab_room) != HHGT_OK) {
-            fail(g, HHGT_ERR_HIP, hhgt_last_error());
-            ok = false;
-            break;
-        }
-        {
-            // one thread copies ~5 GB/s out of the page cache; a 1 GiB text block needs ~40 MB of file
-            const size_t piece = 2u << 20;
-            const int nth = want > 4 * piece ? 4 : 1;
-            std::atomic<size_t> next{0};
-            std::atomic<bool> rd_ok{true};
-            auto work = [&] {
-                for (;;) {
-                    const size_t o = next.fetch_add(piece);
-                    if (o >= want) break;
-                    const size_t n = want - o < piece ? (size_t)(want - o) : piece;
-                    if (!pread_all(sg.h.p + o, n, fpos + o)) rd_ok.store(false);
-                }
-            };
-            std::vector<std::thread> th;
-            for (int i = 1; i < nth; ++i) th.emplace_back(work);
-            work();
-            for (auto &t : th) t.join();
-            if (!rd_ok.load()) {
-                fail(g, HHGT_ERR_IO, "read failed");
-                ok = false;
-                break;
+        if (sg.h.ensure((size_t)want + 64 + tab_room) != HHGT_OK) return fail(g, HHGT_ERR_HIP, hhgt_last_error());
+        // one thread copies ~5 GB/s out of the page cache; a 1 GiB text block needs ~40 MB of file
+        const size_t piece = 2u << 20;
+        const int nth = want > 4 * piece ? 4 : 1;
+        std::atomic<size_t> next{0};
+        std::atomic<bool> rd_ok{true};
+        auto work = [&] {
+            for (;;) {
+                const size_t o = next.fetch_add(piece);
+                if (o >= want) break;
+                const size_t n = want - o < piece ? (size_t)(want - o) : piece;
+                if (!pread_all(file.fd, sg.h.p + o, n, fpos + o)) rd_ok.store(false);
             }
-        }
+        };
+        std::vector<std::thread> th;
+        for (int i = 1; i < nth; ++i) th.emplace_back(work);
+        work();
+        for (auto &t : th) t.join();
+        if (!rd_ok.load()) return fail(g, HHGT_ERR_IO, "read failed");
         trace("src:read_done", (long long)want);
-        // member table of the stretch, cut at the text budget
+        return true;
+    }
+
+    // member table of the stretch, cut at the text budget
+    bool scan_and_cut()
+    {
         const size_t max_m = (size_t)(want / 26 + 2);
-        g->mtab.ensure(max_m);
-        c_off = g->mtab.c_off.get();
-        c_len = g->mtab.c_len.get();
-        isz = g->mtab.isz.get();
-        crc = g->mtab.crc.get();
-        uint64_t nm64 = 0, used = 0;
-        const int rc = hhgt_bgzf_scan(sg.h.p, want, max_m, c_off, c_len, isz, crc, &nm64, &used);
-        if (rc != HHGT_OK) {
-            fail(g, rc, hhgt_last_error());
-            ok = false;
-            break;
-        }
+        if (!g->mtab.ensure(max_m)) return fail(g, HHGT_ERR_IO, "ingest: out of memory for the BGZF member table");
+        uint64_t *c_off = g->mtab.c_off.get();
+        uint32_t *c_len = g->mtab.c_len.get(), *isz = g->mtab.isz.get();
+        uint64_t used = 0;
+        const int rc = hhgt_bgzf_scan(stg->h.p, want, max_m, c_off, c_len, isz, g->mtab.crc.get(), &nm64, &used);
+        if (rc != HHGT_OK) return fail(g, rc, hhgt_last_error());
         if (nm64 == 0) {
-            if (want == flen - fpos) fail(g, HHGT_ERR_MALFORMED, "bytes behind the last whole BGZF member");
-            else fail(g, HHGT_ERR_IO, "a BGZF member larger than the staging stretch");
-            ok = false;
-            break;
+            if (want == flen - fpos) return fail(g, HHGT_ERR_MALFORMED, "bytes behind the last whole BGZF member");
+            return fail(g, HHGT_ERR_IO, "a BGZF member larger than the staging stretch");
         }
-        size_t nm = 0;
-        uint64_t total = 0, consumed = 0;
+        nm = 0;
+        total = consumed = 0;
         while (nm < nm64 && carry + total + isz[nm] <= budget) {
             total += isz[nm];
             consumed = c_off[nm] + c_len[nm] + 8;   // payload + CRC32 + ISIZE
             ++nm;
         }
-        if (nm == 0) {
-            fail(g, HHGT_ERR_IO, "a line is longer than the text block: raise block_bytes");
-            ok = false;
-            break;
-        }
-        const bool last = fpos + consumed >= flen;
+        if (nm == 0) return line_too_long();
+        last = fpos + consumed >= flen;
         trace("src:scan_done", (long long)nm);
-        if (first) {
-            // header: leading members inflated on the host until the '#' lines are complete
-            std::vector<uint8_t> head;
-            bool have = false;
-            for (size_t m = 0; m < nm64 && head.size() < (256u << 20); ++m) {
-                const size_t at = head.size();
-                head.resize(at + isz[m]);
-                if (isz[m] && !host_inflate(sg.h.p, m, head.data() + at)) {
-                    fail(g, HHGT_ERR_IO, "inflate failed (header members)");
-                    ok = false;
-                    break;
-                }
-                size_t hb;
-                uint64_t S;
-                const bool eof = fpos + c_off[m] + c_len[m] + 8 >= flen;
-                if (parse_header_text(head.data(), head.size(), &hb, &S, eof)) {
-                    have = set_header(g, in, head.data(), head.size(), eof);
-                    break;
-                }
-            }
-            if (!ok) break;
-            if (!have) {
-                if (!g->failed.load()) {
-                    hhgt_set_error("%s: no #CHROM header line", in->path.c_str());
-                    fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
-                }
-                ok = false;
+        return true;
+    }
+
+    // header (first block only): leading members inflated on the host until the '#' lines are complete
+    bool read_header()
+    {
+        std::vector<uint8_t> head;
+        bool have = false;
+        for (size_t m = 0; m < nm64 && head.size() < (256u << 20); ++m) {
+            const size_t at = head.size(), isz = g->mtab.isz[m];
+            head.resize(at + isz);
+            if (isz && !host_inflate(m, head.data() + at)) return fail(g, HHGT_ERR_IO, "inflate failed (header members)");
+            size_t hb;
+            uint64_t S;
+            const bool eof = fpos + g->mtab.c_off[m] + g->mtab.c_len[m] + 8 >= flen;
+            if (parse_header_text(head.data(), head.size(), &hb, &S, eof)) {
+                have = set_header(g, in, head.data(), head.size(), eof);
                 break;
             }
         }
-        if (first) trace("src:header_done");
-        // bytes behind the last newline move to the next block: the last member(s) are inflated here to find it
-        uint64_t tail = 0;
-        if (!last) {
-            bool found = false;
-            for (size_t m = nm; m > 0 && !found; --m) {
-                const size_t mm = m - 1;
-                if (isz[mm] == 0) continue;
-                if (!host_inflate(sg.h.p, mm, scratch.data())) {
-                    fail(g, HHGT_ERR_IO, "inflate failed (block tail)");
-                    ok = false;
-                    break;
-                }
-                const void *nl = memrchr(scratch.data(), '\n', isz[mm]);
-                if (nl) {
-                    tail += isz[mm] - ((uint64_t)((const uint8_t *)nl - scratch.data()) + 1);
-                    found = true;
-                } else {
-                    tail += isz[mm];
-                }
-            }
-            if (!ok) break;
-            if (!found) {
-                fail(g, HHGT_ERR_IO, "a line is longer than the text block: raise block_bytes");
-                ok = false;
-                break;
-            }
+        if (!have) {
+            if (g->failed.load()) return false;
+            hhgt_set_error("%s: no #CHROM header line", in->path.c_str());
+            return fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
         }
-        int ti;
-        if (!take_text(g, &ti, (size_t)(carry + total) + 64)) {
-            ok = false;
-            break;
+        trace("src:header_done");
+        return true;
+    }
+
+    // bytes behind the last newline move to the next block: the last member(s) are inflated here to find it
+    bool find_tail()
+    {
+        tail = 0;
+        if (last) return true;
+        for (size_t m = nm; m > 0; --m) {
+            const uint32_t isz = g->mtab.isz[m - 1];
+            if (isz == 0) continue;
+            if (!host_inflate(m - 1, scratch.data())) return fail(g, HHGT_ERR_IO, "inflate failed (block tail)");
+            const void *nl = memrchr(scratch.data(), '\n', isz);
+            if (nl) {
+                tail += isz - ((uint64_t)((const uint8_t *)nl - scratch.data()) + 1);
+                return true;
+            }
+            tail += isz;
         }
+        return line_too_long();
+    }
+
+    // a text buffer for the block, and the staging slot laid out:
+    // [compressed bytes | comp_off u64 | out_off u64 | comp_len u32 | isize u32 | crc u32]
+    bool lay_out_staging()
+    {
+        if (!take_text(g, &ti, (size_t)(carry + total) + 64)) return false;
         TextBuf &tb = g->text[(size_t)ti];
+        Staging &sg = *stg;
         trace("src:took_text", (long long)ti);
-        // staging layout: [compressed bytes | comp_off u64 | out_off u64 | comp_len u32 | isize u32 | crc u32]
-        const size_t comp_bytes = ((size_t)consumed + 3) / 4 * 4 + 4;
-        const size_t o_coff = (comp_bytes + 7) & ~(size_t)7, o_ooff = o_coff + nm * 8, o_clen = o_ooff + nm * 8,
-                     o_isz = o_clen + nm * 4, o_crc = o_isz + nm * 4, stg_bytes = o_crc + nm * 4;
-        if (stg_bytes > sg.h.cap) {
-            fail(g, HHGT_ERR_IO, "ingest: staging slot too small for the member tables");
-            ok = false;
-            break;
-        }
-        if (sg.d.ensure(stg_bytes) != HHGT_OK || tb.status.ensure(nm * 4) != HHGT_OK || tb.bad.ensure(8) != HHGT_OK) {
-            fail(g, HHGT_ERR_HIP, hhgt_last_error());
-            ok = false;
-            break;
-        }
+        comp_bytes = ((size_t)consumed + 3) / 4 * 4 + 4;
+        o_coff = (comp_bytes + 7) & ~(size_t)7;
+        o_ooff = o_coff + nm * 8;
+        o_clen = o_ooff + nm * 8;
+        o_isz = o_clen + nm * 4;
+        o_crc = o_isz + nm * 4;
+        stg_bytes = o_crc + nm * 4;
+        if (stg_bytes > sg.h.cap) return fail(g, HHGT_ERR_IO, "ingest: staging slot too small for the member tables");
+        if (sg.d.ensure(stg_bytes) != HHGT_OK || tb.status.ensure(nm * 4) != HHGT_OK || tb.bad.ensure(8) != HHGT_OK)
+            return fail(g, HHGT_ERR_HIP, hhgt_last_error());
         memset(sg.h.p + consumed, 0, comp_bytes - (size_t)consumed);   // the kernel reads whole dwords
         uint64_t *hc = reinterpret_cast<uint64_t *>(sg.h.p + o_coff), *ho = reinterpret_cast<uint64_t *>(sg.h.p + o_ooff);
         uint32_t *hl = reinterpret_cast<uint32_t *>(sg.h.p + o_clen), *hz = reinterpret_cast<uint32_t *>(sg.h.p + o_isz),
                  *hr = reinterpret_cast<uint32_t *>(sg.h.p + o_crc);
         uint64_t oo = carry;
         for (size_t i = 0; i < nm; ++i) {
-            hc[i] = c_off[i];
+            hc[i] = g->mtab.c_off[i];
             ho[i] = oo;
-            hl[i] = c_len[i];
-            hz[i] = isz[i];
-            hr[i] = crc[i];
-            oo += isz[i];
+            hl[i] = g->mtab.c_len[i];
+            hz[i] = g->mtab.isz[i];
+            hr[i] = g->mtab.crc[i];
+            oo += g->mtab.isz[i];
         }
+        return true;
+    }
+
+    // the block's device work, on the streams it belongs to: nothing but the order of HIP calls lives here
+    bool queue_device_work()
+    {
+        Staging &sg = *stg;
+        TextBuf &tb = g->text[(size_t)ti];
         uint8_t *dd = sg.d.as<uint8_t>();
         hipStream_t si = (g->inf_blocks++ & 1) ? g->s_inf2 : g->s_inf;
         hipError_t e = hipMemcpyAsync(dd, sg.h.p, stg_bytes, hipMemcpyHostToDevice, si);
@@ -843,20 +843,11 @@ bool run_device_inflate_input(hhgt_ingest *g, Input *in)
             if (e == hipSuccess && ti == prev_ti) e = hipStreamWaitEvent(si, tb.carry_done, 0);
         }
         if (e == hipSuccess) e = hipMemsetAsync(tb.bad.p, 0, 8, si);
-        if (e != hipSuccess) {
-            fail(g, HHGT_ERR_HIP, "ingest: upload of compressed members failed");
-            ok = false;
-            break;
-        }
-        const int rc2 = launch_inflate(dd, comp_bytes, reinterpret_cast<const uint64_t *>(dd + o_coff),
-                                       reinterpret_cast<const uint32_t *>(dd + o_clen), reinterpret_cast<const uint64_t *>(dd + o_ooff),
-                                       reinterpret_cast<const uint32_t *>(dd + o_isz), nm, tb.d, tb.cap, tb.status.as<uint32_t>(),
-                                       reinterpret_cast<const uint32_t *>(dd + o_crc), g->crc_x2n.as<uint32_t>(), si);
-        if (rc2 != HHGT_OK) {
-            fail(g, rc2, hhgt_last_error());
-            ok = false;
-            break;
-        }
+        if (e != hipSuccess) return fail(g, HHGT_ERR_HIP, "ingest: upload of compressed members failed");
+        G_TRY(launch_inflate(dd, comp_bytes, reinterpret_cast<const uint64_t *>(dd + o_coff),
+                             reinterpret_cast<const uint32_t *>(dd + o_clen), reinterpret_cast<const uint64_t *>(dd + o_ooff),
+                             reinterpret_cast<const uint32_t *>(dd + o_isz), nm, tb.d, tb.cap, tb.status.as<uint32_t>(),
+                             reinterpret_cast<const uint32_t *>(dd + o_crc), g->crc_x2n.as<uint32_t>(), si));
         hipLaunchKernelGGL(k_count_bad_members, dim3((uint32_t)((nm + 255) / 256)), dim3(256), 0, si, tb.status.as<uint32_t>(),
                            (uint64_t)nm, tb.bad.as<unsigned long long>());
         *tb.h_bad = 0;
@@ -864,31 +855,41 @@ bool run_device_inflate_input(hhgt_ingest *g, Input *in)
         if (e == hipSuccess && carry) e = hipStreamWaitEvent(si, tb.carry_done, 0);
         if (e == hipSuccess) e = hipEventRecord(tb.ready, si);
         if (e == hipSuccess) e = hipEventRecord(sg.done, si);
-        if (e != hipSuccess) {
-            fail(g, HHGT_ERR_HIP, "ingest: device inflate launch failed");
-            ok = false;
-            break;
-        }
+        if (e != hipSuccess) return fail(g, HHGT_ERR_HIP, "ingest: device inflate launch failed");
         sg.used = true;
-        tb.nbytes = carry + total - tail;
-        tb.in = in;
-        tb.first = first;
-        tb.last = last;
-        tb.n_members = nm;
-        tb.first_member = member_index;
+        return true;
+    }
+
+    // the block goes to the driver; where the next one starts, and how much text it may hold
+    bool hand_off_and_advance()
+    {
+        prev_cut = carry + total - tail;
+        if (!hand_off(g, ti, in, prev_cut, first, last, nm, member_index)) return false;
         member_index += nm;
         first = false;
         prev_ti = ti;
-        prev_cut = tb.nbytes;
         carry = tail;
         fpos += consumed;
         if (total && consumed) ratio = 0.5 * ratio + 0.5 * ((double)total / (double)consumed);
         budget = budget * 4 < bb ? budget * 4 : bb;
-        if (!push_text(g, ti)) ok = false;
+        return true;
     }
-    inflateEnd(&zs);
-    close(fd);
-    return ok;
+};
+
+bool run_device_inflate_input(hhgt_ingest *g, Input *in)
+{
+    DeviceInflate d{g, in};
+    if (!d.open_file()) return false;
+    while (d.fpos < d.flen) {
+        if (!d.read_stretch()) return false;
+        if (!d.scan_and_cut()) return false;
+        if (d.first && !d.read_header()) return false;
+        if (!d.find_tail()) return false;
+        if (!d.lay_out_staging()) return false;
+        if (!d.queue_device_work()) return false;
+        if (!d.hand_off_and_advance()) return false;
+    }
+    return true;
 }
 
 void source_main(hhgt_ingest *g)
@@ -1130,14 +1131,12 @@ bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
         const uint32_t code = k < st.size() ? st[k] : 0;
         if (code == 9) hhgt_set_error("BGZF member %llu: CRC-32 of the inflated text differs from the trailer", (unsigned long long)(tb.first_member + k));
         else hhgt_set_error("BGZF member %llu: DEFLATE stream is corrupt (status %u)", (unsigned long long)(tb.first_member + k), code);
-        fail(g, HHGT_ERR_IO, hhgt_last_error());
-        return false;
+        return fail(g, HHGT_ERR_IO, hhgt_last_error());
     }
     if (rec.n_lines_over && !rec.err_density) {
         hhgt_set_error("Error parsing VCF file: %llu more lines than records of %llu samples fit in the block (blank or cut-off lines)",
                        (unsigned long long)rec.n_lines_over, (unsigned long long)in->S_file);
-        fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
-        return false;
+        return fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
     }
     G_TRY(hhgt_encode_result_status(&rec));   // (more than MAX_CHROM_RUNS runs: HHGT_ERR_CAPACITY)
     const uint32_t n_runs = (uint32_t)rec.stats.n_chrom_runs;
@@ -1168,8 +1167,7 @@ bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
     if (b - a > X->kept_per_block) {   // the ring and the variant slots were sized from this bound: never trust it silently
         hhgt_set_error("ingest: a text block kept %llu records, the engine's buffers were sized for %llu (block of %llu bytes)",
                        (unsigned long long)(b - a), (unsigned long long)X->kept_per_block, (unsigned long long)tb.nbytes);
-        fail(g, HHGT_ERR_CAPACITY, hhgt_last_error());
-        return false;
+        return fail(g, HHGT_ERR_CAPACITY, hhgt_last_error());
     }
     g->free_text.push(r.text_idx);   // the text has been consumed: the source may overwrite the buffer
     r.text_idx = -1;
@@ -1426,8 +1424,7 @@ extern "C" int hhgt_ingest_open(hhgt_ctx *ctx, const hhgt_ingest_opts *opts, hhg
     hip(hipStreamCreateWithFlags(&g->s_carry, hipStreamNonBlocking), "stream");
     hip(hipStreamCreateWithPriority(&g->s_out, hipStreamNonBlocking, prio_hi), "stream");
     const bool dev = g->o.device_inflate != 0;
-    const uint64_t bb_host = g->o.block_bytes ? g->o.block_bytes : (64ull << 20);
-    const uint64_t bb_dev = g->o.block_bytes ? g->o.block_bytes : (512ull << 20);
+    const uint64_t bb_host = block_bytes(g, 64ull << 20), bb_dev = block_bytes(g, 512ull << 20);
     const uint64_t bb = dev ? (bb_dev > bb_host ? bb_dev : bb_host) : bb_host;
     g->text.resize(dev ? N_TEXT_DEV : N_TEXT_HOST);
     for (size_t i = 0; i < g->text.size() && rc == HHGT_OK; ++i) {
