@@ -45,6 +45,12 @@ class CountSel(C.Structure):   # hhgt_count_sel
                 ("part", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SampleSel(C.Structure):  # hhgt_sample_sel
+    _fields_ = [("src_ptr", C.c_uint64), ("src_bytes", C.c_uint64), ("row_mask", C.c_uint64), ("out_row", C.c_uint64),
+                ("mask_word", C.c_uint64), ("part", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class EncodeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "n_lines", "n_records", "n_kept", "n_drop_region", "n_drop_filter", "n_haploid_padded",
@@ -123,6 +129,7 @@ def load():
     L.hhgt_decompress_chunks.argtypes = [vp, vp, vp, u64, u64, i32, i32, vp, C.POINTER(u64), vp]
     L.hhgt_decompress_blocks.argtypes = [vp, vp, C.c_uint32, u64, i32, i32, vp, C.POINTER(u64), vp]
     L.hhgt_count_alleles.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, C.POINTER(u64), vp]
+    L.hhgt_count_samples.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, vp, u64, C.POINTER(u64), vp]
     L.hhgt_bgzf_scan.argtypes = [vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.hhgt_inflate_members.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, vp, vp, C.POINTER(u64), vp]
     L.hhgt_onehot_windows.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp, vp]

@@ -1179,3 +1179,47 @@ extern "C" int hhgt_count_alleles(hhgt_ctx *c, const hhgt_count_sel *d_sel, uint
     }
     return HHGT_OK;
 }
+
+extern "C" int hhgt_count_samples(hhgt_ctx *c, const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
+                                  int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
+                                  uint32_t *d_counts, uint64_t n_out, uint64_t *n_bad, void *stream)
+{
+    if (!c || (n_sel && (!d_sel || !d_counts))) {
+        hhgt_set_error("count_samples: null %s", !c ? "context" : !d_sel ? "selection array" : "counts");
+        return HHGT_ERR_ARG;
+    }
+    if (typesize != 2) {
+        hhgt_set_error("count_samples: typesize %d (only 2: one diploid int8 call)", typesize);
+        return HHGT_ERR_ARG;
+    }
+    if (sc < 1 || sc > 64 || vc < 1) {
+        hhgt_set_error("count_samples: chunk of %u samples x %u variants (1 to 64 samples)", sc, vc);
+        return HHGT_ERR_ARG;
+    }
+    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
+    TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
+    if (blocksize > 8192 || ((uint64_t)vc * 2u) % (uint64_t)blocksize) {
+        hhgt_set_error("count_samples: blocksize %d does not cut a row of %u variants into whole blocks of at most 8192 "
+                       "bytes", blocksize, vc);
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n_bad) *n_bad = 0;
+    if (n_sel == 0) return HHGT_OK;
+    TRY(c->dec_bad.ensure(8));
+    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
+    {
+        StageTimer t(c, st, HHGT_STAGE_DECODE);
+        TRY(launch_count_samples(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_counts, n_out,
+                                 c->dec_bad.as<unsigned long long>(), st));
+        t.stop();
+    }
+    if (n_bad) {
+        uint64_t nb = 0;
+        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_bad = nb;
+    }
+    return HHGT_OK;
+}

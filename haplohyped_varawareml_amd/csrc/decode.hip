@@ -370,17 +370,26 @@ __global__ __launch_bounds__(1024) void k_decode_sel(const hhgt_block_sel *__res
 
 // ---- allele counts straight out of LDS (hhgt_count_alleles) ------------------------------------------------------------
 
-// adds the counters of 4 calls to 4 packed byte counters: a, b hold the two alleles of the calls, one call per byte.  After
-// 64 rows no byte exceeds 128, so the packed adds never carry into the next byte.
-__device__ __forceinline__ void count4(uint32_t a, uint32_t b, uint32_t &an, uint32_t &ac, uint32_t &het, uint32_t &hom)
+// classifies 4 calls: a, b hold the two alleles of the calls, one call per byte -> 0x80 in the byte of a call whose allele
+// is called (pa, pb), is 1 (ea, eb), whose alleles differ (ne)
+__device__ __forceinline__ void classify4(uint32_t a, uint32_t b, uint32_t &pa, uint32_t &pb, uint32_t &ea, uint32_t &eb,
+                                          uint32_t &ne)
 {
     const uint32_t H = 0x80808080u, L7 = 0x7F7F7F7Fu;
-    const uint32_t pa = ~a & H, pb = ~b & H;               // 0x80 where the allele is >= 0
+    pa = ~a & H, pb = ~b & H;                              // 0x80 where the allele is >= 0
     const uint32_t xa = a ^ 0x01010101u, xb = b ^ 0x01010101u;
-    const uint32_t ea = ~(((xa & L7) + L7) | xa) & H;      // 0x80 where the allele is 1 (zero-byte test without carries)
-    const uint32_t eb = ~(((xb & L7) + L7) | xb) & H;
+    ea = ~(((xa & L7) + L7) | xa) & H;                     // 0x80 where the allele is 1 (zero-byte test without carries)
+    eb = ~(((xb & L7) + L7) | xb) & H;
     const uint32_t d = a ^ b;
-    const uint32_t ne = (((d & L7) + L7) | d) & H;         // 0x80 where the alleles differ
+    ne = (((d & L7) + L7) | d) & H;                        // 0x80 where the alleles differ
+}
+
+// adds the counters of 4 calls to 4 packed byte counters.  After 64 rows no byte exceeds 128, so the packed adds never
+// carry into the next byte.
+__device__ __forceinline__ void count4(uint32_t a, uint32_t b, uint32_t &an, uint32_t &ac, uint32_t &het, uint32_t &hom)
+{
+    uint32_t pa, pb, ea, eb, ne;
+    classify4(a, b, pa, pb, ea, eb, ne);
     an += (pa >> 7) + (pb >> 7);
     ac += (ea >> 7) + (eb >> 7);
     het += (pa & pb & ne) >> 7;
@@ -392,6 +401,26 @@ __device__ __forceinline__ void count4(uint32_t a, uint32_t b, uint32_t &an, uin
 __device__ __forceinline__ uint32_t stream_byte(const uint8_t *base, uint32_t p, uint32_t neblock, uint32_t sstride)
 {
     return base[p < neblock ? p : sstride + (p - neblock)];
+}
+
+// the calls of variants [v0, v0 + 4) of a block of vb variants in any layout stream_byte reaches -> a, c (first and second
+// alleles, one call per byte; -9 beyond the block: counts nothing).  Allele j of variant v: byte j * vb + v of a shuffled
+// block (doshuffle, not memcpyed), byte 2 v + j of an interleaved one.  The slow path of both count kernels.
+__device__ __forceinline__ void gather4(const uint8_t *base, uint32_t v0, uint32_t vb, uint32_t doshuffle, bool memcpyed,
+                                        uint32_t neblock, uint32_t sstride, uint32_t &a, uint32_t &c)
+{
+    a = 0xF7F7F7F7u, c = 0xF7F7F7F7u;
+#pragma unroll 1
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t v = v0 + j;
+        if (v < vb) {
+            const uint32_t p0 = doshuffle && !memcpyed ? v : 2u * v;
+            const uint32_t p1 = doshuffle && !memcpyed ? vb + v : 2u * v + 1u;
+            const uint32_t sh = 8u * j;
+            a = (a & ~(0xFFu << sh)) | (stream_byte(base, p0, neblock, sstride) << sh);
+            c = (c & ~(0xFFu << sh)) | (stream_byte(base, p1, neblock, sstride) << sh);
+        }
+    }
 }
 
 // grid = n_sel, one selection per workgroup; block = 64 * nwaves (decode_geometry, typesize 2); dynamic LDS = the larger
@@ -464,21 +493,10 @@ __global__ __launch_bounds__(128) void k_count_alleles(const hhgt_count_sel *__r
                     count4(A.w, B.w, acc[k][0][3], acc[k][1][3], acc[k][2][3], acc[k][3][3]);
                 }
             } else {
-                // allele j of variant v: byte j * vb + v of a shuffled block, byte 2 v + j of an interleaved one
 #pragma unroll
                 for (int w = 0; w < 4; ++w) {
-                    uint32_t a = 0xF7F7F7F7u, c = 0xF7F7F7F7u;   // -9 beyond the block: counts nothing
-#pragma unroll 1
-                    for (uint32_t j = 0; j < 4u; ++j) {
-                        const uint32_t v = g + 4u * (uint32_t)w + j;
-                        if (v < vb) {
-                            const uint32_t p0 = h.doshuffle && !memcpyed ? v : 2u * v;
-                            const uint32_t p1 = h.doshuffle && !memcpyed ? vb + v : 2u * v + 1u;
-                            const uint32_t sh = 8u * j;
-                            a = (a & ~(0xFFu << sh)) | (stream_byte(base, p0, neblock, sstride) << sh);
-                            c = (c & ~(0xFFu << sh)) | (stream_byte(base, p1, neblock, sstride) << sh);
-                        }
-                    }
+                    uint32_t a, c;
+                    gather4(base, g + 4u * (uint32_t)w, vb, h.doshuffle, memcpyed, neblock, sstride, a, c);
                     count4(a, c, acc[k][0][w], acc[k][1][w], acc[k][2][w], acc[k][3][w]);
                 }
             }
@@ -517,6 +535,162 @@ __global__ __launch_bounds__(128) void k_count_alleles(const hhgt_count_sel *__r
             const uint32_t x = smem[i];
             if (x) __hip_atomic_fetch_add(out + (4u * (pass0 - lo) + i), x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+    }
+}
+
+// ---- per-sample counts straight out of LDS (hhgt_count_samples) --------------------------------------------------------
+
+// bits 0..3 of n -> 0x80 in bytes 0..3 (the four copies of n sit 7 bits apart, so the products never carry into each other)
+__device__ __forceinline__ uint32_t bits_to_bytes(uint32_t n)
+{
+    return (((n & 0xFu) * 0x00204081u) & 0x01010101u) << 7;
+}
+
+// adds the counters of the calls of a, b (count4's classes) that m selects (0x80 in the byte of a counted call)
+__device__ __forceinline__ void tally4(uint32_t a, uint32_t b, uint32_t m, uint32_t &an, uint32_t &ac, uint32_t &het,
+                                       uint32_t &hom)
+{
+    uint32_t pa, pb, ea, eb, ne;
+    classify4(a, b, pa, pb, ea, eb, ne);
+    pa &= m;
+    ea &= m;
+    an += (uint32_t)__builtin_popcount(pa) + (uint32_t)__builtin_popcount(pb & m);
+    ac += (uint32_t)__builtin_popcount(ea) + (uint32_t)__builtin_popcount(eb & m);
+    het += (uint32_t)__builtin_popcount(pa & pb & ne);
+    hom += (uint32_t)__builtin_popcount(ea & eb);
+}
+
+// sum of x over the wave, the same in every lane: an inclusive scan along each row of 16 lanes (DPP row_shr 1, 2, 4, 8;
+// lanes without a source add 0), then the four row totals read from the last lane of each row
+__device__ __forceinline__ uint32_t wave_sum(uint32_t x)
+{
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 15) + (uint32_t)__builtin_amdgcn_readlane((int)x, 31) +
+           (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+
+// grid = n_sel, one selection per workgroup; block = 64 * nwaves and dynamic LDS as decode_geometry says (typesize 2: two
+// waves).  The variants of a thread are k_count_alleles': [g, g + 16) for g = 16 (t + k blockDim), k = 0, 1.  Which of them
+// count — the range [lo, hi) and the block's bits of vmask — is the same for every row, so it is expanded once, to a byte
+// mask per 4 calls.  Per selected row: decode_block_lds leaves the row's planes in LDS, the thread classifies its calls
+// (count4's classes), masks, popcounts; the four totals of the row travel as two words of 16-bit fields (a block has at
+// most 2 x 4096 alleles, so no field carries) through a DPP reduction to one LDS slot per wave and row.  At the end thread r
+// adds row r's counters to d_counts: at most 4 atomics per row and selection, zeros skipped.
+__global__ __launch_bounds__(128, 8) void k_count_samples(const hhgt_sample_sel *__restrict__ sel, uint32_t sc, uint32_t vc,
+                                                       uint32_t blocksize, uint32_t sstride,
+                                                       const uint32_t *__restrict__ vmask, uint64_t vmask_words,
+                                                       uint32_t *__restrict__ counts, uint64_t n_out,
+                                                       unsigned long long *n_bad)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ uint32_t s_bad;
+    __shared__ uint2 s_rows[2][64];   // [wave][row]: (AN | AC << 16, HET | HOM_ALT << 16) of the wave's variants
+    const uint32_t nwaves = blockDim.x >> 6;
+    const uint32_t wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const hhgt_sample_sel *s = sel + blockIdx.x;
+    // (a chunk lies in global memory: said through the address space, its loads are global_load, not flat_load)
+    const uint8_t *ck = (const uint8_t *)(const __attribute__((address_space(1))) uint8_t *)s->src_ptr;
+    const uint64_t src_bytes = s->src_bytes, mask = s->row_mask, out_row = s->out_row, mask_word = s->mask_word;
+    const uint32_t part = s->part, lo = s->lo, hi = s->hi;
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();
+    const uint32_t avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
+    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
+    const uint32_t vb = blocksize >> 1, parts = vc * 2u / blocksize, mwords = (vb + 31u) >> 5;
+    BloscHdr h;
+    bool ok = blosc_header(ck, avail, chunk_nbytes, 2u, blocksize, h);
+    const uint32_t top = mask ? 63u - (uint32_t)__builtin_clzll(mask) : 0u;      // the highest selected row
+    ok = ok && part < parts && lo < hi && hi <= vb && (sc >= 64u || (mask >> sc) == 0ull) &&
+         (mask == 0ull || (out_row < n_out && top < n_out - out_row)) &&
+         (vmask == nullptr || (mask_word <= vmask_words && mwords <= vmask_words - mask_word));
+    const uint32_t nstreams = block_streams(h, blocksize, blocksize, 2u);   // (every block of such a chunk is whole)
+    ok = ok && nstreams <= nwaves && nwaves <= 2u;
+    if (!ok) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    const bool memcpyed = (h.flags & BLOSC_MEMCPYED) != 0u;
+    const bool shuffled = h.doshuffle && !memcpyed;
+    // the fast form: both planes of a shuffled block split into two streams, 16-byte aligned
+    const bool planes16 = shuffled && nstreams == 2u && (vb & 15u) == 0u;
+    const uint32_t neblock = memcpyed ? blocksize : blocksize / nstreams;
+    uint32_t take[2][4];   // [k][word]: 0x80 in byte j = variant g + 4 w + j is counted
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
+        uint32_t bits = 0u;
+        if (g < hi && g + 16u > lo) {
+            const uint32_t b0 = lo > g ? lo - g : 0u, b1 = hi - g < 16u ? hi - g : 16u;   // [b0, b1) of the 16: 0 <= b0 < b1
+            bits = ((1u << b1) - 1u) & ~((1u << b0) - 1u);
+            if (vmask != nullptr) bits &= vmask[mask_word + (g >> 5)] >> (g & 16u);
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) take[k][w] = bits_to_bytes(bits >> (4 * w));
+    }
+    uint32_t mlo = uni((uint32_t)mask), mhi = uni((uint32_t)(mask >> 32));
+    bool bad = false;
+    while ((mlo | mhi) != 0u) {
+        const uint32_t r = mlo ? (uint32_t)__builtin_ctz(mlo) : 32u + (uint32_t)__builtin_ctz(mhi);
+        if (mlo) mlo &= mlo - 1u;
+        else mhi &= mhi - 1u;
+        const uint32_t b = r * parts + part;
+        if (memcpyed) {
+            // the stored row goes to LDS as one stream, so that the counting below reads one address space
+            const uint8_t *stored = ck + h.hl + (uint64_t)b * blocksize;
+            const uint32_t nd = blocksize >> 2;
+#pragma unroll 1
+            for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) reinterpret_cast<uint32_t *>(smem)[i] = ld32u(stored + 4u * i);
+            if (threadIdx.x < (blocksize & 3u)) smem[4u * nd + threadIdx.x] = stored[4u * nd + threadIdx.x];
+            __syncthreads();
+        } else if (!decode_block_lds(ck, avail, h.hl, b, blocksize, nstreams, sstride, smem, &s_bad)) {
+            bad = true;
+            break;
+        }
+        uint32_t an = 0u, ac = 0u, het = 0u, hom = 0u;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
+            if (planes16) {
+                if (g < vb) {
+                    const uint4 A = *reinterpret_cast<const uint4 *>(smem + g);
+                    const uint4 B = *reinterpret_cast<const uint4 *>(smem + sstride + g);
+                    tally4(A.x, B.x, take[k][0], an, ac, het, hom);
+                    tally4(A.y, B.y, take[k][1], an, ac, het, hom);
+                    tally4(A.z, B.z, take[k][2], an, ac, het, hom);
+                    tally4(A.w, B.w, take[k][3], an, ac, het, hom);
+                }
+            } else {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t a, c;
+                    gather4(smem, g + 4u * (uint32_t)w, vb, h.doshuffle, memcpyed, neblock, sstride, a, c);
+                    tally4(a, c, take[k][w], an, ac, het, hom);
+                }
+            }
+        }
+        const uint32_t t0 = wave_sum(an | (ac << 16)), t1 = wave_sum(het | (hom << 16));
+        if (lane == 0u) s_rows[wave][r] = make_uint2(t0, t1);
+        __syncthreads();   // the planes are read before the next row is decoded over them; every wave's slot is written
+    }
+    if (bad) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    if (threadIdx.x < 64u && ((mask >> threadIdx.x) & 1ull)) {
+        uint2 t = s_rows[0][threadIdx.x];
+        if (nwaves > 1u) {
+            const uint2 u = s_rows[1][threadIdx.x];
+            t.x += u.x;
+            t.y += u.y;
+        }
+        uint32_t *out = counts + (out_row + threadIdx.x) * 4u;
+        const uint32_t v[4] = {t.x & 0xFFFFu, t.x >> 16, t.y & 0xFFFFu, t.y >> 16};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (v[c]) __hip_atomic_fetch_add(out + c, v[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -607,6 +781,24 @@ int launch_count_alleles(const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t s
     }
     hipLaunchKernelGGL(k_count_alleles, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
                        sstride, d_counts, n_out, d_bad);
+    HIP_TRY(hipGetLastError());
+    return HHGT_OK;
+}
+
+int launch_count_samples(const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
+                         const uint32_t *d_vmask, uint64_t vmask_words, uint32_t *d_counts, uint64_t n_out,
+                         unsigned long long *d_bad, hipStream_t st)
+{
+    if (n_sel == 0) return HHGT_OK;
+    uint32_t nwaves, sstride;
+    size_t lds;
+    if (int rc = decode_geometry(2, blocksize, &nwaves, &sstride, &lds)) return rc;   // (blocksize <= 8192: no opt-in needed)
+    if (n_sel > 0x7fffffffu) {
+        hhgt_set_error("count_samples: too many selections");
+        return HHGT_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_count_samples, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
+                       sstride, d_vmask, vmask_words, d_counts, n_out, d_bad);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

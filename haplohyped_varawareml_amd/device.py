@@ -30,6 +30,12 @@ COUNT_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("
                             ("reserved", np.uint32)])
 assert COUNT_SEL_DTYPE.itemsize == C.sizeof(_lib.CountSel) == 48
 
+# hhgt_sample_sel as a numpy record (the layout of _lib.SampleSel)
+SAMPLE_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("row_mask", np.uint64),
+                             ("out_row", np.uint64), ("mask_word", np.uint64), ("part", np.uint32), ("lo", np.uint32),
+                             ("hi", np.uint32), ("reserved", np.uint32)])
+assert SAMPLE_SEL_DTYPE.itemsize == C.sizeof(_lib.SampleSel) == 56
+
 
 def make_ring_layout(n_samples, ring_cols, sc=DEFAULT_SC, vc=DEFAULT_VC):
     """ring of `ring_cols` chunk columns (streaming: kept indices wrap, see include/hhgt.h)"""
@@ -408,6 +414,40 @@ class Context:
             bad = C.c_uint64(0)
             check(self.lib.hhgt_count_alleles(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize,
                                               _ptr(counts), counts.shape[0], C.byref(bad), _stream()))
+        return counts, int(bad.value)
+
+    def count_samples(self, sel, sc, vc, n_out=None, typesize=DEFAULT_TYPESIZE, blocksize=None, vmask=None, counts=None):
+        """per-sample counts (hhgt_count_samples): sel is a numpy structured array of SAMPLE_SEL_DTYPE (device chunk
+        addresses, block `part` of the rows, row mask, variants [lo, hi), out_row of chunk row 0, mask_word), uploaded in
+        one copy.  vmask: None (every variant of the ranges counts) or the variant mask in the block-padded word layout
+        (store.pack_variant_mask): a uint32 numpy array, or an int32 / uint32 device tensor.  The counts are ADDED to
+        `counts`, an int32 tensor [n_out, 4] (AN, AC, HET, HOM_ALT per sample row; default: zeros just large enough for
+        the selections), so calls may accumulate into one buffer.  -> (counts, n_bad)"""
+        if blocksize is None:
+            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
+        sel = np.ascontiguousarray(sel, dtype=SAMPLE_SEL_DTYPE)
+        n = len(sel)
+        with torch.cuda.device(self.device):
+            if counts is None:
+                if n_out is None:
+                    n_out = int(sel["out_row"].max()) + int(sc) if n else 0
+                counts = torch.zeros((int(n_out), 4), dtype=torch.int32, device=self.device)
+            if (counts.dtype not in (torch.int32, torch.uint32) or counts.dim() != 2 or counts.shape[1] != 4
+                    or not counts.is_contiguous()):
+                raise ValueError("counts: a contiguous int32 tensor [n_out, 4]")
+            if vmask is not None:
+                if not torch.is_tensor(vmask):
+                    vmask = torch.from_numpy(np.ascontiguousarray(vmask, dtype=np.uint32).view(np.int32))
+                vmask = vmask.to(self.device)
+                if vmask.dtype not in (torch.int32, torch.uint32) or vmask.dim() != 1 or not vmask.is_contiguous():
+                    raise ValueError("vmask: contiguous uint32 words (store.pack_variant_mask)")
+            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
+            bad = C.c_uint64(0)
+            words = 0 if vmask is None else vmask.numel()
+            if vmask is not None and words == 0:      # (a mask without words is still a mask: every selection is past it)
+                vmask = torch.zeros(1, dtype=torch.int32, device=self.device)
+            check(self.lib.hhgt_count_samples(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize, _ptr(vmask),
+                                              words, _ptr(counts), counts.shape[0], C.byref(bad), _stream()))
         return counts, int(bad.value)
 
     # ---- BGZF on the device (SURVEY §8 f-4) -------------------------------------------------------

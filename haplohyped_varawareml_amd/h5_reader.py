@@ -5,7 +5,9 @@ cohort store.  fetch_genotypes(donor_id, chromosome) returns the reference's per
 fetch_region(donor_id, chromosome, start, end) is the same for the variants with start <= pos < end only: a read of a
 hyperslab, which decodes just the Blosc blocks of those variants (the reference's reader can only read whole datasets).
 allele_frequencies(chromosome, start, end, donor_ids) gives per-variant allele counts and frequencies over the cohort or
-a subset of it, counted on the device (GenotypeStore.allele_counts); the reference has no such query."""
+a subset of it, counted on the device (GenotypeStore.allele_counts); sample_statistics(chromosomes, start, end, donor_ids,
+min_maf, singletons) the same counters per donor, summed over the variants of a region or of a class of variants
+(GenotypeStore.sample_counts): call rate, heterozygosity, singletons carried.  The reference has no such queries."""
 import numpy as np
 
 from .store import AC, AN, HET, HOM_ALT, GenotypeStore
@@ -65,6 +67,57 @@ class VCFH5Reader:
         rec["an"], rec["ac"], rec["het"], rec["hom_alt"] = c[:, AN], c[:, AC], c[:, HET], c[:, HOM_ALT]
         with np.errstate(divide="ignore", invalid="ignore"):
             rec["af"] = np.where(c[:, AN] > 0, c[:, AC] / np.maximum(c[:, AN], 1), np.nan).astype(np.float32)
+        return rec
+
+    def sample_statistics(self, chromosomes=None, start=None, end=None, donor_ids=None, min_maf=None, singletons=False):
+        """per-donor counts over the variants of chr_{N} for N in chromosomes (one name or a list; None: every group), as
+        host numpy records, one per donor in the order asked (default: every sample): sample, n_variants (the variants
+        counted, the same in every row), an (called alleles), ac (alleles equal to 1), het, hom_alt, missing (= 2 *
+        n_variants - an), call_rate (float64 an / (2 * n_variants), NaN when n_variants = 0).  start / end: only the
+        variants whose 0-based start lies in [start, end) — with exactly one chromosome.  min_maf / singletons: only the
+        variants whose minor allele frequency is at least min_maf / whose alternate allele is carried exactly once, both
+        taken over the donors asked for (GenotypeStore.variant_mask over them), computed and applied on the device."""
+        st = self.store
+        if chromosomes is None:
+            chroms = [g[len("chr_"):] for g in st.groups()]
+        else:
+            chroms = [chromosomes] if isinstance(chromosomes, (str, int)) else list(chromosomes)
+        donors = list(st.samples) if donor_ids is None else list(donor_ids)
+        for c in chroms:
+            for d in (st.samples[:1] if donor_ids is None else donors) or st.samples[:1]:     # (the store's own are known)
+                self._group(d, c)
+        if (start is not None or end is not None) and len(chroms) != 1:
+            raise ValueError("sample_statistics: start / end need exactly one chromosome")
+        names = [f"chr_{c}" for c in chroms]
+        who = None if donor_ids is None else donors
+        lo, hi, masks, n_variants = 0, None, {}, 0
+        if start is not None or end is not None:
+            starts = st.variants(names[0])[0].astype(np.int64)
+            lo = 0 if start is None else int(np.searchsorted(starts, start, side="left"))
+            hi = len(starts) if end is None else max(int(np.searchsorted(starts, end, side="left")), lo)
+        for g in names:
+            a, b = (lo, hi) if len(names) == 1 else (0, None)
+            b = st.meta["groups"][g]["n_variants"] if b is None else b
+            if min_maf is not None or singletons:
+                masks[g] = st.variant_mask(g, who, a, b, min_maf=min_maf, min_ac=1 if singletons else None,
+                                           max_ac=1 if singletons else None)
+                n_variants += int(masks[g].sum())
+            else:
+                n_variants += b - a
+        if len(names) == 1:
+            c = st.sample_counts(names[0], who, lo, hi, variant_mask=masks.get(names[0]))
+        else:
+            c = st.sample_counts(names, who, variant_mask=masks or None)
+        c = c.cpu().numpy().astype(np.int64)
+        width = max([len(x.encode()) for x in donors] + [1])
+        rec = np.zeros(len(donors), dtype=[("sample", f"S{width}"), ("n_variants", np.int64), ("an", np.int64),
+                                           ("ac", np.int64), ("het", np.int64), ("hom_alt", np.int64),
+                                           ("missing", np.int64), ("call_rate", np.float64)])
+        rec["sample"] = [x.encode() for x in donors]
+        rec["n_variants"] = n_variants
+        rec["an"], rec["ac"], rec["het"], rec["hom_alt"] = c[:, AN], c[:, AC], c[:, HET], c[:, HOM_ALT]
+        rec["missing"] = 2 * n_variants - c[:, AN]
+        rec["call_rate"] = c[:, AN] / (2.0 * n_variants) if n_variants else np.nan
         return rec
 
     def close(self):

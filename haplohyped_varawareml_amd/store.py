@@ -105,6 +105,57 @@ def plan_counts(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize
     return out[np.lexsort((out["part"], out["scol"], out["vcol"]))]
 
 
+# one selection of the per-sample count planner: plan_counts' cut, with the output row of chunk row 0 and the first word of
+# the block's bits in the packed variant mask
+SAMPLE_PLAN_DTYPE = np.dtype([("vcol", np.int64), ("scol", np.int64), ("part", np.uint32), ("row_mask", np.uint64),
+                              ("lo", np.uint32), ("hi", np.uint32), ("out_row", np.int64), ("mask_word", np.int64)])
+
+
+def mask_words_per_block(blocksize):
+    """uint32 words a Blosc block of blocksize / 2 variants owns in a packed variant mask: its bits start at a word"""
+    return -(-(int(blocksize) // 2) // 32)
+
+
+def plan_sample_counts(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize=None):
+    """the selections of a per-sample count (hhgt_count_samples): plan_counts' cuts of (samples, [v_lo, v_hi)) — the same
+    chunks, blocks, row masks and ranges, in the same order —, where chunk row r of chunk row `scol` is counted into
+    output row scol * sc + r (the sample's index), and the block's mask bits begin at word (vcol * blocks per row + part) *
+    mask_words_per_block(blocksize) of the group's packed variant mask (pack_variant_mask)."""
+    sc, vc = int(sc), int(vc)
+    bs = min(vc * 2, 8192) if blocksize is None else int(blocksize)
+    cut = plan_counts(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize=bs)
+    out = np.zeros(len(cut), SAMPLE_PLAN_DTYPE)
+    for f in ("vcol", "scol", "part", "row_mask", "lo", "hi"):
+        out[f] = cut[f]
+    out["out_row"] = cut["scol"] * sc
+    out["mask_word"] = (cut["vcol"] * (vc * 2 // bs) + cut["part"].astype(np.int64)) * mask_words_per_block(bs)
+    return out
+
+
+def pack_variant_mask(mask, v_lo, n_variants, vc, blocksize):
+    """bool mask [n] over the variants [v_lo, v_lo + n) of a group of n_variants (numpy array or torch tensor, on any
+    device) -> the group's variant mask as hhgt_count_samples reads it: uint32 words (numpy: uint32; torch: int32 on the
+    mask's device, the same bits), mask_words_per_block words per Blosc block of every chunk column, variant v of a block
+    at bit v % 32 of the block's word v // 32.  Variants outside [v_lo, v_lo + n) and the padding are 0."""
+    vc, bs, v_lo, n_variants = int(vc), int(blocksize), int(v_lo), int(n_variants)
+    vb, wpb = bs // 2, mask_words_per_block(bs)
+    n = int(mask.shape[0])
+    if mask.ndim != 1 or not 0 <= v_lo <= v_lo + n <= n_variants:
+        raise IndexError(f"variant mask of shape {tuple(mask.shape)} at {v_lo} outside 0..{n_variants}")
+    n_bits = -(-n_variants // vc) * (vc // vb) * wpb * 32
+    if isinstance(mask, np.ndarray):
+        v = np.arange(v_lo, v_lo + n, dtype=np.int64)
+        bits = np.zeros(n_bits, bool)
+        bits[v // vb * (wpb * 32) + v % vb] = mask.astype(bool)
+        return np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32)
+    import torch
+    v = torch.arange(v_lo, v_lo + n, dtype=torch.int64, device=mask.device)
+    bits = torch.zeros(n_bits, dtype=torch.uint8, device=mask.device)
+    bits[v // vb * (wpb * 32) + v % vb] = mask.to(torch.uint8)
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.uint8, device=mask.device)
+    return (bits.view(-1, 8) * weights).sum(1).to(torch.uint8).view(torch.int32)      # (little-endian words)
+
+
 class StoreWriter:
     def __init__(self, path, samples, sc, vc, typesize=2, cohort_name="", donor_ids=None, chunk_format="blosc2"):
         self.path = path
@@ -193,6 +244,8 @@ class GenotypeStore:
         self.stats = dict(chunks_read=0, compressed_bytes_read=0, blocks_decoded=0, bytes_decoded=0)
         # and of allele_counts: Blosc blocks it decoded, compressed bytes it read from the file (cache hits not included)
         self.stats.update(count_blocks=0, count_compressed_bytes_read=0)
+        # and of sample_counts (which shares count_compressed_bytes_read with it): Blosc blocks it decoded
+        self.stats.update(sample_count_blocks=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -387,11 +440,9 @@ class GenotypeStore:
         counts = torch.zeros((v_hi - v_lo, 4), dtype=torch.int32, device=ctx.device)
         if not len(plan):
             return counts
-        budget = self.cache_bytes if slab_bytes is None else int(slab_bytes)
-        keys = [(group, self._chunk_id(group, int(v), int(c))) for v, c in zip(plan["vcol"], plan["scol"])]
         blocks = np.array([bin(int(m)).count("1") for m in plan["row_mask"]], np.int64)
 
-        def launch(chunks, rows):
+        def launch(chunks, keys, rows):
             dsel = np.zeros(len(rows), COUNT_SEL_DTYPE)
             dsel["src_ptr"] = [chunks[keys[i]].data_ptr() for i in rows]
             dsel["src_bytes"] = [chunks[keys[i]].numel() for i in rows]
@@ -402,7 +453,19 @@ class GenotypeStore:
                 raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
             self.stats["count_blocks"] += int(blocks[rows].sum())
 
-        # selections in plan order (chunk columns in order), cut into slabs; a slab's missing chunks go up in one copy
+        self._scan_slabs(group, plan, slab_bytes, launch)
+        return counts
+
+    def _scan_slabs(self, group, plan, slab_bytes, launch):
+        """the chunk handling of a count over the selections `plan` (vcol / scol per selection, plan order: chunk columns
+        in order) of a group: chunks in the read cache are used as they are, the rest read from the file and uploaded in
+        slabs of at most slab_bytes (default: the cache budget; a larger chunk goes alone), one copy per slab; then
+        launch(chunks, keys, rows) runs the slab's selections — chunks: key -> device tensor, keys[i]: the chunk of
+        selection i, rows: the slab's selections — and must synchronise, for the slab is freed behind it.  The cache is
+        neither filled nor evicted."""
+        budget = self.cache_bytes if slab_bytes is None else int(slab_bytes)
+        keys = [(group, self._chunk_id(group, int(v), int(c))) for v, c in zip(plan["vcol"], plan["scol"])]
+        run = lambda chunks, rows: launch(chunks, keys, rows)
         slab, rows, host, size = {}, [], [], 0
         for i, k in enumerate(keys):
             if k not in slab:
@@ -411,17 +474,16 @@ class GenotypeStore:
                 else:
                     a = self._read_chunk(group, int(plan["vcol"][i]), int(plan["scol"][i]))
                     if host and size + a.size > budget:
-                        self._count_slab(slab, host, rows, launch)
+                        self._count_slab(slab, host, rows, run)
                         slab, rows, host, size = {}, [], [], 0
                     slab[k] = None
                     host.append((k, a))
                     size += a.size
             rows.append(i)
-        self._count_slab(slab, host, rows, launch)
-        return counts
+        self._count_slab(slab, host, rows, run)
 
     def _count_slab(self, slab, host, rows, launch):
-        """uploads the chunks read for one slab of allele_counts in one copy, then runs its selections"""
+        """uploads the chunks read for one slab of a count in one copy, then runs its selections"""
         import torch
         if host:
             cat = np.concatenate([a for _, a in host])
@@ -433,6 +495,94 @@ class GenotypeStore:
             self.stats["count_compressed_bytes_read"] += int(cat.size)
         if rows:
             launch(slab, rows)          # (synchronises: the slab's memory is free to go when this returns)
+
+    def _group_list(self, groups):
+        names = self.groups() if groups is None else [groups] if isinstance(groups, str) else list(groups)
+        for g in names:
+            if g not in self.meta["groups"]:
+                raise KeyError(g)
+        return names
+
+    def sample_counts(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None):
+        """per-sample counts over the variants of `groups` (one name, a list, None = every group): an int32 device tensor
+        [len(samples), 4], columns AN, AC, HET, HOM_ALT as in allele_counts, row i for samples[i] (names or indices; None
+        = every sample in store order; a sample named twice gets the same row twice).  v_lo / v_hi: the variants
+        [v_lo, v_hi) only — with a single group.  variant_mask: count only the variants it marks: a bool tensor or array
+        [v_hi - v_lo] (single group), or a dict group -> mask over the whole group (a group it does not name is counted
+        whole); a device tensor (variant_mask()) never leaves the device.  Missing alleles of a sample are 2 * (variants
+        counted) - AN.  hhgt_count_samples decodes the selected rows' Blosc blocks and reduces each in LDS; no genotype is
+        written anywhere, the groups accumulate into one counter table.  Chunks are handled as in allele_counts: cached
+        ones used, the rest uploaded in slabs of at most slab_bytes, the read cache neither filled nor evicted."""
+        import torch
+        from .device import SAMPLE_SEL_DTYPE
+        ctx = self._context()
+        sc, vc, bs = self.meta["sc"], self.meta["vc"], self._blocksize()
+        names = self._group_list(groups)
+        if len(names) != 1 and (int(v_lo) != 0 or v_hi is not None):
+            raise ValueError("sample_counts: v_lo / v_hi need a single group")
+        if isinstance(variant_mask, dict):
+            for g in variant_mask:
+                if g not in names:
+                    raise KeyError(g)
+            masks = variant_mask
+        elif variant_mask is not None:
+            if len(names) != 1:
+                raise ValueError("sample_counts: one variant_mask needs a single group (several: a dict group -> mask)")
+            masks = {names[0]: variant_mask}
+        else:
+            masks = {}
+        idx = (np.arange(len(self.samples)) if samples is None else
+               np.array([self._sample_index(x) for x in samples], dtype=np.int64).reshape(-1))
+        table = torch.zeros((-(-max(len(self.samples), 1) // sc) * sc, 4), dtype=torch.int32, device=ctx.device)
+        for group in names:
+            n_var = self.meta["groups"][group]["n_variants"]
+            lo, hi = (int(v_lo), n_var if v_hi is None else int(v_hi)) if len(names) == 1 else (0, n_var)
+            if not 0 <= lo <= hi <= n_var:
+                raise IndexError(f"variants [{lo}, {hi}) outside {group} (0..{n_var})")
+            vmask = None
+            if group in masks:
+                m = masks[group]
+                if m.ndim != 1 or int(m.shape[0]) != hi - lo:
+                    raise ValueError(f"variant_mask of {group}: shape {tuple(m.shape)}, expected ({hi - lo},)")
+                vmask = pack_variant_mask(m, lo, n_var, vc, bs)
+                if not torch.is_tensor(vmask):          # a host mask goes up once, not with every slab
+                    vmask = torch.from_numpy(vmask.view(np.int32)).to(ctx.device)
+            plan = plan_sample_counts(idx, len(self.samples), sc, vc, n_var, lo, hi, blocksize=bs)
+            if not len(plan):
+                continue
+            blocks = np.array([bin(int(m)).count("1") for m in plan["row_mask"]], np.int64)
+
+            def launch(chunks, keys, rows, plan=plan, vmask=vmask, group=group, blocks=blocks):
+                dsel = np.zeros(len(rows), SAMPLE_SEL_DTYPE)
+                dsel["src_ptr"] = [chunks[keys[i]].data_ptr() for i in rows]
+                dsel["src_bytes"] = [chunks[keys[i]].numel() for i in rows]
+                for f in ("row_mask", "out_row", "mask_word", "part", "lo", "hi"):
+                    dsel[f] = plan[f][rows]
+                _, bad = ctx.count_samples(dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, vmask=vmask,
+                                           counts=table)
+                if bad:
+                    raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
+                self.stats["sample_count_blocks"] += int(blocks[rows].sum())
+
+            self._scan_slabs(group, plan, slab_bytes, launch)
+        return table[torch.from_numpy(idx).to(ctx.device)]
+
+    def variant_mask(self, group, samples=None, v_lo=0, v_hi=None, min_maf=None, max_ac=None, min_ac=None):
+        """a class of the variants [v_lo, v_hi) of a group, from allele_counts over `samples` (same arguments), as a bool
+        device tensor [v_hi - v_lo] that sample_counts takes as variant_mask; nothing is copied to the host.  A variant
+        is kept iff it passes every bound given: min_maf — AN > 0 and min(AC, AN - AC) >= min_maf * AN, compared as
+        float64 —; min_ac <= AC; AC <= max_ac (integers; singletons: min_ac = max_ac = 1).  No bound: every variant."""
+        import torch
+        c = self.allele_counts(group, samples, v_lo, v_hi)
+        an, ac = c[:, AN].to(torch.int64), c[:, AC].to(torch.int64)
+        keep = torch.ones(c.shape[0], dtype=torch.bool, device=c.device)
+        if min_maf is not None:
+            keep &= (an > 0) & (torch.minimum(ac, an - ac).double() >= float(min_maf) * an.double())
+        if min_ac is not None:
+            keep &= ac >= int(min_ac)
+        if max_ac is not None:
+            keep &= ac <= int(max_ac)
+        return keep
 
     def allele_frequencies(self, group, samples=None, v_lo=0, v_hi=None, slab_bytes=None):
         """AC / AN of allele_counts (same arguments): a float32 device tensor [v_hi - v_lo], NaN where AN == 0"""

@@ -275,6 +275,39 @@ typedef struct {
 int hhgt_count_alleles(hhgt_ctx *ctx, const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
                        int typesize, int blocksize, uint32_t *d_counts, uint64_t n_out, uint64_t *n_bad, void *stream);
 
+/* Per-sample counts, the other direction of the same reduction: the four counters of hhgt_count_alleles (the same
+ * definitions, so the two can be checked against each other), summed over the counted variants of a sample row instead of
+ * over the rows of a variant.  For every selected row r of a selection and its counted variants, with alleles (a, b):
+ *     d_counts[out_row + r][0] AN       [a >= 0] + [b >= 0]
+ *     d_counts[out_row + r][1] AC       [a == 1] + [b == 1]
+ *     d_counts[out_row + r][2] HET      [a >= 0 && b >= 0 && a != b]
+ *     d_counts[out_row + r][3] HOM_ALT  [a == 1 && b == 1]
+ * A selection names a chunk, a block `part` of its rows, the rows and the variants [lo, hi) of that block exactly as a
+ * hhgt_count_sel does; chunk row r goes to row out_row + r of d_counts [n_out][4].  d_vmask (device, optional) restricts
+ * the count to a class of variants: NULL counts every variant of [lo, hi); otherwise variant v of the block is counted
+ * iff lo <= v < hi and bit v % 32 of word d_vmask[mask_word + v / 32] is set.  The bits of a block start at a word
+ * boundary: a block owns ceil(blocksize / 2 / 32) words, whichever of them its variants fill.  The call ADDS to d_counts
+ * (integer agent-scope atomics, at most four per selected row and selection: exact, independent of order), so a host may
+ * split a count over selections, slabs, calls, groups and streams.  Geometries as hhgt_count_alleles (typesize 2,
+ * (vc * 2) % blocksize == 0, blocksize <= 8192, 1 <= sc <= 64), others return HHGT_ERR_ARG.  *n_bad (host, optional,
+ * syncs) = the number of bad selections: invalid chunk header, part past the row's blocks, lo >= hi or hi past the block,
+ * a row bit >= sc, the highest selected row past d_counts (out_row + r >= n_out; a selection without rows is good and
+ * adds nothing), the block's mask words past the mask (mask_word + ceil(blocksize / 64) > vmask_words, with a mask
+ * only), a corrupt stream.  A bad selection adds nothing. */
+typedef struct {
+    uint64_t src_ptr;    /* device address of one framed chunk (either header format)                         */
+    uint64_t src_bytes;  /* its stored size                                                                   */
+    uint64_t row_mask;   /* sample rows of the chunk to count: bit r = row r                                  */
+    uint64_t out_row;    /* row of d_counts that receives chunk row 0 (row r goes to out_row + r)             */
+    uint64_t mask_word;  /* first uint32 word of this block's bits in d_vmask (ignored when d_vmask is NULL)  */
+    uint32_t part;       /* Blosc block of each row (0 .. vc * 2 / blocksize - 1)                             */
+    uint32_t lo, hi;     /* variants [lo, hi) of that block, lo < hi <= blocksize / 2                         */
+    uint32_t reserved;   /* 0 */
+} hhgt_sample_sel;
+int hhgt_count_samples(hhgt_ctx *ctx, const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
+                       int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
+                       uint32_t *d_counts, uint64_t n_out, uint64_t *n_bad, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values
