@@ -10,8 +10,8 @@ LIB_PATH = os.environ.get("HHGT_LIB") or os.path.join(HERE, "libhhgt.so")
 OK = 0
 BLOSC1 = 1
 BLOSC2 = 2
-N_STAGES = 9
-STAGE_NAMES = ["index", "fixed", "encode", "general", "lz4", "frame", "decode", "onehot", "inflate"]
+N_STAGES = 10
+STAGE_NAMES = ["index", "fixed", "encode", "general", "lz4", "frame", "decode", "onehot", "inflate", "pairs"]
 
 
 class HhgtError(RuntimeError):
@@ -49,6 +49,12 @@ class SampleSel(C.Structure):  # hhgt_sample_sel
     _fields_ = [("src_ptr", C.c_uint64), ("src_bytes", C.c_uint64), ("row_mask", C.c_uint64), ("out_row", C.c_uint64),
                 ("mask_word", C.c_uint64), ("part", C.c_uint32), ("lo", C.c_uint32), ("hi", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class PlaneSel(C.Structure):   # hhgt_plane_sel
+    _fields_ = [("src_ptr", C.c_uint64), ("src_bytes", C.c_uint64), ("row_mask", C.c_uint64), ("out_row", C.c_uint64),
+                ("mask_word", C.c_uint64), ("out_word", C.c_uint64), ("part", C.c_uint32), ("lo", C.c_uint32),
+                ("hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class EncodeStats(C.Structure):
@@ -130,6 +136,9 @@ def load():
     L.hhgt_decompress_blocks.argtypes = [vp, vp, C.c_uint32, u64, i32, i32, vp, C.POINTER(u64), vp]
     L.hhgt_count_alleles.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, C.POINTER(u64), vp]
     L.hhgt_count_samples.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, vp, u64, C.POINTER(u64), vp]
+    L.hhgt_genotype_planes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, vp, u64, u64, C.POINTER(u64),
+                                       vp]
+    L.hhgt_pair_counts.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp]
     L.hhgt_bgzf_scan.argtypes = [vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.hhgt_inflate_members.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, vp, vp, C.POINTER(u64), vp]
     L.hhgt_onehot_windows.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp, vp]

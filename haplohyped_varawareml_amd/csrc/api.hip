@@ -1223,3 +1223,74 @@ extern "C" int hhgt_count_samples(hhgt_ctx *c, const hhgt_sample_sel *d_sel, uin
     }
     return HHGT_OK;
 }
+
+extern "C" int hhgt_genotype_planes(hhgt_ctx *c, const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
+                                  int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
+                                  uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t *n_bad,
+                                    void *stream)
+{
+    if (!c || (n_sel && (!d_sel || !d_planes))) {
+        hhgt_set_error("genotype_planes: null %s", !c ? "context" : !d_sel ? "selection array" : "planes");
+        return HHGT_ERR_ARG;
+    }
+    if (typesize != 2) {
+        hhgt_set_error("genotype_planes: typesize %d (only 2: one diploid int8 call)", typesize);
+        return HHGT_ERR_ARG;
+    }
+    if (sc < 1 || sc > 64 || vc < 1) {
+        hhgt_set_error("genotype_planes: chunk of %u samples x %u variants (1 to 64 samples)", sc, vc);
+        return HHGT_ERR_ARG;
+    }
+    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
+    TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
+    if (blocksize > 8192 || ((uint64_t)vc * 2u) % (uint64_t)blocksize) {
+        hhgt_set_error("genotype_planes: blocksize %d does not cut a row of %u variants into whole blocks of at most 8192 "
+                       "bytes", blocksize, vc);
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n_bad) *n_bad = 0;
+    if (n_sel == 0) return HHGT_OK;
+    TRY(c->dec_bad.ensure(8));
+    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
+    {
+        StageTimer t(c, st, HHGT_STAGE_DECODE);
+        TRY(launch_genotype_planes(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_planes, n_rows, row_words,
+                                   c->dec_bad.as<unsigned long long>(), st));
+        t.stop();
+    }
+    if (n_bad) {
+        uint64_t nb = 0;
+        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_bad = nb;
+    }
+    return HHGT_OK;
+}
+
+extern "C" int hhgt_pair_counts(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
+                                uint64_t w_hi, uint32_t *d_table, void *stream)
+{
+    const bool work = n_rows && w_lo < w_hi;
+    if (!c || (work && (!d_planes || !d_table))) {
+        hhgt_set_error("pair_counts: null %s", !c ? "context" : !d_planes ? "planes" : "table");
+        return HHGT_ERR_ARG;
+    }
+    if (w_lo > w_hi || w_hi > row_words || n_rows > 64ull * 65535ull) {
+        hhgt_set_error("pair_counts: words [%llu, %llu) of rows of %llu words, %llu rows", (unsigned long long)w_lo,
+                       (unsigned long long)w_hi, (unsigned long long)row_words, (unsigned long long)n_rows);
+        return HHGT_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(d_table) & 15u) {
+        hhgt_set_error("pair_counts: the table must be 16-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!work) return HHGT_OK;
+    StageTimer t(c, st, HHGT_STAGE_PAIRS);
+    TRY(launch_pair_counts(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_table, st));
+    t.stop();
+    return HHGT_OK;
+}

@@ -276,6 +276,12 @@ int launch_count_alleles(const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t s
 int launch_count_samples(const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
                          const uint32_t *d_vmask, uint64_t vmask_words, uint32_t *d_counts, uint64_t n_out,
                          unsigned long long *d_bad, hipStream_t st);
+int launch_genotype_planes(const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
+                           const uint32_t *d_vmask, uint64_t vmask_words, uint32_t *d_planes, uint64_t n_rows,
+                           uint64_t row_words, unsigned long long *d_bad, hipStream_t st);
+// pairs.hip
+int launch_pair_counts(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
+                       uint32_t *d_table, hipStream_t st);
 int launch_inflate(const uint8_t *d_src, uint64_t src_bytes, const uint64_t *d_comp_off, const uint32_t *d_comp_len,
                    const uint64_t *d_out_off, const uint32_t *d_isize, uint64_t n_members, uint8_t *d_dst,
                    uint64_t dst_bytes, uint32_t *d_status, const uint32_t *d_crc32, const uint32_t *d_x2n, hipStream_t st);

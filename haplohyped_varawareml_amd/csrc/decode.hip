@@ -694,6 +694,150 @@ __global__ __launch_bounds__(128, 8) void k_count_samples(const hhgt_sample_sel 
     }
 }
 
+// ---- genotype bit planes straight out of LDS (hhgt_genotype_planes) ----------------------------------------------------
+
+// 0x80 in the bytes of m that have it -> bits 0..3 (byte j -> bit j; the four shifted copies never meet below bit 28)
+__device__ __forceinline__ uint32_t bytes_to_bits(uint32_t m)
+{
+    return (((m >> 7) * 0x01020408u) >> 24) & 0xFu;
+}
+
+// classifies 4 calls (a, b as classify4 takes them) that m selects and adds their bits, at `sh`, to the three planes: a call
+// is complete iff both alleles are 0 or 1, and then HET (0/1, 1/0), HOM_REF (0/0) or HOM_ALT (1/1)
+__device__ __forceinline__ void planes4(uint32_t a, uint32_t b, uint32_t m, uint32_t sh, uint32_t &het, uint32_t &ref,
+                                        uint32_t &alt)
+{
+    const uint32_t H = 0x80808080u, L7 = 0x7F7F7F7Fu;
+    const uint32_t xa = a ^ 0x01010101u, xb = b ^ 0x01010101u;
+    const uint32_t za = ~(((a & L7) + L7) | a) & H, zb = ~(((b & L7) + L7) | b) & H;        // 0x80 where the allele is 0
+    const uint32_t ea = ~(((xa & L7) + L7) | xa) & H, eb = ~(((xb & L7) + L7) | xb) & H;    // 0x80 where the allele is 1
+    het |= bytes_to_bits(((za & eb) | (ea & zb)) & m) << sh;
+    ref |= bytes_to_bits(za & zb & m) << sh;
+    alt |= bytes_to_bits(ea & eb & m) << sh;
+}
+
+// grid = n_sel, one selection per workgroup; block, dynamic LDS, the variants of a thread ([g, g + 16) for g = 16 (t + k
+// blockDim), k = 0, 1) and the take[][] expansion of range and variant mask as k_count_samples.  Per selected row the thread
+// turns its 16 calls into 16 bits of each plane; lanes 2 i and 2 i + 1 hold the halves of word (t + k blockDim) / 2 of the
+// block, the odd lane's half crosses over with one DPP quad_perm, and the even lane stores the word of each plane — plain
+// vector stores: a (row, block) belongs to one workgroup.  A stream that turns out corrupt after some rows were written gets
+// those rows' words zeroed again (the caller's buffer was zero there), so a bad selection leaves nothing behind.
+__global__ __launch_bounds__(128, 8) void k_genotype_planes(const hhgt_plane_sel *__restrict__ sel, uint32_t sc, uint32_t vc,
+                                                            uint32_t blocksize, uint32_t sstride,
+                                                            const uint32_t *__restrict__ vmask, uint64_t vmask_words,
+                                                            uint32_t *__restrict__ planes, uint64_t n_rows,
+                                                            uint64_t row_words, unsigned long long *n_bad)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ uint32_t s_bad;
+    const uint32_t nwaves = blockDim.x >> 6;
+    const hhgt_plane_sel *s = sel + blockIdx.x;
+    const uint8_t *ck = (const uint8_t *)(const __attribute__((address_space(1))) uint8_t *)s->src_ptr;
+    const uint64_t src_bytes = s->src_bytes, mask = s->row_mask, out_row = s->out_row, mask_word = s->mask_word;
+    const uint64_t out_word = s->out_word;
+    const uint32_t part = s->part, lo = s->lo, hi = s->hi;
+    if (threadIdx.x == 0) s_bad = 0;
+    __syncthreads();
+    const uint32_t avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
+    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
+    const uint32_t vb = blocksize >> 1, parts = vc * 2u / blocksize, mwords = (vb + 31u) >> 5;
+    BloscHdr h;
+    bool ok = blosc_header(ck, avail, chunk_nbytes, 2u, blocksize, h);
+    const uint32_t top = mask ? 63u - (uint32_t)__builtin_clzll(mask) : 0u;      // the highest selected row
+    ok = ok && part < parts && lo < hi && hi <= vb && (sc >= 64u || (mask >> sc) == 0ull) &&
+         (mask == 0ull || (out_row < n_rows && top < n_rows - out_row)) &&
+         out_word <= row_words && mwords <= row_words - out_word &&
+         (vmask == nullptr || (mask_word <= vmask_words && mwords <= vmask_words - mask_word));
+    const uint32_t nstreams = block_streams(h, blocksize, blocksize, 2u);   // (every block of such a chunk is whole)
+    ok = ok && nstreams <= nwaves && nwaves <= 2u;
+    if (!ok) {
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        return;
+    }
+    const bool memcpyed = (h.flags & BLOSC_MEMCPYED) != 0u;
+    const bool shuffled = h.doshuffle && !memcpyed;
+    const bool planes16 = shuffled && nstreams == 2u && (vb & 15u) == 0u;
+    const uint32_t neblock = memcpyed ? blocksize : blocksize / nstreams;
+    uint32_t take[2][4];   // [k][word]: 0x80 in byte j = variant g + 4 w + j is counted
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
+        uint32_t bits = 0u;
+        if (g < hi && g + 16u > lo) {
+            const uint32_t b0 = lo > g ? lo - g : 0u, b1 = hi - g < 16u ? hi - g : 16u;   // [b0, b1) of the 16: 0 <= b0 < b1
+            bits = ((1u << b1) - 1u) & ~((1u << b0) - 1u);
+            if (vmask != nullptr) bits &= vmask[mask_word + (g >> 5)] >> (g & 16u);
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) take[k][w] = bits_to_bytes(bits >> (4 * w));
+    }
+    const uint64_t plane_words = n_rows * row_words;
+    uint32_t mlo = uni((uint32_t)mask), mhi = uni((uint32_t)(mask >> 32));
+    uint32_t bad_row = 64u;   // the row whose stream was corrupt
+    while ((mlo | mhi) != 0u) {
+        const uint32_t r = mlo ? (uint32_t)__builtin_ctz(mlo) : 32u + (uint32_t)__builtin_ctz(mhi);
+        if (mlo) mlo &= mlo - 1u;
+        else mhi &= mhi - 1u;
+        const uint32_t b = r * parts + part;
+        if (memcpyed) {
+            // the stored row goes to LDS as one stream, so that the classification below reads one address space
+            const uint8_t *stored = ck + h.hl + (uint64_t)b * blocksize;
+            const uint32_t nd = blocksize >> 2;
+#pragma unroll 1
+            for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) reinterpret_cast<uint32_t *>(smem)[i] = ld32u(stored + 4u * i);
+            if (threadIdx.x < (blocksize & 3u)) smem[4u * nd + threadIdx.x] = stored[4u * nd + threadIdx.x];
+            __syncthreads();
+        } else if (!decode_block_lds(ck, avail, h.hl, b, blocksize, nstreams, sstride, smem, &s_bad)) {
+            bad_row = r;
+            break;
+        }
+        uint32_t *row = planes + (out_row + r) * row_words + out_word;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t t = threadIdx.x + blockDim.x * (uint32_t)k, g = 16u * t;
+            uint32_t het = 0u, ref = 0u, alt = 0u;
+            if (planes16) {
+                if (g < vb) {
+                    const uint4 A = *reinterpret_cast<const uint4 *>(smem + g);
+                    const uint4 B = *reinterpret_cast<const uint4 *>(smem + sstride + g);
+                    planes4(A.x, B.x, take[k][0], 0u, het, ref, alt);
+                    planes4(A.y, B.y, take[k][1], 4u, het, ref, alt);
+                    planes4(A.z, B.z, take[k][2], 8u, het, ref, alt);
+                    planes4(A.w, B.w, take[k][3], 12u, het, ref, alt);
+                }
+            } else if (g < vb) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    uint32_t a, c;
+                    gather4(smem, g + 4u * (uint32_t)w, vb, h.doshuffle, memcpyed, neblock, sstride, a, c);
+                    planes4(a, c, take[k][w], 4u * (uint32_t)w, het, ref, alt);
+                }
+            }
+            // the neighbour's 16 bits of each plane (quad_perm [1, 0, 3, 2]); every lane of the wave is here
+            const uint32_t hr = het | (ref << 16);
+            const uint32_t nhr = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hr, 0xB1, 0xf, 0xf, false);
+            const uint32_t nalt = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)alt, 0xB1, 0xf, 0xf, false);
+            const uint32_t w = t >> 1;
+            if (!(t & 1u) && w < mwords) {
+                row[w] = het | (nhr << 16);
+                row[plane_words + w] = ref | (nhr & 0xFFFF0000u);
+                row[2u * plane_words + w] = alt | (nalt << 16);
+            }
+        }
+        __syncthreads();   // the planes are read before the next row is decoded (or copied) over them
+    }
+    if (bad_row < 64u) {
+        // rows below the corrupt one were written: back to the zeros the caller put there
+        __syncthreads();
+        for (uint32_t r = 0; r < bad_row; ++r) {
+            if (!((mask >> r) & 1ull)) continue;
+            uint32_t *row = planes + (out_row + r) * row_words + out_word;
+            for (uint32_t w = threadIdx.x; w < mwords; w += blockDim.x) row[w] = row[plane_words + w] = row[2u * plane_words + w] = 0u;
+        }
+        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+    }
+}
+
 // launch shape shared by both kernels: waves per workgroup, the per-stream LDS stride, dynamic LDS bytes
 static int decode_geometry(int typesize, int blocksize, uint32_t *nwaves, uint32_t *sstride, size_t *lds)
 {
@@ -799,6 +943,24 @@ int launch_count_samples(const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t 
     }
     hipLaunchKernelGGL(k_count_samples, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
                        sstride, d_vmask, vmask_words, d_counts, n_out, d_bad);
+    HIP_TRY(hipGetLastError());
+    return HHGT_OK;
+}
+
+int launch_genotype_planes(const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
+                           const uint32_t *d_vmask, uint64_t vmask_words, uint32_t *d_planes, uint64_t n_rows,
+                           uint64_t row_words, unsigned long long *d_bad, hipStream_t st)
+{
+    if (n_sel == 0) return HHGT_OK;
+    uint32_t nwaves, sstride;
+    size_t lds;
+    if (int rc = decode_geometry(2, blocksize, &nwaves, &sstride, &lds)) return rc;   // (blocksize <= 8192: no opt-in needed)
+    if (n_sel > 0x7fffffffu) {
+        hhgt_set_error("genotype_planes: too many selections");
+        return HHGT_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_genotype_planes, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
+                       sstride, d_vmask, vmask_words, d_planes, n_rows, row_words, d_bad);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

@@ -36,6 +36,12 @@ SAMPLE_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), (
                              ("hi", np.uint32), ("reserved", np.uint32)])
 assert SAMPLE_SEL_DTYPE.itemsize == C.sizeof(_lib.SampleSel) == 56
 
+# hhgt_plane_sel as a numpy record (the layout of _lib.PlaneSel)
+PLANE_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("row_mask", np.uint64),
+                            ("out_row", np.uint64), ("mask_word", np.uint64), ("out_word", np.uint64),
+                            ("part", np.uint32), ("lo", np.uint32), ("hi", np.uint32), ("reserved", np.uint32)])
+assert PLANE_SEL_DTYPE.itemsize == C.sizeof(_lib.PlaneSel) == 64
+
 
 def make_ring_layout(n_samples, ring_cols, sc=DEFAULT_SC, vc=DEFAULT_VC):
     """ring of `ring_cols` chunk columns (streaming: kept indices wrap, see include/hhgt.h)"""
@@ -449,6 +455,61 @@ class Context:
             check(self.lib.hhgt_count_samples(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize, _ptr(vmask),
                                               words, _ptr(counts), counts.shape[0], C.byref(bad), _stream()))
         return counts, int(bad.value)
+
+    def genotype_planes(self, sel, sc, vc, n_rows=None, row_words=None, typesize=DEFAULT_TYPESIZE, blocksize=None,
+                        vmask=None, planes=None):
+        """genotype bit planes (hhgt_genotype_planes): sel is a numpy structured array of PLANE_SEL_DTYPE (a sample
+        selection plus out_word), uploaded in one copy; vmask as count_samples takes it.  planes: an int32 tensor
+        [3, n_rows, row_words] (HET, HOM_REF, HOM_ALT; 32 variants per word) that the caller has zeroed where the
+        selections write; default: zeros just large enough for them.  -> (planes, n_bad)"""
+        if blocksize is None:
+            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
+        sel = np.ascontiguousarray(sel, dtype=PLANE_SEL_DTYPE)
+        n = len(sel)
+        with torch.cuda.device(self.device):
+            if planes is None:
+                if n_rows is None:
+                    n_rows = int(sel["out_row"].max()) + int(sc) if n else 0
+                if row_words is None:
+                    row_words = int(sel["out_word"].max()) + -(-(int(blocksize) // 2) // 32) if n else 0
+                planes = torch.zeros((3, int(n_rows), int(row_words)), dtype=torch.int32, device=self.device)
+            if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
+                    or not planes.is_contiguous()):
+                raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
+            if vmask is not None:
+                if not torch.is_tensor(vmask):
+                    vmask = torch.from_numpy(np.ascontiguousarray(vmask, dtype=np.uint32).view(np.int32))
+                vmask = vmask.to(self.device)
+                if vmask.dtype not in (torch.int32, torch.uint32) or vmask.dim() != 1 or not vmask.is_contiguous():
+                    raise ValueError("vmask: contiguous uint32 words (store.pack_variant_mask)")
+            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
+            bad = C.c_uint64(0)
+            words = 0 if vmask is None else vmask.numel()
+            if vmask is not None and words == 0:      # (a mask without words is still a mask: every selection is past it)
+                vmask = torch.zeros(1, dtype=torch.int32, device=self.device)
+            check(self.lib.hhgt_genotype_planes(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize, _ptr(vmask),
+                                                words, _ptr(planes) if planes.numel() else None, planes.shape[1],
+                                                planes.shape[2], C.byref(bad), _stream()))
+        return planes, int(bad.value)
+
+    def pair_counts(self, planes, w_lo=0, w_hi=None, table=None):
+        """pairwise counts (hhgt_pair_counts) over the words [w_lo, w_hi) (default: all) of genotype planes [3, n, words]:
+        ADDED to `table`, an int32 tensor [n, n, 4] (NSNP, HETHET, IBS0, HET1 per ordered pair of rows; default: zeros),
+        on the current stream — calls on one stream may accumulate into one table.  -> table"""
+        if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
+                or not planes.is_contiguous()):
+            raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
+        n, words = int(planes.shape[1]), int(planes.shape[2])
+        w_hi = words if w_hi is None else int(w_hi)
+        with torch.cuda.device(self.device):
+            if table is None:
+                table = torch.zeros((n, n, 4), dtype=torch.int32, device=self.device)
+            if (table.dtype not in (torch.int32, torch.uint32) or tuple(table.shape) != (n, n, 4)
+                    or not table.is_contiguous()):
+                raise ValueError(f"table: a contiguous int32 tensor [{n}, {n}, 4]")
+            check(self.lib.hhgt_pair_counts(self.h, _ptr(planes) if planes.numel() else None, n, words, int(w_lo), w_hi,
+                                            _ptr(table) if table.numel() else None, _stream()))
+        return table
 
     # ---- BGZF on the device (SURVEY §8 f-4) -------------------------------------------------------
     def inflate_bgzf(self, raw, return_status=False, check_crc=True):

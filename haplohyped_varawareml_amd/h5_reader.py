@@ -7,10 +7,12 @@ hyperslab, which decodes just the Blosc blocks of those variants (the reference'
 allele_frequencies(chromosome, start, end, donor_ids) gives per-variant allele counts and frequencies over the cohort or
 a subset of it, counted on the device (GenotypeStore.allele_counts); sample_statistics(chromosomes, start, end, donor_ids,
 min_maf, singletons) the same counters per donor, summed over the variants of a region or of a class of variants
-(GenotypeStore.sample_counts): call rate, heterozygosity, singletons carried.  The reference has no such queries."""
+(GenotypeStore.sample_counts): call rate, heterozygosity, singletons carried; relatedness(chromosomes, donor_ids, min_maf,
+min_kinship) the pairwise counts and the KING-robust kinship of every pair of donors (GenotypeStore.pair_counts).  The
+reference has no such queries."""
 import numpy as np
 
-from .store import AC, AN, HET, HOM_ALT, GenotypeStore
+from .store import AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, kinship_from_counts
 
 
 class VCFH5Reader:
@@ -118,6 +120,46 @@ class VCFH5Reader:
         rec["an"], rec["ac"], rec["het"], rec["hom_alt"] = c[:, AN], c[:, AC], c[:, HET], c[:, HOM_ALT]
         rec["missing"] = 2 * n_variants - c[:, AN]
         rec["call_rate"] = c[:, AN] / (2.0 * n_variants) if n_variants else np.nan
+        return rec
+
+    def relatedness(self, chromosomes=None, donor_ids=None, min_maf=None, min_kinship=None):
+        """the pairs i < j of donor_ids (default: every sample, store order) over the variants of chr_{N} for N in
+        chromosomes (one name or a list; None: every group), as host numpy records: sample1, sample2, nsnp (variants at
+        which both calls are complete: both alleles 0 or 1), hethet (both heterozygous), ibs0 (opposite homozygotes), het1
+        / het2 (sample1 / sample2 heterozygous, the other complete), kinship (float64: store.kinship_from_counts, the
+        KING-robust estimator as defined there — not checked against plink2; NaN where neither has such a heterozygote).
+        min_maf: only the variants whose minor allele frequency over the donors asked for is at least that
+        (GenotypeStore.variant_mask per group, computed and applied on the device).  min_kinship: only the pairs at or above
+        it (NaN pairs are then dropped)."""
+        st = self.store
+        if chromosomes is None:
+            chroms = [g[len("chr_"):] for g in st.groups()]
+        else:
+            chroms = [chromosomes] if isinstance(chromosomes, (str, int)) else list(chromosomes)
+        donors = list(st.samples) if donor_ids is None else list(donor_ids)
+        for c in chroms:
+            for d in (st.samples[:1] if donor_ids is None else donors) or st.samples[:1]:     # (the store's own are known)
+                self._group(d, c)
+        names = [f"chr_{c}" for c in chroms]
+        who = None if donor_ids is None else donors
+        masks = {g: st.variant_mask(g, who, min_maf=min_maf) for g in names} if min_maf is not None else None
+        table = st.pair_counts(names, who, variant_mask=masks)
+        phi = kinship_from_counts(table).cpu().numpy()
+        t = table.cpu().numpy().astype(np.int64)
+        i, j = np.triu_indices(len(donors), 1)
+        if min_kinship is not None:
+            with np.errstate(invalid="ignore"):
+                keep = phi[i, j] >= float(min_kinship)
+            i, j = i[keep], j[keep]
+        width = max([len(x.encode()) for x in donors] + [1])
+        rec = np.zeros(len(i), dtype=[("sample1", f"S{width}"), ("sample2", f"S{width}"), ("nsnp", np.int64),
+                                      ("hethet", np.int64), ("ibs0", np.int64), ("het1", np.int64), ("het2", np.int64),
+                                      ("kinship", np.float64)])
+        enc = np.array([x.encode() for x in donors], dtype=f"S{width}")
+        rec["sample1"], rec["sample2"] = enc[i], enc[j]
+        rec["nsnp"], rec["hethet"], rec["ibs0"] = t[i, j, NSNP], t[i, j, HETHET], t[i, j, IBS0]
+        rec["het1"], rec["het2"] = t[i, j, HET1], t[j, i, HET1]
+        rec["kinship"] = phi[i, j]
         return rec
 
     def close(self):

@@ -156,6 +156,105 @@ def pack_variant_mask(mask, v_lo, n_variants, vc, blocksize):
     return (bits.view(-1, 8) * weights).sum(1).to(torch.uint8).view(torch.int32)      # (little-endian words)
 
 
+# columns of GenotypeStore.pair_counts (and of hhgt_pair_counts' table), for the ordered pair (i, j) over the counted variants.
+# A call is complete iff both alleles are 0 or 1; a missing allele or an allele >= 2 takes the call out of every column.
+NSNP, HETHET, IBS0, HET1 = 0, 1, 2, 3    # both complete; both HET; opposite homozygotes; i HET and j complete
+
+# default budgets of GenotypeStore.pair_counts: the plane buffer of one window of variants, and the largest table it makes
+DEFAULT_PLANE_BYTES = 1 << 30
+MAX_PAIR_TABLE_BYTES = 2 << 30
+
+# one selection of the plane planner: plan_sample_counts' record (out_row: the plane row of chunk row 0) plus the first word
+# of the block's bits in a plane row
+PLANE_PLAN_DTYPE = np.dtype([("vcol", np.int64), ("scol", np.int64), ("part", np.uint32), ("row_mask", np.uint64),
+                             ("lo", np.uint32), ("hi", np.uint32), ("out_row", np.int64), ("mask_word", np.int64),
+                             ("out_word", np.int64)])
+
+
+def plane_rows(sample_idx, sc):
+    """the plane rows of a sample list: chunk rows without a listed sample get none, the others sc rows each in order ->
+    (scols: the chunk rows kept, ascending; rows int64 [len(sample_idx)]: the plane row of each listed sample)"""
+    s = np.asarray(sample_idx, dtype=np.int64).reshape(-1)
+    scols = np.unique(s // int(sc))
+    return scols, np.searchsorted(scols, s // int(sc)) * int(sc) + s % int(sc)
+
+
+def plan_planes(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize=None, block0=None):
+    """the selections of hhgt_genotype_planes: plan_counts' cuts of (samples, [v_lo, v_hi)) — the same chunks, blocks, row
+    masks and ranges, in the same order, mask_word as plan_sample_counts gives it —, with the plane rows compacted by chunk
+    row (plane_rows: the k-th chunk row that has a selected sample owns plane rows [k * sc, (k + 1) * sc)) and the bits of
+    block B of the group (B = v // (blocksize / 2)) at word (B - block0) * mask_words_per_block(blocksize) of a plane row;
+    block0: the first block of the plane buffer (default: the block of v_lo)."""
+    sc, vc = int(sc), int(vc)
+    bs = min(vc * 2, 8192) if blocksize is None else int(blocksize)
+    cut = plan_sample_counts(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize=bs)
+    vb, wpb = bs // 2, mask_words_per_block(bs)
+    block0 = int(v_lo) // vb if block0 is None else int(block0)
+    out = np.zeros(len(cut), PLANE_PLAN_DTYPE)
+    for f in ("vcol", "scol", "part", "row_mask", "lo", "hi", "mask_word"):
+        out[f] = cut[f]
+    scols = np.unique(cut["scol"])
+    out["out_row"] = np.searchsorted(scols, cut["scol"]) * sc
+    out["out_word"] = (cut["vcol"] * (vc // vb) + cut["part"].astype(np.int64) - block0) * wpb
+    if len(out) and int(out["out_word"].min()) < 0:
+        raise IndexError(f"plan_planes: block0 {block0} lies behind variant {int(v_lo)}")
+    return out
+
+
+def plane_windows(v_lo, v_hi, blocksize, n_rows, plane_bytes):
+    """[v_lo, v_hi) cut at Blosc block boundaries into windows whose plane buffer (3 planes x n_rows rows x the words of the
+    window's blocks) is at most plane_bytes, one block at least -> list of (a, b), in order, covering the range once"""
+    v_lo, v_hi, vb = int(v_lo), int(v_hi), int(blocksize) // 2
+    per_block = 3 * max(int(n_rows), 1) * mask_words_per_block(blocksize) * 4
+    step = max(int(plane_bytes) // per_block, 1) * vb
+    out, a = [], v_lo
+    while a < v_hi:
+        b = min((a // vb) * vb + step, v_hi)
+        out.append((a, b))
+        a = b
+    return out
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def ibs_counts(table):
+    """pair table [n, n, 4] (numpy or torch, any integer type) -> (IBS0, IBS1, IBS2), int64 [n, n] each: the variants at
+    which a pair's complete calls share no, one, both alleles.  IBS2 = 2 HETHET + NSNP - HET1[i][j] - HET1[j][i] - IBS0
+    (identical genotypes), IBS1 = NSNP - IBS0 - IBS2."""
+    if _is_torch(table):
+        import torch
+        t = table.to(torch.int64)
+        h2 = t[..., HET1].transpose(0, 1)
+    else:
+        t = np.asarray(table).astype(np.int64)
+        h2 = t[..., HET1].T
+    ibs2 = 2 * t[..., HETHET] + t[..., NSNP] - t[..., HET1] - h2 - t[..., IBS0]
+    return t[..., IBS0], t[..., NSNP] - t[..., IBS0] - ibs2, ibs2
+
+
+def kinship_from_counts(table):
+    """pair table [n, n, 4] (numpy or torch) -> float64 [n, n]: the KING-robust between-family kinship estimator
+    (Manichaikul et al. 2010) as this project defines it,
+        phi = 1/2 - (4 IBS0 + HET1[i][j] + HET1[j][i] - 2 HETHET) / (4 min(HET1[i][j], HET1[j][i])),
+    in float64 from the integer table, NaN where the minimum is 0.  A sample against itself or against a duplicate gives
+    exactly 0.5.  The formula is the contract: equality with plink2's KINSHIP column is neither claimed nor tested."""
+    if _is_torch(table):
+        import torch
+        t = table.to(torch.int64)
+        h1, h2 = t[..., HET1], t[..., HET1].transpose(0, 1)
+        num = (4 * t[..., IBS0] + h1 + h2 - 2 * t[..., HETHET]).to(torch.float64)
+        den = (4 * torch.minimum(h1, h2)).to(torch.float64)
+        return torch.where(den > 0, 0.5 - num / den, torch.full_like(den, float("nan")))
+    t = np.asarray(table).astype(np.int64)
+    h1, h2 = t[..., HET1], t[..., HET1].T
+    num = (4 * t[..., IBS0] + h1 + h2 - 2 * t[..., HETHET]).astype(np.float64)
+    den = (4 * np.minimum(h1, h2)).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, 0.5 - num / den, np.nan)
+
+
 class StoreWriter:
     def __init__(self, path, samples, sc, vc, typesize=2, cohort_name="", donor_ids=None, chunk_format="blosc2"):
         self.path = path
@@ -246,6 +345,8 @@ class GenotypeStore:
         self.stats.update(count_blocks=0, count_compressed_bytes_read=0)
         # and of sample_counts (which shares count_compressed_bytes_read with it): Blosc blocks it decoded
         self.stats.update(sample_count_blocks=0)
+        # and of pair_counts: Blosc blocks its first stage decoded, plane words per row its second stage read
+        self.stats.update(pair_plane_blocks=0, pair_words=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -566,6 +667,100 @@ class GenotypeStore:
 
             self._scan_slabs(group, plan, slab_bytes, launch)
         return table[torch.from_numpy(idx).to(ctx.device)]
+
+    def pair_counts(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None,
+                    plane_bytes=None, max_table_bytes=None):
+        """pairwise counts over the variants of `groups`: an int32 device tensor [n, n, 4], columns NSNP, HETHET, IBS0, HET1
+        (module constants) for the ordered pair (samples[i], samples[j]) — variants at which both calls are complete
+        (both alleles 0 or 1), both heterozygous, opposite homozygotes, i heterozygous and j complete; a sample named twice
+        appears twice and pairs with itself as a duplicate.  groups, samples, v_lo / v_hi, variant_mask and slab_bytes mean
+        what they mean in sample_counts, and the chunks are handled the same way (cached ones used, the read cache neither
+        filled nor evicted).  Two kernels: hhgt_genotype_planes decodes the selected rows' Blosc blocks into three bits per
+        call (HET, HOM_REF, HOM_ALT planes; no genotype is written), hhgt_pair_counts reduces the planes pair by pair.  A
+        group's range is walked in windows of whole Blosc blocks whose plane buffer is at most plane_bytes (default 1 GiB);
+        groups, windows and slabs add into one table.  Plane rows are kept for the chunk rows that hold a listed sample
+        only.  ValueError, before anything is allocated, if the table (16 bytes per pair of plane rows) would exceed
+        max_table_bytes (default 2 GiB)."""
+        import torch
+        from .device import PLANE_SEL_DTYPE
+        sc, vc, bs = self.meta["sc"], self.meta["vc"], self._blocksize()
+        names = self._group_list(groups)
+        if len(names) != 1 and (int(v_lo) != 0 or v_hi is not None):
+            raise ValueError("pair_counts: v_lo / v_hi need a single group")
+        if isinstance(variant_mask, dict):
+            for g in variant_mask:
+                if g not in names:
+                    raise KeyError(g)
+            masks = variant_mask
+        elif variant_mask is not None:
+            if len(names) != 1:
+                raise ValueError("pair_counts: one variant_mask needs a single group (several: a dict group -> mask)")
+            masks = {names[0]: variant_mask}
+        else:
+            masks = {}
+        idx = (np.arange(len(self.samples)) if samples is None else
+               np.array([self._sample_index(x) for x in samples], dtype=np.int64).reshape(-1))
+        scols, rows = plane_rows(idx, sc)
+        n_rows = len(scols) * sc
+        limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
+        if n_rows * n_rows * 16 > limit:
+            raise ValueError(f"pair_counts: a table of {n_rows} x {n_rows} pairs ({n_rows * n_rows * 16} bytes) exceeds "
+                             f"max_table_bytes = {limit}")
+        ctx = self._context()
+        table = torch.zeros((n_rows, n_rows, 4), dtype=torch.int32, device=ctx.device)
+        budget = DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
+        vb, wpb = bs // 2, mask_words_per_block(bs)
+        for group in names:
+            n_var = self.meta["groups"][group]["n_variants"]
+            lo, hi = (int(v_lo), n_var if v_hi is None else int(v_hi)) if len(names) == 1 else (0, n_var)
+            if not 0 <= lo <= hi <= n_var:
+                raise IndexError(f"variants [{lo}, {hi}) outside {group} (0..{n_var})")
+            vmask = None
+            if group in masks:
+                m = masks[group]
+                if m.ndim != 1 or int(m.shape[0]) != hi - lo:
+                    raise ValueError(f"variant_mask of {group}: shape {tuple(m.shape)}, expected ({hi - lo},)")
+                vmask = pack_variant_mask(m, lo, n_var, vc, bs)
+                if not torch.is_tensor(vmask):          # a host mask goes up once, not with every slab
+                    vmask = torch.from_numpy(vmask.view(np.int32)).to(ctx.device)
+            if n_rows == 0:
+                continue
+            planes = None
+            for a, b in plane_windows(lo, hi, bs, n_rows, budget):
+                words = ((b - 1) // vb - a // vb + 1) * wpb
+                if planes is None or planes.shape[2] != words:
+                    planes = None                       # (the last window of a range may be shorter)
+                    planes = torch.zeros((3, n_rows, words), dtype=torch.int32, device=ctx.device)
+                else:
+                    planes.zero_()
+                plan = plan_planes(idx, len(self.samples), sc, vc, n_var, a, b, blocksize=bs)
+                blocks = np.array([bin(int(m)).count("1") for m in plan["row_mask"]], np.int64)
+
+                def launch(chunks, keys, sel_rows, plan=plan, vmask=vmask, group=group, blocks=blocks, planes=planes):
+                    dsel = np.zeros(len(sel_rows), PLANE_SEL_DTYPE)
+                    dsel["src_ptr"] = [chunks[keys[i]].data_ptr() for i in sel_rows]
+                    dsel["src_bytes"] = [chunks[keys[i]].numel() for i in sel_rows]
+                    for f in ("row_mask", "out_row", "mask_word", "out_word", "part", "lo", "hi"):
+                        dsel[f] = plan[f][sel_rows]
+                    _, bad = ctx.genotype_planes(dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, vmask=vmask,
+                                                 planes=planes)
+                    if bad:
+                        raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
+                    self.stats["pair_plane_blocks"] += int(blocks[sel_rows].sum())
+
+                self._scan_slabs(group, plan, slab_bytes, launch)
+                ctx.pair_counts(planes, 0, words, table=table)
+                self.stats["pair_words"] += words
+        pick = torch.from_numpy(rows).to(ctx.device)
+        return table[pick][:, pick].contiguous()
+
+    def kinship(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
+                max_table_bytes=None):
+        """KING-robust kinship of every pair of `samples` from pair_counts (same arguments): a float64 device tensor [n, n],
+        kinship_from_counts' formula — NaN where a pair has no heterozygous call to divide by, exactly 0.5 for a sample
+        against itself or a duplicate.  The formula there is the contract; plink2's KINSHIP column is not."""
+        return kinship_from_counts(self.pair_counts(groups, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes,
+                                                    max_table_bytes))
 
     def variant_mask(self, group, samples=None, v_lo=0, v_hi=None, min_maf=None, max_ac=None, min_ac=None):
         """a class of the variants [v_lo, v_hi) of a group, from allele_counts over `samples` (same arguments), as a bool

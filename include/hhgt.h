@@ -308,6 +308,52 @@ int hhgt_count_samples(hhgt_ctx *ctx, const hhgt_sample_sel *d_sel, uint32_t n_s
                        int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
                        uint32_t *d_counts, uint64_t n_out, uint64_t *n_bad, void *stream);
 
+/* Pairwise sample counts, in two calls with three bits per call between them.
+ *
+ * A call (a, b) is COMPLETE iff both alleles are 0 or 1; a call with a missing allele (negative) or an allele >= 2 is not
+ * and takes part in nothing below.  A complete call is HET (a != b), HOM_REF (0, 0) or HOM_ALT (1, 1).
+ *
+ * hhgt_genotype_planes decodes and classifies: d_planes is uint32 [3][n_rows][row_words] — plane 0 HET, 1 HOM_REF,
+ * 2 HOM_ALT —, which the CALLER ZEROES.  A selection names a chunk, a block `part` of its rows, the rows and the variants
+ * [lo, hi) of that block, and the block's words of d_vmask (optional) exactly as a hhgt_sample_sel does; chunk row r goes
+ * to plane row out_row + r, and the block owns the ceil(blocksize / 2 / 32) words of that row that start at out_word: bit
+ * v % 32 of word out_word + v / 32 = variant v of the block (the variant mask's layout).  A variant outside [lo, hi), outside
+ * the mask, or in the padding of the last word is a 0 bit in all three planes, as is every call that is not complete.  One
+ * workgroup writes the words of its (rows, block) with plain stores and nobody else may: two selections of one buffer must
+ * not name the same (plane row, word).  Geometries as hhgt_count_samples, others return HHGT_ERR_ARG.  *n_bad (host,
+ * optional, syncs) = the number of bad selections, by the rules of hhgt_count_samples (with n_rows for n_out) plus: the
+ * block's words past the row (out_word + ceil(blocksize / 64) > row_words).  A bad selection leaves its words as the caller
+ * zeroed them (a stream found corrupt after some rows were written: those are zeroed again). */
+typedef struct {
+    uint64_t src_ptr;    /* device address of one framed chunk (either header format)                         */
+    uint64_t src_bytes;  /* its stored size                                                                   */
+    uint64_t row_mask;   /* sample rows of the chunk to classify: bit r = row r                               */
+    uint64_t out_row;    /* plane row that receives chunk row 0 (row r goes to out_row + r)                   */
+    uint64_t mask_word;  /* first uint32 word of this block's bits in d_vmask (ignored when d_vmask is NULL)  */
+    uint64_t out_word;   /* first word of this block's bits in a plane row                                    */
+    uint32_t part;       /* Blosc block of each row (0 .. vc * 2 / blocksize - 1)                             */
+    uint32_t lo, hi;     /* variants [lo, hi) of that block, lo < hi <= blocksize / 2                         */
+    uint32_t reserved;   /* 0 */
+} hhgt_plane_sel;
+int hhgt_genotype_planes(hhgt_ctx *ctx, const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
+                         int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
+                         uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t *n_bad, void *stream);
+
+/* hhgt_pair_counts reduces the words [w_lo, w_hi) of every row of such planes to d_table, uint32 [n_rows][n_rows][4]
+ * (16-byte aligned), both triangles: for the ordered pair of plane rows (i, j), over the variants whose bits it reads,
+ *     d_table[i][j][0] NSNP    both calls complete
+ *     d_table[i][j][1] HETHET  both HET
+ *     d_table[i][j][2] IBS0    one HOM_REF, the other HOM_ALT (either way round)
+ *     d_table[i][j][3] HET1    i is HET and j's call is complete
+ * Columns 0-2 are symmetric, d_table[j][i][3] is the other sample's heterozygotes; on the diagonal: (complete calls of i,
+ * HET calls of i, 0, HET calls of i).  A variant with 0 bits in all planes of a row is nobody's complete call, so the
+ * call needs neither mask nor range.  It ADDS to d_table with plain read-modify-write — one workgroup owns a 64 x 64 tile
+ * of the table (and its mirror image) for the whole launch, launches on one stream are ordered: exact, no atomics —, so
+ * windows, groups and calls may accumulate on ONE stream; two streams adding to one table at the same time are the
+ * caller's error.  Any n_rows (up to 64 * 65535) and row_words; w_lo <= w_hi <= row_words, else HHGT_ERR_ARG. */
+int hhgt_pair_counts(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
+                     uint64_t w_hi, uint32_t *d_table, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values
@@ -423,7 +469,8 @@ int hhgt_inflate_members(hhgt_ctx *ctx, const void *d_src, uint64_t src_bytes, c
 #define HHGT_STAGE_DECODE 6   /* chunk decode                                                    */
 #define HHGT_STAGE_ONEHOT 7   /* one-hot haplotype windows                                       */
 #define HHGT_STAGE_INFLATE 8  /* BGZF members inflated on the device                            */
-#define HHGT_N_STAGES 9
+#define HHGT_STAGE_PAIRS 9    /* pairwise sample counts over genotype planes                     */
+#define HHGT_N_STAGES 10
 int hhgt_profile_enable(hhgt_ctx *ctx, int on);
 int hhgt_profile_reset(hhgt_ctx *ctx);
 int hhgt_profile_read(hhgt_ctx *ctx, double *ms /*[HHGT_N_STAGES]*/, uint64_t *launches /*[HHGT_N_STAGES]*/);

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Pairwise sample counts at cohort shape: GenotypeStore.pair_counts on the input of tools/allele_count_bench.py (a
+2504-sample cohort file with one chr1-sized group, 230 k synthetic variants, converter output in /dev/shm), all samples.
+
+Reports, as one JSON line: the call's ms cold (every chunk read from the file and uploaded) and with every chunk in the read
+cache, the kernel ms of its two stages (hhgt_genotype_planes under "decode", hhgt_pair_counts under "pairs",
+ctx.profile_read()), and, alternating with it repetition by repetition in the same warmed-up process, the torch route on the
+cached chunks: read_windows of every sample, the four indicator matrices (HET, complete, HOM_REF, HOM_ALT) as bf16, four
+S x S x V products in variant slabs with fp32 accumulation (0 / 1 operands: exact below 2^24 per slab), summed in int32.
+Medians of the runs and every run; the first repetition is printed but kept out of the medians.  The torch table is
+asserted equal to pair_counts' before any time is taken.  Not timed: building and converting the cohort, the warm-up.
+usage: pair_count_bench.py [variants] [runs]"""
+import json, os, shutil, sys, tempfile, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+from haplohyped_varawareml_amd import device as dev, synth
+from haplohyped_varawareml_amd.reader import write_bgzf_native
+from haplohyped_varawareml_amd.store import GenotypeStore
+from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
+
+V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
+RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+S, SEED, G = 2504, 1001, "chr_1"
+BIG = 1 << 40
+SLAB = 1 << 16            # variants per product: 65 536 < 2^24
+
+
+def torch_route(st):
+    """read_windows of every sample (slices of 256), indicators, four products per variant slab -> int32 [S, S, 4]"""
+    ind = torch.empty((4, S, V), dtype=torch.bfloat16, device=st._context().device)      # HET, M, REF, ALT
+    for i in range(0, S, 256):
+        x = torch.stack(st.read_windows([(G, s, 0, V) for s in range(i, min(i + 256, S))]))   # [n, V, 2] int8
+        a, b = x[..., 0], x[..., 1]
+        done = ((a == 0) | (a == 1)) & ((b == 0) | (b == 1))
+        n = x.shape[0]
+        ind[0, i:i + n] = done & (a != b)
+        ind[1, i:i + n] = done
+        ind[2, i:i + n] = done & (a == 0) & (b == 0)
+        ind[3, i:i + n] = done & (a == 1) & (b == 1)
+    t = torch.zeros((S, S, 4), dtype=torch.int32, device=ind.device)
+    for v in range(0, V, SLAB):
+        h, m, r, al = (ind[k, :, v:v + SLAB] for k in range(4))
+        ra = torch.matmul(r, al.T).float()
+        t[..., 0] += torch.matmul(m, m.T).float().to(torch.int32)
+        t[..., 1] += torch.matmul(h, h.T).float().to(torch.int32)
+        t[..., 2] += (ra + ra.T).to(torch.int32)
+        t[..., 3] += torch.matmul(h, m.T).float().to(torch.int32)
+    return t
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r = fn()
+    torch.cuda.synchronize()
+    return r, (time.perf_counter() - t0) * 1e3
+
+
+tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+try:
+    ctx = dev.Context(0)
+    tab = synth.variant_table(SEED, V, S)
+    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
+    os.makedirs(os.path.join(tmp, "vcf"))
+    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
+    del text
+    samples = os.path.join(tmp, "samples.txt")
+    open(samples, "w").write("\n".join(synth.sample_names(S)) + "\n")
+    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    ctx.profile(True)
+    out = dict(samples=S, variants=V, runs=RUNS, product_slab_variants=SLAB)
+
+    # correctness first, which is also the warm-up of both routes (code objects loaded, the allocator grown)
+    warm = GenotypeStore(h5, ctx=ctx, cache_bytes=BIG)
+    ref = torch_route(warm)
+    got = warm.pair_counts(G)
+    assert torch.equal(got, ref)
+    out.update(same_as_torch=True, nsnp_max=int(got[..., 0].max()), table_bytes=got.numel() * 4)
+    del ref, got
+
+    cold = GenotypeStore(h5, ctx=ctx)
+    runs = dict(call_cold_ms=[], call_cached_ms=[], planes_kernel_ms=[], pairs_kernel_ms=[], torch_cached_ms=[])
+    for _ in range(RUNS + 1):
+        runs["call_cold_ms"].append(timed(lambda: cold.pair_counts(G))[1])
+        runs["torch_cached_ms"].append(timed(lambda: torch_route(warm))[1])
+        ctx.profile_reset()
+        warm.stats.update(pair_plane_blocks=0, pair_words=0)
+        runs["call_cached_ms"].append(timed(lambda: warm.pair_counts(G))[1])
+        prof = ctx.profile_read()
+        runs["planes_kernel_ms"].append(prof["decode"]["ms"])
+        runs["pairs_kernel_ms"].append(prof["pairs"]["ms"])
+    later = {k: v[1:] for k, v in runs.items()}                            # (the first repetition of a fresh box reads high)
+    out.update(runs_ms=runs, **{k: float(np.median(v)) for k, v in later.items()},
+               **{k.replace("_ms", "_spread"): float((max(v) - min(v)) / np.median(v)) for k, v in later.items()})
+    out.update(plane_blocks_decoded=warm.stats["pair_plane_blocks"], plane_words_per_row=warm.stats["pair_words"],
+               call_cached_vs_torch_cached=out["call_cached_ms"] / out["torch_cached_ms"])
+    warm.close()
+    cold.close()
+    print(json.dumps(out))
+finally:
+    shutil.rmtree(tmp, ignore_errors=True)
