@@ -1077,6 +1077,27 @@ extern "C" int hhgt_inflate_members(hhgt_ctx *c, const void *d_src, uint64_t src
     return HHGT_OK;
 }
 
+// the bad-counter protocol around a decode launch: c->dec_bad zeroed on the stream, launch(d_bad) under the DECODE stage
+// timer, then, if the caller wants it, the count copied back (synchronises)
+template <typename Launch>
+static int with_bad_counter(hhgt_ctx *c, hipStream_t st, uint64_t *n_bad, Launch launch)
+{
+    TRY(c->dec_bad.ensure(8));
+    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
+    {
+        StageTimer t(c, st, HHGT_STAGE_DECODE);
+        TRY(launch(c->dec_bad.as<unsigned long long>()));
+        t.stop();
+    }
+    if (n_bad) {
+        uint64_t nb = 0;
+        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_bad = nb;
+    }
+    return HHGT_OK;
+}
+
 extern "C" int hhgt_decompress_chunks(hhgt_ctx *c, const void *d_src, const uint64_t *d_chunk_off, uint64_t n_chunks,
                                       uint64_t chunk_nbytes, int typesize, int blocksize, void *d_dst,
                                       uint64_t *n_bad, void *stream)
@@ -1089,21 +1110,10 @@ extern "C" int hhgt_decompress_chunks(hhgt_ctx *c, const void *d_src, const uint
     if (n_bad) *n_bad = 0;
     if (n_chunks == 0) return HHGT_OK;
     blocksize = effective_blocksize(chunk_nbytes, typesize, blocksize);
-    TRY(c->dec_bad.ensure(8));
-    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
-    {
-        StageTimer t(c, st, HHGT_STAGE_DECODE);
-        TRY(launch_decode(static_cast<const uint8_t *>(d_src), d_chunk_off, n_chunks, chunk_nbytes, typesize,
-                          blocksize, static_cast<uint8_t *>(d_dst), c->dec_bad.as<unsigned long long>(), st));
-        t.stop();
-    }
-    if (n_bad) {
-        uint64_t nb = 0;
-        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *n_bad = nb;
-    }
-    return HHGT_OK;
+    return with_bad_counter(c, st, n_bad, [&](unsigned long long *d_bad) {
+        return launch_decode(static_cast<const uint8_t *>(d_src), d_chunk_off, n_chunks, chunk_nbytes, typesize, blocksize,
+                             static_cast<uint8_t *>(d_dst), d_bad, st);
+    });
 }
 
 extern "C" int hhgt_decompress_blocks(hhgt_ctx *c, const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chunk_nbytes,
@@ -1120,153 +1130,81 @@ extern "C" int hhgt_decompress_blocks(hhgt_ctx *c, const hhgt_block_sel *d_sel, 
     if (n_bad) *n_bad = 0;
     if (n_sel == 0) return HHGT_OK;
     blocksize = effective_blocksize(chunk_nbytes, typesize, blocksize);
-    TRY(c->dec_bad.ensure(8));
-    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
-    {
-        StageTimer t(c, st, HHGT_STAGE_DECODE);
-        TRY(launch_decode_sel(d_sel, n_sel, chunk_nbytes, typesize, blocksize, static_cast<uint8_t *>(d_dst),
-                              c->dec_bad.as<unsigned long long>(), st));
-        t.stop();
+    return with_bad_counter(c, st, n_bad, [&](unsigned long long *d_bad) {
+        return launch_decode_sel(d_sel, n_sel, chunk_nbytes, typesize, blocksize, static_cast<uint8_t *>(d_dst), d_bad, st);
+    });
+}
+
+// the geometry the row-walk kernels (hhgt_count_alleles, hhgt_count_samples, hhgt_genotype_planes) serve; `who` prefixes
+// the message
+static int check_row_kernel_args(const char *who, uint32_t sc, uint32_t vc, int typesize, int blocksize)
+{
+    if (typesize != 2) {
+        hhgt_set_error("%s: typesize %d (only 2: one diploid int8 call)", who, typesize);
+        return HHGT_ERR_ARG;
     }
-    if (n_bad) {
-        uint64_t nb = 0;
-        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *n_bad = nb;
+    if (sc < 1 || sc > 64 || vc < 1) {
+        hhgt_set_error("%s: chunk of %u samples x %u variants (1 to 64 samples)", who, sc, vc);
+        return HHGT_ERR_ARG;
+    }
+    TRY(check_codec_args((uint64_t)sc * vc * 2u, typesize, blocksize, HHGT_BLOSC2));
+    if (blocksize > 8192 || ((uint64_t)vc * 2u) % (uint64_t)blocksize) {
+        hhgt_set_error("%s: blocksize %d does not cut a row of %u variants into whole blocks of at most 8192 bytes", who,
+                       blocksize, vc);
+        return HHGT_ERR_ARG;
     }
     return HHGT_OK;
+}
+
+// what the three entry points do alike: the null checks (`out`: the output's name in the message), the geometry, the
+// device, *n_bad, nothing to do without selections, the launch under the bad-counter protocol
+template <typename Launch>
+static int run_row_kernel(const char *who, const char *out, hhgt_ctx *c, const void *d_sel, uint32_t n_sel, const void *d_out,
+                          uint32_t sc, uint32_t vc, int typesize, int blocksize, uint64_t *n_bad, void *stream, Launch launch)
+{
+    if (!c || (n_sel && (!d_sel || !d_out))) {
+        hhgt_set_error("%s: null %s", who, !c ? "context" : !d_sel ? "selection array" : out);
+        return HHGT_ERR_ARG;
+    }
+    TRY(check_row_kernel_args(who, sc, vc, typesize, blocksize));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (n_bad) *n_bad = 0;
+    if (n_sel == 0) return HHGT_OK;
+    return with_bad_counter(c, st, n_bad, [&](unsigned long long *d_bad) { return launch(d_bad, st); });
 }
 
 extern "C" int hhgt_count_alleles(hhgt_ctx *c, const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
                                   int typesize, int blocksize, uint32_t *d_counts, uint64_t n_out, uint64_t *n_bad,
                                   void *stream)
 {
-    if (!c || (n_sel && (!d_sel || !d_counts))) {
-        hhgt_set_error("count_alleles: null %s", !c ? "context" : !d_sel ? "selection array" : "counts");
-        return HHGT_ERR_ARG;
-    }
-    if (typesize != 2) {
-        hhgt_set_error("count_alleles: typesize %d (only 2: one diploid int8 call)", typesize);
-        return HHGT_ERR_ARG;
-    }
-    if (sc < 1 || sc > 64 || vc < 1) {
-        hhgt_set_error("count_alleles: chunk of %u samples x %u variants (1 to 64 samples)", sc, vc);
-        return HHGT_ERR_ARG;
-    }
-    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
-    TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
-    if (blocksize > 8192 || ((uint64_t)vc * 2u) % (uint64_t)blocksize) {
-        hhgt_set_error("count_alleles: blocksize %d does not cut a row of %u variants into whole blocks of at most 8192 "
-                       "bytes", blocksize, vc);
-        return HHGT_ERR_ARG;
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (n_bad) *n_bad = 0;
-    if (n_sel == 0) return HHGT_OK;
-    TRY(c->dec_bad.ensure(8));
-    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
-    {
-        StageTimer t(c, st, HHGT_STAGE_DECODE);
-        TRY(launch_count_alleles(d_sel, n_sel, sc, vc, blocksize, d_counts, n_out, c->dec_bad.as<unsigned long long>(), st));
-        t.stop();
-    }
-    if (n_bad) {
-        uint64_t nb = 0;
-        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *n_bad = nb;
-    }
-    return HHGT_OK;
+    return run_row_kernel("count_alleles", "counts", c, d_sel, n_sel, d_counts, sc, vc, typesize, blocksize, n_bad, stream,
+                          [&](unsigned long long *d_bad, hipStream_t st) {
+                              return launch_count_alleles(d_sel, n_sel, sc, vc, blocksize, d_counts, n_out, d_bad, st);
+                          });
 }
 
 extern "C" int hhgt_count_samples(hhgt_ctx *c, const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
                                   int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
                                   uint32_t *d_counts, uint64_t n_out, uint64_t *n_bad, void *stream)
 {
-    if (!c || (n_sel && (!d_sel || !d_counts))) {
-        hhgt_set_error("count_samples: null %s", !c ? "context" : !d_sel ? "selection array" : "counts");
-        return HHGT_ERR_ARG;
-    }
-    if (typesize != 2) {
-        hhgt_set_error("count_samples: typesize %d (only 2: one diploid int8 call)", typesize);
-        return HHGT_ERR_ARG;
-    }
-    if (sc < 1 || sc > 64 || vc < 1) {
-        hhgt_set_error("count_samples: chunk of %u samples x %u variants (1 to 64 samples)", sc, vc);
-        return HHGT_ERR_ARG;
-    }
-    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
-    TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
-    if (blocksize > 8192 || ((uint64_t)vc * 2u) % (uint64_t)blocksize) {
-        hhgt_set_error("count_samples: blocksize %d does not cut a row of %u variants into whole blocks of at most 8192 "
-                       "bytes", blocksize, vc);
-        return HHGT_ERR_ARG;
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (n_bad) *n_bad = 0;
-    if (n_sel == 0) return HHGT_OK;
-    TRY(c->dec_bad.ensure(8));
-    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
-    {
-        StageTimer t(c, st, HHGT_STAGE_DECODE);
-        TRY(launch_count_samples(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_counts, n_out,
-                                 c->dec_bad.as<unsigned long long>(), st));
-        t.stop();
-    }
-    if (n_bad) {
-        uint64_t nb = 0;
-        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *n_bad = nb;
-    }
-    return HHGT_OK;
+    return run_row_kernel("count_samples", "counts", c, d_sel, n_sel, d_counts, sc, vc, typesize, blocksize, n_bad, stream,
+                          [&](unsigned long long *d_bad, hipStream_t st) {
+                              return launch_count_samples(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_counts,
+                                                          n_out, d_bad, st);
+                          });
 }
 
 extern "C" int hhgt_genotype_planes(hhgt_ctx *c, const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
-                                  int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
-                                  uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t *n_bad,
+                                    int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
+                                    uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t *n_bad,
                                     void *stream)
 {
-    if (!c || (n_sel && (!d_sel || !d_planes))) {
-        hhgt_set_error("genotype_planes: null %s", !c ? "context" : !d_sel ? "selection array" : "planes");
-        return HHGT_ERR_ARG;
-    }
-    if (typesize != 2) {
-        hhgt_set_error("genotype_planes: typesize %d (only 2: one diploid int8 call)", typesize);
-        return HHGT_ERR_ARG;
-    }
-    if (sc < 1 || sc > 64 || vc < 1) {
-        hhgt_set_error("genotype_planes: chunk of %u samples x %u variants (1 to 64 samples)", sc, vc);
-        return HHGT_ERR_ARG;
-    }
-    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
-    TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
-    if (blocksize > 8192 || ((uint64_t)vc * 2u) % (uint64_t)blocksize) {
-        hhgt_set_error("genotype_planes: blocksize %d does not cut a row of %u variants into whole blocks of at most 8192 "
-                       "bytes", blocksize, vc);
-        return HHGT_ERR_ARG;
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (n_bad) *n_bad = 0;
-    if (n_sel == 0) return HHGT_OK;
-    TRY(c->dec_bad.ensure(8));
-    HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
-    {
-        StageTimer t(c, st, HHGT_STAGE_DECODE);
-        TRY(launch_genotype_planes(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_planes, n_rows, row_words,
-                                   c->dec_bad.as<unsigned long long>(), st));
-        t.stop();
-    }
-    if (n_bad) {
-        uint64_t nb = 0;
-        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        *n_bad = nb;
-    }
-    return HHGT_OK;
+    return run_row_kernel("genotype_planes", "planes", c, d_sel, n_sel, d_planes, sc, vc, typesize, blocksize, n_bad, stream,
+                          [&](unsigned long long *d_bad, hipStream_t st) {
+                              return launch_genotype_planes(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_planes,
+                                                            n_rows, row_words, d_bad, st);
+                          });
 }
 
 extern "C" int hhgt_pair_counts(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,

@@ -368,7 +368,157 @@ __global__ __launch_bounds__(1024) void k_decode_sel(const hhgt_block_sel *__res
     unshuffle_range(smem, h.doshuffle, typesize, nstreams, bsize, sstride, lo, hi, out);
 }
 
-// ---- allele counts straight out of LDS (hhgt_count_alleles) ------------------------------------------------------------
+// ---- the row walk of the three query kernels (hhgt_count_alleles, hhgt_count_samples, hhgt_genotype_planes) -------------
+//
+// Each runs one selection per workgroup (grid = n_sel; block = 64 * nwaves and dynamic LDS as decode_geometry says for
+// typesize 2: two waves): a chunk, the Blosc block `part` of its sample rows, the rows of row_mask and the variants [lo, hi)
+// of that block.  Thread t owns variants [g, g + 16) of the block for g = 16 (t + k blockDim), k = 0, 1 (blockDim * 32 >=
+// blocksize / 2 for every block size served), over every selected row: stage_row leaves the row's block in LDS, for_calls16
+// hands the thread its 2 x 16 calls four at a time.  What a kernel does with four calls (count4, tally4, planes4), at the
+// end of a row and with its totals is its own; so are the checks of its outputs.
+
+// a bad selection counts once, whatever made it bad
+__device__ __forceinline__ void bad_selection(unsigned long long *n_bad)
+{
+    if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+}
+
+// a chunk lies in global memory: said through the address space, its loads are global_load, not flat_load
+__device__ __forceinline__ const uint8_t *global_chunk(uint64_t src_ptr)
+{
+    return (const uint8_t *)(const __attribute__((address_space(1))) uint8_t *)src_ptr;
+}
+
+struct RowWalk {
+    const uint8_t *ck;    // the framed chunk
+    uint32_t avail;       // its stored bytes
+    BloscHdr h;
+    uint64_t mask;        // the selected rows
+    uint32_t part, lo, hi;
+    uint32_t blocksize, vb, parts, mwords;   // variants per block, blocks per row, variant-mask words per block
+    uint32_t nstreams, neblock;              // streams of a block as it lies in LDS, bytes of each
+    bool memcpyed;        // the chunk is stored, not compressed
+    bool shuffled;        // the block in LDS is byte-shuffled: allele j of variant v at byte j * vb + v, else at 2 v + j
+    bool planes16;        // the fast form: both planes of a shuffled block split into two streams, 16-byte aligned
+
+    // fills the walk from the fields every selection struct shares, clears *s_bad (holds a barrier) and validates what
+    // the three kernels validate alike: the header, part, [lo, hi), the row bits, the split against the launch
+    template <typename Sel>
+    __device__ __forceinline__ bool init(const uint8_t *chunk, const Sel *s, uint32_t sc, uint32_t vc, uint32_t bs,
+                                         uint32_t *s_bad)
+    {
+        ck = chunk;
+        const uint64_t src_bytes = s->src_bytes;
+        mask = s->row_mask;
+        part = s->part, lo = s->lo, hi = s->hi;
+        if (threadIdx.x == 0) *s_bad = 0;
+        __syncthreads();
+        avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
+        blocksize = bs;
+        vb = bs >> 1, parts = vc * 2u / bs, mwords = (vb + 31u) >> 5;
+        bool ok = blosc_header(ck, avail, (uint64_t)sc * vc * 2u, 2u, bs, h);
+        ok = ok && part < parts && lo < hi && hi <= vb && (sc >= 64u || (mask >> sc) == 0ull);
+        nstreams = block_streams(h, bs, bs, 2u);   // (every block of such a chunk is whole)
+        memcpyed = (h.flags & BLOSC_MEMCPYED) != 0u;
+        shuffled = h.doshuffle && !memcpyed;
+        planes16 = shuffled && nstreams == 2u && (vb & 15u) == 0u;
+        neblock = memcpyed ? bs : bs / nstreams;   // (a stored row is staged as one stream)
+        return ok && nstreams <= (blockDim.x >> 6);
+    }
+};
+
+// the lowest row of the mask (mlo, mhi: its halves, wave-uniform, not both 0), which leaves the mask
+__device__ __forceinline__ uint32_t next_row(uint32_t &mlo, uint32_t &mhi)
+{
+    const uint32_t r = mlo ? (uint32_t)__builtin_ctz(mlo) : 32u + (uint32_t)__builtin_ctz(mhi);
+    if (mlo) mlo &= mlo - 1u;
+    else mhi &= mhi - 1u;
+    return r;
+}
+
+// block `part` of row r -> LDS: decode_block_lds' planes, or, of a memcpyed chunk, the stored row as one stream, so that
+// the calls are read from one address space whatever the chunk.  Workgroup-cooperative, ends in a barrier; the caller
+// holds another before the next row goes over this one.  false (in every thread): the row's stream is corrupt.
+__device__ __forceinline__ bool stage_row(const RowWalk &W, uint32_t r, uint8_t *smem, uint32_t sstride, uint32_t *s_bad)
+{
+    const uint32_t b = r * W.parts + W.part;
+    if (!W.memcpyed) return decode_block_lds(W.ck, W.avail, W.h.hl, b, W.blocksize, W.nstreams, sstride, smem, s_bad);
+    const uint8_t *stored = W.ck + W.h.hl + (uint64_t)b * W.blocksize;
+    const uint32_t nd = W.blocksize >> 2;
+#pragma unroll 1
+    for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) reinterpret_cast<uint32_t *>(smem)[i] = ld32u(stored + 4u * i);
+    if (threadIdx.x < (W.blocksize & 3u)) smem[4u * nd + threadIdx.x] = stored[4u * nd + threadIdx.x];
+    __syncthreads();
+    return true;
+}
+
+// the calls of variants [v0, v0 + 4) of the block stage_row left at smem, in any layout -> a, c (first and second alleles,
+// one call per byte; -9 beyond the block: counts nothing).  The block is cut into streams of neblock bytes, stream j at
+// smem + j * sstride (typesize 2: at most two streams).  The slow path of for_calls16.
+__device__ __forceinline__ void gather4(const RowWalk &W, const uint8_t *smem, uint32_t sstride, uint32_t v0, uint32_t &a,
+                                        uint32_t &c)
+{
+    a = 0xF7F7F7F7u, c = 0xF7F7F7F7u;
+#pragma unroll 1
+    for (uint32_t j = 0; j < 4u; ++j) {
+        const uint32_t v = v0 + j;
+        if (v < W.vb) {
+            const uint32_t p0 = W.shuffled ? v : 2u * v, p1 = W.shuffled ? W.vb + v : 2u * v + 1u;
+            const uint32_t sh = 8u * j;
+            a = (a & ~(0xFFu << sh)) | ((uint32_t)smem[p0 < W.neblock ? p0 : sstride + (p0 - W.neblock)] << sh);
+            c = (c & ~(0xFFu << sh)) | ((uint32_t)smem[p1 < W.neblock ? p1 : sstride + (p1 - W.neblock)] << sh);
+        }
+    }
+}
+
+// f(a, b, w), w = 0..3, for the calls of variants [g + 4 w, g + 4 w + 4), g = 16 (t + k blockDim): a, b hold the two
+// alleles, one call per byte.  Two 16-byte loads of the planes (planes16), gather4 otherwise; no f past the block.
+template <typename F>
+__device__ __forceinline__ void for_calls16(const RowWalk &W, const uint8_t *smem, uint32_t sstride, uint32_t k, F f)
+{
+    const uint32_t g = 16u * (threadIdx.x + blockDim.x * k);
+    if (W.planes16) {
+        if (g >= W.vb) return;
+        const uint4 A = *reinterpret_cast<const uint4 *>(smem + g);
+        const uint4 B = *reinterpret_cast<const uint4 *>(smem + sstride + g);
+        f(A.x, B.x, 0);
+        f(A.y, B.y, 1);
+        f(A.z, B.z, 2);
+        f(A.w, B.w, 3);
+    } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            uint32_t a, c;
+            gather4(W, smem, sstride, g + 4u * (uint32_t)w, a, c);
+            if (g < W.vb) f(a, c, w);   // (past the block gather4 gives calls that count nothing)
+        }
+    }
+}
+
+// bits 0..3 of n -> 0x80 in bytes 0..3 (the four copies of n sit 7 bits apart, so the products never carry into each other)
+__device__ __forceinline__ uint32_t bits_to_bytes(uint32_t n)
+{
+    return (((n & 0xFu) * 0x00204081u) & 0x01010101u) << 7;
+}
+
+// which of a thread's variants count — the range [lo, hi) and the block's bits of vmask (nullptr: all) — is the same for
+// every row, so it is expanded once: take[k][w] has 0x80 in byte j iff variant g + 4 w + j is counted
+__device__ __forceinline__ void expand_take(uint32_t lo, uint32_t hi, const uint32_t *vmask, uint64_t mask_word,
+                                            uint32_t take[2][4])
+{
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
+        uint32_t bits = 0u;
+        if (g < hi && g + 16u > lo) {
+            const uint32_t b0 = lo > g ? lo - g : 0u, b1 = hi - g < 16u ? hi - g : 16u;   // [b0, b1) of the 16: 0 <= b0 < b1
+            bits = ((1u << b1) - 1u) & ~((1u << b0) - 1u);
+            if (vmask != nullptr) bits &= vmask[mask_word + (g >> 5)] >> (g & 16u);
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) take[k][w] = bits_to_bytes(bits >> (4 * w));
+    }
+}
 
 // classifies 4 calls: a, b hold the two alleles of the calls, one call per byte -> 0x80 in the byte of a call whose allele
 // is called (pa, pb), is 1 (ea, eb), whose alleles differ (ne)
@@ -384,6 +534,8 @@ __device__ __forceinline__ void classify4(uint32_t a, uint32_t b, uint32_t &pa, 
     ne = (((d & L7) + L7) | d) & H;                        // 0x80 where the alleles differ
 }
 
+// ---- allele counts straight out of LDS (hhgt_count_alleles) ------------------------------------------------------------
+
 // adds the counters of 4 calls to 4 packed byte counters.  After 64 rows no byte exceeds 128, so the packed adds never
 // carry into the next byte.
 __device__ __forceinline__ void count4(uint32_t a, uint32_t b, uint32_t &an, uint32_t &ac, uint32_t &het, uint32_t &hom)
@@ -396,69 +548,24 @@ __device__ __forceinline__ void count4(uint32_t a, uint32_t b, uint32_t &an, uin
     hom += (ea & eb) >> 7;
 }
 
-// byte p of a decoded block that is cut into streams of neblock bytes, stream j at base + j * sstride (typesize 2: at
-// most two streams; one stream, or a memcpyed block in global memory, has neblock = the block size)
-__device__ __forceinline__ uint32_t stream_byte(const uint8_t *base, uint32_t p, uint32_t neblock, uint32_t sstride)
-{
-    return base[p < neblock ? p : sstride + (p - neblock)];
-}
-
-// the calls of variants [v0, v0 + 4) of a block of vb variants in any layout stream_byte reaches -> a, c (first and second
-// alleles, one call per byte; -9 beyond the block: counts nothing).  Allele j of variant v: byte j * vb + v of a shuffled
-// block (doshuffle, not memcpyed), byte 2 v + j of an interleaved one.  The slow path of both count kernels.
-__device__ __forceinline__ void gather4(const uint8_t *base, uint32_t v0, uint32_t vb, uint32_t doshuffle, bool memcpyed,
-                                        uint32_t neblock, uint32_t sstride, uint32_t &a, uint32_t &c)
-{
-    a = 0xF7F7F7F7u, c = 0xF7F7F7F7u;
-#pragma unroll 1
-    for (uint32_t j = 0; j < 4u; ++j) {
-        const uint32_t v = v0 + j;
-        if (v < vb) {
-            const uint32_t p0 = doshuffle && !memcpyed ? v : 2u * v;
-            const uint32_t p1 = doshuffle && !memcpyed ? vb + v : 2u * v + 1u;
-            const uint32_t sh = 8u * j;
-            a = (a & ~(0xFFu << sh)) | (stream_byte(base, p0, neblock, sstride) << sh);
-            c = (c & ~(0xFFu << sh)) | (stream_byte(base, p1, neblock, sstride) << sh);
-        }
-    }
-}
-
-// grid = n_sel, one selection per workgroup; block = 64 * nwaves (decode_geometry, typesize 2); dynamic LDS = the larger
-// of decode_geometry's and 64 * blockDim + 16.  Thread t counts variants [g, g + 16) of the block for g = 16 (t + k
-// blockDim), k = 0, 1 (blockDim * 32 >= blocksize / 2 for every block size served), in registers, over every selected
-// row: decode_block_lds leaves the row's two byte planes in LDS, the thread reads its 16 calls of each with one 16-byte
-// load (shuffled, split blocks; any other block layout through stream_byte).  Then the counters go through LDS once,
-// variant-major, and out with one agent-scope add per (variant, counter) and consecutive lanes on consecutive words.
+// The row walk above with dynamic LDS = the larger of decode_geometry's and 64 * blockDim + 16.  The thread counts its
+// variants in registers over every selected row.  Then the counters go through LDS once, variant-major, and out with one
+// agent-scope add per (variant, counter) and consecutive lanes on consecutive words.
 __global__ __launch_bounds__(128) void k_count_alleles(const hhgt_count_sel *__restrict__ sel, uint32_t sc, uint32_t vc,
                                                        uint32_t blocksize, uint32_t sstride, uint32_t *__restrict__ counts,
                                                        uint64_t n_out, unsigned long long *n_bad)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ uint32_t s_bad;
-    const uint32_t nwaves = blockDim.x >> 6;
     const hhgt_count_sel *s = sel + blockIdx.x;
-    const uint8_t *ck = reinterpret_cast<const uint8_t *>(s->src_ptr);
-    const uint64_t src_bytes = s->src_bytes, mask = s->row_mask, out_row = s->out_row;
-    const uint32_t part = s->part, lo = s->lo, hi = s->hi;
-    if (threadIdx.x == 0) s_bad = 0;
-    __syncthreads();
-    const uint32_t avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
-    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
-    const uint32_t vb = blocksize >> 1, parts = vc * 2u / blocksize;
-    BloscHdr h;
-    bool ok = blosc_header(ck, avail, chunk_nbytes, 2u, blocksize, h);
-    ok = ok && part < parts && lo < hi && hi <= vb && (sc >= 64u || (mask >> sc) == 0ull) && out_row <= n_out &&
-         hi - lo <= n_out - out_row;
-    const uint32_t nstreams = block_streams(h, blocksize, blocksize, 2u);   // (every block of such a chunk is whole)
-    ok = ok && nstreams <= nwaves;
-    if (!ok) {
-        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
-    const bool memcpyed = (h.flags & BLOSC_MEMCPYED) != 0u;
-    // the fast form: both planes of a shuffled block split into two streams, 16-byte aligned
-    const bool planes16 = !memcpyed && h.doshuffle && nstreams == 2u && (vb & 15u) == 0u;
-    const uint32_t neblock = memcpyed ? blocksize : blocksize / nstreams;
+    const uint64_t out_row = s->out_row;
+    RowWalk W;
+    // (a generic chunk pointer, not global_chunk: with that one the compiler batches the decoder's global loads and the
+    // 32 counters no longer fit five waves per SIMD — tests/test_isa_counts.py)
+    bool ok = W.init(reinterpret_cast<const uint8_t *>(s->src_ptr), s, sc, vc, blocksize, &s_bad);
+    const uint32_t lo = W.lo, hi = W.hi;
+    ok = ok && out_row <= n_out && hi - lo <= n_out - out_row;
+    if (!ok) return bad_selection(n_bad);
     uint32_t acc[2][4][4];   // [k][counter][word]: byte j of word w = variant g + 4 w + j
 #pragma unroll
     for (int k = 0; k < 2; ++k)
@@ -466,47 +573,22 @@ __global__ __launch_bounds__(128) void k_count_alleles(const hhgt_count_sel *__r
         for (int c = 0; c < 4; ++c)
 #pragma unroll
             for (int w = 0; w < 4; ++w) acc[k][c][w] = 0u;
-    uint32_t mlo = uni((uint32_t)mask), mhi = uni((uint32_t)(mask >> 32));
+    uint32_t mlo = uni((uint32_t)W.mask), mhi = uni((uint32_t)(W.mask >> 32));
     bool bad = false;
     while ((mlo | mhi) != 0u) {
-        const uint32_t r = mlo ? (uint32_t)__builtin_ctz(mlo) : 32u + (uint32_t)__builtin_ctz(mhi);
-        if (mlo) mlo &= mlo - 1u;
-        else mhi &= mhi - 1u;
-        const uint32_t b = r * parts + part;
-        const uint8_t *base = smem;
-        if (memcpyed) {
-            base = ck + h.hl + (uint64_t)b * blocksize;
-        } else if (!decode_block_lds(ck, avail, h.hl, b, blocksize, nstreams, sstride, smem, &s_bad)) {
+        const uint32_t r = next_row(mlo, mhi);
+        if (!stage_row(W, r, smem, sstride, &s_bad)) {
             bad = true;
             break;
         }
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
-            if (planes16) {
-                if (g < vb) {
-                    const uint4 A = *reinterpret_cast<const uint4 *>(smem + g);
-                    const uint4 B = *reinterpret_cast<const uint4 *>(smem + sstride + g);
-                    count4(A.x, B.x, acc[k][0][0], acc[k][1][0], acc[k][2][0], acc[k][3][0]);
-                    count4(A.y, B.y, acc[k][0][1], acc[k][1][1], acc[k][2][1], acc[k][3][1]);
-                    count4(A.z, B.z, acc[k][0][2], acc[k][1][2], acc[k][2][2], acc[k][3][2]);
-                    count4(A.w, B.w, acc[k][0][3], acc[k][1][3], acc[k][2][3], acc[k][3][3]);
-                }
-            } else {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    uint32_t a, c;
-                    gather4(base, g + 4u * (uint32_t)w, vb, h.doshuffle, memcpyed, neblock, sstride, a, c);
-                    count4(a, c, acc[k][0][w], acc[k][1][w], acc[k][2][w], acc[k][3][w]);
-                }
-            }
-        }
-        if (!memcpyed) __syncthreads();   // the planes are read before the next row is decoded over them
+        for (int k = 0; k < 2; ++k)
+            for_calls16(W, smem, sstride, (uint32_t)k, [&](uint32_t a, uint32_t b, int w) {
+                count4(a, b, acc[k][0][w], acc[k][1][w], acc[k][2][w], acc[k][3][w]);
+            });
+        __syncthreads();   // the block is read before the next row goes over it
     }
-    if (bad) {
-        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
+    if (bad) return bad_selection(n_bad);
     // flush, in two passes of 16 * blockDim variants: the packed counters -> LDS as [variant][AN, AC, HET, HOM] bytes (the
     // order of d_counts), then word i of the pass -> d_counts, skipping zeros
     uint32_t *out = counts + out_row * 4u;           // variant v of the block, v in [lo, hi): out + 4 (v - lo)
@@ -540,12 +622,6 @@ __global__ __launch_bounds__(128) void k_count_alleles(const hhgt_count_sel *__r
 
 // ---- per-sample counts straight out of LDS (hhgt_count_samples) --------------------------------------------------------
 
-// bits 0..3 of n -> 0x80 in bytes 0..3 (the four copies of n sit 7 bits apart, so the products never carry into each other)
-__device__ __forceinline__ uint32_t bits_to_bytes(uint32_t n)
-{
-    return (((n & 0xFu) * 0x00204081u) & 0x01010101u) << 7;
-}
-
 // adds the counters of the calls of a, b (count4's classes) that m selects (0x80 in the byte of a counted call)
 __device__ __forceinline__ void tally4(uint32_t a, uint32_t b, uint32_t m, uint32_t &an, uint32_t &ac, uint32_t &het,
                                        uint32_t &hom)
@@ -572,13 +648,10 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t x)
            (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
 }
 
-// grid = n_sel, one selection per workgroup; block = 64 * nwaves and dynamic LDS as decode_geometry says (typesize 2: two
-// waves).  The variants of a thread are k_count_alleles': [g, g + 16) for g = 16 (t + k blockDim), k = 0, 1.  Which of them
-// count — the range [lo, hi) and the block's bits of vmask — is the same for every row, so it is expanded once, to a byte
-// mask per 4 calls.  Per selected row: decode_block_lds leaves the row's planes in LDS, the thread classifies its calls
-// (count4's classes), masks, popcounts; the four totals of the row travel as two words of 16-bit fields (a block has at
-// most 2 x 4096 alleles, so no field carries) through a DPP reduction to one LDS slot per wave and row.  At the end thread r
-// adds row r's counters to d_counts: at most 4 atomics per row and selection, zeros skipped.
+// The row walk above under expand_take's mask.  Per selected row the thread classifies its calls (count4's classes), masks,
+// popcounts; the four totals of the row travel as two words of 16-bit fields (a block has at most 2 x 4096 alleles, so no
+// field carries) through a DPP reduction to one LDS slot per wave and row.  At the end thread r adds row r's counters to
+// d_counts: at most 4 atomics per row and selection, zeros skipped.
 __global__ __launch_bounds__(128, 8) void k_count_samples(const hhgt_sample_sel *__restrict__ sel, uint32_t sc, uint32_t vc,
                                                        uint32_t blocksize, uint32_t sstride,
                                                        const uint32_t *__restrict__ vmask, uint64_t vmask_words,
@@ -591,93 +664,28 @@ __global__ __launch_bounds__(128, 8) void k_count_samples(const hhgt_sample_sel 
     const uint32_t nwaves = blockDim.x >> 6;
     const uint32_t wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;
     const hhgt_sample_sel *s = sel + blockIdx.x;
-    // (a chunk lies in global memory: said through the address space, its loads are global_load, not flat_load)
-    const uint8_t *ck = (const uint8_t *)(const __attribute__((address_space(1))) uint8_t *)s->src_ptr;
-    const uint64_t src_bytes = s->src_bytes, mask = s->row_mask, out_row = s->out_row, mask_word = s->mask_word;
-    const uint32_t part = s->part, lo = s->lo, hi = s->hi;
-    if (threadIdx.x == 0) s_bad = 0;
-    __syncthreads();
-    const uint32_t avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
-    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
-    const uint32_t vb = blocksize >> 1, parts = vc * 2u / blocksize, mwords = (vb + 31u) >> 5;
-    BloscHdr h;
-    bool ok = blosc_header(ck, avail, chunk_nbytes, 2u, blocksize, h);
+    const uint64_t out_row = s->out_row, mask_word = s->mask_word;
+    RowWalk W;
+    bool ok = W.init(global_chunk(s->src_ptr), s, sc, vc, blocksize, &s_bad);
+    const uint64_t mask = W.mask;
     const uint32_t top = mask ? 63u - (uint32_t)__builtin_clzll(mask) : 0u;      // the highest selected row
-    ok = ok && part < parts && lo < hi && hi <= vb && (sc >= 64u || (mask >> sc) == 0ull) &&
-         (mask == 0ull || (out_row < n_out && top < n_out - out_row)) &&
-         (vmask == nullptr || (mask_word <= vmask_words && mwords <= vmask_words - mask_word));
-    const uint32_t nstreams = block_streams(h, blocksize, blocksize, 2u);   // (every block of such a chunk is whole)
-    ok = ok && nstreams <= nwaves && nwaves <= 2u;
-    if (!ok) {
-        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
-    const bool memcpyed = (h.flags & BLOSC_MEMCPYED) != 0u;
-    const bool shuffled = h.doshuffle && !memcpyed;
-    // the fast form: both planes of a shuffled block split into two streams, 16-byte aligned
-    const bool planes16 = shuffled && nstreams == 2u && (vb & 15u) == 0u;
-    const uint32_t neblock = memcpyed ? blocksize : blocksize / nstreams;
-    uint32_t take[2][4];   // [k][word]: 0x80 in byte j = variant g + 4 w + j is counted
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
-        uint32_t bits = 0u;
-        if (g < hi && g + 16u > lo) {
-            const uint32_t b0 = lo > g ? lo - g : 0u, b1 = hi - g < 16u ? hi - g : 16u;   // [b0, b1) of the 16: 0 <= b0 < b1
-            bits = ((1u << b1) - 1u) & ~((1u << b0) - 1u);
-            if (vmask != nullptr) bits &= vmask[mask_word + (g >> 5)] >> (g & 16u);
-        }
-#pragma unroll
-        for (int w = 0; w < 4; ++w) take[k][w] = bits_to_bytes(bits >> (4 * w));
-    }
+    ok = ok && nwaves <= 2u && (mask == 0ull || (out_row < n_out && top < n_out - out_row)) &&
+         (vmask == nullptr || (mask_word <= vmask_words && W.mwords <= vmask_words - mask_word));
+    if (!ok) return bad_selection(n_bad);
+    uint32_t take[2][4];
+    expand_take(W.lo, W.hi, vmask, mask_word, take);
     uint32_t mlo = uni((uint32_t)mask), mhi = uni((uint32_t)(mask >> 32));
-    bool bad = false;
     while ((mlo | mhi) != 0u) {
-        const uint32_t r = mlo ? (uint32_t)__builtin_ctz(mlo) : 32u + (uint32_t)__builtin_ctz(mhi);
-        if (mlo) mlo &= mlo - 1u;
-        else mhi &= mhi - 1u;
-        const uint32_t b = r * parts + part;
-        if (memcpyed) {
-            // the stored row goes to LDS as one stream, so that the counting below reads one address space
-            const uint8_t *stored = ck + h.hl + (uint64_t)b * blocksize;
-            const uint32_t nd = blocksize >> 2;
-#pragma unroll 1
-            for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) reinterpret_cast<uint32_t *>(smem)[i] = ld32u(stored + 4u * i);
-            if (threadIdx.x < (blocksize & 3u)) smem[4u * nd + threadIdx.x] = stored[4u * nd + threadIdx.x];
-            __syncthreads();
-        } else if (!decode_block_lds(ck, avail, h.hl, b, blocksize, nstreams, sstride, smem, &s_bad)) {
-            bad = true;
-            break;
-        }
+        const uint32_t r = next_row(mlo, mhi);
+        if (!stage_row(W, r, smem, sstride, &s_bad)) return bad_selection(n_bad);
         uint32_t an = 0u, ac = 0u, het = 0u, hom = 0u;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
-            if (planes16) {
-                if (g < vb) {
-                    const uint4 A = *reinterpret_cast<const uint4 *>(smem + g);
-                    const uint4 B = *reinterpret_cast<const uint4 *>(smem + sstride + g);
-                    tally4(A.x, B.x, take[k][0], an, ac, het, hom);
-                    tally4(A.y, B.y, take[k][1], an, ac, het, hom);
-                    tally4(A.z, B.z, take[k][2], an, ac, het, hom);
-                    tally4(A.w, B.w, take[k][3], an, ac, het, hom);
-                }
-            } else {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    uint32_t a, c;
-                    gather4(smem, g + 4u * (uint32_t)w, vb, h.doshuffle, memcpyed, neblock, sstride, a, c);
-                    tally4(a, c, take[k][w], an, ac, het, hom);
-                }
-            }
-        }
+        for (int k = 0; k < 2; ++k)
+            for_calls16(W, smem, sstride, (uint32_t)k,
+                        [&](uint32_t a, uint32_t b, int w) { tally4(a, b, take[k][w], an, ac, het, hom); });
         const uint32_t t0 = wave_sum(an | (ac << 16)), t1 = wave_sum(het | (hom << 16));
         if (lane == 0u) s_rows[wave][r] = make_uint2(t0, t1);
-        __syncthreads();   // the planes are read before the next row is decoded over them; every wave's slot is written
-    }
-    if (bad) {
-        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
-        return;
+        __syncthreads();   // the block is read before the next row goes over it; every wave's slot is written
     }
     if (threadIdx.x < 64u && ((mask >> threadIdx.x) & 1ull)) {
         uint2 t = s_rows[0][threadIdx.x];
@@ -716,12 +724,11 @@ __device__ __forceinline__ void planes4(uint32_t a, uint32_t b, uint32_t m, uint
     alt |= bytes_to_bits(ea & eb & m) << sh;
 }
 
-// grid = n_sel, one selection per workgroup; block, dynamic LDS, the variants of a thread ([g, g + 16) for g = 16 (t + k
-// blockDim), k = 0, 1) and the take[][] expansion of range and variant mask as k_count_samples.  Per selected row the thread
-// turns its 16 calls into 16 bits of each plane; lanes 2 i and 2 i + 1 hold the halves of word (t + k blockDim) / 2 of the
-// block, the odd lane's half crosses over with one DPP quad_perm, and the even lane stores the word of each plane — plain
-// vector stores: a (row, block) belongs to one workgroup.  A stream that turns out corrupt after some rows were written gets
-// those rows' words zeroed again (the caller's buffer was zero there), so a bad selection leaves nothing behind.
+// The row walk above under expand_take's mask.  Per selected row the thread turns its 16 calls into 16 bits of each plane;
+// lanes 2 i and 2 i + 1 hold the halves of word (t + k blockDim) / 2 of the block, the odd lane's half crosses over with one
+// DPP quad_perm, and the even lane stores the word of each plane — plain vector stores: a (row, block) belongs to one
+// workgroup.  A stream that turns out corrupt after some rows were written gets those rows' words zeroed again (the caller's
+// buffer was zero there), so a bad selection leaves nothing behind.
 __global__ __launch_bounds__(128, 8) void k_genotype_planes(const hhgt_plane_sel *__restrict__ sel, uint32_t sc, uint32_t vc,
                                                             uint32_t blocksize, uint32_t sstride,
                                                             const uint32_t *__restrict__ vmask, uint64_t vmask_words,
@@ -732,87 +739,35 @@ __global__ __launch_bounds__(128, 8) void k_genotype_planes(const hhgt_plane_sel
     __shared__ uint32_t s_bad;
     const uint32_t nwaves = blockDim.x >> 6;
     const hhgt_plane_sel *s = sel + blockIdx.x;
-    const uint8_t *ck = (const uint8_t *)(const __attribute__((address_space(1))) uint8_t *)s->src_ptr;
-    const uint64_t src_bytes = s->src_bytes, mask = s->row_mask, out_row = s->out_row, mask_word = s->mask_word;
-    const uint64_t out_word = s->out_word;
-    const uint32_t part = s->part, lo = s->lo, hi = s->hi;
-    if (threadIdx.x == 0) s_bad = 0;
-    __syncthreads();
-    const uint32_t avail = src_bytes > 0xffffffffull ? 0u : (uint32_t)src_bytes;   // (too large: fails the header)
-    const uint64_t chunk_nbytes = (uint64_t)sc * vc * 2u;
-    const uint32_t vb = blocksize >> 1, parts = vc * 2u / blocksize, mwords = (vb + 31u) >> 5;
-    BloscHdr h;
-    bool ok = blosc_header(ck, avail, chunk_nbytes, 2u, blocksize, h);
+    const uint64_t out_row = s->out_row, mask_word = s->mask_word, out_word = s->out_word;
+    RowWalk W;
+    bool ok = W.init(global_chunk(s->src_ptr), s, sc, vc, blocksize, &s_bad);
+    const uint64_t mask = W.mask;
+    const uint32_t mwords = W.mwords;
     const uint32_t top = mask ? 63u - (uint32_t)__builtin_clzll(mask) : 0u;      // the highest selected row
-    ok = ok && part < parts && lo < hi && hi <= vb && (sc >= 64u || (mask >> sc) == 0ull) &&
-         (mask == 0ull || (out_row < n_rows && top < n_rows - out_row)) &&
+    ok = ok && nwaves <= 2u && (mask == 0ull || (out_row < n_rows && top < n_rows - out_row)) &&
          out_word <= row_words && mwords <= row_words - out_word &&
          (vmask == nullptr || (mask_word <= vmask_words && mwords <= vmask_words - mask_word));
-    const uint32_t nstreams = block_streams(h, blocksize, blocksize, 2u);   // (every block of such a chunk is whole)
-    ok = ok && nstreams <= nwaves && nwaves <= 2u;
-    if (!ok) {
-        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
-        return;
-    }
-    const bool memcpyed = (h.flags & BLOSC_MEMCPYED) != 0u;
-    const bool shuffled = h.doshuffle && !memcpyed;
-    const bool planes16 = shuffled && nstreams == 2u && (vb & 15u) == 0u;
-    const uint32_t neblock = memcpyed ? blocksize : blocksize / nstreams;
-    uint32_t take[2][4];   // [k][word]: 0x80 in byte j = variant g + 4 w + j is counted
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t g = 16u * (threadIdx.x + blockDim.x * (uint32_t)k);
-        uint32_t bits = 0u;
-        if (g < hi && g + 16u > lo) {
-            const uint32_t b0 = lo > g ? lo - g : 0u, b1 = hi - g < 16u ? hi - g : 16u;   // [b0, b1) of the 16: 0 <= b0 < b1
-            bits = ((1u << b1) - 1u) & ~((1u << b0) - 1u);
-            if (vmask != nullptr) bits &= vmask[mask_word + (g >> 5)] >> (g & 16u);
-        }
-#pragma unroll
-        for (int w = 0; w < 4; ++w) take[k][w] = bits_to_bytes(bits >> (4 * w));
-    }
+    if (!ok) return bad_selection(n_bad);
+    uint32_t take[2][4];
+    expand_take(W.lo, W.hi, vmask, mask_word, take);
     const uint64_t plane_words = n_rows * row_words;
     uint32_t mlo = uni((uint32_t)mask), mhi = uni((uint32_t)(mask >> 32));
     uint32_t bad_row = 64u;   // the row whose stream was corrupt
     while ((mlo | mhi) != 0u) {
-        const uint32_t r = mlo ? (uint32_t)__builtin_ctz(mlo) : 32u + (uint32_t)__builtin_ctz(mhi);
-        if (mlo) mlo &= mlo - 1u;
-        else mhi &= mhi - 1u;
-        const uint32_t b = r * parts + part;
-        if (memcpyed) {
-            // the stored row goes to LDS as one stream, so that the classification below reads one address space
-            const uint8_t *stored = ck + h.hl + (uint64_t)b * blocksize;
-            const uint32_t nd = blocksize >> 2;
-#pragma unroll 1
-            for (uint32_t i = threadIdx.x; i < nd; i += blockDim.x) reinterpret_cast<uint32_t *>(smem)[i] = ld32u(stored + 4u * i);
-            if (threadIdx.x < (blocksize & 3u)) smem[4u * nd + threadIdx.x] = stored[4u * nd + threadIdx.x];
-            __syncthreads();
-        } else if (!decode_block_lds(ck, avail, h.hl, b, blocksize, nstreams, sstride, smem, &s_bad)) {
+        const uint32_t r = next_row(mlo, mhi);
+        if (!stage_row(W, r, smem, sstride, &s_bad)) {
             bad_row = r;
             break;
         }
         uint32_t *row = planes + (out_row + r) * row_words + out_word;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const uint32_t t = threadIdx.x + blockDim.x * (uint32_t)k, g = 16u * t;
+            const uint32_t t = threadIdx.x + blockDim.x * (uint32_t)k;
             uint32_t het = 0u, ref = 0u, alt = 0u;
-            if (planes16) {
-                if (g < vb) {
-                    const uint4 A = *reinterpret_cast<const uint4 *>(smem + g);
-                    const uint4 B = *reinterpret_cast<const uint4 *>(smem + sstride + g);
-                    planes4(A.x, B.x, take[k][0], 0u, het, ref, alt);
-                    planes4(A.y, B.y, take[k][1], 4u, het, ref, alt);
-                    planes4(A.z, B.z, take[k][2], 8u, het, ref, alt);
-                    planes4(A.w, B.w, take[k][3], 12u, het, ref, alt);
-                }
-            } else if (g < vb) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    uint32_t a, c;
-                    gather4(smem, g + 4u * (uint32_t)w, vb, h.doshuffle, memcpyed, neblock, sstride, a, c);
-                    planes4(a, c, take[k][w], 4u * (uint32_t)w, het, ref, alt);
-                }
-            }
+            for_calls16(W, smem, sstride, (uint32_t)k, [&](uint32_t a, uint32_t b, int w) {
+                planes4(a, b, take[k][w], 4u * (uint32_t)w, het, ref, alt);
+            });
             // the neighbour's 16 bits of each plane (quad_perm [1, 0, 3, 2]); every lane of the wave is here
             const uint32_t hr = het | (ref << 16);
             const uint32_t nhr = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hr, 0xB1, 0xf, 0xf, false);
@@ -824,7 +779,7 @@ __global__ __launch_bounds__(128, 8) void k_genotype_planes(const hhgt_plane_sel
                 row[2u * plane_words + w] = alt | (nalt << 16);
             }
         }
-        __syncthreads();   // the planes are read before the next row is decoded (or copied) over them
+        __syncthreads();   // the block is read before the next row goes over it
     }
     if (bad_row < 64u) {
         // rows below the corrupt one were written: back to the zeros the caller put there
@@ -834,7 +789,7 @@ __global__ __launch_bounds__(128, 8) void k_genotype_planes(const hhgt_plane_sel
             uint32_t *row = planes + (out_row + r) * row_words + out_word;
             for (uint32_t w = threadIdx.x; w < mwords; w += blockDim.x) row[w] = row[plane_words + w] = row[2u * plane_words + w] = 0u;
         }
-        if (threadIdx.x == 0) atomicAdd(n_bad, 1ull);
+        bad_selection(n_bad);
     }
 }
 
@@ -910,57 +865,46 @@ int launch_decode_sel(const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chun
     return HHGT_OK;
 }
 
-int launch_count_alleles(const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
-                         uint32_t *d_counts, uint64_t n_out, unsigned long long *d_bad, hipStream_t st)
+// the launch of a row-walk kernel: one workgroup per selection, decode_geometry's shape for typesize 2 (blocksize <= 8192:
+// at most 8.4 KiB of LDS, no opt-in needed), at least lds_floor bytes of dynamic LDS; args follow sstride in the kernel's list
+template <typename Kernel, typename Sel, typename... Args>
+static int launch_row_kernel(const char *who, Kernel kernel, size_t lds_floor, hipStream_t st, const Sel *d_sel, uint32_t n_sel,
+                             uint32_t sc, uint32_t vc, int blocksize, Args... args)
 {
     if (n_sel == 0) return HHGT_OK;
     uint32_t nwaves, sstride;
     size_t lds;
     if (int rc = decode_geometry(2, blocksize, &nwaves, &sstride, &lds)) return rc;
-    const size_t flush = 64u * 64u * nwaves + 16u;   // one pass of the flush: 16 variants x 4 counter bytes per thread
-    if (lds < flush) lds = flush;                     // (blocksize <= 8192: at most 8.4 KiB, no opt-in needed)
+    if (lds < lds_floor) lds = lds_floor;
     if (n_sel > 0x7fffffffu) {
-        hhgt_set_error("count_alleles: too many selections");
+        hhgt_set_error("%s: too many selections", who);
         return HHGT_ERR_ARG;
     }
-    hipLaunchKernelGGL(k_count_alleles, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
-                       sstride, d_counts, n_out, d_bad);
+    hipLaunchKernelGGL(kernel, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize, sstride, args...);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
+}
+
+int launch_count_alleles(const hhgt_count_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
+                         uint32_t *d_counts, uint64_t n_out, unsigned long long *d_bad, hipStream_t st)
+{
+    const size_t flush = 64u * 64u * 2u + 16u;   // one pass of the flush: 16 variants x 4 counter bytes per thread, two waves
+    return launch_row_kernel("count_alleles", k_count_alleles, flush, st, d_sel, n_sel, sc, vc, blocksize, d_counts, n_out,
+                             d_bad);
 }
 
 int launch_count_samples(const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
                          const uint32_t *d_vmask, uint64_t vmask_words, uint32_t *d_counts, uint64_t n_out,
                          unsigned long long *d_bad, hipStream_t st)
 {
-    if (n_sel == 0) return HHGT_OK;
-    uint32_t nwaves, sstride;
-    size_t lds;
-    if (int rc = decode_geometry(2, blocksize, &nwaves, &sstride, &lds)) return rc;   // (blocksize <= 8192: no opt-in needed)
-    if (n_sel > 0x7fffffffu) {
-        hhgt_set_error("count_samples: too many selections");
-        return HHGT_ERR_ARG;
-    }
-    hipLaunchKernelGGL(k_count_samples, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
-                       sstride, d_vmask, vmask_words, d_counts, n_out, d_bad);
-    HIP_TRY(hipGetLastError());
-    return HHGT_OK;
+    return launch_row_kernel("count_samples", k_count_samples, 0, st, d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words,
+                             d_counts, n_out, d_bad);
 }
 
 int launch_genotype_planes(const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
                            const uint32_t *d_vmask, uint64_t vmask_words, uint32_t *d_planes, uint64_t n_rows,
                            uint64_t row_words, unsigned long long *d_bad, hipStream_t st)
 {
-    if (n_sel == 0) return HHGT_OK;
-    uint32_t nwaves, sstride;
-    size_t lds;
-    if (int rc = decode_geometry(2, blocksize, &nwaves, &sstride, &lds)) return rc;   // (blocksize <= 8192: no opt-in needed)
-    if (n_sel > 0x7fffffffu) {
-        hhgt_set_error("genotype_planes: too many selections");
-        return HHGT_ERR_ARG;
-    }
-    hipLaunchKernelGGL(k_genotype_planes, dim3(n_sel), dim3(64u * nwaves), lds, st, d_sel, sc, vc, (uint32_t)blocksize,
-                       sstride, d_vmask, vmask_words, d_planes, n_rows, row_words, d_bad);
-    HIP_TRY(hipGetLastError());
-    return HHGT_OK;
+    return launch_row_kernel("genotype_planes", k_genotype_planes, 0, st, d_sel, n_sel, sc, vc, blocksize, d_vmask,
+                             vmask_words, d_planes, n_rows, row_words, d_bad);
 }

@@ -399,28 +399,58 @@ class Context:
                                                   _ptr(dst), C.byref(bad), _stream()))
         return dst, int(bad.value)
 
+    def _vmask_arg(self, vmask):
+        """a variant mask as the row kernels take it -> (device tensor or None, words): None, a uint32 numpy array, or an
+        int32 / uint32 device tensor"""
+        if vmask is None:
+            return None, 0
+        if not torch.is_tensor(vmask):
+            vmask = torch.from_numpy(np.ascontiguousarray(vmask, dtype=np.uint32).view(np.int32))
+        vmask = vmask.to(self.device)
+        if vmask.dtype not in (torch.int32, torch.uint32) or vmask.dim() != 1 or not vmask.is_contiguous():
+            raise ValueError("vmask: contiguous uint32 words (store.pack_variant_mask)")
+        words = vmask.numel()
+        if words == 0:      # (a mask without words is still a mask: every selection is past it)
+            vmask = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return vmask, words
+
+    def _row_kernel(self, fn, sel, sc, vc, typesize, blocksize, out, *args):
+        """one call of a row kernel (hhgt_count_alleles, hhgt_count_samples, hhgt_genotype_planes): the selections
+        uploaded in one copy, fn(ctx, d_sel, n, sc, vc, typesize, blocksize, *args, &n_bad, stream).  -> (out, n_bad)"""
+        n = len(sel)
+        with torch.cuda.device(self.device):
+            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
+            bad = C.c_uint64(0)
+            check(fn(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize, *args, C.byref(bad), _stream()))
+        return out, int(bad.value)
+
+    @staticmethod
+    def _row_sel(sel, sel_dtype, vc, blocksize):
+        """-> (the selections as a contiguous array of sel_dtype, the block size: by default the row's, at most 8 KiB)"""
+        if blocksize is None:
+            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
+        return np.ascontiguousarray(sel, dtype=sel_dtype), blocksize
+
+    def _counts_arg(self, counts, n_out):
+        """the counts tensor of count_alleles / count_samples: the caller's, or zeros [n_out(), 4]"""
+        if counts is None:
+            counts = torch.zeros((int(n_out()), 4), dtype=torch.int32, device=self.device)
+        if (counts.dtype not in (torch.int32, torch.uint32) or counts.dim() != 2 or counts.shape[1] != 4
+                or not counts.is_contiguous()):
+            raise ValueError("counts: a contiguous int32 tensor [n_out, 4]")
+        return counts
+
     def count_alleles(self, sel, sc, vc, n_out=None, typesize=DEFAULT_TYPESIZE, blocksize=None, counts=None):
         """per-variant allele counts (hhgt_count_alleles): sel is a numpy structured array of COUNT_SEL_DTYPE (device
         chunk addresses, block `part` of the rows, row mask, variants [lo, hi), out_row), uploaded in one copy.  The
         counts are ADDED to `counts`, an int32 tensor [n_out, 4] (the kernel's uint32 words; AN, AC, HET, HOM_ALT; default:
         zeros just large enough for the selections), so calls may accumulate into one buffer.  -> (counts, n_bad)"""
-        if blocksize is None:
-            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
-        sel = np.ascontiguousarray(sel, dtype=COUNT_SEL_DTYPE)
-        n = len(sel)
+        sel, blocksize = self._row_sel(sel, COUNT_SEL_DTYPE, vc, blocksize)
         with torch.cuda.device(self.device):
-            if counts is None:
-                if n_out is None:
-                    n_out = int((sel["out_row"] + sel["hi"] - sel["lo"]).max()) if n else 0
-                counts = torch.zeros((int(n_out), 4), dtype=torch.int32, device=self.device)
-            if (counts.dtype not in (torch.int32, torch.uint32) or counts.dim() != 2 or counts.shape[1] != 4
-                    or not counts.is_contiguous()):
-                raise ValueError("counts: a contiguous int32 tensor [n_out, 4]")
-            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
-            bad = C.c_uint64(0)
-            check(self.lib.hhgt_count_alleles(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize,
-                                              _ptr(counts), counts.shape[0], C.byref(bad), _stream()))
-        return counts, int(bad.value)
+            counts = self._counts_arg(counts, lambda: n_out if n_out is not None else
+                                      int((sel["out_row"] + sel["hi"] - sel["lo"]).max()) if len(sel) else 0)
+            return self._row_kernel(self.lib.hhgt_count_alleles, sel, sc, vc, typesize, blocksize, counts,
+                                    _ptr(counts), counts.shape[0])
 
     def count_samples(self, sel, sc, vc, n_out=None, typesize=DEFAULT_TYPESIZE, blocksize=None, vmask=None, counts=None):
         """per-sample counts (hhgt_count_samples): sel is a numpy structured array of SAMPLE_SEL_DTYPE (device chunk
@@ -429,32 +459,13 @@ class Context:
         (store.pack_variant_mask): a uint32 numpy array, or an int32 / uint32 device tensor.  The counts are ADDED to
         `counts`, an int32 tensor [n_out, 4] (AN, AC, HET, HOM_ALT per sample row; default: zeros just large enough for
         the selections), so calls may accumulate into one buffer.  -> (counts, n_bad)"""
-        if blocksize is None:
-            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
-        sel = np.ascontiguousarray(sel, dtype=SAMPLE_SEL_DTYPE)
-        n = len(sel)
+        sel, blocksize = self._row_sel(sel, SAMPLE_SEL_DTYPE, vc, blocksize)
         with torch.cuda.device(self.device):
-            if counts is None:
-                if n_out is None:
-                    n_out = int(sel["out_row"].max()) + int(sc) if n else 0
-                counts = torch.zeros((int(n_out), 4), dtype=torch.int32, device=self.device)
-            if (counts.dtype not in (torch.int32, torch.uint32) or counts.dim() != 2 or counts.shape[1] != 4
-                    or not counts.is_contiguous()):
-                raise ValueError("counts: a contiguous int32 tensor [n_out, 4]")
-            if vmask is not None:
-                if not torch.is_tensor(vmask):
-                    vmask = torch.from_numpy(np.ascontiguousarray(vmask, dtype=np.uint32).view(np.int32))
-                vmask = vmask.to(self.device)
-                if vmask.dtype not in (torch.int32, torch.uint32) or vmask.dim() != 1 or not vmask.is_contiguous():
-                    raise ValueError("vmask: contiguous uint32 words (store.pack_variant_mask)")
-            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
-            bad = C.c_uint64(0)
-            words = 0 if vmask is None else vmask.numel()
-            if vmask is not None and words == 0:      # (a mask without words is still a mask: every selection is past it)
-                vmask = torch.zeros(1, dtype=torch.int32, device=self.device)
-            check(self.lib.hhgt_count_samples(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize, _ptr(vmask),
-                                              words, _ptr(counts), counts.shape[0], C.byref(bad), _stream()))
-        return counts, int(bad.value)
+            counts = self._counts_arg(counts, lambda: n_out if n_out is not None else
+                                      int(sel["out_row"].max()) + int(sc) if len(sel) else 0)
+            vmask, words = self._vmask_arg(vmask)
+            return self._row_kernel(self.lib.hhgt_count_samples, sel, sc, vc, typesize, blocksize, counts,
+                                    _ptr(vmask), words, _ptr(counts), counts.shape[0])
 
     def genotype_planes(self, sel, sc, vc, n_rows=None, row_words=None, typesize=DEFAULT_TYPESIZE, blocksize=None,
                         vmask=None, planes=None):
@@ -462,9 +473,7 @@ class Context:
         selection plus out_word), uploaded in one copy; vmask as count_samples takes it.  planes: an int32 tensor
         [3, n_rows, row_words] (HET, HOM_REF, HOM_ALT; 32 variants per word) that the caller has zeroed where the
         selections write; default: zeros just large enough for them.  -> (planes, n_bad)"""
-        if blocksize is None:
-            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
-        sel = np.ascontiguousarray(sel, dtype=PLANE_SEL_DTYPE)
+        sel, blocksize = self._row_sel(sel, PLANE_SEL_DTYPE, vc, blocksize)
         n = len(sel)
         with torch.cuda.device(self.device):
             if planes is None:
@@ -476,21 +485,10 @@ class Context:
             if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
                     or not planes.is_contiguous()):
                 raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
-            if vmask is not None:
-                if not torch.is_tensor(vmask):
-                    vmask = torch.from_numpy(np.ascontiguousarray(vmask, dtype=np.uint32).view(np.int32))
-                vmask = vmask.to(self.device)
-                if vmask.dtype not in (torch.int32, torch.uint32) or vmask.dim() != 1 or not vmask.is_contiguous():
-                    raise ValueError("vmask: contiguous uint32 words (store.pack_variant_mask)")
-            d_sel = torch.from_numpy(sel.view(np.uint8)).to(self.device) if n else None
-            bad = C.c_uint64(0)
-            words = 0 if vmask is None else vmask.numel()
-            if vmask is not None and words == 0:      # (a mask without words is still a mask: every selection is past it)
-                vmask = torch.zeros(1, dtype=torch.int32, device=self.device)
-            check(self.lib.hhgt_genotype_planes(self.h, _ptr(d_sel), n, int(sc), int(vc), typesize, blocksize, _ptr(vmask),
-                                                words, _ptr(planes) if planes.numel() else None, planes.shape[1],
-                                                planes.shape[2], C.byref(bad), _stream()))
-        return planes, int(bad.value)
+            vmask, words = self._vmask_arg(vmask)
+            return self._row_kernel(self.lib.hhgt_genotype_planes, sel, sc, vc, typesize, blocksize, planes,
+                                    _ptr(vmask), words, _ptr(planes) if planes.numel() else None, planes.shape[1],
+                                    planes.shape[2])
 
     def pair_counts(self, planes, w_lo=0, w_hi=None, table=None):
         """pairwise counts (hhgt_pair_counts) over the words [w_lo, w_hi) (default: all) of genotype planes [3, n, words]:

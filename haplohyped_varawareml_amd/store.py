@@ -541,21 +541,30 @@ class GenotypeStore:
         counts = torch.zeros((v_hi - v_lo, 4), dtype=torch.int32, device=ctx.device)
         if not len(plan):
             return counts
+        self._run_plan(group, plan, slab_bytes, COUNT_SEL_DTYPE, "count_blocks", lambda dsel: ctx.count_alleles(
+            dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, counts=counts))
+        return counts
+
+    def _run_plan(self, group, plan, slab_bytes, sel_dtype, stat_key, call):
+        """runs the selections `plan` of a group through a row kernel, slab by slab (_scan_slabs): a slab's selections
+        become sel_dtype records — the chunk's address and size from the slab, every other field the plan has from the
+        plan —, call(records) -> (_, n_bad) launches them and synchronises; RuntimeError if a selection was bad;
+        stats[stat_key] counts the blocks decoded (one per selected row and selection)."""
+        fields = [f for f in sel_dtype.names if f in plan.dtype.names]
         blocks = np.array([bin(int(m)).count("1") for m in plan["row_mask"]], np.int64)
 
         def launch(chunks, keys, rows):
-            dsel = np.zeros(len(rows), COUNT_SEL_DTYPE)
+            dsel = np.zeros(len(rows), sel_dtype)
             dsel["src_ptr"] = [chunks[keys[i]].data_ptr() for i in rows]
             dsel["src_bytes"] = [chunks[keys[i]].numel() for i in rows]
-            for f in ("row_mask", "out_row", "part", "lo", "hi"):
+            for f in fields:
                 dsel[f] = plan[f][rows]
-            _, bad = ctx.count_alleles(dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, counts=counts)
+            _, bad = call(dsel)
             if bad:
                 raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
-            self.stats["count_blocks"] += int(blocks[rows].sum())
+            self.stats[stat_key] += int(blocks[rows].sum())
 
         self._scan_slabs(group, plan, slab_bytes, launch)
-        return counts
 
     def _scan_slabs(self, group, plan, slab_bytes, launch):
         """the chunk handling of a count over the selections `plan` (vcol / scol per selection, plan order: chunk columns
@@ -604,6 +613,47 @@ class GenotypeStore:
                 raise KeyError(g)
         return names
 
+    def _group_queries(self, who, groups, samples, v_lo, v_hi, variant_mask):
+        """what sample_counts and pair_counts (`who`, for the messages) do with their arguments first -> (idx, queries):
+        idx, the sample indices (int64 array), and a generator of (group, lo, hi, n_var, vmask) per group — its variant
+        range, checked, and its variant mask packed (pack_variant_mask) and on the device, or None."""
+        import torch
+        bs = self._blocksize()
+        names = self._group_list(groups)
+        if len(names) != 1 and (int(v_lo) != 0 or v_hi is not None):
+            raise ValueError(f"{who}: v_lo / v_hi need a single group")
+        if isinstance(variant_mask, dict):
+            for g in variant_mask:
+                if g not in names:
+                    raise KeyError(g)
+            masks = variant_mask
+        elif variant_mask is not None:
+            if len(names) != 1:
+                raise ValueError(f"{who}: one variant_mask needs a single group (several: a dict group -> mask)")
+            masks = {names[0]: variant_mask}
+        else:
+            masks = {}
+        idx = (np.arange(len(self.samples)) if samples is None else
+               np.array([self._sample_index(x) for x in samples], dtype=np.int64).reshape(-1))
+
+        def queries():
+            for group in names:
+                n_var = self.meta["groups"][group]["n_variants"]
+                lo, hi = (int(v_lo), n_var if v_hi is None else int(v_hi)) if len(names) == 1 else (0, n_var)
+                if not 0 <= lo <= hi <= n_var:
+                    raise IndexError(f"variants [{lo}, {hi}) outside {group} (0..{n_var})")
+                vmask = None
+                if group in masks:
+                    m = masks[group]
+                    if m.ndim != 1 or int(m.shape[0]) != hi - lo:
+                        raise ValueError(f"variant_mask of {group}: shape {tuple(m.shape)}, expected ({hi - lo},)")
+                    vmask = pack_variant_mask(m, lo, n_var, self.meta["vc"], bs)
+                    if not torch.is_tensor(vmask):          # a host mask goes up once, not with every slab
+                        vmask = torch.from_numpy(vmask.view(np.int32)).to(self._context().device)
+                yield group, lo, hi, n_var, vmask
+
+        return idx, queries()
+
     def sample_counts(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None):
         """per-sample counts over the variants of `groups` (one name, a list, None = every group): an int32 device tensor
         [len(samples), 4], columns AN, AC, HET, HOM_ALT as in allele_counts, row i for samples[i] (names or indices; None
@@ -618,54 +668,13 @@ class GenotypeStore:
         from .device import SAMPLE_SEL_DTYPE
         ctx = self._context()
         sc, vc, bs = self.meta["sc"], self.meta["vc"], self._blocksize()
-        names = self._group_list(groups)
-        if len(names) != 1 and (int(v_lo) != 0 or v_hi is not None):
-            raise ValueError("sample_counts: v_lo / v_hi need a single group")
-        if isinstance(variant_mask, dict):
-            for g in variant_mask:
-                if g not in names:
-                    raise KeyError(g)
-            masks = variant_mask
-        elif variant_mask is not None:
-            if len(names) != 1:
-                raise ValueError("sample_counts: one variant_mask needs a single group (several: a dict group -> mask)")
-            masks = {names[0]: variant_mask}
-        else:
-            masks = {}
-        idx = (np.arange(len(self.samples)) if samples is None else
-               np.array([self._sample_index(x) for x in samples], dtype=np.int64).reshape(-1))
+        idx, queries = self._group_queries("sample_counts", groups, samples, v_lo, v_hi, variant_mask)
         table = torch.zeros((-(-max(len(self.samples), 1) // sc) * sc, 4), dtype=torch.int32, device=ctx.device)
-        for group in names:
-            n_var = self.meta["groups"][group]["n_variants"]
-            lo, hi = (int(v_lo), n_var if v_hi is None else int(v_hi)) if len(names) == 1 else (0, n_var)
-            if not 0 <= lo <= hi <= n_var:
-                raise IndexError(f"variants [{lo}, {hi}) outside {group} (0..{n_var})")
-            vmask = None
-            if group in masks:
-                m = masks[group]
-                if m.ndim != 1 or int(m.shape[0]) != hi - lo:
-                    raise ValueError(f"variant_mask of {group}: shape {tuple(m.shape)}, expected ({hi - lo},)")
-                vmask = pack_variant_mask(m, lo, n_var, vc, bs)
-                if not torch.is_tensor(vmask):          # a host mask goes up once, not with every slab
-                    vmask = torch.from_numpy(vmask.view(np.int32)).to(ctx.device)
+        for group, lo, hi, n_var, vmask in queries:
             plan = plan_sample_counts(idx, len(self.samples), sc, vc, n_var, lo, hi, blocksize=bs)
-            if not len(plan):
-                continue
-            blocks = np.array([bin(int(m)).count("1") for m in plan["row_mask"]], np.int64)
-
-            def launch(chunks, keys, rows, plan=plan, vmask=vmask, group=group, blocks=blocks):
-                dsel = np.zeros(len(rows), SAMPLE_SEL_DTYPE)
-                dsel["src_ptr"] = [chunks[keys[i]].data_ptr() for i in rows]
-                dsel["src_bytes"] = [chunks[keys[i]].numel() for i in rows]
-                for f in ("row_mask", "out_row", "mask_word", "part", "lo", "hi"):
-                    dsel[f] = plan[f][rows]
-                _, bad = ctx.count_samples(dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, vmask=vmask,
-                                           counts=table)
-                if bad:
-                    raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
-                self.stats["sample_count_blocks"] += int(blocks[rows].sum())
-
-            self._scan_slabs(group, plan, slab_bytes, launch)
+            self._run_plan(group, plan, slab_bytes, SAMPLE_SEL_DTYPE, "sample_count_blocks",
+                           lambda dsel, vmask=vmask: ctx.count_samples(dsel, sc, vc, typesize=self.meta["typesize"],
+                                                                       blocksize=bs, vmask=vmask, counts=table))
         return table[torch.from_numpy(idx).to(ctx.device)]
 
     def pair_counts(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None,
@@ -684,22 +693,7 @@ class GenotypeStore:
         import torch
         from .device import PLANE_SEL_DTYPE
         sc, vc, bs = self.meta["sc"], self.meta["vc"], self._blocksize()
-        names = self._group_list(groups)
-        if len(names) != 1 and (int(v_lo) != 0 or v_hi is not None):
-            raise ValueError("pair_counts: v_lo / v_hi need a single group")
-        if isinstance(variant_mask, dict):
-            for g in variant_mask:
-                if g not in names:
-                    raise KeyError(g)
-            masks = variant_mask
-        elif variant_mask is not None:
-            if len(names) != 1:
-                raise ValueError("pair_counts: one variant_mask needs a single group (several: a dict group -> mask)")
-            masks = {names[0]: variant_mask}
-        else:
-            masks = {}
-        idx = (np.arange(len(self.samples)) if samples is None else
-               np.array([self._sample_index(x) for x in samples], dtype=np.int64).reshape(-1))
+        idx, queries = self._group_queries("pair_counts", groups, samples, v_lo, v_hi, variant_mask)
         scols, rows = plane_rows(idx, sc)
         n_rows = len(scols) * sc
         limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
@@ -710,19 +704,7 @@ class GenotypeStore:
         table = torch.zeros((n_rows, n_rows, 4), dtype=torch.int32, device=ctx.device)
         budget = DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
         vb, wpb = bs // 2, mask_words_per_block(bs)
-        for group in names:
-            n_var = self.meta["groups"][group]["n_variants"]
-            lo, hi = (int(v_lo), n_var if v_hi is None else int(v_hi)) if len(names) == 1 else (0, n_var)
-            if not 0 <= lo <= hi <= n_var:
-                raise IndexError(f"variants [{lo}, {hi}) outside {group} (0..{n_var})")
-            vmask = None
-            if group in masks:
-                m = masks[group]
-                if m.ndim != 1 or int(m.shape[0]) != hi - lo:
-                    raise ValueError(f"variant_mask of {group}: shape {tuple(m.shape)}, expected ({hi - lo},)")
-                vmask = pack_variant_mask(m, lo, n_var, vc, bs)
-                if not torch.is_tensor(vmask):          # a host mask goes up once, not with every slab
-                    vmask = torch.from_numpy(vmask.view(np.int32)).to(ctx.device)
+        for group, lo, hi, n_var, vmask in queries:
             if n_rows == 0:
                 continue
             planes = None
@@ -734,21 +716,9 @@ class GenotypeStore:
                 else:
                     planes.zero_()
                 plan = plan_planes(idx, len(self.samples), sc, vc, n_var, a, b, blocksize=bs)
-                blocks = np.array([bin(int(m)).count("1") for m in plan["row_mask"]], np.int64)
-
-                def launch(chunks, keys, sel_rows, plan=plan, vmask=vmask, group=group, blocks=blocks, planes=planes):
-                    dsel = np.zeros(len(sel_rows), PLANE_SEL_DTYPE)
-                    dsel["src_ptr"] = [chunks[keys[i]].data_ptr() for i in sel_rows]
-                    dsel["src_bytes"] = [chunks[keys[i]].numel() for i in sel_rows]
-                    for f in ("row_mask", "out_row", "mask_word", "out_word", "part", "lo", "hi"):
-                        dsel[f] = plan[f][sel_rows]
-                    _, bad = ctx.genotype_planes(dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, vmask=vmask,
-                                                 planes=planes)
-                    if bad:
-                        raise RuntimeError(f"{bad} corrupt chunk(s) in {group}")
-                    self.stats["pair_plane_blocks"] += int(blocks[sel_rows].sum())
-
-                self._scan_slabs(group, plan, slab_bytes, launch)
+                self._run_plan(group, plan, slab_bytes, PLANE_SEL_DTYPE, "pair_plane_blocks",
+                               lambda dsel, vmask=vmask, planes=planes: ctx.genotype_planes(
+                                   dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, vmask=vmask, planes=planes))
                 ctx.pair_counts(planes, 0, words, table=table)
                 self.stats["pair_words"] += words
         pick = torch.from_numpy(rows).to(ctx.device)
