@@ -10,8 +10,9 @@ LIB_PATH = os.environ.get("HHGT_LIB") or os.path.join(HERE, "libhhgt.so")
 OK = 0
 BLOSC1 = 1
 BLOSC2 = 2
-N_STAGES = 10
-STAGE_NAMES = ["index", "fixed", "encode", "general", "lz4", "frame", "decode", "onehot", "inflate", "pairs"]
+N_STAGES = 14
+STAGE_NAMES = ["index", "fixed", "encode", "general", "lz4", "frame", "decode", "onehot", "inflate", "pairs", "ld_transpose",
+               "ld", "ld_prune", "ld_walk"]
 
 
 class HhgtError(RuntimeError):
@@ -139,6 +140,9 @@ def load():
     L.hhgt_genotype_planes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, vp, u64, u64, C.POINTER(u64),
                                        vp]
     L.hhgt_pair_counts.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp]
+    L.hhgt_variant_planes.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp]
+    L.hhgt_ld_counts.argtypes = [vp, vp, u64, u64, C.c_uint32, vp, vp]
+    L.hhgt_ld_prune.argtypes = [vp, vp, u64, C.c_uint32, C.c_double, vp, vp]
     L.hhgt_bgzf_scan.argtypes = [vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]
     L.hhgt_inflate_members.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, vp, vp, C.POINTER(u64), vp]
     L.hhgt_onehot_windows.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp, vp]

@@ -112,7 +112,8 @@ extern "C" void hhgt_ctx_destroy(hhgt_ctx *c)
     DevBuf *bufs[] = {&c->slots, &c->counts, &c->prefix, &c->nl, &c->scan_tmp, &c->l_soff, &c->l_lend, &c->l_pos,
                       &c->l_refalt, &c->l_flags, &c->l_keep, &c->l_kidx, &c->l_cnew, &c->l_crun, &c->k_soff,
                       &c->k_lend, &c->k_meta, &c->redo_list, &c->redo_flag, &c->run_first, &c->run_names,
-                      &c->counters, &c->cursor, &c->result, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n};
+                      &c->counters, &c->cursor, &c->result, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n,
+                      &c->ld_bits};
     for (DevBuf *b : bufs) b->release();
     for (auto &w : c->cw) {
         DevBuf *wb[] = {&w.lz_scratch, &w.lz_csize, &w.lz_flags, &w.fr_bsize, &w.fr_csize, &w.fr_flags};
@@ -1230,5 +1231,80 @@ extern "C" int hhgt_pair_counts(hhgt_ctx *c, const uint32_t *d_planes, uint64_t 
     StageTimer t(c, st, HHGT_STAGE_PAIRS);
     TRY(launch_pair_counts(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_table, st));
     t.stop();
+    return HHGT_OK;
+}
+
+extern "C" int hhgt_variant_planes(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
+                                   uint64_t w_hi, uint32_t *d_vplanes, void *stream)
+{
+    const bool work = n_rows && w_lo < w_hi;
+    if (!c || (work && (!d_planes || !d_vplanes))) {
+        hhgt_set_error("variant_planes: null %s", !c ? "context" : !d_planes ? "planes" : "variant planes");
+        return HHGT_ERR_ARG;
+    }
+    if (w_lo > w_hi || w_hi > row_words || n_rows > 256ull * 65535ull) {
+        hhgt_set_error("variant_planes: words [%llu, %llu) of rows of %llu words, %llu rows", (unsigned long long)w_lo,
+                       (unsigned long long)w_hi, (unsigned long long)row_words, (unsigned long long)n_rows);
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!work) return HHGT_OK;
+    StageTimer t(c, st, HHGT_STAGE_LD_TRANSPOSE);
+    TRY(launch_variant_planes(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_vplanes, st));
+    t.stop();
+    return HHGT_OK;
+}
+
+extern "C" int hhgt_ld_counts(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, uint32_t window,
+                              uint32_t *d_table, void *stream)
+{
+    if (window < 1u || window > 1024u) {
+        hhgt_set_error("ld_counts: window %u (1 to 1024)", window);
+        return HHGT_ERR_ARG;
+    }
+    const bool work = n_var && sw;
+    if (!c || (work && (!d_vplanes || !d_table))) {
+        hhgt_set_error("ld_counts: null %s", !c ? "context" : !d_vplanes ? "variant planes" : "table");
+        return HHGT_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(d_table) & 31u) {
+        hhgt_set_error("ld_counts: the table must be 32-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!work) return HHGT_OK;
+    StageTimer t(c, st, HHGT_STAGE_LD);
+    TRY(launch_ld_counts(d_vplanes, n_var, sw, window, d_table, st));
+    t.stop();
+    return HHGT_OK;
+}
+
+extern "C" int hhgt_ld_prune(hhgt_ctx *c, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2,
+                             uint8_t *d_keep, void *stream)
+{
+    if (window < 1u || window > 1024u || !(r2 >= 0.0 && r2 <= 1.0)) {
+        hhgt_set_error("ld_prune: window %u, r2 %g (1 to 1024, 0 to 1)", window, r2);
+        return HHGT_ERR_ARG;
+    }
+    if (!c || (n_var && (!d_table || !d_keep))) {
+        hhgt_set_error("ld_prune: null %s", !c ? "context" : !d_table ? "table" : "keep flags");
+        return HHGT_ERR_ARG;
+    }
+    if (reinterpret_cast<uintptr_t>(d_table) & 31u) {
+        hhgt_set_error("ld_prune: the table must be 32-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!n_var) return HHGT_OK;
+    TRY(c->ld_bits.ensure((size_t)n_var * ld_walk_words(window) * sizeof(uint64_t)));
+    StageTimer t(c, st, HHGT_STAGE_LD_PRUNE);
+    TRY(launch_ld_exceeds(d_table, n_var, window, r2, c->ld_bits.as<uint64_t>(), st));
+    t.stop();
+    StageTimer w(c, st, HHGT_STAGE_LD_WALK);
+    TRY(launch_ld_walk(c->ld_bits.as<uint64_t>(), n_var, window, d_keep, st));
+    w.stop();
     return HHGT_OK;
 }

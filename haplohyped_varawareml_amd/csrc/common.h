@@ -170,6 +170,7 @@ struct hhgt_ctx {
     uint64_t cmp_seq = 0;
     hipStream_t frame_stream = nullptr;   // hhgt_set_frame_stream; nullptr: the framing follows the LZ4 kernels on their stream
     DevBuf dec_bad, oh_ovl, oh_lut, crc_x2n;
+    DevBuf ld_bits;        // hhgt_ld_prune: the per-pair decisions between its two kernels
     bool crc_x2n_ready = false;
     // pinned host mirror for counters
     DevCounters *h_counters = nullptr;
@@ -282,6 +283,14 @@ int launch_genotype_planes(const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t
 // pairs.hip
 int launch_pair_counts(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
                        uint32_t *d_table, hipStream_t st);
+// ld.hip
+int launch_variant_planes(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
+                          uint32_t *d_vplanes, hipStream_t st);
+int launch_ld_counts(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, uint32_t window, uint32_t *d_table,
+                     hipStream_t st);
+uint32_t ld_walk_words(uint32_t window);
+int launch_ld_exceeds(const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, uint64_t *d_bits, hipStream_t st);
+int launch_ld_walk(const uint64_t *d_bits, uint64_t n_var, uint32_t window, uint8_t *d_keep, hipStream_t st);
 int launch_inflate(const uint8_t *d_src, uint64_t src_bytes, const uint64_t *d_comp_off, const uint32_t *d_comp_len,
                    const uint64_t *d_out_off, const uint32_t *d_isize, uint64_t n_members, uint8_t *d_dst,
                    uint64_t dst_bytes, uint32_t *d_status, const uint32_t *d_crc32, const uint32_t *d_x2n, hipStream_t st);

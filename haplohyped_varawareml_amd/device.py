@@ -509,6 +509,69 @@ class Context:
                                             _ptr(table) if table.numel() else None, _stream()))
         return table
 
+    def variant_planes(self, planes, w_lo=0, w_hi=None, vplanes=None):
+        """variant-major planes (hhgt_variant_planes) of the words [w_lo, w_hi) (default: all) of genotype planes
+        [3, n_rows, words]: an int32 tensor [3, 32 * (w_hi - w_lo), ceil(n_rows / 32)] — HET, COMPLETE, HOM_ALT; row p is
+        bit position 32 * w_lo + p of the plane rows, bit r % 32 of word r // 32 is plane row r —, every word of it
+        written (default: a new tensor).  -> vplanes"""
+        if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
+                or not planes.is_contiguous()):
+            raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
+        n, words = int(planes.shape[1]), int(planes.shape[2])
+        w_lo, w_hi = int(w_lo), words if w_hi is None else int(w_hi)
+        shape = (3, 32 * max(w_hi - w_lo, 0), -(-n // 32))
+        with torch.cuda.device(self.device):
+            if vplanes is None:
+                vplanes = torch.empty(shape, dtype=torch.int32, device=self.device)
+            if (vplanes.dtype not in (torch.int32, torch.uint32) or tuple(vplanes.shape) != shape
+                    or not vplanes.is_contiguous()):
+                raise ValueError(f"vplanes: a contiguous int32 tensor {list(shape)}")
+            check(self.lib.hhgt_variant_planes(self.h, _ptr(planes) if planes.numel() else None, n, words, w_lo, w_hi,
+                                               _ptr(vplanes) if vplanes.numel() else None, _stream()))
+        return vplanes
+
+    def ld_counts(self, vplanes, window, table=None):
+        """LD counts (hhgt_ld_counts) of the pairs of rows at most `window` apart of variant-major planes [3, n, sw]: ADDED
+        to `table`, an int32 tensor [n, window, 8] (store.LD_N ... LD_AA of the pair (row k, row k + 1 + d) at [k, d];
+        default: zeros), on the current stream — calls on one stream may accumulate into one table.  -> table"""
+        if (vplanes.dtype not in (torch.int32, torch.uint32) or vplanes.dim() != 3 or vplanes.shape[0] != 3
+                or not vplanes.is_contiguous()):
+            raise ValueError("vplanes: a contiguous int32 tensor [3, n_var, sw]")
+        n, sw, window = int(vplanes.shape[1]), int(vplanes.shape[2]), int(window)
+        if not 0 <= window < 1 << 32:
+            raise ValueError(f"window {window}")
+        with torch.cuda.device(self.device):
+            # a window outside 1..1024 is refused by the library (HhgtError, like every other bad argument of a kernel
+            # call): the default table is then sized for the nearest valid window and the shape check below stands aside
+            if table is None:
+                table = torch.zeros((n, max(min(window, 1024), 1), 8), dtype=torch.int32, device=self.device)
+            if (table.dtype not in (torch.int32, torch.uint32) or table.dim() != 3 or table.shape[0] != n
+                    or table.shape[2] != 8 or (1 <= window <= 1024 and table.shape[1] != window)
+                    or not table.is_contiguous()):
+                raise ValueError(f"table: a contiguous int32 tensor [{n}, {window}, 8]")
+            check(self.lib.hhgt_ld_counts(self.h, _ptr(vplanes) if vplanes.numel() else None, n, sw, window,
+                                          _ptr(table) if table.numel() else None, _stream()))
+        return table
+
+    def ld_prune(self, table, r2, keep=None):
+        """the greedy walk (hhgt_ld_prune) over one tile: table is an int32 tensor [window + n, window, 8] — hhgt_ld_counts
+        over the `window` variants before the tile (rows of zeros where there are none) followed by the tile's n —, keep a
+        uint8 tensor [window + n] whose first `window` bytes are the keep flags of those earlier variants (default: zeros:
+        a first tile); the call fills keep[window:] with 0 / 1.  -> keep"""
+        if (table.dtype not in (torch.int32, torch.uint32) or table.dim() != 3 or table.shape[2] != 8
+                or table.shape[0] < table.shape[1] or not table.is_contiguous()):
+            raise ValueError("table: a contiguous int32 tensor [window + n, window, 8]")
+        window = int(table.shape[1])
+        n = int(table.shape[0]) - window
+        with torch.cuda.device(self.device):
+            if keep is None:
+                keep = torch.zeros(window + n, dtype=torch.uint8, device=self.device)
+            if keep.dtype != torch.uint8 or tuple(keep.shape) != (window + n,) or not keep.is_contiguous():
+                raise ValueError(f"keep: a contiguous uint8 tensor [{window + n}]")
+            check(self.lib.hhgt_ld_prune(self.h, _ptr(table) if table.numel() else None, n, window, float(r2),
+                                         _ptr(keep) if keep.numel() else None, _stream()))
+        return keep
+
     # ---- BGZF on the device (SURVEY §8 f-4) -------------------------------------------------------
     def inflate_bgzf(self, raw, return_status=False, check_crc=True):
         """raw: host bytes / uint8 array holding whole BGZF members.  The host walks the member headers

@@ -8,7 +8,8 @@ allele_frequencies(chromosome, start, end, donor_ids) gives per-variant allele c
 a subset of it, counted on the device (GenotypeStore.allele_counts); sample_statistics(chromosomes, start, end, donor_ids,
 min_maf, singletons) the same counters per donor, summed over the variants of a region or of a class of variants
 (GenotypeStore.sample_counts): call rate, heterozygosity, singletons carried; relatedness(chromosomes, donor_ids, min_maf,
-min_kinship) the pairwise counts and the KING-robust kinship of every pair of donors (GenotypeStore.pair_counts).  The
+min_kinship) the pairwise counts and the KING-robust kinship of every pair of donors (GenotypeStore.pair_counts);
+ld_prune(chromosomes, donor_ids, min_maf, window, r2) the variants a greedy LD pruning keeps (GenotypeStore.ld_prune).  The
 reference has no such queries."""
 import numpy as np
 
@@ -161,6 +162,44 @@ class VCFH5Reader:
         rec["het1"], rec["het2"] = t[i, j, HET1], t[j, i, HET1]
         rec["kinship"] = phi[i, j]
         return rec
+
+    def ld_prune(self, chromosomes=None, donor_ids=None, min_maf=None, window=50, r2=0.2):
+        """greedy LD pruning of chr_{N} for N in chromosomes (one name or a list; None: every group), each group on its own
+        (no LD across groups), over donor_ids (default: every sample), as host numpy records, one per variant of the
+        chosen groups in the order asked: chrom, start (0-based), ref, alt, counted (the variant took part: it passed
+        min_maf, the minor allele frequency over the donors asked for — GenotypeStore.variant_mask, computed and applied
+        on the device; without min_maf every variant), keep (counted, and no kept variant among the `window` counted
+        variants before it has r^2 > r2 with it: GenotypeStore.ld_prune, whose rule is this project's, not plink2's
+        --indep-pairwise)."""
+        st = self.store
+        if chromosomes is None:
+            chroms = [g[len("chr_"):] for g in st.groups()]
+        else:
+            chroms = [chromosomes] if isinstance(chromosomes, (str, int)) else list(chromosomes)
+        donors = list(st.samples) if donor_ids is None else list(donor_ids)
+        for c in chroms:
+            for d in (st.samples[:1] if donor_ids is None else donors) or st.samples[:1]:     # (the store's own are known)
+                self._group(d, c)
+        who = None if donor_ids is None else donors
+        parts, tables = [], [st.variants(f"chr_{c}") for c in chroms]
+        width = max([len(r[1].encode()) for t in tables for r in t[3]] + [1])
+        for c, (start, ref, alt, runs) in zip(chroms, tables):
+            g = f"chr_{c}"
+            mask = st.variant_mask(g, who, min_maf=min_maf) if min_maf is not None else None
+            keep = st.ld_prune(g, who, variant_mask=mask, window=window, r2=r2).cpu().numpy()
+            rec = np.zeros(len(start), dtype=[("chrom", f"S{width}"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"),
+                                              ("counted", bool), ("keep", bool)])
+            bounds = [r[0] for r in runs] + [len(start)]
+            for (a, name), b in zip(runs, bounds[1:]):
+                rec["chrom"][a:b] = name.encode()
+            rec["start"], rec["ref"], rec["alt"] = start, ref.view("S1"), alt.view("S1")
+            rec["counted"] = True if mask is None else mask.cpu().numpy()
+            rec["keep"] = keep
+            parts.append(rec)
+        if not parts:
+            return np.zeros(0, dtype=[("chrom", "S1"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"),
+                                      ("counted", bool), ("keep", bool)])
+        return np.concatenate(parts)
 
     def close(self):
         pass

@@ -255,6 +255,78 @@ def kinship_from_counts(table):
         return np.where(den > 0, 0.5 - num / den, np.nan)
 
 
+# columns of GenotypeStore.ld_counts (and of hhgt_ld_counts' table), for the ordered pair (u, v) of counted variants, v after
+# u, over the counted samples: M = the call is complete, H = HET, A = HOM_ALT.  The dosage of a complete call is 0, 1, 2.
+LD_N, LD_HM, LD_AM, LD_MH, LD_MA = 0, 1, 2, 3, 4     # Mu Mv; Hu Mv; Au Mv; Mu Hv; Mu Av
+LD_HH, LD_HA, LD_AA = 5, 6, 7                        # Hu Hv; Hu Av or Au Hv; Au Av
+
+# the smallest tile of GenotypeStore.ld_prune, in counted variants
+LD_MIN_TILE = 64
+
+
+def plane_positions(v_lo, v_hi, blocksize, block0=None):
+    """the bit positions of the variants [v_lo, v_hi) of a group in a plane row whose first block is block0 (default: the
+    block of v_lo), as plan_planes lays them out -> int64 [v_hi - v_lo]: variant v of block B = v // (blocksize / 2) sits
+    at bit (B - block0) * 32 * mask_words_per_block(blocksize) + v % (blocksize / 2).  The padding of a block whose
+    blocksize / 2 variants do not fill whole words is nobody's position."""
+    v_lo, v_hi, vb = int(v_lo), int(v_hi), int(blocksize) // 2
+    block0 = v_lo // vb if block0 is None else int(block0)
+    if v_hi < v_lo or block0 * vb > v_lo:
+        raise IndexError(f"plane_positions: variants [{v_lo}, {v_hi}) in a row that begins at block {block0}")
+    v = np.arange(v_lo, v_hi, dtype=np.int64)
+    return (v // vb - block0) * (32 * mask_words_per_block(blocksize)) + v % vb
+
+
+def ld_sums(table):
+    """LD table [..., 8] (numpy or torch, any integer type) -> (n, sx, sy, sxx, syy, sxy), int64 each: over the samples at
+    which both calls of a pair are complete, their number and the sums of the dosages x (first variant) and y (second),
+    of their squares and of their products: sx = HM + 2 AM, sxx = HM + 4 AM, sy = MH + 2 MA, syy = MH + 4 MA,
+    sxy = HH + 2 HA + 4 AA."""
+    if _is_torch(table):
+        import torch
+        t = table.to(torch.int64)
+    else:
+        t = np.asarray(table).astype(np.int64)
+    return (t[..., LD_N], t[..., LD_HM] + 2 * t[..., LD_AM], t[..., LD_MH] + 2 * t[..., LD_MA],
+            t[..., LD_HM] + 4 * t[..., LD_AM], t[..., LD_MH] + 4 * t[..., LD_MA],
+            t[..., LD_HH] + 2 * t[..., LD_HA] + 4 * t[..., LD_AA])
+
+
+def _ld_products(table):
+    """-> (num * num, dx * dy) of an LD table, float64: num = N sxy - sx sy, dx = N sxx - sx^2, dy = N syy - sy^2 in int64,
+    converted, and the two products, each rounded once"""
+    n, sx, sy, sxx, syy, sxy = ld_sums(table)
+    num, dx, dy = n * sxy - sx * sy, n * sxx - sx * sx, n * syy - sy * sy
+    if _is_torch(table):
+        import torch
+        num, dx, dy = num.to(torch.float64), dx.to(torch.float64), dy.to(torch.float64)
+    else:
+        num, dx, dy = num.astype(np.float64), dx.astype(np.float64), dy.astype(np.float64)
+    return num * num, dx * dy
+
+
+def r2_from_counts(table):
+    """LD table [n, W, 8] (numpy or torch) -> float64 [n, W]: r^2 = (num * num) / (dx * dy) with num = N sxy - sx sy,
+    dx = N sxx - sx^2, dy = N syy - sy^2 of ld_sums — the squared Pearson correlation of the two variants' dosages over
+    the samples at which both calls are complete (unphased).  NaN where dx * dy = 0: one of the two is monomorphic among
+    those samples, or there are none.  A variant against a duplicate of itself gives exactly 1.0.  The formula is the
+    contract: equality with plink2's --r2-unphased column is neither claimed nor tested."""
+    nn, den = _ld_products(table)
+    if _is_torch(table):
+        import torch
+        return torch.where(den != 0, nn / den, torch.full_like(den, float("nan")))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den != 0, nn / den, np.nan)
+
+
+def ld_exceeds(table, r2):
+    """LD table [n, W, 8] (numpy or torch) -> bool [n, W]: num * num > r2 * (dx * dy), the three products in float64 and
+    each rounded once — the decision hhgt_ld_prune makes from the same integers, bit for bit.  A pair whose r^2 is NaN
+    (zero denominator) never exceeds."""
+    nn, den = _ld_products(table)
+    return nn > float(r2) * den
+
+
 class StoreWriter:
     def __init__(self, path, samples, sc, vc, typesize=2, cohort_name="", donor_ids=None, chunk_format="blosc2"):
         self.path = path
@@ -347,6 +419,8 @@ class GenotypeStore:
         self.stats.update(sample_count_blocks=0)
         # and of pair_counts: Blosc blocks its first stage decoded, plane words per row its second stage read
         self.stats.update(pair_plane_blocks=0, pair_words=0)
+        # and of ld_counts / ld_prune: Blosc blocks their plane stage decoded, pairs of counted variants they counted
+        self.stats.update(ld_plane_blocks=0, ld_pairs=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -731,6 +805,178 @@ class GenotypeStore:
         against itself or a duplicate.  The formula there is the contract; plink2's KINSHIP column is not."""
         return kinship_from_counts(self.pair_counts(groups, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes,
                                                     max_table_bytes))
+
+    def _ld_rows(self, who, group, samples, v_lo, v_hi, variant_mask, window, slab_bytes, plane_bytes):
+        """what ld_counts and ld_prune (`who`, for the messages) do alike -> (lo, hi, counted, n_counted, rows): the range,
+        checked; the offsets into it of the variants the mask marks, an int64 device tensor, or None; the number of counted variants (with a mask
+        it comes from the device, together with the number of counted variants per plane window: one small copy per call,
+        whatever the number of windows); and a generator of int32 device tensors [3, m, sw], the variant-major
+        planes (HET, COMPLETE, HOM_ALT over the plane rows of `samples`) of the counted variants, in order, plane window by
+        plane window: the planes come as in pair_counts (cached chunks used, the read cache neither filled nor evicted;
+        no variant mask there), each window is transposed (hhgt_variant_planes) and the rows at plane_positions of the
+        counted variants gathered, which leaves out block padding and masked variants in one step."""
+        import torch
+        from .device import PLANE_SEL_DTYPE
+        if not isinstance(group, str) or group not in self.meta["groups"]:
+            raise KeyError(group)
+        window = int(window)
+        if not 1 <= window <= 1024:
+            raise ValueError(f"{who}: window {window} (1 to 1024)")
+        ctx = self._context()
+        sc, vc, bs = self.meta["sc"], self.meta["vc"], self._blocksize()
+        n_var = self.meta["groups"][group]["n_variants"]
+        lo, hi = int(v_lo), n_var if v_hi is None else int(v_hi)
+        if not 0 <= lo <= hi <= n_var:
+            raise IndexError(f"variants [{lo}, {hi}) outside {group} (0..{n_var})")
+        idx = (np.arange(len(self.samples)) if samples is None else
+               np.array([self._sample_index(x) for x in samples], dtype=np.int64).reshape(-1))
+        mask = None
+        if variant_mask is not None:
+            if variant_mask.ndim != 1 or int(variant_mask.shape[0]) != hi - lo:
+                raise ValueError(f"variant_mask of {group}: shape {tuple(variant_mask.shape)}, expected ({hi - lo},)")
+            mask = (variant_mask if torch.is_tensor(variant_mask) else
+                    torch.from_numpy(np.ascontiguousarray(variant_mask, dtype=bool))).to(ctx.device).to(torch.bool)
+        n_rows = len(plane_rows(idx, sc)[0]) * sc
+        budget = DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
+        vb, wpb = bs // 2, mask_words_per_block(bs)
+        windows = plane_windows(lo, hi, bs, n_rows, budget) if n_rows else []
+        if mask is None:
+            n_counted, counted, cuts = hi - lo, None, None
+        else:
+            # the counted variants (offsets into the range) stay on the device; what comes back, in one copy for the whole
+            # call, is how many of them lie before each plane window's end
+            counted = torch.nonzero(mask).reshape(-1)
+            ends = torch.tensor([0] + [b - lo for _, b in windows] + [hi - lo], dtype=torch.int64, device=ctx.device)
+            cuts = torch.searchsorted(counted, ends).cpu().tolist()
+            n_counted = cuts[-1]
+
+        def rows():
+            planes = None
+            for w, (a, b) in enumerate(windows):
+                words = ((b - 1) // vb - a // vb + 1) * wpb
+                if planes is None or planes.shape[2] != words:
+                    planes = None                       # (the last window of a range may be shorter)
+                    planes = torch.zeros((3, n_rows, words), dtype=torch.int32, device=ctx.device)
+                else:
+                    planes.zero_()
+                plan = plan_planes(idx, len(self.samples), sc, vc, n_var, a, b, blocksize=bs)
+                self._run_plan(group, plan, slab_bytes, PLANE_SEL_DTYPE, "ld_plane_blocks",
+                               lambda dsel, planes=planes: ctx.genotype_planes(
+                                   dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, planes=planes))
+                pos = torch.from_numpy(plane_positions(a, b, bs)).to(ctx.device)
+                if counted is not None:
+                    pos = pos.index_select(0, counted[cuts[w]:cuts[w + 1]] - (a - lo))
+                if pos.numel():
+                    yield ctx.variant_planes(planes, 0, words).index_select(1, pos)
+
+        return lo, hi, counted, n_counted, rows()
+
+    @staticmethod
+    def _ld_pairs(n, window):
+        """pairs (k, k + 1 + d), d < window, among n variants"""
+        return n * (n - 1) // 2 if n <= window else n * window - window * (window + 1) // 2
+
+    def ld_counts(self, group, samples=None, v_lo=0, v_hi=None, variant_mask=None, window=50, slab_bytes=None,
+                  plane_bytes=None, max_table_bytes=None):
+        """LD counts between nearby variants of a group: an int32 device tensor [n_counted, window, 8], columns LD_N, LD_HM,
+        LD_AM, LD_MH, LD_MA, LD_HH, LD_HA, LD_AA (module constants).  The counted variants are those of [v_lo, v_hi) that
+        variant_mask marks (a bool tensor or array [v_hi - v_lo]; None: all of them), in order; entry [k, d] belongs to the
+        ordered pair (u, v) = (counted variant k, counted variant k + 1 + d) — neighbours are counted variants: a variant
+        outside the mask takes no place in a window — and counts, over `samples` (names or indices, each counted once
+        however often it is named; None: every sample), the samples at which both calls are complete (both alleles 0 or
+        1), u is HET / HOM_ALT and v complete, v is HET / HOM_ALT and u complete, both are HET, one is HET and the other
+        HOM_ALT, both are HOM_ALT.  Entries with k + 1 + d >= n_counted are 0.  ld_sums / r2_from_counts / ld_exceeds read
+        the table.  Three kernels: hhgt_genotype_planes decodes the selected rows' Blosc blocks into three bits per call
+        (chunks handled as in pair_counts: slab_bytes, plane_bytes mean what they mean there), hhgt_variant_planes
+        transposes each window of planes, hhgt_ld_counts reduces the counted variants' rows pair by pair; the last `window`
+        rows of one plane window are carried into the next, so no pair is lost or counted twice at a seam.  ValueError,
+        before the table is allocated, if it (32 bytes per entry) would exceed max_table_bytes (default 2 GiB)."""
+        import torch
+        window = int(window)
+        lo, hi, _, n, rows = self._ld_rows("ld_counts", group, samples, v_lo, v_hi, variant_mask, window, slab_bytes,
+                                              plane_bytes)
+        limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
+        if n * window * 32 > limit:
+            raise ValueError(f"ld_counts: a table of {n} x {window} pairs ({n * window * 32} bytes) exceeds "
+                             f"max_table_bytes = {limit}")
+        ctx = self._context()
+        table = torch.zeros((n, window, 8), dtype=torch.int32, device=ctx.device)
+        carry, k0 = None, 0                 # the last rows of the windows so far; the counted index of the next new row
+        for new in rows:
+            c = 0 if carry is None else int(carry.shape[1])
+            buf = new if carry is None else torch.cat([carry, new], dim=1)
+            part = table[k0 - c:k0 - c + buf.shape[1]]
+            # an entry is one pair: both variants carried (complete since the last window) or the second one new (still 0)
+            old = part[:c].clone()
+            ctx.ld_counts(buf, window, table=part)
+            if c:
+                k, d = torch.arange(c, device=ctx.device)[:, None], torch.arange(window, device=ctx.device)[None, :]
+                part[:c] = torch.where((k + 1 + d < c)[..., None], old, part[:c])
+            carry = buf[:, -window:].contiguous()
+            k0 += int(new.shape[1])
+        self.stats["ld_pairs"] += self._ld_pairs(n, window)
+        return table
+
+    def ld_r2(self, group, samples=None, v_lo=0, v_hi=None, variant_mask=None, window=50, slab_bytes=None,
+              plane_bytes=None, max_table_bytes=None):
+        """r^2 between nearby variants: r2_from_counts of ld_counts (same arguments) — a float64 device tensor
+        [n_counted, window], the squared correlation of the unphased dosages over the jointly complete samples, NaN where
+        it is undefined and in the entries past the last variant.  The formula there is the contract; plink2's
+        --r2-unphased column is not."""
+        return r2_from_counts(self.ld_counts(group, samples, v_lo, v_hi, variant_mask, window, slab_bytes, plane_bytes,
+                                             max_table_bytes))
+
+    def ld_prune(self, group, samples=None, v_lo=0, v_hi=None, variant_mask=None, window=50, r2=0.2, slab_bytes=None,
+                 plane_bytes=None):
+        """greedy LD pruning of the counted variants of a group (group, samples, v_lo / v_hi, variant_mask, window,
+        slab_bytes as in ld_counts): a bool device tensor [v_hi - v_lo], False outside variant_mask, that sample_counts,
+        pair_counts and kinship take as variant_mask.  Walking the counted variants in order, a variant is kept iff no
+        already-kept variant among the `window` counted variants before it has ld_exceeds with it (r^2 > r2, decided from
+        the integer counts).  So the first variant is kept, a monomorphic variant is kept, of two duplicates the second
+        goes.  This is our rule, simpler than plink2's --indep-pairwise (which slides its window in steps and drops the
+        variant with the lower minor allele frequency): the two select different sets.  The work goes tile by tile —
+        at least LD_MIN_TILE counted variants, and as many as keep the tile's table within plane_bytes (default 1 GiB) —:
+        hhgt_ld_counts over the tile and the `window` rows before it, hhgt_ld_prune over that table with the keep flags of
+        those rows carried in.  The whole table never exists, and no genotype, LD count or keep flag goes to the host (with
+        a variant_mask, how many variants it marks per plane window does: they size the buffers).  plane_bytes bounds the
+        plane window and the tile's table each, not their sum: at its peak a call holds a window's planes, their
+        transposed copy, the gathered rows of the counted variants (each up to plane_bytes) and one tile's table (up to
+        plane_bytes again): about 4 GiB at the default with every variant counted, less in proportion under a mask."""
+        import torch
+        window, r2 = int(window), float(r2)
+        if not 0.0 <= r2 <= 1.0:
+            raise ValueError(f"ld_prune: r2 {r2} (0 to 1)")
+        lo, hi, counted, n, rows = self._ld_rows("ld_prune", group, samples, v_lo, v_hi, variant_mask, window, slab_bytes,
+                                              plane_bytes)
+        ctx = self._context()
+        budget = DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
+        tile = max(budget // (window * 32) - window, LD_MIN_TILE)
+        carry = carry_keep = table = None
+        flags = []
+        for new in rows:
+            if carry is None:               # before the first variant: rows without a bit, flags of 0
+                carry = torch.zeros((3, window, new.shape[2]), dtype=torch.int32, device=ctx.device)
+                carry_keep = torch.zeros(window, dtype=torch.uint8, device=ctx.device)
+            for t0 in range(0, int(new.shape[1]), tile):
+                buf = torch.cat([carry, new[:, t0:t0 + tile]], dim=1)
+                if table is None or table.shape[0] != buf.shape[1]:
+                    table = None
+                    table = torch.zeros((buf.shape[1], window, 8), dtype=torch.int32, device=ctx.device)
+                else:
+                    table.zero_()
+                ctx.ld_counts(buf, window, table=table)
+                keep = torch.cat([carry_keep, torch.zeros(buf.shape[1] - window, dtype=torch.uint8, device=ctx.device)])
+                ctx.ld_prune(table, r2, keep=keep)
+                flags.append(keep[window:])
+                carry, carry_keep = buf[:, -window:].contiguous(), keep[-window:].contiguous()
+        self.stats["ld_pairs"] += self._ld_pairs(n, window)
+        # (without a sample no pair exceeds: every counted variant stays)
+        kept = torch.cat(flags).to(torch.bool) if flags else torch.ones(n, dtype=torch.bool, device=ctx.device)
+        if counted is None:
+            return kept
+        out = torch.zeros(hi - lo, dtype=torch.bool, device=ctx.device)
+        out[counted] = kept
+        return out
 
     def variant_mask(self, group, samples=None, v_lo=0, v_hi=None, min_maf=None, max_ac=None, min_ac=None):
         """a class of the variants [v_lo, v_hi) of a group, from allele_counts over `samples` (same arguments), as a bool

@@ -354,6 +354,49 @@ int hhgt_genotype_planes(hhgt_ctx *ctx, const hhgt_plane_sel *d_sel, uint32_t n_
 int hhgt_pair_counts(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
                      uint64_t w_hi, uint32_t *d_table, void *stream);
 
+/* Linkage disequilibrium between nearby variants, in three calls.  Dosage x of a COMPLETE call: 0 HOM_REF, 1 HET, 2 HOM_ALT;
+ * a call that is not complete takes part in nothing.
+ *
+ * hhgt_variant_planes bit-transposes the words [w_lo, w_hi) of hhgt_genotype_planes' output (d_planes, uint32
+ * [3][n_rows][row_words]: HET, HOM_REF, HOM_ALT) into variant-major planes: d_vplanes is uint32 [3][32 (w_hi - w_lo)][sw],
+ * sw = ceil(n_rows / 32); its row p is bit position 32 w_lo + p of the plane rows, bit r % 32 of word r / 32 of it is plane
+ * row r.  The output planes are HET, COMPLETE (= HET | HOM_REF | HOM_ALT) and HOM_ALT; bits for rows >= n_rows are 0.  Every
+ * output word is written, with plain stores: the caller zeroes nothing.  The call knows positions, not variants: which
+ * position is which variant (blocks are padded to whole words), and leaving out the rest, is the caller's.  n_rows up to
+ * 256 * 65535; w_lo <= w_hi <= row_words, else HHGT_ERR_ARG. */
+int hhgt_variant_planes(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
+                        uint64_t w_hi, uint32_t *d_vplanes, void *stream);
+
+/* hhgt_ld_counts reduces the pairs of rows of d_vplanes, uint32 [3][n_var][sw] (planes H, M, A as above; any three planes
+ * of that shape work: the arithmetic is defined on the bits), that are at most `window` rows apart.  d_table is uint32
+ * [n_var][window][8], 32-byte aligned; entry [k][d] belongs to the ordered pair (u, v) = (row k, row k + 1 + d) and counts
+ * the bit positions (samples) with
+ *     [0] LD_N   Mu and Mv        [1] LD_HM  Hu and Mv        [2] LD_AM  Au and Mv        [3] LD_MH  Mu and Hv
+ *     [4] LD_MA  Mu and Av        [5] LD_HH  Hu and Hv        [6] LD_HA  (Hu and Av) or (Au and Hv)   [7] LD_AA  Au and Av
+ * Entries with k + 1 + d >= n_var are not touched.  It ADDS to d_table, which the caller zeroes, with plain read-modify-write:
+ * each entry is owned by exactly one workgroup of the launch, launches on one stream are ordered — exact, no atomics —, so
+ * calls on ONE stream may accumulate (the samples split over several buffers); two streams adding to one table at the same
+ * time are the caller's error.  1 <= window <= 1024, any n_var (below 2^32 - 256) and sw, else HHGT_ERR_ARG. */
+int hhgt_ld_counts(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, uint32_t window, uint32_t *d_table,
+                   void *stream);
+
+/* hhgt_ld_prune walks one tile of n_var variants greedily.  With, in int64 from an entry of the table,
+ *     sx = HM + 2 AM, sxx = HM + 4 AM, sy = MH + 2 MA, syy = MH + 4 MA, sxy = HH + 2 HA + 4 AA,
+ *     num = N sxy - sx sy, dx = N sxx - sx^2, dy = N syy - sy^2                 (counts below 2^30: no overflow)
+ * exceeds(u, v, r2) := num * num > r2 * (dx * dy), in float64, each of the three products rounded once (r^2 = num^2 / (dx dy)
+ * is the squared Pearson correlation of the dosages over the jointly complete samples; a zero denominator compares
+ * false).  Variant v is kept iff no kept variant u among the `window` variants before it has exceeds(u, v, r2).
+ * d_keep is uint8 [window + n_var]: its first `window` bytes are the keep flags of the variants before the tile, in order
+ * (carry-in; 0 where there is none), the call fills d_keep[window + k] with 0 or 1.  d_table is uint32
+ * [window + n_var][window][8], 32-byte aligned, laid out like d_keep: row window + k is variant k of the tile, the first
+ * `window` rows are those of the variants before it — hhgt_ld_counts over the carried rows followed by the tile's; a carried
+ * row whose flag is 0 is not read for a decision that matters and may hold anything, zeros included.  Entries that pair a
+ * variant with one past the tile are ignored.  Two kernels: the decisions of all pairs in parallel, then one wave that
+ * walks the variants with the keep flags of the last `window` in a shift register.  1 <= window <= 1024, 0 <= r2 <= 1,
+ * else HHGT_ERR_ARG.  This is not plink2's --indep-pairwise (no step, no lower-MAF-loses rule). */
+int hhgt_ld_prune(hhgt_ctx *ctx, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, uint8_t *d_keep,
+                  void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values
@@ -470,7 +513,11 @@ int hhgt_inflate_members(hhgt_ctx *ctx, const void *d_src, uint64_t src_bytes, c
 #define HHGT_STAGE_ONEHOT 7   /* one-hot haplotype windows                                       */
 #define HHGT_STAGE_INFLATE 8  /* BGZF members inflated on the device                            */
 #define HHGT_STAGE_PAIRS 9    /* pairwise sample counts over genotype planes                     */
-#define HHGT_N_STAGES 10
+#define HHGT_STAGE_LD_TRANSPOSE 10 /* genotype planes to variant-major planes                    */
+#define HHGT_STAGE_LD 11      /* eight counts per pair of nearby variants                        */
+#define HHGT_STAGE_LD_PRUNE 12 /* r^2 decisions of every pair                                    */
+#define HHGT_STAGE_LD_WALK 13 /* the greedy walk over the decisions                              */
+#define HHGT_N_STAGES 14
 int hhgt_profile_enable(hhgt_ctx *ctx, int on);
 int hhgt_profile_reset(hhgt_ctx *ctx);
 int hhgt_profile_read(hhgt_ctx *ctx, double *ms /*[HHGT_N_STAGES]*/, uint64_t *launches /*[HHGT_N_STAGES]*/);
