@@ -56,18 +56,28 @@ def parse_region(region):
     return m.group(1), beg - 1, end
 
 
+def ordered_chromosomes(reader, chromosomes=None):
+    """the N of a VCFH5Reader's groups chr_N in chromosome order; with `chromosomes`, only those of them, and behind them
+    the ones asked for that the cohort does not have (the query raises for them)"""
+    names = [g[len("chr_"):] for g in sorted(reader.store.groups(), key=_chrom_key)]
+    if chromosomes:
+        want = [str(x) for x in chromosomes]
+        names = [x for x in names if x in want] + [x for x in want if x not in names]
+    return names
+
+
+def read_sample_list(path):
+    """the names of a --sample_list file, one per line -> list; None for no file"""
+    return None if path is None else [x.strip() for x in open(path) if x.strip()]
+
+
 def write_tsv(reader, out, donor_ids=None, chromosomes=None, region=None):
     """the TSV of a VCFH5Reader's cohort to the path `out`: every group (or chr_{N} for N in chromosomes), or the region
     (N, start, end) of parse_region"""
-    groups = sorted(reader.store.groups(), key=_chrom_key)
     if region is not None:
         spans = [(region[0], region[1], region[2])]
     else:
-        names = [g[len("chr_"):] for g in groups]
-        if chromosomes:
-            want = [str(x) for x in chromosomes]
-            names = [x for x in names if x in want] + [x for x in want if x not in names]   # unknown ones raise below
-        spans = [(x, None, None) for x in names]
+        spans = [(x, None, None) for x in ordered_chromosomes(reader, chromosomes)]
     with open(out, "w") as f:
         f.write(HEADER)
         for chrom, a, b in spans:
@@ -88,12 +98,10 @@ def main(h5, out, sample_list, chromosome, region):
     from .h5_reader import VCFH5Reader
     if region is not None and chromosome:
         raise click.UsageError("--region and --chromosome are exclusive")
-    donors = None
-    if sample_list is not None:
-        donors = [x.strip() for x in open(sample_list) if x.strip()]
     r = VCFH5Reader(h5)
     try:
-        write_tsv(r, out, donor_ids=donors, chromosomes=list(chromosome), region=parse_region(region) if region else None)
+        write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome),
+                  region=parse_region(region) if region else None)
     finally:
         r.close()
 

@@ -13,7 +13,16 @@ ld_prune(chromosomes, donor_ids, min_maf, window, r2) the variants a greedy LD p
 reference has no such queries."""
 import numpy as np
 
-from .store import AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, kinship_from_counts
+from .store import AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, chrom_column, kinship_from_counts
+
+
+def _span(starts, start, end):
+    """the variants of a group (their 0-based starts, ascending) whose start lies in [start, end) (None: no bound) ->
+    (lo, hi), indices"""
+    starts = starts.astype(np.int64)
+    lo = 0 if start is None else int(np.searchsorted(starts, start, side="left"))
+    hi = len(starts) if end is None else max(int(np.searchsorted(starts, end, side="left")), lo)
+    return lo, hi
 
 
 class VCFH5Reader:
@@ -27,6 +36,21 @@ class VCFH5Reader:
             raise KeyError(f"No data found for donor_{donor_id}/chr_{chromosome}")     # h5_reader.py:42-43
         return group
 
+    def _cohort(self, chromosomes, donor_ids):
+        """what the queries ask for -> (the chromosomes' group names, donors, who): chromosomes one name, a list or None for
+        every group; donor_ids a list or None for every sample, `who` being what GenotypeStore takes for them (None stays
+        None).  KeyError, in the reference's words, for a chromosome or a donor the file does not have."""
+        st = self.store
+        if chromosomes is None:
+            chroms = [g[len("chr_"):] for g in st.groups()]
+        else:
+            chroms = [chromosomes] if isinstance(chromosomes, (str, int)) else list(chromosomes)
+        donors = list(st.samples) if donor_ids is None else list(donor_ids)
+        for c in chroms:
+            for d in (st.samples[:1] if donor_ids is None else donors) or st.samples[:1]:     # (the store's own are known)
+                self._group(d, c)
+        return [f"chr_{c}" for c in chroms], donors, None if donor_ids is None else donors
+
     def fetch_genotypes(self, donor_id, chromosome):
         return self.store.snp_records(self._group(donor_id, chromosome), donor_id)
 
@@ -34,9 +58,7 @@ class VCFH5Reader:
         """the records of fetch_genotypes whose 0-based start lies in [start, end)"""
         group = self._group(donor_id, chromosome)
         tables = self.store.variants(group)
-        starts = tables[0].astype(np.int64)
-        lo = int(np.searchsorted(starts, start, side="left"))
-        hi = max(int(np.searchsorted(starts, end, side="left")), lo)
+        lo, hi = _span(tables[0], start, end)
         return self.store.snp_records(group, donor_id, lo, hi, tables=tables)
 
     def allele_frequencies(self, chromosome, start=None, end=None, donor_ids=None):
@@ -44,25 +66,15 @@ class VCFH5Reader:
         0-based start lies in [start, end) (None: no bound), as host numpy records: chrom (the group's CHROM runs),
         start, stop, ref, alt as in fetch_genotypes, then an (called alleles), ac (alleles equal to 1), af = ac / an
         (float32, NaN where an == 0), het, hom_alt"""
-        donors = list(self.store.samples[:1]) if donor_ids is None else list(donor_ids)
-        group = f"chr_{chromosome}"
-        for d in donors or self.store.samples[:1]:
-            self._group(d, chromosome)
+        [group], _, who = self._cohort([chromosome], donor_ids)
         start_, ref, alt, runs = self.store.variants(group)
-        starts = start_.astype(np.int64)
-        lo = 0 if start is None else int(np.searchsorted(starts, start, side="left"))
-        hi = len(starts) if end is None else max(int(np.searchsorted(starts, end, side="left")), lo)
-        c = self.store.allele_counts(group, None if donor_ids is None else donors, lo, hi).cpu().numpy()
-        names = [r[1] for r in runs]
-        width = max([len(x.encode()) for x in names] + [1])
+        lo, hi = _span(start_, start, end)
+        c = self.store.allele_counts(group, who, lo, hi).cpu().numpy()
+        width = max([len(r[1].encode()) for r in runs] + [1])
         rec = np.zeros(hi - lo, dtype=[("chrom", f"S{width}"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
                                        ("alt", "S10"), ("an", np.int32), ("ac", np.int32), ("af", np.float32),
                                        ("het", np.int32), ("hom_alt", np.int32)])
-        bounds = [r[0] for r in runs] + [len(starts)]
-        for (a, name), b in zip(runs, bounds[1:]):
-            a, b = max(a, lo), min(b, hi)
-            if a < b:
-                rec["chrom"][a - lo:b - lo] = name.encode()
+        rec["chrom"] = chrom_column(runs, len(start_), lo, hi, width)
         rec["start"] = start_[lo:hi]
         rec["stop"] = start_[lo:hi] + 1
         rec["ref"] = ref[lo:hi].view("S1")
@@ -81,23 +93,12 @@ class VCFH5Reader:
         variants whose minor allele frequency is at least min_maf / whose alternate allele is carried exactly once, both
         taken over the donors asked for (GenotypeStore.variant_mask over them), computed and applied on the device."""
         st = self.store
-        if chromosomes is None:
-            chroms = [g[len("chr_"):] for g in st.groups()]
-        else:
-            chroms = [chromosomes] if isinstance(chromosomes, (str, int)) else list(chromosomes)
-        donors = list(st.samples) if donor_ids is None else list(donor_ids)
-        for c in chroms:
-            for d in (st.samples[:1] if donor_ids is None else donors) or st.samples[:1]:     # (the store's own are known)
-                self._group(d, c)
-        if (start is not None or end is not None) and len(chroms) != 1:
+        names, donors, who = self._cohort(chromosomes, donor_ids)
+        if (start is not None or end is not None) and len(names) != 1:
             raise ValueError("sample_statistics: start / end need exactly one chromosome")
-        names = [f"chr_{c}" for c in chroms]
-        who = None if donor_ids is None else donors
         lo, hi, masks, n_variants = 0, None, {}, 0
         if start is not None or end is not None:
-            starts = st.variants(names[0])[0].astype(np.int64)
-            lo = 0 if start is None else int(np.searchsorted(starts, start, side="left"))
-            hi = len(starts) if end is None else max(int(np.searchsorted(starts, end, side="left")), lo)
+            lo, hi = _span(st.variants(names[0])[0], start, end)
         for g in names:
             a, b = (lo, hi) if len(names) == 1 else (0, None)
             b = st.meta["groups"][g]["n_variants"] if b is None else b
@@ -133,16 +134,7 @@ class VCFH5Reader:
         (GenotypeStore.variant_mask per group, computed and applied on the device).  min_kinship: only the pairs at or above
         it (NaN pairs are then dropped)."""
         st = self.store
-        if chromosomes is None:
-            chroms = [g[len("chr_"):] for g in st.groups()]
-        else:
-            chroms = [chromosomes] if isinstance(chromosomes, (str, int)) else list(chromosomes)
-        donors = list(st.samples) if donor_ids is None else list(donor_ids)
-        for c in chroms:
-            for d in (st.samples[:1] if donor_ids is None else donors) or st.samples[:1]:     # (the store's own are known)
-                self._group(d, c)
-        names = [f"chr_{c}" for c in chroms]
-        who = None if donor_ids is None else donors
+        names, donors, who = self._cohort(chromosomes, donor_ids)
         masks = {g: st.variant_mask(g, who, min_maf=min_maf) for g in names} if min_maf is not None else None
         table = st.pair_counts(names, who, variant_mask=masks)
         phi = kinship_from_counts(table).cpu().numpy()
@@ -172,26 +164,15 @@ class VCFH5Reader:
         variants before it has r^2 > r2 with it: GenotypeStore.ld_prune, whose rule is this project's, not plink2's
         --indep-pairwise)."""
         st = self.store
-        if chromosomes is None:
-            chroms = [g[len("chr_"):] for g in st.groups()]
-        else:
-            chroms = [chromosomes] if isinstance(chromosomes, (str, int)) else list(chromosomes)
-        donors = list(st.samples) if donor_ids is None else list(donor_ids)
-        for c in chroms:
-            for d in (st.samples[:1] if donor_ids is None else donors) or st.samples[:1]:     # (the store's own are known)
-                self._group(d, c)
-        who = None if donor_ids is None else donors
-        parts, tables = [], [st.variants(f"chr_{c}") for c in chroms]
+        names, donors, who = self._cohort(chromosomes, donor_ids)
+        parts, tables = [], [st.variants(g) for g in names]
         width = max([len(r[1].encode()) for t in tables for r in t[3]] + [1])
-        for c, (start, ref, alt, runs) in zip(chroms, tables):
-            g = f"chr_{c}"
+        for g, (start, ref, alt, runs) in zip(names, tables):
             mask = st.variant_mask(g, who, min_maf=min_maf) if min_maf is not None else None
             keep = st.ld_prune(g, who, variant_mask=mask, window=window, r2=r2).cpu().numpy()
             rec = np.zeros(len(start), dtype=[("chrom", f"S{width}"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"),
                                               ("counted", bool), ("keep", bool)])
-            bounds = [r[0] for r in runs] + [len(start)]
-            for (a, name), b in zip(runs, bounds[1:]):
-                rec["chrom"][a:b] = name.encode()
+            rec["chrom"] = chrom_column(runs, len(start), 0, len(start), width)
             rec["start"], rec["ref"], rec["alt"] = start, ref.view("S1"), alt.view("S1")
             rec["counted"] = True if mask is None else mask.cpu().numpy()
             rec["keep"] = keep

@@ -13,7 +13,7 @@ the listed samples is at least X; --min_kinship X writes only the pairs at or ab
 (GenotypeStore.pair_counts)."""
 import click
 
-from .allele_freq import _chrom_key
+from .allele_freq import ordered_chromosomes, read_sample_list
 
 HEADER = "#IID1\tIID2\tNSNP\tHETHET\tIBS0\tHET1\tHET2\tKINSHIP\n"
 
@@ -29,11 +29,8 @@ def format_rows(rec):
 
 def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, min_kinship=None):
     """the TSV of a VCFH5Reader's cohort to the path `out`: over every group, or chr_{N} for N in chromosomes"""
-    names = [g[len("chr_"):] for g in sorted(reader.store.groups(), key=_chrom_key)]
-    if chromosomes:
-        want = [str(x) for x in chromosomes]
-        names = [x for x in names if x in want] + [x for x in want if x not in names]   # unknown ones raise below
-    rec = reader.relatedness(names, donor_ids=donor_ids, min_maf=min_maf, min_kinship=min_kinship)
+    rec = reader.relatedness(ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf,
+                             min_kinship=min_kinship)
     with open(out, "w") as f:
         f.write(HEADER)
         f.write(format_rows(rec))
@@ -49,12 +46,10 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, min_k
 def main(h5, out, sample_list, chromosome, min_maf, min_kinship):
     """Writes the pairwise counts and kinship of the cohort in H5 to OUT."""
     from .h5_reader import VCFH5Reader
-    donors = None
-    if sample_list is not None:
-        donors = [x.strip() for x in open(sample_list) if x.strip()]
     r = VCFH5Reader(h5)
     try:
-        write_tsv(r, out, donor_ids=donors, chromosomes=list(chromosome), min_maf=min_maf, min_kinship=min_kinship)
+        write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
+                  min_kinship=min_kinship)
     finally:
         r.close()
 

@@ -13,7 +13,7 @@ decisions and the walk run on the device (GenotypeStore.ld_prune)."""
 import click
 import numpy as np
 
-from .allele_freq import _bases, _chrom_key
+from .allele_freq import _bases, ordered_chromosomes, read_sample_list
 
 HEADER = "#CHROM\tPOS\tREF\tALT\n"
 
@@ -31,11 +31,8 @@ def format_rows(chrom, pos, ref, alt):
 
 def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, window=50, r2=0.2):
     """the TSV of a VCFH5Reader's cohort to the path `out`: over every group, or chr_{N} for N in chromosomes"""
-    names = [g[len("chr_"):] for g in sorted(reader.store.groups(), key=_chrom_key)]
-    if chromosomes:
-        want = [str(x) for x in chromosomes]
-        names = [x for x in names if x in want] + [x for x in want if x not in names]   # unknown ones raise below
-    rec = reader.ld_prune(names, donor_ids=donor_ids, min_maf=min_maf, window=window, r2=r2)
+    rec = reader.ld_prune(ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf, window=window,
+                          r2=r2)
     rec = rec[rec["keep"]]
     with open(out, "w") as f:
         f.write(HEADER)
@@ -53,12 +50,10 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, windo
 def main(h5, out, sample_list, chromosome, min_maf, window, r2):
     """Writes the variants of the cohort in H5 that a greedy LD pruning keeps to OUT."""
     from .h5_reader import VCFH5Reader
-    donors = None
-    if sample_list is not None:
-        donors = [x.strip() for x in open(sample_list) if x.strip()]
     r = VCFH5Reader(h5)
     try:
-        write_tsv(r, out, donor_ids=donors, chromosomes=list(chromosome), min_maf=min_maf, window=window, r2=r2)
+        write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
+                  window=window, r2=r2)
     finally:
         r.close()
 

@@ -12,7 +12,7 @@ number of singletons a sample carries).  The counts run on the device (GenotypeS
 import click
 import numpy as np
 
-from .allele_freq import _chrom_key, parse_region
+from .allele_freq import ordered_chromosomes, parse_region, read_sample_list
 from .store import AC, AN, HET, HOM_ALT
 
 HEADER = "#IID\tVARIANT_CT\tOBS_CT\tMISSING_CT\tALT_CTS\tHET_CT\tHOM_ALT_CT\n"
@@ -38,11 +38,8 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, region=None, min_ma
         rec = reader.sample_statistics([region[0]], region[1], region[2], donor_ids=donor_ids, min_maf=min_maf,
                                        singletons=singletons)
     else:
-        names = [g[len("chr_"):] for g in sorted(reader.store.groups(), key=_chrom_key)]
-        if chromosomes:
-            want = [str(x) for x in chromosomes]
-            names = [x for x in names if x in want] + [x for x in want if x not in names]   # unknown ones raise below
-        rec = reader.sample_statistics(names, donor_ids=donor_ids, min_maf=min_maf, singletons=singletons)
+        rec = reader.sample_statistics(ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf,
+                                       singletons=singletons)
     counts = np.stack([rec["an"], rec["ac"], rec["het"], rec["hom_alt"]], axis=1)
     with open(out, "w") as f:
         f.write(HEADER)
@@ -63,13 +60,10 @@ def main(h5, out, sample_list, chromosome, region, min_maf, singletons):
     from .h5_reader import VCFH5Reader
     if region is not None and chromosome:
         raise click.UsageError("--region and --chromosome are exclusive")
-    donors = None
-    if sample_list is not None:
-        donors = [x.strip() for x in open(sample_list) if x.strip()]
     r = VCFH5Reader(h5)
     try:
-        write_tsv(r, out, donor_ids=donors, chromosomes=list(chromosome), region=parse_region(region) if region else None,
-                  min_maf=min_maf, singletons=singletons)
+        write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome),
+                  region=parse_region(region) if region else None, min_maf=min_maf, singletons=singletons)
     finally:
         r.close()
 
