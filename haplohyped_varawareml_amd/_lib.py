@@ -10,9 +10,9 @@ LIB_PATH = os.environ.get("HHGT_LIB") or os.path.join(HERE, "libhhgt.so")
 OK = 0
 BLOSC1 = 1
 BLOSC2 = 2
-N_STAGES = 14
+N_STAGES = 15
 STAGE_NAMES = ["index", "fixed", "encode", "general", "lz4", "frame", "decode", "onehot", "inflate", "pairs", "ld_transpose",
-               "ld", "ld_prune", "ld_walk"]
+               "ld", "ld_prune", "ld_walk", "grm"]
 
 
 class HhgtError(RuntimeError):
@@ -140,6 +140,7 @@ def load():
     L.hhgt_genotype_planes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, vp, u64, u64, C.POINTER(u64),
                                        vp]
     L.hhgt_pair_counts.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp]
+    L.hhgt_grm.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp, vp]
     L.hhgt_variant_planes.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp]
     L.hhgt_ld_counts.argtypes = [vp, vp, u64, u64, C.c_uint32, vp, vp]
     L.hhgt_ld_prune.argtypes = [vp, vp, u64, C.c_uint32, C.c_double, vp, vp]

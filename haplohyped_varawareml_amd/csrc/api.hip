@@ -1234,6 +1234,32 @@ extern "C" int hhgt_pair_counts(hhgt_ctx *c, const uint32_t *d_planes, uint64_t 
     return HHGT_OK;
 }
 
+extern "C" int hhgt_grm(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
+                        const float *d_z, double *d_table, void *stream)
+{
+    const bool work = n_rows && w_lo < w_hi;
+    if (!c || (work && (!d_planes || !d_z || !d_table))) {
+        hhgt_set_error("grm: null %s", !c ? "context" : !d_planes ? "planes" : !d_z ? "weights" : "table");
+        return HHGT_ERR_ARG;
+    }
+    if (w_lo > w_hi || w_hi > row_words || n_rows > 64ull * 65535ull) {
+        hhgt_set_error("grm: words [%llu, %llu) of rows of %llu words, %llu rows", (unsigned long long)w_lo,
+                       (unsigned long long)w_hi, (unsigned long long)row_words, (unsigned long long)n_rows);
+        return HHGT_ERR_ARG;
+    }
+    if ((reinterpret_cast<uintptr_t>(d_table) & 7u) || (reinterpret_cast<uintptr_t>(d_z) & 15u)) {
+        hhgt_set_error("grm: the table must be 8-byte aligned, the weights 16-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!work) return HHGT_OK;
+    StageTimer t(c, st, HHGT_STAGE_GRM);
+    TRY(launch_grm(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_z, d_table, st));
+    t.stop();
+    return HHGT_OK;
+}
+
 extern "C" int hhgt_variant_planes(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
                                    uint64_t w_hi, uint32_t *d_vplanes, void *stream)
 {

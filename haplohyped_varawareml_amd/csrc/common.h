@@ -283,6 +283,9 @@ int launch_genotype_planes(const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t
 // pairs.hip
 int launch_pair_counts(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
                        uint32_t *d_table, hipStream_t st);
+// grm.hip
+int launch_grm(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi, const float *d_z,
+               double *d_table, hipStream_t st);
 // ld.hip
 int launch_variant_planes(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
                           uint32_t *d_vplanes, hipStream_t st);

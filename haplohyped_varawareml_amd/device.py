@@ -509,6 +509,27 @@ class Context:
                                             _ptr(table) if table.numel() else None, _stream()))
         return table
 
+    def grm(self, planes, z, w_lo=0, w_hi=None, table=None):
+        """sums of products of standardised dosages (hhgt_grm) over the words [w_lo, w_hi) (default: all) of genotype
+        planes [3, n, words]: z is a float32 tensor [3, 32 * words], the value of a HOM_REF, HET, HOM_ALT call at every bit
+        position; the sums are ADDED to `table`, a float64 tensor [n, n] (default: zeros), on the current stream — calls
+        on one stream may accumulate into one table.  -> table"""
+        if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
+                or not planes.is_contiguous()):
+            raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
+        n, words = int(planes.shape[1]), int(planes.shape[2])
+        w_hi = words if w_hi is None else int(w_hi)
+        if z.dtype != torch.float32 or tuple(z.shape) != (3, 32 * words) or not z.is_contiguous() or z.device != planes.device:
+            raise ValueError(f"z: a contiguous float32 tensor [3, {32 * words}] on the planes' device")
+        with torch.cuda.device(self.device):
+            if table is None:
+                table = torch.zeros((n, n), dtype=torch.float64, device=self.device)
+            if table.dtype != torch.float64 or tuple(table.shape) != (n, n) or not table.is_contiguous():
+                raise ValueError(f"table: a contiguous float64 tensor [{n}, {n}]")
+            check(self.lib.hhgt_grm(self.h, _ptr(planes) if planes.numel() else None, n, words, int(w_lo), w_hi,
+                                    _ptr(z) if z.numel() else None, _ptr(table) if table.numel() else None, _stream()))
+        return table
+
     def variant_planes(self, planes, w_lo=0, w_hi=None, vplanes=None):
         """variant-major planes (hhgt_variant_planes) of the words [w_lo, w_hi) (default: all) of genotype planes
         [3, n_rows, words]: an int32 tensor [3, 32 * (w_hi - w_lo), ceil(n_rows / 32)] — HET, COMPLETE, HOM_ALT; row p is

@@ -9,11 +9,15 @@ a subset of it, counted on the device (GenotypeStore.allele_counts); sample_stat
 min_maf, singletons) the same counters per donor, summed over the variants of a region or of a class of variants
 (GenotypeStore.sample_counts): call rate, heterozygosity, singletons carried; relatedness(chromosomes, donor_ids, min_maf,
 min_kinship) the pairwise counts and the KING-robust kinship of every pair of donors (GenotypeStore.pair_counts);
-ld_prune(chromosomes, donor_ids, min_maf, window, r2) the variants a greedy LD pruning keeps (GenotypeStore.ld_prune).  The
-reference has no such queries."""
+ld_prune(chromosomes, donor_ids, min_maf, window, r2) the variants a greedy LD pruning keeps (GenotypeStore.ld_prune);
+genetic_relationship(chromosomes, donor_ids, min_maf, ld_window, ld_r2) the standardised genetic relationship matrix of the
+donors over the variants that pass min_maf and, with ld_window, the LD pruning (GenotypeStore.grm_sums), and
+principal_components(k, ...) its k largest eigenpairs, one record per donor (store.top_eigenpairs: numpy.linalg.eigh on the
+host).  The reference has no such queries."""
 import numpy as np
 
-from .store import AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, chrom_column, kinship_from_counts
+from .store import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, chrom_column, grm_from_sums,
+                    kinship_from_counts, top_eigenpairs)
 
 
 def _span(starts, start, end):
@@ -181,6 +185,44 @@ class VCFH5Reader:
             return np.zeros(0, dtype=[("chrom", "S1"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"),
                                       ("counted", bool), ("keep", bool)])
         return np.concatenate(parts)
+
+    def genetic_relationship(self, chromosomes=None, donor_ids=None, min_maf=None, ld_window=None, ld_r2=0.2):
+        """the standardised genetic relationship matrix of donor_ids (default: every sample, store order) over the
+        variants of chr_{N} for N in chromosomes (one name or a list; None: every group) -> (donors, grm float64 [n, n],
+        nsnp int32 [n, n]), host numpy: store.grm_from_sums of GenotypeStore.grm_sums — per pair, the mean over the variants
+        at which both calls are complete (nsnp of them) of the product of the two standardised dosages, NaN where there is
+        none; the formulas there are the contract, not GCTA's or plink2's files.  min_maf: only the variants whose minor
+        allele frequency over the donors asked for is at least that (GenotypeStore.variant_mask per group); ld_window: of
+        those, only the variants a greedy LD pruning keeps (GenotypeStore.ld_prune per group, `ld_window` counted variants,
+        r^2 > ld_r2 drops).  Every mask is computed and applied on the device."""
+        st = self.store
+        names, donors, who = self._cohort(chromosomes, donor_ids)
+        masks = {}
+        for g in names:
+            if min_maf is not None:
+                masks[g] = st.variant_mask(g, who, min_maf=min_maf)
+            if ld_window is not None:
+                masks[g] = st.ld_prune(g, who, variant_mask=masks.get(g), window=ld_window, r2=ld_r2)
+        sums, nsnp = st.grm_sums(names, who, variant_mask=masks or None)
+        return donors, grm_from_sums(sums, nsnp).cpu().numpy(), nsnp.cpu().numpy()
+
+    def principal_components(self, k=10, chromosomes=None, donor_ids=None, min_maf=None, ld_window=None, ld_r2=0.2):
+        """the k largest principal components of genetic_relationship (same arguments after k) -> (records, values):
+        host numpy records, one per donor in the order asked — sample, pc1 .. pck (float64: the donor's component of each
+        unit eigenvector, whose component of largest magnitude is positive) —, and the eigenvalues float64 [k], descending
+        (store.top_eigenpairs: numpy.linalg.eigh on the host).  ValueError if k is outside 1..n or a pair of donors has
+        no jointly complete variant."""
+        n = len(self.store.samples) if donor_ids is None else len(list(donor_ids))
+        if not 1 <= int(k) <= n:
+            raise ValueError(f"pca: k = {int(k)} (1 to {n})")
+        donors, grm, _ = self.genetic_relationship(chromosomes, donor_ids, min_maf, ld_window, ld_r2)
+        values, vectors = top_eigenpairs(grm, k)
+        width = max([len(x.encode()) for x in donors] + [1])
+        rec = np.zeros(len(donors), dtype=[("sample", f"S{width}")] + [(f"pc{c + 1}", np.float64) for c in range(int(k))])
+        rec["sample"] = [x.encode() for x in donors]
+        for c in range(int(k)):
+            rec[f"pc{c + 1}"] = vectors[:, c]
+        return rec, values
 
     def close(self):
         pass

@@ -25,8 +25,9 @@ from .store_plan import (COUNT_PLAN_DTYPE, DEFAULT_PLANE_BYTES, LD_MIN_TILE, MAX
                          PLAN_DTYPE, PLANE_PLAN_DTYPE, ROW_PLAN_DTYPE, SAMPLE_PLAN_DTYPE, default_blocksize,
                          mask_words_per_block, pack_variant_mask, plan_counts, plan_planes, plan_rows, plan_sample_counts,
                          plan_windows, plane_positions, plane_rows, plane_windows, query_args, sample_index)
-from .store_stats import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, LD_AA, LD_AM, LD_HA, LD_HH, LD_HM, LD_MA,  # noqa: F401
-                          LD_MH, LD_N, NSNP, ibs_counts, kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts)
+from .store_stats import (AC, AN, GRM_SPAN, HET, HET1, HETHET, HOM_ALT, IBS0, LD_AA, LD_AM, LD_HA, LD_HH, LD_HM,  # noqa: F401
+                          LD_MA, LD_MH, LD_N, NSNP, grm_from_sums, ibs_counts, kinship_from_counts, ld_exceeds, ld_sums,
+                          r2_from_counts, standardized_dosages, top_eigenpairs)
 
 # the reference's per-donor record (vcf_to_h5.py:119-127): packed, 35 bytes
 SNP_DTYPE = np.dtype([("chrom", "S5"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
@@ -129,6 +130,8 @@ class GenotypeStore:
         self.stats.update(pair_plane_blocks=0, pair_words=0)
         # and of ld_counts / ld_prune: Blosc blocks their plane stage decoded, pairs of counted variants they counted
         self.stats.update(ld_plane_blocks=0, ld_pairs=0)
+        # and of grm_sums: Blosc blocks its plane stage decoded, plane words per row its two reductions read
+        self.stats.update(grm_plane_blocks=0, grm_words=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -468,6 +471,68 @@ class GenotypeStore:
         against itself or a duplicate.  The formula there is the contract; plink2's KINSHIP column is not."""
         return kinship_from_counts(self.pair_counts(groups, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes,
                                                     max_table_bytes))
+
+    def grm_sums(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
+                 max_table_bytes=None):
+        """the sums behind the genetic relationship matrix of `samples` over the variants of `groups` -> (S, N) on the
+        device: S float64 [n, n], the sum over the variants of x_i * x_j, and N int32 [n, n], the variants at which both
+        calls are complete (pair_counts' NSNP).  Every argument means what it means in pair_counts, a sample named twice
+        included.  Per group, allele_counts over the listed samples (each counted once, as variant_mask counts them)
+        gives standardized_dosages' z and `used`; the variants that take part are those variant_mask marks and that are
+        used (ANDed on the device, and handed to the plane walk as its packed mask); a complete call of dosage d contributes
+        x = z[d] of its variant, any other call 0.  Each plane window is reduced twice while it is resident, by
+        hhgt_pair_counts and by hhgt_grm (the f32-input MFMA over the planes, z scattered to the window's bit positions:
+        include/hhgt.h states its arithmetic and error bound); groups, windows and slabs add into the same two tables.
+        ValueError, before anything is allocated, if the two tables (16 + 8 bytes per pair of plane rows) would exceed
+        max_table_bytes (default 2 GiB)."""
+        import torch
+        idx, queries = self._query("grm_sums", groups, samples, v_lo, v_hi, variant_mask)
+        scols, rows = plane_rows(idx, self.meta["sc"])
+        n_rows = len(scols) * self.meta["sc"]
+        limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
+        if n_rows * n_rows * 24 > limit:
+            raise ValueError(f"grm_sums: tables of {n_rows} x {n_rows} pairs ({n_rows * n_rows * 24} bytes) exceed "
+                             f"max_table_bytes = {limit}")
+        ctx = self._context()
+        bs = self._blocksize()
+        counts = torch.zeros((n_rows, n_rows, 4), dtype=torch.int32, device=ctx.device)
+        sums = torch.zeros((n_rows, n_rows), dtype=torch.float64, device=ctx.device)
+        for group, lo, hi, n_var, mask in queries if n_rows else ():
+            z, used = standardized_dosages(self.allele_counts(group, idx, lo, hi, slab_bytes))
+            if mask is not None:
+                mask = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(mask, dtype=bool))
+                used = used & mask.to(ctx.device).to(torch.bool)
+            for a, b, words, planes in self._plane_walk(group, idx, lo, hi, n_var, "grm_plane_blocks", slab_bytes,
+                                                        plane_bytes, self._device_mask(used, lo, n_var)):
+                d_z = torch.zeros((3, 32 * words), dtype=torch.float32, device=ctx.device)
+                d_z[:, torch.from_numpy(plane_positions(a, b, bs)).to(ctx.device)] = z[:, a - lo:b - lo]
+                ctx.pair_counts(planes, 0, words, table=counts)
+                ctx.grm(planes, d_z, 0, words, table=sums)
+                self.stats["grm_words"] += words
+        pick = torch.from_numpy(rows).to(ctx.device)
+        return sums[pick][:, pick].contiguous(), counts[..., NSNP][pick][:, pick].contiguous()
+
+    def grm(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
+            max_table_bytes=None):
+        """the standardised genetic relationship matrix of `samples`: grm_from_sums of grm_sums (same arguments) — a
+        float64 device tensor [n, n], exactly symmetric, NaN where a pair has no jointly complete variant.  The formulas
+        there are the contract; GCTA's and plink2 --make-rel's files are not."""
+        return grm_from_sums(*self.grm_sums(groups, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes,
+                                            max_table_bytes))
+
+    def pca(self, k, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
+            max_table_bytes=None):
+        """the k largest principal components of grm (same arguments after k) -> (values float64 [k], vectors float64
+        [n, k]), host numpy arrays: top_eigenpairs of the host copy of the matrix — numpy.linalg.eigh, descending, unit
+        vectors whose component of largest magnitude is positive.  The decomposition runs on the host on purpose: it is
+        n^3 on an n x n matrix, not the hot path, and needs no solver library on the device.  ValueError if k is outside
+        1..n (before anything is computed) or a pair of samples has no jointly complete variant."""
+        samples = None if samples is None else list(samples)
+        n = len(self.samples) if samples is None else len(samples)
+        if not 1 <= int(k) <= n:
+            raise ValueError(f"pca: k = {int(k)} (1 to {n})")
+        g = self.grm(groups, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes, max_table_bytes)
+        return top_eigenpairs(g.cpu().numpy(), k)
 
     def _ld_rows(self, who, group, samples, v_lo, v_hi, variant_mask, window, slab_bytes, plane_bytes):
         """what ld_counts and ld_prune (`who`, for the messages) do alike -> (lo, hi, counted, n_counted, rows): the range,

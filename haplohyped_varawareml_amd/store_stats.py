@@ -89,3 +89,59 @@ def ld_exceeds(table, r2):
     (zero denominator) never exceeds."""
     nn, den = _ld_products(table)
     return nn > float(r2) * den
+
+
+# plane words of one f32 chain of hhgt_grm (HHGT_GRM_SPAN of include/hhgt.h): the K of its error bound is 32 * GRM_SPAN
+GRM_SPAN = 128
+
+
+def standardized_dosages(counts):
+    """allele count table [V, 4] (numpy or torch, columns AN, AC, ...) -> (z, used): z float32 [3, V], the standardised
+    value of a complete call of dosage d = 0, 1, 2 (HOM_REF, HET, HOM_ALT) at every variant, and used bool [V].  A variant
+    is used iff AN > 0 and 0 < AC < AN; then p = AC / AN and z[d] = (d - 2p) / sqrt(2p(1 - p)), computed in float64 and
+    rounded once to float32 (the standardisation of GCTA's and plink2 --make-rel's relationship matrix).  A variant that
+    is not used has 0 in all three."""
+    i64, f64 = _ops(counts)[:2]
+    t = i64(counts)
+    an, ac = t[..., AN], t[..., AC]
+    used = (an > 0) & (ac > 0) & (ac < an)
+    # (a variant that is not used gets p = 1/2 here, so that nothing divides by 0, and 0 at the end)
+    p = f64(ac * used + (~used) * 1) / f64(an * used + (~used) * 2)
+    sd = (2.0 * p * (1.0 - p)) ** 0.5
+    rows = [(float(d) - 2.0 * p) / sd for d in range(3)]
+    if type(counts).__module__.split(".")[0] == "torch":
+        import torch
+        z = torch.stack(rows)
+        return torch.where(used, z, torch.zeros_like(z)).to(torch.float32), used
+    return np.where(used, np.stack(rows), 0.0).astype(np.float32), used
+
+
+def grm_from_sums(S, N):
+    """(S float64 [n, n], N integer [n, n]) of GenotypeStore.grm_sums (numpy or torch) -> float64 [n, n]: the genetic
+    relationship matrix S / N — per pair, the mean over the variants at which both calls are complete of the product of
+    the two standardised dosages —, NaN where N == 0.  The formula is the contract: equality with GCTA's or plink2's
+    files is neither claimed nor tested."""
+    _, f64, _, nan_unless = _ops(S)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return nan_unless(N != 0, f64(S) / f64(N))
+
+
+def top_eigenpairs(grm, k):
+    """symmetric float64 [n, n] (host numpy) -> (values float64 [k], vectors float64 [n, k]): the k largest eigenpairs of
+    numpy.linalg.eigh, in descending order; every vector of unit length as eigh returns it, its sign chosen so that its
+    component of largest magnitude (the first such one) is positive.  ValueError if k is outside 1..n or the matrix holds
+    a NaN (the message counts the pairs i <= j)."""
+    g = np.asarray(grm, dtype=np.float64)
+    n, k = g.shape[0], int(k)
+    if g.ndim != 2 or g.shape[1] != n:
+        raise ValueError(f"pca: a square matrix, not {g.shape}")
+    if not 1 <= k <= n:
+        raise ValueError(f"pca: k = {k} (1 to {n})")
+    bad = int(np.isnan(g[np.triu_indices(n)]).sum())
+    if bad:
+        raise ValueError(f"pca: {bad} pair(s) of samples have no jointly complete variant (NaN in the relationship matrix)")
+    w, v = np.linalg.eigh(g)
+    w, v = w[::-1][:k].copy(), v[:, ::-1][:, :k].copy()
+    lead = np.argmax(np.abs(v), axis=0)
+    v[:, v[lead, np.arange(k)] < 0] *= -1.0
+    return w, v

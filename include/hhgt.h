@@ -354,6 +354,26 @@ int hhgt_genotype_planes(hhgt_ctx *ctx, const hhgt_plane_sel *d_sel, uint32_t n_
 int hhgt_pair_counts(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
                      uint64_t w_hi, uint32_t *d_table, void *stream);
 
+/* hhgt_grm reduces the words [w_lo, w_hi) of every row of such planes to d_table, double [n_rows][n_rows], both triangles:
+ * the sums behind the genetic relationship matrix.  d_z is float [3][32 * row_words]: d_z[d][p] is the value of a call of
+ * dosage d (0 HOM_REF, 1 HET, 2 HOM_ALT) at bit position p of a plane row (the caller's standardised dosages, scattered to
+ * the positions of the variants; finite; 16-byte aligned).  With x(r, p) = d_z[d][p] for the class d whose bit row r has at position p (HET
+ * before HOM_REF before HOM_ALT, should planes overlap) and 0 without a bit,
+ *     d_table[i][j] += sum over the positions p of words [w_lo, w_hi) of x(i, p) * x(j, p).
+ * Arithmetic: v_mfma_f32_32x32x2_f32, so a pair's sum is the f32 chain c = fmaf(x(i, p), x(j, p), c) over the positions in
+ * order, one rounding per step — deterministic, and the same bits for (i, j) and (j, i) —, run for at most HHGT_GRM_SPAN
+ * words (counted from w_lo) at a time: at the end of each span, and of the range, the chain is converted to double and added
+ * to a double sum, and restarts from 0; the double sum is added to d_table at the end.  So the error of an entry is
+ * bounded by that of chains of 32 * HHGT_GRM_SPAN steps relative to the sum of |x(i, p) x(j, p)|, however long the rows and
+ * however many calls accumulate.  It ADDS to d_table (8-byte aligned) with plain read-modify-write — one workgroup owns a
+ * 64 x 64 tile of the table and its mirror image for the whole launch, which receives the same values: a table that is
+ * symmetric stays so, bit for bit —, so windows, groups and calls may accumulate on ONE stream; two streams adding to one
+ * table at the same time are the caller's error.  Any n_rows (up to 64 * 65535) and row_words (below 2^27);
+ * w_lo <= w_hi <= row_words, else HHGT_ERR_ARG. */
+#define HHGT_GRM_SPAN 128
+int hhgt_grm(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
+             const float *d_z, double *d_table, void *stream);
+
 /* Linkage disequilibrium between nearby variants, in three calls.  Dosage x of a COMPLETE call: 0 HOM_REF, 1 HET, 2 HOM_ALT;
  * a call that is not complete takes part in nothing.
  *
@@ -517,7 +537,8 @@ int hhgt_inflate_members(hhgt_ctx *ctx, const void *d_src, uint64_t src_bytes, c
 #define HHGT_STAGE_LD 11      /* eight counts per pair of nearby variants                        */
 #define HHGT_STAGE_LD_PRUNE 12 /* r^2 decisions of every pair                                    */
 #define HHGT_STAGE_LD_WALK 13 /* the greedy walk over the decisions                              */
-#define HHGT_N_STAGES 14
+#define HHGT_STAGE_GRM 14     /* sums of products of standardised dosages over genotype planes   */
+#define HHGT_N_STAGES 15
 int hhgt_profile_enable(hhgt_ctx *ctx, int on);
 int hhgt_profile_reset(hhgt_ctx *ctx);
 int hhgt_profile_read(hhgt_ctx *ctx, double *ms /*[HHGT_N_STAGES]*/, uint64_t *launches /*[HHGT_N_STAGES]*/);
