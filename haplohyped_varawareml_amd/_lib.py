@@ -81,6 +81,62 @@ class EncodeResultRec(C.Structure):     # hhgt_encode_result
         return [(int(self.run_first[i]), bytes(self.run_names[i]).split(b"\0")[0].decode()) for i in range(n)]
 
 
+_vp, _u64, _u32, _i32, _str = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_char_p
+_lay, _pu64 = C.POINTER(Layout), C.POINTER(C.c_uint64)
+# every function of include/hhgt.h and include/hhgt_synth.h this package calls: name -> (restype, argtypes).  load() applies
+# the table; tests/test_abi_binding.py holds it against the headers.  (The reader and the ingest engine have headers of their
+# own, include/hhgt_reader.h and include/hhgt_ingest.h: reader.py, sharding.py and ingest.py bind those.)
+PROTOTYPES = {
+    "hhgt_version": (_str, []),
+    "hhgt_last_error": (_str, []),
+    "hhgt_device_count": (_i32, []),
+    "hhgt_ctx_create": (_i32, [_i32, C.POINTER(_vp)]),
+    "hhgt_ctx_destroy": (None, [_vp]),
+    "hhgt_layout_bytes": (_u64, [_lay]),
+    "hhgt_layout_offset": (_u64, [_lay, _u32, _u64]),
+    "hhgt_encode_text": (_i32, [_vp, _vp, _u64, _str, _lay, _u64, _vp, _vp, _vp, _vp, _vp, C.POINTER(EncodeStats), _vp]),
+    "hhgt_encode_text_async": (_i32, [_vp, _vp, _u64, _str, _lay, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hhgt_encode_text_planes_async": (_i32, [_vp, _vp, _u64, _str, _lay, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hhgt_encode_result_status": (_i32, [_vp]),
+    "hhgt_encode_chrom_runs": (_i32, [_vp, _u32, _vp, _vp, C.POINTER(_u32)]),
+    "hhgt_pad_tail": (_i32, [_vp, _lay, _u64, _u64, _u64, _vp, _vp]),
+    "hhgt_pad_tail_cursor": (_i32, [_vp, _lay, _vp, _vp, _vp]),
+    "hhgt_planes_bytes": (_u64, [_lay]),
+    "hhgt_pad_tail_planes": (_i32, [_vp, _lay, _u64, _u64, _u64, _vp, _vp]),
+    "hhgt_pad_tail_planes_cursor": (_i32, [_vp, _lay, _vp, _vp, _vp]),
+    "hhgt_compress_planes": (_i32, [_vp, _lay, _vp, _vp, _u32, _u32, _i32, _vp, _u64, _vp, _pu64, _vp]),
+    "hhgt_planes_expand": (_i32, [_vp, _lay, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "hhgt_set_clevel": (_i32, [_vp, _i32]),
+    "hhgt_reserve": (_i32, [_vp, _u64, _u32, _u64, _u64, _i32, _i32]),
+    "hhgt_set_keep_multiallelic": (_i32, [_vp, _i32]),
+    "hhgt_set_index_mode": (_i32, [_vp, _i32]),
+    "hhgt_stream_create": (_i32, [_vp, _i32, C.POINTER(_vp)]),
+    "hhgt_stream_destroy": (_i32, [_vp, _vp]),
+    "hhgt_set_frame_stream": (_i32, [_vp, _vp]),
+    "hhgt_compress_bound": (_u64, [_u64, _u64, _i32, _i32]),
+    "hhgt_compress_chunks": (_i32, [_vp, _vp, _u64, _u64, _i32, _i32, _i32, _vp, _u64, _vp, _pu64, _vp]),
+    "hhgt_decompress_chunks": (_i32, [_vp, _vp, _vp, _u64, _u64, _i32, _i32, _vp, _pu64, _vp]),
+    "hhgt_decompress_blocks": (_i32, [_vp, _vp, _u32, _u64, _i32, _i32, _vp, _pu64, _vp]),
+    "hhgt_count_alleles": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _u64, _pu64, _vp]),
+    "hhgt_count_samples": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _u64, _vp, _u64, _pu64, _vp]),
+    "hhgt_genotype_planes": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _u64, _vp, _u64, _u64, _pu64, _vp]),
+    "hhgt_pair_counts": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
+    "hhgt_grm": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "hhgt_variant_planes": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
+    "hhgt_ld_counts": (_i32, [_vp, _vp, _u64, _u64, _u32, _vp, _vp]),
+    "hhgt_ld_prune": (_i32, [_vp, _vp, _u64, _u32, C.c_double, _vp, _vp]),
+    "hhgt_bgzf_scan": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _pu64, _pu64]),
+    "hhgt_inflate_members": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _pu64, _vp]),
+    "hhgt_onehot_windows": (_i32, [_vp, _vp, _u32, _u32, _vp, _i32, _vp, _vp, _vp]),
+    "hhgt_onehot_bases_u8": (_i32, [_vp, _vp, _u64, _vp, _i32, _vp, _vp]),
+    "hhgt_profile_enable": (_i32, [_vp, _i32]),
+    "hhgt_profile_reset": (_i32, [_vp]),
+    "hhgt_profile_read": (_i32, [_vp, C.POINTER(C.c_double), _pu64]),
+    "hhgt_synth_render_fixed": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _str, _i32, _u64, _vp]),
+    "hhgt_synth_render_mixed": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _str, _i32, _u64, _vp]),
+    "hhgt_synth_write_bgzf": (_i32, [_str, _vp, _u64, _i32, _i32]),
+}
+
 _lib = None
 
 
@@ -96,61 +152,9 @@ def load():
             f"{LIB_PATH} is missing. Build it with `python -m haplohyped_varawareml_amd.build` "
             "(hipcc, gfx950). There is no CPU fallback for this path.")
     L = C.CDLL(LIB_PATH)
-    vp, u64, i32 = C.c_void_p, C.c_uint64, C.c_int
-    L.hhgt_version.restype = C.c_char_p
-    L.hhgt_last_error.restype = C.c_char_p
-    L.hhgt_device_count.restype = i32
-    L.hhgt_ctx_create.argtypes = [i32, C.POINTER(vp)]
-    L.hhgt_ctx_destroy.argtypes = [vp]
-    L.hhgt_ctx_destroy.restype = None
-    L.hhgt_layout_bytes.restype = u64
-    L.hhgt_layout_bytes.argtypes = [C.POINTER(Layout)]
-    L.hhgt_layout_offset.restype = u64
-    L.hhgt_layout_offset.argtypes = [C.POINTER(Layout), C.c_uint32, u64]
-    L.hhgt_encode_text.argtypes = [vp, vp, u64, C.c_char_p, C.POINTER(Layout), u64, vp, vp, vp, vp, vp,
-                                   C.POINTER(EncodeStats), vp]
-    L.hhgt_encode_text_async.argtypes = [vp, vp, u64, C.c_char_p, C.POINTER(Layout), vp, C.c_uint32, vp, vp, vp, vp, vp,
-                                         vp, vp]
-    L.hhgt_planes_bytes.restype = u64
-    L.hhgt_planes_bytes.argtypes = [C.POINTER(Layout)]
-    L.hhgt_encode_text_planes_async.argtypes = [vp, vp, u64, C.c_char_p, C.POINTER(Layout), vp, C.c_uint32, vp, vp, vp, vp, vp, vp,
-                                                vp, vp]
-    L.hhgt_pad_tail_planes_cursor.argtypes = [vp, C.POINTER(Layout), vp, vp, vp]
-    L.hhgt_pad_tail_planes.argtypes = [vp, C.POINTER(Layout), u64, u64, u64, vp, vp]
-    L.hhgt_compress_planes.argtypes = [vp, C.POINTER(Layout), vp, vp, C.c_uint32, C.c_uint32, i32, vp, u64, vp, C.POINTER(u64), vp]
-    L.hhgt_planes_expand.argtypes = [vp, C.POINTER(Layout), vp, vp, C.c_uint32, C.c_uint32, vp, vp]
-    L.hhgt_encode_result_status.argtypes = [vp]
-    L.hhgt_pad_tail_cursor.argtypes = [vp, C.POINTER(Layout), vp, vp, vp]
-    L.hhgt_encode_chrom_runs.argtypes = [vp, C.c_uint32, vp, vp, C.POINTER(C.c_uint32)]
-    L.hhgt_pad_tail.argtypes = [vp, C.POINTER(Layout), u64, u64, u64, vp, vp]
-    L.hhgt_set_clevel.argtypes = [vp, i32]
-    L.hhgt_reserve.argtypes = [vp, u64, C.c_uint32, u64, u64, i32, i32]
-    L.hhgt_set_keep_multiallelic.argtypes = [vp, i32]
-    L.hhgt_set_index_mode.argtypes = [vp, i32]
-    L.hhgt_stream_create.argtypes = [vp, i32, C.POINTER(vp)]
-    L.hhgt_stream_destroy.argtypes = [vp, vp]
-    L.hhgt_set_frame_stream.argtypes = [vp, vp]
-    L.hhgt_compress_bound.restype = u64
-    L.hhgt_compress_bound.argtypes = [u64, u64, i32, i32]
-    L.hhgt_compress_chunks.argtypes = [vp, vp, u64, u64, i32, i32, i32, vp, u64, vp, C.POINTER(u64), vp]
-    L.hhgt_decompress_chunks.argtypes = [vp, vp, vp, u64, u64, i32, i32, vp, C.POINTER(u64), vp]
-    L.hhgt_decompress_blocks.argtypes = [vp, vp, C.c_uint32, u64, i32, i32, vp, C.POINTER(u64), vp]
-    L.hhgt_count_alleles.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, C.POINTER(u64), vp]
-    L.hhgt_count_samples.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, vp, u64, C.POINTER(u64), vp]
-    L.hhgt_genotype_planes.argtypes = [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, i32, i32, vp, u64, vp, u64, u64, C.POINTER(u64),
-                                       vp]
-    L.hhgt_pair_counts.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp]
-    L.hhgt_grm.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp, vp]
-    L.hhgt_variant_planes.argtypes = [vp, vp, u64, u64, u64, u64, vp, vp]
-    L.hhgt_ld_counts.argtypes = [vp, vp, u64, u64, C.c_uint32, vp, vp]
-    L.hhgt_ld_prune.argtypes = [vp, vp, u64, C.c_uint32, C.c_double, vp, vp]
-    L.hhgt_bgzf_scan.argtypes = [vp, u64, u64, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(u64)]
-    L.hhgt_inflate_members.argtypes = [vp, vp, u64, vp, vp, vp, vp, u64, vp, u64, vp, vp, C.POINTER(u64), vp]
-    L.hhgt_onehot_windows.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, i32, vp, vp, vp]
-    L.hhgt_onehot_bases_u8.argtypes = [vp, vp, u64, vp, i32, vp, vp]
-    L.hhgt_profile_enable.argtypes = [vp, i32]
-    L.hhgt_profile_reset.argtypes = [vp]
-    L.hhgt_profile_read.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64)]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -65,6 +65,52 @@ void DevBuf::release()
         if (_rc != HHGT_OK) return _rc; \
     } while (0)
 
+int EncodeWs::ensure_index(uint32_t n_regions)
+{
+    TRY(slots.ensure((size_t)n_regions * INDEX_CAP * 4));
+    TRY(counts.ensure((size_t)n_regions * 4));
+    TRY(prefix.ensure(((size_t)n_regions + 1) * 4));
+    return ensure_scan(n_regions);
+}
+
+int EncodeWs::ensure_lines(uint32_t max_lines)
+{
+    const size_t nl4 = ((size_t)max_lines + 1) * 4;
+    TRY(nl.ensure(nl4));
+    TRY(ensure_scan(max_lines));
+    for (DevBuf &b : line) TRY(b.ensure(nl4));
+    return ensure_runs();
+}
+
+int EncodeWs::ensure_scan(uint64_t n) { return scan_tmp.ensure(2 * scan_tmp_elems(n) * 4); }
+
+int EncodeWs::ensure_runs()
+{
+    TRY(run_first.ensure(MAX_CHROM_RUNS * 8));
+    TRY(run_names.ensure(MAX_CHROM_RUNS * 32));
+    return result.ensure(sizeof(hhgt_encode_result));
+}
+
+int hhgt_ctx::CodecWs::ensure(uint64_t n_chunks, uint32_t nblocks, uint32_t nwaves, size_t slot)
+{
+    const uint64_t n_streams = n_chunks * nblocks * nwaves;
+    TRY(lz_scratch.ensure((size_t)n_streams * slot));
+    TRY(lz_csize.ensure((size_t)n_streams * 4));
+    TRY(fr_bsize.ensure((size_t)n_chunks * nblocks * 4));
+    TRY(fr_csize.ensure(((size_t)n_chunks + 1) * 8));
+    return fr_flags.ensure((size_t)n_chunks * 4);
+}
+
+// a launch under the timer of its stage
+template <typename Launch>
+static int timed(hhgt_ctx *c, hipStream_t st, int stage, Launch launch)
+{
+    StageTimer t(c, st, stage);
+    TRY(launch());
+    t.stop();
+    return HHGT_OK;
+}
+
 extern "C" int hhgt_ctx_create(int device, hhgt_ctx **out)
 {
     if (!out) return HHGT_ERR_ARG;
@@ -109,11 +155,8 @@ extern "C" void hhgt_ctx_destroy(hhgt_ctx *c)
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
-    DevBuf *bufs[] = {&c->slots, &c->counts, &c->prefix, &c->nl, &c->scan_tmp, &c->l_soff, &c->l_lend, &c->l_pos,
-                      &c->l_refalt, &c->l_flags, &c->l_keep, &c->l_kidx, &c->l_cnew, &c->l_crun, &c->k_soff,
-                      &c->k_lend, &c->k_meta, &c->redo_list, &c->redo_flag, &c->run_first, &c->run_names,
-                      &c->counters, &c->cursor, &c->result, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n,
-                      &c->ld_bits};
+    c->enc.each([](DevBuf &b) { b.release(); });
+    DevBuf *bufs[] = {&c->counters, &c->cursor, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n, &c->ld_bits};
     for (DevBuf *b : bufs) b->release();
     for (auto &w : c->cw) {
         DevBuf *wb[] = {&w.lz_scratch, &w.lz_csize, &w.lz_flags, &w.fr_bsize, &w.fr_csize, &w.fr_flags};
@@ -358,18 +401,19 @@ static int encode_check_args(hhgt_ctx *c, const void *d_text, uint64_t nbytes, c
     return rc;
 }
 
+// regions of the newline index over a text block (and the byte behind it)
+static uint32_t index_regions(uint64_t nbytes) { return (uint32_t)((nbytes + 1 + INDEX_REGION - 1) / INDEX_REGION); }
+
 // stage 1: newline index of the block -> prefix[n_regions] holds the line count (device).  min_line: a record with S
 // sample columns cannot be shorter than 9 fixed columns and S fields of one byte and a separator each (0: unknown)
 static int encode_stage_index(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes, uint32_t n_regions, uint32_t min_line, uint32_t S,
                               DevCounters *cnt, hipStream_t st)
 {
-    TRY(c->slots.ensure((size_t)n_regions * INDEX_CAP * 4));
-    TRY(c->counts.ensure((size_t)n_regions * 4));
-    TRY(c->prefix.ensure(((size_t)n_regions + 1) * 4));
-    TRY(c->scan_tmp.ensure(2 * scan_tmp_elems(n_regions) * 4));
-    TRY(launch_index_newlines(text, nbytes, c->slots.as<uint32_t>(), c->counts.as<uint32_t>(), n_regions, min_line, S, c->index_mode, cnt, st));
-    TRY(launch_scan_exclusive_u32_pair(c->counts.as<uint32_t>(), c->prefix.as<uint32_t>(), nullptr, nullptr, n_regions,
-                                       c->scan_tmp.as<uint32_t>(), c->scan_tmp.cap / 4, st));
+    EncodeWs &w = c->enc;
+    TRY(w.ensure_index(n_regions));
+    TRY(launch_index_newlines(text, nbytes, w.slots.as<uint32_t>(), w.counts.as<uint32_t>(), n_regions, min_line, S, c->index_mode, cnt, st));
+    TRY(launch_scan_exclusive_u32_pair(w.counts.as<uint32_t>(), w.prefix.as<uint32_t>(), nullptr, nullptr, n_regions,
+                                       w.scan_tmp.as<uint32_t>(), w.scan_tmp.cap / 4, st));
     return HHGT_OK;
 }
 
@@ -378,66 +422,42 @@ static int encode_stage_rest(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes, 
                              const RegionFilter &rf, const LayoutDev &L, const uint64_t *d_cursor, void *d_G, void *d_P, uint32_t *d_start, uint32_t *d_stop,
                              uint8_t *d_ref, uint8_t *d_alt, DevCounters *cnt, hipStream_t st)
 {
-    const uint32_t *d_nlines = c->prefix.as<uint32_t>() + n_regions;
-    const size_t nl4 = ((size_t)max_lines + 1) * 4;
-    TRY(c->nl.ensure(nl4));
-    TRY(c->scan_tmp.ensure(2 * scan_tmp_elems(max_lines) * 4));
-    DevBuf *per_line[] = {&c->l_soff, &c->l_lend, &c->l_pos, &c->l_refalt, &c->l_flags, &c->l_keep,
-                          &c->l_kidx, &c->l_cnew, &c->l_crun, &c->k_soff, &c->k_lend, &c->k_meta,
-                          &c->redo_list, &c->redo_flag};
-    for (DevBuf *b : per_line) TRY(b->ensure(nl4));
-    TRY(c->run_first.ensure(MAX_CHROM_RUNS * 8));
-    TRY(c->run_names.ensure(MAX_CHROM_RUNS * 32));
-    {
-        StageTimer t(c, st, HHGT_STAGE_INDEX);
-        TRY(launch_compact_newlines(c->slots.as<uint32_t>(), c->counts.as<uint32_t>(), c->prefix.as<uint32_t>(),
-                                    n_regions, c->nl.as<uint32_t>(), max_lines, st));
-        t.stop();
-    }
+    EncodeWs &w = c->enc;
+    TRY(w.ensure_lines(max_lines));
+    const uint32_t *nl = w.nl.as<uint32_t>(), *d_nlines = w.prefix.as<uint32_t>() + n_regions;
+    uint32_t *scan_tmp = w.scan_tmp.as<uint32_t>();
+    const LineCols l = w.line_cols();
+    const KeptCols k = w.kept_cols();
+    TRY(timed(c, st, HHGT_STAGE_INDEX, [&] {
+        return launch_compact_newlines(w.slots.as<uint32_t>(), w.counts.as<uint32_t>(), w.prefix.as<uint32_t>(), n_regions,
+                                       w.nl.as<uint32_t>(), max_lines, st);
+    }));
     if (max_lines == 0) return HHGT_OK;
-    {
-        StageTimer t(c, st, HHGT_STAGE_FIXED);
-        TRY(launch_parse_fixed(text, nbytes, c->nl.as<uint32_t>(), d_nlines, max_lines, rf, L.S,
-                               c->l_soff.as<uint32_t>(), c->l_lend.as<uint32_t>(), c->l_pos.as<uint32_t>(),
-                               c->l_refalt.as<uint32_t>(), c->l_flags.as<uint32_t>(), c->l_keep.as<uint32_t>(),
-                               c->l_cnew.as<uint32_t>(), c->index_mode, cnt, st));
-        TRY(launch_scan_exclusive_u32_pair(c->l_keep.as<uint32_t>(), c->l_kidx.as<uint32_t>(), c->l_cnew.as<uint32_t>(),
-                                           c->l_crun.as<uint32_t>(), max_lines, c->scan_tmp.as<uint32_t>(), c->scan_tmp.cap / 4, st));
-        TRY(launch_compact_kept(text, nbytes, c->nl.as<uint32_t>(), d_nlines, max_lines, c->l_soff.as<uint32_t>(),
-                                c->l_lend.as<uint32_t>(), c->l_pos.as<uint32_t>(), c->l_refalt.as<uint32_t>(),
-                                c->l_flags.as<uint32_t>(), c->l_kidx.as<uint32_t>(), c->l_crun.as<uint32_t>(),
-                                c->k_soff.as<uint32_t>(), c->k_lend.as<uint32_t>(), c->k_meta.as<uint32_t>(),
-                                c->redo_list.as<uint32_t>(), c->redo_flag.as<uint32_t>(), c->run_first.as<uint64_t>(), c->run_names.as<uint8_t>(),
-                                MAX_CHROM_RUNS, d_cursor, L.v_capacity, L.ring, d_start, d_stop, d_ref, d_alt, cnt, d_P != nullptr, st));
-        t.stop();
-    }
-    if (L.S > 0) {
-        StageTimer t(c, st, HHGT_STAGE_ENCODE);
-        if (d_P)
-            TRY(launch_encode_planes(text, nbytes, c->k_soff.as<uint32_t>(), c->k_meta.as<uint32_t>(), max_lines, d_cursor, L,
-                                     static_cast<uint8_t *>(d_P), static_cast<int8_t *>(d_G), c->redo_list.as<uint32_t>(),
-                                     c->redo_flag.as<uint32_t>(), cnt, st));
-        else
-            TRY(launch_encode_tiles(text, nbytes, c->k_soff.as<uint32_t>(), c->k_meta.as<uint32_t>(), max_lines, d_cursor,
-                                    L, static_cast<int8_t *>(d_G), c->redo_list.as<uint32_t>(),
-                                    c->redo_flag.as<uint32_t>(), cnt, st));
-        t.stop();
-        StageTimer t2(c, st, HHGT_STAGE_GENERAL);
-        TRY(launch_encode_general(text, nbytes, c->k_soff.as<uint32_t>(), c->k_lend.as<uint32_t>(),
-                                  c->k_meta.as<uint32_t>(), c->redo_list.as<uint32_t>(), d_cursor, L,
-                                  static_cast<int8_t *>(d_G), static_cast<uint8_t *>(d_P), cnt, c->prop.multiProcessorCount, st));
-        t2.stop();
-    }
-    return HHGT_OK;
+    TRY(timed(c, st, HHGT_STAGE_FIXED, [&] {
+        TRY(launch_parse_fixed(text, nbytes, nl, d_nlines, max_lines, rf, L.S, l, c->index_mode, cnt, st));
+        TRY(launch_scan_exclusive_u32_pair(l.keep, l.kidx, l.cnew, l.crun, max_lines, scan_tmp, w.scan_tmp.cap / 4, st));
+        return launch_compact_kept(text, nbytes, nl, d_nlines, max_lines, l, k, MAX_CHROM_RUNS, d_cursor, L.v_capacity, L.ring,
+                                   d_start, d_stop, d_ref, d_alt, cnt, d_P != nullptr, st);
+    }));
+    if (L.S == 0) return HHGT_OK;
+    TRY(timed(c, st, HHGT_STAGE_ENCODE, [&] {
+        return d_P ? launch_encode_planes(text, nbytes, k.soff, k.meta, max_lines, d_cursor, L, static_cast<uint8_t *>(d_P),
+                                          static_cast<int8_t *>(d_G), k.redo_list, k.redo_flag, cnt, st)
+                   : launch_encode_tiles(text, nbytes, k.soff, k.meta, max_lines, d_cursor, L, static_cast<int8_t *>(d_G),
+                                         k.redo_list, k.redo_flag, cnt, st);
+    }));
+    return timed(c, st, HHGT_STAGE_GENERAL, [&] {
+        return launch_encode_general(text, nbytes, k.soff, k.lend, k.meta, k.redo_list, d_cursor, L, static_cast<int8_t *>(d_G),
+                                     static_cast<uint8_t *>(d_P), cnt, c->prop.multiProcessorCount, st);
+    });
 }
 
 static int encode_finish(hhgt_ctx *c, uint64_t *d_cursor, const LayoutDev &L, DevCounters *cnt, hipStream_t st)
 {
-    TRY(c->run_first.ensure(MAX_CHROM_RUNS * 8));
-    TRY(c->run_names.ensure(MAX_CHROM_RUNS * 32));
-    TRY(c->result.ensure(sizeof(hhgt_encode_result)));
-    hipLaunchKernelGGL(k_encode_finish, dim3(1), dim3(256), 0, st, cnt, d_cursor, c->run_first.as<uint64_t>(),
-                       c->run_names.as<uint8_t>(), L.ring ? 0ull : L.v_capacity, c->result.as<hhgt_encode_result>());
+    TRY(c->enc.ensure_runs());
+    const KeptCols k = c->enc.kept_cols();
+    hipLaunchKernelGGL(k_encode_finish, dim3(1), dim3(256), 0, st, cnt, d_cursor, k.run_first, k.run_names,
+                       L.ring ? 0ull : L.v_capacity, c->enc.result.as<hhgt_encode_result>());
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }
@@ -513,6 +533,25 @@ static int planes_columns(const hhgt_layout *lay, uint32_t col0, uint32_t n_cols
     return HHGT_OK;
 }
 
+// what the four pad_tail entry points begin with: the null checks (the cursor forms add theirs), the device, the layout (planes: one that carries them)
+static int pad_tail_begin(hhgt_ctx *c, const void *d_buf, const hhgt_layout *lay, bool planes, LayoutDev *L)
+{
+    if (!c || !d_buf) return HHGT_ERR_ARG;
+    HIP_TRY(hipSetDevice(c->device));
+    TRY(make_layout(lay, L));
+    return planes ? planes_check_layout(*L) : HHGT_OK;
+}
+
+// the range form: v_end and the columns lie inside the layout
+static int pad_tail_range(const LayoutDev &L, uint64_t v_end, uint64_t vcol_end)
+{
+    if (v_end > L.v_capacity || vcol_end > L.v_capacity / L.Vc) {
+        hhgt_set_error("pad_tail: range outside the layout");
+        return HHGT_ERR_ARG;
+    }
+    return HHGT_OK;
+}
+
 static int encode_async_impl(hhgt_ctx *c, const void *d_text, uint64_t nbytes, const char *region, const hhgt_layout *lay,
                              uint64_t *d_cursor, uint32_t max_lines, void *d_G, void *d_P, bool planes, uint32_t *d_start,
                              uint32_t *d_stop, uint8_t *d_ref, uint8_t *d_alt, hhgt_encode_result *h_result, void *stream)
@@ -528,13 +567,9 @@ static int encode_async_impl(hhgt_ctx *c, const void *d_text, uint64_t nbytes, c
     DevCounters *cnt = c->counters.as<DevCounters>();
     if (!c->counters_clean) HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(DevCounters), st));   // (the last call's epilogue did not get to zero them)
     c->counters_clean = false;
-    const uint32_t n_regions = (uint32_t)((nbytes + 1 + INDEX_REGION - 1) / INDEX_REGION);
+    const uint32_t n_regions = index_regions(nbytes);
     if (nbytes) {
-        {
-            StageTimer t(c, st, HHGT_STAGE_INDEX);
-            TRY(encode_stage_index(c, text, nbytes, n_regions, L.S ? 2u * L.S + 17u : 0u, L.S, cnt, st));
-            t.stop();
-        }
+        TRY(timed(c, st, HHGT_STAGE_INDEX, [&] { return encode_stage_index(c, text, nbytes, n_regions, L.S ? 2u * L.S + 17u : 0u, L.S, cnt, st); }));
         TRY(encode_stage_rest(c, text, nbytes, n_regions, max_lines, rf, L, d_cursor, d_G, planes ? d_P : nullptr, d_start, d_stop, d_ref,
                               d_alt, cnt, st));
     }
@@ -542,7 +577,7 @@ static int encode_async_impl(hhgt_ctx *c, const void *d_text, uint64_t nbytes, c
     c->counters_clean = true;   // (calls on one context are serialised by the caller: the next one is queued behind this epilogue)
     if (h_result) {
         h_result->done = 0u;
-        HIP_TRY(hipMemcpyAsync(h_result, c->result.p, sizeof(hhgt_encode_result), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_result, c->enc.result.p, sizeof(hhgt_encode_result), hipMemcpyDeviceToHost, st));
     }
     return HHGT_OK;
 }
@@ -568,25 +603,17 @@ extern "C" int hhgt_encode_text_planes_async(hhgt_ctx *c, const void *d_text, ui
 extern "C" int hhgt_pad_tail_planes(hhgt_ctx *c, const hhgt_layout *lay, uint64_t v_end, uint64_t vcol_begin, uint64_t vcol_end,
                                     void *d_P, void *stream)
 {
-    if (!c || !d_P) return HHGT_ERR_ARG;
-    HIP_TRY(hipSetDevice(c->device));
     LayoutDev L;
-    TRY(make_layout(lay, &L));
-    TRY(planes_check_layout(L));
-    if (v_end > L.v_capacity || vcol_end > L.v_capacity / L.Vc) {
-        hhgt_set_error("pad_tail: range outside the layout");
-        return HHGT_ERR_ARG;
-    }
+    TRY(pad_tail_begin(c, d_P, lay, true, &L));
+    TRY(pad_tail_range(L, v_end, vcol_end));
     return launch_pad_tail_planes(L, v_end, vcol_begin, vcol_end, static_cast<uint8_t *>(d_P), reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int hhgt_pad_tail_planes_cursor(hhgt_ctx *c, const hhgt_layout *lay, const uint64_t *d_cursor, void *d_P, void *stream)
 {
-    if (!c || !d_P || !d_cursor) return HHGT_ERR_ARG;
-    HIP_TRY(hipSetDevice(c->device));
     LayoutDev L;
-    TRY(make_layout(lay, &L));
-    TRY(planes_check_layout(L));
+    if (!d_cursor) return HHGT_ERR_ARG;
+    TRY(pad_tail_begin(c, d_P, lay, true, &L));
     return launch_pad_tail_planes_cursor(L, d_cursor, static_cast<uint8_t *>(d_P), reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -652,7 +679,7 @@ static int encode_text_once(hhgt_ctx *c, const void *d_text, uint64_t nbytes, co
     HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(DevCounters), st));
     c->counters_clean = false;
     hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, st, c->cursor.as<uint64_t>(), v_base);
-    const uint32_t n_regions = (uint32_t)((nbytes + 1 + INDEX_REGION - 1) / INDEX_REGION);
+    const uint32_t n_regions = index_regions(nbytes);
     uint32_t n_lines = 0;
     {
         // the synchronous form sizes everything by the exact line count: it is read back once (any input, however
@@ -661,7 +688,7 @@ static int encode_text_once(hhgt_ctx *c, const void *d_text, uint64_t nbytes, co
         TRY(encode_stage_index(c, text, nbytes, n_regions, L.S ? 2u * L.S + 17u : 0u, L.S, cnt, st));
         c->h_counters->n_lines = 0;
         c->h_counters->err_density = 0;
-        HIP_TRY(hipMemcpyAsync(&c->h_counters->n_lines, c->prefix.as<uint32_t>() + n_regions, 4,
+        HIP_TRY(hipMemcpyAsync(&c->h_counters->n_lines, c->enc.prefix.as<uint32_t>() + n_regions, 4,
                                hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&c->h_counters->err_density, &cnt->err_density, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -681,7 +708,7 @@ static int encode_text_once(hhgt_ctx *c, const void *d_text, uint64_t nbytes, co
     c->counters_clean = true;
     hhgt_encode_result *hr = &c->h_result;
     hr->done = 0u;
-    HIP_TRY(hipMemcpyAsync(c->h_result_pinned, c->result.p, sizeof(hhgt_encode_result), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c->h_result_pinned, c->enc.result.p, sizeof(hhgt_encode_result), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     *hr = *c->h_result_pinned;
     if (stats) *stats = hr->stats;
@@ -695,8 +722,8 @@ static int encode_text_once(hhgt_ctx *c, const void *d_text, uint64_t nbytes, co
             memcpy(first.data(), hr->run_first, n_runs * 8);
             memcpy(names.data(), hr->run_names, (size_t)n_runs * 32);
         } else {
-            HIP_TRY(hipMemcpy(first.data(), c->run_first.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(names.data(), c->run_names.p, (size_t)n_runs * 32, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(first.data(), c->enc.run_first.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(names.data(), c->enc.run_names.p, (size_t)n_runs * 32, hipMemcpyDeviceToHost));
         }
         for (uint32_t r = 0; r < n_runs; ++r) {
             c->run_first_kept.push_back(first[r]);
@@ -727,24 +754,18 @@ extern "C" int hhgt_encode_chrom_runs(hhgt_ctx *c, uint32_t max_runs, uint64_t *
 extern "C" int hhgt_pad_tail(hhgt_ctx *c, const hhgt_layout *lay, uint64_t v_end, uint64_t vcol_begin,
                              uint64_t vcol_end, void *d_G, void *stream)
 {
-    if (!c || !d_G) return HHGT_ERR_ARG;
-    HIP_TRY(hipSetDevice(c->device));
     LayoutDev L;
-    TRY(make_layout(lay, &L));
-    if (v_end > L.v_capacity || vcol_end > L.v_capacity / L.Vc) {
-        hhgt_set_error("pad_tail: range outside the layout");
-        return HHGT_ERR_ARG;
-    }
+    TRY(pad_tail_begin(c, d_G, lay, false, &L));
+    TRY(pad_tail_range(L, v_end, vcol_end));
     return launch_pad_tail(L, v_end, vcol_begin, vcol_end, static_cast<int8_t *>(d_G),
                            reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int hhgt_pad_tail_cursor(hhgt_ctx *c, const hhgt_layout *lay, const uint64_t *d_cursor, void *d_G, void *stream)
 {
-    if (!c || !d_G || !d_cursor) return HHGT_ERR_ARG;
-    HIP_TRY(hipSetDevice(c->device));
     LayoutDev L;
-    TRY(make_layout(lay, &L));
+    if (!d_cursor) return HHGT_ERR_ARG;
+    TRY(pad_tail_begin(c, d_G, lay, false, &L));
     return launch_pad_tail_cursor(L, d_cursor, static_cast<int8_t *>(d_G), reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -821,46 +842,37 @@ static int compress_impl(hhgt_ctx *c, const void *d_src, const void *d_planes, P
     uint32_t nblocks, nwaves;
     size_t slot;
     codec_geometry(chunk_nbytes, typesize, blocksize, &nblocks, &nwaves, &slot);
-    const uint64_t n_streams = n_chunks * nblocks * nwaves;
     // With a frame stream the framing of this call runs there, behind the LZ4 kernels, while the caller's stream is free
     // for the LZ4 kernels of the next call — which write the other workspace set, and wait for the framing that last read it.
     hipStream_t fst = c->frame_stream ? c->frame_stream : st;
     hhgt_ctx::CodecWs &w = c->cw[c->frame_stream ? (c->cmp_seq++ & 1u) : 0u];
-    TRY(w.lz_scratch.ensure((size_t)n_streams * slot));
-    TRY(w.lz_csize.ensure((size_t)n_streams * 4));
-    TRY(w.fr_bsize.ensure((size_t)n_chunks * nblocks * 4));
-    TRY(w.fr_csize.ensure(((size_t)n_chunks + 1) * 8));
-    TRY(w.fr_flags.ensure((size_t)n_chunks * 4));
+    TRY(w.ensure(n_chunks, nblocks, nwaves, slot));
     if (w.fr_pending) {
         HIP_TRY(hipStreamWaitEvent(st, w.fr_done, 0));
         w.fr_pending = false;
     }
-    {
-        StageTimer t(c, st, HHGT_STAGE_LZ4);
+    TRY(timed(c, st, HHGT_STAGE_LZ4, [&] {
         if (!w.lz_flags.p) {
             TRY(w.lz_flags.ensure(4));
             HIP_TRY(hipMemsetAsync(w.lz_flags.p, 0, 4, st));
         }
         if (++w.lz_tag == 0) w.lz_tag = 1;
-        TRY(launch_lz4_blocks(static_cast<const uint8_t *>(d_src), static_cast<const uint8_t *>(d_planes), pg, n_chunks, chunk_nbytes, typesize,
-                              blocksize, w.lz_scratch.as<uint8_t>(), slot, w.lz_csize.as<uint32_t>(), c->clevel, w.lz_flags.as<uint32_t>(),
-                              w.lz_tag, st));
-        t.stop();
-    }
+        return launch_lz4_blocks(static_cast<const uint8_t *>(d_src), static_cast<const uint8_t *>(d_planes), pg, n_chunks, chunk_nbytes,
+                                 typesize, blocksize, w.lz_scratch.as<uint8_t>(), slot, w.lz_csize.as<uint32_t>(), c->clevel,
+                                 w.lz_flags.as<uint32_t>(), w.lz_tag, st);
+    }));
     if (fst != st) {
         if (!w.lz_done) HIP_TRY(hipEventCreateWithFlags(&w.lz_done, hipEventDisableTiming));
         if (!w.fr_done) HIP_TRY(hipEventCreateWithFlags(&w.fr_done, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(w.lz_done, st));
         HIP_TRY(hipStreamWaitEvent(fst, w.lz_done, 0));
     }
-    {
-        StageTimer t(c, fst, HHGT_STAGE_FRAME);
-        TRY(launch_frame(w.lz_scratch.as<uint8_t>(), slot, w.lz_csize.as<uint32_t>(),
-                         static_cast<const uint8_t *>(d_src), static_cast<const uint8_t *>(d_planes), pg, n_chunks, chunk_nbytes, typesize,
-                         blocksize, format, w.fr_bsize.as<uint32_t>(), w.fr_csize.as<uint64_t>(), static_cast<uint8_t *>(d_dst),
-                         dst_cap, d_chunk_off, w.fr_flags.as<uint32_t>(), fst));
-        t.stop();
-    }
+    TRY(timed(c, fst, HHGT_STAGE_FRAME, [&] {
+        return launch_frame(w.lz_scratch.as<uint8_t>(), slot, w.lz_csize.as<uint32_t>(), static_cast<const uint8_t *>(d_src),
+                            static_cast<const uint8_t *>(d_planes), pg, n_chunks, chunk_nbytes, typesize, blocksize, format,
+                            w.fr_bsize.as<uint32_t>(), w.fr_csize.as<uint64_t>(), static_cast<uint8_t *>(d_dst), dst_cap, d_chunk_off,
+                            w.fr_flags.as<uint32_t>(), fst);
+    }));
     if (fst != st) {
         HIP_TRY(hipEventRecord(w.fr_done, fst));
         w.fr_pending = true;
@@ -913,20 +925,10 @@ extern "C" int hhgt_reserve(hhgt_ctx *c, uint64_t text_bytes, uint32_t max_lines
     if (!c) return HHGT_ERR_ARG;
     HIP_TRY(hipSetDevice(c->device));
     if (text_bytes) {
-        const uint32_t n_regions = (uint32_t)((text_bytes + 1 + INDEX_REGION - 1) / INDEX_REGION);
-        TRY(c->slots.ensure((size_t)n_regions * INDEX_CAP * 4));
-        TRY(c->counts.ensure((size_t)n_regions * 4));
-        TRY(c->prefix.ensure(((size_t)n_regions + 1) * 4));
-        const size_t st_el = scan_tmp_elems(n_regions) > scan_tmp_elems(max_lines) ? scan_tmp_elems(n_regions) : scan_tmp_elems(max_lines);
-        TRY(c->scan_tmp.ensure(2 * st_el * 4));
-        const size_t nl4 = ((size_t)max_lines + 1) * 4;
-        TRY(c->nl.ensure(nl4));
-        DevBuf *per_line[] = {&c->l_soff, &c->l_lend, &c->l_pos, &c->l_refalt, &c->l_flags, &c->l_keep, &c->l_kidx, &c->l_cnew, &c->l_crun,
-                              &c->k_soff, &c->k_lend, &c->k_meta, &c->redo_list, &c->redo_flag};
-        for (DevBuf *b : per_line) TRY(b->ensure(nl4));
-        TRY(c->run_first.ensure(MAX_CHROM_RUNS * 8));
-        TRY(c->run_names.ensure(MAX_CHROM_RUNS * 32));
-        TRY(c->result.ensure(sizeof(hhgt_encode_result)));
+        const uint32_t n_regions = index_regions(text_bytes);
+        TRY(c->enc.ensure_scan(n_regions > max_lines ? n_regions : max_lines));   // the larger of the two scans: made once
+        TRY(c->enc.ensure_index(n_regions));
+        TRY(c->enc.ensure_lines(max_lines));
     }
     if (n_chunks) {
         TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));
@@ -934,13 +936,7 @@ extern "C" int hhgt_reserve(hhgt_ctx *c, uint64_t text_bytes, uint32_t max_lines
         uint32_t nblocks, nwaves;
         size_t slot;
         codec_geometry(chunk_nbytes, typesize, blocksize, &nblocks, &nwaves, &slot);
-        const uint64_t n_streams = n_chunks * nblocks * nwaves;
-        hhgt_ctx::CodecWs &w = c->cw[0];
-        TRY(w.lz_scratch.ensure((size_t)n_streams * slot));
-        TRY(w.lz_csize.ensure((size_t)n_streams * 4));
-        TRY(w.fr_bsize.ensure((size_t)n_chunks * nblocks * 4));
-        TRY(w.fr_csize.ensure(((size_t)n_chunks + 1) * 8));
-        TRY(w.fr_flags.ensure((size_t)n_chunks * 4));
+        TRY(c->cw[0].ensure(n_chunks, nblocks, nwaves, slot));
     }
     return HHGT_OK;
 }
@@ -1057,13 +1053,10 @@ extern "C" int hhgt_inflate_members(hhgt_ctx *c, const void *d_src, uint64_t src
         HIP_TRY(hipMemcpy(c->crc_x2n.p, t, sizeof(t), hipMemcpyHostToDevice));
         c->crc_x2n_ready = true;
     }
-    {
-        StageTimer t(c, st, HHGT_STAGE_INFLATE);
-        TRY(launch_inflate(static_cast<const uint8_t *>(d_src), src_bytes, d_comp_off, d_comp_len, d_out_off, d_isize,
-                           n_members, static_cast<uint8_t *>(d_dst), dst_bytes, d_status, d_crc32,
-                           c->crc_x2n.as<uint32_t>(), st));
-        t.stop();
-    }
+    TRY(timed(c, st, HHGT_STAGE_INFLATE, [&] {
+        return launch_inflate(static_cast<const uint8_t *>(d_src), src_bytes, d_comp_off, d_comp_len, d_out_off, d_isize, n_members,
+                              static_cast<uint8_t *>(d_dst), dst_bytes, d_status, d_crc32, c->crc_x2n.as<uint32_t>(), st);
+    }));
     if (n_bad) {
         TRY(c->dec_bad.ensure(8));
         HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
@@ -1085,11 +1078,7 @@ static int with_bad_counter(hhgt_ctx *c, hipStream_t st, uint64_t *n_bad, Launch
 {
     TRY(c->dec_bad.ensure(8));
     HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
-    {
-        StageTimer t(c, st, HHGT_STAGE_DECODE);
-        TRY(launch(c->dec_bad.as<unsigned long long>()));
-        t.stop();
-    }
+    TRY(timed(c, st, HHGT_STAGE_DECODE, [&] { return launch(c->dec_bad.as<unsigned long long>()); }));
     if (n_bad) {
         uint64_t nb = 0;
         HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
@@ -1208,129 +1197,107 @@ extern "C" int hhgt_genotype_planes(hhgt_ctx *c, const hhgt_plane_sel *d_sel, ui
                           });
 }
 
-extern "C" int hhgt_pair_counts(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
-                                uint64_t w_hi, uint32_t *d_table, void *stream)
+// what hhgt_pair_counts, hhgt_grm and hhgt_variant_planes do alike.  null_arg: the name of the first null pointer among those
+// the work needs, misaligned: what to say about a pointer off its alignment (nullptr: none); the words [w_lo, w_hi) must lie
+// in the rows, of which there are at most row_limit; nothing to do without rows or words; the launch under its stage's timer
+template <typename Launch>
+static int run_plane_kernel(const char *who, int stage, hhgt_ctx *c, const char *null_arg, const char *misaligned, uint64_t n_rows,
+                            uint64_t row_words, uint64_t w_lo, uint64_t w_hi, uint64_t row_limit, void *stream, Launch launch)
 {
     const bool work = n_rows && w_lo < w_hi;
-    if (!c || (work && (!d_planes || !d_table))) {
-        hhgt_set_error("pair_counts: null %s", !c ? "context" : !d_planes ? "planes" : "table");
+    if (!c || (work && null_arg)) {
+        hhgt_set_error("%s: null %s", who, !c ? "context" : null_arg);
         return HHGT_ERR_ARG;
     }
-    if (w_lo > w_hi || w_hi > row_words || n_rows > 64ull * 65535ull) {
-        hhgt_set_error("pair_counts: words [%llu, %llu) of rows of %llu words, %llu rows", (unsigned long long)w_lo,
+    if (w_lo > w_hi || w_hi > row_words || n_rows > row_limit) {
+        hhgt_set_error("%s: words [%llu, %llu) of rows of %llu words, %llu rows", who, (unsigned long long)w_lo,
                        (unsigned long long)w_hi, (unsigned long long)row_words, (unsigned long long)n_rows);
         return HHGT_ERR_ARG;
     }
-    if (reinterpret_cast<uintptr_t>(d_table) & 15u) {
-        hhgt_set_error("pair_counts: the table must be 16-byte aligned");
+    if (misaligned) {
+        hhgt_set_error("%s: %s", who, misaligned);
         return HHGT_ERR_ARG;
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
     if (!work) return HHGT_OK;
-    StageTimer t(c, st, HHGT_STAGE_PAIRS);
-    TRY(launch_pair_counts(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_table, st));
-    t.stop();
-    return HHGT_OK;
+    return timed(c, st, stage, [&] { return launch(st); });
+}
+
+static bool off_alignment(const void *p, uintptr_t align) { return reinterpret_cast<uintptr_t>(p) & (align - 1u); }
+
+extern "C" int hhgt_pair_counts(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
+                                uint64_t w_hi, uint32_t *d_table, void *stream)
+{
+    return run_plane_kernel("pair_counts", HHGT_STAGE_PAIRS, c, !d_planes ? "planes" : !d_table ? "table" : nullptr,
+                            off_alignment(d_table, 16) ? "the table must be 16-byte aligned" : nullptr, n_rows, row_words, w_lo, w_hi,
+                            64ull * 65535ull, stream, [&](hipStream_t st) {
+                                return launch_pair_counts(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_table, st);
+                            });
 }
 
 extern "C" int hhgt_grm(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
                         const float *d_z, double *d_table, void *stream)
 {
-    const bool work = n_rows && w_lo < w_hi;
-    if (!c || (work && (!d_planes || !d_z || !d_table))) {
-        hhgt_set_error("grm: null %s", !c ? "context" : !d_planes ? "planes" : !d_z ? "weights" : "table");
-        return HHGT_ERR_ARG;
-    }
-    if (w_lo > w_hi || w_hi > row_words || n_rows > 64ull * 65535ull) {
-        hhgt_set_error("grm: words [%llu, %llu) of rows of %llu words, %llu rows", (unsigned long long)w_lo,
-                       (unsigned long long)w_hi, (unsigned long long)row_words, (unsigned long long)n_rows);
-        return HHGT_ERR_ARG;
-    }
-    if ((reinterpret_cast<uintptr_t>(d_table) & 7u) || (reinterpret_cast<uintptr_t>(d_z) & 15u)) {
-        hhgt_set_error("grm: the table must be 8-byte aligned, the weights 16-byte aligned");
-        return HHGT_ERR_ARG;
-    }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!work) return HHGT_OK;
-    StageTimer t(c, st, HHGT_STAGE_GRM);
-    TRY(launch_grm(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_z, d_table, st));
-    t.stop();
-    return HHGT_OK;
+    return run_plane_kernel("grm", HHGT_STAGE_GRM, c, !d_planes ? "planes" : !d_z ? "weights" : !d_table ? "table" : nullptr,
+                            off_alignment(d_table, 8) || off_alignment(d_z, 16)
+                                ? "the table must be 8-byte aligned, the weights 16-byte aligned" : nullptr,
+                            n_rows, row_words, w_lo, w_hi, 64ull * 65535ull, stream, [&](hipStream_t st) {
+                                return launch_grm(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_z, d_table, st);
+                            });
 }
 
 extern "C" int hhgt_variant_planes(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
                                    uint64_t w_hi, uint32_t *d_vplanes, void *stream)
 {
-    const bool work = n_rows && w_lo < w_hi;
-    if (!c || (work && (!d_planes || !d_vplanes))) {
-        hhgt_set_error("variant_planes: null %s", !c ? "context" : !d_planes ? "planes" : "variant planes");
+    return run_plane_kernel("variant_planes", HHGT_STAGE_LD_TRANSPOSE, c, !d_planes ? "planes" : !d_vplanes ? "variant planes" : nullptr,
+                            nullptr, n_rows, row_words, w_lo, w_hi, 256ull * 65535ull, stream, [&](hipStream_t st) {
+                                return launch_variant_planes(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_vplanes, st);
+                            });
+}
+
+// what hhgt_ld_counts and hhgt_ld_prune check alike: the window (and r2, where there is one), the pointers (null_arg as above),
+// the table's alignment
+static int check_ld_args(const char *who, hhgt_ctx *c, uint32_t window, const double *r2, const char *null_arg, const uint32_t *d_table)
+{
+    if (window < 1u || window > 1024u || (r2 && !(*r2 >= 0.0 && *r2 <= 1.0))) {
+        if (r2)
+            hhgt_set_error("%s: window %u, r2 %g (1 to 1024, 0 to 1)", who, window, *r2);
+        else
+            hhgt_set_error("%s: window %u (1 to 1024)", who, window);
         return HHGT_ERR_ARG;
     }
-    if (w_lo > w_hi || w_hi > row_words || n_rows > 256ull * 65535ull) {
-        hhgt_set_error("variant_planes: words [%llu, %llu) of rows of %llu words, %llu rows", (unsigned long long)w_lo,
-                       (unsigned long long)w_hi, (unsigned long long)row_words, (unsigned long long)n_rows);
+    if (!c || null_arg) {
+        hhgt_set_error("%s: null %s", who, !c ? "context" : null_arg);
         return HHGT_ERR_ARG;
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!work) return HHGT_OK;
-    StageTimer t(c, st, HHGT_STAGE_LD_TRANSPOSE);
-    TRY(launch_variant_planes(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_vplanes, st));
-    t.stop();
+    if (off_alignment(d_table, 32)) {
+        hhgt_set_error("%s: the table must be 32-byte aligned", who);
+        return HHGT_ERR_ARG;
+    }
     return HHGT_OK;
 }
 
 extern "C" int hhgt_ld_counts(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, uint32_t window,
                               uint32_t *d_table, void *stream)
 {
-    if (window < 1u || window > 1024u) {
-        hhgt_set_error("ld_counts: window %u (1 to 1024)", window);
-        return HHGT_ERR_ARG;
-    }
     const bool work = n_var && sw;
-    if (!c || (work && (!d_vplanes || !d_table))) {
-        hhgt_set_error("ld_counts: null %s", !c ? "context" : !d_vplanes ? "variant planes" : "table");
-        return HHGT_ERR_ARG;
-    }
-    if (reinterpret_cast<uintptr_t>(d_table) & 31u) {
-        hhgt_set_error("ld_counts: the table must be 32-byte aligned");
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_ld_args("ld_counts", c, window, nullptr, !work ? nullptr : !d_vplanes ? "variant planes" : !d_table ? "table" : nullptr, d_table));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
     if (!work) return HHGT_OK;
-    StageTimer t(c, st, HHGT_STAGE_LD);
-    TRY(launch_ld_counts(d_vplanes, n_var, sw, window, d_table, st));
-    t.stop();
-    return HHGT_OK;
+    return timed(c, st, HHGT_STAGE_LD, [&] { return launch_ld_counts(d_vplanes, n_var, sw, window, d_table, st); });
 }
 
 extern "C" int hhgt_ld_prune(hhgt_ctx *c, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2,
                              uint8_t *d_keep, void *stream)
 {
-    if (window < 1u || window > 1024u || !(r2 >= 0.0 && r2 <= 1.0)) {
-        hhgt_set_error("ld_prune: window %u, r2 %g (1 to 1024, 0 to 1)", window, r2);
-        return HHGT_ERR_ARG;
-    }
-    if (!c || (n_var && (!d_table || !d_keep))) {
-        hhgt_set_error("ld_prune: null %s", !c ? "context" : !d_table ? "table" : "keep flags");
-        return HHGT_ERR_ARG;
-    }
-    if (reinterpret_cast<uintptr_t>(d_table) & 31u) {
-        hhgt_set_error("ld_prune: the table must be 32-byte aligned");
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_ld_args("ld_prune", c, window, &r2, !n_var ? nullptr : !d_table ? "table" : !d_keep ? "keep flags" : nullptr, d_table));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
     if (!n_var) return HHGT_OK;
     TRY(c->ld_bits.ensure((size_t)n_var * ld_walk_words(window) * sizeof(uint64_t)));
-    StageTimer t(c, st, HHGT_STAGE_LD_PRUNE);
-    TRY(launch_ld_exceeds(d_table, n_var, window, r2, c->ld_bits.as<uint64_t>(), st));
-    t.stop();
-    StageTimer w(c, st, HHGT_STAGE_LD_WALK);
-    TRY(launch_ld_walk(c->ld_bits.as<uint64_t>(), n_var, window, d_keep, st));
-    w.stop();
-    return HHGT_OK;
+    uint64_t *bits = c->ld_bits.as<uint64_t>();
+    TRY(timed(c, st, HHGT_STAGE_LD_PRUNE, [&] { return launch_ld_exceeds(d_table, n_var, window, r2, bits, st); }));
+    return timed(c, st, HHGT_STAGE_LD_WALK, [&] { return launch_ld_walk(bits, n_var, window, d_keep, st); });
 }

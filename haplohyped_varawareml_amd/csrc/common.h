@@ -148,16 +148,59 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// the per-line columns of an encode call as the launchers take them: one word per line of the text block.  k_parse_fixed
+// writes soff .. flags, keep and cnew; the scan turns keep / cnew into kidx / crun; k_compact_kept reads all but keep / cnew
+struct LineCols {
+    uint32_t *soff, *lend, *pos, *refalt, *flags, *keep, *kidx, *cnew, *crun;
+};
+// what k_compact_kept writes: one word per kept line, the list of lines for the general encoder, the CHROM runs
+struct KeptCols {
+    uint32_t *soff, *lend, *meta, *redo_list, *redo_flag;
+    uint64_t *run_first;   // [MAX_CHROM_RUNS]
+    uint8_t *run_names;    // [MAX_CHROM_RUNS][32]
+};
+
+// encode workspaces of a context.  They grow inside the calls, or ahead of them in hhgt_reserve: both through ensure_index
+// and ensure_lines, so a size is written once
+struct EncodeWs {
+    DevBuf slots, counts, prefix, nl, scan_tmp;
+    enum { L_SOFF, L_LEND, L_POS, L_REFALT, L_FLAGS, L_KEEP, L_KIDX, L_CNEW, L_CRUN, K_SOFF, K_LEND, K_META, REDO_LIST, REDO_FLAG, N_LINE };
+    DevBuf line[N_LINE];   // a word per line each
+    DevBuf run_first, run_names;
+    DevBuf result;         // hhgt_encode_result staging of the asynchronous form
+    int ensure_index(uint32_t n_regions);   // what the newline index of n_regions regions and its scan write
+    int ensure_lines(uint32_t max_lines);   // what the stages behind the index write for at most max_lines lines
+    int ensure_scan(uint64_t n);            // scan_tmp for a pair of scans over n elements
+    int ensure_runs();                      // run_first, run_names, result: one size each (a call without text still finishes)
+    template <typename F> void each(F f)
+    {
+        for (DevBuf *b : {&slots, &counts, &prefix, &nl, &scan_tmp, &run_first, &run_names, &result}) f(*b);
+        for (DevBuf &b : line) f(b);
+    }
+    // the launchers' view: every member by name beside its buffer
+    uint32_t *col(int i) const { return line[i].as<uint32_t>(); }
+    LineCols line_cols() const
+    {
+        LineCols l;
+        l.soff = col(L_SOFF), l.lend = col(L_LEND), l.pos = col(L_POS), l.refalt = col(L_REFALT), l.flags = col(L_FLAGS);
+        l.keep = col(L_KEEP), l.kidx = col(L_KIDX), l.cnew = col(L_CNEW), l.crun = col(L_CRUN);
+        return l;
+    }
+    KeptCols kept_cols() const
+    {
+        KeptCols k;
+        k.soff = col(K_SOFF), k.lend = col(K_LEND), k.meta = col(K_META), k.redo_list = col(REDO_LIST), k.redo_flag = col(REDO_FLAG);
+        k.run_first = run_first.as<uint64_t>(), k.run_names = run_names.as<uint8_t>();
+        return k;
+    }
+};
+
 struct hhgt_ctx {
     int device = 0;
     hipDeviceProp_t prop;
-    // index / fixed / keep workspaces
-    DevBuf slots, counts, prefix, nl, scan_tmp;
-    DevBuf l_soff, l_lend, l_pos, l_refalt, l_flags, l_keep, l_kidx, l_cnew, l_crun;
-    DevBuf k_soff, k_lend, k_meta, redo_list, redo_flag, run_first, run_names;
+    EncodeWs enc;
     DevBuf counters;       // DevCounters
     DevBuf cursor;         // uint64: v_base of the synchronous hhgt_encode_text (the asynchronous form gets the caller's)
-    DevBuf result;         // hhgt_encode_result staging of the asynchronous form
     // compress workspaces
     // two sets: with a frame stream (hhgt_set_frame_stream) the framing of call k reads set k & 1 while the LZ4 kernels of
     // call k + 1 write the other
@@ -166,6 +209,9 @@ struct hhgt_ctx {
         uint32_t lz_tag = 0;       // tag of the last launch_lz4_blocks on lz_flags
         hipEvent_t lz_done = nullptr, fr_done = nullptr;
         bool fr_pending = false;   // fr_done was recorded behind a framing that read this set
+        // all but lz_flags (one word, made and zeroed by the first launch on the set) for n_chunks chunks of nblocks blocks
+        // of nwaves streams, `slot` scratch bytes per stream
+        int ensure(uint64_t n_chunks, uint32_t nblocks, uint32_t nwaves, size_t slot);
     } cw[2];
     uint64_t cmp_seq = 0;
     hipStream_t frame_stream = nullptr;   // hhgt_set_frame_stream; nullptr: the framing follows the LZ4 kernels on their stream
@@ -221,16 +267,12 @@ int index_mode_default();
 int launch_compact_newlines(const uint32_t *d_slots, const uint32_t *d_counts, const uint32_t *d_prefix,
                             uint32_t n_regions, uint32_t *d_nl, uint32_t max_lines, hipStream_t st);
 int launch_parse_fixed(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl, const uint32_t *d_nlines,
-                       uint32_t max_lines, const RegionFilter &region, uint32_t S, uint32_t *l_soff, uint32_t *l_lend,
-                       uint32_t *l_pos, uint32_t *l_refalt, uint32_t *l_flags, uint32_t *l_keep,
-                       uint32_t *l_cnew, int mode, DevCounters *d_cnt, hipStream_t st);
+                       uint32_t max_lines, const RegionFilter &region, uint32_t S, const LineCols &l, int mode,
+                       DevCounters *d_cnt, hipStream_t st);
 int launch_compact_kept(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl, const uint32_t *d_nlines, uint32_t max_lines,
-                        const uint32_t *l_soff, const uint32_t *l_lend,
-                        const uint32_t *l_pos, const uint32_t *l_refalt, const uint32_t *l_flags,
-                        const uint32_t *l_kidx, const uint32_t *l_crun, uint32_t *k_soff, uint32_t *k_lend,
-                        uint32_t *k_meta, uint32_t *redo_list, uint32_t *redo_flag, uint64_t *run_first, uint8_t *run_names,
-                        uint32_t max_runs, const uint64_t *d_cursor, uint64_t v_capacity, uint32_t ring, uint32_t *d_start,
-                        uint32_t *d_stop, uint8_t *d_ref, uint8_t *d_alt, DevCounters *d_cnt, bool strided, hipStream_t st);
+                        const LineCols &l, const KeptCols &k, uint32_t max_runs, const uint64_t *d_cursor, uint64_t v_capacity,
+                        uint32_t ring, uint32_t *d_start, uint32_t *d_stop, uint8_t *d_ref, uint8_t *d_alt, DevCounters *d_cnt,
+                        bool strided, hipStream_t st);
 
 // encode.hip
 int launch_encode_tiles(const uint8_t *d_text, uint64_t n, const uint32_t *k_soff, const uint32_t *k_meta,

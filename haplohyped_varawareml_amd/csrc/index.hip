@@ -912,9 +912,8 @@ int launch_compact_newlines(const uint32_t *d_slots, const uint32_t *d_counts, c
 }
 
 int launch_parse_fixed(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl, const uint32_t *d_nlines,
-                       uint32_t max_lines, const RegionFilter &region, uint32_t S, uint32_t *l_soff, uint32_t *l_lend,
-                       uint32_t *l_pos, uint32_t *l_refalt, uint32_t *l_flags, uint32_t *l_keep,
-                       uint32_t *l_cnew, int mode, DevCounters *d_cnt, hipStream_t st)
+                       uint32_t max_lines, const RegionFilter &region, uint32_t S, const LineCols &l, int mode,
+                       DevCounters *d_cnt, hipStream_t st)
 {
     if (max_lines == 0) return HHGT_OK;
     if (mode < 0) mode = index_mode_default();
@@ -923,23 +922,20 @@ int launch_parse_fixed(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl, 
     uint32_t hop_skip = index_hop_skip(S ? 2u * S + 17u : 0u, mode);
     if (hop_skip && mode >= 2) hop_skip = 0xFFFFFFFFu;
     hipLaunchKernelGGL(k_parse_fixed, dim3((max_lines + 255) / 256), dim3(256), 0, st, d_text, n, d_nl, d_nlines,
-                       max_lines, region, S, l_soff, l_lend, l_pos, l_refalt, l_flags, l_keep, l_cnew, d_cnt, hop_skip);
+                       max_lines, region, S, l.soff, l.lend, l.pos, l.refalt, l.flags, l.keep, l.cnew, d_cnt, hop_skip);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }
 
 int launch_compact_kept(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl, const uint32_t *d_nlines, uint32_t max_lines,
-                        const uint32_t *l_soff, const uint32_t *l_lend,
-                        const uint32_t *l_pos, const uint32_t *l_refalt, const uint32_t *l_flags,
-                        const uint32_t *l_kidx, const uint32_t *l_crun, uint32_t *k_soff, uint32_t *k_lend,
-                        uint32_t *k_meta, uint32_t *redo_list, uint32_t *redo_flag, uint64_t *run_first, uint8_t *run_names,
-                        uint32_t max_runs, const uint64_t *d_cursor, uint64_t v_capacity, uint32_t ring, uint32_t *d_start,
-                        uint32_t *d_stop, uint8_t *d_ref, uint8_t *d_alt, DevCounters *d_cnt, bool strided, hipStream_t st)
+                        const LineCols &l, const KeptCols &k, uint32_t max_runs, const uint64_t *d_cursor, uint64_t v_capacity,
+                        uint32_t ring, uint32_t *d_start, uint32_t *d_stop, uint8_t *d_ref, uint8_t *d_alt, DevCounters *d_cnt,
+                        bool strided, hipStream_t st)
 {
     if (max_lines == 0) return HHGT_OK;
     hipLaunchKernelGGL(k_compact_kept, dim3((max_lines + 255) / 256), dim3(256), 0, st, d_text, n, d_nl, d_nlines, max_lines,
-                       l_soff, l_lend, l_pos, l_refalt, l_flags, l_kidx, l_crun, k_soff, k_lend, k_meta, redo_list, redo_flag,
-                       run_first, run_names, max_runs, d_cursor, v_capacity, ring, d_start, d_stop, d_ref, d_alt, d_cnt, strided ? 1u : 0u);
+                       l.soff, l.lend, l.pos, l.refalt, l.flags, l.kidx, l.crun, k.soff, k.lend, k.meta, k.redo_list, k.redo_flag,
+                       k.run_first, k.run_names, max_runs, d_cursor, v_capacity, ring, d_start, d_stop, d_ref, d_alt, d_cnt, strided ? 1u : 0u);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

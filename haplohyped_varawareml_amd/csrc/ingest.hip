@@ -1276,8 +1276,8 @@ void driver_main(hhgt_ingest *g)
                                              (uint32_t)(max_lines > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : max_lines), X->G.p,
                                              X->t_start.as<uint32_t>(), nullptr, X->t_ref.as<uint8_t>(), X->t_alt.as<uint8_t>(), r.rec,
                                              g->s_main));
-            G_HIP(hipMemcpyAsync(r.run_first.p, g->ctx->run_first.p, MAX_CHROM_RUNS * 8, hipMemcpyDeviceToDevice, g->s_main));
-            G_HIP(hipMemcpyAsync(r.run_names.p, g->ctx->run_names.p, MAX_CHROM_RUNS * 32, hipMemcpyDeviceToDevice, g->s_main));
+            G_HIP(hipMemcpyAsync(r.run_first.p, g->ctx->enc.run_first.p, MAX_CHROM_RUNS * 8, hipMemcpyDeviceToDevice, g->s_main));
+            G_HIP(hipMemcpyAsync(r.run_names.p, g->ctx->enc.run_names.p, MAX_CHROM_RUNS * 32, hipMemcpyDeviceToDevice, g->s_main));
             G_HIP(hipEventRecord(r.ev, g->s_main));
             r.text_idx = ti;
             pending.push_back(next_res);

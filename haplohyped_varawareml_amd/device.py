@@ -1,5 +1,6 @@
 """Thin Python layer over the C ABI (include/hhgt.h): torch tensors provide device memory and the
 stream; every computation happens inside libhhgt.so's HIP kernels."""
+import collections
 import ctypes as C
 from dataclasses import dataclass, field
 
@@ -19,28 +20,11 @@ DEFAULT_TYPESIZE = 2
 DEFAULT_BLOCKSIZE = 8192
 
 
-# hhgt_block_sel as a numpy record (the layout of _lib.BlockSel)
-SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("dst_off", np.uint64), ("block", np.uint32),
-                      ("lo", np.uint32), ("hi", np.uint32), ("reserved", np.uint32)])
-assert SEL_DTYPE.itemsize == C.sizeof(_lib.BlockSel) == 40
-
-# hhgt_count_sel as a numpy record (the layout of _lib.CountSel)
-COUNT_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("row_mask", np.uint64),
-                            ("out_row", np.uint64), ("part", np.uint32), ("lo", np.uint32), ("hi", np.uint32),
-                            ("reserved", np.uint32)])
-assert COUNT_SEL_DTYPE.itemsize == C.sizeof(_lib.CountSel) == 48
-
-# hhgt_sample_sel as a numpy record (the layout of _lib.SampleSel)
-SAMPLE_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("row_mask", np.uint64),
-                             ("out_row", np.uint64), ("mask_word", np.uint64), ("part", np.uint32), ("lo", np.uint32),
-                             ("hi", np.uint32), ("reserved", np.uint32)])
-assert SAMPLE_SEL_DTYPE.itemsize == C.sizeof(_lib.SampleSel) == 56
-
-# hhgt_plane_sel as a numpy record (the layout of _lib.PlaneSel)
-PLANE_SEL_DTYPE = np.dtype([("src_ptr", np.uint64), ("src_bytes", np.uint64), ("row_mask", np.uint64),
-                            ("out_row", np.uint64), ("mask_word", np.uint64), ("out_word", np.uint64),
-                            ("part", np.uint32), ("lo", np.uint32), ("hi", np.uint32), ("reserved", np.uint32)])
-assert PLANE_SEL_DTYPE.itemsize == C.sizeof(_lib.PlaneSel) == 64
+# the selection records of include/hhgt.h as numpy records: derived from the ctypes structures, so there is one description
+SEL_DTYPE = np.dtype(_lib.BlockSel)            # hhgt_block_sel
+COUNT_SEL_DTYPE = np.dtype(_lib.CountSel)      # hhgt_count_sel
+SAMPLE_SEL_DTYPE = np.dtype(_lib.SampleSel)    # hhgt_sample_sel
+PLANE_SEL_DTYPE = np.dtype(_lib.PlaneSel)      # hhgt_plane_sel
 
 
 def make_ring_layout(n_samples, ring_cols, sc=DEFAULT_SC, vc=DEFAULT_VC):
@@ -87,6 +71,34 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _ptr_if_any(t):
+    """the kernels take NULL for a tensor without elements"""
+    return _ptr(t) if t.numel() else None
+
+
+_Geometry = collections.namedtuple("_Geometry", "Vc Sc n_vc n_sc")
+
+
+def _geometry(lay):
+    """-> (Vc, Sc, n_vc, n_sc): variants and samples per chunk, chunk columns, chunks per column (dense: one chunk)"""
+    Vc, Sc = lay.vc or lay.v_capacity, lay.sc or max(lay.n_samples, 1)
+    return _Geometry(Vc, Sc, lay.v_capacity // Vc if Vc else 0, -(-lay.n_samples // Sc) if lay.sc else 1)
+
+
+def _default_blocksize(nbytes, typesize=1):
+    """the chunk (or row), at most 8 KiB, in whole elements"""
+    blocksize = min(int(nbytes), DEFAULT_BLOCKSIZE)
+    return blocksize - blocksize % typesize
+
+
+def _planes_arg(planes, what="planes: a contiguous int32 tensor [3, n_rows, row_words]"):
+    """bit planes as the kernels take them -> (rows, words per row)"""
+    if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
+            or not planes.is_contiguous()):
+        raise ValueError(what)
+    return int(planes.shape[1]), int(planes.shape[2])
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -110,9 +122,7 @@ class EncodeResult:
         S, n = lay.n_samples, self.n_kept
         if lay.sc == 0 and lay.vc == 0:
             return self.G.view(torch.int8).view(max(S, 1), lay.v_capacity, 2)[:S, :n]
-        Sc, Vc = lay.sc or max(S, 1), lay.vc or lay.v_capacity
-        n_sc = -(-S // Sc) if lay.sc else 1
-        n_vc = lay.v_capacity // Vc
+        Vc, Sc, n_vc, n_sc = _geometry(lay)
         g = self.G.view(torch.int8).view(n_vc, n_sc, Sc, Vc, 2).permute(1, 2, 0, 3, 4)
         return g.reshape(n_sc * Sc, n_vc * Vc, 2)[:S, :n]
 
@@ -203,21 +213,24 @@ class Context:
             out.chrom_runs = self.chrom_runs()
         return out
 
-    def encode_text_async(self, text, n_samples, out, cursor, max_lines=None, region="", pending=None):
-        """hhgt_encode_text_async: appends at the device-resident `cursor` (int64 tensor [1]) into `out`'s buffers and
-        returns without waiting.  -> PendingEncode (call .wait() once the counts are needed)"""
-        assert text.is_cuda and text.dtype == torch.uint8 and text.is_contiguous()
+    def _encode_async(self, planes, text, n_samples, out, cursor, max_lines, region, pending):
+        assert text.is_cuda and text.dtype == torch.uint8 and text.is_contiguous() and (out.P is not None or not planes)
         nbytes = text.numel()
         if max_lines is None:
             max_lines = nbytes // (16 + 2 * max(n_samples, 0)) + 64
         pending = pending or PendingEncode()
+        fn, mats = (self.lib.hhgt_encode_text_planes_async, (_ptr(out.P), _ptr(out.G))) if planes else \
+            (self.lib.hhgt_encode_text_async, (_ptr(out.G),))
         with torch.cuda.device(self.device):
-            check(self.lib.hhgt_encode_text_async(self.h, _ptr(text), nbytes, (region or "").encode(),
-                                                  C.byref(out.layout), _ptr(cursor), int(max_lines), _ptr(out.G),
-                                                  _ptr(out.start), _ptr(out.stop), _ptr(out.ref), _ptr(out.alt),
-                                                  C.c_void_p(pending.buf.data_ptr()), _stream()))
+            check(fn(self.h, _ptr(text), nbytes, (region or "").encode(), C.byref(out.layout), _ptr(cursor), int(max_lines), *mats,
+                     _ptr(out.start), _ptr(out.stop), _ptr(out.ref), _ptr(out.alt), C.c_void_p(pending.buf.data_ptr()), _stream()))
             pending.event.record(torch.cuda.current_stream())
         return pending
+
+    def encode_text_async(self, text, n_samples, out, cursor, max_lines=None, region="", pending=None):
+        """hhgt_encode_text_async: appends at the device-resident `cursor` (int64 tensor [1]) into `out`'s buffers and
+        returns without waiting.  -> PendingEncode (call .wait() once the counts are needed)"""
+        return self._encode_async(False, text, n_samples, out, cursor, max_lines, region, pending)
 
     def pad_tail_cursor(self, res, cursor):
         with torch.cuda.device(self.device):
@@ -228,18 +241,7 @@ class Context:
         """hhgt_encode_text_planes_async: like encode_text_async, but the calls land in out.P as two bits per allele;
         out.G (may be None) only receives the bytes of calls beyond 0 / 1 / missing.  -> PendingEncode
         (.rec.reserved = number of such calls)"""
-        assert text.is_cuda and text.dtype == torch.uint8 and text.is_contiguous() and out.P is not None
-        nbytes = text.numel()
-        if max_lines is None:
-            max_lines = nbytes // (16 + 2 * max(n_samples, 0)) + 64
-        pending = pending or PendingEncode()
-        with torch.cuda.device(self.device):
-            check(self.lib.hhgt_encode_text_planes_async(self.h, _ptr(text), nbytes, (region or "").encode(),
-                                                         C.byref(out.layout), _ptr(cursor), int(max_lines), _ptr(out.P), _ptr(out.G),
-                                                         _ptr(out.start), _ptr(out.stop), _ptr(out.ref), _ptr(out.alt),
-                                                         C.c_void_p(pending.buf.data_ptr()), _stream()))
-            pending.event.record(torch.cuda.current_stream())
-        return pending
+        return self._encode_async(True, text, n_samples, out, cursor, max_lines, region, pending)
 
     def pad_tail_planes_cursor(self, res, cursor):
         with torch.cuda.device(self.device):
@@ -247,9 +249,8 @@ class Context:
 
     def pad_tail_planes(self, res, v_end, vcol_begin=0, vcol_end=None):
         lay = res.layout
-        Vc = lay.vc or lay.v_capacity
         if vcol_end is None:
-            vcol_end = -(-max(v_end, 1) // Vc)
+            vcol_end = -(-max(v_end, 1) // _geometry(lay).Vc)
         with torch.cuda.device(self.device):
             check(self.lib.hhgt_pad_tail_planes(self.h, C.byref(lay), int(v_end), int(vcol_begin), int(vcol_end), _ptr(res.P), _stream()))
 
@@ -258,10 +259,10 @@ class Context:
         the int8 matrix whose bytes back the calls beyond 0 / 1 / missing), typesize 2, 8 KiB blocks.
         -> (dst, chunk_off, total_bytes or None) like compress()"""
         lay = res.layout
-        Vc, Sc = lay.vc or lay.v_capacity, lay.sc or max(lay.n_samples, 1)
+        Vc, Sc, n_vc, n_sc = _geometry(lay)
         if n_cols is None:
-            n_cols = lay.v_capacity // Vc - col0
-        n_chunks = n_cols * (-(-lay.n_samples // Sc) if lay.sc else 1)
+            n_cols = n_vc - col0
+        n_chunks = n_cols * n_sc
         chunk_nbytes = Sc * Vc * 2
         with torch.cuda.device(self.device):
             cap = int(self.lib.hhgt_compress_bound(n_chunks, chunk_nbytes, 2, 8192))
@@ -278,9 +279,8 @@ class Context:
         """hhgt_planes_expand: planes (+ res.G's bytes for the calls beyond 0 / 1 / missing) of column slots [col0, col0 + n_cols)
         -> the int8 matrix bytes at their place in `out` (a buffer of the int8 layout; default: a new zeroed one)"""
         lay = res.layout
-        Vc = lay.vc or lay.v_capacity
         if n_cols is None:
-            n_cols = lay.v_capacity // Vc - col0
+            n_cols = _geometry(lay).n_vc - col0
         with torch.cuda.device(self.device):
             if out is None:
                 out = torch.zeros(layout_bytes(lay), dtype=torch.uint8, device=self.device)
@@ -299,10 +299,9 @@ class Context:
 
     def pad_tail(self, res, v_end=None, vcol_begin=0, vcol_end=None):
         lay = res.layout
-        Vc = lay.vc or lay.v_capacity
         v_end = res.n_kept if v_end is None else v_end
         if vcol_end is None:
-            vcol_end = -(-max(v_end, 1) // Vc)
+            vcol_end = -(-max(v_end, 1) // _geometry(lay).Vc)
         with torch.cuda.device(self.device):
             check(self.lib.hhgt_pad_tail(self.h, C.byref(lay), int(v_end), int(vcol_begin), int(vcol_end),
                                          _ptr(res.G), _stream()))
@@ -349,8 +348,7 @@ class Context:
         assert src.numel() % chunk_nbytes == 0
         n_chunks = src.numel() // chunk_nbytes
         if blocksize is None:
-            blocksize = min(chunk_nbytes, DEFAULT_BLOCKSIZE)
-            blocksize -= blocksize % typesize
+            blocksize = _default_blocksize(chunk_nbytes, typesize)
         with torch.cuda.device(self.device):
             cap = int(self.lib.hhgt_compress_bound(n_chunks, chunk_nbytes, typesize, blocksize))
             if cap == 0:
@@ -369,8 +367,7 @@ class Context:
                    dst=None):
         """-> (dst uint8 tensor [n_chunks*chunk_nbytes], n_bad)"""
         if blocksize is None:
-            blocksize = min(int(chunk_nbytes), DEFAULT_BLOCKSIZE)
-            blocksize -= blocksize % typesize
+            blocksize = _default_blocksize(chunk_nbytes, typesize)
         with torch.cuda.device(self.device):
             if dst is None:
                 dst = torch.empty(int(n_chunks) * int(chunk_nbytes), dtype=torch.uint8, device=self.device)
@@ -385,8 +382,7 @@ class Context:
         block, decoded byte range [lo, hi), dst_off), uploaded in one copy.  dst: uint8 tensor (default: just large
         enough for the selections).  -> (dst, n_bad)"""
         if blocksize is None:
-            blocksize = min(int(chunk_nbytes), DEFAULT_BLOCKSIZE)
-            blocksize -= blocksize % typesize
+            blocksize = _default_blocksize(chunk_nbytes, typesize)
         sel = np.ascontiguousarray(sel, dtype=SEL_DTYPE)
         n = len(sel)
         with torch.cuda.device(self.device):
@@ -428,8 +424,18 @@ class Context:
     def _row_sel(sel, sel_dtype, vc, blocksize):
         """-> (the selections as a contiguous array of sel_dtype, the block size: by default the row's, at most 8 KiB)"""
         if blocksize is None:
-            blocksize = min(int(vc) * 2, DEFAULT_BLOCKSIZE)
+            blocksize = _default_blocksize(int(vc) * 2)
         return np.ascontiguousarray(sel, dtype=sel_dtype), blocksize
+
+    def _out_arg(self, tensor, dtype, shape, name, loose=()):
+        """an output tensor: the caller's, checked (contiguous; dtype, where uint32 stands for int32; shape, but for the axes in
+        `loose`), or zeros"""
+        if tensor is None:
+            return torch.zeros(shape, dtype=dtype, device=self.device)
+        same = tensor.dim() == len(shape) and all(a == b for i, (a, b) in enumerate(zip(tensor.shape, shape)) if i not in loose)
+        if tensor.dtype not in ((dtype, torch.uint32) if dtype == torch.int32 else (dtype,)) or not same or not tensor.is_contiguous():
+            raise ValueError(f"{name}: a contiguous {str(dtype).split('.')[1]} tensor {list(shape)}")
+        return tensor
 
     def _counts_arg(self, counts, n_out):
         """the counts tensor of count_alleles / count_samples: the caller's, or zeros [n_out(), 4]"""
@@ -482,31 +488,20 @@ class Context:
                 if row_words is None:
                     row_words = int(sel["out_word"].max()) + -(-(int(blocksize) // 2) // 32) if n else 0
                 planes = torch.zeros((3, int(n_rows), int(row_words)), dtype=torch.int32, device=self.device)
-            if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
-                    or not planes.is_contiguous()):
-                raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
+            n_rows, row_words = _planes_arg(planes)
             vmask, words = self._vmask_arg(vmask)
             return self._row_kernel(self.lib.hhgt_genotype_planes, sel, sc, vc, typesize, blocksize, planes,
-                                    _ptr(vmask), words, _ptr(planes) if planes.numel() else None, planes.shape[1],
-                                    planes.shape[2])
+                                    _ptr(vmask), words, _ptr_if_any(planes), n_rows, row_words)
 
     def pair_counts(self, planes, w_lo=0, w_hi=None, table=None):
         """pairwise counts (hhgt_pair_counts) over the words [w_lo, w_hi) (default: all) of genotype planes [3, n, words]:
         ADDED to `table`, an int32 tensor [n, n, 4] (NSNP, HETHET, IBS0, HET1 per ordered pair of rows; default: zeros),
         on the current stream — calls on one stream may accumulate into one table.  -> table"""
-        if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
-                or not planes.is_contiguous()):
-            raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
-        n, words = int(planes.shape[1]), int(planes.shape[2])
+        n, words = _planes_arg(planes)
         w_hi = words if w_hi is None else int(w_hi)
         with torch.cuda.device(self.device):
-            if table is None:
-                table = torch.zeros((n, n, 4), dtype=torch.int32, device=self.device)
-            if (table.dtype not in (torch.int32, torch.uint32) or tuple(table.shape) != (n, n, 4)
-                    or not table.is_contiguous()):
-                raise ValueError(f"table: a contiguous int32 tensor [{n}, {n}, 4]")
-            check(self.lib.hhgt_pair_counts(self.h, _ptr(planes) if planes.numel() else None, n, words, int(w_lo), w_hi,
-                                            _ptr(table) if table.numel() else None, _stream()))
+            table = self._out_arg(table, torch.int32, (n, n, 4), "table")
+            check(self.lib.hhgt_pair_counts(self.h, _ptr_if_any(planes), n, words, int(w_lo), w_hi, _ptr_if_any(table), _stream()))
         return table
 
     def grm(self, planes, z, w_lo=0, w_hi=None, table=None):
@@ -514,20 +509,14 @@ class Context:
         planes [3, n, words]: z is a float32 tensor [3, 32 * words], the value of a HOM_REF, HET, HOM_ALT call at every bit
         position; the sums are ADDED to `table`, a float64 tensor [n, n] (default: zeros), on the current stream — calls
         on one stream may accumulate into one table.  -> table"""
-        if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
-                or not planes.is_contiguous()):
-            raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
-        n, words = int(planes.shape[1]), int(planes.shape[2])
+        n, words = _planes_arg(planes)
         w_hi = words if w_hi is None else int(w_hi)
         if z.dtype != torch.float32 or tuple(z.shape) != (3, 32 * words) or not z.is_contiguous() or z.device != planes.device:
             raise ValueError(f"z: a contiguous float32 tensor [3, {32 * words}] on the planes' device")
         with torch.cuda.device(self.device):
-            if table is None:
-                table = torch.zeros((n, n), dtype=torch.float64, device=self.device)
-            if table.dtype != torch.float64 or tuple(table.shape) != (n, n) or not table.is_contiguous():
-                raise ValueError(f"table: a contiguous float64 tensor [{n}, {n}]")
-            check(self.lib.hhgt_grm(self.h, _ptr(planes) if planes.numel() else None, n, words, int(w_lo), w_hi,
-                                    _ptr(z) if z.numel() else None, _ptr(table) if table.numel() else None, _stream()))
+            table = self._out_arg(table, torch.float64, (n, n), "table")
+            check(self.lib.hhgt_grm(self.h, _ptr_if_any(planes), n, words, int(w_lo), w_hi, _ptr_if_any(z), _ptr_if_any(table),
+                                    _stream()))
         return table
 
     def variant_planes(self, planes, w_lo=0, w_hi=None, vplanes=None):
@@ -535,30 +524,21 @@ class Context:
         [3, n_rows, words]: an int32 tensor [3, 32 * (w_hi - w_lo), ceil(n_rows / 32)] — HET, COMPLETE, HOM_ALT; row p is
         bit position 32 * w_lo + p of the plane rows, bit r % 32 of word r // 32 is plane row r —, every word of it
         written (default: a new tensor).  -> vplanes"""
-        if (planes.dtype not in (torch.int32, torch.uint32) or planes.dim() != 3 or planes.shape[0] != 3
-                or not planes.is_contiguous()):
-            raise ValueError("planes: a contiguous int32 tensor [3, n_rows, row_words]")
-        n, words = int(planes.shape[1]), int(planes.shape[2])
+        n, words = _planes_arg(planes)
         w_lo, w_hi = int(w_lo), words if w_hi is None else int(w_hi)
-        shape = (3, 32 * max(w_hi - w_lo, 0), -(-n // 32))
         with torch.cuda.device(self.device):
-            if vplanes is None:
+            shape = (3, 32 * max(w_hi - w_lo, 0), -(-n // 32))
+            if vplanes is None:     # (every word is written: no need for zeros)
                 vplanes = torch.empty(shape, dtype=torch.int32, device=self.device)
-            if (vplanes.dtype not in (torch.int32, torch.uint32) or tuple(vplanes.shape) != shape
-                    or not vplanes.is_contiguous()):
-                raise ValueError(f"vplanes: a contiguous int32 tensor {list(shape)}")
-            check(self.lib.hhgt_variant_planes(self.h, _ptr(planes) if planes.numel() else None, n, words, w_lo, w_hi,
-                                               _ptr(vplanes) if vplanes.numel() else None, _stream()))
+            vplanes = self._out_arg(vplanes, torch.int32, shape, "vplanes")
+            check(self.lib.hhgt_variant_planes(self.h, _ptr_if_any(planes), n, words, w_lo, w_hi, _ptr_if_any(vplanes), _stream()))
         return vplanes
 
     def ld_counts(self, vplanes, window, table=None):
         """LD counts (hhgt_ld_counts) of the pairs of rows at most `window` apart of variant-major planes [3, n, sw]: ADDED
         to `table`, an int32 tensor [n, window, 8] (store.LD_N ... LD_AA of the pair (row k, row k + 1 + d) at [k, d];
         default: zeros), on the current stream — calls on one stream may accumulate into one table.  -> table"""
-        if (vplanes.dtype not in (torch.int32, torch.uint32) or vplanes.dim() != 3 or vplanes.shape[0] != 3
-                or not vplanes.is_contiguous()):
-            raise ValueError("vplanes: a contiguous int32 tensor [3, n_var, sw]")
-        n, sw, window = int(vplanes.shape[1]), int(vplanes.shape[2]), int(window)
+        (n, sw), window = _planes_arg(vplanes, "vplanes: a contiguous int32 tensor [3, n_var, sw]"), int(window)
         if not 0 <= window < 1 << 32:
             raise ValueError(f"window {window}")
         with torch.cuda.device(self.device):
@@ -566,12 +546,8 @@ class Context:
             # call): the default table is then sized for the nearest valid window and the shape check below stands aside
             if table is None:
                 table = torch.zeros((n, max(min(window, 1024), 1), 8), dtype=torch.int32, device=self.device)
-            if (table.dtype not in (torch.int32, torch.uint32) or table.dim() != 3 or table.shape[0] != n
-                    or table.shape[2] != 8 or (1 <= window <= 1024 and table.shape[1] != window)
-                    or not table.is_contiguous()):
-                raise ValueError(f"table: a contiguous int32 tensor [{n}, {window}, 8]")
-            check(self.lib.hhgt_ld_counts(self.h, _ptr(vplanes) if vplanes.numel() else None, n, sw, window,
-                                          _ptr(table) if table.numel() else None, _stream()))
+            table = self._out_arg(table, torch.int32, (n, window, 8), "table", loose=() if 1 <= window <= 1024 else (1,))
+            check(self.lib.hhgt_ld_counts(self.h, _ptr_if_any(vplanes), n, sw, window, _ptr_if_any(table), _stream()))
         return table
 
     def ld_prune(self, table, r2, keep=None):
@@ -585,12 +561,8 @@ class Context:
         window = int(table.shape[1])
         n = int(table.shape[0]) - window
         with torch.cuda.device(self.device):
-            if keep is None:
-                keep = torch.zeros(window + n, dtype=torch.uint8, device=self.device)
-            if keep.dtype != torch.uint8 or tuple(keep.shape) != (window + n,) or not keep.is_contiguous():
-                raise ValueError(f"keep: a contiguous uint8 tensor [{window + n}]")
-            check(self.lib.hhgt_ld_prune(self.h, _ptr(table) if table.numel() else None, n, window, float(r2),
-                                         _ptr(keep) if keep.numel() else None, _stream()))
+            keep = self._out_arg(keep, torch.uint8, (window + n,), "keep")
+            check(self.lib.hhgt_ld_prune(self.h, _ptr_if_any(table), n, window, float(r2), _ptr_if_any(keep), _stream()))
         return keep
 
     # ---- BGZF on the device -------------------------------------------------------
@@ -634,66 +606,48 @@ class Context:
         return int(bad.value) if count_bad else None
 
     # ---- synthetic workloads (bench / test tooling) -----------------------------------------------
+    def _synth_text(self, contig, line_lengths, n_samples, with_header, names):
+        """what the two renderers begin with: the header, the line offsets behind it, the text buffer with the header in it
+        -> (text, off, nbytes)"""
+        from . import synth
+        head = synth.header_text(contig, names or synth.sample_names(n_samples)) if with_header else b""
+        off = np.zeros(len(line_lengths) + 1, dtype=np.uint64)
+        off[0] = len(head)
+        off[1:] = len(head) + np.cumsum(line_lengths).astype(np.uint64)
+        nbytes = int(off[-1])
+        text = torch.empty(nbytes + 16, dtype=torch.uint8, device=self.device)
+        if head:
+            text[:len(head)] = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(self.device)
+        return text, off, nbytes
+
+    def _up(self, a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(self.device)
+
     def synth_fixed(self, contig, table, n_samples, seed, v_first=0, with_header=True, names=None):
         """Render a fixed-width synthetic shard directly in HBM.  -> (text uint8 tensor, nbytes)"""
         from . import synth
-        lib = self.lib
-        if not hasattr(lib, "_synth_bound"):
-            lib.hhgt_synth_render_fixed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
-                                                    C.c_char_p, C.c_int, C.c_uint64, C.c_void_p]
-            lib._synth_bound = True
-        S = int(n_samples)
-        pos = table["pos"]
-        V = len(pos)
-        head = synth.header_text(contig, names or synth.sample_names(S)) if with_header else b""
-        ll = synth.fixed_line_lengths(contig, pos, S)
-        off = np.zeros(V + 1, dtype=np.uint64)
-        off[0] = len(head)
-        off[1:] = len(head) + np.cumsum(ll).astype(np.uint64)
-        nbytes = int(off[-1])
+        S, pos = int(n_samples), table["pos"]
         with torch.cuda.device(self.device):
-            text = torch.empty(nbytes + 16, dtype=torch.uint8, device=self.device)
-            if head:
-                text[:len(head)] = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(self.device)
-            d_off = torch.from_numpy(off.view(np.int64)).to(self.device)
-            d_pos = torch.from_numpy(pos.view(np.int32)).to(self.device)
-            d_ref = torch.from_numpy(table["ref"]).to(self.device)
-            d_alt = torch.from_numpy(table["alt"]).to(self.device)
-            d_thr = torch.from_numpy(table["thr"].view(np.int32)).to(self.device)
-            check(lib.hhgt_synth_render_fixed(self.h, _ptr(text), nbytes, _ptr(d_off), _ptr(d_pos), _ptr(d_ref),
-                                              _ptr(d_alt), _ptr(d_thr), V, int(v_first), contig.encode(), S,
-                                              int(seed), _stream()))
+            text, off, nbytes = self._synth_text(contig, synth.fixed_line_lengths(contig, pos, S), S, with_header, names)
+            d_off, d_pos, d_thr = self._up(off, np.int64), self._up(pos, np.int32), self._up(table["thr"], np.int32)
+            d_ref, d_alt = torch.from_numpy(table["ref"]).to(self.device), torch.from_numpy(table["alt"]).to(self.device)
+            check(self.lib.hhgt_synth_render_fixed(self.h, _ptr(text), nbytes, _ptr(d_off), _ptr(d_pos), _ptr(d_ref), _ptr(d_alt),
+                                                   _ptr(d_thr), len(pos), int(v_first), contig.encode(), S, int(seed), _stream()))
             torch.cuda.current_stream().synchronize()
         return text[:nbytes], nbytes
 
     def synth_mixed(self, contig, table, n_samples, seed, v_first=0, with_header=True, names=None):
         """config-4 style shard (synth.mixed_table) rendered in HBM -> (text uint8 tensor, nbytes, line_off)"""
         from . import synth
-        lib = self.lib
-        if not hasattr(lib, "_synth_mixed_bound"):
-            lib.hhgt_synth_render_mixed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + [C.c_void_p] * 6 + [
-                C.c_uint64, C.c_uint64, C.c_char_p, C.c_int, C.c_uint64, C.c_void_p]
-            lib._synth_mixed_bound = True
         S = int(n_samples)
-        V = len(table["pos"])
-        head = synth.header_text(contig, names or synth.sample_names(S)) if with_header else b""
-        ll = synth.mixed_line_lengths(contig, table, S)
-        off = np.zeros(V + 1, dtype=np.uint64)
-        off[0] = len(head)
-        off[1:] = len(head) + np.cumsum(ll).astype(np.uint64)
-        nbytes = int(off[-1])
         with torch.cuda.device(self.device):
-            text = torch.empty(nbytes + 16, dtype=torch.uint8, device=self.device)
-            if head:
-                text[:len(head)] = torch.frombuffer(bytearray(head), dtype=torch.uint8).to(self.device)
-            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).view(dt)).to(self.device)
-            d_off, d_pos = up(off, np.int64), up(table["pos"], np.int32)
-            d_ref8, d_alt8 = up(table["ref8"], np.int64), up(table["alt8"], np.int64)
-            d_meta, d_thr = up(table["meta"], np.int32), up(table["thr"], np.int32)
-            check(lib.hhgt_synth_render_mixed(self.h, _ptr(text), nbytes, _ptr(d_off), _ptr(d_pos), _ptr(d_ref8),
-                                              _ptr(d_alt8), _ptr(d_meta), _ptr(d_thr), V, int(v_first),
-                                              contig.encode(), S, int(seed), _stream()))
+            text, off, nbytes = self._synth_text(contig, synth.mixed_line_lengths(contig, table, S), S, with_header, names)
+            d_off, d_pos = self._up(off, np.int64), self._up(table["pos"], np.int32)
+            d_ref8, d_alt8 = self._up(table["ref8"], np.int64), self._up(table["alt8"], np.int64)
+            d_meta, d_thr = self._up(table["meta"], np.int32), self._up(table["thr"], np.int32)
+            check(self.lib.hhgt_synth_render_mixed(self.h, _ptr(text), nbytes, _ptr(d_off), _ptr(d_pos), _ptr(d_ref8), _ptr(d_alt8),
+                                                   _ptr(d_meta), _ptr(d_thr), len(table["pos"]), int(v_first), contig.encode(), S,
+                                                   int(seed), _stream()))
             torch.cuda.current_stream().synchronize()
         return text[:nbytes], nbytes, off
 

@@ -112,7 +112,6 @@ def write_bgzf_native(path, data, level=6, n_threads=0):
     """the same file as write_bgzf, members deflated in parallel by libhhgt (`hhgt_synth_write_bgzf`; bench tooling).
     data: bytes-like or a uint8 numpy array (not copied)"""
     L = _lib.load()
-    L.hhgt_synth_write_bgzf.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int]
     a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
     a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
     check(L.hhgt_synth_write_bgzf(str(path).encode(), C.c_void_p(a.ctypes.data), a.size, int(level), int(n_threads)))
