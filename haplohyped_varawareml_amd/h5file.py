@@ -67,12 +67,52 @@ def _object_header(messages, refcount=1):
     return struct.pack("<BBHII4x", 1, 0, len(messages), refcount, len(body)) + body
 
 
+def _pwrite_all(fd, mv, pos):
+    while len(mv):
+        k = os.pwrite(fd, mv, pos)
+        mv = mv[k:]
+        pos += k
+
+
+class ParallelWrite:
+    """Large writes at known addresses, split over H5Writer.PAR_THREADS threads (os.pwrite and os.copy_file_range release the
+    GIL: one thread copies ~2 GB/s into the page cache, and the converter writes 40 MB batches).  The pool is made here, at
+    construction: one object may serve two threads (H5Writer.append beside write_at)."""
+
+    def __init__(self):
+        self.threads = H5Writer.PAR_THREADS
+        self._pool = None
+        if self.threads > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            self._pool = ThreadPoolExecutor(self.threads)
+
+    def pieces(self, n, piece):
+        """piece(offset, count) over [0, n): 4096-aligned pieces on the pool's threads from H5Writer.PAR_MIN bytes on, one
+        call otherwise"""
+        if n >= H5Writer.PAR_MIN and self._pool is not None:
+            step = -(-(-(-n // self.threads)) // 4096) * 4096
+            for fut in [self._pool.submit(piece, o, min(step, n - o)) for o in range(0, n, step)]:
+                fut.result()
+        else:
+            piece(0, n)
+
+    def write(self, fd, data, addr):
+        mv = memoryview(data).cast("B")
+        self.pieces(len(mv), lambda o, cnt: _pwrite_all(fd, mv[o:o + cnt], addr + o))
+        return len(mv)
+
+    def close(self):
+        if self._pool is not None:
+            self._pool.shutdown()
+            self._pool = None
+
+
 class H5Writer:
     """Append-only writer.  Usage:
         w = H5Writer(path); addr = w.append(chunk_bytes) ...; w.add_chunked(...); w.add_array(...); w.close()"""
 
-    PAR_MIN = 8 << 20      # appends at least this large are written by PAR_THREADS threads (os.pwrite releases the GIL:
-    PAR_THREADS = int(os.environ.get("HHGT_H5_WRITE_THREADS", "8"))   # one thread copies ~2 GB/s into the page cache, and the converter appends 40 MB batches)
+    PAR_MIN = 8 << 20      # writes at least this large go to PAR_THREADS threads (ParallelWrite)
+    PAR_THREADS = int(os.environ.get("HHGT_H5_WRITE_THREADS", "8"))
 
     def __init__(self, path):
         self.f = open(path, "wb", buffering=0)   # unbuffered: every write is a pwrite at an address this object keeps
@@ -80,64 +120,31 @@ class H5Writer:
         os.pwrite(self.fd, b"\0" * 2048, 0)    # superblock goes here at close
         self.pos = 2048
         self.groups = {"/": {}}              # group path -> {name: ("group", path) | ("dataset", header_addr)}
-        self._pool = None
-        if self.PAR_THREADS > 1:             # (made here, not at first use: append and write_at may run on two threads)
-            from concurrent.futures import ThreadPoolExecutor
-            self._pool = ThreadPoolExecutor(self.PAR_THREADS)
+        self._par = ParallelWrite()
 
     # ---- raw space ------------------------------------------------------------------------------------------
-    @staticmethod
-    def _pwrite_all(fd, mv, pos):
-        while len(mv):
-            k = os.pwrite(fd, mv, pos)
-            mv = mv[k:]
-            pos += k
-
-    def append(self, data, align=8):
+    def _aligned(self, align):
+        """pads the file to `align` -> the address of what comes next"""
         pad = -self.pos % align
         if pad:
             os.pwrite(self.fd, b"\0" * pad, self.pos)
             self.pos += pad
-        addr = self.pos
-        mv = memoryview(data).cast("B")
-        n = len(mv)
-        if n >= self.PAR_MIN:
-            if self._pool is None:
-                from concurrent.futures import ThreadPoolExecutor
-                self._pool = ThreadPoolExecutor(self.PAR_THREADS)
-            step = -(-n // self.PAR_THREADS)
-            step = -(-step // 4096) * 4096
-            for fut in [self._pool.submit(self._pwrite_all, self.fd, mv[o:o + step], addr + o) for o in range(0, n, step)]:
-                fut.result()
-        else:
-            self._pwrite_all(self.fd, mv, addr)
-        self.pos += n
+        return self.pos
+
+    def append(self, data, align=8):
+        addr = self._aligned(align)
+        self.pos += self._par.write(self.fd, data, addr)
         return addr
 
     def reserve(self, n, align=8):
         """n bytes of the file for a later write_at (their place is fixed now, their bytes may arrive on another thread)"""
-        pad = -self.pos % align
-        if pad:
-            os.pwrite(self.fd, b"\0" * pad, self.pos)
-            self.pos += pad
-        addr = self.pos
+        addr = self._aligned(align)
         self.pos += int(n)
         return addr
 
     def write_at(self, addr, data):
-        """the bytes of a reserve()d range; large ranges by PAR_THREADS threads.  Safe beside append() on another thread: the
-        two never share a range"""
-        mv = memoryview(data).cast("B")
-        n = len(mv)
-        if n >= self.PAR_MIN and self.PAR_THREADS > 1:
-            if self._pool is None:
-                from concurrent.futures import ThreadPoolExecutor
-                self._pool = ThreadPoolExecutor(self.PAR_THREADS)
-            step = -(-(-(-n // self.PAR_THREADS)) // 4096) * 4096
-            for fut in [self._pool.submit(self._pwrite_all, self.fd, mv[o:o + step], addr + o) for o in range(0, n, step)]:
-                fut.result()
-        else:
-            self._pwrite_all(self.fd, mv, addr)
+        """the bytes of a reserve()d range.  Safe beside append() on another thread: the two never share a range"""
+        self._par.write(self.fd, data, addr)
 
     def append_file(self, path, align=8):
         """the bytes of the file at `path` (a store's chunks.bin) -> file address; copied inside the kernel where it can
@@ -146,11 +153,7 @@ class H5Writer:
         n = os.path.getsize(path)
         if n == 0:
             return self.pos
-        pad = -self.pos % align
-        if pad:
-            os.pwrite(self.fd, b"\0" * pad, self.pos)
-            self.pos += pad
-        addr = self.pos
+        addr = self._aligned(align)
         src = os.open(path, os.O_RDONLY)
 
         def piece(o, cnt):
@@ -166,20 +169,12 @@ class H5Writer:
                     buf = os.pread(src, min(cnt - done, 16 << 20), o + done)
                     if not buf:
                         raise IOError(f"h5file: {path} ended early")
-                    self._pwrite_all(self.fd, memoryview(buf), addr + o + done)
+                    _pwrite_all(self.fd, memoryview(buf), addr + o + done)
                     k = len(buf)
                 done += k
 
         try:
-            if n >= self.PAR_MIN and self.PAR_THREADS > 1:
-                if self._pool is None:
-                    from concurrent.futures import ThreadPoolExecutor
-                    self._pool = ThreadPoolExecutor(self.PAR_THREADS)
-                step = -(-(-(-n // self.PAR_THREADS)) // 4096) * 4096
-                for fut in [self._pool.submit(piece, o, min(step, n - o)) for o in range(0, n, step)]:
-                    fut.result()
-            else:
-                piece(0, n)
+            self._par.pieces(n, piece)
         finally:
             os.close(src)
         self.pos += n
@@ -273,7 +268,7 @@ class H5Writer:
                                              addrs[gi + 1] if gi + 1 < len(groups) else UNDEF) + body
                 out += node + b"\0" * (node_bytes - len(node))
                 nxt.append((g[0][0], g[0][1], addrs[gi]))
-            self._pwrite_all(self.fd, memoryview(bytes(out)), self.pos)
+            _pwrite_all(self.fd, memoryview(bytes(out)), self.pos)
             self.pos += len(out)
             if len(groups) == 1:
                 return addrs[0]
@@ -321,11 +316,14 @@ class H5Writer:
         sb = SIG + struct.pack("<BBBBBBBB", 0, 0, 0, 0, 0, 8, 8, 0) + struct.pack("<HHI", LEAF_K, GROUP_K, 0) + \
             struct.pack("<QQQQ", 0, UNDEF, eof, UNDEF) + struct.pack("<QQI4xQQ", 0, hdr, 1, bt, hp)
         os.pwrite(self.fd, sb, 0)
-        if self._pool is not None:
-            self._pool.shutdown()
-            self._pool = None
-        self.f.close()
-        self.f = None
+        self.abandon()
+
+    def abandon(self):
+        """closes the file as it is: without close()'s superblock it is not an HDF5 file"""
+        if self.f is not None:
+            self._par.close()
+            self.f.close()
+            self.f = None
 
     def __enter__(self):
         return self

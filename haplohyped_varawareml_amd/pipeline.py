@@ -209,17 +209,6 @@ class _DeviceBgzfBlocks:
         self.raw = None
 
 
-class RawColumns:
-    """what on_columns gets as its first argument from the native engine: the size of the uncompressed columns
-    (the engine hands out framed chunks only; the legacy loop passes the device tensor itself)"""
-
-    def __init__(self, nbytes):
-        self._n = int(nbytes)
-
-    def numel(self):
-        return self._n
-
-
 def _want_device_inflate(device_inflate):
     """False: the host reader inflates (the north star's design, always selectable); True: BGZF files are inflated on the
     device; "auto" (the default since round 3; HHGT_DEVICE_INFLATE=0|1|auto overrides): in the ENGINE (stream_files, the
@@ -260,15 +249,16 @@ def peek_sample_count(path, limit=64 << 20):
 
 def stream_files(ctx, jobs, sc=dev.DEFAULT_SC, vc=dev.DEFAULT_VC, block_bytes=None, n_threads=0, sites_only=False,
                  fmt=dev.BLOSC2, device_inflate=None, on_header=None, on_variants=None, on_columns=None, on_end=None,
-                 files_ahead=1, expect_samples=None, clevel=None, hold_columns=False):
+                 files_ahead=1, expect_samples=None, clevel=None):
     """Several inputs through ONE native ingest engine (csrc/ingest.hip): the inflate of the next file overlaps the
     encode of the current one, and nothing waits on the host between blocks.
     jobs: [(path_or_host_buffer, region)]; callbacks get the job index first:
-        on_header(i, sample_names)   on_variants(i, start, ref, alt)   on_columns(i, RawColumns, n_cols, (bytes, offsets))
-        on_end(i, FileStats)
-    hold_columns: on_columns gets a fifth argument `release` and the (bytes, offsets) views stay valid until it is called
-        (from any thread) instead of until the callback returns — a consumer that writes the chunks on another thread
-        (hhgt_ingest_hold; the engine has five chunk buffers, so at most four batches can be in flight behind the current one)
+        on_header(i, sample_names)   on_variants(i, start, ref, alt)   on_columns(i, cols, hold)   on_end(i, FileStats)
+    cols: the engine's ingest.Columns event (framed, chunk_off, n_cols, raw_bytes), its views valid until the callback returns —
+        unless the consumer calls hold(): that returns `release`, and the views stay valid until release() is called (from
+        any thread) — a consumer that writes the chunks on another thread (hhgt_ingest_hold; the engine has five chunk
+        buffers, so at most four batches can be in flight behind the current one).  The engine is closed, on every way out,
+        only after each release taken has been called.
     -> [FileStats] in job order"""
     from .ingest import Columns, Header, Ingest, InputEnd, Variants
     stats = [FileStats() for _ in jobs]
@@ -279,58 +269,51 @@ def stream_files(ctx, jobs, sc=dev.DEFAULT_SC, vc=dev.DEFAULT_VC, block_bytes=No
     # level is restored afterwards.
     if clevel is None:
         clevel = int(os.environ.get("HHGT_FILE_CLEVEL", FILE_CLEVEL))
-    prev_clevel = getattr(ctx, "clevel", 5)
-    if hasattr(ctx, "set_clevel"):
-        ctx.set_clevel(clevel)
-    try:
-        return _stream_files(ctx, jobs, stats, sc, vc, block_bytes, n_threads, sites_only, fmt, device_inflate, on_header, on_variants,
-                             on_columns, on_end, files_ahead, expect_samples, hold_columns)
-    finally:
-        if hasattr(ctx, "set_clevel"):
-            ctx.set_clevel(prev_clevel)
-
-
-def _stream_files(ctx, jobs, stats, sc, vc, block_bytes, n_threads, sites_only, fmt, device_inflate, on_header, on_variants, on_columns,
-                  on_end, files_ahead, expect_samples, hold_columns=False):
-    from .ingest import Columns, Header, Ingest, InputEnd, Variants
     if expect_samples is None:     # the first file's header says how wide the cohort is: the engine sizes and pins at open
         first = next((src for src, _ in jobs if isinstance(src, (str, os.PathLike))), None)
         expect_samples = peek_sample_count(first) if first is not None else 0
-    with Ingest(ctx, sc=sc, vc=vc, fmt=fmt, sites_only=sites_only, device_inflate=_want_device_inflate(device_inflate),
-                n_threads=n_threads, block_bytes=block_bytes or 0, files_ahead=files_ahead, expect_samples=expect_samples) as ing:
-        for src, region in jobs:
-            if isinstance(src, (str, os.PathLike)):
-                ing.add_file(src, region)
-            else:
-                ing.add_memory(src, region)
-        ing.finish()
-        for ev in ing.events():
-            fs = stats[ev.input]
-            if isinstance(ev, Header):
-                names, _ = parse_header(np.frombuffer(ev.header, dtype=np.uint8))
-                fs.samples = names
-                if on_header:
-                    on_header(ev.input, names)
-            elif isinstance(ev, Variants):
-                fs.chrom_runs.extend(ev.runs)
-                if on_variants and len(ev.start):
-                    on_variants(ev.input, ev.start, ev.ref, ev.alt)
-            elif isinstance(ev, Columns):
-                if on_columns and hold_columns:
-                    token = ing.hold()
-                    on_columns(ev.input, RawColumns(ev.raw_bytes), ev.n_cols, (ev.framed, ev.chunk_off),
-                               (lambda t=token: ing.release(t)))
-                elif on_columns:
-                    on_columns(ev.input, RawColumns(ev.raw_bytes), ev.n_cols, (ev.framed, ev.chunk_off))
-            elif isinstance(ev, InputEnd):
-                for k, v in ev.stats.items():
-                    if hasattr(fs, k):
-                        setattr(fs, k, v)
-                fs.is_bgzf = bool(ev.stats["is_bgzf"])
-                if on_end:
-                    on_end(ev.input, fs)
-        if hold_columns:
-            ing.wait_released()      # the consumer's writer thread may still be writing held chunks: closing the engine frees them
+    prev_clevel = ctx.clevel
+    ctx.set_clevel(clevel)
+    try:
+        with Ingest(ctx, sc=sc, vc=vc, fmt=fmt, sites_only=sites_only, device_inflate=_want_device_inflate(device_inflate),
+                    n_threads=n_threads, block_bytes=block_bytes or 0, files_ahead=files_ahead, expect_samples=expect_samples) as ing:
+            for src, region in jobs:
+                if isinstance(src, (str, os.PathLike)):
+                    ing.add_file(src, region)
+                else:
+                    ing.add_memory(src, region)
+            ing.finish()
+
+            def hold():
+                token = ing.hold()
+                return lambda: ing.release(token)
+
+            try:
+                for ev in ing.events():
+                    fs = stats[ev.input]
+                    if isinstance(ev, Header):
+                        names, _ = parse_header(np.frombuffer(ev.header, dtype=np.uint8))
+                        fs.samples = names
+                        if on_header:
+                            on_header(ev.input, names)
+                    elif isinstance(ev, Variants):
+                        fs.chrom_runs.extend(ev.runs)
+                        if on_variants and len(ev.start):
+                            on_variants(ev.input, ev.start, ev.ref, ev.alt)
+                    elif isinstance(ev, Columns):
+                        if on_columns:
+                            on_columns(ev.input, ev, hold)
+                    elif isinstance(ev, InputEnd):
+                        for k, v in ev.stats.items():
+                            if hasattr(fs, k):
+                                setattr(fs, k, v)
+                        fs.is_bgzf = bool(ev.stats["is_bgzf"])
+                        if on_end:
+                            on_end(ev.input, fs)
+            finally:
+                ing.wait_released()      # a consumer's writer thread may still be writing held chunks: closing the engine frees them
+    finally:
+        ctx.set_clevel(prev_clevel)
     return stats
 
 
@@ -343,17 +326,20 @@ def stream_file(ctx, path, region="", sc=dev.DEFAULT_SC, vc=dev.DEFAULT_VC, bloc
     on_header(samples)                         once
     on_variants(start, ref, alt)               numpy arrays for each text block's kept records
     on_columns(G_cols, n_cols, framed)         for every batch of completed chunk columns:
-        G_cols: uint8 CUDA tensor [n_cols * column_bytes] (valid during the call),
         framed: (host bytes, offsets uint64[n_chunks+1]) when compress=True else None
+        G_cols: from the Python loop the uint8 CUDA tensor [n_cols * column_bytes]; the engine hands out framed chunks only,
+            so from it the ingest.Columns event (raw_bytes: the size of the uncompressed columns).  Valid during the call
     device_inflate: BGZF members are inflated on the device instead of by the host reader threads (None: the
         HHGT_DEVICE_INFLATE environment variable, default off — the north star keeps BGZF on the host)
     -> FileStats"""
     if compress and sc and not sites_only:
+        def columns(i, cols, hold):
+            on_columns(cols, cols.n_cols, (cols.framed, cols.chunk_off))
         return stream_files(ctx, [(path, region)], sc=sc, vc=vc, block_bytes=block_bytes, n_threads=n_threads, fmt=fmt,
                             device_inflate=device_inflate,
                             on_header=(lambda i, names: on_header(names)) if on_header else None,
                             on_variants=(lambda i, a, b, c: on_variants(a, b, c)) if on_variants else None,
-                            on_columns=(lambda i, g, n, f: on_columns(g, n, f)) if on_columns else None)[0]
+                            on_columns=columns if on_columns else None)[0]
     t_start = time.perf_counter()
     fs = FileStats()
     d = ctx.device

@@ -19,7 +19,8 @@ from collections import OrderedDict
 import numpy as np
 
 # (every public name of the split modules stays importable from here)
-from .store_h5 import (DONOR_CHUNK_ROWS, H5CohortWriter, _h5_group_datasets, _h5_strings, export_h5,  # noqa: F401
+from .h5file import ParallelWrite
+from .store_h5 import (DONOR_CHUNK_ROWS, CohortWriter, H5CohortWriter, _h5_group_datasets, _h5_strings, export_h5,  # noqa: F401
                        group_record, writer_meta)
 from .store_plan import (COUNT_PLAN_DTYPE, DEFAULT_PLANE_BYTES, LD_MIN_TILE, MAX_PAIR_TABLE_BYTES,  # noqa: F401
                          PLAN_DTYPE, PLANE_PLAN_DTYPE, ROW_PLAN_DTYPE, SAMPLE_PLAN_DTYPE, default_blocksize,
@@ -51,58 +52,42 @@ def chrom_column(runs, n, lo, hi, width):
     return col
 
 
-class StoreWriter:
+class StoreWriter(CohortWriter):
+    """CohortWriter into the store directory: a group's chunk bytes go into its chunks.bin as they arrive (add_chunks has
+    written them when it returns), its index and tables at end_group, meta.json at close"""
+
     def __init__(self, path, samples, sc, vc, typesize=2, cohort_name="", donor_ids=None, chunk_format="blosc2"):
+        assert chunk_format in ("blosc1", "blosc2")
+        super().__init__(samples, sc, vc, typesize, cohort_name, donor_ids, chunk_format)
         self.path = path
         os.makedirs(path, exist_ok=True)
-        assert chunk_format in ("blosc1", "blosc2")
-        self.meta = writer_meta(samples, sc, vc, typesize, cohort_name, donor_ids, chunk_format)
-        self._cur = None
+        self._f = None                      # the running group's chunks.bin
+        self._par = ParallelWrite()
 
-    def begin_group(self, group):
-        d = os.path.join(self.path, group)
-        os.makedirs(d, exist_ok=True)
-        self._cur = dict(name=group, dir=d, f=open(os.path.join(d, "chunks.bin"), "wb", buffering=0), offsets=[0],
-                         start=[], ref=[], alt=[], runs=[], n_variants=0, raw_bytes=0)
+    def _open_group(self, group):
+        self._dir = os.path.join(self.path, group)
+        os.makedirs(self._dir, exist_ok=True)
+        self._f = open(os.path.join(self._dir, "chunks.bin"), "wb", buffering=0)
 
-    def add_chunks(self, data, offsets, raw_bytes):
-        """data: bytes-like of concatenated framed chunks; offsets: uint64 relative offsets [k+1]"""
-        from .h5file import H5Writer
-        c = self._cur
-        base = c["offsets"][-1]
-        mv = memoryview(data).cast("B")
-        n, fd = len(mv), c["f"].fileno()
-        if n >= H5Writer.PAR_MIN and H5Writer.PAR_THREADS > 1:     # large batches: several pwrite threads (see H5Writer.append)
-            if getattr(self, "_pool", None) is None:
-                from concurrent.futures import ThreadPoolExecutor
-                self._pool = ThreadPoolExecutor(H5Writer.PAR_THREADS)
-            step = -(-(-(-n // H5Writer.PAR_THREADS)) // 4096) * 4096
-            for fut in [self._pool.submit(H5Writer._pwrite_all, fd, mv[o:o + step], base + o) for o in range(0, n, step)]:
-                fut.result()
-        else:
-            H5Writer._pwrite_all(fd, mv, base)
-        c["offsets"].extend(int(base + o) for o in offsets[1:])
-        c["raw_bytes"] += int(raw_bytes)
+    def _put(self, data, at, release):
+        self._par.write(self._f.fileno(), data, at)
 
-    add_variants = H5CohortWriter.add_variants          # (both writers keep a group's tables in the same running record)
-    add_chrom_runs = H5CohortWriter.add_chrom_runs
+    def _write_group(self, c, g):
+        self._f.close()
+        self._f = None
+        np.save(os.path.join(self._dir, "offsets.npy"), np.asarray(c.offsets, np.uint64))
+        for k, arr in zip(("start", "ref", "alt"), c.columns()):
+            np.save(os.path.join(self._dir, k + ".npy"), arr)
+        json.dump(c.runs, open(os.path.join(self._dir, "chrom_runs.json"), "w"))
 
-    def end_group(self):
-        c = self._cur
-        c["f"].close()
-        np.save(os.path.join(c["dir"], "offsets.npy"), np.asarray(c["offsets"], np.uint64))
-        for k in ("start", "ref", "alt"):
-            arr = np.concatenate(c[k]) if c[k] else np.zeros(0, np.uint32 if k == "start" else np.uint8)
-            np.save(os.path.join(c["dir"], k + ".npy"), arr)
-        json.dump(c["runs"], open(os.path.join(c["dir"], "chrom_runs.json"), "w"))
-        self.meta["groups"][c["name"]] = group_record(self.meta, c)
-        self._cur = None
-
-    def close(self):
-        if getattr(self, "_pool", None) is not None:
-            self._pool.shutdown()
-            self._pool = None
+    def _finish(self):
         json.dump(self.meta, open(os.path.join(self.path, "meta.json"), "w"), indent=1)
+
+    def _free(self):
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+        self._par.close()
 
 
 class GenotypeStore:

@@ -91,43 +91,28 @@ def wait_workers(procs, poll=0.2):
     return [p.exitcode for p in procs if p.exitcode != 0]
 
 
-def _default_stream():
-    from .pipeline import stream_files
-    return stream_files
+def rank_devices(world):
+    """GPU index of every rank: rank r drives GPU r % n_dev (counting devices does not initialise the GPU)"""
+    import torch
+    n_dev = max(torch.cuda.device_count(), 1)
+    return [r % n_dev for r in range(world)]
 
 
 def convert_rank(conv, rank, world, device, chromosomes, part_path, stream_fn=None, make_ctx=None, h5_path=None):
     """the work of one rank: its chromosome files -> groups of the (partial) store at part_path, all through ONE
     ingest engine (pipeline.stream_files): while chromosome k is being encoded, the host threads already inflate k+1.
-    stream_fn / make_ctx exist so that the CPU test suite can drive the rank / merge logic without a GPU.
+    stream_fn / make_ctx: the CPU test suite's stand-ins for pipeline.stream_files / device.Context (no GPU there).
     h5_path: write OUT/{cohort}.h5 directly instead of a store (one rank, no store asked for: store.H5CohortWriter)."""
+    from contextlib import closing
     from ._lib import BLOSC1      # filter 32001 = hdf5-blosc: Blosc-1 chunk framing
-    from .device import DEFAULT_SC, DEFAULT_VC
+    from .device import DEFAULT_SC, DEFAULT_VC, Context
+    from .pipeline import stream_files
+    from .sharding import pin_rank
     from .store import H5CohortWriter, StoreWriter
-    stream_fn = stream_fn or _default_stream()
-    real_device = make_ctx is None      # (decided before the default is filled in: a test's fake context has no GPU to ask)
-    if make_ctx is None:
-        from .device import Context
-        make_ctx = Context
     # this rank's share of the host: its reader threads (the engine starts `n_threads` per open file) stay on the CPUs of
     # its GPU's NUMA node and the N ranks of a node do not oversubscribe it (N x --cores threads before)
-    from .sharding import pin_rank
-    devices = None
-    if real_device:
-        try:
-            import torch
-            n_dev = max(torch.cuda.device_count(), 1)
-            devices = [r % n_dev for r in range(world)]      # worker_entry's rule: rank r drives GPU r % n_dev
-        except Exception:
-            devices = None
-    host = pin_rank(rank, world, device if real_device else None, conv.cores, devices=devices)
-    ctx = make_ctx(device)
-    if h5_path:
-        writer = H5CohortWriter(h5_path, [], DEFAULT_SC, DEFAULT_VC, cohort_name=conv.cohort_name,
-                                donor_ids=[d for d in conv.donor_ids if d])
-    else:
-        writer = StoreWriter(part_path, [], DEFAULT_SC, DEFAULT_VC, cohort_name=conv.cohort_name,
-                             donor_ids=[d for d in conv.donor_ids if d], chunk_format="blosc1")
+    host = pin_rank(rank, world, device, conv.cores, devices=rank_devices(world))
+    cohort = dict(samples=[], sc=DEFAULT_SC, vc=DEFAULT_VC, cohort_name=conv.cohort_name, donor_ids=[d for d in conv.donor_ids if d])
     stats = {}
     jobs = [(os.path.join(conv.vcf_dir, f"chr{c}.filtered.vcf.gz"), f"chr{c}") for c in chromosomes]
 
@@ -142,6 +127,11 @@ def convert_rank(conv, rank, world, device, chromosomes, part_path, stream_fn=No
             writer.meta["samples"] = list(names)
         writer.begin_group(f"chr_{chromosomes[i]}")
 
+    def on_columns(i, cols, hold):
+        # a writer that writes behind the engine keeps the chunk buffers until they are on file; the other has written them
+        # when add_chunks returns, and the engine may take them back then
+        writer.add_chunks(cols.framed, cols.chunk_off, cols.raw_bytes, release=hold() if writer.writes_behind else None)
+
     def on_end(i, fs):
         group = f"chr_{chromosomes[i]}"
         writer.add_chrom_runs(fs.chrom_runs)
@@ -154,19 +144,12 @@ def convert_rank(conv, rank, world, device, chromosomes, part_path, stream_fn=No
                     f"({fs.n_lines / max(fs.seconds, 1e-9):.0f} lines/s), ratio "
                     f"{fs.raw_bytes / max(fs.compressed_bytes, 1):.2f}")
 
-    try:
+    with closing((make_ctx or Context)(device)) as ctx, \
+            (H5CohortWriter(h5_path, **cohort) if h5_path else StoreWriter(part_path, chunk_format="blosc1", **cohort)) as writer:
         if jobs:
-            extra = {}
-            if h5_path and real_device:      # the .h5 is written behind the engine: the chunk buffers are held until they are on file
-                extra["hold_columns"] = True
-            stream_fn(ctx, jobs, sc=writer.meta["sc"], vc=writer.meta["vc"], n_threads=host["n_threads"], fmt=BLOSC1,
-                      on_header=on_header, on_variants=lambda i, a, b, c: writer.add_variants(a, b, c),
-                      on_columns=(lambda i, g, n, framed, release=None: writer.add_chunks(framed[0], framed[1], g.numel(), **({"release": release} if release else {}))),
-                      on_end=on_end, **extra)
-        writer.close()
-    finally:
-        if hasattr(ctx, "close"):
-            ctx.close()
+            (stream_fn or stream_files)(ctx, jobs, sc=DEFAULT_SC, vc=DEFAULT_VC, n_threads=host["n_threads"], fmt=BLOSC1,
+                                        on_header=on_header, on_variants=lambda i, a, b, c: writer.add_variants(a, b, c),
+                                        on_columns=on_columns, on_end=on_end)
     return stats
 
 
@@ -185,8 +168,7 @@ def worker_entry(rank, world, port, cfg, stream_fn=None, make_ctx=None):
     # instead of gloo's default 30, and run() ends them as soon as it sees the dead one
     dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(minutes=10))
     try:
-        n_dev = torch.cuda.device_count() if make_ctx is None else world
-        device = rank % max(n_dev, 1)
+        device = rank_devices(world)[rank]
         dist.barrier()
         t0 = time.time()
         err = None
@@ -248,35 +230,6 @@ class VCFtoHDF5Converter:
     def h5_path(self):
         """the reference's output file (vcf_to_h5.py:161)"""
         return os.path.join(self.out_dir, f"{self.cohort_name}.h5")
-
-    def genotype_vcf_to_store(self, ctx, writer, data_path: str, chromosome: int):
-        """one chromosome file -> group chr_{N} (all samples at once); the single-file form of what convert_rank
-        does for a whole rank (the reference's per-(donor, chromosome) method, vcf_to_h5.py:79-140)"""
-        from ._lib import BLOSC1      # filter 32001 = hdf5-blosc: Blosc-1 chunk framing
-        from .pipeline import stream_file as stream_fn
-        group = f"chr_{chromosome}"
-
-        def on_header(names):
-            missing = [d for d in self.donor_ids if d and d not in names]
-            if missing:   # cpp/vcfpp.h:373-377
-                raise RuntimeError(f"Error parsing VCF file: the {len(missing)}-th sample are not in the VCF.\n"
-                                   f"parameter samples:{missing[0]}")
-            if writer.meta["samples"] != list(names):
-                if writer.meta["groups"]:
-                    raise RuntimeError(f"{data_path}: sample columns differ from the previous chromosome files")
-                writer.meta["samples"] = list(names)
-            writer.begin_group(group)
-
-        def on_columns(G_cols, n_cols, framed):
-            writer.add_chunks(framed[0], framed[1], G_cols.numel())
-
-        fs = stream_fn(ctx, data_path, region=f"chr{chromosome}", sc=writer.meta["sc"], vc=writer.meta["vc"],
-                       n_threads=self.cores or 0, on_header=on_header, on_columns=on_columns,
-                       on_variants=writer.add_variants, fmt=BLOSC1)
-        writer.add_chrom_runs(fs.chrom_runs)
-        writer.end_group()
-        self.stats[group] = fs
-        return fs
 
     def process_donor(self, donor_id: str) -> None:
         """kept for API compatibility: the cohort path has no per-donor pass"""

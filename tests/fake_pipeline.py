@@ -24,15 +24,24 @@ def _read_text(path):
     return gzip.decompress(raw) if raw[:2] == b"\x1f\x8b" else raw      # BGZF is multi-member gzip
 
 
+holds = []      # one [released?] per hold() a stream_files of this module has handed out, in order
+
+
 def stream_files(ctx, jobs, sc=64, vc=8192, block_bytes=None, n_threads=0, sites_only=False, fmt=oracle.BLOSC2,
                  device_inflate=None, on_header=None, on_variants=None, on_columns=None, on_end=None, files_ahead=1):
-    """same interface as pipeline.stream_files"""
+    """same interface as pipeline.stream_files: on_columns(i, cols, hold), where cols has the fields of ingest.Columns that a
+    consumer reads and hold() returns a release that records its call in `holds`"""
+    def hold():
+        holds.append([False])
+        return lambda h=holds[-1]: h.__setitem__(0, True)
+
     out = []
     for i, (path, region) in enumerate(jobs):
         fs = stream_file(ctx, path, region=region, sc=sc, vc=vc, fmt=fmt,
                          on_header=(lambda names, i=i: on_header(i, names)) if on_header else None,
                          on_variants=(lambda a, b, c, i=i: on_variants(i, a, b, c)) if on_variants else None,
-                         on_columns=(lambda g, n, f, i=i: on_columns(i, g, n, f)) if on_columns else None)
+                         on_columns=(lambda g, n, f, i=i: on_columns(i, SimpleNamespace(input=i, n_cols=n, framed=f[0], chunk_off=f[1],
+                                                                                          raw_bytes=g.numel()), hold)) if on_columns else None)
         if on_end:
             on_end(i, fs)
         out.append(fs)

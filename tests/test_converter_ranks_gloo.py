@@ -88,6 +88,25 @@ def test_two_ranks_equal_single_process(tmp_path, golden_dir, fixture_golden):
     assert np.array_equal(back[:3, :1000], np.load(os.path.join(golden_dir, "fixture_G.npy")))
 
 
+def test_convert_rank_direct_h5_equals_the_export_of_its_store(tmp_path, golden_dir, fixture_golden):
+    """convert_rank with h5_path= (the converter's default on one GPU: store.H5CohortWriter behind the engine, every batch
+    of chunks held until it is on file) writes the file that export_h5 makes of the store convert_rank writes from the same
+    files, and has released every hold when it returns"""
+    from haplohyped_varawareml_amd.store import export_h5
+    vcf_dir, samples = _make_inputs(tmp_path, golden_dir, fixture_golden)
+    conv = vcf_to_h5.VCFtoHDF5Converter("c", vcf_dir, str(tmp_path / "out"), samples, 2, 1, n_gpus=1)
+    chroms = conv.present_chromosomes()
+    vcf_to_h5.convert_rank(conv, 0, 1, 0, chroms, conv.store_path, fake_pipeline.stream_files, fake_pipeline.FakeCtx)
+    exported = export_h5(conv.store_path, str(tmp_path / "exported.h5"))
+    n_before = len(fake_pipeline.holds)
+    vcf_to_h5.convert_rank(conv, 0, 1, 0, chroms, str(tmp_path / "unused"), fake_pipeline.stream_files, fake_pipeline.FakeCtx,
+                           h5_path=conv.h5_path)
+    taken = fake_pipeline.holds[n_before:]
+    assert len(taken) >= 3 and all(released for released, in taken)
+    assert not os.path.exists(tmp_path / "unused")
+    assert open(conv.h5_path, "rb").read() == open(exported, "rb").read()
+
+
 def test_failing_rank_fails_the_job(tmp_path, golden_dir, fixture_golden):
     """a rank that raises must not leave the others hanging in a collective, and the job must fail (the reference
     swallows worker exceptions, vcf_to_h5.py:191-192,204-205 — deliberately not mirrored)"""

@@ -137,7 +137,8 @@ def test_stream_files_callbacks(ctx, tmp_path):
     stats = stream_files(ctx, [(p, "chr8"), (p, "chr9")], sc=64, vc=1024, block_bytes=1 << 20,
                          on_header=lambda i, names: seen["h"].append((i, len(names), names[0])),
                          on_variants=lambda i, a, b, c: seen.__setitem__("v", seen["v"] + len(a)),
-                         on_columns=lambda i, g, n, f: (seen.__setitem__("c", seen["c"] + n), seen.__setitem__("raw", seen["raw"] + g.numel())),
+                         on_columns=lambda i, cols, hold: (seen.__setitem__("c", seen["c"] + cols.n_cols),
+                                                           seen.__setitem__("raw", seen["raw"] + cols.raw_bytes)),
                          on_end=lambda i, fs: seen["end"].append((i, fs.n_kept)))
     assert seen["h"] == [(0, S, "S00001"), (1, S, "S00001")] and seen["v"] == V and seen["c"] == 3
     assert seen["end"] == [(0, V), (1, 0)] and stats[0].chrom_runs == [(0, "chr8")] and stats[1].n_drop_region == V
@@ -145,8 +146,9 @@ def test_stream_files_callbacks(ctx, tmp_path):
 
 
 def test_stream_files_closes_after_held_columns_are_released(ctx, tmp_path, monkeypatch):
-    """hold_columns: closing the engine frees the held chunk bytes, so stream_files returns only after every release has
-    come back — the converter's .h5 writer thread releases a batch once it is on file, which may be after the last event"""
+    """hold(): closing the engine frees the held chunk bytes, so stream_files leaves only after every release has come
+    back — the converter's .h5 writer thread releases a batch once it is on file, which may be after the last event, or
+    after the consumer has raised inside on_columns with a hold taken"""
     import threading
     import time
     S, V = 70, 2500
@@ -167,14 +169,24 @@ def test_stream_files_closes_after_held_columns_are_released(ctx, tmp_path, monk
         log.append("release")
         release()
 
-    def on_columns(i, g, n, framed, release):
-        writers.append(threading.Thread(target=write_later, args=(release,)))
+    def on_columns(i, cols, hold):
+        writers.append(threading.Thread(target=write_later, args=(hold(),)))
         writers[-1].start()
 
-    stream_files(ctx, [(p, "chr8")], sc=64, vc=1024, block_bytes=1 << 20, on_columns=on_columns, hold_columns=True)
+    stream_files(ctx, [(p, "chr8")], sc=64, vc=1024, block_bytes=1 << 20, on_columns=on_columns)
     for t in writers:
         t.join()
     assert writers and log.index("close") == len(writers), log
+
+    def raising(i, cols, hold):
+        on_columns(i, cols, hold)
+        raise KeyError("consumer")
+
+    del log[:], writers[:]
+    with pytest.raises(KeyError, match="consumer"):
+        stream_files(ctx, [(p, "chr8")], sc=64, vc=1024, block_bytes=1 << 20, on_columns=raising)
+    writers[0].join()
+    assert len(writers) == 1 and log.index("close") == 1, log      # (Ingest.__del__ may log a second close)
 
 
 def test_errors_surface(ctx, tmp_path):

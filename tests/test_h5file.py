@@ -332,7 +332,8 @@ def test_genotype_store_opens_an_h5_file_cpu(tmp_path):
 def test_cohort_writer_equals_the_export_of_a_store(tmp_path):
     """store.H5CohortWriter (the converter's direct path) against StoreWriter + export_h5 on the same batches of chunks:
     byte-identical files — with the chunks written before add_chunks returns, and with them handed to the writer thread and
-    released afterwards (large batches go through the parallel pwrite path); an empty group among them"""
+    released afterwards (large batches go through the parallel pwrite path); an empty group among them.  StoreWriter takes
+    release= too: the same store, every release called before add_chunks returns"""
     import threading
     from oracle import oracle
     from haplohyped_varawareml_amd.store import GenotypeStore, H5CohortWriter, StoreWriter, export_h5
@@ -341,7 +342,7 @@ def test_cohort_writer_equals_the_export_of_a_store(tmp_path):
     samples = [f"S{i:03d}" for i in range(S)]
     groups = {"chr_3": 300, "chr_5": 0, "chr_9": 4000}
 
-    def feed(w, release_log=None):
+    def feed(w, release_log=None, released_on_return=False):
         w.meta["samples"] = list(samples)
         for gi, (group, V) in enumerate(groups.items()):
             g_rng = np.random.default_rng(100 + gi)
@@ -367,6 +368,7 @@ def test_cohort_writer_equals_the_export_of_a_store(tmp_path):
                     ev = threading.Event()
                     release_log.append(ev)
                     w.add_chunks(data, np.asarray(offs, np.uint64), raw, release=ev.set)
+                    assert ev.is_set() or not released_on_return
                 a, b = v0 * vc, min((v0 + 7) * vc, V)
                 w.add_variants(start[a:b], np.full(b - a, ord("A"), np.uint8), np.full(b - a, ord("G"), np.uint8))
             w.add_chrom_runs([(0, group.replace("_", ""))] if V else [])
@@ -382,8 +384,15 @@ def test_cohort_writer_equals_the_export_of_a_store(tmp_path):
     h5file.H5Writer.PAR_MIN = 4096                               # the small batches of this test through the parallel writes too
     try:
         feed(H5CohortWriter(str(tmp_path / "behind.h5"), [], sc, vc, cohort_name="c", donor_ids=samples[:2]), release_log=log)
+        store_log = []
+        feed(StoreWriter(store + ".released", [], sc, vc, cohort_name="c", donor_ids=samples[:2], chunk_format="blosc1"),
+             release_log=store_log, released_on_return=True)
     finally:
         h5file.H5Writer.PAR_MIN = old
+    assert store_log and all(ev.is_set() for ev in store_log)
+    tree = lambda root: {os.path.relpath(os.path.join(d, f), root): open(os.path.join(d, f), "rb").read()
+                         for d, _, fs in os.walk(root) for f in fs}
+    assert tree(store + ".released") == tree(store) and len(tree(store)) == 1 + 6 * len(groups)
     want = open(tmp_path / "exported.h5", "rb").read()
     assert open(tmp_path / "direct.h5", "rb").read() == want
     assert open(tmp_path / "behind.h5", "rb").read() == want
@@ -392,3 +401,76 @@ def test_cohort_writer_equals_the_export_of_a_store(tmp_path):
     assert st.groups() == ["chr_3", "chr_5", "chr_9"] and st.meta["groups"]["chr_9"]["n_variants"] == 4000
     assert st.meta["groups"]["chr_5"]["n_chunks"] == 0
     st.close()
+
+
+PAR_SIZES = [0, 1, 4095, 4096, 4097, 8 * 4096 - 1, 8 * 4096, 8 * 4096 + 1, 3 * 8 * 4096 + 5]
+
+
+@pytest.mark.parametrize("threads", [8, 1])
+@pytest.mark.parametrize("via", ["append", "write_at", "append_file"])
+def test_parallel_writes_land_where_pos_says(tmp_path, monkeypatch, via, threads):
+    """the one split of a large write (h5file.ParallelWrite: pieces of a multiple of 4096 bytes from PAR_MIN on) under
+    append, reserve + write_at and append_file, at the sizes around one piece, PAR_THREADS pieces and several pieces each:
+    the bytes at the returned address are the input, and what is appended next sits at the next multiple of 8 behind
+    zeros; with one thread the same through the single write"""
+    monkeypatch.setattr(h5file.H5Writer, "PAR_MIN", 4096)
+    monkeypatch.setattr(h5file.H5Writer, "PAR_THREADS", threads)
+    rng = np.random.default_rng(3)
+    p, src = str(tmp_path / "raw.h5"), str(tmp_path / "src.bin")
+    w = h5file.H5Writer(p)
+    want = []                                      # (address, bytes the file must hold there)
+    for n in PAR_SIZES:
+        data = rng.integers(1, 256, n, dtype=np.uint8).tobytes()      # no zero byte: padding cannot pass for data
+        before = w.pos
+        if via == "append":
+            addr = w.append(np.frombuffer(data, np.uint8), align=8)
+        elif via == "write_at":
+            addr = w.reserve(n, align=8)
+            w.write_at(addr, data)
+        else:
+            open(src, "wb").write(data)
+            addr = w.append_file(src, align=8)
+        if via == "append_file" and n == 0:         # an empty file appends nothing, no padding either
+            assert addr == before == w.pos
+        else:
+            assert addr == before + -before % 8 and w.pos == addr + n
+            want += [(before, bytes(addr - before)), (addr, data)]
+        end = w.pos
+        mark = w.append(b"\xAA\xBB\xCC", align=8)    # 3 bytes: the next write starts off the alignment
+        assert mark == end + -end % 8 and w.pos == mark + 3
+        want += [(end, bytes(mark - end)), (mark, b"\xAA\xBB\xCC")]
+    w.close()
+    got = open(p, "rb").read()
+    for addr, data in want:
+        assert got[addr:addr + len(data)] == data, (addr, len(data))
+
+
+@pytest.mark.parametrize("kind", ["store", "h5"])
+def test_writer_left_on_an_exception(tmp_path, kind):
+    """either cohort writer as a context manager, left by an exception with two held batches handed over: both releases
+    are called, the .h5 writer's thread has ended, the file handle is closed, and nothing that would make the output look
+    complete (meta.json, the superblock) is written"""
+    import threading
+    from haplohyped_varawareml_amd.store import H5CohortWriter, StoreWriter
+    out = str(tmp_path / ("c.hhgt" if kind == "store" else "c.h5"))
+    w = (StoreWriter(out, ["a", "b"], 64, 128, chunk_format="blosc1") if kind == "store" else
+         H5CohortWriter(out, ["a", "b"], 64, 128))
+    released, fd = [], []
+    with pytest.raises(ZeroDivisionError):
+        with w:
+            w.begin_group("chr_1")
+            fd.append(w._f.fileno() if kind == "store" else w.w.fd)
+            for k in range(2):
+                w.add_chunks(np.full(5000, 1 + k, np.uint8), np.array([0, 5000], np.uint64), 64 * 128 * 2,
+                             release=lambda k=k: released.append(k))
+            1 / 0
+    assert sorted(released) == [0, 1]
+    assert not [t for t in threading.enumerate() if t.name == "h5-cohort-writer"]
+    with pytest.raises(OSError):
+        os.fstat(fd[0])
+    if kind == "store":
+        assert not os.path.exists(os.path.join(out, "meta.json"))
+    else:
+        assert open(out, "rb").read(8) == bytes(8)
+        with pytest.raises(ValueError):
+            h5file.H5Reader(out)
