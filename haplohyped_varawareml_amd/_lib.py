@@ -10,9 +10,9 @@ LIB_PATH = os.environ.get("HHGT_LIB") or os.path.join(HERE, "libhhgt.so")
 OK = 0
 BLOSC1 = 1
 BLOSC2 = 2
-N_STAGES = 15
+N_STAGES = 16
 STAGE_NAMES = ["index", "fixed", "encode", "general", "lz4", "frame", "decode", "onehot", "inflate", "pairs", "ld_transpose",
-               "ld", "ld_prune", "ld_walk", "grm"]
+               "ld", "ld_prune", "ld_walk", "grm", "assoc"]
 
 
 class HhgtError(RuntimeError):
@@ -125,6 +125,7 @@ PROTOTYPES = {
     "hhgt_variant_planes": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
     "hhgt_ld_counts": (_i32, [_vp, _vp, _u64, _u64, _u32, _vp, _vp]),
     "hhgt_ld_prune": (_i32, [_vp, _vp, _u64, _u32, C.c_double, _vp, _vp]),
+    "hhgt_assoc_sums": (_i32, [_vp, _vp, _u64, _u64, _vp, _u32, _vp, _vp]),
     "hhgt_bgzf_scan": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _pu64, _pu64]),
     "hhgt_inflate_members": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _pu64, _vp]),
     "hhgt_onehot_windows": (_i32, [_vp, _vp, _u32, _u32, _vp, _i32, _vp, _vp, _vp]),

@@ -1301,3 +1301,28 @@ extern "C" int hhgt_ld_prune(hhgt_ctx *c, const uint32_t *d_table, uint64_t n_va
     TRY(timed(c, st, HHGT_STAGE_LD_PRUNE, [&] { return launch_ld_exceeds(d_table, n_var, window, r2, bits, st); }));
     return timed(c, st, HHGT_STAGE_LD_WALK, [&] { return launch_ld_walk(bits, n_var, window, d_keep, st); });
 }
+
+// hhgt_assoc_sums checks for itself (a family of one): the columns, the pointers its work needs (the sums with a variant,
+// the planes and the weights with a variant and a word), their alignment
+extern "C" int hhgt_assoc_sums(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w,
+                               uint32_t n_cols, double *d_sums, void *stream)
+{
+    if (n_cols < 1u || n_cols > 64u) {
+        hhgt_set_error("assoc_sums: %u columns (1 to 64)", n_cols);
+        return HHGT_ERR_ARG;
+    }
+    const bool reads = n_var && sw;
+    const char *null_arg = !n_var ? nullptr : !d_sums ? "sums" : !reads ? nullptr : !d_vplanes ? "variant planes" : !d_w ? "weights" : nullptr;
+    if (!c || null_arg) {
+        hhgt_set_error("assoc_sums: null %s", !c ? "context" : null_arg);
+        return HHGT_ERR_ARG;
+    }
+    if (off_alignment(d_w, 8) || off_alignment(d_sums, 8)) {
+        hhgt_set_error("assoc_sums: the weights and the sums must be 8-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!n_var) return HHGT_OK;
+    return timed(c, st, HHGT_STAGE_ASSOC, [&] { return launch_assoc_sums(d_vplanes, n_var, sw, d_w, n_cols, d_sums, st); });
+}

@@ -336,6 +336,9 @@ int launch_ld_counts(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, uin
 uint32_t ld_walk_words(uint32_t window);
 int launch_ld_exceeds(const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, uint64_t *d_bits, hipStream_t st);
 int launch_ld_walk(const uint64_t *d_bits, uint64_t n_var, uint32_t window, uint8_t *d_keep, hipStream_t st);
+// assoc.hip
+int launch_assoc_sums(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
+                      double *d_sums, hipStream_t st);
 int launch_inflate(const uint8_t *d_src, uint64_t src_bytes, const uint64_t *d_comp_off, const uint32_t *d_comp_len,
                    const uint64_t *d_out_off, const uint32_t *d_isize, uint64_t n_members, uint8_t *d_dst,
                    uint64_t dst_bytes, uint32_t *d_status, const uint32_t *d_crc32, const uint32_t *d_x2n, hipStream_t st);

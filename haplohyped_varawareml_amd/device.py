@@ -550,6 +550,26 @@ class Context:
             check(self.lib.hhgt_ld_counts(self.h, _ptr_if_any(vplanes), n, sw, window, _ptr_if_any(table), _stream()))
         return table
 
+    def assoc_sums(self, vplanes, w, sums=None):
+        """sums of per-sample weights under the bits (hhgt_assoc_sums) of variant-major planes [3, n, sw]: w is a float64
+        tensor [32 * sw, n_cols] (1 <= n_cols <= 64; zeros in the rows of no listed sample); sums, a float64 tensor
+        [n, 3, n_cols], gets at [v, k, c] the sum of w[s, c] over the bits s of row v of plane k — every entry written
+        (default: a new tensor), on the current stream.  -> sums"""
+        n, sw = _planes_arg(vplanes, "vplanes: a contiguous int32 tensor [3, n_var, sw]")
+        if (w.dtype != torch.float64 or w.dim() != 2 or w.shape[0] != 32 * sw or not w.is_contiguous()
+                or w.device != vplanes.device):
+            raise ValueError(f"w: a contiguous float64 tensor [{32 * sw}, n_cols] on the planes' device")
+        n_cols = int(w.shape[1])
+        if not 0 <= n_cols < 1 << 32:
+            raise ValueError(f"n_cols {n_cols}")
+        with torch.cuda.device(self.device):
+            if sums is None:        # (every entry is written: no need for zeros)
+                sums = torch.empty((n, 3, n_cols), dtype=torch.float64, device=self.device)
+            sums = self._out_arg(sums, torch.float64, (n, 3, n_cols), "sums")
+            check(self.lib.hhgt_assoc_sums(self.h, _ptr_if_any(vplanes), n, sw, _ptr_if_any(w), n_cols, _ptr_if_any(sums),
+                                           _stream()))
+        return sums
+
     def ld_prune(self, table, r2, keep=None):
         """the greedy walk (hhgt_ld_prune) over one tile: table is an int32 tensor [window + n, window, 8] — hhgt_ld_counts
         over the `window` variants before the tile (rows of zeros where there are none) followed by the tile's n —, keep a

@@ -13,11 +13,12 @@ ld_prune(chromosomes, donor_ids, min_maf, window, r2) the variants a greedy LD p
 genetic_relationship(chromosomes, donor_ids, min_maf, ld_window, ld_r2) the standardised genetic relationship matrix of the
 donors over the variants that pass min_maf and, with ld_window, the LD pruning (GenotypeStore.grm_sums), and
 principal_components(k, ...) its k largest eigenpairs, one record per donor (store.top_eigenpairs: numpy.linalg.eigh on the
-host).  The reference has no such queries."""
+host); association(phenotypes, covariates, chromosomes, donor_ids, min_maf, pcs, ...) a single-variant linear regression
+scan of every variant against one or more phenotypes (GenotypeStore.assoc).  The reference has no such queries."""
 import numpy as np
 
-from .store import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, chrom_column, grm_from_sums,
-                    kinship_from_counts, top_eigenpairs)
+from .store import (AC, AN, ASSOC_BETA, ASSOC_P, ASSOC_SE, ASSOC_T, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
+                    chrom_column, grm_from_sums, kinship_from_counts, top_eigenpairs)
 
 
 def _span(starts, start, end):
@@ -223,6 +224,49 @@ class VCFH5Reader:
         for c in range(int(k)):
             rec[f"pc{c + 1}"] = vectors[:, c]
         return rec, values
+
+    def association(self, phenotypes, covariates=None, chromosomes=None, donor_ids=None, min_maf=None, pcs=0,
+                    ld_window=None, ld_r2=0.2):
+        """single-variant linear regression scan of chr_{N} for N in chromosomes (one name or a list; None: every group)
+        over donor_ids (default: every sample, store order; each donor once) -> a list with one host numpy record array
+        per phenotype, one record per scanned variant in group and variant order: chrom, pos (1-based, the VCF's POS),
+        ref, alt, n (complete calls among the donors), af (mean dosage of the complete calls / 2; NaN without one), beta,
+        se, t, p (float64: store.assoc_from_sums, whose formulas are the contract — the coefficient of the dosage in the
+        fit of the phenotype on [1 | covariates | dosage], a call that is not complete imputed to the variant's mean; NaN
+        where the variant is not tested).  phenotypes is [n] or [n, P], covariates [n, q0] or None, both aligned with the
+        donors.  pcs = K appends the K components of principal_components over the same donors and chromosomes, with
+        min_maf, ld_window and ld_r2, to the covariates.  The scan itself runs over the variants that pass min_maf (the
+        minor allele frequency over the donors: GenotypeStore.variant_mask), not over the LD-pruned set."""
+        st = self.store
+        names, donors, who = self._cohort(chromosomes, donor_ids)
+        y = np.asarray(phenotypes, dtype=np.float64)
+        P = 1 if y.ndim == 1 else y.shape[1]
+        cov = None if covariates is None else np.asarray(covariates, dtype=np.float64)
+        if int(pcs):
+            rec, _ = self.principal_components(int(pcs), chromosomes, donor_ids, min_maf, ld_window, ld_r2)
+            pc = np.stack([rec[f"pc{c + 1}"] for c in range(int(pcs))], axis=1)
+            cov = pc if cov is None else np.concatenate([cov, pc], axis=1)
+        tables = [st.variants(g) for g in names]
+        width = max([len(r[1].encode()) for t in tables for r in t[3]] + [1])
+        dtype = [("chrom", f"S{width}"), ("pos", np.uint32), ("ref", "S10"), ("alt", "S10"), ("n", np.int64),
+                 ("af", np.float64), ("beta", np.float64), ("se", np.float64), ("t", np.float64), ("p", np.float64)]
+        parts = [[] for _ in range(P)]
+        for g, (start, ref, alt, runs) in zip(names, tables):
+            mask = st.variant_mask(g, who, min_maf=min_maf) if min_maf is not None else None
+            stats, calls = st.assoc(g, y, cov, who, variant_mask=mask)
+            stats, calls = stats.cpu().numpy(), calls.cpu().numpy()
+            at = np.arange(len(start)) if mask is None else np.flatnonzero(mask.cpu().numpy())
+            for k in range(P):
+                rec = np.zeros(len(at), dtype=dtype)
+                rec["chrom"] = chrom_column(runs, len(start), 0, len(start), width)[at]
+                rec["pos"], rec["ref"], rec["alt"] = start[at] + 1, ref.view("S1")[at], alt.view("S1")[at]
+                rec["n"] = calls[:, 0]
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    rec["af"] = (calls[:, 1] + 2.0 * calls[:, 2]) / calls[:, 0] / 2.0
+                rec["beta"], rec["se"] = stats[:, k, ASSOC_BETA], stats[:, k, ASSOC_SE]
+                rec["t"], rec["p"] = stats[:, k, ASSOC_T], stats[:, k, ASSOC_P]
+                parts[k].append(rec)
+        return [np.concatenate(p) if p else np.zeros(0, dtype=dtype) for p in parts]
 
     def close(self):
         pass

@@ -26,9 +26,11 @@ from .store_plan import (COUNT_PLAN_DTYPE, DEFAULT_PLANE_BYTES, LD_MIN_TILE, MAX
                          PLAN_DTYPE, PLANE_PLAN_DTYPE, ROW_PLAN_DTYPE, SAMPLE_PLAN_DTYPE, default_blocksize,
                          mask_words_per_block, pack_variant_mask, plan_counts, plan_planes, plan_rows, plan_sample_counts,
                          plan_windows, plane_positions, plane_rows, plane_windows, query_args, sample_index)
-from .store_stats import (AC, AN, GRM_SPAN, HET, HET1, HETHET, HOM_ALT, IBS0, LD_AA, LD_AM, LD_HA, LD_HH, LD_HM,  # noqa: F401
-                          LD_MA, LD_MH, LD_N, NSNP, grm_from_sums, ibs_counts, kinship_from_counts, ld_exceeds, ld_sums,
-                          r2_from_counts, standardized_dosages, top_eigenpairs)
+from .store_stats import (AC, AN, ASSOC_ALT, ASSOC_BETA, ASSOC_COMPLETE, ASSOC_HET, ASSOC_MAX_COLS, ASSOC_P,  # noqa: F401
+                          ASSOC_SE, ASSOC_T, GRM_SPAN, HET, HET1, HETHET, HOM_ALT, IBS0, LD_AA, LD_AM, LD_HA, LD_HH,
+                          LD_HM, LD_MA, LD_MH, LD_N, NSNP, assoc_design, assoc_from_sums, grm_from_sums, ibs_counts,
+                          kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts, standardized_dosages,
+                          student_t_two_sided, top_eigenpairs)
 
 # the reference's per-donor record (vcf_to_h5.py:119-127): packed, 35 bytes
 SNP_DTYPE = np.dtype([("chrom", "S5"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
@@ -117,6 +119,8 @@ class GenotypeStore:
         self.stats.update(ld_plane_blocks=0, ld_pairs=0)
         # and of grm_sums: Blosc blocks its plane stage decoded, plane words per row its two reductions read
         self.stats.update(grm_plane_blocks=0, grm_words=0)
+        # and of assoc_sums: Blosc blocks its plane stage decoded, counted variants it reduced
+        self.stats.update(assoc_plane_blocks=0, assoc_variants=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -520,8 +524,18 @@ class GenotypeStore:
         return top_eigenpairs(g.cpu().numpy(), k)
 
     def _ld_rows(self, who, group, samples, v_lo, v_hi, variant_mask, window, slab_bytes, plane_bytes):
-        """what ld_counts and ld_prune (`who`, for the messages) do alike -> (lo, hi, counted, n_counted, rows): the range,
-        checked; the offsets into it of the variants the mask marks, an int64 device tensor, or None; the number of counted
+        """what ld_counts and ld_prune (`who`, for the messages) do alike: the group and the window, checked, then
+        _variant_rows"""
+        if not isinstance(group, str) or group not in self.meta["groups"]:
+            raise KeyError(group)
+        if not 1 <= int(window) <= 1024:
+            raise ValueError(f"{who}: window {int(window)} (1 to 1024)")
+        return self._variant_rows(who, group, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes, "ld_plane_blocks")
+
+    def _variant_rows(self, who, group, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes, stat_key):
+        """the counted variants of a group as rows of bits, for `who` (in the messages), the plane stage's blocks counted in
+        stats[stat_key] -> (lo, hi, counted, n_counted, rows): the range, checked; the offsets into it of the variants the
+        mask marks, an int64 device tensor, or None; the number of counted
         variants (with a mask it comes from the device, together with the number of counted variants per plane window: one
         small copy per call, whatever the number of windows); and a generator of int32 device tensors [3, m, sw], the
         variant-major planes (HET, COMPLETE, HOM_ALT over the plane rows of `samples`) of the counted variants, in order,
@@ -529,10 +543,6 @@ class GenotypeStore:
         neither filled nor evicted; no variant mask there), each window is transposed (hhgt_variant_planes) and the rows at
         plane_positions of the counted variants gathered, which leaves out block padding and masked variants in one step."""
         import torch
-        if not isinstance(group, str) or group not in self.meta["groups"]:
-            raise KeyError(group)
-        if not 1 <= int(window) <= 1024:
-            raise ValueError(f"{who}: window {int(window)} (1 to 1024)")
         ctx = self._context()
         bs = self._blocksize()
         idx, [(group, lo, hi, n_var, variant_mask)] = self._query(who, group, samples, v_lo, v_hi, variant_mask, single=True)
@@ -552,7 +562,7 @@ class GenotypeStore:
             n_counted = cuts[-1]
 
         def rows():
-            walk = self._plane_walk(group, idx, lo, hi, n_var, "ld_plane_blocks", slab_bytes, plane_bytes)
+            walk = self._plane_walk(group, idx, lo, hi, n_var, stat_key, slab_bytes, plane_bytes)
             for w, (a, b, words, planes) in enumerate(walk):
                 pos = torch.from_numpy(plane_positions(a, b, bs)).to(ctx.device)
                 if counted is not None:
@@ -668,6 +678,50 @@ class GenotypeStore:
         out = torch.zeros(hi - lo, dtype=torch.bool, device=ctx.device)
         out[counted] = kept
         return out
+
+    def assoc_sums(self, group, W, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None):
+        """the sums over samples behind an association scan of a group: a float64 device tensor [n_counted, 3, C] — for
+        counted variant v (those of [v_lo, v_hi) that variant_mask marks, in order, as in ld_counts), plane k (ASSOC_HET,
+        ASSOC_COMPLETE, ASSOC_ALT: the call is HET, complete, HOM_ALT) and column c, the sum of W[i, c] over the samples i
+        whose call at v is of that class.  W: float64 [len(samples), C], host or device, 1 <= C <= 64, row i for
+        samples[i] (names or indices; None: every sample, store order).  The samples must be distinct — a regression has
+        no use for a row counted twice —: ValueError before anything is allocated.  W is scattered once to the plane
+        rows of the samples (zeros elsewhere); the rows of bits come as in ld_counts (hhgt_genotype_planes, then
+        hhgt_variant_planes per plane window: slab_bytes and plane_bytes mean what they mean there; cached chunks used,
+        the read cache neither filled nor evicted), and every window is reduced by one hhgt_assoc_sums call (the f64
+        MFMA; include/hhgt.h states its arithmetic: sums of exactly representable partial sums are exact).  No genotype
+        and no dosage is written anywhere."""
+        import torch
+        idx = self._query("assoc_sums", group, samples, v_lo, v_hi, variant_mask, single=True)[0]
+        if len(np.unique(idx)) != len(idx):
+            raise ValueError("assoc_sums: a sample is listed twice")
+        W = W if torch.is_tensor(W) else torch.from_numpy(np.ascontiguousarray(W))
+        if W.dtype != torch.float64 or W.dim() != 2 or W.shape[0] != len(idx) or not 1 <= W.shape[1] <= ASSOC_MAX_COLS:
+            raise ValueError(f"assoc_sums: W must be float64 [{len(idx)}, 1 to {ASSOC_MAX_COLS}], not {W.dtype} {list(W.shape)}")
+        ctx = self._context()
+        scols, rows = plane_rows(idx, self.meta["sc"])
+        sw = -(-len(scols) * self.meta["sc"] // 32)
+        _, _, _, n, vrows = self._variant_rows("assoc_sums", group, idx, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes,
+                                               "assoc_plane_blocks")
+        d_w = torch.zeros((32 * sw, W.shape[1]), dtype=torch.float64, device=ctx.device)
+        d_w[torch.from_numpy(rows).to(ctx.device)] = W.to(ctx.device)
+        parts = [ctx.assoc_sums(v, d_w) for v in vrows]
+        self.stats["assoc_variants"] += n
+        # (without a sample there is no row of bits: every sum is 0)
+        return torch.cat(parts) if parts else torch.zeros((n, 3, W.shape[1]), dtype=torch.float64, device=ctx.device)
+
+    def assoc(self, group, y, covariates=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None,
+              plane_bytes=None):
+        """single-variant linear regression scan of a group -> (stats, calls) on the device: assoc_design(y, covariates)
+        on the host (y [n] or [n, P], covariates [n, q0] or None, row i for samples[i]), assoc_sums of its W (same
+        remaining arguments), assoc_from_sums.  stats is float64 [n_counted, P, 4] — ASSOC_BETA, ASSOC_SE, ASSOC_T, ASSOC_P
+        of the dosage's coefficient in the fit of each phenotype on [1 | covariates | dosage], a call that is not
+        complete imputed to the variant's mean dosage; NaN where the variant is not tested —, calls int64 [n_counted, 3]:
+        complete, HET, HOM_ALT calls.  The formulas of assoc_from_sums are the contract; plink2's .glm.linear is not."""
+        import torch
+        W, q, yy = assoc_design(y, covariates)
+        T = self.assoc_sums(group, W, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes)
+        return assoc_from_sums(T, torch.from_numpy(W.sum(axis=0)).to(T.device), q, torch.from_numpy(yy).to(T.device))
 
     def variant_mask(self, group, samples=None, v_lo=0, v_hi=None, min_maf=None, max_ac=None, min_ac=None):
         """a class of the variants [v_lo, v_hi) of a group, from allele_counts over `samples` (same arguments), as a bool

@@ -1,6 +1,8 @@
 """The columns of GenotypeStore's count tables and the statistics read from them.  Every formula is written once and takes
 a numpy array or a torch tensor (on any device), answering in kind: _ops hands it the few operations the two spell
 differently."""
+import math
+
 import numpy as np
 
 # columns of GenotypeStore.allele_counts (and of hhgt_count_alleles' counters)
@@ -145,3 +147,148 @@ def top_eigenpairs(grm, k):
     lead = np.argmax(np.abs(v), axis=0)
     v[:, v[lead, np.arange(k)] < 0] *= -1.0
     return w, v
+
+
+# columns of the statistics table of assoc_from_sums (and GenotypeStore.assoc), per variant and phenotype
+ASSOC_BETA, ASSOC_SE, ASSOC_T, ASSOC_P = 0, 1, 2, 3
+# planes of GenotypeStore.assoc_sums (and of hhgt_assoc_sums' sums), in the kernel's order: HET calls, complete calls (both
+# alleles 0 or 1), HOM_ALT calls
+ASSOC_HET, ASSOC_COMPLETE, ASSOC_ALT = 0, 1, 2
+# columns of the per-sample matrix a call of hhgt_assoc_sums takes at most
+ASSOC_MAX_COLS = 64
+
+
+def _host_f64(x, name):
+    """numpy array or torch tensor -> float64 numpy array on the host, every value finite"""
+    if type(x).__module__.split(".")[0] == "torch":
+        x = x.detach().cpu().numpy()
+    a = np.asarray(x, dtype=np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError(f"assoc_design: {name} holds a value that is not finite")
+    return a
+
+
+def assoc_design(y, covariates=None):
+    """the per-sample matrix of an association scan -> (W, q, yy), host numpy, float64: y is [n] or [n, P] (P phenotypes),
+    covariates [n, q0] or None (numpy or torch).  Q = the orthonormal basis of [1 | covariates] from numpy.linalg.qr
+    (q = 1 + q0 columns), Yr = Y - Q Q^T Y the phenotypes with the covariates regressed out, W = [1 | Q | Yr],
+    [n, 1 + q + P], and yy [P] the column sums of Yr^2.  ValueError for a value that is not finite, covariates of another
+    row count than y, a rank-deficient [1 | covariates] (a diagonal entry of R below n * eps times the largest in
+    magnitude), n - q - 1 < 1 (no degree of freedom left for the variant) and 1 + q + P > 64 (hhgt_assoc_sums' columns)."""
+    Y = _host_f64(y, "y")
+    if Y.ndim == 1:
+        Y = Y[:, None]
+    if Y.ndim != 2:
+        raise ValueError(f"assoc_design: y of shape {Y.shape} ([n] or [n, P])")
+    n, P = Y.shape
+    X = np.ones((n, 1))
+    if covariates is not None:
+        cov = _host_f64(covariates, "covariates")
+        if cov.ndim != 2 or cov.shape[0] != n:
+            raise ValueError(f"assoc_design: covariates of shape {cov.shape} for {n} rows of y ([n, q0])")
+        X = np.concatenate([X, cov], axis=1)
+    q = X.shape[1]
+    if n - q - 1 < 1:
+        raise ValueError(f"assoc_design: {n} samples leave no degree of freedom beside {q} covariate columns and the variant")
+    if 1 + q + P > ASSOC_MAX_COLS:
+        raise ValueError(f"assoc_design: 1 + {q} covariate columns + {P} phenotypes exceed {ASSOC_MAX_COLS} columns")
+    Q, R = np.linalg.qr(X)
+    d = np.abs(np.diag(R))
+    if d.min() < n * np.finfo(np.float64).eps * d.max():
+        raise ValueError("assoc_design: [1 | covariates] is rank-deficient")
+    Yr = Y - Q @ (Q.T @ Y)
+    return np.concatenate([np.ones((n, 1)), Q, Yr], axis=1), q, (Yr * Yr).sum(axis=0)
+
+
+def _math(x):
+    """-> (log1p, exp, absolute, where, stack) for x's kind, numpy array or torch tensor"""
+    if type(x).__module__.split(".")[0] == "torch":
+        import torch
+        return torch.log1p, torch.exp, torch.abs, torch.where, torch.stack
+    return np.log1p, np.exp, np.abs, np.where, np.stack
+
+
+def _beta_fraction(a, b, x, steps, absolute, where):
+    """the continued fraction of the incomplete beta function at x (array), parameters a, b (numbers), by the modified
+    Lentz recurrence run for `steps` double steps whatever the values"""
+    tiny = 1e-300
+
+    def guard(v):
+        return where(absolute(v) < tiny, v * 0.0 + tiny, v)
+
+    qab, qap, qam = a + b, a + 1.0, a - 1.0
+    c = x * 0.0 + 1.0
+    d = 1.0 / guard(1.0 - qab * x / qap)
+    h = d
+    for m in range(1, steps + 1):
+        m2 = 2.0 * m
+        for aa in (m * (b - m) / ((qam + m2) * (a + m2)), -(a + m) * (qab + m) / ((a + m2) * (qap + m2))):
+            d = 1.0 / guard(1.0 + aa * x * d)
+            c = guard(1.0 + aa * x / c)
+            h = h * d * c
+    return h
+
+
+def student_t_two_sided(t, df):
+    """the two-sided p-value of Student's t with df degrees of freedom (a number) at t (numpy or torch, any shape) ->
+    float64 of t's shape: I_x(df / 2, 1 / 2) at x = df / (df + t^2), the regularised incomplete beta function, from its
+    continued fraction.  The fraction has a fixed length that depends on df alone (50 + 8 sqrt(df / 2) double steps of the
+    modified Lentz recurrence: it converges in O(sqrt(max(a, b))) steps), so every element does the same work and numpy
+    and torch run the same operations.  For x above (a + 1) / (a + b + 2) the fraction is that of 1 - I_(1-x)(1/2, df/2);
+    log x and log (1 - x) come from log1p of t^2 / df and df / t^2, so that a small p keeps its relative accuracy.
+    t = 0 gives 1, an infinite t 0, NaN stays NaN."""
+    log1p, exp, absolute, where, _ = _math(t)
+    f64 = _ops(t)[1]
+    df = float(df)
+    a, b = 0.5 * df, 0.5
+    steps = 50 + int(8.0 * math.sqrt(max(a, b)))
+    lbeta = math.lgamma(a + b) - math.lgamma(a) - math.lgamma(b)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        u = f64(t) * f64(t)
+        x, y = df / (df + u), u / (df + u)                      # y = 1 - x
+        lnx, lny = -log1p(u / df), -log1p(df / u)
+        front = exp(a * lnx + b * lny + lbeta)
+        # (an infinite t: x is 0, y is NaN, and the direct branch, which is taken, is 0)
+        direct = front * _beta_fraction(a, b, x, steps, absolute, where) / a
+        mirror = 1.0 - front * _beta_fraction(b, a, y, steps, absolute, where) / b
+        return where(x < (a + 1.0) / (a + b + 2.0), direct, mirror)
+
+
+def assoc_from_sums(T, W_total, q, yy):
+    """the statistics of a single-variant linear regression scan from the sums of GenotypeStore.assoc_sums ->
+    (stats, calls): T float64 [V, 3, C] (planes ASSOC_HET, ASSOC_COMPLETE, ASSOC_ALT; columns those of assoc_design's
+    W = [1 | Q | Yr], C = 1 + q + P), W_total [C] the column sums of W, yy [P] (numpy or torch, all of one kind).
+    calls is int64 [V, 3]: the complete, HET and HOM_ALT calls of each variant among the listed samples (column 0 of T:
+    exact).  With n = W_total[0], m, h, a those counts and mu = (h + 2a) / m — the dosage of a call that is not complete
+    is imputed to the mean of the complete ones —,
+        g.w_c = T[HET][c] + 2 T[ALT][c] + mu (W_total[c] - T[COMPLETE][c])      g.g = h + 4a + mu^2 (n - m)
+        D = g.g - sum_j (g.Q_j)^2      U_p = g.Yr_p      beta = U / D      rss = yy - U^2 / D      df = n - q - 1
+        se = sqrt(rss / df / D)        t = beta / se     p = student_t_two_sided(t, df)
+    stats is float64 [V, P, 4], columns ASSOC_BETA, ASSOC_SE, ASSOC_T, ASSOC_P: the coefficient of the dosage in the least-
+    squares fit of phenotype p on [1 | covariates | dosage].  All four are NaN where the variant is not tested: m == 0,
+    fewer than two of the three complete classes (HOM_REF, HET, HOM_ALT) non-empty, or D <= 1e-12 g.g (the covariates
+    explain the dosage).  The formula is the contract: plink2's .glm.linear, which drops the samples without a complete
+    call per variant where this imputes, is not."""
+    i64, f64, _, nan_unless = _ops(T)
+    stack = _math(T)[4]
+    q = int(q)
+    T, W_total, yy = f64(T), f64(W_total), f64(yy)
+    calls = stack([i64(T[:, ASSOC_COMPLETE, 0]), i64(T[:, ASSOC_HET, 0]), i64(T[:, ASSOC_ALT, 0])], -1)
+    n = W_total[0]
+    m, h, a = T[:, ASSOC_COMPLETE, 0], T[:, ASSOC_HET, 0], T[:, ASSOC_ALT, 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = (h + 2.0 * a) / m
+        gw = T[:, ASSOC_HET] + 2.0 * T[:, ASSOC_ALT] + mu[:, None] * (W_total[None, :] - T[:, ASSOC_COMPLETE])
+        gg = h + 4.0 * a + mu * mu * (n - m)
+        D = gg - (gw[:, 1:1 + q] * gw[:, 1:1 + q]).sum(-1)
+        classes = i64(m - h - a > 0) + i64(h > 0) + i64(a > 0)
+        tested = (m > 0) & (classes >= 2) & (D > 1e-12 * gg)
+        U = gw[:, 1 + q:]
+        df = n - q - 1
+        beta = U / D[:, None]
+        rss = yy[None, :] - U * U / D[:, None]
+        se = (rss / df / D[:, None]) ** 0.5
+        t = beta / se
+        p = student_t_two_sided(t, float(df))
+        stats = stack([beta, se, t, p], -1)
+        return nan_unless(tested[:, None, None], stats), calls

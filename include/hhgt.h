@@ -417,6 +417,24 @@ int hhgt_ld_counts(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uin
 int hhgt_ld_prune(hhgt_ctx *ctx, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, uint8_t *d_keep,
                   void *stream);
 
+/* hhgt_assoc_sums reduces the rows of d_vplanes, uint32 [3][n_var][sw] (hhgt_variant_planes' layout: HET, COMPLETE, HOM_ALT;
+ * bit s % 32 of word s / 32 of a row is plane row s; any three planes of that shape work: the arithmetic is defined on the
+ * bits), against per-sample weights: d_w is double [32 * sw][n_cols], row-major, 8-byte aligned, finite; the caller puts zeros
+ * in the rows that belong to no listed sample.  d_sums is double [n_var][3][n_cols], 8-byte aligned:
+ *     d_sums[v][k][c] = the sum of d_w[s][c] over the bit positions s at which row v of plane k has a 1.
+ * Every entry of d_sums is WRITTEN, with plain stores — the caller zeroes nothing, nothing accumulates, nothing outside
+ * [n_var][3][n_cols] is touched; with sw == 0 the sums are zeros.  The association scan behind GenotypeStore.assoc reads
+ * everything it needs from these sums (store_stats.assoc_from_sums).
+ * Arithmetic: v_mfma_f64_16x16x4_f64 with a plane bit as 0.0 / 1.0 on one side and d_w on the other, so every product is
+ * 0 or a value of d_w exactly and an entry is a float64 sum of the selected values and of zeros, taken in a fixed order:
+ * the result is deterministic, the same bits on every call; it is exact whenever every partial sum is representable;
+ * otherwise its error is bounded, to first order, by (m - 1) * 2^-53 * (the sum of |d_w[s][c]| over the selected s) for an
+ * entry that sums m values — the bound of a summation in any order: no order inside the instruction is claimed.
+ * 1 <= n_cols <= 64; any n_var up to 128 * (2^31 - 1) and any sw below 2^27, else HHGT_ERR_ARG; n_var == 0 is HHGT_OK and
+ * touches nothing. */
+int hhgt_assoc_sums(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
+                    double *d_sums, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values
@@ -538,7 +556,8 @@ int hhgt_inflate_members(hhgt_ctx *ctx, const void *d_src, uint64_t src_bytes, c
 #define HHGT_STAGE_LD_PRUNE 12 /* r^2 decisions of every pair                                    */
 #define HHGT_STAGE_LD_WALK 13 /* the greedy walk over the decisions                              */
 #define HHGT_STAGE_GRM 14     /* sums of products of standardised dosages over genotype planes   */
-#define HHGT_N_STAGES 15
+#define HHGT_STAGE_ASSOC 15   /* sums of per-sample weights under the bits of variant-major planes */
+#define HHGT_N_STAGES 16
 int hhgt_profile_enable(hhgt_ctx *ctx, int on);
 int hhgt_profile_reset(hhgt_ctx *ctx);
 int hhgt_profile_read(hhgt_ctx *ctx, double *ms /*[HHGT_N_STAGES]*/, uint64_t *launches /*[HHGT_N_STAGES]*/);
