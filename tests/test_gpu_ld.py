@@ -4,7 +4,9 @@ windows across one and several tiles, calls accumulating, the samples split over
 the walk of one wave) against the numpy walk, in one tile and in three with carry-in; GenotypeStore.ld_counts / ld_r2 /
 ld_prune on stores written from a known matrix in three geometries (one with padded blocks), directory and exported .h5 —
 sample lists, sub-ranges, MAF masks, seams in every block, the read cache untouched, the pruned mask fed to pair_counts;
-VCFH5Reader.ld_prune and the ld_prune CLI."""
+VCFH5Reader.ld_prune and the ld_prune CLI.  Windows past 65 up to the limit of 1024: hhgt_ld_counts with up to 33 tile rows, hhgt_ld_prune with
+4, 8 and 16 register words on the long-range recipe of tests/test_ld_plan.py (far_genotypes), its decisions at counts up to
+2^30 against exact integers and at exact ties, and the store with a window wider than its plane windows and tiles."""
 import numpy as np
 import pytest
 import torch
@@ -14,7 +16,8 @@ from haplohyped_varawareml_amd._lib import HhgtError
 from haplohyped_varawareml_amd.store import (LD_HM, LD_MH, GenotypeStore, StoreWriter, export_h5, ld_exceeds, plan_planes,
                                              plane_rows)
 from tests.test_gpu_sample_counts import np_variant_mask
-from tests.test_ld_plan import check_r2, ld_genotypes, np_exceeds, np_ld_table, np_prune, np_r2
+from tests.test_ld_plan import (FAR_V, FAR_WINDOWS, check_r2, exact_decisions, far_cohort, ld_genotypes, np_exceeds,
+                                np_ld_table, np_products, np_prune, np_r2, scaled_entries, tie_entries, walk_words)
 from tests.test_pair_count_plan import np_pair_table
 
 pytestmark = pytest.mark.gpu
@@ -118,6 +121,41 @@ def test_ld_counts_match_numpy(ctx, n_var, window):
             assert np.array_equal(t2.cpu().numpy(), want)
 
 
+WIDE = [(w, n) for w in (66, 96, 97, 128, 129, 1000, 1024)
+        for n in sorted({40, w, w + 1, w + 33} | ({1100} if w == 1024 else set()))]
+
+
+@pytest.mark.parametrize("window,n_var", WIDE)
+def test_ld_counts_wide_windows(ctx, window, n_var):
+    """hhgt_ld_counts with 4 to 33 tile rows in blockIdx.y: the ownership cut j - i > window where the window is no
+    multiple of 32, fewer variants than the window, the entry addressing (i * window + d) * 2 at wide rows.  Guards
+    `d < window` off by one (an entry at distance window + 1 written, or the one at distance window left out) and a pair
+    owned by two workgroups or by none.  Exact, into a table pre-filled with a pattern: what the call does not own it does
+    not touch."""
+    k, dd = np.arange(n_var)[:, None], np.arange(window)[None, :]
+    past = k + 1 + dd >= n_var
+    pattern = (np.arange(n_var * window * 8, dtype=np.int64) % 1009 + 1).astype(np.int32).reshape(n_var, window, 8)
+    for sw in (1, 3):
+        rng = np.random.default_rng(n_var * 1000 + window * 10 + sw)
+        vp, (m, h, a) = random_vplanes(rng, n_var, sw)
+        want = np_ld_from_classes(m, h, a, window)
+        assert (want[..., LD_HM] != want[..., LD_MH]).any() and past.any() and not want[past].any()
+        d = to_dev(ctx, vp)
+        table = torch.from_numpy(pattern).to(ctx.device)
+        assert ctx.ld_counts(d, window, table=table) is table
+        got = table.cpu().numpy()
+        assert np.array_equal(got[past], pattern[past])                      # past the end: untouched
+        assert np.array_equal(got, pattern + want), (n_var, window, sw)
+        assert ctx.ld_counts(d, window, table=table) is table                # a second call adds
+        assert np.array_equal(table.cpu().numpy(), pattern + 2 * want)
+        assert np.array_equal(ctx.ld_counts(d, window).cpu().numpy(), want)  # the default table: zeros
+        if sw > 1:                                                           # the samples split over two buffers
+            half = sw // 2
+            t2 = ctx.ld_counts(to_dev(ctx, vp[:, :, :half]), window)
+            ctx.ld_counts(to_dev(ctx, vp[:, :, half:]), window, table=t2)
+            assert np.array_equal(t2.cpu().numpy(), want)
+
+
 def test_ld_counts_constant_planes_and_bad_windows(ctx):
     n_var, window, sw = 70, 40, 3
     zeros = torch.zeros((3, n_var, sw), dtype=torch.int32, device=ctx.device)
@@ -181,6 +219,140 @@ def test_ld_prune_kernel_matches_numpy_walk(ctx, recipe, window):
             parts.append(out[window:])
             flags = np.concatenate([flags, out[window:]])[-window:]
         assert np.array_equal(np.concatenate(parts).astype(bool), want), (window, t)
+
+
+@pytest.fixture(scope="module")
+def far():
+    """the long-range cohort and its table at window 1024 (tests/test_ld_plan.py proves on the CPU that it bites)"""
+    return far_cohort()
+
+
+def prune_in_tiles(ctx, table, window, t, cuts):
+    """hhgt_ld_prune over the tiles [cuts[i], cuts[i + 1]), the flags of the last `window` variants carried in -> bool"""
+    flags = np.zeros(window, np.uint8)
+    parts = []
+    for a, b in zip(cuts, cuts[1:]):
+        buf = torch.from_numpy(np.concatenate([flags, np.full(b - a, 7, np.uint8)])).to(ctx.device)
+        out = ctx.ld_prune(to_dev(ctx, padded(table, window, a, b)), t, keep=buf).cpu().numpy()
+        assert np.array_equal(out[:window], flags) and set(np.unique(out[window:])) <= {0, 1}
+        parts.append(out[window:])
+        flags = np.concatenate([flags, out[window:]])[-window:]
+    return np.concatenate(parts).astype(bool)
+
+
+@pytest.mark.parametrize("window", FAR_WINDOWS)
+def test_ld_prune_wide_registers(ctx, far, window):
+    """k_ld_walk<2>, <4>, <8>, <16> (and k_ld_exceeds with as many words per variant) on the recipe whose every register
+    word decides alone: guards an upper register word dropped or its carry K[q - 1] >> 63 lost, the initial load of the
+    upper words from carried flags, the padded bits of a register wider than the window, and `d < window` off by one (a copy
+    at distance window goes, one at window + 1 stays).  In one tile and in four, one of them shorter than the window and one
+    cut between u and v of the chain, so that v stays because of a carried flag of 0 far back."""
+    table = far["table"][:, :window]
+    u0, u, v = far["chains"][window]
+    cuts = [0, window + 70, window + 71, max(u + 1, window + 200), FAR_V]
+    assert cuts == sorted(set(cuts)) and u < cuts[3] <= v
+    n_in_reach = sum(D <= window for D, _, _ in far["dups"])
+    assert walk_words(window) == {128: 2, 129: 4, 256: 4, 300: 8, 512: 8, 513: 16, 1024: 16}[window]
+    dev_table = to_dev(ctx, table)
+    whole = to_dev(ctx, padded(table, window, 0, FAR_V))
+    for t in (0.5, 0.999999):
+        want = np_prune(table, t)
+        assert (want[u0], want[u], want[v]) == (True, False, True) and (~want).sum() >= n_in_reach
+        assert np.array_equal(ld_exceeds(dev_table, t).cpu().numpy(), np_exceeds(table, t))
+        got = ctx.ld_prune(whole, t).cpu().numpy()
+        assert not got[:window].any() and set(np.unique(got)) <= {0, 1}
+        assert np.array_equal(got[window:].astype(bool), want), (window, t, np.nonzero(got[window:] != want)[0])
+        assert np.array_equal(prune_in_tiles(ctx, table, window, t, cuts), want), (window, t)
+
+
+@pytest.mark.parametrize("window", FAR_WINDOWS)
+def test_ld_prune_carried_flags_of_ones(ctx, far, window):
+    """the initial load K[q] = ballot(d < window && keep[window - 1 - d]) in every word: carried flags of 1 over table rows of
+    zeros prune nothing; a single carried variant at distance exactly `window` — the last bit in reach — prunes its
+    duplicate iff its flag is 1; one at window + 1 is not seen.  Guards `d < window` off by one and an upper word not
+    loaded."""
+    table = far["table"][:, :window]
+    n = 70
+    keep = torch.from_numpy(np.concatenate([np.ones(window, np.uint8), np.full(n, 7, np.uint8)])).to(ctx.device)
+    out = ctx.ld_prune(torch.zeros((window + n, window, 8), dtype=torch.int32, device=ctx.device), 0.5, keep=keep)
+    assert out.cpu().numpy().tolist() == [1] * (window + n)
+    by_distance = {D: (orig, copy) for D, orig, copy in far["dups"]}
+    orig, copy = by_distance[window]
+    tile = to_dev(ctx, padded(table, window, copy, copy + 1))           # row 0 is the original, `window` places back
+    assert copy - orig == window and np_exceeds(table, 0.5)[orig, window - 1]
+    one, rest = np.zeros(window, np.uint8), np.ones(window, np.uint8)
+    one[0], rest[0] = 1, 0
+    for flags, kept in ((one, 0), (np.zeros(window, np.uint8), 1), (rest, 1), (np.ones(window, np.uint8), 0)):
+        buf = torch.from_numpy(np.concatenate([flags, np.full(1, 7, np.uint8)])).to(ctx.device)
+        out = ctx.ld_prune(tile, 0.5, keep=buf).cpu().numpy()
+        assert np.array_equal(out[:window], flags) and out[window] == kept, (window, flags[:2], kept)
+    orig, copy = by_distance[window + 1]                                # out of reach: nothing in the tile's rows exceeds
+    buf = torch.from_numpy(np.concatenate([np.ones(window, np.uint8), np.full(1, 7, np.uint8)])).to(ctx.device)
+    assert ctx.ld_prune(to_dev(ctx, padded(table, window, copy, copy + 1)), 0.5, keep=buf).cpu().numpy()[window] == 1
+
+
+def device_decisions(ctx, entries, t, window=64):
+    """exceeds of each entry [n, 8] as hhgt_ld_prune decides it, one by one: blocks of one variant whose table row holds
+    `window` of the entries, followed by `window` variants whose rows are zeros — the first is kept (the rows before it
+    decide nothing), follower j is pruned iff entry j - 1 of the row exceeds, and lane d of a wave decides entry d
+    -> bool [n]"""
+    e = np.asarray(entries).reshape(-1, 8)
+    n, blocks = len(e), -(-len(e) // window)
+    assert e.min() >= 0 and e.max() < 1 << 30
+    rows = np.zeros((blocks * window, 8), np.int32)
+    rows[:n] = e
+    tab = np.zeros((window + blocks * (window + 1), window, 8), np.int32)
+    tab[window + np.arange(blocks) * (window + 1)] = rows.reshape(blocks, window, 8)
+    keep = ctx.ld_prune(to_dev(ctx, tab), t).cpu().numpy()
+    assert not keep[:window].any() and set(np.unique(keep)) <= {0, 1}
+    keep = keep[window:].reshape(blocks, window + 1)
+    assert keep[:, 0].all()
+    return (keep[:, 1:] == 0).reshape(-1)[:n]
+
+
+def test_ld_prune_decides_in_int64_at_large_counts(ctx):
+    """ld_exceeds of csrc/ld.hip at counts up to 2^30 - 1, where N sxy passes 2^57: guards a 32-bit (or float32) product
+    anywhere in n * sxy - sx * sy, which every table of 130 samples passes.  The decisions equal np_exceeds bit for bit,
+    and the exact ones (Python integers, fractions.Fraction(t); tests/test_ld_plan.py checks np_exceeds against them)
+    outside the near ties, which are at most 1 %.  With 8 register words too: the unit / nq, unit % nq split and the
+    d < window cut inside a word."""
+    small, big = scaled_entries()
+    table = big.reshape(600, 7, 8)
+    assert (np_products(big)[0] > 2.0 ** 100).any()
+    for t in (0.0, 0.2, 0.5, 1.0):
+        ex, near = exact_decisions(big, t)
+        assert near.mean() <= 0.01 and np.array_equal(ex, exact_decisions(small, t)[0])
+        want = np_exceeds(big, t)
+        for window in (64, 300):
+            got = device_decisions(ctx, big, t, window)
+            assert np.array_equal(got, want), (t, window, np.nonzero(got != want)[0][:10])
+            assert np.array_equal(got[~near], ex[~near]), (t, window)
+        assert np.array_equal(ld_exceeds(to_dev(ctx, big.astype(np.int32)), t).cpu().numpy(), want)
+        keep = ctx.ld_prune(to_dev(ctx, padded(table, 7, 0, 600)), t).cpu().numpy()[7:].astype(bool)
+        assert np.array_equal(keep, np_prune(table, t)) and np.array_equal(keep, np_prune(small.reshape(600, 7, 8), t))
+        assert keep.all() == (t == 1.0)
+
+
+def test_ld_prune_ties_and_the_ends_of_the_range(ctx, far):
+    """the contract says >: guards `>=` in place of `>`.  An entry whose r^2 is exactly t (1/4 or 1, at small counts and
+    near 2^30) does not exceed, one ulp below t it does; at 0 every entry with num != 0 exceeds and none with num = 0; at 1
+    nothing exceeds, and the walk keeps every variant, duplicates included."""
+    entries, r2 = tie_entries()
+    below = lambda x: float(np.nextafter(x, 0.0))
+    for window in (64, 129):
+        dec = lambda t: device_decisions(ctx, entries, t, window)
+        assert not dec(1.0).any() and np.array_equal(dec(below(1.0)), r2 == 1.0)
+        assert np.array_equal(dec(0.25), r2 == 1.0) and dec(below(0.25)).all()
+        assert np.array_equal(dec(float(np.nextafter(0.25, 1.0))), r2 == 1.0) and dec(0.0).all()
+    small, big = scaled_entries()
+    every = np.concatenate([entries, small, big])
+    num_is_0 = np_products(every)[0] == 0
+    assert num_is_0.any() and not num_is_0.all()
+    assert np.array_equal(device_decisions(ctx, every, 0.0), ~num_is_0)
+    assert not device_decisions(ctx, every, 1.0).any()
+    table = far["table"][:, :129]
+    assert (np_r2(table) == 1.0).sum() >= sum(D <= 129 for D, _, _ in far["dups"]) >= 9
+    assert ctx.ld_prune(to_dev(ctx, padded(table, 129, 0, FAR_V)), 1.0).cpu().numpy()[129:].all()
 
 
 def test_ld_prune_kernel_refuses(ctx):
@@ -321,6 +493,66 @@ def test_store_ld(ctx, stores, geom):
         st.close()
 
 
+@pytest.fixture(scope="module")
+def seam_store(ctx, stores):
+    """the padded geometry (100 variants per Blosc block) with two more duplicates, 101 and 250 places behind their
+    originals: whether they stay is decided across the seams of two or three plane windows"""
+    c = stores["geoms"][2]
+    g = c["g"].copy()
+    dups = ((300, 401), (370, 620))
+    for orig, copy in dups:
+        g[:, copy] = g[:, orig]
+    path = str(stores["tmp"] / "seam.hhgt")
+    write_store(ctx, path, g, c["sc"], c["vc"])
+    keep = {w: np_prune(np_ld_table(g, w), 0.2) for w in (50, 129, 300)}
+    for w, seen in ((129, (True, False)), (300, (True, True))):         # a condition on the data: the wide window decides
+        assert [bool(keep[50][copy] != keep[w][copy]) for _, copy in dups] == list(seen), w
+    return dict(g=g, path=path, V=c["V"])
+
+
+@pytest.mark.parametrize("window", [129, 300])
+def test_store_ld_window_wider_than_plane_windows(ctx, seam_store, window):
+    """GenotypeStore.ld_counts / ld_r2 / ld_prune with a carry longer than the new rows: at plane_bytes = 1 a plane window is
+    one block of 100 variants and a tile 64, so `carry = buf[:, -window:]` spans two to three plane windows, `old` is
+    restored over pairs carried more than once, and carry_keep holds flags of several tiles.  Guards a seam losing or
+    double-counting pairs (or keep flags) when the carry is longer than the new rows."""
+    g, n_v = seam_store["g"], seam_store["V"]
+    st = GenotypeStore(seam_store["path"], ctx=ctx)
+    pairs = GenotypeStore._ld_pairs(n_v, window)
+    assert pairs == n_v * window - window * (window + 1) // 2
+    for kw in (dict(plane_bytes=1), dict(), dict(slab_bytes=300_000), dict(plane_bytes=1, slab_bytes=3000)):
+        st.stats["ld_pairs"] = 0
+        kept = check_store(st, g, window, 0.2, None, 0, n_v, **kw)
+        assert st.stats["ld_pairs"] == 3 * pairs                         # ld_counts, ld_r2, ld_prune: once each
+        assert 0.1 * n_v <= kept.sum() <= 0.8 * n_v
+    check_store(st, g, window, 0.2, PICK, 0, n_v, plane_bytes=1)
+    check_store(st, g, window, 0.8, SPARSE, 55, n_v - 7, plane_bytes=1)                     # cut inside blocks at both ends
+    st.close()
+
+
+def test_store_ld_wide_window_under_a_mask_and_in_a_short_range(ctx, stores):
+    """window 300 on 128-variant chunks: a variant mask keeping about half (a carried row is a counted variant up to ~600
+    places back: four to five chunks), and a range shorter than the window (n < window: every pair of the range).  Guards
+    the same seam logic under a mask, and _ld_pairs / the table's shape with fewer variants than the window."""
+    c = stores["geoms"][0]
+    g, n_v, window = c["g"], c["V"], 300
+    mask = np.random.default_rng(5).random(n_v) < 0.5
+    n = int(mask.sum())
+    assert 0.4 * n_v < n < 0.6 * n_v
+    for path in c["paths"]:
+        st = GenotypeStore(path, ctx=ctx)
+        for kw in (dict(), dict(plane_bytes=1)):
+            st.stats["ld_pairs"] = 0
+            kept = check_store(st, g, window, 0.2, None, 0, n_v, mask_arg=mask, mask=mask, **kw)
+            assert st.stats["ld_pairs"] == 3 * (n * window - window * (window + 1) // 2) == 3 * GenotypeStore._ld_pairs(n, window)
+            assert not kept[~mask].any() and 0 < kept.sum() < n
+            st.stats["ld_pairs"] = 0
+            kept = check_store(st, g, window, 0.2, PICK, 700, 900, **kw)
+            assert st.stats["ld_pairs"] == 3 * (200 * 199 // 2) == 3 * GenotypeStore._ld_pairs(200, window)
+            assert 0 < kept.sum() < 200
+        st.close()
+
+
 def test_store_ld_leaves_read_cache_alone(ctx, stores):
     c = stores["geoms"][0]
     for path in c["paths"]:
@@ -359,7 +591,8 @@ def test_reader_ld_prune_and_cli(ctx, stores):
     maf = np_variant_mask(g[idx], min_maf=0.1)
     cases = [(dict(), None, np.ones(n_v, bool), 50, 0.2),
              (dict(donor_ids=donors, min_maf=0.1, window=7, r2=0.8), idx, maf, 7, 0.8),
-             (dict(chromosomes=[7], donor_ids=donors), idx, np.ones(n_v, bool), 50, 0.2)]
+             (dict(chromosomes=[7], donor_ids=donors), idx, np.ones(n_v, bool), 50, 0.2),
+             (dict(donor_ids=donors, window=300, r2=0.5), idx, np.ones(n_v, bool), 300, 0.5)]     # wider than two chunks
     wants = []
     for path in c["paths"]:
         r = VCFH5Reader(path, ctx=ctx)

@@ -89,7 +89,8 @@ def np_prune(table, r2, n=None):
     ex = np_exceeds(table, r2)
     keep = np.zeros(n, bool)
     for v in range(n):
-        keep[v] = not any(keep[u] and ex[u, v - u - 1] for u in range(max(v - window, 0), v))
+        u = np.arange(max(v - window, 0), v)
+        keep[v] = not (keep[u] & ex[u, v - u - 1]).any()
     return keep
 
 
@@ -101,6 +102,146 @@ def check_r2(got, want):
     assert np.array_equal(np.isnan(got), np.isnan(want))
     ok = ~np.isnan(want)
     np.testing.assert_allclose(got[ok], want[ok], rtol=1e-12, atol=0)
+
+
+# ---- the long-range recipe (wide windows: the keep flags of up to 1024 variants back decide) ---------------------------------
+
+FAR_WINDOWS = (128, 129, 256, 300, 512, 513, 1024)
+# distances of the planted duplicates: around every boundary of the walk's 64-bit register words that a power-of-two
+# register has, five places into each of the 16 words, and w, w + 1 of every window tested (the last in reach, the first out)
+FAR_DISTANCES = tuple(sorted({1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025}
+                             | {64 * q + 5 for q in range(16)} | {w + e for w in FAR_WINDOWS for e in (0, 1)}))
+FAR_S, FAR_V, FAR_SEED = 130, 3000, 7
+
+
+def walk_words(window):
+    """the 64-bit words of the walk's register (ld_walk_words of csrc/ld.hip restated): a power of two, 64 nq >= window"""
+    nq = 1
+    while nq * 64 < window:
+        nq *= 2
+    return nq
+
+
+def chain_distances(window):
+    """(D1, D2) of the chain planted for `window`: 700 and 600 at 1024, in proportion below — each within the window and
+    in its upper half, together beyond it"""
+    return 700 * window // 1024, 600 * window // 1024
+
+
+def far_layout(n_variants, window):
+    """where far_genotypes plants -> dict(dups=[(D, original, copy)], chains={w: (u0, u, v)}): every copy lies after
+    position `window`, and no two planted positions (originals included) are less than three places apart, so the only
+    identical variants are a duplicate and its original, and the three of a chain"""
+    used = []
+
+    def place(p, back):
+        while True:
+            spots = [p - b for b in back]
+            if min(spots) >= 0 and all(abs(x - y) >= 3 for x in spots for y in used):
+                used.extend(spots)
+                return spots
+            p += 1
+
+    dups, chains, p = [], {}, window + 6
+    for D in FAR_DISTANCES:
+        copy, orig = place(max(p, D), (0, D))
+        dups.append((D, orig, copy))
+        p = copy + 5
+    for w in sorted({x for x in FAR_WINDOWS if x <= window} | {window}):
+        d1, d2 = chain_distances(w)
+        v, u, u0 = place(max(p, d1 + d2), (0, d1, d1 + d2))
+        chains[w] = (u0, u, v)
+        p = v + 5
+    assert p <= n_variants, (p, n_variants)
+    return dict(dups=dups, chains=chains)
+
+
+def far_genotypes(seed, n_samples, n_variants, window):
+    """int8 [S, V, 2] with long-range structure and nothing else.  Base variants are independent, each with its own allele
+    frequency in U(0.1, 0.5), 1 % of the alleles -9.  At far_layout's places a variant is an exact copy (missing calls
+    included) of the one D places before it, for every D of FAR_DISTANCES; and per window w of FAR_WINDOWS up to `window`
+    (and `window` itself) there is one chain u0 -> u -> v: u copies u0 from D2 places back, v copies u from D1 places back,
+    (D1, D2) = chain_distances(w): at window w, u is pruned by u0, and v stays because u0 is out of reach and u not kept."""
+    rng = np.random.default_rng(seed)
+    af = rng.uniform(0.1, 0.5, n_variants)
+    g = (rng.random((n_samples, n_variants, 2)) < af[None, :, None]).astype(np.int8)
+    g[rng.random(g.shape) < 0.01] = -9
+    lay = far_layout(n_variants, window)
+    for _, orig, copy in lay["dups"]:
+        g[:, copy] = g[:, orig]
+    for u0, u, v in lay["chains"].values():
+        g[:, u] = g[:, u0]
+        g[:, v] = g[:, u]
+    return g
+
+
+_FAR = {}
+
+
+def far_cohort():
+    """the long-range cohort and its LD table at window 1024, int32 and read-only, computed once per process (the table of
+    a window w is its first w columns) -> dict(g, table, dups, chains)"""
+    if not _FAR:
+        g = far_genotypes(FAR_SEED, FAR_S, FAR_V, 1024)
+        table = np_ld_table(g, 1024).astype(np.int32)
+        table.setflags(write=False)
+        _FAR.update(g=g, table=table, **far_layout(FAR_V, 1024))
+    return _FAR
+
+
+# ---- exact decisions (Python integers and fractions) and crafted entries ---------------------------------------------------
+
+def exact_decisions(entries, t):
+    """entries [n, 8] -> (exceeds, near), bool [n] each: num^2 > t dx dy over the integers and fractions.Fraction(t) (the
+    exact value of the float), and the near ties |num^2 - t dx dy| <= 2^-48 num^2 with num != 0, the only entries at which
+    three float64 products and three conversions, each within 2^-53, may decide otherwise (with num = 0 the left side is an
+    exact 0 in float64 too, and never exceeds)"""
+    from fractions import Fraction
+    tt = Fraction(float(t))
+    ex, near = [], []
+    for e in np.asarray(entries).reshape(-1, 8).tolist():
+        n, hm, am, mh, ma, hh, ha, aa = e
+        sx, sxx, sy, syy, sxy = hm + 2 * am, hm + 4 * am, mh + 2 * ma, mh + 4 * ma, hh + 2 * ha + 4 * aa
+        num, dx, dy = n * sxy - sx * sy, n * sxx - sx * sx, n * syy - sy * sy
+        ex.append(num * num > tt * dx * dy)
+        near.append(num != 0 and abs(num * num - tt * dx * dy) <= Fraction(num * num, 1 << 48))
+    return np.array(ex), np.array(near)
+
+
+def scaled_entries(seed=0):
+    """the entries of a real table (ld_genotypes(1, 130, 600) at window 7), all eight counts of each multiplied by one
+    factor per entry, drawn so that the entry's largest count lies in [2^28, 2^30) -> (small int64 [n, 8], scaled int64
+    [n, 8]); r^2 is the same in both, N sxy and its like pass 2^57"""
+    rng = np.random.default_rng(seed)
+    small = np_ld_table(ld_genotypes(1, 130, 600), 7).reshape(-1, 8)
+    top = small.max(axis=1)
+    k = np.ones(len(small), np.int64)
+    live = top > 0
+    lo, hi = -(-(1 << 28) // top[live]), ((1 << 30) - 1) // top[live]
+    k[live] = rng.integers(lo, hi + 1)
+    big = small * k[:, None]
+    assert (big[live].max(axis=1) >= 1 << 28).all() and big.max() < 1 << 30
+    return small, big
+
+
+def duplicate_entry(n, het, alt, k=1):
+    """a variant of n complete calls, het HET and alt HOM_ALT, against itself, counts times k: r^2 is exactly 1"""
+    return [n * k, het * k, alt * k, het * k, alt * k, het * k, 0, alt * k]
+
+
+def quarter_entry(k=1):
+    """two 0 / 1 dosages over 8 samples with the 2 x 2 table (3, 1; 1, 3), counts times k: num = 8 k^2, dx = dy = 16 k^2,
+    so r^2 is exactly 1/4 — and in float64 too, whatever k: dx and dy are twice num, so dx dy rounds to 4 (num num)"""
+    return [8 * k, 4 * k, 0, 4 * k, 0, 3 * k, 0, 0]
+
+
+def tie_entries():
+    """-> (entries int64 [n, 8], r2 [n]): crafted entries whose r^2 is exactly 1 or exactly 1/4, at small counts and scaled
+    to the top of the contract's range (below 2^30)"""
+    e = [duplicate_entry(130, 40, 7), duplicate_entry(130, 40, 7, 8259552), duplicate_entry(97, 1, 0),
+         duplicate_entry(64, 0, 32, 1 << 23), quarter_entry(), quarter_entry(3), quarter_entry((1 << 27) - 1),
+         quarter_entry(123456789)]
+    return np.array(e, np.int64), np.array([1.0] * 4 + [0.25] * 4)
 
 
 # ---- plane_positions ------------------------------------------------------------------------------------------------------
@@ -231,3 +372,103 @@ def test_np_prune_on_the_recipe(n_samples, n_variants, window):
         hits = [u for u in range(max(v - window, 0), v) if keep[u] and ex[u, v - u - 1]]
         assert bool(hits) != bool(keep[v])
     assert np.array_equal(np_prune(table, 1.0), np.ones(n_variants, bool))
+
+
+# ---- the long-range recipe bites -------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def far():
+    return far_cohort()
+
+
+def test_far_recipe_layout_and_chance_pairs(far):
+    """the recipe is what it says: every planted copy lies past position 1024, the planted places are apart, and at 0.5 (and
+    at 0.999999) the pairs that exceed within 1024 places are exactly the pairs of identical planted variants — no chance
+    pair among 3 million at S = 130 —, so every decision of a walk is one the layout names"""
+    g, table, dups, chains = far["g"], far["table"], far["dups"], far["chains"]
+    assert g.shape == (FAR_S, FAR_V, 2) and g.dtype == np.int8 and (g == -9).any()
+    assert [D for D, _, _ in dups] == list(FAR_DISTANCES) and sorted(chains) == list(FAR_WINDOWS)
+    groups = [(o, c) for _, o, c in dups] + list(chains.values())
+    spots = sorted((x, i) for i, grp in enumerate(groups) for x in grp)
+    assert all(b - a >= 3 for (a, i), (b, j) in zip(spots, spots[1:]) if i != j)
+    assert spots[-1][0] < FAR_V and min(c for _, _, c in dups) > 1024
+    want = {(a, b) for grp in groups for a in grp for b in grp if a < b and b - a <= 1024}
+    for t in (0.5, 0.999999):
+        u, d = np.nonzero(np_exceeds(table, t))
+        assert {(int(a), int(a + 1 + b)) for a, b in zip(u, d)} == want
+    for grp in groups:
+        assert all(np.array_equal(g[:, grp[0]], g[:, x]) for x in grp[1:])
+
+
+@pytest.mark.parametrize("window", FAR_WINDOWS)
+def test_far_recipe_is_sensitive_to_every_register_word(far, window):
+    """conditions on the data that the GPU tests of hhgt_ld_prune at 4, 8 and 16 register words lean on: a walk that drops
+    an upper word of the keep-flag register or loses its carry, or cuts d < window one place early or late, gives another
+    mask on this recipe.  A seed that fails them is the wrong seed."""
+    table, dups, (u0, u, v) = far["table"][:, :window], far["dups"], far["chains"][window]
+    keep = np_prune(table, 0.5)
+    # a copy within reach goes, the first one out of reach stays; originals stay
+    assert {window, window + 1} <= {D for D, _, _ in dups}
+    for D, orig, copy in dups:
+        assert keep[orig] and keep[copy] == (D > window), (D, window)
+    # the chain: v's only exceeding predecessor in reach is u, whose flag is 0
+    d1, d2 = chain_distances(window)
+    assert (v - u, u - u0) == (d1, d2) and window / 2 < d2 <= d1 <= window < d1 + d2
+    assert (keep[u0], keep[u], keep[v]) == (True, False, True)
+    # every word of the register decides alone somewhere: a pruned variant whose only kept exceeding predecessor lies at
+    # bit d = v - u - 1 of that word
+    ex = np_exceeds(table, 0.5)
+    alone = set()
+    for x in np.nonzero(~keep)[0]:
+        cand = np.arange(max(x - window, 0), x)
+        hits = cand[keep[cand] & ex[cand, x - cand - 1]]
+        if len(hits) == 1:
+            alone.add(int(x - hits[0] - 1) // 64)
+    assert alone >= set(range(-(-window // 64))), (window, sorted(alone))
+    # and the next narrower register is not enough
+    half = 64 * walk_words(window) // 2
+    assert half < window and not np.array_equal(np_prune(table[:, :half], 0.5), keep)
+    # at 1 nothing exceeds: every variant stays, duplicates included
+    assert np_prune(table, 1.0).all()
+
+
+# ---- the decision arithmetic: np_exceeds and store.ld_exceeds against exact integers ---------------------------------------
+
+def test_exceeds_matches_exact_integers_at_large_counts():
+    """a 32-bit (or float32) intermediate anywhere in N sxy - sx sy passes every table of 130 samples; here the counts
+    reach 2^30 - 1 and the decisions are compared with Python integers.  Near ties (exact_decisions) are left out and must
+    be at most 1 % — a condition on the data."""
+    small, big = scaled_entries()
+    assert len(big) == 600 * 7 and (np.abs(np_products(big)[0]) > 2.0 ** 100).any()
+    for t in (0.0, 0.2, 0.5, 1.0):
+        ex_small, _ = exact_decisions(small, t)
+        ex, near = exact_decisions(big, t)
+        assert np.array_equal(ex, ex_small)                              # r^2 does not change under the scaling
+        assert near.mean() <= 0.01, (t, near.sum())
+        for got in (np_exceeds(big, t), S_.ld_exceeds(big, t), S_.ld_exceeds(torch.from_numpy(big), t).numpy()):
+            assert np.array_equal(got[~near], ex[~near]), t
+        assert ex.any() == (t < 1.0) and not ex.all()
+    # a product taken in 32 bits decides otherwise: the comparison notices
+    n, hm, am, mh, ma, hh, ha, aa = (big[:, c].astype(np.int32) for c in range(8))
+    with np.errstate(over="ignore"):
+        num = n * (hh + 2 * ha + 4 * aa) - (hm + 2 * am) * (mh + 2 * ma)
+        dx, dy = n * (hm + 4 * am) - (hm + 2 * am) ** 2, n * (mh + 4 * ma) - (mh + 2 * ma) ** 2
+    wrong = num.astype(np.float64) ** 2 > 0.2 * (dx.astype(np.float64) * dy.astype(np.float64))
+    assert not np.array_equal(wrong, exact_decisions(big, 0.2)[0])
+
+
+def test_exceeds_at_ties_and_at_the_ends_of_the_range():
+    """the contract says >: an entry whose r^2 is exactly t does not exceed, one ulp below it does (a >= would pass every
+    other test); at 0 every entry with num != 0 exceeds and none with num = 0; at 1 nothing does"""
+    entries, r2 = tie_entries()
+    assert np.array_equal(np_r2(entries), r2)
+    small, big = scaled_entries()
+    every = np.concatenate([entries, small, big])
+    num_is_0 = np_products(every)[0] == 0
+    assert num_is_0.any() and not num_is_0.all()
+    for f in (np_exceeds, S_.ld_exceeds):
+        assert not f(entries, 1.0).any() and np.array_equal(f(entries, 0.25), r2 == 1.0)
+        assert np.array_equal(f(entries, np.nextafter(1.0, 0.0)), r2 == 1.0)
+        assert f(entries, np.nextafter(0.25, 0.0)).all() and not f(entries, np.nextafter(0.25, 1.0))[r2 == 0.25].any()
+        assert np.array_equal(f(every, 0.0), ~num_is_0) and not f(every, 1.0).any()
+    assert np.array_equal(exact_decisions(every, 0.0)[0], ~num_is_0) and not exact_decisions(every, 1.0)[0].any()
