@@ -6,69 +6,23 @@
 #CHROM POS REF ALT ALT_CTS OBS_CT ALT_FREQS HET_CT HOM_ALT_CT, tab-separated: POS 1-based, ALT_CTS = alleles equal to 1,
 OBS_CT = called alleles, ALT_FREQS = ALT_CTS / OBS_CT as %.6g (NA where OBS_CT = 0), HET_CT / HOM_ALT_CT = heterozygous /
 1/1 calls.  The counts run on the device (GenotypeStore.allele_counts); groups come in chromosome order."""
-import re
-
 import click
 import numpy as np
 
+from .cohort_cli import (chromosome_option, h5_option, open_reader, ordered_chromosomes, out_option, parse_region,  # noqa: F401
+                         read_sample_list, region_excludes_chromosomes, region_option, sample_list_option, variant_lines)
 from .store import AC, AN, HET, HOM_ALT
 
 HEADER = "#CHROM\tPOS\tREF\tALT\tALT_CTS\tOBS_CT\tALT_FREQS\tHET_CT\tHOM_ALT_CT\n"
 
 
-def _bases(x):
-    x = np.asarray(x)
-    return (x.astype(np.uint8).view("S1") if x.dtype.kind == "u" else x.astype("S1")).astype("U1")
-
-
 def format_rows(chrom, pos, ref, alt, counts):
     """TSV lines (no header) for n variants: chrom str array-like [n], pos 1-based ints [n], ref / alt single-byte arrays
     (uint8 or S1) [n], counts int [n, 4] (AN, AC, HET, HOM_ALT) -> str, one line per variant, each ending in a newline"""
-    n = len(pos)
-    if n == 0:
-        return ""
-    c = np.asarray(counts, dtype=np.int64).reshape(n, 4)
+    c = np.asarray(counts, dtype=np.int64).reshape(len(pos), 4)
     an, ac = c[:, AN], c[:, AC]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        af = np.where(an > 0, ac / np.maximum(an, 1), 0.0)
-    freq = np.where(an > 0, np.char.mod("%.6g", af), "NA")
-    cols = [np.asarray(chrom).astype("U"), np.asarray(pos, np.int64).astype("U"), _bases(ref), _bases(alt),
-            ac.astype("U"), an.astype("U"), freq, c[:, HET].astype("U"), c[:, HOM_ALT].astype("U")]
-    line = cols[0]
-    for x in cols[1:]:
-        line = np.char.add(np.char.add(line, "\t"), x)
-    return "\n".join(line.tolist()) + "\n"
-
-
-def _chrom_key(group):
-    n = group[len("chr_"):]
-    return (0, int(n), "") if n.isdigit() else (1, 0, n)
-
-
-def parse_region(region):
-    """"chrN:beg-end" (1-based, inclusive) -> (N, 0-based start, 0-based end exclusive)"""
-    m = re.fullmatch(r"(?:chr)?([^:]+):([0-9,]+)-([0-9,]+)", region.strip())
-    if not m:
-        raise click.BadParameter(f"{region!r}: expected chrN:beg-end", param_hint="--region")
-    beg, end = int(m.group(2).replace(",", "")), int(m.group(3).replace(",", ""))
-    if beg < 1 or end < beg:
-        raise click.BadParameter(f"{region!r}: need 1 <= beg <= end", param_hint="--region")
-    return m.group(1), beg - 1, end
-
-
-def ordered_chromosomes(reader, chromosomes=None):
-    """the N of a VCFH5Reader's groups chr_N in chromosome order; with `chromosomes`, only those of them, and behind them
-    the ones asked for that the cohort does not have (the query raises for them)"""
-    names = [g[len("chr_"):] for g in sorted(reader.store.groups(), key=_chrom_key)]
-    if chromosomes:
-        want = [str(x) for x in chromosomes]
-        names = [x for x in names if x in want] + [x for x in want if x not in names]
-    return names
-
-
-def read_sample_list(path):
-    """the names of a --sample_list file, one per line -> list; None for no file"""
-    return None if path is None else [x.strip() for x in open(path) if x.strip()]
+    freq = np.where(an > 0, np.char.mod("%.6g", ac / np.maximum(an, 1)), "NA")
+    return variant_lines(chrom, pos, ref, alt, ac, an, freq, c[:, HET], c[:, HOM_ALT])
 
 
 def write_tsv(reader, out, donor_ids=None, chromosomes=None, region=None):
@@ -88,22 +42,17 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, region=None):
 
 
 @click.command()
-@click.option("--h5", "h5", required=True, type=str, help="Cohort file written by vcf_to_h5 (or a store directory)")
-@click.option("--out", required=True, type=str, help="Output TSV path")
-@click.option("--sample_list", default=None, type=str, help="Samples to count, one per line (default: all)")
-@click.option("--chromosome", multiple=True, type=str, help="Chromosome N of group chr_N (repeatable; default: all)")
-@click.option("--region", default=None, type=str, help="chrN:beg-end, 1-based inclusive")
+@h5_option
+@out_option("Output TSV path")
+@sample_list_option("Samples to count, one per line (default: all)")
+@chromosome_option
+@region_option
 def main(h5, out, sample_list, chromosome, region):
     """Writes per-variant allele counts and frequencies of the cohort in H5 to OUT."""
-    from .h5_reader import VCFH5Reader
-    if region is not None and chromosome:
-        raise click.UsageError("--region and --chromosome are exclusive")
-    r = VCFH5Reader(h5)
-    try:
+    region_excludes_chromosomes(region, chromosome)
+    with open_reader(h5) as r:
         write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome),
                   region=parse_region(region) if region else None)
-    finally:
-        r.close()
 
 
 if __name__ == "__main__":

@@ -19,7 +19,7 @@ contract, not plink2's .glm.linear).  Floats are %.17g, nan where the variant is
 import click
 import numpy as np
 
-from .allele_freq import ordered_chromosomes
+from . import cohort_cli as cli
 
 HEADER = "#CHROM\tPOS\tREF\tALT\tPHENO\tN\tAF\tBETA\tSE\tT\tP\n"
 
@@ -62,7 +62,7 @@ def write_tsv(reader, out, pheno, covar=None, chromosomes=None, min_maf=None, pc
             raise ValueError(f"{covar}: not the samples of {pheno}")
         at = {s: i for i, s in enumerate(c_samples)}
         cov = c[[at[s] for s in samples]]
-    recs = reader.association(y, cov, ordered_chromosomes(reader, chromosomes), donor_ids=samples, min_maf=min_maf, pcs=pcs,
+    recs = reader.association(y, cov, cli.ordered_chromosomes(reader, chromosomes), donor_ids=samples, min_maf=min_maf, pcs=pcs,
                               ld_window=ld_window, ld_r2=ld_r2)
     with open(out, "w") as f:
         f.write(HEADER)
@@ -74,26 +74,22 @@ def write_tsv(reader, out, pheno, covar=None, chromosomes=None, min_maf=None, pc
 
 
 @click.command()
-@click.option("--h5", "h5", required=True, type=str, help="Cohort file written by vcf_to_h5 (or a store directory)")
+@cli.h5_option
 @click.option("--pheno", required=True, type=str, help="Phenotypes: #IID<TAB>name..., one line per sample")
-@click.option("--out", required=True, type=str, help="Output TSV")
+@cli.out_option("Output TSV")
 @click.option("--covar", default=None, type=str, help="Covariates, same format (grm --pcs writes one)")
 @click.option("--pcs", default=0, type=int, help="Append this many principal components to the covariates")
-@click.option("--ld_window", default=None, type=int, help="LD-prune the variants of the components: counted variants back")
-@click.option("--ld_r2", default=0.2, type=float, help="LD-prune threshold on r^2 (with --ld_window)")
-@click.option("--min_maf", default=None, type=float, help="Scan only variants with at least this minor allele frequency")
-@click.option("--chromosome", multiple=True, type=str, help="Chromosome N of group chr_N (repeatable; default: all)")
+@cli.ld_options("LD-prune the variants of the components: counted variants back")
+@cli.min_maf_option("Scan only variants with at least this minor allele frequency")
+@cli.chromosome_option
 def main(h5, pheno, out, covar, pcs, ld_window, ld_r2, min_maf, chromosome):
     """Regresses every phenotype of PHENO on every variant of the cohort in H5 and writes the table OUT."""
-    from .h5_reader import VCFH5Reader
-    r = VCFH5Reader(h5)
-    try:
-        write_tsv(r, out, pheno, covar, chromosomes=list(chromosome), min_maf=min_maf, pcs=pcs, ld_window=ld_window,
-                  ld_r2=ld_r2)
-    except ValueError as e:
-        raise click.ClickException(str(e))
-    finally:
-        r.close()
+    with cli.open_reader(h5) as r:
+        try:
+            write_tsv(r, out, pheno, covar, chromosomes=list(chromosome), min_maf=min_maf, pcs=pcs, ld_window=ld_window,
+                      ld_r2=ld_r2)
+        except ValueError as e:
+            raise click.ClickException(str(e))
 
 
 if __name__ == "__main__":

@@ -15,14 +15,14 @@ the device (GenotypeStore.grm_sums), the eigendecomposition on the host (numpy.l
 import click
 import numpy as np
 
-from .allele_freq import ordered_chromosomes, read_sample_list
+from . import cohort_cli as cli
 
 
 def write_files(reader, prefix, donor_ids=None, chromosomes=None, min_maf=None, ld_window=None, ld_r2=0.2, pcs=None):
     """the files of a VCFH5Reader's cohort under the path prefix `prefix`: over every group, or chr_{N} for N in
     chromosomes; pcs: the number of principal components to write, None for none"""
     from .store import top_eigenpairs
-    donors, grm, _ = reader.genetic_relationship(ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids,
+    donors, grm, _ = reader.genetic_relationship(cli.ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids,
                                                  min_maf=min_maf, ld_window=ld_window, ld_r2=ld_r2)
     if pcs is not None:
         values, vectors = top_eigenpairs(grm, pcs)
@@ -38,23 +38,18 @@ def write_files(reader, prefix, donor_ids=None, chromosomes=None, min_maf=None, 
 
 
 @click.command()
-@click.option("--h5", "h5", required=True, type=str, help="Cohort file written by vcf_to_h5 (or a store directory)")
-@click.option("--out", required=True, type=str, help="Output path prefix")
-@click.option("--sample_list", default=None, type=str, help="Samples of the matrix, one per line (default: all)")
-@click.option("--chromosome", multiple=True, type=str, help="Chromosome N of group chr_N (repeatable; default: all)")
-@click.option("--min_maf", default=None, type=float, help="Use only variants with at least this minor allele frequency")
-@click.option("--ld_window", default=None, type=int, help="LD-prune first: counted variants to look back")
-@click.option("--ld_r2", default=0.2, type=float, help="LD-prune threshold on r^2 (with --ld_window)")
+@cli.h5_option
+@cli.out_option("Output path prefix")
+@cli.sample_list_option("Samples of the matrix, one per line (default: all)")
+@cli.chromosome_option
+@cli.min_maf_option("Use only variants with at least this minor allele frequency")
+@cli.ld_options("LD-prune first: counted variants to look back")
 @click.option("--pcs", default=None, type=int, help="Also write this many principal components")
 def main(h5, out, sample_list, chromosome, min_maf, ld_window, ld_r2, pcs):
     """Writes the genetic relationship matrix (and principal components) of the cohort in H5 under the prefix OUT."""
-    from .h5_reader import VCFH5Reader
-    r = VCFH5Reader(h5)
-    try:
-        write_files(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
+    with cli.open_reader(h5) as r:
+        write_files(r, out, donor_ids=cli.read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
                     ld_window=ld_window, ld_r2=ld_r2, pcs=pcs)
-    finally:
-        r.close()
 
 
 if __name__ == "__main__":

@@ -18,7 +18,7 @@ scan of every variant against one or more phenotypes (GenotypeStore.assoc).  The
 import numpy as np
 
 from .store import (AC, AN, ASSOC_BETA, ASSOC_P, ASSOC_SE, ASSOC_T, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
-                    chrom_column, grm_from_sums, kinship_from_counts, top_eigenpairs)
+                    check_components, grm_from_sums, kinship_from_counts, top_eigenpairs, variant_columns)
 
 
 def _span(starts, start, end):
@@ -34,6 +34,12 @@ class VCFH5Reader:
     def __init__(self, h5_file, ctx=None):
         self.h5_file = h5_file
         self.store = GenotypeStore(h5_file, ctx=ctx)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def _group(self, donor_id, chromosome):
         group = f"chr_{chromosome}"
@@ -56,6 +62,23 @@ class VCFH5Reader:
                 self._group(d, c)
         return [f"chr_{c}" for c in chroms], donors, None if donor_ids is None else donors
 
+    def _variant_masks(self, names, who, spans=None, min_maf=None, singletons=False, ld_window=None, ld_r2=0.2):
+        """which variants of the groups `names` a query over `who` takes -> {group: bool device tensor}, {} for all: those
+        that pass min_maf / singletons (variant_mask over spans[group] = (lo, hi), default all), then ld_prune's of them"""
+        st, masks, one = self.store, {}, 1 if singletons else None
+        for g in names:
+            if min_maf is not None or singletons:
+                masks[g] = st.variant_mask(g, who, *(spans or {}).get(g, (0, None)), min_maf=min_maf, min_ac=one, max_ac=one)
+            if ld_window is not None:
+                masks[g] = st.ld_prune(g, who, variant_mask=masks.get(g), window=ld_window, r2=ld_r2)
+        return masks
+
+    _variant_columns = staticmethod(variant_columns)      # (GenotypeStore.snp_records fills its records with it too)
+
+    def _donor_column(self, donors):
+        """the names as bytes -> S{width} [len(donors)], width that of the longest encoded name, at least 1"""
+        return np.array([x.encode() for x in donors], dtype=f"S{max([len(x.encode()) for x in donors] + [1])}")
+
     def fetch_genotypes(self, donor_id, chromosome):
         return self.store.snp_records(self._group(donor_id, chromosome), donor_id)
 
@@ -72,21 +95,16 @@ class VCFH5Reader:
         start, stop, ref, alt as in fetch_genotypes, then an (called alleles), ac (alleles equal to 1), af = ac / an
         (float32, NaN where an == 0), het, hom_alt"""
         [group], _, who = self._cohort([chromosome], donor_ids)
-        start_, ref, alt, runs = self.store.variants(group)
-        lo, hi = _span(start_, start, end)
+        tables = self.store.variants(group)
+        lo, hi = _span(tables[0], start, end)
         c = self.store.allele_counts(group, who, lo, hi).cpu().numpy()
-        width = max([len(r[1].encode()) for r in runs] + [1])
+        width = max([len(r[1].encode()) for r in tables[3]] + [1])
         rec = np.zeros(hi - lo, dtype=[("chrom", f"S{width}"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
                                        ("alt", "S10"), ("an", np.int32), ("ac", np.int32), ("af", np.float32),
                                        ("het", np.int32), ("hom_alt", np.int32)])
-        rec["chrom"] = chrom_column(runs, len(start_), lo, hi, width)
-        rec["start"] = start_[lo:hi]
-        rec["stop"] = start_[lo:hi] + 1
-        rec["ref"] = ref[lo:hi].view("S1")
-        rec["alt"] = alt[lo:hi].view("S1")
+        self._variant_columns(rec, tables, width, lo=lo, hi=hi)
         rec["an"], rec["ac"], rec["het"], rec["hom_alt"] = c[:, AN], c[:, AC], c[:, HET], c[:, HOM_ALT]
-        with np.errstate(divide="ignore", invalid="ignore"):
-            rec["af"] = np.where(c[:, AN] > 0, c[:, AC] / np.maximum(c[:, AN], 1), np.nan).astype(np.float32)
+        rec["af"] = np.where(c[:, AN] > 0, c[:, AC] / np.maximum(c[:, AN], 1), np.nan).astype(np.float32)
         return rec
 
     def sample_statistics(self, chromosomes=None, start=None, end=None, donor_ids=None, min_maf=None, singletons=False):
@@ -101,29 +119,18 @@ class VCFH5Reader:
         names, donors, who = self._cohort(chromosomes, donor_ids)
         if (start is not None or end is not None) and len(names) != 1:
             raise ValueError("sample_statistics: start / end need exactly one chromosome")
-        lo, hi, masks, n_variants = 0, None, {}, 0
+        spans = {g: (0, st.meta["groups"][g]["n_variants"]) for g in names}
         if start is not None or end is not None:
-            lo, hi = _span(st.variants(names[0])[0], start, end)
-        for g in names:
-            a, b = (lo, hi) if len(names) == 1 else (0, None)
-            b = st.meta["groups"][g]["n_variants"] if b is None else b
-            if min_maf is not None or singletons:
-                masks[g] = st.variant_mask(g, who, a, b, min_maf=min_maf, min_ac=1 if singletons else None,
-                                           max_ac=1 if singletons else None)
-                n_variants += int(masks[g].sum())
-            else:
-                n_variants += b - a
-        if len(names) == 1:
-            c = st.sample_counts(names[0], who, lo, hi, variant_mask=masks.get(names[0]))
-        else:
-            c = st.sample_counts(names, who, variant_mask=masks or None)
-        c = c.cpu().numpy().astype(np.int64)
-        width = max([len(x.encode()) for x in donors] + [1])
-        rec = np.zeros(len(donors), dtype=[("sample", f"S{width}"), ("n_variants", np.int64), ("an", np.int64),
+            spans[names[0]] = _span(st.variants(names[0])[0], start, end)
+        masks = self._variant_masks(names, who, spans, min_maf, singletons)
+        n_variants = sum(int(masks[g].sum()) if g in masks else spans[g][1] - spans[g][0] for g in names)
+        lo, hi = spans[names[0]] if len(names) == 1 else (0, None)
+        c = st.sample_counts(names, who, lo, hi, variant_mask=masks or None).cpu().numpy().astype(np.int64)
+        sample = self._donor_column(donors)
+        rec = np.zeros(len(donors), dtype=[("sample", sample.dtype), ("n_variants", np.int64), ("an", np.int64),
                                            ("ac", np.int64), ("het", np.int64), ("hom_alt", np.int64),
                                            ("missing", np.int64), ("call_rate", np.float64)])
-        rec["sample"] = [x.encode() for x in donors]
-        rec["n_variants"] = n_variants
+        rec["sample"], rec["n_variants"] = sample, n_variants
         rec["an"], rec["ac"], rec["het"], rec["hom_alt"] = c[:, AN], c[:, AC], c[:, HET], c[:, HOM_ALT]
         rec["missing"] = 2 * n_variants - c[:, AN]
         rec["call_rate"] = c[:, AN] / (2.0 * n_variants) if n_variants else np.nan
@@ -140,8 +147,7 @@ class VCFH5Reader:
         it (NaN pairs are then dropped)."""
         st = self.store
         names, donors, who = self._cohort(chromosomes, donor_ids)
-        masks = {g: st.variant_mask(g, who, min_maf=min_maf) for g in names} if min_maf is not None else None
-        table = st.pair_counts(names, who, variant_mask=masks)
+        table = st.pair_counts(names, who, variant_mask=self._variant_masks(names, who, min_maf=min_maf) or None)
         phi = kinship_from_counts(table).cpu().numpy()
         t = table.cpu().numpy().astype(np.int64)
         i, j = np.triu_indices(len(donors), 1)
@@ -149,11 +155,10 @@ class VCFH5Reader:
             with np.errstate(invalid="ignore"):
                 keep = phi[i, j] >= float(min_kinship)
             i, j = i[keep], j[keep]
-        width = max([len(x.encode()) for x in donors] + [1])
-        rec = np.zeros(len(i), dtype=[("sample1", f"S{width}"), ("sample2", f"S{width}"), ("nsnp", np.int64),
+        enc = self._donor_column(donors)
+        rec = np.zeros(len(i), dtype=[("sample1", enc.dtype), ("sample2", enc.dtype), ("nsnp", np.int64),
                                       ("hethet", np.int64), ("ibs0", np.int64), ("het1", np.int64), ("het2", np.int64),
                                       ("kinship", np.float64)])
-        enc = np.array([x.encode() for x in donors], dtype=f"S{width}")
         rec["sample1"], rec["sample2"] = enc[i], enc[j]
         rec["nsnp"], rec["hethet"], rec["ibs0"] = t[i, j, NSNP], t[i, j, HETHET], t[i, j, IBS0]
         rec["het1"], rec["het2"] = t[i, j, HET1], t[j, i, HET1]
@@ -172,20 +177,15 @@ class VCFH5Reader:
         names, donors, who = self._cohort(chromosomes, donor_ids)
         parts, tables = [], [st.variants(g) for g in names]
         width = max([len(r[1].encode()) for t in tables for r in t[3]] + [1])
-        for g, (start, ref, alt, runs) in zip(names, tables):
-            mask = st.variant_mask(g, who, min_maf=min_maf) if min_maf is not None else None
+        dtype = [("chrom", f"S{width}"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"), ("counted", bool), ("keep", bool)]
+        for g, t in zip(names, tables):
+            mask = self._variant_masks([g], who, min_maf=min_maf).get(g)
             keep = st.ld_prune(g, who, variant_mask=mask, window=window, r2=r2).cpu().numpy()
-            rec = np.zeros(len(start), dtype=[("chrom", f"S{width}"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"),
-                                              ("counted", bool), ("keep", bool)])
-            rec["chrom"] = chrom_column(runs, len(start), 0, len(start), width)
-            rec["start"], rec["ref"], rec["alt"] = start, ref.view("S1"), alt.view("S1")
-            rec["counted"] = True if mask is None else mask.cpu().numpy()
-            rec["keep"] = keep
+            rec = np.zeros(len(t[0]), dtype=dtype)
+            self._variant_columns(rec, t, width)
+            rec["counted"], rec["keep"] = True if mask is None else mask.cpu().numpy(), keep
             parts.append(rec)
-        if not parts:
-            return np.zeros(0, dtype=[("chrom", "S1"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"),
-                                      ("counted", bool), ("keep", bool)])
-        return np.concatenate(parts)
+        return np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
 
     def genetic_relationship(self, chromosomes=None, donor_ids=None, min_maf=None, ld_window=None, ld_r2=0.2):
         """the standardised genetic relationship matrix of donor_ids (default: every sample, store order) over the
@@ -196,15 +196,9 @@ class VCFH5Reader:
         allele frequency over the donors asked for is at least that (GenotypeStore.variant_mask per group); ld_window: of
         those, only the variants a greedy LD pruning keeps (GenotypeStore.ld_prune per group, `ld_window` counted variants,
         r^2 > ld_r2 drops).  Every mask is computed and applied on the device."""
-        st = self.store
         names, donors, who = self._cohort(chromosomes, donor_ids)
-        masks = {}
-        for g in names:
-            if min_maf is not None:
-                masks[g] = st.variant_mask(g, who, min_maf=min_maf)
-            if ld_window is not None:
-                masks[g] = st.ld_prune(g, who, variant_mask=masks.get(g), window=ld_window, r2=ld_r2)
-        sums, nsnp = st.grm_sums(names, who, variant_mask=masks or None)
+        masks = self._variant_masks(names, who, min_maf=min_maf, ld_window=ld_window, ld_r2=ld_r2)
+        sums, nsnp = self.store.grm_sums(names, who, variant_mask=masks or None)
         return donors, grm_from_sums(sums, nsnp).cpu().numpy(), nsnp.cpu().numpy()
 
     def principal_components(self, k=10, chromosomes=None, donor_ids=None, min_maf=None, ld_window=None, ld_r2=0.2):
@@ -213,15 +207,13 @@ class VCFH5Reader:
         unit eigenvector, whose component of largest magnitude is positive) —, and the eigenvalues float64 [k], descending
         (store.top_eigenpairs: numpy.linalg.eigh on the host).  ValueError if k is outside 1..n or a pair of donors has
         no jointly complete variant."""
-        n = len(self.store.samples) if donor_ids is None else len(list(donor_ids))
-        if not 1 <= int(k) <= n:
-            raise ValueError(f"pca: k = {int(k)} (1 to {n})")
+        k = check_components(k, len(self.store.samples) if donor_ids is None else len(list(donor_ids)))
         donors, grm, _ = self.genetic_relationship(chromosomes, donor_ids, min_maf, ld_window, ld_r2)
         values, vectors = top_eigenpairs(grm, k)
-        width = max([len(x.encode()) for x in donors] + [1])
-        rec = np.zeros(len(donors), dtype=[("sample", f"S{width}")] + [(f"pc{c + 1}", np.float64) for c in range(int(k))])
-        rec["sample"] = [x.encode() for x in donors]
-        for c in range(int(k)):
+        sample = self._donor_column(donors)
+        rec = np.zeros(len(donors), dtype=[("sample", sample.dtype)] + [(f"pc{c + 1}", np.float64) for c in range(k)])
+        rec["sample"] = sample
+        for c in range(k):
             rec[f"pc{c + 1}"] = vectors[:, c]
         return rec, values
 
@@ -251,18 +243,17 @@ class VCFH5Reader:
         dtype = [("chrom", f"S{width}"), ("pos", np.uint32), ("ref", "S10"), ("alt", "S10"), ("n", np.int64),
                  ("af", np.float64), ("beta", np.float64), ("se", np.float64), ("t", np.float64), ("p", np.float64)]
         parts = [[] for _ in range(P)]
-        for g, (start, ref, alt, runs) in zip(names, tables):
-            mask = st.variant_mask(g, who, min_maf=min_maf) if min_maf is not None else None
-            stats, calls = st.assoc(g, y, cov, who, variant_mask=mask)
-            stats, calls = stats.cpu().numpy(), calls.cpu().numpy()
-            at = np.arange(len(start)) if mask is None else np.flatnonzero(mask.cpu().numpy())
+        for g, t in zip(names, tables):
+            mask = self._variant_masks([g], who, min_maf=min_maf).get(g)
+            stats, calls = (x.cpu().numpy() for x in st.assoc(g, y, cov, who, variant_mask=mask))
+            at = np.arange(len(t[0])) if mask is None else np.flatnonzero(mask.cpu().numpy())
+            shared = np.zeros(len(at), dtype=dtype)             # what every phenotype's records say alike
+            self._variant_columns(shared, t, width, at=at, pos=True)
+            shared["n"] = calls[:, 0]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                shared["af"] = (calls[:, 1] + 2.0 * calls[:, 2]) / calls[:, 0] / 2.0
             for k in range(P):
-                rec = np.zeros(len(at), dtype=dtype)
-                rec["chrom"] = chrom_column(runs, len(start), 0, len(start), width)[at]
-                rec["pos"], rec["ref"], rec["alt"] = start[at] + 1, ref.view("S1")[at], alt.view("S1")[at]
-                rec["n"] = calls[:, 0]
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    rec["af"] = (calls[:, 1] + 2.0 * calls[:, 2]) / calls[:, 0] / 2.0
+                rec = shared.copy()
                 rec["beta"], rec["se"] = stats[:, k, ASSOC_BETA], stats[:, k, ASSOC_SE]
                 rec["t"], rec["p"] = stats[:, k, ASSOC_T], stats[:, k, ASSOC_P]
                 parts[k].append(rec)

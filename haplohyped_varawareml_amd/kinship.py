@@ -13,7 +13,7 @@ the listed samples is at least X; --min_kinship X writes only the pairs at or ab
 (GenotypeStore.pair_counts)."""
 import click
 
-from .allele_freq import ordered_chromosomes, read_sample_list
+from . import cohort_cli as cli
 
 HEADER = "#IID1\tIID2\tNSNP\tHETHET\tIBS0\tHET1\tHET2\tKINSHIP\n"
 
@@ -29,7 +29,7 @@ def format_rows(rec):
 
 def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, min_kinship=None):
     """the TSV of a VCFH5Reader's cohort to the path `out`: over every group, or chr_{N} for N in chromosomes"""
-    rec = reader.relatedness(ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf,
+    rec = reader.relatedness(cli.ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf,
                              min_kinship=min_kinship)
     with open(out, "w") as f:
         f.write(HEADER)
@@ -37,21 +37,17 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, min_k
 
 
 @click.command()
-@click.option("--h5", "h5", required=True, type=str, help="Cohort file written by vcf_to_h5 (or a store directory)")
-@click.option("--out", required=True, type=str, help="Output TSV path")
-@click.option("--sample_list", default=None, type=str, help="Samples to pair, one per line (default: all)")
-@click.option("--chromosome", multiple=True, type=str, help="Chromosome N of group chr_N (repeatable; default: all)")
-@click.option("--min_maf", default=None, type=float, help="Count only variants with at least this minor allele frequency")
+@cli.h5_option
+@cli.out_option("Output TSV path")
+@cli.sample_list_option("Samples to pair, one per line (default: all)")
+@cli.chromosome_option
+@cli.min_maf_option("Count only variants with at least this minor allele frequency")
 @click.option("--min_kinship", default=None, type=float, help="Write only pairs with at least this kinship")
 def main(h5, out, sample_list, chromosome, min_maf, min_kinship):
     """Writes the pairwise counts and kinship of the cohort in H5 to OUT."""
-    from .h5_reader import VCFH5Reader
-    r = VCFH5Reader(h5)
-    try:
-        write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
+    with cli.open_reader(h5) as r:
+        write_tsv(r, out, donor_ids=cli.read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
                   min_kinship=min_kinship)
-    finally:
-        r.close()
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ decisions and the walk run on the device (GenotypeStore.ld_prune)."""
 import click
 import numpy as np
 
-from .allele_freq import _bases, ordered_chromosomes, read_sample_list
+from . import cohort_cli as cli
 
 HEADER = "#CHROM\tPOS\tREF\tALT\n"
 
@@ -21,17 +21,12 @@ HEADER = "#CHROM\tPOS\tREF\tALT\n"
 def format_rows(chrom, pos, ref, alt):
     """TSV lines (no header) for n variants: chrom str array-like [n], pos 1-based ints [n], ref / alt single-byte arrays
     (uint8 or S1) [n] -> str, one line per variant, each ending in a newline"""
-    if len(pos) == 0:
-        return ""
-    line = np.asarray(chrom).astype("U")
-    for x in (np.asarray(pos, np.int64).astype("U"), _bases(ref), _bases(alt)):
-        line = np.char.add(np.char.add(line, "\t"), x)
-    return "\n".join(line.tolist()) + "\n"
+    return cli.variant_lines(chrom, pos, ref, alt)
 
 
 def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, window=50, r2=0.2):
     """the TSV of a VCFH5Reader's cohort to the path `out`: over every group, or chr_{N} for N in chromosomes"""
-    rec = reader.ld_prune(ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf, window=window,
+    rec = reader.ld_prune(cli.ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf, window=window,
                           r2=r2)
     rec = rec[rec["keep"]]
     with open(out, "w") as f:
@@ -40,22 +35,18 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, min_maf=None, windo
 
 
 @click.command()
-@click.option("--h5", "h5", required=True, type=str, help="Cohort file written by vcf_to_h5 (or a store directory)")
-@click.option("--out", required=True, type=str, help="Output TSV path")
-@click.option("--sample_list", default=None, type=str, help="Samples to correlate over, one per line (default: all)")
-@click.option("--chromosome", multiple=True, type=str, help="Chromosome N of group chr_N (repeatable; default: all)")
-@click.option("--min_maf", default=None, type=float, help="Only variants with at least this minor allele frequency take part")
+@cli.h5_option
+@cli.out_option("Output TSV path")
+@cli.sample_list_option("Samples to correlate over, one per line (default: all)")
+@cli.chromosome_option
+@cli.min_maf_option("Only variants with at least this minor allele frequency take part")
 @click.option("--window", default=50, type=click.IntRange(1, 1024), help="Neighbours looked back at, in counted variants")
 @click.option("--r2", default=0.2, type=click.FloatRange(0.0, 1.0), help="A kept neighbour with r^2 above this prunes a variant")
 def main(h5, out, sample_list, chromosome, min_maf, window, r2):
     """Writes the variants of the cohort in H5 that a greedy LD pruning keeps to OUT."""
-    from .h5_reader import VCFH5Reader
-    r = VCFH5Reader(h5)
-    try:
-        write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
+    with cli.open_reader(h5) as r:
+        write_tsv(r, out, donor_ids=cli.read_sample_list(sample_list), chromosomes=list(chromosome), min_maf=min_maf,
                   window=window, r2=r2)
-    finally:
-        r.close()
 
 
 if __name__ == "__main__":

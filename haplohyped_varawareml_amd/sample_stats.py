@@ -12,7 +12,7 @@ number of singletons a sample carries).  The counts run on the device (GenotypeS
 import click
 import numpy as np
 
-from .allele_freq import ordered_chromosomes, parse_region, read_sample_list
+from . import cohort_cli as cli
 from .store import AC, AN, HET, HOM_ALT
 
 HEADER = "#IID\tVARIANT_CT\tOBS_CT\tMISSING_CT\tALT_CTS\tHET_CT\tHOM_ALT_CT\n"
@@ -38,7 +38,7 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, region=None, min_ma
         rec = reader.sample_statistics([region[0]], region[1], region[2], donor_ids=donor_ids, min_maf=min_maf,
                                        singletons=singletons)
     else:
-        rec = reader.sample_statistics(ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf,
+        rec = reader.sample_statistics(cli.ordered_chromosomes(reader, chromosomes), donor_ids=donor_ids, min_maf=min_maf,
                                        singletons=singletons)
     counts = np.stack([rec["an"], rec["ac"], rec["het"], rec["hom_alt"]], axis=1)
     with open(out, "w") as f:
@@ -48,24 +48,19 @@ def write_tsv(reader, out, donor_ids=None, chromosomes=None, region=None, min_ma
 
 
 @click.command()
-@click.option("--h5", "h5", required=True, type=str, help="Cohort file written by vcf_to_h5 (or a store directory)")
-@click.option("--out", required=True, type=str, help="Output TSV path")
-@click.option("--sample_list", default=None, type=str, help="Samples to report, one per line (default: all)")
-@click.option("--chromosome", multiple=True, type=str, help="Chromosome N of group chr_N (repeatable; default: all)")
-@click.option("--region", default=None, type=str, help="chrN:beg-end, 1-based inclusive")
-@click.option("--min_maf", default=None, type=float, help="Count only variants with at least this minor allele frequency")
+@cli.h5_option
+@cli.out_option("Output TSV path")
+@cli.sample_list_option("Samples to report, one per line (default: all)")
+@cli.chromosome_option
+@cli.region_option
+@cli.min_maf_option("Count only variants with at least this minor allele frequency")
 @click.option("--singletons", is_flag=True, help="Count only variants whose alternate allele is carried exactly once")
 def main(h5, out, sample_list, chromosome, region, min_maf, singletons):
     """Writes per-sample genotype counts of the cohort in H5 to OUT."""
-    from .h5_reader import VCFH5Reader
-    if region is not None and chromosome:
-        raise click.UsageError("--region and --chromosome are exclusive")
-    r = VCFH5Reader(h5)
-    try:
-        write_tsv(r, out, donor_ids=read_sample_list(sample_list), chromosomes=list(chromosome),
-                  region=parse_region(region) if region else None, min_maf=min_maf, singletons=singletons)
-    finally:
-        r.close()
+    cli.region_excludes_chromosomes(region, chromosome)
+    with cli.open_reader(h5) as r:
+        write_tsv(r, out, donor_ids=cli.read_sample_list(sample_list), chromosomes=list(chromosome),
+                  region=cli.parse_region(region) if region else None, min_maf=min_maf, singletons=singletons)
 
 
 if __name__ == "__main__":

@@ -29,8 +29,8 @@ from .store_plan import (COUNT_PLAN_DTYPE, DEFAULT_PLANE_BYTES, LD_MIN_TILE, MAX
 from .store_stats import (AC, AN, ASSOC_ALT, ASSOC_BETA, ASSOC_COMPLETE, ASSOC_HET, ASSOC_MAX_COLS, ASSOC_P,  # noqa: F401
                           ASSOC_SE, ASSOC_T, GRM_SPAN, HET, HET1, HETHET, HOM_ALT, IBS0, LD_AA, LD_AM, LD_HA, LD_HH,
                           LD_HM, LD_MA, LD_MH, LD_N, NSNP, assoc_design, assoc_from_sums, grm_from_sums, ibs_counts,
-                          kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts, standardized_dosages,
-                          student_t_two_sided, top_eigenpairs)
+                          check_components, kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts,
+                          standardized_dosages, student_t_two_sided, top_eigenpairs)
 
 # the reference's per-donor record (vcf_to_h5.py:119-127): packed, 35 bytes
 SNP_DTYPE = np.dtype([("chrom", "S5"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
@@ -52,6 +52,26 @@ def chrom_column(runs, n, lo, hi, width):
         if a < b:
             col[a - lo:b - lo] = name.encode()[:width]
     return col
+
+
+def variant_columns(rec, tables, width, at=None, lo=0, hi=None, pos=False):
+    """fills rec's variant columns from a group's variants() `tables`, for its variants [lo, hi) or those at the indices
+    `at`: chrom (the CHROM runs, cut to width), start (pos=True: pos = start + 1), stop if rec has one, ref, alt"""
+    start, ref, alt, runs = tables
+    n, hi = len(start), len(start) if hi is None else hi
+    pick = slice(lo, hi) if at is None else at
+    rec["chrom"] = chrom_column(runs, n, lo, hi, width) if at is None else chrom_column(runs, n, 0, n, width)[at]
+    rec["pos" if pos else "start"] = start[pick] + int(pos)
+    if "stop" in rec.dtype.names:
+        rec["stop"] = start[pick] + 1
+    rec["ref"], rec["alt"] = ref[pick].view("S1"), alt[pick].view("S1")
+
+
+def _table_budget(who, what, nbytes, max_table_bytes):
+    """ValueError if tables of nbytes exceed max_table_bytes (None: MAX_PAIR_TABLE_BYTES); what: the message's middle"""
+    limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
+    if nbytes > limit:
+        raise ValueError(f"{who}: {what.format(nbytes)} max_table_bytes = {limit}")
 
 
 class StoreWriter(CohortWriter):
@@ -226,7 +246,6 @@ class GenotypeStore:
             bs = nbytes - (nbytes % ts if ts > 1 and nbytes >= ts else 0)
         return max(bs, 1)
 
-
     def _query(self, who, groups, samples=None, v_lo=0, v_hi=None, variant_mask=None, single=False):
         """query_args over this store: -> (sample indices, [(group, lo, hi, n_var, mask)])"""
         return query_args(self.meta, self._idx, who, groups, samples, v_lo, v_hi, variant_mask, single)
@@ -351,6 +370,12 @@ class GenotypeStore:
         vmask = pack_variant_mask(mask, lo, n_var, self.meta["vc"], self._blocksize())
         return vmask if torch.is_tensor(vmask) else torch.from_numpy(vmask.view(np.int32)).to(self._context().device)
 
+    def _device_bool(self, mask):
+        """a variant mask, host array or tensor -> a bool tensor on the device"""
+        import torch
+        mask = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(mask, dtype=bool))
+        return mask.to(self._context().device).to(torch.bool)
+
     def allele_counts(self, group, samples=None, v_lo=0, v_hi=None, slab_bytes=None):
         """per-variant allele counts of the variants [v_lo, v_hi) of a group over `samples` (names or indices, each counted
         once; None = every sample): an int32 device tensor [v_hi - v_lo, 4], columns AN, AC, HET, HOM_ALT (module
@@ -422,6 +447,19 @@ class GenotypeStore:
                 dsel, sc, vc, typesize=self.meta["typesize"], blocksize=bs, vmask=vmask, planes=planes))
             yield a, b, words, planes
 
+    def _pair_query(self, who, groups, samples, v_lo, v_hi, variant_mask, bytes_per_pair, max_table_bytes):
+        """pair_counts' and grm_sums' (`who`) start: _query, the plane rows, the budget of their tables of bytes_per_pair
+        per pair of plane rows -> (idx, queries, n_rows, pick: a table [n_rows, n_rows, ...] -> the samples' part of it)"""
+        import torch
+        idx, queries = self._query(who, groups, samples, v_lo, v_hi, variant_mask)
+        scols, rows = plane_rows(idx, self.meta["sc"])
+        n_rows = len(scols) * self.meta["sc"]
+        what = ("a table of {0} x {0} pairs ({{}} bytes) exceeds" if bytes_per_pair == 16 else
+                "tables of {0} x {0} pairs ({{}} bytes) exceed").format(n_rows)
+        _table_budget(who, what, n_rows * n_rows * bytes_per_pair, max_table_bytes)
+        rows = torch.from_numpy(rows).to(self._context().device)
+        return idx, queries, n_rows, lambda table: table[rows][:, rows].contiguous()
+
     def pair_counts(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None,
                     plane_bytes=None, max_table_bytes=None):
         """pairwise counts over the variants of `groups`: an int32 device tensor [n, n, 4], columns NSNP, HETHET, IBS0, HET1
@@ -436,13 +474,7 @@ class GenotypeStore:
         only.  ValueError, before anything is allocated, if the table (16 bytes per pair of plane rows) would exceed
         max_table_bytes (default 2 GiB)."""
         import torch
-        idx, queries = self._query("pair_counts", groups, samples, v_lo, v_hi, variant_mask)
-        scols, rows = plane_rows(idx, self.meta["sc"])
-        n_rows = len(scols) * self.meta["sc"]
-        limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
-        if n_rows * n_rows * 16 > limit:
-            raise ValueError(f"pair_counts: a table of {n_rows} x {n_rows} pairs ({n_rows * n_rows * 16} bytes) exceeds "
-                             f"max_table_bytes = {limit}")
+        idx, queries, n_rows, pick = self._pair_query("pair_counts", groups, samples, v_lo, v_hi, variant_mask, 16, max_table_bytes)
         ctx = self._context()
         table = torch.zeros((n_rows, n_rows, 4), dtype=torch.int32, device=ctx.device)
         for group, lo, hi, n_var, mask in queries:
@@ -450,8 +482,7 @@ class GenotypeStore:
                                                         plane_bytes, self._device_mask(mask, lo, n_var)):
                 ctx.pair_counts(planes, 0, words, table=table)
                 self.stats["pair_words"] += words
-        pick = torch.from_numpy(rows).to(ctx.device)
-        return table[pick][:, pick].contiguous()
+        return pick(table)
 
     def kinship(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
                 max_table_bytes=None):
@@ -475,22 +506,14 @@ class GenotypeStore:
         ValueError, before anything is allocated, if the two tables (16 + 8 bytes per pair of plane rows) would exceed
         max_table_bytes (default 2 GiB)."""
         import torch
-        idx, queries = self._query("grm_sums", groups, samples, v_lo, v_hi, variant_mask)
-        scols, rows = plane_rows(idx, self.meta["sc"])
-        n_rows = len(scols) * self.meta["sc"]
-        limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
-        if n_rows * n_rows * 24 > limit:
-            raise ValueError(f"grm_sums: tables of {n_rows} x {n_rows} pairs ({n_rows * n_rows * 24} bytes) exceed "
-                             f"max_table_bytes = {limit}")
-        ctx = self._context()
-        bs = self._blocksize()
+        idx, queries, n_rows, pick = self._pair_query("grm_sums", groups, samples, v_lo, v_hi, variant_mask, 24, max_table_bytes)
+        ctx, bs = self._context(), self._blocksize()
         counts = torch.zeros((n_rows, n_rows, 4), dtype=torch.int32, device=ctx.device)
         sums = torch.zeros((n_rows, n_rows), dtype=torch.float64, device=ctx.device)
         for group, lo, hi, n_var, mask in queries if n_rows else ():
             z, used = standardized_dosages(self.allele_counts(group, idx, lo, hi, slab_bytes))
             if mask is not None:
-                mask = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(mask, dtype=bool))
-                used = used & mask.to(ctx.device).to(torch.bool)
+                used = used & self._device_bool(mask)
             for a, b, words, planes in self._plane_walk(group, idx, lo, hi, n_var, "grm_plane_blocks", slab_bytes,
                                                         plane_bytes, self._device_mask(used, lo, n_var)):
                 d_z = torch.zeros((3, 32 * words), dtype=torch.float32, device=ctx.device)
@@ -498,8 +521,7 @@ class GenotypeStore:
                 ctx.pair_counts(planes, 0, words, table=counts)
                 ctx.grm(planes, d_z, 0, words, table=sums)
                 self.stats["grm_words"] += words
-        pick = torch.from_numpy(rows).to(ctx.device)
-        return sums[pick][:, pick].contiguous(), counts[..., NSNP][pick][:, pick].contiguous()
+        return pick(sums), pick(counts[..., NSNP])
 
     def grm(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
             max_table_bytes=None):
@@ -517,9 +539,7 @@ class GenotypeStore:
         n^3 on an n x n matrix, not the hot path, and needs no solver library on the device.  ValueError if k is outside
         1..n (before anything is computed) or a pair of samples has no jointly complete variant."""
         samples = None if samples is None else list(samples)
-        n = len(self.samples) if samples is None else len(samples)
-        if not 1 <= int(k) <= n:
-            raise ValueError(f"pca: k = {int(k)} (1 to {n})")
+        check_components(k, len(self.samples) if samples is None else len(samples))
         g = self.grm(groups, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes, max_table_bytes)
         return top_eigenpairs(g.cpu().numpy(), k)
 
@@ -551,9 +571,7 @@ class GenotypeStore:
         else:
             # the counted variants (offsets into the range) stay on the device; what comes back, in one copy for the whole
             # call, is how many of them lie before each plane window's end
-            mask = (variant_mask if torch.is_tensor(variant_mask) else
-                    torch.from_numpy(np.ascontiguousarray(variant_mask, dtype=bool))).to(ctx.device).to(torch.bool)
-            counted = torch.nonzero(mask).reshape(-1)
+            counted = torch.nonzero(self._device_bool(variant_mask)).reshape(-1)
             n_rows = len(plane_rows(idx, self.meta["sc"])[0]) * self.meta["sc"]
             budget = DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
             windows = plane_windows(lo, hi, bs, n_rows, budget) if n_rows else []
@@ -596,10 +614,7 @@ class GenotypeStore:
         window = int(window)
         lo, hi, _, n, rows = self._ld_rows("ld_counts", group, samples, v_lo, v_hi, variant_mask, window, slab_bytes,
                                               plane_bytes)
-        limit = MAX_PAIR_TABLE_BYTES if max_table_bytes is None else int(max_table_bytes)
-        if n * window * 32 > limit:
-            raise ValueError(f"ld_counts: a table of {n} x {window} pairs ({n * window * 32} bytes) exceeds "
-                             f"max_table_bytes = {limit}")
+        _table_budget("ld_counts", f"a table of {n} x {window} pairs ({{}} bytes) exceeds", n * window * 32, max_table_bytes)
         ctx = self._context()
         table = torch.zeros((n, window, 8), dtype=torch.int32, device=ctx.device)
         carry, k0 = None, 0                 # the last rows of the windows so far; the counted index of the next new row
@@ -754,23 +769,16 @@ class GenotypeStore:
             return np.zeros((0, 2), np.int8)
         return self.read_windows([(group, sample, 0, g["n_variants"])])[0].cpu().numpy()
 
-
     def snp_records(self, group, sample, v_lo=0, v_hi=None, tables=None):
         """the reference's per-donor compound records (vcf_to_h5.py:119-129), synthesised on demand; v_lo / v_hi: those
         of the group's variants [v_lo, v_hi) only (a windowed read); tables: variants(group), when the caller has it"""
-        start, ref, alt, runs = tables if tables is not None else self.variants(group)
-        n = len(start)
-        v_hi = n if v_hi is None else v_hi
-        if v_lo == 0 and v_hi == n:
+        tables = tables if tables is not None else self.variants(group)
+        v_hi = len(tables[0]) if v_hi is None else v_hi
+        if v_lo == 0 and v_hi == len(tables[0]):
             ph = self.sample_row(group, sample)
         else:
             ph = self.read_windows([(group, sample, v_lo, v_hi)])[0].cpu().numpy()
         rec = np.zeros(v_hi - v_lo, dtype=SNP_DTYPE)
-        rec["chrom"] = chrom_column(runs, n, v_lo, v_hi, 5)
-        rec["start"] = start[v_lo:v_hi]
-        rec["stop"] = start[v_lo:v_hi] + 1
-        rec["ref"] = ref[v_lo:v_hi].view("S1")
-        rec["alt"] = alt[v_lo:v_hi].view("S1")
-        rec["phase1"] = ph[:, 0]
-        rec["phase2"] = ph[:, 1]
+        variant_columns(rec, tables, 5, lo=v_lo, hi=v_hi)
+        rec["phase1"], rec["phase2"] = ph[:, 0], ph[:, 1]
         return rec

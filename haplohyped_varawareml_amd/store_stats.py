@@ -128,17 +128,22 @@ def grm_from_sums(S, N):
         return nan_unless(N != 0, f64(S) / f64(N))
 
 
+def check_components(k, n):
+    """int(k), the number of principal components asked of n samples: ValueError if it is outside 1..n"""
+    if not 1 <= int(k) <= n:
+        raise ValueError(f"pca: k = {int(k)} (1 to {n})")
+    return int(k)
+
+
 def top_eigenpairs(grm, k):
     """symmetric float64 [n, n] (host numpy) -> (values float64 [k], vectors float64 [n, k]): the k largest eigenpairs of
     numpy.linalg.eigh, in descending order; every vector of unit length as eigh returns it, its sign chosen so that its
     component of largest magnitude (the first such one) is positive.  ValueError if k is outside 1..n or the matrix holds
     a NaN (the message counts the pairs i <= j)."""
     g = np.asarray(grm, dtype=np.float64)
-    n, k = g.shape[0], int(k)
-    if g.ndim != 2 or g.shape[1] != n:
+    if g.ndim != 2 or g.shape[1] != g.shape[0]:
         raise ValueError(f"pca: a square matrix, not {g.shape}")
-    if not 1 <= k <= n:
-        raise ValueError(f"pca: k = {k} (1 to {n})")
+    n, k = g.shape[0], check_components(k, g.shape[0])
     bad = int(np.isnan(g[np.triu_indices(n)]).sum())
     if bad:
         raise ValueError(f"pca: {bad} pair(s) of samples have no jointly complete variant (NaN in the relationship matrix)")

@@ -8,7 +8,7 @@ import types
 import numpy as np
 import pytest
 
-from haplohyped_varawareml_amd.store import GenotypeStore, query_args
+from haplohyped_varawareml_amd.store import MAX_PAIR_TABLE_BYTES, GenotypeStore, _table_budget, query_args
 
 SAMPLES = [f"s{i}" for i in range(5)]
 BOTH = ["chr_1", "chr_2"]
@@ -103,3 +103,20 @@ def test_sample_indices_and_group_ranges(st):
     assert [x[0] for x in query_args(st.meta, index, "x", ["chr_2", "chr_1"])[1]] == ["chr_2", "chr_1"]
     m = np.ones(7, bool)
     assert query_args(st.meta, index, "x", "chr_1", None, 2, 9, m)[1][0][4] is m
+
+
+def test_table_budget():
+    for given, limit in ((1000, 1000), (None, MAX_PAIR_TABLE_BYTES)):
+        _table_budget("q", "a table of 5 x 5 pairs ({} bytes) exceeds", limit, given)
+        with pytest.raises(ValueError, match="max_table_bytes") as e:
+            _table_budget("q", "a table of 5 x 5 pairs ({} bytes) exceeds", limit + 1, given)
+        assert str(e.value) == f"q: a table of 5 x 5 pairs ({limit + 1} bytes) exceeds max_table_bytes = {limit}"
+
+
+def test_table_budget_messages_of_the_three_queries(st):
+    # 5 samples at sc = 2: 3 chunk rows, 6 plane rows; the budget fails before any device is asked for
+    for who, text in (("pair_counts", "pair_counts: a table of 6 x 6 pairs (576 bytes) exceeds max_table_bytes = 575"),
+                      ("grm_sums", "grm_sums: tables of 6 x 6 pairs (864 bytes) exceed max_table_bytes = 863")):
+        with pytest.raises(ValueError) as e:
+            getattr(st, who)("chr_1", max_table_bytes=int(text.split("= ")[1]))
+        assert str(e.value) == text

@@ -9,15 +9,12 @@ reduction of the int8 matrix), its ms and the bytes of matrix it writes; and hhg
 every chunk of the same group, the whole-chunk decode the fused kernel is measured against.  The fused and the naive
 counts are compared.
 usage: allele_count_bench.py [variants] [runs]"""
-import json, os, shutil, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import os, shutil, sys, tempfile
 import numpy as np
 import torch
-from haplohyped_varawareml_amd import device as dev, synth
-from haplohyped_varawareml_amd.reader import write_bgzf_native
+from cohort_bench import build_cohort, report, timed
+from haplohyped_varawareml_amd import device as dev
 from haplohyped_varawareml_amd.store import GenotypeStore
-from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
 RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -42,11 +39,8 @@ def measure(ctx, h5, idx):
     for _ in range(RUNS):
         st.stats.update(count_blocks=0, count_compressed_bytes_read=0)
         ctx.profile_reset()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        c = st.allele_counts(G, samples)
-        torch.cuda.synchronize()
-        call_ms.append((time.perf_counter() - t0) * 1e3)
+        c, ms = timed(lambda: st.allele_counts(G, samples))
+        call_ms.append(ms)
         kern_ms.append(ctx.profile_read()["decode"]["ms"])
         assert torch.equal(c, first)
     res = dict(kernel_ms=float(np.median(kern_ms)), call_ms=float(np.median(call_ms)),
@@ -56,11 +50,8 @@ def measure(ctx, h5, idx):
     st = GenotypeStore(h5, ctx=ctx, cache_bytes=1 << 40)
     nv_ms = []
     for _ in range(2):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        nv = naive(st, idx)
-        torch.cuda.synchronize()
-        nv_ms.append((time.perf_counter() - t0) * 1e3)
+        nv, ms = timed(lambda: naive(st, idx))
+        nv_ms.append(ms)
     res.update(naive_cold_ms=nv_ms[0], naive_warm_ms=nv_ms[1], naive_matrix_bytes=2 * V * len(idx),
                same_as_naive=bool(torch.equal(nv, first)))
     st.close()
@@ -71,14 +62,7 @@ def measure(ctx, h5, idx):
 tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     ctx = dev.Context(0)
-    tab = synth.variant_table(SEED, V, S)
-    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
-    os.makedirs(os.path.join(tmp, "vcf"))
-    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
-    del text
-    samples = os.path.join(tmp, "samples.txt")
-    open(samples, "w").write("\n".join(synth.sample_names(S)) + "\n")
-    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    h5 = build_cohort(ctx, tmp, V, S, SEED)
     ctx.profile(True)
     out = dict(samples=S, variants=V, runs=RUNS, all=measure(ctx, h5, np.arange(S)),
                subset64=measure(ctx, h5, np.sort(np.random.default_rng(3).choice(S, 64, replace=False))))
@@ -101,6 +85,6 @@ try:
                group_chunks=len(parts))
     out["all"]["kernel_vs_decode_blocks"] = out["all"]["kernel_ms"] / out["decode_blocks_kernel_ms"]
     st.close()
-    print(json.dumps(out))
+    report("allele_count_bench", out)
 finally:
     shutil.rmtree(tmp, ignore_errors=True)

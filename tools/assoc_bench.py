@@ -14,15 +14,12 @@ routes' statistics are compared: the same variants tested, the largest relative 
 asserted below 1e-6 (a BETA or T near 0 carries the absolute error of its sum).  Not timed: building and converting the
 cohort, the design on the host, the warm-up.
 usage: assoc_bench.py [variants] [runs]"""
-import json, os, shutil, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import os, shutil, sys, tempfile, time
 import numpy as np
 import torch
-from haplohyped_varawareml_amd import device as dev, synth
-from haplohyped_varawareml_amd.reader import write_bgzf_native
+from cohort_bench import build_cohort, report, summarize, timed
+from haplohyped_varawareml_amd import device as dev
 from haplohyped_varawareml_amd.store import ASSOC_P, GenotypeStore, assoc_design, student_t_two_sided
-from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
 RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -64,25 +61,10 @@ def torch_route(st, W, q, yy, times=None):
     return torch.where(tested[:, None, None], stats, torch.full_like(stats, float("nan")))
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return r, (time.perf_counter() - t0) * 1e3
-
-
 tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     ctx = dev.Context(0)
-    tab = synth.variant_table(SEED, V, S)
-    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
-    os.makedirs(os.path.join(tmp, "vcf"))
-    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
-    del text
-    samples = os.path.join(tmp, "samples.txt")
-    open(samples, "w").write("\n".join(synth.sample_names(S)) + "\n")
-    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    h5 = build_cohort(ctx, tmp, V, S, SEED)
     ctx.profile(True)
     rng = np.random.default_rng(SEED)
     cov, y = rng.normal(size=(S, COVARIATES)), rng.normal(size=S)
@@ -115,9 +97,8 @@ try:
         runs["planes_kernel_ms"].append(prof["decode"]["ms"])
         runs["transpose_kernel_ms"].append(prof["ld_transpose"]["ms"])
         runs["assoc_kernel_ms"].append(prof["assoc"]["ms"])
-    later = {k: v[1:] for k, v in runs.items()}                            # (the first repetition of a fresh box reads high)
-    out.update(runs_ms=runs, **{k: float(np.median(v)) for k, v in later.items()},
-               **{k.replace("_ms", "_spread"): float((max(v) - min(v)) / np.median(v)) for k, v in later.items()})
+    medians, spreads = summarize(runs)                  # (of every repetition but the first)
+    out.update(runs_ms=runs, **medians, **spreads)
     sw = -(-(-(-S // 64) * 64) // 32)
     mfma = 3 * -(-V // 16) * 8 * sw * -(-W.shape[1] // 16)
     out.update(plane_blocks_decoded=warm.stats["assoc_plane_blocks"], assoc_kernel_mfma=mfma,
@@ -126,9 +107,6 @@ try:
                call_cached_vs_torch_cached=out["call_cached_ms"] / out["torch_cached_ms"])
     warm.close()
     cold.close()
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    open(os.path.join(ROOT, "profiles", "assoc_bench.json"), "w").write(line + "\n")
+    report("assoc_bench", out)
 finally:
     shutil.rmtree(tmp, ignore_errors=True)

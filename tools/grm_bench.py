@@ -13,15 +13,12 @@ every run; the first repetition is printed but kept out of the medians.  Before 
 the store's S of the first 256 samples is asserted within the chain bound of a float64 product of the same Z.  Last,
 numpy.linalg.eigh of the matrix on the host, once.  Not timed: building and converting the cohort, the warm-up.
 usage: grm_bench.py [variants] [runs]"""
-import json, os, shutil, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import os, shutil, sys, tempfile, time
 import numpy as np
 import torch
-from haplohyped_varawareml_amd import device as dev, synth
-from haplohyped_varawareml_amd.reader import write_bgzf_native
+from cohort_bench import build_cohort, report, summarize, timed
+from haplohyped_varawareml_amd import device as dev
 from haplohyped_varawareml_amd.store import GRM_SPAN, GenotypeStore, grm_from_sums, standardized_dosages
-from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
 RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -59,25 +56,10 @@ def torch_route(st, times=None):
     return sums, N, Z
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return r, (time.perf_counter() - t0) * 1e3
-
-
 tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     ctx = dev.Context(0)
-    tab = synth.variant_table(SEED, V, S)
-    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
-    os.makedirs(os.path.join(tmp, "vcf"))
-    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
-    del text
-    samples = os.path.join(tmp, "samples.txt")
-    open(samples, "w").write("\n".join(synth.sample_names(S)) + "\n")
-    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    h5 = build_cohort(ctx, tmp, V, S, SEED)
     ctx.profile(True)
     out = dict(samples=S, variants=V, runs=RUNS, grm_span=GRM_SPAN)
 
@@ -113,9 +95,8 @@ try:
         runs["decode_kernels_ms"].append(prof["decode"]["ms"])
         runs["pairs_kernel_ms"].append(prof["pairs"]["ms"])
         runs["grm_kernel_ms"].append(prof["grm"]["ms"])
-    later = {k: v[1:] for k, v in runs.items()}                            # (the first repetition of a fresh box reads high)
-    out.update(runs_ms=runs, **{k: float(np.median(v)) for k, v in later.items()},
-               **{k.replace("_ms", "_spread"): float((max(v) - min(v)) / np.median(v)) for k, v in later.items()})
+    medians, spreads = summarize(runs)                  # (of every repetition but the first)
+    out.update(runs_ms=runs, **medians, **spreads)
     tiles = -(-S // 64)
     flop = 2.0 * (tiles * (tiles + 1) // 2) * 64 * 64 * 32 * warm.stats["grm_words"]
     out.update(planes_kernel_ms=out["decode_kernels_ms"] - out["count_kernel_ms"],
@@ -128,9 +109,6 @@ try:
     t0 = time.perf_counter()
     w = np.linalg.eigh(grm)[0]
     out.update(host_eigh_ms=(time.perf_counter() - t0) * 1e3, largest_eigenvalue=float(w[-1]))
-    line = json.dumps(out)
-    print(line)
-    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-    open(os.path.join(ROOT, "profiles", "grm_bench.json"), "w").write(line + "\n")
+    report("grm_bench", out)
 finally:
     shutil.rmtree(tmp, ignore_errors=True)

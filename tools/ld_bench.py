@@ -13,15 +13,12 @@ the medians.  The torch mask is asserted equal to ld_prune's before any time is 
 are independent, so nearly every variant is kept: the cost does not depend on that, the kept count is reported.  Not timed:
 building and converting the cohort, the warm-up.
 usage: ld_bench.py [variants] [runs]"""
-import json, os, shutil, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import os, shutil, sys, tempfile, time
 import numpy as np
 import torch
-from haplohyped_varawareml_amd import device as dev, synth
-from haplohyped_varawareml_amd.reader import write_bgzf_native
+from cohort_bench import build_cohort, report, summarize, timed
+from haplohyped_varawareml_amd import device as dev
 from haplohyped_varawareml_amd.store import GenotypeStore
-from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
 RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -60,25 +57,10 @@ def torch_route(st):
     return keep
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return r, (time.perf_counter() - t0) * 1e3
-
-
 tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     ctx = dev.Context(0)
-    tab = synth.variant_table(SEED, V, S)
-    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
-    os.makedirs(os.path.join(tmp, "vcf"))
-    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
-    del text
-    samples = os.path.join(tmp, "samples.txt")
-    open(samples, "w").write("\n".join(synth.sample_names(S)) + "\n")
-    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    h5 = build_cohort(ctx, tmp, V, S, SEED)
     ctx.profile(True)
     out = dict(date=time.strftime("%Y-%m-%d"), samples=S, variants=V, window=WINDOW, r2=R2, runs=RUNS)
 
@@ -103,17 +85,12 @@ try:
         prof = ctx.profile_read()
         for k, stage in stages.items():
             runs[k].append(prof[stage]["ms"])
-    later = {k: v[1:] for k, v in runs.items()}                            # (the first repetition of a fresh box reads high)
-    out.update(runs_ms=runs, **{k: float(np.median(v)) for k, v in later.items()},
-               **{k.replace("_ms", "_spread"): float((max(v) - min(v)) / np.median(v)) for k, v in later.items()})
+    medians, spreads = summarize(runs)                  # (of every repetition but the first)
+    out.update(runs_ms=runs, **medians, **spreads)
     out.update(plane_blocks_decoded=warm.stats["ld_plane_blocks"], pairs_counted=warm.stats["ld_pairs"],
                call_cached_vs_torch_cached=out["call_cached_ms"] / out["torch_cached_ms"])
     warm.close()
     cold.close()
-    line = json.dumps(out)
-    print(line)
-    dst = os.path.join(ROOT, os.environ.get("HHGT_LD_BENCH_OUT", os.path.join("profiles", "ld_bench.json")))
-    os.makedirs(os.path.dirname(dst), exist_ok=True)
-    open(dst, "w").write(line + "\n")
+    report("ld_bench", out)
 finally:
     shutil.rmtree(tmp, ignore_errors=True)

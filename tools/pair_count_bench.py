@@ -10,15 +10,11 @@ S x S x V products in variant slabs with fp32 accumulation (0 / 1 operands: exac
 Medians of the runs and every run; the first repetition is printed but kept out of the medians.  The torch table is
 asserted equal to pair_counts' before any time is taken.  Not timed: building and converting the cohort, the warm-up.
 usage: pair_count_bench.py [variants] [runs]"""
-import json, os, shutil, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import numpy as np
+import os, shutil, sys, tempfile
 import torch
-from haplohyped_varawareml_amd import device as dev, synth
-from haplohyped_varawareml_amd.reader import write_bgzf_native
+from cohort_bench import build_cohort, report, summarize, timed
+from haplohyped_varawareml_amd import device as dev
 from haplohyped_varawareml_amd.store import GenotypeStore
-from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
 RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -50,25 +46,10 @@ def torch_route(st):
     return t
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return r, (time.perf_counter() - t0) * 1e3
-
-
 tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     ctx = dev.Context(0)
-    tab = synth.variant_table(SEED, V, S)
-    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
-    os.makedirs(os.path.join(tmp, "vcf"))
-    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
-    del text
-    samples = os.path.join(tmp, "samples.txt")
-    open(samples, "w").write("\n".join(synth.sample_names(S)) + "\n")
-    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    h5 = build_cohort(ctx, tmp, V, S, SEED)
     ctx.profile(True)
     out = dict(samples=S, variants=V, runs=RUNS, product_slab_variants=SLAB)
 
@@ -91,13 +72,12 @@ try:
         prof = ctx.profile_read()
         runs["planes_kernel_ms"].append(prof["decode"]["ms"])
         runs["pairs_kernel_ms"].append(prof["pairs"]["ms"])
-    later = {k: v[1:] for k, v in runs.items()}                            # (the first repetition of a fresh box reads high)
-    out.update(runs_ms=runs, **{k: float(np.median(v)) for k, v in later.items()},
-               **{k.replace("_ms", "_spread"): float((max(v) - min(v)) / np.median(v)) for k, v in later.items()})
+    medians, spreads = summarize(runs)                  # (of every repetition but the first)
+    out.update(runs_ms=runs, **medians, **spreads)
     out.update(plane_blocks_decoded=warm.stats["pair_plane_blocks"], plane_words_per_row=warm.stats["pair_words"],
                call_cached_vs_torch_cached=out["call_cached_ms"] / out["torch_cached_ms"])
     warm.close()
     cold.close()
-    print(json.dumps(out))
+    report("pair_count_bench", out)
 finally:
     shutil.rmtree(tmp, ignore_errors=True)

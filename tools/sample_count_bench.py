@@ -12,15 +12,12 @@ k_count_alleles on the same selections and k_decode_blocks on the same chunks (k
 and the first, slower, repetition can be seen).  The fused counts are asserted equal to the naive ones before any
 time is printed.
 usage: sample_count_bench.py [variants] [runs]"""
-import json, os, shutil, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import os, shutil, sys, tempfile
 import numpy as np
 import torch
-from haplohyped_varawareml_amd import device as dev, synth
-from haplohyped_varawareml_amd.reader import write_bgzf_native
+from cohort_bench import build_cohort, report, summarize, timed
+from haplohyped_varawareml_amd import device as dev
 from haplohyped_varawareml_amd.store import GenotypeStore
-from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
 RUNS = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -42,14 +39,6 @@ def naive(st, idx, keep=None):
     return torch.cat(out)
 
 
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    r = fn()
-    torch.cuda.synchronize()
-    return r, (time.perf_counter() - t0) * 1e3
-
-
 def kernel_ms(ctx, fn):
     ctx.profile_reset()
     r = fn()
@@ -59,14 +48,7 @@ def kernel_ms(ctx, fn):
 tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     ctx = dev.Context(0)
-    tab = synth.variant_table(SEED, V, S)
-    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
-    os.makedirs(os.path.join(tmp, "vcf"))
-    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
-    del text
-    samples = os.path.join(tmp, "samples.txt")
-    open(samples, "w").write("\n".join(synth.sample_names(S)) + "\n")
-    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    h5 = build_cohort(ctx, tmp, V, S, SEED)
     ctx.profile(True)
     every, sub = np.arange(S), np.sort(np.random.default_rng(3).choice(S, 64, replace=False))
     out = dict(samples=S, variants=V, runs=RUNS)
@@ -124,9 +106,8 @@ try:
         (_, bad), ms = kernel_ms(ctx, lambda: ctx.decompress(src, d_off, len(parts), cn, typesize=2, blocksize=bs))
         assert bad == 0
         runs["decode_blocks"].append(ms)
-    later = {k: v[1:] for k, v in runs.items()}                            # (the first repetition of a fresh box reads high)
-    out["kernels"] = dict(runs_ms=runs, **{k + "_ms": float(np.median(v)) for k, v in later.items()},
-                          **{k + "_spread": float((max(v) - min(v)) / np.median(v)) for k, v in later.items()})
+    medians, spreads = summarize(runs)                  # (of every repetition but the first)
+    out["kernels"] = dict(runs_ms=runs, **medians, **spreads)
     out["kernels"]["count_samples_vs_count_alleles"] = out["kernels"]["count_samples_ms"] / out["kernels"]["count_alleles_ms"]
     out["kernels"]["count_samples_vs_decode_blocks"] = out["kernels"]["count_samples_ms"] / out["kernels"]["decode_blocks_ms"]
     out["call_cold_vs_naive_cold"] = out["all"]["call_cold_ms"] / naive_cold
@@ -134,6 +115,6 @@ try:
     out.update(group_compressed_bytes=int(rel[-1]), group_chunks=len(parts))
     warm.close()
     cold.close()
-    print(json.dumps(out))
+    report("sample_count_bench", out)
 finally:
     shutil.rmtree(tmp, ignore_errors=True)

@@ -8,16 +8,13 @@ and one-hot kernel ms (ctx.profile_read()); the one-hot write rate against 8 TB/
 whole-chunk-row decode the store used before windowed reads (every chunk of the donor's 64-sample chunk row decoded with
 hhgt_decompress_chunks, one sample kept, copied to the host and back), rebuilt here as the comparison point.
 usage: window_bench.py [variants] [batches]"""
-import json, os, shutil, sys, tempfile, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import os, shutil, sys, tempfile, time
 import numpy as np
 import torch
+from cohort_bench import build_cohort, report
 from haplohyped_varawareml_amd import device as dev, synth
 from haplohyped_varawareml_amd.dataset import RandomHaplotypeDataset
-from haplohyped_varawareml_amd.reader import write_bgzf_native
 from haplohyped_varawareml_amd.store import GenotypeStore
-from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
 V = int(sys.argv[1]) if len(sys.argv) > 1 else 230_000
 NB = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -25,17 +22,10 @@ S, B, L, SEED = 2504, 32, 131072, 1001
 tmp = tempfile.mkdtemp(dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
 try:
     ctx = dev.Context(0)
-    tab = synth.variant_table(SEED, V, S)
-    text, n = ctx.synth_fixed("chr1", tab, S, seed=SEED)
-    os.makedirs(os.path.join(tmp, "vcf"))
-    write_bgzf_native(os.path.join(tmp, "vcf", "chr1.filtered.vcf.gz"), text[:n].cpu().numpy())
-    del text
-    names = synth.sample_names(S)
-    samples = os.path.join(tmp, "samples.txt")
-    open(samples, "w").write("\n".join(names) + "\n")
-    h5 = VCFtoHDF5Converter("c", os.path.join(tmp, "vcf"), os.path.join(tmp, "out"), samples, 2, 1).run()
+    h5 = build_cohort(ctx, tmp, V, S, SEED)
+    names, samples = synth.sample_names(S), os.path.join(tmp, "samples.txt")
     rng = np.random.default_rng(5)
-    span = int(tab["pos"][-1]) + 1000
+    span = int(synth.variant_table(SEED, V, S)["pos"][-1]) + 1000
     np.savez(os.path.join(tmp, "ref.npz"), chr1=np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, span)])
     bed = os.path.join(tmp, "regions.bed")
     with open(bed, "w") as f:
@@ -119,6 +109,6 @@ try:
                decoded_bytes_ratio=old_decoded / max(float(np.mean(decoded)), 1.0),
                cold_target_5ms_met=bool(np.median(cold_ms) <= 5.0))
     ds.close()
-    print(json.dumps(res))
+    report("window_bench", res)
 finally:
     shutil.rmtree(tmp, ignore_errors=True)
