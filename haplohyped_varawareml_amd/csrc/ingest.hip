@@ -20,6 +20,7 @@
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -74,9 +75,35 @@ template <class T> struct BQ {
     }
 };
 
-struct PinnedBuf {   // grows on demand; pinned allocations are slow, so they only ever grow
+// What the engine holds on the device and in pinned memory.  Each holder's own code is the only place its resource is released,
+// and none can be copied: a slot cannot free what another still uses.  hhgt_ingest_close synchronises the streams, then deletes.
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+struct Event : NoCopy {
+    hipEvent_t e = nullptr;
+    ~Event() { if (e) hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+struct Stream : NoCopy {
+    hipStream_t s = nullptr;
+    ~Stream() { if (s) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+struct DevMem : DevBuf, NoCopy {   // common.h's DevBuf has no destructor: the context shares it
+    ~DevMem() { release(); }
+};
+template <class T> struct PinnedRec : NoCopy {   // one pinned record
+    T *p = nullptr;
+    ~PinnedRec() { if (p) hipHostFree(p); }
+    operator T *() const { return p; }
+};
+struct PinnedBuf : NoCopy {   // grows on demand; pinned allocations are slow, so they only ever grow
     uint8_t *p = nullptr;
     size_t cap = 0;
+    ~PinnedBuf() { if (p) hipHostFree(p); }
     int ensure(size_t n)
     {
         if (n <= cap) return HHGT_OK;
@@ -85,9 +112,7 @@ struct PinnedBuf {   // grows on demand; pinned allocations are slow, so they on
         cap = 0;
         const size_t want = n + n / 4 + 4096;
         static const bool dbg = getenv("HHGT_ALLOC_DEBUG") != nullptr;
-        if (dbg)
-            fprintf(stderr, "[alloc] %.3f ms  hipHostMalloc %zu\n",
-                    std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() * 1e3, want);
+        if (dbg) fprintf(stderr, "[alloc] %.3f ms  hipHostMalloc %zu\n", now_s() * 1e3, want);
         if (hipHostMalloc(reinterpret_cast<void **>(&p), want, hipHostMallocDefault) != hipSuccess) {
             p = nullptr;
             hhgt_set_error("ingest: hipHostMalloc(%zu) failed", want);
@@ -95,12 +120,6 @@ struct PinnedBuf {   // grows on demand; pinned allocations are slow, so they on
         }
         cap = want;
         return HHGT_OK;
-    }
-    void release()
-    {
-        if (p) hipHostFree(p);
-        p = nullptr;
-        cap = 0;
     }
 };
 
@@ -119,28 +138,29 @@ struct Input {
     hhgt_ingest_stats st;
     double t_first = 0;
     std::string last_run;
-    void *state = nullptr;       // hhgt_ingest::InState of this input (driver thread)
+    struct InState *state = nullptr;   // encode state of this input (driver thread)
     bool header_sent = false;
     Input() { memset(&st, 0, sizeof(st)); }
 };
 
-struct TextBuf {   // device-resident text block
-    uint8_t *d = nullptr;
+struct TextBuf : NoCopy {   // device-resident text block
+    uint8_t *d = nullptr;   // sized to the byte by open and take_text, so freed here
     size_t cap = 0;
-    hipEvent_t ready = nullptr, carry_done = nullptr;
+    Event ready, carry_done;
     uint64_t nbytes = 0;
     Input *in = nullptr;
     bool first = false, last = false;
     // device-side inflate: per-member status and the count of failures (checked at harvest)
-    DevBuf status, bad;
-    unsigned long long *h_bad = nullptr;   // pinned
+    DevMem status, bad;
+    PinnedRec<unsigned long long> h_bad;
     uint64_t n_members = 0, first_member = 0;
+    ~TextBuf() { if (d) hipFree(d); }
 };
 
 struct Staging {   // device-inflate: one block's compressed bytes + member tables, host (pinned) and device
     PinnedBuf h;
-    DevBuf d;
-    hipEvent_t done = nullptr;   // the inflate that read the device copy has finished
+    DevMem d;
+    Event done;   // the inflate that read the device copy has finished
     bool used = false;
 };
 
@@ -149,7 +169,7 @@ enum { B_VARIANTS = 2, B_COLUMNS = 3, B_INPUT_END = 4, B_HEADER = 1, B_END = 0 }
 struct Batch {
     int kind = 0;
     Input *in = nullptr;
-    hipEvent_t ev = nullptr;   // recorded on the main stream behind the batch's device work
+    hipEvent_t ev = nullptr;   // recorded on the main stream behind the batch's device work (one of batch_events)
     // VARIANTS
     int var_slot = -1;
     uint64_t first_variant = 0, n_variants = 0;
@@ -157,6 +177,7 @@ struct Batch {
     // COLUMNS
     int dst_slot = -1, out_slot = -1;
     uint64_t n_chunks = 0, first_col = 0, n_cols = 0, raw_bytes = 0, framed_bytes = 0;
+    Batch(int kind_ = B_END, Input *in_ = nullptr) : kind(kind_), in(in_) {}
 };
 
 struct VarSlot {
@@ -165,7 +186,7 @@ struct VarSlot {
     char run_names[MAX_CHROM_RUNS][32];
 };
 struct DstSlot {
-    DevBuf d, off;          // framed bytes, chunk_off (device)
+    DevMem d, off;          // framed bytes, chunk_off (device)
     PinnedBuf h_off;        // chunk_off (host)
 };
 struct OutSlot {
@@ -181,16 +202,63 @@ struct OutSlot {
 #define N_OUT 5
 #define N_STG 4   // device-inflate staging slots: one per text buffer, so the source never waits for an inflate two blocks back
 
+// encode state of an input (driver thread only).  The ring holds the matrix as int8 or as bit planes; the four calls at the end
+// are the only places that choose between the two kernel families
+struct InState {
+    hhgt_layout lay;
+    DevMem G, P, t_start, t_ref, t_alt, cursor;
+    bool planes = false;   // the ring holds the matrix as bit planes (include/hhgt.h "Bit-plane form"); G only backs calls beyond 0 / 1 / missing
+    uint64_t ring_cols = 0, col_bytes = 0, n_sc = 0, chunk_nbytes = 0, kept_per_block = 0, done_cols = 0;
+
+    int encode(hhgt_ctx *ctx, const TextBuf &tb, uint32_t max_lines, hhgt_encode_result *rec, hipStream_t s)   // a text block, at the cursor
+    {
+        const char *region = tb.in->region.c_str();
+        uint64_t *cur = cursor.as<uint64_t>();
+        uint32_t *start = t_start.as<uint32_t>();
+        uint8_t *ref = t_ref.as<uint8_t>(), *alt = t_alt.as<uint8_t>();
+        return planes ? hhgt_encode_text_planes_async(ctx, tb.d, tb.nbytes, region, &lay, cur, max_lines, P.p, G.p, start, nullptr, ref, alt, rec, s)
+                      : hhgt_encode_text_async(ctx, tb.d, tb.nbytes, region, &lay, cur, max_lines, G.p, start, nullptr, ref, alt, rec, s);
+    }
+    int compress(hhgt_ctx *ctx, const hhgt_ingest_opts &o, uint64_t slot, uint64_t n, DstSlot &d, hipStream_t s)   // ring slots [slot, slot + n)
+    {
+        uint64_t *off = d.off.as<uint64_t>();
+        return planes ? hhgt_compress_planes(ctx, &lay, P.p, G.p, (uint32_t)slot, (uint32_t)n, o.format, d.d.p, d.d.cap, off, nullptr, s)
+                      : hhgt_compress_chunks(ctx, G.as<uint8_t>() + slot * col_bytes, n * n_sc, chunk_nbytes, o.typesize, o.blocksize, o.format,
+                                             d.d.p, d.d.cap, off, nullptr, s);
+    }
+    int pad_samples(hhgt_ctx *ctx, hipStream_t s)   // zero the sample padding rows (S .. round_up(S, sc)) of every ring column
+    {
+        return planes ? hhgt_pad_tail_planes(ctx, &lay, lay.v_capacity, 0, ring_cols, P.p, s)
+                      : hhgt_pad_tail(ctx, &lay, lay.v_capacity, 0, ring_cols, G.p, s);
+    }
+    int pad_open_column(hhgt_ctx *ctx, hipStream_t s)   // zero the open column behind the cursor
+    {
+        return planes ? hhgt_pad_tail_planes_cursor(ctx, &lay, cursor.as<uint64_t>(), P.p, s)
+                      : hhgt_pad_tail_cursor(ctx, &lay, cursor.as<uint64_t>(), G.p, s);
+    }
+};
+
+struct Res {   // result slot of an encoded block
+    PinnedRec<hhgt_encode_result> rec;
+    // the block's whole CHROM run table (MAX_CHROM_RUNS entries; the record holds the first HHGT_RESULT_RUNS): copied out of
+    // the context's scratch on the main stream right behind the encode, before the next block's encode overwrites it
+    DevMem run_first, run_names;
+    Event ev;
+    int text_idx = -1;
+};
+
 }  // namespace
 
 struct hhgt_ingest {
     hhgt_ctx *ctx = nullptr;
     hhgt_ingest_opts o;
     int device = 0;
-    hipStream_t s_main = nullptr, s_copy = nullptr, s_inf = nullptr, s_out = nullptr;
+    // The streams stand first: every buffer and event below is released before them.
+    Stream s_main, s_copy, s_inf, s_out;
     // device inflate: the blocks alternate between s_inf and s_inf2 (one wave per member is latency-bound: the tail round of
     // one block's launch overlaps the next block's), the few bytes behind a block's last newline move on s_carry
-    hipStream_t s_inf2 = nullptr, s_carry = nullptr;
+    Stream s_inf2, s_carry;
+    std::array<hipStream_t, 6> streams() const { return {s_main.s, s_copy.s, s_inf.s, s_inf2.s, s_carry.s, s_out.s}; }
     uint64_t inf_blocks = 0;              // source thread only
     hipEvent_t last_carry = nullptr;      // the latest carry copy queued (an event of some TextBuf), or null
     // inputs
@@ -232,40 +300,26 @@ struct hhgt_ingest {
             return true;
         }
     } mtab;
-    DevBuf crc_x2n;
-    // encode state of an input (driver thread only).  Two sets, used alternately: the first blocks of input k+1 are
-    // encoded while the last blocks of input k are still being harvested, so the GPU's queue does not drain at a
-    // file boundary
-    struct InState {
-        hhgt_layout lay;
-        DevBuf G, P, t_start, t_ref, t_alt, cursor;
-        bool planes = false;   // the ring holds the matrix as bit planes (include/hhgt.h "Bit-plane form"); G only backs calls beyond 0 / 1 / missing
-        uint64_t ring_cols = 0, col_bytes = 0, n_sc = 0, chunk_nbytes = 0, kept_per_block = 0, done_cols = 0, host_cursor = 0;
-    } ist[2];
+    DevMem crc_x2n;
+    // Two encode states, used alternately: the first blocks of input k+1 are encoded while the last blocks of input k are still
+    // being harvested, so the GPU's queue does not drain at a file boundary
+    InState ist[2];
     uint64_t n_begun = 0;
-    struct Res {
-        hhgt_encode_result *rec = nullptr;   // pinned
-        // the block's whole CHROM run table (MAX_CHROM_RUNS entries; the record holds the first HHGT_RESULT_RUNS): copied out of
-        // the context's scratch on the main stream right behind the encode, before the next block's encode overwrites it
-        DevBuf run_first, run_names;
-        hipEvent_t ev = nullptr;
-        int text_idx = -1;
-        InState *st = nullptr;
-    } res[N_RES];
+    Res res[N_RES];
     // slot pools
     VarSlot var[N_VAR];
     DstSlot dst[N_DST];
     OutSlot out[N_OUT];
     BQ<int> free_var, free_dst, free_out;
-    std::vector<hipEvent_t> batch_events;
+    Event batch_events[N_VAR + N_DST + 4];
     BQ<hipEvent_t> free_ev;
     // stages
     BQ<Batch> q_ship, q_out;
     std::thread th_source, th_driver, th_ship;
-    // where the threads spend their time (seconds; HHGT_INGEST_DEBUG=1 prints them at close)
+    // where the threads spend their time (seconds; HHGT_INGEST_DEBUG prints them at the end of each input)
     struct Times {
         double src_wait_text = 0, src_work = 0, drv_wait_text = 0, drv_launch = 0, drv_harvest_wait = 0, drv_harvest = 0,
-               drv_begin = 0, ship_wait_ev = 0, ship_copy = 0, ship_wait_out = 0, t_open = 0, t_first_text = 0, t_end = 0;
+               drv_begin = 0, ship_wait_ev = 0, ship_copy = 0, ship_wait_out = 0;
     } tm;
     // consumer side: what the previous hhgt_ingest_next handed out
     Batch held;
@@ -325,21 +379,14 @@ bool fail(hhgt_ingest *g, int code, const char *msg)
     return false;
 }
 
-#define G_TRY(expr)                                  \
-    do {                                             \
-        int _rc = (expr);                            \
-        if (_rc != HHGT_OK) {                        \
-            return fail(g, _rc, hhgt_last_error());  \
-        }                                            \
-    } while (0)
-#define G_HIP(expr)                                                                                 \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            hhgt_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            return fail(g, HHGT_ERR_HIP, hhgt_last_error());                                        \
-        }                                                                                           \
-    } while (0)
+// error exits.  G_*: in the threads, through fail().  OPEN_*: in the steps of hhgt_ingest_open, which return HHGT_OK or the code of
+// what failed, the message in hhgt_last_error
+#define G_TRY(expr) do { int _rc = (expr); if (_rc != HHGT_OK) return fail(g, _rc, hhgt_last_error()); } while (0)
+#define G_HIP(expr) \
+    do { hipError_t _e = (expr); if (_e != hipSuccess) { hhgt_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); return fail(g, HHGT_ERR_HIP, hhgt_last_error()); } } while (0)
+#define OPEN_TRY(expr) do { int _rc = (expr); if (_rc != HHGT_OK) return _rc; } while (0)
+#define OPEN_HIP(expr, what) \
+    do { hipError_t _e = (expr); if (_e != hipSuccess) { hhgt_set_error("ingest: %s failed: %s", what, hipGetErrorString(_e)); return HHGT_ERR_HIP; } } while (0)
 
 // '#' lines at the start of `p`: bytes, line count, number of sample columns.  false: no complete header in [p, p+n)
 bool parse_header_text(const uint8_t *p, size_t n, size_t *header_bytes, uint64_t *n_samples, bool at_eof)
@@ -409,10 +456,6 @@ bool wants_device_inflate(int mode, const char *path)
 struct Fd {
     int fd = -1;
     ~Fd() { if (fd >= 0) close(fd); }
-};
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() { if (e) hipEventDestroy(e); }
 };
 struct Inflater {   // host zlib, raw DEFLATE: one BGZF member per call
     z_stream zs;
@@ -937,10 +980,41 @@ void source_main(hhgt_ingest *g)
 // ---------------------------------------------------------------------------------------------------------------
 // driver thread
 // ---------------------------------------------------------------------------------------------------------------
+// The batch slots for blocks that keep up to `kept` records.  They may still be in use by batches of the previous input that
+// are on their way out, so when one has to grow (this input has more samples, or is the first) every slot is collected first —
+// the shipper and the consumer give them back as they go; at open all of them sit in their pools — and returned afterwards.
+static bool grow_batch_slots(hhgt_ingest *g, size_t need_d, size_t need_off, size_t kept)
+{
+    const size_t need_start = kept * 4 + 16, need_base = kept + 4;   // k_tables_to_host writes whole groups of four
+    bool grow = false;
+    for (auto &d : g->dst) grow = grow || d.d.cap < need_d || d.off.cap < need_off || d.h_off.cap < need_off;
+    for (auto &v : g->var) grow = grow || v.start.cap < need_start || v.ref.cap < need_base;
+    if (grow) {
+        int tmp;
+        for (int i = 0; i < N_DST; ++i)
+            if (!g->free_dst.pop(tmp)) return false;
+        for (int i = 0; i < N_VAR; ++i)
+            if (!g->free_var.pop(tmp)) return false;
+        for (auto &d : g->dst) {
+            G_TRY(d.d.ensure(need_d));
+            G_TRY(d.off.ensure(need_off));
+            G_TRY(d.h_off.ensure(need_off));
+        }
+        for (auto &v : g->var) {
+            G_TRY(v.start.ensure(need_start));
+            G_TRY(v.ref.ensure(need_base));
+            G_TRY(v.alt.ensure(need_base));
+        }
+        for (int i = 0; i < N_DST; ++i) g->free_dst.push(i);
+        for (int i = 0; i < N_VAR; ++i) g->free_var.push(i);
+    }
+    return true;
+}
+
 // geometry of an input's ring + every buffer whose size follows from the sample count: the state's own (ring of chunk columns
 // as planes / int8, variant tables, cursor) and the batch slots.  at_open: called from hhgt_ingest_open with the caller's
-// expect_samples, when every slot still sits in its pool — so that the first input finds its buffers made (and pinned).
-static bool size_input_state(hhgt_ingest *g, hhgt_ingest::InState *X, uint64_t S, uint64_t S_file, uint64_t block_bytes, bool at_open)
+// expect_samples, so that the first input finds its buffers made (and pinned) — the shipper's pinned copies among them.
+static bool size_input_state(hhgt_ingest *g, InState *X, uint64_t S, uint64_t S_file, uint64_t block_bytes, bool at_open)
 {
     const int32_t sc = g->o.sc, vc = g->o.vc;
     // a kept line holds S sample columns of at least two bytes behind nine fixed columns
@@ -949,12 +1023,7 @@ static bool size_input_state(hhgt_ingest *g, hhgt_ingest::InState *X, uint64_t S
     X->kept_per_block = block_bytes / (2 * S_file + 16) + 2;
     const uint64_t W = X->kept_per_block / (uint64_t)vc + 2;   // chunk columns one block can touch
     X->ring_cols = 2 * W + 6;
-    memset(&X->lay, 0, sizeof(X->lay));
-    X->lay.n_samples = (int32_t)S;
-    X->lay.sc = sc;
-    X->lay.vc = vc;
-    X->lay.ring = (int32_t)X->ring_cols;
-    X->lay.v_capacity = X->ring_cols * (uint64_t)vc;
+    X->lay = hhgt_layout{(int32_t)S, sc, vc, (int32_t)X->ring_cols, X->ring_cols * (uint64_t)vc};   // a ring of ring_cols chunk columns
     X->n_sc = S ? (S + (uint64_t)sc - 1) / (uint64_t)sc : 0;
     X->chunk_nbytes = (uint64_t)sc * (uint64_t)vc * 2;
     X->col_bytes = X->n_sc * X->chunk_nbytes;
@@ -969,37 +1038,9 @@ static bool size_input_state(hhgt_ingest *g, hhgt_ingest::InState *X, uint64_t S
     G_TRY(X->t_ref.ensure((size_t)X->lay.v_capacity));
     G_TRY(X->t_alt.ensure((size_t)X->lay.v_capacity));
     G_TRY(X->cursor.ensure(8));
-    // batch buffers.  They may still be in use by batches of the previous input that are on their way out, so when
-    // one has to grow (this input has more samples, or is the first) every slot is collected first — the shipper and
-    // the consumer give them back as they go — and returned to the pools afterwards.
     const uint64_t max_cols = W + 2;
     const size_t need_d = (size_t)(max_cols * X->n_sc * (X->chunk_nbytes + 32) + 64), need_off = (size_t)((max_cols * X->n_sc + 1) * 8);
-    bool grow = false;
-    for (auto &d : g->dst) grow = grow || d.d.cap < need_d || d.off.cap < need_off || d.h_off.cap < need_off;
-    for (auto &v : g->var) grow = grow || v.start.cap < (size_t)X->kept_per_block * 4 + 16 || v.ref.cap < (size_t)X->kept_per_block + 4;
-    if (grow) {
-        int tmp;
-        if (!at_open) {
-            for (int i = 0; i < N_DST; ++i)
-                if (!g->free_dst.pop(tmp)) return false;
-            for (int i = 0; i < N_VAR; ++i)
-                if (!g->free_var.pop(tmp)) return false;
-        }
-        for (auto &d : g->dst) {
-            G_TRY(d.d.ensure(need_d));
-            G_TRY(d.off.ensure(need_off));
-            G_TRY(d.h_off.ensure(need_off));
-        }
-        for (auto &v : g->var) {
-            G_TRY(v.start.ensure((size_t)X->kept_per_block * 4 + 16));   // k_tables_to_host writes whole groups of four
-            G_TRY(v.ref.ensure((size_t)X->kept_per_block + 4));
-            G_TRY(v.alt.ensure((size_t)X->kept_per_block + 4));
-        }
-        if (!at_open) {
-            for (int i = 0; i < N_DST; ++i) g->free_dst.push(i);
-            for (int i = 0; i < N_VAR; ++i) g->free_var.push(i);
-        }
-    }
+    if (!grow_batch_slots(g, need_d, need_off, (size_t)X->kept_per_block)) return false;
     if (at_open) {
         // the shipper's pinned copies of the framed chunks: a batch is at most need_d bytes and about a fifth of that on
         // genotype planes — a slot that turns out too small still grows where it is used
@@ -1010,23 +1051,15 @@ static bool size_input_state(hhgt_ingest *g, hhgt_ingest::InState *X, uint64_t S
 
 bool begin_input(hhgt_ingest *g, Input *in, uint64_t block_bytes)
 {
-    hhgt_ingest::InState *X = &g->ist[g->n_begun++ & 1u];
+    InState *X = &g->ist[g->n_begun++ & 1u];
     in->state = X;
-    const uint64_t S = in->S;
-    if (!size_input_state(g, X, S, in->S_file, block_bytes, false)) return false;
-    const uint64_t gbytes = hhgt_layout_bytes(&X->lay);
-    const int32_t sc = g->o.sc;
+    if (!size_input_state(g, X, in->S, in->S_file, block_bytes, false)) return false;
     // sample padding rows (S .. round_up(S, sc)) are never written by the encoder: zeroed once per input for every
     // ring column (everything else of a column is overwritten, or zeroed by the tail padding, before it is framed)
-    if (gbytes && S % (uint64_t)sc) {
-        if (X->planes) G_TRY(hhgt_pad_tail_planes(g->ctx, &X->lay, X->lay.v_capacity, 0, X->ring_cols, X->P.p, g->s_main));
-        else G_TRY(hhgt_pad_tail(g->ctx, &X->lay, X->lay.v_capacity, 0, X->ring_cols, X->G.p, g->s_main));
-    }
+    if (hhgt_layout_bytes(&X->lay) && in->S % (uint64_t)g->o.sc) G_TRY(X->pad_samples(g->ctx, g->s_main));
     G_HIP(hipMemsetAsync(X->cursor.p, 0, 8, g->s_main));
     X->done_cols = 0;
-    X->host_cursor = 0;
     in->t_first = now_s();
-    in->header_sent = false;   // announced by the first harvest of this input: behind the previous input's last events
     return true;
 }
 
@@ -1055,35 +1088,22 @@ __global__ void __launch_bounds__(256) k_tables_to_host(const uint32_t *__restri
     h_alt[i] = al;
 }
 
-bool get_event(hhgt_ingest *g, hipEvent_t *ev)
-{
-    return g->free_ev.pop(*ev);
-}
-
 // completed columns [c0, c1) -> compress batches (one per contiguous run of ring slots)
 bool queue_columns(hhgt_ingest *g, Input *in, uint64_t c0, uint64_t c1)
 {
-    hhgt_ingest::InState *X = static_cast<hhgt_ingest::InState *>(in->state);
+    InState *X = in->state;
     while (c0 < c1) {
         const uint64_t slot = c0 % X->ring_cols;
         const uint64_t n = (c1 - c0) < (X->ring_cols - slot) ? (c1 - c0) : (X->ring_cols - slot);
-        Batch b;
-        b.kind = B_COLUMNS;
-        b.in = in;
+        Batch b(B_COLUMNS, in);
         b.first_col = c0;
         b.n_cols = n;
         b.n_chunks = n * X->n_sc;
         b.raw_bytes = n * X->col_bytes;
-        if (!g->free_dst.pop(b.dst_slot) || !get_event(g, &b.ev)) return false;
+        if (!g->free_dst.pop(b.dst_slot) || !g->free_ev.pop(b.ev)) return false;
         trace("drv:dst_slot", (long long)n);
         DstSlot &d = g->dst[(size_t)b.dst_slot];
-        const int bs = g->o.blocksize;
-        if (X->planes)
-            G_TRY(hhgt_compress_planes(g->ctx, &X->lay, X->P.p, X->G.p, (uint32_t)slot, (uint32_t)n, g->o.format, d.d.p, d.d.cap,
-                                       d.off.as<uint64_t>(), nullptr, g->s_main));
-        else
-            G_TRY(hhgt_compress_chunks(g->ctx, X->G.as<uint8_t>() + slot * X->col_bytes, b.n_chunks, X->chunk_nbytes, g->o.typesize, bs,
-                                       g->o.format, d.d.p, d.d.cap, d.off.as<uint64_t>(), nullptr, g->s_main));
+        G_TRY(X->compress(g->ctx, g->o, slot, n, d, g->s_main));
         trace("drv:compress_queued", (long long)b.n_chunks);
         G_HIP(hipMemcpyAsync(d.h_off.p, d.off.p, (size_t)((b.n_chunks + 1) * 8), hipMemcpyDeviceToHost, g->s_main));
         G_HIP(hipEventRecord(b.ev, g->s_main));
@@ -1094,35 +1114,30 @@ bool queue_columns(hhgt_ingest *g, Input *in, uint64_t c0, uint64_t c1)
     return true;
 }
 
-// look at the result record of an encoded block (its event has been waited for)
-bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r);
-bool harvest(hhgt_ingest *g, hhgt_ingest::Res &r)
-{
-    const double t0 = now_s();
-    G_HIP(hipEventSynchronize(r.ev));
-    const double t1 = now_s();
-    trace("drv:encode_done", r.text_idx);
-    const bool ok = harvest_body(g, r);
-    trace("drv:harvested");
-    g->tm.drv_harvest_wait += t1 - t0;
-    g->tm.drv_harvest += now_s() - t1;
-    return ok;
-}
-
-bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
-{
+// The result record of an encoded block, once its event has been waited for: one Harvest per block, its steps in the order of run()
+struct Harvest {
+    hhgt_ingest *g;
+    Res &r;
     TextBuf &tb = g->text[(size_t)r.text_idx];
     Input *in = tb.in;
-    hhgt_ingest::InState *X = r.st;
-    if (!in->header_sent) {
-        Batch h;
-        h.kind = B_HEADER;
-        h.in = in;
-        g->q_ship.push(h);
-        in->header_sent = true;
-    }
+    InState *X = in->state;
+    const bool last = tb.last;
     const hhgt_encode_result rec = *r.rec;
-    if (in->dev_inflate && *tb.h_bad) {
+    const uint64_t a = rec.cursor_before, b = rec.cursor_after;   // the input's kept records before and behind the block
+
+    bool report_failed_block()
+    {
+        if (in->dev_inflate && *tb.h_bad) return report_failed_inflate();   // (the text behind it means nothing)
+        if (rec.n_lines_over && !rec.err_density) {
+            hhgt_set_error("Error parsing VCF file: %llu more lines than records of %llu samples fit in the block (blank or cut-off lines)",
+                           (unsigned long long)rec.n_lines_over, (unsigned long long)in->S_file);
+            return fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
+        }
+        G_TRY(hhgt_encode_result_status(&rec));   // (more than MAX_CHROM_RUNS runs: HHGT_ERR_CAPACITY)
+        return true;
+    }
+    bool report_failed_inflate()
+    {
         // which member, and why: only now is the per-member status worth copying
         std::vector<uint32_t> st((size_t)tb.n_members);
         hipMemcpy(st.data(), tb.status.p, st.size() * 4, hipMemcpyDeviceToHost);
@@ -1133,60 +1148,56 @@ bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
         else hhgt_set_error("BGZF member %llu: DEFLATE stream is corrupt (status %u)", (unsigned long long)(tb.first_member + k), code);
         return fail(g, HHGT_ERR_IO, hhgt_last_error());
     }
-    if (rec.n_lines_over && !rec.err_density) {
-        hhgt_set_error("Error parsing VCF file: %llu more lines than records of %llu samples fit in the block (blank or cut-off lines)",
-                       (unsigned long long)rec.n_lines_over, (unsigned long long)in->S_file);
-        return fail(g, HHGT_ERR_MALFORMED, hhgt_last_error());
+    // the block's counts; its text has then been consumed and goes back to the source: nothing behind this step reads `tb`
+    bool tally_stats_and_release_text()
+    {
+        in->st.n_lines += rec.stats.n_lines;
+        in->st.n_records += rec.stats.n_records;
+        in->st.n_drop_region += rec.stats.n_drop_region;
+        in->st.n_drop_filter += rec.stats.n_drop_filter;
+        in->st.n_haploid_padded += rec.stats.n_haploid_padded;
+        in->st.n_general_lines += rec.stats.n_general_lines;
+        in->st.text_bytes += tb.nbytes;
+        in->st.n_blocks += 1;
+        if (b - a > X->kept_per_block) {   // the ring and the variant slots were sized from this bound: never trust it silently
+            hhgt_set_error("ingest: a text block kept %llu records, the engine's buffers were sized for %llu (block of %llu bytes)",
+                           (unsigned long long)(b - a), (unsigned long long)X->kept_per_block, (unsigned long long)tb.nbytes);
+            return fail(g, HHGT_ERR_CAPACITY, hhgt_last_error());
+        }
+        g->free_text.push(r.text_idx);   // the text has been consumed: the source may overwrite the buffer
+        r.text_idx = -1;
+        in->st.n_kept = b;
+        return true;
     }
-    G_TRY(hhgt_encode_result_status(&rec));   // (more than MAX_CHROM_RUNS runs: HHGT_ERR_CAPACITY)
-    const uint32_t n_runs = (uint32_t)rec.stats.n_chrom_runs;
-    const uint64_t *run_first = rec.run_first;
-    const char *run_names = &rec.run_names[0][0];
-    std::vector<uint64_t> more_first;
-    std::vector<char> more_names;
-    if (n_runs > HHGT_RESULT_RUNS) {
-        // every empty or header line and every CHROM change inside the block starts a run (the ones with no kept record
-        // included): the rest of the table is in the copy queued behind the block's encode
-        more_first.resize(n_runs);
-        more_names.resize((size_t)n_runs * 32);
-        G_HIP(hipMemcpy(more_first.data(), r.run_first.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost));
-        G_HIP(hipMemcpy(more_names.data(), r.run_names.p, (size_t)n_runs * 32, hipMemcpyDeviceToHost));
-        run_first = more_first.data();
-        run_names = more_names.data();
-    }
-    in->st.n_lines += rec.stats.n_lines;
-    in->st.n_records += rec.stats.n_records;
-    in->st.n_drop_region += rec.stats.n_drop_region;
-    in->st.n_drop_filter += rec.stats.n_drop_filter;
-    in->st.n_haploid_padded += rec.stats.n_haploid_padded;
-    in->st.n_general_lines += rec.stats.n_general_lines;
-    in->st.text_bytes += tb.nbytes;
-    in->st.n_blocks += 1;
-    const uint64_t a = rec.cursor_before, b = rec.cursor_after;
-    const bool last = tb.last;
-    if (b - a > X->kept_per_block) {   // the ring and the variant slots were sized from this bound: never trust it silently
-        hhgt_set_error("ingest: a text block kept %llu records, the engine's buffers were sized for %llu (block of %llu bytes)",
-                       (unsigned long long)(b - a), (unsigned long long)X->kept_per_block, (unsigned long long)tb.nbytes);
-        return fail(g, HHGT_ERR_CAPACITY, hhgt_last_error());
-    }
-    g->free_text.push(r.text_idx);   // the text has been consumed: the source may overwrite the buffer
-    r.text_idx = -1;
-    X->host_cursor = b;
-    in->st.n_kept = b;
-    if (b > a || n_runs) {
-        Batch v;
-        v.kind = B_VARIANTS;
-        v.in = in;
+    // the block's rows of the variant tables and its CHROM runs, fetched here where the record is too small for them
+    bool queue_variants()
+    {
+        const uint32_t n_runs = (uint32_t)rec.stats.n_chrom_runs;
+        if (b == a && !n_runs) return true;
+        const uint64_t *run_first = rec.run_first;
+        const char *run_names = &rec.run_names[0][0];
+        std::vector<uint64_t> more_first;
+        std::vector<char> more_names;
+        if (n_runs > HHGT_RESULT_RUNS) {
+            // every empty or header line and every CHROM change inside the block starts a run (the ones with no kept record
+            // included): the rest of the table is in the copy queued behind the block's encode
+            more_first.resize(n_runs);
+            more_names.resize((size_t)n_runs * 32);
+            G_HIP(hipMemcpy(more_first.data(), r.run_first.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost));
+            G_HIP(hipMemcpy(more_names.data(), r.run_names.p, (size_t)n_runs * 32, hipMemcpyDeviceToHost));
+            run_first = more_first.data();
+            run_names = more_names.data();
+        }
+        Batch v(B_VARIANTS, in);
         v.first_variant = a;
         v.n_variants = b - a;
-        if (!g->free_var.pop(v.var_slot) || !get_event(g, &v.ev)) return false;
+        if (!g->free_var.pop(v.var_slot) || !g->free_ev.pop(v.ev)) return false;
         trace("drv:var_slot");
         VarSlot &vs = g->var[(size_t)v.var_slot];
-        const uint64_t cap = X->lay.v_capacity;
         if (b > a) {
             const uint64_t nt = (b - a + 3) / 4;
             hipLaunchKernelGGL(k_tables_to_host, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, g->s_main, X->t_start.as<uint32_t>(),
-                               X->t_ref.as<uint8_t>(), X->t_alt.as<uint8_t>(), a, b - a, cap, reinterpret_cast<uint32_t *>(vs.start.p),
+                               X->t_ref.as<uint8_t>(), X->t_alt.as<uint8_t>(), a, b - a, X->lay.v_capacity, reinterpret_cast<uint32_t *>(vs.start.p),
                                reinterpret_cast<uint32_t *>(vs.ref.p), reinterpret_cast<uint32_t *>(vs.alt.p));
             G_HIP(hipGetLastError());
         }
@@ -1204,178 +1215,344 @@ bool harvest_body(hhgt_ingest *g, hhgt_ingest::Res &r)
         G_HIP(hipEventRecord(v.ev, g->s_main));
         g->q_ship.push(v);
         trace("drv:var_queued");
+        return true;
     }
-    if (in->S) {
-        const uint64_t done = b / (uint64_t)g->o.vc;
+    bool queue_finished_columns()
+    {
+        if (!in->S) return true;
+        const uint64_t vc = (uint64_t)g->o.vc, done = b / vc;
         if (done > X->done_cols) {
             if (!queue_columns(g, in, X->done_cols, done)) return false;
             X->done_cols = done;
         }
-        if (last && b % (uint64_t)g->o.vc) {
+        if (last && b % vc) {
             // the open column: zero behind the cursor, frame it
-            if (X->planes) G_TRY(hhgt_pad_tail_planes_cursor(g->ctx, &X->lay, X->cursor.as<uint64_t>(), X->P.p, g->s_main));
-            else G_TRY(hhgt_pad_tail_cursor(g->ctx, &X->lay, X->cursor.as<uint64_t>(), X->G.p, g->s_main));
+            G_TRY(X->pad_open_column(g->ctx, g->s_main));
             if (!queue_columns(g, in, X->done_cols, X->done_cols + 1)) return false;
             X->done_cols += 1;
         }
+        return true;
     }
-    if (last) {
-        Batch e;
-        e.kind = B_INPUT_END;
-        e.in = in;
-        g->q_ship.push(e);
+    bool run()
+    {
+        if (!in->header_sent) g->q_ship.push(Batch(B_HEADER, in));   // by the input's first harvest: behind the previous input's last events
+        in->header_sent = true;
+        if (!report_failed_block() || !tally_stats_and_release_text() || !queue_variants() || !queue_finished_columns()) return false;
+        if (last) g->q_ship.push(Batch(B_INPUT_END, in));            // end of input
+        return true;
     }
-    return true;
+};
+
+// Bound on a block's line count (sizes the workspaces and every grid behind the index): a record of a file with S sample
+// columns has at least 2 S + 17 bytes (a sites-only file's eight columns: 16), so apart from the header lines of the first
+// block more lines than that can only be blank or cut-off lines — which are a parse error anyway (reported as such by
+// harvest).  The unconditional bound, 1024 lines per 16 KiB region, would size the grids for lines of 16 bytes: 10 M empty
+// workgroups per 1 GiB block.
+uint32_t max_lines_of(const TextBuf &tb)
+{
+    const uint64_t n_regions = (tb.nbytes + 1 + INDEX_REGION - 1) / INDEX_REGION;
+    const uint64_t min_record = tb.in->S_file ? 2 * (uint64_t)tb.in->S_file + 17 : 16;
+    uint64_t max_lines = tb.nbytes / min_record + (tb.first ? tb.in->header_lines : 0) + 64;
+    if (max_lines > n_regions * INDEX_CAP) max_lines = n_regions * INDEX_CAP;
+    return (uint32_t)(max_lines > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : max_lines);
 }
+
+// One Driver per engine: block() takes the text blocks in order; a block's result is looked at one block later.
+struct Driver {
+    hhgt_ingest *g;
+    std::deque<int> pending;   // result slots in flight, oldest first
+    int next_res = 0;
+
+    bool harvest_oldest()
+    {
+        Res &r = g->res[pending.front()];
+        const double t0 = now_s();
+        G_HIP(hipEventSynchronize(r.ev));
+        const double t1 = now_s();
+        trace("drv:encode_done", r.text_idx);
+        const bool ok = Harvest{g, r}.run();
+        trace("drv:harvested");
+        g->tm.drv_harvest_wait += t1 - t0;
+        g->tm.drv_harvest += now_s() - t1;
+        if (ok) pending.pop_front();
+        return ok;
+    }
+    bool block(int ti)
+    {
+        TextBuf &tb = g->text[(size_t)ti];
+        const double tb0 = now_s();
+        if (tb.first && !begin_input(g, tb.in, tb.cap)) return false;
+        g->tm.drv_begin += now_s() - tb0;
+        if ((int)pending.size() >= N_RES - 1 && !harvest_oldest()) return false;
+        Res &r = g->res[next_res];
+        const double tl0 = now_s();
+        trace("drv:encode_launch", ti, (long long)tb.nbytes);
+        G_HIP(hipStreamWaitEvent(g->s_main, tb.ready, 0));
+        G_TRY(tb.in->state->encode(g->ctx, tb, max_lines_of(tb), r.rec, g->s_main));
+        G_HIP(hipMemcpyAsync(r.run_first.p, g->ctx->enc.run_first.p, MAX_CHROM_RUNS * 8, hipMemcpyDeviceToDevice, g->s_main));
+        G_HIP(hipMemcpyAsync(r.run_names.p, g->ctx->enc.run_names.p, MAX_CHROM_RUNS * 32, hipMemcpyDeviceToDevice, g->s_main));
+        G_HIP(hipEventRecord(r.ev, g->s_main));
+        r.text_idx = ti;
+        pending.push_back(next_res);
+        next_res = (next_res + 1) % N_RES;
+        g->tm.drv_launch += now_s() - tl0;
+        // one block behind: the GPU has the encode above queued while the host looks at the previous result.  The
+        // last block of an input is only drained at once when nothing else is waiting to be queued.
+        while (pending.size() > 1 || (tb.last && !pending.empty() && g->q_text.size() == 0))
+            if (!harvest_oldest()) return false;
+        return true;
+    }
+};
 
 void driver_main(hhgt_ingest *g)
 {
     hipSetDevice(g->device);
-    std::deque<int> pending;   // result slots in flight, oldest first
-    int next_res = 0;
+    Driver drv{g};
     for (;;) {
         int ti;
         const double tw = now_s();
         const bool got = g->q_text.pop(ti);
         g->tm.drv_wait_text += now_s() - tw;
-        if (!got) break;
-        if (ti < 0) break;   // end of inputs
-        if (g->tm.t_first_text == 0) g->tm.t_first_text = now_s();
-        TextBuf &tb = g->text[(size_t)ti];
-        Input *in = tb.in;
-        auto drv = [&]() -> bool {
-            const double tb0 = now_s();
-            if (tb.first && !begin_input(g, in, tb.cap)) return false;
-            g->tm.drv_begin += now_s() - tb0;
-            if ((int)pending.size() >= N_RES - 1) {
-                if (!harvest(g, g->res[pending.front()])) return false;
-                pending.pop_front();
-            }
-            hhgt_ingest::Res &r = g->res[next_res];
-            hhgt_ingest::InState *X = static_cast<hhgt_ingest::InState *>(in->state);
-            r.st = X;
-            const double tl0 = now_s();
-            trace("drv:encode_launch", ti, (long long)tb.nbytes);
-            G_HIP(hipStreamWaitEvent(g->s_main, tb.ready, 0));
-            // Bound on the block's line count (sizes the workspaces and every grid behind the index): a record of a
-            // file with S sample columns has at least 2 S + 17 bytes (a sites-only file's eight columns: 16), so apart from the header lines of the first
-            // block more lines than that can only be blank or cut-off lines — which are a parse error anyway
-            // (reported as such by harvest).  The unconditional bound, 1024 lines per 16 KiB region, would size the
-            // grids for lines of 16 bytes: 10 M empty workgroups per 1 GiB block.
-            const uint64_t n_regions = (tb.nbytes + 1 + INDEX_REGION - 1) / INDEX_REGION;
-            const uint64_t min_record = in->S_file ? 2 * (uint64_t)in->S_file + 17 : 16;
-            uint64_t max_lines = tb.nbytes / min_record + (tb.first ? in->header_lines : 0) + 64;
-            if (max_lines > n_regions * INDEX_CAP) max_lines = n_regions * INDEX_CAP;
-            if (X->planes)
-                G_TRY(hhgt_encode_text_planes_async(g->ctx, tb.d, tb.nbytes, in->region.c_str(), &X->lay, X->cursor.as<uint64_t>(),
-                                                    (uint32_t)(max_lines > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : max_lines), X->P.p, X->G.p,
-                                                    X->t_start.as<uint32_t>(), nullptr, X->t_ref.as<uint8_t>(), X->t_alt.as<uint8_t>(),
-                                                    r.rec, g->s_main));
-            else
-                G_TRY(hhgt_encode_text_async(g->ctx, tb.d, tb.nbytes, in->region.c_str(), &X->lay, X->cursor.as<uint64_t>(),
-                                             (uint32_t)(max_lines > 0xFFFFFFF0ull ? 0xFFFFFFF0ull : max_lines), X->G.p,
-                                             X->t_start.as<uint32_t>(), nullptr, X->t_ref.as<uint8_t>(), X->t_alt.as<uint8_t>(), r.rec,
-                                             g->s_main));
-            G_HIP(hipMemcpyAsync(r.run_first.p, g->ctx->enc.run_first.p, MAX_CHROM_RUNS * 8, hipMemcpyDeviceToDevice, g->s_main));
-            G_HIP(hipMemcpyAsync(r.run_names.p, g->ctx->enc.run_names.p, MAX_CHROM_RUNS * 32, hipMemcpyDeviceToDevice, g->s_main));
-            G_HIP(hipEventRecord(r.ev, g->s_main));
-            r.text_idx = ti;
-            pending.push_back(next_res);
-            next_res = (next_res + 1) % N_RES;
-            g->tm.drv_launch += now_s() - tl0;
-            // one block behind: the GPU has the encode above queued while the host looks at the previous result.  The
-            // last block of an input is only drained at once when nothing else is waiting to be queued.
-            while (pending.size() > 1 || (tb.last && !pending.empty() && g->q_text.size() == 0)) {
-                if (!harvest(g, g->res[pending.front()])) return false;
-                pending.pop_front();
-            }
-            return true;
-        };
-        if (!drv()) break;
+        if (!got || ti < 0) break;   // stopped, or the end of inputs
+        if (!drv.block(ti)) break;
     }
-    while (!g->failed.load() && !pending.empty()) {
-        if (!harvest(g, g->res[pending.front()])) break;
-        pending.pop_front();
-    }
-    if (!g->failed.load()) {
-        Batch e;
-        e.kind = B_END;
-        g->q_ship.push(e);
-    }
+    while (!g->failed.load() && !drv.pending.empty())
+        if (!drv.harvest_oldest()) break;
+    if (!g->failed.load()) g->q_ship.push(Batch(B_END, nullptr));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // shipper thread: sizes -> device-to-host copy of the framed bytes -> out queue
 // ---------------------------------------------------------------------------------------------------------------
+bool wait_batch(hhgt_ingest *g, Batch &b, const char *message)
+{
+    if (hipEventSynchronize(b.ev) != hipSuccess) return fail(g, HHGT_ERR_HIP, message);
+    g->free_ev.push(b.ev);
+    b.ev = nullptr;
+    return true;
+}
+
+bool ship_columns(hhgt_ingest *g, Batch &b, hipEvent_t copied)
+{
+    const double ts0 = now_s();
+    if (!wait_batch(g, b, "ingest: compress failed")) return false;
+    g->tm.ship_wait_ev += now_s() - ts0;
+    trace("ship:compress_done", (long long)b.n_cols);
+    DstSlot &d = g->dst[(size_t)b.dst_slot];
+    const uint64_t *off = reinterpret_cast<const uint64_t *>(d.h_off.p);
+    // the device wrote these offsets, and the last one sizes an allocation and a copy
+    bool sane = off[b.n_chunks] <= d.d.cap;
+    for (uint64_t i = 0; i < b.n_chunks && sane; ++i) sane = off[i] <= off[i + 1];
+    if (!sane) return fail(g, HHGT_ERR_CAPACITY, "ingest: the chunk offset table of a compressed batch is inconsistent");
+    b.framed_bytes = off[b.n_chunks];
+    const double tso = now_s();
+    if (!g->free_out.pop(b.out_slot)) return false;
+    g->tm.ship_wait_out += now_s() - tso;
+    const double tsc = now_s();
+    OutSlot &o = g->out[(size_t)b.out_slot];
+    if (o.h.ensure((size_t)b.framed_bytes + 64) != HHGT_OK) return fail(g, HHGT_ERR_HIP, hhgt_last_error());
+    o.off.assign(off, off + b.n_chunks + 1);
+    if (hipMemcpyAsync(o.h.p, d.d.p, (size_t)b.framed_bytes, hipMemcpyDeviceToHost, g->s_out) != hipSuccess ||
+        hipEventRecord(copied, g->s_out) != hipSuccess || hipEventSynchronize(copied) != hipSuccess)
+        return fail(g, HHGT_ERR_HIP, "ingest: copy of the framed chunks failed");
+    g->tm.ship_copy += now_s() - tsc;
+    trace("ship:copied", (long long)b.framed_bytes, (long long)b.n_cols);
+    g->free_dst.push(b.dst_slot);
+    b.dst_slot = -1;
+    b.in->st.raw_bytes += b.raw_bytes;
+    b.in->st.compressed_bytes += b.framed_bytes;
+    return true;
+}
+
+// the input's seconds; HHGT_INGEST_DEBUG: where the threads spent them, then reset (the counters are only read here: a development aid)
+void end_of_input_times(hhgt_ingest *g, Input *in)
+{
+    in->st.seconds = now_s() - in->t_first;
+    static const bool dbg = getenv("HHGT_INGEST_DEBUG") != nullptr;
+    if (!dbg) return;
+    auto &t = g->tm;
+    fprintf(stderr, "[hhgt ingest] input %d: %.1f ms | source: wait for a text buffer %.1f | driver: wait for text %.1f, begin_input %.1f, "
+            "encode launch %.1f, harvest wait %.1f, harvest work %.1f | shipper: wait for compress %.1f, wait for an out slot %.1f, "
+            "copy %.1f (ms)\n",
+            in->index, in->st.seconds * 1e3, t.src_wait_text * 1e3, t.drv_wait_text * 1e3, t.drv_begin * 1e3, t.drv_launch * 1e3,
+            t.drv_harvest_wait * 1e3, t.drv_harvest * 1e3, t.ship_wait_ev * 1e3, t.ship_wait_out * 1e3, t.ship_copy * 1e3);
+    t = hhgt_ingest::Times();
+}
+
 void ship_main(hhgt_ingest *g)
 {
     hipSetDevice(g->device);
-    hipEvent_t cev = nullptr;
-    hipEventCreateWithFlags(&cev, wait_event_flags());
-    for (;;) {
-        Batch b;
-        if (!g->q_ship.pop(b)) break;
-        const double ts0 = now_s();
-        if (b.kind == B_VARIANTS) {
-            if (hipEventSynchronize(b.ev) != hipSuccess) {
-                fail(g, HHGT_ERR_HIP, "ingest: variant table copy failed");
-                break;
-            }
-            g->free_ev.push(b.ev);
-            b.ev = nullptr;
-        } else if (b.kind == B_COLUMNS) {
-            if (hipEventSynchronize(b.ev) != hipSuccess) {
-                fail(g, HHGT_ERR_HIP, "ingest: compress failed");
-                break;
-            }
-            g->free_ev.push(b.ev);
-            b.ev = nullptr;
-            g->tm.ship_wait_ev += now_s() - ts0;
-            trace("ship:compress_done", (long long)b.n_cols);
-            DstSlot &d = g->dst[(size_t)b.dst_slot];
-            const uint64_t *off = reinterpret_cast<const uint64_t *>(d.h_off.p);
-            b.framed_bytes = off[b.n_chunks];
-            const double tso = now_s();
-            if (!g->free_out.pop(b.out_slot)) break;
-            g->tm.ship_wait_out += now_s() - tso;
-            const double tsc = now_s();
-            OutSlot &o = g->out[(size_t)b.out_slot];
-            if (o.h.ensure((size_t)b.framed_bytes + 64) != HHGT_OK) {
-                fail(g, HHGT_ERR_HIP, hhgt_last_error());
-                break;
-            }
-            o.off.assign(off, off + b.n_chunks + 1);
-            if (hipMemcpyAsync(o.h.p, d.d.p, (size_t)b.framed_bytes, hipMemcpyDeviceToHost, g->s_out) != hipSuccess ||
-                hipEventRecord(cev, g->s_out) != hipSuccess || hipEventSynchronize(cev) != hipSuccess) {
-                fail(g, HHGT_ERR_HIP, "ingest: copy of the framed chunks failed");
-                break;
-            }
-            g->tm.ship_copy += now_s() - tsc;
-            trace("ship:copied", (long long)b.framed_bytes, (long long)b.n_cols);
-            g->free_dst.push(b.dst_slot);
-            b.dst_slot = -1;
-            b.in->st.raw_bytes += b.raw_bytes;
-            b.in->st.compressed_bytes += b.framed_bytes;
-        } else if (b.kind == B_INPUT_END) {
-            b.in->st.seconds = now_s() - b.in->t_first;
-            static const bool dbg = getenv("HHGT_INGEST_DEBUG") != nullptr;
-            if (dbg) {   // per input, then reset (the threads' counters are only read here: a development aid)
-                auto &t = g->tm;
-                fprintf(stderr,
-                        "[hhgt ingest] input %d: %.1f ms | source: wait for a text buffer %.1f | driver: wait for text %.1f, begin_input %.1f, "
-                        "encode launch %.1f, harvest wait %.1f, harvest work %.1f | shipper: wait for compress %.1f, wait for an out slot %.1f, "
-                        "copy %.1f (ms)\n",
-                        b.in->index, b.in->st.seconds * 1e3, t.src_wait_text * 1e3, t.drv_wait_text * 1e3, t.drv_begin * 1e3, t.drv_launch * 1e3,
-                        t.drv_harvest_wait * 1e3, t.drv_harvest * 1e3, t.ship_wait_ev * 1e3, t.ship_wait_out * 1e3, t.ship_copy * 1e3);
-                t = hhgt_ingest::Times();
-            }
-        }
-        const int kind = b.kind;
-        if (kind == B_END) g->tm.t_end = now_s();
+    Event copied;
+    hipEventCreateWithFlags(&copied.e, wait_event_flags());
+    for (Batch b; g->q_ship.pop(b);) {
+        if (b.kind == B_VARIANTS && !wait_batch(g, b, "ingest: variant table copy failed")) break;
+        if (b.kind == B_COLUMNS && !ship_columns(g, b, copied)) break;
+        if (b.kind == B_INPUT_END) end_of_input_times(g, b.in);
         g->q_out.push(b);
-        if (kind == B_END) break;
+        if (b.kind == B_END) break;
     }
-    if (cev) hipEventDestroy(cev);
+}
+
+// hhgt_ingest_open, step by step
+int resolve_opts(const hhgt_ingest_opts *opts, hhgt_ingest_opts *o)
+{
+    *o = opts ? *opts : hhgt_ingest_opts{};
+    if (o->sc <= 0) o->sc = 64;
+    if (o->vc <= 0) o->vc = 8192;
+    if (o->typesize <= 0) o->typesize = 2;
+    if (o->blocksize <= 0) o->blocksize = o->vc * 2 < 8192 ? o->vc * 2 : 8192;
+    if (o->format != HHGT_BLOSC1 && o->format != HHGT_BLOSC2) o->format = HHGT_BLOSC2;
+    if ((o->sc & (o->sc - 1)) || o->vc % TILE_V) {
+        hhgt_set_error("ingest: sc must be a power of two and vc a multiple of %d", TILE_V);
+        return HHGT_ERR_ARG;
+    }
+    return HHGT_OK;
+}
+
+int make_streams(hhgt_ingest *g)
+{
+    OPEN_HIP(hipSetDevice(g->device), "hipSetDevice");
+    OPEN_HIP(hipStreamCreateWithFlags(&g->s_main.s, hipStreamNonBlocking), "stream");
+    // the copy streams get the highest priority: on this platform pinned copies can run as blit kernels, and a blit
+    // queued behind thousands of resident LZ4 / inflate waves crawled at 4-13 GB/s (a 50 MB batch took up to 12 ms,
+    // the driver ran out of batch slots and the GPU idled)
+    int prio_lo = 0, prio_hi = 0;
+    hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    OPEN_HIP(hipStreamCreateWithPriority(&g->s_copy.s, hipStreamNonBlocking, prio_hi), "stream");
+    // the inflate streams at the lowest priority: one wave per member lives for the whole launch, so a freed wave slot should
+    // go to the encode / compress kernels of the block before, not to the next inflate
+    OPEN_HIP(hipStreamCreateWithPriority(&g->s_inf.s, hipStreamNonBlocking, prio_lo), "stream");
+    OPEN_HIP(hipStreamCreateWithPriority(&g->s_inf2.s, hipStreamNonBlocking, prio_lo), "stream");
+    OPEN_HIP(hipStreamCreateWithFlags(&g->s_carry.s, hipStreamNonBlocking), "stream");
+    OPEN_HIP(hipStreamCreateWithPriority(&g->s_out.s, hipStreamNonBlocking, prio_hi), "stream");
+    return HHGT_OK;
+}
+
+int make_pools(hhgt_ingest *g)
+{
+    const bool dev = g->o.device_inflate != 0;
+    // a text buffer holds a block of the host reader, or of the device inflater where that may run and is larger
+    const uint64_t bb_host = block_bytes(g, 64ull << 20), bb_dev = block_bytes(g, 512ull << 20);
+    const size_t text_cap = (size_t)(dev && bb_dev > bb_host ? bb_dev : bb_host) + 256;
+    g->text = std::vector<TextBuf>(dev ? N_TEXT_DEV : N_TEXT_HOST);
+    for (size_t i = 0; i < g->text.size(); ++i) {
+        TextBuf &tb = g->text[i];
+        OPEN_HIP(hipMalloc(reinterpret_cast<void **>(&tb.d), text_cap), "hipMalloc(text block)");
+        tb.cap = text_cap;
+        OPEN_HIP(hipEventCreateWithFlags(&tb.ready.e, hipEventDisableTiming), "event");
+        OPEN_HIP(hipEventCreateWithFlags(&tb.carry_done.e, hipEventDisableTiming), "event");
+        OPEN_HIP(hipHostMalloc(reinterpret_cast<void **>(&tb.h_bad.p), 8, hipHostMallocDefault), "hipHostMalloc");
+        g->free_text.push((int)i);
+    }
+    for (auto &s : g->stg) OPEN_HIP(hipEventCreateWithFlags(&s.done.e, wait_event_flags()), "event");
+    for (auto &r : g->res) {
+        OPEN_HIP(hipHostMalloc(reinterpret_cast<void **>(&r.rec.p), sizeof(hhgt_encode_result), hipHostMallocDefault), "hipHostMalloc");
+        OPEN_HIP(hipEventCreateWithFlags(&r.ev.e, wait_event_flags()), "event");
+        OPEN_TRY(r.run_first.ensure(MAX_CHROM_RUNS * 8));
+        OPEN_TRY(r.run_names.ensure(MAX_CHROM_RUNS * 32));
+    }
+    for (int i = 0; i < N_VAR; ++i) g->free_var.push(i);
+    for (int i = 0; i < N_DST; ++i) g->free_dst.push(i);
+    for (int i = 0; i < N_OUT; ++i) g->free_out.push(i);
+    for (auto &e : g->batch_events) {
+        OPEN_HIP(hipEventCreateWithFlags(&e.e, wait_event_flags()), "event");
+        g->free_ev.push(e.e);
+    }
+    if (dev) {
+        uint32_t t[32];
+        crc32_x2n_table(t);
+        OPEN_TRY(g->crc_x2n.ensure(sizeof(t)));
+        OPEN_HIP(hipMemcpy(g->crc_x2n.p, t, sizeof(t), hipMemcpyHostToDevice), "hipMemcpy");
+    }
+    return HHGT_OK;
+}
+
+// the device inflater's pinned staging of a block's compressed members, and its status words
+int presize_device_inflate(hhgt_ingest *g)
+{
+    const uint64_t bb = block_bytes(g, 512ull << 20), want = (uint64_t)((double)bb / 24.0 * 1.15) + (256u << 10);
+    const size_t tab_room = (size_t)(want / 26 + 2) * 28 + 64;
+    for (auto &sg : g->stg) {
+        OPEN_TRY(sg.h.ensure((size_t)want + 64 + tab_room));
+        OPEN_TRY(sg.d.ensure((size_t)want + 64 + tab_room));
+    }
+    // per text buffer: a status word per member (files written by bgzip hold ~64 KB of text per member; four times as
+    // many fit before these grow inside a pass — a hipFree there waits for the device to drain)
+    for (auto &tb : g->text) {
+        OPEN_TRY(tb.status.ensure((size_t)(bb / 16384 + 64) * 4));
+        OPEN_TRY(tb.bad.ensure(8));
+    }
+    return HHGT_OK;
+}
+
+// one chunk column through the compressor on the engine's stream: the first launch of a kernel that spills
+// (k_lz4_blocks) makes the runtime allocate the queue's scratch arena — 28 ms inside the first batch of the first
+// input otherwise (HHGT_INGEST_DEBUG: "harvest work" 28.1 ms against 0.3)
+int warm_compress(hhgt_ingest *g)
+{
+    InState &X0 = g->ist[0];
+    // (what the compressor reads of ring slot 0: planes are not laid out by column, so all of them)
+    OPEN_HIP(X0.planes ? hipMemsetAsync(X0.P.p, 0, (size_t)hhgt_planes_bytes(&X0.lay), g->s_main)
+                       : hipMemsetAsync(X0.G.p, 0, (size_t)X0.col_bytes, g->s_main), "hipMemsetAsync");
+    OPEN_TRY(X0.compress(g->ctx, g->o, 0, 1, g->dst[0], g->s_main));
+    OPEN_HIP(hipStreamSynchronize(g->s_main), "hipStreamSynchronize");
+    return HHGT_OK;
+}
+
+// one small copy each way on every stream the engine copies on (the first copy of a direction on a stream
+// sets the runtime's copy path up: milliseconds, once)
+int warm_copies(hhgt_ingest *g)
+{
+    void *cursor = g->ist[0].cursor.p;
+    uint8_t *h8 = g->dst[0].h_off.p;   // pinned, >= 16 bytes
+    for (hipStream_t st : g->streams()) {
+        OPEN_HIP(hipMemcpyAsync(cursor, h8, 8, hipMemcpyHostToDevice, st), "hipMemcpyAsync");
+        OPEN_HIP(hipMemcpyAsync(h8 + 8, cursor, 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync");
+        OPEN_HIP(hipMemsetAsync(cursor, 0, 8, st), "hipMemsetAsync");
+        OPEN_HIP(hipStreamSynchronize(st), "hipStreamSynchronize");
+    }
+    return HHGT_OK;
+}
+
+// every pinned buffer the device will copy into is copied into once, in full (HHGT_INGEST_DEBUG=2 showed the
+// first device -> host copy into each fresh pinned slot taking 7-10 ms where later ones take microseconds)
+int touch_pinned_slots(hhgt_ingest *g)
+{
+    const InState &X0 = g->ist[0];
+    auto least = [](size_t a, size_t b) { return a < b ? a : b; };
+    for (auto &v : g->var) {
+        const size_t n4 = least(v.start.cap, X0.t_start.cap), n1 = least(v.ref.cap, X0.t_ref.cap);
+        OPEN_HIP(hipMemcpyAsync(v.start.p, X0.t_start.p, n4, hipMemcpyDeviceToHost, g->s_main), "hipMemcpyAsync");
+        OPEN_HIP(hipMemcpyAsync(v.ref.p, X0.t_ref.p, n1, hipMemcpyDeviceToHost, g->s_main), "hipMemcpyAsync");
+        OPEN_HIP(hipMemcpyAsync(v.alt.p, X0.t_alt.p, n1, hipMemcpyDeviceToHost, g->s_main), "hipMemcpyAsync");
+    }
+    for (auto &d : g->dst)
+        OPEN_HIP(hipMemcpyAsync(d.h_off.p, d.off.p, least(d.h_off.cap, d.off.cap), hipMemcpyDeviceToHost, g->s_main), "hipMemcpyAsync");
+    for (auto &o : g->out)
+        OPEN_HIP(hipMemcpyAsync(o.h.p, g->dst[0].d.p, least(o.h.cap, g->dst[0].d.cap), hipMemcpyDeviceToHost, g->s_out), "hipMemcpyAsync");
+    OPEN_HIP(hipStreamSynchronize(g->s_main), "hipStreamSynchronize");
+    OPEN_HIP(hipStreamSynchronize(g->s_out), "hipStreamSynchronize");
+    return HHGT_OK;
+}
+
+// the caller knows the cohort's width: everything whose size follows from it is made (and pinned) now instead of
+// inside the first input — both ring states, the batch slots, the shipper's pinned copies, and for the device
+// inflater the pinned staging of a block's compressed members
+int prepare_for_expected_samples(hhgt_ingest *g)
+{
+    const uint64_t S = g->o.sites_only ? 0ull : (uint64_t)g->o.expect_samples, text_cap = g->text[0].cap;
+    for (auto &X : g->ist)
+        if (!size_input_state(g, &X, S, (uint64_t)g->o.expect_samples, text_cap, true)) return g->err ? g->err : HHGT_ERR_HIP;
+    // the context's own workspaces for a block / a batch of that size
+    const InState &X0 = g->ist[0];
+    OPEN_TRY(hhgt_reserve(g->ctx, text_cap, (uint32_t)X0.kept_per_block, (X0.kept_per_block / (uint64_t)g->o.vc + 4) * X0.n_sc,
+                          X0.chunk_nbytes, g->o.typesize, g->o.blocksize));
+    if (g->o.device_inflate != 0) OPEN_TRY(presize_device_inflate(g));
+    if (g->o.device_inflate != 1) hhgt_reader_prewarm(block_bytes(g, 64ull << 20), 6 * ((g->o.files_ahead > 0 ? g->o.files_ahead : 1) + 1));
+    if (S > 0) OPEN_TRY(warm_compress(g));
+    OPEN_TRY(warm_copies(g));
+    if (S > 0) OPEN_TRY(touch_pinned_slots(g));
+    return HHGT_OK;
 }
 
 }  // namespace
@@ -1387,159 +1564,21 @@ extern "C" int hhgt_ingest_open(hhgt_ctx *ctx, const hhgt_ingest_opts *opts, hhg
 {
     if (!ctx || !out) return HHGT_ERR_ARG;
     *out = nullptr;
-    hhgt_ingest *g = new hhgt_ingest();
+    hhgt_ingest_opts o;
+    OPEN_TRY(resolve_opts(opts, &o));
+    // a failing step leaves through hhgt_ingest_close: no thread was started, it synchronises whatever streams exist, then releases
+    std::unique_ptr<hhgt_ingest, void (*)(hhgt_ingest *)> owner(new hhgt_ingest(), hhgt_ingest_close);
+    hhgt_ingest *g = owner.get();
     g->ctx = ctx;
     g->device = ctx->device;
-    if (opts) g->o = *opts;
-    else memset(&g->o, 0, sizeof(g->o));
-    if (g->o.sc <= 0) g->o.sc = 64;
-    if (g->o.vc <= 0) g->o.vc = 8192;
-    if (g->o.typesize <= 0) g->o.typesize = 2;
-    if (g->o.blocksize <= 0) g->o.blocksize = g->o.vc * 2 < 8192 ? g->o.vc * 2 : 8192;
-    if (g->o.format != HHGT_BLOSC1 && g->o.format != HHGT_BLOSC2) g->o.format = HHGT_BLOSC2;
-    if ((g->o.sc & (g->o.sc - 1)) || g->o.vc % TILE_V) {
-        hhgt_set_error("ingest: sc must be a power of two and vc a multiple of %d", TILE_V);
-        delete g;
-        return HHGT_ERR_ARG;
-    }
-    int rc = HHGT_OK;
-    auto hip = [&](hipError_t e, const char *what) {
-        if (e != hipSuccess && rc == HHGT_OK) {
-            hhgt_set_error("ingest: %s failed: %s", what, hipGetErrorString(e));
-            rc = HHGT_ERR_HIP;
-        }
-    };
-    hip(hipSetDevice(g->device), "hipSetDevice");
-    hip(hipStreamCreateWithFlags(&g->s_main, hipStreamNonBlocking), "stream");
-    // the copy streams get the highest priority: on this platform pinned copies can run as blit kernels, and a blit
-    // queued behind thousands of resident LZ4 / inflate waves crawled at 4-13 GB/s (a 50 MB batch took up to 12 ms,
-    // the driver ran out of batch slots and the GPU idled)
-    int prio_lo = 0, prio_hi = 0;
-    hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    hip(hipStreamCreateWithPriority(&g->s_copy, hipStreamNonBlocking, prio_hi), "stream");
-    // the inflate streams at the lowest priority: one wave per member lives for the whole launch, so a freed wave slot should
-    // go to the encode / compress kernels of the block before, not to the next inflate
-    hip(hipStreamCreateWithPriority(&g->s_inf, hipStreamNonBlocking, prio_lo), "stream");
-    hip(hipStreamCreateWithPriority(&g->s_inf2, hipStreamNonBlocking, prio_lo), "stream");
-    hip(hipStreamCreateWithFlags(&g->s_carry, hipStreamNonBlocking), "stream");
-    hip(hipStreamCreateWithPriority(&g->s_out, hipStreamNonBlocking, prio_hi), "stream");
-    const bool dev = g->o.device_inflate != 0;
-    const uint64_t bb_host = block_bytes(g, 64ull << 20), bb_dev = block_bytes(g, 512ull << 20);
-    const uint64_t bb = dev ? (bb_dev > bb_host ? bb_dev : bb_host) : bb_host;
-    g->text.resize(dev ? N_TEXT_DEV : N_TEXT_HOST);
-    for (size_t i = 0; i < g->text.size() && rc == HHGT_OK; ++i) {
-        TextBuf &tb = g->text[i];
-        hip(hipMalloc(reinterpret_cast<void **>(&tb.d), (size_t)bb + 256), "hipMalloc(text block)");
-        tb.cap = rc == HHGT_OK ? (size_t)bb + 256 : 0;
-        hip(hipEventCreateWithFlags(&tb.ready, hipEventDisableTiming), "event");
-        hip(hipEventCreateWithFlags(&tb.carry_done, hipEventDisableTiming), "event");
-        hip(hipHostMalloc(reinterpret_cast<void **>(&tb.h_bad), 8, hipHostMallocDefault), "hipHostMalloc");
-        if (rc == HHGT_OK) g->free_text.push((int)i);
-    }
-    for (auto &s : g->stg) hip(hipEventCreateWithFlags(&s.done, wait_event_flags()), "event");
-    for (int i = 0; i < N_RES && rc == HHGT_OK; ++i) {
-        hip(hipHostMalloc(reinterpret_cast<void **>(&g->res[i].rec), sizeof(hhgt_encode_result), hipHostMallocDefault), "hipHostMalloc");
-        hip(hipEventCreateWithFlags(&g->res[i].ev, wait_event_flags()), "event");
-        if (rc == HHGT_OK) rc = g->res[i].run_first.ensure(MAX_CHROM_RUNS * 8);
-        if (rc == HHGT_OK) rc = g->res[i].run_names.ensure(MAX_CHROM_RUNS * 32);
-    }
-    for (int i = 0; i < N_VAR; ++i) g->free_var.push(i);
-    for (int i = 0; i < N_DST; ++i) g->free_dst.push(i);
-    for (int i = 0; i < N_OUT; ++i) g->free_out.push(i);
-    for (int i = 0; i < N_VAR + N_DST + 4 && rc == HHGT_OK; ++i) {
-        hipEvent_t e = nullptr;
-        hip(hipEventCreateWithFlags(&e, wait_event_flags()), "event");
-        if (e) {
-            g->batch_events.push_back(e);
-            g->free_ev.push(e);
-        }
-    }
-    if (rc == HHGT_OK && dev) {
-        uint32_t t[32];
-        crc32_x2n_table(t);
-        rc = g->crc_x2n.ensure(sizeof(t));
-        if (rc == HHGT_OK) hip(hipMemcpy(g->crc_x2n.p, t, sizeof(t), hipMemcpyHostToDevice), "hipMemcpy");
-    }
-    if (rc != HHGT_OK) {
-        hhgt_ingest_close(g);
-        return rc;
-    }
-    if (g->o.expect_samples > 0) {
-        // the caller knows the cohort's width: everything whose size follows from it is made (and pinned) now instead of
-        // inside the first input — both ring states, the batch slots, the shipper's pinned copies, and for the device
-        // inflater the pinned staging of a block's compressed members
-        const uint64_t S = g->o.sites_only ? 0ull : (uint64_t)g->o.expect_samples;
-        bool ok = size_input_state(g, &g->ist[0], S, (uint64_t)g->o.expect_samples, bb + 256, true) &&
-                  size_input_state(g, &g->ist[1], S, (uint64_t)g->o.expect_samples, bb + 256, true);
-        if (ok) {   // the context's own workspaces for a block / a batch of that size
-            const hhgt_ingest::InState &X0 = g->ist[0];
-            const uint64_t W = X0.kept_per_block / (uint64_t)g->o.vc + 2;
-            ok = hhgt_reserve(g->ctx, bb + 256, (uint32_t)X0.kept_per_block, (W + 2) * X0.n_sc, X0.chunk_nbytes, g->o.typesize,
-                              g->o.blocksize) == HHGT_OK;
-        }
-        if (ok && dev) {
-            const uint64_t want = (uint64_t)((double)bb_dev / 24.0 * 1.15) + (256u << 10);
-            const size_t tab_room = (size_t)(want / 26 + 2) * 28 + 64;
-            for (auto &sg : g->stg) ok = ok && sg.h.ensure((size_t)want + 64 + tab_room) == HHGT_OK && sg.d.ensure((size_t)want + 64 + tab_room) == HHGT_OK;
-            // per text buffer: a status word per member (files written by bgzip hold ~64 KB of text per member; four times as
-            // many fit before these grow inside a pass — a hipFree there waits for the device to drain)
-            for (auto &tb : g->text) ok = ok && tb.status.ensure((size_t)(bb_dev / 16384 + 64) * 4) == HHGT_OK && tb.bad.ensure(8) == HHGT_OK;
-        }
-        if (ok && g->o.device_inflate != 1) hhgt_reader_prewarm(bb_host, 6 * ((g->o.files_ahead > 0 ? g->o.files_ahead : 1) + 1));
-        if (ok && S > 0) {
-            // one chunk column through the compressor on the engine's stream: the first launch of a kernel that spills
-            // (k_lz4_blocks) makes the runtime allocate the queue's scratch arena — 28 ms inside the first batch of the first
-            // input otherwise (HHGT_INGEST_DEBUG: "harvest work" 28.1 ms against 0.3)
-            hhgt_ingest::InState &X0 = g->ist[0];
-            DstSlot &d0 = g->dst[0];
-            if (X0.planes) {
-                ok = hipMemsetAsync(X0.P.p, 0, (size_t)hhgt_planes_bytes(&X0.lay), g->s_main) == hipSuccess &&
-                     hhgt_compress_planes(g->ctx, &X0.lay, X0.P.p, X0.G.p, 0u, 1u, g->o.format, d0.d.p, d0.d.cap, d0.off.as<uint64_t>(), nullptr,
-                                          g->s_main) == HHGT_OK;
-            } else {
-                ok = hipMemsetAsync(X0.G.p, 0, (size_t)X0.col_bytes, g->s_main) == hipSuccess &&
-                     hhgt_compress_chunks(g->ctx, X0.G.p, X0.n_sc, X0.chunk_nbytes, g->o.typesize, g->o.blocksize, g->o.format, d0.d.p, d0.d.cap,
-                                          d0.off.as<uint64_t>(), nullptr, g->s_main) == HHGT_OK;
-            }
-            ok = ok && hipStreamSynchronize(g->s_main) == hipSuccess;
-        }
-        if (ok) {
-            // ... and one small copy each way on every stream the engine copies on (the first copy of a direction on a stream
-            // sets the runtime's copy path up: milliseconds, once)
-            hhgt_ingest::InState &X0 = g->ist[0];
-            DstSlot &d0 = g->dst[0];
-            uint8_t *h8 = d0.h_off.p;   // pinned, >= 16 bytes
-            for (hipStream_t st : {g->s_main, g->s_copy, g->s_inf, g->s_inf2, g->s_carry, g->s_out}) {
-                ok = ok && hipMemcpyAsync(X0.cursor.p, h8, 8, hipMemcpyHostToDevice, st) == hipSuccess &&
-                     hipMemcpyAsync(h8 + 8, X0.cursor.p, 8, hipMemcpyDeviceToHost, st) == hipSuccess &&
-                     hipMemsetAsync(X0.cursor.p, 0, 8, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
-            }
-            // ... and every pinned buffer the device will copy into is copied into once, in full (HHGT_INGEST_DEBUG=2 showed the
-            // first device -> host copy into each fresh pinned slot taking 7-10 ms where later ones take microseconds)
-            if (S > 0) {
-                for (auto &v : g->var) {
-                    const size_t n4 = v.start.cap < X0.t_start.cap ? v.start.cap : X0.t_start.cap, n1 = v.ref.cap < X0.t_ref.cap ? v.ref.cap : X0.t_ref.cap;
-                    ok = ok && hipMemcpyAsync(v.start.p, X0.t_start.p, n4, hipMemcpyDeviceToHost, g->s_main) == hipSuccess &&
-                         hipMemcpyAsync(v.ref.p, X0.t_ref.p, n1, hipMemcpyDeviceToHost, g->s_main) == hipSuccess &&
-                         hipMemcpyAsync(v.alt.p, X0.t_alt.p, n1, hipMemcpyDeviceToHost, g->s_main) == hipSuccess;
-                }
-                for (auto &d : g->dst)
-                    ok = ok && hipMemcpyAsync(d.h_off.p, d.off.p, d.h_off.cap < d.off.cap ? d.h_off.cap : d.off.cap, hipMemcpyDeviceToHost, g->s_main) == hipSuccess;
-                for (auto &o : g->out)
-                    ok = ok && hipMemcpyAsync(o.h.p, d0.d.p, o.h.cap < d0.d.cap ? o.h.cap : d0.d.cap, hipMemcpyDeviceToHost, g->s_out) == hipSuccess;
-                ok = ok && hipStreamSynchronize(g->s_main) == hipSuccess && hipStreamSynchronize(g->s_out) == hipSuccess;
-            }
-        }
-        if (!ok) {
-            hhgt_ingest_close(g);
-            return HHGT_ERR_HIP;
-        }
-    }
-    g->tm.t_open = now_s();
+    g->o = o;
+    OPEN_TRY(make_streams(g));
+    OPEN_TRY(make_pools(g));
+    if (g->o.expect_samples > 0) OPEN_TRY(prepare_for_expected_samples(g));
     g->th_source = std::thread(source_main, g);
     g->th_driver = std::thread(driver_main, g);
     g->th_ship = std::thread(ship_main, g);
-    *out = g;
+    *out = owner.release();
     return HHGT_OK;
 }
 
@@ -1687,12 +1726,10 @@ extern "C" void hhgt_ingest_close(hhgt_ingest *g)
 {
     if (!g) return;
     hipSetDevice(g->device);
-    // stop the stages (a normal end has already drained them)
-    if (!g->ended) fail(g, HHGT_ERR_IO, "ingest: closed");
+    if (!g->ended) fail(g, HHGT_ERR_IO, "ingest: closed");   // stop the stages (a normal end has already drained them)
     hhgt_ingest_finish(g);
-    if (g->th_source.joinable()) g->th_source.join();
-    if (g->th_driver.joinable()) g->th_driver.join();
-    if (g->th_ship.joinable()) g->th_ship.join();
+    for (std::thread *t : {&g->th_source, &g->th_driver, &g->th_ship})
+        if (t->joinable()) t->join();
     if (trace_level() >= 2) {
         std::lock_guard<std::mutex> lk(g_trace_mu);
         const double t0 = g_trace.empty() ? 0 : g_trace[0].t;
@@ -1700,49 +1737,12 @@ extern "C" void hhgt_ingest_close(hhgt_ingest *g)
         for (auto &r : g_trace) fprintf(stderr, "[trace] %9.3f ms  %-20s %lld %lld\n", (r.t - t0) * 1e3, r.tag, r.a, r.b);
         g_trace.clear();
     }
-    for (hipStream_t s : {g->s_main, g->s_copy, g->s_inf, g->s_inf2, g->s_carry, g->s_out})
-        if (s) {
-            hipStreamSynchronize(s);
-            hipStreamDestroy(s);
-        }
-    for (auto &tb : g->text) {
-        if (tb.d) hipFree(tb.d);
-        if (tb.ready) hipEventDestroy(tb.ready);
-        if (tb.carry_done) hipEventDestroy(tb.carry_done);
-        if (tb.h_bad) hipHostFree(tb.h_bad);
-        tb.status.release();
-        tb.bad.release();
-    }
-    for (auto &s : g->stg) {
-        s.h.release();
-        s.d.release();
-        if (s.done) hipEventDestroy(s.done);
-    }
-    g->crc_x2n.release();
-    for (auto &x : g->ist)
-        for (DevBuf *b : {&x.G, &x.P, &x.t_start, &x.t_ref, &x.t_alt, &x.cursor}) b->release();
-    for (auto &r : g->res) {
-        if (r.rec) hipHostFree(r.rec);
-        r.run_first.release();
-        r.run_names.release();
-        if (r.ev) hipEventDestroy(r.ev);
-    }
-    for (auto &v : g->var) {
-        v.start.release();
-        v.ref.release();
-        v.alt.release();
-    }
-    for (auto &d : g->dst) {
-        d.d.release();
-        d.off.release();
-        d.h_off.release();
-    }
-    for (auto &o : g->out) o.h.release();
-    for (hipEvent_t e : g->batch_events) hipEventDestroy(e);
-    {
+    for (hipStream_t s : g->streams())
+        if (s) hipStreamSynchronize(s);
+    {   // readers opened ahead and never run
         std::lock_guard<std::mutex> lk(g->in_mu);
         for (auto &in : g->inputs)
             if (in->rd) hhgt_reader_close(in->rd);
     }
-    delete g;
+    delete g;   // every buffer and event by its holder; the streams, declared first, go last
 }

@@ -1,6 +1,7 @@
 """-m gpu: the native streaming ingest engine (include/hhgt_ingest.h) against the oracle, for every source mode
 (host reader: BGZF / gzip / plain file; BGZF inflated on the device; text in host memory), with small text blocks so
 that lines, chunk columns and ring slots wrap many times."""
+import functools
 import gzip
 import os
 
@@ -74,7 +75,7 @@ def check_against_oracle(r, text, S, region, sc, vc, runs=None):
     assert np.array_equal(cat(r["start"], np.uint32), o["start"])
     assert np.array_equal(cat(r["ref"], np.uint8), o["ref"]) and np.array_equal(cat(r["alt"], np.uint8), o["alt"])
     want = tiled_expected(o["G"], S, V, sc, vc)
-    assert len(r["chunks"]) == len(want) and sum(r["cols"]) == -(-V // vc)
+    assert len(r["chunks"]) == len(want) and sum(r["cols"]) == (-(-V // vc) if S else 0)     # (sites only: no columns)
     for k, (a, b) in enumerate(zip(r["chunks"], want)):
         assert np.array_equal(a, b), f"chunk {k}"
     st = r["stats"]
@@ -418,3 +419,52 @@ def test_held_chunk_buffers_outlive_later_events(ctx, tmp_path):
     assert n_cols == -(-o["n_kept"] // vc) and len(chunks) == len(want)
     for k, (a, b) in enumerate(zip(chunks, want)):
         assert np.array_equal(a, b), f"chunk {k}"
+
+
+def mem(text):
+    return torch.frombuffer(bytearray(text), dtype=torch.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def width_texts():
+    """40, 130 (mixed text) and 40 samples again: rendered once for the tests below"""
+    t3, _ = synth.render_fixed_numpy("chr3", synth.variant_table(3, 3000, 40), 40, seed=3)
+    t5, _ = synth.render_fixed_numpy("chr5", synth.variant_table(5, 2000, 40), 40, seed=5)
+    return bytes(t3), synth.render_mixed("chr4", 1200, 130, seed=4), bytes(t5)
+
+
+@pytest.mark.parametrize("vc", [256, 4096])
+def test_expected_width_differs_from_what_arrives(ctx, vc):
+    """expect_samples=40 sizes (and pins) every slot at open; the second input is 130 samples wide, so the batch slots are
+    collected and grown while the first input's batches are still on their way out, and the ring state sized at open grows
+    again; the third input finds everything larger than it needs.  vc 256: int8 ring, vc 4096: bit-plane ring.
+    (stream_files peeks at the first file, so it never reaches this path.)"""
+    t3, mixed, t5 = width_texts()
+    res = run_engine(ctx, [(mem(t3), "chr3"), (mem(mixed), "chr4"), (mem(t5), "chr5")], sc=64, vc=vc, block_bytes=1 << 20,
+                     expect_samples=40)
+    check_against_oracle(res[0], t3, 40, "chr3", 64, vc, runs=[(0, "chr3")])
+    check_against_oracle(res[1], mixed, 130, "chr4", 64, vc)
+    check_against_oracle(res[2], t5, 40, "chr5", 64, vc, runs=[(0, "chr5")])
+
+
+def test_expected_width_above_what_arrives(ctx):
+    """expect_samples=300, 40 arrive: nothing grows, the ring is re-laid for the narrower input"""
+    t3 = width_texts()[0]
+    res = run_engine(ctx, [(mem(t3), "chr3")], sc=64, vc=256, block_bytes=1 << 20, expect_samples=300)
+    check_against_oracle(res[0], t3, 40, "chr3", 64, 256, runs=[(0, "chr3")])
+
+
+def test_expected_width_sites_only(ctx):
+    S = 30
+    text, _ = synth.render_fixed_numpy("chr5", synth.variant_table(5, 2000, S), S, seed=5)
+    res = run_engine(ctx, [(mem(text), "chr5")], sites_only=True, expect_samples=S, block_bytes=1 << 20)
+    check_against_oracle(res[0], text, 0, "chr5", 64, 8192, runs=[(0, "chr5")])
+
+
+def test_open_refuses_bad_geometry_and_leaves_the_context_usable(ctx):
+    for bad in (dict(sc=48), dict(vc=100)):
+        with pytest.raises(dev.HhgtError, match="power of two"):
+            Ingest(ctx, **bad)
+    t3 = width_texts()[0]
+    res = run_engine(ctx, [(mem(t3), "chr3")], sc=64, vc=512, block_bytes=1 << 20)
+    check_against_oracle(res[0], t3, 40, "chr3", 64, 512, runs=[(0, "chr3")])
