@@ -82,10 +82,10 @@ class EncodeResultRec(C.Structure):     # hhgt_encode_result
 
 
 _vp, _u64, _u32, _i32, _str = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_char_p
-_lay, _pu64 = C.POINTER(Layout), C.POINTER(C.c_uint64)
-# every function of include/hhgt.h and include/hhgt_synth.h this package calls: name -> (restype, argtypes).  load() applies
-# the table; tests/test_abi_binding.py holds it against the headers.  (The reader and the ingest engine have headers of their
-# own, include/hhgt_reader.h and include/hhgt_ingest.h: reader.py, sharding.py and ingest.py bind those.)
+_lay, _pu64, _pi32, _pvp = C.POINTER(Layout), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_void_p)
+# every function of include/hhgt.h, include/hhgt_synth.h and include/hhgt_reader.h this package or its tests call: name ->
+# (restype, argtypes).  load() applies the table; tests/test_abi_binding.py holds it against the headers.  (The ingest engine
+# has a header of its own, include/hhgt_ingest.h: ingest.py binds that.)
 PROTOTYPES = {
     "hhgt_version": (_str, []),
     "hhgt_last_error": (_str, []),
@@ -136,6 +136,19 @@ PROTOTYPES = {
     "hhgt_synth_render_fixed": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _str, _i32, _u64, _vp]),
     "hhgt_synth_render_mixed": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _str, _i32, _u64, _vp]),
     "hhgt_synth_write_bgzf": (_i32, [_str, _vp, _u64, _i32, _i32]),
+    "hhgt_reader_open": (_i32, [_str, _u64, _i32, _i32, _pvp]),
+    "hhgt_reader_close": (None, [_vp]),
+    "hhgt_reader_is_bgzf": (_i32, [_vp]),
+    "hhgt_reader_next": (_i32, [_vp, _pvp, _pu64]),
+    "hhgt_reader_acquire": (_i32, [_vp, _pvp, _pu64, _pi32, _pi32]),
+    "hhgt_reader_release": (_i32, [_vp, _i32]),
+    "hhgt_reader_copy_async": (_i32, [_vp, _vp, _u64, _vp, _vp]),
+    "hhgt_reader_stats": (_i32, [_vp, _pu64, _pu64]),
+    "hhgt_reader_trim_pool": (None, []),
+    "hhgt_reader_prewarm": (_i32, [_u64, _i32]),
+    "hhgt_effective_cpus": (_i32, []),
+    "hhgt_crc32": (_u32, [_vp, _u64]),
+    "hhgt_fast_inflate": (_i32, [_vp, _u64, _vp, _u64]),
 }
 
 _lib = None

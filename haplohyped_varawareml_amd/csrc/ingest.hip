@@ -10,9 +10,9 @@
 // record, the compressed sizes of a batch are read by another thread one stage later, and all staging memory is
 // pinned and reused.
 #include "common.h"
+#include "host_owners.h"
 #include "../../include/hhgt_ingest.h"
 #include "../../include/hhgt_reader.h"
-#include <zlib.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <fcntl.h>
@@ -76,12 +76,8 @@ template <class T> struct BQ {
 };
 
 // What the engine holds on the device and in pinned memory.  Each holder's own code is the only place its resource is released,
-// and none can be copied: a slot cannot free what another still uses.  hhgt_ingest_close synchronises the streams, then deletes.
-struct NoCopy {
-    NoCopy() = default;
-    NoCopy(const NoCopy &) = delete;
-    NoCopy &operator=(const NoCopy &) = delete;
-};
+// and none can be copied (NoCopy, host_owners.h): a slot cannot free what another still uses.  hhgt_ingest_close synchronises
+// the streams, then deletes.
 struct Event : NoCopy {
     hipEvent_t e = nullptr;
     ~Event() { if (e) hipEventDestroy(e); }
@@ -452,29 +448,7 @@ bool wants_device_inflate(int mode, const char *path)
 // ---------------------------------------------------------------------------------------------------------------
 // source thread
 // ---------------------------------------------------------------------------------------------------------------
-// What an early return in this section must not leak.  Each holder's own code is the only place its resource is released.
-struct Fd {
-    int fd = -1;
-    ~Fd() { if (fd >= 0) close(fd); }
-};
-struct Inflater {   // host zlib, raw DEFLATE: one BGZF member per call
-    z_stream zs;
-    Inflater()
-    {
-        memset(&zs, 0, sizeof(zs));
-        inflateInit2(&zs, -15);
-    }
-    ~Inflater() { inflateEnd(&zs); }
-    bool member(const uint8_t *src, uint32_t n_in, uint8_t *dst, uint32_t n_out)
-    {
-        if (inflateReset(&zs) != Z_OK) return false;
-        zs.next_in = const_cast<Bytef *>(src);
-        zs.avail_in = n_in;
-        zs.next_out = dst;
-        zs.avail_out = n_out;
-        return inflate(&zs, Z_FINISH) == Z_STREAM_END && zs.avail_out == 0;
-    }
-};
+// What an early return in this section must not leak: Fd and Inflater (host_owners.h), and the reader's block below.
 struct ReaderBlock {   // a pinned block of the reader: it goes back to the reader once its copy has left it (`copied`)
     hhgt_reader *rd = nullptr;
     int tok = -1;

@@ -11,91 +11,27 @@
 // itself: it inflates the block's LAST member right away (30 us of zlib), finds the last newline in it and thereby
 // knows where the next block's members start.  (Round 1 filled one block at a time with a wake-all / wait-all
 // around it: 48 threads delivered 20 GB/s of text where one delivers 2.2.)
-// Every member's text is hashed and compared with the CRC-32 in its trailer, as htslib's bgzf.c does; the hash is
-// the carry-less-multiply folding form (PCLMULQDQ), an order of magnitude faster than zlib 1.2.11's table crc32()
-// so the check no longer costs as much as the inflate it guards.  Plain gzip streams through one inflater,
-// uncompressed files are pread into the ring by the same worker pool.
+// Every member's text is hashed and compared with the CRC-32 in its trailer, as htslib's bgzf.c does (crc32.h).
+// Plain gzip streams through one inflater, uncompressed files are pread into the ring by the same worker pool.
+//
+// What the reader holds sits in owners (host_owners.h, BlockBuf): open and close have no cleanup code of their own.
 #include "common.h"
 #include "../../include/hhgt_reader.h"
+#include "crc32.h"
 #include "fast_inflate.h"
-#include <zlib.h>
-#include <sys/mman.h>
+#include "host_owners.h"
 #include <sys/stat.h>
 #include <fcntl.h>
-#include <unistd.h>
 #include <sched.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <deque>
 #include <memory>
 #include <mutex>
 #include <thread>
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
-
-namespace {
-
-struct Task {
-    const uint8_t *src = nullptr;
-    uint32_t src_len = 0;
-    uint8_t *dst = nullptr;
-    uint32_t dst_len = 0;
-    int fd = -1;            // >= 0: an uncompressed piece, read with pread(fd, dst, dst_len, file_off)
-    uint64_t file_off = 0;
-    bool check_crc = false;  // BGZF member: compare crc32(dst) with the trailer behind src
-};
-
-// one ring block: its task list is written by the scanner before the block is opened to the workers
-struct Block {
-    uint8_t *buf = nullptr;
-    bool pinned = false;
-    size_t n = 0;                      // published bytes (whole lines)
-    std::vector<Task> tasks;
-    // generation << 32 | next task to draw.  Workers advance it by compare-and-swap against the generation they were
-    // given with the block, so a worker that still holds a recycled block can neither run a task of its next life
-    // nor swallow one of its tickets
-    std::atomic<uint64_t> ticket{0};
-    std::atomic<uint32_t> done{0};     // tasks finished
-    uint32_t gen = 0;
-    uint32_t n_tasks = 0;
-    bool scanned = false;              // layout complete (n, n_tasks final)
-    bool last = false;                 // last block of the input
-};
-
-}  // namespace
-
-struct hhgt_reader {
-    int fd = -1;
-    const uint8_t *map = nullptr;
-    size_t map_len = 0;
-    size_t in_pos = 0;  // next unread compressed byte
-    bool is_gzip = false, is_bgzf = false;
-    bool check_crc = true;   // HHGT_BGZF_NO_CRC=1 skips the per-member CRC32 (htslib always checks it)
-    size_t block_bytes = 0;
-    bool pinned = false;
-    int n_blocks = 0;
-    std::unique_ptr<Block[]> ring;
-    // block life cycle: free_ -> (scanner) open_ (workers draw tasks) -> order (publication order) -> held by the
-    // consumer -> free_
-    std::deque<int> free_, open_, order;
-    std::vector<char> held;          // per block: 1 while the consumer holds it
-    int auto_held = -1;              // block handed out by hhgt_reader_next (released by the following call)
-    bool eof = false, stop = false;  // eof: the scanner has laid out the last block
-    int error = 0;
-    std::string errmsg;
-    std::mutex mu;                   // guards the deques, eof/stop/error
-    std::condition_variable cv_free, cv_open, cv_pub;
-    std::thread producer;
-    std::vector<std::thread> workers;
-    // plain gzip state
-    z_stream zs;
-    bool zs_init = false;
-    std::atomic<uint64_t> text_bytes{0};
-};
 
 // Pinned ring blocks are expensive to make (hipHostMalloc pins page by page) and a converter opens one reader per
 // chromosome file: closed readers park their blocks here and the next open takes them back.
@@ -126,7 +62,7 @@ static bool pool_give(size_t bytes, void *p)
 extern "C" void hhgt_reader_trim_pool(void)
 {
     std::lock_guard<std::mutex> lk(g_pool_mu);
-    for (auto &e : g_pool) hipHostFree(e.second);
+    for (auto &e : g_pool) (void)hipHostFree(e.second);
     g_pool.clear();
 }
 
@@ -144,7 +80,7 @@ extern "C" int hhgt_reader_prewarm(uint64_t block_bytes, int n_blocks)
         void *p = nullptr;
         if (hipHostMalloc(&p, (size_t)block_bytes, hipHostMallocDefault) != hipSuccess) break;
         if (!pool_give((size_t)block_bytes, p)) {
-            hipHostFree(p);
+            (void)hipHostFree(p);
             break;
         }
         ++have;
@@ -152,197 +88,150 @@ extern "C" int hhgt_reader_prewarm(uint64_t block_bytes, int n_blocks)
     return have;
 }
 
+namespace {
+
+// a ring block's memory, which knows how it goes back: pinned to the pool (or hipHostFree when that is full), pageable to free
+struct BlockBuf : NoCopy {
+    uint8_t *p = nullptr;
+    size_t bytes = 0;
+    bool pinned = false;
+    // Pinned, from the pool or fresh, while *pin holds.  The first hipHostMalloc that fails clears it: that block and the
+    // later ones are pageable, the earlier ones stay pinned.
+    bool make(size_t n, bool *pin)
+    {
+        void *m = *pin ? pool_take(n) : nullptr;
+        if (!m && *pin && hipHostMalloc(&m, n, hipHostMallocDefault) != hipSuccess) {
+            *pin = false;
+            m = nullptr;
+        }
+        pinned = m != nullptr;
+        if (!m) m = malloc(n);
+        p = static_cast<uint8_t *>(m);
+        bytes = n;
+        return p != nullptr;
+    }
+    ~BlockBuf()
+    {
+        if (!p) return;
+        if (!pinned) free(p);
+        else if (!pool_give(bytes, p)) (void)hipHostFree(p);
+    }
+};
+
+struct Task {
+    const uint8_t *src = nullptr;
+    uint32_t src_len = 0;
+    uint8_t *dst = nullptr;
+    uint32_t dst_len = 0;
+    int fd = -1;            // >= 0: an uncompressed piece, read with pread(fd, dst, dst_len, file_off)
+    uint64_t file_off = 0;
+    bool check_crc = false;  // BGZF member: compare crc32(dst) with the trailer behind src
+};
+
+// one ring block: its task list is written by the scanner before the block is opened to the workers
+struct Block {
+    BlockBuf buf;
+    size_t n = 0;                      // published bytes (whole lines)
+    std::vector<Task> tasks;
+    // generation << 32 | next task to draw.  Workers advance it by compare-and-swap against the generation they were
+    // given with the block, so a worker that still holds a recycled block can neither run a task of its next life
+    // nor swallow one of its tickets
+    std::atomic<uint64_t> ticket{0};
+    std::atomic<uint32_t> done{0};     // tasks finished
+    uint32_t gen = 0;
+    uint32_t n_tasks = 0;
+    bool scanned = false;              // layout complete (n, n_tasks final)
+    bool last = false;                 // last block of the input
+    bool held = false;                 // in the consumer's hands
+};
+
+// every text a read can fail with
+const char *const ERR_LONG_LINE = "a line is longer than the reader's block size";
+const char *const ERR_HEADER = "corrupt BGZF block header";
+const char *const ERR_TRUNCATED = "truncated compressed input";
+const char *const ERR_INFLATE = "inflate failed";
+const char *const ERR_CRC = "BGZF member: CRC32 checksum mismatch";
+
+}  // namespace
+
+struct hhgt_reader {
+    Fd file;
+    Mapping map;
+    bool is_gzip = false, is_bgzf = false;
+    bool check_crc = true;   // HHGT_BGZF_NO_CRC=1 skips the per-member CRC32 (htslib always checks it)
+    size_t block_bytes = 0;
+    int n_blocks = 0;
+    std::unique_ptr<Block[]> ring;
+    // block life cycle: free_ -> (scanner) open_ (workers draw tasks) -> order (publication order) -> held by the
+    // consumer -> free_
+    std::deque<int> free_, open_, order;
+    int auto_held = -1;              // block handed out by hhgt_reader_next (released by the following call)
+    bool eof = false, stop = false;  // eof: the scanner has laid out the last block
+    int error = 0;
+    std::string errmsg;
+    std::mutex mu;                   // guards the deques, eof/stop/error and the blocks' `held`
+    std::condition_variable cv_free, cv_open, cv_pub;
+    std::thread producer;
+    std::vector<std::thread> workers;
+    // totals for hhgt_reader_stats, published by the scanner with each block (its own cursor is private to it)
+    std::atomic<uint64_t> file_bytes{0}, text_bytes{0};
+};
+
+// one cgroup's CPU quota: false when the cgroup has no such file, *quota stays <= 0 when the file sets none
+static bool cgroup_v2_quota(long long *quota, long long *period)
+{
+    FILE *fp = fopen("/sys/fs/cgroup/cpu.max", "r");
+    if (!fp) return false;
+    char a[64] = "", b[64] = "";
+    const int got = fscanf(fp, "%63s %63s", a, b);
+    fclose(fp);
+    if (got >= 1 && strcmp(a, "max") != 0) *quota = atoll(a);
+    if (got >= 2) *period = atoll(b);
+    return true;
+}
+
+static bool cgroup_v1_quota(long long *quota, long long *period)
+{
+    FILE *fp = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r");
+    if (!fp) return false;
+    char a[64] = "";
+    if (fscanf(fp, "%63s", a) == 1) *quota = atoll(a);
+    fclose(fp);
+    fp = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r");
+    if (fp) {
+        if (fscanf(fp, "%63s", a) == 1) *period = atoll(a);
+        fclose(fp);
+    }
+    return true;
+}
+
 // CPUs this process may actually use: the affinity mask, capped by the cgroup's CPU quota (a GPU box of this pool
 // shows 256 hardware threads and grants 16 CPUs' worth of time: 96 inflate threads on it only fight each other)
 extern "C" int hhgt_effective_cpus(void)
 {
     int n = (int)std::thread::hardware_concurrency();
+    auto cap = [&n](long long k) {
+        if (k > 0 && (n <= 0 || k < n)) n = (int)k;
+    };
     cpu_set_t set;
     CPU_ZERO(&set);
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) {
-        const int k = CPU_COUNT(&set);
-        if (k > 0 && (n <= 0 || k < n)) n = k;
-    }
-    const char *files[] = {"/sys/fs/cgroup/cpu.max", "/sys/fs/cgroup/cpu/cpu.cfs_quota_us"};
-    for (int f = 0; f < 2; ++f) {
-        FILE *fp = fopen(files[f], "r");
-        if (!fp) continue;
-        char a[64] = "", b[64] = "";
-        const int got = fscanf(fp, "%63s %63s", a, b);
-        fclose(fp);
-        long long quota = -1, period = 100000;
-        if (f == 0) {
-            if (got >= 1 && strcmp(a, "max") != 0) quota = atoll(a);
-            if (got >= 2) period = atoll(b);
-        } else {
-            if (got >= 1) quota = atoll(a);
-            FILE *pp = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r");
-            if (pp) {
-                if (fscanf(pp, "%63s", b) == 1) period = atoll(b);
-                fclose(pp);
-            }
-        }
-        if (quota > 0 && period > 0) {
-            const int k = (int)((quota + period - 1) / period);
-            if (k > 0 && (n <= 0 || k < n)) n = k;
-        }
-        break;
-    }
+    if (sched_getaffinity(0, sizeof(set), &set) == 0) cap(CPU_COUNT(&set));
+    long long quota = -1, period = 100000;
+    if (!cgroup_v2_quota(&quota, &period)) cgroup_v1_quota(&quota, &period);
+    if (quota > 0 && period > 0) cap((int)((quota + period - 1) / period));
     return n > 0 ? n : 1;
 }
-
-static bool looks_bgzf(const uint8_t *p, size_t n)
-{
-    return n >= 18 && p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && (p[3] & 4) && p[10] == 6 && p[11] == 0 &&
-           p[12] == 'B' && p[13] == 'C' && p[14] == 2 && p[15] == 0;
-}
-
-// ---- CRC-32 (RFC 1952) --------------------------------------------------------------------------------------------
-// table form, sixteen bytes per step (portable path and tails)
-static uint32_t g_crc_tab[16][256];
-static std::once_flag g_crc_once;
-
-static void crc_init()
-{
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-        g_crc_tab[0][i] = c;
-    }
-    for (int t = 1; t < 16; ++t)
-        for (uint32_t i = 0; i < 256; ++i) g_crc_tab[t][i] = (g_crc_tab[t - 1][i] >> 8) ^ g_crc_tab[0][g_crc_tab[t - 1][i] & 0xFFu];
-}
-
-// raw update: c is the running register (already inverted), returns the register
-static uint32_t crc32_table_update(uint32_t c, const uint8_t *p, size_t n)
-{
-    std::call_once(g_crc_once, crc_init);
-    const uint32_t(*T)[256] = g_crc_tab;
-    while (n >= 16) {
-        uint32_t a, b, d, e;
-        memcpy(&a, p, 4);
-        memcpy(&b, p + 4, 4);
-        memcpy(&d, p + 8, 4);
-        memcpy(&e, p + 12, 4);
-        a ^= c;
-        c = T[15][a & 0xFFu] ^ T[14][(a >> 8) & 0xFFu] ^ T[13][(a >> 16) & 0xFFu] ^ T[12][a >> 24] ^
-            T[11][b & 0xFFu] ^ T[10][(b >> 8) & 0xFFu] ^ T[9][(b >> 16) & 0xFFu] ^ T[8][b >> 24] ^
-            T[7][d & 0xFFu] ^ T[6][(d >> 8) & 0xFFu] ^ T[5][(d >> 16) & 0xFFu] ^ T[4][d >> 24] ^
-            T[3][e & 0xFFu] ^ T[2][(e >> 8) & 0xFFu] ^ T[1][(e >> 16) & 0xFFu] ^ T[0][e >> 24];
-        p += 16;
-        n -= 16;
-    }
-    while (n--) c = T[0][(c ^ *p++) & 0xFFu] ^ (c >> 8);
-    return c;
-}
-
-#if defined(__x86_64__)
-// Carry-less-multiply folding (Gopal et al., "Fast CRC Computation for Generic Polynomials Using PCLMULQDQ", the
-// scheme zlib-ng / Chromium's zlib use): four 128-bit lanes are folded over the input 64 bytes per step, then
-// into one lane, then reduced to 32 bits (Barrett).  Constants are x^k mod P for the bit-reflected polynomial
-// 0xEDB88320.  n >= 64 and n % 16 == 0; the caller feeds the tail through the table form.
-__attribute__((target("pclmul,sse4.1"))) static uint32_t crc32_clmul_update(uint32_t crc, const uint8_t *buf, size_t len)
-{
-    const __m128i k1k2 = _mm_set_epi64x(0x00000001c6e41596, 0x0000000154442bd4);
-    const __m128i k3k4 = _mm_set_epi64x(0x00000000ccaa009e, 0x00000001751997d0);
-    const __m128i k5k0 = _mm_set_epi64x(0x0000000000000000, 0x0000000163cd6124);
-    const __m128i poly = _mm_set_epi64x(0x00000001f7011641, 0x00000001db710641);
-    __m128i x0, x1, x2, x3, x4, x5, x6, x7, x8, y5, y6, y7, y8;
-    x1 = _mm_loadu_si128((const __m128i *)(buf + 0x00));
-    x2 = _mm_loadu_si128((const __m128i *)(buf + 0x10));
-    x3 = _mm_loadu_si128((const __m128i *)(buf + 0x20));
-    x4 = _mm_loadu_si128((const __m128i *)(buf + 0x30));
-    x1 = _mm_xor_si128(x1, _mm_cvtsi32_si128((int)crc));
-    x0 = k1k2;
-    buf += 64;
-    len -= 64;
-    while (len >= 64) {   // fold four lanes in parallel
-        x5 = _mm_clmulepi64_si128(x1, x0, 0x00);
-        x6 = _mm_clmulepi64_si128(x2, x0, 0x00);
-        x7 = _mm_clmulepi64_si128(x3, x0, 0x00);
-        x8 = _mm_clmulepi64_si128(x4, x0, 0x00);
-        x1 = _mm_clmulepi64_si128(x1, x0, 0x11);
-        x2 = _mm_clmulepi64_si128(x2, x0, 0x11);
-        x3 = _mm_clmulepi64_si128(x3, x0, 0x11);
-        x4 = _mm_clmulepi64_si128(x4, x0, 0x11);
-        y5 = _mm_loadu_si128((const __m128i *)(buf + 0x00));
-        y6 = _mm_loadu_si128((const __m128i *)(buf + 0x10));
-        y7 = _mm_loadu_si128((const __m128i *)(buf + 0x20));
-        y8 = _mm_loadu_si128((const __m128i *)(buf + 0x30));
-        x1 = _mm_xor_si128(_mm_xor_si128(x1, x5), y5);
-        x2 = _mm_xor_si128(_mm_xor_si128(x2, x6), y6);
-        x3 = _mm_xor_si128(_mm_xor_si128(x3, x7), y7);
-        x4 = _mm_xor_si128(_mm_xor_si128(x4, x8), y8);
-        buf += 64;
-        len -= 64;
-    }
-    x0 = k3k4;   // fold the four lanes into one
-    x5 = _mm_clmulepi64_si128(x1, x0, 0x00);
-    x1 = _mm_clmulepi64_si128(x1, x0, 0x11);
-    x1 = _mm_xor_si128(_mm_xor_si128(x1, x2), x5);
-    x5 = _mm_clmulepi64_si128(x1, x0, 0x00);
-    x1 = _mm_clmulepi64_si128(x1, x0, 0x11);
-    x1 = _mm_xor_si128(_mm_xor_si128(x1, x3), x5);
-    x5 = _mm_clmulepi64_si128(x1, x0, 0x00);
-    x1 = _mm_clmulepi64_si128(x1, x0, 0x11);
-    x1 = _mm_xor_si128(_mm_xor_si128(x1, x4), x5);
-    while (len >= 16) {   // single-lane folds over the remaining 16-byte pieces
-        x2 = _mm_loadu_si128((const __m128i *)buf);
-        x5 = _mm_clmulepi64_si128(x1, x0, 0x00);
-        x1 = _mm_clmulepi64_si128(x1, x0, 0x11);
-        x1 = _mm_xor_si128(_mm_xor_si128(x1, x2), x5);
-        buf += 16;
-        len -= 16;
-    }
-    // 128 -> 64 bits
-    x2 = _mm_clmulepi64_si128(x1, x0, 0x10);
-    x3 = _mm_setr_epi32(~0, 0, ~0, 0);
-    x1 = _mm_srli_si128(x1, 8);
-    x1 = _mm_xor_si128(x1, x2);
-    x0 = k5k0;
-    x2 = _mm_srli_si128(x1, 4);
-    x1 = _mm_and_si128(x1, x3);
-    x1 = _mm_clmulepi64_si128(x1, x0, 0x00);
-    x1 = _mm_xor_si128(x1, x2);
-    // Barrett reduction 64 -> 32 bits
-    x0 = poly;
-    x2 = _mm_and_si128(x1, x3);
-    x2 = _mm_clmulepi64_si128(x2, x0, 0x10);
-    x2 = _mm_and_si128(x2, x3);
-    x2 = _mm_clmulepi64_si128(x2, x0, 0x00);
-    x1 = _mm_xor_si128(x1, x2);
-    return (uint32_t)_mm_extract_epi32(x1, 1);
-}
-
-static bool have_clmul()
-{
-    static const bool ok = __builtin_cpu_supports("pclmul") && __builtin_cpu_supports("sse4.1");
-    return ok;
-}
-#endif
 
 extern "C" int hhgt_fast_inflate(const void *in, uint64_t in_len, void *out, uint64_t out_len)
 {
     return hhgt_fast_inflate_impl(static_cast<const uint8_t *>(in), (size_t)in_len, static_cast<uint8_t *>(out), (size_t)out_len);
 }
 
-extern "C" uint32_t hhgt_crc32(const void *data, uint64_t n)
-{
-    const uint8_t *p = static_cast<const uint8_t *>(data);
-    uint32_t c = 0xFFFFFFFFu;
-#if defined(__x86_64__)
-    if (n >= 64 && have_clmul()) {
-        const size_t body = (size_t)n & ~(size_t)15;
-        c = crc32_clmul_update(c, p, body);
-        p += body;
-        n -= body;
-    }
-#endif
-    return ~crc32_table_update(c, p, (size_t)n);
-}
+extern "C" uint32_t hhgt_crc32(const void *data, uint64_t n) { return hhgt_crc::crc32(data, (size_t)n); }
 
 // ---- tasks --------------------------------------------------------------------------------------------------------
-static int run_task(z_stream *zs, const Task &t)
+// nullptr, or the text the read fails with
+static const char *run_task(Inflater &z, const Task &t)
 {
     if (t.fd >= 0) {
         // plain-text piece of an uncompressed file: pread straight into the pinned block.  (A memcpy out of the
@@ -350,31 +239,24 @@ static int run_task(z_stream *zs, const Task &t)
         size_t got = 0;
         while (got < t.dst_len) {
             ssize_t k = pread(t.fd, t.dst + got, t.dst_len - got, (off_t)(t.file_off + got));
-            if (k <= 0) return -1;
+            if (k <= 0) return ERR_INFLATE;
             got += (size_t)k;
         }
-        return 0;
+        return nullptr;
     }
     // own decoder first (fast_inflate.h: ~4x zlib on genotype text); whatever it does not accept goes to zlib, which
     // stays the arbiter of what is a corrupt member (HHGT_ZLIB_INFLATE=1: zlib only)
     static const bool zlib_only = getenv("HHGT_ZLIB_INFLATE") && atoi(getenv("HHGT_ZLIB_INFLATE")) != 0;
-    if (zlib_only || hhgt_fast_inflate_impl(t.src, t.src_len, t.dst, t.dst_len) != 0) {
-        if (inflateReset(zs) != Z_OK) return -1;
-        zs->next_in = const_cast<Bytef *>(t.src);
-        zs->avail_in = t.src_len;
-        zs->next_out = t.dst;
-        zs->avail_out = t.dst_len;
-        int rc = inflate(zs, Z_FINISH);
-        if (rc != Z_STREAM_END || zs->avail_out != 0) return -1;
-    }
+    if ((zlib_only || hhgt_fast_inflate_impl(t.src, t.src_len, t.dst, t.dst_len) != 0) && !z.member(t.src, t.src_len, t.dst, t.dst_len))
+        return ERR_INFLATE;
     if (t.check_crc) {
         // the member's trailer (CRC32, ISIZE) follows the payload; htslib's bgzf.c rejects a member whose text does
         // not hash to it ("CRC32 checksum mismatch")
         const uint8_t *tr = t.src + t.src_len;
         const uint32_t want = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-        if (hhgt_crc32(t.dst, t.dst_len) != want) return -2;
+        if (hhgt_crc::crc32(t.dst, t.dst_len) != want) return ERR_CRC;
     }
-    return 0;
+    return nullptr;
 }
 
 static void set_error(hhgt_reader *r, const char *msg)
@@ -394,9 +276,7 @@ static void set_error(hhgt_reader *r, const char *msg)
 
 static void worker_main(hhgt_reader *r)
 {
-    z_stream zs;
-    memset(&zs, 0, sizeof(zs));
-    inflateInit2(&zs, -15);
+    Inflater z;
     for (;;) {
         int bi;
         uint32_t gen, n_tasks;
@@ -421,10 +301,8 @@ static void worker_main(hhgt_reader *r)
             if (!got) break;
             const uint32_t t0 = (uint32_t)cur;
             const uint32_t t1 = t0 + TASK_BATCH < n_tasks ? t0 + TASK_BATCH : n_tasks;
-            for (uint32_t t = t0; t < t1; ++t) {
-                const int rc = run_task(&zs, b.tasks[t]);
-                if (rc != 0) set_error(r, rc == -2 ? "BGZF member: CRC32 checksum mismatch" : "inflate failed");
-            }
+            for (uint32_t t = t0; t < t1; ++t)
+                if (const char *err = run_task(z, b.tasks[t])) set_error(r, err);
             if (b.done.fetch_add(t1 - t0) + (t1 - t0) == n_tasks) {
                 std::lock_guard<std::mutex> lk(r->mu);   // the block's last task: it may be published now
                 r->cv_pub.notify_all();
@@ -435,10 +313,10 @@ static void worker_main(hhgt_reader *r)
             if (!r->open_.empty() && r->open_.front() == bi && r->ring[bi].gen == gen) r->open_.pop_front();
         }
     }
-    inflateEnd(&zs);
 }
 
-// scanner side: a free block (waits), or -1 when the reader is closing
+// ---- scanner: the steps every source shares ---------------------------------------------------------------------
+// a free block (waits), or -1 when the reader is closing
 static int take_free(hhgt_reader *r)
 {
     std::unique_lock<std::mutex> lk(r->mu);
@@ -477,207 +355,220 @@ static void open_block(hhgt_reader *r, int bi, size_t pub, bool last)
     r->cv_pub.notify_all();
 }
 
+// offset behind the last newline of p[0, n), or 0 when there is none
+static size_t line_end(const uint8_t *p, size_t n)
+{
+    const void *nl = n ? memrchr(p, '\n', n) : nullptr;
+    return nl ? (size_t)((const uint8_t *)nl - p) + 1 : 0;
+}
+
+namespace {
+// The block the scanner is laying out, and what it carries from block to block: its place in the file and the partial last
+// line.  A source calls begin(), lays out `n` bytes behind the carried ones, looks for the last newline where it may (BGZF: in
+// members, inflated from the back; gzip: in the block; plain: in the mapping, before anything is read) and calls cut().
+struct Scan : NoCopy {
+    hhgt_reader *const r;
+    size_t pos = 0;               // next unread byte of the file
+    std::vector<uint8_t> carry;   // bytes behind the previous block's last newline: they hold none
+    int bi = -1;
+    Block *b = nullptr;
+    size_t n = 0;                 // bytes laid out in *b
+    explicit Scan(hhgt_reader *r_) : r(r_) {}
+    bool input_done() const { return pos >= r->map.len; }
+    size_t room() const { return r->block_bytes - n; }
+    // a free block with the carried bytes at its front; false when the reader is closing
+    bool begin()
+    {
+        bi = take_free(r);
+        if (bi < 0) return false;
+        b = &r->ring[bi];
+        n = carry.size();
+        if (n) memcpy(b->buf.p, carry.data(), n);
+        carry.clear();
+        return true;
+    }
+    // The line cut.  `end` = offset in the block behind the last newline the source found, 0 for none.  Publishes the block up
+    // to there and carries the rest — all of it when it is the last of the input, final newline or not — or fails the read: a
+    // line that does not end in this block does not fit any.  false: the scanner is done.
+    bool cut(size_t end, bool last)
+    {
+        if (last) end = n;
+        else if (!end) {
+            set_error(r, ERR_LONG_LINE);
+            return false;
+        }
+        carry.assign(b->buf.p + end, b->buf.p + n);
+        r->file_bytes.store(pos);
+        open_block(r, bi, end, last);
+        return !last;
+    }
+};
+}  // namespace
+
 // ---- BGZF: barrier-free scanner --------------------------------------------------------------------------------
+static bool looks_bgzf(const uint8_t *p, size_t n)
+{
+    return n >= 18 && p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && (p[3] & 4) && p[10] == 6 && p[11] == 0 &&
+           p[12] == 'B' && p[13] == 'C' && p[14] == 2 && p[15] == 0;
+}
+
+// The member at p, of which `left` bytes are mapped: its payload and the size of its text (ISIZE) as a task that still lacks
+// its place in a block, and the member's whole size; or the text the read fails with.
+static const char *parse_member(const uint8_t *p, size_t left, Task *t, size_t *size)
+{
+    if (!looks_bgzf(p, left)) return ERR_HEADER;
+    *size = (size_t)((uint32_t)p[16] | ((uint32_t)p[17] << 8)) + 1;
+    if (*size > left || *size < 26) return ERR_TRUNCATED;
+    const uint8_t *tr = p + *size - 4;
+    t->dst_len = (uint32_t)tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
+    if (t->dst_len > 65536) return ERR_INFLATE;
+    t->src = p + 18;
+    t->src_len = (uint32_t)(*size - 18 - 8);
+    return nullptr;
+}
+
+// members become tasks while their text fits the block
+static const char *lay_out_members(Scan &s)
+{
+    const hhgt_reader *r = s.r;
+    while (!s.input_done()) {
+        Task t;
+        size_t size;
+        if (const char *err = parse_member(r->map.p + s.pos, r->map.len - s.pos, &t, &size)) return err;
+        if (t.dst_len > s.room()) break;
+        t.dst = s.b->buf.p + s.n;
+        t.check_crc = r->check_crc;
+        if (t.dst_len) s.b->tasks.push_back(t);
+        s.n += t.dst_len;
+        s.pos += size;
+    }
+    return nullptr;
+}
+
+// Where does the last whole line end?  Inflate members from the back (normally just the last one) until one holds a
+// newline; they are done here, so they leave the task list.  *end stays 0 when no member holds one: the carried bytes in
+// front of them hold none either (Scan::carry), so no line ends in this block.
+static const char *last_line_end(Block &b, Inflater &z, size_t *end)
+{
+    while (!*end && !b.tasks.empty()) {
+        const Task t = b.tasks.back();
+        b.tasks.pop_back();
+        if (const char *err = run_task(z, t)) return err;
+        if (const size_t e = line_end(t.dst, t.dst_len)) *end = (size_t)(t.dst - b.buf.p) + e;
+    }
+    return nullptr;
+}
+
 static void scan_bgzf(hhgt_reader *r)
 {
-    std::vector<uint8_t> carry;   // partial last line of the previous block
-    z_stream zs;
-    memset(&zs, 0, sizeof(zs));
-    inflateInit2(&zs, -15);
-    bool input_done = r->in_pos >= r->map_len;
-    while (!input_done) {
-        const int bi = take_free(r);
-        if (bi < 0) break;
-        Block &b = r->ring[bi];
-        size_t n = carry.size();
-        if (n) memcpy(b.buf, carry.data(), n);
-        carry.clear();
-        const size_t first_member_at = n;
-        // lay out members while they fit
-        while (r->in_pos < r->map_len) {
-            const uint8_t *p = r->map + r->in_pos;
-            const size_t left = r->map_len - r->in_pos;
-            if (!looks_bgzf(p, left)) {
-                set_error(r, "corrupt BGZF block header");
-                inflateEnd(&zs);
-                return;
-            }
-            const uint32_t bsize = (uint32_t)p[16] | ((uint32_t)p[17] << 8);
-            const size_t total = (size_t)bsize + 1;
-            if (total > left || total < 26) {
-                set_error(r, "truncated compressed input");
-                inflateEnd(&zs);
-                return;
-            }
-            const uint32_t isize = (uint32_t)p[total - 4] | ((uint32_t)p[total - 3] << 8) | ((uint32_t)p[total - 2] << 16) |
-                                   ((uint32_t)p[total - 1] << 24);
-            if (isize > 65536) {
-                set_error(r, "inflate failed");
-                inflateEnd(&zs);
-                return;
-            }
-            if (n + isize > r->block_bytes) break;
-            if (isize) {
-                Task t;
-                t.src = p + 18;
-                t.src_len = (uint32_t)(total - 18 - 8);
-                t.dst = b.buf + n;
-                t.dst_len = isize;
-                t.check_crc = r->check_crc;
-                b.tasks.push_back(t);
-            }
-            n += isize;
-            r->in_pos += total;
-        }
-        input_done = r->in_pos >= r->map_len;
-        if (b.tasks.empty() && !input_done) {
-            set_error(r, "a line is longer than the reader's block size");
-            break;
-        }
-        size_t pub = n;
-        if (!input_done) {
-            // Where does the last whole line end?  Inflate members from the back (normally just the last one) until
-            // one holds a newline; they are done here, so they leave the task list.
-            size_t cut = (size_t)-1;
-            while (!b.tasks.empty()) {
-                const Task t = b.tasks.back();
-                b.tasks.pop_back();
-                const int rc = run_task(&zs, t);
-                if (rc != 0) {
-                    set_error(r, rc == -2 ? "BGZF member: CRC32 checksum mismatch" : "inflate failed");
-                    inflateEnd(&zs);
-                    return;
-                }
-                const void *nl = memrchr(t.dst, '\n', t.dst_len);
-                if (nl) {
-                    cut = (size_t)((const uint8_t *)nl - b.buf) + 1;
-                    break;
-                }
-            }
-            if (cut == (size_t)-1) {
-                // no newline in any member of this block: only the carried bytes may hold one
-                const void *nl = first_member_at ? memrchr(b.buf, '\n', first_member_at) : nullptr;
-                if (!nl) {
-                    set_error(r, "a line is longer than the reader's block size");
-                    break;
-                }
-                cut = (size_t)((const uint8_t *)nl - b.buf) + 1;
-            }
-            pub = cut;
-            carry.assign(b.buf + cut, b.buf + n);
-        }
-        open_block(r, bi, pub, input_done);
-    }
-    inflateEnd(&zs);
-    if (input_done) {
-        std::lock_guard<std::mutex> lk(r->mu);
-        r->eof = true;
-        r->cv_pub.notify_all();
-    }
+    Scan s(r);
+    Inflater z;
+    size_t end;
+    do {
+        if (!s.begin()) return;
+        const char *err = lay_out_members(s);
+        end = 0;
+        if (!err && !s.input_done()) err = last_line_end(*s.b, z, &end);
+        if (err) return set_error(r, err);
+    } while (s.cut(end, s.input_done()));
 }
 
 // ---- plain gzip (one stream) and uncompressed input ------------------------------------------------------------
-static long long fill_gzip(hhgt_reader *r, uint8_t *dst, size_t cap)
+// inflates into dst[0, cap) until it is full or the file ends; a gzip member may follow another
+static const char *fill_gzip(Scan &s, GzipInflater &z, uint8_t *dst, size_t cap, size_t *produced)
 {
-    size_t produced = 0;
-    while (produced < cap) {
-        if (!r->zs_init) {
-            if (r->in_pos >= r->map_len) break;
-            memset(&r->zs, 0, sizeof(r->zs));
-            if (inflateInit2(&r->zs, 15 + 32) != Z_OK) return -1;
-            r->zs_init = true;
+    const Mapping &map = s.r->map;
+    *produced = 0;
+    while (*produced < cap) {
+        if (!z.open) {
+            if (s.input_done()) break;
+            if (!z.begin()) return ERR_INFLATE;
         }
-        size_t in_avail = r->map_len - r->in_pos;
-        uInt chunk_in = in_avail > (1u << 30) ? (1u << 30) : (uInt)in_avail;
-        size_t out_avail = cap - produced;
-        uInt chunk_out = out_avail > (1u << 30) ? (1u << 30) : (uInt)out_avail;
-        r->zs.next_in = const_cast<Bytef *>(r->map + r->in_pos);
-        r->zs.avail_in = chunk_in;
-        r->zs.next_out = dst + produced;
-        r->zs.avail_out = chunk_out;
-        int rc = inflate(&r->zs, Z_NO_FLUSH);
-        r->in_pos += chunk_in - r->zs.avail_in;
-        produced += chunk_out - r->zs.avail_out;
+        const uInt chunk_in = (uInt)std::min<size_t>(map.len - s.pos, 1u << 30);
+        const uInt chunk_out = (uInt)std::min<size_t>(cap - *produced, 1u << 30);
+        z.zs.next_in = const_cast<Bytef *>(map.p + s.pos);
+        z.zs.avail_in = chunk_in;
+        z.zs.next_out = dst + *produced;
+        z.zs.avail_out = chunk_out;
+        const int rc = inflate(&z.zs, Z_NO_FLUSH);
+        s.pos += chunk_in - z.zs.avail_in;
+        *produced += chunk_out - z.zs.avail_out;
         if (rc == Z_STREAM_END) {  // gzip member finished; another may follow
-            inflateEnd(&r->zs);
-            r->zs_init = false;
+            z.end();
             continue;
         }
-        if (rc == Z_BUF_ERROR && chunk_in == 0) return -2;  // truncated file
-        if (rc != Z_OK && rc != Z_BUF_ERROR) return -1;
-        if (r->in_pos >= r->map_len && r->zs.avail_out != 0) return -2;  // input exhausted mid-member
+        if (rc == Z_BUF_ERROR && chunk_in == 0) return ERR_TRUNCATED;
+        if (rc != Z_OK && rc != Z_BUF_ERROR) return ERR_INFLATE;
+        if (s.input_done() && z.zs.avail_out != 0) return ERR_TRUNCATED;   // input exhausted mid-member
     }
-    return (long long)produced;
+    return nullptr;
 }
 
-static void scan_stream(hhgt_reader *r)
+static void scan_gzip(hhgt_reader *r)
 {
-    std::vector<uint8_t> carry;
-    bool input_done = r->map_len == 0;
-    while (!input_done) {
-        const int bi = take_free(r);
-        if (bi < 0) return;
-        Block &b = r->ring[bi];
-        size_t n = carry.size();
-        if (n) memcpy(b.buf, carry.data(), n);
-        carry.clear();
-        size_t pub;
-        if (r->is_gzip) {
-            const long long got = fill_gzip(r, b.buf + n, r->block_bytes - n);
-            if (got < 0) {
-                set_error(r, got == -2 ? "truncated compressed input" : "inflate failed");
-                return;
-            }
-            n += (size_t)got;
-            input_done = r->in_pos >= r->map_len && !r->zs_init;
-            if (got == 0 && !input_done) input_done = r->in_pos >= r->map_len;
-            pub = n;
-            if (!input_done) {
-                const void *nl = n ? memrchr(b.buf, '\n', n) : nullptr;
-                if (!nl) {
-                    set_error(r, "a line is longer than the reader's block size");
-                    return;
-                }
-                pub = (size_t)((const uint8_t *)nl - b.buf) + 1;
-                carry.assign(b.buf + pub, b.buf + n);
-            }
-        } else {
-            // uncompressed: the cut is found in the mapping itself, the bytes are pread by the workers
-            const size_t avail = r->map_len - r->in_pos;
-            size_t take = avail < r->block_bytes - n ? avail : r->block_bytes - n;
-            input_done = take == avail;
-            if (!input_done) {
-                const void *nl = memrchr(r->map + r->in_pos, '\n', take);
-                if (!nl) {
-                    set_error(r, "a line is longer than the reader's block size");
-                    return;
-                }
-                take = (size_t)((const uint8_t *)nl - (r->map + r->in_pos)) + 1;
-            }
-            const size_t piece = 4u << 20;
-            for (size_t o = 0; o < take; o += piece) {
-                Task t;
-                t.dst = b.buf + n + o;
-                t.dst_len = (uint32_t)(take - o < piece ? take - o : piece);
-                t.fd = r->fd;
-                t.file_off = r->in_pos + o;
-                b.tasks.push_back(t);
-            }
-            r->in_pos += take;
-            n += take;
-            pub = n;
+    Scan s(r);
+    GzipInflater z;
+    bool last;
+    do {
+        if (!s.begin()) return;
+        size_t got = 0;
+        if (const char *err = fill_gzip(s, z, s.b->buf.p + s.n, s.room(), &got)) return set_error(r, err);
+        s.n += got;
+        last = s.input_done() && (!z.open || got == 0);
+    } while (s.cut(line_end(s.b->buf.p, s.n), last));
+}
+
+// uncompressed: the cut is found in the mapping itself, the bytes are pread by the workers in pieces of 4 MiB
+static void scan_plain(hhgt_reader *r)
+{
+    Scan s(r);
+    size_t take;
+    bool last;
+    do {
+        if (!s.begin()) return;
+        take = std::min(r->map.len - s.pos, s.room());
+        last = s.pos + take == r->map.len;
+        if (!last) take = line_end(r->map.p + s.pos, take);
+        const size_t piece = 4u << 20;
+        for (size_t o = 0; o < take; o += piece) {
+            Task t;
+            t.dst = s.b->buf.p + s.n + o;
+            t.dst_len = (uint32_t)std::min(take - o, piece);
+            t.fd = r->file.fd;
+            t.file_off = s.pos + o;
+            s.b->tasks.push_back(t);
         }
-        open_block(r, bi, pub, input_done);
-    }
-    std::lock_guard<std::mutex> lk(r->mu);
-    r->eof = true;
-    r->cv_pub.notify_all();
+        s.pos += take;
+        s.n += take;
+    } while (s.cut(take ? s.n : 0, last));
 }
 
 static void producer_main(hhgt_reader *r)
 {
-    if (r->is_bgzf) scan_bgzf(r);
-    else scan_stream(r);
+    if (r->map.len == 0) {   // an empty file: no block will say that it is the last
+        std::lock_guard<std::mutex> lk(r->mu);
+        r->eof = true;
+        r->cv_pub.notify_all();
+    } else if (r->is_bgzf)
+        scan_bgzf(r);
+    else if (r->is_gzip)
+        scan_gzip(r);
+    else
+        scan_plain(r);
+}
+
+// BGZF default: one worker per CPU the process may use (hhgt_effective_cpus), at most 96; HHGT_READER_THREADS or the
+// n_threads argument override, up to 192.  Uncompressed input: 16 pread threads saturate the page cache copy.  Plain gzip
+// is inflated by the scanner alone.
+static int worker_count(const hhgt_reader *r, int n_threads)
+{
+    if (r->is_gzip && !r->is_bgzf) return 0;
+    const char *e = getenv("HHGT_READER_THREADS");
+    const int eff = hhgt_effective_cpus();
+    int nt = n_threads > 0 ? n_threads : (e && atoi(e) > 0 ? atoi(e) : (eff < 96 ? eff : 96));
+    if (nt > 192) nt = 192;
+    if (!r->is_bgzf && nt > 16) nt = 16;
+    return nt;
 }
 
 extern "C" int hhgt_reader_open(const char *path, uint64_t block_bytes, int n_threads, int n_blocks, hhgt_reader **out)
@@ -687,73 +578,49 @@ extern "C" int hhgt_reader_open(const char *path, uint64_t block_bytes, int n_th
     if (block_bytes < (1u << 20)) block_bytes = 1u << 20;
     if (n_blocks <= 0) n_blocks = 4;
     if (n_blocks < 2) n_blocks = 2;
-    int fd = open(path, O_RDONLY);
-    if (fd < 0) {
+    std::unique_ptr<hhgt_reader> r(new hhgt_reader());
+    r->file.fd = open(path, O_RDONLY);
+    if (r->file.fd < 0) {
         hhgt_set_error("cannot open %s", path);
         return HHGT_ERR_IO;
     }
     struct stat st;
-    if (fstat(fd, &st) != 0) {
-        close(fd);
+    if (fstat(r->file.fd, &st) != 0) {
         hhgt_set_error("cannot stat %s", path);
         return HHGT_ERR_IO;
     }
-    hhgt_reader *r = new hhgt_reader();
-    r->fd = fd;
-    r->map_len = (size_t)st.st_size;
-    if (r->map_len) {
-        void *m = mmap(nullptr, r->map_len, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (st.st_size) {
+        void *m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, r->file.fd, 0);
         if (m == MAP_FAILED) {
-            close(fd);
-            delete r;
             hhgt_set_error("cannot mmap %s", path);
             return HHGT_ERR_IO;
         }
-        madvise(m, r->map_len, MADV_SEQUENTIAL);
-        r->map = static_cast<const uint8_t *>(m);
+        madvise(m, (size_t)st.st_size, MADV_SEQUENTIAL);
+        r->map.p = static_cast<const uint8_t *>(m);
+        r->map.len = (size_t)st.st_size;
     }
-    r->is_gzip = r->map_len >= 2 && r->map[0] == 0x1f && r->map[1] == 0x8b;
-    r->is_bgzf = r->is_gzip && looks_bgzf(r->map, r->map_len);
-    {
-        const char *e = getenv("HHGT_BGZF_NO_CRC");
-        r->check_crc = !(e && *e && *e != '0');
-    }
+    r->is_gzip = r->map.len >= 2 && r->map.p[0] == 0x1f && r->map.p[1] == 0x8b;
+    r->is_bgzf = r->is_gzip && looks_bgzf(r->map.p, r->map.len);
+    const char *no_crc = getenv("HHGT_BGZF_NO_CRC");
+    r->check_crc = !(no_crc && *no_crc && *no_crc != '0');
     r->block_bytes = (size_t)block_bytes;
     r->n_blocks = n_blocks;
     r->ring.reset(new Block[(size_t)n_blocks]);
-    r->held.assign((size_t)n_blocks, 0);
     // pinned when a HIP device exists (the copy engine can then DMA straight out of the ring);
     // plain pages otherwise (CPU-only hosts still frame and inflate, e.g. in the CPU test suite)
     int ndev = 0;
-    r->pinned = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
+    bool pin = hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0;
     for (int i = 0; i < n_blocks; ++i) {
-        void *p = r->pinned ? pool_take(r->block_bytes) : nullptr;
-        if (!p && r->pinned && hipHostMalloc(&p, r->block_bytes, hipHostMallocDefault) != hipSuccess) {
-            r->pinned = false;   // (blocks already taken stay pinned: pinned and pageable memory are freed alike below)
-            p = nullptr;
-        }
-        r->ring[i].pinned = p != nullptr;
-        if (!p) p = malloc(r->block_bytes);
-        if (!p) {
+        if (!r->ring[i].buf.make(r->block_bytes, &pin)) {
             hhgt_set_error("reader: out of memory for %zu-byte blocks", r->block_bytes);
-            hhgt_reader_close(r);
             return HHGT_ERR_IO;
         }
-        r->ring[i].buf = static_cast<uint8_t *>(p);
         r->free_.push_back(i);
     }
-    if (r->is_bgzf || !r->is_gzip) {
-        // BGZF default: one worker per CPU the process may use (hhgt_effective_cpus), at most 96; HHGT_READER_THREADS
-        // or the n_threads argument override.  Uncompressed input: 16 pread threads saturate the page cache copy.
-        const char *e = getenv("HHGT_READER_THREADS");
-        const int eff = hhgt_effective_cpus();
-        int nt = n_threads > 0 ? n_threads : (e && atoi(e) > 0 ? atoi(e) : (eff < 96 ? eff : 96));
-        if (nt > 192) nt = 192;
-        if (!r->is_bgzf && nt > 16) nt = 16;
-        for (int i = 0; i < nt; ++i) r->workers.emplace_back(worker_main, r);
-    }
-    r->producer = std::thread(producer_main, r);
-    *out = r;
+    // nothing below can fail: the threads only start once the reader is whole
+    for (int i = worker_count(r.get(), n_threads); i > 0; --i) r->workers.emplace_back(worker_main, r.get());
+    r->producer = std::thread(producer_main, r.get());
+    *out = r.release();
     return HHGT_OK;
 }
 
@@ -767,19 +634,8 @@ extern "C" void hhgt_reader_close(hhgt_reader *r)
     r->cv_free.notify_all();
     r->cv_open.notify_all();
     r->cv_pub.notify_all();
-    if (r->producer.joinable()) r->producer.join();
+    r->producer.join();
     for (auto &t : r->workers) t.join();
-    if (r->zs_init) inflateEnd(&r->zs);
-    for (int i = 0; i < r->n_blocks; ++i) {
-        uint8_t *b = r->ring[i].buf;
-        if (!b) continue;
-        if (r->ring[i].pinned) {
-            if (!pool_give(r->block_bytes, b)) hipHostFree(b);
-        } else
-            free(b);
-    }
-    if (r->map) munmap(const_cast<uint8_t *>(r->map), r->map_len);
-    if (r->fd >= 0) close(r->fd);
     delete r;
 }
 
@@ -798,40 +654,36 @@ extern "C" int hhgt_reader_acquire(hhgt_reader *r, const void **host_ptr, uint64
             hhgt_set_error("reader: %s", r->errmsg.c_str());
             return r->error;
         }
-        if (!r->order.empty()) {
-            Block &b = r->ring[r->order.front()];
-            if (b.scanned && b.done.load() >= b.n_tasks) break;
-        } else if (r->eof) {
-            return HHGT_OK;  // end of file
+        const int bi = r->order.empty() ? -1 : r->order.front();
+        if (bi < 0 && r->eof) return HHGT_OK;   // end of file
+        if (bi < 0 || !r->ring[bi].scanned || r->ring[bi].done.load() < r->ring[bi].n_tasks) {
+            if (r->stop) return HHGT_OK;
+            r->cv_pub.wait(lk);
+            continue;
         }
-        if (r->stop) return HHGT_OK;
-        r->cv_pub.wait(lk);
-    }
-    const int bi = r->order.front();
-    r->order.pop_front();
-    Block &b = r->ring[bi];
-    if (b.n == 0) {   // an empty block (e.g. only empty members): recycle and look again
+        Block &b = r->ring[bi];
+        r->order.pop_front();
+        if (b.n) {
+            b.held = true;
+            *host_ptr = b.buf.p;
+            *nbytes = b.n;
+            *token = bi;
+            if (is_last) *is_last = b.last ? 1 : 0;
+            return HHGT_OK;
+        }
+        // an empty block (e.g. only empty members): recycle it and look again
         r->free_.push_back(bi);
         r->cv_free.notify_all();
-        const bool last = b.last;
-        lk.unlock();
-        if (last) return HHGT_OK;
-        return hhgt_reader_acquire(r, host_ptr, nbytes, token, is_last);
+        if (b.last) return HHGT_OK;
     }
-    r->held[(size_t)bi] = 1;
-    *host_ptr = b.buf;
-    *nbytes = b.n;
-    *token = bi;
-    if (is_last) *is_last = b.last ? 1 : 0;
-    return HHGT_OK;
 }
 
 extern "C" int hhgt_reader_release(hhgt_reader *r, int token)
 {
     if (!r || token < 0 || token >= r->n_blocks) return HHGT_ERR_ARG;
     std::lock_guard<std::mutex> lk(r->mu);
-    if (!r->held[(size_t)token]) return HHGT_ERR_ARG;
-    r->held[(size_t)token] = 0;
+    if (!r->ring[token].held) return HHGT_ERR_ARG;
+    r->ring[token].held = false;
     r->free_.push_back(token);
     r->cv_free.notify_all();
     return HHGT_OK;
@@ -860,94 +712,7 @@ extern "C" int hhgt_reader_copy_async(hhgt_reader *r, const void *host_ptr, uint
 extern "C" int hhgt_reader_stats(const hhgt_reader *r, uint64_t *file_bytes, uint64_t *text_bytes)
 {
     if (!r) return HHGT_ERR_ARG;
-    if (file_bytes) *file_bytes = r->in_pos;
+    if (file_bytes) *file_bytes = r->file_bytes.load();
     if (text_bytes) *text_bytes = r->text_bytes.load();
-    return HHGT_OK;
-}
-
-// ---- bench / test tooling: parallel BGZF writer (declared in include/hhgt_synth.h) ---------------------------------
-#include "../../include/hhgt_synth.h"
-#include <stdio.h>
-
-static bool bgzf_member(z_stream *zs, int level, const uint8_t *src, uint32_t n, std::vector<uint8_t> &out)
-{
-    const size_t at = out.size();
-    out.resize(at + 18 + 65536 + 8);
-    uint8_t *h = out.data() + at;
-    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-    memcpy(h, head, 16);
-    (void)level;
-    if (deflateReset(zs) != Z_OK) return false;
-    zs->next_in = const_cast<Bytef *>(src);
-    zs->avail_in = n;
-    zs->next_out = h + 18;
-    zs->avail_out = 65536 - 18 - 8;
-    if (deflate(zs, Z_FINISH) != Z_STREAM_END) return false;
-    const uint32_t clen = (uint32_t)(65536 - 18 - 8 - zs->avail_out);
-    const uint32_t bsize = clen + 25;   // total member size - 1
-    h[16] = (uint8_t)(bsize & 0xFF);
-    h[17] = (uint8_t)(bsize >> 8);
-    uint8_t *t = h + 18 + clen;
-    const uint32_t crc = hhgt_crc32(src, n);
-    for (int k = 0; k < 4; ++k) t[k] = (uint8_t)(crc >> (8 * k));
-    for (int k = 0; k < 4; ++k) t[4 + k] = (uint8_t)(n >> (8 * k));
-    out.resize(at + 18 + clen + 8);
-    return true;
-}
-
-extern "C" int hhgt_synth_write_bgzf(const char *path, const void *text, uint64_t nbytes, int level, int n_threads)
-{
-    if (!path || (!text && nbytes)) return HHGT_ERR_ARG;
-    const uint32_t piece = 0xFF00;
-    const uint64_t n_members = (nbytes + piece - 1) / piece;
-    unsigned hw = std::thread::hardware_concurrency();
-    int nt = n_threads > 0 ? n_threads : (int)(hw ? hw : 4);
-    if ((uint64_t)nt > n_members) nt = (int)(n_members ? n_members : 1);
-    std::vector<std::vector<uint8_t>> parts((size_t)nt);
-    std::atomic<int> bad{0};
-    std::vector<std::thread> th;
-    const uint8_t *src = static_cast<const uint8_t *>(text);
-    for (int i = 0; i < nt; ++i) {
-        th.emplace_back([&, i] {
-            z_stream zs;
-            memset(&zs, 0, sizeof(zs));
-            if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) {
-                bad.store(1);
-                return;
-            }
-            const uint64_t m0 = n_members * (uint64_t)i / (uint64_t)nt, m1 = n_members * (uint64_t)(i + 1) / (uint64_t)nt;
-            parts[(size_t)i].reserve((size_t)((m1 - m0) * 4096));
-            for (uint64_t m = m0; m < m1; ++m) {
-                const uint64_t o = m * piece;
-                const uint32_t n = (uint32_t)(nbytes - o < piece ? nbytes - o : piece);
-                if (!bgzf_member(&zs, level, src + o, n, parts[(size_t)i])) {
-                    bad.store(1);   // (incompressible input would need a smaller member; the generator's text never is)
-                    break;
-                }
-            }
-            deflateEnd(&zs);
-        });
-    }
-    for (auto &t : th) t.join();
-    if (bad.load()) {
-        hhgt_set_error("write_bgzf: deflate failed");
-        return HHGT_ERR_IO;
-    }
-    FILE *f = fopen(path, "wb");
-    if (!f) {
-        hhgt_set_error("cannot create %s", path);
-        return HHGT_ERR_IO;
-    }
-    bool ok = true;
-    for (auto &p : parts) ok = ok && (p.empty() || fwrite(p.data(), 1, p.size(), f) == p.size());
-    // empty end-of-file member, as bgzip writes it (deflate of nothing = 03 00)
-    static const uint8_t eof_member[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0,
-                                           0, 0, 0, 0, 0, 0, 0, 0};
-    ok = ok && fwrite(eof_member, 1, 28, f) == 28;
-    ok = (fclose(f) == 0) && ok;
-    if (!ok) {
-        hhgt_set_error("short write to %s", path);
-        return HHGT_ERR_IO;
-    }
     return HHGT_OK;
 }

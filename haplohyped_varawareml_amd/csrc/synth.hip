@@ -2,7 +2,12 @@
 // include/hhgt_synth.h).  One workgroup per line; lanes write 16 B (4 "a|b\t" fields) each.
 #include "common.h"
 #include "../../include/hhgt_synth.h"
+#include "../../include/hhgt_reader.h"   // hhgt_crc32, hhgt_effective_cpus
+#include <zlib.h>
+#include <stdio.h>
 #include <string.h>
+#include <atomic>
+#include <thread>
 
 __host__ __device__ static inline unsigned long long mix64(unsigned long long x)
 {
@@ -207,5 +212,87 @@ extern "C" int hhgt_synth_render_mixed(hhgt_ctx *c, void *d_text, uint64_t text_
                        reinterpret_cast<const unsigned long long *>(d_alt8), d_meta, d_thr, n_variants, v_first, sc,
                        (uint32_t)n_samples, mix64(seed + 0x9E3779B97F4A7C15ull));
     HIP_TRY(hipGetLastError());
+    return HHGT_OK;
+}
+
+// ---- parallel BGZF writer -----------------------------------------------------------------------------------------
+static bool bgzf_member(z_stream *zs, const uint8_t *src, uint32_t n, std::vector<uint8_t> &out)
+{
+    const size_t at = out.size();
+    out.resize(at + 18 + 65536 + 8);
+    uint8_t *h = out.data() + at;
+    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+    memcpy(h, head, 16);
+    if (deflateReset(zs) != Z_OK) return false;
+    zs->next_in = const_cast<Bytef *>(src);
+    zs->avail_in = n;
+    zs->next_out = h + 18;
+    zs->avail_out = 65536 - 18 - 8;
+    if (deflate(zs, Z_FINISH) != Z_STREAM_END) return false;
+    const uint32_t clen = (uint32_t)(65536 - 18 - 8 - zs->avail_out);
+    const uint32_t bsize = clen + 25;   // total member size - 1
+    h[16] = (uint8_t)(bsize & 0xFF);
+    h[17] = (uint8_t)(bsize >> 8);
+    uint8_t *t = h + 18 + clen;
+    const uint32_t crc = hhgt_crc32(src, n);
+    for (int k = 0; k < 4; ++k) t[k] = (uint8_t)(crc >> (8 * k));
+    for (int k = 0; k < 4; ++k) t[4 + k] = (uint8_t)(n >> (8 * k));
+    out.resize(at + 18 + clen + 8);
+    return true;
+}
+
+extern "C" int hhgt_synth_write_bgzf(const char *path, const void *text, uint64_t nbytes, int level, int n_threads)
+{
+    if (!path || (!text && nbytes)) return HHGT_ERR_ARG;
+    const uint32_t piece = 0xFF00;
+    const uint64_t n_members = (nbytes + piece - 1) / piece;
+    int nt = n_threads > 0 ? n_threads : hhgt_effective_cpus();
+    if ((uint64_t)nt > n_members) nt = (int)(n_members ? n_members : 1);
+    std::vector<std::vector<uint8_t>> parts((size_t)nt);
+    std::atomic<int> bad{0};
+    std::vector<std::thread> th;
+    const uint8_t *src = static_cast<const uint8_t *>(text);
+    for (int i = 0; i < nt; ++i) {
+        th.emplace_back([&, i] {
+            z_stream zs;
+            memset(&zs, 0, sizeof(zs));
+            if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) {
+                bad.store(1);
+                return;
+            }
+            const uint64_t m0 = n_members * (uint64_t)i / (uint64_t)nt, m1 = n_members * (uint64_t)(i + 1) / (uint64_t)nt;
+            parts[(size_t)i].reserve((size_t)((m1 - m0) * 4096));
+            for (uint64_t m = m0; m < m1; ++m) {
+                const uint64_t o = m * piece;
+                const uint32_t n = (uint32_t)(nbytes - o < piece ? nbytes - o : piece);
+                if (!bgzf_member(&zs, src + o, n, parts[(size_t)i])) {
+                    bad.store(1);   // (incompressible input would need a smaller member; the generator's text never is)
+                    break;
+                }
+            }
+            deflateEnd(&zs);
+        });
+    }
+    for (auto &t : th) t.join();
+    if (bad.load()) {
+        hhgt_set_error("write_bgzf: deflate failed");
+        return HHGT_ERR_IO;
+    }
+    FILE *f = fopen(path, "wb");
+    if (!f) {
+        hhgt_set_error("cannot create %s", path);
+        return HHGT_ERR_IO;
+    }
+    bool ok = true;
+    for (auto &p : parts) ok = ok && (p.empty() || fwrite(p.data(), 1, p.size(), f) == p.size());
+    // empty end-of-file member, as bgzip writes it (deflate of nothing = 03 00)
+    static const uint8_t eof_member[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0,
+                                           0, 0, 0, 0, 0, 0, 0, 0};
+    ok = ok && fwrite(eof_member, 1, 28, f) == 28;
+    ok = (fclose(f) == 0) && ok;
+    if (!ok) {
+        hhgt_set_error("short write to %s", path);
+        return HHGT_ERR_IO;
+    }
     return HHGT_OK;
 }

@@ -10,23 +10,10 @@ import numpy as np
 from . import _lib
 from ._lib import check
 
-_bound = False
-
 
 def _lib_reader():
-    global _bound
-    L = _lib.load()
-    if not _bound:
-        vp, u64 = C.c_void_p, C.c_uint64
-        L.hhgt_reader_open.argtypes = [C.c_char_p, u64, C.c_int, C.c_int, C.POINTER(vp)]
-        L.hhgt_reader_close.argtypes = [vp]
-        L.hhgt_reader_close.restype = None
-        L.hhgt_reader_is_bgzf.argtypes = [vp]
-        L.hhgt_reader_next.argtypes = [vp, C.POINTER(vp), C.POINTER(u64)]
-        L.hhgt_reader_copy_async.argtypes = [vp, vp, u64, vp, vp]
-        L.hhgt_reader_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
-        _bound = True
-    return L
+    """the loaded library; _lib.PROTOTYPES binds the functions of include/hhgt_reader.h with all the others"""
+    return _lib.load()
 
 
 class VcfReader:

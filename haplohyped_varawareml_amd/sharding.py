@@ -122,11 +122,8 @@ def effective_cpus():
     """CPUs' worth of time the process is granted: the affinity mask capped by the cgroup quota (libhhgt's
     hhgt_effective_cpus: a GPU box may show 256 hardware threads and grant 16)"""
     try:
-        import ctypes
         from . import _lib
-        L = _lib.load()
-        L.hhgt_effective_cpus.restype = ctypes.c_int
-        return max(int(L.hhgt_effective_cpus()), 1)
+        return max(int(_lib.load().hhgt_effective_cpus()), 1)
     except Exception:
         return max(len(os.sched_getaffinity(0)), 1)
 

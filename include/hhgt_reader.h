@@ -26,7 +26,10 @@ extern "C" {
 typedef struct hhgt_reader hhgt_reader;
 
 /* path: .vcf, .vcf.gz (gzip or BGZF).  block_bytes: size of each pinned block (>= 1 MiB; lines longer
- * than a block are an error).  n_threads: BGZF inflate workers (0 = hardware concurrency, max 192).
+ * than a block are an error).  A BGZF block holds whole members, so there a line needs up to 64 KiB of room beyond its
+ * own length: at 1 MiB blocks a 990 KiB line that gzip and uncompressed input deliver is refused from BGZF.
+ * n_threads: inflate workers of BGZF input; <= 0: the environment's HHGT_READER_THREADS, else hhgt_effective_cpus()
+ * up to 96.  At most 192 in every case, and at most 16 for uncompressed input (pread workers); plain gzip has none.
  * n_blocks: ring depth (>= 2; 0 = 4). */
 int hhgt_reader_open(const char *path, uint64_t block_bytes, int n_threads, int n_blocks, hhgt_reader **out);
 void hhgt_reader_close(hhgt_reader *r);

@@ -40,7 +40,7 @@ int hhgt_synth_render_mixed(hhgt_ctx *ctx, void *d_text, uint64_t text_cap, cons
                             const char *contig, int n_samples, uint64_t seed, void *stream);
 
 /* BGZF writer for synthetic shards (BASELINE.md §3 asks for BGZF-compressed inputs; htslib / bgzip are not in the
- * image): host text -> 0xFF00-byte members deflated at `level` by n_threads threads (0 = hardware concurrency) ->
+ * image): host text -> 0xFF00-byte members deflated at `level` by n_threads threads (0 = hhgt_effective_cpus()) ->
  * file, with the empty end-of-file member.  Byte-identical to haplohyped_varawareml_amd.reader.write_bgzf. */
 int hhgt_synth_write_bgzf(const char *path, const void *text, uint64_t nbytes, int level, int n_threads);
 

@@ -63,9 +63,9 @@ def _param_class(ctype):
 
 
 def header_prototypes():
-    """{name: (class of the return value, [class of each parameter])} of the functions of hhgt.h and hhgt_synth.h"""
+    """{name: (class of the return value, [class of each parameter])} of the functions of hhgt.h, hhgt_synth.h and hhgt_reader.h"""
     protos = {}
-    for src in (HHGT_H, _header("hhgt_synth.h")):
+    for src in (HHGT_H, _header("hhgt_synth.h"), _header("hhgt_reader.h")):
         for ret, name, params in re.findall(r"^((?:const\s+)?\w+\s*\**)\s*(hhgt_\w+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
             def cls(decl, with_name):
                 decl = re.sub(r"\bconst\b", " ", decl).strip()
@@ -82,8 +82,9 @@ def header_prototypes():
 
 def test_prototype_table_is_the_headers():
     declared = header_prototypes()
-    assert len(declared) >= 45 and "hhgt_synth_render_mixed" in declared and "hhgt_reserve" in declared
-    assert len(_lib.PROTOTYPES) >= 45
+    assert len(declared) >= 58 and "hhgt_synth_render_mixed" in declared and "hhgt_reserve" in declared
+    assert "hhgt_reader_acquire" in declared and "hhgt_crc32" in declared
+    assert len(_lib.PROTOTYPES) >= 58 and "hhgt_reader_acquire" in _lib.PROTOTYPES
     for name, (restype, argtypes) in _lib.PROTOTYPES.items():
         assert name in declared, f"{name} is in no header"
         ret, params = declared[name]
@@ -94,9 +95,11 @@ def test_prototype_table_is_the_headers():
 
 
 def test_package_binds_no_prototype_elsewhere():
-    """the renderers' prototypes used to be bound on first use in device.py"""
-    src = open(device.__file__).read()
-    assert "argtypes" not in src and "restype" not in src
+    """the renderers' prototypes used to be bound on first use in device.py, the reader's in reader.py and sharding.py"""
+    from haplohyped_varawareml_amd import reader, sharding
+    for module in (device, reader, sharding):
+        src = open(module.__file__).read()
+        assert "argtypes" not in src and "restype" not in src, module.__name__
 
 
 @pytest.mark.parametrize("dtype,struct,size", [(device.SEL_DTYPE, _lib.BlockSel, 40), (device.COUNT_SEL_DTYPE, _lib.CountSel, 48),

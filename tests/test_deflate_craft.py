@@ -5,7 +5,6 @@
 * the host decoder (csrc/fast_inflate.h, `hhgt_fast_inflate`): 0 with zlib's bytes or a negative code, never 0 on a
   stream zlib rejects, nothing written outside the output; the valid streams it leaves to zlib are listed by name;
 * a libdeflate-written BGZF file through the reader, with either host inflater."""
-import ctypes as C
 import hashlib
 import os
 import subprocess
@@ -102,10 +101,7 @@ def test_libdeflate_agrees_with_zlib(case):
 @pytest.fixture(scope="module")
 def fast_inflate():
     from haplohyped_varawareml_amd import _lib
-    L = _lib.load()
-    L.hhgt_fast_inflate.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
-    L.hhgt_fast_inflate.restype = C.c_int
-    return L.hhgt_fast_inflate
+    return _lib.load().hhgt_fast_inflate
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)

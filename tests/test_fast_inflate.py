@@ -1,7 +1,6 @@
 """CPU: the host DEFLATE decoder of the BGZF reader (csrc/fast_inflate.h) against zlib — every kind of stream zlib
 writes, corrupted and truncated streams, under AddressSanitizer / UBSan (tests/fast_inflate_fuzz.cpp), and through the
 library's own entry point."""
-import ctypes as C
 import os
 import subprocess
 import zlib
@@ -24,7 +23,6 @@ def test_library_entry_point_and_reader_use_it(tmp_path):
     from haplohyped_varawareml_amd import _lib, synth
     from haplohyped_varawareml_amd.reader import VcfReader, write_bgzf
     L = _lib.load()
-    L.hhgt_fast_inflate.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
     tab = synth.variant_table(3, 40, 2504)
     text, _ = synth.render_fixed_numpy("chr3", tab, 2504, seed=3)
     for level in (1, 6, 9):

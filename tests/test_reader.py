@@ -1,13 +1,21 @@
 """CPU: the host reader (C++: mmap + zlib, BGZF blocks inflated in parallel) delivers exactly the
 file's text, cut at line boundaries, for plain / gzip / multi-member gzip / BGZF inputs."""
+import ctypes as C
 import gzip
 import os
+import struct
+import subprocess
+import zlib
 
 import numpy as np
 import pytest
 
 from haplohyped_varawareml_amd import synth
-from haplohyped_varawareml_amd.reader import VcfReader, parse_header, write_bgzf
+from haplohyped_varawareml_amd._lib import HhgtError
+from haplohyped_varawareml_amd.reader import VcfReader, _lib_reader, check, parse_header, write_bgzf, write_bgzf_native
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MiB = 1 << 20
 
 
 def collect(path, **kw):
@@ -105,12 +113,8 @@ def test_bgzf_crc_mismatch_is_an_error(tmp_path, monkeypatch):
 
 def test_crc32_matches_zlib():
     """hhgt_crc32 (PCLMULQDQ folding + table tail) against zlib's crc32 at every alignment / length class"""
-    import ctypes as C
-    import zlib
     from haplohyped_varawareml_amd import _lib
     L = _lib.load()
-    L.hhgt_crc32.restype = C.c_uint32
-    L.hhgt_crc32.argtypes = [C.c_void_p, C.c_uint64]
     rng = np.random.default_rng(5)
     big = rng.integers(0, 256, 70000, dtype=np.uint8)
     for n in list(range(0, 200)) + [255, 256, 257, 1023, 4096, 65280, 65535, 65536, 69999]:
@@ -125,7 +129,6 @@ def test_crc32_matches_zlib():
 def test_bgzf_many_blocks_in_flight(tmp_path, threads, blocks, block_kb):
     """the barrier-free BGZF path: many ring blocks open to the workers at once, held blocks released out of
     order, every byte and every line boundary intact"""
-    import ctypes as C
     from haplohyped_varawareml_amd import reader as rd
     rng = np.random.default_rng(11)
     lines = [b"chr1\t%d\t.\tA\tC\t" % i + bytes(rng.integers(48, 50, int(rng.integers(10, 9000)), dtype=np.uint8)) + b"\n"
@@ -134,8 +137,6 @@ def test_bgzf_many_blocks_in_flight(tmp_path, threads, blocks, block_kb):
     p = str(tmp_path / "x.vcf.gz")
     rd.write_bgzf(p, text, level=1)
     L = rd._lib_reader()
-    L.hhgt_reader_acquire.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.hhgt_reader_release.argtypes = [C.c_void_p, C.c_int]
     h = C.c_void_p()
     rd.check(L.hhgt_reader_open(p.encode(), block_kb << 10, threads, blocks, C.byref(h)))
     got, held, saw_last = [], [], False
@@ -194,3 +195,210 @@ def test_peek_sample_count(tmp_path):
     nohdr = tmp_path / "n.vcf"
     nohdr.write_bytes(b"chr1\t5\t.\tA\tC\t.\t.\t.\n")
     assert peek_sample_count(str(nohdr)) == 0
+
+
+# ---- the reader's hand-over through hhgt_reader_acquire: exact fill, lines across members, empty input, errors ------------
+EMPTY_MEMBER = b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0\x1b\0\x03\0" + b"\0" * 8   # what bgzip ends a file with
+
+
+def bgzf_members(data, size=0xFF00, level=1):
+    """the members of write_bgzf(data), one bytes object each, without the empty end-of-file member"""
+    out = []
+    for i in range(0, len(data), size):
+        chunk = data[i:i + size]
+        co = zlib.compressobj(level, zlib.DEFLATED, -15)
+        comp = co.compress(chunk) + co.flush()
+        out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(comp) + 25) + comp +
+                   struct.pack("<II", zlib.crc32(chunk) & 0xFFFFFFFF, len(chunk)))
+    return out
+
+
+def write_as(path, kind, data):
+    if kind == "plain":
+        open(path, "wb").write(data)
+    elif kind == "gzip":
+        open(path, "wb").write(gzip.compress(data, 1))
+    else:
+        open(path, "wb").write(b"".join(bgzf_members(data)) + EMPTY_MEMBER)
+    return path
+
+
+def acquire_all(path, n_threads=3, n_blocks=3, block_bytes=MiB):
+    """every block through hhgt_reader_acquire, released at once -> ([(bytes, is_last)], stats at end of file)"""
+    L = _lib_reader()
+    h = C.c_void_p()
+    check(L.hhgt_reader_open(str(path).encode(), block_bytes, n_threads, n_blocks, C.byref(h)))
+    try:
+        got = []
+        while True:
+            ptr, n, tok, last = C.c_void_p(), C.c_uint64(0), C.c_int(-2), C.c_int(0)
+            check(L.hhgt_reader_acquire(h, C.byref(ptr), C.byref(n), C.byref(tok), C.byref(last)))
+            if n.value == 0:
+                assert tok.value == -1 and not last.value
+                break
+            got.append((C.string_at(ptr, n.value), bool(last.value)))
+            check(L.hhgt_reader_release(h, tok.value))
+        fb, tb = C.c_uint64(0), C.c_uint64(0)
+        check(L.hhgt_reader_stats(h, C.byref(fb), C.byref(tb)))
+        return got, dict(file_bytes=fb.value, text_bytes=tb.value)
+    finally:
+        L.hhgt_reader_close(h)
+
+
+def lines64(total):
+    """`total` bytes of 64-byte lines; the last line is shorter where 64 does not divide the total"""
+    full = b"".join(b"%062d\t\n" % i for i in range(total // 64))
+    return full + (b"x" * (total % 64 - 1) + b"\n" if total % 64 else b"")
+
+
+PARENT_LENGTHS = {("stream", MiB): [MiB], ("stream", 2 * MiB): [MiB, MiB], ("stream", MiB + 1): [MiB, 1],
+                  ("bgzf", 2 * MiB): [1044480, 1044480, 8192], ("bgzf", MiB + 1): [1044480, 4097]}
+
+
+@pytest.mark.parametrize("kind", ["plain", "gzip", "bgzf"])
+@pytest.mark.parametrize("total", [MiB - 1, MiB, MiB + 1, 2 * MiB])
+def test_exact_fill(tmp_path, kind, total):
+    """text that fills the 1 MiB blocks to the byte, one short of it and one past it"""
+    text = lines64(total)
+    assert len(text) == total
+    p = write_as(str(tmp_path / "x"), kind, text)
+    got, st = acquire_all(p, n_threads=3)
+    blocks = [b for b, _ in got]
+    assert b"".join(blocks) == text
+    assert all(b.endswith(b"\n") for b in blocks)
+    assert [last for _, last in got] == [False] * (len(got) - 1) + [True]
+    assert st["text_bytes"] == total
+    if kind != "gzip":
+        assert st["file_bytes"] == os.path.getsize(p)
+    want = PARENT_LENGTHS.get(("bgzf" if kind == "bgzf" else "stream", total))
+    if want:
+        assert [len(b) for b in blocks] == want
+
+
+@pytest.fixture(scope="module")
+def long_lines():
+    rng = np.random.default_rng(23)
+    return b"".join(bytes(rng.integers(48, 58, int(rng.integers(150000, 400001)) - 1, dtype=np.uint8)) + b"\n" for _ in range(30))
+
+
+@pytest.mark.parametrize("kind", ["bgzf", "gzip", "plain"])
+def test_lines_across_members(tmp_path, long_lines, kind):
+    """lines of several members each, empty members between them, a ring of two blocks"""
+    p = str(tmp_path / "x")
+    if kind == "bgzf":
+        ms = bgzf_members(long_lines)
+        assert len(ms) > 41
+        for at in (40, 4, 3):
+            ms.insert(at, EMPTY_MEMBER)
+        open(p, "wb").write(b"".join(ms) + EMPTY_MEMBER)
+    else:
+        write_as(p, kind, long_lines)
+    got, st = acquire_all(p, n_threads=4, n_blocks=2)
+    assert b"".join(b for b, _ in got) == long_lines
+    assert all(b.endswith(b"\n") for b, _ in got) and len(got) > 5
+    assert st["text_bytes"] == len(long_lines)
+
+
+@pytest.mark.parametrize("kind", ["bgzf", "gzip"])
+def test_lines_across_members_no_final_newline(tmp_path, long_lines, kind):
+    text = long_lines[:-1]
+    got, _ = acquire_all(write_as(str(tmp_path / "x"), kind, text), n_threads=4, n_blocks=2)
+    assert b"".join(b for b, _ in got) == text
+
+
+@pytest.mark.parametrize("n", [1, 3])
+def test_empty_bgzf(tmp_path, n):
+    p = str(tmp_path / "e.vcf.gz")
+    open(p, "wb").write(EMPTY_MEMBER * n)
+    got, st = acquire_all(p)
+    assert got == [] and st == dict(file_bytes=28 * n, text_bytes=0)
+
+
+def member_offsets(raw):
+    off = [0]
+    while off[-1] < len(raw):
+        off.append(off[-1] + (raw[off[-1] + 16] | (raw[off[-1] + 17] << 8)) + 1)
+    return off
+
+
+@pytest.mark.parametrize("damage,message", [("cut40", "truncated compressed input"), ("half", "truncated compressed input"),
+                                            ("header", "corrupt BGZF block header"), ("payload", "inflate failed")])
+def test_damaged_bgzf(tmp_path, text, damage, message):
+    raw = bytearray(b"".join(bgzf_members(text)) + EMPTY_MEMBER)
+    off = member_offsets(raw)
+    if damage == "cut40":
+        raw = raw[:-40]
+    elif damage == "half":
+        raw = raw[:len(raw) // 2]
+    elif damage == "header":
+        raw[off[2] + 12] = 0x58
+    else:
+        mid = (off[1] + off[2]) // 2
+        raw[mid] ^= 0xFF
+        raw[mid + 1] ^= 0xFF
+    p = str(tmp_path / "d.vcf.gz")
+    open(p, "wb").write(bytes(raw))
+    with pytest.raises(HhgtError, match=message):
+        acquire_all(p)
+
+
+@pytest.mark.parametrize("kind", ["bgzf", "gzip"])
+@pytest.mark.parametrize("head", [b"", b"ab\n"])
+def test_one_line_of_three_blocks(tmp_path, kind, head):
+    p = write_as(str(tmp_path / "x"), kind, head + b"x" * (3 * MiB - 1) + b"\n")
+    with pytest.raises(HhgtError, match="longer than"):
+        acquire_all(p)
+
+
+def newline_free_carry():
+    """548 KiB of lines, then one line of 1300 KiB: the second block holds a carry and members without any newline"""
+    return lines64(548 << 10) + b"y" * ((1300 << 10) - 1) + b"\n"
+
+
+@pytest.mark.parametrize("kind", ["bgzf", "gzip", "plain"])
+def test_newline_free_carry(tmp_path, kind):
+    p = write_as(str(tmp_path / "x"), kind, newline_free_carry())
+    with pytest.raises(HhgtError, match="longer than"):
+        acquire_all(p)
+
+
+def test_native_writer_is_independent_of_its_thread_count(tmp_path, text):
+    files = []
+    for nt in (1, 3, 16, 0):
+        p = str(tmp_path / f"w{nt}.vcf.gz")
+        write_bgzf_native(p, text, level=6, n_threads=nt)
+        files.append(open(p, "rb").read())
+    assert all(f == files[0] for f in files[1:])
+    got, st = acquire_all(str(tmp_path / "w3.vcf.gz"))
+    assert b"".join(b for b, _ in got) == text and st["file_bytes"] == len(files[0])
+
+
+READER_HIP = os.path.join(ROOT, "haplohyped_varawareml_amd", "csrc", "reader.hip")
+
+
+def run_harness(tmp_path, text, sanitize, reader_hip=READER_HIP):
+    """builds tests/reader_harness.cpp with csrc/reader.hip under a host sanitizer and runs it on files written here"""
+    from haplohyped_varawareml_amd.build import _hipcc
+    exe = str(tmp_path / "reader_harness")
+    subprocess.check_call([_hipcc(), "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-mssse3", "-Wno-unused-value"] +
+                          ["-Xarch_host"] + " -Xarch_host ".join(sanitize).split() +
+                          ["-o", exe, os.path.join(ROOT, "tests", "reader_harness.cpp"), reader_hip, "-lz", "-lpthread"])
+    paths = [str(tmp_path / n) for n in ("text", "bgzf", "gzip", "plain", "too_long", "missing")]
+    open(paths[0], "wb").write(text)
+    for p, kind in zip(paths[1:4], ("bgzf", "gzip", "plain")):
+        write_as(p, kind, text)
+    write_as(paths[4], "bgzf", newline_free_carry())
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1")
+    return subprocess.run([exe] + paths, capture_output=True, text=True, timeout=300, env=env)
+
+
+@pytest.mark.parametrize("sanitize", [["-fsanitize=thread"], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]],
+                         ids=["thread", "address"])
+def test_harness_under_sanitizers(tmp_path, text, sanitize):
+    """the C API driven as the ingest engine drives it (tests/reader_harness.cpp), as a program of its own: scanner, workers
+    and consumer under ThreadSanitizer, and under AddressSanitizer / UBSan.  Host code only: never where a device is visible"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a sanitized program must not open a device: this test runs on CPU-only hosts")
+    r = run_harness(tmp_path, text, sanitize)
+    assert r.returncode == 0 and r.stdout.strip() == "ok" and "Sanitizer" not in r.stderr, r.stdout + r.stderr
