@@ -65,24 +65,29 @@ void DevBuf::release()
         if (_rc != HHGT_OK) return _rc; \
     } while (0)
 
-int EncodeWs::ensure_index(uint32_t n_regions)
+int EncodeWs::ensure_index(uint32_t n_regions, hipStream_t st)
 {
     TRY(slots.ensure((size_t)n_regions * INDEX_CAP * 4));
     TRY(counts.ensure((size_t)n_regions * 4));
-    TRY(prefix.ensure(((size_t)n_regions + 1) * 4));
-    return ensure_scan(n_regions);
+    TRY(n_lines.ensure(4));
+    const size_t had = region_tot.cap;
+    TRY(region_tot.ensure((size_t)chain_groups(n_regions) * 4));
+    if (region_tot.cap != had) HIP_TRY(hipMemsetAsync(region_tot.p, 0, region_tot.cap, st));   // new memory: zero once, in front of the index
+    return HHGT_OK;
 }
 
 int EncodeWs::ensure_lines(uint32_t max_lines)
 {
     const size_t nl4 = ((size_t)max_lines + 1) * 4;
     TRY(nl.ensure(nl4));
-    TRY(ensure_scan(max_lines));
     for (DevBuf &b : line) TRY(b.ensure(nl4));
+    TRY(line_tot.ensure(2 * (size_t)chain_groups(max_lines) * 4));
+    if (chain_scanned(max_lines)) {
+        for (DevBuf &b : scanned) TRY(b.ensure(nl4));
+        TRY(scan_tmp.ensure(2 * scan_tmp_elems(max_lines) * 4));
+    }
     return ensure_runs();
 }
-
-int EncodeWs::ensure_scan(uint64_t n) { return scan_tmp.ensure(2 * scan_tmp_elems(n) * 4); }
 
 int EncodeWs::ensure_runs()
 {
@@ -340,9 +345,12 @@ static int parse_region_host(const char *region, RegionFilter *rf)
 }
 
 // ---- encode ---------------------------------------------------------------------------------------
-// device-side epilogue of one encode call: advance the cursor, assemble the result record (counts, CHROM runs)
+// device-side epilogue of one encode call: advance the cursor, assemble the result record (counts, CHROM runs).  `res` is
+// the caller's record itself where the device can write it (pinned host memory: no staging copy behind this kernel), so
+// `done` is stored last and with system-scope release: whoever sees it set sees the record.
 __global__ void k_encode_finish(DevCounters *cnt, uint64_t *cursor, const uint64_t *__restrict__ run_first,
-                                const uint8_t *__restrict__ run_names, uint64_t v_capacity, hhgt_encode_result *res)
+                                const uint8_t *__restrict__ run_names, uint64_t v_capacity, hhgt_encode_result *res,
+                                uint32_t *region_tot, uint32_t n_region_tot)
 {
     const uint32_t t = threadIdx.x;
     const uint64_t before = *cursor;
@@ -365,16 +373,19 @@ __global__ void k_encode_finish(DevCounters *cnt, uint64_t *cursor, const uint64
         res->n_lines_over = cnt->err_lines;
         res->err_density = cnt->err_density;
         res->v_capacity = v_capacity;
-        res->done = 1u;
         res->reserved = cnt->n_other > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)cnt->n_other;   // bit-plane form: calls beyond 0 / 1 / missing
     }
     const uint64_t n_runs = cnt->n_chrom_runs;
     if (t < HHGT_RESULT_RUNS) res->run_first[t] = t < n_runs ? run_first[t] : 0ull;
     for (uint32_t q = t; q < HHGT_RESULT_RUNS * 32u; q += blockDim.x)
         res->run_names[q >> 5][q & 31u] = (q >> 5) < n_runs ? (char)run_names[q] : 0;
-    // the counters go back to zero for the next call on this context (one memset launch less per call: counters_clean)
+    __threadfence_system();
+    // the counters and the index's region totals go back to zero for the next call on this context (one memset launch less
+    // per call: counters_clean)
     __syncthreads();
+    if (t == 0) __hip_atomic_store(&res->done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     if (t < sizeof(DevCounters) / 8u) reinterpret_cast<unsigned long long *>(cnt)[t] = 0ull;
+    for (uint32_t q = t; q < n_region_tot; q += blockDim.x) region_tot[q] = 0u;
 }
 
 __global__ void k_set_u64(uint64_t *p, uint64_t v) { *p = v; }
@@ -404,17 +415,28 @@ static int encode_check_args(hhgt_ctx *c, const void *d_text, uint64_t nbytes, c
 // regions of the newline index over a text block (and the byte behind it)
 static uint32_t index_regions(uint64_t nbytes) { return (uint32_t)((nbytes + 1 + INDEX_REGION - 1) / INDEX_REGION); }
 
-// stage 1: newline index of the block -> prefix[n_regions] holds the line count (device).  min_line: a record with S
-// sample columns cannot be shorter than 9 fixed columns and S fields of one byte and a separator each (0: unknown)
+// the DevCounters and the index's region totals are zero when a call starts: the epilogue of the last call left them so
+// (counters_clean); behind a call that did not get that far, zero them here
+static int encode_begin_clean(hhgt_ctx *c, DevCounters *cnt, hipStream_t st)
+{
+    if (!c->counters_clean) {
+        HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(DevCounters), st));
+        if (c->enc.region_tot.p) HIP_TRY(hipMemsetAsync(c->enc.region_tot.p, 0, c->enc.region_tot.cap, st));
+    }
+    c->counters_clean = false;
+    return HHGT_OK;
+}
+
+// stage 1: newline index of the block -> slots / counts per region and the totals per CHAIN_GROUP regions, whose sum is the
+// line count (k_compact_newlines puts it into enc.n_lines).  min_line: a record with S sample columns cannot be shorter
+// than 9 fixed columns and S fields of one byte and a separator each (0: unknown)
 static int encode_stage_index(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes, uint32_t n_regions, uint32_t min_line, uint32_t S,
                               DevCounters *cnt, hipStream_t st)
 {
     EncodeWs &w = c->enc;
-    TRY(w.ensure_index(n_regions));
-    TRY(launch_index_newlines(text, nbytes, w.slots.as<uint32_t>(), w.counts.as<uint32_t>(), n_regions, min_line, S, c->index_mode, cnt, st));
-    TRY(launch_scan_exclusive_u32_pair(w.counts.as<uint32_t>(), w.prefix.as<uint32_t>(), nullptr, nullptr, n_regions,
-                                       w.scan_tmp.as<uint32_t>(), w.scan_tmp.cap / 4, st));
-    return HHGT_OK;
+    TRY(w.ensure_index(n_regions, st));
+    return launch_index_newlines(text, nbytes, w.slots.as<uint32_t>(), w.counts.as<uint32_t>(), w.region_tot.as<uint32_t>(), n_regions,
+                                 min_line, S, c->index_mode, cnt, st);
 }
 
 // stages 2..: everything behind the index, sized by max_lines, counts and append position read on the device
@@ -424,18 +446,18 @@ static int encode_stage_rest(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes, 
 {
     EncodeWs &w = c->enc;
     TRY(w.ensure_lines(max_lines));
-    const uint32_t *nl = w.nl.as<uint32_t>(), *d_nlines = w.prefix.as<uint32_t>() + n_regions;
-    uint32_t *scan_tmp = w.scan_tmp.as<uint32_t>();
-    const LineCols l = w.line_cols();
+    const uint32_t *nl = w.nl.as<uint32_t>(), *d_nlines = w.n_lines.as<uint32_t>();
+    const LineCols l = w.line_cols(max_lines);
     const KeptCols k = w.kept_cols();
     TRY(timed(c, st, HHGT_STAGE_INDEX, [&] {
-        return launch_compact_newlines(w.slots.as<uint32_t>(), w.counts.as<uint32_t>(), w.prefix.as<uint32_t>(), n_regions,
-                                       w.nl.as<uint32_t>(), max_lines, st);
+        return launch_compact_newlines(w.slots.as<uint32_t>(), w.counts.as<uint32_t>(), w.region_tot.as<uint32_t>(), n_regions,
+                                       w.nl.as<uint32_t>(), max_lines, w.n_lines.as<uint32_t>(), st);
     }));
     if (max_lines == 0) return HHGT_OK;
     TRY(timed(c, st, HHGT_STAGE_FIXED, [&] {
         TRY(launch_parse_fixed(text, nbytes, nl, d_nlines, max_lines, rf, L.S, l, c->index_mode, cnt, st));
-        TRY(launch_scan_exclusive_u32_pair(l.keep, l.kidx, l.cnew, l.crun, max_lines, scan_tmp, w.scan_tmp.cap / 4, st));
+        if (chain_scanned(max_lines))   // more lines than k_compact_kept sums totals for: kidx / crun from the scan launches
+            TRY(launch_scan_exclusive_u32_pair(l.keep, l.kidx, l.cnew, l.crun, max_lines, w.scan_tmp.as<uint32_t>(), w.scan_tmp.cap / 4, st));
         return launch_compact_kept(text, nbytes, nl, d_nlines, max_lines, l, k, MAX_CHROM_RUNS, d_cursor, L.v_capacity, L.ring,
                                    d_start, d_stop, d_ref, d_alt, cnt, d_P != nullptr, st);
     }));
@@ -452,13 +474,34 @@ static int encode_stage_rest(hhgt_ctx *c, const uint8_t *text, uint64_t nbytes, 
     });
 }
 
-static int encode_finish(hhgt_ctx *c, uint64_t *d_cursor, const LayoutDev &L, DevCounters *cnt, hipStream_t st)
+// the address under which this context's device writes *h_result itself: pinned host memory (hipHostMalloc, hipHostRegister)
+// made on its device.  nullptr: anything else (pageable memory, or unknown to the runtime) goes through staging and a copy
+static hhgt_encode_result *result_on_device(const hhgt_ctx *c, hhgt_encode_result *h_result)
+{
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, h_result) != hipSuccess) {
+        (void)hipGetLastError();   // (not an error of the call: the runtime does not know the pointer)
+        return nullptr;
+    }
+    if (a.type != hipMemoryTypeHost || !a.devicePointer || a.device != c->device) return nullptr;
+    return static_cast<hhgt_encode_result *>(a.devicePointer);
+}
+
+// epilogue of a call over n_regions index regions; h_result (may be NULL) receives the record when the stream gets there
+static int encode_finish(hhgt_ctx *c, uint64_t *d_cursor, const LayoutDev &L, DevCounters *cnt, uint32_t n_regions,
+                         hhgt_encode_result *h_result, hipStream_t st)
 {
     TRY(c->enc.ensure_runs());
     const KeptCols k = c->enc.kept_cols();
+    hhgt_encode_result *staging = c->enc.result.as<hhgt_encode_result>();
+    hhgt_encode_result *direct = h_result ? result_on_device(c, h_result) : nullptr;
+    if (h_result) h_result->done = 0u;
     hipLaunchKernelGGL(k_encode_finish, dim3(1), dim3(256), 0, st, cnt, d_cursor, k.run_first, k.run_names,
-                       L.ring ? 0ull : L.v_capacity, c->enc.result.as<hhgt_encode_result>());
+                       L.ring ? 0ull : L.v_capacity, direct ? direct : staging, c->enc.region_tot.as<uint32_t>(),
+                       c->enc.region_tot.p ? chain_groups(n_regions) : 0u);
     HIP_TRY(hipGetLastError());
+    c->counters_clean = true;   // (calls on one context are serialised by the caller: the next one is queued behind this epilogue)
+    if (h_result && !direct) HIP_TRY(hipMemcpyAsync(h_result, staging, sizeof(hhgt_encode_result), hipMemcpyDeviceToHost, st));
     return HHGT_OK;
 }
 
@@ -565,21 +608,14 @@ static int encode_async_impl(hhgt_ctx *c, const void *d_text, uint64_t nbytes, c
     if (planes) TRY(planes_check_layout(L));
     const uint8_t *text = static_cast<const uint8_t *>(d_text);
     DevCounters *cnt = c->counters.as<DevCounters>();
-    if (!c->counters_clean) HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(DevCounters), st));   // (the last call's epilogue did not get to zero them)
-    c->counters_clean = false;
+    TRY(encode_begin_clean(c, cnt, st));
     const uint32_t n_regions = index_regions(nbytes);
     if (nbytes) {
         TRY(timed(c, st, HHGT_STAGE_INDEX, [&] { return encode_stage_index(c, text, nbytes, n_regions, L.S ? 2u * L.S + 17u : 0u, L.S, cnt, st); }));
         TRY(encode_stage_rest(c, text, nbytes, n_regions, max_lines, rf, L, d_cursor, d_G, planes ? d_P : nullptr, d_start, d_stop, d_ref,
                               d_alt, cnt, st));
     }
-    TRY(encode_finish(c, d_cursor, L, cnt, st));
-    c->counters_clean = true;   // (calls on one context are serialised by the caller: the next one is queued behind this epilogue)
-    if (h_result) {
-        h_result->done = 0u;
-        HIP_TRY(hipMemcpyAsync(h_result, c->enc.result.p, sizeof(hhgt_encode_result), hipMemcpyDeviceToHost, st));
-    }
-    return HHGT_OK;
+    return encode_finish(c, d_cursor, L, cnt, n_regions, h_result, st);
 }
 
 extern "C" int hhgt_encode_text_async(hhgt_ctx *c, const void *d_text, uint64_t nbytes, const char *region,
@@ -676,24 +712,23 @@ static int encode_text_once(hhgt_ctx *c, const void *d_text, uint64_t nbytes, co
     const uint8_t *text = static_cast<const uint8_t *>(d_text);
     DevCounters *cnt = c->counters.as<DevCounters>();
     TRY(c->cursor.ensure(8));
-    HIP_TRY(hipMemsetAsync(cnt, 0, sizeof(DevCounters), st));
-    c->counters_clean = false;
+    TRY(encode_begin_clean(c, cnt, st));
     hipLaunchKernelGGL(k_set_u64, dim3(1), dim3(1), 0, st, c->cursor.as<uint64_t>(), v_base);
     const uint32_t n_regions = index_regions(nbytes);
     uint32_t n_lines = 0;
     {
-        // the synchronous form sizes everything by the exact line count: it is read back once (any input, however
-        // short its lines, fits), where the asynchronous form takes the caller's bound
+        // the synchronous form sizes everything by the exact line count: the index's totals (at most 1024 words) are read
+        // back once and added up (any input, however short its lines, fits), where the asynchronous form takes the
+        // caller's bound
         StageTimer t(c, st, HHGT_STAGE_INDEX);
         TRY(encode_stage_index(c, text, nbytes, n_regions, L.S ? 2u * L.S + 17u : 0u, L.S, cnt, st));
-        c->h_counters->n_lines = 0;
+        std::vector<uint32_t> totals(chain_groups(n_regions));
         c->h_counters->err_density = 0;
-        HIP_TRY(hipMemcpyAsync(&c->h_counters->n_lines, c->enc.prefix.as<uint32_t>() + n_regions, 4,
-                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(totals.data(), c->enc.region_tot.p, totals.size() * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&c->h_counters->err_density, &cnt->err_density, 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         t.stop();
-        n_lines = (uint32_t)(c->h_counters->n_lines & 0xFFFFFFFFull);
+        for (uint32_t x : totals) n_lines += x;
         if (c->h_counters->err_density) {
             hhgt_set_error("encode: more than %u newlines inside one %u-byte region (not VCF text)", INDEX_CAP,
                            INDEX_REGION);
@@ -704,11 +739,8 @@ static int encode_text_once(hhgt_ctx *c, const void *d_text, uint64_t nbytes, co
     if (n_lines == 0) return HHGT_OK;
     TRY(encode_stage_rest(c, text, nbytes, n_regions, n_lines, rf, L, c->cursor.as<uint64_t>(), d_G, nullptr, d_start, d_stop, d_ref,
                           d_alt, cnt, st));
-    TRY(encode_finish(c, c->cursor.as<uint64_t>(), L, cnt, st));
-    c->counters_clean = true;
+    TRY(encode_finish(c, c->cursor.as<uint64_t>(), L, cnt, n_regions, c->h_result_pinned, st));
     hhgt_encode_result *hr = &c->h_result;
-    hr->done = 0u;
-    HIP_TRY(hipMemcpyAsync(c->h_result_pinned, c->enc.result.p, sizeof(hhgt_encode_result), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     *hr = *c->h_result_pinned;
     if (stats) *stats = hr->stats;
@@ -926,9 +958,9 @@ extern "C" int hhgt_reserve(hhgt_ctx *c, uint64_t text_bytes, uint32_t max_lines
     HIP_TRY(hipSetDevice(c->device));
     if (text_bytes) {
         const uint32_t n_regions = index_regions(text_bytes);
-        TRY(c->enc.ensure_scan(n_regions > max_lines ? n_regions : max_lines));   // the larger of the two scans: made once
-        TRY(c->enc.ensure_index(n_regions));
+        TRY(c->enc.ensure_index(n_regions, nullptr));
         TRY(c->enc.ensure_lines(max_lines));
+        HIP_TRY(hipStreamSynchronize(nullptr));   // (new region totals are zeroed on the null stream: done before any call's stream runs)
     }
     if (n_chunks) {
         TRY(check_codec_args(chunk_nbytes, typesize, blocksize, HHGT_BLOSC2));

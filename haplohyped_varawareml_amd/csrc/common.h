@@ -30,6 +30,37 @@ __device__ __forceinline__ uint32_t wave_scan_sum_dpp(uint32_t x, uint32_t lane)
     const uint32_t row = lane >> 4;
     return x + (row == 0u ? 0u : (row == 1u ? t0 : (row == 2u ? t1 : t2)));
 }
+
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        uint32_t t = __shfl_up(v, d, 64);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+
+// exclusive scan of one value per thread across a 256-thread block; returns exclusive prefix,
+// *total = block sum (valid in all threads)
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total, uint32_t *sm /*>=8*/)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = wave_incl_scan(v);
+    if (lane == 63) sm[w] = inc;
+    __syncthreads();
+    uint32_t base = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint32_t x = sm[i];
+        if (i < w) base += x;
+        tot += x;
+    }
+    __syncthreads();
+    *total = tot;
+    return base + inc - v;
+}
 #endif
 
 // ---- error plumbing -------------------------------------------------------------------------
@@ -148,10 +179,29 @@ struct DevBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// ---- prefix sums of the encode chain without scan launches ----------------------------------------------------------------
+// A compaction workgroup owns CHAIN_GROUP entries (index regions for k_compact_newlines, lines for k_compact_kept).  The
+// kernel in front of it leaves one total per group behind, and workgroup b sums the totals in front of it itself, the way
+// k_scan_down_n sums its tiles' partials.  That fan-in is linear in the number of groups, so it is bounded like
+// SCAN_SHORT_MAX: at CHAIN_FANIN_MAX = 2048 groups the last workgroup reads 8 words per thread and array (what a scan tile
+// reads per thread, SCAN_ITEMS) and all workgroups together 2048^2 / 2 words per array, 8 MB out of L2.  Four times that
+// many groups would be 16 times the reads, beyond what the two scan launches cost.
+//  - regions: a text block is below 4 GiB (encode_check_args), i.e. at most 2^18 regions or 1024 groups: always inside.
+//  - lines: up to 2048 * 256 = 524 288 (the caller's max_lines); beyond, k_parse_fixed writes its keep / cnew flags and
+//    launch_scan_exclusive_u32_pair scans them as before (chain_scanned).
+#define CHAIN_GROUP 256u
+#define CHAIN_FANIN_MAX 2048u
+static_assert(((0xFFFFFFF0ull + 1 + INDEX_REGION - 1) / INDEX_REGION + CHAIN_GROUP - 1) / CHAIN_GROUP <= CHAIN_FANIN_MAX,
+              "the region totals of the largest text block must stay inside the fan-in bound");
+static inline uint32_t chain_groups(uint32_t n) { return (n + CHAIN_GROUP - 1u) / CHAIN_GROUP; }
+static inline bool chain_scanned(uint32_t max_lines) { return chain_groups(max_lines) > CHAIN_FANIN_MAX; }
+
 // the per-line columns of an encode call as the launchers take them: one word per line of the text block.  k_parse_fixed
-// writes soff .. flags, keep and cnew; the scan turns keep / cnew into kidx / crun; k_compact_kept reads all but keep / cnew
+// writes soff .. flags and the two totals per 256 lines (tot: keep flags of group b at [b], CHROM-run flags at [groups + b]);
+// k_compact_kept makes kept index and run index of every line from flags and totals.  More lines than the fan-in bound
+// (chain_scanned): keep / cnew are written too and the scan turns them into kidx / crun; the four are NULL otherwise
 struct LineCols {
-    uint32_t *soff, *lend, *pos, *refalt, *flags, *keep, *kidx, *cnew, *crun;
+    uint32_t *soff, *lend, *pos, *refalt, *flags, *tot, *keep, *kidx, *cnew, *crun;
 };
 // what k_compact_kept writes: one word per kept line, the list of lines for the general encoder, the CHROM runs
 struct KeptCols {
@@ -163,27 +213,37 @@ struct KeptCols {
 // encode workspaces of a context.  They grow inside the calls, or ahead of them in hhgt_reserve: both through ensure_index
 // and ensure_lines, so a size is written once
 struct EncodeWs {
-    DevBuf slots, counts, prefix, nl, scan_tmp;
-    enum { L_SOFF, L_LEND, L_POS, L_REFALT, L_FLAGS, L_KEEP, L_KIDX, L_CNEW, L_CRUN, K_SOFF, K_LEND, K_META, REDO_LIST, REDO_FLAG, N_LINE };
-    DevBuf line[N_LINE];   // a word per line each
+    DevBuf slots, counts, nl, scan_tmp;
+    // region_tot: newlines per CHAIN_GROUP regions, added up by the index kernels.  Zero between calls: k_encode_finish zeroes
+    // what its call used, like the DevCounters (hhgt_ctx::counters_clean covers both), and new memory is zeroed where it is made
+    DevBuf region_tot;
+    DevBuf n_lines;        // one word: the lines the index found (k_compact_newlines)
+    DevBuf line_tot;       // LineCols::tot
+    enum { L_SOFF, L_LEND, L_POS, L_REFALT, L_FLAGS, K_SOFF, K_LEND, K_META, REDO_LIST, REDO_FLAG, N_LINE };
+    enum { S_KEEP, S_KIDX, S_CNEW, S_CRUN, N_SCANNED };
+    DevBuf line[N_LINE];         // a word per line each
+    DevBuf scanned[N_SCANNED];   // ... and these four for more lines than the fan-in bound only (chain_scanned)
     DevBuf run_first, run_names;
-    DevBuf result;         // hhgt_encode_result staging of the asynchronous form
-    int ensure_index(uint32_t n_regions);   // what the newline index of n_regions regions and its scan write
+    DevBuf result;         // hhgt_encode_result staging, for a caller's record the device cannot write itself
+    int ensure_index(uint32_t n_regions, hipStream_t st);   // what the newline index of n_regions regions writes
     int ensure_lines(uint32_t max_lines);   // what the stages behind the index write for at most max_lines lines
-    int ensure_scan(uint64_t n);            // scan_tmp for a pair of scans over n elements
     int ensure_runs();                      // run_first, run_names, result: one size each (a call without text still finishes)
     template <typename F> void each(F f)
     {
-        for (DevBuf *b : {&slots, &counts, &prefix, &nl, &scan_tmp, &run_first, &run_names, &result}) f(*b);
+        for (DevBuf *b : {&slots, &counts, &nl, &scan_tmp, &region_tot, &n_lines, &line_tot, &run_first, &run_names, &result}) f(*b);
         for (DevBuf &b : line) f(b);
+        for (DevBuf &b : scanned) f(b);
     }
     // the launchers' view: every member by name beside its buffer
     uint32_t *col(int i) const { return line[i].as<uint32_t>(); }
-    LineCols line_cols() const
+    LineCols line_cols(uint32_t max_lines) const
     {
         LineCols l;
         l.soff = col(L_SOFF), l.lend = col(L_LEND), l.pos = col(L_POS), l.refalt = col(L_REFALT), l.flags = col(L_FLAGS);
-        l.keep = col(L_KEEP), l.kidx = col(L_KIDX), l.cnew = col(L_CNEW), l.crun = col(L_CRUN);
+        l.tot = line_tot.as<uint32_t>();
+        const bool sc = chain_scanned(max_lines);
+        l.keep = sc ? scanned[S_KEEP].as<uint32_t>() : nullptr, l.kidx = sc ? scanned[S_KIDX].as<uint32_t>() : nullptr;
+        l.cnew = sc ? scanned[S_CNEW].as<uint32_t>() : nullptr, l.crun = sc ? scanned[S_CRUN].as<uint32_t>() : nullptr;
         return l;
     }
     KeptCols kept_cols() const
@@ -258,14 +318,15 @@ int launch_scan_exclusive_u32_pair(const uint32_t *in_a, uint32_t *out_a, const 
 size_t scan_tmp_elems(uint64_t n);
 
 // index.hip
-int launch_index_newlines(const uint8_t *d_text, uint64_t n, uint32_t *d_slots, uint32_t *d_counts,
+// d_region_tot: chain_groups(n_regions) words, zero on entry; the kernels add every region's count to its group's word
+int launch_index_newlines(const uint8_t *d_text, uint64_t n, uint32_t *d_slots, uint32_t *d_counts, uint32_t *d_region_tot,
                           uint32_t n_regions, uint32_t min_line, uint32_t S, int mode, DevCounters *d_cnt, hipStream_t st);
 int index_mode_default();
 // Everything after the newline index is sized by a host-side BOUND on the line count (max_lines) and reads the
-// actual count (d_nlines = prefix[n_regions]) and the append position (d_cursor) from device memory, so the chain
-// can be queued without a host round trip (hhgt_encode_text_async).
-int launch_compact_newlines(const uint32_t *d_slots, const uint32_t *d_counts, const uint32_t *d_prefix,
-                            uint32_t n_regions, uint32_t *d_nl, uint32_t max_lines, hipStream_t st);
+// actual count (d_nlines, written by k_compact_newlines) and the append position (d_cursor) from device memory, so the
+// chain can be queued without a host round trip (hhgt_encode_text_async).
+int launch_compact_newlines(const uint32_t *d_slots, const uint32_t *d_counts, const uint32_t *d_region_tot,
+                            uint32_t n_regions, uint32_t *d_nl, uint32_t max_lines, uint32_t *d_nlines, hipStream_t st);
 int launch_parse_fixed(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl, const uint32_t *d_nlines,
                        uint32_t max_lines, const RegionFilter &region, uint32_t S, const LineCols &l, int mode,
                        DevCounters *d_cnt, hipStream_t st);

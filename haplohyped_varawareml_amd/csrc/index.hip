@@ -10,11 +10,12 @@
 // Stage 1 (k_index_newlines): ONE streaming read of the text, 16 B per lane, coalesced; each wave
 //   owns a 16 KiB region and records the newline positions it finds in a private slot array.
 //   HBM bound: algorithmic bytes = nbytes read + 4 B per line written.
-// Stage 2 (k_compact_newlines): prefix over per-region counts -> dense nl[] array (O(lines)).
+// Stage 2 (k_compact_newlines): prefix over per-region counts -> dense nl[] array (O(lines)).  No scan launch: stage 1
+//   leaves a total per 256 regions, every workgroup sums the totals in front of it (common.h, CHAIN_GROUP).
 // Stage 3 (k_parse_fixed): one lane per line walks the 9 fixed columns (O(F) bytes per line,
 //   F ~ 60-300 B, versus the ~10 KB sample region that only the encode stage reads).
-// Stage 4 (k_compact_kept): kept records are compacted (exclusive scan of keep flags) and the
-//   per-record table (start, stop, ref, alt) is written at v_base + k.
+// Stage 4 (k_compact_kept): kept records are compacted (exclusive scan of keep flags: stage 3's totals per 256 lines
+//   and a scan inside the workgroup) and the per-record table (start, stop, ref, alt) is written at v_base + k.
 #include "common.h"
 
 typedef uint32_t u32x4_unaligned __attribute__((ext_vector_type(4), aligned(1)));
@@ -31,8 +32,8 @@ __device__ __forceinline__ uint32_t nl_mask4(uint32_t x)
 // grid: ceil(n_regions / 4) blocks of 256 threads; wave w of block b scans region 4b + w.
 __global__ __launch_bounds__(256) void k_index_newlines(const uint8_t *__restrict__ text, uint64_t n,
                                                         uint32_t *__restrict__ slots,
-                                                        uint32_t *__restrict__ counts, uint32_t n_regions,
-                                                        DevCounters *cnt)
+                                                        uint32_t *__restrict__ counts, uint32_t *__restrict__ region_tot,
+                                                        uint32_t n_regions, DevCounters *cnt)
 {
     HHGT_WAVE_PRIO();
     const uint32_t lane = threadIdx.x & 63u;
@@ -88,7 +89,11 @@ __global__ __launch_bounds__(256) void k_index_newlines(const uint8_t *__restric
         wcount += __shfl(inc, 63, 64);
     }
     if (__ballot(overflow) != 0ull && lane == 0) atomicAdd(&cnt->err_density, 1ull);
-    if (lane == 0) counts[r] = wcount < INDEX_CAP ? wcount : INDEX_CAP;
+    if (lane == 0) {
+        const uint32_t c = wcount < INDEX_CAP ? wcount : INDEX_CAP;
+        counts[r] = c;
+        if (c) atomicAdd(&region_tot[r / CHAIN_GROUP], c);   // (k_compact_newlines sums these instead of a scan of counts[])
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -158,8 +163,8 @@ __device__ __forceinline__ uint32_t head_kth(uint32_t m16, uint32_t cum, uint32_
 #endif
 template <int U, bool WALK>
 __global__ __launch_bounds__(256) void k_index_hop(const uint8_t *__restrict__ text, uint64_t n, uint32_t *__restrict__ slots,
-                                                   uint32_t *__restrict__ counts, uint32_t n_regions, uint32_t skip, uint32_t S,
-                                                   DevCounters *cnt, uint32_t HOP_K)
+                                                   uint32_t *__restrict__ counts, uint32_t *__restrict__ region_tot, uint32_t n_regions,
+                                                   uint32_t skip, uint32_t S, DevCounters *cnt, uint32_t HOP_K)
 {
     HHGT_WAVE_PRIO();
     const uint32_t lane = threadIdx.x & 63u;
@@ -505,20 +510,40 @@ __global__ __launch_bounds__(256) void k_index_hop(const uint8_t *__restrict__ t
         if (have_cand && fb > last_term) fb = p + 1 > last_term ? p + 1 : last_term;
     }
     if (overflow && lane == 0) atomicAdd(&cnt->err_density, 1ull);
-    if (lane < r_cnt) counts[r_first + lane] = cntv < INDEX_CAP ? cntv : INDEX_CAP;
+    const uint32_t mine = lane < r_cnt ? (cntv < INDEX_CAP ? cntv : INDEX_CAP) : 0u;
+    if (lane < r_cnt) counts[r_first + lane] = mine;
+    // the totals k_compact_newlines sums instead of a scan of counts[]: the wave's HOP_K <= 64 regions lie in one group of
+    // CHAIN_GROUP regions or in two neighbouring ones
+    const uint32_t g0 = r_first / CHAIN_GROUP;
+    const uint32_t split = (g0 + 1u) * CHAIN_GROUP - r_first;   // the lanes from here on hold regions of group g0 + 1
+    const uint32_t a = lane < split ? mine : 0u;
+    const uint32_t sum_a = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_sum_dpp(a, lane), 63);
+    const uint32_t sum_b = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_sum_dpp(mine - a, lane), 63);
+    if (lane == 0) {
+        if (sum_a) atomicAdd(&region_tot[g0], sum_a);
+        if (sum_b) atomicAdd(&region_tot[g0 + 1u], sum_b);
+    }
 }
 
-// one thread per region: copy its slot entries to their final place
-__global__ __launch_bounds__(256) void k_compact_newlines(const uint32_t *__restrict__ slots,
-                                                          const uint32_t *__restrict__ counts,
-                                                          const uint32_t *__restrict__ prefix,
-                                                          uint32_t n_regions, uint32_t *__restrict__ nl,
-                                                          uint32_t max_lines)
+// one thread per region: copy its slot entries to their final place.  The place is the sum of the counts in front of the
+// region: the totals of the workgroups (CHAIN_GROUP regions each) in front of this one, left behind by the index kernel
+// and summed here by every workgroup for itself, plus a scan of the workgroup's own counts.  *d_nlines = all of them
+__global__ __launch_bounds__(CHAIN_GROUP) void k_compact_newlines(const uint32_t *__restrict__ slots,
+                                                                  const uint32_t *__restrict__ counts,
+                                                                  const uint32_t *__restrict__ region_tot,
+                                                                  uint32_t n_regions, uint32_t *__restrict__ nl,
+                                                                  uint32_t max_lines, uint32_t *__restrict__ d_nlines)
 {
     HHGT_WAVE_PRIO();
-    uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_regions) return;
-    uint32_t c = counts[r], p = prefix[r];
+    __shared__ uint32_t sm[8];
+    const uint32_t r = blockIdx.x * CHAIN_GROUP + threadIdx.x;
+    uint32_t pre = 0;
+    for (uint32_t g = threadIdx.x; g < blockIdx.x; g += CHAIN_GROUP) pre += region_tot[g];
+    uint32_t front, own;
+    block_excl_scan(pre, &front, sm);
+    const uint32_t c = r < n_regions ? counts[r] : 0u;
+    const uint32_t p = front + block_excl_scan(c, &own, sm);
+    if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0u) *d_nlines = front + own;   // (the workgroup of the last region)
     const uint32_t *my = slots + (size_t)r * INDEX_CAP;
     for (uint32_t k = 0; k < c && p + k < max_lines; ++k) nl[p + k] = my[k];   // lines past the caller's bound: err_lines
 }
@@ -530,9 +555,11 @@ __global__ __launch_bounds__(256) void k_parse_fixed(const uint8_t *__restrict__
                                                      uint32_t max_lines, const RegionFilter rfv, uint32_t S,
                                                      uint32_t *__restrict__ l_soff, uint32_t *__restrict__ l_lend,
                                                      uint32_t *__restrict__ l_pos, uint32_t *__restrict__ l_refalt,
-                                                     uint32_t *__restrict__ l_flags, uint32_t *__restrict__ l_keep,
-                                                     uint32_t *__restrict__ l_cnew, DevCounters *cnt, uint32_t hop_skip)
+                                                     uint32_t *__restrict__ l_flags, uint32_t *__restrict__ l_tot,
+                                                     uint32_t *__restrict__ l_keep, uint32_t *__restrict__ l_cnew,
+                                                     DevCounters *cnt, uint32_t hop_skip)
 {
+    static_assert(CHAIN_GROUP == 256u, "one k_parse_fixed workgroup is one group of k_compact_kept's prefix");
     HHGT_WAVE_PRIO();
     // The walk below is byte-serial per line; straight from global memory that is ~80 dependent loads per lane with
     // every wave of the grid resident at once, i.e. the kernel lasts one full latency chain (89 us for 136 k lines).
@@ -549,8 +576,10 @@ __global__ __launch_bounds__(256) void k_parse_fixed(const uint8_t *__restrict__
         cnt->err_lines = n_found > max_lines ? (unsigned long long)(n_found - max_lines) : 0ull;
     }
     if (blockIdx.x * blockDim.x >= n_lines) {
-        // the grid is sized by max_lines: the scans behind this kernel run over max_lines flags
-        if (i < max_lines) l_keep[i] = l_cnew[i] = 0u;
+        // the grid is sized by max_lines, and so is k_compact_kept's: every workgroup leaves its two totals (l_keep: the scans
+        // behind this kernel run over max_lines flags)
+        if (threadIdx.x == 0u) l_tot[blockIdx.x] = l_tot[gridDim.x + blockIdx.x] = 0u;
+        if (l_keep && i < max_lines) l_keep[i] = l_cnew[i] = 0u;
         return;
     }
     uint32_t flags = 0;
@@ -747,20 +776,22 @@ __global__ __launch_bounds__(256) void k_parse_fixed(const uint8_t *__restrict__
         l_pos[i] = pos0;
         l_refalt[i] = refalt | ((gtidx & 0xFFFu) << 16) | (stride << 28);   // (12 bits of GT key index: a FORMAT column of 4096 keys is reported, below)
         l_flags[i] = flags;
+    }
+    if (l_keep && i < max_lines) {
         l_keep[i] = (flags & LF_KEEP) ? 1u : 0u;
         l_cnew[i] = (flags & LF_CHROM_NEW) ? 1u : 0u;
-    } else if (i < max_lines) {
-        l_keep[i] = l_cnew[i] = 0u;
     }
     // statistics: one atomic per WORKGROUP per category.  (One per wave was 4 k atomic adds on one address for a chr1-sized
     // block — they retire one every ~12 ns, so the kernel took 66 us where its parse needs 20: round 4, from the kernel trace.)
-    __shared__ uint32_t s_stat[4];
+    // The kept lines and the CHROM-run starts of the workgroup are counted the same way and stored, not added: the totals
+    // k_compact_kept sums for its prefixes.
+    __shared__ uint32_t s_stat[6];
     const uint32_t lane = threadIdx.x & 63u;
-    if (threadIdx.x < 4u) s_stat[threadIdx.x] = 0u;
+    if (threadIdx.x < 6u) s_stat[threadIdx.x] = 0u;
     __syncthreads();
-    const uint32_t kinds[4] = {LF_RECORD, LF_DROP_REGION, LF_DROP_FILTER, LF_MALFORMED};
+    const uint32_t kinds[6] = {LF_RECORD, LF_DROP_REGION, LF_DROP_FILTER, LF_MALFORMED, LF_KEEP, LF_CHROM_NEW};
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < 6; ++k) {
         const unsigned long long b = __ballot(flags & kinds[k]);
         if (lane == 0 && b) atomicAdd(&s_stat[k], (uint32_t)__popcll(b));
     }
@@ -769,33 +800,64 @@ __global__ __launch_bounds__(256) void k_parse_fixed(const uint8_t *__restrict__
         unsigned long long *dst = threadIdx.x == 0u ? &cnt->n_records : (threadIdx.x == 1u ? &cnt->n_drop_region : (threadIdx.x == 2u ? &cnt->n_drop_filter : &cnt->n_malformed));
         atomicAdd(dst, (unsigned long long)s_stat[threadIdx.x]);
     }
+    if (threadIdx.x == 4u) l_tot[blockIdx.x] = s_stat[4];
+    if (threadIdx.x == 5u) l_tot[gridDim.x + blockIdx.x] = s_stat[5];
 }
 
-// one thread per line; kept lines scatter to their compacted slot
-__global__ __launch_bounds__(256) void k_compact_kept(
+// one thread per line; kept lines scatter to their compacted slot.  A line's slot is the number of kept lines in front of
+// it (kidx) and its CHROM run the number of run starts in front of it (crun): the totals k_parse_fixed left for the
+// workgroups in front of this one, summed here by every workgroup for itself, plus a scan of the workgroup's own flags.
+// SCANNED (more workgroups than CHAIN_FANIN_MAX): both come from the scan launches in between, l_kidx / l_crun.
+template <bool SCANNED>
+__global__ __launch_bounds__(CHAIN_GROUP) void k_compact_kept(
     const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ nl, const uint32_t *__restrict__ d_nlines,
     uint32_t max_lines, const uint32_t *__restrict__ l_soff,
     const uint32_t *__restrict__ l_lend, const uint32_t *__restrict__ l_pos, const uint32_t *__restrict__ l_refalt,
-    const uint32_t *__restrict__ l_flags, const uint32_t *__restrict__ l_kidx, const uint32_t *__restrict__ l_crun,
+    const uint32_t *__restrict__ l_flags, const uint32_t *__restrict__ l_tot, const uint32_t *__restrict__ l_kidx,
+    const uint32_t *__restrict__ l_crun,
     uint32_t *__restrict__ k_soff, uint32_t *__restrict__ k_lend, uint32_t *__restrict__ k_meta,
     uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag, uint64_t *__restrict__ run_first, uint8_t *__restrict__ run_names,
     uint32_t max_runs, const uint64_t *__restrict__ d_cursor, uint64_t v_capacity, uint32_t ring, uint32_t *__restrict__ d_start,
     uint32_t *__restrict__ d_stop, uint8_t *__restrict__ d_ref, uint8_t *__restrict__ d_alt, DevCounters *cnt, uint32_t strided)
 {
     HHGT_WAVE_PRIO();
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t i = blockIdx.x * CHAIN_GROUP + threadIdx.x;
     const uint32_t n_found = *d_nlines;
     const uint32_t n_lines = n_found < max_lines ? n_found : max_lines;
-    if (i >= n_lines) return;
+    if (blockIdx.x * CHAIN_GROUP >= n_lines) return;   // (the whole workgroup: the ones that stay scan together)
+    const bool live = i < n_lines;
+    const uint32_t flags = live ? l_flags[i] : 0u;
+    uint32_t kidx, crun;
+    if (SCANNED) {
+        kidx = live ? l_kidx[i] : 0u;
+        crun = live ? l_crun[i] : 0u;
+    } else {
+        __shared__ uint32_t sm[8];
+        uint32_t pre_k = 0, pre_c = 0;
+        for (uint32_t g = threadIdx.x; g < blockIdx.x; g += CHAIN_GROUP) {
+            pre_k += l_tot[g];
+            pre_c += l_tot[gridDim.x + g];
+        }
+        uint32_t front_k, front_c, own;
+        block_excl_scan(pre_k, &front_k, sm);
+        block_excl_scan(pre_c, &front_c, sm);
+        // both flags in one scan: at most 256 of either, so the halves of a word hold them
+        const uint32_t ex = block_excl_scan(((flags & LF_KEEP) ? 1u : 0u) | ((flags & LF_CHROM_NEW) ? 0x10000u : 0u), &own, sm);
+        kidx = front_k + (ex & 0xFFFFu);
+        crun = front_c + (ex >> 16);
+    }
+    if (i == n_lines - 1) {
+        cnt->n_kept = (unsigned long long)kidx + ((flags & LF_KEEP) ? 1u : 0u);
+        cnt->n_chrom_runs = (unsigned long long)crun + ((flags & LF_CHROM_NEW) ? 1u : 0u);
+    }
     const uint64_t v_base = *d_cursor;
-    const uint32_t flags = l_flags[i];
     if (flags & LF_CHROM_NEW) {
         // run id = number of CHROM_NEW flags before this line; the run's first kept index is the
         // exclusive kept-prefix here; its name is the CHROM field at the start of this line (copied out now: the text
         // buffer may be recycled before the host looks at the runs)
-        uint32_t rid = l_crun[i];
+        uint32_t rid = crun;
         if (rid < max_runs) {
-            run_first[rid] = l_kidx[i];
+            run_first[rid] = kidx;
             const uint32_t s0 = i ? nl[i - 1] + 1u : 0u;
             uint8_t *nm = run_names + (size_t)rid * 32u;
             uint32_t q = 0;
@@ -807,16 +869,12 @@ __global__ __launch_bounds__(256) void k_compact_kept(
             for (; q < 32u; ++q) nm[q] = 0;
         }
     }
-    if (i == n_lines - 1) {
-        cnt->n_kept = (unsigned long long)l_kidx[n_lines];
-        cnt->n_chrom_runs = (unsigned long long)l_crun[n_lines];
-    }
     // kept lines that are not of the fixed-width shape go on the variable-width kernel's list: one atomic add per WAVE (config
     // 4 has 88 k such lines per pass — one returning add each on one address was most of this kernel's time)
     // (k_meta: bit 2 FAST, bits 8-19 GT key index, bits 20-23 column stride of a GT-first record whose columns are all of one
     // width; with `strided` — the bit-plane encoder runs — such a record is the tile kernel's, not the variable-width kernel's)
     const bool keep = (flags & LF_KEEP) != 0u;
-    const bool slow = keep && !(flags & LF_FAST) && !(strided && (l_refalt[i < n_lines ? i : 0u] >> 28) != 0u);
+    const bool slow = keep && !(flags & LF_FAST) && !(strided && (l_refalt[live ? i : 0u] >> 28) != 0u);
     const unsigned long long sm = __ballot(slow);
     unsigned long long slot0 = 0ull;
     if (sm != 0ull) {
@@ -828,7 +886,7 @@ __global__ __launch_bounds__(256) void k_compact_kept(
         slot0 = base + (unsigned long long)__popcll(sm & ((1ull << lane) - 1ull));
     }
     if (!keep) return;
-    const uint32_t k = l_kidx[i];
+    const uint32_t k = kidx;
     uint64_t v = v_base + k;
     const uint32_t ra = l_refalt[i];
     k_soff[k] = l_soff[i];
@@ -866,7 +924,7 @@ static uint32_t index_hop_skip(uint32_t min_line, int mode)
     return mode && min_line >= 1536u ? min_line - 16u : 0u;   // margin: the loads start at the 16-byte line in front of the target
 }
 
-int launch_index_newlines(const uint8_t *d_text, uint64_t n, uint32_t *d_slots, uint32_t *d_counts,
+int launch_index_newlines(const uint8_t *d_text, uint64_t n, uint32_t *d_slots, uint32_t *d_counts, uint32_t *d_region_tot,
                           uint32_t n_regions, uint32_t min_line, uint32_t S, int mode, DevCounters *d_cnt, hipStream_t st)
 {
     if (mode < 0) mode = index_mode_default();
@@ -884,7 +942,7 @@ int launch_index_newlines(const uint8_t *d_text, uint64_t n, uint32_t *d_slots, 
         K = K > 64u ? 64u : K;
 #define HOP_LAUNCH(U, W)                                                                                                      \
     hipLaunchKernelGGL((k_index_hop<U, W>), dim3(((n_regions + K - 1) / K + 3) / 4), dim3(256), 0, st, d_text, n, d_slots, d_counts, \
-                       n_regions, skip, S, d_cnt, K)
+                       d_region_tot, n_regions, skip, S, d_cnt, K)
         if (min_line >= 4096u) {
             if (walk) HOP_LAUNCH(5, true);
             else HOP_LAUNCH(5, false);
@@ -897,16 +955,16 @@ int launch_index_newlines(const uint8_t *d_text, uint64_t n, uint32_t *d_slots, 
         return HHGT_OK;
     }
     hipLaunchKernelGGL(k_index_newlines, dim3((n_regions + 3) / 4), dim3(256), 0, st, d_text, n, d_slots,
-                       d_counts, n_regions, d_cnt);
+                       d_counts, d_region_tot, n_regions, d_cnt);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }
 
-int launch_compact_newlines(const uint32_t *d_slots, const uint32_t *d_counts, const uint32_t *d_prefix,
-                            uint32_t n_regions, uint32_t *d_nl, uint32_t max_lines, hipStream_t st)
+int launch_compact_newlines(const uint32_t *d_slots, const uint32_t *d_counts, const uint32_t *d_region_tot,
+                            uint32_t n_regions, uint32_t *d_nl, uint32_t max_lines, uint32_t *d_nlines, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_compact_newlines, dim3((n_regions + 255) / 256), dim3(256), 0, st, d_slots, d_counts,
-                       d_prefix, n_regions, d_nl, max_lines);
+    hipLaunchKernelGGL(k_compact_newlines, dim3(chain_groups(n_regions)), dim3(CHAIN_GROUP), 0, st, d_slots, d_counts,
+                       d_region_tot, n_regions, d_nl, max_lines, d_nlines);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }
@@ -921,8 +979,8 @@ int launch_parse_fixed(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl, 
     // may have looked at nothing but the head of a record: a dropped record is examined from end to end)
     uint32_t hop_skip = index_hop_skip(S ? 2u * S + 17u : 0u, mode);
     if (hop_skip && mode >= 2) hop_skip = 0xFFFFFFFFu;
-    hipLaunchKernelGGL(k_parse_fixed, dim3((max_lines + 255) / 256), dim3(256), 0, st, d_text, n, d_nl, d_nlines,
-                       max_lines, region, S, l.soff, l.lend, l.pos, l.refalt, l.flags, l.keep, l.cnew, d_cnt, hop_skip);
+    hipLaunchKernelGGL(k_parse_fixed, dim3(chain_groups(max_lines)), dim3(CHAIN_GROUP), 0, st, d_text, n, d_nl, d_nlines,
+                       max_lines, region, S, l.soff, l.lend, l.pos, l.refalt, l.flags, l.tot, l.keep, l.cnew, d_cnt, hop_skip);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }
@@ -933,9 +991,15 @@ int launch_compact_kept(const uint8_t *d_text, uint64_t n, const uint32_t *d_nl,
                         bool strided, hipStream_t st)
 {
     if (max_lines == 0) return HHGT_OK;
-    hipLaunchKernelGGL(k_compact_kept, dim3((max_lines + 255) / 256), dim3(256), 0, st, d_text, n, d_nl, d_nlines, max_lines,
-                       l.soff, l.lend, l.pos, l.refalt, l.flags, l.kidx, l.crun, k.soff, k.lend, k.meta, k.redo_list, k.redo_flag,
-                       k.run_first, k.run_names, max_runs, d_cursor, v_capacity, ring, d_start, d_stop, d_ref, d_alt, d_cnt, strided ? 1u : 0u);
+    // (the grid of k_parse_fixed: l.tot holds a pair of totals per workgroup of either)
+#define KEPT_LAUNCH(SCANNED)                                                                                                         \
+    hipLaunchKernelGGL(k_compact_kept<SCANNED>, dim3(chain_groups(max_lines)), dim3(CHAIN_GROUP), 0, st, d_text, n, d_nl, d_nlines, \
+                       max_lines, l.soff, l.lend, l.pos, l.refalt, l.flags, l.tot, l.kidx, l.crun, k.soff, k.lend, k.meta,          \
+                       k.redo_list, k.redo_flag, k.run_first, k.run_names, max_runs, d_cursor, v_capacity, ring, d_start, d_stop,   \
+                       d_ref, d_alt, d_cnt, strided ? 1u : 0u)
+    if (chain_scanned(max_lines)) KEPT_LAUNCH(true);
+    else KEPT_LAUNCH(false);
+#undef KEPT_LAUNCH
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

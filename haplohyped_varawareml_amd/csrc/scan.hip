@@ -1,5 +1,5 @@
 // scan.hip — device-wide exclusive prefix sum of uint32 (reduce / scan-partials / downsweep).
-// Small helper used by the line index, the kept-record compaction and the chunk framing; the
+// Small helper used by the kept-record compaction of long line lists and the chunk framing; the
 // arrays are O(lines) or O(chunks), never O(text bytes), so this is not a bandwidth-critical kernel.
 #include "common.h"
 
@@ -7,37 +7,7 @@
 #define SCAN_ITEMS 8
 #define SCAN_TILE (SCAN_BLOCK * SCAN_ITEMS)
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-
-// exclusive scan of one value per thread across a 256-thread block; returns exclusive prefix,
-// *total = block sum (valid in all threads)
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *total, uint32_t *sm /*>=8*/)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t inc = wave_incl_scan(v);
-    if (lane == 63) sm[w] = inc;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
-        uint32_t x = sm[i];
-        if (i < w) base += x;
-        tot += x;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
-
+// (wave_incl_scan, block_excl_scan: common.h — the compactions of index.hip scan with them too)
 __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_reduce(const uint32_t *__restrict__ in, uint64_t n,
                                                             uint32_t *__restrict__ partial)
 {
@@ -121,7 +91,7 @@ int launch_scan_exclusive_u32(const uint32_t *d_in, uint32_t *d_out, uint64_t n,
 
 // ---- two launches instead of three, and two arrays per pass: the arrays scanned on the encode path have at most a few
 // hundred tiles, so every downsweep block sums the partials in front of it itself (no k_scan_partials in between), and
-// the keep / chrom-run flags of the lines go through together.  B = 1 or 2 arrays.
+// the keep / chrom-run flags of the lines go through together (B = 2 arrays).
 template <int B>
 __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_reduce_n(const uint32_t *__restrict__ in0, const uint32_t *__restrict__ in1,
                                                               uint64_t n, uint32_t *__restrict__ partial, uint32_t nb)
@@ -181,7 +151,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_down_n(const uint32_t *__re
     }
 }
 
-// out_a[0..n] / out_b[0..n] = exclusive prefix sums of in_a / in_b (out[n] = total); in_b == nullptr: one array.
+// out_a[0..n] / out_b[0..n] = exclusive prefix sums of in_a / in_b (out[n] = total).
 // d_tmp: 2 * scan_tmp_elems(n) elements.  More than SCAN_SHORT_MAX tiles: the three-launch form, one array at a time.
 #define SCAN_SHORT_MAX 2048u
 int launch_scan_exclusive_u32_pair(const uint32_t *in_a, uint32_t *out_a, const uint32_t *in_b, uint32_t *out_b, uint64_t n,
@@ -191,20 +161,15 @@ int launch_scan_exclusive_u32_pair(const uint32_t *in_a, uint32_t *out_a, const 
     if (nb == 0) nb = 1;
     if (nb > SCAN_SHORT_MAX) {
         int rc = launch_scan_exclusive_u32(in_a, out_a, n, d_tmp, tmp_elems, st);
-        if (rc == HHGT_OK && in_b) rc = launch_scan_exclusive_u32(in_b, out_b, n, d_tmp, tmp_elems, st);
+        if (rc == HHGT_OK) rc = launch_scan_exclusive_u32(in_b, out_b, n, d_tmp, tmp_elems, st);
         return rc;
     }
     if (tmp_elems < 2 * (size_t)nb) {
         hhgt_set_error("scan: tmp too small");
         return HHGT_ERR_ARG;
     }
-    if (in_b) {
-        hipLaunchKernelGGL(k_scan_reduce_n<2>, dim3(nb), dim3(SCAN_BLOCK), 0, st, in_a, in_b, n, d_tmp, nb);
-        hipLaunchKernelGGL(k_scan_down_n<2>, dim3(nb), dim3(SCAN_BLOCK), 0, st, in_a, in_b, n, d_tmp, nb, out_a, out_b);
-    } else {
-        hipLaunchKernelGGL(k_scan_reduce_n<1>, dim3(nb), dim3(SCAN_BLOCK), 0, st, in_a, in_a, n, d_tmp, nb);
-        hipLaunchKernelGGL(k_scan_down_n<1>, dim3(nb), dim3(SCAN_BLOCK), 0, st, in_a, in_a, n, d_tmp, nb, out_a, out_a);
-    }
+    hipLaunchKernelGGL(k_scan_reduce_n<2>, dim3(nb), dim3(SCAN_BLOCK), 0, st, in_a, in_b, n, d_tmp, nb);
+    hipLaunchKernelGGL(k_scan_down_n<2>, dim3(nb), dim3(SCAN_BLOCK), 0, st, in_a, in_b, n, d_tmp, nb, out_a, out_b);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

@@ -126,9 +126,10 @@ int hhgt_encode_text(hhgt_ctx *ctx, const void *d_text, uint64_t nbytes, const c
  *   max_lines : caller's bound on the number of lines in the block (a VCF with S samples has at least 2*S + 16 bytes
  *               per data line).  Sizes the workspaces and the grids; lines beyond it are not encoded and reported in
  *               h_result->n_lines_over (hhgt_encode_result_status: HHGT_ERR_CAPACITY).
- *   h_result  : PINNED host memory (hipHostMalloc / torch pin_memory), written by a copy queued on `stream` behind the
- *               kernels; valid once the stream (or an event recorded after the call) has completed.  `done` is set
- *               to 1 by that copy.  May be NULL.
+ *   h_result  : PINNED host memory (hipHostMalloc / torch pin_memory), written by the call's last kernel itself; valid
+ *               once the stream (or an event recorded after the call) has completed.  `done` is stored last, 1, with
+ *               system-scope release.  (Memory the device cannot write: a copy queued on `stream` behind the kernels
+ *               writes record and `done`.)  May be NULL.
  * Errors that need the counts (malformed records, capacity, line density) are reported by hhgt_encode_result_status
  * on the completed h_result, not by the call.
  */
