@@ -16,9 +16,10 @@
 #define HHGT_WAVE_PRIO()
 #endif
 
-// wave-wide inclusive sum on DPP row shifts (no LDS round trips)
+// wave-wide inclusive sum on DPP row shifts (no LDS round trips); *total = the wave's sum (uniform), formed from the
+// rows' sums on the scalar unit, beside the lanes' last add
 #ifdef __HIPCC__
-__device__ __forceinline__ uint32_t wave_scan_sum_dpp(uint32_t x, uint32_t lane)
+__device__ __forceinline__ uint32_t wave_scan_sum_dpp(uint32_t x, uint32_t lane, uint32_t *total)
 {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);   // row_shr:1
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
@@ -27,8 +28,15 @@ __device__ __forceinline__ uint32_t wave_scan_sum_dpp(uint32_t x, uint32_t lane)
     const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 15);
     const uint32_t t1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 31) + t0;
     const uint32_t t2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + t1;
+    *total = (uint32_t)__builtin_amdgcn_readlane((int)x, 63) + t2;
     const uint32_t row = lane >> 4;
     return x + (row == 0u ? 0u : (row == 1u ? t0 : (row == 2u ? t1 : t2)));
+}
+
+__device__ __forceinline__ uint32_t wave_scan_sum_dpp(uint32_t x, uint32_t lane)
+{
+    uint32_t total;
+    return wave_scan_sum_dpp(x, lane, &total);
 }
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)

@@ -84,35 +84,6 @@ __device__ __forceinline__ Own6 lds_load6(const uint8_t *in, uint32_t pos)
 
 __device__ __forceinline__ uint32_t div255(uint32_t x) { return (x * 0x8081u) >> 23; }  // exact for x < 65536
 
-// ---------------------------------------------------------------------------------------------
-// DPP row shifts and the wave-wide inclusive scan built from them (used by the flush)
-__device__ __forceinline__ uint32_t dpp_row_shr(uint32_t x, int d)
-{
-    switch (d) {
-    case 1: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);
-    case 2: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
-    case 4: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);
-    default: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
-    }
-}
-
-// inclusive prefix sum over the 64 lanes; *total = wave sum (uniform)
-__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t x, uint32_t lane, uint32_t *total)
-{
-    x += dpp_row_shr(x, 1);
-    x += dpp_row_shr(x, 2);
-    x += dpp_row_shr(x, 4);
-    x += dpp_row_shr(x, 8);
-    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 15);
-    const uint32_t t1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 31) + t0;
-    const uint32_t t2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + t1;
-    const uint32_t t3 = (uint32_t)__builtin_amdgcn_readlane((int)x, 63) + t2;
-    const uint32_t row = lane >> 4;
-    x += row == 0u ? 0u : (row == 1u ? t0 : (row == 2u ? t1 : t2));
-    *total = t3;
-    return x;
-}
-
 #ifdef HHGT_LZ4_STATS
 // development build only (tools/lz4_stats.py): event counts of the window loop
 __device__ unsigned long long g_lz4_stat[8];
@@ -175,7 +146,7 @@ __device__ __forceinline__ void lz4_flush_queue(const uint8_t *in, uint8_t *__re
     const uint32_t mlx = (valid && mlc >= 15u) ? div255(mlc - 15u) + 1u : 0u;
     const uint32_t size = valid ? 3u + llx + ll + mlx : 0u;
     uint32_t total;
-    const uint32_t so = op + wave_incl_scan_dpp(size, lane, &total) - size;
+    const uint32_t so = op + wave_scan_sum_dpp(size, lane, &total) - size;
     if (valid) {
         const uint32_t token = ((ll < 15u ? ll : 15u) << 4) | (mlc < 15u ? mlc : 15u);
         const uint32_t q = so + 1u + llx + ll;

@@ -105,45 +105,6 @@ __device__ __forceinline__ uint2 bp_entry(uint32_t E, uint32_t msr, bool onM, bo
     return make_uint2(E | ((msr & 0x1FFFu) << 13) | (onM ? 1u << 26 : 0u) | (onT ? 1u << 27 : 0u) | ((rs - E) << 28), re | (off << 13));
 }
 
-// wave-wide inclusive scans on DPP row shifts (no LDS round trips): sum and max of non-negative values
-__device__ __forceinline__ uint32_t bp_row_shr(uint32_t x, int d)
-{
-    switch (d) {
-    case 1: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);
-    case 2: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
-    case 4: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);
-    default: return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
-    }
-}
-
-__device__ __forceinline__ uint32_t bp_scan_sum(uint32_t x, uint32_t lane)   // inclusive
-{
-    x += bp_row_shr(x, 1);
-    x += bp_row_shr(x, 2);
-    x += bp_row_shr(x, 4);
-    x += bp_row_shr(x, 8);
-    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 15);
-    const uint32_t t1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 31) + t0;
-    const uint32_t t2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + t1;
-    const uint32_t row = lane >> 4;
-    return x + (row == 0u ? 0u : (row == 1u ? t0 : (row == 2u ? t1 : t2)));
-}
-
-__device__ __forceinline__ uint32_t bp_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
-
-__device__ __forceinline__ uint32_t bp_scan_max(uint32_t x, uint32_t lane)   // inclusive
-{
-    x = bp_max(x, bp_row_shr(x, 1));
-    x = bp_max(x, bp_row_shr(x, 2));
-    x = bp_max(x, bp_row_shr(x, 4));
-    x = bp_max(x, bp_row_shr(x, 8));
-    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 15);
-    const uint32_t t1 = bp_max((uint32_t)__builtin_amdgcn_readlane((int)x, 31), t0);
-    const uint32_t t2 = bp_max((uint32_t)__builtin_amdgcn_readlane((int)x, 47), t1);
-    const uint32_t row = lane >> 4;
-    return bp_max(x, row == 0u ? 0u : (row == 1u ? t0 : (row == 2u ? t1 : t2)));
-}
-
 // 32 bits of the map starting at bit q (0 <= q < 4096 + 96)
 __device__ __forceinline__ uint32_t bp_bits(const uint32_t *bm, uint32_t q)
 {
@@ -300,7 +261,7 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     const uint32_t llT = onT ? rs - pe2 : 0u, lenT = re - rs;
     const uint32_t szM = onM ? 3u + bp_len_ext(llM) + llM + bp_len_ext(lenM - 4u) : 0u;
     const uint32_t szT = onT ? 3u + bp_len_ext(llT) + llT + bp_len_ext(lenT - 4u) : 0u;
-    const uint32_t sincl = bp_scan_sum(szM + szT, lane);
+    const uint32_t sincl = wave_scan_sum_dpp(szM + szT, lane);
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)sincl, 63);
     BP_MARK("sizes_done");
     // the batch's bytes go to the staging area; what is staged leaves in coalesced dwords when the next batch would not
@@ -324,21 +285,500 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     return BpOut{prev_end, gop, sop};
 }
 
+// ---- the plane coder: wave w codes plane w, in the phases below (bp_code_plane at the end calls them in order)
+// The lanes of the wave exchange data through the wave's BpLds (S) with no barrier in between: the LDS executes a wave's
+// instructions in order.  What the COMPILER must not do is move a lane's read in front of another lane's earlier write;
+// every such hand-over below is an access whose address it cannot tell apart from the lane's own writes, and BP_FENCE marks
+// the phase boundaries for good measure: a phase whose writes other lanes read next ends with one.  (volatile pointers
+// would also do — and turn every access into a serialised flat load with its own wait, which made this kernel 2x slower
+// than it had to be.)
+// How state travels, one rule per kind:
+//   * a phase RETURNS its results by value, as a small struct (like BpOut, and for BpOut's reason);
+//   * a phase TAKES the window's values as plain scalar parameters, not as those structs: the compiler simplifies every phase
+//     on its own before it inlines it, a scalar parameter is known to hold a defined value there and a struct's field is not,
+//     and what it makes of a bool that might be anything stays in the inlined code (lane masks turned into bytes in vector
+//     registers: 0.7 % of the step at clevel 9).  bp_lane_one's BpOne goes as a struct only to bp_table_insert, which
+//     does no arithmetic on it that differs;
+//   * the four arrays several phases share — bm, P, wpre, flag — come as pointer parameters ("P: parameter" in the
+//     headers below): bp_code_plane takes their addresses once, in front of everything, and the order in which the compiler
+//     meets them decides its schedule (taken inside the phases, at first use, the int8 kernel needs 66 vector registers
+//     instead of 64).  Every other array (cls, tab, chain, gbw, queue, stage, xm) a phase reaches through S.
+
+// development probes; all three are empty in the default build
+// -DBP_PROBE_SALU=n / -DBP_PROBE_VALU=n: n extra independent scalar / vector instructions per window — which issue port is
+// the tight one?
+__device__ __forceinline__ void bp_probe_salu()
+{
+#ifdef BP_PROBE_SALU
+#pragma unroll
+    for (int pr = 0; pr < BP_PROBE_SALU; ++pr) asm volatile("s_mov_b32 s90, 0" ::: "s90");
+#endif
+}
+
+__device__ __forceinline__ void bp_probe_valu()
+{
+#ifdef BP_PROBE_VALU
+    uint32_t pv;
+#pragma unroll
+    for (int pr = 0; pr < BP_PROBE_VALU; ++pr) asm volatile("v_mov_b32 %0, 0" : "=v"(pv));
+#endif
+}
+
+// -DBP_PROBE_HANDOFF (round 4): the least a wave would pay to hand its stream to another workgroup INSIDE this launch
+// (framing fused by a look-back, or "the chunk's last stream frames the chunk"): its stores drained, then one returning
+// agent-scope atomic on a word the 256 streams of its chunk share (a spare word behind the chunk's first scratch slot).
+// LZ4 stage with it: tools/dev/lz4_handoff.sh, DESIGN.md 3.3.  Returns the stream's size, op.
+__device__ __forceinline__ uint32_t bp_probe_handoff(uint8_t *__restrict__ scratch, uint64_t sidx, uint64_t slot_bytes, uint32_t op, uint32_t lane)
+{
+#ifdef BP_PROBE_HANDOFF
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    uint32_t old = 0;
+    if (lane == 0) old = atomicAdd(reinterpret_cast<uint32_t *>(scratch + (sidx & ~255ull) * slot_bytes + slot_bytes - 8u), 1u);
+    old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
+    op += old == 0xFFFFFFF0u ? 1u : 0u;   // (keeps the returned value alive; never true)
+#endif
+    return op;
+}
+
+// the ones of one 32-position half of the lane's 64 positions (bits w, EXC: missing-call bits x; the half starts at position
+// base - 1) go to P[at...] (P: parameter, see above); returns the P-index behind the last one stored.  Each round is a count-trailing-zeros, a clear
+// and a store, and there are as many rounds as the fullest word of the wave has ones.
+// (no `if (w != 0)` around the body: a lane that has run out stores to P's spare entry — an exec-mask region costs two
+// scalar instructions and a branch per round, and scalar issue is this kernel's tightest port)
+template <bool EXC, typename LDS>
+__device__ __forceinline__ uint32_t bp_list_half(LDS &S, uint16_t *P, uint32_t w, uint32_t x, uint32_t at, uint32_t base)
+{
+    while (__builtin_amdgcn_ballot_w64(w != 0u) != 0ull) {
+        const bool on = w != 0u;
+        const uint32_t bpos = (uint32_t)__builtin_ctz(w | 0x80000000u);
+        if (EXC && on && ((x >> bpos) & 1u)) atomicOr(&S.cls[at >> 5], 1u << (at & 31u));   // (LDS: ds_or_b32)
+        P[on ? at : BpCfg<EXC>::PTRASH] = (uint16_t)(base + bpos);
+        at += on ? 1u : 0u;
+        w &= w - 1u;
+    }
+    return at;
+}
+
+// the list of ones.  Reads nothing from S; writes wpre (every lane its own entry), P[0 .. m + 4] (P[0] = 0, the m ones, the
+// four sentinels behind them) and, EXC, the class bits in cls (zeroed by the kernel before the call).  The lane's bit-map
+// words (wlo, whi; EXC: xlo, xhi) and the scan over their counts (cnt, incl) come in registers.  Returns nothing.
+// (P, wpre: parameters, see above.)
+// (the two halves of the lane's 64 positions one after the other: twice ~6 rounds, where one loop over the 64-bit word ran
+// ~11 rounds of twice the work)
+template <bool EXC, typename LDS>
+__device__ __forceinline__ void bp_list_ones(LDS &S, uint16_t *P, uint16_t *wpre, uint32_t wlo, uint32_t whi, uint32_t xlo, uint32_t xhi, uint32_t incl,
+                                             uint32_t cnt, uint32_t m, uint32_t lane)
+{
+    wpre[lane] = (uint16_t)(incl - cnt);
+    BP_FENCE();
+    P[lane == 0u ? 0u : BpCfg<EXC>::PTRASH] = 0;
+    const uint32_t base = 64u * lane + 1u;
+    const uint32_t at = bp_list_half<EXC>(S, P, wlo, xlo, incl - cnt + 1u, base);
+    bp_list_half<EXC>(S, P, whi, xhi, at, base + 32u);
+    P[lane < 4u ? m + 1u + lane : BpCfg<EXC>::PTRASH] = (uint16_t)(BP_N + 1);
+    BP_FENCE();
+}
+
+// gap bytes of all ones (a candidate is compared on them, 4 at a time).  Reads P (bp_list_ones); writes gbw[0 .. m + 8)
+// as bytes: the zeros behind the one with P-index i, clipped to 255, and 255 from the last one on.  Returns nothing.
+// (P: parameter, see above.)
+template <bool EXC, typename LDS>
+__device__ __forceinline__ void bp_gap_bytes(LDS &S, const uint16_t *P, uint32_t m, uint32_t lane)
+{
+    uint8_t *gb = reinterpret_cast<uint8_t *>(S.gbw);
+    for (uint32_t i = lane; i < m + 8u; i += 64u) {
+        const uint32_t i1 = i + 1u < BpCfg<EXC>::PTRASH ? i + 1u : BpCfg<EXC>::PTRASH;   // (i < m + 8 <= 644: the loads stay inside P)
+        uint32_t g = (uint32_t)P[i1] - (uint32_t)P[i1 - 1u] - 1u;
+        g = g < 255u ? g : 255u;
+        gb[i] = (uint8_t)(i < m ? g : 255u);
+    }
+    BP_FENCE();
+}
+
+// the candidate table starts empty.  Writes tab; reads nothing.  (No fence: the first access behind it is the window's
+// exchange on tab itself, bp_table_insert.)
+template <typename LDS>
+__device__ __forceinline__ void bp_clear_table(LDS &S, uint32_t lane)
+{
+#pragma unroll
+    for (int k = 0; k < (1 << BP_HLOG) / 64; ++k) S.tab[64 * k + lane] = 0u;
+}
+
+// a lane's one of the window that starts at one jw (lane l has one j = jw + l; jw = -1 first: the virtual one at -1)
+struct BpOne {
+    int j, q;                    // index of the one (-1: the virtual one), its position
+    uint32_t jj, q1, qn1, qp1;   // index into P (0 for a lane behind the last one); P[jj], P[jj + 1], P[jj - 1] (0 for jj = 0)
+    uint32_t c5a;                // EXC: classes of this one (bit 0) and of the four ones behind it
+    bool valid, can;             // there is a one j; it may start a table match
+};
+
+// Reads P (parameter, see above) and, EXC, cls (both bp_list_ones); writes nothing.  Returns the lane's one.
+template <int DEPTH, bool EXC, typename LDS>
+__device__ __forceinline__ BpOne bp_lane_one(LDS &S, const uint16_t *P, int jw, uint32_t m, uint32_t lane)
+{
+    BpOne o;
+    o.j = jw + (int)lane;
+    o.valid = o.j < (int)m;
+    o.jj = o.valid ? (uint32_t)(o.j + 1) : 0u;
+    o.q1 = P[o.jj], o.qn1 = P[o.jj + 1u];
+    o.qp1 = o.jj ? P[o.jj - 1u] : 0u;
+    o.q = (int)o.q1 - 1;
+    o.can = DEPTH > 0 && o.valid && o.j >= 0 && o.q + 12 <= BP_N;
+    o.c5a = EXC ? (bp_bits(S.cls, o.jj) & 31u) : 0u;
+    return o;
+}
+
+// candidate table: keyed on the gap behind the one; exact recency through the LDS's lane order.  Reads and writes tab by
+// ONE exchange (cleared by bp_clear_table, filled by this phase in the windows before); CHAIN: writes chain[jj], what this
+// one replaced, the next candidate down the chain.  Returns jc1: the most recent earlier one with the lane's key + 1, 0: none.
+template <bool CHAIN, bool EXC, typename LDS>
+__device__ __forceinline__ uint32_t bp_table_insert(LDS &S, BpOne o)
+{
+    uint32_t jc1 = 0;
+    if (o.can) {
+        const uint32_t g1 = o.qn1 - o.q1;
+        const uint32_t idx = (g1 < BP_GAPCLIP ? g1 : BP_GAPCLIP) ^ ((EXC && (o.c5a & 1u)) ? 63u : 0u);
+        jc1 = atomicExch(&S.tab[idx], (uint32_t)(o.j + 1));
+        if (CHAIN) S.chain[o.jj] = (uint16_t)jc1;
+    }
+    BP_FENCE();
+    return jc1;
+}
+
+struct BpPick {
+    int best;            // the winner's score; < 0: no candidate agrees at all
+    uint32_t bjq, bk;    // best >= 0: its P-index, full gaps it agrees on (0..BP_PICK)
+    uint32_t a4;         // the lane's own next four gap bytes
+};
+
+// pick: the candidate with the longest forward agreement, judged on the gap BYTES — up to BP_PICK equal gaps, then 1 + the
+// smaller of the next pair.  All a candidate costs is one unaligned 4-byte fetch from the gap bytes, an xor and a
+// count-trailing-zeros; ties go to the nearer one.  Reads gbw (bp_gap_bytes), chain (bp_table_insert, this window and
+// earlier ones: jc1 and everything down the chain lies in front of the lane's one) and, EXC, cls; writes nothing.  Returns
+// the winner and the lane's own gap bytes, which the pricing needs again.
+template <int DEPTH, bool EXC, typename LDS>
+__device__ __forceinline__ BpPick bp_pick(LDS &S, bool can, uint32_t jj, uint32_t c5a, uint32_t jc1)
+{
+    constexpr bool CHAIN = DEPTH > 1;
+    const uint32_t a4 = bp_gap4(S.gbw, jj);
+    const uint8_t *gbb = reinterpret_cast<const uint8_t *>(S.gbw);
+    const uint32_t fa = jj ? (uint32_t)gbb[jj - 1u] : 0u;    // zeros in front of this one (clipped to 255)
+    const uint32_t na4 = ~a4;
+    const uint32_t stop4 = ((na4 - 0x01010101u) & ~na4 & 0x80808080u) | 0xFF000000u;   // a 255 agrees with nothing; 3 gaps at most
+    int best = -1;
+    uint32_t bjq = 0, bk = 0;
+    // (counted down: counted up, the compiler keeps this counter in a vector register where the loop is a function of its
+    // own, and a vector compare ends each of up to DEPTH rounds; so written it stays on the scalar unit, as it was inline)
+#pragma unroll 1
+    for (int left = DEPTH; left > 0; --left) {
+        const bool have = can && jc1 != 0u;
+        if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
+        const uint32_t jq = have ? jc1 : 1u;
+        const uint32_t b4 = bp_gap4(S.gbw, jq);
+        const uint32_t fb = (uint32_t)gbb[jq - 1u];
+        uint32_t nextc = 0;
+        if (CHAIN) nextc = S.chain[jq];
+        const uint32_t x = (a4 ^ b4) | stop4;
+        uint32_t k = (uint32_t)__builtin_ctz(x) >> 3;                           // agreeing gaps: 0..3
+        bool same = true;
+        if (EXC) {   // ... of which only those count whose next ones are of the same class; the first byte must agree at all
+            const uint32_t xc = c5a ^ (bp_bits(S.cls, jq) & 31u);
+            same = (xc & 1u) == 0u;
+            const uint32_t tv = (uint32_t)__builtin_ctz((xc >> 1) | 8u);
+            k = k < tv ? k : tv;
+        }
+        const uint32_t below = (1u << (8u * k)) - 1u;
+        const uint32_t sumg = __builtin_amdgcn_sad_u8(a4 & below, 0u, k + 1u);  // their zeros + their ones + this one
+        const uint32_t za = (a4 >> (8u * k)) & 0xFFu, zb = (b4 >> (8u * k)) & 0xFFu;
+        uint32_t fz = fa < fb ? fa : fb;                                        // the zeros in front a match would take along
+        fz = fz < BP_BACK ? fz : BP_BACK;
+        const int score = (int)(sumg + (za < zb ? za : zb) + fz);
+        const bool up = have & same & (score > best);   // (selects, not a branch)
+        best = up ? score : best;
+        bjq = up ? jq : bjq;
+        bk = up ? k : bk;
+        if (!CHAIN) break;
+        jc1 = have ? nextc : 0u;
+    }
+    return BpPick{best, bjq, bk, a4};
+}
+
+// what a one's table match is worth
+struct BpMatch {
+    bool hv;            // the one codes a match
+    uint32_t len, nb;   // hv: bytes from the one on, zeros in front of the one the match is pulled back over
+    uint32_t c1;        // hv: P[candidate] (the offset is q1 - c1)
+    uint32_t a_last;    // hv: P-index of the last one the match covers
+    uint32_t z_last;    // hv: zeros the match takes behind that one (0: it ends with the one)
+    bool clamped;       // hv: the match was cut at the stream's match limit
+};
+
+// the chosen candidate, exactly (positions from P): agreement may continue past the third gap (periodic planes; rare), then
+// the costs decide between this match and literals.  Reads P (parameter, see above) and, EXC, cls (bp_list_ones); writes
+// nothing.  Takes the pick's result and the lane's one as scalars.  Returns the
+// lane's match (hv = false where there is no candidate or literals are cheaper).
+template <bool EXC, typename LDS>
+__device__ __forceinline__ BpMatch bp_extend_and_price(LDS &S, const uint16_t *P, bool got, uint32_t bjq, uint32_t bk, uint32_t a4, uint32_t jj, int q,
+                                                       uint32_t q1, uint32_t qp1, uint32_t m)
+{
+    uint32_t len = 0, nb = 0, c1 = 0, a_last = jj, z_last = 0;
+    bool hv = false, clamped = false;
+    if (__builtin_amdgcn_ballot_w64(got) != 0ull) {
+        const uint32_t jq = got ? bjq : 1u;
+        const uint32_t cc1 = P[jq], cp1 = P[jq - 1u];
+        uint32_t a = jj + bk, b = jq + bk;          // P-indices of the ones the first open comparison starts at
+        uint32_t pa = P[a], pb = P[b];
+        uint32_t clen = pa - q1, costR = 0, tailz = 0, zl = 0;
+#pragma unroll
+        for (uint32_t s = 0; s < BP_PICK; ++s) {
+            const uint32_t g = (a4 >> (8u * s)) & 0xFFu;
+            costR += s < bk ? 1u + (g >= BP_TMIN + 1u ? 4u : g) : 0u;
+        }
+        bool act = got;
+        for (uint32_t s = bk;; ++s) {   // (per lane: s starts at the lane's own bk; the trip count is what the wave needs)
+            if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
+            // (branch-free body: lanes that are done keep their values through selects; a + 1, b + 1 <= m + 4 stay inside P)
+            const uint32_t na = P[a + 1u], nbn = P[b + 1u];
+            const uint32_t ga = na - pa - 1u, gb = nbn - pb - 1u;
+            const bool cdiff = EXC && (((bp_bits(S.cls, a + 1u) ^ bp_bits(S.cls, b + 1u)) & 1u) != 0u);
+            const bool stop = (s < BP_PICK) | (ga != gb) | (ga >= 255u) | (a >= m) | (s >= BP_STEPS) | cdiff;
+            const uint32_t z = ga < gb ? ga : gb;
+            costR += act ? 1u + (ga >= BP_TMIN + 1u ? 4u : ga) : 0u;
+            clen += act ? 1u + (stop ? z : ga) : 0u;
+            tailz = (act & stop) ? ga - z : tailz;
+            zl = (act & stop) ? z : zl;
+            act = act & !stop;
+            a += act ? 1u : 0u;
+            b += act ? 1u : 0u;
+            pa = act ? na : pa;
+            pb = act ? nbn : pb;
+        }
+        const uint32_t gq = q1 - qp1 - 1u, gc = cc1 - cp1 - 1u;
+        uint32_t cnb = gq < gc ? gq : gc;
+        cnb = cnb < BP_BACK ? cnb : BP_BACK;
+        const uint32_t costH = 3u + (clen + cnb >= 19u ? 1u : 0u) - cnb + (tailz >= BP_TMIN ? 3u : tailz);
+        uint32_t end = (uint32_t)q + clen;
+        const bool cut = end > BP_MATCHLIMIT;
+        end = end < BP_MATCHLIMIT ? end : BP_MATCHLIMIT;
+        // signed compares: costH may go below zero when many zeros are pulled in
+        const int gain = (int)costR - (int)costH;
+        hv = got & (gain > 0) & ((int)end - q >= 4) & ((int)end - (q - (int)cnb) >= BP_MINM) & (q <= BP_MFLIMIT);   // (& not &&: no nest of exec-mask regions)
+        len = hv ? end - (uint32_t)q : 0u;
+        nb = hv ? cnb : 0u;
+        c1 = hv ? cc1 : 0u;
+        a_last = a;
+        z_last = zl;
+        clamped = cut & hv;
+    }
+    return BpMatch{hv, len, nb, c1, a_last, z_last, clamped};
+}
+
+// one-step lazy rule (the file-writing paths' effort level; tools/sim/gapenc_ref.c states it): a one gives up its match when
+// the NEXT one lies inside that match and has a match of its own that ends further by at least BP_LAZY_MIN + what giving up
+// costs (the zeros this one's match was pulled back over, the zeros between this one and the start of the next one's
+// match).  The next one is the neighbouring lane (the window's last lane keeps its match); in a run of lanes that all would
+// give up, every other one does, counted from the far end.  Touches no LDS: the neighbour's match comes over DPP.  Returns
+// the lane's match, or no match where it gave up.
+__device__ __forceinline__ BpMatch bp_lazy_rule(bool hv, uint32_t len, uint32_t nb, uint32_t c1, uint32_t a_last, uint32_t z_last, bool clamped, int j, int q,
+                                             uint32_t jj, uint32_t q1, uint32_t qn1, uint32_t m, uint32_t lane)
+{
+    const uint32_t E0 = hv ? (uint32_t)q + len : (uint32_t)(q + 1);
+    const uint32_t hvN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(hv ? 1u : 0u), 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+    const uint32_t EN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)E0, 0x130, 0xf, 0xf, false);
+    const uint32_t nbN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nb, 0x130, 0xf, 0xf, false);
+    const int msN = (int)qn1 - 1 - (int)nbN;                        // where the next one's match starts
+    const int between = msN - (int)q1 > 0 ? msN - (int)q1 : 0;     // zeros between this one and that start
+    const bool Ln = hv & (hvN != 0u) & (lane < 63u) & (j + 1 < (int)m) & (qn1 <= E0) &
+                    ((int)EN - (int)E0 >= (int)(BP_LAZY_MIN + nb) + between);
+    const unsigned long long lm = __builtin_amdgcn_ballot_w64(Ln);
+    const unsigned long long rest = ~(lm >> lane);                 // first zero bit = end of this lane's run
+    const uint32_t tlo = (uint32_t)__builtin_ctz((uint32_t)rest | 0x80000000u), thi = (uint32_t)__builtin_ctz((uint32_t)(rest >> 32) | 0x80000000u);
+    const uint32_t t = (uint32_t)rest != 0u ? tlo : 32u + thi;     // (lm >> lane has zeros from bit 64 - lane on: the run ends inside)
+    const bool give = Ln && (t & 1u);
+    return BpMatch{hv && !give, give ? 0u : len, give ? 0u : nb, give ? 0u : c1, give ? jj : a_last, give ? 0u : z_last, clamped && !give};
+}
+
+struct BpNext {
+    uint32_t E;     // end of what this one codes (0 for the virtual one)
+    uint32_t nxt;   // index of the first one at or behind E: the next coded one if this one is coded
+};
+
+// where the greedy parse goes on behind this one: first one at or behind E = the number of ones in front of position E.  A
+// one that codes itself alone (E = q + 1) has itself and its predecessors in front: its own P-index.  A match ends in the
+// zeros behind the last one it covers (or exactly at the next one): that one's P-index.  Only a match that was cut at the
+// stream's match limit (a handful of ones at the very end of a plane) needs the count from the bit map: reads bm (the
+// kernel, before bp_code_plane) and wpre (bp_list_ones) then, nothing otherwise (both parameters, see above); writes nothing.
+__device__ __forceinline__ BpNext bp_next_one(const uint32_t *bm, const uint16_t *wpre, bool hv, uint32_t len, uint32_t a_last, bool clamped, int q, uint32_t jj,
+                                           uint32_t m)
+{
+    const uint32_t E = hv ? (uint32_t)q + len : (uint32_t)(q + 1);
+    uint32_t nxt = hv ? a_last : jj;
+    if (__builtin_amdgcn_ballot_w64(clamped) != 0ull) {   // (wave-uniform, rare)
+        const uint32_t w = E >> 6, bb = E & 63u, wc = w < 63u ? w : 63u;
+        const uint32_t lo = bm[2u * wc], hi = bm[2u * wc + 1u];
+        const uint32_t mlo = bb >= 32u ? 0xFFFFFFFFu : ((1u << bb) - 1u);
+        const uint32_t mhi = bb > 32u ? ((1u << (bb - 32u)) - 1u) : 0u;
+        const uint32_t in_map = (uint32_t)wpre[wc] + (uint32_t)__popc(lo & mlo) + (uint32_t)__popc(hi & mhi);
+        nxt = clamped ? (w >= 64u ? m : in_map) : nxt;
+    }
+    return BpNext{E, nxt};
+}
+
+struct BpSel {
+    bool sel;   // this one is coded
+    int cur;    // next one to be coded behind this window (unchanged where the window's last coded one is not known yet)
+};
+
+// which ones of the window are coded: follow nxt from `cur` by pointer doubling.  Writes and reads flag[0 .. 64] (and its
+// two spare bytes), in rounds that a fence separates: a lane marks where it jumps to, then reads its own mark; nobody else
+// uses flag (parameter, see above).  (Measured against the plain walk on the scalar unit — one v_readlane + 5 scalar instructions per coded one,
+// half the vector instructions: 14.8 against 13.0 ms per step; rebuilt leaner in round 4, one v_readlane + ~6 scalar
+// instructions and no LDS: LZ4 stage 14.0 against 12.1 ms.  A wave's dependent chain is what counts, not its instruction total.)
+__device__ __forceinline__ BpSel bp_select_coded(uint8_t *flag, bool valid, uint32_t nxt, int jw, int cur, uint32_t lane)
+{
+    bool sel = false;
+    if (cur < jw + 64) {   // (wave-uniform) otherwise the whole window lies inside an earlier match
+        const uint32_t e0 = (uint32_t)(cur - jw);
+        uint32_t jump = valid ? (nxt - (uint32_t)jw < 64u ? nxt - (uint32_t)jw : 64u) : 64u;   // nxt > j: always forward
+        const uint32_t p0 = jump;
+        flag[lane] = lane == e0 ? 1u : 0u;
+        flag[lane == 0u ? 64u : 69u] = 0u;
+        BP_FENCE();
+        bool reach = lane == e0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            flag[reach ? jump : 68u] = 1u;   // (no exec-mask region: a scalar instruction costs this kernel four times a vector one)
+            BP_FENCE();
+            reach = flag[lane] != 0u;
+            const uint32_t j2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((jump & 63u) << 2), (int)jump);
+            jump = jump < 64u ? j2 : 64u;
+        }
+        sel = reach && valid;
+        const unsigned long long ex = __builtin_amdgcn_ballot_w64(sel && p0 == 64u);
+        // the coded one whose successor lies outside the window hands over to the next window
+        if (ex != 0ull) cur = (int)__builtin_amdgcn_readlane((int)nxt, (int)(__ffsll((long long)ex) - 1));
+    }
+    return BpSel{sel, cur};
+}
+
+struct BpQueued {
+    BpOut out;     // where the stream stands
+    uint32_t qn;   // queued coded ones
+};
+
+// the coded ones that emit something — a match M (if hv) and / or a tail run T over the zeros up to the next coded one — are
+// queued; layout and emission run on 64 of them at a time (bp_emit_batch), every lane busy, where the first version laid out
+// and emitted per window with the ~30 % of its lanes that were coded ones.  Reads P (bp_list_ones) and, for a clamped match,
+// bm (both parameters, see above); writes queue, which bp_emit_batch reads behind a fence, and moves what a batch leaves to the queue's front (read, fence,
+// write); bp_emit_batch fills stage.  Returns the stream's state and the queue's length.
+template <bool EXC, typename LDS>
+__device__ __forceinline__ BpQueued bp_queue_and_drain(LDS &S, const uint32_t *bm, const uint16_t *P, uint8_t *out, int q, uint32_t q1, bool hv, uint32_t nb,
+                                                       uint32_t c1, uint32_t z_last, bool clamped, uint32_t E, uint32_t nxt, bool sel, int jw, uint32_t m,
+                                                       uint32_t prev_end, uint32_t gop, uint32_t sop, uint32_t qn, uint32_t lane)
+{
+    const bool onM = sel && hv;
+    // the run behind E starts one later when byte E - 1 is a one (an offset-1 run copies its predecessor): always for a one
+    // that codes itself alone (and the virtual one in front of the stream), for a match when it ends with its last one
+    uint32_t rs = E + ((!hv || z_last == 0u) ? 1u : 0u);
+    if (__builtin_amdgcn_ballot_w64(clamped) != 0ull)   // (wave-uniform, rare: a match cut at the match limit — ask the bit map)
+        rs = clamped ? E + ((bp_bits(bm, E - 1u) & 1u) ? 1u : 0u) : rs;
+    uint32_t re = (uint32_t)P[(nxt < m ? nxt : m) + 1u] - 1u;   // position of the next one (n behind the last)
+    re = re < BP_MATCHLIMIT ? re : BP_MATCHLIMIT;
+    const bool onT = sel && (int)re - (int)rs >= BP_TMIN && rs <= BP_MFLIMIT;   // (long enough; emitted or not: bp_emit_batch)
+    const bool want = onM || onT;
+    const unsigned long long wm = __builtin_amdgcn_ballot_w64(want);
+    const uint32_t nw = (uint32_t)__builtin_popcountll(wm);
+    const bool last = jw + 64 >= (int)m;
+    // one call site for the batch code: first make room if this window's coded ones would not fit (rare), then queue
+    // them, then drain whole batches (everything at the end)
+    for (int phase = 0; phase < 2; ++phase) {
+        if (phase == 1) {
+            const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
+            S.queue[want ? slot : (uint32_t)BP_QCAP] = bp_entry(E, (uint32_t)(q - (int)nb), onM, onT, rs, re, q1 - c1);
+            qn += nw;
+            BP_MARK("queued");
+        }
+        // a batch leaves the queue when the entry behind its last one is there too (the run rule looks at it) — or when
+        // the stream ends
+        while (phase == 0 ? qn + nw > BP_QCAP : (qn >= 65u || (last && qn != 0u))) {   // (wave-uniform)
+            const uint32_t keep = phase == 1 && last ? 0u : 1u;
+            const uint32_t nb_ = qn - keep < 64u ? qn - keep : 64u;
+            BP_FENCE();
+            const BpOut r = bp_emit_batch<EXC>(S, bm, out, nb_, qn, BpOut{prev_end, gop, sop}, lane);
+            prev_end = r.prev_end, gop = r.gop, sop = r.sop;
+            BP_FENCE();
+            const bool mvp = lane + nb_ < qn;
+            const uint2 mv = S.queue[mvp ? nb_ + lane : (uint32_t)BP_QCAP];
+            BP_FENCE();
+            S.queue[mvp ? lane : (uint32_t)BP_QCAP] = mv;
+            qn -= nb_;
+        }
+    }
+    return BpQueued{BpOut{prev_end, gop, sop}, qn};
+}
+
+// the last literals: everything behind the last sequence's end, as a sequence without a match.  Reads bm (parameter, see
+// above) and, EXC, xm (the kernel); writes stage behind what bp_emit_batch staged (or, a run larger than the staging area, the stream's slot).
+// Returns where the stream stands.
+template <bool EXC, typename LDS>
+__device__ __forceinline__ BpOut bp_last_literals(LDS &S, const uint32_t *bm, uint8_t *out, uint32_t prev_end, uint32_t gop, uint32_t sop, uint32_t lane)
+{
+    const uint32_t ll = BP_N - prev_end, llx = bp_len_ext(ll);
+    BP_FENCE();
+    if (sop + 1u + llx + ll > BpCfg<EXC>::STAGE) {
+        bp_flush(S.stage, out + gop, sop, lane);
+        gop += sop;
+        sop = 0;
+    }
+    const bool direct = 1u + llx + ll > BpCfg<EXC>::STAGE;
+    auto tail = [&](auto dstp) {
+        if (lane == 0) {
+            dstp[0] = (uint8_t)((ll < 15u ? ll : 15u) << 4);
+            uint32_t r = ll - 15u;
+            for (uint32_t k = 0; k < llx; ++k) {
+                dstp[1u + k] = (uint8_t)(k + 1u == llx ? r : 255u);
+                r -= 255u;
+            }
+        }
+        for (uint32_t k = lane; k < ll; k += 64u)
+            dstp[1u + llx + k] = (uint8_t)bp_lit<EXC>(bp_bits(bm, prev_end + k), EXC ? bp_bits(S.xm, prev_end + k) : 0u, 0u);
+    };
+    if (direct) {
+        tail(out + gop);
+        gop += 1u + llx + ll;
+    } else {
+        tail(S.stage + sop);
+        sop += 1u + llx + ll;
+    }
+    return BpOut{prev_end, gop, sop};
+}
+
+// the end of the stream: what is staged leaves for the stream's slot — or, incompressible, the plane itself does: Blosc
+// stores the (shuffled) stream verbatim.  Reads stage (bp_emit_batch, bp_last_literals) or bm (parameter, see above) and xm.  Returns the stream's size.
+template <bool EXC, typename LDS>
+__device__ __forceinline__ uint32_t bp_finish_stream(LDS &S, const uint32_t *bm, uint8_t *out, BpOut st, uint32_t lane)
+{
+    uint32_t op = st.gop + st.sop;
+    if (op >= BP_N) {
+        for (uint32_t k = lane; k < BP_N; k += 64u) out[k] = (uint8_t)bp_lit<EXC>(bp_bits(bm, k), EXC ? bp_bits(S.xm, k) : 0u, 0u);
+        op = BP_N;
+    } else {
+        BP_FENCE();
+        bp_flush(S.stage, out + st.gop, st.sop, lane);
+    }
+    return op;
+}
+
 // One plane, from its bit map(s) in registers to its stream (or its mark): everything behind the loads.  A plane left to the
 // byte-wise kernel gets csize = MARK, and flags[0] = tag says "this call left a mark" to that kernel's scan.
+// The BP_SKIP exits (development, timing only) cut the coder short between two phases; `sink` keeps what was computed alive.
 template <int DEPTH, bool EXC, bool LAZY, typename LDS>
 __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi, uint32_t xlo, uint32_t xhi, bool nonbinary, uint32_t bid,
                                               uint32_t wave, uint32_t lane, uint8_t *__restrict__ scratch, uint64_t slot_bytes,
                                               uint32_t *__restrict__ csize, uint32_t *__restrict__ flags, uint32_t tag)
 {
-    constexpr bool CHAIN = DEPTH > 1;
     uint32_t sink = 0;
-    // ---- phase B: wave w codes plane w
-    // The lanes of the wave exchange data through S with no barrier in between: the LDS executes a wave's instructions in
-    // order.  What the COMPILER must not do is move a lane's read in front of another lane's earlier write; every such
-    // hand-over below is an access whose address it cannot tell apart from the lane's own writes, and BP_FENCE marks
-    // the phase boundaries for good measure.  (volatile pointers would also do — and turn every access into a
-    // serialised flat load with its own wait, which made this kernel 2x slower than it had to be.)
+    // (the shared arrays' addresses, taken here and in this order: see "the plane coder" above)
     uint32_t *bm = S.bm;
     uint16_t *P = S.P;
     uint16_t *wpre = S.wpre;
@@ -347,8 +787,8 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
     uint8_t *out = scratch + sidx * slot_bytes;
 
     const uint32_t cnt = (uint32_t)__popc(wlo) + (uint32_t)__popc(whi);
-    const uint32_t incl = bp_scan_sum(cnt, lane);
-    const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    uint32_t m;   // ones in the plane
+    const uint32_t incl = wave_scan_sum_dpp(cnt, lane, &m);
     if (nonbinary || m > BpCfg<EXC>::MAXONES) {
         // (the flag: read first — the line sits in the L2 and after the first few marking waves of an XCD it holds the tag)
         if (lane == 0 && flags && flags[0] != tag) flags[0] = tag;
@@ -356,367 +796,55 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
         return;
     }
     BP_MARK("scan_done");
-    wpre[lane] = (uint16_t)(incl - cnt);
-    BP_FENCE();
-    {   // the list of ones
-        // (the two halves of the lane's 64 positions one after the other: each round is a count-trailing-zeros, a clear
-        // and a store, and there are as many rounds as the fullest 32-position word has ones — twice ~6 — where one loop
-        // over the 64-bit word ran ~11 rounds of twice the work)
-        // (no `if (lo != 0)` around the body: a lane that has run out stores to P's spare entry — an exec-mask region costs
-        // two scalar instructions and a branch per round, and scalar issue is this kernel's tightest port)
-        uint32_t lo = wlo, hi = whi, at = incl - cnt + 1u;
-        P[lane == 0u ? 0u : BpCfg<EXC>::PTRASH] = 0;
-        uint32_t base = 64u * lane + 1u;
-        while (__builtin_amdgcn_ballot_w64(lo != 0u) != 0ull) {
-            const bool on = lo != 0u;
-            const uint32_t bpos = (uint32_t)__builtin_ctz(lo | 0x80000000u);
-            if (EXC && on && ((xlo >> bpos) & 1u)) atomicOr(&S.cls[at >> 5], 1u << (at & 31u));   // (LDS: ds_or_b32)
-            P[on ? at : BpCfg<EXC>::PTRASH] = (uint16_t)(base + bpos);
-            at += on ? 1u : 0u;
-            lo &= lo - 1u;
-        }
-        base += 32u;
-        while (__builtin_amdgcn_ballot_w64(hi != 0u) != 0ull) {
-            const bool on = hi != 0u;
-            const uint32_t bpos = (uint32_t)__builtin_ctz(hi | 0x80000000u);
-            if (EXC && on && ((xhi >> bpos) & 1u)) atomicOr(&S.cls[at >> 5], 1u << (at & 31u));
-            P[on ? at : BpCfg<EXC>::PTRASH] = (uint16_t)(base + bpos);
-            at += on ? 1u : 0u;
-            hi &= hi - 1u;
-        }
-        P[lane < 4u ? m + 1u + lane : BpCfg<EXC>::PTRASH] = (uint16_t)(BP_N + 1);
-    }
-    BP_FENCE();
-    if (DEPTH > 0) {   // gap bytes of all ones (a candidate is compared on them, 4 at a time)
-        uint8_t *gb = reinterpret_cast<uint8_t *>(S.gbw);
-        for (uint32_t i = lane; i < m + 8u; i += 64u) {
-            const uint32_t i1 = i + 1u < BpCfg<EXC>::PTRASH ? i + 1u : BpCfg<EXC>::PTRASH;   // (i < m + 8 <= 644: the loads stay inside P)
-            uint32_t g = (uint32_t)P[i1] - (uint32_t)P[i1 - 1u] - 1u;
-            g = g < 255u ? g : 255u;
-            gb[i] = (uint8_t)(i < m ? g : 255u);
-        }
-        BP_FENCE();
-    }
-#pragma unroll
-    for (int k = 0; k < (1 << BP_HLOG) / 64; ++k) S.tab[64 * k + lane] = 0u;
-
+    bp_list_ones<EXC>(S, P, wpre, wlo, whi, xlo, xhi, incl, cnt, m, lane);
+    if (DEPTH > 0) bp_gap_bytes<EXC>(S, P, m, lane);
+    bp_clear_table(S, lane);
     BP_MARK("plist_done");
     if (BP_SKIP >= 4) {
         if (lane == 0) csize[sidx] = P[m] & 1u;
         return;
     }
-    uint32_t gop = 0, sop = 0, prev_end = 0, qn = 0;   // bytes written to global / staged; end of the last sequence; queued coded ones
+    BpQueued st{BpOut{0u, 0u, 0u}, 0u};
     int cur = -1;   // next one to be coded (the virtual one in front of the stream first)
     for (int jw = -1; jw < (int)m; jw += 64) {
         BP_MARK("win_begin");
-#ifdef BP_PROBE_SALU   // development: extra independent scalar / vector instructions per window — which issue port is the tight one?
-#pragma unroll
-        for (int pr = 0; pr < BP_PROBE_SALU; ++pr) asm volatile("s_mov_b32 s90, 0" ::: "s90");
-#endif
-#ifdef BP_PROBE_VALU
-        {
-            uint32_t pv;
-#pragma unroll
-            for (int pr = 0; pr < BP_PROBE_VALU; ++pr) asm volatile("v_mov_b32 %0, 0" : "=v"(pv));
-        }
-#endif
-        const int j = jw + (int)lane;
-        const bool valid = j < (int)m;
-        const uint32_t jj = valid ? (uint32_t)(j + 1) : 0u;          // index into P of this one
-        const uint32_t q1 = P[jj], qn1 = P[jj + 1u];
-        const uint32_t qp1 = jj ? P[jj - 1u] : 0u;
-        const int q = (int)q1 - 1;
-        // ---- candidate table: keyed on the gap behind the one; exact recency through the LDS's lane order
-        const bool can = DEPTH > 0 && valid && j >= 0 && q + 12 <= BP_N;
-        uint32_t jc1 = 0;
-        // EXC: classes of this one (bit 0) and of the four ones behind it
-        const uint32_t c5a = EXC ? (bp_bits(S.cls, jj) & 31u) : 0u;
-        if (can) {
-            const uint32_t g1 = qn1 - q1;
-            const uint32_t idx = (g1 < BP_GAPCLIP ? g1 : BP_GAPCLIP) ^ ((EXC && (c5a & 1u)) ? 63u : 0u);
-            jc1 = atomicExch(&S.tab[idx], (uint32_t)(j + 1));
-            if (CHAIN) S.chain[jj] = (uint16_t)jc1;   // what this one replaced: the next candidate down the chain
-        }
-        BP_FENCE();
+        bp_probe_salu();
+        bp_probe_valu();
+        const BpOne o = bp_lane_one<DEPTH, EXC>(S, P, jw, m, lane);
+        const uint32_t jc1 = bp_table_insert<(DEPTH > 1), EXC>(S, o);
         BP_MARK("hash_done");
-        // ---- pick: the candidate with the longest forward agreement, judged on the gap BYTES — up to BP_PICK equal
-        //      gaps, then 1 + the smaller of the next pair.  All a candidate costs is one unaligned 4-byte fetch from
-        //      the gap bytes, an xor and a count-trailing-zeros; ties go to the nearer one.
-        const uint32_t gq = q1 - qp1 - 1u;
-        uint32_t len = 0, nb = 0, c1 = 0;
-        bool hv = false;
-        uint32_t a_last = jj;   // hv: P-index of the last one the match covers
-        uint32_t z_last = 0;    // hv: zeros the match takes behind that one (0: it ends with the one)
-        bool clamped = false;   // hv: the match was cut at the stream's match limit
+        BpMatch mt{false, 0u, 0u, 0u, o.jj, 0u, false};
         if (DEPTH > 0) {
-            const uint32_t a4 = bp_gap4(S.gbw, jj);
-            const uint8_t *gbb = reinterpret_cast<const uint8_t *>(S.gbw);
-            const uint32_t fa = jj ? (uint32_t)gbb[jj - 1u] : 0u;    // zeros in front of this one (clipped to 255)
-            const uint32_t na4 = ~a4;
-            const uint32_t stop4 = ((na4 - 0x01010101u) & ~na4 & 0x80808080u) | 0xFF000000u;   // a 255 agrees with nothing; 3 gaps at most
-            int best = -1;
-            uint32_t bjq = 0, bk = 0;
-#pragma unroll 1
-            for (int dpt = 0; dpt < DEPTH; ++dpt) {
-                const bool have = can && jc1 != 0u;
-                if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
-                const uint32_t jq = have ? jc1 : 1u;
-                const uint32_t b4 = bp_gap4(S.gbw, jq);
-                const uint32_t fb = (uint32_t)gbb[jq - 1u];
-                uint32_t nextc = 0;
-                if (CHAIN) nextc = S.chain[jq];
-                const uint32_t x = (a4 ^ b4) | stop4;
-                uint32_t k = (uint32_t)__builtin_ctz(x) >> 3;                           // agreeing gaps: 0..3
-                bool same = true;
-                if (EXC) {   // ... of which only those count whose next ones are of the same class; the first byte must agree at all
-                    const uint32_t xc = c5a ^ (bp_bits(S.cls, jq) & 31u);
-                    same = (xc & 1u) == 0u;
-                    const uint32_t tv = (uint32_t)__builtin_ctz((xc >> 1) | 8u);
-                    k = k < tv ? k : tv;
-                }
-                const uint32_t below = (1u << (8u * k)) - 1u;
-                const uint32_t sumg = __builtin_amdgcn_sad_u8(a4 & below, 0u, k + 1u);  // their zeros + their ones + this one
-                const uint32_t za = (a4 >> (8u * k)) & 0xFFu, zb = (b4 >> (8u * k)) & 0xFFu;
-                uint32_t fz = fa < fb ? fa : fb;                                        // the zeros in front a match would take along
-                fz = fz < BP_BACK ? fz : BP_BACK;
-                const int score = (int)(sumg + (za < zb ? za : zb) + fz);
-                const bool up = have & same & (score > best);   // (selects, not a branch)
-                best = up ? score : best;
-                bjq = up ? jq : bjq;
-                bk = up ? k : bk;
-                if (!CHAIN) break;
-                jc1 = have ? nextc : 0u;
-            }
-            // ---- the chosen one, exactly (positions from P): agreement may continue past the third gap (periodic
-            //      planes; rare), then the costs decide between this match and literals
-            const bool got = best >= 0;
-            if (__builtin_amdgcn_ballot_w64(got) != 0ull) {
-                const uint32_t jq = got ? bjq : 1u;
-                const uint32_t cc1 = P[jq], cp1 = P[jq - 1u];
-                uint32_t a = jj + bk, b = jq + bk;          // P-indices of the ones the first open comparison starts at
-                uint32_t pa = P[a], pb = P[b];
-                uint32_t clen = pa - q1, costR = 0, tailz = 0, zl = 0;
-#pragma unroll
-                for (uint32_t s = 0; s < BP_PICK; ++s) {
-                    const uint32_t g = (a4 >> (8u * s)) & 0xFFu;
-                    costR += s < bk ? 1u + (g >= BP_TMIN + 1u ? 4u : g) : 0u;
-                }
-                bool act = got;
-                for (uint32_t s = bk;; ++s) {   // (per lane: s starts at the lane's own bk; the trip count is what the wave needs)
-                    if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
-                    // (branch-free body: lanes that are done keep their values through selects; a + 1, b + 1 <= m + 4 stay inside P)
-                    const uint32_t na = P[a + 1u], nbn = P[b + 1u];
-                    const uint32_t ga = na - pa - 1u, gb = nbn - pb - 1u;
-                    const bool cdiff = EXC && (((bp_bits(S.cls, a + 1u) ^ bp_bits(S.cls, b + 1u)) & 1u) != 0u);
-                    const bool stop = (s < BP_PICK) | (ga != gb) | (ga >= 255u) | (a >= m) | (s >= BP_STEPS) | cdiff;
-                    const uint32_t z = ga < gb ? ga : gb;
-                    costR += act ? 1u + (ga >= BP_TMIN + 1u ? 4u : ga) : 0u;
-                    clen += act ? 1u + (stop ? z : ga) : 0u;
-                    tailz = (act & stop) ? ga - z : tailz;
-                    zl = (act & stop) ? z : zl;
-                    act = act & !stop;
-                    a += act ? 1u : 0u;
-                    b += act ? 1u : 0u;
-                    pa = act ? na : pa;
-                    pb = act ? nbn : pb;
-                }
-                {
-                    const uint32_t gc = cc1 - cp1 - 1u;
-                    uint32_t cnb = gq < gc ? gq : gc;
-                    cnb = cnb < BP_BACK ? cnb : BP_BACK;
-                    const uint32_t costH = 3u + (clen + cnb >= 19u ? 1u : 0u) - cnb + (tailz >= BP_TMIN ? 3u : tailz);
-                    uint32_t end = (uint32_t)q + clen;
-                    clamped = end > BP_MATCHLIMIT;
-                    end = end < BP_MATCHLIMIT ? end : BP_MATCHLIMIT;
-                    // signed compares: costH may go below zero when many zeros are pulled in
-                    const int gain = (int)costR - (int)costH;
-                    hv = got & (gain > 0) & ((int)end - q >= 4) & ((int)end - (q - (int)cnb) >= BP_MINM) & (q <= BP_MFLIMIT);   // (& not &&: no nest of exec-mask regions)
-                    len = hv ? end - (uint32_t)q : 0u;
-                    nb = hv ? cnb : 0u;
-                    c1 = hv ? cc1 : 0u;
-                    a_last = a;
-                    z_last = zl;
-                    clamped = clamped & hv;
-                }
-            }
+            const BpPick pk = bp_pick<DEPTH, EXC>(S, o.can, o.jj, o.c5a, jc1);
+            mt = bp_extend_and_price<EXC>(S, P, pk.best >= 0, pk.bjq, pk.bk, pk.a4, o.jj, o.q, o.q1, o.qp1, m);
         }
         BP_MARK("cand_done");
-        if (LAZY) {
-            // ---- one-step lazy rule (the file-writing paths' effort level; tools/sim/gapenc_ref.c states it): a one gives up
-            //      its match when the NEXT one lies inside that match and has a match of its own that ends further by at least
-            //      BP_LAZY_MIN + what giving up costs (the zeros this one's match was pulled back over, the zeros between this
-            //      one and the start of the next one's match).  The next one is the neighbouring lane (the window's last lane
-            //      keeps its match); in a run of lanes that all would give up, every other one does, counted from the far end.
-            const uint32_t E0 = hv ? (uint32_t)q + len : (uint32_t)(q + 1);
-            const uint32_t hvN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(hv ? 1u : 0u), 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-            const uint32_t EN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)E0, 0x130, 0xf, 0xf, false);
-            const uint32_t nbN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nb, 0x130, 0xf, 0xf, false);
-            const int msN = (int)qn1 - 1 - (int)nbN;                      // where the next one's match starts
-            const int between = msN - (int)q1 > 0 ? msN - (int)q1 : 0;     // zeros between this one and that start
-            const bool Ln = hv & (hvN != 0u) & (lane < 63u) & (j + 1 < (int)m) & (qn1 <= E0) & ((int)EN - (int)E0 >= (int)(BP_LAZY_MIN + nb) + between);
-            const unsigned long long lm = __builtin_amdgcn_ballot_w64(Ln);
-            const unsigned long long rest = ~(lm >> lane);                 // first zero bit = end of this lane's run
-            const uint32_t tlo = (uint32_t)__builtin_ctz((uint32_t)rest | 0x80000000u), thi = (uint32_t)__builtin_ctz((uint32_t)(rest >> 32) | 0x80000000u);
-            const uint32_t t = (uint32_t)rest != 0u ? tlo : 32u + thi;     // (lm >> lane has zeros from bit 64 - lane on: the run ends inside)
-            const bool give = Ln && (t & 1u);
-            hv = hv && !give;
-            len = give ? 0u : len;
-            nb = give ? 0u : nb;
-            c1 = give ? 0u : c1;
-            a_last = give ? jj : a_last;
-            z_last = give ? 0u : z_last;
-            clamped = clamped && !give;
-        }
-        const uint32_t E = hv ? (uint32_t)q + len : (uint32_t)(q + 1);   // end of what this one codes (0 for the virtual one)
-        // first one at or behind E = the number of ones in front of position E.  A one that codes itself alone (E = q + 1) has
-        // itself and its predecessors in front: its own P-index.  A match ends in the zeros behind the last one it covers (or
-        // exactly at the next one): that one's P-index.  Only a match that was cut at the stream's match limit (a handful of
-        // ones at the very end of a plane) needs the count from the bit map.
-        uint32_t nxt = hv ? a_last : jj;
-        if (__builtin_amdgcn_ballot_w64(clamped) != 0ull) {   // (wave-uniform, rare)
-            const uint32_t w = E >> 6, bb = E & 63u, wc = w < 63u ? w : 63u;
-            const uint32_t lo = bm[2u * wc], hi = bm[2u * wc + 1u];
-            const uint32_t mlo = bb >= 32u ? 0xFFFFFFFFu : ((1u << bb) - 1u);
-            const uint32_t mhi = bb > 32u ? ((1u << (bb - 32u)) - 1u) : 0u;
-            const uint32_t in_map = (uint32_t)wpre[wc] + (uint32_t)__popc(lo & mlo) + (uint32_t)__popc(hi & mhi);
-            nxt = clamped ? (w >= 64u ? m : in_map) : nxt;
-        }
+        if (LAZY) mt = bp_lazy_rule(mt.hv, mt.len, mt.nb, mt.c1, mt.a_last, mt.z_last, mt.clamped, o.j, o.q, o.jj, o.q1, o.qn1, m, lane);
+        const BpNext nx = bp_next_one(bm, wpre, mt.hv, mt.len, mt.a_last, mt.clamped, o.q, o.jj, m);
         BP_MARK("nxt_done");
-        // ---- which ones of the window are coded: follow nxt from `cur` by pointer doubling.  (Measured against the plain
-        //      walk on the scalar unit — one v_readlane + 5 scalar instructions per coded one, half the vector instructions:
-        //      14.8 against 13.0 ms per step; rebuilt leaner in round 4, one v_readlane + ~6 scalar instructions and no LDS:
-        //      LZ4 stage 14.0 against 12.1 ms.  A wave's dependent chain is what counts, not its instruction total.)
-        bool sel = false;
         if (BP_SKIP >= 3) {
-            sink += nxt + E;
+            sink += nx.nxt + nx.E;
             continue;
         }
-        if (cur < jw + 64) {   // (wave-uniform) otherwise the whole window lies inside an earlier match
-            const uint32_t e0 = (uint32_t)(cur - jw);
-            uint32_t jump = valid ? (nxt - (uint32_t)jw < 64u ? nxt - (uint32_t)jw : 64u) : 64u;   // nxt > j: always forward
-            const uint32_t p0 = jump;
-            flag[lane] = lane == e0 ? 1u : 0u;
-            flag[lane == 0u ? 64u : 69u] = 0u;
-            BP_FENCE();
-            bool reach = lane == e0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-                flag[reach ? jump : 68u] = 1u;   // (no exec-mask region: a scalar instruction costs this kernel four times a vector one)
-                BP_FENCE();
-                reach = flag[lane] != 0u;
-                const uint32_t j2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((jump & 63u) << 2), (int)jump);
-                jump = jump < 64u ? j2 : 64u;
-            }
-            sel = reach && valid;
-            const unsigned long long ex = __builtin_amdgcn_ballot_w64(sel && p0 == 64u);
-            // the coded one whose successor lies outside the window hands over to the next window
-            if (ex != 0ull) cur = (int)__builtin_amdgcn_readlane((int)nxt, (int)(__ffsll((long long)ex) - 1));
-        }
+        const BpSel sl = bp_select_coded(flag, o.valid, nx.nxt, jw, cur, lane);
+        cur = sl.cur;
         BP_MARK("sel_done");
         if (BP_SKIP >= 2) {
-            sink += sel ? nxt : 0u;
+            sink += sl.sel ? nx.nxt : 0u;
             continue;
         }
-        // ---- the coded ones that emit something — a match M (if hv) and / or a tail run T over the zeros up to the next
-        //      coded one — are queued; layout and emission run on 64 of them at a time (bp_emit_batch), every lane busy,
-        //      where the first version laid out and emitted per window with the ~30 % of its lanes that were coded ones
-        const bool onM = sel && hv;
-        // the run behind E starts one later when byte E - 1 is a one (an offset-1 run copies its predecessor): always for a one
-        // that codes itself alone (and the virtual one in front of the stream), for a match when it ends with its last one
-        uint32_t rs = E + ((!hv || z_last == 0u) ? 1u : 0u);
-        if (__builtin_amdgcn_ballot_w64(clamped) != 0ull)   // (wave-uniform, rare: a match cut at the match limit — ask the bit map)
-            rs = clamped ? E + ((bp_bits(bm, E - 1u) & 1u) ? 1u : 0u) : rs;
-        uint32_t re = (uint32_t)P[(nxt < m ? nxt : m) + 1u] - 1u;   // position of the next one (n behind the last)
-        re = re < BP_MATCHLIMIT ? re : BP_MATCHLIMIT;
-        const bool onT = sel && (int)re - (int)rs >= BP_TMIN && rs <= BP_MFLIMIT;   // (long enough; emitted or not: bp_emit_batch)
-        const bool want = onM || onT;
-        const unsigned long long wm = __builtin_amdgcn_ballot_w64(want);
-        const uint32_t nw = (uint32_t)__builtin_popcountll(wm);
-        const bool last = jw + 64 >= (int)m;
-        // one call site for the batch code: first make room if this window's coded ones would not fit (rare), then queue
-        // them, then drain whole batches (everything at the end)
-        for (int phase = 0; phase < 2; ++phase) {
-            if (phase == 1) {
-                const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
-                S.queue[want ? slot : (uint32_t)BP_QCAP] = bp_entry(E, (uint32_t)(q - (int)nb), onM, onT, rs, re, q1 - c1);
-                qn += nw;
-                BP_MARK("queued");
-            }
-            // a batch leaves the queue when the entry behind its last one is there too (the run rule looks at it) — or when
-            // the stream ends
-            while (phase == 0 ? qn + nw > BP_QCAP : (qn >= 65u || (last && qn != 0u))) {   // (wave-uniform)
-                const uint32_t keep = phase == 1 && last ? 0u : 1u;
-                const uint32_t nb_ = qn - keep < 64u ? qn - keep : 64u;
-                BP_FENCE();
-                const BpOut r = bp_emit_batch<EXC>(S, bm, out, nb_, qn, BpOut{prev_end, gop, sop}, lane);
-                prev_end = r.prev_end, gop = r.gop, sop = r.sop;
-                BP_FENCE();
-                const bool mvp = lane + nb_ < qn;
-                const uint2 mv = S.queue[mvp ? nb_ + lane : (uint32_t)BP_QCAP];
-                BP_FENCE();
-                S.queue[mvp ? lane : (uint32_t)BP_QCAP] = mv;
-                qn -= nb_;
-            }
-        }
+        st = bp_queue_and_drain<EXC>(S, bm, P, out, o.q, o.q1, mt.hv, mt.nb, mt.c1, mt.z_last, mt.clamped, nx.E, nx.nxt, sl.sel, jw, m, st.out.prev_end,
+                                     st.out.gop, st.out.sop, st.qn, lane);
         BP_MARK("emit_done");
     }
     BP_MARK("loop_done");
     if (BP_SKIP >= 1) {
-        if (lane == 0) csize[sidx] = (prev_end + sink) & 0xFFFu;
+        if (lane == 0) csize[sidx] = (st.out.prev_end + sink) & 0xFFFu;
         return;
     }
-    // ---- last literals
-    {
-        const uint32_t ll = BP_N - prev_end, llx = bp_len_ext(ll);
-        BP_FENCE();
-        if (sop + 1u + llx + ll > BpCfg<EXC>::STAGE) {
-            bp_flush(S.stage, out + gop, sop, lane);
-            gop += sop;
-            sop = 0;
-        }
-        const bool direct = 1u + llx + ll > BpCfg<EXC>::STAGE;
-        auto tail = [&](auto dstp) {
-            if (lane == 0) {
-                dstp[0] = (uint8_t)((ll < 15u ? ll : 15u) << 4);
-                uint32_t r = ll - 15u;
-                for (uint32_t k = 0; k < llx; ++k) {
-                    dstp[1u + k] = (uint8_t)(k + 1u == llx ? r : 255u);
-                    r -= 255u;
-                }
-            }
-            for (uint32_t k = lane; k < ll; k += 64u)
-                dstp[1u + llx + k] = (uint8_t)bp_lit<EXC>(bp_bits(bm, prev_end + k), EXC ? bp_bits(S.xm, prev_end + k) : 0u, 0u);
-        };
-        if (direct) {
-            tail(out + gop);
-            gop += 1u + llx + ll;
-        } else {
-            tail(S.stage + sop);
-            sop += 1u + llx + ll;
-        }
-    }
-    uint32_t op = gop + sop;
-    if (op >= BP_N) {   // incompressible: Blosc stores the (shuffled) stream verbatim
-        for (uint32_t k = lane; k < BP_N; k += 64u) out[k] = (uint8_t)bp_lit<EXC>(bp_bits(bm, k), EXC ? bp_bits(S.xm, k) : 0u, 0u);
-        op = BP_N;
-    } else {
-        BP_FENCE();
-        bp_flush(S.stage, out + gop, sop, lane);
-    }
+    uint32_t op = bp_finish_stream<EXC>(S, bm, out, bp_last_literals<EXC>(S, bm, out, st.out.prev_end, st.out.gop, st.out.sop, lane), lane);
     if (BP_SKIP) op = (op & 0xFFFu) + (sink & 1u);
-#ifdef BP_PROBE_HANDOFF
-    // development (round 4): the least a wave would pay to hand its stream to another workgroup INSIDE this launch (framing
-    // fused by a look-back, or "the chunk's last stream frames the chunk"): its stores drained, then one returning
-    // agent-scope atomic on a word the 256 streams of its chunk share (a spare word behind the chunk's first scratch slot).
-    // LZ4 stage with it: tools/dev/lz4_handoff.sh, DESIGN.md 3.3.
-    {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        uint32_t old = 0;
-        if (lane == 0) old = atomicAdd(reinterpret_cast<uint32_t *>(scratch + (sidx & ~255ull) * slot_bytes + slot_bytes - 8u), 1u);
-        old = (uint32_t)__builtin_amdgcn_readfirstlane((int)old);
-        op += old == 0xFFFFFFF0u ? 1u : 0u;   // (keeps the returned value alive; never true)
-    }
-#endif
+    op = bp_probe_handoff(scratch, sidx, slot_bytes, op, lane);
     if (lane == 0) csize[sidx] = op;
 }
 
@@ -733,9 +861,10 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes(const uint8_t *
     __shared__ uint32_t nonbin[2][2];
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
     const uint32_t bid = blockIdx.x;
-    // (a one-trip loop: it keeps the compiler's schedule of this kernel as it was when the body sat in the loop of the removed
-    // exception-aware form; without it phase A is scheduled differently — 66 instead of 64 VGPRs at most depths, 7 instead
-    // of 8 waves per SIMD at depth 0)
+    // (a one-trip loop, kept for what it buys in the compiler's schedule.  Without it every instantiation grows — by 1 to 3
+    // instructions without the lazy rule at depth >= 2, by 9 to 14 elsewhere — and depths 0 and 1 and the two lazy forms take
+    // 66 instead of 64 VGPRs; at depths 0 and 1, where the LDS would allow nine workgroups per SIMD pair, that is 7 instead of
+    // 8 waves per SIMD.  Checked per instantiation by tests/test_isa_counts.py.)
     for (int once = 0; once < 1; ++once) {
     const uint8_t *blk = src + (uint64_t)bid * 8192u;
 
@@ -823,6 +952,8 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8
     planes_block(pg, bid, &col, &row, &bi);
     const u32x2 *pl = reinterpret_cast<const u32x2 *>(src + planes_piece(pg, col, bi * 16u + (lane >> 2), wave, row)) + (lane & 3u);
     const u32x2 one = *pl, exc = *(pl + (uint64_t)pg.S_pad * 8ull);
+    // (both branches store the bit map of the nonzero bytes, at the same place: stored once in front of the branch, every
+    // instantiation but depth 0 takes 72 instead of 70 VGPRs)
     if (__builtin_amdgcn_ballot_w64((exc.x | exc.y) != 0u) == 0ull) {   // no missing call in this plane: the plain coder
         BpLds<CHAIN, false> &S = lds[wave].p;
         S.bm[2u * lane] = one.x;
@@ -844,6 +975,19 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8
     }
 }
 
+// one launch of the coder with D candidates per one and, LZ, the lazy rule: the plane-input kernel (its grid rounded up to
+// whole groups of 64, for its XCD-aware order) or the int8-input one
+template <int D, bool LZ>
+static void bp_launch(bool planes, const uint8_t *d_src, PlanesGeom pg, uint32_t n_blocks, uint8_t *d_scratch, uint64_t slot_bytes, uint32_t *d_csize,
+                      uint32_t *d_flags, uint32_t tag, hipStream_t st)
+{
+    if (planes)
+        hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((n_blocks + 63u) / 64u * 64u), dim3(128), 0, st, d_src, pg, n_blocks, d_scratch, slot_bytes,
+                           d_csize, d_flags, tag);
+    else
+        hipLaunchKernelGGL((k_lz4_bitplanes<D, LZ>), dim3(n_blocks), dim3(128), 0, st, d_src, pg, n_blocks, d_scratch, slot_bytes, d_csize, d_flags, tag);
+}
+
 // depth: candidates per one; + 0x100: with the lazy rule (instantiated for 12 candidates — clevel 9 — and, for measurements, 2)
 int launch_lz4_bitplanes(const uint8_t *d_src, bool planes, PlanesGeom pg, uint64_t n_blocks, uint8_t *d_scratch, size_t slot_bytes, uint32_t *d_csize,
                          int depth, uint32_t *d_flags, uint32_t tag, hipStream_t st)
@@ -855,25 +999,15 @@ int launch_lz4_bitplanes(const uint8_t *d_src, bool planes, PlanesGeom pg, uint6
         hhgt_set_error("lz4: too many blocks");
         return HHGT_ERR_ARG;
     }
-#define BP_LAUNCH(D, LZ)                                                                                                    \
-    do {                                                                                                                    \
-        if (planes)                                                                                                         \
-            hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((uint32_t)((n_blocks + 63) / 64 * 64)), dim3(128), 0, st, d_src, pg, \
-                               (uint32_t)n_blocks, d_scratch, (uint64_t)slot_bytes, d_csize, d_flags, tag);                 \
-        else                                                                                                                \
-            hipLaunchKernelGGL((k_lz4_bitplanes<D, LZ>), dim3((uint32_t)n_blocks), dim3(128), 0, st, d_src, pg, (uint32_t)n_blocks, \
-                               d_scratch, (uint64_t)slot_bytes, d_csize, d_flags, tag);                                     \
-    } while (0)
-    if (lazy && depth == 2) BP_LAUNCH(2, true);
-    else if (lazy) BP_LAUNCH(12, true);
-    else if (depth <= 0) BP_LAUNCH(0, false);
-    else if (depth == 1) BP_LAUNCH(1, false);
-    else if (depth == 2) BP_LAUNCH(2, false);
-    else if (depth <= 4) BP_LAUNCH(4, false);
-    else if (depth <= 8) BP_LAUNCH(8, false);
-    else if (depth <= 12) BP_LAUNCH(12, false);
-    else BP_LAUNCH(16, false);
-#undef BP_LAUNCH
+    const auto launch = lazy ? (depth == 2 ? bp_launch<2, true> : bp_launch<12, true>)
+                        : depth <= 0 ? bp_launch<0, false>
+                        : depth == 1 ? bp_launch<1, false>
+                        : depth == 2 ? bp_launch<2, false>
+                        : depth <= 4 ? bp_launch<4, false>
+                        : depth <= 8 ? bp_launch<8, false>
+                        : depth <= 12 ? bp_launch<12, false>
+                                      : bp_launch<16, false>;
+    launch(planes, d_src, pg, (uint32_t)n_blocks, d_scratch, (uint64_t)slot_bytes, d_csize, d_flags, tag, st);
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

@@ -2,7 +2,12 @@
 DESIGN.md §6a "one row walk": the three row-walk kernels (k_count_alleles, k_count_samples, k_genotype_planes) share their
 prologue, row loop and call reader as inlined device functions, and sharing them must cost no registers, no spills, no
 scratch and no LDS over what the three separate copies took; the two decode kernels, which share none of it, keep their
-counts.  SGPR counts and SGPR spills move with the compiler's scalar allocation and are printed, not asserted."""
+counts.  SGPR counts and SGPR spills move with the compiler's scalar allocation and are printed, not asserted.
+
+The same for csrc/lz4bits.hip: the plane coder is a chain of inlined phases, and every instantiation of its
+two kernels must keep the registers, spills, scratch and LDS it had as one function body: 72 VGPRs is the last count at
+seven waves per SIMD (64 the last at eight, which the int8 kernel reaches at depths 0 and 1), and 11 248 bytes of LDS keep
+14 workgroups per CU.  That test reads the kernels' metadata only."""
 import os
 import re
 import shutil
@@ -22,18 +27,38 @@ BUDGET = {
 }
 
 
-@pytest.fixture(scope="module")
-def decode_asm(tmp_path_factory):
+# (kernel, candidates per one, lazy rule) -> (VGPRs, spilled VGPRs, scratch bytes, static LDS bytes) before the plane coder
+# was cut into phases
+BP_BUDGET = {}
+for _d in (0, 1, 2, 4, 8, 12, 16):
+    BP_BUDGET[("k_lz4_bitplanes", _d, False)] = (64 if _d < 2 else 66, 0, 0, 8688 if _d < 2 else 11248)
+    BP_BUDGET[("k_lz4_bitplanes_uni", _d, False)] = (64 if _d == 0 else 70, 0, 0, 9072 if _d < 2 else 11248)
+for _d in (2, 12):
+    BP_BUDGET[("k_lz4_bitplanes", _d, True)] = (64, 0, 0, 11248)
+    BP_BUDGET[("k_lz4_bitplanes_uni", _d, True)] = (70, 0, 0, 11248)
+
+
+def gfx950_asm(tmp_path_factory, stem):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "haplohyped_varawareml_amd", "csrc", "decode.hip")
-    out = tmp_path_factory.mktemp("isa") / "decode.s"
+    src = os.path.join(ROOT, "haplohyped_varawareml_amd", "csrc", stem + ".hip")
+    out = tmp_path_factory.mktemp("isa") / (stem + ".s")
     r = subprocess.run([hipcc, "-O3", "--offload-arch=gfx950", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
                         "-I" + os.path.dirname(src), "-S", "--cuda-device-only", "-o", str(out), src],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     return open(out).read()
+
+
+@pytest.fixture(scope="module")
+def decode_asm(tmp_path_factory):
+    return gfx950_asm(tmp_path_factory, "decode")
+
+
+@pytest.fixture(scope="module")
+def lz4bits_asm(tmp_path_factory):
+    return gfx950_asm(tmp_path_factory, "lz4bits")
 
 
 def kernel_body(asm, name):
@@ -73,3 +98,17 @@ def test_calls_come_from_lds_in_16_byte_loads(decode_asm, name):
     assert len(re.findall(r"\bds_read_b128\b", body)) >= 4, name      # 2 planes x 2 groups of 16 calls per thread
     if name != "k_count_alleles":        # (its chunk pointer is generic on purpose: DESIGN.md §6a)
         assert not re.search(r"\bflat_\w+", body), name
+
+
+@pytest.mark.parametrize("kernel,depth,lazy", sorted(BP_BUDGET))
+def test_plane_coder_budget(lz4bits_asm, kernel, depth, lazy):
+    # one instantiation by its template arguments, as they stand in the mangled name
+    meta = kernel_meta(lz4bits_asm, f"{kernel}ILi{depth}ELb{int(lazy)}EE")
+    vgprs, vgpr_spills, scratch, lds = BP_BUDGET[(kernel, depth, lazy)]
+    print(f"{kernel}<{depth}, {str(lazy).lower()}>: {meta['vgpr_count']} VGPRs, {meta['sgpr_count']} SGPRs, "
+          f"{meta['sgpr_spill_count']} SGPR spills, {meta['vgpr_spill_count']} VGPR spills, "
+          f"{meta['private_segment_fixed_size']} B scratch, {meta['group_segment_fixed_size']} B static LDS")
+    assert meta["vgpr_count"] <= vgprs, meta["vgpr_count"]
+    assert meta["vgpr_spill_count"] <= vgpr_spills, meta["vgpr_spill_count"]
+    assert meta["private_segment_fixed_size"] <= scratch, meta["private_segment_fixed_size"]
+    assert meta["group_segment_fixed_size"] <= lds, meta["group_segment_fixed_size"]

@@ -1,7 +1,7 @@
 """Static instruction counts per marked section of the bit-plane coder at depth D (hipcc -S -DBP_MARKS): which part of the
-window loop the vector instructions sit in.  usage: python tools/isa_sections.py [depth] [planes]   (needs hipcc)
+window loop the vector instructions sit in.  usage: python tools/isa_sections.py [depth] [planes] [lazy]   (needs hipcc)
 planes 1: k_lz4_bitplanes_uni<D> (bit-plane input; its plain and exception-aware paths both count), 0: k_lz4_bitplanes<D>
-(int8 input).
+(int8 input).  lazy 1: the instantiation with the lazy rule (built for depths 2 and 12), 0 (default): without.
 Counts are per textual section between markers, in listing order (a basic block the compiler moved elsewhere is
 attributed to where it landed), so read them as a map, not as a cycle count."""
 import collections
@@ -13,7 +13,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 depth = int(sys.argv[1]) if len(sys.argv) > 1 else 2
 planes = int(sys.argv[2]) if len(sys.argv) > 2 else 1   # 1: the plane-input kernel, 0: int8 input
-kernel = f"_Z19k_lz4_bitplanes_uniILi{depth}ELb0E" if planes else f"_Z15k_lz4_bitplanesILi{depth}ELb0E"
+lazy = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+kernel = f"_Z19k_lz4_bitplanes_uniILi{depth}ELb{lazy}E" if planes else f"_Z15k_lz4_bitplanesILi{depth}ELb{lazy}E"
 out = "/tmp/lz4bits_marks.s"
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-S", "--cuda-device-only", "-DBP_MARKS",
                        "-I", os.path.join(ROOT, "include"), "-o", out,
@@ -43,6 +44,6 @@ for line in open(out):
     cnt.setdefault(sec, collections.Counter())[kind] += 1
     if op == "s_waitcnt" and "lgkmcnt" in t:
         cnt[sec]["lgkm_wait"] += 1          # a wait on LDS / scalar-memory results: one link of the wave's dependent chain
-print(f"{'k_lz4_bitplanes_uni' if planes else 'k_lz4_bitplanes'}<{depth}>: instructions in the listing after each marker")
+print(f"{'k_lz4_bitplanes_uni' if planes else 'k_lz4_bitplanes'}<{depth}{', lazy' if lazy else ''}>: instructions in the listing after each marker")
 for k, c in cnt.items():
     print(f"  {k:12s} valu {c['valu']:5d}  salu {c['salu']:5d}  lds {c['lds']:4d}  vmem {c['vmem']:4d}  waits on lds {c['lgkm_wait']:3d}")
