@@ -161,7 +161,7 @@ extern "C" void hhgt_ctx_destroy(hhgt_ctx *c)
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     c->enc.each([](DevBuf &b) { b.release(); });
-    DevBuf *bufs[] = {&c->counters, &c->cursor, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n, &c->ld_bits};
+    DevBuf *bufs[] = {&c->counters, &c->cursor, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n, &c->ld_bits, &c->score_part};
     for (DevBuf *b : bufs) b->release();
     for (auto &w : c->cw) {
         DevBuf *wb[] = {&w.lz_scratch, &w.lz_csize, &w.lz_flags, &w.fr_bsize, &w.fr_csize, &w.fr_flags};
@@ -1357,4 +1357,22 @@ extern "C" int hhgt_assoc_sums(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t 
     HIP_TRY(hipSetDevice(c->device));
     if (!n_var) return HHGT_OK;
     return timed(c, st, HHGT_STAGE_ASSOC, [&] { return launch_assoc_sums(d_vplanes, n_var, sw, d_w, n_cols, d_sums, st); });
+}
+
+// hhgt_score_sums: a plane kernel with columns — their number and the rows' length checked here, the rest with the family;
+// the partial sums' workspace grows in the call, like hhgt_ld_prune's; both launches run under one timer of HHGT_STAGE_ASSOC
+extern "C" int hhgt_score_sums(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
+                               uint64_t w_hi, const double *d_w, uint32_t n_cols, double *d_sums, void *stream)
+{
+    if (n_cols < 1u || n_cols > 64u || row_words >= (1ull << 27)) {
+        hhgt_set_error("score_sums: %u columns (1 to 64), rows of %llu words (below 2^27)", n_cols, (unsigned long long)row_words);
+        return HHGT_ERR_ARG;
+    }
+    return run_plane_kernel("score_sums", HHGT_STAGE_ASSOC, c, !d_planes ? "planes" : !d_w ? "weights" : !d_sums ? "sums" : nullptr,
+                            off_alignment(d_w, 8) || off_alignment(d_sums, 8) ? "the weights and the sums must be 8-byte aligned" : nullptr,
+                            n_rows, row_words, w_lo, w_hi, 0xffffffffull, stream, [&](hipStream_t st) {
+                                TRY(c->score_part.ensure((size_t)score_spans(w_hi - w_lo) * n_rows * n_cols * sizeof(double)));
+                                return launch_score_sums(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_w, n_cols,
+                                                         c->score_part.as<double>(), d_sums, st);
+                            });
 }

@@ -285,6 +285,7 @@ struct hhgt_ctx {
     hipStream_t frame_stream = nullptr;   // hhgt_set_frame_stream; nullptr: the framing follows the LZ4 kernels on their stream
     DevBuf dec_bad, oh_ovl, oh_lut, crc_x2n;
     DevBuf ld_bits;        // hhgt_ld_prune: the per-pair decisions between its two kernels
+    DevBuf score_part;     // hhgt_score_sums: the spans' partial sums between its two kernels
     bool crc_x2n_ready = false;
     // pinned host mirror for counters
     DevCounters *h_counters = nullptr;
@@ -408,6 +409,10 @@ int launch_ld_walk(const uint64_t *d_bits, uint64_t n_var, uint32_t window, uint
 // assoc.hip
 int launch_assoc_sums(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
                       double *d_sums, hipStream_t st);
+// score.hip
+uint64_t score_spans(uint64_t n_words);   // spans of a range of n_words words: rows of d_part
+int launch_score_sums(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi, const double *d_w,
+                      uint32_t n_cols, double *d_part, double *d_sums, hipStream_t st);
 int launch_inflate(const uint8_t *d_src, uint64_t src_bytes, const uint64_t *d_comp_off, const uint32_t *d_comp_len,
                    const uint64_t *d_out_off, const uint32_t *d_isize, uint64_t n_members, uint8_t *d_dst,
                    uint64_t dst_bytes, uint32_t *d_status, const uint32_t *d_crc32, const uint32_t *d_x2n, hipStream_t st);

@@ -570,6 +570,28 @@ class Context:
                                            _stream()))
         return sums
 
+    def score_sums(self, planes, w, w_lo=0, w_hi=None, sums=None):
+        """sums of per-variant weights under the bits (hhgt_score_sums) of the words [w_lo, w_hi) (default: all) of genotype
+        planes [3, n, words]: w is a float64 tensor [3, 32 * words, n_cols] (1 <= n_cols <= 64) — the value of a HOM_REF,
+        HET, HOM_ALT call at every bit position, finite inside the words of the range, never read outside them; the sums
+        are ADDED to `sums`, a float64 tensor [n, n_cols] (default: zeros), on the current stream — calls on one stream may
+        accumulate into one table.  -> sums"""
+        n, words = _planes_arg(planes)
+        w_hi = words if w_hi is None else int(w_hi)
+        if (w.dtype != torch.float64 or w.dim() != 3 or tuple(w.shape[:2]) != (3, 32 * words) or not w.is_contiguous()
+                or w.device != planes.device):
+            raise ValueError(f"w: a contiguous float64 tensor [3, {32 * words}, n_cols] on the planes' device")
+        n_cols = int(w.shape[2])
+        if not 0 <= n_cols < 1 << 32:
+            raise ValueError(f"n_cols {n_cols}")
+        with torch.cuda.device(self.device):
+            sums = self._out_arg(sums, torch.float64, (n, n_cols), "sums")
+            if sums.device != planes.device:
+                raise ValueError("sums: on the planes' device")
+            check(self.lib.hhgt_score_sums(self.h, _ptr_if_any(planes), n, words, int(w_lo), w_hi, _ptr_if_any(w), n_cols,
+                                           _ptr_if_any(sums), _stream()))
+        return sums
+
     def ld_prune(self, table, r2, keep=None):
         """the greedy walk (hhgt_ld_prune) over one tile: table is an int32 tensor [window + n, window, 8] — hhgt_ld_counts
         over the `window` variants before the tile (rows of zeros where there are none) followed by the tile's n —, keep a

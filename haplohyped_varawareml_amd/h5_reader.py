@@ -14,7 +14,10 @@ genetic_relationship(chromosomes, donor_ids, min_maf, ld_window, ld_r2) the stan
 donors over the variants that pass min_maf and, with ld_window, the LD pruning (GenotypeStore.grm_sums), and
 principal_components(k, ...) its k largest eigenpairs, one record per donor (store.top_eigenpairs: numpy.linalg.eigh on the
 host); association(phenotypes, covariates, chromosomes, donor_ids, min_maf, pcs, ...) a single-variant linear regression
-scan of every variant against one or more phenotypes (GenotypeStore.assoc).  The reference has no such queries."""
+scan of every variant against one or more phenotypes (GenotypeStore.assoc); polygenic_scores(variants, weights, ...) the
+per-donor sums of per-allele effects over listed variants (GenotypeStore.score), and project_components(k,
+train_donor_ids, donor_ids, ...) principal components fitted on some donors and the projection of others onto them
+(GenotypeStore.project).  The reference has no such queries."""
 import numpy as np
 
 from .store import (AC, AN, ASSOC_BETA, ASSOC_P, ASSOC_SE, ASSOC_T, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
@@ -210,12 +213,106 @@ class VCFH5Reader:
         k = check_components(k, len(self.store.samples) if donor_ids is None else len(list(donor_ids)))
         donors, grm, _ = self.genetic_relationship(chromosomes, donor_ids, min_maf, ld_window, ld_r2)
         values, vectors = top_eigenpairs(grm, k)
-        sample = self._donor_column(donors)
+        return self._component_records(donors, vectors), values
+
+    def _component_records(self, donors, vectors):
+        """float64 [len(donors), k] -> principal_components' records: sample, pc1 .. pck"""
+        sample, k = self._donor_column(donors), vectors.shape[1]
         rec = np.zeros(len(donors), dtype=[("sample", sample.dtype)] + [(f"pc{c + 1}", np.float64) for c in range(k)])
         rec["sample"] = sample
         for c in range(k):
             rec[f"pc{c + 1}"] = vectors[:, c]
-        return rec, values
+        return rec
+
+    def project_components(self, k, train_donor_ids, donor_ids=None, chromosomes=None, min_maf=None, ld_window=None, ld_r2=0.2):
+        """principal components fitted on train_donor_ids and the projection of donor_ids onto them -> (training records,
+        projected records, values), records as principal_components returns them.  The variant masks (min_maf, ld_window,
+        ld_r2), the relationship matrix and its k largest eigenpairs run over the training donors exactly as
+        principal_components(k, chromosomes, train_donor_ids, ...) runs them, so the held-out donors touch neither; they are
+        then projected (GenotypeStore.project: the components' variant loadings from the training donors, applied to each
+        donor's complete calls).  donor_ids: default every sample that is not a training donor, in store order.  A
+        training donor listed in donor_ids gets its projection, which is its fitted entry only up to its incomplete
+        calls (GenotypeStore.project says how far)."""
+        train = list(train_donor_ids)
+        k = check_components(k, len(train))
+        names, train, who = self._cohort(chromosomes, train)
+        if donor_ids is None:
+            fitted = set(train)
+            donor_ids = [s for s in self.store.samples if s not in fitted]
+        _, donors, _ = self._cohort(chromosomes, list(donor_ids))
+        masks = self._variant_masks(names, who, min_maf=min_maf, ld_window=ld_window, ld_r2=ld_r2)
+        sums, nsnp = self.store.grm_sums(names, who, variant_mask=masks or None)
+        values, vectors = top_eigenpairs(grm_from_sums(sums, nsnp).cpu().numpy(), k)
+        projected = np.zeros((0, k))
+        if donors:
+            projected = self.store.project(vectors, values, who, donors, names, variant_mask=masks or None).cpu().numpy()
+        return self._component_records(train, vectors), self._component_records(donors, projected), values
+
+    def polygenic_scores(self, variants, weights, names=None, donor_ids=None, chromosomes=None, impute="mean", freq_donor_ids=None):
+        """polygenic scores of donor_ids (default: every sample, store order) -> (records, info).  variants: n records with
+        chrom, pos (1-based, the VCF's POS), ref, alt (a numpy record array with those fields, or a sequence of such
+        4-tuples; str or bytes); weights: float64 [n, K] (or [n]), the effect per ALT allele of variant i in score c; names: the K field
+        names (default score1 .. scoreK).  A listed variant is matched to the store's by (group chr_{N} of its chrom, with
+        or without a leading "chr"; pos; REF base; ALT base): the store holds one base each, so a longer allele matches
+        nothing, and there is no allele or strand flipping.  chromosomes: only those groups (one name or a list; None:
+        every group); a variant of another chromosome is unmatched.  A key listed twice: ValueError.  The matched variants
+        go to GenotypeStore.score (impute "mean" or "none"; freq_donor_ids: the donors of the allele frequencies, default
+        the scored ones), whose formulas are the contract.  records: host numpy, one per donor in the order asked —
+        sample, n_variants (the variants that took part: the same in every row), one float64 field per name; info: a dict
+        of matched, unmatched (listed variants the store does not have) and unused (matched, but without a called allele
+        among the frequency donors)."""
+        st = self.store
+        groups, donors, who = self._cohort(chromosomes, donor_ids)
+        freq = None if freq_donor_ids is None else self._cohort(chromosomes, list(freq_donor_ids))[2]
+        if isinstance(variants, np.ndarray) and variants.dtype.names:
+            columns = [variants[f].tolist() for f in ("chrom", "pos", "ref", "alt")]
+        else:
+            columns = [list(c) for c in zip(*(tuple(x) for x in variants))] or [[], [], [], []]
+        text = lambda col: [x.decode() if isinstance(x, bytes) else str(x) for x in col]                       # noqa: E731
+        chrom, ref, alt = text(columns[0]), text(columns[2]), text(columns[3])
+        pos = np.array([int(p) for p in columns[1]], dtype=np.int64)
+        w = np.asarray(weights, dtype=np.float64)
+        w = w[:, None] if w.ndim == 1 else w
+        if w.ndim != 2 or w.shape[0] != len(pos) or not 1 <= w.shape[1] <= 64:
+            raise ValueError(f"polygenic_scores: weights {list(w.shape)} for {len(pos)} variants ([n, K], 1 <= K <= 64)")
+        names = [f"score{c + 1}" for c in range(w.shape[1])] if names is None else [str(x) for x in names]
+        if len(names) != w.shape[1] or len(set(names)) != len(names) or set(names) & {"sample", "n_variants"}:
+            raise ValueError(f"polygenic_scores: {w.shape[1]} distinct names other than sample and n_variants, not {names}")
+        keys = list(zip((c[3:] if c.startswith("chr") else c for c in chrom), pos.tolist(), ref, alt))
+        if len(set(keys)) != len(keys):
+            seen = set()
+            twice = next(k for k in keys if k in seen or seen.add(k))
+            raise ValueError(f"polygenic_scores: chr{twice[0]}:{twice[1]} {twice[2]}>{twice[3]} is listed twice")
+        betas, masks, matched = {}, {}, 0
+        for g in groups:
+            mine = [i for i, k in enumerate(keys) if "chr_" + k[0] == g and len(k[2]) == 1 and len(k[3]) == 1]
+            if not mine:
+                continue
+            start, s_ref, s_alt, _ = st.variants(g)
+            # one int64 per variant: (0-based start, REF base, ALT base); the first of a store's equal keys is the match
+            code = (start.astype(np.int64) << 16) | (s_ref.astype(np.int64) << 8) | s_alt.astype(np.int64)
+            order = np.argsort(code, kind="stable")
+            want = np.array([((keys[i][1] - 1) << 16) | (ord(keys[i][2]) << 8) | ord(keys[i][3]) for i in mine], dtype=np.int64)
+            at = np.searchsorted(code[order], want)
+            hit = (at < len(code)) & (code[order][np.minimum(at, len(code) - 1)] == want) if len(code) else np.zeros(len(mine), bool)
+            if not hit.any():
+                continue
+            where = order[at[hit]]
+            betas[g] = np.zeros((len(start), w.shape[1]))
+            betas[g][where] = w[np.array(mine)[hit]]
+            masks[g] = np.zeros(len(start), bool)
+            masks[g][where] = True
+            matched += int(hit.sum())
+        scores, used = np.zeros((len(donors), w.shape[1])), {}
+        if betas:
+            scores, used = st.score(betas, list(betas), who, variant_mask=masks, impute=impute, freq_samples=freq)
+            scores = scores.cpu().numpy()
+        sample = self._donor_column(donors)
+        rec = np.zeros(len(donors), dtype=[("sample", sample.dtype), ("n_variants", np.int64)] + [(n, np.float64) for n in names])
+        rec["sample"], rec["n_variants"] = sample, sum(used.values())
+        for c, n in enumerate(names):
+            rec[n] = scores[:, c]
+        return rec, dict(matched=matched, unmatched=len(keys) - matched, unused=matched - sum(used.values()))
 
     def association(self, phenotypes, covariates=None, chromosomes=None, donor_ids=None, min_maf=None, pcs=0,
                     ld_window=None, ld_r2=0.2):

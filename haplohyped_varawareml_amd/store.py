@@ -31,6 +31,8 @@ from .store_stats import (AC, AN, ASSOC_ALT, ASSOC_BETA, ASSOC_COMPLETE, ASSOC_H
                           LD_HM, LD_MA, LD_MH, LD_N, NSNP, assoc_design, assoc_from_sums, grm_from_sums, ibs_counts,
                           check_components, kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts,
                           standardized_dosages, student_t_two_sided, top_eigenpairs)
+from .store_stats import (SCORE_MAX_COLS, SCORE_SLICE, SCORE_SPAN, loadings_from_sums, projection_class_weights,  # noqa: F401
+                          score_class_weights)
 
 # the reference's per-donor record (vcf_to_h5.py:119-127): packed, 35 bytes
 SNP_DTYPE = np.dtype([("chrom", "S5"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
@@ -141,6 +143,8 @@ class GenotypeStore:
         self.stats.update(grm_plane_blocks=0, grm_words=0)
         # and of assoc_sums: Blosc blocks its plane stage decoded, counted variants it reduced
         self.stats.update(assoc_plane_blocks=0, assoc_variants=0)
+        # and of score_sums: Blosc blocks its plane stage decoded, counted variants whose weights it summed
+        self.stats.update(score_plane_blocks=0, score_variants=0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -737,6 +741,157 @@ class GenotypeStore:
         W, q, yy = assoc_design(y, covariates)
         T = self.assoc_sums(group, W, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes)
         return assoc_from_sums(T, torch.from_numpy(W.sum(axis=0)).to(T.device), q, torch.from_numpy(yy).to(T.device))
+
+    def _score_weights(self, who, weights, groups, samples, v_lo, v_hi, variant_mask, inner):
+        """score_sums' and score's (`who`) start: `weights` — one array for one group or a dict group -> array, each
+        float64 with the axes `inner` ("3VK" or "VK": V the group's range) — against _query -> (idx, queries, {group: host
+        array or tensor}, K).  groups = None with a dict: its keys, in order.  KeyError for a listed group without weights,
+        ValueError for a shape or dtype that does not fit; nothing is allocated on the device."""
+        import torch
+        if isinstance(weights, dict) and groups is None:
+            groups = list(weights)
+        idx, queries = self._query(who, groups, samples, v_lo, v_hi, variant_mask)
+        if not isinstance(weights, dict):
+            if len(queries) != 1:
+                raise ValueError(f"{who}: one array of weights needs a single group (several: a dict group -> array)")
+            weights = {queries[0][0]: weights}
+        out, K = {}, None
+        for group, lo, hi, _, _ in queries:
+            if group not in weights:
+                raise KeyError(group)
+            w = weights[group] if torch.is_tensor(weights[group]) else np.asarray(weights[group])
+            shape = tuple(int(x) for x in w.shape)
+            if inner == "VK" and len(shape) == 1:
+                w, shape = w[:, None], shape + (1,)
+            want = (3, hi - lo) if inner == "3VK" else (hi - lo,)
+            if (str(w.dtype).split(".")[-1] != "float64" or len(shape) != len(want) + 1 or shape[:-1] != want
+                    or not 1 <= shape[-1] <= SCORE_MAX_COLS or K not in (None, shape[-1])):
+                raise ValueError(f"{who}: the weights of {group} must be float64 {list(want)} + [K], 1 <= K <= {SCORE_MAX_COLS}, "
+                                 f"the same K in every group, not {w.dtype} {list(shape)}")
+            out[group], K = w, shape[-1]
+        if K is None:
+            raise ValueError(f"{who}: no group")
+        return idx, queries, out, K
+
+    def _to_device(self, x):
+        """host array or tensor -> a contiguous tensor on the device"""
+        import torch
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        return x.to(self._context().device).contiguous()
+
+    def score_sums(self, weights, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None,
+                   plane_bytes=None):
+        """per-sample sums of per-variant weights over the variants of `groups`: a float64 device tensor [len(samples), K],
+        row i for samples[i] (names or indices; None = every sample in store order; a sample named twice gets its row
+        twice) — the sum over the counted variants v at which the sample's call is complete, of weights[d, v, :] for the
+        call's dosage d (0 HOM_REF, 1 HET, 2 HOM_ALT); a call that is not complete contributes nothing.  weights: float64
+        [3, v_hi - v_lo, K], host or device, 1 <= K <= 64, for one group, or a dict group -> such an array over the whole
+        group (groups = None: the dict's keys, in order); KeyError for a listed group without weights, ValueError for a
+        shape or dtype that does not fit, before anything is allocated.  groups, samples, v_lo / v_hi, variant_mask,
+        slab_bytes and plane_bytes mean what they mean in pair_counts; a variant the mask leaves out has no bit and its
+        weights are not read, the others' must be finite.  Per plane window (_plane_walk: hhgt_genotype_planes under the
+        packed mask; cached chunks used, the read cache neither filled nor evicted) the window's weights are scattered to
+        its bit positions and one hhgt_score_sums call (the f64 MFMA; include/hhgt.h states its arithmetic: sums of
+        exactly representable partial sums are exact) adds to one table [plane rows, K]; groups, windows and slabs add
+        into it and the samples' rows are picked at the end.  No genotype and no dosage is written anywhere."""
+        import torch
+        idx, queries, weights, K = self._score_weights("score_sums", weights, groups, samples, v_lo, v_hi, variant_mask, "3VK")
+        ctx, bs = self._context(), self._blocksize()
+        scols, rows = plane_rows(idx, self.meta["sc"])
+        table = torch.zeros((len(scols) * self.meta["sc"], K), dtype=torch.float64, device=ctx.device)
+        for group, lo, hi, n_var, mask in queries if len(idx) else ():
+            w = self._to_device(weights[group])
+            if mask is not None:
+                mask = self._device_bool(mask)
+                w = torch.where(mask[None, :, None], w, torch.zeros_like(w))
+            for a, b, words, planes in self._plane_walk(group, idx, lo, hi, n_var, "score_plane_blocks", slab_bytes,
+                                                        plane_bytes, self._device_mask(mask, lo, n_var)):
+                d_w = torch.zeros((3, 32 * words, K), dtype=torch.float64, device=ctx.device)
+                d_w[:, torch.from_numpy(plane_positions(a, b, bs)).to(ctx.device)] = w[:, a - lo:b - lo]
+                ctx.score_sums(planes, d_w, 0, words, sums=table)
+            self.stats["score_variants"] += hi - lo if mask is None else int(mask.sum())
+        return table[torch.from_numpy(rows).to(ctx.device)]
+
+    def score(self, betas, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
+              impute="mean", freq_samples=None):
+        """polygenic scores of `samples` -> (scores, used): scores a float64 device tensor [len(samples), K], used a dict
+        group -> the number of its variants that took part.  betas: float64 [v_hi - v_lo, K] (or [v_hi - v_lo]: K = 1), host
+        or device, the effect per ALT allele, for one group, or a dict group -> such an array over the whole group; the
+        other arguments up to plane_bytes mean what they mean in score_sums.  Per group, allele_counts over freq_samples
+        (default: the scored samples, each once) and score_class_weights (impute "mean" or "none") give the class weights,
+        the offset and the variants used; scores = score_sums of the weights + the offsets.  With "mean" that is, per
+        sample, the sum over the used variants of beta x (the dosage, or twice the ALT frequency among freq_samples where
+        the call is not complete); a variant without a called allele among freq_samples is not used.  A variant the mask
+        leaves out takes part in nothing.  score_class_weights' formulas are the contract: these are sums, not plink2
+        --score's per-allele averages."""
+        import torch
+        idx, queries, betas, K = self._score_weights("score", betas, groups, samples, v_lo, v_hi, variant_mask, "VK")
+        if impute not in ("mean", "none"):
+            raise ValueError(f"score: impute {impute!r} (\"mean\" or \"none\")")
+        freq = np.unique(idx) if freq_samples is None else self._query("score", queries[0][0], freq_samples, single=True)[0]
+        ctx = self._context()
+        weights, masks, used_n = {}, {}, {}
+        offset = torch.zeros(K, dtype=torch.float64, device=ctx.device)
+        for group, lo, hi, n_var, mask in queries:
+            beta = self._to_device(betas[group])
+            if mask is not None:
+                masks[group] = mask = self._device_bool(mask)
+                beta = torch.where(mask[:, None], beta, torch.zeros_like(beta))
+            weights[group], off, used = score_class_weights(beta, self.allele_counts(group, freq, lo, hi, slab_bytes), impute)
+            offset += off
+            used_n[group] = int((used if mask is None else used & mask).sum())
+        lo, hi = queries[0][1:3] if len(queries) == 1 else (0, None)
+        mask = None if not masks else masks if len(queries) > 1 else masks[queries[0][0]]
+        sums = self.score_sums(weights, [q[0] for q in queries], idx, lo, hi, mask, slab_bytes, plane_bytes)
+        return sums + offset[None, :], used_n
+
+    def projection_weights(self, vectors, values, groups=None, samples=None, variant_mask=None, slab_bytes=None,
+                           plane_bytes=None):
+        """the class weights that project a sample onto principal components fitted on `samples` (the TRAINING samples:
+        names or indices, distinct; None = every sample) -> a dict group -> float64 device tensor [3, n_variants, k], what
+        score_sums takes.  vectors float64 [len(samples), k] and values [k] are pca's (or top_eigenpairs') over the same
+        samples, groups and variant_mask.  Per group: allele_counts over the samples -> standardized_dosages' z and used;
+        assoc_sums of the vectors over the variants that are used and that the mask marks -> loadings_from_sums, with
+        n_variants the number of such variants over all groups -> projection_class_weights, scattered to the group's
+        variants (zeros elsewhere).  ValueError if no variant is used, an eigenvalue is not positive or the shapes
+        disagree."""
+        import torch
+        idx, queries = self._query("projection_weights", groups, samples, 0, None, variant_mask)
+        vectors = np.ascontiguousarray(vectors.detach().cpu().numpy() if torch.is_tensor(vectors) else vectors)
+        if vectors.dtype != np.float64 or vectors.ndim != 2 or vectors.shape[0] != len(idx) or len(np.reshape(values, -1)) != vectors.shape[1]:
+            raise ValueError(f"projection_weights: vectors must be float64 [{len(idx)}, k] with k values, "
+                             f"not {vectors.dtype} {list(vectors.shape)}")
+        ctx = self._context()
+        fitted = []
+        for group, lo, hi, n_var, mask in queries:
+            z, used = standardized_dosages(self.allele_counts(group, idx, lo, hi, slab_bytes))
+            if mask is not None:
+                used = used & self._device_bool(mask)
+            fitted.append((z, used))
+        n_variants = sum(int(used.sum()) for _, used in fitted)
+        if n_variants == 0:
+            raise ValueError("projection_weights: no variant is used")
+        out = {}
+        for (group, lo, hi, n_var, _), (z, used) in zip(queries, fitted):
+            T = self.assoc_sums(group, vectors, idx, lo, hi, used, slab_bytes, plane_bytes)
+            counted = torch.nonzero(used).reshape(-1)
+            zc = z[:, counted]
+            Wd = torch.zeros((3, n_var, vectors.shape[1]), dtype=torch.float64, device=ctx.device)
+            Wd[:, counted] = projection_class_weights(zc, loadings_from_sums(T, zc, values, n_variants))
+            out[group] = Wd
+        return out
+
+    def project(self, vectors, values, train_samples, samples, groups=None, variant_mask=None, slab_bytes=None, plane_bytes=None):
+        """the components of `samples` on principal components fitted on train_samples: score_sums(projection_weights(
+        vectors, values, groups, train_samples, variant_mask), samples = samples, variant_mask = variant_mask) -> a float64
+        device tensor [len(samples), k].  This is how held-out samples get components without entering the fit: fit
+        (pca) on the training samples, project the rest.  A training sample with no incomplete call gets back its own
+        eigenvector entry, up to the relationship matrix's f32-chain error (hhgt_grm) passed through the decomposition.
+        With incomplete calls it differs, in the order of the missing rate, because the relationship matrix divides each
+        pair's sum by the number of its jointly complete variants while the loadings divide by the number of variants; no
+        shrinkage correction is attempted either."""
+        Wd = self.projection_weights(vectors, values, groups, train_samples, variant_mask, slab_bytes, plane_bytes)
+        return self.score_sums(Wd, list(Wd), samples, 0, None, variant_mask, slab_bytes, plane_bytes)
 
     def variant_mask(self, group, samples=None, v_lo=0, v_hi=None, min_maf=None, max_ac=None, min_ac=None):
         """a class of the variants [v_lo, v_hi) of a group, from allele_counts over `samples` (same arguments), as a bool

@@ -154,6 +154,90 @@ def top_eigenpairs(grm, k):
     return w, v
 
 
+# hhgt_score_sums' geometry (HHGT_SCORE_SLICE, HHGT_SCORE_SPAN of include/hhgt.h): plane words whose weights are staged at a
+# time, and plane words per span of a range of up to SCORE_SPAN * 65535 words — the kernel's paths change at their multiples
+SCORE_SLICE = 1
+SCORE_SPAN = 64
+# columns of the per-variant weights a call of hhgt_score_sums takes at most
+SCORE_MAX_COLS = 64
+
+
+def _is_torch(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def score_class_weights(beta, counts, impute="mean"):
+    """the per-class weights of a polygenic score -> (Wd float64 [3, V, K], offset float64 [K], used bool [V]): beta is
+    [V, K] (or [V]: K = 1), the effect per ALT allele of every variant in each of K scores, counts an allele count table
+    [V, 4] of the frequency samples (numpy or torch, both of one kind).  impute = "mean": with p = AC / AN as in
+    standardized_dosages, Wd[d] = (d - 2p) beta for a complete call of dosage d = 0, 1, 2 and offset = the sum over the
+    variants of 2p beta; a variant with AN == 0 is not used: zeros, nothing in the offset.  A call that is not complete has
+    no bit and contributes 0, so offset + (the sum of Wd over a sample's calls) = the sum over the used variants of beta x
+    (the dosage, or 2p where the call is not complete).  impute = "none": Wd[d] = d beta, offset 0, every variant used: a
+    call that is not complete counts as dosage 0.  Scores are sums, not per-allele averages: plink2's .sscore is not the
+    contract.  ValueError for another impute, a beta that is not [V] or [V, K] or not of counts' length."""
+    if impute not in ("mean", "none"):
+        raise ValueError(f"score_class_weights: impute {impute!r} (\"mean\" or \"none\")")
+    i64, f64 = _ops(counts)[:2]
+    stack = _math(counts)[4]
+    if _is_torch(beta) != _is_torch(counts):
+        raise ValueError("score_class_weights: beta and counts must both be numpy arrays or both torch tensors")
+    b = f64(beta)
+    if len(b.shape) == 1:
+        b = b[:, None]
+    if len(b.shape) != 2 or len(counts.shape) != 2 or counts.shape[1] != 4 or b.shape[0] != counts.shape[0]:
+        raise ValueError(f"score_class_weights: beta {list(beta.shape)} ([V] or [V, K]) for counts {list(counts.shape)} ([V, 4])")
+    t = i64(counts)
+    an, ac = t[:, AN], t[:, AC]
+    if impute == "none":
+        used = an == an
+        two_p = f64(an) * 0.0
+    else:
+        used = an > 0
+        # (a variant that is not used gets AN = 1 here, so that nothing divides by 0, and 0 at the end)
+        two_p = 2.0 * (f64(ac * used) / f64(an * used + (~used) * 1))
+    bu = b * f64(used)[:, None]
+    Wd = stack([(float(d) - two_p)[:, None] * bu for d in range(3)])
+    return Wd, (two_p[:, None] * bu).sum(0), used
+
+
+def loadings_from_sums(T, z, values, n_variants):
+    """the variant loadings of principal components from the sums over the fitted samples -> float64 [n_counted, k]: T is
+    float64 [n_counted, 3, k], GenotypeStore.assoc_sums of the eigenvectors U [n, k] of the relationship matrix (planes
+    ASSOC_HET, ASSOC_COMPLETE, ASSOC_ALT), z [3, n_counted] the standardised dosages of the same variants
+    (standardized_dosages over the same samples), values [k] the eigenvalues, n_variants the number of variants the matrix
+    was averaged over (all groups).  A = z[0] (T_COMPLETE - T_HET - T_ALT) + z[1] T_HET + z[2] T_ALT is X^T U for the
+    standardised dosage matrix X (0 where a call is not complete), and loadings = A / (n_variants * values): where no call
+    is incomplete the relationship matrix is X X^T / n_variants, so X loadings = U.  ValueError if an eigenvalue is <= 0
+    or the shapes disagree."""
+    f64 = _ops(T)[1]
+    T, z = f64(T), f64(z)
+    lam = np.asarray(values.detach().cpu().numpy() if _is_torch(values) else values, dtype=np.float64).reshape(-1)
+    if len(T.shape) != 3 or T.shape[1] != 3 or tuple(z.shape) != (3, T.shape[0]) or len(lam) != T.shape[2]:
+        raise ValueError(f"loadings_from_sums: T {list(T.shape)} ([n, 3, k]), z {list(z.shape)} ([3, n]), {len(lam)} values (k)")
+    if not (lam > 0).all():
+        raise ValueError(f"loadings_from_sums: eigenvalue {lam[~(lam > 0)][0]:g} (every eigenvalue must be positive)")
+    if int(n_variants) < 1:
+        raise ValueError(f"loadings_from_sums: {int(n_variants)} variants")
+    ref = T[:, ASSOC_COMPLETE] - T[:, ASSOC_HET] - T[:, ASSOC_ALT]
+    A = z[0][:, None] * ref + z[1][:, None] * T[:, ASSOC_HET] + z[2][:, None] * T[:, ASSOC_ALT]
+    scale = float(int(n_variants)) * lam
+    if _is_torch(T):
+        import torch
+        scale = torch.from_numpy(scale).to(T.device)
+    return A / scale[None, :]
+
+
+def projection_class_weights(z, loadings):
+    """(z [3, V] of standardized_dosages, loadings float64 [V, k]; numpy or torch) -> Wd float64 [3, V, k]:
+    Wd[d, v, c] = z[d, v] * loadings[v, c], the weight of a complete call of dosage d in component c — zero where the
+    variant is not used, for z is zero there.  ValueError if the shapes disagree."""
+    f64 = _ops(z)[1]
+    if len(z.shape) != 2 or z.shape[0] != 3 or len(loadings.shape) != 2 or loadings.shape[0] != z.shape[1]:
+        raise ValueError(f"projection_class_weights: z {list(z.shape)} ([3, V]), loadings {list(loadings.shape)} ([V, k])")
+    return f64(z)[:, :, None] * f64(loadings)[None, :, :]
+
+
 # columns of the statistics table of assoc_from_sums (and GenotypeStore.assoc), per variant and phenotype
 ASSOC_BETA, ASSOC_SE, ASSOC_T, ASSOC_P = 0, 1, 2, 3
 # planes of GenotypeStore.assoc_sums (and of hhgt_assoc_sums' sums), in the kernel's order: HET calls, complete calls (both

@@ -436,6 +436,40 @@ int hhgt_ld_prune(hhgt_ctx *ctx, const uint32_t *d_table, uint64_t n_var, uint32
 int hhgt_assoc_sums(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
                     double *d_sums, void *stream);
 
+/* hhgt_score_sums reduces the words [w_lo, w_hi) of every row of genotype planes — d_planes, hhgt_genotype_planes' output,
+ * uint32 [3][n_rows][row_words]: HET, HOM_REF, HOM_ALT — against per-variant weights: the sum over variants behind a
+ * polygenic score or a projection onto principal components, the transpose of hhgt_assoc_sums.  d_w is double
+ * [3][32 * row_words][n_cols], row-major, 8-byte aligned, indexed by DOSAGE CLASS and then absolute bit position, as hhgt_grm's
+ * d_z is: class 0 HOM_REF, 1 HET, 2 HOM_ALT — so plane 0 reads d_w[1], plane 1 d_w[0], plane 2 d_w[2].  It must be finite
+ * at every position of the words [w_lo, w_hi) (a 0 bit times NaN is NaN) and is never read outside them.  d_sums is double
+ * [n_rows][n_cols], 8-byte aligned:
+ *     d_sums[r][c] += sum over the positions p of words [w_lo, w_hi) and the planes k of bit_k(r, p) * d_w[class(k)][p][c].
+ * The arithmetic is defined on the bits: should planes overlap at a position, all of them count.  It ADDS to d_sums, as
+ * hhgt_pair_counts and hhgt_grm add to their tables — every entry has one owner in the launch that touches it, a plain
+ * read-modify-write, no atomics anywhere —, so windows, groups and calls may accumulate on ONE stream; two streams adding
+ * to one table at the same time are the caller's error.
+ * Two kernels.  The range is cut into spans of
+ *     span(n) = HHGT_SCORE_SPAN * max(1, ceil(ceil(n / HHGT_SCORE_SPAN) / HHGT_SCORE_MAX_SPANS)) words, n = w_hi - w_lo,
+ * counted from w_lo — HHGT_SCORE_SPAN words for every range of up to HHGT_SCORE_SPAN * HHGT_SCORE_MAX_SPANS words; a
+ * function of n alone, not of n_rows, n_cols or the device.  One workgroup per (128 plane rows, span) reduces its span
+ * with v_mfma_f64_16x16x4_f64, a plane bit as 0.0 / 1.0 on one side and the weights, staged HHGT_SCORE_SLICE words at a
+ * time, on the other, the three planes chained into one accumulator, and stores its partial sums [span][row][column] in the
+ * context's workspace (8 bytes x spans x n_rows x n_cols, grown on demand).  The second adds an entry's partial sums in
+ * ascending order of the span, starting from 0, and adds the total to d_sums.
+ * Numerics: every product is 0 or a value of d_w exactly, and an entry is a float64 sum of the selected values and of zeros,
+ * taken in an order fixed by the arguments: the result is a function of the arguments alone, the same bits on every call
+ * and in every state of the device.  It is exact whenever every partial sum is representable (then splitting a range over
+ * several calls changes nothing either); otherwise its error is bounded, to first order, by (m - 1) * 2^-53 * (the sum of
+ * |d_w| over the selected values) for an entry that sums m values — the bound of a summation in any order: no order inside
+ * the instruction is claimed.
+ * 1 <= n_cols <= 64; n_rows below 2^32 (128 rows a workgroup on grid.x: below 2^25 workgroups); w_lo <= w_hi <= row_words
+ * < 2^27; else HHGT_ERR_ARG with a message.  n_rows == 0 or w_lo == w_hi is HHGT_OK and touches nothing. */
+#define HHGT_SCORE_SLICE 1
+#define HHGT_SCORE_SPAN 64
+#define HHGT_SCORE_MAX_SPANS 65535
+int hhgt_score_sums(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
+                    const double *d_w, uint32_t n_cols, double *d_sums, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values
@@ -557,7 +591,7 @@ int hhgt_inflate_members(hhgt_ctx *ctx, const void *d_src, uint64_t src_bytes, c
 #define HHGT_STAGE_LD_PRUNE 12 /* r^2 decisions of every pair                                    */
 #define HHGT_STAGE_LD_WALK 13 /* the greedy walk over the decisions                              */
 #define HHGT_STAGE_GRM 14     /* sums of products of standardised dosages over genotype planes   */
-#define HHGT_STAGE_ASSOC 15   /* sums of per-sample weights under the bits of variant-major planes */
+#define HHGT_STAGE_ASSOC 15   /* sums of weights under plane bits (hhgt_assoc_sums, hhgt_score_sums) */
 #define HHGT_N_STAGES 16
 int hhgt_profile_enable(hhgt_ctx *ctx, int on);
 int hhgt_profile_reset(hhgt_ctx *ctx);
