@@ -116,6 +116,31 @@ static int timed(hhgt_ctx *c, hipStream_t st, int stage, Launch launch)
     return HHGT_OK;
 }
 
+// "<who>: null context", or "<who>: null <null_arg>" for the first null pointer among those the work needs (nullptr: none)
+static int check_not_null(const char *who, const hhgt_ctx *c, const char *null_arg)
+{
+    if (c && !null_arg) return HHGT_OK;
+    hhgt_set_error("%s: null %s", who, !c ? "context" : null_arg);
+    return HHGT_ERR_ARG;
+}
+
+// what an entry does behind its checks: the stream, the device, nothing without work, then run(stream)
+template <typename Run>
+static int on_device(hhgt_ctx *c, void *stream, bool work, Run run)
+{
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipSetDevice(c->device));
+    if (!work) return HHGT_OK;
+    return run(st);
+}
+
+// the same for one launch under the timer of its stage
+template <typename Launch>
+static int launch_on_device(hhgt_ctx *c, void *stream, int stage, bool work, Launch launch)
+{
+    return on_device(c, stream, work, [&](hipStream_t st) { return timed(c, st, stage, [&] { return launch(st); }); });
+}
+
 extern "C" int hhgt_ctx_create(int device, hhgt_ctx **out)
 {
     if (!out) return HHGT_ERR_ARG;
@@ -1141,10 +1166,7 @@ extern "C" int hhgt_decompress_chunks(hhgt_ctx *c, const void *d_src, const uint
 extern "C" int hhgt_decompress_blocks(hhgt_ctx *c, const hhgt_block_sel *d_sel, uint32_t n_sel, uint64_t chunk_nbytes,
                                       int typesize, int blocksize, void *d_dst, uint64_t *n_bad, void *stream)
 {
-    if (!c || (n_sel && (!d_sel || !d_dst))) {
-        hhgt_set_error("decompress_blocks: null %s", !c ? "context" : !d_sel ? "selection array" : "destination");
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_not_null("decompress_blocks", c, !n_sel ? nullptr : !d_sel ? "selection array" : !d_dst ? "destination" : nullptr));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
     TRY(check_decode_block(typesize, blocksize));
@@ -1184,10 +1206,7 @@ template <typename Launch>
 static int run_row_kernel(const char *who, const char *out, hhgt_ctx *c, const void *d_sel, uint32_t n_sel, const void *d_out,
                           uint32_t sc, uint32_t vc, int typesize, int blocksize, uint64_t *n_bad, void *stream, Launch launch)
 {
-    if (!c || (n_sel && (!d_sel || !d_out))) {
-        hhgt_set_error("%s: null %s", who, !c ? "context" : !d_sel ? "selection array" : out);
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_not_null(who, c, !n_sel ? nullptr : !d_sel ? "selection array" : !d_out ? out : nullptr));
     TRY(check_row_kernel_args(who, sc, vc, typesize, blocksize));
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipSetDevice(c->device));
@@ -1237,10 +1256,7 @@ static int run_plane_kernel(const char *who, int stage, hhgt_ctx *c, const char 
                             uint64_t row_words, uint64_t w_lo, uint64_t w_hi, uint64_t row_limit, void *stream, Launch launch)
 {
     const bool work = n_rows && w_lo < w_hi;
-    if (!c || (work && null_arg)) {
-        hhgt_set_error("%s: null %s", who, !c ? "context" : null_arg);
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_not_null(who, c, work ? null_arg : nullptr));
     if (w_lo > w_hi || w_hi > row_words || n_rows > row_limit) {
         hhgt_set_error("%s: words [%llu, %llu) of rows of %llu words, %llu rows", who, (unsigned long long)w_lo,
                        (unsigned long long)w_hi, (unsigned long long)row_words, (unsigned long long)n_rows);
@@ -1250,10 +1266,7 @@ static int run_plane_kernel(const char *who, int stage, hhgt_ctx *c, const char 
         hhgt_set_error("%s: %s", who, misaligned);
         return HHGT_ERR_ARG;
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!work) return HHGT_OK;
-    return timed(c, st, stage, [&] { return launch(st); });
+    return launch_on_device(c, stream, stage, work, launch);
 }
 
 static bool off_alignment(const void *p, uintptr_t align) { return reinterpret_cast<uintptr_t>(p) & (align - 1u); }
@@ -1299,10 +1312,7 @@ static int check_ld_args(const char *who, hhgt_ctx *c, uint32_t window, const do
             hhgt_set_error("%s: window %u (1 to 1024)", who, window);
         return HHGT_ERR_ARG;
     }
-    if (!c || null_arg) {
-        hhgt_set_error("%s: null %s", who, !c ? "context" : null_arg);
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_not_null(who, c, null_arg));
     if (off_alignment(d_table, 32)) {
         hhgt_set_error("%s: the table must be 32-byte aligned", who);
         return HHGT_ERR_ARG;
@@ -1315,48 +1325,45 @@ extern "C" int hhgt_ld_counts(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n
 {
     const bool work = n_var && sw;
     TRY(check_ld_args("ld_counts", c, window, nullptr, !work ? nullptr : !d_vplanes ? "variant planes" : !d_table ? "table" : nullptr, d_table));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!work) return HHGT_OK;
-    return timed(c, st, HHGT_STAGE_LD, [&] { return launch_ld_counts(d_vplanes, n_var, sw, window, d_table, st); });
+    return launch_on_device(c, stream, HHGT_STAGE_LD, work,
+                            [&](hipStream_t st) { return launch_ld_counts(d_vplanes, n_var, sw, window, d_table, st); });
 }
 
 extern "C" int hhgt_ld_prune(hhgt_ctx *c, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2,
                              uint8_t *d_keep, void *stream)
 {
     TRY(check_ld_args("ld_prune", c, window, &r2, !n_var ? nullptr : !d_table ? "table" : !d_keep ? "keep flags" : nullptr, d_table));
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!n_var) return HHGT_OK;
-    TRY(c->ld_bits.ensure((size_t)n_var * ld_walk_words(window) * sizeof(uint64_t)));
-    uint64_t *bits = c->ld_bits.as<uint64_t>();
-    TRY(timed(c, st, HHGT_STAGE_LD_PRUNE, [&] { return launch_ld_exceeds(d_table, n_var, window, r2, bits, st); }));
-    return timed(c, st, HHGT_STAGE_LD_WALK, [&] { return launch_ld_walk(bits, n_var, window, d_keep, st); });
+    return on_device(c, stream, n_var != 0, [&](hipStream_t st) {
+        TRY(c->ld_bits.ensure((size_t)n_var * ld_walk_words(window) * sizeof(uint64_t)));
+        uint64_t *bits = c->ld_bits.as<uint64_t>();
+        TRY(timed(c, st, HHGT_STAGE_LD_PRUNE, [&] { return launch_ld_exceeds(d_table, n_var, window, r2, bits, st); }));
+        return timed(c, st, HHGT_STAGE_LD_WALK, [&] { return launch_ld_walk(bits, n_var, window, d_keep, st); });
+    });
 }
 
-// hhgt_assoc_sums checks for itself (a family of one): the columns, the pointers its work needs (the sums with a variant,
-// the planes and the weights with a variant and a word), their alignment
+// 1 to 64 columns of weights: hhgt_assoc_sums and hhgt_score_sums
+static int check_columns(const char *who, uint32_t n_cols)
+{
+    if (n_cols >= 1u && n_cols <= 64u) return HHGT_OK;
+    hhgt_set_error("%s: %u columns (1 to 64)", who, n_cols);
+    return HHGT_ERR_ARG;
+}
+
+// hhgt_assoc_sums: the columns, the pointers its work needs (the sums with a variant, the planes and the weights with a
+// variant and a word), their alignment
 extern "C" int hhgt_assoc_sums(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w,
                                uint32_t n_cols, double *d_sums, void *stream)
 {
-    if (n_cols < 1u || n_cols > 64u) {
-        hhgt_set_error("assoc_sums: %u columns (1 to 64)", n_cols);
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_columns("assoc_sums", n_cols));
     const bool reads = n_var && sw;
-    const char *null_arg = !n_var ? nullptr : !d_sums ? "sums" : !reads ? nullptr : !d_vplanes ? "variant planes" : !d_w ? "weights" : nullptr;
-    if (!c || null_arg) {
-        hhgt_set_error("assoc_sums: null %s", !c ? "context" : null_arg);
-        return HHGT_ERR_ARG;
-    }
+    TRY(check_not_null("assoc_sums", c,
+                       !n_var ? nullptr : !d_sums ? "sums" : !reads ? nullptr : !d_vplanes ? "variant planes" : !d_w ? "weights" : nullptr));
     if (off_alignment(d_w, 8) || off_alignment(d_sums, 8)) {
         hhgt_set_error("assoc_sums: the weights and the sums must be 8-byte aligned");
         return HHGT_ERR_ARG;
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HIP_TRY(hipSetDevice(c->device));
-    if (!n_var) return HHGT_OK;
-    return timed(c, st, HHGT_STAGE_ASSOC, [&] { return launch_assoc_sums(d_vplanes, n_var, sw, d_w, n_cols, d_sums, st); });
+    return launch_on_device(c, stream, HHGT_STAGE_ASSOC, n_var != 0,
+                            [&](hipStream_t st) { return launch_assoc_sums(d_vplanes, n_var, sw, d_w, n_cols, d_sums, st); });
 }
 
 // hhgt_score_sums: a plane kernel with columns — their number and the rows' length checked here, the rest with the family;
@@ -1364,7 +1371,7 @@ extern "C" int hhgt_assoc_sums(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t 
 extern "C" int hhgt_score_sums(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,
                                uint64_t w_hi, const double *d_w, uint32_t n_cols, double *d_sums, void *stream)
 {
-    if (n_cols < 1u || n_cols > 64u || row_words >= (1ull << 27)) {
+    if (check_columns("score_sums", n_cols) != HHGT_OK || row_words >= (1ull << 27)) {   // (one message names both)
         hhgt_set_error("score_sums: %u columns (1 to 64), rows of %llu words (below 2^27)", n_cols, (unsigned long long)row_words);
         return HHGT_ERR_ARG;
     }

@@ -4,25 +4,16 @@
 // positions at which one row of one plane has a 1: a (variants x samples) . (samples x columns) product whose left factor is
 // bits, done on the f64 MFMA.  include/hhgt.h has the contract.
 #include "common.h"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+#include "plane_tiles.h"
 
 static constexpr uint32_t WAVES = 8;                     // waves per workgroup: 16 variants each
 static constexpr uint32_t VARS = 16u * WAVES;            // variants per workgroup
 static constexpr uint32_t SLICE = 4;                     // sample words per row staged at a time: 128 rows of the weights
 
-// grid = ceil(n_var / 128), 512 threads as 8 waves; CT = ceil(n_cols / 16) column tiles.  Wave u owns the variants
-// 128 b + 16 u + (0..15) x the three planes x all column tiles: 3 CT accumulators of v_mfma_f64_16x16x4_f64 (4 doubles a
-// lane each: 96 registers at CT = 4), and walks the sample words of its rows.  A: lane l is variant (l & 15) and sample
-// (l >> 4) of a step of four samples; it holds the words of its variant's three rows (the four lanes of a variant load the
-// same word: 16 distinct addresses a wave, one per row, sw words apart — a row's words stay in cache for the next slices)
-// and per step takes bit 4 t + (l >> 4) of each as 0.0 / 1.0: a bit-field extract and an AND that make the high half of the
-// double.  B: the weights of the slice's 128 samples, staged by the whole workgroup in LDS as [column tile][sample][16
-// doubles] — columns >= n_cols and samples of words >= sw as zeros, so that no product reads what nobody wrote —; lane l
-// reads double (l & 15) of sample 4 t + (l >> 4): the 32 lanes of one ds_read_b64 pass read two consecutive samples' 128
-// bytes, 256 consecutive bytes, every bank once.  The products are 0 or a weight exactly, and an accumulator takes the
-// samples in ascending order of their step: the same order on every call.  At the end register r of lane l is
-// variant (l >> 4) + 4 r, column l & 15 (the f64 C/D map: not the f32 one): 16 lanes store 128 consecutive bytes.
+// The bit-sum tile of plane_tiles.h with a variant for a row and a sample for a position.  grid = ceil(n_var / 128); wave u
+// owns the variants 128 b + 16 u + (0..15) x the three planes x all column tiles: 3 CT accumulators (4 doubles a lane each: 96
+// registers at CT = 4), one class of weights that all three planes read.  A variant's words are sw apart, 16 distinct
+// addresses a wave — a row's words stay in cache for the next slices.  Samples of words >= sw are staged as zeros.
 // The weights do not fit LDS whole (2560 x 16 doubles = 320 KiB): every workgroup reads all of them once, slice by slice,
 // from L2; 128 variants a workgroup keep that traffic near the planes' own.
 template <uint32_t CT>
@@ -59,7 +50,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_assoc_sums(const uint32_t *__res
             const uint32_t c = item % (CT * 16u), s = item / (CT * 16u);       // (constants: shifts, or a multiply for 48)
             const uint64_t row = 32ull * w0 + s;
             const double x = (c < n_cols && row < 32ull * sw) ? w[row * n_cols + c] : 0.0;
-            s_w[((c >> 4) * 32u * SLICE + s) * 16u + (c & 15u)] = x;
+            s_w[weight_at<CT, SLICE>(0u, c >> 4, s, c & 15u)] = x;
         }
         __syncthreads();
 #pragma unroll
@@ -68,14 +59,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_assoc_sums(const uint32_t *__res
             for (uint32_t t = 0; t < 8u; ++t) {
                 double a[3];
 #pragma unroll
-                for (uint32_t p = 0; p < 3u; ++p) {
-                    // bit 4 t + k of the word as 0.0 / 1.0: the bit, sign-extended, masks the high half of 1.0
-                    const int32_t on = ((int32_t)(bits[p][i] << (31u - 4u * t - k))) >> 31;
-                    a[p] = __hiloint2double(on & 0x3ff00000, 0);
-                }
+                for (uint32_t p = 0; p < 3u; ++p) a[p] = bit_as_f64(bits[p][i], 4u * t + k);
 #pragma unroll
                 for (uint32_t ct = 0; ct < CT; ++ct) {
-                    const double b = b_src[((ct * 32u * SLICE) + 32u * i + 4u * t) * 16u];
+                    const double b = b_src[weight_at<CT, SLICE>(0u, ct, 32u * i + 4u * t, 0u)];
 #pragma unroll
                     for (uint32_t p = 0; p < 3u; ++p)
                         acc[p][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[p], b, acc[p][ct], 0, 0, 0);
@@ -83,11 +70,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_assoc_sums(const uint32_t *__res
             }
         }
     }
-    // C/D of the f64 16 x 16 MFMA: column = lane & 15, row = (lane >> 4) + 4 r for register r
     const uint32_t col = lane & 15u;
 #pragma unroll
     for (uint32_t r = 0; r < 4u; ++r) {
-        const uint64_t v = (uint64_t)blockIdx.x * VARS + wave * 16u + k + 4u * r;
+        const uint64_t v = (uint64_t)blockIdx.x * VARS + wave * 16u + tile_row(lane, r);
         if (v >= n_var) continue;
 #pragma unroll
         for (uint32_t p = 0; p < 3u; ++p)
@@ -109,15 +95,10 @@ int launch_assoc_sums(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, co
                        (unsigned long long)n_var, (unsigned long long)sw, 0x7fffffffull * VARS);
         return HHGT_ERR_ARG;
     }
-    void (*kernel)(const uint32_t *, uint64_t, uint32_t, const double *, uint32_t, double *) = nullptr;
-    switch ((n_cols + 15u) / 16u) {
-    case 1: kernel = k_assoc_sums<1>; break;
-    case 2: kernel = k_assoc_sums<2>; break;
-    case 3: kernel = k_assoc_sums<3>; break;
-    default: kernel = k_assoc_sums<4>; break;
-    }
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)blocks), dim3(64 * WAVES), 0, st, d_vplanes, n_var, (uint32_t)sw, d_w, n_cols,
-                       d_sums);
+    by_column_tiles(n_cols, [&](auto ct) {
+        hipLaunchKernelGGL(k_assoc_sums<decltype(ct)::value>, dim3((uint32_t)blocks), dim3(64 * WAVES), 0, st, d_vplanes, n_var,
+                           (uint32_t)sw, d_w, n_cols, d_sums);
+    });
     HIP_TRY(hipGetLastError());
     return HHGT_OK;
 }

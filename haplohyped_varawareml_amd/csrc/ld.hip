@@ -3,8 +3,7 @@
 // of rows at most `window` apart to eight popcounts, hhgt_ld_prune decides r^2 > t per pair from those integers and walks the
 // variants greedily.  include/hhgt.h has the contract.
 #include "common.h"
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // one 16-byte LDS slot: HET, COMPLETE, HOM_ALT, unused
+#include "plane_tiles.h"
 
 // ---- hhgt_variant_planes: the bit transposition ------------------------------------------------------------------------
 
@@ -86,20 +85,6 @@ int launch_variant_planes(const uint32_t *d_planes, uint32_t n_rows, uint64_t ro
 static constexpr uint32_t TILE = 32;     // variants per tile side: a workgroup owns the pairs (i, j) of 32 i-rows x 32 j-rows
 static constexpr uint32_t SLICE = 16;    // sample words per row staged at a time: 64 bytes of each row and plane
 
-// slot of (word w of the slice, row r of a side), as in pairs.hip: the 32 rows of a word are consecutive 16-byte slots (the
-// 16 lanes of a ds_read_b128 group read 16 rows of one word: one 256-byte bank row), and a word's rows begin one slot past
-// the previous word's (the 8 lanes of a ds_write_b128 group store 8 words of one row)
-__device__ __forceinline__ uint32_t ld_slot(uint32_t side, uint32_t w, uint32_t r)
-{
-    return (side * SLICE + w) * (TILE + 1u) + r;
-}
-
-// acc += popcount(x): v_bcnt_u32_b32 adds into its third operand
-__device__ __forceinline__ void ld_bcnt(uint32_t &acc, uint32_t x)
-{
-    asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc) : "v"(x));
-}
-
 // grid = (T, 1 + ceil(window / 32)) for T = ceil(n_var / 32): workgroup (ti, b) holds the i-rows of tile ti and the j-rows of
 // tile ti + b, and owns the entries (k, d) = (i, j - i - 1) with 1 <= j - i <= window of them: a pair lies in one i-tile and
 // one j-tile, at most ceil(window / 32) tiles on, so every entry of the table has exactly one owner.  256 threads as 16 x 16: thread
@@ -127,41 +112,27 @@ __global__ __launch_bounds__(256, 4) void k_ld_counts(const uint32_t *__restrict
 #pragma unroll
             for (int e = 0; e < 8; ++e) cnt[a][c][e] = 0u;
     for (uint32_t w0 = 0; w0 < sw; w0 += SLICE) {
-        __syncthreads();   // the previous slice has been read
-#pragma unroll
-        for (uint32_t q = 0; q < 2u * TILE * SLICE / 256u; ++q) {
-            const uint32_t item = threadIdx.x + 256u * q;
-            const uint32_t w = item & (SLICE - 1u), rr = item / SLICE, side = rr / TILE, r = rr & (TILE - 1u);
-            const uint64_t row = (side ? j0 : (uint64_t)i0) + r;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (row < n_var && w < sw - w0) {
-                const uint32_t *p = vplanes + row * sw + w0 + w;
-                v.x = p[0];
-                v.y = p[plane_words];
-                v.z = p[2u * plane_words];
-            }
-            s_slice[ld_slot(side, w, r)] = v;
-        }
-        __syncthreads();
+        stage_slice<TILE, SLICE, 2u * TILE * SLICE / 256u>(s_slice, vplanes, sw, plane_words, (uint64_t)i0, j0, n_var, w0, sw - w0,
+                                                           [](uint32_t het, uint32_t m, uint32_t alt) { return u32x4{het, m, alt, 0u}; });
 #pragma unroll 4
         for (uint32_t w = 0; w < SLICE; ++w) {
             u32x4 I[2];
 #pragma unroll
-            for (int a = 0; a < 2; ++a) I[a] = s_slice[ld_slot(0u, w, ty + 16u * (uint32_t)a)];
+            for (int a = 0; a < 2; ++a) I[a] = s_slice[tile_slot<TILE, SLICE>(0u, w, ty + 16u * (uint32_t)a)];
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const u32x4 J = s_slice[ld_slot(1u, w, tx + 16u * (uint32_t)c)];
+                const u32x4 J = s_slice[tile_slot<TILE, SLICE>(1u, w, tx + 16u * (uint32_t)c)];
 #pragma unroll
                 for (int a = 0; a < 2; ++a) {
                     uint32_t *t = cnt[a][c];
-                    ld_bcnt(t[0], I[a].y & J.y);                              // N:  Mu Mv
-                    ld_bcnt(t[1], I[a].x & J.y);                              // HM: Hu Mv
-                    ld_bcnt(t[2], I[a].z & J.y);                              // AM: Au Mv
-                    ld_bcnt(t[3], I[a].y & J.x);                              // MH: Mu Hv
-                    ld_bcnt(t[4], I[a].y & J.z);                              // MA: Mu Av
-                    ld_bcnt(t[5], I[a].x & J.x);                              // HH: Hu Hv
-                    ld_bcnt(t[6], (I[a].x & J.z) | (I[a].z & J.x));           // HA: Hu Av or Au Hv
-                    ld_bcnt(t[7], I[a].z & J.z);                              // AA: Au Av
+                    bcnt_acc(t[0], I[a].y & J.y);                              // N:  Mu Mv
+                    bcnt_acc(t[1], I[a].x & J.y);                              // HM: Hu Mv
+                    bcnt_acc(t[2], I[a].z & J.y);                              // AM: Au Mv
+                    bcnt_acc(t[3], I[a].y & J.x);                              // MH: Mu Hv
+                    bcnt_acc(t[4], I[a].y & J.z);                              // MA: Mu Av
+                    bcnt_acc(t[5], I[a].x & J.x);                              // HH: Hu Hv
+                    bcnt_acc(t[6], (I[a].x & J.z) | (I[a].z & J.x));           // HA: Hu Av or Au Hv
+                    bcnt_acc(t[7], I[a].z & J.z);                              // AA: Au Av
                 }
             }
         }

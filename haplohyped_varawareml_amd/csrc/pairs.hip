@@ -2,27 +2,10 @@
 // state.  The planes are hhgt_genotype_planes' — uint32 [3][n_rows][row_words], HET, HOM_REF, HOM_ALT, 32 variants per
 // word, a variant that is not counted is a 0 bit in all three — so a pair's counters are popcounts of ANDs of two rows.
 #include "common.h"
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));   // one 16-byte LDS slot: HET, M, REF, ALT
+#include "plane_tiles.h"
 
 static constexpr uint32_t TILE = 64;     // pairs per tile side: a workgroup owns table[64 i-rows][64 j-rows]
 static constexpr uint32_t SLICE = 16;    // plane words per row staged at a time: 64 bytes of each row and plane
-
-// slot of (word w of the slice, row r of a side) in the staged slice: the 64 rows of a word are consecutive 16-byte slots
-// (one 256-byte bank row: the 16 lanes of a ds_read_b128 group read 16 rows of one word), and a word's rows begin one slot
-// past a bank row after the previous word's (the 8 lanes of a ds_write_b128 group store 8 words of one row).  Offsets
-// between a thread's reads are constants: one address register per side.
-__device__ __forceinline__ uint32_t slot(uint32_t side, uint32_t w, uint32_t r)
-{
-    return (side * SLICE + w) * (TILE + 1u) + r;
-}
-
-// acc += popcount(x): v_bcnt_u32_b32 adds into its third operand.  Said as one instruction so that the 80 counters of a
-// thread stay 80 scalar registers (left to the vectoriser, __builtin_popcount + add pairs them up and spills)
-__device__ __forceinline__ void bcnt_acc(uint32_t &acc, uint32_t x)
-{
-    asm("v_bcnt_u32_b32 %0, %1, %0" : "+v"(acc) : "v"(x));
-}
 
 // grid = (T, T) for T = ceil(n_rows / 64); the workgroups with blockIdx.y <= blockIdx.x work, tile (ti = y, tj = x).  256
 // threads as 16 x 16: thread (ty, tx) keeps the pairs (i, j) = (64 ti + ty + 16 a, 64 tj + tx + 16 b), a, b = 0..3, and
@@ -48,32 +31,16 @@ __global__ __launch_bounds__(256, 4) void k_pair_counts(const uint32_t *__restri
 #pragma unroll
         for (int b = 0; b < 4; ++b) nsnp[a][b] = hh[a][b] = ibs0[a][b] = h1[a][b] = h2[a][b] = 0u;
     for (uint32_t w0 = w_lo; w0 < w_hi; w0 += SLICE) {
-        __syncthreads();   // the previous slice has been read
-        // item = (row of the 128, word of the slice): consecutive lanes on consecutive words of one row
-#pragma unroll 4
-        for (uint32_t q = 0; q < 2u * TILE * SLICE / 256u; ++q) {
-            const uint32_t item = threadIdx.x + 256u * q;
-            const uint32_t w = item & (SLICE - 1u), rr = item / SLICE, side = rr / TILE, r = rr & (TILE - 1u);
-            const uint32_t row = (side ? tj : ti) * TILE + r;
-            u32x4 v = {0u, 0u, 0u, 0u};
-            if (row < n_rows && w < w_hi - w0) {
-                const uint32_t *p = planes + (uint64_t)row * row_words + w0 + w;
-                v.x = p[0];
-                v.z = p[plane_words];
-                v.w = p[2u * plane_words];
-                v.y = v.x | v.z | v.w;
-            }
-            s_slice[slot(side, w, r)] = v;
-        }
-        __syncthreads();
+        stage_slice<TILE, SLICE, 4>(s_slice, planes, row_words, plane_words, ti * TILE, tj * TILE, n_rows, w0, w_hi - w0,
+                                    [](uint32_t het, uint32_t ref, uint32_t alt) { return u32x4{het, het | ref | alt, ref, alt}; });
 #pragma unroll 4
         for (uint32_t w = 0; w < SLICE; ++w) {
             u32x4 I[4];
 #pragma unroll
-            for (int a = 0; a < 4; ++a) I[a] = s_slice[slot(0u, w, ty + 16u * (uint32_t)a)];
+            for (int a = 0; a < 4; ++a) I[a] = s_slice[tile_slot<TILE, SLICE>(0u, w, ty + 16u * (uint32_t)a)];
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                const u32x4 J = s_slice[slot(1u, w, tx + 16u * (uint32_t)b)];
+                const u32x4 J = s_slice[tile_slot<TILE, SLICE>(1u, w, tx + 16u * (uint32_t)b)];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) {
                     bcnt_acc(nsnp[a][b], I[a].y & J.y);

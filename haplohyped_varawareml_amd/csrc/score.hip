@@ -5,8 +5,7 @@
 // planes together: a (samples x variants) . (variants x columns) product whose left factor is bits, done on the f64 MFMA —
 // the transpose of assoc.hip's.  include/hhgt.h has the contract.
 #include "common.h"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+#include "plane_tiles.h"
 
 static constexpr uint32_t WAVES = 8;                     // waves per workgroup: 16 plane rows each
 static constexpr uint32_t ROWS = 16u * WAVES;            // plane rows per workgroup
@@ -16,19 +15,13 @@ static constexpr uint32_t ADD_THREADS = 256;             // k_score_add: one ent
 // the class of weights plane k reads: the planes are HET, HOM_REF, HOM_ALT, the weights HOM_REF, HET, HOM_ALT
 __device__ static constexpr uint32_t class_of_plane(uint32_t p) { return p == 0u ? 1u : p == 1u ? 0u : 2u; }
 
-// grid = (ceil(n_rows / 128), spans), 512 threads as 8 waves; CT = ceil(n_cols / 16) column tiles.  Workgroup (b, y) owns the
-// plane rows 128 b + (0..127) over the words [w_lo + y span, min(w_lo + (y + 1) span, w_hi)); wave u its rows 16 u + (0..15)
-// x all column tiles: CT accumulators of v_mfma_f64_16x16x4_f64 (4 doubles a lane each: 32 registers at CT = 4), into which
-// the three planes' MFMAs chain.  A: lane l is plane row (l & 15) and position (l >> 4) of a step of four positions; it holds
-// the slice's word of its row in each plane (the four lanes of a row load the same word) and per step takes bit
-// 4 t + (l >> 4) of each as 0.0 / 1.0: the bit, sign-extended, masks the high half of 1.0.  B: the slice's weights, staged by
-// the whole workgroup in LDS as [class][column tile][position][16 doubles] — columns >= n_cols and positions of words past
-// the span's end as zeros, so that no product reads what nobody wrote, and nothing outside [w_lo, w_hi) is loaded —; lane l
-// reads double (l & 15) of position 4 t + (l >> 4): the 32 lanes of one ds_read_b64 pass read 256 consecutive bytes, every
-// bank once.  The products are 0 or a weight exactly; an accumulator takes the positions in ascending order and, at a
-// position, the planes in theirs: the same order on every call.  At the end register r of lane l is row (l >> 4) + 4 r,
-// column l & 15 (the f64 C/D map), and goes to part[y][row][column] with a plain store: every entry of the span's partial
-// table that belongs to a row and a column is written, by exactly one lane.
+// The bit-sum tile of plane_tiles.h with a plane row (a sample's row) for a row and a variant for a position.  grid =
+// (ceil(n_rows / 128), spans): workgroup (b, y) owns the plane rows 128 b + (0..127) over the words [w_lo + y span,
+// min(w_lo + (y + 1) span, w_hi)); wave u its rows 16 u + (0..15) x all column tiles: CT accumulators (4 doubles a lane each:
+// 32 registers at CT = 4), into which the three planes' MFMAs chain, each plane against its class of weights: at a position
+// the planes in their order.  Positions of words past the span's end are staged as zeros, and nothing outside [w_lo, w_hi) is
+// loaded.  The accumulators go to part[y][row][column] with a plain store: every entry of the span's partial table that
+// belongs to a row and a column is written, by exactly one lane.
 // The weights do not fit LDS: every row tile streams its spans' weights once from L2 / MALL.  128 rows a tile, not 256: a
 // 256-row tile would halve that stream (an estimate: at 2560 rows, 230 k positions and 16 columns, 10 x 88 MB in place of
 // 20 x 88 MB), but needs 16 waves a workgroup or two accumulator sets a wave, and the stream is served by the caches, not
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_sums(const uint32_t *__res
             const uint32_t s = rest % (32u * SLICE), cls = rest / (32u * SLICE);
             const uint64_t pos = 32ull * w0 + s;
             const double x = (c < n_cols && pos < 32ull * w_end) ? w[(cls * class_stride + pos) * n_cols + c] : 0.0;
-            s_w[((cls * CT + (c >> 4)) * 32u * SLICE + s) * 16u + (c & 15u)] = x;
+            s_w[weight_at<CT, SLICE>(cls, c >> 4, s, c & 15u)] = x;
         }
         __syncthreads();
 #pragma unroll
@@ -85,27 +78,22 @@ __global__ __launch_bounds__(64 * WAVES) void k_score_sums(const uint32_t *__res
             for (uint32_t t = 0; t < 8u; ++t) {
                 double a[3];
 #pragma unroll
-                for (uint32_t p = 0; p < 3u; ++p) {
-                    // bit 4 t + k of the word as 0.0 / 1.0: the bit, sign-extended, masks the high half of 1.0
-                    const int32_t on = ((int32_t)(bits[p][i] << (31u - 4u * t - k))) >> 31;
-                    a[p] = __hiloint2double(on & 0x3ff00000, 0);
-                }
+                for (uint32_t p = 0; p < 3u; ++p) a[p] = bit_as_f64(bits[p][i], 4u * t + k);
 #pragma unroll
                 for (uint32_t ct = 0; ct < CT; ++ct)
 #pragma unroll
                     for (uint32_t p = 0; p < 3u; ++p) {
-                        const double b = b_src[((class_of_plane(p) * CT + ct) * 32u * SLICE + 32u * i + 4u * t) * 16u];
+                        const double b = b_src[weight_at<CT, SLICE>(class_of_plane(p), ct, 32u * i + 4u * t, 0u)];
                         acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[p], b, acc[ct], 0, 0, 0);
                     }
             }
         }
     }
-    // C/D of the f64 16 x 16 MFMA: column = lane & 15, row = (lane >> 4) + 4 r for register r
     const uint32_t col = lane & 15u;
     double *dst = part + (uint64_t)blockIdx.y * n_rows * n_cols;
 #pragma unroll
     for (uint32_t r = 0; r < 4u; ++r) {
-        const uint64_t out_row = (uint64_t)blockIdx.x * ROWS + wave * 16u + k + 4u * r;
+        const uint64_t out_row = (uint64_t)blockIdx.x * ROWS + wave * 16u + tile_row(lane, r);
         if (out_row >= n_rows) continue;
 #pragma unroll
         for (uint32_t ct = 0; ct < CT; ++ct) {
@@ -149,15 +137,10 @@ int launch_score_sums(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_wo
 {
     const uint64_t span = score_span_words(w_hi - w_lo), spans = score_spans(w_hi - w_lo);
     const uint64_t tiles = ((uint64_t)n_rows + ROWS - 1u) / ROWS;
-    void (*kernel)(const uint32_t *, uint32_t, uint64_t, uint64_t, uint64_t, uint64_t, const double *, uint32_t, double *) = nullptr;
-    switch ((n_cols + 15u) / 16u) {
-    case 1: kernel = k_score_sums<1>; break;
-    case 2: kernel = k_score_sums<2>; break;
-    case 3: kernel = k_score_sums<3>; break;
-    default: kernel = k_score_sums<4>; break;
-    }
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)tiles, (uint32_t)spans), dim3(64 * WAVES), 0, st, d_planes, n_rows, row_words, w_lo,
-                       w_hi, span, d_w, n_cols, d_part);
+    by_column_tiles(n_cols, [&](auto ct) {
+        hipLaunchKernelGGL(k_score_sums<decltype(ct)::value>, dim3((uint32_t)tiles, (uint32_t)spans), dim3(64 * WAVES), 0, st, d_planes,
+                           n_rows, row_words, w_lo, w_hi, span, d_w, n_cols, d_part);
+    });
     HIP_TRY(hipGetLastError());
     const uint64_t n_entries = (uint64_t)n_rows * n_cols;
     hipLaunchKernelGGL(k_score_add, dim3((uint32_t)((n_entries + ADD_THREADS - 1u) / ADD_THREADS)), dim3(ADD_THREADS), 0, st, d_part,

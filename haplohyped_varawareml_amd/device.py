@@ -99,6 +99,23 @@ def _planes_arg(planes, what="planes: a contiguous int32 tensor [3, n_rows, row_
     return int(planes.shape[1]), int(planes.shape[2])
 
 
+def _plane_words(planes, w_lo, w_hi):
+    """genotype planes and a word range as the plane kernels take them -> (n_rows, words, w_lo, w_hi); w_hi None: all words"""
+    n, words = _planes_arg(planes)
+    return n, words, int(w_lo), words if w_hi is None else int(w_hi)
+
+
+def _weights_arg(w, lead, planes):
+    """the weights of assoc_sums / score_sums: contiguous float64 [*lead, n_cols] on the planes' device -> n_cols"""
+    if (w.dtype != torch.float64 or w.dim() != len(lead) + 1 or tuple(w.shape[:-1]) != lead or not w.is_contiguous()
+            or w.device != planes.device):
+        raise ValueError(f"w: a contiguous float64 tensor [{', '.join(map(str, lead))}, n_cols] on the planes' device")
+    n_cols = int(w.shape[-1])
+    if not 0 <= n_cols < 1 << 32:
+        raise ValueError(f"n_cols {n_cols}")
+    return n_cols
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -497,11 +514,10 @@ class Context:
         """pairwise counts (hhgt_pair_counts) over the words [w_lo, w_hi) (default: all) of genotype planes [3, n, words]:
         ADDED to `table`, an int32 tensor [n, n, 4] (NSNP, HETHET, IBS0, HET1 per ordered pair of rows; default: zeros),
         on the current stream — calls on one stream may accumulate into one table.  -> table"""
-        n, words = _planes_arg(planes)
-        w_hi = words if w_hi is None else int(w_hi)
+        n, words, w_lo, w_hi = _plane_words(planes, w_lo, w_hi)
         with torch.cuda.device(self.device):
             table = self._out_arg(table, torch.int32, (n, n, 4), "table")
-            check(self.lib.hhgt_pair_counts(self.h, _ptr_if_any(planes), n, words, int(w_lo), w_hi, _ptr_if_any(table), _stream()))
+            check(self.lib.hhgt_pair_counts(self.h, _ptr_if_any(planes), n, words, w_lo, w_hi, _ptr_if_any(table), _stream()))
         return table
 
     def grm(self, planes, z, w_lo=0, w_hi=None, table=None):
@@ -509,13 +525,12 @@ class Context:
         planes [3, n, words]: z is a float32 tensor [3, 32 * words], the value of a HOM_REF, HET, HOM_ALT call at every bit
         position; the sums are ADDED to `table`, a float64 tensor [n, n] (default: zeros), on the current stream — calls
         on one stream may accumulate into one table.  -> table"""
-        n, words = _planes_arg(planes)
-        w_hi = words if w_hi is None else int(w_hi)
+        n, words, w_lo, w_hi = _plane_words(planes, w_lo, w_hi)
         if z.dtype != torch.float32 or tuple(z.shape) != (3, 32 * words) or not z.is_contiguous() or z.device != planes.device:
             raise ValueError(f"z: a contiguous float32 tensor [3, {32 * words}] on the planes' device")
         with torch.cuda.device(self.device):
             table = self._out_arg(table, torch.float64, (n, n), "table")
-            check(self.lib.hhgt_grm(self.h, _ptr_if_any(planes), n, words, int(w_lo), w_hi, _ptr_if_any(z), _ptr_if_any(table),
+            check(self.lib.hhgt_grm(self.h, _ptr_if_any(planes), n, words, w_lo, w_hi, _ptr_if_any(z), _ptr_if_any(table),
                                     _stream()))
         return table
 
@@ -524,8 +539,7 @@ class Context:
         [3, n_rows, words]: an int32 tensor [3, 32 * (w_hi - w_lo), ceil(n_rows / 32)] — HET, COMPLETE, HOM_ALT; row p is
         bit position 32 * w_lo + p of the plane rows, bit r % 32 of word r // 32 is plane row r —, every word of it
         written (default: a new tensor).  -> vplanes"""
-        n, words = _planes_arg(planes)
-        w_lo, w_hi = int(w_lo), words if w_hi is None else int(w_hi)
+        n, words, w_lo, w_hi = _plane_words(planes, w_lo, w_hi)
         with torch.cuda.device(self.device):
             shape = (3, 32 * max(w_hi - w_lo, 0), -(-n // 32))
             if vplanes is None:     # (every word is written: no need for zeros)
@@ -556,12 +570,7 @@ class Context:
         [n, 3, n_cols], gets at [v, k, c] the sum of w[s, c] over the bits s of row v of plane k — every entry written
         (default: a new tensor), on the current stream.  -> sums"""
         n, sw = _planes_arg(vplanes, "vplanes: a contiguous int32 tensor [3, n_var, sw]")
-        if (w.dtype != torch.float64 or w.dim() != 2 or w.shape[0] != 32 * sw or not w.is_contiguous()
-                or w.device != vplanes.device):
-            raise ValueError(f"w: a contiguous float64 tensor [{32 * sw}, n_cols] on the planes' device")
-        n_cols = int(w.shape[1])
-        if not 0 <= n_cols < 1 << 32:
-            raise ValueError(f"n_cols {n_cols}")
+        n_cols = _weights_arg(w, (32 * sw,), vplanes)
         with torch.cuda.device(self.device):
             if sums is None:        # (every entry is written: no need for zeros)
                 sums = torch.empty((n, 3, n_cols), dtype=torch.float64, device=self.device)
@@ -576,19 +585,13 @@ class Context:
         HET, HOM_ALT call at every bit position, finite inside the words of the range, never read outside them; the sums
         are ADDED to `sums`, a float64 tensor [n, n_cols] (default: zeros), on the current stream — calls on one stream may
         accumulate into one table.  -> sums"""
-        n, words = _planes_arg(planes)
-        w_hi = words if w_hi is None else int(w_hi)
-        if (w.dtype != torch.float64 or w.dim() != 3 or tuple(w.shape[:2]) != (3, 32 * words) or not w.is_contiguous()
-                or w.device != planes.device):
-            raise ValueError(f"w: a contiguous float64 tensor [3, {32 * words}, n_cols] on the planes' device")
-        n_cols = int(w.shape[2])
-        if not 0 <= n_cols < 1 << 32:
-            raise ValueError(f"n_cols {n_cols}")
+        n, words, w_lo, w_hi = _plane_words(planes, w_lo, w_hi)
+        n_cols = _weights_arg(w, (3, 32 * words), planes)
         with torch.cuda.device(self.device):
             sums = self._out_arg(sums, torch.float64, (n, n_cols), "sums")
             if sums.device != planes.device:
                 raise ValueError("sums: on the planes' device")
-            check(self.lib.hhgt_score_sums(self.h, _ptr_if_any(planes), n, words, int(w_lo), w_hi, _ptr_if_any(w), n_cols,
+            check(self.lib.hhgt_score_sums(self.h, _ptr_if_any(planes), n, words, w_lo, w_hi, _ptr_if_any(w), n_cols,
                                            _ptr_if_any(sums), _stream()))
         return sums
 

@@ -114,6 +114,23 @@ class StoreWriter(CohortWriter):
         self._par.close()
 
 
+# GenotypeStore.stats: host counters, all from 0
+STAT_KEYS = (
+    # read_windows: chunks and compressed bytes read from the file, Blosc blocks decoded and their decoded size (the kernel
+    # decodes a block whole and writes the selected range of it)
+    "chunks_read", "compressed_bytes_read", "blocks_decoded", "bytes_decoded",
+    # allele_counts: Blosc blocks it decoded, compressed bytes it read from the file (cache hits not included)
+    "count_blocks", "count_compressed_bytes_read",
+    "sample_count_blocks",                      # sample_counts (shares count_compressed_bytes_read): Blosc blocks it decoded
+    # the plane queries: Blosc blocks their plane stage decoded, and what they reduced
+    "pair_plane_blocks", "pair_words",          # pair_counts: plane words per row
+    "ld_plane_blocks", "ld_pairs",              # ld_counts / ld_prune: pairs of counted variants
+    "grm_plane_blocks", "grm_words",            # grm_sums: plane words per row, read by its two reductions
+    "assoc_plane_blocks", "assoc_variants",     # assoc_sums: counted variants
+    "score_plane_blocks", "score_variants",     # score_sums: counted variants whose weights it summed
+)
+
+
 class GenotypeStore:
     """Reader.  Opens either the working store directory or the HDF5 file the converter exports
     (`OUT/{cohort}.h5`: read natively through h5file.H5Reader — metadata and raw chunks only).  Decoding runs on the
@@ -128,23 +145,7 @@ class GenotypeStore:
         self.cache_bytes = int(cache_bytes)
         self._cache = OrderedDict()      # (group, chunk id) -> device uint8 tensor of the framed chunk
         self._cache_used = 0
-        # host counters of read_windows: chunks and compressed bytes read from the file, Blosc blocks decoded and their
-        # decoded size (the kernel decodes a block whole and writes the selected range of it)
-        self.stats = dict(chunks_read=0, compressed_bytes_read=0, blocks_decoded=0, bytes_decoded=0)
-        # and of allele_counts: Blosc blocks it decoded, compressed bytes it read from the file (cache hits not included)
-        self.stats.update(count_blocks=0, count_compressed_bytes_read=0)
-        # and of sample_counts (which shares count_compressed_bytes_read with it): Blosc blocks it decoded
-        self.stats.update(sample_count_blocks=0)
-        # and of pair_counts: Blosc blocks its first stage decoded, plane words per row its second stage read
-        self.stats.update(pair_plane_blocks=0, pair_words=0)
-        # and of ld_counts / ld_prune: Blosc blocks their plane stage decoded, pairs of counted variants they counted
-        self.stats.update(ld_plane_blocks=0, ld_pairs=0)
-        # and of grm_sums: Blosc blocks its plane stage decoded, plane words per row its two reductions read
-        self.stats.update(grm_plane_blocks=0, grm_words=0)
-        # and of assoc_sums: Blosc blocks its plane stage decoded, counted variants it reduced
-        self.stats.update(assoc_plane_blocks=0, assoc_variants=0)
-        # and of score_sums: Blosc blocks its plane stage decoded, counted variants whose weights it summed
-        self.stats.update(score_plane_blocks=0, score_variants=0)
+        self.stats = dict.fromkeys(STAT_KEYS, 0)
         if os.path.isdir(path):
             self.meta = json.load(open(os.path.join(path, "meta.json")))
         else:
@@ -423,6 +424,35 @@ class GenotypeStore:
                                                           vmask=vmask, counts=table))
         return table[torch.from_numpy(idx).to(ctx.device)]
 
+    def _plane_rows(self, idx):
+        """the plane rows of the samples idx (store_plan.plane_rows) -> (their number, the plane row of each of idx, on the host)"""
+        scols, rows = plane_rows(idx, self.meta["sc"])
+        return len(scols) * self.meta["sc"], rows
+
+    @staticmethod
+    def _plane_budget(plane_bytes):
+        """the bound of a plane window's buffer (and of ld_prune's table), default 1 GiB"""
+        return DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
+
+    def _window_values(self, x, lo, a, b, words):
+        """x [k, n, ...]: a value per variant of a range that begins at variant lo -> zeros [k, 32 * words, ...] of x's dtype
+        with those of the variants [a, b), a plane window of `words` words, at their bit positions (plane_positions)"""
+        import torch
+        out = torch.zeros((x.shape[0], 32 * words) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
+        out[:, torch.from_numpy(plane_positions(a, b, self._blocksize())).to(x.device)] = x[:, a - lo:b - lo]
+        return out
+
+    def _dosages(self, group, idx, lo, hi, mask, slab_bytes):
+        """standardized_dosages of allele_counts over the samples idx -> (z, used), used ANDed with the variant mask"""
+        z, used = standardized_dosages(self.allele_counts(group, idx, lo, hi, slab_bytes))
+        return z, used if mask is None else used & self._device_bool(mask)
+
+    @staticmethod
+    def _zero_outside(w, mask):
+        """w [..., n, K] with zeros at the variants a bool device tensor [n] leaves out"""
+        import torch
+        return torch.where(mask[:, None], w, torch.zeros_like(w))
+
     def _plane_walk(self, group, idx, lo, hi, n_var, stat_key, slab_bytes, plane_bytes, vmask=None):
         """the genotype planes of the samples idx over the variants [lo, hi) of a group, window by window: yields (a, b,
         words, planes) per window [a, b) of plane_windows (whole Blosc blocks whose plane buffer is at most plane_bytes,
@@ -434,12 +464,12 @@ class GenotypeStore:
         from .device import PLANE_SEL_DTYPE
         ctx = self._context()
         sc, vc, bs = self.meta["sc"], self.meta["vc"], self._blocksize()
-        n_rows = len(plane_rows(idx, sc)[0]) * sc
+        n_rows = self._plane_rows(idx)[0]
         if n_rows == 0:
             return
         vb, wpb = bs // 2, mask_words_per_block(bs)
         planes = None
-        for a, b in plane_windows(lo, hi, bs, n_rows, DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)):
+        for a, b in plane_windows(lo, hi, bs, n_rows, self._plane_budget(plane_bytes)):
             words = ((b - 1) // vb - a // vb + 1) * wpb
             if planes is None or planes.shape[2] != words:
                 planes = None                       # (the last window of a range may be shorter)
@@ -454,14 +484,12 @@ class GenotypeStore:
     def _pair_query(self, who, groups, samples, v_lo, v_hi, variant_mask, bytes_per_pair, max_table_bytes):
         """pair_counts' and grm_sums' (`who`) start: _query, the plane rows, the budget of their tables of bytes_per_pair
         per pair of plane rows -> (idx, queries, n_rows, pick: a table [n_rows, n_rows, ...] -> the samples' part of it)"""
-        import torch
         idx, queries = self._query(who, groups, samples, v_lo, v_hi, variant_mask)
-        scols, rows = plane_rows(idx, self.meta["sc"])
-        n_rows = len(scols) * self.meta["sc"]
+        n_rows, rows = self._plane_rows(idx)
         what = ("a table of {0} x {0} pairs ({{}} bytes) exceeds" if bytes_per_pair == 16 else
                 "tables of {0} x {0} pairs ({{}} bytes) exceed").format(n_rows)
         _table_budget(who, what, n_rows * n_rows * bytes_per_pair, max_table_bytes)
-        rows = torch.from_numpy(rows).to(self._context().device)
+        rows = self._to_device(rows)
         return idx, queries, n_rows, lambda table: table[rows][:, rows].contiguous()
 
     def pair_counts(self, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None,
@@ -511,17 +539,14 @@ class GenotypeStore:
         max_table_bytes (default 2 GiB)."""
         import torch
         idx, queries, n_rows, pick = self._pair_query("grm_sums", groups, samples, v_lo, v_hi, variant_mask, 24, max_table_bytes)
-        ctx, bs = self._context(), self._blocksize()
+        ctx = self._context()
         counts = torch.zeros((n_rows, n_rows, 4), dtype=torch.int32, device=ctx.device)
         sums = torch.zeros((n_rows, n_rows), dtype=torch.float64, device=ctx.device)
         for group, lo, hi, n_var, mask in queries if n_rows else ():
-            z, used = standardized_dosages(self.allele_counts(group, idx, lo, hi, slab_bytes))
-            if mask is not None:
-                used = used & self._device_bool(mask)
+            z, used = self._dosages(group, idx, lo, hi, mask, slab_bytes)
             for a, b, words, planes in self._plane_walk(group, idx, lo, hi, n_var, "grm_plane_blocks", slab_bytes,
                                                         plane_bytes, self._device_mask(used, lo, n_var)):
-                d_z = torch.zeros((3, 32 * words), dtype=torch.float32, device=ctx.device)
-                d_z[:, torch.from_numpy(plane_positions(a, b, bs)).to(ctx.device)] = z[:, a - lo:b - lo]
+                d_z = self._window_values(z, lo, a, b, words)
                 ctx.pair_counts(planes, 0, words, table=counts)
                 ctx.grm(planes, d_z, 0, words, table=sums)
                 self.stats["grm_words"] += words
@@ -576,9 +601,8 @@ class GenotypeStore:
             # the counted variants (offsets into the range) stay on the device; what comes back, in one copy for the whole
             # call, is how many of them lie before each plane window's end
             counted = torch.nonzero(self._device_bool(variant_mask)).reshape(-1)
-            n_rows = len(plane_rows(idx, self.meta["sc"])[0]) * self.meta["sc"]
-            budget = DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
-            windows = plane_windows(lo, hi, bs, n_rows, budget) if n_rows else []
+            n_rows = self._plane_rows(idx)[0]
+            windows = plane_windows(lo, hi, bs, n_rows, self._plane_budget(plane_bytes)) if n_rows else []
             ends = torch.tensor([0] + [b - lo for _, b in windows] + [hi - lo], dtype=torch.int64, device=ctx.device)
             cuts = torch.searchsorted(counted, ends).cpu().tolist()
             n_counted = cuts[-1]
@@ -669,8 +693,7 @@ class GenotypeStore:
         lo, hi, counted, n, rows = self._ld_rows("ld_prune", group, samples, v_lo, v_hi, variant_mask, window, slab_bytes,
                                               plane_bytes)
         ctx = self._context()
-        budget = DEFAULT_PLANE_BYTES if plane_bytes is None else int(plane_bytes)
-        tile = max(budget // (window * 32) - window, LD_MIN_TILE)
+        tile = max(self._plane_budget(plane_bytes) // (window * 32) - window, LD_MIN_TILE)
         carry = carry_keep = table = None
         flags = []
         for new in rows:
@@ -718,12 +741,12 @@ class GenotypeStore:
         if W.dtype != torch.float64 or W.dim() != 2 or W.shape[0] != len(idx) or not 1 <= W.shape[1] <= ASSOC_MAX_COLS:
             raise ValueError(f"assoc_sums: W must be float64 [{len(idx)}, 1 to {ASSOC_MAX_COLS}], not {W.dtype} {list(W.shape)}")
         ctx = self._context()
-        scols, rows = plane_rows(idx, self.meta["sc"])
-        sw = -(-len(scols) * self.meta["sc"] // 32)
+        n_rows, rows = self._plane_rows(idx)
+        sw = -(-n_rows // 32)
         _, _, _, n, vrows = self._variant_rows("assoc_sums", group, idx, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes,
                                                "assoc_plane_blocks")
         d_w = torch.zeros((32 * sw, W.shape[1]), dtype=torch.float64, device=ctx.device)
-        d_w[torch.from_numpy(rows).to(ctx.device)] = W.to(ctx.device)
+        d_w[self._to_device(rows)] = W.to(ctx.device)
         parts = [ctx.assoc_sums(v, d_w) for v in vrows]
         self.stats["assoc_variants"] += n
         # (without a sample there is no row of bits: every sum is 0)
@@ -796,21 +819,19 @@ class GenotypeStore:
         into it and the samples' rows are picked at the end.  No genotype and no dosage is written anywhere."""
         import torch
         idx, queries, weights, K = self._score_weights("score_sums", weights, groups, samples, v_lo, v_hi, variant_mask, "3VK")
-        ctx, bs = self._context(), self._blocksize()
-        scols, rows = plane_rows(idx, self.meta["sc"])
-        table = torch.zeros((len(scols) * self.meta["sc"], K), dtype=torch.float64, device=ctx.device)
+        ctx = self._context()
+        n_rows, rows = self._plane_rows(idx)
+        table = torch.zeros((n_rows, K), dtype=torch.float64, device=ctx.device)
         for group, lo, hi, n_var, mask in queries if len(idx) else ():
             w = self._to_device(weights[group])
             if mask is not None:
                 mask = self._device_bool(mask)
-                w = torch.where(mask[None, :, None], w, torch.zeros_like(w))
+                w = self._zero_outside(w, mask)
             for a, b, words, planes in self._plane_walk(group, idx, lo, hi, n_var, "score_plane_blocks", slab_bytes,
                                                         plane_bytes, self._device_mask(mask, lo, n_var)):
-                d_w = torch.zeros((3, 32 * words, K), dtype=torch.float64, device=ctx.device)
-                d_w[:, torch.from_numpy(plane_positions(a, b, bs)).to(ctx.device)] = w[:, a - lo:b - lo]
-                ctx.score_sums(planes, d_w, 0, words, sums=table)
+                ctx.score_sums(planes, self._window_values(w, lo, a, b, words), 0, words, sums=table)
             self.stats["score_variants"] += hi - lo if mask is None else int(mask.sum())
-        return table[torch.from_numpy(rows).to(ctx.device)]
+        return table[self._to_device(rows)]
 
     def score(self, betas, groups=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
               impute="mean", freq_samples=None):
@@ -836,7 +857,7 @@ class GenotypeStore:
             beta = self._to_device(betas[group])
             if mask is not None:
                 masks[group] = mask = self._device_bool(mask)
-                beta = torch.where(mask[:, None], beta, torch.zeros_like(beta))
+                beta = self._zero_outside(beta, mask)
             weights[group], off, used = score_class_weights(beta, self.allele_counts(group, freq, lo, hi, slab_bytes), impute)
             offset += off
             used_n[group] = int((used if mask is None else used & mask).sum())
@@ -864,10 +885,7 @@ class GenotypeStore:
         ctx = self._context()
         fitted = []
         for group, lo, hi, n_var, mask in queries:
-            z, used = standardized_dosages(self.allele_counts(group, idx, lo, hi, slab_bytes))
-            if mask is not None:
-                used = used & self._device_bool(mask)
-            fitted.append((z, used))
+            fitted.append(self._dosages(group, idx, lo, hi, mask, slab_bytes))
         n_variants = sum(int(used.sum()) for _, used in fitted)
         if n_variants == 0:
             raise ValueError("projection_weights: no variant is used")

@@ -7,7 +7,12 @@ counts.  SGPR counts and SGPR spills move with the compiler's scalar allocation 
 The same for csrc/lz4bits.hip: the plane coder is a chain of inlined phases, and every instantiation of its
 two kernels must keep the registers, spills, scratch and LDS it had as one function body: 72 VGPRs is the last count at
 seven waves per SIMD (64 the last at eight, which the int8 kernel reaches at depths 0 and 1), and 11 248 bytes of LDS keep
-14 workgroups per CU.  That test reads the kernels' metadata only."""
+14 workgroups per CU.  That test reads the kernels' metadata only.
+
+The same for the reductions over bit planes (DESIGN.md §6a "plane reductions"): k_pair_counts and k_ld_counts share the
+popcount tile of csrc/plane_tiles.h, k_assoc_sums and k_score_sums the bit-sum tile's pieces, and each keeps the registers
+and the LDS of its separate copy, without spills or scratch; the kernels of ld.hip that share nothing keep their exact
+counts.  Metadata only."""
 import os
 import re
 import shutil
@@ -38,6 +43,19 @@ for _d in (2, 12):
     BP_BUDGET[("k_lz4_bitplanes_uni", _d, True)] = (70, 0, 0, 11248)
 
 
+# (file, kernel as it stands in the mangled name) -> (VGPRs, static LDS bytes) before the plane tiles were shared; none of
+# them spills or uses scratch
+PLANE_BUDGET = {("pairs", "k_pair_counts"): (118, 33280), ("ld", "k_ld_counts"): (66, 16896)}
+PLANE_BUDGET.update({("assoc", f"k_assoc_sumsILj{_ct}EE"): b
+                     for _ct, b in zip((1, 2, 3, 4), ((72, 16384), (114, 32768), (166, 49152), (184, 65536)))})
+# (k_score_sums<4> has the smaller STEP_UNROLL: score.hip)
+PLANE_BUDGET.update({("score", f"k_score_sumsILj{_ct}EE"): b
+                     for _ct, b in zip((1, 2, 3, 4), ((62, 12288), (86, 24576), (114, 36864), (100, 49152)))})
+# the kernels of ld.hip outside the shared tile -> VGPRs, exactly
+LD_UNTOUCHED = {"k_variant_planes": 25, "k_ld_exceeds": 26}
+LD_UNTOUCHED.update({f"k_ld_walkILi{_nq}EE": v for _nq, v in zip((1, 2, 4, 8, 16), (16, 16, 20, 28, 44))})
+
+
 def gfx950_asm(tmp_path_factory, stem):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -59,6 +77,11 @@ def decode_asm(tmp_path_factory):
 @pytest.fixture(scope="module")
 def lz4bits_asm(tmp_path_factory):
     return gfx950_asm(tmp_path_factory, "lz4bits")
+
+
+@pytest.fixture(scope="module")
+def plane_asm(tmp_path_factory):
+    return {stem: gfx950_asm(tmp_path_factory, stem) for stem in ("pairs", "ld", "assoc", "score")}
 
 
 def kernel_body(asm, name):
@@ -112,3 +135,28 @@ def test_plane_coder_budget(lz4bits_asm, kernel, depth, lazy):
     assert meta["vgpr_spill_count"] <= vgpr_spills, meta["vgpr_spill_count"]
     assert meta["private_segment_fixed_size"] <= scratch, meta["private_segment_fixed_size"]
     assert meta["group_segment_fixed_size"] <= lds, meta["group_segment_fixed_size"]
+
+
+def meta_line(name, meta):
+    return (f"{name}: {meta['vgpr_count']} VGPRs, {meta['sgpr_count']} SGPRs, {meta['sgpr_spill_count']} SGPR spills, "
+            f"{meta['vgpr_spill_count']} VGPR spills, {meta['private_segment_fixed_size']} B scratch, "
+            f"{meta['group_segment_fixed_size']} B static LDS")
+
+
+@pytest.mark.parametrize("stem,kernel", sorted(PLANE_BUDGET))
+def test_plane_reduction_budget(plane_asm, stem, kernel):
+    meta = kernel_meta(plane_asm[stem], kernel)
+    vgprs, lds = PLANE_BUDGET[(stem, kernel)]
+    print(meta_line(kernel, meta))
+    assert meta["vgpr_count"] <= vgprs, meta["vgpr_count"]
+    assert meta["vgpr_spill_count"] == 0, meta["vgpr_spill_count"]
+    assert meta["private_segment_fixed_size"] == 0, meta["private_segment_fixed_size"]
+    assert meta["group_segment_fixed_size"] <= lds, meta["group_segment_fixed_size"]
+
+
+@pytest.mark.parametrize("kernel", sorted(LD_UNTOUCHED))
+def test_ld_kernels_outside_the_tile_keep_their_registers(plane_asm, kernel):
+    meta = kernel_meta(plane_asm["ld"], kernel)
+    print(meta_line(kernel, meta))
+    assert meta["vgpr_count"] == LD_UNTOUCHED[kernel], meta["vgpr_count"]
+    assert (meta["vgpr_spill_count"], meta["private_segment_fixed_size"]) == (0, 0)
