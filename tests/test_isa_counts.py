@@ -12,7 +12,11 @@ seven waves per SIMD (64 the last at eight, which the int8 kernel reaches at dep
 The same for the reductions over bit planes (DESIGN.md §6a "plane reductions"): k_pair_counts and k_ld_counts share the
 popcount tile of csrc/plane_tiles.h, k_assoc_sums and k_score_sums the bit-sum tile's pieces, and each keeps the registers
 and the LDS of its separate copy, without spills or scratch; the kernels of ld.hip that share nothing keep their exact
-counts.  Metadata only."""
+counts.  Metadata only.
+
+The same for csrc/lz4.hip: the byte-wise coder is a driver over inlined phases, and each of the nine
+instantiations of k_lz4_blocks keeps the registers, spills and scratch it had as one function body; three of them sit exactly
+on an occupancy line (72 VGPRs at seven waves per SIMD, 64 at eight).  Its LDS is all dynamic.  Metadata only."""
 import os
 import re
 import shutil
@@ -56,6 +60,13 @@ LD_UNTOUCHED = {"k_variant_planes": 25, "k_ld_exceeds": 26}
 LD_UNTOUCHED.update({f"k_ld_walkILi{_nq}EE": v for _nq, v in zip((1, 2, 4, 8, 16), (16, 16, 20, 28, 44))})
 
 
+# k_lz4_blocks<minimum waves per SIMD, effort (5 run only, 6 hash, 7 long run), from bit planes> -> (VGPRs, spilled VGPRs,
+# scratch bytes) before the stream coder was cut into phases
+LZ4_BUDGET = {(0, 5, False): (76, 0, 0), (8, 5, False): (64, 12, 48), (0, 6, False): (80, 0, 0), (7, 6, False): (72, 3, 12),
+              (0, 7, False): (80, 0, 0), (7, 7, False): (72, 3, 12), (8, 5, True): (64, 19, 76), (7, 6, True): (72, 17, 68),
+              (7, 7, True): (72, 18, 72)}
+
+
 def gfx950_asm(tmp_path_factory, stem):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -77,6 +88,11 @@ def decode_asm(tmp_path_factory):
 @pytest.fixture(scope="module")
 def lz4bits_asm(tmp_path_factory):
     return gfx950_asm(tmp_path_factory, "lz4bits")
+
+
+@pytest.fixture(scope="module")
+def lz4_asm(tmp_path_factory):
+    return gfx950_asm(tmp_path_factory, "lz4")
 
 
 @pytest.fixture(scope="module")
@@ -160,3 +176,14 @@ def test_ld_kernels_outside_the_tile_keep_their_registers(plane_asm, kernel):
     print(meta_line(kernel, meta))
     assert meta["vgpr_count"] == LD_UNTOUCHED[kernel], meta["vgpr_count"]
     assert (meta["vgpr_spill_count"], meta["private_segment_fixed_size"]) == (0, 0)
+
+
+@pytest.mark.parametrize("mw,effort,planes", sorted(LZ4_BUDGET))
+def test_bytewise_coder_budget(lz4_asm, mw, effort, planes):
+    meta = kernel_meta(lz4_asm, f"k_lz4_blocksILi{mw}ELi{effort}ELb{int(planes)}EE")
+    vgprs, vgpr_spills, scratch = LZ4_BUDGET[(mw, effort, planes)]
+    print(meta_line(f"k_lz4_blocks<{mw}, {effort}, {str(planes).lower()}>", meta))
+    assert meta["vgpr_count"] <= vgprs, meta["vgpr_count"]
+    assert meta["vgpr_spill_count"] <= vgpr_spills, meta["vgpr_spill_count"]
+    assert meta["private_segment_fixed_size"] <= scratch, meta["private_segment_fixed_size"]
+    assert meta["group_segment_fixed_size"] == 0, meta["group_segment_fixed_size"]
