@@ -132,71 +132,81 @@ template <bool EXC> __device__ __forceinline__ uint32_t bp_lit(uint32_t b, uint3
     return EXC ? (((x >> k) & 1u) ? 0xF7u : v) : v;
 }
 
+#define BP_FENCE() asm volatile("" ::: "memory")
+// the compiler forgets what it knows about x: what was derived from x in front of this point is worked out again behind it,
+// not carried in registers across (the length fields' extension counts across the size scan of a batch)
+#define BP_FORGET(x) asm volatile("" : "+v"(x))
 #ifndef BP_EMITSKIP
 #define BP_EMITSKIP 0   // development (timing only, invalid streams): 1 no literal bytes, 2 no long literal runs, 3 no sequence bytes at all
 #endif
-// one LZ4 sequence: literals [anchor, start) (bytes generated from the bit map), match (len, off).  OUT is a pointer
-// into the staging area (LDS: ds_write_b8) or, for a window too large for it, into the stream's slot in global memory.
-// TR: out[tr] is a byte nobody reads (staging area only) — lanes with nothing to store write there instead of sitting out
-// an exec-mask region: `if (p) store` costs two scalar instructions and often a branch, `store at (p ? a : tr)` one vector
-// select, and scalar issue is what this kernel runs out of first (probe builds).
+// the (at most two) sequences of one queue entry, in one pass.  The FIRST is the match M (onM) or, without one, the run T:
+// literals [pe, s1) generated from the bit map — the only literal run of an entry that needs it — then (len1, off1).  The
+// SECOND is the run T behind a match: its literals are [E, rs), none or one byte, and that byte is a zero (a run is only
+// queued over >= BP_TMIN zeros up to the next nonzero byte at or behind E, so byte E is none; tools/sim/gapenc_ref.c's
+// last loop, where prev_end = e behind a match): token, the constant 0, the offset bytes 1, 0, and the length.
+// OUT is a pointer into the staging area (LDS: ds_write_b8) or, for a batch too large for it, into the stream's slot in
+// global memory.  TR: out[tr] is a byte nobody reads (staging area only) — lanes with nothing to store write there instead
+// of sitting out an exec-mask region: `if (p) store` costs two scalar instructions and often a branch, `store at
+// (p ? a : tr)` one vector select, and a wave pays for its branch points.
+// at: where the entry's bytes start; pe: where its literals start in the plane; (on1, ll1, ml1 = length - 4, off1): the
+// first sequence; (on2, lit2: it has its one literal, ml2): the second.  The counts of extension bytes are worked out here
+// again, not handed over from the caller's size scan (BP_FORGET there): three multiplies against three registers.
+// (Up to round 8 a batch called bp_put_seq twice, for M and for T, each with its own fetch from the bit map behind its own
+// `any literals?` ballot, its own rare-length branch and its own long-literal loop: profiles/r09_emit_split.txt.)
 template <bool EXC, bool TR, typename OUT>
-__device__ __forceinline__ void bp_put_seq(const uint32_t *bm, const uint32_t *xm, OUT out, uint32_t tr, uint32_t at, uint32_t anchor,
-                                           uint32_t start, uint32_t len, uint32_t off, bool on, uint32_t lane)
+__device__ __forceinline__ void bp_put_entry(const uint32_t *bm, const uint32_t *xm, OUT out, uint32_t tr, uint32_t at, uint32_t pe, bool on1, uint32_t ll1,
+                                             uint32_t ml1, uint32_t off1, bool on2, bool lit2, uint32_t ml2, uint32_t lane)
 {
-    const uint32_t ll = on ? start - anchor : 0u, ml = len - 4u;
-    const uint32_t llx = on ? bp_len_ext(ll) : 0u, mlx = on ? bp_len_ext(ml) : 0u;
     if (BP_EMITSKIP == 3) return;
-    // Straight-line byte stores for what nearly every sequence has — token, at most one extension byte per length,
-    // offset — and ONE wave-uniform branch for lengths that need more (>= 270).
-    const uint32_t lit = at + 1u + llx, o = lit + ll;
-    const uint32_t tok = ((ll < 15u ? ll : 15u) << 4) | (ml < 15u ? ml : 15u);
-    if (TR) {
-        out[on ? at : tr] = (uint8_t)tok;
-        out[on ? o : tr] = (uint8_t)(off & 0xFFu);
-        out[on ? o + 1u : tr] = (uint8_t)(off >> 8);
-        out[llx != 0u ? at + 1u : tr] = (uint8_t)(llx == 1u ? ll - 15u : 255u);
-        out[mlx != 0u ? o + 2u : tr] = (uint8_t)(mlx == 1u ? ml - 15u : 255u);
-    } else {
-        if (on) {
-            out[at] = (uint8_t)tok;
-            out[o] = (uint8_t)(off & 0xFFu);
-            out[o + 1u] = (uint8_t)(off >> 8);
-        }
-        if (llx != 0u) out[at + 1u] = (uint8_t)(llx == 1u ? ll - 15u : 255u);
-        if (mlx != 0u) out[o + 2u] = (uint8_t)(mlx == 1u ? ml - 15u : 255u);
-    }
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(llx > 1u || mlx > 1u) != 0ull, 0)) {   // (wave-uniform, rare)
-        uint32_t r = ll - 15u - 255u;
+    const uint32_t llx1 = bp_len_ext(ll1), mlx1 = on1 ? bp_len_ext(ml1) : 0u, mlx2 = on2 ? bp_len_ext(ml2) : 0u, ll2 = lit2 ? 1u : 0u;
+    auto put = [&](bool p, uint32_t a, uint32_t v) {
+        if (TR) out[p ? a : tr] = (uint8_t)v;
+        else if (p) out[a] = (uint8_t)v;
+    };
+    const uint32_t lit = at + 1u + llx1, o1 = lit + ll1;       // first sequence: its literals, its offset
+    const uint32_t at2 = o1 + 2u + mlx1, o2 = at2 + 1u + ll2;  // second sequence: its token, its offset
+    // ONE wave-uniform branch, over both sequences, for lengths that need more than one extension byte (>= 270) ...
+    // (in front of the straight-line stores and the second sequence in front of the first: every value dies with its last
+    // store, the literals' three stay — the other way round the kernel takes 72 registers instead of 70)
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64((llx1 > 1u) | (mlx1 > 1u) | (mlx2 > 1u)) != 0ull, 0)) {   // (rare)
+        auto more = [&](uint32_t a, uint32_t v, uint32_t nx) {   // extension bytes 1 .. nx - 1 of the length v, at a + 1 ...
+            uint32_t r = v - 15u - 255u;
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (uint32_t k = 1; k < llx; ++k) {
-            out[at + 1u + k] = (uint8_t)(k + 1u == llx ? r : 255u);
-            r -= 255u;
-        }
-        r = ml - 15u - 255u;
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-        for (uint32_t k = 1; k < mlx; ++k) {
-            out[o + 2u + k] = (uint8_t)(k + 1u == mlx ? r : 255u);
-            r -= 255u;
-        }
+            for (uint32_t k = 1; k < nx; ++k) {
+                out[a + k] = (uint8_t)(k + 1u == nx ? r : 255u);
+                r -= 255u;
+            }
+        };
+        more(at + 1u, ll1, llx1);
+        more(o1 + 2u, ml1, mlx1);
+        more(o2 + 2u, ml2, mlx2);
     }
-    // literals.  Most runs are 1-3 bytes ("1", "1 0"): up to 6 go out as byte stores of the owning lane.
-    // Longer runs (the literals of all the ones in between that code nothing pile up in front of the next sequence)
-    // are written by the whole wave, one run at a time — a lockstep per-lane loop would run max(ll) times for all.
-    if (BP_EMITSKIP != 1 && __builtin_amdgcn_ballot_w64(ll != 0u) != 0ull) {
-        const uint32_t b = bp_bits(bm, anchor), x = EXC ? bp_bits(xm, anchor) : 0u;
-        const uint32_t nsm = ll <= 6u ? ll : 0u;   // bytes this lane stores itself
+    // ... and straight-line byte stores for what nearly every sequence has: token, at most one extension byte per length,
+    // offset
+    put(on2, at2, (ll2 << 4) | (ml2 < 15u ? ml2 : 15u));
+    put(lit2, at2 + 1u, 0u);
+    put(on2, o2, 1u);
+    put(on2, o2 + 1u, 0u);
+    put(mlx2 != 0u, o2 + 2u, mlx2 == 1u ? ml2 - 15u : 255u);
+    put(on1, at, ((ll1 < 15u ? ll1 : 15u) << 4) | (ml1 < 15u ? ml1 : 15u));
+    put(llx1 != 0u, at + 1u, llx1 == 1u ? ll1 - 15u : 255u);
+    put(on1, o1, off1 & 0xFFu);
+    put(on1, o1 + 1u, off1 >> 8);
+    put(mlx1 != 0u, o1 + 2u, mlx1 == 1u ? ml1 - 15u : 255u);
+    // Most literal runs are 1-3 bytes ("1", "1 0"): up to 6 go out as byte stores of the owning lane.  Longer runs (the
+    // literals of all the ones in between that code nothing pile up in front of the next sequence) are written by the whole
+    // wave, one run at a time — a lockstep per-lane loop would run max(ll) times for all.
+    if (BP_EMITSKIP != 1) {
+        const uint32_t b = bp_bits(bm, pe), x = EXC ? bp_bits(xm, pe) : 0u;   // the entry's ONE fetch from the bit map
+        const uint32_t nsm = ll1 <= 6u ? ll1 : 0u;   // bytes this lane stores itself
 #pragma unroll
-        for (uint32_t k = 0; k < 6u; ++k) {
-            if (TR) out[k < nsm ? lit + k : tr] = (uint8_t)bp_lit<EXC>(b, x, k);
-            else if (k < nsm) out[lit + k] = (uint8_t)bp_lit<EXC>(b, x, k);
-        }
-        unsigned long long big = BP_EMITSKIP == 2 ? 0ull : __builtin_amdgcn_ballot_w64(ll > 6u);
+        for (uint32_t k = 0; k < 6u; ++k) put(k < nsm, lit + k, bp_lit<EXC>(b, x, k));
+        unsigned long long big = BP_EMITSKIP == 2 ? 0ull : __builtin_amdgcn_ballot_w64(ll1 > 6u);
         while (big != 0ull) {
             const int l = __builtin_ctzll(big);
             big &= big - 1ull;
-            const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)ll, l);
-            const uint32_t src = (uint32_t)__builtin_amdgcn_readlane((int)anchor, l);
+            const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)ll1, l);
+            const uint32_t src = (uint32_t)__builtin_amdgcn_readlane((int)pe, l);
             const uint32_t dst = (uint32_t)__builtin_amdgcn_readlane((int)lit, l);
             for (uint32_t k = lane; k < n; k += 64u) out[dst + k] = (uint8_t)bp_lit<EXC>(bp_bits(bm, src + k), EXC ? bp_bits(xm, src + k) : 0u, 0u);
         }
@@ -215,7 +225,6 @@ __device__ __forceinline__ void bp_flush(const uint8_t *stage, uint8_t *__restri
     if (t < n) dst[t] = stage[t];
 }
 
-#define BP_FENCE() asm volatile("" ::: "memory")
 // layout + emission of the first n (<= 64) of the qn queued coded ones, one per lane, in stream order (n < qn unless the
 // stream ends with entry n - 1: every entry sees its successor).  The end of a coded one's last sequence is where the
 // next one's literals start (pe): the neighbouring lane's value, no scan.
@@ -254,14 +263,17 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     const uint32_t F = (onM || onT) ? F0 : Fp;
     uint32_t pe = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)F, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
     pe = lane ? pe : prev_end;
-    uint32_t ms = msr > pe ? msr : pe;                                 // the previous sequence may have taken some of the zeros in front
-    ms = onM ? ms : 0u;
-    const uint32_t llM = onM ? ms - pe : 0u, lenM = E - ms;
-    const uint32_t pe2 = onM ? E : pe;
-    const uint32_t llT = onT ? rs - pe2 : 0u, lenT = re - rs;
-    const uint32_t szM = onM ? 3u + bp_len_ext(llM) + llM + bp_len_ext(lenM - 4u) : 0u;
-    const uint32_t szT = onT ? 3u + bp_len_ext(llT) + llT + bp_len_ext(lenT - 4u) : 0u;
-    const uint32_t sincl = wave_scan_sum_dpp(szM + szT, lane);
+    prev_end = (uint32_t)__builtin_amdgcn_readlane((int)F, (int)(n - 1u));   // (handed on here: F is not carried across the stores)
+    const uint32_t ms = msr > pe ? msr : pe;                           // the previous sequence may have taken some of the zeros in front
+    // the entry's first sequence: M, or T alone (its literals start at pe either way); its second: T behind M
+    const bool on1 = onM | onT, on2 = onM & onT;
+    const uint32_t s1 = onM ? ms : rs, e1 = onM ? E : re;
+    uint32_t ll1 = on1 ? s1 - pe : 0u, ml1 = e1 - s1 - 4u;
+    const uint32_t off1 = onM ? off : 1u;
+    const bool lit2 = on2 & (rs != E);
+    uint32_t ml2 = re - rs - 4u;
+    const uint32_t sz = (on1 ? 3u + bp_len_ext(ll1) + ll1 + bp_len_ext(ml1) : 0u) + (on2 ? 3u + (lit2 ? 1u : 0u) + bp_len_ext(ml2) : 0u);
+    const uint32_t sincl = wave_scan_sum_dpp(sz, lane);
     const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)sincl, 63);
     BP_MARK("sizes_done");
     // the batch's bytes go to the staging area; what is staged leaves in coalesced dwords when the next batch would not
@@ -271,17 +283,17 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
         gop += sop;
         sop = 0;
     }
-    const uint32_t at = sincl - (szM + szT);
+    const uint32_t at = sincl - sz;
+    BP_FORGET(ll1);
+    BP_FORGET(ml1);
+    BP_FORGET(ml2);
     if (__builtin_expect(total > BpCfg<EXC>::STAGE, 0)) {   // (wave-uniform, rare: a batch with hundreds of literals)
-        bp_put_seq<EXC, false>(bm, xm, out + gop, 0u, at, pe, ms, lenM, off, onM, lane);
-        bp_put_seq<EXC, false>(bm, xm, out + gop, 0u, at + szM, pe2, rs, lenT, 1u, onT, lane);
+        bp_put_entry<EXC, false>(bm, xm, out + gop, 0u, at, pe, on1, ll1, ml1, off1, on2, lit2, ml2, lane);
         gop += total;
     } else {
-        bp_put_seq<EXC, true>(bm, xm, S.stage + sop, BpCfg<EXC>::STAGE - sop, at, pe, ms, lenM, off, onM, lane);
-        bp_put_seq<EXC, true>(bm, xm, S.stage + sop, BpCfg<EXC>::STAGE - sop, at + szM, pe2, rs, lenT, 1u, onT, lane);
+        bp_put_entry<EXC, true>(bm, xm, S.stage + sop, BpCfg<EXC>::STAGE - sop, at, pe, on1, ll1, ml1, off1, on2, lit2, ml2, lane);
         sop += total;
     }
-    prev_end = (uint32_t)__builtin_amdgcn_readlane((int)F, (int)(n - 1u));
     return BpOut{prev_end, gop, sop};
 }
 
@@ -689,12 +701,13 @@ __device__ __forceinline__ BpQueued bp_queue_and_drain(LDS &S, const uint32_t *b
     const unsigned long long wm = __builtin_amdgcn_ballot_w64(want);
     const uint32_t nw = (uint32_t)__builtin_popcountll(wm);
     const bool last = jw + 64 >= (int)m;
+    const uint2 ent = bp_entry(E, (uint32_t)(q - (int)nb), onM, onT, rs, re, q1 - c1);   // (packed here: two registers live across a make-room batch)
     // one call site for the batch code: first make room if this window's coded ones would not fit (rare), then queue
     // them, then drain whole batches (everything at the end)
     for (int phase = 0; phase < 2; ++phase) {
         if (phase == 1) {
             const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
-            S.queue[want ? slot : (uint32_t)BP_QCAP] = bp_entry(E, (uint32_t)(q - (int)nb), onM, onT, rs, re, q1 - c1);
+            S.queue[want ? slot : (uint32_t)BP_QCAP] = ent;
             qn += nw;
             BP_MARK("queued");
         }
