@@ -1,6 +1,9 @@
 """-m gpu: the genetic relationship matrix.  hhgt_grm (64 x 64 tiles of pairs on the f32-input MFMA, plane bits expanded to
 weights in LDS) against numpy with weights for which float32 is exact — one tile, the tile edge, off-diagonal and edge
-tiles; rows below, at and across the ends of a chain; word sub-ranges; calls accumulating; the mirror write —;
+tiles; rows below, at and across the ends of a chain; word sub-ranges; calls accumulating; the mirror write —; against
+np_grm_chain of tests/test_grm_stats.py, the header's arithmetic restated on the CPU, where float32 rounds — the restart of
+the chain every GRM_SPAN words from w_lo, exact; the chain bit for bit —; with standardised dosages of rare variants within
+S_BOUND at up to eight spans; overlapping planes (HET before HOM_REF before HOM_ALT);
 GenotypeStore.grm_sums / grm / pca, VCFH5Reader.genetic_relationship / principal_components and the grm CLI on converter
 output against the synthetic generator's own genotypes in float64, within the bound of a float32 chain of 32 * GRM_SPAN
 steps; two populations told apart by the first principal component."""
@@ -10,11 +13,14 @@ import torch
 
 from haplohyped_varawareml_amd import synth
 from haplohyped_varawareml_amd._lib import HhgtError
-from haplohyped_varawareml_amd.store import NSNP, GenotypeStore, grm_from_sums, plan_planes, top_eigenpairs
+from haplohyped_varawareml_amd.store import (NSNP, GenotypeStore, grm_from_sums, plan_planes, standardized_dosages,
+                                             top_eigenpairs)
 from tests.test_gpu_allele_counts import CHROM3, S3, V3, cohort  # noqa: F401 (cohort: fixture)
 from tests.test_gpu_pair_counts import PICK, random_planes
 from tests.test_gpu_sample_counts import np_variant_mask, two_groups  # noqa: F401 (two_groups: fixture)
-from tests.test_grm_stats import S_BOUND, np_counts, np_grm_sums, np_z
+from tests.test_grm_stats import (CHAIN_SHAPES, S_BOUND, SPAN_SUM, SPAN_W, chain_case, chain_ranges, chain_reference, np_counts,
+                                  np_exact_ranges, np_grm_sums, np_plane_values, np_z, span_case, span_signs, span_split_sums,
+                                  span_splits)
 
 pytestmark = pytest.mark.gpu
 
@@ -77,6 +83,120 @@ def test_grm_kernel_is_exact_on_quarters(ctx, n_rows, row_words):
     assert np.array_equal(pre.cpu().numpy(), pattern + 2 * want)
     assert not ctx.grm(torch.zeros_like(planes), dz).any()
     assert not ctx.grm(planes, torch.zeros_like(dz)).any()
+
+
+def on_device(ctx, planes, z):
+    return torch.from_numpy(planes.view(np.int32)).to(ctx.device), torch.from_numpy(z).to(ctx.device)
+
+
+def grm_calls(ctx, planes, dz, ranges):
+    """one table, one call per range"""
+    table = None
+    for a, b in ranges:
+        table = ctx.grm(planes, dz, a, b, table=table)
+    return table.cpu().numpy()
+
+
+SPAN_ROWS = [dict(n_rows=2, plus=(0, 1), minus=()), dict(n_rows=66, plus=(0, 64), minus=(63, 65)),
+             dict(n_rows=130, plus=(0, 64, 129), minus=(63, 65))]
+
+
+@pytest.mark.parametrize("w_lo", [0, 5])
+@pytest.mark.parametrize("rows", SPAN_ROWS, ids=lambda r: str(r["n_rows"]))
+def test_grm_chain_restarts_every_span_from_w_lo(ctx, rows, w_lo):
+    """the span case of tests/test_grm_stats.py: 4096 positions of 64 * 64 followed by 4096 of 2^-6 * 2^-6 sum to 2^24 + 1
+    only if the first chain is put aside before the second begins, GRM_SPAN words from w_lo.  Guards an `in_span == SPAN`
+    flush that never fires (2^24) and spans counted from word 0 (0.96 short at w_lo = 5).  At 66 and 130 rows the carrying
+    rows sit on both sides of the tile edges, so the diagonal, off-diagonal and edge tiles all hold such pairs, of both signs;
+    the other rows have no bit.  Then the same range in several calls into one table, where the second call's spans count
+    from its own w_lo, against the emulator given the same calls.  Exact: nothing here depends on how the instruction takes
+    its two positions."""
+    host, z = span_case(w_lo, **rows)
+    planes, dz = on_device(ctx, host, z)
+    s = span_signs(**rows)
+    want = SPAN_SUM * np.outer(s, s)
+    assert (want != 0).sum() == len(rows["plus"] + rows["minus"]) ** 2
+    got = ctx.grm(planes, dz, w_lo, SPAN_W).cpu().numpy()
+    assert np.array_equal(got, want), (got[got != want][:4], want[got != want][:4])
+    for ranges, (seq, two) in zip(span_splits(w_lo), span_split_sums(w_lo)):
+        assert seq == two                                                             # (whatever the instruction does)
+        want = seq * np.outer(s, s)                                                   # (rounding is symmetric in the sign)
+        got = grm_calls(ctx, planes, dz, ranges)
+        assert np.array_equal(got, want), (ranges, got[got != want][:4], want[got != want][:4])
+
+
+@pytest.mark.parametrize("n_rows,row_words", CHAIN_SHAPES)
+def test_grm_kernel_is_the_sequential_chain_bit_for_bit(ctx, n_rows, row_words):
+    """the arithmetic contract of include/hhgt.h on weights that round at almost every step (tests/test_grm_stats.py shows
+    that at least half of the entries differ from the exact sum and from the paired chain): the table equals
+    np_grm_chain(paired=False) — one rounding per position, in ascending order, restarts every GRM_SPAN words from w_lo —
+    in every bit, is symmetric in every bit, and is the same on a second call.  (On an MI355X the table differed from the
+    sequential chain in no entry, from the paired chain in 76 % to 90 % of them: v_mfma_f32_32x32x2_f32 rounds after each
+    of its two positions, as the header says.)"""
+    host, z = chain_case(n_rows, row_words)
+    planes, dz = on_device(ctx, host, z)
+    for words in chain_ranges(row_words):
+        table = ctx.grm(planes, dz, *words)
+        got = table.cpu().numpy()
+        seq, two = chain_reference(n_rows, row_words, words, False), chain_reference(n_rows, row_words, words, True)
+        exact = np_exact_ranges(np_plane_values(host, z), [words])
+        print(f"grm chain {n_rows} x {row_words} {words}: differs from the sequential chain in {(got != seq).mean():.3f} of "
+              f"the entries, from the paired chain in {(got != two).mean():.3f}, from the exact sum in {(got != exact).mean():.3f}")
+        assert np.array_equal(got.view(np.uint64), seq.view(np.uint64)), words
+        assert np.array_equal(got.view(np.uint64), got.T.copy().view(np.uint64)), words
+        assert torch.equal(ctx.grm(planes, dz, *words), table), words
+
+
+def rare_cohort(n, V):
+    """int8 [n, V, 2] with allele frequencies log-uniform from a singleton (1 / 2n) to 1/2, 1 % of the alleles missing:
+    standardised values up to sqrt(n) at the rare variants, products with a heavy tail"""
+    rng = np.random.default_rng(V)
+    p = np.exp(rng.uniform(np.log(0.5 / n), np.log(0.5), V))
+    g = (rng.random((n, V, 2)) < p[None, :, None]).astype(np.int8)
+    g[rng.random((n, V, 2)) < 0.01] = -9
+    return g
+
+
+@pytest.mark.parametrize("row_words", [1, 128, 129, 1024])
+def test_grm_kernel_with_real_weights_is_within_the_bound(ctx, row_words):
+    """the header's bound at the kernel: float32 z of standardized_dosages, 130 rows, rows of one position word, one span,
+    one span and a word, eight spans — every entry within S_BOUND * T of the float64 product of the same float32 values"""
+    from tests.test_gpu_pair_counts import np_classes, pack_bits
+    n = 130
+    g = rare_cohort(n, 32 * row_words)
+    z, used = standardized_dosages(np_counts(g))
+    host = pack_bits(np_classes(g))
+    assert host.shape == (3, n, row_words) and used.any() and (row_words == 1 or np.abs(z).max() > 10.0)
+    x = np_plane_values(host, z).astype(np.float64)
+    want, total = x @ x.T, np.abs(x) @ np.abs(x).T
+    got = ctx.grm(*on_device(ctx, host, z)).cpu().numpy()
+    err, bound = np.abs(got - want), S_BOUND * total
+    print(f"grm kernel, {row_words} words: largest error / bound = {(err / np.maximum(bound, 1e-300)).max():.3g}")
+    assert (err <= bound).all()
+    assert np.array_equal(got.view(np.uint64), got.T.copy().view(np.uint64))
+
+
+def test_grm_kernel_overlapping_planes_het_then_ref_then_alt(ctx):
+    """the overlap rule of include/hhgt.h: a position with bits in several planes takes the HET weight before the HOM_REF
+    weight before the HOM_ALT weight.  Every combination of the three bits, many times in every row, with quarter weights
+    that differ between the classes at every position: exact.  Guards another order of the select chain, and planes whose
+    weights add (hhgt_score_sums' rule, which np_grm_words restates: it must give another table here)."""
+    n_rows, row_words = 65, 5
+    rng = np.random.default_rng(65005)
+    combo = rng.integers(0, 8, (n_rows, 32 * row_words))                              # bit 0 HET, 1 HOM_REF, 2 HOM_ALT
+    assert min(int((combo[r] == c).sum()) for r in range(n_rows) for c in range(1, 8)) >= 5
+    host = np.stack([np.packbits((combo >> k & 1).astype(bool), axis=1, bitorder="little").view(np.uint32) for k in range(3)])
+    z = np.ascontiguousarray(rng.permuted(np.tile(np.r_[-8:0, 1:9], (32 * row_words, 1)), axis=1)[:, :3].T / 4.0, np.float32)
+    assert (z[0] != z[1]).all() and (z[0] != z[2]).all() and (z[1] != z[2]).all() and (z != 0).all()
+    x = np.where(combo & 1, z[1], np.where(combo & 2, z[0], np.where(combo & 4, z[2], 0.0))).astype(np.float64)
+    assert np.array_equal(x, np_plane_values(host, z))
+    want = x @ x.T
+    assert not np.array_equal(np_grm_words(host, z, 0, row_words), want)
+    planes, dz = on_device(ctx, host, z)
+    got = ctx.grm(planes, dz).cpu().numpy()
+    assert np.array_equal(got, want), np.nonzero(got != want)
+    for a, b in ((1, 4), (4, 5)):
+        assert np.array_equal(ctx.grm(planes, dz, a, b).cpu().numpy(), x[:, 32 * a:32 * b] @ x[:, 32 * a:32 * b].T)
 
 
 def test_grm_kernel_arguments(ctx):

@@ -1,4 +1,5 @@
-"""-m gpu: LD between nearby variants.  hhgt_variant_planes (the bit transposition) against numpy unpackbits / transpose;
+"""-m gpu: LD between nearby variants.  hhgt_variant_planes (the bit transposition) against numpy unpackbits / transpose, in
+one tile of 256 plane rows and in up to three, between sentinel words;
 hhgt_ld_counts (32 x 32 tiles of the band, popcounts of ANDs) against the numpy restatement on random planes — tile edges,
 windows across one and several tiles, calls accumulating, the samples split over two buffers; hhgt_ld_prune (decisions, then
 the walk of one wave) against the numpy walk, in one tile and in three with carry-in; GenotypeStore.ld_counts / ld_r2 /
@@ -69,6 +70,38 @@ def test_variant_planes_match_numpy(ctx, n_rows, row_words):
                                                                   dtype=torch.int32, device=ctx.device))
     with pytest.raises(ValueError):
         ctx.variant_planes(d, 0, W, vplanes=torch.zeros((3, 32 * W, 99), dtype=torch.int32, device=ctx.device))
+
+
+GUARD = 1024        # sentinel words on either side of the output
+
+
+@pytest.mark.parametrize("n_rows", [255, 256, 257, 288, 289, 511, 513, 600])
+@pytest.mark.parametrize("row_words", [1, 9, 17])
+def test_variant_planes_past_one_row_tile(ctx, n_rows, row_words):
+    """k_variant_planes beyond its tile of 256 plane rows x 8 words: all four waves with rows, blockIdx.y up to 2, a last
+    tile of one row, of one output word (288: `s0 + 1 < sw` cuts the upper half of a wave's mask in the second tile) and of
+    an odd number of them; word ranges of one and of several tiles of 8 words, from a start that is no multiple of 8,
+    ending inside a tile.  Guards a wave or a row tile left out or stored to another's words, and a store past the output:
+    the output is a view between two stretches of sentinel words that must come back as they were."""
+    rng = np.random.default_rng(n_rows * 100 + row_words)
+    cls = rng.integers(0, 5, (n_rows, row_words * 32))                       # 3, 4: not complete; classes are disjoint
+    planes = np.stack([np.packbits(cls == k, axis=1, bitorder="little").view(np.uint32) for k in range(3)])
+    d = to_dev(ctx, planes)
+    W, sw = row_words, -(-n_rows // 32)
+    ranges = {(0, W), (W - 1, W)} | ({(3, min(W, 12)), (2, 7), (1, W - 2)} if W >= 9 else set())
+    for w_lo, w_hi in sorted(ranges):
+        size = 3 * 32 * (w_hi - w_lo) * sw
+        buf = torch.full((GUARD + size + GUARD,), 0x5a5a5a5a, dtype=torch.int32, device=ctx.device)
+        out = buf[GUARD:GUARD + size].view(3, 32 * (w_hi - w_lo), sw)
+        out.fill_(-1)                                                        # pre-filled with ones
+        assert ctx.variant_planes(d, w_lo, w_hi, vplanes=out) is out
+        host = as_u32(buf)
+        assert (host[:GUARD] == 0x5a5a5a5a).all() and (host[GUARD + size:] == 0x5a5a5a5a).all(), (w_lo, w_hi)
+        got, want = host[GUARD:GUARD + size].reshape(3, 32 * (w_hi - w_lo), sw), np_transpose(planes, w_lo, w_hi)
+        assert np.array_equal(got, want), (w_lo, w_hi, np.argwhere(got != want)[:4])
+        assert np.array_equal(got[1], np_transpose(np.stack([planes[0] | planes[1] | planes[2]] * 3), w_lo, w_hi)[0])
+        if n_rows % 32:
+            assert not (got[:, :, -1] >> (n_rows % 32)).any()               # bits past n_rows
 
 
 # ---- hhgt_ld_counts --------------------------------------------------------------------------------------------------------
