@@ -58,6 +58,12 @@ class PlaneSel(C.Structure):   # hhgt_plane_sel
                 ("hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class GatherSel(C.Structure):  # hhgt_gather_sel
+    _fields_ = [("src_ptr", C.c_uint64), ("src_bytes", C.c_uint64), ("row_mask", C.c_uint64), ("out_row", C.c_uint64),
+                ("mask_word", C.c_uint64), ("out_col", C.c_uint64), ("part", C.c_uint32), ("lo", C.c_uint32),
+                ("hi", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class EncodeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "n_lines", "n_records", "n_kept", "n_drop_region", "n_drop_filter", "n_haploid_padded",
@@ -120,6 +126,8 @@ PROTOTYPES = {
     "hhgt_count_alleles": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _u64, _pu64, _vp]),
     "hhgt_count_samples": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _u64, _vp, _u64, _pu64, _vp]),
     "hhgt_genotype_planes": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _u64, _vp, _u64, _u64, _pu64, _vp]),
+    "hhgt_gather_calls": (_i32, [_vp, _vp, _u32, _u32, _u32, _i32, _i32, _vp, _u64, _vp, _u64, _vp, _i32, _vp, _u64, _u64, _u64,
+                                 _pu64, _vp]),
     "hhgt_pair_counts": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),
     "hhgt_grm": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp, _vp]),
     "hhgt_variant_planes": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _vp]),

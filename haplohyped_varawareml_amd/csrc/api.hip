@@ -1179,8 +1179,8 @@ extern "C" int hhgt_decompress_blocks(hhgt_ctx *c, const hhgt_block_sel *d_sel, 
     });
 }
 
-// the geometry the row-walk kernels (hhgt_count_alleles, hhgt_count_samples, hhgt_genotype_planes) serve; `who` prefixes
-// the message
+// the geometry the row-walk kernels (hhgt_count_alleles, hhgt_count_samples, hhgt_genotype_planes, hhgt_gather_calls) serve;
+// `who` prefixes the message
 static int check_row_kernel_args(const char *who, uint32_t sc, uint32_t vc, int typesize, int blocksize)
 {
     if (typesize != 2) {
@@ -1200,7 +1200,7 @@ static int check_row_kernel_args(const char *who, uint32_t sc, uint32_t vc, int 
     return HHGT_OK;
 }
 
-// what the three entry points do alike: the null checks (`out`: the output's name in the message), the geometry, the
+// what the row kernels' entry points do alike: the null checks (`out`: the output's name in the message), the geometry, the
 // device, *n_bad, nothing to do without selections, the launch under the bad-counter protocol
 template <typename Launch>
 static int run_row_kernel(const char *who, const char *out, hhgt_ctx *c, const void *d_sel, uint32_t n_sel, const void *d_out,
@@ -1245,6 +1245,34 @@ extern "C" int hhgt_genotype_planes(hhgt_ctx *c, const hhgt_plane_sel *d_sel, ui
                           [&](unsigned long long *d_bad, hipStream_t st) {
                               return launch_genotype_planes(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_planes,
                                                             n_rows, row_words, d_bad, st);
+                          });
+}
+
+extern "C" int hhgt_gather_calls(hhgt_ctx *c, const hhgt_gather_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
+                                 int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
+                                 const uint32_t *d_row_map, uint64_t n_map, const void *d_values, int elem_bytes,
+                                 void *d_out, uint64_t n_rows, uint64_t n_cols, uint64_t row_stride, uint64_t *n_bad,
+                                 void *stream)
+{
+    const bool table = d_values != nullptr;
+    if (table ? (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) : elem_bytes != 2) {
+        hhgt_set_error("gather_calls: elem_bytes %d (%s)", elem_bytes, table ? "1, 2, 4 or 8" : "2 without a table: an allele pair");
+        return HHGT_ERR_ARG;
+    }
+    if (row_stride < n_cols) {
+        hhgt_set_error("gather_calls: row_stride %llu below n_cols %llu", (unsigned long long)row_stride, (unsigned long long)n_cols);
+        return HHGT_ERR_ARG;
+    }
+    const uintptr_t off = (uintptr_t)elem_bytes - 1u;
+    if ((reinterpret_cast<uintptr_t>(d_out) & off) || (reinterpret_cast<uintptr_t>(d_values) & off)) {
+        hhgt_set_error("gather_calls: %s not aligned to elem_bytes %d", (reinterpret_cast<uintptr_t>(d_out) & off) ? "d_out" : "d_values",
+                       elem_bytes);
+        return HHGT_ERR_ARG;
+    }
+    return run_row_kernel("gather_calls", "output", c, d_sel, n_sel, d_out, sc, vc, typesize, blocksize, n_bad, stream,
+                          [&](unsigned long long *d_bad, hipStream_t st) {
+                              return launch_gather_calls(d_sel, n_sel, sc, vc, blocksize, d_vmask, vmask_words, d_row_map, n_map,
+                                                         d_values, elem_bytes, d_out, n_rows, n_cols, row_stride, d_bad, st);
                           });
 }
 

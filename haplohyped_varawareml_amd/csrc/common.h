@@ -392,6 +392,10 @@ int launch_count_samples(const hhgt_sample_sel *d_sel, uint32_t n_sel, uint32_t 
 int launch_genotype_planes(const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
                            const uint32_t *d_vmask, uint64_t vmask_words, uint32_t *d_planes, uint64_t n_rows,
                            uint64_t row_words, unsigned long long *d_bad, hipStream_t st);
+int launch_gather_calls(const hhgt_gather_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
+                        const uint32_t *d_vmask, uint64_t vmask_words, const uint32_t *d_row_map, uint64_t n_map,
+                        const void *d_values, int elem_bytes, void *d_out, uint64_t n_rows, uint64_t n_cols,
+                        uint64_t row_stride, unsigned long long *d_bad, hipStream_t st);
 // pairs.hip
 int launch_pair_counts(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
                        uint32_t *d_table, hipStream_t st);

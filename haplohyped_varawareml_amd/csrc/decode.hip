@@ -368,13 +368,13 @@ __global__ __launch_bounds__(1024) void k_decode_sel(const hhgt_block_sel *__res
     unshuffle_range(smem, h.doshuffle, typesize, nstreams, bsize, sstride, lo, hi, out);
 }
 
-// ---- the row walk of the three query kernels (hhgt_count_alleles, hhgt_count_samples, hhgt_genotype_planes) -------------
+// ---- the row walk of the four query kernels (hhgt_count_alleles, hhgt_count_samples, hhgt_genotype_planes, hhgt_gather_calls)
 //
 // Each runs one selection per workgroup (grid = n_sel; block = 64 * nwaves and dynamic LDS as decode_geometry says for
 // typesize 2: two waves): a chunk, the Blosc block `part` of its sample rows, the rows of row_mask and the variants [lo, hi)
 // of that block.  Thread t owns variants [g, g + 16) of the block for g = 16 (t + k blockDim), k = 0, 1 (blockDim * 32 >=
 // blocksize / 2 for every block size served), over every selected row: stage_row leaves the row's block in LDS, for_calls16
-// hands the thread its 2 x 16 calls four at a time.  What a kernel does with four calls (count4, tally4, planes4), at the
+// hands the thread its 2 x 16 calls four at a time.  What a kernel does with four calls (count4, tally4, planes4, classes4), at the
 // end of a row and with its totals is its own; so are the checks of its outputs.
 
 // a bad selection counts once, whatever made it bad
@@ -793,6 +793,151 @@ __global__ __launch_bounds__(128, 8) void k_genotype_planes(const hhgt_plane_sel
     }
 }
 
+// ---- selected variants as dense columns straight out of LDS (hhgt_gather_calls) -----------------------------------------
+
+// the classes of 4 calls (a, b as classify4 takes them), one per byte: 0 HOM_REF, 1 HET, 2 HOM_ALT, 3 not complete
+// (planes4's definitions)
+__device__ __forceinline__ uint32_t classes4(uint32_t a, uint32_t b)
+{
+    const uint32_t H = 0x80808080u, L7 = 0x7F7F7F7Fu;
+    const uint32_t xa = a ^ 0x01010101u, xb = b ^ 0x01010101u;
+    const uint32_t za = ~(((a & L7) + L7) | a) & H, zb = ~(((b & L7) + L7) | b) & H;        // 0x80 where the allele is 0
+    const uint32_t ea = ~(((xa & L7) + L7) | xa) & H, eb = ~(((xb & L7) + L7) | xb) & H;    // 0x80 where the allele is 1
+    const uint32_t het = (za & eb) | (ea & zb), alt = ea & eb;
+    const uint32_t nc = ~((za & zb) | het | alt) & H;
+    return ((het | nc) >> 7) | ((alt | nc) >> 6);
+}
+
+// dst[i] = get(i), i < n, by the whole workgroup, consecutive lanes on consecutive elements; elements narrower than a dword
+// go out as whole dwords wherever dst's alignment allows (the same bytes either way)
+template <typename T, typename Get>
+__device__ __forceinline__ void store_elements(T *dst, uint32_t n, Get get)
+{
+    constexpr uint32_t PER = sizeof(T) < 4u ? 4u / (uint32_t)sizeof(T) : 1u;
+    if constexpr (PER == 1u) {
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = get(i);
+        return;
+    }
+    const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u);      // (a multiple of sizeof(T))
+    uint32_t head = mis ? (4u - mis) / (uint32_t)sizeof(T) : 0u;
+    if (head > n) head = n;
+    const uint32_t body = (n - head) / PER, tail = head + body * PER;
+    if (threadIdx.x < head) dst[threadIdx.x] = get(threadIdx.x);
+    uint32_t *d32 = reinterpret_cast<uint32_t *>(dst + head);
+    for (uint32_t q = threadIdx.x; q < body; q += blockDim.x) {
+        uint32_t v = 0u;
+#pragma unroll
+        for (uint32_t e = 0; e < PER; ++e) v |= (uint32_t)get(head + q * PER + e) << (8u * (uint32_t)sizeof(T) * e);
+        d32[q] = v;
+    }
+    if (tail + threadIdx.x < n) dst[tail + threadIdx.x] = get(tail + threadIdx.x);    // (fewer than PER <= blockDim)
+}
+
+// a row's gathered calls, their classes in `codes` (LDS), as elements of T: element j = values[class j][col0 + j]
+template <typename T>
+__device__ __forceinline__ void store_classes(void *out, uint64_t first, const void *values, uint64_t n_cols, uint64_t col0,
+                                              const uint8_t *codes, uint32_t n)
+{
+    const T *tab = static_cast<const T *>(values) + col0;
+    store_elements(static_cast<T *>(out) + first, n, [&](uint32_t j) { return tab[(uint64_t)codes[j] * n_cols + j]; });
+}
+
+// The row walk above under expand_take's mask, which also says where a thread's calls go: the gathered variants before
+// the thread's own (its popcounts through one workgroup scan, once per selection: pass 0's 16-variant groups come before pass
+// 1's).  Per selected row the thread classifies its calls (classes4) and puts the gathered ones' classes — raw mode: their
+// allele pairs — at those places of a row buffer in LDS behind the decoder's area; after a barrier consecutive lanes turn
+// consecutive entries into output elements (table mode: one opaque element of d_values per entry, read through L2) with
+// plain vector stores: an (output row, column) belongs to one workgroup.  Dynamic LDS: decode_geometry's, rounded up to 16,
+// plus blocksize / 2 entries of one byte (table) or two (raw): 12.5 KiB at 8 KiB blocks, twelve workgroups a CU — six waves a
+// SIMD, which the second launch bound asks of the registers too (80 VGPRs, no spill; unbounded the compiler takes 109 and
+// four waves, measured 20 % slower).  The table is not staged in LDS: that was measured slower.
+__global__ __launch_bounds__(128, 6) void k_gather_calls(const hhgt_gather_sel *__restrict__ sel, uint32_t sc, uint32_t vc,
+                                                      uint32_t blocksize, uint32_t sstride, const uint32_t *__restrict__ vmask,
+                                                      uint64_t vmask_words, const uint32_t *__restrict__ row_map, uint64_t n_map,
+                                                      const void *__restrict__ values, uint32_t elem_bytes, void *out,
+                                                      uint64_t n_rows, uint64_t n_cols, uint64_t row_stride,
+                                                      unsigned long long *n_bad)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    __shared__ uint32_t s_bad;
+    __shared__ uint32_t s_tot[2];      // per wave: gathered variants of pass 0 | pass 1 << 16
+    __shared__ uint32_t s_past;        // a selected row lies past the output
+    __shared__ uint64_t s_row[64];     // the output row of every selected chunk row
+    const uint32_t nwaves = blockDim.x >> 6;
+    const uint32_t wave = uni(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const hhgt_gather_sel *s = sel + blockIdx.x;
+    const uint64_t out_row = s->out_row, mask_word = s->mask_word, out_col = s->out_col;
+    if (threadIdx.x == 0) s_past = 0u;
+    RowWalk W;
+    bool ok = W.init(global_chunk(s->src_ptr), s, sc, vc, blocksize, &s_bad);      // (holds the barrier behind s_past = 0)
+    const uint64_t mask = W.mask;
+    const uint32_t top = mask ? 63u - (uint32_t)__builtin_clzll(mask) : 0u;      // the highest selected row
+    const uint64_t n_in = row_map != nullptr ? n_map : n_rows;                    // what out_row + r must stay below
+    ok = ok && nwaves <= 2u && (mask == 0ull || (out_row < n_in && top < n_in - out_row)) &&
+         (vmask == nullptr || (mask_word <= vmask_words && W.mwords <= vmask_words - mask_word));
+    if (!ok) return bad_selection(n_bad);
+    uint32_t take[2][4];
+    expand_take(W.lo, W.hi, vmask, mask_word, take);
+    // where the thread's gathered variants go, and how many the selection gathers
+    uint32_t mine = 0u;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) mine += (uint32_t)__builtin_popcount(take[k][w]) << (16 * k);
+    uint32_t incl = mine;
+#pragma unroll
+    for (uint32_t d = 1u; d < 64u; d <<= 1) {
+        const uint32_t below = (uint32_t)__shfl_up((int)incl, d, 64);
+        if (lane >= d) incl += below;
+    }
+    if (lane == 63u) s_tot[wave] = incl;
+    if (threadIdx.x < 64u && ((mask >> threadIdx.x) & 1ull)) {
+        const uint64_t R = row_map != nullptr ? (uint64_t)row_map[out_row + threadIdx.x] : out_row + threadIdx.x;
+        s_row[threadIdx.x] = R;
+        if (R >= n_rows) atomicOr(&s_past, 1u);
+    }
+    __syncthreads();
+    const uint32_t tot0 = s_tot[0], tot1 = nwaves > 1u ? s_tot[1] : 0u;
+    const uint32_t n0 = (tot0 & 0xFFFFu) + (tot1 & 0xFFFFu), total = n0 + (tot0 >> 16) + (tot1 >> 16);
+    const uint32_t before = wave ? tot0 : 0u, excl = incl - mine;
+    const uint32_t place[2] = {(before & 0xFFFFu) + (excl & 0xFFFFu), n0 + (before >> 16) + (excl >> 16)};
+    if (s_past != 0u || out_col > n_cols || total > n_cols - out_col) return bad_selection(n_bad);
+    if (total == 0u) return;
+    const bool raw = values == nullptr;
+    uint8_t *codes = smem + (((size_t)nwaves * sstride + 16u + 15u) & ~(size_t)15u);      // the row buffer
+    uint16_t *pairs = reinterpret_cast<uint16_t *>(codes);
+    uint32_t mlo = uni((uint32_t)mask), mhi = uni((uint32_t)(mask >> 32));
+    while ((mlo | mhi) != 0u) {
+        const uint32_t r = next_row(mlo, mhi);
+        if (!stage_row(W, r, smem, sstride, &s_bad)) return bad_selection(n_bad);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            uint32_t A[4] = {0u, 0u, 0u, 0u}, B[4] = {0u, 0u, 0u, 0u};
+            for_calls16(W, smem, sstride, (uint32_t)k, [&](uint32_t a, uint32_t b, int w) { A[w] = a, B[w] = b; });
+            uint32_t pos = place[k];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t cw = classes4(A[w], B[w]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!((take[k][w] >> (8 * j + 7)) & 1u)) continue;
+                    if (raw) pairs[pos] = (uint16_t)(((A[w] >> (8 * j)) & 0xFFu) | (((B[w] >> (8 * j)) & 0xFFu) << 8));
+                    else codes[pos] = (uint8_t)(cw >> (8 * j));
+                    ++pos;
+                }
+            }
+        }
+        __syncthreads();   // the row buffer is whole; the block is read before the next row goes over it
+        const uint64_t first = s_row[r] * row_stride + out_col;
+        if (raw) store_elements(static_cast<uint16_t *>(out) + first, total, [&](uint32_t j) { return pairs[j]; });
+        else if (elem_bytes == 1u) store_classes<uint8_t>(out, first, values, n_cols, out_col, codes, total);
+        else if (elem_bytes == 2u) store_classes<uint16_t>(out, first, values, n_cols, out_col, codes, total);
+        else if (elem_bytes == 4u) store_classes<uint32_t>(out, first, values, n_cols, out_col, codes, total);
+        else store_classes<uint64_t>(out, first, values, n_cols, out_col, codes, total);
+        // (the next row's stage_row holds a barrier before anybody writes the row buffer again)
+    }
+}
+
 // launch shape shared by both kernels: waves per workgroup, the per-stream LDS stride, dynamic LDS bytes
 static int decode_geometry(int typesize, int blocksize, uint32_t *nwaves, uint32_t *sstride, size_t *lds)
 {
@@ -907,4 +1052,19 @@ int launch_genotype_planes(const hhgt_plane_sel *d_sel, uint32_t n_sel, uint32_t
 {
     return launch_row_kernel("genotype_planes", k_genotype_planes, 0, st, d_sel, n_sel, sc, vc, blocksize, d_vmask,
                              vmask_words, d_planes, n_rows, row_words, d_bad);
+}
+
+int launch_gather_calls(const hhgt_gather_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc, int blocksize,
+                        const uint32_t *d_vmask, uint64_t vmask_words, const uint32_t *d_row_map, uint64_t n_map,
+                        const void *d_values, int elem_bytes, void *d_out, uint64_t n_rows, uint64_t n_cols,
+                        uint64_t row_stride, unsigned long long *d_bad, hipStream_t st)
+{
+    uint32_t nwaves, sstride;
+    size_t lds;
+    if (int rc = decode_geometry(2, blocksize, &nwaves, &sstride, &lds)) return rc;
+    // the row buffer behind the decoder's area: one entry per variant of a block, a class byte or an allele pair
+    const size_t row_buffer = (size_t)(blocksize / 2) * (d_values ? 1u : 2u);
+    return launch_row_kernel("gather_calls", k_gather_calls, ((lds + 15u) & ~(size_t)15u) + row_buffer, st, d_sel, n_sel, sc,
+                             vc, blocksize, d_vmask, vmask_words, d_row_map, n_map, d_values, (uint32_t)elem_bytes, d_out,
+                             n_rows, n_cols, row_stride, d_bad);
 }

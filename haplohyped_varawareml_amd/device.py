@@ -25,6 +25,11 @@ SEL_DTYPE = np.dtype(_lib.BlockSel)            # hhgt_block_sel
 COUNT_SEL_DTYPE = np.dtype(_lib.CountSel)      # hhgt_count_sel
 SAMPLE_SEL_DTYPE = np.dtype(_lib.SampleSel)    # hhgt_sample_sel
 PLANE_SEL_DTYPE = np.dtype(_lib.PlaneSel)      # hhgt_plane_sel
+GATHER_SEL_DTYPE = np.dtype(_lib.GatherSel)    # hhgt_gather_sel
+
+# the element types of a gather_calls table: the kernel copies them as opaque bytes
+GATHER_DTYPES = (torch.int8, torch.uint8, torch.int16, torch.float16, torch.bfloat16, torch.int32, torch.float32,
+                 torch.int64, torch.float64)
 
 
 def make_ring_layout(n_samples, ring_cols, sc=DEFAULT_SC, vc=DEFAULT_VC):
@@ -509,6 +514,56 @@ class Context:
             vmask, words = self._vmask_arg(vmask)
             return self._row_kernel(self.lib.hhgt_genotype_planes, sel, sc, vc, typesize, blocksize, planes,
                                     _ptr(vmask), words, _ptr_if_any(planes), n_rows, row_words)
+
+    def gather_calls(self, sel, sc, vc, values=None, out=None, n_rows=None, n_cols=None, row_map=None, vmask=None,
+                     typesize=DEFAULT_TYPESIZE, blocksize=None):
+        """selected variants as dense columns (hhgt_gather_calls): sel is a numpy structured array of GATHER_SEL_DTYPE (a
+        sample selection plus out_col; out_row indexes row_map), uploaded in one copy; vmask as count_samples takes it.
+        values: the class table, a contiguous device tensor [4, n_cols] of one of GATHER_DTYPES (rows HOM_REF, HET,
+        HOM_ALT, not complete), copied element by element as opaque bytes; None: raw mode, the element is the call's two
+        int8 alleles.  row_map: None (chunk row r of a selection goes to output row out_row + r) or the output row of
+        every entry, a numpy array or an int32 / uint32 device tensor.  out: [n_rows, row_stride] of the table's dtype, or
+        [n_rows, row_stride, 2] int8 in raw mode — dense rows (the last stride 1), a row stride of at least n_cols
+        (n_cols: the table's, or by default the width of `out`), any element-aligned address —, of which only the owned
+        elements are written; default: zeros just large enough for the selections.  -> (out, n_bad)"""
+        sel, blocksize = self._row_sel(sel, GATHER_SEL_DTYPE, vc, blocksize)
+        n, raw = len(sel), values is None
+        with torch.cuda.device(self.device):
+            if not raw:
+                if (not torch.is_tensor(values) or values.dtype not in GATHER_DTYPES or values.dim() != 2 or values.shape[0] != 4
+                        or not values.is_contiguous() or not values.is_cuda):
+                    raise ValueError("values: a contiguous device tensor [4, n_cols] of an 8, 16, 32 or 64 bit type")
+                if n_cols is not None and int(n_cols) != values.shape[1]:
+                    raise ValueError(f"n_cols {int(n_cols)} with a table of {values.shape[1]} columns")
+                n_cols = int(values.shape[1])
+            if row_map is not None:
+                if not torch.is_tensor(row_map):
+                    row_map = torch.from_numpy(np.ascontiguousarray(row_map, dtype=np.uint32).view(np.int32))
+                row_map = row_map.to(self.device)
+                if row_map.dtype not in (torch.int32, torch.uint32) or row_map.dim() != 1 or not row_map.is_contiguous():
+                    raise ValueError("row_map: contiguous uint32 output rows")
+            dtype, tail = (torch.int8, (2,)) if raw else (values.dtype, ())
+            if out is None:
+                if n_rows is None:
+                    n_rows = (0 if not n else int(sel["out_row"].max()) + int(sc) if row_map is None else
+                              int(row_map.view(torch.int32).max()) + 1 if row_map.numel() else 0)
+                if n_cols is None:
+                    n_cols = int((sel["out_col"] + sel["hi"] - sel["lo"]).max()) if n else 0
+                out = torch.zeros((int(n_rows), int(n_cols)) + tail, dtype=dtype, device=self.device)
+            want = f"out: a {str(dtype).split('.')[1]} device tensor [n_rows, row_stride{', 2' if raw else ''}] with dense rows"
+            if (not torch.is_tensor(out) or out.dtype != dtype or out.dim() != 2 + len(tail) or tuple(out.shape[2:]) != tail
+                    or not out.is_cuda or (n_rows is not None and int(n_rows) != out.shape[0])):
+                raise ValueError(want)
+            unit = 2 if raw else 1                  # elements of `out` per element of the kernel
+            n_cols = int(out.shape[1]) if n_cols is None else int(n_cols)
+            stride = out.stride(0) // unit if out.shape[0] > 1 else int(out.shape[1])
+            dense = out.stride(-1) == 1 and (not raw or out.stride(1) == 2) and (out.shape[0] <= 1 or out.stride(0) % unit == 0)
+            if not dense or n_cols > out.shape[1] or stride < out.shape[1]:
+                raise ValueError(want + f" of at least {n_cols} columns")
+            vmask, words = self._vmask_arg(vmask)
+            return self._row_kernel(self.lib.hhgt_gather_calls, sel, sc, vc, typesize, blocksize, out, _ptr(vmask), words,
+                                    _ptr(row_map), 0 if row_map is None else row_map.numel(), _ptr(values),
+                                    2 if raw else values.element_size(), _ptr_if_any(out), out.shape[0], n_cols, stride)
 
     def pair_counts(self, planes, w_lo=0, w_hi=None, table=None):
         """pairwise counts (hhgt_pair_counts) over the words [w_lo, w_hi) (default: all) of genotype planes [3, n, words]:

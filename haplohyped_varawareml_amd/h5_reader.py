@@ -17,7 +17,9 @@ host); association(phenotypes, covariates, chromosomes, donor_ids, min_maf, pcs,
 scan of every variant against one or more phenotypes (GenotypeStore.assoc); polygenic_scores(variants, weights, ...) the
 per-donor sums of per-allele effects over listed variants (GenotypeStore.score), and project_components(k,
 train_donor_ids, donor_ids, ...) principal components fitted on some donors and the projection of others onto them
-(GenotypeStore.project).  The reference has no such queries."""
+(GenotypeStore.project); feature_matrix(chromosomes, donor_ids, min_maf, ld_window, ..., train_donor_ids) donors x selected
+variants as a model-ready device tensor with its variant records (GenotypeStore.feature_matrix).  The reference has no such
+queries."""
 import numpy as np
 
 from .store import (AC, AN, ASSOC_BETA, ASSOC_P, ASSOC_SE, ASSOC_T, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
@@ -203,6 +205,30 @@ class VCFH5Reader:
         masks = self._variant_masks(names, who, min_maf=min_maf, ld_window=ld_window, ld_r2=ld_r2)
         sums, nsnp = self.store.grm_sums(names, who, variant_mask=masks or None)
         return donors, grm_from_sums(sums, nsnp).cpu().numpy(), nsnp.cpu().numpy()
+
+    def feature_matrix(self, chromosomes=None, donor_ids=None, min_maf=None, ld_window=None, ld_r2=0.2, coding="dosage",
+                       dtype=None, impute="mean", train_donor_ids=None):
+        """donors x selected variants as a model-ready tensor -> (donors, X, variant records): X is
+        GenotypeStore.feature_matrix's device tensor (coding, dtype and impute mean what they mean there), row i for
+        donor_ids[i] in the order asked (default: every sample, store order), its columns the variants of chr_{N} for N in
+        chromosomes (one name or a list; None: every group) that pass min_maf and, with ld_window, the LD pruning, as in
+        genetic_relationship; the records, host numpy, one per column: chrom, start (0-based), ref, alt.  With
+        train_donor_ids the masks AND the frequencies behind the imputed and standardised values are computed over the
+        training donors only, so held-out donors leak into neither; without it, over the donors asked for."""
+        names, donors, who = self._cohort(chromosomes, donor_ids)
+        train = who if train_donor_ids is None else self._cohort(chromosomes, list(train_donor_ids))[2]
+        masks = self._variant_masks(names, train, min_maf=min_maf, ld_window=ld_window, ld_r2=ld_r2)
+        X, columns = self.store.feature_matrix(names, who, variant_mask=masks or None, coding=coding, dtype=dtype,
+                                               impute=impute, freq_samples=train)
+        tables = {g: self.store.variants(g) for g, _ in columns}
+        width = max([len(r[1].encode()) for t in tables.values() for r in t[3]] + [1])
+        dtype = [("chrom", f"S{width}"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10")]
+        parts = []
+        for g, at in columns:
+            rec = np.zeros(int(at.numel()), dtype=dtype)
+            self._variant_columns(rec, tables[g], width, at=at.cpu().numpy())
+            parts.append(rec)
+        return donors, X, np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)
 
     def principal_components(self, k=10, chromosomes=None, donor_ids=None, min_maf=None, ld_window=None, ld_r2=0.2):
         """the k largest principal components of genetic_relationship (same arguments after k) -> (records, values):

@@ -1,6 +1,7 @@
 """The host-side planning of GenotypeStore's queries, numpy only (no device, no torch unless a torch mask is packed): what
 a query's arguments mean (query_args), and which chunks, Blosc blocks, rows and variant ranges a query touches and where
-their results go (plan_windows for reads, plan_rows and its three public faces for the row kernels, the plane layout)."""
+their results go (plan_windows for reads, plan_rows and its three public faces for the row kernels, plan_gather on top of
+it for the feature matrix, the plane layout)."""
 import numpy as np
 
 # one selection of the window planner: request q, chunk (vcol, scol), Blosc block, decoded bytes [lo, hi) of the block,
@@ -11,6 +12,8 @@ PLAN_DTYPE = np.dtype([("req", np.int64), ("vcol", np.int64), ("scol", np.int64)
 # default budgets of GenotypeStore.pair_counts: the plane buffer of one window of variants, and the largest table it makes
 DEFAULT_PLANE_BYTES = 1 << 30
 MAX_PAIR_TABLE_BYTES = 2 << 30
+# the largest matrix GenotypeStore.feature_matrix makes by default
+MAX_FEATURE_BYTES = 4 << 30
 
 # the smallest tile of GenotypeStore.ld_prune, in counted variants
 LD_MIN_TILE = 64
@@ -183,6 +186,35 @@ def plan_planes(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize
     block B of the group (B = v // (blocksize / 2)) at word (B - block0) * mask_words_per_block(blocksize) of a plane row;
     block0: the first block of the plane buffer (default: the block of v_lo)."""
     return plan_rows(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize, "plane", block0)
+
+
+# one selection of plan_gather: the row planner's fields, and the output column of the block's first gathered variant
+GATHER_PLAN_DTYPE = np.dtype(ROW_PLAN_DTYPE.descr + [("out_col", np.int64)])
+
+
+def plan_gather(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, block_counts, blocksize=None, col0=0):
+    """the selections of hhgt_gather_calls: plan_sample_counts' cuts of (samples, [v_lo, v_hi)) — the same chunks, blocks,
+    row masks, ranges and mask_word, in the same order; out_row = scol * sc, the entry of chunk row 0 in a row map of
+    ceil(n_samples / sc) * sc entries — with the output columns of every block: block_counts[k] is the number of
+    gathered variants in the k-th Blosc block (of blocksize / 2 variants) the range touches, and the block's first gathered
+    variant owns column out_col = col0 + the sum of the counts of the blocks before it.  A block that gathers nothing gives
+    no selection.  ValueError if block_counts is not one count per touched block, or a count exceeds its block's part of
+    the range."""
+    plan = plan_rows(sample_idx, n_samples, sc, vc, n_variants, v_lo, v_hi, blocksize, "sample")
+    v_lo, v_hi = int(v_lo), int(v_hi)
+    vb = (default_blocksize(vc) if blocksize is None else int(blocksize)) // 2
+    counts = np.asarray(block_counts, dtype=np.int64).reshape(-1)
+    seg = np.arange(v_lo // vb, (v_hi - 1) // vb + 1, dtype=np.int64) if v_hi > v_lo else np.zeros(0, np.int64)
+    room = np.minimum(v_hi, (seg + 1) * vb) - np.maximum(v_lo, seg * vb)
+    if counts.size != seg.size or (counts < 0).any() or (counts > room).any():
+        raise ValueError(f"plan_gather: {counts.size} block counts for the {seg.size} blocks of [{v_lo}, {v_hi}), each at most its block's variants")
+    first = int(col0) + np.cumsum(counts) - counts
+    out = np.zeros(len(plan), GATHER_PLAN_DTYPE)
+    for f in ROW_PLAN_DTYPE.names:
+        out[f] = plan[f]
+    k = plan["vcol"] * (int(vc) // vb) + plan["part"].astype(np.int64) - (v_lo // vb)        # the selection's touched block
+    out["out_col"] = first[k] if len(plan) else 0
+    return out[counts[k] > 0] if len(plan) else out
 
 
 def pack_variant_mask(mask, v_lo, n_variants, vc, blocksize):

@@ -238,6 +238,55 @@ def projection_class_weights(z, loadings):
     return f64(z)[:, :, None] * f64(loadings)[None, :, :]
 
 
+def _is_integer_dtype(dtype):
+    """a numpy or torch dtype (or its name) is an integer type"""
+    return "int" in str(dtype)
+
+
+def call_class_values(counts, coding, impute, dtype=None):
+    """the value of each call class at every variant of a feature matrix -> (values float64 [4, V], used bool [V]):
+    counts is an allele count table [V, 4] of the frequency samples (numpy or torch; columns AN, AC, ...), the classes
+    those of hhgt_gather_calls — 0 HOM_REF, 1 HET, 2 HOM_ALT, 3 not complete.  coding = "dosage": classes 0..2 take 0, 1,
+    2; with impute = "mean" class 3 takes 2p, p = AC / AN, and a variant is used iff AN > 0 (an unused one: 0); with
+    impute = "missing" class 3 takes the missing marker, every variant is used and the counts are not looked at.  coding =
+    "standardized": classes 0..2 are standardized_dosages' z (float32 values, widened) and `used` is that function's;
+    class 3 is 0.0, the mean, with "mean" and the missing marker with "missing".  The missing marker is NaN here; the cast
+    (cast_class_values) makes it -1 for an integer dtype.  dtype (optional: the type the values will be cast to) only
+    checks: "mean" with an integer dtype is a ValueError, for neither 2p nor z is an integer.  ValueError for another
+    coding or impute."""
+    if coding not in ("dosage", "standardized") or impute not in ("mean", "missing"):
+        raise ValueError(f"call_class_values: coding {coding!r} (\"dosage\" or \"standardized\"), impute {impute!r} (\"mean\" or \"missing\")")
+    if impute == "mean" and dtype is not None and _is_integer_dtype(dtype):
+        raise ValueError(f"call_class_values: impute \"mean\" needs a float dtype, not {dtype} (an imputed value is no integer)")
+    if len(counts.shape) != 2 or counts.shape[1] != 4:
+        raise ValueError(f"call_class_values: counts {list(counts.shape)} ([V, 4])")
+    i64, f64 = _ops(counts)[:2]
+    stack = _math(counts)[4]
+    t = i64(counts)
+    an, ac = t[:, AN], t[:, AC]
+    zero = f64(an) * 0.0
+    missing = zero + float("nan")
+    if coding == "dosage":
+        if impute == "missing":
+            return stack([zero, zero + 1.0, zero + 2.0, missing]), an == an
+        used = an > 0
+        # (a variant that is not used gets AN = 1 here, so that nothing divides by 0)
+        two_p = 2.0 * (f64(ac * used) / f64(an * used + (~used) * 1))
+        return stack([zero, zero + 1.0, zero + 2.0, two_p]), used
+    z, used = standardized_dosages(counts)
+    z = f64(z)
+    return stack([z[0], z[1], z[2], zero if impute == "mean" else missing]), used
+
+
+def cast_class_values(values, dtype):
+    """call_class_values' table (a torch tensor) as elements of a torch dtype: torch's .to(dtype), the missing marker (NaN)
+    made -1 first for an integer dtype"""
+    import torch
+    if _is_integer_dtype(dtype):
+        values = torch.where(torch.isnan(values), torch.full_like(values, -1.0), values)
+    return values.to(dtype)
+
+
 # columns of the statistics table of assoc_from_sums (and GenotypeStore.assoc), per variant and phenotype
 ASSOC_BETA, ASSOC_SE, ASSOC_T, ASSOC_P = 0, 1, 2, 3
 # planes of GenotypeStore.assoc_sums (and of hhgt_assoc_sums' sums), in the kernel's order: HET calls, complete calls (both

@@ -340,7 +340,50 @@ int hhgt_genotype_planes(hhgt_ctx *ctx, const hhgt_plane_sel *d_sel, uint32_t n_
                          int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
                          uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t *n_bad, void *stream);
 
-/* hhgt_pair_counts reduces the words [w_lo, w_hi) of every row of such planes to d_table, uint32 [n_rows][n_rows][4]
+/* Selected variants as dense columns: hhgt_gather_calls decodes as hhgt_genotype_planes does and writes one element per
+ * (selected row, gathered variant) of a selection into a row-major matrix d_out of n_rows rows and n_cols columns, rows
+ * row_stride >= n_cols elements apart (so one group's columns can be written into a wider matrix).  A selection names a
+ * chunk, a block `part` of its rows, the rows and the variants [lo, hi) of that block as a hhgt_sample_sel does.
+ * Gathered variants and columns: the gathered variants of a selection are those v in [lo, hi) whose bit is set in the
+ * block's words of d_vmask (the mask layout and mask_word of hhgt_count_samples); with d_vmask == NULL all of [lo, hi).
+ * They are taken in ascending order, and the j-th one owns output column out_col + j.
+ * Rows: selected chunk row r goes to output row R = d_row_map[out_row + r] (d_row_map: uint32 [n_map], device); with
+ * d_row_map == NULL, R = out_row + r.
+ * Call classes, by the definitions of hhgt_genotype_planes: 0 HOM_REF (0,0), 1 HET, 2 HOM_ALT (1,1), 3 not complete (a
+ * negative allele or an allele >= 2).
+ * Table mode (d_values != NULL): elem_bytes is 1, 2, 4 or 8, d_values is [4][n_cols] elements aligned to elem_bytes, and
+ * the element at d_out + (R * row_stride + c) * elem_bytes receives d_values[class][c].  Elements are copied as opaque
+ * bytes — no arithmetic, no rounding, NaN payloads survive —, so the caller chooses the dtype by how it fills the table:
+ * an int8 dosage, float16 / bfloat16 / float32 / float64 standardised values and a dominance coding are the same kernel.
+ * Raw mode (d_values == NULL): elem_bytes must be 2 and the element is the call itself, the two int8 alleles (h0, h1),
+ * phase kept.
+ * d_out needs only elem_bytes alignment; the kernel stores wider where alignment allows, the same bytes.  Plain vector
+ * stores, no atomics: two selections of one call or stream must not own the same (output row, column) — the caller's
+ * error, as for hhgt_genotype_planes.  Every element a good selection owns is written, nothing else in d_out is touched.
+ * *n_bad (host, optional, syncs) = the number of bad selections, by the rules of hhgt_count_samples plus: out_row + (the
+ * highest selected row) >= n_map (with a map), a selected row whose R >= n_rows, out_col + (number gathered) > n_cols.  A
+ * selection bad for its header or bounds writes nothing; one whose stream turns out corrupt midway may leave unspecified
+ * values in its own elements only; a selection with no gathered variant or no row is good and writes nothing.
+ * HHGT_ERR_ARG for another elem_bytes, row_stride < n_cols, a misaligned d_out or d_values, and the geometries
+ * hhgt_count_samples refuses. */
+typedef struct {
+    uint64_t src_ptr;    /* device address of one framed chunk (either header format)                         */
+    uint64_t src_bytes;  /* its stored size                                                                   */
+    uint64_t row_mask;   /* sample rows of the chunk to gather: bit r = row r                                 */
+    uint64_t out_row;    /* entry of d_row_map of chunk row 0 (row r uses entry out_row + r)                  */
+    uint64_t mask_word;  /* first uint32 word of this block's bits in d_vmask (ignored when d_vmask is NULL)  */
+    uint64_t out_col;    /* output column of the block's first gathered variant                               */
+    uint32_t part;       /* Blosc block of each row (0 .. vc * 2 / blocksize - 1)                             */
+    uint32_t lo, hi;     /* variants [lo, hi) of that block, lo < hi <= blocksize / 2                         */
+    uint32_t reserved;   /* 0 */
+} hhgt_gather_sel;
+int hhgt_gather_calls(hhgt_ctx *ctx, const hhgt_gather_sel *d_sel, uint32_t n_sel, uint32_t sc, uint32_t vc,
+                      int typesize, int blocksize, const uint32_t *d_vmask, uint64_t vmask_words,
+                      const uint32_t *d_row_map, uint64_t n_map, const void *d_values, int elem_bytes,
+                      void *d_out, uint64_t n_rows, uint64_t n_cols, uint64_t row_stride,
+                      uint64_t *n_bad, void *stream);
+
+/* hhgt_pair_counts reduces the words [w_lo, w_hi) of every row of hhgt_genotype_planes' planes to d_table, uint32 [n_rows][n_rows][4]
  * (16-byte aligned), both triangles: for the ordered pair of plane rows (i, j), over the variants whose bits it reads,
  *     d_table[i][j][0] NSNP    both calls complete
  *     d_table[i][j][1] HETHET  both HET
