@@ -1394,6 +1394,29 @@ extern "C" int hhgt_assoc_sums(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t 
                             [&](hipStream_t st) { return launch_assoc_sums(d_vplanes, n_var, sw, d_w, n_cols, d_sums, st); });
 }
 
+// hhgt_logistic_fit: the columns of X, the pointers its work needs (the records with a variant, everything else with a variant
+// and a word), their alignment
+extern "C" int hhgt_logistic_fit(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const uint32_t *d_valid,
+                                 const double *d_x, uint32_t q, const double *d_y, const double *d_beta0, double *d_out,
+                                 void *stream)
+{
+    if (q < 1u || q > HHGT_LOGIT_MAX_COLS - 1u) {
+        hhgt_set_error("logistic_fit: %u columns of X (1 to %u)", q, HHGT_LOGIT_MAX_COLS - 1u);
+        return HHGT_ERR_ARG;
+    }
+    const bool reads = n_var && sw;
+    TRY(check_not_null("logistic_fit", c,
+                       !n_var ? nullptr : !d_out ? "records" : !reads ? nullptr : !d_vplanes ? "variant planes"
+                       : !d_valid ? "valid bits" : !d_x ? "X" : !d_y ? "y" : !d_beta0 ? "beta0" : nullptr));
+    if (off_alignment(d_x, 8) || off_alignment(d_y, 8) || off_alignment(d_beta0, 8) || off_alignment(d_out, 8)) {
+        hhgt_set_error("logistic_fit: X, y, beta0 and the records must be 8-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    return launch_on_device(c, stream, HHGT_STAGE_ASSOC, n_var != 0, [&](hipStream_t st) {
+        return launch_logistic_fit(d_vplanes, n_var, sw, d_valid, d_x, q, d_y, d_beta0, d_out, st);
+    });
+}
+
 // hhgt_score_sums: a plane kernel with columns — their number and the rows' length checked here, the rest with the family;
 // the partial sums' workspace grows in the call, like hhgt_ld_prune's; both launches run under one timer of HHGT_STAGE_ASSOC
 extern "C" int hhgt_score_sums(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo,

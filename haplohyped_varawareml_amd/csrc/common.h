@@ -413,6 +413,9 @@ int launch_ld_walk(const uint64_t *d_bits, uint64_t n_var, uint32_t window, uint
 // assoc.hip
 int launch_assoc_sums(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
                       double *d_sums, hipStream_t st);
+// logistic.hip
+int launch_logistic_fit(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const uint32_t *d_valid, const double *d_x,
+                        uint32_t q, const double *d_y, const double *d_beta0, double *d_out, hipStream_t st);
 // score.hip
 uint64_t score_spans(uint64_t n_words);   // spans of a range of n_words words: rows of d_part
 int launch_score_sums(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi, const double *d_w,

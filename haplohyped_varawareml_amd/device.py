@@ -634,6 +634,28 @@ class Context:
                                            _stream()))
         return sums
 
+    def logistic_fit(self, vplanes, valid, X, y, beta0, out=None):
+        """per-variant logistic fits (hhgt_logistic_fit) over variant-major planes [3, n, sw]: valid is an int32 tensor [sw]
+        with a bit for every position that is a listed sample, X float64 [32 * sw, q] (1 <= q <= 14), y float64 [32 * sw]
+        of 0 / 1 and beta0 float64 [q] the null fit, all contiguous and on the planes' device; out, a float64 tensor
+        [n, 9], gets the record of every variant (store.REC_*: include/hhgt.h names the fields) — every entry written
+        (default: a new tensor), on the current stream.  -> out"""
+        n, sw = _planes_arg(vplanes, "vplanes: a contiguous int32 tensor [3, n_var, sw]")
+        q = _weights_arg(X, (32 * sw,), vplanes)
+        if (valid.dtype not in (torch.int32, torch.uint32) or tuple(valid.shape) != (sw,) or not valid.is_contiguous()
+                or valid.device != vplanes.device):
+            raise ValueError(f"valid: a contiguous int32 tensor [{sw}] on the planes' device")
+        for name, t, shape in (("y", y, (32 * sw,)), ("beta0", beta0, (q,))):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != vplanes.device:
+                raise ValueError(f"{name}: a contiguous float64 tensor {list(shape)} on the planes' device")
+        with torch.cuda.device(self.device):
+            if out is None:         # (every entry is written: no need for zeros)
+                out = torch.empty((n, 9), dtype=torch.float64, device=self.device)
+            out = self._out_arg(out, torch.float64, (n, 9), "out")
+            check(self.lib.hhgt_logistic_fit(self.h, _ptr_if_any(vplanes), n, sw, _ptr_if_any(valid), _ptr_if_any(X), q,
+                                             _ptr_if_any(y), _ptr(beta0), _ptr_if_any(out), _stream()))
+        return out
+
     def score_sums(self, planes, w, w_lo=0, w_hi=None, sums=None):
         """sums of per-variant weights under the bits (hhgt_score_sums) of the words [w_lo, w_hi) (default: all) of genotype
         planes [3, n, words]: w is a float64 tensor [3, 32 * words, n_cols] (1 <= n_cols <= 64) — the value of a HOM_REF,

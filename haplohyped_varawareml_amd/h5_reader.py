@@ -14,7 +14,8 @@ genetic_relationship(chromosomes, donor_ids, min_maf, ld_window, ld_r2) the stan
 donors over the variants that pass min_maf and, with ld_window, the LD pruning (GenotypeStore.grm_sums), and
 principal_components(k, ...) its k largest eigenpairs, one record per donor (store.top_eigenpairs: numpy.linalg.eigh on the
 host); association(phenotypes, covariates, chromosomes, donor_ids, min_maf, pcs, ...) a single-variant linear regression
-scan of every variant against one or more phenotypes (GenotypeStore.assoc); polygenic_scores(variants, weights, ...) the
+scan of every variant against one or more phenotypes (GenotypeStore.assoc), or with model="logistic" the logistic one of
+case / control phenotypes (GenotypeStore.assoc_logistic); polygenic_scores(variants, weights, ...) the
 per-donor sums of per-allele effects over listed variants (GenotypeStore.score), and project_components(k,
 train_donor_ids, donor_ids, ...) principal components fitted on some donors and the projection of others onto them
 (GenotypeStore.project); feature_matrix(chromosomes, donor_ids, min_maf, ld_window, ..., train_donor_ids) donors x selected
@@ -22,7 +23,7 @@ variants as a model-ready device tensor with its variant records (GenotypeStore.
 queries."""
 import numpy as np
 
-from .store import (AC, AN, ASSOC_BETA, ASSOC_P, ASSOC_SE, ASSOC_T, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
+from .store import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
                     check_components, grm_from_sums, kinship_from_counts, top_eigenpairs, variant_columns)
 
 
@@ -341,7 +342,7 @@ class VCFH5Reader:
         return rec, dict(matched=matched, unmatched=len(keys) - matched, unused=matched - sum(used.values()))
 
     def association(self, phenotypes, covariates=None, chromosomes=None, donor_ids=None, min_maf=None, pcs=0,
-                    ld_window=None, ld_r2=0.2):
+                    ld_window=None, ld_r2=0.2, model="linear", test="wald"):
         """single-variant linear regression scan of chr_{N} for N in chromosomes (one name or a list; None: every group)
         over donor_ids (default: every sample, store order; each donor once) -> a list with one host numpy record array
         per phenotype, one record per scanned variant in group and variant order: chrom, pos (1-based, the VCF's POS),
@@ -351,7 +352,14 @@ class VCFH5Reader:
         where the variant is not tested).  phenotypes is [n] or [n, P], covariates [n, q0] or None, both aligned with the
         donors.  pcs = K appends the K components of principal_components over the same donors and chromosomes, with
         min_maf, ld_window and ld_r2, to the covariates.  The scan itself runs over the variants that pass min_maf (the
-        minor allele frequency over the donors: GenotypeStore.variant_mask), not over the LD-pruned set."""
+        minor allele frequency over the donors: GenotypeStore.variant_mask), not over the LD-pruned set.
+        model = "logistic": the phenotypes are 0 / 1 and every variant gets a logistic regression
+        (GenotypeStore.assoc_logistic; store.logistic_fit_reference is the contract): after af the records carry beta (the
+        log odds ratio per ALT allele), se, z, p (the Wald test), score_chi2, score_p (the score test at the null model),
+        steps (Newton steps) and status (store.LOGIT_TESTED ... LOGIT_NOT_CONVERGED; the six statistics are NaN unless
+        tested).  test = "score" skips the fits: the score test alone, the Wald columns NaN."""
+        if model not in ("linear", "logistic"):
+            raise ValueError(f"association: model {model!r} (\"linear\" or \"logistic\")")
         st = self.store
         names, donors, who = self._cohort(chromosomes, donor_ids)
         y = np.asarray(phenotypes, dtype=np.float64)
@@ -363,12 +371,18 @@ class VCFH5Reader:
             cov = pc if cov is None else np.concatenate([cov, pc], axis=1)
         tables = [st.variants(g) for g in names]
         width = max([len(r[1].encode()) for t in tables for r in t[3]] + [1])
+        floats = ("beta", "se", "t", "p") if model == "linear" else ("beta", "se", "z", "p", "score_chi2", "score_p")
         dtype = [("chrom", f"S{width}"), ("pos", np.uint32), ("ref", "S10"), ("alt", "S10"), ("n", np.int64),
-                 ("af", np.float64), ("beta", np.float64), ("se", np.float64), ("t", np.float64), ("p", np.float64)]
+                 ("af", np.float64)] + [(f, np.float64) for f in floats]
+        if model == "logistic":
+            dtype += [("steps", np.int64), ("status", np.int64)]
         parts = [[] for _ in range(P)]
         for g, t in zip(names, tables):
             mask = self._variant_masks([g], who, min_maf=min_maf).get(g)
-            stats, calls = (x.cpu().numpy() for x in st.assoc(g, y, cov, who, variant_mask=mask))
+            if model == "linear":
+                stats, calls = (x.cpu().numpy() for x in st.assoc(g, y, cov, who, variant_mask=mask))
+            else:
+                stats, calls, info = (x.cpu().numpy() for x in st.assoc_logistic(g, y, cov, who, variant_mask=mask, test=test))
             at = np.arange(len(t[0])) if mask is None else np.flatnonzero(mask.cpu().numpy())
             shared = np.zeros(len(at), dtype=dtype)             # what every phenotype's records say alike
             self._variant_columns(shared, t, width, at=at, pos=True)
@@ -377,8 +391,10 @@ class VCFH5Reader:
                 shared["af"] = (calls[:, 1] + 2.0 * calls[:, 2]) / calls[:, 0] / 2.0
             for k in range(P):
                 rec = shared.copy()
-                rec["beta"], rec["se"] = stats[:, k, ASSOC_BETA], stats[:, k, ASSOC_SE]
-                rec["t"], rec["p"] = stats[:, k, ASSOC_T], stats[:, k, ASSOC_P]
+                for c, f in enumerate(floats):       # (the statistics' columns in the records' order: ASSOC_*, LOGIT_*)
+                    rec[f] = stats[:, k, c]
+                if model == "logistic":
+                    rec["steps"], rec["status"] = info[:, k, 0], info[:, k, 1]
                 parts[k].append(rec)
         return [np.concatenate(p) if p else np.zeros(0, dtype=dtype) for p in parts]
 

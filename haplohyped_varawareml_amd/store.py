@@ -29,7 +29,12 @@ from .store_plan import (COUNT_PLAN_DTYPE, DEFAULT_PLANE_BYTES, GATHER_PLAN_DTYP
                          sample_index)
 from .store_stats import (AC, AN, ASSOC_ALT, ASSOC_BETA, ASSOC_COMPLETE, ASSOC_HET, ASSOC_MAX_COLS, ASSOC_P,  # noqa: F401
                           ASSOC_SE, ASSOC_T, GRM_SPAN, HET, HET1, HETHET, HOM_ALT, IBS0, LD_AA, LD_AM, LD_HA, LD_HH,
-                          LD_HM, LD_MA, LD_MH, LD_N, NSNP, assoc_design, assoc_from_sums, grm_from_sums, ibs_counts,
+                          LD_HM, LD_MA, LD_MH, LD_N, LOGIT_BETA, LOGIT_COLLINEAR, LOGIT_MAX_COLS, LOGIT_NO_CALL, LOGIT_NOT_CONVERGED,
+                          LOGIT_ONE_CLASS, LOGIT_P, LOGIT_REC, LOGIT_SCORE_CHI2, LOGIT_SCORE_P, LOGIT_SE, LOGIT_STATUS_NAMES,
+                          LOGIT_TESTED, LOGIT_Z, NSNP, REC_ALT, REC_COMPLETE, REC_GAMMA, REC_HET, REC_HINV, REC_HINV0, REC_STATUS,
+                          REC_STEPS, REC_U0, assoc_design, assoc_from_sums, grm_from_sums, ibs_counts, logistic_design,
+                          logistic_fit_reference, logistic_from_fit, logistic_score_design, logistic_score_from_sums,
+                          normal_two_sided,
                           check_components, kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts,
                           standardized_dosages, student_t_two_sided, top_eigenpairs)
 from .store_stats import (SCORE_MAX_COLS, SCORE_SLICE, SCORE_SPAN, call_class_values, cast_class_values,  # noqa: F401
@@ -128,6 +133,7 @@ STAT_KEYS = (
     "ld_plane_blocks", "ld_pairs",              # ld_counts / ld_prune: pairs of counted variants
     "grm_plane_blocks", "grm_words",            # grm_sums: plane words per row, read by its two reductions
     "assoc_plane_blocks", "assoc_variants",     # assoc_sums: counted variants
+    "logistic_variants",                        # assoc_logistic: counted variants (per phenotype)
     "score_plane_blocks", "score_variants",     # score_sums: counted variants whose weights it summed
     "gather_blocks",                            # feature_matrix: Blosc blocks its gather decoded
 )
@@ -766,6 +772,66 @@ class GenotypeStore:
         W, q, yy = assoc_design(y, covariates)
         T = self.assoc_sums(group, W, samples, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes)
         return assoc_from_sums(T, torch.from_numpy(W.sum(axis=0)).to(T.device), q, torch.from_numpy(yy).to(T.device))
+
+    def assoc_logistic(self, group, y, covariates=None, samples=None, v_lo=0, v_hi=None, variant_mask=None, test="wald",
+                       slab_bytes=None, plane_bytes=None):
+        """case / control scan of a group: per counted variant and phenotype, the logistic regression of a 0 / 1 phenotype
+        on [1 | covariates | dosage] -> (stats, calls, info) on the device.  y is [n] or [n, P] (every value 0 or 1),
+        covariates [n, q0] or None, row i for samples[i]; every phenotype gets its own logistic_design (host), and the
+        planes of a window — produced as in assoc_sums: same samples, v_lo / v_hi, variant_mask, slab_bytes, plane_bytes,
+        the read cache neither filled nor evicted — are made once and fitted P times.  test = "wald": hhgt_logistic_fit
+        (Newton's method per variant on the device; logistic_fit_reference is the contract) and logistic_from_fit;
+        test = "score": hhgt_assoc_sums of logistic_score_design's columns and logistic_score_from_sums — the score test
+        alone, no iteration, the four Wald columns NaN.  stats is float64 [n_counted, P, 6], columns LOGIT_BETA, LOGIT_SE,
+        LOGIT_Z, LOGIT_P, LOGIT_SCORE_CHI2, LOGIT_SCORE_P, a call that is not complete imputed to the variant's mean dosage,
+        NaN where the variant is not tested; calls int64 [n_counted, 3]: complete, HET, HOM_ALT calls; info int64
+        [n_counted, P, 2]: Newton steps and status (LOGIT_TESTED ... LOGIT_NOT_CONVERGED).  The samples must be distinct:
+        ValueError before anything is allocated, as for a y that is not 0 / 1 or a design logistic_design refuses."""
+        import torch
+        if test not in ("wald", "score"):
+            raise ValueError(f"assoc_logistic: test {test!r} (\"wald\" or \"score\")")
+        idx = self._query("assoc_logistic", group, samples, v_lo, v_hi, variant_mask, single=True)[0]
+        if len(np.unique(idx)) != len(idx):
+            raise ValueError("assoc_logistic: a sample is listed twice")
+        Y = y.detach().cpu().numpy() if torch.is_tensor(y) else np.asarray(y)
+        Y = Y[:, None] if Y.ndim == 1 else Y
+        if Y.ndim != 2 or Y.shape[0] != len(idx):
+            raise ValueError(f"assoc_logistic: y of shape {Y.shape} for {len(idx)} samples ([n] or [n, P])")
+        designs = [logistic_design(Y[:, p], covariates) for p in range(Y.shape[1])]
+        ctx = self._context()
+        n_rows, rows = self._plane_rows(idx)
+        sw = -(-n_rows // 32)
+        _, _, _, n, vrows = self._variant_rows("assoc_logistic", group, idx, v_lo, v_hi, variant_mask, slab_bytes, plane_bytes,
+                                               "assoc_plane_blocks")
+        d_rows = self._to_device(rows)
+
+        def scattered(a):
+            """a [n, ...] on the host -> zeros [32 sw, ...] on the device with a's rows at the samples' plane rows"""
+            out = torch.zeros((32 * sw,) + a.shape[1:], dtype=torch.float64, device=ctx.device)
+            out[d_rows] = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(ctx.device)
+            return out
+
+        if test == "wald":
+            bits = np.zeros(32 * sw, dtype=np.uint8)
+            bits[rows] = 1
+            valid = self._to_device(np.packbits(bits, bitorder="little").view(np.int32))
+            args = [(valid, scattered(X), scattered(Y[:, p].astype(np.float64)), self._to_device(beta0))
+                    for p, (X, beta0) in enumerate(designs)]
+            fit = lambda v, a: ctx.logistic_fit(v, *a)
+            finish = [logistic_from_fit] * len(designs)
+        else:
+            score = [logistic_score_design(X, Y[:, p], beta0) for p, (X, beta0) in enumerate(designs)]
+            args = [scattered(W) for W, _ in score]
+            fit = ctx.assoc_sums
+            finish = [lambda T, W=W, XWX=XWX: logistic_score_from_sums(T, self._to_device(W.sum(axis=0)), XWX.shape[0],
+                                                                        self._to_device(XWX)) for W, XWX in score]
+        parts = [[fit(v, a) for a in args] for v in vrows]
+        self.stats["logistic_variants"] += n * len(designs)
+        if not parts:               # (no counted variant: a design has samples, so every counted variant has a row of bits)
+            shape = (0, LOGIT_REC) if test == "wald" else (0, 3, args[0].shape[1])
+            parts = [[torch.zeros(shape, dtype=torch.float64, device=ctx.device)] * len(designs)]
+        out = [finish[p](torch.cat([w[p] for w in parts])) for p in range(len(designs))]
+        return torch.stack([o[0] for o in out], 1), out[0][1], torch.stack([o[2] for o in out], 1)
 
     def _score_weights(self, who, weights, groups, samples, v_lo, v_hi, variant_mask, inner):
         """score_sums' and score's (`who`) start: `weights` — one array for one group or a dict group -> array, each

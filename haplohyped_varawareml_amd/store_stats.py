@@ -430,3 +430,249 @@ def assoc_from_sums(T, W_total, q, yy):
         p = student_t_two_sided(t, float(df))
         stats = stack([beta, se, t, p], -1)
         return nan_unless(tested[:, None, None], stats), calls
+
+
+# ---- the case / control scan: a logistic regression per variant -----------------------------------------------------------------
+# columns of the statistics table of logistic_from_fit (and GenotypeStore.assoc_logistic), per variant and phenotype
+LOGIT_BETA, LOGIT_SE, LOGIT_Z, LOGIT_P, LOGIT_SCORE_CHI2, LOGIT_SCORE_P = 0, 1, 2, 3, 4, 5
+# columns of [X | dosage] that hhgt_logistic_fit's tile takes at most (HHGT_LOGIT_MAX_COLS): X has one fewer
+LOGIT_MAX_COLS = 15
+# Newton steps at most (HHGT_LOGIT_MAX_STEPS), the step below which they end, the pivot below which an evaluation fails
+LOGIT_MAX_STEPS, LOGIT_STEP_TOL, LOGIT_PIVOT_TOL = 25, 1e-8, 1e-12
+# the per-variant record of hhgt_logistic_fit and logistic_fit_reference (HHGT_LOGIT_* of include/hhgt.h): the dosage's
+# coefficient and (H^-1)_gg after the last step, the dosage's entry of the gradient and (H^-1)_gg at the first evaluation,
+# steps, status, complete / HET / HOM_ALT calls
+LOGIT_REC = 9
+REC_GAMMA, REC_HINV, REC_U0, REC_HINV0, REC_STEPS, REC_STATUS, REC_COMPLETE, REC_HET, REC_ALT = range(9)
+# the status of a variant: fitted; no complete call; fewer than two of HOM_REF / HET / HOM_ALT; the first evaluation's
+# factorisation failed (the covariates explain the dosage); a later one failed or the last permitted step was too large
+LOGIT_TESTED, LOGIT_NO_CALL, LOGIT_ONE_CLASS, LOGIT_COLLINEAR, LOGIT_NOT_CONVERGED = 0, 1, 2, 3, 4
+LOGIT_STATUS_NAMES = ("tested", "no call", "one class", "collinear", "not converged")
+
+
+def normal_two_sided(z):
+    """the two-sided p-value of a standard normal at z (numpy or torch, any shape) -> float64 of z's shape:
+    erfc(|z| / sqrt 2), from the C library's erfc (numpy: math.erfc element by element) or torch.special.erfc — both keep
+    their relative accuracy in the tail, down to the smallest normal numbers.  NaN stays NaN."""
+    f64 = _ops(z)[1]
+    x = _math(z)[2](f64(z)) / math.sqrt(2.0)
+    if _is_torch(z):
+        import torch
+        return torch.special.erfc(x)
+    x = np.asarray(x, dtype=np.float64)
+    return np.frompyfunc(math.erfc, 1, 1)(x).astype(np.float64).reshape(x.shape)
+
+
+def _logit_evaluate(Xt, y, theta):
+    """one evaluation of V models at once: Xt [V or 1, n, p], y [n], theta [V, p] -> (U [V, p], H [V, p, p]):
+    eta = Xt theta, mu = 1 / (1 + exp(-eta)), w = mu (1 - mu), U = Xt^T (y - mu), H = Xt^T diag(w) Xt"""
+    Xt = np.broadcast_to(Xt, (theta.shape[0],) + Xt.shape[1:])
+    with np.errstate(over="ignore", invalid="ignore"):
+        mu = 1.0 / (1.0 + np.exp(-np.matmul(Xt, theta[:, :, None])[:, :, 0]))
+        w = mu * (1.0 - mu)
+        return np.matmul((y[None, :] - mu)[:, None, :], Xt)[:, 0], np.matmul(Xt.transpose(0, 2, 1) * w[:, None, :], Xt)
+
+
+def _logit_solve(H, U):
+    """H [V, p, p], U [V, p] -> (delta [V, p], hinv [V], ok [V]): delta = H^-1 U by a Cholesky factorisation in the order
+    of the columns, hinv = (H^-1) of the last column = 1 / its pivot, ok: every pivot was above LOGIT_PIVOT_TOL times its
+    diagonal entry of H (a NaN is not)"""
+    V, p = U.shape
+    A, L, u = H.copy(), np.zeros_like(H), U.copy()
+    ok = np.ones(V, dtype=bool)
+    z, delta = np.zeros_like(U), np.zeros_like(U)
+    with np.errstate(all="ignore"):
+        for k in range(p):
+            d = A[:, k, k]
+            ok &= d > LOGIT_PIVOT_TOL * H[:, k, k]
+            L[:, k:, k] = A[:, k:, k] / np.sqrt(d)[:, None]
+            A[:, k + 1:, k + 1:] -= L[:, k + 1:, k, None] * L[:, None, k + 1:, k]
+        for k in range(p):
+            z[:, k] = u[:, k] / L[:, k, k]
+            u[:, k + 1:] -= L[:, k + 1:, k] * z[:, k, None]
+        for i in range(p - 1, -1, -1):
+            delta[:, i] = z[:, i] / L[:, i, i]
+            z[:, :i] -= L[:, i, :i] * delta[:, i, None]
+        return delta, 1.0 / (L[:, -1, -1] * L[:, -1, -1]), ok
+
+
+def logistic_design(y, covariates=None):
+    """the design of a case / control scan -> (X, beta0), host numpy, float64: y is [n], every value 0 or 1 and both
+    present, covariates [n, q0] or None (numpy or torch).  X = sqrt(n) Q, [n, q], Q the orthonormal basis of
+    [1 | covariates] from numpy.linalg.qr (q = 1 + q0): X^T X = n I whatever the covariates' units, and the dosage's
+    coefficient does not depend on the basis.  beta0 [q] is the fit of y on X alone, by the Newton iteration of
+    logistic_fit_reference run until max |delta| <= 1e-12, 50 steps at most.  ValueError for a value that is not finite or
+    not 0 / 1, one class only, covariates of another row count, a rank-deficient [1 | covariates] (assoc_design's rule),
+    n - q - 1 < 1, q > LOGIT_MAX_COLS - 1 (hhgt_logistic_fit's tile), and a null fit that does not get there (the
+    covariates separate the classes)."""
+    yv = _host_f64(y, "y")
+    if yv.ndim != 1:
+        raise ValueError(f"logistic_design: y of shape {yv.shape} ([n]: one phenotype)")
+    if not ((yv == 0.0) | (yv == 1.0)).all():
+        raise ValueError("logistic_design: y holds a value that is neither 0 nor 1")
+    n = len(yv)
+    if not 0 < yv.sum() < n:
+        raise ValueError("logistic_design: y holds one class only (cases and controls are both needed)")
+    A = np.ones((n, 1))
+    if covariates is not None:
+        cov = _host_f64(covariates, "covariates")
+        if cov.ndim != 2 or cov.shape[0] != n:
+            raise ValueError(f"logistic_design: covariates of shape {cov.shape} for {n} rows of y ([n, q0])")
+        A = np.concatenate([A, cov], axis=1)
+    q = A.shape[1]
+    if q > LOGIT_MAX_COLS - 1:
+        raise ValueError(f"logistic_design: {q} covariate columns and the variant exceed {LOGIT_MAX_COLS} columns")
+    if n - q - 1 < 1:
+        raise ValueError(f"logistic_design: {n} samples leave no degree of freedom beside {q} covariate columns and the variant")
+    Q, R = np.linalg.qr(A)
+    d = np.abs(np.diag(R))
+    if d.min() < n * np.finfo(np.float64).eps * d.max():
+        raise ValueError("logistic_design: [1 | covariates] is rank-deficient")
+    X = math.sqrt(n) * Q
+    theta = np.zeros((1, q))
+    for _ in range(50):
+        delta, _, ok = _logit_solve(*_logit_evaluate(X[None], yv, theta)[::-1])
+        if not ok[0] or not np.isfinite(delta).all():
+            break
+        theta += delta
+        if np.abs(delta).max() <= 1e-12:
+            return X, theta[0]
+    raise ValueError("logistic_design: the fit of y on the covariates alone does not converge (they separate the classes)")
+
+
+def logistic_fit_reference(dosage, X, y, beta0):
+    """the per-variant logistic fit, in plain numpy: the contract of hhgt_logistic_fit.  dosage is float [V, n] (or [n]: one
+    variant), 0, 1 or 2 for a complete call and NaN for one that is not; X [n, q], y [n], beta0 [q] as logistic_design gives
+    them -> the record, float64 [V, LOGIT_REC] (or [LOGIT_REC]), columns REC_*.  A call that is not complete takes the mean
+    (h + 2 a) / m of the complete ones.  theta = (beta0, 0); one evaluation at theta: eta = [X | g] theta,
+    mu = 1 / (1 + exp(-eta)), w = mu (1 - mu), U = [X | g]^T (y - mu), H = [X | g]^T diag(w) [X | g], delta = H^-1 U by
+    Cholesky, the dosage last; a pivot not above 1e-12 times its diagonal entry of H fails the evaluation.  The first
+    evaluation gives REC_U0 (the dosage's entry of U) and REC_HINV0 = (H^-1)_gg: the score test.  A step is theta += delta
+    and a new evaluation; the steps end after the first one with max |delta_j| <= 1e-8 — the evaluation after it gives
+    REC_HINV and takes no step, so a fit that takes a step more or fewer by another route differs at second order only —
+    or after LOGIT_MAX_STEPS.  Status: LOGIT_NO_CALL without a complete call, LOGIT_ONE_CLASS with fewer than two of
+    HOM_REF, HET, HOM_ALT (assoc_from_sums' rule), LOGIT_COLLINEAR when the first evaluation fails — four NaNs each —,
+    LOGIT_NOT_CONVERGED when a later one fails (a NaN or an infinity fails one) or step LOGIT_MAX_STEPS is still above
+    1e-8: separation, REC_GAMMA and REC_HINV NaN (Firth's correction is not made).  ValueError for a dosage outside
+    0, 1, 2, NaN or shapes that disagree."""
+    D = np.asarray(dosage, dtype=np.float64)
+    single = D.ndim == 1
+    D = D.reshape(1, -1) if single else D
+    X, y, beta0 = (np.asarray(t, dtype=np.float64) for t in (X, y, beta0))
+    n, q = X.shape
+    if D.ndim != 2 or D.shape[1] != n or y.shape != (n,) or beta0.shape != (q,):
+        raise ValueError(f"logistic_fit_reference: dosage {D.shape}, X {X.shape}, y {y.shape}, beta0 {beta0.shape}")
+    comp = ~np.isnan(D)
+    if not (~comp | (D == 0.0) | (D == 1.0) | (D == 2.0)).all():
+        raise ValueError("logistic_fit_reference: a dosage that is not 0, 1, 2 or NaN")
+    V = D.shape[0]
+    m, h, a = comp.sum(1), (D == 1.0).sum(1), (D == 2.0).sum(1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = (h + 2.0 * a) / m
+    g = np.where(comp, D, mean[:, None])
+    rec = np.full((V, LOGIT_REC), np.nan)
+    rec[:, REC_COMPLETE], rec[:, REC_HET], rec[:, REC_ALT], rec[:, REC_STEPS] = m, h, a, 0.0
+    classes = (m - h - a > 0).astype(int) + (h > 0) + (a > 0)
+    status = np.where(m == 0, LOGIT_NO_CALL, np.where(classes < 2, LOGIT_ONE_CLASS, LOGIT_TESTED))
+    run = np.flatnonzero(status == LOGIT_TESTED)                      # the variants still fitted
+    theta = np.concatenate([np.broadcast_to(beta0, (V, q)), np.zeros((V, 1))], axis=1)
+    steps = np.zeros(V, dtype=np.int64)
+    last = np.zeros(V, dtype=bool)
+    for ev in range(LOGIT_MAX_STEPS + 1):
+        if not len(run):
+            break
+        Xt = np.concatenate([np.broadcast_to(X, (len(run), n, q)), g[run][:, :, None]], axis=2)
+        U, H = _logit_evaluate(Xt, y, theta[run])
+        delta, hinv, ok = _logit_solve(H, U)
+        if ev == 0:
+            status[run[~ok]] = LOGIT_COLLINEAR
+            rec[run[ok], REC_U0], rec[run[ok], REC_HINV0] = U[ok, -1], hinv[ok]
+        else:
+            status[run[~ok]] = LOGIT_NOT_CONVERGED
+        done = last[run] & ok
+        rec[run[done], REC_HINV] = hinv[done]
+        step = ok & ~done
+        with np.errstate(invalid="ignore", over="ignore"):
+            theta[run[step]] += delta[step]
+            biggest = np.abs(np.nan_to_num(delta, nan=np.inf)).max(axis=1)
+        steps[run[step]] += 1
+        last[run[step & (biggest <= LOGIT_STEP_TOL)]] = True
+        lost = step & ~(biggest <= LOGIT_STEP_TOL) & ((steps[run] == LOGIT_MAX_STEPS) | ~np.isfinite(biggest))
+        status[run[lost]] = LOGIT_NOT_CONVERGED
+        run = run[step & ~lost]
+    tested = status == LOGIT_TESTED
+    rec[:, REC_GAMMA] = np.where(tested, theta[:, -1], np.nan)
+    rec[~tested, REC_HINV] = np.nan
+    rec[:, REC_STEPS], rec[:, REC_STATUS] = steps, status
+    return rec[0] if single else rec
+
+
+def logistic_from_fit(raw):
+    """the statistics of a case / control scan from the records of hhgt_logistic_fit or logistic_fit_reference ->
+    (stats, calls, info): raw float64 [V, LOGIT_REC] (numpy or torch).  stats is float64 [V, 6]: LOGIT_BETA the log odds
+    ratio per ALT allele, LOGIT_SE = sqrt((H^-1)_gg) at the fitted model, LOGIT_Z = BETA / SE, LOGIT_P =
+    normal_two_sided(Z) (the Wald test), LOGIT_SCORE_CHI2 = U^2 (H^-1)_gg at the null model and LOGIT_SCORE_P =
+    normal_two_sided(sqrt(CHI2)) (the score test, one degree of freedom) — all six NaN where the status is not LOGIT_TESTED.
+    calls is int64 [V, 3]: complete, HET, HOM_ALT calls, as assoc_from_sums gives them; info int64 [V, 2]: steps, status."""
+    i64, f64, _, nan_unless = _ops(raw)
+    stack = _math(raw)[4]
+    raw = f64(raw)
+    if len(raw.shape) != 2 or raw.shape[1] != LOGIT_REC:
+        raise ValueError(f"logistic_from_fit: records of shape {list(raw.shape)} ([V, {LOGIT_REC}])")
+    calls = stack([i64(raw[:, REC_COMPLETE]), i64(raw[:, REC_HET]), i64(raw[:, REC_ALT])], -1)
+    info = stack([i64(raw[:, REC_STEPS]), i64(raw[:, REC_STATUS])], -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        beta, se = raw[:, REC_GAMMA], raw[:, REC_HINV] ** 0.5
+        z = beta / se
+        chi2 = raw[:, REC_U0] * raw[:, REC_U0] * raw[:, REC_HINV0]
+        stats = stack([beta, se, z, normal_two_sided(z), chi2, normal_two_sided(chi2 ** 0.5)], -1)
+    return nan_unless((info[:, 1] == LOGIT_TESTED)[:, None], stats), calls, info
+
+
+def logistic_score_design(X, y, beta0):
+    """what the score test by sums needs of a design -> (W, XWX), host numpy, float64: with mu0 = 1 / (1 + exp(-X beta0))
+    and w0 = mu0 (1 - mu0), W = [1 | y - mu0 | w0 | w0 X], [n, 3 + q], the per-sample matrix for assoc_sums, and
+    XWX = X^T diag(w0) X, [q, q]"""
+    X, y, beta0 = (np.asarray(t, dtype=np.float64) for t in (X, y, beta0))
+    mu = 1.0 / (1.0 + np.exp(-(X @ beta0)))
+    w = mu * (1.0 - mu)
+    return np.concatenate([np.ones((len(y), 1)), (y - mu)[:, None], w[:, None], w[:, None] * X], axis=1), X.T @ (w[:, None] * X)
+
+
+def logistic_score_from_sums(T, W_total, q, XWX):
+    """the score test of a case / control scan at the null model from the sums of GenotypeStore.assoc_sums, without a fit
+    -> (stats, calls, info) as logistic_from_fit gives them, the four Wald columns NaN and steps 0: T float64
+    [V, 3, 3 + q] over logistic_score_design's W = [1 | y - mu0 | w0 | w0 X], W_total [3 + q] the column sums of W, XWX
+    [q, q] (numpy or torch, all of one kind).  With m, h, a and the imputed mean mu as in assoc_from_sums and
+    g.c = T[HET][c] + 2 T[ALT][c] + mu (W_total[c] - T[COMPLETE][c]) for a column c of W:
+        U = g.(y - mu0)      b = g.(w0 X)      gWg = T[HET][w0] + 4 T[ALT][w0] + mu^2 (W_total[w0] - T[COMPLETE][w0])
+        V = gWg - b XWX^-1 b^T      LOGIT_SCORE_CHI2 = U^2 / V      LOGIT_SCORE_P = normal_two_sided(sqrt(CHI2))
+    — the first evaluation of logistic_fit_reference by another route: V is the pivot of the dosage there.  Status
+    LOGIT_NO_CALL and LOGIT_ONE_CLASS as there, LOGIT_COLLINEAR where V <= 1e-12 gWg, LOGIT_TESTED else; never
+    LOGIT_NOT_CONVERGED: a variant that separates the classes has a score test."""
+    i64, f64, _, nan_unless = _ops(T)
+    stack = _math(T)[4]
+    q = int(q)
+    T, W_total, XWX = f64(T), f64(W_total), f64(XWX)
+    if len(T.shape) != 3 or T.shape[1] != 3 or T.shape[2] != 3 + q or tuple(XWX.shape) != (q, q):
+        raise ValueError(f"logistic_score_from_sums: T {list(T.shape)} ([V, 3, {3 + q}]), XWX {list(XWX.shape)} ([{q}, {q}])")
+    m, h, a = T[:, ASSOC_COMPLETE, 0], T[:, ASSOC_HET, 0], T[:, ASSOC_ALT, 0]
+    calls = stack([i64(m), i64(h), i64(a)], -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = (h + 2.0 * a) / m
+        gw = T[:, ASSOC_HET] + 2.0 * T[:, ASSOC_ALT] + mu[:, None] * (W_total[None, :] - T[:, ASSOC_COMPLETE])
+        gWg = T[:, ASSOC_HET, 2] + 4.0 * T[:, ASSOC_ALT, 2] + mu * mu * (W_total[2] - T[:, ASSOC_COMPLETE, 2])
+        b = gw[:, 3:]
+        if _is_torch(T):
+            import torch
+            sol = torch.linalg.solve(XWX, b.T).T
+        else:
+            sol = np.linalg.solve(XWX, b.T).T
+        Vg = gWg - (b * sol).sum(-1)
+        chi2 = gw[:, 1] * gw[:, 1] / Vg
+        classes = i64(m - h - a > 0) + i64(h > 0) + i64(a > 0)
+        status = (i64(m == 0) * LOGIT_NO_CALL + i64((m > 0) & (classes < 2)) * LOGIT_ONE_CLASS
+                  + i64((m > 0) & (classes >= 2) & ~(Vg > LOGIT_PIVOT_TOL * gWg)) * LOGIT_COLLINEAR)
+        nan = chi2 * 0.0 + float("nan")
+        stats = stack([nan, nan, nan, nan, chi2, normal_two_sided(chi2 ** 0.5)], -1)
+    return nan_unless((status == LOGIT_TESTED)[:, None], stats), calls, stack([status * 0, status], -1)

@@ -513,6 +513,60 @@ int hhgt_assoc_sums(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, ui
 int hhgt_score_sums(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
                     const double *d_w, uint32_t n_cols, double *d_sums, void *stream);
 
+/* hhgt_logistic_fit fits, for every row of d_vplanes — uint32 [3][n_var][sw], the planes HET, COMPLETE, HOM_ALT of
+ * hhgt_variant_planes —, the logistic regression of a 0 / 1 phenotype on [X | dosage] by Newton's method: the kernel of
+ * GenotypeStore.assoc_logistic; store_stats.logistic_fit_reference is the same iteration in numpy and is the contract.
+ * d_valid is uint32 [sw]: bit s % 32 of word s / 32 says that position s is a listed sample; the positions without that bit
+ * take no part in anything (plane rows come in whole chunk rows, and in a likelihood a row of zeros does not vanish as it
+ * does from a sum).  d_x is double [32 * sw][q], row-major, d_y double [32 * sw] (0.0 or 1.0), d_beta0 double [q] the null
+ * fit; all 8-byte aligned; the rows of d_x and d_y at positions without a valid bit are never read.
+ * Per variant, over the valid positions: m, h, a = the COMPLETE, HET, HOM_ALT bits; the dosage g is [HET] + 2 [HOM_ALT]
+ * where COMPLETE is set and (h + 2 a) / m elsewhere.  theta = (beta0, 0).  One evaluation at theta: eta = [X | g] theta,
+ * mu = 1 / (1 + exp(-eta)), w = mu (1 - mu), U = [X | g]^T (y - mu), H = [X | g]^T diag(w) [X | g], delta = H^-1 U by a
+ * Cholesky factorisation with the dosage last; a pivot that is not above 1e-12 times its diagonal entry of H fails the
+ * evaluation.  A step is theta += delta and another evaluation; the steps end after the first one with max |delta_j| <= 1e-8
+ * (the evaluation after it gives the final (H^-1)_gg and takes no step) or after HHGT_LOGIT_MAX_STEPS of them.
+ * d_out is double [n_var][HHGT_LOGIT_REC], 8-byte aligned; every entry is WRITTEN, with plain stores, nothing outside it is
+ * touched, nothing accumulates:
+ *     [HHGT_LOGIT_GAMMA]   the dosage's coefficient after the last step         [HHGT_LOGIT_HINV]   (H^-1)_gg at that theta
+ *     [HHGT_LOGIT_U0]      the dosage's entry of U at the first evaluation      [HHGT_LOGIT_HINV0]  (H^-1)_gg at the first one
+ *     [HHGT_LOGIT_STEPS]   steps taken                                          [HHGT_LOGIT_STATUS] one of HHGT_LOGIT_* below
+ *     [HHGT_LOGIT_N_COMPLETE], [HHGT_LOGIT_N_HET], [HHGT_LOGIT_N_ALT]   m, h, a (exact)
+ * Status: HHGT_LOGIT_NO_CALL m == 0; HHGT_LOGIT_ONE_CLASS fewer than two of m - h - a, h, a are positive (neither is
+ * fitted: the four statistics are NaN, steps 0); HHGT_LOGIT_COLLINEAR the first evaluation failed (X explains the dosage;
+ * four NaNs, steps 0); HHGT_LOGIT_NOT_CONVERGED a later evaluation failed (a NaN or an infinity fails one) or the last
+ * permitted step was still above 1e-8 (separation: GAMMA and HINV are NaN, U0 and HINV0 stand); HHGT_LOGIT_TESTED else.
+ * Arithmetic: float64 throughout.  U and H of an evaluation are one (16 x S) . (S x 16) product on v_mfma_f64_16x16x4_f64,
+ * rows [X | g], columns [w X | w g | y - mu], one accumulator that takes the positions in ascending order; eta is a chain of
+ * fused multiply-adds in ascending column order, the dosage last; exp is the device library's.  One wave fits a variant;
+ * the 8 waves of a workgroup share the slices of X through LDS and draw the workgroup's 64 variants one after another, so
+ * which wave fits a variant is not fixed — its arithmetic is: every sum is taken in an order fixed by the arguments and
+ * there are no float atomics (the draw is an integer counter in LDS): two calls give the same bits.  Equality
+ * with numpy's bits is NOT claimed: summation order, the fused multiply-adds and exp differ; tests/test_logistic_stats.py
+ * derives the tolerance.
+ * 1 <= q <= HHGT_LOGIT_MAX_COLS - 1 (the dosage is the last column of the tile's 15; the 16th carries U); n_var up to
+ * 64 * (2^31 - 1), sw below 2^27, else HHGT_ERR_ARG.  n_var == 0 is HHGT_OK and touches nothing; with sw == 0 every variant
+ * is HHGT_LOGIT_NO_CALL.  Timed under HHGT_STAGE_ASSOC. */
+#define HHGT_LOGIT_MAX_COLS 15    /* columns of [X | dosage] */
+#define HHGT_LOGIT_MAX_STEPS 25
+#define HHGT_LOGIT_REC 9
+#define HHGT_LOGIT_GAMMA 0
+#define HHGT_LOGIT_HINV 1
+#define HHGT_LOGIT_U0 2
+#define HHGT_LOGIT_HINV0 3
+#define HHGT_LOGIT_STEPS 4
+#define HHGT_LOGIT_STATUS 5
+#define HHGT_LOGIT_N_COMPLETE 6
+#define HHGT_LOGIT_N_HET 7
+#define HHGT_LOGIT_N_ALT 8
+#define HHGT_LOGIT_TESTED 0
+#define HHGT_LOGIT_NO_CALL 1
+#define HHGT_LOGIT_ONE_CLASS 2
+#define HHGT_LOGIT_COLLINEAR 3
+#define HHGT_LOGIT_NOT_CONVERGED 4
+int hhgt_logistic_fit(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const uint32_t *d_valid,
+                      const double *d_x, uint32_t q, const double *d_y, const double *d_beta0, double *d_out, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Bit-plane form of the genotype matrix: the intermediate between encode and compress when the compressor is the only
  * consumer of the matrix (converter, ingest engine, bench).  Same path, same results — the int8 values

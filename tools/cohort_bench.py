@@ -9,7 +9,7 @@ from haplohyped_varawareml_amd import synth
 from haplohyped_varawareml_amd.reader import write_bgzf_native
 from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
-RECORDED = ("ld_bench", "grm_bench", "assoc_bench", "score_bench", "feature_bench")      # the tools whose line is also kept under profiles/
+RECORDED = ("ld_bench", "grm_bench", "assoc_bench", "score_bench", "feature_bench", "logistic_bench")     # the tools whose line is also kept under profiles/
 
 
 def build_cohort(ctx, tmp, variants, samples=2504, seed=1001):
