@@ -42,27 +42,38 @@
 #ifndef BP_MAXONES
 #define BP_MAXONES 636
 #endif
+// Queue and staging area are what is left of 5120 bytes of LDS per plane — 32 single-wave workgroups of k_lz4_bitplanes_uni
+// per CU, eight waves per SIMD — behind the arrays whose sizes the coder's decisions hang on: 896 bytes on the plain path,
+// 760 on the exception-aware one, which carries a second bit map and the ones' classes (624 bytes) and a shorter list.
+// Neither size changes a stream: a window whose coded ones would not fit sends a batch off first, staged bytes leave
+// when the next batch would not fit, and a batch larger than the whole area goes to the stream's slot directly.
+// (DESIGN.md 3.2 "One plane per workgroup" has the stage times of the splits that were tried.)
+#ifndef BP_QCAP
+#define BP_QCAP 80      // queued coded ones a wave can hold (a window adds at most 64 to at most 64)
+#endif
 #ifndef BP_STAGE
-#define BP_STAGE 576    // staging area; with the queue below the workgroup stays under 11 KiB of LDS = 14 workgroups per CU
+#define BP_STAGE 240    // staging area
 #endif
 #ifndef BP_WAVES
-#define BP_WAVES 7       // waves per SIMD the kernels are compiled for (LDS must allow 2 x BP_WAVES workgroups per CU)
+#define BP_WAVES 7       // waves per SIMD the kernels are compiled for (k_lz4_bitplanes: LDS must allow 2 x BP_WAVES workgroups per CU)
 #endif
-#define BP_QCAP 100     // queued coded ones a wave can hold (a window adds at most 64 to fewer than 64)
-// the exception-aware path carries a second bit map and the ones' classes (624 bytes per wave): its list and its staging
-// area are smaller by as much, so that it too stays under 11 KiB per workgroup = 14 workgroups per CU, 7 waves per SIMD (round 4;
-// it ran at 13 / 6 before, and this kernel's time is 1 / occupancy)
 #ifndef BP_MAXONES_EXC
 #define BP_MAXONES_EXC 540
 #endif
-#ifndef BP_STAGE_EXC
-#define BP_STAGE_EXC 448
+#ifndef BP_QCAP_EXC
+#define BP_QCAP_EXC 80
 #endif
+#ifndef BP_STAGE_EXC
+#define BP_STAGE_EXC 104
+#endif
+#define BP_PLANE_LDS 5120   // k_lz4_bitplanes_uni: LDS of a workgroup = a plane (163 840 / 32)
 template <bool EXC> struct BpCfg {
     static constexpr uint32_t MAXONES = EXC ? BP_MAXONES_EXC : BP_MAXONES;
+    static constexpr uint32_t QCAP = EXC ? BP_QCAP_EXC : BP_QCAP;
     static constexpr uint32_t STAGE = EXC ? BP_STAGE_EXC : BP_STAGE;
     static constexpr uint32_t PTRASH = MAXONES + 7;   // P's spare entry: written by lanes that have nothing to store, never read
 };
+static_assert(BP_QCAP >= 65 && BP_QCAP_EXC >= 65, "a batch of 64 needs the entry behind it in the queue");
 #define BP_HLOG 6
 #define BP_GAPCLIP 40
 #define BP_MINM 6     // total length a hash match must have
@@ -92,7 +103,7 @@ template <bool CHAIN, bool EXC> struct BpLds {
     uint16_t P[BpCfg<EXC>::MAXONES + 8];      // P[j + 1] = q_j + 1 (P[0] = 0: a virtual one at -1; P[m + 1] = P[m + 2] = n + 1)
     uint16_t chain[CHAIN ? BpCfg<EXC>::MAXONES + 8 : 4];   // chain[j + 1] = (previous one with the same context hash) + 1, 0 = none
     uint32_t gbw[(BpCfg<EXC>::MAXONES + 16) / 4];   // gap bytes: zeros behind the one with P-index i, clipped to 255 (255 from the last one on)
-    uint2 queue[BP_QCAP + 1];        // coded ones waiting for layout + emission (bp_emit_batch takes 64 at a time); [BP_QCAP]: written by lanes that queue nothing
+    uint2 queue[BpCfg<EXC>::QCAP + 1];       // coded ones waiting for layout + emission (bp_emit_batch takes 64 at a time); [QCAP]: written by lanes that queue nothing
     uint8_t stage[BpCfg<EXC>::STAGE + 8];     // output staged here, written out in coalesced dwords; [BP_STAGE]: written by lanes that have no byte to store
 };
 
@@ -238,7 +249,7 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     const uint32_t *xm = S.xm;
     uint32_t prev_end = st.prev_end, gop = st.gop, sop = st.sop;
     const bool have = lane < n;
-    uint2 en = S.queue[lane];   // (lane < 64 <= BP_QCAP: inside the queue whatever n is)
+    uint2 en = S.queue[lane];   // (lane < 64 <= QCAP: inside the queue whatever n is)
     en.x = have ? en.x : 0u;
     en.y = have ? en.y : 0u;
     const uint32_t E = en.x & 0x1FFFu, msr = (en.x >> 13) & 0x1FFFu, rs = E + (en.x >> 28), re = en.y & 0x1FFFu, off = en.y >> 13;
@@ -297,7 +308,7 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     return BpOut{prev_end, gop, sop};
 }
 
-// ---- the plane coder: wave w codes plane w, in the phases below (bp_code_plane at the end calls them in order)
+// ---- the plane coder: one wave codes one plane (`wave`: which of the block's two), in the phases below (bp_code_plane at the end calls them in order)
 // The lanes of the wave exchange data through the wave's BpLds (S) with no barrier in between: the LDS executes a wave's
 // instructions in order.  What the COMPILER must not do is move a lane's read in front of another lane's earlier write;
 // every such hand-over below is an access whose address it cannot tell apart from the lane's own writes, and BP_FENCE marks
@@ -707,13 +718,13 @@ __device__ __forceinline__ BpQueued bp_queue_and_drain(LDS &S, const uint32_t *b
     for (int phase = 0; phase < 2; ++phase) {
         if (phase == 1) {
             const uint32_t slot = qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(wm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)wm, 0u));
-            S.queue[want ? slot : (uint32_t)BP_QCAP] = ent;
+            S.queue[want ? slot : BpCfg<EXC>::QCAP] = ent;
             qn += nw;
             BP_MARK("queued");
         }
         // a batch leaves the queue when the entry behind its last one is there too (the run rule looks at it) — or when
         // the stream ends
-        while (phase == 0 ? qn + nw > BP_QCAP : (qn >= 65u || (last && qn != 0u))) {   // (wave-uniform)
+        while (phase == 0 ? qn + nw > BpCfg<EXC>::QCAP : (qn >= 65u || (last && qn != 0u))) {   // (wave-uniform)
             const uint32_t keep = phase == 1 && last ? 0u : 1u;
             const uint32_t nb_ = qn - keep < 64u ? qn - keep : 64u;
             BP_FENCE();
@@ -721,9 +732,9 @@ __device__ __forceinline__ BpQueued bp_queue_and_drain(LDS &S, const uint32_t *b
             prev_end = r.prev_end, gop = r.gop, sop = r.sop;
             BP_FENCE();
             const bool mvp = lane + nb_ < qn;
-            const uint2 mv = S.queue[mvp ? nb_ + lane : (uint32_t)BP_QCAP];
+            const uint2 mv = S.queue[mvp ? nb_ + lane : BpCfg<EXC>::QCAP];
             BP_FENCE();
-            S.queue[mvp ? lane : (uint32_t)BP_QCAP] = mv;
+            S.queue[mvp ? lane : BpCfg<EXC>::QCAP] = mv;
             qn -= nb_;
         }
     }
@@ -934,30 +945,40 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes(const uint8_t *
 }
 
 // Bit-plane input (include/hhgt.h, tile-major: common.h; written by k_encode_planes): the wave's bit map is 16 pieces of
-// 32 bytes it gathers as they are (one load instruction: lane l takes 8 bytes of tile l / 4).  The pieces of four
-// neighbouring sample rows share a 128-byte line, so the blocks are dealt to the workgroups in an XCD-aware order: of 64
-// consecutive workgroups the eight that land on one XCD (round robin) take eight consecutive blocks — one L2 fetches each
-// line once (the grid is rounded up to whole groups of 64).
-// The plain and the exception-aware coder in ONE launch (round 4): a wave looks at its plane's missing-call map and takes the
-// one or the other path (wave-uniform; both are bp_code_plane, inlined).  The exception-aware path codes planes whose bytes
+// 32 bytes it gathers as they are (one load instruction: lane l takes 8 bytes of tile l / 4).
+// Grid: ONE WAVE PER WORKGROUP, one workgroup per plane, two per block (stream 2 block + plane, as ever).  The kernel has no
+// barrier and the two planes of a block share nothing; as a pair they shared one LDS allocation, and the wave slot of the
+// plane that finished first (a plane runs four or five windows, by its ones) idled until its sibling ended.  Alone, a
+// finished plane frees slot, registers and LDS at once.  LDS per workgroup: sizeof(BpBoth) <= BP_PLANE_LDS = 5120 bytes,
+// 32 workgroups per CU; the single-wave form compiles to 64 VGPRs (the pair took 70-72), so registers allow those eight
+// waves per SIMD as well (seven before: 14 pairs).
+// Order: the pieces of four neighbouring sample rows share a 128-byte line, so the planes are dealt to the workgroups in an
+// XCD-aware order: of 128 consecutive workgroups the sixteen that land on one XCD (round robin) take both planes of eight
+// consecutive blocks — one L2 fetches each line once (the grid is rounded up to whole groups of 128 = 64 blocks; workgroups
+// beyond the last block return).
+// The plain and the exception-aware coder in ONE launch (round 4): a workgroup looks at its plane's missing-call map and takes
+// the one or the other path (both are bp_code_plane, inlined).  The exception-aware path codes planes whose bytes
 // are 0, 1 or 0xF7 (missing calls; config 4): the bit map is the map of NONZERO bytes, a second map says which of them are
 // 0xF7, every one carries that bit as its class, and two ones only agree if their classes do (tools/sim/gapenc_ref.c states
 // the rules).  What this replaced was a plain launch marking every plane that holds a missing call for a second, scanning
 // launch — on config 4, where every plane does, 0.4 ms of reading all planes for nothing.  Planes neither path can code (a
 // call beyond 0 / 1 / missing, too many nonzero bytes) are marked for the byte-wise kernel (flags[0]).
 template <int DEPTH, bool LAZY>
-__global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8_t *__restrict__ src, PlanesGeom pg, uint32_t n_blocks,
-                                                                      uint8_t *__restrict__ scratch, uint64_t slot_bytes,
-                                                                      uint32_t *__restrict__ csize, uint32_t *__restrict__ flags, uint32_t tag)
+__global__ __launch_bounds__(64, BP_WAVES) void k_lz4_bitplanes_uni(const uint8_t *__restrict__ src, PlanesGeom pg, uint32_t n_blocks,
+                                                                     uint8_t *__restrict__ scratch, uint64_t slot_bytes,
+                                                                     uint32_t *__restrict__ csize, uint32_t *__restrict__ flags, uint32_t tag)
 {
     constexpr bool CHAIN = DEPTH > 1;
     union BpBoth {
         BpLds<CHAIN, false> p;
         BpLds<CHAIN, true> x;
     };
-    __shared__ BpBoth lds[2];
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
-    const uint32_t bid = (blockIdx.x & ~63u) | ((blockIdx.x & 7u) << 3) | ((blockIdx.x >> 3) & 7u);   // (XCD-aware order)
+    static_assert(sizeof(BpBoth) <= BP_PLANE_LDS, "32 planes per CU");
+    __shared__ BpBoth lds;
+    const uint32_t lane = threadIdx.x;
+    // (XCD-aware order: of a group of 128 workgroups, XCD slot r & 7 takes blocks 8 (r & 7) .. 8 (r & 7) + 7 of the group's 64, both planes)
+    const uint32_t r = blockIdx.x & 127u, k = r >> 3;
+    const uint32_t bid = (blockIdx.x >> 7) * 64u + (r & 7u) * 8u + (k >> 1), wave = k & 1u;   // (wave: the byte plane, as before)
     if (bid >= n_blocks) return;
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     uint64_t col;
@@ -968,13 +989,13 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8
     // (both branches store the bit map of the nonzero bytes, at the same place: stored once in front of the branch, every
     // instantiation but depth 0 takes 72 instead of 70 VGPRs)
     if (__builtin_amdgcn_ballot_w64((exc.x | exc.y) != 0u) == 0ull) {   // no missing call in this plane: the plain coder
-        BpLds<CHAIN, false> &S = lds[wave].p;
+        BpLds<CHAIN, false> &S = lds.p;
         S.bm[2u * lane] = one.x;
         S.bm[2u * lane + 1u] = one.y;
         if (lane < 4u) S.bm[128u + lane] = 0u;
         bp_code_plane<DEPTH, false, LAZY>(S, one.x, one.y, 0u, 0u, false, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
     } else {
-        BpLds<CHAIN, true> &S = lds[wave].x;
+        BpLds<CHAIN, true> &S = lds.x;
         // (ONE, EXC) = (0, 1): a call beyond 0 / 1 / missing, its byte lives in the int8 matrix — not this coder's
         const bool nonbinary = __builtin_amdgcn_ballot_w64(((exc.x & ~one.x) | (exc.y & ~one.y)) != 0u) != 0ull;
         S.bm[2u * lane] = one.x;
@@ -988,14 +1009,14 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes_uni(const uint8
     }
 }
 
-// one launch of the coder with D candidates per one and, LZ, the lazy rule: the plane-input kernel (its grid rounded up to
-// whole groups of 64, for its XCD-aware order) or the int8-input one
+// one launch of the coder with D candidates per one and, LZ, the lazy rule: the plane-input kernel (one workgroup per plane,
+// its grid rounded up to whole groups of 128 = 64 blocks, for its XCD-aware order) or the int8-input one (one per block)
 template <int D, bool LZ>
 static void bp_launch(bool planes, const uint8_t *d_src, PlanesGeom pg, uint32_t n_blocks, uint8_t *d_scratch, uint64_t slot_bytes, uint32_t *d_csize,
                       uint32_t *d_flags, uint32_t tag, hipStream_t st)
 {
     if (planes)
-        hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((n_blocks + 63u) / 64u * 64u), dim3(128), 0, st, d_src, pg, n_blocks, d_scratch, slot_bytes,
+        hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((n_blocks + 63u) / 64u * 128u), dim3(64), 0, st, d_src, pg, n_blocks, d_scratch, slot_bytes,
                            d_csize, d_flags, tag);
     else
         hipLaunchKernelGGL((k_lz4_bitplanes<D, LZ>), dim3(n_blocks), dim3(128), 0, st, d_src, pg, n_blocks, d_scratch, slot_bytes, d_csize, d_flags, tag);
@@ -1008,7 +1029,7 @@ int launch_lz4_bitplanes(const uint8_t *d_src, bool planes, PlanesGeom pg, uint6
     const bool lazy = (depth & 0x100) != 0;
     depth &= 0xFF;
     if (n_blocks == 0) return HHGT_OK;
-    if (n_blocks > 0x7fffffffull) {
+    if (2u * n_blocks > 0x7fffff80ull) {   // (the plane-input grid: two workgroups per block, rounded up to whole groups of 128)
         hhgt_set_error("lz4: too many blocks");
         return HHGT_ERR_ARG;
     }
