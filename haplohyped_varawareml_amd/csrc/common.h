@@ -177,6 +177,61 @@ static inline __host__ __device__ void planes_block(const PlanesGeom &g, uint64_
     *row = rem / g.bpr;
     *bi = rem - (rem / g.bpr) * g.bpr;
 }
+// The same on 32 bits without a division, for k_lz4_bitplanes_uni (lz4bits.hip), where the two divisions stood in front of
+// the address of every wave's only global load: floor(n / d) = (mul * 2 n) >> (32 + sh) with sh = ceil(log2 d) and
+// mul = ceil(2^(31 + sh) / d) < 2^32 (Granlund / Montgomery 1994, N = 31: mul * d = 2^(31 + sh) + e with e < d <= 2^sh, so
+// the quotient is off by n e / (d 2^(31 + sh)) < 1 / d).  EXACT FOR every n < 2^31 and every 1 <= d < 2^31;
+// launch_lz4_bitplanes makes sure of both (block ids stay below 2^30 there).
+struct PlanesDiv {
+    uint32_t mul_col, sh_col;   // / (S_pad * bpr): blocks per column
+    uint32_t mul_row, sh_row;   // / bpr
+};
+static inline __host__ __device__ void planes_recip(uint32_t d, uint32_t *mul, uint32_t *sh)
+{
+    uint32_t l = 0;
+    while (l < 31u && (1u << l) < d) ++l;
+    *mul = (uint32_t)(((1ull << (31u + l)) + d - 1u) / d);
+    *sh = l;
+}
+static inline __host__ __device__ uint32_t planes_div32(uint32_t n, uint32_t mul, uint32_t sh)
+{
+    return (uint32_t)(((uint64_t)mul * (n << 1)) >> 32) >> sh;
+}
+static inline __host__ __device__ PlanesDiv planes_div(const PlanesGeom &g)
+{
+    PlanesDiv dv;
+    planes_recip(g.S_pad * g.bpr, &dv.mul_col, &dv.sh_col);
+    planes_recip(g.bpr, &dv.mul_row, &dv.sh_row);
+    return dv;
+}
+static inline __host__ __device__ void planes_block32(const PlanesGeom &g, const PlanesDiv &dv, uint32_t id, uint64_t *col, uint32_t *row, uint32_t *bi)
+{
+    const uint32_t c = planes_div32(id, dv.mul_col, dv.sh_col);
+    const uint32_t rem = id - c * (g.S_pad * g.bpr);
+    const uint32_t r = planes_div32(rem, dv.mul_row, dv.sh_row);
+    *col = (uint64_t)g.col0 + c;
+    *row = r;
+    *bi = rem - r * g.bpr;
+}
+// workgroup wg of k_lz4_bitplanes_uni's grid -> the block and the byte plane (0 / 1) it codes.  XCD-aware: of a group of 128
+// workgroups, XCD slot r & 7 takes blocks 8 (r & 7) .. 8 (r & 7) + 7 of the group's 64, both planes
+static inline __host__ __device__ void planes_wg_plane(uint32_t wg, uint32_t *bid, uint32_t *h)
+{
+    const uint32_t r = wg & 127u, k = r >> 3;
+    *bid = (wg >> 7) * 64u + (r & 7u) * 8u + (k >> 1);
+    *h = k & 1u;
+}
+// where lane `lane` of the wave that codes byte plane h of block bid takes its 8 bytes of the ONE planes from (bytes into the
+// planes buffer): lane l reads quarter l & 3 of the 32-byte piece of tile l / 4.  Its 8 bytes of the EXC planes lie
+// planes_exc_step(g) bytes behind
+static inline __host__ __device__ uint64_t planes_lane_bytes(const PlanesGeom &g, const PlanesDiv &dv, uint32_t bid, uint32_t h, uint32_t lane)
+{
+    uint64_t col;
+    uint32_t row, bi;
+    planes_block32(g, dv, bid, &col, &row, &bi);
+    return planes_piece(g, col, bi * 16u + (lane >> 2), h, row) + (lane & 3u) * 8ull;
+}
+static inline __host__ __device__ uint64_t planes_exc_step(const PlanesGeom &g) { return (uint64_t)g.S_pad * 64ull; }
 
 // workspace buffer that only grows
 struct DevBuf {

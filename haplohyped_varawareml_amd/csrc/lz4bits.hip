@@ -88,8 +88,9 @@ static_assert(BP_QCAP >= 65 && BP_QCAP_EXC >= 65, "a batch of 64 needs the entry
 #define BP_MARK(name)
 #endif
 #ifndef BP_SKIP
-#define BP_SKIP 0   // development: 1 no emission, 2 no layout either, 3 no selection, 4 no window loop, 5 phase A only (invalid output; timing only)
+#define BP_SKIP 0   // development: 1 no emission, 2 no layout either, 3 no selection, 4 no window loop, 5 phase A only, 6 plane input: load + bit map only (invalid output; timing only)
 #endif
+#define BP_EMPTY_BYTES 26u   // the stream of a plane of 4096 zeros (k_lz4_bitplanes_uni writes it itself)
 #define BP_MFLIMIT (BP_N - 12)
 #define BP_MATCHLIMIT (BP_N - 5)
 
@@ -966,7 +967,7 @@ __global__ __launch_bounds__(128, BP_WAVES) void k_lz4_bitplanes(const uint8_t *
 template <int DEPTH, bool LAZY>
 __global__ __launch_bounds__(64, BP_WAVES) void k_lz4_bitplanes_uni(const uint8_t *__restrict__ src, PlanesGeom pg, uint32_t n_blocks,
                                                                      uint8_t *__restrict__ scratch, uint64_t slot_bytes,
-                                                                     uint32_t *__restrict__ csize, uint32_t *__restrict__ flags, uint32_t tag)
+                                                                     uint32_t *__restrict__ csize, uint32_t *__restrict__ flags, uint32_t tag, PlanesDiv dv)
 {
     constexpr bool CHAIN = DEPTH > 1;
     union BpBoth {
@@ -976,23 +977,37 @@ __global__ __launch_bounds__(64, BP_WAVES) void k_lz4_bitplanes_uni(const uint8_
     static_assert(sizeof(BpBoth) <= BP_PLANE_LDS, "32 planes per CU");
     __shared__ BpBoth lds;
     const uint32_t lane = threadIdx.x;
-    // (XCD-aware order: of a group of 128 workgroups, XCD slot r & 7 takes blocks 8 (r & 7) .. 8 (r & 7) + 7 of the group's 64, both planes)
-    const uint32_t r = blockIdx.x & 127u, k = r >> 3;
-    const uint32_t bid = (blockIdx.x >> 7) * 64u + (r & 7u) * 8u + (k >> 1), wave = k & 1u;   // (wave: the byte plane, as before)
+    uint32_t bid, wave;   // (XCD-aware order, common.h; wave: the byte plane, as before)
+    planes_wg_plane(blockIdx.x, &bid, &wave);
     if (bid >= n_blocks) return;
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-    uint64_t col;
-    uint32_t row, bi;
-    planes_block(pg, bid, &col, &row, &bi);
-    const u32x2 *pl = reinterpret_cast<const u32x2 *>(src + planes_piece(pg, col, bi * 16u + (lane >> 2), wave, row)) + (lane & 3u);
+    // (block -> column, row, block in the row by the launch's reciprocals: the two divisions of planes_block were 32 scalar and 13
+    // vector instructions of the 157 in front of the address of the wave's only global load.  dv is the LAST argument on purpose: in
+    // front of n_blocks the same code takes 70 VGPRs instead of 64 in every instantiation — the order of the kernel-argument
+    // loads moves the register allocation of the whole body; tests/test_lz4_plane_occupancy.py holds the line)
+    const u32x2 *pl = reinterpret_cast<const u32x2 *>(src + planes_lane_bytes(pg, dv, bid, wave, lane));
     const u32x2 one = *pl, exc = *(pl + (uint64_t)pg.S_pad * 8ull);
     // (both branches store the bit map of the nonzero bytes, at the same place: stored once in front of the branch, every
     // instantiation but depth 0 takes 72 instead of 70 VGPRs)
     if (__builtin_amdgcn_ballot_w64((exc.x | exc.y) != 0u) == 0ull) {   // no missing call in this plane: the plain coder
+        // An empty plane (3.6 % of the flagship's: padded sample rows, columns rounded up to whole chunks) leaves at once with
+        // the stream every instantiation's bp_code_plane makes of 4096 zeros — tools/sim/gapenc_ref.c's, at every depth and
+        // with the lazy rule: a zero literal, an offset-1 match of 4090 (15 + 15 x 255 + 246 + 4), the last five literals.
+        if (BP_SKIP < 6 && __builtin_amdgcn_ballot_w64((one.x | one.y) != 0u) == 0ull) {
+            const uint64_t sidx = (uint64_t)bid * 2u + wave;
+            const uint32_t v = lane == 0u ? 0x1Fu : lane == 2u ? 1u : lane == 19u ? 0xF6u : lane == 20u ? 0x50u : (lane - 4u < 15u ? 0xFFu : 0u);
+            if (lane < BP_EMPTY_BYTES) scratch[sidx * slot_bytes + lane] = (uint8_t)v;
+            if (lane == 0) csize[sidx] = BP_EMPTY_BYTES;
+            return;
+        }
         BpLds<CHAIN, false> &S = lds.p;
         S.bm[2u * lane] = one.x;
         S.bm[2u * lane + 1u] = one.y;
         if (lane < 4u) S.bm[128u + lane] = 0u;
+        if (BP_SKIP >= 6) {
+            if (lane == 0) csize[(uint64_t)bid * 2u + wave] = S.bm[5] & 1u;
+            return;
+        }
         bp_code_plane<DEPTH, false, LAZY>(S, one.x, one.y, 0u, 0u, false, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
     } else {
         BpLds<CHAIN, true> &S = lds.x;
@@ -1005,6 +1020,10 @@ __global__ __launch_bounds__(64, BP_WAVES) void k_lz4_bitplanes_uni(const uint8_
         S.xm[2u * lane + 1u] = exc.y;
         if (lane < 4u) S.xm[128u + lane] = 0u;
         if (lane < 24u) S.cls[lane] = 0u;
+        if (BP_SKIP >= 6) {
+            if (lane == 0) csize[(uint64_t)bid * 2u + wave] = (S.bm[5] ^ S.xm[5]) & 1u;
+            return;
+        }
         bp_code_plane<DEPTH, true, LAZY>(S, one.x, one.y, exc.x, exc.y, nonbinary, bid, wave, lane, scratch, slot_bytes, csize, flags, tag);
     }
 }
@@ -1016,8 +1035,8 @@ static void bp_launch(bool planes, const uint8_t *d_src, PlanesGeom pg, uint32_t
                       uint32_t *d_flags, uint32_t tag, hipStream_t st)
 {
     if (planes)
-        hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((n_blocks + 63u) / 64u * 128u), dim3(64), 0, st, d_src, pg, n_blocks, d_scratch, slot_bytes,
-                           d_csize, d_flags, tag);
+        hipLaunchKernelGGL((k_lz4_bitplanes_uni<D, LZ>), dim3((n_blocks + 63u) / 64u * 128u), dim3(64), 0, st, d_src, pg, n_blocks, d_scratch,
+                           slot_bytes, d_csize, d_flags, tag, planes_div(pg));
     else
         hipLaunchKernelGGL((k_lz4_bitplanes<D, LZ>), dim3(n_blocks), dim3(128), 0, st, d_src, pg, n_blocks, d_scratch, slot_bytes, d_csize, d_flags, tag);
 }
@@ -1031,6 +1050,11 @@ int launch_lz4_bitplanes(const uint8_t *d_src, bool planes, PlanesGeom pg, uint6
     if (n_blocks == 0) return HHGT_OK;
     if (2u * n_blocks > 0x7fffff80ull) {   // (the plane-input grid: two workgroups per block, rounded up to whole groups of 128)
         hhgt_set_error("lz4: too many blocks");
+        return HHGT_ERR_ARG;
+    }
+    // (planes_block32's reciprocals are exact for block ids below 2^31 — above — and divisors below 2^31)
+    if (planes && (pg.bpr == 0 || (uint64_t)pg.S_pad * pg.bpr == 0 || (uint64_t)pg.S_pad * pg.bpr > 0x7fffffffull)) {
+        hhgt_set_error("lz4: a chunk column of the planes must hold between 1 and 2^31 - 1 blocks");
         return HHGT_ERR_ARG;
     }
     const auto launch = lazy ? (depth == 2 ? bp_launch<2, true> : bp_launch<12, true>)
