@@ -186,7 +186,7 @@ extern "C" void hhgt_ctx_destroy(hhgt_ctx *c)
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     c->enc.each([](DevBuf &b) { b.release(); });
-    DevBuf *bufs[] = {&c->counters, &c->cursor, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n, &c->ld_bits, &c->score_part};
+    DevBuf *bufs[] = {&c->counters, &c->cursor, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n, &c->ld_bits, &c->score_part, &c->clump_ws};
     for (DevBuf *b : bufs) b->release();
     for (auto &w : c->cw) {
         DevBuf *wb[] = {&w.lz_scratch, &w.lz_csize, &w.lz_flags, &w.fr_bsize, &w.fr_csize, &w.fr_flags};
@@ -1366,6 +1366,69 @@ extern "C" int hhgt_ld_prune(hhgt_ctx *c, const uint32_t *d_table, uint64_t n_va
         uint64_t *bits = c->ld_bits.as<uint64_t>();
         TRY(timed(c, st, HHGT_STAGE_LD_PRUNE, [&] { return launch_ld_exceeds(d_table, n_var, window, r2, bits, st); }));
         return timed(c, st, HHGT_STAGE_LD_WALK, [&] { return launch_ld_walk(bits, n_var, window, d_keep, st); });
+    });
+}
+
+// n_var of the clumping calls: int32 owners, 2^33 link words
+static int check_clump_variants(const char *who, uint64_t n_var)
+{
+    if (n_var <= 0x7fffffffull) return HHGT_OK;
+    hhgt_set_error("%s: %llu variants (below 2^31)", who, (unsigned long long)n_var);
+    return HHGT_ERR_ARG;
+}
+
+extern "C" int hhgt_ld_decisions(hhgt_ctx *c, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2,
+                                 const int64_t *d_pos, int64_t max_dist, uint64_t *d_bits, void *stream)
+{
+    TRY(check_ld_args("ld_decisions", c, window, &r2, !n_var ? nullptr : !d_table ? "table" : !d_bits ? "link bits" : nullptr, d_table));
+    TRY(check_clump_variants("ld_decisions", n_var));
+    if (max_dist < 0) {
+        hhgt_set_error("ld_decisions: max_dist %lld (at least 0)", (long long)max_dist);
+        return HHGT_ERR_ARG;
+    }
+    return launch_on_device(c, stream, HHGT_STAGE_LD_PRUNE, n_var != 0, [&](hipStream_t st) {
+        return launch_ld_decisions(d_table, n_var, window, r2, d_pos, max_dist, d_bits, st);
+    });
+}
+
+// the rounds go out in batches of CLUMP_BATCH launches, each with a counter of its own; the host reads a batch's counters in
+// one copy and stops at the first round that decided nothing (the state no longer changes: whichever buffer was written
+// last holds it).  All of it under the walk's timer.
+extern "C" int hhgt_ld_clump(hhgt_ctx *c, const uint64_t *d_bits, uint64_t n_var, uint32_t window, const uint32_t *d_rank,
+                             const uint8_t *d_eligible, int32_t *d_owner, uint32_t *rounds, void *stream)
+{
+    if (rounds) *rounds = 0;
+    TRY(check_ld_args("ld_clump", c, window, nullptr, !n_var ? nullptr : !d_bits ? "link bits" : !d_rank ? "ranks"
+                      : !d_eligible ? "eligible flags" : !d_owner ? "owners" : nullptr, nullptr));
+    TRY(check_clump_variants("ld_clump", n_var));
+    return on_device(c, stream, n_var != 0, [&](hipStream_t st) {
+        const uint32_t nq = (window + 63u) / 64u;
+        TRY(c->clump_ws.ensure(ClumpWs::bytes(n_var, nq)));
+        const ClumpWs ws(c->clump_ws.p, n_var, nq);
+        uint64_t decided = 0;
+        TRY(timed(c, st, HHGT_STAGE_LD_WALK, [&] {
+            TRY(launch_clump_blockers(d_bits, n_var, window, d_rank, d_eligible, ws, st));
+            uint32_t from = 0, h_count[CLUMP_BATCH];
+            for (bool more = true; more;) {
+                HIP_TRY(hipMemsetAsync(ws.counters, 0, sizeof(h_count), st));
+                for (uint32_t r = 0; r < CLUMP_BATCH; ++r, from ^= 1u) TRY(launch_clump_round(n_var, window, ws, from, ws.counters + r, st));
+                HIP_TRY(hipMemcpyAsync(h_count, ws.counters, sizeof(h_count), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                for (uint32_t r = 0; r < CLUMP_BATCH && more; ++r) {
+                    if (h_count[r] == 0u) {
+                        more = false;
+                    } else if (++decided > n_var) {
+                        hhgt_set_error("ld_clump: %llu rounds over %llu variants still decide", (unsigned long long)decided,
+                                       (unsigned long long)n_var);
+                        return HHGT_ERR_HIP;
+                    }
+                }
+            }
+            return launch_clump_owners(d_bits, n_var, window, d_rank, ws, from, d_owner, st);
+        }));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (rounds) *rounds = (uint32_t)decided;
+        return HHGT_OK;
     });
 }
 

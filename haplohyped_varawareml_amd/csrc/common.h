@@ -341,6 +341,7 @@ struct hhgt_ctx {
     DevBuf dec_bad, oh_ovl, oh_lut, crc_x2n;
     DevBuf ld_bits;        // hhgt_ld_prune: the per-pair decisions between its two kernels
     DevBuf score_part;     // hhgt_score_sums: the spans' partial sums between its two kernels
+    DevBuf clump_ws;       // hhgt_ld_clump: forward links, blockers, the two states and the rounds' counters (ClumpWs)
     bool crc_x2n_ready = false;
     // pinned host mirror for counters
     DevCounters *h_counters = nullptr;
@@ -465,6 +466,29 @@ int launch_ld_counts(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, uin
 uint32_t ld_walk_words(uint32_t window);
 int launch_ld_exceeds(const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, uint64_t *d_bits, hipStream_t st);
 int launch_ld_walk(const uint64_t *d_bits, uint64_t n_var, uint32_t window, uint8_t *d_keep, hipStream_t st);
+int launch_ld_decisions(const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, const int64_t *d_pos, int64_t max_dist,
+                        uint64_t *d_bits, hipStream_t st);
+// clump.hip
+#define CLUMP_BATCH 8u      // rounds between two reads of the counters
+// hhgt_ld_clump's workspace, carved out of one buffer: uint64 fwd [n][nq] (bit d: linked with variant k + 1 + d), uint64
+// blk [n][2 nq] (the blockers: nq words back, nq words forward), uint8 state [2][n], uint32 counters [CLUMP_BATCH]
+struct ClumpWs {
+    uint64_t *fwd, *blk;
+    uint32_t *counters;
+    uint8_t *state[2];
+    static size_t bytes(uint64_t n, uint32_t nq) { return (size_t)n * nq * 24u + CLUMP_BATCH * 4u + 2u * (size_t)n; }
+    ClumpWs(void *p, uint64_t n, uint32_t nq)
+    {
+        fwd = reinterpret_cast<uint64_t *>(p), blk = fwd + n * nq;
+        counters = reinterpret_cast<uint32_t *>(blk + 2u * n * nq);
+        state[0] = reinterpret_cast<uint8_t *>(counters + CLUMP_BATCH), state[1] = state[0] + n;
+    }
+};
+int launch_clump_blockers(const uint64_t *d_bits, uint64_t n_var, uint32_t window, const uint32_t *d_rank, const uint8_t *d_eligible,
+                          const ClumpWs &ws, hipStream_t st);
+int launch_clump_round(uint64_t n_var, uint32_t window, const ClumpWs &ws, uint32_t from, uint32_t *d_counter, hipStream_t st);
+int launch_clump_owners(const uint64_t *d_bits, uint64_t n_var, uint32_t window, const uint32_t *d_rank, const ClumpWs &ws,
+                        uint32_t from, int32_t *d_owner, hipStream_t st);
 // assoc.hip
 int launch_assoc_sums(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
                       double *d_sums, hipStream_t st);

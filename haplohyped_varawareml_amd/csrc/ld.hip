@@ -1,7 +1,8 @@
 // Linkage disequilibrium between nearby variants from genotype bit planes: hhgt_variant_planes turns hhgt_genotype_planes'
 // sample-major rows (32 variants per word) into variant-major rows (32 samples per word), hhgt_ld_counts reduces every pair
 // of rows at most `window` apart to eight popcounts, hhgt_ld_prune decides r^2 > t per pair from those integers and walks the
-// variants greedily.  include/hhgt.h has the contract.
+// variants greedily; hhgt_ld_decisions makes the same decisions, with a distance cut, for the clumping of clump.hip.
+// include/hhgt.h has the contract.
 #include "common.h"
 #include "plane_tiles.h"
 
@@ -200,6 +201,47 @@ __global__ __launch_bounds__(256) void k_ld_exceeds(const uint4 *__restrict__ ta
     }
     const uint64_t m = __ballot(x);
     if ((threadIdx.x & 63u) == 0u) bits[unit] = m;
+}
+
+// hhgt_ld_decisions: k_ld_exceeds with a distance cut and the public layout of include/hhgt.h — nq = ceil(window / 64) words
+// per variant, not the walk's power of two.  pos (NULL: no limit) is laid out like the table's rows: pos[window + v] is
+// variant v of the tile.  The difference of two int64 is taken in uint64, where it cannot overflow.
+__global__ __launch_bounds__(256) void k_ld_decisions(const uint4 *__restrict__ table, uint32_t n_var, uint32_t window,
+                                                      uint32_t nq, double t, const int64_t *__restrict__ pos,
+                                                      uint64_t max_dist, uint64_t *__restrict__ bits)
+{
+    const uint64_t unit = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (unit >= (uint64_t)n_var * nq) return;
+    const uint32_t v = (uint32_t)(unit / nq), q = (uint32_t)(unit % nq), d = q * 64u + (threadIdx.x & 63u);
+    bool x = false;
+    if (d < window) {
+        const uint64_t u = (uint64_t)window + v - 1u - d;
+        const uint4 *e = table + (u * window + d) * 2u;
+        x = ld_exceeds(e[0], e[1], t);
+        if (x && pos) {
+            const int64_t a = pos[(uint64_t)window + v], b = pos[u];
+            x = (a >= b ? (uint64_t)a - (uint64_t)b : (uint64_t)b - (uint64_t)a) <= max_dist;
+        }
+    }
+    const uint64_t m = __ballot(x);
+    if ((threadIdx.x & 63u) == 0u) bits[unit] = m;
+}
+
+int launch_ld_decisions(const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, const int64_t *d_pos, int64_t max_dist,
+                        uint64_t *d_bits, hipStream_t st)
+{
+    if (n_var == 0) return HHGT_OK;
+    const uint32_t nq = (window + 63u) / 64u;
+    const uint64_t blocks = (n_var * nq + 3u) / 4u;
+    if (n_var > 0x7fffffffull || blocks > 0x7fffffffull) {
+        hhgt_set_error("ld_decisions: %llu variants at window %u (at most 2^31 - 1 variants, 2^33 decision words)",
+                       (unsigned long long)n_var, window);
+        return HHGT_ERR_ARG;
+    }
+    hipLaunchKernelGGL(k_ld_decisions, dim3((uint32_t)blocks), dim3(256), 0, st, reinterpret_cast<const uint4 *>(d_table),
+                       (uint32_t)n_var, window, nq, r2, d_pos, (uint64_t)max_dist, d_bits);
+    HIP_TRY(hipGetLastError());
+    return HHGT_OK;
 }
 
 // one wave.  K[q] bit l = the keep flag of the variant 64 q + l + 1 places before the current one: a shift register of

@@ -687,6 +687,60 @@ class Context:
             check(self.lib.hhgt_ld_prune(self.h, _ptr_if_any(table), n, window, float(r2), _ptr_if_any(keep), _stream()))
         return keep
 
+    def ld_decisions(self, table, r2, pos=None, max_dist=None, bits=None):
+        """the link bits of one tile (hhgt_ld_decisions), without a walk: table as ld_prune takes it, an int32 tensor
+        [window + n, window, 8] whose first `window` rows are carried; pos, an int64 tensor [window + n] laid out like the
+        rows, and max_dist >= 0 together set a distance limit (inclusive), neither means none.  bits, an int64 tensor
+        [n, ceil(window / 64)] (default: a new one), gets at bit d % 64 of word [k, d // 64] whether the pair (k - 1 - d, k)
+        is linked: ld_exceeds of the entry, strictly, and within max_dist — every word written, bits at or past `window`
+        0.  -> bits"""
+        if (table.dtype not in (torch.int32, torch.uint32) or table.dim() != 3 or table.shape[2] != 8
+                or table.shape[0] < table.shape[1] or table.shape[1] < 1 or not table.is_contiguous()):
+            raise ValueError("table: a contiguous int32 tensor [window + n, window, 8]")
+        window = int(table.shape[1])
+        n = int(table.shape[0]) - window
+        if (pos is None) != (max_dist is None):
+            raise ValueError("pos and max_dist: both or neither")
+        if pos is not None and (pos.dtype != torch.int64 or tuple(pos.shape) != (window + n,) or not pos.is_contiguous()
+                                or pos.device != table.device):
+            raise ValueError(f"pos: a contiguous int64 tensor [{window + n}] on the table's device")
+        if max_dist is not None and not 0 <= int(max_dist) < 1 << 63:
+            raise ValueError(f"max_dist {max_dist} (at least 0)")
+        with torch.cuda.device(self.device):
+            shape = (n, -(-window // 64))
+            if bits is None:        # (every word is written: no need for zeros)
+                bits = torch.empty(shape, dtype=torch.int64, device=self.device)
+            bits = self._out_arg(bits, torch.int64, shape, "bits")
+            check(self.lib.hhgt_ld_decisions(self.h, _ptr_if_any(table), n, window, float(r2), None if pos is None else _ptr(pos),
+                                             0 if max_dist is None else int(max_dist), _ptr_if_any(bits), _stream()))
+        return bits
+
+    def ld_clump(self, bits, window, rank, eligible, owner=None):
+        """LD clumping from link bits (hhgt_ld_clump): bits an int64 tensor [n, ceil(window / 64)] as ld_decisions writes
+        it, for all n counted variants of a group at once; rank an int32 tensor [n] (store_stats.clump_rank: the place in
+        a stable ascending sort by p), eligible a uint8 or bool tensor [n] (p <= p1).  owner, an int32 tensor [n]
+        (default: a new one), gets per variant its own offset if it is an index variant, the offset of the linked index
+        variant of lowest rank if it has one, else -1 — store_stats.clump_reference is the contract.  The call waits for
+        the stream.  -> (owner, rounds): rounds the number of rounds that decided at least one variant"""
+        window = int(window)
+        if not 0 <= window < 1 << 32:
+            raise ValueError(f"window {window}")
+        nq = -(-max(min(window, 1024), 1) // 64)
+        if bits.dtype != torch.int64 or bits.dim() != 2 or bits.shape[1] != nq or not bits.is_contiguous():
+            raise ValueError(f"bits: a contiguous int64 tensor [n, {nq}]")
+        n = int(bits.shape[0])
+        for name, t, dtypes in (("rank", rank, (torch.int32, torch.uint32)), ("eligible", eligible, (torch.uint8, torch.bool))):
+            if t.dtype not in dtypes or tuple(t.shape) != (n,) or not t.is_contiguous() or t.device != bits.device:
+                raise ValueError(f"{name}: a contiguous {str(dtypes[0]).split('.')[1]} tensor [{n}] on the bits' device")
+        rounds = C.c_uint32(0)
+        with torch.cuda.device(self.device):
+            if owner is None:       # (every entry is written: no need for zeros)
+                owner = torch.empty((n,), dtype=torch.int32, device=self.device)
+            owner = self._out_arg(owner, torch.int32, (n,), "owner")
+            check(self.lib.hhgt_ld_clump(self.h, _ptr_if_any(bits), n, window, _ptr_if_any(rank), _ptr_if_any(eligible),
+                                         _ptr_if_any(owner), C.byref(rounds), _stream()))
+        return owner, int(rounds.value)
+
     # ---- BGZF on the device (SURVEY §8 f-4) -------------------------------------------------------
     def inflate_bgzf(self, raw, return_status=False, check_crc=True):
         """raw: host bytes / uint8 array holding whole BGZF members.  The host walks the member headers

@@ -19,12 +19,13 @@ case / control phenotypes (GenotypeStore.assoc_logistic); polygenic_scores(varia
 per-donor sums of per-allele effects over listed variants (GenotypeStore.score), and project_components(k,
 train_donor_ids, donor_ids, ...) principal components fitted on some donors and the projection of others onto them
 (GenotypeStore.project); feature_matrix(chromosomes, donor_ids, min_maf, ld_window, ..., train_donor_ids) donors x selected
-variants as a model-ready device tensor with its variant records (GenotypeStore.feature_matrix).  The reference has no such
-queries."""
+variants as a model-ready device tensor with its variant records (GenotypeStore.feature_matrix); clump(variants, p, ...) the
+LD clumps of a scan's p-values, one record per listed variant with its role and its index variant (GenotypeStore.ld_clump).
+The reference has no such queries."""
 import numpy as np
 
 from .store import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
-                    check_components, grm_from_sums, kinship_from_counts, top_eigenpairs, variant_columns)
+                    check_components, clump_summary, grm_from_sums, kinship_from_counts, top_eigenpairs, variant_columns)
 
 
 def _span(starts, start, end):
@@ -275,6 +276,92 @@ class VCFH5Reader:
             projected = self.store.project(vectors, values, who, donors, names, variant_mask=masks or None).cpu().numpy()
         return self._component_records(train, vectors), self._component_records(donors, projected), values
 
+    @staticmethod
+    def _listed_keys(variants):
+        """listed variants — a numpy record array with chrom, pos (1-based), ref, alt, or a sequence of such 4-tuples; str
+        or bytes — -> their keys, a list of (chrom without a leading "chr", pos, ref, alt)"""
+        if isinstance(variants, np.ndarray) and variants.dtype.names:
+            columns = [variants[f].tolist() for f in ("chrom", "pos", "ref", "alt")]
+        else:
+            columns = [list(c) for c in zip(*(tuple(x) for x in variants))] or [[], [], [], []]
+        text = lambda col: [x.decode() if isinstance(x, bytes) else str(x) for x in col]                       # noqa: E731
+        chrom, ref, alt = text(columns[0]), text(columns[2]), text(columns[3])
+        pos = np.array([int(p) for p in columns[1]], dtype=np.int64)
+        return list(zip((c[3:] if c.startswith("chr") else c for c in chrom), pos.tolist(), ref, alt))
+
+    def _match_listed(self, who, keys, groups):
+        """the listed variants (_listed_keys) matched to the store's, for `who` in the message: by (group chr_{N} of the
+        chrom, pos, REF base, ALT base) — one base each, no flipping; the first of a store's equal keys is the match —
+        -> {group: (listed, where, n_var)} for the groups of `groups` with a match, in their order: the indices into keys of
+        the matched variants, the offsets of their matches in the group, the group's number of variants.  ValueError for
+        a key listed twice."""
+        if len(set(keys)) != len(keys):
+            seen = set()
+            twice = next(k for k in keys if k in seen or seen.add(k))
+            raise ValueError(f"{who}: chr{twice[0]}:{twice[1]} {twice[2]}>{twice[3]} is listed twice")
+        out = {}
+        for g in groups:
+            mine = [i for i, k in enumerate(keys) if "chr_" + k[0] == g and len(k[2]) == 1 and len(k[3]) == 1]
+            if not mine:
+                continue
+            start, s_ref, s_alt, _ = self.store.variants(g)
+            # one int64 per variant: (0-based start, REF base, ALT base); the first of a store's equal keys is the match
+            code = (start.astype(np.int64) << 16) | (s_ref.astype(np.int64) << 8) | s_alt.astype(np.int64)
+            order = np.argsort(code, kind="stable")
+            want = np.array([((keys[i][1] - 1) << 16) | (ord(keys[i][2]) << 8) | ord(keys[i][3]) for i in mine], dtype=np.int64)
+            at = np.searchsorted(code[order], want)
+            hit = (at < len(code)) & (code[order][np.minimum(at, len(code) - 1)] == want) if len(code) else np.zeros(len(mine), bool)
+            if hit.any():
+                out[g] = (np.array(mine)[hit], order[at[hit]], len(start))
+        return out
+
+    def clump(self, variants, p, chromosomes=None, donor_ids=None, p1=1e-4, p2=1e-2, r2=0.5, window=1024, kb=250.0):
+        """LD clumping of the listed variants by their p-values -> (records, info).  variants: n records with chrom, pos
+        (1-based), ref, alt, matched to the store's exactly as polygenic_scores matches its weights (no flipping; a key
+        listed twice: ValueError); p: float64 [n], NaN for a variant that takes no part.  Each group of chromosomes (one
+        name or a list; None: every group) is clumped on its own, over donor_ids (default: every sample), by
+        GenotypeStore.ld_clump (p1, p2, r2, window, kb mean what they mean there; its rule is this project's, not plink's
+        .clumped file).  records: host numpy, one per matched listed variant with p <= p2, in group and file order — chrom,
+        start (0-based), ref, alt, p, role (store_stats.CLUMP_NONE, CLUMP_INDEX, CLUMP_CLUMPED), index (the row, within
+        these records, of its index variant: its own row for an index, -1 for none), n_clumped (the members an index
+        variant claimed; 0 otherwise), listed (its row in `variants`).  info: matched, unmatched (listed variants the
+        store does not have) and window_short (GenotypeStore.stats["clump_window_short"] of the calls: variants where
+        `window`, not kb, ended the search)."""
+        st = self.store
+        groups, _, who = self._cohort(chromosomes, donor_ids)
+        keys = self._listed_keys(variants)
+        p = np.asarray(p, dtype=np.float64).reshape(-1)
+        if len(p) != len(keys):
+            raise ValueError(f"clump: {len(p)} p-values for {len(keys)} variants")
+        matches = self._match_listed("clump", keys, groups)
+        tables = {g: st.variants(g) for g in matches}
+        width = max([len(r[1].encode()) for t in tables.values() for r in t[3]] + [1])
+        dtype = [("chrom", f"S{width}"), ("start", np.uint32), ("ref", "S10"), ("alt", "S10"), ("p", np.float64),
+                 ("role", np.int8), ("index", np.int64), ("n_clumped", np.int64), ("listed", np.int64)]
+        parts, base, short0 = [], 0, st.stats["clump_window_short"]
+        for g, (listed, where, n_var) in matches.items():
+            pg = np.full(n_var, np.nan)
+            pg[where] = p[listed]
+            row_of = np.full(n_var, -1, np.int64)
+            row_of[where] = listed
+            owner = st.ld_clump(g, pg, who, p1=p1, p2=p2, r2=r2, window=window, kb=kb).cpu().numpy()
+            with np.errstate(invalid="ignore"):
+                at = np.flatnonzero(pg <= p2)
+            rec = np.zeros(len(at), dtype=dtype)
+            self._variant_columns(rec, tables[g], width, at=at)
+            local = np.full(n_var, -1, np.int64)            # offsets into the group -> rows of this group's records
+            local[at] = np.arange(len(at))
+            own = np.where(owner[at] >= 0, local[np.maximum(owner[at], 0)], -1)
+            s = clump_summary(own, pg[at])
+            rec["p"], rec["listed"], rec["role"] = pg[at], row_of[at], s["role"]
+            rec["index"] = np.where(own >= 0, base + own, -1)
+            rec["n_clumped"][s["index"]] = s["n_clumped"]
+            parts.append(rec)
+            base += len(at)
+        matched = sum(len(m[0]) for m in matches.values())
+        info = dict(matched=matched, unmatched=len(keys) - matched, window_short=st.stats["clump_window_short"] - short0)
+        return (np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)), info
+
     def polygenic_scores(self, variants, weights, names=None, donor_ids=None, chromosomes=None, impute="mean", freq_donor_ids=None):
         """polygenic scores of donor_ids (default: every sample, store order) -> (records, info).  variants: n records with
         chrom, pos (1-based, the VCF's POS), ref, alt (a numpy record array with those fields, or a sequence of such
@@ -291,45 +378,21 @@ class VCFH5Reader:
         st = self.store
         groups, donors, who = self._cohort(chromosomes, donor_ids)
         freq = None if freq_donor_ids is None else self._cohort(chromosomes, list(freq_donor_ids))[2]
-        if isinstance(variants, np.ndarray) and variants.dtype.names:
-            columns = [variants[f].tolist() for f in ("chrom", "pos", "ref", "alt")]
-        else:
-            columns = [list(c) for c in zip(*(tuple(x) for x in variants))] or [[], [], [], []]
-        text = lambda col: [x.decode() if isinstance(x, bytes) else str(x) for x in col]                       # noqa: E731
-        chrom, ref, alt = text(columns[0]), text(columns[2]), text(columns[3])
-        pos = np.array([int(p) for p in columns[1]], dtype=np.int64)
+        keys = self._listed_keys(variants)
         w = np.asarray(weights, dtype=np.float64)
         w = w[:, None] if w.ndim == 1 else w
-        if w.ndim != 2 or w.shape[0] != len(pos) or not 1 <= w.shape[1] <= 64:
-            raise ValueError(f"polygenic_scores: weights {list(w.shape)} for {len(pos)} variants ([n, K], 1 <= K <= 64)")
+        if w.ndim != 2 or w.shape[0] != len(keys) or not 1 <= w.shape[1] <= 64:
+            raise ValueError(f"polygenic_scores: weights {list(w.shape)} for {len(keys)} variants ([n, K], 1 <= K <= 64)")
         names = [f"score{c + 1}" for c in range(w.shape[1])] if names is None else [str(x) for x in names]
         if len(names) != w.shape[1] or len(set(names)) != len(names) or set(names) & {"sample", "n_variants"}:
             raise ValueError(f"polygenic_scores: {w.shape[1]} distinct names other than sample and n_variants, not {names}")
-        keys = list(zip((c[3:] if c.startswith("chr") else c for c in chrom), pos.tolist(), ref, alt))
-        if len(set(keys)) != len(keys):
-            seen = set()
-            twice = next(k for k in keys if k in seen or seen.add(k))
-            raise ValueError(f"polygenic_scores: chr{twice[0]}:{twice[1]} {twice[2]}>{twice[3]} is listed twice")
         betas, masks, matched = {}, {}, 0
-        for g in groups:
-            mine = [i for i, k in enumerate(keys) if "chr_" + k[0] == g and len(k[2]) == 1 and len(k[3]) == 1]
-            if not mine:
-                continue
-            start, s_ref, s_alt, _ = st.variants(g)
-            # one int64 per variant: (0-based start, REF base, ALT base); the first of a store's equal keys is the match
-            code = (start.astype(np.int64) << 16) | (s_ref.astype(np.int64) << 8) | s_alt.astype(np.int64)
-            order = np.argsort(code, kind="stable")
-            want = np.array([((keys[i][1] - 1) << 16) | (ord(keys[i][2]) << 8) | ord(keys[i][3]) for i in mine], dtype=np.int64)
-            at = np.searchsorted(code[order], want)
-            hit = (at < len(code)) & (code[order][np.minimum(at, len(code) - 1)] == want) if len(code) else np.zeros(len(mine), bool)
-            if not hit.any():
-                continue
-            where = order[at[hit]]
-            betas[g] = np.zeros((len(start), w.shape[1]))
-            betas[g][where] = w[np.array(mine)[hit]]
-            masks[g] = np.zeros(len(start), bool)
+        for g, (listed, where, n_var) in self._match_listed("polygenic_scores", keys, groups).items():
+            betas[g] = np.zeros((n_var, w.shape[1]))
+            betas[g][where] = w[listed]
+            masks[g] = np.zeros(n_var, bool)
             masks[g][where] = True
-            matched += int(hit.sum())
+            matched += len(listed)
         scores, used = np.zeros((len(donors), w.shape[1])), {}
         if betas:
             scores, used = st.score(betas, list(betas), who, variant_mask=masks, impute=impute, freq_samples=freq)

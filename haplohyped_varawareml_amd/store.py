@@ -35,7 +35,7 @@ from .store_stats import (AC, AN, ASSOC_ALT, ASSOC_BETA, ASSOC_COMPLETE, ASSOC_H
                           REC_STEPS, REC_U0, assoc_design, assoc_from_sums, grm_from_sums, ibs_counts, logistic_design,
                           logistic_fit_reference, logistic_from_fit, logistic_score_design, logistic_score_from_sums,
                           normal_two_sided,
-                          check_components, kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts,
+                          check_components, clump_rank, clump_reference, clump_summary, kinship_from_counts, ld_exceeds, ld_sums, r2_from_counts,
                           standardized_dosages, student_t_two_sided, top_eigenpairs)
 from .store_stats import (SCORE_MAX_COLS, SCORE_SLICE, SCORE_SPAN, call_class_values, cast_class_values,  # noqa: F401
                           loadings_from_sums, projection_class_weights, score_class_weights)
@@ -130,7 +130,9 @@ STAT_KEYS = (
     "sample_count_blocks",                      # sample_counts (shares count_compressed_bytes_read): Blosc blocks it decoded
     # the plane queries: Blosc blocks their plane stage decoded, and what they reduced
     "pair_plane_blocks", "pair_words",          # pair_counts: plane words per row
-    "ld_plane_blocks", "ld_pairs",              # ld_counts / ld_prune: pairs of counted variants
+    "ld_plane_blocks", "ld_pairs",              # ld_counts / ld_prune / ld_clump: pairs of counted variants
+    # ld_clump: rounds that decided a variant; counted variants whose window-th follower is still within the distance limit
+    "clump_rounds", "clump_window_short",
     "grm_plane_blocks", "grm_words",            # grm_sums: plane words per row, read by its two reductions
     "assoc_plane_blocks", "assoc_variants",     # assoc_sums: counted variants
     "logistic_variants",                        # assoc_logistic: counted variants (per phenotype)
@@ -728,6 +730,98 @@ class GenotypeStore:
         out = torch.zeros(hi - lo, dtype=torch.bool, device=ctx.device)
         out[counted] = kept
         return out
+
+    def ld_clump(self, group, p, samples=None, v_lo=0, v_hi=None, variant_mask=None, p1=1e-4, p2=1e-2, r2=0.5, window=1024,
+                 kb=250.0, slab_bytes=None, plane_bytes=None):
+        """LD clumping of association results over the variants [v_lo, v_hi) of a group (group, samples, v_lo / v_hi,
+        variant_mask, slab_bytes, plane_bytes as in ld_prune): p is float64 [v_hi - v_lo], a host array or a device tensor,
+        NaN for a variant that takes no part (a finite value outside [0, 1]: ValueError).  -> an int64 device tensor
+        [v_hi - v_lo]: per variant the offset into the range of its index variant — its own offset for an index variant —,
+        -1 where it has none and outside the counted set.  The counted variants are those variant_mask marks whose p is
+        finite and <= p2, in order; neighbours are counted variants.  Two of them are linked iff they are at most `window`
+        counted variants apart, ld_exceeds holds between them (r^2 > r2, strictly, from the integer counts) and, unless kb
+        is None, their starts are at most int(kb * 1000) bp apart.  Walking the counted variants by ascending p (ties to
+        the earlier one), a variant with p <= p1 that is not yet claimed becomes an index variant and claims every linked
+        variant that is neither an index nor claimed: store_stats.clump_reference is the contract.  With p1 = p2 = 1, no
+        distance limit and p ascending in file order the index variants are the variants ld_prune keeps.  This is our
+        rule, not plink's .clumped file column for column: no --clump-replicate, no ranges, no secondary lists, and
+        neighbours are counted in variants first, then cut by distance — stats["clump_window_short"] counts the variants
+        whose `window`-th follower is still within the distance, where `window`, not kb, ended the search.  The tile loop
+        is ld_prune's with hhgt_ld_decisions in place of the walk: each tile's link bits go into one tensor [n_counted,
+        ceil(window / 64)] (128 bytes per variant at window 1024), which one hhgt_ld_clump call resolves in parallel
+        rounds (stats["clump_rounds"]; at most n_counted).  No genotype, count, bit or owner goes to the host; what does:
+        the counted numbers per plane window, the rounds' counters and the window-short count."""
+        import torch
+        lo, hi, counted, bits, pc = self._clump_links(group, p, samples, v_lo, v_hi, variant_mask, p1, p2, r2, window, kb,
+                                                      slab_bytes, plane_bytes)
+        out = torch.full((hi - lo,), -1, dtype=torch.int64, device=self._context().device)
+        if pc.numel():
+            owner, rounds = self._context().ld_clump(bits, int(window), clump_rank(pc).to(torch.int32),
+                                                     (pc <= float(p1)).to(torch.uint8))
+            self.stats["clump_rounds"] += rounds
+            own = owner.to(torch.int64)
+            out[counted] = torch.where(own >= 0, counted[own.clamp(min=0)], own)
+        return out
+
+    def _clump_links(self, group, p, samples, v_lo, v_hi, variant_mask, p1, p2, r2, window, kb, slab_bytes, plane_bytes):
+        """ld_clump up to the link bits: the arguments checked, the counted variants, the tile loop -> (lo, hi, counted — the
+        offsets into the range of the counted variants, an int64 device tensor —, bits int64 [n_counted, ceil(window / 64)],
+        the counted variants' p float64 [n_counted]); tools/clump_bench.py resolves the same bits on the host"""
+        import torch
+        window, r2, p1, p2 = int(window), float(r2), float(p1), float(p2)
+        if not 0.0 <= r2 <= 1.0:
+            raise ValueError(f"ld_clump: r2 {r2} (0 to 1)")
+        if not 0.0 <= p1 <= p2 <= 1.0:
+            raise ValueError(f"ld_clump: p1 {p1}, p2 {p2} (0 <= p1 <= p2 <= 1)")
+        if kb is not None and not 0.0 <= float(kb) < 1e12:
+            raise ValueError(f"ld_clump: kb {kb} (at least 0, or None)")
+        max_dist = None if kb is None else int(float(kb) * 1000)
+        if not isinstance(group, str) or group not in self.meta["groups"]:
+            raise KeyError(group)
+        if not 1 <= window <= 1024:
+            raise ValueError(f"ld_clump: window {window} (1 to 1024)")
+        _, [(group, lo, hi, _, mask)] = self._query("ld_clump", group, samples, v_lo, v_hi, variant_mask, single=True)
+        ctx = self._context()
+        p = p if torch.is_tensor(p) else torch.from_numpy(np.ascontiguousarray(p, dtype=np.float64))
+        if p.dtype != torch.float64 or tuple(p.shape) != (hi - lo,):
+            raise ValueError(f"ld_clump: p {list(p.shape)} {p.dtype}, expected float64 [{hi - lo}]")
+        p = p.to(ctx.device)
+        finite = torch.isfinite(p)
+        if bool((finite & ((p < 0.0) | (p > 1.0))).any()) or bool(torch.isinf(p).any()):
+            raise ValueError("ld_clump: a p-value outside [0, 1]")
+        take = finite & (p <= p2)
+        if mask is not None:
+            take &= self._device_bool(mask)
+        lo, hi, counted, n, rows = self._ld_rows("ld_clump", group, samples, lo, hi, take, window, slab_bytes, plane_bytes)
+        self.stats["ld_pairs"] += self._ld_pairs(n, window)
+        nq = -(-window // 64)
+        bits = torch.empty((n, nq), dtype=torch.int64, device=ctx.device)
+        pos = None
+        if max_dist is not None:        # laid out like a tile's rows: `window` places in front of the first variant
+            start = torch.from_numpy(self.variants(group)[0][lo:hi].astype(np.int64)).to(ctx.device)[counted]
+            pos = torch.cat([torch.zeros(window, dtype=torch.int64, device=ctx.device), start])
+            if n > window:
+                self.stats["clump_window_short"] += int((start[window:] - start[:-window] <= max_dist).sum())
+        tile = max(self._plane_budget(plane_bytes) // (window * 32) - window, LD_MIN_TILE)
+        carry = table = None
+        k0 = 0                              # the counted index of the next new row
+        for new in rows:
+            if carry is None:               # before the first variant: rows without a bit
+                carry = torch.zeros((3, window, new.shape[2]), dtype=torch.int32, device=ctx.device)
+            for t0 in range(0, int(new.shape[1]), tile):
+                buf = torch.cat([carry, new[:, t0:t0 + tile]], dim=1)
+                m = int(buf.shape[1]) - window
+                if table is None or table.shape[0] != buf.shape[1]:
+                    table = None
+                    table = torch.zeros((buf.shape[1], window, 8), dtype=torch.int32, device=ctx.device)
+                else:
+                    table.zero_()
+                ctx.ld_counts(buf, window, table=table)
+                ctx.ld_decisions(table, r2, None if pos is None else pos[k0:k0 + window + m], max_dist, bits=bits[k0:k0 + m])
+                carry = buf[:, -window:].contiguous()
+                k0 += m
+        bits[k0:].zero_()                   # (without a sample there are no rows, and nothing is linked)
+        return lo, hi, counted, bits, p[counted]
 
     def assoc_sums(self, group, W, samples=None, v_lo=0, v_hi=None, variant_mask=None, slab_bytes=None, plane_bytes=None):
         """the sums over samples behind an association scan of a group: a float64 device tensor [n_counted, 3, C] — for

@@ -93,6 +93,78 @@ def ld_exceeds(table, r2):
     return nn > float(r2) * den
 
 
+# ---- LD clumping: the rule (include/hhgt.h restates it; hhgt_ld_decisions / hhgt_ld_clump compute it on the device) ----------
+# Over the counted variants of a group, in file order: u < v are LINKED iff v - u <= window (in counted variants),
+# ld_exceeds(u, v, r2) — strictly > — and, with a distance limit, |pos_v - pos_u| <= max_dist (inclusive).  rank: the place
+# in a stable ascending sort by p, ties to the earlier variant.  Walk the variants in rank order: one that is eligible
+# (p <= p1) and not yet claimed becomes an INDEX variant and claims every linked variant that is neither an index nor
+# claimed.  owner[k]: k for an index; else the index that claimed it, which is the linked index of lowest rank; else -1
+# (p > p1 or unclaimed, and no index is linked to it).  With every variant eligible and p strictly ascending in file order
+# this is ld_prune's rule: owner[k] == k exactly where it keeps k.  It is this project's rule, not plink's .clumped file
+# column for column: no --clump-replicate, no ranges, no secondary lists.
+
+CLUMP_NONE, CLUMP_INDEX, CLUMP_CLUMPED = 0, 1, 2     # roles of clump_summary
+CLUMP_ROLE_NAMES = ("none", "index", "clumped")
+
+
+def clump_rank(p):
+    """p [n] (numpy or torch) -> rank [n], int64 in kind: the position of each variant in a stable ascending sort by p, so
+    that equal p rank in file order"""
+    if type(p).__module__.split(".")[0] == "torch":
+        import torch
+        order = torch.sort(p, stable=True).indices
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(len(order), dtype=order.dtype, device=order.device)
+        return rank
+    order = np.argsort(np.asarray(p), kind="stable")
+    rank = np.empty(len(order), np.int64)
+    rank[order] = np.arange(len(order))
+    return rank
+
+
+def clump_reference(linked_back, p, p1):
+    """the sequential rule above, plain numpy: linked_back bool [n, window] — [k, d]: variant k is linked with the variant
+    d + 1 places before it (entries that point before variant 0 are ignored) —, p float [n], p1 the index threshold
+    -> owner int64 [n].  This is the contract the device route is held to."""
+    linked_back = np.asarray(linked_back, bool)
+    p = np.asarray(p, np.float64)
+    n, window = len(p), linked_back.shape[1] if linked_back.ndim == 2 else 0
+    owner = np.full(n, -1, np.int64)
+    is_index = np.zeros(n, bool)
+    for k in np.argsort(p, kind="stable").tolist():
+        if not p[k] <= p1 or owner[k] >= 0:
+            continue
+        owner[k], is_index[k] = k, True
+        d = np.flatnonzero(linked_back[k, :min(window, k)])
+        back = k - 1 - d
+        e = np.arange(min(window, n - 1 - k))
+        ahead = k + 1 + e[linked_back[k + 1 + e, e]]
+        for nb in (back, ahead):
+            nb = nb[owner[nb] < 0]
+            owner[nb] = k
+    return owner
+
+
+def clump_summary(owner, p):
+    """owner int [n] of a clumping and its p [n] (host arrays) -> dict: role int8 [n] (CLUMP_NONE, CLUMP_INDEX,
+    CLUMP_CLUMPED), index int64 [m] (the index variants, in file order), n_clumped int64 [m] (the members each claimed,
+    itself not counted), members (a list of m int64 arrays, each in file order), best int64 [m] (1 + the number of index
+    variants with a lower p, ties to the earlier one: 1 is the strongest signal), n_index, n_clumped_total, n_none"""
+    owner, p = np.asarray(owner, np.int64), np.asarray(p, np.float64)
+    at = np.arange(len(owner))
+    role = np.where(owner == at, CLUMP_INDEX, np.where(owner >= 0, CLUMP_CLUMPED, CLUMP_NONE)).astype(np.int8)
+    index = at[role == CLUMP_INDEX]
+    claimed = at[role == CLUMP_CLUMPED]
+    slot = np.searchsorted(index, owner[claimed])
+    n_clumped = np.bincount(slot, minlength=len(index)).astype(np.int64)
+    by_slot = claimed[np.argsort(slot, kind="stable")]
+    members = np.split(by_slot, np.cumsum(n_clumped)[:-1]) if len(index) else []
+    best = np.empty(len(index), np.int64)
+    best[np.argsort(p[index], kind="stable")] = np.arange(1, len(index) + 1)
+    return dict(role=role, index=index, n_clumped=n_clumped, members=members, best=best, n_index=len(index),
+                n_clumped_total=len(claimed), n_none=int((role == CLUMP_NONE).sum()))
+
+
 # plane words of one f32 chain of hhgt_grm (HHGT_GRM_SPAN of include/hhgt.h): the K of its error bound is 32 * GRM_SPAN
 GRM_SPAN = 128
 

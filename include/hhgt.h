@@ -461,6 +461,43 @@ int hhgt_ld_counts(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uin
 int hhgt_ld_prune(hhgt_ctx *ctx, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, uint8_t *d_keep,
                   void *stream);
 
+/* LD clumping of association results, in two calls.  The rule (store_stats.clump_reference states it as plain numpy): over
+ * the counted variants of a group, in order, u < v are LINKED iff v - u <= window (in counted variants), exceeds(u, v, r2)
+ * as hhgt_ld_prune defines it (strictly >) and, with a distance limit, |pos_v - pos_u| <= max_dist.  Every variant has a
+ * rank (its place in a stable ascending sort by p: ties to the earlier variant) and a flag `eligible` (p <= p1).  Walking
+ * the variants in rank order, one that is eligible and not yet claimed becomes an INDEX variant and claims every linked
+ * variant that is neither an index nor claimed.  owner[k] is k for an index, the index that claimed k — the linked index
+ * of lowest rank — otherwise, and -1 where there is none.  With every variant eligible and the ranks ascending in order
+ * this is hhgt_ld_prune's rule: owner[k] == k exactly where it keeps k.  This is the project's rule, not plink's .clumped
+ * file column for column: no --clump-replicate, no ranges, no secondary lists.
+ *
+ * hhgt_ld_decisions writes the link bits of one tile of n_var variants, without a walk.  d_table is laid out exactly as
+ * for hhgt_ld_prune: uint32 [window + n_var][window][8], 32-byte aligned, the first `window` rows carried (rows of zeros
+ * link nothing).  d_pos is int64 [window + n_var], laid out like the table's rows, or NULL for no distance limit; max_dist
+ * >= 0, inclusive.  d_bits is uint64 [n_var][nq], nq = ceil(window / 64): bit d % 64 of word d / 64 of variant k is set iff
+ * d < window and the pair (k - 1 - d, k) is linked.  Every word is written, with plain stores; bits at or past `window`
+ * are 0.  Asynchronous.  1 <= window <= 1024, 0 <= r2 <= 1, n_var below 2^31, else HHGT_ERR_ARG. */
+int hhgt_ld_decisions(hhgt_ctx *ctx, const uint32_t *d_table, uint64_t n_var, uint32_t window, double r2, const int64_t *d_pos,
+                      int64_t max_dist, uint64_t *d_bits, void *stream);
+
+/* hhgt_ld_clump resolves a whole group from its link bits: d_bits is uint64 [n_var][nq] as above for ALL counted variants
+ * of the group (a set bit that points before variant 0 is ignored), d_rank uint32 [n_var], d_eligible uint8 [n_var] (0 or
+ * not 0), d_owner int32 [n_var], every entry written.  The walk above is the lexicographically first maximal independent
+ * set of the link graph among the eligible variants under the ranking, and is computed in its parallel form: (1) one pass
+ * gives every variant its blockers, the linked eligible neighbours of lower rank on either side; (2) rounds, one launch
+ * each over all variants, on double-buffered state: an undecided variant becomes not-index if a blocker was an index after
+ * the previous round, index if every blocker was decided, and waits otherwise; (3) one pass writes the owners.  There is
+ * no barrier between workgroups: a round is a launch, ordered by the stream.  The undecided eligible variant of lowest
+ * rank always decides, so at most n_var rounds decide anything; the loop stops after a round that decided nothing (the
+ * host reads the rounds' counters once per 8 rounds) and returns HHGT_ERR_HIP should n_var + 1 rounds all decide — a bug,
+ * whatever the ranks: d_rank need not be a permutation, two linked variants of equal rank block neither each other (both
+ * can be index variants; among linked indexes of equal rank the earlier one owns).  *rounds (host, may be NULL) receives
+ * the number of rounds that decided at least one variant: the same on every call.  Unlike every other LD call here, this
+ * one SYNCHRONISES the stream before it returns.  Workspace of the context: n_var * (3 nq * 8 + 2) bytes.
+ * 1 <= window <= 1024, n_var below 2^31, else HHGT_ERR_ARG; n_var == 0 is HHGT_OK with *rounds = 0. */
+int hhgt_ld_clump(hhgt_ctx *ctx, const uint64_t *d_bits, uint64_t n_var, uint32_t window, const uint32_t *d_rank,
+                  const uint8_t *d_eligible, int32_t *d_owner, uint32_t *rounds, void *stream);
+
 /* hhgt_assoc_sums reduces the rows of d_vplanes, uint32 [3][n_var][sw] (hhgt_variant_planes' layout: HET, COMPLETE, HOM_ALT;
  * bit s % 32 of word s / 32 of a row is plane row s; any three planes of that shape work: the arithmetic is defined on the
  * bits), against per-sample weights: d_w is double [32 * sw][n_cols], row-major, 8-byte aligned, finite; the caller puts zeros
