@@ -138,6 +138,7 @@ PROTOTYPES = {
     "hhgt_assoc_sums": (_i32, [_vp, _vp, _u64, _u64, _vp, _u32, _vp, _vp]),
     "hhgt_logistic_fit": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "hhgt_score_sums": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _u32, _vp, _vp]),
+    "hhgt_region_sums": (_i32, [_vp, _vp, _u64, _u64, _vp, _u32, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _pu64, _vp]),
     "hhgt_bgzf_scan": (_i32, [_vp, _u64, _u64, _vp, _vp, _vp, _vp, _pu64, _pu64]),
     "hhgt_inflate_members": (_i32, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _pu64, _vp]),
     "hhgt_onehot_windows": (_i32, [_vp, _vp, _u32, _u32, _vp, _i32, _vp, _vp, _vp]),

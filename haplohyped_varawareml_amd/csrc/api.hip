@@ -186,7 +186,8 @@ extern "C" void hhgt_ctx_destroy(hhgt_ctx *c)
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     c->enc.each([](DevBuf &b) { b.release(); });
-    DevBuf *bufs[] = {&c->counters, &c->cursor, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n, &c->ld_bits, &c->score_part, &c->clump_ws};
+    DevBuf *bufs[] = {&c->counters, &c->cursor, &c->dec_bad, &c->oh_ovl, &c->oh_lut, &c->crc_x2n, &c->ld_bits, &c->score_part, &c->region_part,
+                       &c->clump_ws};
     for (DevBuf *b : bufs) b->release();
     for (auto &w : c->cw) {
         DevBuf *wb[] = {&w.lz_scratch, &w.lz_csize, &w.lz_flags, &w.fr_bsize, &w.fr_csize, &w.fr_flags};
@@ -1496,4 +1497,54 @@ extern "C" int hhgt_score_sums(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n
                                 return launch_score_sums(d_planes, (uint32_t)n_rows, row_words, w_lo, w_hi, d_w, n_cols,
                                                          c->score_part.as<double>(), d_sums, st);
                             });
+}
+
+// hhgt_region_sums: the scalars are checked here, the tables — they are on the device — by the kernels, under the bad-counter
+// protocol of the row kernels (with_bad_counter) but with both launches under one timer of HHGT_STAGE_ASSOC, and with a
+// count above 0 an error of the arguments; the partial sums' workspace grows in the call
+extern "C" int hhgt_region_sums(hhgt_ctx *c, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, const double *d_w,
+                                uint32_t n_cols, const int64_t *d_pieces, uint64_t n_pieces, const int64_t *d_runs, uint64_t n_runs,
+                                uint64_t n_slots, uint64_t n_regions, double *d_sums, uint64_t *n_bad, void *stream)
+{
+    if (n_bad) *n_bad = 0;
+    const bool work = n_rows && n_pieces;
+    if (n_cols < 1u || n_cols > HHGT_REGION_MAX_COLS || row_words >= (1ull << 27) || n_rows >= (1ull << 32) || n_regions >= (1ull << 32)) {
+        hhgt_set_error("region_sums: %u columns (1 to %u), %llu rows (below 2^32) of %llu words (below 2^27), %llu regions (below 2^32)",
+                       n_cols, (unsigned)HHGT_REGION_MAX_COLS, (unsigned long long)n_rows, (unsigned long long)row_words,
+                       (unsigned long long)n_regions);
+        return HHGT_ERR_ARG;
+    }
+    TRY(check_not_null("region_sums", c, !work ? nullptr : !d_planes ? "planes" : !d_w ? "weights" : !d_pieces ? "pieces"
+                       : n_runs && !d_runs ? "runs" : !d_sums ? "sums" : nullptr));
+    const uint64_t tiles = (n_rows + 127u) / 128u, per_run = n_rows * n_cols;   // (below 2^25, below 2^36)
+    if (n_pieces >= (1ull << 31) || tiles * n_pieces >= (1ull << 31) || n_runs >= (1ull << 31) || n_slots >= (1ull << 31)
+        || (per_run && (n_runs * per_run + 255u) / 256u >= (1ull << 31)) || n_slots * per_run >= (1ull << 40)) {
+        hhgt_set_error("region_sums: %llu pieces, %llu runs and %llu slots over %llu rows of %u columns: more than a launch or the workspace takes",
+                       (unsigned long long)n_pieces, (unsigned long long)n_runs, (unsigned long long)n_slots,
+                       (unsigned long long)n_rows, n_cols);
+        return HHGT_ERR_ARG;
+    }
+    if (off_alignment(d_w, 8) || off_alignment(d_sums, 8) || off_alignment(d_pieces, 8) || off_alignment(d_runs, 8)) {
+        hhgt_set_error("region_sums: the weights, the sums, the pieces and the runs must be 8-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    return on_device(c, stream, work, [&](hipStream_t st) {
+        TRY(c->region_part.ensure((size_t)(n_slots * per_run) * sizeof(double)));
+        TRY(c->dec_bad.ensure(8));
+        HIP_TRY(hipMemsetAsync(c->dec_bad.p, 0, 8, st));
+        TRY(timed(c, st, HHGT_STAGE_ASSOC, [&] {
+            return launch_region_sums(d_planes, (uint32_t)n_rows, row_words, d_w, n_cols, d_pieces, n_pieces, d_runs, n_runs, n_slots,
+                                      n_regions, c->region_part.as<double>(), d_sums, c->dec_bad.as<unsigned long long>(), st);
+        }));
+        if (!n_bad) return HHGT_OK;
+        uint64_t nb = 0;
+        HIP_TRY(hipMemcpyAsync(&nb, c->dec_bad.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        *n_bad = nb;
+        if (!nb) return HHGT_OK;
+        hhgt_set_error("region_sums: %llu pieces or runs outside rows of %llu words, %u words a piece, %llu regions or %llu slots",
+                       (unsigned long long)nb, (unsigned long long)row_words, (unsigned)HHGT_REGION_SPAN,
+                       (unsigned long long)n_regions, (unsigned long long)n_slots);
+        return HHGT_ERR_ARG;
+    });
 }

@@ -341,6 +341,7 @@ struct hhgt_ctx {
     DevBuf dec_bad, oh_ovl, oh_lut, crc_x2n;
     DevBuf ld_bits;        // hhgt_ld_prune: the per-pair decisions between its two kernels
     DevBuf score_part;     // hhgt_score_sums: the spans' partial sums between its two kernels
+    DevBuf region_part;    // hhgt_region_sums: the partial sums of the regions of several pieces, by slot
     DevBuf clump_ws;       // hhgt_ld_clump: forward links, blockers, the two states and the rounds' counters (ClumpWs)
     bool crc_x2n_ready = false;
     // pinned host mirror for counters
@@ -499,6 +500,10 @@ int launch_logistic_fit(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, 
 uint64_t score_spans(uint64_t n_words);   // spans of a range of n_words words: rows of d_part
 int launch_score_sums(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi, const double *d_w,
                       uint32_t n_cols, double *d_part, double *d_sums, hipStream_t st);
+// region.hip
+int launch_region_sums(const uint32_t *d_planes, uint32_t n_rows, uint64_t row_words, const double *d_w, uint32_t n_cols,
+                       const int64_t *d_pieces, uint64_t n_pieces, const int64_t *d_runs, uint64_t n_runs, uint64_t n_slots,
+                       uint64_t n_regions, double *d_part, double *d_sums, unsigned long long *d_bad, hipStream_t st);
 int launch_inflate(const uint8_t *d_src, uint64_t src_bytes, const uint64_t *d_comp_off, const uint32_t *d_comp_len,
                    const uint64_t *d_out_off, const uint32_t *d_isize, uint64_t n_members, uint8_t *d_dst,
                    uint64_t dst_bytes, uint32_t *d_status, const uint32_t *d_crc32, const uint32_t *d_x2n, hipStream_t st);

@@ -672,6 +672,41 @@ class Context:
                                            _ptr_if_any(sums), _stream()))
         return sums
 
+    def region_sums(self, planes, w, pieces, runs, n_slots, n_regions, sums=None, wait=True):
+        """per-region sums of per-variant weights under the bits (hhgt_region_sums) of genotype planes [3, n, words]: w is a
+        float64 tensor [3, 32 * words, n_cols] (1 <= n_cols <= 16), indexed as score_sums' — finite inside the pieces, never
+        read outside them; pieces int64 [n_pieces, 4], runs int64 [n_runs, 3] and n_slots are store_plan.plan_regions'
+        tables (numpy arrays, which are copied to the device, or contiguous tensors on the planes' device).  The sums of
+        the pieces of region g are ADDED to sums[:, g, :] of `sums`, a float64 tensor [n, n_regions, n_cols] (default:
+        zeros), on the current stream — calls on one stream may accumulate into one table.  wait: wait for the kernels'
+        count of pieces and runs that lie outside the rows, the regions or the slots, and raise if there is one; False
+        leaves the call asynchronous, and such a piece is skipped.  -> sums"""
+        n, words = _planes_arg(planes)
+        n_cols = _weights_arg(w, (3, 32 * words), planes)
+        n_slots, n_regions = int(n_slots), int(n_regions)
+        if not 0 <= n_slots < 1 << 64 or not 0 <= n_regions < 1 << 64:
+            raise ValueError(f"n_slots {n_slots}, n_regions {n_regions}")
+        tables = []
+        for name, t, fields in (("pieces", pieces, 4), ("runs", runs, 3)):
+            if isinstance(t, np.ndarray):
+                if t.dtype != np.int64:
+                    raise ValueError(f"{name}: an int64 array [n, {fields}]")
+                t = torch.from_numpy(np.ascontiguousarray(t)).to(planes.device)
+            if (t.dtype != torch.int64 or t.dim() != 2 or t.shape[1] != fields or not t.is_contiguous()
+                    or t.device != planes.device):
+                raise ValueError(f"{name}: a contiguous int64 tensor [n, {fields}] on the planes' device")
+            tables.append(t)
+        pieces, runs = tables
+        with torch.cuda.device(self.device):
+            sums = self._out_arg(sums, torch.float64, (n, n_regions, n_cols), "sums")
+            if sums.device != planes.device:
+                raise ValueError("sums: on the planes' device")
+            n_bad = C.c_uint64(0)
+            check(self.lib.hhgt_region_sums(self.h, _ptr_if_any(planes), n, words, _ptr_if_any(w), n_cols, _ptr_if_any(pieces),
+                                            pieces.shape[0], _ptr_if_any(runs), runs.shape[0], n_slots, n_regions,
+                                            _ptr_if_any(sums), C.byref(n_bad) if wait else None, _stream()))
+        return sums
+
     def ld_prune(self, table, r2, keep=None):
         """the greedy walk (hhgt_ld_prune) over one tile: table is an int32 tensor [window + n, window, 8] — hhgt_ld_counts
         over the `window` variants before the tile (rows of zeros where there are none) followed by the tile's n —, keep a

@@ -20,12 +20,15 @@ per-donor sums of per-allele effects over listed variants (GenotypeStore.score),
 train_donor_ids, donor_ids, ...) principal components fitted on some donors and the projection of others onto them
 (GenotypeStore.project); feature_matrix(chromosomes, donor_ids, min_maf, ld_window, ..., train_donor_ids) donors x selected
 variants as a model-ready device tensor with its variant records (GenotypeStore.feature_matrix); clump(variants, p, ...) the
-LD clumps of a scan's p-values, one record per listed variant with its role and its index variant (GenotypeStore.ld_clump).
-The reference has no such queries."""
+LD clumps of a scan's p-values, one record per listed variant with its role and its index variant (GenotypeStore.ld_clump);
+burden(regions, donor_ids, max_maf, ...) one score per donor and region — the rare variants of a gene collapsed into one
+number (GenotypeStore.burden) — and burden_association(regions, phenotypes, ...) the regression or score test of phenotypes
+on those scores.  The reference has no such queries."""
 import numpy as np
 
-from .store import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore,
-                    check_components, clump_summary, grm_from_sums, kinship_from_counts, top_eigenpairs, variant_columns)
+from .store import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, assoc_design,
+                    check_components, clump_summary, dense_assoc, dense_logistic_score, grm_from_sums, kinship_from_counts,
+                    logistic_design, logistic_score_design, top_eigenpairs, variant_columns)
 
 
 def _span(starts, start, end):
@@ -460,6 +463,148 @@ class VCFH5Reader:
                     rec["steps"], rec["status"] = info[:, k, 0], info[:, k, 1]
                 parts[k].append(rec)
         return [np.concatenate(p) if p else np.zeros(0, dtype=dtype) for p in parts]
+
+    def _burden_regions(self, who, regions):
+        """regions (chrom, start, end, name), 0-based and half-open, any order -> (records, {group: rows}): one record per
+        region in the order asked — name, chrom (without a leading "chr"), start, end, lo, hi (its variants [lo, hi) of the
+        group: those whose start lies inside it) — and per group the rows of its regions.  KeyError for a chromosome the file
+        lacks, ValueError for a region that is not four fields with 0 <= start <= end"""
+        rows = []
+        for k, r in enumerate(regions):
+            r = tuple(r)
+            if len(r) != 4:
+                raise ValueError(f"{who}: region {k} is not (chrom, start, end, name)")
+            chrom = r[0].decode() if isinstance(r[0], bytes) else str(r[0])
+            name = r[3].decode() if isinstance(r[3], bytes) else str(r[3])
+            start, end = int(r[1]), int(r[2])
+            if not 0 <= start <= end:
+                raise ValueError(f"{who}: region {name} [{start}, {end}) on {chrom}: need 0 <= start <= end")
+            rows.append((chrom[3:] if chrom.startswith("chr") else chrom, start, end, name))
+        wn = max([len(r[3].encode()) for r in rows] + [1])
+        wc = max([len(r[0].encode()) for r in rows] + [1])
+        rec = np.zeros(len(rows), dtype=[("name", f"S{wn}"), ("chrom", f"S{wc}"), ("start", np.int64), ("end", np.int64),
+                                         ("lo", np.int64), ("hi", np.int64)])
+        groups = {}
+        for k, (chrom, start, end, name) in enumerate(rows):
+            rec[k] = (name.encode(), chrom.encode(), start, end, 0, 0)
+            groups.setdefault(self._group(self.store.samples[0] if self.store.samples else None, chrom), []).append(k)
+        for g, at in groups.items():
+            starts = self.store.variants(g)[0]
+            for k in at:
+                rec["lo"][k], rec["hi"][k] = _span(starts, rec["start"][k], rec["end"][k])
+        return rec, groups
+
+    def _burden(self, who_says, regions, donor_ids, max_maf, min_ac, weights, coding, impute, train_donor_ids, carriers=False):
+        """burden's work -> (donors, B, records, carriers float64 device tensor [R] or None): per chromosome the mask of the
+        regions' hull, GenotypeStore.burden, and with `carriers` the donors that carry an ALT allele in each region"""
+        import torch
+        st = self.store
+        if weights is not None and weights != "beta":
+            raise ValueError(f"{who_says}: weights {weights!r} (None: 1 per ALT allele, or \"beta\")")
+        rec, groups = self._burden_regions(who_says, regions)
+        _, donors, who = self._cohort([g[len("chr_"):] for g in groups], donor_ids)
+        train = who if train_donor_ids is None else self._cohort([g[len("chr_"):] for g in groups], list(train_donor_ids))[2]
+        ctx = st._context()
+        B = torch.zeros((len(donors), len(rec)), dtype=torch.float64, device=ctx.device)
+        n_used = np.zeros(len(rec), np.int64)
+        carry = torch.zeros(len(rec), dtype=torch.float64, device=ctx.device) if carriers else None
+        for g, at in groups.items():
+            intervals = np.stack([rec["lo"][at], rec["hi"][at]], axis=1)
+            full = intervals[intervals[:, 0] < intervals[:, 1]]
+            mask = torch.zeros(st.meta["groups"][g]["n_variants"], dtype=torch.bool, device=ctx.device)
+            if len(full):                                       # the mask of the regions' hull: nothing else is read
+                lo, hi = int(full[:, 0].min()), int(full[:, 1].max())
+                mask[lo:hi] = st.variant_mask(g, train, lo, hi, min_ac=min_ac, max_maf=max_maf)
+            cols = self.store._to_device(np.array(at))
+            scores, used = st.burden(g, intervals, weights, who, mask, coding, impute, freq_samples=train)
+            B[:, cols] = scores[:, :, 0]
+            n_used[at] = used.cpu().numpy()
+            if carriers:
+                c = scores if coding == "carrier" else st.burden(g, intervals, None, who, mask, "carrier", freq_samples=train)[0]
+                carry[cols] = c[:, :, 0].sum(0)
+        out = np.zeros(len(rec), dtype=[("name", rec.dtype["name"]), ("chrom", rec.dtype["chrom"]), ("start", np.int64),
+                                        ("end", np.int64), ("n_variants", np.int64), ("n_used", np.int64)])
+        for f in ("name", "chrom", "start", "end"):
+            out[f] = rec[f]
+        out["n_variants"], out["n_used"] = rec["hi"] - rec["lo"], n_used
+        return donors, B, out, carry
+
+    def burden(self, regions, donor_ids=None, max_maf=0.01, min_ac=1, weights=None, coding="additive", impute="mean",
+               train_donor_ids=None):
+        """region burden scores: one number per donor and region -> (donors, B, records).  regions: (chrom, start, end, name)
+        rows, 0-based and half-open (a BED file's), in any order, overlapping or not; a region's variants are those whose
+        start lies inside it; a chromosome the file lacks: KeyError.  B is a float64 device tensor [len(donors), R], row i
+        for donor_ids[i] in the order asked (default: every sample, store order), column r for regions[r]:
+        GenotypeStore.burden of the region's variants that pass variant_mask(max_maf=, min_ac=) — the rare ones: at most
+        max_maf minor allele frequency and at least min_ac ALT alleles (None: no bound) —, with weights None (1 per ALT
+        allele) or "beta" (SKAT's 25 (1 - maf)^24), coding "additive" or "carrier" and impute "mean" or "none" as there.
+        With train_donor_ids the mask AND the frequencies (the weights' and the imputed calls') come from the training donors
+        only, so held-out donors leak into neither; without it, from the donors asked for.  records: host numpy, one per
+        region in the order asked: name, chrom, start, end, n_variants (variants inside the region), n_used (of them, those
+        that pass the mask and have a called allele among the frequency donors)."""
+        return self._burden("burden", regions, donor_ids, max_maf, min_ac, weights, coding, impute, train_donor_ids)[:3]
+
+    def burden_association(self, regions, phenotypes, covariates=None, pcs=0, model="linear", donor_ids=None, max_maf=0.01,
+                           min_ac=1, weights=None, coding="additive", impute="mean", train_donor_ids=None, pc_min_maf=None,
+                           ld_window=None, ld_r2=0.2):
+        """the test of every phenotype on every region's burden score -> a list with one host numpy record array per
+        phenotype, one record per region in the order asked: burden's region columns (name, chrom, start, end, n_variants,
+        n_used), carriers (the donors with a complete call that carries an ALT allele at a used variant of the region),
+        then with model = "linear" beta, se, t, p — store.dense_assoc: the coefficient of the score in the least-squares
+        fit of the phenotype on [1 | covariates | score] — and with model = "logistic" (0 / 1 phenotypes) score_chi2,
+        score_p — store.dense_logistic_score: the score test at the null model; there is no Wald or Firth fit of a burden
+        column.  NaN where the score is constant or explained by the covariates.  phenotypes is [n] or [n, P], covariates
+        [n, q0] or None, both aligned with the donors; pcs = K appends the K components of principal_components over the
+        donors and the regions' chromosomes (pc_min_maf, ld_window, ld_r2: its min_maf and LD pruning), as association
+        does.  The other arguments are burden's."""
+        self._check_burden_model(model)
+        donors, B, rec, carriers = self._burden("burden_association", regions, donor_ids, max_maf, min_ac, weights, coding, impute,
+                                                train_donor_ids, carriers=True)
+        return self._burden_tests(donors, B, rec, carriers, phenotypes, covariates, pcs, model, donor_ids, pc_min_maf, ld_window, ld_r2)
+
+    @staticmethod
+    def _check_burden_model(model):
+        if model not in ("linear", "logistic"):
+            raise ValueError(f"burden_association: model {model!r} (\"linear\" or \"logistic\")")
+
+    def _burden_tests(self, donors, B, rec, carriers, phenotypes, covariates=None, pcs=0, model="linear", donor_ids=None,
+                      pc_min_maf=None, ld_window=None, ld_r2=0.2):
+        """burden_association behind the scores: _burden's (donors, B, records, carriers) -> its list of record arrays"""
+        self._check_burden_model(model)
+        y = np.asarray(phenotypes, dtype=np.float64)
+        y = y[:, None] if y.ndim == 1 else y
+        cov = None if covariates is None else np.asarray(covariates, dtype=np.float64)
+        if y.ndim != 2 or y.shape[0] != len(donors):
+            raise ValueError(f"burden_association: phenotypes {list(y.shape)} for {len(donors)} donors ([n] or [n, P])")
+        if int(pcs):
+            chroms = list(dict.fromkeys(c.decode() for c in rec["chrom"]))
+            pc_rec, _ = self.principal_components(int(pcs), chroms, donor_ids, pc_min_maf, ld_window, ld_r2)
+            pc = np.stack([pc_rec[f"pc{c + 1}"] for c in range(int(pcs))], axis=1)
+            cov = pc if cov is None else np.concatenate([cov, pc], axis=1)
+        up = self.store._to_device
+        if model == "linear":
+            floats = ("beta", "se", "t", "p")
+            W, q, yy = assoc_design(y, cov)
+            stats = dense_assoc(B, up(W), q, up(yy)).cpu().numpy()                     # [R, P, 4]
+        else:
+            floats = ("score_chi2", "score_p")
+            per = []
+            for k in range(y.shape[1]):
+                X, beta0 = logistic_design(y[:, k], cov)
+                W, XWX = logistic_score_design(X, y[:, k], beta0)
+                per.append(dense_logistic_score(B, up(W), X.shape[1], up(XWX)))
+            stats = np.stack([x.cpu().numpy() for x in per], axis=1)                   # [R, P, 2]
+        dtype = rec.dtype.descr + [("carriers", np.int64)] + [(f, np.float64) for f in floats]
+        out = []
+        for k in range(y.shape[1]):
+            r = np.zeros(len(rec), dtype=dtype)
+            for f in rec.dtype.names:
+                r[f] = rec[f]
+            r["carriers"] = carriers.cpu().numpy().astype(np.int64)
+            for c, f in enumerate(floats):
+                r[f] = stats[:, k, c]
+            out.append(r)
+        return out
 
     def close(self):
         pass

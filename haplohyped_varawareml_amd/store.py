@@ -27,6 +27,7 @@ from .store_plan import (COUNT_PLAN_DTYPE, DEFAULT_PLANE_BYTES, GATHER_PLAN_DTYP
                          default_blocksize, mask_words_per_block, pack_variant_mask, plan_counts, plan_gather, plan_planes,
                          plan_rows, plan_sample_counts, plan_windows, plane_positions, plane_rows, plane_windows, query_args,
                          sample_index)
+from .store_plan import REGION_MAX_COLS, REGION_SPAN, plan_regions  # noqa: F401
 from .store_stats import (AC, AN, ASSOC_ALT, ASSOC_BETA, ASSOC_COMPLETE, ASSOC_HET, ASSOC_MAX_COLS, ASSOC_P,  # noqa: F401
                           ASSOC_SE, ASSOC_T, GRM_SPAN, HET, HET1, HETHET, HOM_ALT, IBS0, LD_AA, LD_AM, LD_HA, LD_HH,
                           LD_HM, LD_MA, LD_MH, LD_N, LOGIT_BETA, LOGIT_COLLINEAR, LOGIT_MAX_COLS, LOGIT_NO_CALL, LOGIT_NOT_CONVERGED,
@@ -39,6 +40,8 @@ from .store_stats import (AC, AN, ASSOC_ALT, ASSOC_BETA, ASSOC_COMPLETE, ASSOC_H
                           standardized_dosages, student_t_two_sided, top_eigenpairs)
 from .store_stats import (SCORE_MAX_COLS, SCORE_SLICE, SCORE_SPAN, call_class_values, cast_class_values,  # noqa: F401
                           loadings_from_sums, projection_class_weights, score_class_weights)
+from .store_stats import (beta_density_weights, burden_class_weights, dense_assoc, dense_logistic_score,  # noqa: F401
+                          region_totals)
 
 # the reference's per-donor record (vcf_to_h5.py:119-127): packed, 35 bytes
 SNP_DTYPE = np.dtype([("chrom", "S5"), ("start", np.uint32), ("stop", np.uint32), ("ref", "S10"),
@@ -138,6 +141,8 @@ STAT_KEYS = (
     "logistic_variants",                        # assoc_logistic: counted variants (per phenotype)
     "score_plane_blocks", "score_variants",     # score_sums: counted variants whose weights it summed
     "gather_blocks",                            # feature_matrix: Blosc blocks its gather decoded
+    # region_sums: pieces its windows gave hhgt_region_sums; counted variants that lie in at least one region
+    "region_plane_blocks", "region_pieces", "region_variants",
 )
 
 
@@ -1028,6 +1033,136 @@ class GenotypeStore:
         sums = self.score_sums(weights, [q[0] for q in queries], idx, lo, hi, mask, slab_bytes, plane_bytes)
         return sums + offset[None, :], used_n
 
+    def _regions_arg(self, who, group, regions):
+        """`regions` as int64 [R, 2] variant intervals [lo, hi) of a group, clipped to it (an interval the wrong way round
+        is empty) -> (regions, lo, hi): the hull [lo, hi) of the non-empty ones, (0, 0) without one"""
+        n_var = self.meta["groups"][group]["n_variants"]
+        r = np.asarray(regions)
+        if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
+            raise ValueError(f"{who}: regions must be integer [R, 2] variant intervals [lo, hi), not {r.dtype} {list(r.shape)}")
+        r = np.clip(r.astype(np.int64), 0, n_var)
+        full = r[r[:, 0] < r[:, 1]]
+        return r, (int(full[:, 0].min()), int(full[:, 1].max())) if len(full) else (0, 0)
+
+    def region_sums(self, group, regions, weights, samples=None, variant_mask=None, slab_bytes=None, plane_bytes=None,
+                    max_table_bytes=None):
+        """score_sums cut at the boundaries of regions: a float64 device tensor [len(samples), R, K], entry [i, r] the
+        sum over the counted variants v of region r at which samples[i]'s call is complete, of weights[d, v, :] for the
+        call's dosage d — one number per sample and region (a gene, a window of a tiling) and column, from ONE pass over
+        the planes however many regions there are.  regions: integer [R, 2] variant intervals [lo, hi) of `group`, in
+        any order, overlapping, repeated or empty (an empty one gives zeros), clipped to the group.  weights: float64
+        [3, n_variants, K], or [3, n_variants] for K = 1, host or device, 1 <= K <= 16, over the whole group; finite at
+        the counted variants of the regions.  samples, variant_mask (one mask over the whole group), slab_bytes and
+        plane_bytes mean what they mean in score_sums; a sample named twice gets its row twice.  ValueError before
+        anything is allocated for a shape or dtype that does not fit and for a table [plane rows, R, K] of more than
+        max_table_bytes (default MAX_PAIR_TABLE_BYTES).  Per plane window of the regions' hull (_plane_walk under the
+        packed mask) the weights are scattered to their bit positions, zeros where the mask leaves a variant out, the
+        regions become pieces (store_plan.plan_regions: cut every REGION_SPAN words from a region's own first word, so a
+        region's sums do not depend on the others) and one hhgt_region_sums call adds into the table; a region across
+        two windows adds from both.  include/hhgt.h states the arithmetic: exact where every partial sum is representable."""
+        import torch
+        idx, [(group, _, _, n_var, mask)] = self._query("region_sums", group, samples, 0, None, variant_mask, single=True)
+        regions, (lo, hi) = self._regions_arg("region_sums", group, regions)
+        w = weights if torch.is_tensor(weights) else np.asarray(weights)
+        shape = tuple(int(x) for x in w.shape)
+        if len(shape) == 2:
+            w, shape = w[:, :, None], shape + (1,)
+        if (str(w.dtype).split(".")[-1] != "float64" or len(shape) != 3 or shape[:2] != (3, n_var)
+                or not 1 <= shape[2] <= REGION_MAX_COLS):
+            raise ValueError(f"region_sums: the weights of {group} must be float64 [3, {n_var}] + [K], 1 <= K <= {REGION_MAX_COLS}, "
+                             f"not {w.dtype} {list(shape)}")
+        R, K = len(regions), shape[2]
+        n_rows, rows = self._plane_rows(idx)
+        _table_budget("region_sums", f"a table of {n_rows} rows x {R} regions x {K} columns ({{}} bytes) exceeds",
+                      n_rows * R * K * 8, max_table_bytes)
+        ctx = self._context()
+        table = torch.zeros((n_rows, R, K), dtype=torch.float64, device=ctx.device)
+        if len(idx) and hi > lo:
+            w = self._to_device(w[:, lo:hi])
+            full = regions[regions[:, 0] < regions[:, 1]]
+            covered = np.zeros(hi - lo + 1, np.int64)           # the variants of the hull that lie in at least one region
+            np.add.at(covered, full[:, 0] - lo, 1)
+            np.add.at(covered, full[:, 1] - lo, -1)
+            covered = self._to_device(np.cumsum(covered)[:-1] > 0)
+            if mask is not None:
+                mask = self._device_bool(mask)[lo:hi]
+                w = self._zero_outside(w, mask)
+                covered = covered & mask
+            bs = self._blocksize()
+            for a, b, words, planes in self._plane_walk(group, idx, lo, hi, n_var, "region_plane_blocks", slab_bytes,
+                                                        plane_bytes, self._device_mask(mask, lo, n_var)):
+                pieces, runs, n_slots = plan_regions(regions, a, b, bs)
+                ctx.region_sums(planes, self._window_values(w, lo, a, b, words), pieces, runs, n_slots, R, sums=table, wait=False)
+                self.stats["region_pieces"] += len(pieces)
+            self.stats["region_variants"] += int(covered.sum())
+        return table[self._to_device(rows)]
+
+    def burden(self, group, regions, weights=None, samples=None, variant_mask=None, coding="additive", impute="mean",
+               freq_samples=None, slab_bytes=None, plane_bytes=None, max_table_bytes=None):
+        """region burden scores of `samples` -> (B, used): B a float64 device tensor [len(samples), R, K], one number per
+        sample, region and weight column — the (rare) variants of a region collapsed into one score, which has far more
+        carriers than any of them —, used an int64 device tensor [R]: the variants of each region that variant_mask marks
+        and that have a called allele (AN > 0) among freq_samples (default: the scored samples, each once).  regions,
+        samples, variant_mask and the budgets as in region_sums.  weights, per ALT allele: None — 1; a float64 array [V]
+        or [V, K] over the whole group, host or device, K <= 16; "beta" — 25 (1 - maf)^24, SKAT's Beta(1, 25) density at
+        maf = min(p, 1 - p), p = AC / AN among freq_samples (store_stats.beta_density_weights).
+        coding "additive": store_stats.burden_class_weights (impute "mean" or "none") gives the class weights Wd and the
+        per-variant offsets o, and B = region_sums(Wd) + region_totals(o): per sample and region the sum over the used,
+        marked variants of weight x (the ALT dosage, or 2p where the call is not complete — p from freq_samples alone, so
+        rows held out of them leak nothing); with "none" a call that is not complete counts 0.  coding "carrier": the CMC
+        collapse, 1.0 where the sample has a complete call with an ALT allele at a used, marked variant of the region and
+        0.0 elsewhere; it takes no weights (ValueError).  The counted alleles are ALT alleles: nothing is flipped to the
+        minor one.  Those formulas are the contract, not REGENIE's or plink2's files."""
+        import torch
+        if coding not in ("additive", "carrier"):
+            raise ValueError(f"burden: coding {coding!r} (\"additive\" or \"carrier\")")
+        if impute not in ("mean", "none"):
+            raise ValueError(f"burden: impute {impute!r} (\"mean\" or \"none\")")
+        if coding == "carrier" and weights is not None:
+            raise ValueError("burden: coding \"carrier\" takes no weights")
+        idx, [(group, _, _, n_var, mask)] = self._query("burden", group, samples, 0, None, variant_mask, single=True)
+        regions, (lo, hi) = self._regions_arg("burden", group, regions)
+        named = isinstance(weights, str)
+        if named and weights != "beta":
+            raise ValueError(f"burden: weights {weights!r} (None, \"beta\" or an array)")
+        if weights is not None and not named:
+            w = weights if torch.is_tensor(weights) else np.asarray(weights)
+            shape = tuple(int(x) for x in w.shape)
+            if (str(w.dtype).split(".")[-1] != "float64" or len(shape) not in (1, 2) or shape[0] != n_var
+                    or not 1 <= (shape + (1,))[1] <= REGION_MAX_COLS):
+                raise ValueError(f"burden: the weights of {group} must be float64 [{n_var}] or [{n_var}, K], 1 <= K <= "
+                                 f"{REGION_MAX_COLS}, not {w.dtype} {list(shape)}")
+        K = 1 if weights is None or named or len(shape) == 1 else shape[1]
+        n_rows = self._plane_rows(idx)[0]
+        _table_budget("burden", f"a table of {n_rows} rows x {len(regions)} regions x {K} columns ({{}} bytes) exceeds",
+                      n_rows * len(regions) * K * 8, max_table_bytes)
+        freq = np.unique(idx) if freq_samples is None else self._query("burden", group, freq_samples, single=True)[0]
+        ctx = self._context()
+        # the allele counts of the regions' hull, zeros (AN == 0: not used) in the rest of the group
+        counts = torch.zeros((n_var, 4), dtype=torch.int32, device=ctx.device)
+        if hi > lo:
+            counts[lo:hi] = self.allele_counts(group, freq, lo, hi, slab_bytes)
+        marked = counts[:, AN] > 0
+        if mask is not None:
+            mask = self._device_bool(mask)
+            marked = marked & mask
+        used = region_totals(marked.to(torch.float64)[:, None], regions)[:, 0].to(torch.int64)
+        if coding == "carrier":
+            Wd = torch.stack([torch.zeros(n_var, dtype=torch.float64, device=ctx.device)] + [marked.to(torch.float64)] * 2)
+            sums = self.region_sums(group, regions, Wd, idx, mask, slab_bytes, plane_bytes, max_table_bytes)
+            return (sums > 0).to(torch.float64), used
+        if weights is None:
+            w = torch.ones((n_var, 1), dtype=torch.float64, device=ctx.device)
+        elif named:
+            w = beta_density_weights(counts)[:, None]
+        else:
+            w = self._to_device(w)
+        Wd, o, _ = burden_class_weights(w, counts, impute)
+        if mask is not None:
+            o = self._zero_outside(o, mask)
+        sums = self.region_sums(group, regions, Wd.contiguous(), idx, mask, slab_bytes, plane_bytes, max_table_bytes)
+        return sums + region_totals(o, regions)[None], used
+
     def projection_weights(self, vectors, values, groups=None, samples=None, variant_mask=None, slab_bytes=None,
                            plane_bytes=None):
         """the class weights that project a sample onto principal components fitted on `samples` (the TRAINING samples:
@@ -1161,17 +1296,20 @@ class GenotypeStore:
             out[self._to_device(np.array(again))] = out[self._to_device(np.array([first[int(idx[i])] for i in again]))]
         return out, columns
 
-    def variant_mask(self, group, samples=None, v_lo=0, v_hi=None, min_maf=None, max_ac=None, min_ac=None):
+    def variant_mask(self, group, samples=None, v_lo=0, v_hi=None, min_maf=None, max_ac=None, min_ac=None, max_maf=None):
         """a class of the variants [v_lo, v_hi) of a group, from allele_counts over `samples` (same arguments), as a bool
         device tensor [v_hi - v_lo] that sample_counts takes as variant_mask; nothing is copied to the host.  A variant
         is kept iff it passes every bound given: min_maf — AN > 0 and min(AC, AN - AC) >= min_maf * AN, compared as
-        float64 —; min_ac <= AC; AC <= max_ac (integers; singletons: min_ac = max_ac = 1).  No bound: every variant."""
+        float64 —; max_maf — AN > 0 and min(AC, AN - AC) <= max_maf * AN, likewise (the rare variants of a burden score) —;
+        min_ac <= AC; AC <= max_ac (integers; singletons: min_ac = max_ac = 1).  No bound: every variant."""
         import torch
         c = self.allele_counts(group, samples, v_lo, v_hi)
         an, ac = c[:, AN].to(torch.int64), c[:, AC].to(torch.int64)
         keep = torch.ones(c.shape[0], dtype=torch.bool, device=c.device)
         if min_maf is not None:
             keep &= (an > 0) & (torch.minimum(ac, an - ac).double() >= float(min_maf) * an.double())
+        if max_maf is not None:
+            keep &= (an > 0) & (torch.minimum(ac, an - ac).double() <= float(max_maf) * an.double())
         if min_ac is not None:
             keep &= ac >= int(min_ac)
         if max_ac is not None:

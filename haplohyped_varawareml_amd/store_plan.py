@@ -274,3 +274,51 @@ def plane_positions(v_lo, v_hi, blocksize, block0=None):
         raise IndexError(f"plane_positions: variants [{v_lo}, {v_hi}) in a row that begins at block {block0}")
     v = np.arange(v_lo, v_hi, dtype=np.int64)
     return (v // vb - block0) * (32 * mask_words_per_block(blocksize)) + v % vb
+
+
+# hhgt_region_sums' geometry and tables (HHGT_REGION_SPAN, HHGT_REGION_MAX_COLS, HHGT_PIECE_*, HHGT_RUN_* of include/hhgt.h):
+# the plane words a piece has at most, the columns of weights a call takes at most, the fields of a piece and of a run
+REGION_SPAN = 64
+REGION_MAX_COLS = 16
+PIECE_LO, PIECE_HI, PIECE_OUT, PIECE_SLOT, PIECE_FIELDS = 0, 1, 2, 3, 4
+PIECE_DIRECT = -1
+RUN_OUT, RUN_SLOT, RUN_PIECES, RUN_FIELDS = 0, 1, 2, 3
+
+
+def plan_regions(regions, a, b, blocksize, block0=None):
+    """the tables of hhgt_region_sums for `regions`, int64 [R, 2] variant intervals [lo, hi) of one group, over the plane
+    window of the variants [a, b), whose rows begin at Blosc block block0 (default: the block of a) -> (pieces int64
+    [n, PIECE_FIELDS], runs int64 [m, RUN_FIELDS], n_slots).  The regions may come in any order, overlap, repeat each other
+    or be empty; region r adds to output r.  Each is clipped to the window and mapped through plane_positions: its pieces
+    cover the bit positions from its first variant's to its last one's — the padding of the blocks in between included,
+    which has no bit and no weight — and it is cut every REGION_SPAN words counted from the word of its OWN first position,
+    so a region's pieces, and with them its sums to the bit, do not depend on which other regions the call carries (they do
+    depend on the window, where the window clips).  A region without a variant in the window gives no piece.  Pieces come
+    in the order of the regions, a region's in ascending order of position; a region of one piece is PIECE_DIRECT, one of
+    several holds consecutive slots from the running total and gets a run."""
+    a, b, vb = int(a), int(b), int(blocksize) // 2
+    block0 = a // vb if block0 is None else int(block0)
+    regions = np.asarray(regions, dtype=np.int64).reshape(-1, 2)
+    if b < a or block0 * vb > a:
+        raise IndexError(f"plan_regions: a window [{a}, {b}) in rows that begin at block {block0}")
+    lo, hi = np.maximum(regions[:, 0], a), np.minimum(regions[:, 1], b)
+    out = np.nonzero(lo < hi)[0]
+    lo, last = lo[out], hi[out] - 1
+    bits = 32 * mask_words_per_block(blocksize)
+    p_lo = (lo // vb - block0) * bits + lo % vb
+    p_hi = (last // vb - block0) * bits + last % vb + 1
+    w0 = p_lo // 32
+    n = -(-(-(-p_hi // 32) - w0) // REGION_SPAN)            # pieces of every region: at least 1
+    first = np.cumsum(n) - n
+    k = np.arange(int(n.sum()), dtype=np.int64) - np.repeat(first, n)       # a piece's number in its region
+    rep = lambda x: np.repeat(x, n)
+    pieces = np.zeros((k.size, PIECE_FIELDS), np.int64)
+    pieces[:, PIECE_LO] = np.maximum(rep(p_lo), 32 * (rep(w0) + k * REGION_SPAN))
+    pieces[:, PIECE_HI] = np.minimum(rep(p_hi), 32 * (rep(w0) + (k + 1) * REGION_SPAN))
+    pieces[:, PIECE_OUT] = rep(out)
+    long = n > 1
+    slots = np.where(long, n, 0)
+    slot0 = np.cumsum(slots) - slots
+    pieces[:, PIECE_SLOT] = np.where(rep(long), rep(slot0) + k, PIECE_DIRECT)
+    runs = np.stack([out[long], slot0[long], n[long]], axis=1).astype(np.int64).reshape(-1, RUN_FIELDS)
+    return pieces, runs, int(slots.sum())

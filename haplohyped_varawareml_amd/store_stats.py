@@ -748,3 +748,108 @@ def logistic_score_from_sums(T, W_total, q, XWX):
         nan = chi2 * 0.0 + float("nan")
         stats = stack([nan, nan, nan, nan, chi2, normal_two_sided(chi2 ** 0.5)], -1)
     return nan_unless((status == LOGIT_TESTED)[:, None], stats), calls, stack([status * 0, status], -1)
+
+
+# ---- region burden scores: the rare variants of a gene collapsed into one per-sample number -------------------------------------
+def burden_class_weights(weights, counts, impute="mean"):
+    """the per-class weights of a burden score -> (Wd float64 [3, V, K], o float64 [V, K], used bool [V]): weights is [V, K]
+    (or [V]: K = 1), the weight per ALT allele of every variant in each of K scores, counts the allele count table [V, 4] of
+    the frequency samples (numpy or torch, both of one kind).  Wd and used are score_class_weights'; o is its offset before
+    the sum over the variants: with impute = "mean", o[v] = 2 p_v weights[v] at a used variant (AN > 0; p = AC / AN) and 0
+    at the others, so that (the sum of Wd over a sample's complete calls of a region) + (the sum of o over the region) is
+    the sum over the region's used variants of weight x (the dosage, or 2p where the call is not complete); with "none",
+    Wd[d] = d weights and o = 0.  The counted alleles are ALT alleles: nothing is flipped to the minor one."""
+    Wd, _, used = score_class_weights(weights, counts, impute)
+    return Wd, 0.0 - Wd[0], used
+
+
+def region_totals(o, regions):
+    """the sums of a per-variant table over regions -> float64 [R, K]: o is [V, K] (numpy or torch), regions int64 [R, 2],
+    host, variant intervals [lo, hi) — in any order, overlapping or empty; clipped to [0, V).  A segmented sum without a
+    loop over the regions: the difference of two entries of the running sum of o down the variants, so a region's total
+    carries the rounding of the prefix before it: its error is bounded by about V 2^-53 times the sum of |o| over the
+    variants before the region's end, and the same input gives the same bits."""
+    f64 = _ops(o)[1]
+    o = f64(o)
+    V = int(o.shape[0])
+    regions = np.asarray(regions, dtype=np.int64).reshape(-1, 2)
+    lo = np.clip(regions[:, 0], 0, V)
+    hi = np.maximum(np.clip(regions[:, 1], 0, V), lo)
+    if _is_torch(o):
+        import torch
+        running = torch.cat([torch.zeros_like(o[:1]), torch.cumsum(o, 0)])
+        lo, hi = torch.from_numpy(lo).to(o.device), torch.from_numpy(hi).to(o.device)
+    else:
+        running = np.concatenate([np.zeros_like(o[:1]), np.cumsum(o, axis=0)])
+    return running[hi] - running[lo]
+
+
+def beta_density_weights(counts):
+    """SKAT's Beta(1, 25) density at the minor allele frequency of every variant of an allele count table [V, 4] (numpy or
+    torch) -> float64 [V]: 25 (1 - maf)^24, maf = min(p, 1 - p), p = AC / AN; 0 where AN == 0.  The weight goes with the
+    ALT allele whichever allele is the minor one."""
+    i64, f64, minimum, _ = _ops(counts)
+    t = i64(counts)
+    an, ac = t[:, AN], t[:, AC]
+    used = an > 0
+    p = f64(ac * used) / f64(an * used + (~used) * 1)
+    return 25.0 * (1.0 - minimum(p, 1.0 - p)) ** 24 * f64(used)
+
+
+def dense_assoc(B, W, q, yy):
+    """the tail of assoc_from_sums for real-valued columns: the linear regression of every phenotype on [1 | covariates |
+    g] for each column g = B[:, r] of B float64 [n, R] — burden scores, one row per sample of assoc_design's W = [1 | Q |
+    Yr] [n, 1 + q + P]; yy [P] (numpy or torch, all of one kind) -> float64 [R, P, 4], columns ASSOC_BETA, ASSOC_SE, ASSOC_T,
+    ASSOC_P.  With g.w_c = B^T W and g.g = the column sums of B^2,
+        D = g.g - sum_j (g.Q_j)^2      U_p = g.Yr_p      beta = U / D      rss = yy - U^2 / D      df = n - q - 1
+        se = sqrt(rss / df / D)        t = beta / se     p = student_t_two_sided(t, df)
+    exactly as there.  All four are NaN where D <= 1e-12 g.g: a constant column, or one in the covariates' span."""
+    _, f64, _, nan_unless = _ops(B)
+    stack = _math(B)[4]
+    q = int(q)
+    B, W, yy = f64(B), f64(W), f64(yy)
+    if len(B.shape) != 2 or len(W.shape) != 2 or B.shape[0] != W.shape[0] or W.shape[1] != 1 + q + yy.shape[0]:
+        raise ValueError(f"dense_assoc: B {list(B.shape)} ([n, R]), W {list(W.shape)} ([n, 1 + {q} + P]), yy {list(yy.shape)} ([P])")
+    n = B.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gw = B.T @ W
+        gg = (B * B).sum(0)
+        D = gg - (gw[:, 1:1 + q] * gw[:, 1:1 + q]).sum(-1)
+        U = gw[:, 1 + q:]
+        df = n - q - 1
+        beta = U / D[:, None]
+        rss = yy[None, :] - U * U / D[:, None]
+        se = (rss / df / D[:, None]) ** 0.5
+        t = beta / se
+        stats = stack([beta, se, t, student_t_two_sided(t, float(df))], -1)
+        return nan_unless((D > 1e-12 * gg)[:, None, None], stats)
+
+
+def dense_logistic_score(B, W, q, XWX):
+    """the score test of logistic_score_from_sums for real-valued columns -> float64 [R, 2], columns the statistic and its
+    p-value (LOGIT_SCORE_CHI2, LOGIT_SCORE_P of the scan's table): B float64 [n, R], one row per sample of
+    logistic_score_design's W = [1 | y - mu0 | w0 | w0 X] [n, 3 + q], XWX [q, q] (numpy or torch, all of one kind).  For a
+    column g of B:
+        U = g.(y - mu0)      b = g.(w0 X)      gWg = sum w0 g^2      V = gWg - b XWX^-1 b^T
+        chi2 = U^2 / V       p = normal_two_sided(sqrt(chi2))
+    — the first evaluation of logistic_fit_reference with g as the dosage.  Both NaN where V <= 1e-12 gWg: a constant
+    column, or one in the span of X under the null weights.  No fit is made: there is no Wald test of a burden column."""
+    _, f64, _, nan_unless = _ops(B)
+    stack = _math(B)[4]
+    q = int(q)
+    B, W, XWX = f64(B), f64(W), f64(XWX)
+    if len(B.shape) != 2 or len(W.shape) != 2 or B.shape[0] != W.shape[0] or W.shape[1] != 3 + q or tuple(XWX.shape) != (q, q):
+        raise ValueError(f"dense_logistic_score: B {list(B.shape)} ([n, R]), W {list(W.shape)} ([n, {3 + q}]), XWX {list(XWX.shape)} ([{q}, {q}])")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        gw = B.T @ W
+        gWg = (B * B).T @ W[:, 2]
+        b = gw[:, 3:]
+        if _is_torch(B):
+            import torch
+            sol = torch.linalg.solve(XWX, b.T).T
+        else:
+            sol = np.linalg.solve(XWX, b.T).T
+        Vg = gWg - (b * sol).sum(-1)
+        chi2 = gw[:, 1] * gw[:, 1] / Vg
+        stats = stack([chi2, normal_two_sided(chi2 ** 0.5)], -1)
+        return nan_unless((Vg > 1e-12 * gWg)[:, None], stats)

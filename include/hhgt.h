@@ -550,6 +550,65 @@ int hhgt_assoc_sums(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, ui
 int hhgt_score_sums(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, uint64_t w_lo, uint64_t w_hi,
                     const double *d_w, uint32_t n_cols, double *d_sums, void *stream);
 
+/* hhgt_region_sums is hhgt_score_sums cut at the boundaries of regions instead of every HHGT_SCORE_SPAN words: one pass over
+ * genotype planes gives every region (a gene, a window of a tiling) its own columns of sums — the reduction behind a burden
+ * score.  d_planes is hhgt_genotype_planes' output, uint32 [3][n_rows][row_words]: HET, HOM_REF, HOM_ALT; d_w is double
+ * [3][32 * row_words][n_cols], row-major, 8-byte aligned, indexed exactly as hhgt_score_sums' d_w is (dosage class, then
+ * absolute bit position).  As with hhgt_variant_planes the call knows bit positions, not variants.
+ * The cuts come as a table of PIECES, d_pieces, int64 [n_pieces][HHGT_PIECE_FIELDS], 8-byte aligned, on the device:
+ *     [HHGT_PIECE_LO], [HHGT_PIECE_HI]   the bit positions [p_lo, p_hi) of a plane row, with bit granularity; the words they
+ *                                        touch, ceil(p_hi / 32) - floor(p_lo / 32), are at most HHGT_REGION_SPAN
+ *     [HHGT_PIECE_OUT]                   the region g the piece adds to, 0 <= g < n_regions
+ *     [HHGT_PIECE_SLOT]                  HHGT_PIECE_DIRECT for the only piece of its region; else the piece's slot s in the
+ *                                        workspace, 0 <= s < n_slots, no two pieces with the same
+ * and the regions of several pieces as a table of RUNS, d_runs, int64 [n_runs][HHGT_RUN_FIELDS] (NULL with n_runs == 0):
+ *     [HHGT_RUN_OUT] the region, [HHGT_RUN_SLOT] the slot of its first piece, [HHGT_RUN_PIECES] how many pieces it has — the
+ * pieces of one region are adjacent in d_pieces, in ascending order of position, and hold consecutive slots in that order.  A
+ * region is named by at most one run or one direct piece of a call; regions may overlap and repeat each other, each with
+ * an index of its own.  store_plan.plan_regions makes both tables.  d_sums is double [n_rows][n_regions][n_cols], 8-byte aligned:
+ *     d_sums[r][g][c] += sum over the pieces of g, the positions p in [p_lo, p_hi) and the planes k
+ *                        of bit_k(r, p) * d_w[class(k)][p][c].
+ * d_w must be finite at every position of a piece (a 0 bit times NaN is NaN) and is NEVER read outside the union of the
+ * pieces: inside the first and the last word of a piece the positions outside [p_lo, p_hi) are staged as 0.0 without a load,
+ * and so are the columns >= n_cols.  It ADDS to d_sums, as hhgt_score_sums does — every entry has one owner in the launch
+ * that touches it, a plain read-modify-write, no atomics on a sum anywhere —, so windows and calls may accumulate on ONE stream;
+ * entries of regions without a piece are not touched.
+ * Two kernels.  One workgroup per (128 plane rows, piece) reduces its piece as hhgt_score_sums reduces a span
+ * (v_mfma_f64_16x16x4_f64, one word staged at a time, the three planes chained into one accumulator) and either adds its
+ * sums to d_sums (a direct piece) or stores them at [slot][row][column] in the context's workspace — 8 bytes x n_slots x
+ * n_rows x n_cols, grown on demand: proportional to the pieces of the regions longer than HHGT_REGION_SPAN words, not to
+ * all regions.  The second kernel adds a run's partial sums in ascending order of the slot, starting from 0, and adds the
+ * total to d_sums.
+ * Numerics: every product is 0 or a value of d_w exactly, and an entry is a float64 sum of the selected values and of zeros,
+ * taken in an order fixed by the region's pieces: the result is a function of the arguments alone, the same bits on every
+ * call and in every state of the device, and — a region's pieces being its own — the same whichever other regions the call
+ * carries.  It is exact whenever every partial sum is representable; otherwise its error is bounded, to first order, by
+ * (m - 1) * 2^-53 * (the sum of |d_w| over the selected values) for an entry that sums m values — the bound of a summation
+ * in any order: no order inside the instruction is claimed.
+ * The tables are on the device, so the host checks only the scalars: 1 <= n_cols <= HHGT_REGION_MAX_COLS (one column tile);
+ * n_rows below 2^32, row_words below 2^27, n_regions below 2^32; ceil(n_rows / 128) * n_pieces and ceil(n_runs * n_rows * n_cols
+ * / 256) below 2^31; n_slots * n_rows * n_cols below 2^40; else HHGT_ERR_ARG with a message.  The kernels check every piece and run
+ * against row_words, HHGT_REGION_SPAN, n_regions and n_slots: one that fails touches nothing — nothing outside the planes,
+ * the weights, the workspace and d_sums is ever read or written — and is counted.  With n_bad != NULL the call waits for the
+ * stream, *n_bad receives the count, and a count above 0 is HHGT_ERR_ARG with a message (d_sums is then not to be used);
+ * with n_bad == NULL the call is asynchronous on `stream` and the count is dropped.  n_rows == 0 or n_pieces == 0 is HHGT_OK
+ * and touches nothing. */
+#define HHGT_REGION_SPAN 64
+#define HHGT_REGION_MAX_COLS 16
+#define HHGT_PIECE_FIELDS 4
+#define HHGT_PIECE_LO 0
+#define HHGT_PIECE_HI 1
+#define HHGT_PIECE_OUT 2
+#define HHGT_PIECE_SLOT 3
+#define HHGT_PIECE_DIRECT (-1)
+#define HHGT_RUN_FIELDS 3
+#define HHGT_RUN_OUT 0
+#define HHGT_RUN_SLOT 1
+#define HHGT_RUN_PIECES 2
+int hhgt_region_sums(hhgt_ctx *ctx, const uint32_t *d_planes, uint64_t n_rows, uint64_t row_words, const double *d_w,
+                     uint32_t n_cols, const int64_t *d_pieces, uint64_t n_pieces, const int64_t *d_runs, uint64_t n_runs,
+                     uint64_t n_slots, uint64_t n_regions, double *d_sums, uint64_t *n_bad, void *stream);
+
 /* hhgt_logistic_fit fits, for every row of d_vplanes — uint32 [3][n_var][sw], the planes HET, COMPLETE, HOM_ALT of
  * hhgt_variant_planes —, the logistic regression of a 0 / 1 phenotype on [X | dosage] by Newton's method: the kernel of
  * GenotypeStore.assoc_logistic; store_stats.logistic_fit_reference is the same iteration in numpy and is the contract.
