@@ -137,6 +137,16 @@ __device__ __forceinline__ uint32_t bp_gap4(const uint32_t *gbw, uint32_t i)
 // kernel evaluates this eight times per window)
 __device__ __forceinline__ uint32_t bp_len_ext(uint32_t x) { return __umul24(x + 240u, 32897u) >> 23; }
 
+// a pair (one's side, candidate's side) of values below 65536 in the halves of one register: positions P[...] <= BP_N + 1, gaps
+// and lengths <= BP_N.  One v_pk_* instruction works on both, an SDWA compare or minimum takes its two sides from the halves.
+// (Built from two 16-bit LDS loads by one v_perm_b32: the compiler does not load into halves — ds_read_u16_d16 / _d16_hi — here,
+// and it turns this shift-and-or into the permute whatever is done to hide it; DESIGN.md 3.2 "Pairs in 16-bit halves".)
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u16x2 bp_pair(uint16_t a, uint16_t b)
+{
+    return __builtin_bit_cast(u16x2, (uint32_t)a | ((uint32_t)b << 16));
+}
+
 // literal bytes of positions whose map bits are b (and, EXC, whose missing-call bits are x): 0, 1 or 0xF7
 template <bool EXC> __device__ __forceinline__ uint32_t bp_lit(uint32_t b, uint32_t x, uint32_t k)
 {
@@ -445,7 +455,10 @@ __device__ __forceinline__ BpOne bp_lane_one(LDS &S, const uint16_t *P, int jw, 
     o.valid = o.j < (int)m;
     o.jj = o.valid ? (uint32_t)(o.j + 1) : 0u;
     o.q1 = P[o.jj], o.qn1 = P[o.jj + 1u];
-    o.qp1 = o.jj ? P[o.jj - 1u] : 0u;
+    o.qp1 = P[(o.jj ? o.jj : 1u) - 1u];   // (jj = 0 reads P[0] = 0: one address, no exec-mask region around the load and no wait of its own)
+    // (the three loads leave together and share one wait: left to itself the compiler moves the load of qn1 into the exec-mask
+    // region of bp_table_insert, its only reader without the lazy rule — a second LDS round trip in front of the exchange)
+    BP_FORGET(o.qn1);
     o.q = (int)o.q1 - 1;
     o.can = DEPTH > 0 && o.valid && o.j >= 0 && o.q + 12 <= BP_N;
     o.c5a = EXC ? (bp_bits(S.cls, o.jj) & 31u) : 0u;
@@ -481,12 +494,16 @@ struct BpPick {
 // earlier ones: jc1 and everything down the chain lies in front of the lane's one) and, EXC, cls; writes nothing.  Returns
 // the winner and the lane's own gap bytes, which the pricing needs again.
 template <int DEPTH, bool EXC, typename LDS>
-__device__ __forceinline__ BpPick bp_pick(LDS &S, bool can, uint32_t jj, uint32_t c5a, uint32_t jc1)
+__device__ __forceinline__ BpPick bp_pick(LDS &S, uint32_t jj, uint32_t c5a, uint32_t jc1)
 {
     constexpr bool CHAIN = DEPTH > 1;
     const uint32_t a4 = bp_gap4(S.gbw, jj);
     const uint8_t *gbb = reinterpret_cast<const uint8_t *>(S.gbw);
-    const uint32_t fa = jj ? (uint32_t)gbb[jj - 1u] : 0u;    // zeros in front of this one (clipped to 255)
+    // zeros in front of this one (clipped to 255).  (jj = 0, a lane without a one of its own, reads gbb[0]: it has no candidate
+    // (jc1 = 0 there) and fa goes into candidates' scores only — one address for all lanes, no exec-mask region)
+    uint32_t fa = (uint32_t)gbb[(jj ? jj : 1u) - 1u];
+    fa = fa < BP_BACK ? fa : BP_BACK;   // (what a match takes along at most, clipped once for all candidates ...
+    BP_FORGET(fa);                      // ... and kept so: the compiler would fold the clip back into every candidate's minimum)
     const uint32_t na4 = ~a4;
     const uint32_t stop4 = ((na4 - 0x01010101u) & ~na4 & 0x80808080u) | 0xFF000000u;   // a 255 agrees with nothing; 3 gaps at most
     int best = -1;
@@ -495,7 +512,7 @@ __device__ __forceinline__ BpPick bp_pick(LDS &S, bool can, uint32_t jj, uint32_
     // own, and a vector compare ends each of up to DEPTH rounds; so written it stays on the scalar unit, as it was inline)
 #pragma unroll 1
     for (int left = DEPTH; left > 0; --left) {
-        const bool have = can && jc1 != 0u;
+        const bool have = jc1 != 0u;   // (a lane that may start no match has jc1 = 0 from bp_table_insert: the ballot is one compare's)
         if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
         const uint32_t jq = have ? jc1 : 1u;
         const uint32_t b4 = bp_gap4(S.gbw, jq);
@@ -514,8 +531,7 @@ __device__ __forceinline__ BpPick bp_pick(LDS &S, bool can, uint32_t jj, uint32_
         const uint32_t below = (1u << (8u * k)) - 1u;
         const uint32_t sumg = __builtin_amdgcn_sad_u8(a4 & below, 0u, k + 1u);  // their zeros + their ones + this one
         const uint32_t za = (a4 >> (8u * k)) & 0xFFu, zb = (b4 >> (8u * k)) & 0xFFu;
-        uint32_t fz = fa < fb ? fa : fb;                                        // the zeros in front a match would take along
-        fz = fz < BP_BACK ? fz : BP_BACK;
+        const uint32_t fz = fa < fb ? fa : fb;                                  // the zeros in front a match would take along (fa: at most BP_BACK)
         const int score = (int)(sumg + (za < zb ? za : zb) + fz);
         const bool up = have & same & (score > best);   // (selects, not a branch)
         best = up ? score : best;
@@ -550,36 +566,53 @@ __device__ __forceinline__ BpMatch bp_extend_and_price(LDS &S, const uint16_t *P
     if (__builtin_amdgcn_ballot_w64(got) != 0ull) {
         const uint32_t jq = got ? bjq : 1u;
         const uint32_t cc1 = P[jq], cp1 = P[jq - 1u];
-        uint32_t a = jj + bk, b = jq + bk;          // P-indices of the ones the first open comparison starts at
-        uint32_t pa = P[a], pb = P[b];
-        uint32_t clen = pa - q1, costR = 0, tailz = 0, zl = 0;
-#pragma unroll
-        for (uint32_t s = 0; s < BP_PICK; ++s) {
-            const uint32_t g = (a4 >> (8u * s)) & 0xFFu;
-            costR += s < bk ? 1u + (g >= BP_TMIN + 1u ? 4u : g) : 0u;
-        }
-        bool act = got;
-        for (uint32_t s = bk;; ++s) {   // (per lane: s starts at the lane's own bk; the trip count is what the wave needs)
-            if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
-            // (branch-free body: lanes that are done keep their values through selects; a + 1, b + 1 <= m + 4 stay inside P)
-            const uint32_t na = P[a + 1u], nbn = P[b + 1u];
-            const uint32_t ga = na - pa - 1u, gb = nbn - pb - 1u;
-            const bool cdiff = EXC && (((bp_bits(S.cls, a + 1u) ^ bp_bits(S.cls, b + 1u)) & 1u) != 0u);
-            const bool stop = (s < BP_PICK) | (ga != gb) | (ga >= 255u) | (a >= m) | (s >= BP_STEPS) | cdiff;
-            const uint32_t z = ga < gb ? ga : gb;
-            costR += act ? 1u + (ga >= BP_TMIN + 1u ? 4u : ga) : 0u;
-            clen += act ? 1u + (stop ? z : ga) : 0u;
-            tailz = (act & stop) ? ga - z : tailz;
-            zl = (act & stop) ? z : zl;
-            act = act & !stop;
-            a += act ? 1u : 0u;
-            b += act ? 1u : 0u;
-            pa = act ? na : pa;
-            pb = act ? nbn : pb;
-        }
+        // the zeros in front that the one and its candidate share: what the match is pulled back over, at most BP_BACK
         const uint32_t gq = q1 - qp1 - 1u, gc = cc1 - cp1 - 1u;
         uint32_t cnb = gq < gc ? gq : gc;
         cnb = cnb < BP_BACK ? cnb : BP_BACK;
+        // The one's side (a) and the candidate's side (b) walk in step, so b is a fixed distance behind a: ONE index is loop
+        // state, doubled (a2 = 2 a: the byte offset into P).  The two positions travel as the halves of one register —
+        // (pa, pb), at most BP_N + 1 each — and one packed subtraction gives both steps d = (ga + 1, gb + 1).  What the
+        // loop used to add up it no longer does: the steps taken telescope to pa - q1, and the last step's gaps are read
+        // off the d the lane stopped at.  The step count s = a - jj needs no counter either: s < BP_PICK can only hold at a
+        // lane's first step, and s >= BP_STEPS and a >= m are one limit on a (lim2).  Same decisions, tools/sim/gapenc_ref.c's.
+        const uint8_t *P8 = reinterpret_cast<const uint8_t *>(P);
+        const uint32_t back2 = 2u * (jj - jq);      // (jq < jj: the candidate lies in front)
+        uint32_t a2 = 2u * (jj + bk);               // twice the P-index of the one the first open comparison starts at
+        const uint32_t lim = m < jj + BP_STEPS ? m : jj + BP_STEPS;
+        uint32_t lim2 = bk < BP_PICK ? 0u : 2u * lim;   // (s < BP_PICK: a limit every a has reached)
+        BP_FORGET(lim2);   // (or the compiler turns the select back into a lane mask that lives across the loop, and the lazy forms run out of scalar registers)
+        u16x2 pp = bp_pair(*reinterpret_cast<const uint16_t *>(P8 + a2), *reinterpret_cast<const uint16_t *>(P8 + a2 - back2));
+        u16x2 dl = bp_pair(1, 1);
+        // what the bk agreed gaps cost as literals and runs: 1 + min(gap, BP_TMIN) each (the gaps behind them masked away once,
+        // not one select per gap)
+        uint32_t am = a4 & ((1u << (8u * bk)) - 1u);
+        BP_FORGET(am);   // (or mask and byte select merge into one operation per gap, each with a constant in a scalar register)
+        uint32_t costR = bk;
+#pragma unroll
+        for (uint32_t s = 0; s < BP_PICK; ++s) {
+            const uint32_t g = (am >> (8u * s)) & 0xFFu;
+            costR += g < BP_TMIN ? g : BP_TMIN;
+        }
+        uint32_t st2 = got ? 2u : 0u;   // what a2 advances by: 2 while the lane goes on, 0 once it has stopped (as a number, not a lane mask: the ballot is one compare's)
+        for (;;) {   // (the trip count is what the wave needs)
+            const bool act = st2 != 0u;
+            if (__builtin_amdgcn_ballot_w64(act) == 0ull) break;
+            // (branch-free body: lanes that are done keep their values through selects; a + 1, b + 1 <= m + 4 stay inside P)
+            const u16x2 nn = bp_pair(*reinterpret_cast<const uint16_t *>(P8 + a2 + 2u), *reinterpret_cast<const uint16_t *>(P8 + a2 - back2 + 2u));
+            const u16x2 d = nn - pp;
+            const uint32_t da = d.x, db = d.y;
+            const bool cdiff = EXC && (((bp_bits(S.cls, (a2 >> 1) + 1u) ^ bp_bits(S.cls, ((a2 - back2) >> 1) + 1u)) & 1u) != 0u);
+            const bool stop = (da != db) | (((__builtin_bit_cast(uint32_t, d) >> 8) & 0xFFu) != 0u) | (a2 >= lim2) | cdiff;   // (da >= 256 by its high byte: no constant in a scalar register)
+            costR += act ? (da < BP_TMIN + 1u ? da : BP_TMIN + 1u) : 0u;
+            dl = act ? d : dl;
+            st2 = stop ? 0u : st2;
+            a2 += st2;
+            pp = st2 != 0u ? nn : pp;
+        }
+        const uint32_t a = a2 >> 1;
+        const uint32_t z1 = dl.x < dl.y ? dl.x : dl.y, zl = z1 - 1u, tailz = (uint32_t)dl.x - z1;
+        const uint32_t clen = (uint32_t)pp.x - q1 + z1;
         const uint32_t costH = 3u + (clen + cnb >= 19u ? 1u : 0u) - cnb + (tailz >= BP_TMIN ? 3u : tailz);
         uint32_t end = (uint32_t)q + clen;
         const bool cut = end > BP_MATCHLIMIT;
@@ -840,7 +873,7 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
         BP_MARK("hash_done");
         BpMatch mt{false, 0u, 0u, 0u, o.jj, 0u, false};
         if (DEPTH > 0) {
-            const BpPick pk = bp_pick<DEPTH, EXC>(S, o.can, o.jj, o.c5a, jc1);
+            const BpPick pk = bp_pick<DEPTH, EXC>(S, o.jj, o.c5a, jc1);
             mt = bp_extend_and_price<EXC>(S, P, pk.best >= 0, pk.bjq, pk.bk, pk.a4, o.jj, o.q, o.q1, o.qp1, m);
         }
         BP_MARK("cand_done");
