@@ -66,6 +66,7 @@
 #ifndef BP_STAGE_EXC
 #define BP_STAGE_EXC 104
 #endif
+#define BP_SPARE 8          // bytes in front of the staging area that nobody reads
 #define BP_PLANE_LDS 5120   // k_lz4_bitplanes_uni: LDS of a workgroup = a plane (163 840 / 32)
 template <bool EXC> struct BpCfg {
     static constexpr uint32_t MAXONES = EXC ? BP_MAXONES_EXC : BP_MAXONES;
@@ -74,6 +75,7 @@ template <bool EXC> struct BpCfg {
     static constexpr uint32_t PTRASH = MAXONES + 7;   // P's spare entry: written by lanes that have nothing to store, never read
 };
 static_assert(BP_QCAP >= 65 && BP_QCAP_EXC >= 65, "a batch of 64 needs the entry behind it in the queue");
+static_assert(BP_SPARE >= 6 && BP_SPARE % 4 == 0, "store k of an entry (k < 6) has spare byte k; the staged bytes behind them leave as dwords");
 #define BP_HLOG 6
 #define BP_GAPCLIP 40
 #define BP_MINM 6     // total length a hash match must have
@@ -105,16 +107,19 @@ template <bool CHAIN, bool EXC> struct BpLds {
     uint16_t chain[CHAIN ? BpCfg<EXC>::MAXONES + 8 : 4];   // chain[j + 1] = (previous one with the same context hash) + 1, 0 = none
     uint32_t gbw[(BpCfg<EXC>::MAXONES + 16) / 4];   // gap bytes: zeros behind the one with P-index i, clipped to 255 (255 from the last one on)
     uint2 queue[BpCfg<EXC>::QCAP + 1];       // coded ones waiting for layout + emission (bp_emit_batch takes 64 at a time); [QCAP]: written by lanes that queue nothing
-    uint8_t stage[BpCfg<EXC>::STAGE + 8];     // output staged here, written out in coalesced dwords; [BP_STAGE]: written by lanes that have no byte to store
+    uint8_t stage[BP_SPARE + BpCfg<EXC>::STAGE];   // [0, BP_SPARE): written by lanes that have no byte to store (store k of an entry: byte k); behind them the output staged, written out in coalesced dwords
 };
 
 // a queued coded one: what its sequences need that does not depend on the sequences in front of it
-//   x: E (13 bits) | msr = q - nb (13) << 13 | onM << 26 | onT << 27 | (rs - E) << 28        (E: end of what the one codes;
-//      onT: the run is long enough — whether it is emitted is decided against the next entry, bp_emit_batch)
+//   x: E (13 bits) | msr = q - nb (13) << 13 | (rs - E) << 26 | onM << 30 | onT << 31        (E: end of what the one codes;
+//      onT: the run is long enough — whether it is emitted is decided against the next entry, bp_emit_batch.  The two on
+//      top: "this one queues something" is x >= BP_ENT_ANY, one compare whose result is the lane mask; onT is the sign.
+//      msr and off mean something only with onM)
 //   y: re (13 bits) | off << 13                                                                (re: start of the next coded one)
+#define BP_ENT_ANY (1u << 30)
 __device__ __forceinline__ uint2 bp_entry(uint32_t E, uint32_t msr, bool onM, bool onT, uint32_t rs, uint32_t re, uint32_t off)
 {
-    return make_uint2(E | ((msr & 0x1FFFu) << 13) | (onM ? 1u << 26 : 0u) | (onT ? 1u << 27 : 0u) | ((rs - E) << 28), re | (off << 13));
+    return make_uint2(E | ((msr & 0x1FFFu) << 13) | ((rs - E) << 26) | (onM ? 1u << 30 : 0u) | (onT ? 1u << 31 : 0u), re | (off << 13));
 }
 
 // 32 bits of the map starting at bit q (0 <= q < 4096 + 96)
@@ -147,14 +152,21 @@ __device__ __forceinline__ u16x2 bp_pair(uint16_t a, uint16_t b)
     return __builtin_bit_cast(u16x2, (uint32_t)a | ((uint32_t)b << 16));
 }
 
+#define BP_FENCE() asm volatile("" ::: "memory")
+// the compiler forgets what it knows about x, at no fixed place in the order of things (it may move this, and drop it with x)
+#define BP_HIDE(x) asm("" : "+v"(x))
 // literal bytes of positions whose map bits are b (and, EXC, whose missing-call bits are x): 0, 1 or 0xF7
 template <bool EXC> __device__ __forceinline__ uint32_t bp_lit(uint32_t b, uint32_t x, uint32_t k)
 {
     const uint32_t v = (b >> k) & 1u;
-    return EXC ? (((x >> k) & 1u) ? 0xF7u : v) : v;
+    if (!EXC) return v;
+    // (a missing call's bit in x stands on a bit of b, the map of the nonzero bytes: 1 + 0xF6, one multiply-add behind the
+    // v_bfe_u32 that BP_HIDE holds the compiler to)
+    uint32_t e = (x >> k) & 1u;
+    BP_HIDE(e);
+    return __umul24(e, 0xF6u) + v;
 }
 
-#define BP_FENCE() asm volatile("" ::: "memory")
 // the compiler forgets what it knows about x: what was derived from x in front of this point is worked out again behind it,
 // not carried in registers across (the length fields' extension counts across the size scan of a batch)
 #define BP_FORGET(x) asm volatile("" : "+v"(x))
@@ -166,24 +178,43 @@ template <bool EXC> __device__ __forceinline__ uint32_t bp_lit(uint32_t b, uint3
 // SECOND is the run T behind a match: its literals are [E, rs), none or one byte, and that byte is a zero (a run is only
 // queued over >= BP_TMIN zeros up to the next nonzero byte at or behind E, so byte E is none; tools/sim/gapenc_ref.c's
 // last loop, where prev_end = e behind a match): token, the constant 0, the offset bytes 1, 0, and the length.
-// OUT is a pointer into the staging area (LDS: ds_write_b8) or, for a batch too large for it, into the stream's slot in
-// global memory.  TR: out[tr] is a byte nobody reads (staging area only) — lanes with nothing to store write there instead
-// of sitting out an exec-mask region: `if (p) store` costs two scalar instructions and often a branch, `store at
-// (p ? a : tr)` one vector select, and a wave pays for its branch points.
-// at: where the entry's bytes start; pe: where its literals start in the plane; (on1, ll1, ml1 = length - 4, off1): the
+// OUT is the staging area (S.stage; LDS: ds_write_b8) or, for a batch too large for it, a pointer into the stream's slot in
+// global memory.  TR (staging area only): out[0 .. BP_SPARE) are bytes nobody reads — lanes with nothing to store write there
+// instead of sitting out an exec-mask region: `if (p) store` costs two scalar instructions and often a branch, `store at
+// (p ? a : 0)` one vector select with an inline constant, and a wave pays for its branch points.
+// at: where the entry's bytes start in out (staged: BP_SPARE and the batch's place in the area are in it, added once per entry
+// and not to each store's address); pe: where its literals start in the plane; (on1, ll1, ml1 = length - 4, off1): the
 // first sequence; (on2, lit2: it has its one literal, ml2): the second.  The counts of extension bytes are worked out here
 // again, not handed over from the caller's size scan (BP_FORGET there): three multiplies against three registers.
 // (Up to round 8 a batch called bp_put_seq twice, for M and for T, each with its own fetch from the bit map behind its own
 // `any literals?` ballot, its own rare-length branch and its own long-literal loop: profiles/r09_emit_split.txt.)
 template <bool EXC, bool TR, typename OUT>
-__device__ __forceinline__ void bp_put_entry(const uint32_t *bm, const uint32_t *xm, OUT out, uint32_t tr, uint32_t at, uint32_t pe, bool on1, uint32_t ll1,
-                                             uint32_t ml1, uint32_t off1, bool on2, bool lit2, uint32_t ml2, uint32_t lane)
+__device__ __forceinline__ void bp_put_entry(const uint32_t *bm, const uint32_t *xm, OUT out, uint32_t at, uint32_t pe, bool on1, uint32_t ll1, uint32_t ml1,
+                                             uint32_t off1, bool on2, bool lit2, uint32_t ml2, uint32_t lane)
 {
     if (BP_EMITSKIP == 3) return;
     const uint32_t llx1 = bp_len_ext(ll1), mlx1 = on1 ? bp_len_ext(ml1) : 0u, mlx2 = on2 ? bp_len_ext(ml2) : 0u, ll2 = lit2 ? 1u : 0u;
-    auto put = [&](bool p, uint32_t a, uint32_t v) {
-        if (TR) out[p ? a : tr] = (uint8_t)v;
-        else if (p) out[a] = (uint8_t)v;
+    // byte v to out[a + k], k a constant, if p.  Staged: the select picks a or 0, and + k rides in the store's offset field —
+    // a lane with nothing to store writes spare byte k (behind BP_HIDE: or the compiler adds k in front of the select, one
+    // v_add per store)
+    auto put = [&](bool p, uint32_t a, uint32_t k, uint32_t v) {
+        if (TR) {
+            uint32_t i = p ? a : 0u;
+            BP_HIDE(i);
+            out[i + k] = (uint8_t)v;
+        } else if (p) out[a + k] = (uint8_t)v;
+    };
+    // the same for two neighbouring bytes under one predicate: one select (spare bytes 0, 1)
+    auto put2 = [&](bool p, uint32_t a, uint32_t v0, uint32_t v1) {
+        if (TR) {
+            uint32_t i = p ? a : 0u;
+            BP_HIDE(i);
+            out[i] = (uint8_t)v0;
+            out[i + 1u] = (uint8_t)v1;
+        } else if (p) {
+            out[a] = (uint8_t)v0;
+            out[a + 1u] = (uint8_t)v1;
+        }
     };
     const uint32_t lit = at + 1u + llx1, o1 = lit + ll1;       // first sequence: its literals, its offset
     const uint32_t at2 = o1 + 2u + mlx1, o2 = at2 + 1u + ll2;  // second sequence: its token, its offset
@@ -205,24 +236,29 @@ __device__ __forceinline__ void bp_put_entry(const uint32_t *bm, const uint32_t 
     }
     // ... and straight-line byte stores for what nearly every sequence has: token, at most one extension byte per length,
     // offset
-    put(on2, at2, (ll2 << 4) | (ml2 < 15u ? ml2 : 15u));
-    put(lit2, at2 + 1u, 0u);
-    put(on2, o2, 1u);
-    put(on2, o2 + 1u, 0u);
-    put(mlx2 != 0u, o2 + 2u, mlx2 == 1u ? ml2 - 15u : 255u);
-    put(on1, at, ((ll1 < 15u ? ll1 : 15u) << 4) | (ml1 < 15u ? ml1 : 15u));
-    put(llx1 != 0u, at + 1u, llx1 == 1u ? ll1 - 15u : 255u);
-    put(on1, o1, off1 & 0xFFu);
-    put(on1, o1 + 1u, off1 >> 8);
-    put(mlx1 != 0u, o1 + 2u, mlx1 == 1u ? ml1 - 15u : 255u);
+    put(on2, at2, 0u, (ll2 << 4) | (ml2 < 15u ? ml2 : 15u));
+    put(lit2, at2, 1u, 0u);
+    put2(on2, o2, 1u, 0u);
+    put(mlx2 != 0u, o2, 2u, mlx2 == 1u ? ml2 - 15u : 255u);
+    put(on1, at, 0u, ((ll1 < 15u ? ll1 : 15u) << 4) | (ml1 < 15u ? ml1 : 15u));
+    put(llx1 != 0u, at, 1u, llx1 == 1u ? ll1 - 15u : 255u);
+    put2(on1, o1, off1, off1 >> 8);
+    put(mlx1 != 0u, o1, 2u, mlx1 == 1u ? ml1 - 15u : 255u);
     // Most literal runs are 1-3 bytes ("1", "1 0"): up to 6 go out as byte stores of the owning lane.  Longer runs (the
     // literals of all the ones in between that code nothing pile up in front of the next sequence) are written by the whole
     // wave, one run at a time — a lockstep per-lane loop would run max(ll) times for all.
     if (BP_EMITSKIP != 1) {
         const uint32_t b = bp_bits(bm, pe), x = EXC ? bp_bits(xm, pe) : 0u;   // the entry's ONE fetch from the bit map
-        const uint32_t nsm = ll1 <= 6u ? ll1 : 0u;   // bytes this lane stores itself
+        uint32_t nsm = ll1 <= 6u ? ll1 : 0u;   // bytes this lane stores itself
+        BP_HIDE(nsm);                          // (one number for the six compares, not a compare of ll1 per byte)
 #pragma unroll
-        for (uint32_t k = 0; k < 6u; ++k) put(k < nsm, lit + k, bp_lit<EXC>(b, x, k));
+        for (uint32_t k = 0; k < 6u; ++k) {
+            uint32_t v = bp_lit<EXC>(b, x, k);
+            // (staged: the byte stays 32 bits wide up to the store, bit k is one v_bfe_u32; left to itself the compiler narrows it
+            // to a 16-bit shift and a mask.  Not so in the direct form: the int8 kernel goes from 64 to 66 VGPRs with it)
+            if (TR) BP_HIDE(v);
+            put(k < nsm, lit, k, v);
+        }
         unsigned long long big = BP_EMITSKIP == 2 ? 0ull : __builtin_amdgcn_ballot_w64(ll1 > 6u);
         while (big != 0ull) {
             const int l = __builtin_ctzll(big);
@@ -263,15 +299,15 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     uint2 en = S.queue[lane];   // (lane < 64 <= QCAP: inside the queue whatever n is)
     en.x = have ? en.x : 0u;
     en.y = have ? en.y : 0u;
-    const uint32_t E = en.x & 0x1FFFu, msr = (en.x >> 13) & 0x1FFFu, rs = E + (en.x >> 28), re = en.y & 0x1FFFu, off = en.y >> 13;
-    const bool onM = (en.x >> 26) & 1u;
-    bool onT = (en.x >> 27) & 1u;
+    const uint32_t E = en.x & 0x1FFFu, msr = (en.x >> 13) & 0x1FFFu, rs = E + ((en.x >> 26) & 1u), re = en.y & 0x1FFFu, off = en.y >> 13;
+    const bool onM = (en.x >> 30) & 1u;
+    bool onT = (int)en.x < 0;
     {   // the run is dropped when the next coded one's match starts so far in front of its one that fewer than BP_TMIN
         // zeros are left to the run (the next coded one with a match IS the next entry: msr <= re says so)
         uint32_t nx = S.queue[lane + 1u].x;
         nx = lane + 1u < qn ? nx : 0u;
         const uint32_t nmsr = (nx >> 13) & 0x1FFFu;
-        const bool nM = (nx >> 26) & 1u;
+        const bool nM = (nx >> 30) & 1u;
         uint32_t nbk = nM && nmsr <= re ? re - nmsr : 0u;
         const uint32_t zt = re - rs;
         nbk = nbk < zt ? nbk : zt;
@@ -301,7 +337,7 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     // the batch's bytes go to the staging area; what is staged leaves in coalesced dwords when the next batch would not
     // fit (a batch larger than the whole area is written to global memory directly)
     if (__builtin_expect(sop + total > BpCfg<EXC>::STAGE, 0)) {
-        bp_flush(S.stage, out + gop, sop, lane);
+        bp_flush(S.stage + BP_SPARE, out + gop, sop, lane);
         gop += sop;
         sop = 0;
     }
@@ -310,10 +346,10 @@ __device__ __forceinline__ BpOut bp_emit_batch(LDS &S, const uint32_t *bm, uint8
     BP_FORGET(ml1);
     BP_FORGET(ml2);
     if (__builtin_expect(total > BpCfg<EXC>::STAGE, 0)) {   // (wave-uniform, rare: a batch with hundreds of literals)
-        bp_put_entry<EXC, false>(bm, xm, out + gop, 0u, at, pe, on1, ll1, ml1, off1, on2, lit2, ml2, lane);
+        bp_put_entry<EXC, false>(bm, xm, out + gop, at, pe, on1, ll1, ml1, off1, on2, lit2, ml2, lane);
         gop += total;
     } else {
-        bp_put_entry<EXC, true>(bm, xm, S.stage + sop, BpCfg<EXC>::STAGE - sop, at, pe, on1, ll1, ml1, off1, on2, lit2, ml2, lane);
+        bp_put_entry<EXC, true>(bm, xm, S.stage, at + (sop + BP_SPARE), pe, on1, ll1, ml1, off1, on2, lit2, ml2, lane);
         sop += total;
     }
     return BpOut{prev_end, gop, sop};
@@ -508,12 +544,10 @@ __device__ __forceinline__ BpPick bp_pick(LDS &S, uint32_t jj, uint32_t c5a, uin
     const uint32_t stop4 = ((na4 - 0x01010101u) & ~na4 & 0x80808080u) | 0xFF000000u;   // a 255 agrees with nothing; 3 gaps at most
     int best = -1;
     uint32_t bjq = 0, bk = 0;
-    // (counted down: counted up, the compiler keeps this counter in a vector register where the loop is a function of its
-    // own, and a vector compare ends each of up to DEPTH rounds; so written it stays on the scalar unit, as it was inline)
-#pragma unroll 1
-    for (int left = DEPTH; left > 0; --left) {
-        const bool have = jc1 != 0u;   // (a lane that may start no match has jc1 = 0 from bp_table_insert: the ballot is one compare's)
-        if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
+    // one candidate per lane: jc1, then what the chain holds behind it.  (A lane that may start no match has jc1 = 0 from
+    // bp_table_insert, so `have` is one compare; a lane without a candidate reads the entries of one 1: a safe address, no
+    // exec-mask region)
+    auto consider = [&](const bool have) {
         const uint32_t jq = have ? jc1 : 1u;
         const uint32_t b4 = bp_gap4(S.gbw, jq);
         const uint32_t fb = (uint32_t)gbb[jq - 1u];
@@ -537,8 +571,23 @@ __device__ __forceinline__ BpPick bp_pick(LDS &S, uint32_t jj, uint32_t c5a, uin
         best = up ? score : best;
         bjq = up ? jq : bjq;
         bk = up ? k : bk;
-        if (!CHAIN) break;
         jc1 = have ? nextc : 0u;
+    };
+    if (DEPTH <= 2) {
+        // one or two candidates: straight-line code.  The loop below asks the wave in front of every candidate whether any lane
+        // still has one — a compare, its mask to the scalar unit, a branch, DEPTH + 1 times per window — and in a window of these
+        // planes some lane nearly always has
+#pragma unroll
+        for (int left = 0; left < DEPTH; ++left) consider(jc1 != 0u);
+    } else {
+        // (counted down: counted up, the compiler keeps this counter in a vector register where the loop is a function of its
+        // own, and a vector compare ends each of up to DEPTH rounds; so written it stays on the scalar unit, as it was inline)
+#pragma unroll 1
+        for (int left = DEPTH; left > 0; --left) {
+            const bool have = jc1 != 0u;
+            if (__builtin_amdgcn_ballot_w64(have) == 0ull) break;
+            consider(have);
+        }
     }
     return BpPick{best, bjq, bk, a4};
 }
@@ -550,8 +599,13 @@ struct BpMatch {
     uint32_t c1;        // hv: P[candidate] (the offset is q1 - c1)
     uint32_t a_last;    // hv: P-index of the last one the match covers
     uint32_t z_last;    // hv: zeros the match takes behind that one (0: it ends with the one)
-    bool clamped;       // hv: the match was cut at the stream's match limit
-};
+    bool anycut;        // (wave-uniform) some lane's candidate reached past the stream's match limit: a match of this window may
+                        // have been cut there, and what follows from a_last and z_last does not hold for such a match
+};   // (len, nb, c1 without hv: anything — every reader asks hv first; zeroing them was three selects per window)
+
+// hv: the match ends at the match limit or was cut there.  Asked only behind anycut, where the next one and the start of the run
+// come from the bit map — which is right for every match, so the test may say yes to one that merely ends there
+__device__ __forceinline__ bool bp_at_limit(bool hv, uint32_t E) { return hv & (E >= BP_MATCHLIMIT); }
 
 // the chosen candidate, exactly (positions from P): agreement may continue past the third gap (periodic planes; rare), then
 // the costs decide between this match and literals.  Reads P (parameter, see above) and, EXC, cls (bp_list_ones); writes
@@ -562,7 +616,7 @@ __device__ __forceinline__ BpMatch bp_extend_and_price(LDS &S, const uint16_t *P
                                                        uint32_t q1, uint32_t qp1, uint32_t m)
 {
     uint32_t len = 0, nb = 0, c1 = 0, a_last = jj, z_last = 0;
-    bool hv = false, clamped = false;
+    bool hv = false, anycut = false;
     if (__builtin_amdgcn_ballot_w64(got) != 0ull) {
         const uint32_t jq = got ? bjq : 1u;
         const uint32_t cc1 = P[jq], cp1 = P[jq - 1u];
@@ -620,14 +674,17 @@ __device__ __forceinline__ BpMatch bp_extend_and_price(LDS &S, const uint16_t *P
         // signed compares: costH may go below zero when many zeros are pulled in
         const int gain = (int)costR - (int)costH;
         hv = got & (gain > 0) & ((int)end - q >= 4) & ((int)end - (q - (int)cnb) >= BP_MINM) & (q <= BP_MFLIMIT);   // (& not &&: no nest of exec-mask regions)
-        len = hv ? end - (uint32_t)q : 0u;
-        nb = hv ? cnb : 0u;
-        c1 = hv ? cc1 : 0u;
+        len = end - (uint32_t)q;
+        nb = cnb;
+        c1 = cc1;
         a_last = a;
         z_last = zl;
-        clamped = cut & hv;
+        // (the ballot of ONE compare, taken here and handed on as a scalar: `cut & hv` per lane crossed this block's end as a
+        // number and was compared again in front of each of the two branches that ask.  A lane without a candidate has
+        // clen = 1 here and says yes only for a one in the plane's last five bytes)
+        anycut = __builtin_amdgcn_ballot_w64(cut) != 0ull;
     }
-    return BpMatch{hv, len, nb, c1, a_last, z_last, clamped};
+    return BpMatch{hv, len, nb, c1, a_last, z_last, anycut};
 }
 
 // one-step lazy rule (the file-writing paths' effort level; tools/sim/gapenc_ref.c states it): a one gives up its match when
@@ -636,13 +693,13 @@ __device__ __forceinline__ BpMatch bp_extend_and_price(LDS &S, const uint16_t *P
 // match).  The next one is the neighbouring lane (the window's last lane keeps its match); in a run of lanes that all would
 // give up, every other one does, counted from the far end.  Touches no LDS: the neighbour's match comes over DPP.  Returns
 // the lane's match, or no match where it gave up.
-__device__ __forceinline__ BpMatch bp_lazy_rule(bool hv, uint32_t len, uint32_t nb, uint32_t c1, uint32_t a_last, uint32_t z_last, bool clamped, int j, int q,
+__device__ __forceinline__ BpMatch bp_lazy_rule(bool hv, uint32_t len, uint32_t nb, uint32_t c1, uint32_t a_last, uint32_t z_last, bool anycut, int j, int q,
                                              uint32_t jj, uint32_t q1, uint32_t qn1, uint32_t m, uint32_t lane)
 {
     const uint32_t E0 = hv ? (uint32_t)q + len : (uint32_t)(q + 1);
     const uint32_t hvN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(hv ? 1u : 0u), 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
     const uint32_t EN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)E0, 0x130, 0xf, 0xf, false);
-    const uint32_t nbN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nb, 0x130, 0xf, 0xf, false);
+    const uint32_t nbN = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)nb, 0x130, 0xf, 0xf, false);   // (means something with hvN)
     const int msN = (int)qn1 - 1 - (int)nbN;                        // where the next one's match starts
     const int between = msN - (int)q1 > 0 ? msN - (int)q1 : 0;     // zeros between this one and that start
     const bool Ln = hv & (hvN != 0u) & (lane < 63u) & (j + 1 < (int)m) & (qn1 <= E0) &
@@ -652,7 +709,7 @@ __device__ __forceinline__ BpMatch bp_lazy_rule(bool hv, uint32_t len, uint32_t 
     const uint32_t tlo = (uint32_t)__builtin_ctz((uint32_t)rest | 0x80000000u), thi = (uint32_t)__builtin_ctz((uint32_t)(rest >> 32) | 0x80000000u);
     const uint32_t t = (uint32_t)rest != 0u ? tlo : 32u + thi;     // (lm >> lane has zeros from bit 64 - lane on: the run ends inside)
     const bool give = Ln && (t & 1u);
-    return BpMatch{hv && !give, give ? 0u : len, give ? 0u : nb, give ? 0u : c1, give ? jj : a_last, give ? 0u : z_last, clamped && !give};
+    return BpMatch{hv && !give, len, nb, c1, give ? jj : a_last, give ? 0u : z_last, anycut};
 }
 
 struct BpNext {
@@ -665,12 +722,13 @@ struct BpNext {
 // zeros behind the last one it covers (or exactly at the next one): that one's P-index.  Only a match that was cut at the
 // stream's match limit (a handful of ones at the very end of a plane) needs the count from the bit map: reads bm (the
 // kernel, before bp_code_plane) and wpre (bp_list_ones) then, nothing otherwise (both parameters, see above); writes nothing.
-__device__ __forceinline__ BpNext bp_next_one(const uint32_t *bm, const uint16_t *wpre, bool hv, uint32_t len, uint32_t a_last, bool clamped, int q, uint32_t jj,
+__device__ __forceinline__ BpNext bp_next_one(const uint32_t *bm, const uint16_t *wpre, bool hv, uint32_t len, uint32_t a_last, bool anycut, int q, uint32_t jj,
                                            uint32_t m)
 {
     const uint32_t E = hv ? (uint32_t)q + len : (uint32_t)(q + 1);
     uint32_t nxt = hv ? a_last : jj;
-    if (__builtin_amdgcn_ballot_w64(clamped) != 0ull) {   // (wave-uniform, rare)
+    if (__builtin_expect(anycut, 0)) {   // (wave-uniform, rare)
+        const bool clamped = bp_at_limit(hv, E);
         const uint32_t w = E >> 6, bb = E & 63u, wc = w < 63u ? w : 63u;
         const uint32_t lo = bm[2u * wc], hi = bm[2u * wc + 1u];
         const uint32_t mlo = bb >= 32u ? 0xFFFFFFFFu : ((1u << bb) - 1u);
@@ -696,22 +754,26 @@ __device__ __forceinline__ BpSel bp_select_coded(uint8_t *flag, bool valid, uint
     bool sel = false;
     if (cur < jw + 64) {   // (wave-uniform) otherwise the whole window lies inside an earlier match
         const uint32_t e0 = (uint32_t)(cur - jw);
-        uint32_t jump = valid ? (nxt - (uint32_t)jw < 64u ? nxt - (uint32_t)jw : 64u) : 64u;   // nxt > j: always forward
+        // nxt > j: always forward.  (65 for a lane without a one: `the coded one whose successor lies outside` below is p0 == 64
+        // alone; such a lane, if reached, marks flag[65], which like flag[64] nobody reads)
+        uint32_t jump = valid ? (nxt - (uint32_t)jw < 64u ? nxt - (uint32_t)jw : 64u) : 65u;
         const uint32_t p0 = jump;
         flag[lane] = lane == e0 ? 1u : 0u;
         flag[lane == 0u ? 64u : 69u] = 0u;
         BP_FENCE();
-        bool reach = lane == e0;
+        uint32_t mark = lane == e0 ? 1u : 0u;   // the lane's flag: 0 or 1
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
-            flag[reach ? jump : 68u] = 1u;   // (no exec-mask region: a scalar instruction costs this kernel four times a vector one)
+            flag[mark != 0u ? jump : 68u] = 1u;   // (no exec-mask region: a scalar instruction costs this kernel four times a vector one)
             BP_FENCE();
-            reach = flag[lane] != 0u;
-            const uint32_t j2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((jump & 63u) << 2), (int)jump);
+            mark = flag[lane];
+            // (the lane is bits 2-7 of the address: no mask for jump = 64, 65, whose result is not used)
+            const uint32_t j2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(jump << 2), (int)jump);
             jump = jump < 64u ? j2 : 64u;
         }
-        sel = reach && valid;
-        const unsigned long long ex = __builtin_amdgcn_ballot_w64(sel && p0 == 64u);
+        sel = mark != 0u && valid;
+        // (mark and p0 as numbers, one compare for the ballot: not two lane masks joined and turned into a number again)
+        const unsigned long long ex = __builtin_amdgcn_ballot_w64(__umul24(mark, p0) == 64u);
         // the coded one whose successor lies outside the window hands over to the next window
         if (ex != 0ull) cur = (int)__builtin_amdgcn_readlane((int)nxt, (int)(__ffsll((long long)ex) - 1));
     }
@@ -730,23 +792,26 @@ struct BpQueued {
 // write); bp_emit_batch fills stage.  Returns the stream's state and the queue's length.
 template <bool EXC, typename LDS>
 __device__ __forceinline__ BpQueued bp_queue_and_drain(LDS &S, const uint32_t *bm, const uint16_t *P, uint8_t *out, int q, uint32_t q1, bool hv, uint32_t nb,
-                                                       uint32_t c1, uint32_t z_last, bool clamped, uint32_t E, uint32_t nxt, bool sel, int jw, uint32_t m,
+                                                       uint32_t c1, uint32_t z_last, bool anycut, uint32_t E, uint32_t nxt, bool sel, int jw, uint32_t m,
                                                        uint32_t prev_end, uint32_t gop, uint32_t sop, uint32_t qn, uint32_t lane)
 {
     const bool onM = sel && hv;
     // the run behind E starts one later when byte E - 1 is a one (an offset-1 run copies its predecessor): always for a one
     // that codes itself alone (and the virtual one in front of the stream), for a match when it ends with its last one
     uint32_t rs = E + ((!hv || z_last == 0u) ? 1u : 0u);
-    if (__builtin_amdgcn_ballot_w64(clamped) != 0ull)   // (wave-uniform, rare: a match cut at the match limit — ask the bit map)
-        rs = clamped ? E + ((bp_bits(bm, E - 1u) & 1u) ? 1u : 0u) : rs;
+    if (__builtin_expect(anycut, 0))   // (wave-uniform, rare: a match cut at the match limit — ask the bit map)
+        rs = bp_at_limit(hv, E) ? E + ((bp_bits(bm, E - 1u) & 1u) ? 1u : 0u) : rs;
     uint32_t re = (uint32_t)P[(nxt < m ? nxt : m) + 1u] - 1u;   // position of the next one (n behind the last)
     re = re < BP_MATCHLIMIT ? re : BP_MATCHLIMIT;
     const bool onT = sel && (int)re - (int)rs >= BP_TMIN && rs <= BP_MFLIMIT;   // (long enough; emitted or not: bp_emit_batch)
-    const bool want = onM || onT;
+    uint2 ent = bp_entry(E, (uint32_t)(q - (int)nb), onM, onT, rs, re, q1 - c1);   // (packed here: two registers live across a make-room batch)
+    // onM || onT, read off the packed entry: ONE compare, and its result is the ballot (as `onM || onT` the two lane masks are
+    // joined on the scalar unit, turned into 0 / 1 per lane and compared again — the compiler's way from a lane mask to a ballot)
+    BP_HIDE(ent.x);
+    const bool want = ent.x >= BP_ENT_ANY;
     const unsigned long long wm = __builtin_amdgcn_ballot_w64(want);
     const uint32_t nw = (uint32_t)__builtin_popcountll(wm);
     const bool last = jw + 64 >= (int)m;
-    const uint2 ent = bp_entry(E, (uint32_t)(q - (int)nb), onM, onT, rs, re, q1 - c1);   // (packed here: two registers live across a make-room batch)
     // one call site for the batch code: first make room if this window's coded ones would not fit (rare), then queue
     // them, then drain whole batches (everything at the end)
     for (int phase = 0; phase < 2; ++phase) {
@@ -784,7 +849,7 @@ __device__ __forceinline__ BpOut bp_last_literals(LDS &S, const uint32_t *bm, ui
     const uint32_t ll = BP_N - prev_end, llx = bp_len_ext(ll);
     BP_FENCE();
     if (sop + 1u + llx + ll > BpCfg<EXC>::STAGE) {
-        bp_flush(S.stage, out + gop, sop, lane);
+        bp_flush(S.stage + BP_SPARE, out + gop, sop, lane);
         gop += sop;
         sop = 0;
     }
@@ -805,7 +870,7 @@ __device__ __forceinline__ BpOut bp_last_literals(LDS &S, const uint32_t *bm, ui
         tail(out + gop);
         gop += 1u + llx + ll;
     } else {
-        tail(S.stage + sop);
+        tail(S.stage + BP_SPARE + sop);
         sop += 1u + llx + ll;
     }
     return BpOut{prev_end, gop, sop};
@@ -822,7 +887,7 @@ __device__ __forceinline__ uint32_t bp_finish_stream(LDS &S, const uint32_t *bm,
         op = BP_N;
     } else {
         BP_FENCE();
-        bp_flush(S.stage, out + st.gop, st.sop, lane);
+        bp_flush(S.stage + BP_SPARE, out + st.gop, st.sop, lane);
     }
     return op;
 }
@@ -877,8 +942,8 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
             mt = bp_extend_and_price<EXC>(S, P, pk.best >= 0, pk.bjq, pk.bk, pk.a4, o.jj, o.q, o.q1, o.qp1, m);
         }
         BP_MARK("cand_done");
-        if (LAZY) mt = bp_lazy_rule(mt.hv, mt.len, mt.nb, mt.c1, mt.a_last, mt.z_last, mt.clamped, o.j, o.q, o.jj, o.q1, o.qn1, m, lane);
-        const BpNext nx = bp_next_one(bm, wpre, mt.hv, mt.len, mt.a_last, mt.clamped, o.q, o.jj, m);
+        if (LAZY) mt = bp_lazy_rule(mt.hv, mt.len, mt.nb, mt.c1, mt.a_last, mt.z_last, mt.anycut, o.j, o.q, o.jj, o.q1, o.qn1, m, lane);
+        const BpNext nx = bp_next_one(bm, wpre, mt.hv, mt.len, mt.a_last, mt.anycut, o.q, o.jj, m);
         BP_MARK("nxt_done");
         if (BP_SKIP >= 3) {
             sink += nx.nxt + nx.E;
@@ -891,7 +956,7 @@ __device__ __forceinline__ void bp_code_plane(LDS &S, uint32_t wlo, uint32_t whi
             sink += sl.sel ? nx.nxt : 0u;
             continue;
         }
-        st = bp_queue_and_drain<EXC>(S, bm, P, out, o.q, o.q1, mt.hv, mt.nb, mt.c1, mt.z_last, mt.clamped, nx.E, nx.nxt, sl.sel, jw, m, st.out.prev_end,
+        st = bp_queue_and_drain<EXC>(S, bm, P, out, o.q, o.q1, mt.hv, mt.nb, mt.c1, mt.z_last, mt.anycut, nx.E, nx.nxt, sl.sel, jw, m, st.out.prev_end,
                                      st.out.gop, st.out.sop, st.qn, lane);
         BP_MARK("emit_done");
     }
