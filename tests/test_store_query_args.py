@@ -1,7 +1,9 @@
 """CPU: what GenotypeStore's six queries make of bad arguments — read_windows, allele_counts, sample_counts, pair_counts,
 ld_counts, ld_prune, all through store_plan.query_args — on a store that is metadata only (no chunk is ever read, no
 device touched: every call below fails at its arguments).  The exception types and texts are those each query raised when
-it still checked its arguments itself; and the sample index arrays query_args returns."""
+it still checked its arguments itself; and the sample index arrays query_args returns.  The later queries (LD clumping, the
+scans, scores, regions, the feature matrix, the pair matrices) follow with the texts they raised while GenotypeStore was
+one class in one module: the selection first, then each query's own checks, in the order in which they fire."""
 import json
 import types
 
@@ -84,6 +86,209 @@ def test_window_and_r2_come_with_the_query_name(st):
     with pytest.raises(ValueError) as e:
         st.ld_prune("chr_1", r2=1.5)
     assert str(e.value) == "ld_prune: r2 1.5 (0 to 1)"
+
+
+# ---- the later queries: what each raises before it uses the device ---------------------------------------------------------
+
+def n_of(s):
+    return 5 if s is None else len(s)
+
+
+def p_with(i, x):
+    p = np.full(20, 0.5)
+    p[i] = x
+    return p
+
+
+REGION, SEVEN = np.array([[0, 5]]), np.zeros((7, 2), np.int64)
+P, Y = np.full(20, 0.5), np.array([0, 1, 0, 1, 1])
+# each called with (group or groups, samples, v_lo, v_hi, variant_mask) and good arguments otherwise; region_sums, burden and
+# projection_weights take no range
+LATER = dict(
+    ld_clump=lambda st, g, s, lo, hi, m: st.ld_clump(g, P, s, lo, hi, m),
+    assoc_sums=lambda st, g, s, lo, hi, m: st.assoc_sums(g, np.zeros((n_of(s), 1)), s, lo, hi, m),
+    assoc=lambda st, g, s, lo, hi, m: st.assoc(g, np.arange(n_of(s)) * 1.0, None, s, lo, hi, m),
+    assoc_logistic=lambda st, g, s, lo, hi, m: st.assoc_logistic(g, np.arange(n_of(s)) % 2, None, s, lo, hi, m),
+    score_sums=lambda st, g, s, lo, hi, m: st.score_sums(np.zeros((3, 20, 1)), g, s, lo, hi, m),
+    score=lambda st, g, s, lo, hi, m: st.score(np.zeros(20), g, s, lo, hi, m),
+    region_sums=lambda st, g, s, lo, hi, m: st.region_sums(g, REGION, np.zeros((3, 20)), s, m),
+    burden=lambda st, g, s, lo, hi, m: st.burden(g, REGION, None, s, m),
+    projection_weights=lambda st, g, s, lo, hi, m: st.projection_weights(np.zeros((n_of(s), 1)), [1.0], g, s, m),
+    feature_matrix=lambda st, g, s, lo, hi, m: st.feature_matrix(g, s, lo, hi, m, impute="missing"),
+    kinship=lambda st, g, s, lo, hi, m: st.kinship(g, s, lo, hi, m),
+    grm=lambda st, g, s, lo, hi, m: st.grm(g, s, lo, hi, m),
+    pca=lambda st, g, s, lo, hi, m: st.pca(1, g, s, lo, hi, m),
+    ld_r2=lambda st, g, s, lo, hi, m: st.ld_r2(g, s, lo, hi, m))
+NO_RANGE = ("region_sums", "burden", "projection_weights")
+# a foreign group, a sample out of range, an unknown name, a range outside the group, a mask of the wrong length
+LATER_CASES = [
+    (tuple(LATER), ("chr_9", None, 0, None, None), KeyError, "'chr_9'"),
+    (tuple(LATER), ("chr_1", [0, 1, 2, 5], 0, None, None), IndexError, "sample 5 out of range (0..4)"),
+    (tuple(LATER), ("chr_1", ["s0", "s1", "s2", "nobody"], 0, None, None), KeyError, "'nobody'"),
+    (tuple(q for q in LATER if q not in NO_RANGE), ("chr_1", None, 3, 21, None), IndexError,
+     "variants [3, 21) outside chr_1 (0..20)"),
+    (tuple(LATER), ("chr_1", None, 0, None, np.ones(7, bool)), ValueError, "variant_mask of chr_1: shape (7,), expected (20,)"),
+]
+
+
+@pytest.mark.parametrize("who", tuple(LATER))
+def test_later_queries_bad_selection(st, who):
+    n = 0
+    for queries, args, exc, text in LATER_CASES:
+        if who in queries:
+            with pytest.raises(exc) as e:
+                LATER[who](st, *args)
+            assert type(e.value) is exc and str(e.value) == text, (who, args)
+            n += 1
+    assert n >= 4
+
+
+ONE_ARRAY = "{who}: one array of weights needs a single group (several: a dict group -> array)"
+SCORE_W = "{who}: the weights of {g} must be float64 {want} + [K], 1 <= K <= 64, the same K in every group, not {got}"
+REGIONS = "{who}: regions must be integer [R, 2] variant intervals [lo, hi), not {got}"
+REGION_W = "region_sums: the weights of chr_1 must be float64 [3, 20] + [K], 1 <= K <= 16, not {got}"
+BURDEN_W = "burden: the weights of chr_1 must be float64 [20] or [20, K], 1 <= K <= 16, not {got}"
+BUDGET = "{who}: a table of 6 rows x 7 regions x {K} columns ({n} bytes) exceeds max_table_bytes = {limit}"
+P_SHAPE = "ld_clump: p {got}, expected float64 [{n}]"
+P_RANGE = "ld_clump: a p-value outside [0, 1]"
+W_SHAPE = "assoc_sums: W must be float64 [{n}, 1 to 64], not {got}"
+MEAN_INT8 = "call_class_values: impute \"mean\" needs a float dtype, not torch.int8 (an imputed value is no integer)"
+
+
+def own_cases():
+    import torch
+    f32 = lambda a: torch.from_numpy(a).float()
+    cases = [
+        # ld_clump: r2, then the group, then the window; p1 / p2; kb; p
+        (lambda st: st.ld_clump("chr_1", P, window=0), ValueError, "ld_clump: window 0 (1 to 1024)"),
+        (lambda st: st.ld_clump("chr_1", P, window=1025), ValueError, "ld_clump: window 1025 (1 to 1024)"),
+        (lambda st: st.ld_clump("chr_1", P, r2=1.5), ValueError, "ld_clump: r2 1.5 (0 to 1)"),
+        (lambda st: st.ld_clump("chr_1", P, r2=-0.1), ValueError, "ld_clump: r2 -0.1 (0 to 1)"),
+        (lambda st: st.ld_clump("chr_9", P, r2=1.5), ValueError, "ld_clump: r2 1.5 (0 to 1)"),
+        (lambda st: st.ld_clump("chr_9", P, window=0), KeyError, "'chr_9'"),
+        (lambda st: st.ld_clump(BOTH, P), KeyError, "['chr_1', 'chr_2']"),
+        (lambda st: st.ld_clump("chr_1", P, p1=0.5, p2=0.1), ValueError, "ld_clump: p1 0.5, p2 0.1 (0 <= p1 <= p2 <= 1)"),
+        (lambda st: st.ld_clump("chr_1", P, p2=1.5), ValueError, "ld_clump: p1 0.0001, p2 1.5 (0 <= p1 <= p2 <= 1)"),
+        (lambda st: st.ld_clump("chr_1", P, p1=-0.5), ValueError, "ld_clump: p1 -0.5, p2 0.01 (0 <= p1 <= p2 <= 1)"),
+        (lambda st: st.ld_clump("chr_1", P, kb=-1), ValueError, "ld_clump: kb -1 (at least 0, or None)"),
+        (lambda st: st.ld_clump("chr_1", P, kb=1e12), ValueError, "ld_clump: kb 1000000000000.0 (at least 0, or None)"),
+        (lambda st: st.ld_clump("chr_1", P[:19]), ValueError, P_SHAPE.format(got="[19] torch.float64", n=20)),
+        (lambda st: st.ld_clump("chr_1", P, v_lo=2, v_hi=9), ValueError, P_SHAPE.format(got="[20] torch.float64", n=7)),
+        (lambda st: st.ld_clump("chr_1", P[:, None]), ValueError, P_SHAPE.format(got="[20, 1] torch.float64", n=20)),
+        (lambda st: st.ld_clump("chr_1", f32(P)), ValueError, P_SHAPE.format(got="[20] torch.float32", n=20)),
+        (lambda st: st.ld_clump("chr_1", p_with(3, 1.5)), ValueError, P_RANGE),
+        (lambda st: st.ld_clump("chr_1", p_with(3, -0.25)), ValueError, P_RANGE),
+        (lambda st: st.ld_clump("chr_1", p_with(3, np.inf)), ValueError, P_RANGE),
+        (lambda st: st.ld_clump("chr_1", p_with(19, -np.inf)), ValueError, P_RANGE),
+        (lambda st: st.ld_r2("chr_1", window=0), ValueError, "ld_counts: window 0 (1 to 1024)"),
+        # assoc_sums: distinct samples, then W
+        (lambda st: st.assoc_sums("chr_1", np.zeros((3, 1)), [0, "s0", 1]), ValueError, "assoc_sums: a sample is listed twice"),
+        (lambda st: st.assoc_sums("chr_1", np.zeros((5, 1), np.float32)), ValueError,
+         W_SHAPE.format(n=5, got="torch.float32 [5, 1]")),
+        (lambda st: st.assoc_sums("chr_1", np.zeros(5)), ValueError, W_SHAPE.format(n=5, got="torch.float64 [5]")),
+        (lambda st: st.assoc_sums("chr_1", np.zeros((5, 1)), [0, 1]), ValueError, W_SHAPE.format(n=2, got="torch.float64 [5, 1]")),
+        (lambda st: st.assoc_sums("chr_1", np.zeros((5, 0))), ValueError, W_SHAPE.format(n=5, got="torch.float64 [5, 0]")),
+        (lambda st: st.assoc_sums("chr_1", torch.zeros((5, 65), dtype=torch.float64)), ValueError,
+         W_SHAPE.format(n=5, got="torch.float64 [5, 65]")),
+        # assoc_logistic: the test before the group, distinct samples, y
+        (lambda st: st.assoc_logistic("chr_1", Y, test="firth"), ValueError, "assoc_logistic: test 'firth' (\"wald\" or \"score\")"),
+        (lambda st: st.assoc_logistic("chr_9", Y, test="firth"), ValueError, "assoc_logistic: test 'firth' (\"wald\" or \"score\")"),
+        (lambda st: st.assoc_logistic("chr_1", Y, samples=[0, 1, 2, 3, "s3"]), ValueError,
+         "assoc_logistic: a sample is listed twice"),
+        (lambda st: st.assoc_logistic("chr_1", Y[:4]), ValueError,
+         "assoc_logistic: y of shape (4, 1) for 5 samples ([n] or [n, P])"),
+        (lambda st: st.assoc_logistic("chr_1", np.zeros((5, 1, 1))), ValueError,
+         "assoc_logistic: y of shape (5, 1, 1) for 5 samples ([n] or [n, P])"),
+        (lambda st: st.score_sums(np.zeros((3, 20)), "chr_1"), ValueError,
+         SCORE_W.format(who="score_sums", g="chr_1", want="[3, 20]", got="float64 [3, 20]")),
+        (lambda st: st.score(np.zeros((20, 2)), "chr_1", impute="zero"), ValueError, "score: impute 'zero' (\"mean\" or \"none\")"),
+        (lambda st: st.score(np.zeros((20, 2)), "chr_1", freq_samples=[7]), IndexError, "sample 7 out of range (0..4)"),
+    ]
+    # score_sums takes [3, V, K], score [V, K] (lead: the leading axes as the messages print them)
+    for who, w, lead in (("score_sums", np.zeros((3, 20, 2)), "[3, {}"), ("score", np.zeros((20, 2)), "[{}")):
+        call = lambda *a, who=who, **k: (lambda st: getattr(st, who)(*a, **k))
+        text = lambda g, V, got: SCORE_W.format(who=who, g=g, want=lead.format(V) + "]", got=got.format(lead.format(20)))
+        cases += [
+            (call(w, BOTH), ValueError, ONE_ARRAY.format(who=who)),
+            (call(w), ValueError, ONE_ARRAY.format(who=who)),
+            (call({"chr_1": w}, BOTH), KeyError, "'chr_2'"),
+            (call(w.astype(np.float32), "chr_1"), ValueError, text("chr_1", 20, "float32 {}, 2]")),
+            (call(f32(w), "chr_1"), ValueError, text("chr_1", 20, "torch.float32 {}, 2]")),
+            (call(w[..., None], "chr_1"), ValueError, text("chr_1", 20, "float64 {}, 2, 1]")),
+            (call(w, "chr_1", v_lo=1), ValueError, text("chr_1", 19, "float64 {}, 2]")),
+            (call(w[..., :0], "chr_1"), ValueError, text("chr_1", 20, "float64 {}, 0]")),
+            (call(np.zeros(w.shape[:-1] + (65,)), "chr_1"), ValueError, text("chr_1", 20, "float64 {}, 65]")),
+            (call({"chr_1": w, "chr_2": w[..., :5, :1]}), ValueError,
+             SCORE_W.format(who=who, g="chr_2", want=lead.format(5) + "]", got="float64 " + lead.format(5) + ", 1]")),
+            (call({}, []), ValueError, f"{who}: no group"),
+        ]
+    # region_sums takes [3, V, K], burden [V, K]
+    for who, w, W, lead in (("region_sums", np.zeros((3, 20, 2)), REGION_W, "[3, {}"), ("burden", np.zeros((20, 2)), BURDEN_W, "[{}")):
+        call = lambda *a, who=who, **k: (lambda st: getattr(st, who)("chr_1", *a, **k))
+        cases += [
+            (call(np.array([0, 5]), w), ValueError, REGIONS.format(who=who, got="int64 [2]")),
+            (call(np.zeros((2, 3), np.int64), w), ValueError, REGIONS.format(who=who, got="int64 [2, 3]")),
+            (call(np.array([[0.0, 5.0]]), w), ValueError, REGIONS.format(who=who, got="float64 [1, 2]")),
+            (call(REGION, w.astype(np.float32)), ValueError, W.format(got="float32 " + lead.format(20) + ", 2]")),
+            (call(REGION, w[..., :19, :]), ValueError, W.format(got="float64 " + lead.format(19) + ", 2]")),
+            (call(REGION, w[..., None]), ValueError, W.format(got="float64 " + lead.format(20) + ", 2, 1]")),
+            (call(REGION, w[..., :0]), ValueError, W.format(got="float64 " + lead.format(20) + ", 0]")),
+            (call(REGION, np.zeros(w.shape[:-1] + (17,))), ValueError, W.format(got="float64 " + lead.format(20) + ", 17]")),
+            (call(SEVEN, w, max_table_bytes=671), ValueError, BUDGET.format(who=who, K=2, n=672, limit=671)),
+        ]
+    cases += [
+        (lambda st: st.region_sums("chr_1", REGION, np.zeros((20, 2))), ValueError, REGION_W.format(got="float64 [20, 2, 1]")),
+        (lambda st: st.burden("chr_1", REGION, np.zeros((3, 20))), ValueError, BURDEN_W.format(got="float64 [3, 20]")),
+        (lambda st: st.burden("chr_1", SEVEN, max_table_bytes=335), ValueError, BUDGET.format(who="burden", K=1, n=336, limit=335)),
+        (lambda st: st.burden("chr_1", REGION, "gamma"), ValueError, "burden: weights 'gamma' (None, \"beta\" or an array)"),
+        (lambda st: st.burden("chr_1", REGION, coding="dominant"), ValueError,
+         "burden: coding 'dominant' (\"additive\" or \"carrier\")"),
+        (lambda st: st.burden("chr_9", REGION, coding="dominant"), ValueError,
+         "burden: coding 'dominant' (\"additive\" or \"carrier\")"),
+        (lambda st: st.burden("chr_1", REGION, impute="zero"), ValueError, "burden: impute 'zero' (\"mean\" or \"none\")"),
+        (lambda st: st.burden("chr_1", REGION, np.zeros(20), coding="carrier"), ValueError,
+         "burden: coding \"carrier\" takes no weights"),
+        (lambda st: st.burden("chr_1", REGION, "beta", coding="carrier"), ValueError, "burden: coding \"carrier\" takes no weights"),
+        (lambda st: st.burden("chr_1", REGION, freq_samples=["nobody"]), KeyError, "'nobody'"),
+        (lambda st: st.projection_weights(np.zeros((5, 2), np.float32), [1.0, 1.0]), ValueError,
+         "projection_weights: vectors must be float64 [5, k] with k values, not float32 [5, 2]"),
+        (lambda st: st.projection_weights(np.zeros((4, 2)), [1.0, 1.0]), ValueError,
+         "projection_weights: vectors must be float64 [5, k] with k values, not float64 [4, 2]"),
+        (lambda st: st.projection_weights(np.zeros((5, 2)), [1.0]), ValueError,
+         "projection_weights: vectors must be float64 [5, k] with k values, not float64 [5, 2]"),
+        # feature_matrix: the coding before the group; "mean" with int8 is the default's own refusal
+        (lambda st: st.feature_matrix("chr_1", coding="one-hot"), ValueError,
+         "feature_matrix: coding 'one-hot' (\"dosage\", \"standardized\" or \"haplotypes\")"),
+        (lambda st: st.feature_matrix("chr_9", coding="one-hot"), ValueError,
+         "feature_matrix: coding 'one-hot' (\"dosage\", \"standardized\" or \"haplotypes\")"),
+        (lambda st: st.feature_matrix("chr_1", coding="haplotypes", dtype=torch.float32), ValueError,
+         "feature_matrix: dtype torch.float32 for coding 'haplotypes'"),
+        (lambda st: st.feature_matrix("chr_1", dtype=torch.int32), ValueError, "feature_matrix: dtype torch.int32 for coding 'dosage'"),
+        (lambda st: st.feature_matrix("chr_1"), ValueError, MEAN_INT8),
+        (lambda st: st.feature_matrix("chr_1", coding="standardized", dtype=torch.int8), ValueError, MEAN_INT8),
+        (lambda st: st.feature_matrix("chr_1", dtype=torch.float32, impute="zero"), ValueError,
+         "call_class_values: coding 'dosage' (\"dosage\" or \"standardized\"), impute 'zero' (\"mean\" or \"missing\")"),
+        (lambda st: st.feature_matrix("chr_1", dtype=torch.float32, freq_samples=[9]), IndexError, "sample 9 out of range (0..4)"),
+        # pca: k before the group
+        (lambda st: st.pca(0, "chr_1"), ValueError, "pca: k = 0 (1 to 5)"),
+        (lambda st: st.pca(6, "chr_1"), ValueError, "pca: k = 6 (1 to 5)"),
+        (lambda st: st.pca(3, "chr_1", ["s0", "s4"]), ValueError, "pca: k = 3 (1 to 2)"),
+        (lambda st: st.pca(0, "chr_9"), ValueError, "pca: k = 0 (1 to 5)"),
+        (lambda st: st.kinship("chr_1", max_table_bytes=575), ValueError,
+         "pair_counts: a table of 6 x 6 pairs (576 bytes) exceeds max_table_bytes = 575"),
+        (lambda st: st.grm("chr_1", max_table_bytes=863), ValueError,
+         "grm_sums: tables of 6 x 6 pairs (864 bytes) exceed max_table_bytes = 863"),
+    ]
+    return cases
+
+
+def test_later_queries_own_checks(st):
+    cases = own_cases()
+    assert len(cases) == 102
+    for i, (call, exc, text) in enumerate(cases):
+        with pytest.raises(exc) as e:
+            call(st)
+        assert type(e.value) is exc and str(e.value) == text, (i, text)
 
 
 def test_sample_indices_and_group_ranges(st):
