@@ -285,3 +285,196 @@ def test_read_assoc(tmp_path):
     f.write_text(LINEAR)                                                 # a scan without a line is an empty one
     v, p, lines, _ = clump_cli.read_assoc(str(f))
     assert len(v) == 0 and len(p) == 0 and lines == []
+
+
+# ---- the cases of tests/test_gpu_clump.py: every lane-group width, link word and round batch ---------------------------------
+
+from tests import clump_cases as CC                                                                          # noqa: E402
+
+
+def rank_reference(lb, rank, eligible):
+    """clump_reference under a ranking: p = rank for the eligible, above p1 with the order kept for the others (as check_clump
+    of tests/test_gpu_clump.py has it)"""
+    rank, n = np.asarray(rank), len(rank)
+    p = np.where(np.asarray(eligible, bool), rank, rank + 2.0 * n) / (4.0 * n + 1.0)
+    return SS.clump_reference(lb, p, (n + 0.5) / (4.0 * n + 1.0))
+
+
+def hold_case(case, dense=True):
+    """a built case against the word model and, dense, against clump_reference and np_rounds"""
+    n, window = case["n"], case["window"]
+    words = CC.link_words(case["k"], case["d"], n, window)
+    owner, rounds = CC.word_rounds(words, window, case["rank"], case["eligible"])
+    assert np.array_equal(owner, case["owner"]) and rounds == case["rounds"], (window, np.flatnonzero(owner != case["owner"])[:5])
+    if dense:
+        inside = case["d"] < window                                       # (a stray bit has no place in the dense matrix)
+        lb = CC.link_matrix(case["k"][inside], case["d"][inside], n, window)
+        assert inside.all() == np.array_equal(pack_bits(lb), words)
+        assert np.array_equal(rank_reference(lb, case["rank"], case["eligible"]), case["owner"])
+        owner, rounds = np_rounds(lb, case["rank"], case["eligible"].astype(bool))
+        assert np.array_equal(owner, case["owner"]) and rounds == case["rounds"]
+    return words
+
+
+def n_blockers(case):
+    """per variant the linked, eligible variants of lower rank — and the links, read back from the packed words"""
+    words = CC.link_words(case["k"], case["d"], case["n"], case["window"])
+    k, d = CC.links_of(words)
+    u, rank, el = k - 1 - d, case["rank"], case["eligible"].astype(bool)
+    return (np.bincount(k[el[u] & (rank[u] < rank[k])], minlength=case["n"])
+            + np.bincount(u[el[k] & (rank[k] < rank[u])], minlength=case["n"])), words, k, d
+
+
+def test_clump_windows_reach_every_lane_group_width():
+    want = [(1, 2), (2, 4), (2, 4), (3, 8), (3, 8), (4, 8), (5, 16), (5, 16), (7, 16), (8, 16), (9, 32), (15, 32), (16, 32), (16, 32)]
+    assert CC.CLUMP_WINDOWS == (64, 65, 128, 129, 192, 256, 257, 300, 448, 512, 513, 960, 1000, 1024)
+    assert [CC.CLUMP_SHAPES[w] for w in CC.CLUMP_WINDOWS] == want
+    for w, (nq, lpv) in zip(CC.CLUMP_WINDOWS, want):                     # the table is what the rule says: the words of
+        assert 64 * (nq - 1) < w <= 64 * nq                              # the window, the power of two >= 2 nq
+        assert lpv & (lpv - 1) == 0 and 2 * nq <= lpv and (lpv == 2 or lpv < 4 * nq)
+    assert {lpv for _, lpv in want} == {2, 4, 8, 16, 32}
+    for lpv in (8, 16, 32):                                              # a full group, and one with idle lanes j >= 2 nq
+        assert any(l == lpv == 2 * nq for nq, l in want) and any(l == lpv > 2 * nq for nq, l in want)
+    assert {3, 7, 15} <= {nq for nq, _ in want}                          # one below a power of two
+
+
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
+def test_strided_cases_lie_in_one_word_and_have_one_blocker(window):
+    """what the GPU test leans on, for every case it runs: the links of a case lie in exactly one word, every variant that
+    waits has exactly one blocker — so that word decides alone, back under the identity ranking, forward under the reversed
+    one — and the closed forms are what the rounds on the packed words give (the dense references: below)"""
+    nq = CC.n_words(window)
+    pairs = CC.strided_distances(window)
+    assert sorted({q for q, _ in pairs}) == list(range(nq)) and all(64 * q < D <= min(64 * q + 64, window) for q, D in pairs)
+    assert {D for q, D in pairs if q == nq - 1} == {64 * (nq - 1) + 1, window}
+    for q, D in pairs:
+        for ranking in CC.RANKINGS:
+            case = CC.strided(window, D, ranking)
+            n = case["n"]
+            assert n == 9 * D + 1 <= 9217 and case["rounds"] == 10
+            blockers, words, k, d = n_blockers(case)
+            assert words.nbytes < 1.2e6 and np.flatnonzero(words.any(axis=0)).tolist() == [q]
+            assert np.array_equal(k, np.arange(D, n)) and (d == D - 1).all()
+            at = np.arange(n)
+            if ranking == "identity":
+                assert np.array_equal(blockers, at >= D)
+            elif ranking == "reversed":
+                assert np.array_equal(blockers, at < n - D)
+            else:                                                        # the second of an odd chain has none: its head is not eligible
+                assert np.array_equal(blockers, (at >= D) & ~((at < 2 * D) & (at % D % 2 == 1)))
+                assert (case["eligible"] == 0).sum() == D // 2
+            hold_case(case, dense=False)
+
+
+SMALL = tuple(w for w in CC.CLUMP_WINDOWS if w <= 300)
+
+
+@pytest.mark.parametrize("window", SMALL)
+def test_strided_closed_forms_small_windows(window):
+    for q, D in CC.strided_distances(window):
+        for ranking in CC.RANKINGS:
+            hold_case(CC.strided(window, D, ranking))
+
+
+@pytest.mark.parametrize("ranking", CC.RANKINGS)
+@pytest.mark.parametrize("window", tuple(w for w in CC.CLUMP_WINDOWS if w > 300))
+def test_strided_closed_forms_first_and_last_word(window, ranking):
+    nq = CC.n_words(window)
+    for q, D in CC.strided_distances(window):
+        if q in (0, nq - 1):
+            hold_case(CC.strided(window, D, ranking))
+
+
+def test_strided_cases_cut_short():
+    """the closed forms at any number of variants (the workgroup-boundary cases), chains of unequal length included"""
+    for window, D in ((1, 1), (64, 3), (128, 5), (192, 7), (448, 2), (960, 3), (129, 129), (300, 257)):
+        for n in (1, 2, 7, 8, 9, 15, 16, 17, 24, 25, 31, 32, 33, 65, 127, 128, 129, 257, 2 * D + 1, 3 * D - 1):
+            for ranking in CC.RANKINGS:
+                case = CC.strided(window, D, ranking, n=n)
+                hold_case(case)
+                assert case["rounds"] == (n - 1) // D + 1 and (D > 1 or case["rounds"] == n)
+
+
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
+def test_gadgets_and_edges(window):
+    """the builders against the word model at every window, against clump_reference and np_rounds at windows <= 129; every
+    one of a variant's 2 nq words holds the owner of some gadget alone"""
+    nq = CC.n_words(window)
+    alone = set()
+    for turn in range(3):
+        case = CC.gadgets(window, turn)
+        assert case["n"] < 150_000 and len(case["triples"]) == 4 * nq
+        words = hold_case(case, dense=window <= 129)
+        for g, (v, a, b) in enumerate(case["triples"]):
+            assert not case["eligible"][v] and case["eligible"][a] and case["eligible"][b] and case["owner"][a] == a and case["owner"][b] == b
+            assert case["owner"][v] == (a, b, min(a, b))[(g + turn) % 3]
+        for j in range(2 * nq):
+            got, _ = CC.word_rounds(words, window, case["rank"], case["eligible"], ("drop_owner", j))
+            alone |= {(j, v) for v in np.flatnonzero(got != case["owner"])}
+            assert any(v for jj, v in alone if jj == j)
+    ways = {}
+    for turn in range(3):                                                # every gadget goes every way; neighbours differ
+        tr = CC.gadgets(window, turn)
+        for g, (v, a, b) in enumerate(tr["triples"]):
+            ways.setdefault(g, set()).add(int(np.sign(tr["rank"][a] - tr["rank"][b])))
+            assert g % 2 or tr["triples"][g + 1][0] == v + 1
+    assert all(w == {-1, 0, 1} for w in ways.values())
+    for case in CC.edge_cases(window):
+        hold_case(case, dense=window <= 300)
+        assert (case["d"] >= window).any() == bool(case.get("stray")) and (case["d"] == window - 1).any()
+    assert any(c.get("stray") for c in CC.edge_cases(window)) == (window % 64 != 0)
+
+
+def test_word_model_is_the_round_model():
+    """word_rounds against np_rounds on random links, variants that are not eligible among them, and with tied ranks"""
+    rng = np.random.default_rng(0)
+    for window in (1, 7, 65, 129, 300):
+        for density in (min(0.5 / window, 0.4), min(1.5 / window, 0.6)):     # half a link a variant, and one and a half
+            n = 400
+            lb = rng.random((n, window)) < density
+            rank = rng.permutation(n)
+            eligible = rng.random(n) < 0.8
+            want = np_rounds(lb, rank, eligible)
+            got = CC.word_rounds(pack_bits(lb), window, rank, eligible)
+            assert np.array_equal(got[0], want[0]) and got[1] == want[1] >= 2
+            assert np.array_equal(want[0], rank_reference(lb, rank, eligible))
+            rank[0:392:7] = rank[3:392:7]                                # equal ranks, linked ones among them, block neither
+            want = np_rounds(lb, rank, eligible)                         # way (clump_rank never ties: the rounds only)
+            got = CC.word_rounds(pack_bits(lb), window, rank, eligible)
+            assert np.array_equal(got[0], want[0]) and got[1] == want[1] >= 2
+
+
+def device_cases(window):
+    """every crafted case tests/test_gpu_clump.py runs at a window (the paths and the cut cases apart)"""
+    for _, D in CC.strided_distances(window):
+        for ranking in CC.RANKINGS:
+            yield CC.strided(window, D, ranking)
+    for turn in range(3):
+        yield CC.gadgets(window, turn)
+    yield from CC.edge_cases(window)
+
+
+def noticed(cases, mutant):
+    """whether some case gives other owners or rounds under the mutant (the cases with links in the mutant's word first)"""
+    first = lambda c: 0                                                                                     # noqa: E731
+    if isinstance(mutant, tuple) and mutant[0] != "lanes":
+        first = lambda c: not (c["d"] // 64 == mutant[1] % CC.n_words(c["window"])).any()                   # noqa: E731
+    for case in sorted(cases, key=first):
+        owner, rounds = CC.word_rounds(case["words"], case["window"], case["rank"], case["eligible"], mutant)
+        if not np.array_equal(owner, case["owner"]) or rounds != case["rounds"]:
+            return True
+    return False
+
+
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
+def test_the_cases_notice_a_broken_round_model(window):
+    """mutations of the numpy model, never of the device: each one changes the owners or the rounds of some case"""
+    nq, lpv = CC.CLUMP_SHAPES[window]
+    cases = [dict(c, words=CC.link_words(c["k"], c["d"], c["n"], window)) for c in device_cases(window)]
+    for mutant in CC.MUTANTS:
+        assert noticed(cases, mutant) == (mutant != "stray" or window % 64 != 0), mutant
+    for j in range(2 * nq):                                              # a word dropped in the rounds, or by the owners
+        assert noticed(cases, ("drop", j)) and noticed(cases, ("drop_owner", j)), j
+    for lanes in range(1, 2 * nq):                                       # the template of a narrower window: upper words idle
+        assert noticed(cases, ("lanes", lanes)), lanes
+    assert not noticed(cases, None) and not noticed(cases, ("lanes", 2 * nq)) and not noticed(cases, ("lanes", lpv))

@@ -1,7 +1,17 @@
 """GPU: LD clumping.  hhgt_ld_decisions against the numpy restatement of the link bits, hhgt_ld_clump on crafted bits and on
 real tables against store_stats.clump_reference (tests/test_clump_plan.py holds that against a brute force on the CPU and
 proves that the recipes bite), GenotypeStore.ld_clump on real stores against the reference on np_ld_table of the same
-selection, and VCFH5Reader.clump with the clump command end to end."""
+selection, and VCFH5Reader.clump with the clump command end to end.
+
+k_clump_round and k_clump_owners are compiled at LPV = 2, 4, 8, 16 and 32 lanes per variant, the power of two >= 2 nq with nq =
+ceil(window / 64).  The crafted cases run at every window of CLUMP_WINDOWS (tests/clump_cases.py), which reach
+    LPV  2: 64 (nq 1)                LPV  4: 65, 128 (nq 2)           LPV  8: 129, 192 (nq 3: two idle lanes), 256 (nq 4)
+    LPV 16: 257, 300 (nq 5), 448 (nq 7), 512 (nq 8: a full group)     LPV 32: 513 (nq 9), 960 (nq 15), 1000, 1024 (nq 16)
+and at each of them every word on either side decides alone at least once: the strided paths have all their links in one
+word q < nq — at its first and at its last usable bit — and every waiting variant has one blocker, behind it under the
+identity ranking, ahead of it under the reversed one, for ten rounds (past the host's batch of eight); the gadgets have an
+owner found only in word j, for every j of the 2 nq.  tests/test_clump_plan.py holds the expected owners to clump_reference
+on the CPU and proves on the numpy round model that a dropped word, a narrower template or a wider group mask shows."""
 import numpy as np
 import pytest
 import torch
@@ -9,16 +19,18 @@ import torch
 from haplohyped_varawareml_amd import store_stats as SS
 from haplohyped_varawareml_amd._lib import HhgtError
 from haplohyped_varawareml_amd.store import GenotypeStore, export_h5
+from tests import clump_cases as CC
 from tests.test_clump_plan import SEED, np_linked_back, np_rounds, pack_bits, random_p
 from tests.test_gpu_ld import GEOMS, GROUP, PICK, SPARSE, padded, to_dev, write_store
 from tests.test_gpu_sample_counts import np_variant_mask
-from tests.test_ld_plan import FAR_V, far_cohort, ld_genotypes, np_ld_table, np_prune, tie_entries
+from tests.test_ld_plan import FAR_V, FAR_WINDOWS, far_cohort, ld_genotypes, np_ld_table, np_prune, tie_entries
 
 pytestmark = pytest.mark.gpu
 
 S, V = 130, 600
 GUARD = 64                      # sentinel words on either side of the link bits
 SENTINEL = 0x5A5A5A5A5A5A5A5A
+SENTINEL32 = 0x5A5A5A5A                                                 # around the owners (int32)
 
 
 @pytest.fixture(scope="module")
@@ -124,20 +136,33 @@ def test_ld_decisions_at_ties(ctx):
 
 # ---- hhgt_ld_clump on crafted bits -------------------------------------------------------------------------------------------
 
-def clump(ctx, lb, rank, eligible):
-    """hhgt_ld_clump on the link bits of bool [n, window] -> (owner int64 [n], rounds)"""
+def clump_words(ctx, words, window, rank, eligible, guarded=False):
+    """hhgt_ld_clump on packed link words int64 [n, nq] -> (owner int64 [n], rounds); guarded: the owners go into a buffer
+    between sentinels, and nothing outside them is written"""
     dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(ctx.device)                # noqa: E731
-    owner, rounds = ctx.ld_clump(dev(pack_bits(lb), np.int64), lb.shape[1], dev(rank, np.int32), dev(eligible, np.uint8))
-    assert owner.dtype == torch.int32 and tuple(owner.shape) == (len(lb),) and isinstance(rounds, int)
+    n, buf, out = len(words), None, None
+    if guarded:
+        buf = torch.full((2 * GUARD + n,), SENTINEL32, dtype=torch.int32, device=ctx.device)
+        out = buf[GUARD:GUARD + n]
+    owner, rounds = ctx.ld_clump(dev(words, np.int64), window, dev(rank, np.int32), dev(eligible, np.uint8), owner=out)
+    assert owner.dtype == torch.int32 and tuple(owner.shape) == (n,) and isinstance(rounds, int)
+    if guarded:
+        host = buf.cpu().numpy()
+        assert owner.data_ptr() == out.data_ptr() and (host[:GUARD] == SENTINEL32).all() and (host[GUARD + n:] == SENTINEL32).all()
     return owner.cpu().numpy().astype(np.int64), rounds
 
 
-def check_clump(ctx, lb, rank, eligible):
+def clump(ctx, lb, rank, eligible, guarded=False):
+    """hhgt_ld_clump on the link bits of bool [n, window] -> (owner int64 [n], rounds)"""
+    return clump_words(ctx, pack_bits(lb), lb.shape[1], rank, eligible, guarded)
+
+
+def check_clump(ctx, lb, rank, eligible, guarded=False):
     """against clump_reference (p = rank, p1 = the eligible ones' largest) and the numpy rounds"""
     rank, eligible = np.asarray(rank), np.asarray(eligible, bool)
     p = np.where(eligible, rank, rank + 2.0 * len(rank)) / (4.0 * len(rank) + 1.0)     # not eligible: above p1, order kept
     want = SS.clump_reference(lb, p, (len(rank) + 0.5) / (4.0 * len(rank) + 1.0))
-    got, rounds = clump(ctx, lb, rank, eligible)
+    got, rounds = clump(ctx, lb, rank, eligible, guarded)
     assert np.array_equal(got, want), np.flatnonzero(got != want)[:10]
     want_rounds = np_rounds(lb, rank, eligible)
     assert np.array_equal(want_rounds[0], want) and rounds == want_rounds[1]
@@ -161,12 +186,13 @@ def test_ld_clump_path_takes_n_rounds(ctx):
         assert 2 <= rounds < n
 
 
-@pytest.mark.parametrize("window", [1024, 1000, 65])
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
 def test_ld_clump_star(ctx, window):
-    """a centre with leaves at distances 1, 64, 65, 1023 and 1024 on both sides (those within the window): guards an upper
-    word, the forward / backward transposition and d < window off by one; and a bit that points before variant 0"""
+    """a centre with leaves at distances 1, 64, 65, 1023, 1024, window - 1 and window on both sides (those within the window):
+    guards an upper word, the forward / backward transposition and d < window off by one; and a bit that points before
+    variant 0"""
     c, n = 1050, 2100
-    dists = [D for D in (1, 64, 65, 1023, 1024) if D <= window]
+    dists = sorted(D for D in {1, 64, 65, 1023, 1024, window - 1, window} if 1 <= D <= window)
     lb = np.zeros((n, window), bool)
     for D in dists:
         lb[c, D - 1] = lb[c + D, D - 1] = True
@@ -209,6 +235,99 @@ def test_ld_clump_small_and_degenerate(ctx):
         assert owner.tolist() == [-1] and rounds == 0
 
 
+# ---- hhgt_ld_clump at every lane-group width: one word at a time, the owners' minimum, batch and workgroup boundaries ----------
+
+def run_case(ctx, case, guarded=False):
+    """a case of tests/clump_cases.py on the device, against the owners and rounds it was built for"""
+    words = CC.link_words(case["k"], case["d"], case["n"], case["window"])
+    owner, rounds = clump_words(ctx, words, case["window"], case["rank"], case["eligible"], guarded)
+    bad = np.flatnonzero(owner != case["owner"])
+    assert not len(bad) and rounds == case["rounds"], (case["window"], case["n"], bad[:10], owner[bad[:10]], rounds)
+
+
+def check_case(ctx, case, guarded=False):
+    """the same through check_clump: against clump_reference and the numpy rounds, and then against the case's own owners"""
+    lb = CC.link_matrix(case["k"], case["d"], case["n"], case["window"])
+    owner, rounds = check_clump(ctx, lb, case["rank"], case["eligible"], guarded)
+    assert np.array_equal(owner, case["owner"]) and rounds == case["rounds"], (case["window"], case["n"])
+
+
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
+def test_ld_clump_strided_paths(ctx, window):
+    """chains of stride D, 9 D + 1 variants: all links in word (D - 1) // 64, for every word of the window at its first and
+    its last usable bit.  Identity ranking: every blocker in a back word; reversed: in a forward word; both wait through
+    that word for ten rounds.  Opposite: neighbouring lane groups of a wave give opposite verdicts in every round.  Guards a
+    word that is not walked (a lane group too narrow for the window, idle lanes cut at the wrong place), a group mask that
+    takes in the neighbour, the state handed over across the batch of eight rounds"""
+    for _, D in CC.strided_distances(window):
+        for ranking in CC.RANKINGS:
+            run_case(ctx, CC.strided(window, D, ranking))
+
+
+@pytest.mark.parametrize("ranking", CC.RANKINGS)
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
+def test_ld_clump_strided_paths_against_the_reference(ctx, window, ranking):
+    """the first and the last word of every window once more, against clump_reference and np_rounds themselves"""
+    nq = CC.n_words(window)
+    for q, D in CC.strided_distances(window):
+        if q in (0, nq - 1):
+            check_case(ctx, CC.strided(window, D, ranking))
+
+
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
+def test_ld_clump_owner_is_the_minimum_over_the_words(ctx, window):
+    """k_clump_owners' shuffle reduction over LPV lanes: per word j of the 2 nq a variant that is not eligible, with one
+    linked index in word j and one in word j + 1 or j - 1 — the lower rank owns it, the earlier variant at equal ranks —,
+    two such variants side by side that go different ways"""
+    for turn in range(3):
+        case = CC.gadgets(window, turn)
+        run_case(ctx, case)
+        if window <= 129:
+            check_case(ctx, case)
+
+
+@pytest.mark.parametrize("window", CC.CLUMP_WINDOWS)
+def test_ld_clump_edges_of_the_last_word(ctx, window):
+    """a link at exactly distance `window` counts, either way round; a bit at or past `window` in the last word of a window
+    that is no multiple of 64 counts for nothing — csrc/clump.hip masks d < window on both sides when it gathers the
+    blockers and the forward links, and again when the owners walk the back words — whether it sits on an eligible variant,
+    on one that is not, or beside a real link (include/hhgt.h: hhgt_ld_decisions leaves such bits 0)"""
+    cases = CC.edge_cases(window)
+    assert len(cases) == (3 if window % 64 else 2)
+    for case in cases:
+        run_case(ctx, case)
+
+
+@pytest.mark.parametrize("window", [1, 129])
+def test_ld_clump_rounds_at_the_batch_boundary(ctx, window):
+    """paths of n variants take n rounds: one below, at and one past the host's batches of eight launches, one and two
+    variants; the owners alternate; a second call, on the workspace of the first, gives the same"""
+    for n in (1, 2, 7, 8, 9, 15, 16, 17, 24, 25):
+        for ranking in ("identity", "reversed"):
+            case = CC.strided(window, 1, ranking, n=n)
+            assert case["rounds"] == n
+            if ranking == "identity":
+                assert case["owner"].tolist() == [k - k % 2 for k in range(n)]
+            else:
+                assert case["owner"].tolist() == [k + (n - 1 - k) % 2 for k in range(n)]
+            for _ in range(2):
+                check_case(ctx, case)
+
+
+@pytest.mark.parametrize("window", [64, 128, 192, 448, 960])
+def test_ld_clump_variants_at_the_workgroup_boundary(ctx, window):
+    """a workgroup holds 256 / LPV variants: one less, exactly that, one more, and two workgroups and one — the owners
+    between sentinels, nothing written outside them"""
+    per = 256 // CC.CLUMP_SHAPES[window][1]
+    assert per == {64: 128, 128: 64, 192: 32, 448: 16, 960: 8}[window]
+    for n in (per - 1, per, per + 1, 2 * per + 1):
+        for D in sorted({1, 2, min(max(n // 3, 1), window)}):
+            for ranking in CC.RANKINGS:
+                case = CC.strided(window, D, ranking, n=n)
+                assert len(case["k"]) == n - D > 0
+                check_case(ctx, case, guarded=True)
+
+
 # ---- both kernels on real tables ---------------------------------------------------------------------------------------------
 
 def device_clump(ctx, table, window, r2, p, p1, pos=None, max_dist=None):
@@ -243,20 +362,27 @@ def test_ld_clump_on_the_recipe(ctx, recipe, window):
         assert np.array_equal(got, narrow) and np.array_equal(got, SS.clump_reference(np_linked_back(table[:, :20], 0.2), p, 0.3))
 
 
-def test_ld_clump_on_the_far_recipe(ctx, far):
-    """n = 3000 at window 1024: sixteen words a side; the only links are the planted copies, up to 1024 places apart"""
-    table = far["table"]
-    lb = far_links(far, 1024, 0.5)
+@pytest.mark.parametrize("window", FAR_WINDOWS)
+def test_ld_clump_on_the_far_recipe(ctx, far, window):
+    """n = 3000 at windows of two to sixteen words a side (LPV 4 to 32; 300 and 513 with idle lanes); the only links are the
+    planted copies, up to `window` places apart"""
+    table = far["table"][:, :window]
+    lb = far_links(far, window, 0.5)
     p = random_p(SEED, FAR_V)
     for p1 in (1.0, 0.3):
         want = SS.clump_reference(lb, p, p1)
-        got, rounds = device_clump(ctx, table, 1024, 0.5, p, p1)
+        got, rounds = device_clump(ctx, table, window, 0.5, p, p1)
         assert np.array_equal(got, want), np.flatnonzero(got != want)[:10]
         assert rounds == np_rounds(lb, SS.clump_rank(p), p <= p1)[1] >= 2
         claimed = np.flatnonzero((want >= 0) & (want != np.arange(FAR_V)))
-        assert len(claimed) >= 10 and np.abs(want[claimed] - claimed).max() >= 1000
-    keep = ctx.ld_prune(to_dev(ctx, padded(table, 1024, 0, FAR_V)), 0.5).cpu().numpy()[1024:].astype(bool)
-    got, _ = device_clump(ctx, table, 1024, 0.5, np.linspace(1e-9, 1.0, FAR_V), 1.0)
+        farthest = np.abs(want[claimed] - claimed).max()
+        if window == 1024:
+            assert len(claimed) >= 10 and farthest >= 1000
+        if p1 == 1.0:                                                    # the copy at distance `window`: its top word decides
+            assert len(claimed) >= 10 and farthest == window
+        assert len(claimed) >= 5
+    keep = ctx.ld_prune(to_dev(ctx, padded(table, window, 0, FAR_V)), 0.5).cpu().numpy()[window:].astype(bool)
+    got, _ = device_clump(ctx, table, window, 0.5, np.linspace(1e-9, 1.0, FAR_V), 1.0)
     assert np.array_equal(got == np.arange(FAR_V), keep) and not keep.all()
 
 
@@ -427,6 +553,26 @@ def test_store_ld_clump_leaves_read_cache_alone(ctx, stores):
         assert st.stats["chunks_read"] == n and all(np.array_equal(x, y) for x, y in zip(first, again))
         assert np.array_equal(st.ld_clump(GROUP, p, PICK, p1=0.3, p2=0.8, slab_bytes=3000).cpu().numpy(), a) and (a >= 0).any()
         st.close()
+
+
+def test_store_ld_clump_far_windows(ctx, far, tmp_path):
+    """the long-range cohort in a store of 128-variant chunks at windows of 3, 5 and 9 words (LPV 8, 16, 32, all with idle
+    lanes): with the default budgets and with tiles shorter than the window, the bits then written by several
+    hhgt_ld_decisions calls; a claimed variant lies in the top word of its owner"""
+    d = str(tmp_path / "far.hhgt")
+    write_store(ctx, d, far["g"], 64, 128)
+    p = random_p(SEED, FAR_V)
+    st = GenotypeStore(d, ctx=ctx)
+    for window in (129, 300, 513):
+        want = SS.clump_reference(far_links(far, window, 0.5), p, 1.0)
+        claimed = np.flatnonzero((want >= 0) & (want != np.arange(FAR_V)))
+        assert (np.abs(want[claimed] - claimed) > 64 * (CC.n_words(window) - 1)).any()
+        for kw in (dict(), dict(plane_bytes=1, slab_bytes=3000)):
+            st.stats["clump_rounds"] = 0
+            got = st.ld_clump(GROUP, p, p1=1.0, p2=1.0, r2=0.5, window=window, kb=None, **kw).cpu().numpy()
+            assert np.array_equal(got, want), (window, kw, np.flatnonzero(got != want)[:10])
+            assert st.stats["clump_rounds"] == np_rounds(far_links(far, window, 0.5), SS.clump_rank(p), np.ones(FAR_V, bool))[1]
+    st.close()
 
 
 # ---- reader and CLI ----------------------------------------------------------------------------------------------------------
