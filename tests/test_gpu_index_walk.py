@@ -193,6 +193,81 @@ def test_newline_of_another_line_where_the_head_points(ctx, S):
     assert_one_pass(ctx, t3, S, o3, region="chr7")
 
 
+# ---- the hand-overs between the walk's phases (csrc/index.hip: walk_batch -> check_candidate -> search_newline / read_head) --
+# Fixed-width GT records — the batch path, four lines per step — with ONE line that breaks the chain, at every slot of the
+# four-line step: each kind of break leaves the batch by another door.
+
+def _info(new):
+    def f(ln, S):
+        c = ln.split(b"\t")
+        c[7] = new(c[7])
+        return [b"\t".join(c)]
+    return f
+
+
+def _gt_dp(ln, S):
+    c = ln.split(b"\t")
+    c[8] = b"GT:DP"
+    c[9:] = [x + b":7" for x in c[9:]]
+    return [b"\t".join(c)]
+
+
+HAND_OVERS = {
+    "info_300_longer": _info(lambda c: c + b"q" * 300),     # the head ends past the batch's 256-byte window, inside the 1 KiB one
+    "info_1000": _info(lambda c: b"X=" + b"q" * 998),       # fewer than nine tabs in the 1 KiB head
+    "gt_dp": _gt_dp,                         # a FORMAT without a computable width
+    "crlf": lambda ln, S: [ln + b"\r"],
+    "header_and_blank": lambda ln, S: [ln, b"##note=between the records", b""],
+    "one_column_short": lambda ln, S: [b"\t".join(ln.split(b"\t")[:9 + S - 1])],      # the batch head cannot see it (`rehead`)
+}
+_hand_over_cache = {}
+
+
+def hand_over_text(kind, k, twice, S=800, V=100):
+    """-> (text, the oracle's result or None where it rejects the text).  The break replaces line 40 + k (and, `twice`,
+    line 41 + k: two steps in a row that get nowhere switch the batches off for the wave's range); uniform lines follow."""
+    if "lines" not in _hand_over_cache:
+        _hand_over_cache["lines"] = wide_lines(S, V)
+    hdr, rec = _hand_over_cache["lines"]
+    out = []
+    for j, ln in enumerate(rec):
+        out += HAND_OVERS[kind](ln, S) if j == 40 + k or (twice and j == 41 + k) else [ln]
+    t = b"\n".join(hdr + out) + b"\n"
+    assert len(t) > 3 * WAVE_RANGE
+    try:
+        return t, oracle.vcf_encode(t, S, region="chr7")
+    except RuntimeError as e:
+        assert "oracle_vcf_encode failed rc=-2" in str(e), e      # the oracle's parse error (too few sample columns), nothing else
+        return t, None
+
+
+@pytest.mark.parametrize("twice", [False, True], ids=["once", "twice"])
+@pytest.mark.parametrize("k", range(4))
+@pytest.mark.parametrize("kind", sorted(HAND_OVERS))
+def test_hand_overs_between_the_phases(ctx, kind, k, twice):
+    S = 800
+    t, o = hand_over_text(kind, k, twice, S)
+    if kind == "one_column_short":
+        assert o is None
+        for m in (0, 1, 2):                  # every mode reports HHGT_ERR_MALFORMED
+            ctx.set_index_mode(m)
+            try:
+                with pytest.raises(HhgtError, match="Error parsing VCF file"):
+                    gpu_encode(ctx, t, S, region="chr7")
+            finally:
+                ctx.set_index_mode(-1)
+        assert_one_pass(ctx, t, S, None, region="chr7", flaggable=True, forms=[(m, p) for m in (0, 1, 2) for p in (False, True)])
+        return
+    assert o is not None and o["n_kept"] == 100
+    g = encode_modes(ctx, t, S, "chr7")
+    for m in g:
+        assert_same_as_oracle(g[m], o)
+    same(g[0], g[2])
+    same(g[1], g[2])
+    # (the synchronous call scans every byte once more where a pass fails: one pass of each mode must equal the oracle too)
+    assert_one_pass(ctx, t, S, o, region="chr7", forms=[(m, p) for m in (0, 1, 2) for p in (False, True)])
+
+
 # ---- the width of the last non-GT record as the guess for the next one (the walk's `len_other`) -------------------------
 # A non-GT record A, a shorter non-GT record B, then lines whose lengths add up so that one of them ends exactly at
 # soff_B + len(A's sample columns): where the last record of B's kind says B's newline is.  Valid text, none of the shapes

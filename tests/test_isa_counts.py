@@ -16,7 +16,12 @@ counts.  Metadata only.
 
 The same for csrc/lz4.hip: the byte-wise coder is a driver over inlined phases, and each of the nine
 instantiations of k_lz4_blocks keeps the registers, spills and scratch it had as one function body; three of them sit exactly
-on an occupancy line (72 VGPRs at seven waves per SIMD, 64 at eight).  Its LDS is all dynamic.  Metadata only."""
+on an occupancy line (72 VGPRs at seven waves per SIMD, 64 at eight).  Its LDS is all dynamic.  Metadata only.
+
+The same for csrc/index.hip: k_index_hop is a loop over inlined phases and k_parse_fixed a sequence of steps,
+and the four instantiations of the one and the other keep what they had as one function body each — here the scalar side
+counts too (the walk's state is wave-uniform and must stay in scalar registers: SGPRs and SGPR spills are part of the budget).
+The instruction lines of each body are printed beside profiles/r15_index_isa.txt."""
 import os
 import re
 import shutil
@@ -65,6 +70,13 @@ LD_UNTOUCHED.update({f"k_ld_walkILi{_nq}EE": v for _nq, v in zip((1, 2, 4, 8, 16
 LZ4_BUDGET = {(0, 5, False): (76, 0, 0), (8, 5, False): (64, 12, 48), (0, 6, False): (80, 0, 0), (7, 6, False): (72, 3, 12),
               (0, 7, False): (80, 0, 0), (7, 7, False): (72, 3, 12), (8, 5, True): (64, 19, 76), (7, 6, True): (72, 17, 68),
               (7, 7, True): (72, 18, 72)}
+
+
+# kernel of index.hip as it stands in the mangled name -> (VGPRs, SGPRs, SGPR spills, spilled VGPRs, scratch bytes, static LDS
+# bytes) before k_index_hop and k_parse_fixed were cut into phases
+INDEX_BUDGET = {"k_index_hopILi5ELb1EE": (94, 106, 8, 0, 0, 0), "k_index_hopILi3ELb1EE": (57, 106, 2, 0, 0, 0),
+                "k_index_hopILi5ELb0EE": (52, 101, 0, 0, 0, 0), "k_index_hopILi3ELb0EE": (42, 89, 0, 0, 0, 0),
+                "k_parse_fixed": (83, 82, 0, 0, 0, 17432)}
 
 
 def gfx950_asm(tmp_path_factory, stem):
@@ -176,6 +188,21 @@ def test_ld_kernels_outside_the_tile_keep_their_registers(plane_asm, kernel):
     print(meta_line(kernel, meta))
     assert meta["vgpr_count"] == LD_UNTOUCHED[kernel], meta["vgpr_count"]
     assert (meta["vgpr_spill_count"], meta["private_segment_fixed_size"]) == (0, 0)
+
+
+@pytest.fixture(scope="module")
+def index_asm(tmp_path_factory):
+    return gfx950_asm(tmp_path_factory, "index")
+
+
+@pytest.mark.parametrize("kernel", sorted(INDEX_BUDGET))
+def test_line_index_budget(index_asm, kernel):
+    meta = kernel_meta(index_asm, kernel)
+    body = [ln for ln in kernel_body(index_asm, kernel).splitlines() if ln.strip()]
+    print(meta_line(kernel, meta) + f", {len(body)} lines of kernel body (profiles/r15_index_isa.txt)")
+    got = (meta["vgpr_count"], meta["sgpr_count"], meta["sgpr_spill_count"], meta["vgpr_spill_count"],
+           meta["private_segment_fixed_size"], meta["group_segment_fixed_size"])
+    assert all(g <= b for g, b in zip(got, INDEX_BUDGET[kernel])), (got, INDEX_BUDGET[kernel])
 
 
 @pytest.mark.parametrize("mw,effort,planes", sorted(LZ4_BUDGET))
