@@ -136,6 +136,7 @@ PROTOTYPES = {
     "hhgt_ld_decisions": (_i32, [_vp, _vp, _u64, _u32, C.c_double, _vp, C.c_int64, _vp, _vp]),
     "hhgt_ld_clump": (_i32, [_vp, _vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(_u32), _vp]),
     "hhgt_assoc_sums": (_i32, [_vp, _vp, _u64, _u64, _vp, _u32, _vp, _vp]),
+    "hhgt_quad_forms": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "hhgt_logistic_fit": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "hhgt_score_sums": (_i32, [_vp, _vp, _u64, _u64, _u64, _u64, _vp, _u32, _vp, _vp]),
     "hhgt_region_sums": (_i32, [_vp, _vp, _u64, _u64, _vp, _u32, _vp, _u64, _vp, _u64, _u64, _u64, _vp, _pu64, _vp]),

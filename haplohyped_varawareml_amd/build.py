@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libhhgt.so")
 OBJ = os.path.join(ROOT, "build", "obj")
 SOURCES = ["scan.hip", "index.hip", "encode.hip", "lz4.hip", "lz4bits.hip", "frame.hip", "decode.hip", "inflate.hip", "synth.hip",
-           "reader.hip", "ingest.hip", "onehot.hip", "pairs.hip", "grm.hip", "ld.hip", "clump.hip", "assoc.hip", "logistic.hip", "score.hip", "region.hip",
+           "reader.hip", "ingest.hip", "onehot.hip", "pairs.hip", "grm.hip", "ld.hip", "clump.hip", "assoc.hip", "quad.hip", "logistic.hip", "score.hip", "region.hip",
            "api.hip"]
 # -mssse3: host side only (pshufb in csrc/fast_inflate.h; every x86-64 host of an MI355X has it)
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wno-unused-value", "-mssse3"]

@@ -1458,6 +1458,23 @@ extern "C" int hhgt_assoc_sums(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t 
                             [&](hipStream_t st) { return launch_assoc_sums(d_vplanes, n_var, sw, d_w, n_cols, d_sums, st); });
 }
 
+// hhgt_quad_forms: the pointers its work needs (the forms with a variant, everything else with a variant and a word), their
+// alignment; the limits on the variants and the words are the launch's
+extern "C" int hhgt_quad_forms(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_coef,
+                               const double *d_a, double *d_q, void *stream)
+{
+    const bool reads = n_var && sw;
+    TRY(check_not_null("quad_forms", c,
+                       !n_var ? nullptr : !d_q ? "forms" : !reads ? nullptr : !d_vplanes ? "variant planes"
+                       : !d_coef ? "coefficients" : !d_a ? "matrix" : nullptr));
+    if (off_alignment(d_coef, 8) || off_alignment(d_a, 16) || off_alignment(d_q, 8)) {
+        hhgt_set_error("quad_forms: the coefficients and the forms must be 8-byte aligned, the matrix 16-byte aligned");
+        return HHGT_ERR_ARG;
+    }
+    return launch_on_device(c, stream, HHGT_STAGE_ASSOC, n_var != 0,
+                            [&](hipStream_t st) { return launch_quad_forms(d_vplanes, n_var, sw, d_coef, d_a, d_q, st); });
+}
+
 // hhgt_logistic_fit: the columns of X, the pointers its work needs (the records with a variant, everything else with a variant
 // and a word), their alignment
 extern "C" int hhgt_logistic_fit(hhgt_ctx *c, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const uint32_t *d_valid,

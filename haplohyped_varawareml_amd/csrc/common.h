@@ -493,6 +493,9 @@ int launch_clump_owners(const uint64_t *d_bits, uint64_t n_var, uint32_t window,
 // assoc.hip
 int launch_assoc_sums(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
                       double *d_sums, hipStream_t st);
+// quad.hip
+int launch_quad_forms(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_coef, const double *d_a, double *d_q,
+                      hipStream_t st);
 // logistic.hip
 int launch_logistic_fit(const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const uint32_t *d_valid, const double *d_x,
                         uint32_t q, const double *d_y, const double *d_beta0, double *d_out, hipStream_t st);

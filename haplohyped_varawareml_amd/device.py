@@ -634,6 +634,24 @@ class Context:
                                            _stream()))
         return sums
 
+    def quad_forms(self, vplanes, coef, a, q=None):
+        """the quadratic form of every variant (hhgt_quad_forms) of variant-major planes [3, n, sw] in one matrix: coef is a
+        float64 tensor [n, 3], a float64 [32 * sw, 32 * sw], symmetric (the caller's promise: one triangle is read) and
+        finite, zeros in the rows and columns of no listed sample, both contiguous and on the planes' device; q, a float64
+        tensor [n], gets x^T a x with x(s) = coef[v, 0] HET + coef[v, 1] COMPLETE + coef[v, 2] HOM_ALT of the bits at s —
+        every entry written (default: a new tensor), on the current stream.  -> q"""
+        n, sw = _planes_arg(vplanes, "vplanes: a contiguous int32 tensor [3, n_var, sw]")
+        for name, t, shape in (("coef", coef, (n, 3)), ("a", a, (32 * sw, 32 * sw))):
+            if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != vplanes.device:
+                raise ValueError(f"{name}: a contiguous float64 tensor {list(shape)} on the planes' device")
+        with torch.cuda.device(self.device):
+            if q is None:           # (every entry is written: no need for zeros)
+                q = torch.empty((n,), dtype=torch.float64, device=self.device)
+            q = self._out_arg(q, torch.float64, (n,), "q")
+            check(self.lib.hhgt_quad_forms(self.h, _ptr_if_any(vplanes), n, sw, _ptr_if_any(coef), _ptr_if_any(a), _ptr_if_any(q),
+                                           _stream()))
+        return q
+
     def logistic_fit(self, vplanes, valid, X, y, beta0, out=None):
         """per-variant logistic fits (hhgt_logistic_fit) over variant-major planes [3, n, sw]: valid is an int32 tensor [sw]
         with a bit for every position that is a listed sample, X float64 [32 * sw, q] (1 <= q <= 14), y float64 [32 * sw]

@@ -28,7 +28,7 @@ import numpy as np
 
 from .store import (AC, AN, HET, HET1, HETHET, HOM_ALT, IBS0, NSNP, GenotypeStore, assoc_design,
                     check_components, clump_summary, dense_assoc, dense_logistic_score, grm_from_sums, kinship_from_counts,
-                    logistic_design, logistic_score_design, top_eigenpairs, variant_columns)
+                    logistic_design, logistic_score_design, loco_sums, mixed_null, top_eigenpairs, variant_columns)
 
 
 def _span(starts, start, end):
@@ -463,6 +463,67 @@ class VCFH5Reader:
                     rec["steps"], rec["status"] = info[:, k, 0], info[:, k, 1]
                 parts[k].append(rec)
         return [np.concatenate(p) if p else np.zeros(0, dtype=dtype) for p in parts]
+
+    def mixed_association(self, phenotypes, covariates=None, chromosomes=None, donor_ids=None, min_maf=None, grm_min_maf=None,
+                          ld_window=None, ld_r2=0.2, loco=False):
+        """mixed-model association scan of chr_{N} for N in chromosomes (one name or a list; None: every group) over
+        donor_ids (default: every sample, store order; each donor once) -> (records, nulls).  records is association's
+        list — one host numpy record array per phenotype, one record per scanned variant: chrom, pos, ref, alt, n, af, beta,
+        se, z, p —, the statistics those of store_stats.mixed_from_forms: the generalised least-squares effect of the
+        dosage in y = [1 | covariates] alpha + dosage beta + u + e with Var(u) = sg2 K, the variance components fixed at
+        the null model (store_stats.mixed_null; the formulas there are the contract, not GCTA's .mlma file).  K is the
+        relationship matrix of genetic_relationship over the same donors and chromosomes, with grm_min_maf, ld_window and
+        ld_r2 as its min_maf, ld_window and ld_r2; the scan itself runs over the variants that pass min_maf.  loco = True:
+        every scanned chromosome is tested against the K of the other chosen chromosomes (GenotypeStore.grm_sums once per
+        group, store_stats.loco_sums, a null fit per chromosome and phenotype) — ValueError if only one is chosen.  nulls is
+        a list with one record array per phenotype: chrom, h2, sigma2 — one record with chrom "*" without loco, one per
+        scanned chromosome with it."""
+        from .store_mixed import scan_under_null
+        st = self.store
+        names, donors, who = self._cohort(chromosomes, donor_ids)
+        y = np.asarray(phenotypes, dtype=np.float64)
+        y = y[:, None] if y.ndim == 1 else y
+        cov = None if covariates is None else np.asarray(covariates, dtype=np.float64)
+        grm_masks = self._variant_masks(names, who, min_maf=grm_min_maf, ld_window=ld_window, ld_r2=ld_r2)
+        tables = [st.variants(g) for g in names]
+        width = max([len(r[1].encode()) for t in tables for r in t[3]] + [1])
+        if loco:
+            by_group = {g: st.grm_sums([g], who, variant_mask={g: grm_masks[g]} if g in grm_masks else None) for g in names}
+            sums, nsnp = {g: x[0] for g, x in by_group.items()}, {g: x[1] for g, x in by_group.items()}
+            kin = {g: grm_from_sums(*loco_sums(sums, nsnp, g)).cpu().numpy() for g in names}
+        else:
+            kin = dict.fromkeys(names, grm_from_sums(*st.grm_sums(names, who, variant_mask=grm_masks or None)).cpu().numpy())
+        fitted = {}                                              # (id of the matrix, phenotype) -> its null model
+
+        def null_of(g, k):
+            key = (id(kin[g]), k)
+            if key not in fitted:
+                fitted[key] = mixed_null(kin[g], y[:, k], cov)
+            return fitted[key]
+        floats = ("beta", "se", "z", "p")
+        dtype = [("chrom", f"S{width}"), ("pos", np.uint32), ("ref", "S10"), ("alt", "S10"), ("n", np.int64),
+                 ("af", np.float64)] + [(f, np.float64) for f in floats]
+        null_dtype = [("chrom", f"S{width}"), ("h2", np.float64), ("sigma2", np.float64)]
+        parts, nulls = [[] for _ in range(y.shape[1])], [[] for _ in range(y.shape[1])]
+        for g, t in zip(names, tables):
+            mask = self._variant_masks([g], who, min_maf=min_maf).get(g)
+            at = np.arange(len(t[0])) if mask is None else np.flatnonzero(mask.cpu().numpy())
+            for k in range(y.shape[1]):
+                null = null_of(g, k)
+                stats, calls = (x.cpu().numpy() for x in scan_under_null(st, g, null, who, variant_mask=mask))
+                rec = np.zeros(len(at), dtype=dtype)
+                self._variant_columns(rec, t, width, at=at, pos=True)
+                rec["n"] = calls[:, 0]
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    rec["af"] = (calls[:, 1] + 2.0 * calls[:, 2]) / calls[:, 0] / 2.0
+                for c, f in enumerate(floats):                   # (the statistics' columns in the records' order: MIXED_*)
+                    rec[f] = stats[:, c]
+                parts[k].append(rec)
+                if loco or not nulls[k]:
+                    chrom = (t[3][0][1] if t[3] else g).encode() if loco else b"*"
+                    nulls[k].append(np.array([(chrom, null["h2"], null["sigma2"])], dtype=null_dtype))
+        return ([np.concatenate(p) if p else np.zeros(0, dtype=dtype) for p in parts],
+                [np.concatenate(x) if x else np.zeros(0, dtype=null_dtype) for x in nulls])
 
     def _burden_regions(self, who, regions):
         """regions (chrom, start, end, name), 0-based and half-open, any order -> (records, {group: rows}): one record per

@@ -853,3 +853,169 @@ def dense_logistic_score(B, W, q, XWX):
         chi2 = gw[:, 1] * gw[:, 1] / Vg
         stats = stack([chi2, normal_two_sided(chi2 ** 0.5)], -1)
         return nan_unless((Vg > 1e-12 * gWg)[:, None], stats)
+
+
+# ---- the mixed-model scan: y = X alpha + g beta + u + e, Var(u) = sg2 K, variance components fixed at the null model -----------
+# columns of the statistics table of mixed_from_forms (and store_mixed.assoc_mixed), per variant and phenotype
+MIXED_BETA, MIXED_SE, MIXED_Z, MIXED_P = 0, 1, 2, 3
+# the grid of the null model's search for h2: k / MIXED_GRID, k = 0 .. MIXED_GRID - 1, and the golden-section steps after it
+MIXED_GRID, MIXED_STEPS = 100, 60
+
+
+def _reml_profile(lam, Xt, yt, h2):
+    """the REML log-likelihood of h2, profiled over sigma2 and up to a constant, in the eigenbasis of K -> (value, sigma2):
+    lam [n] the eigenvalues, Xt = U^T X, yt = U^T y.  With d = h2 lam + (1 - h2), P = D^-1 - D^-1 Xt (Xt^T D^-1 Xt)^-1 Xt^T D^-1
+    and sigma2 = yt^T P yt / (n - q):  -1/2 ((n - q) log sigma2 + sum log d + log det (Xt^T D^-1 Xt))"""
+    n, q = Xt.shape
+    d = h2 * lam + (1.0 - h2)
+    Xd = Xt / d[:, None]
+    XdX = Xt.T @ Xd
+    b = np.linalg.solve(XdX, Xd.T @ yt)
+    sigma2 = float(yt @ (yt / d) - (Xd.T @ yt) @ b) / (n - q)
+    return -0.5 * ((n - q) * math.log(sigma2) + float(np.log(d).sum()) + float(np.linalg.slogdet(XdX)[1])), sigma2
+
+
+def mixed_null(K, y, covariates=None):
+    """the null model of a mixed-model association scan, y = X alpha + u + e with Var(u) = sg2 K and Var(e) = se2 I, fitted
+    by REML (EMMAX's and GCTA --mlma's approach: the variance components are estimated once, without a variant, and held
+    fixed in the scan) -> dict(h2, sigma2, M, My, q), host float64.  K is the relationship matrix [n, n] (numpy or torch;
+    grm_from_sums), y [n], covariates [n, q0] or None; X = [1 | covariates], q = 1 + q0 columns, checked as assoc_design
+    checks them.  numpy.linalg.eigh(K), its negative eigenvalues set to 0; the profile likelihood (_reml_profile) in
+    h2 = sg2 / (sg2 + se2) is evaluated at k / 100, k = 0..99, and refined by 60 golden-section steps between the best grid
+    point's neighbours (the best point itself where it is the first or the last): a fixed number of evaluations, none
+    beyond 0.99, the same answer on every call.  sigma2 is the profiled REML estimate of sg2 + se2 at that h2, and with
+    V = sigma2 (h2 K + (1 - h2) I)
+        M = V^-1 - V^-1 X (X^T V^-1 X)^-1 X^T V^-1,
+    symmetrised as (M + M^T) / 2: M X = 0, and for a variant x the generalised least-squares estimate of its effect is
+    x^T M y / x^T M x with variance 1 / x^T M x (mixed_from_forms).  My = M y.  ValueError for a K that is not [n, n], holds
+    a value that is not finite (a pair of samples without a jointly complete variant is NaN in grm_from_sums) or is not
+    symmetric to 1e-8 of its largest magnitude, a y that is not [n], and what assoc_design refuses."""
+    K = K.detach().cpu().numpy() if _is_torch(K) else K
+    K = np.asarray(K, dtype=np.float64)
+    yv = _host_f64(y, "y")
+    if yv.ndim != 1:
+        raise ValueError(f"mixed_null: y of shape {yv.shape} ([n]: one phenotype)")
+    n = len(yv)
+    if K.shape != (n, n):
+        raise ValueError(f"mixed_null: a relationship matrix of shape {K.shape} for {n} samples ([n, n])")
+    bad = int((~np.isfinite(K[np.triu_indices(n)])).sum())
+    if bad:
+        raise ValueError(f"mixed_null: {bad} pair(s) of samples have no finite relationship (no jointly complete variant?)")
+    if np.abs(K - K.T).max() > 1e-8 * max(np.abs(K).max(), 1e-300):
+        raise ValueError("mixed_null: the relationship matrix is not symmetric")
+    X = assoc_design(yv, covariates)[0][:, :1]                          # (the checks; X itself is rebuilt: W holds Q, not X)
+    if covariates is not None:
+        X = np.concatenate([X, _host_f64(covariates, "covariates")], axis=1)
+    q = X.shape[1]
+    lam, U = np.linalg.eigh((K + K.T) / 2.0)
+    lam = np.maximum(lam, 0.0)
+    Xt, yt = U.T @ X, U.T @ yv
+    f = lambda h2: _reml_profile(lam, Xt, yt, h2)[0]
+    grid = [f(k / MIXED_GRID) for k in range(MIXED_GRID)]
+    best = int(np.argmax(grid))
+    lo, hi = max(best - 1, 0) / MIXED_GRID, min(best + 1, MIXED_GRID - 1) / MIXED_GRID
+    g = (math.sqrt(5.0) - 1.0) / 2.0
+    a, b = hi - g * (hi - lo), lo + g * (hi - lo)
+    fa, fb = f(a), f(b)
+    for _ in range(MIXED_STEPS):
+        if fa >= fb:
+            hi, b, fb = b, a, fa
+            a = hi - g * (hi - lo)
+            fa = f(a)
+        else:
+            lo, a, fa = a, b, fb
+            b = lo + g * (hi - lo)
+            fb = f(b)
+    h2 = 0.5 * (lo + hi)
+    if grid[best] >= f(h2):                                           # (a flat or ragged likelihood: the grid point stands)
+        h2 = best / MIXED_GRID
+    sigma2 = _reml_profile(lam, Xt, yt, h2)[1]
+    d = sigma2 * (h2 * lam + (1.0 - h2))
+    Vinv = (U / d[None, :]) @ U.T
+    VX = Vinv @ X
+    M = Vinv - VX @ np.linalg.solve(X.T @ VX, VX.T)
+    M = (M + M.T) / 2.0
+    return dict(h2=float(h2), sigma2=float(sigma2), M=M, My=M @ yv, q=q)
+
+
+def mixed_coefficients(T):
+    """the coefficients that make hhgt_quad_forms' x the mean-centred dosage -> float64 [V, 3] in kind: T is float64
+    [V, 3, C] (numpy or torch), assoc_sums of a W whose column 0 is all ones, so that m, h, a = the complete, HET and
+    HOM_ALT calls of column 0 and mu = (h + 2a) / m.  Row v is (1, -mu, 2) — x = HET - mu COMPLETE + 2 HOM_ALT: dosage - mu
+    at a complete call, 0 elsewhere —, and (0, 0, 0) for a variant without a complete call."""
+    _, f64, _, _ = _ops(T)
+    where, stack = _math(T)[3:5]
+    T = f64(T)
+    m, h, a = T[:, ASSOC_COMPLETE, 0], T[:, ASSOC_HET, 0], T[:, ASSOC_ALT, 0]
+    some = m > 0
+    one = f64(some)
+    mu = (h + 2.0 * a) / where(some, m, m * 0.0 + 1.0)
+    return stack([one, -mu * one, 2.0 * one], -1)
+
+
+def mixed_from_forms(T, q, trace_m_over_n):
+    """the statistics of a mixed-model scan from the sums and the quadratic forms of store_mixed.mixed_sums ->
+    (stats, calls): T float64 [V, 3, 2], assoc_sums of W = [1 | My] (planes ASSOC_HET, ASSOC_COMPLETE, ASSOC_ALT; My of
+    mixed_null), q float64 [V] = x^T M x for x of mixed_coefficients (numpy or torch, both of one kind), trace_m_over_n the
+    number trace(M) / n.  calls is int64 [V, 3]: the complete, HET and HOM_ALT calls (column 0 of T: exact).  With m, h, a
+    those counts and mu = (h + 2a) / m — a call that is not complete is imputed to the mean, and M 1 = 0 —,
+        U = T[HET][1] + 2 T[ALT][1] - mu T[COMPLETE][1] = x^T M y
+        beta = U / q      se = q^-1/2      z = U / sqrt(q)      p = normal_two_sided(z)
+    (z^2 is the chi-square on 1 df that GCTA --mlma reports).  stats is float64 [V, 4], columns MIXED_BETA, MIXED_SE, MIXED_Z,
+    MIXED_P; all four are NaN unless m > 0, at least two of the three complete classes (HOM_REF, HET, HOM_ALT) are
+    non-empty and q > 1e-12 (h + 4a - mu^2 m) trace(M) / n — x^T x times the mean eigenvalue of M: below it the covariates
+    explain the dosage.  The formulas are the contract: GCTA's .mlma file is not."""
+    i64, f64, _, nan_unless = _ops(T)
+    stack = _math(T)[4]
+    T, q = f64(T), f64(q)
+    if len(T.shape) != 3 or tuple(T.shape[1:]) != (3, 2) or tuple(q.shape) != (T.shape[0],):
+        raise ValueError(f"mixed_from_forms: T {list(T.shape)} ([V, 3, 2]), q {list(q.shape)} ([V])")
+    m, h, a = T[:, ASSOC_COMPLETE, 0], T[:, ASSOC_HET, 0], T[:, ASSOC_ALT, 0]
+    calls = stack([i64(m), i64(h), i64(a)], -1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = (h + 2.0 * a) / m
+        U = T[:, ASSOC_HET, 1] + 2.0 * T[:, ASSOC_ALT, 1] - mu * T[:, ASSOC_COMPLETE, 1]
+        xx = h + 4.0 * a - mu * mu * m
+        classes = i64(m - h - a > 0) + i64(h > 0) + i64(a > 0)
+        tested = (m > 0) & (classes >= 2) & (q > 1e-12 * xx * float(trace_m_over_n))
+        root = q ** 0.5
+        z = U / root
+        stats = stack([U / q, 1.0 / root, z, normal_two_sided(z)], -1)
+        return nan_unless(tested[:, None], stats), calls
+
+
+def mixed_reference(dosage, complete, M, y):
+    """the quantities of a mixed-model scan in plain dense numpy, the reference of the device route -> dict(x, q, U, stats,
+    calls): dosage is an integer array [n, V] (0, 1, 2: ALT alleles; ignored where the call is not complete), complete bool
+    [n, V], M [n, n] and y [n] as in mixed_null.  x float64 [n, V] is dosage - mu at a complete call (mu the variant's mean
+    over them) and 0 elsewhere, q = x^T M x, U = x^T (M y) per variant, and stats [V, 4], calls [V, 3] are
+    mixed_from_forms' of them."""
+    complete = np.asarray(complete, bool)
+    d = np.where(complete, np.asarray(dosage), 0).astype(np.float64)
+    M, y = np.asarray(M, np.float64), np.asarray(y, np.float64)
+    m, h, a = complete.sum(0).astype(np.float64), (d == 1).sum(0).astype(np.float64), (d == 2).sum(0).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mu = np.where(m > 0, (h + 2.0 * a) / m, 0.0)
+    x = np.where(complete, d - mu[None, :], 0.0)
+    My = M @ y
+    q = ((M @ x) * x).sum(0)
+    T = np.zeros((x.shape[1], 3, 2))
+    T[:, ASSOC_HET, 0], T[:, ASSOC_COMPLETE, 0], T[:, ASSOC_ALT, 0] = h, m, a
+    T[:, ASSOC_HET, 1], T[:, ASSOC_COMPLETE, 1], T[:, ASSOC_ALT, 1] = (d == 1).T @ My, complete.T @ My, (d == 2).T @ My
+    stats, calls = mixed_from_forms(T, q, np.trace(M) / len(y))
+    return dict(x=x, q=q, U=x.T @ My, stats=stats, calls=calls)
+
+
+def loco_sums(sums_by_group, nsnp_by_group, group):
+    """leave one chromosome out: grm_sums is additive over groups, so the relationship matrix without `group` is
+    grm_from_sums of the other groups' sums -> (S, N): sums_by_group and nsnp_by_group map every group to its S [n, n] and
+    N [n, n] (numpy or torch).  ValueError if `group` is not among them or no other group is left."""
+    if group not in sums_by_group or set(sums_by_group) != set(nsnp_by_group):
+        raise ValueError(f"loco_sums: group {group!r} of {sorted(sums_by_group)} (sums) and {sorted(nsnp_by_group)} (counts)")
+    others = [g for g in sums_by_group if g != group]
+    if not others:
+        raise ValueError(f"loco_sums: {group!r} is the only group: leaving it out leaves no variant for the relationship matrix")
+    S, N = sums_by_group[others[0]], nsnp_by_group[others[0]]
+    for g in others[1:]:
+        S, N = S + sums_by_group[g], N + nsnp_by_group[g]
+    return S, N

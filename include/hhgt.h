@@ -516,6 +516,33 @@ int hhgt_ld_clump(hhgt_ctx *ctx, const uint64_t *d_bits, uint64_t n_var, uint32_
 int hhgt_assoc_sums(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_w, uint32_t n_cols,
                     double *d_sums, void *stream);
 
+/* hhgt_quad_forms takes the quadratic form of every row of d_vplanes, uint32 [3][n_var][sw] (hhgt_variant_planes' layout: HET,
+ * COMPLETE, HOM_ALT; bit s % 32 of word s / 32 of a row is plane row s; any three planes of that shape work: the arithmetic
+ * is defined on the bits), in one dense matrix: the x^T M x of every variant of a mixed-model association scan
+ * (store_stats.mixed_from_forms).  d_coef is double [n_var][3], 8-byte aligned; d_a is double [32 * sw][32 * sw], row-major,
+ * 16-byte aligned, finite everywhere and SYMMETRIC — the caller promises that, and puts zeros in the rows and columns that
+ * belong to no listed sample; d_q is double [n_var], 8-byte aligned:
+ *     x_v(s) = d_coef[v][0] * HET_v(s) + d_coef[v][1] * COMPLETE_v(s) + d_coef[v][2] * HOM_ALT_v(s)
+ *     d_q[v] = the sum over s and t of x_v(s) * d_a[s][t] * x_v(t).
+ * With d_coef[v] = (1, -mean, 2) x_v is the mean-centred dosage, 0 where the call is not complete or the row is not listed.
+ * Every entry of d_q is WRITTEN, with plain stores — nothing accumulates, nothing outside [n_var] is touched; with sw == 0
+ * the forms are zeros.  Asynchronous on the stream.
+ * Of d_a the kernel reads the blocks of 128 x 128 on the diagonal in full and, outside them, the upper triangle
+ * (d_a[s][t] with s < t) alone: for the rows s of block b it takes the t below 128 b once, as d_a[t][s], and counts them
+ * twice.  No samples x variants matrix is written anywhere.
+ * Arithmetic: x_v(s) = (c0 h + c1 m) + c2 a in float64, the products exact.  v_mfma_f64_16x16x4_f64 with d_a on one side and
+ * x_v on the other gives y(s) = the sum over t of d_a[s][t] x_v(t), the t of the blocks left of s's in ascending steps of
+ * four, that sum doubled (exact), then the t of s's own block; d_q[v] adds y(s) x_v(s) with one fused multiply-add each: per
+ * lane group g = 0..3 over the rows s = g (mod 4) in ascending order, then ((g0 + g1) + g2) + g3.  The order is fixed: the
+ * same bits on every call, no float atomics.  The result is exact whenever every partial sum is representable; otherwise
+ * its error is bounded, to first order, by (2 n + 2) * 2^-53 * (the sum over s, t of |x(s)| |d_a[s][t]| |x(t)|), n = 32 * sw
+ * — the bound of an inner product in any order, applied twice: no order inside the instruction is claimed.
+ * sw at most HHGT_QUAD_MAX_WORDS, n_var below 128 * (2^31 - 1), else HHGT_ERR_ARG; n_var == 0 is HHGT_OK and touches
+ * nothing.  Timed under HHGT_STAGE_ASSOC. */
+#define HHGT_QUAD_MAX_WORDS 1024
+int hhgt_quad_forms(hhgt_ctx *ctx, const uint32_t *d_vplanes, uint64_t n_var, uint64_t sw, const double *d_coef, const double *d_a,
+                    double *d_q, void *stream);
+
 /* hhgt_score_sums reduces the words [w_lo, w_hi) of every row of genotype planes — d_planes, hhgt_genotype_planes' output,
  * uint32 [3][n_rows][row_words]: HET, HOM_REF, HOM_ALT — against per-variant weights: the sum over variants behind a
  * polygenic score or a projection onto principal components, the transpose of hhgt_assoc_sums.  d_w is double
@@ -784,7 +811,7 @@ int hhgt_inflate_members(hhgt_ctx *ctx, const void *d_src, uint64_t src_bytes, c
 #define HHGT_STAGE_LD_PRUNE 12 /* r^2 decisions of every pair                                    */
 #define HHGT_STAGE_LD_WALK 13 /* the greedy walk over the decisions                              */
 #define HHGT_STAGE_GRM 14     /* sums of products of standardised dosages over genotype planes   */
-#define HHGT_STAGE_ASSOC 15   /* sums of weights under plane bits (hhgt_assoc_sums, hhgt_score_sums) */
+#define HHGT_STAGE_ASSOC 15   /* sums of weights under plane bits (hhgt_assoc_sums, hhgt_score_sums, hhgt_quad_forms) */
 #define HHGT_N_STAGES 16
 int hhgt_profile_enable(hhgt_ctx *ctx, int on);
 int hhgt_profile_reset(hhgt_ctx *ctx);

@@ -1,4 +1,4 @@
-"""What the cohort bench tools (allele_count, sample_count, pair_count, ld, clump, grm, assoc, score, feature, burden and window _bench.py) share: their
+"""What the cohort bench tools (allele_count, sample_count, pair_count, ld, clump, grm, assoc, score, feature, burden, mixed and window _bench.py) share: their
 input, their clock, the medians of their runs and their result line.  A library, not a tool."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,7 +9,7 @@ from haplohyped_varawareml_amd import synth
 from haplohyped_varawareml_amd.reader import write_bgzf_native
 from haplohyped_varawareml_amd.vcf_to_h5 import VCFtoHDF5Converter
 
-RECORDED = ("ld_bench", "grm_bench", "assoc_bench", "score_bench", "feature_bench", "logistic_bench", "clump_bench", "burden_bench")     # the tools whose line is also kept under profiles/
+RECORDED = ("ld_bench", "grm_bench", "assoc_bench", "score_bench", "feature_bench", "logistic_bench", "clump_bench", "burden_bench", "mixed_bench")     # the tools whose line is also kept under profiles/
 
 
 def build_cohort(ctx, tmp, variants, samples=2504, seed=1001):
