@@ -140,6 +140,15 @@ struct LayoutDev {
     uint32_t ring;       // > 0: G is a ring of `ring` chunk columns (v_capacity = ring * Vc), kept indices unbounded
     uint32_t pad_;
 };
+// byte offset of (chunk column slot vcol, sample row s, variant vin of the column) in the int8 matrix — chunk-tiled:
+// G[column][sample chunk][row in chunk][variant][haplotype]; matrix_row: where the row's Vc variants start
+static inline __host__ __device__ uint64_t matrix_at(const LayoutDev &L, uint64_t vcol, uint32_t s, uint64_t vin)
+{
+    const uint32_t scol = L.sc_log2 >= 31u ? 0u : (s >> L.sc_log2);
+    const uint32_t sin = s - scol * L.Sc;
+    return ((((vcol * L.n_sc + scol) * L.Sc + sin) * L.Vc) + vin) * 2ull;
+}
+static inline __host__ __device__ uint64_t matrix_row(const LayoutDev &L, uint64_t vcol, uint32_t s) { return matrix_at(L, vcol, s, 0ull); }
 
 // ---- bit-plane form of the matrix (include/hhgt.h "Bit-plane form"): tile-major ----------------------------------------
 // A chunk column (Vc variants x S_pad padded sample rows) is cut into tiles of PL_TILE variants; a tile holds, per kind-plane

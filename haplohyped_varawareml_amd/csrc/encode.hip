@@ -7,19 +7,102 @@
 // kept lines that emits every sample at once as G[s, v', 2].
 //
 // k_encode_tiles (fixed-width lines "a|b\t" x S — the 1000G shape): a 256-thread workgroup owns a
-//   TV-variant x 256-sample tile (TV = 64: 32 KiB of LDS, four workgroups per CU).  Wave w reads
-//   TV/4 lines; lane l reads 16 contiguous bytes (4 samples) of each line, so every wave-load is a coalesced
-//   1 KiB run of raw GT bytes.  Each lane packs its 4 samples x TV/4 variants in registers, the tile is
+//   TL_V-variant x 256-sample tile (TL_V = 64: 32 KiB of LDS, four workgroups per CU).  Wave w reads
+//   TL_V/4 lines; lane l reads 16 contiguous bytes (4 samples) of each line, so every wave-load is a coalesced
+//   1 KiB run of raw GT bytes.  Each lane packs its 4 samples x TL_V/4 variants in registers, the tile is
 //   transposed through an XOR-swizzled LDS image (conflict-free ds_write_b128 / ds_read_b128) and leaves as
-//   2*TV-byte sample-row segments.
+//   2*TL_V-byte sample-row segments.
 //   HBM roofline: algorithmic bytes per variant = 4*S read + 2*S written; no MFMA (byte work).
 // k_encode_general (anything else: GT:DP columns, multi-digit alleles, haploid calls ...): one wave
 //   per line, tab-rank by ballot/prefix over 1 KiB pieces, htslib GT rule per field.
 #include "common.h"
 
 // -------------------------------------------------------------------------------------------------
-// one "a|b\t" field in a dword (little endian: a, sep, b, terminator) -> h0 | h1 << 8 ; bit 31 = not
-// a fixed-width field this path may decode
+// what the three encode kernels share
+typedef uint32_t u32x4_unaligned __attribute__((ext_vector_type(4), aligned(1)));
+typedef uint32_t u32x4_al __attribute__((ext_vector_type(4)));
+constexpr uint32_t FILL_FIELD = 0x09307C30u;  // "0|0\t"
+// Text near its end, the one careful load behind the kernels' hot ones.  room16: how many of the 16 bytes at `at` lie inside the
+// text; tail4_or: the dword at p of which `room` bytes exist, every byte past them reads `fill`; load16_or: 16 bytes read so.
+__device__ __forceinline__ uint32_t room16(uint64_t n, uint64_t at) { return at >= n ? 0u : (n - at >= 16ull ? 16u : (uint32_t)(n - at)); }
+__device__ __forceinline__ uint32_t tail4_or(const uint8_t *p, uint32_t room, uint32_t fill)
+{
+    uint32_t x = 0;
+#pragma unroll
+    for (uint32_t bb = 0; bb < 4u; ++bb) x |= (bb < room ? (uint32_t)p[bb] : fill) << (bb * 8u);
+    return x;
+}
+
+__device__ __forceinline__ uint4 load16_or(const uint8_t *__restrict__ text, uint64_t n, uint64_t at, uint32_t fill)
+{
+    const uint32_t room = room16(n, at);
+    if (room == 16u) {
+        const u32x4_unaligned t = *reinterpret_cast<const u32x4_unaligned *>(text + at);
+        return make_uint4(t.x, t.y, t.z, t.w);
+    }
+    uint32_t w[4];
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) w[q] = tail4_or(text + at + 4u * q, room > 4u * q ? room - 4u * q : 0u, fill);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// Where a tile (or, for the variable-width kernel, one line) stands: gv0 = its first global column, k0 = the batch-local
+// kept index of that column (negative: the tile straddles the append position), (vcol, vin) = the chunk column slot — ring
+// wrap applied — and the variant inside it; live = there is a kept line at or behind k0 and the column is inside the matrix.
+struct TilePlace {
+    uint64_t gv0, vcol, vin;
+    long long k0;
+    bool live;
+};
+// global column v -> its chunk column slot (ring wrap applied) and the variant inside it
+__device__ __forceinline__ void column_of(const LayoutDev &lay, uint64_t v, uint64_t *vcol, uint64_t *vin)
+{
+    *vcol = v / lay.Vc;
+    *vin = v - *vcol * lay.Vc;
+    if (lay.ring) *vcol %= lay.ring;
+}
+// the tile of `width` columns that is `tile` tiles behind the one that holds the append position v_base
+__device__ __forceinline__ TilePlace tile_place(const LayoutDev &lay, uint64_t v_base, uint32_t n_kept, uint32_t width, uint64_t tile)
+{
+    TilePlace t;
+    t.gv0 = (v_base / width + tile) * (uint64_t)width;
+    t.k0 = (long long)t.gv0 - (long long)v_base;
+    t.live = t.k0 < (long long)n_kept && (lay.ring || t.gv0 < lay.v_capacity);
+    column_of(lay, t.gv0, &t.vcol, &t.vin);
+    return t;
+}
+
+// a line of the fixed-width kernels that holds a field they cannot decode goes to the variable-width kernel, once
+__device__ __forceinline__ void send_to_general(uint32_t k, uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag, DevCounters *cnt)
+{
+    if (atomicExch(&redo_flag[k], 1u) == 0u) {
+        unsigned long long slot = atomicAdd(&cnt->n_general, 1ull);
+        redo_list[slot] = k;
+    }
+}
+
+// One field "a|b" + terminator in a dword (little endian: a, sep, b, terminator) over the alphabet {0, 1, .} x {|, /} —
+// branch-free SWAR on x ^ "0|0\t": an allele byte must be 0x00, 0x01 or 0x1E ('.'), bit 4 of it is the EXC bit and
+// bit 0 | bit 4 the ONE bit; the separator byte 0x00 or 0x53 ('/').  one / exc: bit 0 = haplotype 0, bit 16 = haplotype 1;
+// off != 0: a field outside the alphabet.  The terminator rule is the caller's: EXACT_TAB folds "it is a tab" into `off` (the
+// tile kernel); without it the byte is not looked at (the variable-width kernel accepts a tab, a newline or ':').
+struct FieldBits { uint32_t one, exc, off; };
+template <bool EXACT_TAB>
+__device__ __forceinline__ FieldBits classify_field(uint32_t x)
+{
+    FieldBits f;
+    const uint32_t y = x ^ FILL_FIELD;
+    const uint32_t t4 = y >> 4;
+    f.exc = t4 & 0x00010001u;                                              // '.' in either allele
+    f.one = (y | t4) & 0x00010001u;                                        // '1' or '.'
+    const uint32_t want = __umul24(f.exc, 30u) | (y & 0x00010001u & ~f.exc);   // what the allele bytes must then be
+    const uint32_t z = y & (EXACT_TAB ? 0xFF00FF00u : 0x0000FF00u), zz = z ^ 0x00005300u;   // separator (/ terminator) bytes
+    f.off = ((y & 0x00FF00FFu) ^ want) | (z < zz ? z : zz);
+    return f;
+}
+
+// -------------------------------------------------------------------------------------------------
+// one "a|b\t" field in a dword -> h0 | h1 << 8 ; bit 31 = not a fixed-width field this path may decode
 __device__ __forceinline__ uint32_t parse_field_exact(uint32_t x)
 {
     uint32_t a = x & 0xFFu, sep = (x >> 8) & 0xFFu, b = (x >> 16) & 0xFFu, t = x >> 24;
@@ -37,143 +120,103 @@ __device__ __forceinline__ uint32_t parse_field(uint32_t x)
     return parse_field_exact(x);
 }
 
-typedef uint32_t u32x4_unaligned __attribute__((ext_vector_type(4), aligned(1)));
-typedef uint32_t u32x4_al __attribute__((ext_vector_type(4)));
-
-#define FILL_FIELD 0x09307C30u  // "0|0\t"
-#ifndef TILE_G
-#define TILE_G 16  // lines whose 16-byte loads are in flight together per wave (1 KiB each)
-#endif
-
-// TV = variants per tile.  LDS = 256 rows x 2*TV bytes = 32 KiB: four workgroups share a CU, so the load, transpose and
-// store phases of different tiles overlap (TV = 128, 64 KiB and two workgroups per CU, was the other width built).
-__global__ __launch_bounds__(256, 4) void k_encode_tiles(
-    const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ k_soff,
-    const uint32_t *__restrict__ k_meta, const uint64_t *__restrict__ d_cursor, LayoutDev lay, int8_t *__restrict__ G,
-    uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag, DevCounters *cnt)
+// TL_V = variants per tile.  LDS = 256 rows x 2*TL_V bytes = 32 KiB: four workgroups share a CU, so the load, transpose and
+// store phases of different tiles overlap (TL_V = 128, 64 KiB and two workgroups per CU, was the other width built).
+constexpr int TL_V = 64;
+constexpr int TL_LW = TL_V / 4;        // lines per wave: their 16-byte loads are all in flight together (1 KiB each)
+constexpr int TL_SLOTS = TL_V / 8;     // 16-byte slots per LDS row
+constexpr int TL_WSL = TL_SLOTS / 4;   // slots per row owned by one wave
+// The lane's 4 fields of each of the wave's lines kw .. kw + TL_LW - 1 as they were read; returns which of them are kept
+// fixed-width lines (bit j, wave-uniform).  Any other line, and every field past the last sample, reads "0|0\t".
+__device__ __forceinline__ uint32_t load_lines(uint4 (&raw)[TL_LW], const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ k_soff,
+                                           const uint32_t *__restrict__ k_meta, long long kw, uint32_t n_kept, uint32_t ls, uint32_t nval)
 {
-    constexpr int TV = 64;
-    const uint64_t v_base = *d_cursor;   // append position: device-resident, so a chain of calls needs no host round trip
-    constexpr int LW = TV / 4;        // lines per wave
-    constexpr int SLOTS = TV / 8;     // 16-byte slots per LDS row
-    constexpr int WSL = SLOTS / 4;    // slots per row owned by one wave
-    constexpr int G_ = LW < TILE_G ? LW : TILE_G;
-    __shared__ uint4 tile[TILE_S * SLOTS];  // 256 rows x 2*TV B, 16-byte slots XOR-swizzled by (row >> 2) & 7
-    const uint32_t n_kept = (uint32_t)cnt->n_kept;
-    const uint64_t gv0 = (v_base / TV + blockIdx.x) * (uint64_t)TV;  // first global column of tile
-    const long long k0 = (long long)gv0 - (long long)v_base;         // batch-local kept index of it
-    if (k0 >= (long long)n_kept || (!lay.ring && gv0 >= lay.v_capacity)) return;
-    const uint32_t s0 = blockIdx.y * TILE_S;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t S = lay.S;
-    const uint32_t ls = s0 + 4u * lane;                                 // first sample of this lane
-    const uint32_t nval = ls >= S ? 0u : (S - ls >= 4u ? 4u : S - ls);  // samples this lane owns
-    const uint32_t last_q = (S - 1u >= ls && S - 1u < ls + 4u) ? S - 1u - ls : 4u;  // which dword is sample S-1
-
-    uint32_t acc[4][LW / 2];
+    uint32_t lvalid = 0u;
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int c = 0; c < LW / 2; ++c) acc[q][c] = 0;
-
-#pragma unroll
-    for (int g = 0; g < LW / G_; ++g) {
-        uint4 raw[G_];
-        bool lvalid[G_];
-#pragma unroll
-        for (int j = 0; j < G_; ++j) {
-            const long long k = k0 + (long long)(w * LW + g * G_ + j);
-            bool valid = k >= 0 && k < (long long)n_kept;
-            uint32_t meta = 0, soff = 0;
-            if (valid) {
-                meta = k_meta[k];
-                soff = k_soff[k];
-            }
-            valid = valid && (meta & LF_FAST);
-            lvalid[j] = valid;
-            uint4 v = make_uint4(FILL_FIELD, FILL_FIELD, FILL_FIELD, FILL_FIELD);
-            if (valid && nval) {
-                const uint64_t off = (uint64_t)soff + 4ull * ls;
-                if (nval == 4u && off + 16ull <= n) {
-                    u32x4_unaligned t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(text + off));
-                    v = make_uint4(t.x, t.y, t.z, t.w);
-                } else {
-                    uint32_t d[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        uint32_t x = FILL_FIELD;
-                        if ((uint32_t)q < nval) {
-#pragma unroll
-                            for (int bb = 0; bb < 4; ++bb) {
-                                uint64_t idx = off + (uint64_t)(q * 4 + bb);
-                                uint32_t c = idx < n ? text[idx] : (uint32_t)'\t';
-                                x = (x & ~(0xFFu << (bb * 8))) | (c << (bb * 8));
-                            }
-                        }
-                        d[q] = x;
-                    }
-                    v = make_uint4(d[0], d[1], d[2], d[3]);
-                }
-            }
-            raw[j] = v;
+    for (int j = 0; j < TL_LW; ++j) {
+        const long long k = kw + j;
+        bool valid = k >= 0 && k < (long long)n_kept;
+        uint32_t meta = 0, soff = 0;
+        if (valid) {
+            meta = k_meta[k];
+            soff = k_soff[k];
         }
+        valid = valid && (meta & LF_FAST);
+        lvalid |= valid ? 1u << j : 0u;
+        uint4 v = make_uint4(FILL_FIELD, FILL_FIELD, FILL_FIELD, FILL_FIELD);
+        if (valid && nval) {
+            const uint64_t off = (uint64_t)soff + 4ull * ls;
+            if (nval == 4u && off + 16ull <= n) {
+                u32x4_unaligned t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_unaligned *>(text + off));
+                v = make_uint4(t.x, t.y, t.z, t.w);
+            } else {
+                // (field by field, each behind its own branch: the 16 bytes in one go cost the kernel 4 VGPRs and 6 SGPRs.  No
+                // field of an LF_FAST line starts past the end of the text: parse_record, index.hip, sets the flag only where
+                // the 4 S - 1 bytes of sample columns end inside it; reading such a field as tabs cost 2 SGPRs over the budget)
+                const uint32_t room = room16(n, off);
+                uint32_t d[4];
 #pragma unroll
-        for (int j = 0; j < G_; ++j) {
-            uint32_t x[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
-            uint32_t bad = 0;
+                for (uint32_t q = 0; q < 4u; ++q)
+                    d[q] = q < nval && 4u * q < room ? tail4_or(text + off + 4u * q, room - 4u * q, (uint32_t)'\t') : FILL_FIELD;
+                v = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+        }
+        raw[j] = v;
+    }
+    return lvalid;
+}
+
+// every field to its two int8 calls: acc[q][c] holds sample q's calls of lines 2 c (low half) and 2 c + 1
+__device__ __forceinline__ void pack_lines(const uint4 (&raw)[TL_LW], uint32_t lvalid, uint32_t (&acc)[4][TL_LW / 2], uint32_t last_q, long long kw, uint32_t lane,
+                                           uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag, DevCounters *cnt)
+{
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t xx = x[q];
-                // the last sample of a line is terminated by the line end, not by a tab (the region
-                // length check LF_FAST already pinned where it ends)
-                if ((uint32_t)q == last_q) xx = (xx & 0x00FFFFFFu) | 0x09000000u;
-                uint32_t r = parse_field(xx);
-                bad |= r;
-                const int col = g * G_ + j;
-                acc[q][col >> 1] |= (r & 0xFFFFu) << ((col & 1) * 16);
-            }
-            if (lvalid[j]) {
-                unsigned long long bm = __ballot((bad & 0x80000000u) != 0u);
-                if (bm != 0ull && lane == 0) {
-                    const uint32_t k = (uint32_t)(k0 + (long long)(w * LW + g * G_ + j));
-                    if (atomicExch(&redo_flag[k], 1u) == 0u) {
-                        unsigned long long slot = atomicAdd(&cnt->n_general, 1ull);
-                        redo_list[slot] = k;
-                    }
-                }
-            }
+    for (int j = 0; j < TL_LW; ++j) {
+        uint32_t x[4] = {raw[j].x, raw[j].y, raw[j].z, raw[j].w};
+        uint32_t bad = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            uint32_t xx = x[q];
+            // the last sample of a line is terminated by the line end, not by a tab (LF_FAST already pinned where it ends)
+            if ((uint32_t)q == last_q) xx = (xx & 0x00FFFFFFu) | 0x09000000u;
+            uint32_t r = parse_field(xx);
+            bad |= r;
+            acc[q][j >> 1] |= (r & 0xFFFFu) << ((j & 1) * 16);
+        }
+        if ((lvalid >> j) & 1u) {
+            unsigned long long bm = __ballot((bad & 0x80000000u) != 0u);
+            if (bm != 0ull && lane == 0) send_to_general((uint32_t)(kw + j), redo_list, redo_flag, cnt);
         }
     }
-    // registers -> LDS (sample-major rows).  Wave w owns byte columns [w * TV/2, (w+1) * TV/2) of every row.
+}
+
+// registers -> LDS (sample-major rows; wave w owns byte columns [w * TL_V/2, (w+1) * TL_V/2) of every row), one barrier,
+// LDS -> HBM: each row leaves as one contiguous 2*TL_V-byte run (TL_SLOTS lanes x 16 B)
+__device__ __forceinline__ void transpose_out(uint4 *tile, const uint32_t (&acc)[4][TL_LW / 2], const TilePlace &at, const LayoutDev &lay,
+                                              int8_t *__restrict__ G, uint32_t s0, uint32_t w, uint32_t lane)
+{
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const uint32_t row = 4u * lane + q;
         const uint32_t swz = (row >> 2) & 7u;
 #pragma unroll
-        for (int c = 0; c < WSL; ++c) {
-            const uint32_t slot = (w * WSL + c) ^ (swz & (SLOTS - 1));
-            tile[row * SLOTS + slot] = make_uint4(acc[q][c * 4 + 0], acc[q][c * 4 + 1], acc[q][c * 4 + 2], acc[q][c * 4 + 3]);
+        for (int c = 0; c < TL_WSL; ++c) {
+            const uint32_t slot = (w * TL_WSL + c) ^ (swz & (TL_SLOTS - 1));
+            tile[row * TL_SLOTS + slot] = make_uint4(acc[q][c * 4 + 0], acc[q][c * 4 + 1], acc[q][c * 4 + 2], acc[q][c * 4 + 3]);
         }
     }
     __syncthreads();
-    // LDS -> HBM: each row leaves as one contiguous 2*TV-byte run (SLOTS lanes x 16 B)
-    const uint32_t c16 = threadIdx.x & (SLOTS - 1);
-    uint64_t vcol = gv0 / lay.Vc;
-    const uint64_t vin = gv0 - vcol * lay.Vc;
-    if (lay.ring) vcol %= lay.ring;
-    const long long kfirst = k0 + (long long)c16 * 8;  // batch-local kept index of this lane's 8 columns
-    constexpr int ROWS_PER_IT = 256 / SLOTS;
+    const uint32_t c16 = threadIdx.x & (TL_SLOTS - 1);
+    const long long kfirst = at.k0 + (long long)c16 * 8;  // batch-local kept index of this lane's 8 columns
+    constexpr int ROWS_PER_IT = 256 / TL_SLOTS;
 #pragma unroll 4
     for (int it = 0; it < TILE_S / ROWS_PER_IT; ++it) {
-        const uint32_t row = it * ROWS_PER_IT + (threadIdx.x / SLOTS);
+        const uint32_t row = it * ROWS_PER_IT + (threadIdx.x / TL_SLOTS);
         const uint32_t s = s0 + row;
-        if (s >= S) continue;
+        if (s >= lay.S) continue;
         const uint32_t swz = (row >> 2) & 7u;
-        uint4 v = tile[row * SLOTS + (c16 ^ (swz & (SLOTS - 1)))];
-        const uint32_t scol = lay.sc_log2 >= 31u ? 0u : (s >> lay.sc_log2);
-        const uint32_t sin = s - scol * lay.Sc;
-        int8_t *dst = G + ((((vcol * lay.n_sc + scol) * lay.Sc + sin) * lay.Vc + vin) * 2ull) + c16 * 16u;
+        uint4 v = tile[row * TL_SLOTS + (c16 ^ (swz & (TL_SLOTS - 1)))];
+        int8_t *dst = G + matrix_at(lay, at.vcol, s, at.vin) + c16 * 16u;
         if (kfirst >= 0) {
             __builtin_nontemporal_store(u32x4_al{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4_al *>(dst));
         } else if (kfirst + 8 > 0) {  // tile straddles v_base: keep the columns the previous batch wrote
@@ -184,6 +227,31 @@ __global__ __launch_bounds__(256, 4) void k_encode_tiles(
                     reinterpret_cast<uint16_t *>(dst)[e] = (uint16_t)(d[e >> 1] >> ((e & 1) * 16));
         }
     }
+}
+
+__global__ __launch_bounds__(256, 4) void k_encode_tiles(
+    const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ k_soff,
+    const uint32_t *__restrict__ k_meta, const uint64_t *__restrict__ d_cursor, LayoutDev lay, int8_t *__restrict__ G,
+    uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag, DevCounters *cnt)
+{
+    __shared__ uint4 tile[TILE_S * TL_SLOTS];  // 256 rows x 2*TL_V B, 16-byte slots XOR-swizzled by (row >> 2) & 7
+    // (*d_cursor) append position: device-resident, so a chain of calls needs no host round trip
+    const uint32_t n_kept = (uint32_t)cnt->n_kept;
+    const TilePlace at = tile_place(lay, *d_cursor, n_kept, TL_V, blockIdx.x);
+    if (!at.live) return;
+    const uint32_t s0 = blockIdx.y * TILE_S;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t S = lay.S;
+    const uint32_t ls = s0 + 4u * lane;                                 // first sample of this lane
+    const uint32_t nval = ls >= S ? 0u : (S - ls >= 4u ? 4u : S - ls);  // samples this lane owns
+    const uint32_t last_q = (S - 1u >= ls && S - 1u < ls + 4u) ? S - 1u - ls : 4u;  // which dword is sample S-1
+    const long long kw = at.k0 + (long long)(w * TL_LW);                // the wave's first line
+    uint4 raw[TL_LW];
+    uint32_t acc[4][TL_LW / 2] = {};
+    const uint32_t lvalid = load_lines(raw, text, n, k_soff, k_meta, kw, n_kept, ls, nval);
+    pack_lines(raw, lvalid, acc, last_q, kw, lane, redo_list, redo_flag, cnt);
+    transpose_out(tile, acc, at, lay, G, s0, w, lane);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -206,36 +274,35 @@ __global__ __launch_bounds__(256, 4) void k_encode_tiles(
 // 1008 bytes, so with any start phase they fit one 16-byte-aligned 1 KiB window, one load instruction per line and wave
 // with every lane aligned.  Lanes that load at the (arbitrary) byte where the sample columns start run ~20 % slower
 // (tools/micro/strided_read.hip: 6.4 -> 5.1 TB/s), and a 256-sample band needs a 65th aligned chunk per line.
-#define PT_S 252           // samples per band: 63 owner lanes x 4 (TILE_S stays k_encode_tiles')
-#define PT_V 256           // = PL_TILE
-#define PT_ROWDW (PT_V / 32)                    // dwords per image row
-#ifndef PT_NW
-#define PT_NW 4            // waves per workgroup
-#endif
-#define PT_LW (PT_V / PT_NW)   // lines per wave
-#ifndef PT_G
-#define PT_G 8             // lines per load group
-#endif
-#ifndef PT_DB
-#define PT_DB 1            // the next group's loads are issued before a group is packed
-#endif
-#ifndef PT_WGS
-#define PT_WGS 4           // waves per SIMD the register allocation leaves room for (= workgroups per CU)
-#endif
-#define PT_C 0x09307C30u   // "0|0\t"
-
+constexpr int PT_S = 252;             // samples per band: 63 owner lanes x 4 (TILE_S stays k_encode_tiles')
+constexpr int PT_V = 256;             // = PL_TILE
+constexpr int PT_ROWDW = PT_V / 32;   // dwords per image row
+constexpr int PT_NW = 4;              // waves per workgroup
+constexpr int PT_LW = PT_V / PT_NW;   // lines per wave
+constexpr int PT_G = 8;               // lines per load group; the next group's loads are issued before a group is packed
+constexpr int PT_NG = 32 / PT_G;      // load groups per step of 32 lines
+constexpr int PT_WGS = 4;             // waves per SIMD the register allocation leaves room for (= workgroups per CU)
 struct PlGroup {
     uint4 raw[PT_G];
     uint32_t lvalid;   // bit j: line j of the group is a kept fixed-width line (wave-uniform)
     uint32_t lstride;  // bit j: line j is a kept record whose columns are all of one width of 5 .. 8 bytes, GT first (k_meta bits 20-23)
 };
-
 // the line table of 32 lines at once: lane j holds soff / meta of line kb + j (meta = 0 beyond the batch), so that a
 // load group needs no scalar loads (the first version paid two dependent s_load round trips in front of every line)
-struct PlStep {
-    uint32_t soff, meta;
+struct PlStep { uint32_t soff, meta; };
+// What a wave keeps for its tile, and `stp` for a step of 32 lines (index.hip's HopState is the model): s0 = the band's first
+// sample, ls / nval = the lane's first sample and how many it owns (lane 63 none), rel = (S - 1) - ls for pl_edge_fields
+struct PlWave {
+    const uint8_t *__restrict__ text;
+    uint64_t n;
+    PlStep stp;
+    uint32_t s0, ls, nval, lane, S;
+    int rel;
+    uint32_t *__restrict__ redo_list, *__restrict__ redo_flag;
+    DevCounters *cnt;
+    __device__ __forceinline__ uint32_t soff(int j) const { return (uint32_t)__builtin_amdgcn_readlane((int)stp.soff, j); }
+    __device__ __forceinline__ uint32_t meta(int j) const { return (uint32_t)__builtin_amdgcn_readlane((int)stp.meta, j); }
 };
-
 __device__ __forceinline__ PlStep pl_load_step(const uint32_t *__restrict__ k_soff, const uint32_t *__restrict__ k_meta, long long kb,
                                                uint32_t n_kept, uint32_t lane)
 {
@@ -253,29 +320,18 @@ __device__ __forceinline__ PlStep pl_load_step(const uint32_t *__restrict__ k_so
 // reach up to 12 bytes past the line's end (the band behind it has fewer than 4 samples) or into the bytes in front of F
 // (band 0): none of those bytes is a field this lane owns, and the window has to stay inside the text only.  EDGE (k_encode_planes: the
 // last band, and any band of a tile whose last line's window could end past the text) reads a window that would end past
-// the text's end byte by byte, and what lies past the end reads as a tab; every other tile reads flat.
+// the text's end with care, and what lies past the end reads as a tab; every other tile reads flat.
 template <bool EDGE>
-__device__ __forceinline__ uint4 pl_load_window(const uint8_t *__restrict__ text, uint64_t n, uint32_t soff, uint32_t s0, uint32_t lane)
+__device__ __forceinline__ uint4 pl_load_window(const PlWave &w, uint32_t soff)
 {
-    const uint64_t F = (uint64_t)soff + 4ull * s0;
+    const uint64_t F = (uint64_t)soff + 4ull * w.s0;
     const uint64_t A = F & ~15ull;
-    const uint64_t off = A + 16ull * lane;
-    if (!EDGE || A + 1024ull <= n) {   // (wave-uniform)
-        const u32x4_al t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_al *>(text + off));
+    const uint64_t off = A + 16ull * w.lane;
+    if (!EDGE || A + 1024ull <= w.n) {   // (wave-uniform)
+        const u32x4_al t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_al *>(w.text + off));
         return make_uint4(t.x, t.y, t.z, t.w);
     }
-    uint32_t d[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint32_t x = 0;
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-            const uint64_t idx = off + (uint64_t)(q * 4 + bb);
-            x |= (idx < n ? (uint32_t)text[idx] : (uint32_t)'\t') << (bb * 8);
-        }
-        d[q] = x;
-    }
-    return make_uint4(d[0], d[1], d[2], d[3]);
+    return load16_or(w.text, w.n, off, (uint32_t)'\t');
 }
 
 // The lane's four fields from its window chunk c and lane + 1's: bytes [d, d + 16) of the 32 (d = the line's phase,
@@ -319,242 +375,157 @@ __device__ __forceinline__ uint4 pl_edge_fields(uint4 v, int rel)
     return v;
 }
 
-struct __attribute__((packed)) PlU32 {
-    uint32_t v;
-};
-
-// the raw window chunks of PT_G lines (the funnel waits for pl_pack_group: the chunks in flight stay 4 registers per line)
+struct __attribute__((packed)) PlU32 { uint32_t v; };
+// the raw window chunks of the PT_G lines of group g of the step (the funnel waits for pl_pack_group: the chunks in flight
+// stay 4 registers per line)
 template <bool EDGE>
-__device__ __forceinline__ void pl_load_group(PlGroup &gr, const uint8_t *__restrict__ text, uint64_t n, const PlStep &stp,
-                                              const int j0, uint32_t s0, uint32_t lane)
+__device__ __forceinline__ void pl_load_group(const PlWave &w, PlGroup &gr, const int g)
 {
     uint32_t lv = 0, lst = 0;
 #pragma unroll
     for (int j = 0; j < PT_G; ++j) {
-        const uint32_t meta = (uint32_t)__builtin_amdgcn_readlane((int)stp.meta, j0 + j);
-        const uint32_t soff = (uint32_t)__builtin_amdgcn_readlane((int)stp.soff, j0 + j);
+        const uint32_t meta = w.meta(g * PT_G + j);
+        const uint32_t soff = w.soff(g * PT_G + j);
         uint4 v = make_uint4(FILL_FIELD, FILL_FIELD, FILL_FIELD, FILL_FIELD);
         if (meta & LF_FAST) {   // (wave-uniform)
             lv |= 1u << j;
-            v = pl_load_window<EDGE>(text, n, soff, s0, lane);
+            v = pl_load_window<EDGE>(w, soff);
         } else if ((meta >> 20) & 15u)
-            lst |= 1u << j;   // decoded by the second level below, at its stride
+            lst |= 1u << j;   // decoded by the second level (pack_careful), at its stride
         gr.raw[j] = v;
     }
     gr.lvalid = lv;
     gr.lstride = lst;
 }
 
-// PT_G lines -> per sample q: one[q] / exc[q], bit sh + j (haplotype 0) and bit 16 + sh + j (haplotype 1) for line j.
-// Three levels.  (1) every field of every lane is "[01]|[01]\t": ~14 vector instructions per line, unrolled.  (2) some
-// lane saw something else: the group again, line by line in a rolled loop that reads the (cache-hot) line once more and
-// classifies every field over the alphabet {0, 1, .} x {|, /} — branch-free SWAR on the field dword, x ^ "0|0\t": an
-// allele byte must be 0x00, 0x01 or 0x1E ('.'), bit 4 of it is the EXC bit and bit 0 | bit 4 the ONE bit; the separator
-// byte 0x00 or 0x53 ('/'), the terminator 0x00.  (3) a field outside that alphabet (a third allele, a multi-digit index,
-// anything malformed) contributes zero bits and sends its line to the variable-width kernel, which sets the bits of the
-// whole line (idempotent for the fields that were fine here).  Keeping (2) rolled and out of the registers of (1) is
-// what lets four workgroups share a CU.
+// Level (1) of pl_pack_group: true, and the group's ONE bits in one[q], when every field of every lane is "[01]|[01]\t"
+// (~14 vector instructions per line, unrolled); false, and nothing added, when some lane saw something else.
 template <bool EDGE>
-__device__ __forceinline__ void pl_pack_group(const PlGroup &gr, const int sh, uint32_t (&one)[4], uint32_t (&exc)[4], long long kbase,
-                                              const uint8_t *__restrict__ text, uint64_t n, const PlStep &stp, const int j0,
-                                              uint32_t s0, uint32_t ls, uint32_t nval, uint32_t *__restrict__ redo_list,
-                                              uint32_t *__restrict__ redo_flag, DevCounters *cnt, uint32_t lane, uint32_t S_all)
+__device__ __forceinline__ bool pack_fast(const PlWave &w, const PlGroup &gr, const int j0, const int sh, uint32_t (&one)[4])
 {
-    const int rel = lane == 63u ? -1 : (int)(S_all - 1u) - (int)ls;   // (EDGE: pl_edge_fields)
     uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, bad = 0;
 #pragma unroll
     for (int j = 0; j < PT_G; ++j) {
         // the line's phase (a line that was not loaded holds "0|0\t" in every dword: phase 0 keeps it so)
-        const uint32_t soff = (uint32_t)__builtin_amdgcn_readlane((int)stp.soff, j0 + j);
+        const uint32_t soff = w.soff(j0 + j);   // (read outside the select: a lane read is not speculated, it would become a branch per line)
         const uint32_t d = ((gr.lvalid >> j) & 1u) ? soff & 15u : 0u;
-        const uint4 x = pl_edge_fields<EDGE>(pl_funnel(gr.raw[j], d), rel);
+        const uint4 x = pl_edge_fields<EDGE>(pl_funnel(gr.raw[j], d), w.rel);
         a0 |= (x.x & 0x00010001u) << (sh + j);
         a1 |= (x.y & 0x00010001u) << (sh + j);
         a2 |= (x.z & 0x00010001u) << (sh + j);
         a3 |= (x.w & 0x00010001u) << (sh + j);
-        bad |= ((x.x ^ PT_C) | (x.y ^ PT_C)) | ((x.z ^ PT_C) | (x.w ^ PT_C));
+        bad |= ((x.x ^ FILL_FIELD) | (x.y ^ FILL_FIELD)) | ((x.z ^ FILL_FIELD) | (x.w ^ FILL_FIELD));
     }
     bad |= gr.lstride ? 2u : 0u;   // a record decoded at its stride is the second level's (as data, not as a branch: the branch cost 86 spilled registers)
     // (lane 63 owns nothing: what it holds is the next band's, or past the line)
-    if ((__builtin_amdgcn_ballot_w64((bad & 0xFFFEFFFEu) != 0u) & 0x7FFFFFFFFFFFFFFFull) == 0ull) {
-        one[0] |= a0, one[1] |= a1, one[2] |= a2, one[3] |= a3;
-        return;
-    }
+    if ((__builtin_amdgcn_ballot_w64((bad & 0xFFFEFFFEu) != 0u) & 0x7FFFFFFFFFFFFFFFull) != 0ull) return false;
+    one[0] |= a0, one[1] |= a1, one[2] |= a2, one[3] |= a3;
+    return true;
+}
+
+// Sample s's column of a record whose columns are all `wd` (5 .. 8) bytes wide with the GT sub-field first — "a|b:dd\t" — as
+// the field dword "a|b\t", or all ones (a field no alphabet accepts) for a column of any other shape.  The column is checked
+// where it stands: byte 3 is the ':' that ends the GT, bytes 4 .. wd - 2 hold neither a tab nor a newline (the bytes above
+// read 0), byte wd - 1 is the tab (the newline behind the last sample).  lbase: wave-uniform, 32-bit lane offsets behind it
+__device__ __forceinline__ uint32_t strided_field(const uint8_t *lbase, uint32_t room, uint32_t wd, uint32_t s, bool last_sample)
+{
+    const uint32_t shb = 8u * (wd - 5u);   // where the column's last byte sits in its second dword
+    const uint32_t lowm = shb ? (1u << shb) - 1u : 0u;
+    const uint32_t vo = wd * s;
+    if (vo + 8u > room) return 0xFFFFFFFFu;
+    const uint32_t d1 = reinterpret_cast<const PlU32 *>(lbase + vo + 4u)->v;
+    const uint32_t low = d1 & lowm;
+    const uint32_t t9 = low ^ 0x09090909u, tA = low ^ 0x0A0A0A0Au;
+    uint32_t bad = (((t9 - 0x01010101u) & ~t9) | ((tA - 0x01010101u) & ~tA)) & 0x80808080u;
+    bad |= ((d1 >> shb) & 0xFFu) ^ (last_sample ? 0x0Au : 0x09u);
+    const uint32_t d0 = reinterpret_cast<const PlU32 *>(lbase + vo)->v;
+    bad |= (d0 >> 24) ^ (uint32_t)':';
+    return bad ? 0xFFFFFFFFu : ((d0 & 0x00FFFFFFu) | 0x09000000u);
+}
+
+// Levels (2) and (3) of pl_pack_group: the group again, line by line in a ROLLED loop that reads the (cache-hot) line once
+// more and classifies every field (classify_field, exact tab).  k = the batch-local kept index of the group's first line.
+template <bool EDGE>
+__device__ __forceinline__ void pack_careful(const PlWave &w, const int j0, const int sh, uint32_t (&one)[4], uint32_t (&exc)[4], long long k)
+{
 #pragma unroll 1
     for (int j = 0; j < PT_G; ++j) {
-        const uint32_t meta = (uint32_t)__builtin_amdgcn_readlane((int)stp.meta, j0 + j);
+        const uint32_t meta = w.meta(j0 + j);
         const uint32_t wd = (meta >> 20) & 15u;
         if (!(meta & LF_FAST) && wd == 0u) continue;
-        const uint32_t soff = (uint32_t)__builtin_amdgcn_readlane((int)stp.soff, j0 + j);
+        const uint32_t soff = w.soff(j0 + j);
         uint32_t hard = 0;
-        // one field "a|b\t" over the alphabet {0, 1, .} x {|, /}: bits into one[q] / exc[q], anything else -> hard
-#define PL_CLASSIFY(XQ, Q)                                                                                            \
-    do {                                                                                                               \
-        const uint32_t y = (XQ) ^ PT_C;                                                                                \
-        const uint32_t t4 = y >> 4;                                                                                    \
-        const uint32_t e2 = t4 & 0x00010001u;                              /* '.' in either allele */                  \
-        const uint32_t o2 = (y | t4) & 0x00010001u;                        /* '1' or '.' */                            \
-        const uint32_t want = __umul24(e2, 30u) | (y & 0x00010001u & ~e2); /* what the allele bytes must then be */    \
-        const uint32_t z = y & 0xFF00FF00u, zz = z ^ 0x00005300u;          /* separator / terminator bytes */          \
-        const uint32_t off = ((y & 0x00FF00FFu) ^ want) | (z < zz ? z : zz);                                           \
-        const uint32_t keep = off ? 0u : 0xFFFFFFFFu;                                                                  \
-        one[Q] |= (o2 & keep) << (sh + j);                                                                             \
-        exc[Q] |= (e2 & keep) << (sh + j);                                                                             \
-        hard |= off;                                                                                                   \
-    } while (0)
+        auto add_field = [&](uint32_t x, int q) {   // bits into one[q] / exc[q], anything outside the alphabet -> hard
+            const FieldBits f = classify_field<true>(x);
+            const uint32_t keep = f.off ? 0u : 0xFFFFFFFFu;
+            one[q] |= (f.one & keep) << (sh + j);
+            exc[q] |= (f.exc & keep) << (sh + j);
+            hard |= f.off;
+        };
         if (meta & LF_FAST) {   // (wave-uniform)
-            const uint4 v = pl_edge_fields<EDGE>(pl_funnel(pl_load_window<EDGE>(text, n, soff, s0, lane), soff & 15u), rel);
-            PL_CLASSIFY(v.x, 0);
-            PL_CLASSIFY(v.y, 1);
-            PL_CLASSIFY(v.z, 2);
-            PL_CLASSIFY(v.w, 3);
+            const uint4 v = pl_edge_fields<EDGE>(pl_funnel(pl_load_window<EDGE>(w, soff), soff & 15u), w.rel);
+            add_field(v.x, 0), add_field(v.y, 1), add_field(v.z, 2), add_field(v.w, 3);
         } else {
-            // a record whose columns are all `wd` (5 .. 8) bytes wide with the GT sub-field first — "a|b:dd\t": config 4's GT:DP
-            // records (round 3 sent them all to the variable-width kernel: 3.5 of config 4's 16 ms, tab ranking and one atomic
-            // per nonzero call).  Each column is checked where it stands — byte 3 is the ':' that ends the GT, no tab or
-            // newline up to the column's last byte, which is the tab (the newline for the last sample) — and classified as
-            // "a|b\t"; a column of any other shape is a field no alphabet accepts, which sends the line to the variable-width
-            // kernel like any other surprise.  One field at a time: the first level's registers stay what they were.
-            const uint32_t shb = 8u * (wd - 5u);   // where the column's last byte sits in its second dword
-            const uint8_t *lbase = text + soff;    // (wave-uniform base, 32-bit lane offsets: no 64-bit address pairs per lane)
-            const uint64_t room64 = n - (uint64_t)soff;
+            // config 4's GT:DP records (round 3 sent them all to the variable-width kernel: 3.5 of config 4's 16 ms, tab
+            // ranking and one atomic per nonzero call); a column of any other shape sends the line there like any other
+            // surprise.  One field at a time: the first level's registers stay what they were.
+            const uint64_t room64 = w.n - (uint64_t)soff;
             const uint32_t room = room64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)room64;
-            const uint32_t lowm = shb ? (1u << shb) - 1u : 0u;
-#define PL_STRIDED(Q)                                                                                                  \
-    do {                                                                                                               \
-        uint32_t x = FILL_FIELD;                                                                                       \
-        if ((uint32_t)(Q) < nval) {                                                                                    \
-            const uint32_t vo = wd * (ls + (uint32_t)(Q));                                                             \
-            x = 0xFFFFFFFFu;                                                                                           \
-            if (vo + 8u <= room) {                                                                                     \
-                /* bytes 4 .. wd - 2 hold neither a tab nor a newline (the bytes above read 0), byte wd - 1 is the   */ \
-                /* tab (the newline behind the last sample), byte 3 the ':' that ends the GT                          */ \
-                const uint32_t d1 = reinterpret_cast<const PlU32 *>(lbase + vo + 4u)->v;                               \
-                const uint32_t low = d1 & lowm;                                                                        \
-                const uint32_t t9 = low ^ 0x09090909u, tA = low ^ 0x0A0A0A0Au;                                         \
-                uint32_t bad = (((t9 - 0x01010101u) & ~t9) | ((tA - 0x01010101u) & ~tA)) & 0x80808080u;                \
-                bad |= ((d1 >> shb) & 0xFFu) ^ (ls + (uint32_t)(Q) == S_all - 1u ? 0x0Au : 0x09u);                     \
-                const uint32_t d0 = reinterpret_cast<const PlU32 *>(lbase + vo)->v;                                    \
-                bad |= (d0 >> 24) ^ (uint32_t)':';                                                                     \
-                x = bad ? 0xFFFFFFFFu : ((d0 & 0x00FFFFFFu) | 0x09000000u);                                            \
-            }                                                                                                          \
-        }                                                                                                              \
-        PL_CLASSIFY(x, Q);                                                                                             \
-    } while (0)
-            PL_STRIDED(0);
-            PL_STRIDED(1);
-            PL_STRIDED(2);
-            PL_STRIDED(3);
-#undef PL_STRIDED
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                add_field((uint32_t)q < w.nval ? strided_field(w.text + soff, room, wd, w.ls + (uint32_t)q, w.ls + (uint32_t)q == w.S - 1u) : FILL_FIELD, q);
         }
-#undef PL_CLASSIFY
         const unsigned long long bm = __builtin_amdgcn_ballot_w64(hard != 0u) & 0x7FFFFFFFFFFFFFFFull;
-        if (bm != 0ull && lane == 0) {
-            const uint32_t k = (uint32_t)(kbase + j);
-            if (atomicExch(&redo_flag[k], 1u) == 0u) {
-                unsigned long long slot = atomicAdd(&cnt->n_general, 1ull);
-                redo_list[slot] = k;
-            }
-        }
+        if (bm != 0ull && w.lane == 0) send_to_general((uint32_t)(k + j), w.redo_list, w.redo_flag, w.cnt);
     }
 }
 
+// Group g of a step (kb = the kept index of the step's first line) -> per sample q: o / e[half][q], bit sh + j (haplotype 0)
+// and bit 16 + sh + j (haplotype 1) for line j of the group.  Three levels.  (1) pack_fast.  (2) some lane saw something
+// else: pack_careful classifies every field over the alphabet {0, 1, .} x {|, /}.  (3) a field outside that
+// alphabet (a third allele, a multi-digit index, anything malformed) contributes zero bits and sends its line to the
+// variable-width kernel, which sets the bits of the whole line (idempotent for the fields that were fine here).  Keeping (2)
+// rolled and out of the registers of (1) is what lets four workgroups share a CU.
 template <bool EDGE>
-__device__ __forceinline__ void encode_planes_tile(const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ k_soff,
-                                                   const uint32_t *__restrict__ k_meta, uint64_t v_base, uint32_t n_kept,
-                                                   const LayoutDev &lay, uint8_t *__restrict__ P, int8_t *__restrict__ G,
-                                                   uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag,
-                                                   DevCounters *cnt, uint32_t *img, uint32_t tile_v, uint32_t band)
+__device__ __forceinline__ void pl_pack_group(const PlWave &w, const PlGroup &gr, const int g, uint32_t (&o)[2][4], uint32_t (&e)[2][4], long long kb)
 {
-    const uint64_t gv0 = (v_base / PT_V + tile_v) * (uint64_t)PT_V;   // first global column of the tile
-    const long long k0 = (long long)gv0 - (long long)v_base;              // batch-local kept index of it
-    if (k0 >= (long long)n_kept || (!lay.ring && gv0 >= lay.v_capacity)) return;
-    const uint32_t s0 = band * PT_S;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t S = lay.S;
-    const uint32_t ls = s0 + 4u * lane;
-    const uint32_t nval = (lane == 63u || ls >= S) ? 0u : (S - ls >= 4u ? 4u : S - ls);
-    const long long kw = k0 + (long long)(w * PT_LW);
+    const int j0 = g * PT_G, half = j0 >> 4, sh = j0 & 15;
+    if (!pack_fast<EDGE>(w, gr, j0, sh, o[half])) pack_careful<EDGE>(w, j0, sh, o[half], e[half], kb + j0);
+}
 
-    constexpr int NG = 32 / PT_G;   // load groups per 32 lines
-    PlStep nxt = pl_load_step(k_soff, k_meta, kw, n_kept, lane);
-#pragma unroll 1
-    for (int gp = 0; gp < PT_LW / 32; ++gp) {   // 32 lines -> one dword per (kind, plane, sample)
-        const long long kb = kw + (long long)(gp * 32);
-        const PlStep stp = nxt;
-        if (gp + 1 < PT_LW / 32) nxt = pl_load_step(k_soff, k_meta, kb + 32, n_kept, lane);
-        uint32_t o[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, e[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        // PT_SCHED(): the instruction scheduler may not move anything across — it would otherwise hoist the loads of all
-        // four groups of a step to its top (128 registers of text in flight per lane, and spills)
-#define PT_SCHED() __builtin_amdgcn_sched_barrier(0)
-        // (the careful path of EDGE tiles does not fit the registers next to a second group in flight: they load one group
-        // at a time)
-        if (PT_DB && !EDGE) {
-            PlGroup A, B;
-            pl_load_group<EDGE>(A, text, n, stp, 0, s0, lane);
+// a step (32 lines; step = which of the tile's) -> image row (kind * 2 + plane) * 256 + sample, dword step ^ ((lane >> 1) & 7)
+__device__ __forceinline__ void write_image(uint32_t *img, const uint32_t (&o)[2][4], const uint32_t (&e)[2][4], uint32_t step, uint32_t lane)
+{
+    const uint32_t c = step ^ ((lane >> 1) & 7u);
 #pragma unroll
-            for (int g = 0; g < NG; g += 2) {
-                pl_load_group<EDGE>(B, text, n, stp, (g + 1) * PT_G, s0, lane);
-                PT_SCHED();
-                pl_pack_group<EDGE>(A, (g * PT_G) & 15, o[(g * PT_G) >> 4], e[(g * PT_G) >> 4], kb + g * PT_G, text, n, stp, g * PT_G, s0, ls,
-                                    nval, redo_list, redo_flag, cnt, lane, S);
-                PT_SCHED();
-                if (g + 2 < NG) pl_load_group<EDGE>(A, text, n, stp, (g + 2) * PT_G, s0, lane);
-                PT_SCHED();
-                pl_pack_group<EDGE>(B, ((g + 1) * PT_G) & 15, o[((g + 1) * PT_G) >> 4], e[((g + 1) * PT_G) >> 4], kb + (g + 1) * PT_G, text, n,
-                                    stp, (g + 1) * PT_G, s0, ls, nval, redo_list, redo_flag, cnt, lane, S);
-                PT_SCHED();
-            }
-        } else {
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                PlGroup A;
-                pl_load_group<EDGE>(A, text, n, stp, g * PT_G, s0, lane);
-                PT_SCHED();
-                pl_pack_group<EDGE>(A, (g * PT_G) & 15, o[(g * PT_G) >> 4], e[(g * PT_G) >> 4], kb + g * PT_G, text, n, stp, g * PT_G, s0, ls,
-                                    nval, redo_list, redo_flag, cnt, lane, S);
-                PT_SCHED();
-            }
-        }
-        // image row (kind * 2 + plane) * 256 + sample, 8 dwords; dword c of a row sits at c ^ ((lane >> 1) & 7)
-        const uint32_t c = (w * (uint32_t)(PT_LW / 32) + (uint32_t)gp) ^ ((lane >> 1) & 7u);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t r = (4u * lane + (uint32_t)q) * PT_ROWDW + c;
-            img[r] = __builtin_amdgcn_perm(o[1][q], o[0][q], 0x05040100u);                   // ONE, haplotype 0
-            img[256u * PT_ROWDW + r] = __builtin_amdgcn_perm(o[1][q], o[0][q], 0x07060302u);   // ONE, haplotype 1
-            img[512u * PT_ROWDW + r] = __builtin_amdgcn_perm(e[1][q], e[0][q], 0x05040100u);   // EXC, haplotype 0
-            img[768u * PT_ROWDW + r] = __builtin_amdgcn_perm(e[1][q], e[0][q], 0x07060302u);   // EXC, haplotype 1
-        }
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t r = (4u * lane + (uint32_t)q) * PT_ROWDW + c;
+        img[r] = __builtin_amdgcn_perm(o[1][q], o[0][q], 0x05040100u);                   // ONE, haplotype 0
+        img[256u * PT_ROWDW + r] = __builtin_amdgcn_perm(o[1][q], o[0][q], 0x07060302u);   // ONE, haplotype 1
+        img[512u * PT_ROWDW + r] = __builtin_amdgcn_perm(e[1][q], e[0][q], 0x05040100u);   // EXC, haplotype 0
+        img[768u * PT_ROWDW + r] = __builtin_amdgcn_perm(e[1][q], e[0][q], 0x07060302u);   // EXC, haplotype 1
     }
-    __syncthreads();
-    // image -> HBM: per kind-plane the band's 252 rows are one contiguous 8064-byte run of the tile (tile-major planes,
-    // common.h); rows 252..255 (lane 63's) are not the band's
-    uint64_t vcol = gv0 / lay.Vc;
-    const uint64_t vin = gv0 - vcol * lay.Vc;
-    if (lay.ring) vcol %= lay.ring;
+}
+
+// image -> HBM: per kind-plane the band's 252 rows are one contiguous 8064-byte run of the tile (tile-major planes,
+// common.h); rows 252..255 (lane 63's) are not the band's.  Un-swizzle in registers, then the append-position merge.
+__device__ __forceinline__ void store_image(const uint32_t *img, const TilePlace &at, const LayoutDev &lay, uint8_t *__restrict__ P, uint32_t s0)
+{
     const PlanesGeom pg = planes_geom(lay, 0u);
-    const uint32_t tile = (uint32_t)(vin / PL_TILE);
-    const uint32_t nkeep = k0 < 0 ? (uint32_t)(-k0) : 0u;     // leading columns that belong to the previous call
+    const uint32_t tile = (uint32_t)(at.vin / PL_TILE);
+    const uint32_t nkeep = at.k0 < 0 ? (uint32_t)(-at.k0) : 0u;     // leading columns that belong to the previous call
 #pragma unroll 4
     for (int it = 0; it < 2048 / (64 * PT_NW); ++it) {
         const uint32_t pi = (uint32_t)it * (64u * PT_NW) + threadIdx.x;   // 16-byte piece: kp * 512 + row * 2 + half
         const uint32_t kp = pi >> 9, row = (pi >> 1) & 255u, half = pi & 1u;
         const uint32_t s = s0 + row;
-        if (row >= PT_S || s >= S) continue;
+        if (row >= PT_S || s >= lay.S) continue;
         const uint32_t sw = (row >> 3) & 7u;   // the writer's (lane >> 1) & 7: row = 4 lane + q
         const uint4 t = reinterpret_cast<const uint4 *>(img)[(kp * 256u + row) * 2u + (half ^ (sw >> 2))];
-        uint32_t d0 = t.x, d1 = t.y, d2 = t.z, d3 = t.w;
-        if (sw & 1u) {
-            uint32_t u = d0; d0 = d1; d1 = u;
-            u = d2; d2 = d3; d3 = u;
-        }
-        if (sw & 2u) {
-            uint32_t u = d0; d0 = d2; d2 = u;
-            u = d1; d1 = d3; d3 = u;
-        }
-        uint8_t *dst = P + planes_piece(pg, vcol, tile, kp, s) + half * 16u;
+        const bool s1 = sw & 1u, s2 = sw & 2u;   // dword c of the piece sits at c ^ (sw & 3)
+        const uint32_t a0 = s1 ? t.y : t.x, a1 = s1 ? t.x : t.y, a2 = s1 ? t.w : t.z, a3 = s1 ? t.z : t.w;
+        uint32_t d0 = s2 ? a2 : a0, d1 = s2 ? a3 : a1, d2 = s2 ? a0 : a2, d3 = s2 ? a1 : a3;
+        uint8_t *dst = P + planes_piece(pg, at.vcol, tile, kp, s) + half * 16u;
         if (nkeep) {   // (workgroup-uniform) the tile straddles the append position
             const uint32_t b0 = half * 128u;
             if (b0 + 128u <= nkeep) continue;
@@ -575,22 +546,66 @@ __device__ __forceinline__ void encode_planes_tile(const uint8_t *__restrict__ t
     }
 }
 
+template <bool EDGE>
+__device__ __forceinline__ void encode_planes_tile(PlWave &w, const uint32_t *__restrict__ k_soff, const uint32_t *__restrict__ k_meta,
+                                                   uint32_t n_kept, const TilePlace &at, const LayoutDev &lay, uint8_t *__restrict__ P, uint32_t *img)
+{
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long long kw = at.k0 + (long long)(wv * PT_LW);
+    PlStep nxt = pl_load_step(k_soff, k_meta, kw, n_kept, w.lane);
+#pragma unroll 1
+    for (int gp = 0; gp < PT_LW / 32; ++gp) {   // 32 lines -> one dword per (kind, plane, sample)
+        const long long kb = kw + (long long)(gp * 32);
+        w.stp = nxt;
+        if (gp + 1 < PT_LW / 32) nxt = pl_load_step(k_soff, k_meta, kb + 32, n_kept, w.lane);
+        uint32_t o[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, e[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        // sched_barrier(0): the instruction scheduler may not move anything across — it would otherwise hoist the loads of
+        // all four groups of a step to its top (128 registers of text in flight per lane, and spills)
+        if (!EDGE) {
+            // two groups in flight: load B, pack A, load A, pack B
+            PlGroup A, B;
+            pl_load_group<EDGE>(w, A, 0);
+#pragma unroll
+            for (int g = 0; g < PT_NG; g += 2) {
+                pl_load_group<EDGE>(w, B, g + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                pl_pack_group<EDGE>(w, A, g, o, e, kb);
+                __builtin_amdgcn_sched_barrier(0);
+                if (g + 2 < PT_NG) pl_load_group<EDGE>(w, A, g + 2);
+                __builtin_amdgcn_sched_barrier(0);
+                pl_pack_group<EDGE>(w, B, g + 1, o, e, kb);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            // (EDGE tiles' careful path does not fit the registers next to a second group in flight: one group at a time)
+#pragma unroll
+            for (int g = 0; g < PT_NG; ++g) {
+                PlGroup A;
+                pl_load_group<EDGE>(w, A, g);
+                __builtin_amdgcn_sched_barrier(0);
+                pl_pack_group<EDGE>(w, A, g, o, e, kb);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        write_image(img, o, e, wv * (uint32_t)(PT_LW / 32) + (uint32_t)gp, w.lane);
+    }
+    __syncthreads();
+    store_image(img, at, lay, P, w.s0);
+}
+
 // The band of sample columns that holds the last sample (and lanes past it) reads with care (EDGE), and so does every band
 // of a tile whose last line's window could end past the text (the text's last lines, in front of a last band of 1..3
 // samples): kept lines are in text order, so no line of the tile starts behind its last one.  Every other tile reads flat.
 // One launch, a workgroup-uniform branch: since the medium path is a rolled loop both bodies fit the same registers, and
 // the last band's tiles fill the tail of the grid instead of being an under-filled launch of their own (round 3 first split
 // them: 1.2 of 7.8 ms per step).
-__global__ __launch_bounds__(64 * PT_NW, PT_WGS) void k_encode_planes(const uint8_t *__restrict__ text, uint64_t n,
-                                                          const uint32_t *__restrict__ k_soff, const uint32_t *__restrict__ k_meta,
-                                                          const uint64_t *__restrict__ d_cursor, LayoutDev lay,
-                                                          uint8_t *__restrict__ P, int8_t *__restrict__ G,
-                                                          uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag,
-                                                          DevCounters *cnt, uint32_t tiles_v, uint32_t tiles_s)
+__global__ __launch_bounds__(64 * PT_NW, PT_WGS) void k_encode_planes(
+    const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ k_soff, const uint32_t *__restrict__ k_meta,
+    const uint64_t *__restrict__ d_cursor, LayoutDev lay, uint8_t *__restrict__ P, int8_t *__restrict__ G,
+    uint32_t *__restrict__ redo_list, uint32_t *__restrict__ redo_flag, DevCounters *cnt, uint32_t tiles_v, uint32_t tiles_s)
 {
     HHGT_WAVE_PRIO();
     __shared__ __attribute__((aligned(16))) uint32_t img[1024 * PT_ROWDW];   // 32 KiB
-    const uint64_t v_base = *d_cursor;
     const uint32_t n_kept = (uint32_t)cnt->n_kept;
     // which tile: (variant tile, sample band) from the linear workgroup id.  Sample band fastest, so workgroups that run
     // together read neighbouring KiB of the same lines, and the bands of one variant tile stay on one XCD (workgroup id
@@ -599,16 +614,20 @@ __global__ __launch_bounds__(64 * PT_NW, PT_WGS) void k_encode_planes(const uint
     const uint32_t band = q % tiles_s;
     const uint32_t tile_v = (q / tiles_s) * 8u + x;
     if (tile_v >= tiles_v) return;
+    const TilePlace at = tile_place(lay, *d_cursor, n_kept, PT_V, tile_v);
+    if (!at.live) return;
     bool edge = band + 1u == tiles_s;
     if (!edge) {
-        const long long k0 = (long long)((v_base / PT_V + tile_v) * (uint64_t)PT_V) - (long long)v_base;
-        const long long kl = k0 + (PT_V - 1) < (long long)n_kept - 1 ? k0 + (PT_V - 1) : (long long)n_kept - 1;
+        const long long kl = at.k0 + (PT_V - 1) < (long long)n_kept - 1 ? at.k0 + (PT_V - 1) : (long long)n_kept - 1;
         if (kl >= 0) edge = (uint64_t)k_soff[kl] + 4ull * PT_S * band + 1024ull > n;
     }
+    const uint32_t lane = threadIdx.x & 63u, S = lay.S, s0 = band * PT_S, ls = s0 + 4u * lane;
+    const uint32_t nval = (lane == 63u || ls >= S) ? 0u : (S - ls >= 4u ? 4u : S - ls);
+    PlWave w = {text, n, {0u, 0u}, s0, ls, nval, lane, S, lane == 63u ? -1 : (int)(S - 1u) - (int)ls, redo_list, redo_flag, cnt};
     if (edge)
-        encode_planes_tile<true>(text, n, k_soff, k_meta, v_base, n_kept, lay, P, G, redo_list, redo_flag, cnt, img, tile_v, band);
+        encode_planes_tile<true>(w, k_soff, k_meta, n_kept, at, lay, P, img);
     else
-        encode_planes_tile<false>(text, n, k_soff, k_meta, v_base, n_kept, lay, P, G, redo_list, redo_flag, cnt, img, tile_v, band);
+        encode_planes_tile<false>(w, k_soff, k_meta, n_kept, at, lay, P, img);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -649,34 +668,152 @@ __device__ __forceinline__ uint32_t parse_gt_bytes(RD rd, uint32_t p, uint32_t l
     return ((uint32_t)vals[0] & 0xFFu) | (((uint32_t)vals[1] & 0xFFu) << 8);
 }
 
-#define GEN_HALO 64u  // bytes staged past each 1 KiB piece: a GT sub-field that starts in the piece ends inside it
+// -------------------------------------------------------------------------------------------------
+constexpr uint32_t GEN_HALO = 64u;  // bytes staged past each 1 KiB piece: a GT sub-field that starts in the piece ends inside it
 
-// 16 bytes of the text at `at` if they lie inside it, else what there is (zero-filled): the last line of a text may end
-// within 16 bytes of the buffer's end
-__device__ __forceinline__ uint4 gen_load16(const uint8_t *__restrict__ text, uint64_t n, uint64_t at)
+// The staged piece and the column list are reached through pointers that CARRY the LDS address space.  Through a generic
+// pointer variable (or as one arm of a select against the global text) the reader below lost the address space and every
+// character it fetches became a flat_load — 915 global-load instructions per line, 520 us per line.
+typedef __attribute__((address_space(3))) uint8_t lds_u8;
+typedef __attribute__((address_space(3))) uint16_t lds_u16;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
+typedef __attribute__((address_space(3))) u32x4_al lds_u128;
+// the lanes hand the staged piece and the column list to each other through LDS, which executes a wave's accesses in order: this
+// keeps the COMPILER from moving a lane's read of another lane's slot across the stores (no instruction; lz4bits.hip's BP_FENCE)
+__device__ __forceinline__ void gen_fence()
 {
-    if (at + 16ull <= n) {
-        const u32x4_unaligned t = *reinterpret_cast<const u32x4_unaligned *>(text + at);
-        return make_uint4(t.x, t.y, t.z, t.w);
-    }
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    for (uint32_t k = 0; k < 16u; ++k)
-        if (at + k < n) w[k >> 2] |= (uint32_t)text[at + k] << (8u * (k & 3u));
-    return make_uint4(w[0], w[1], w[2], w[3]);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
 }
 
-// inclusive wave scan of small counts on DPP row shifts (no LDS round trips)
-__device__ __forceinline__ uint32_t gen_scan_incl(uint32_t x, uint32_t lane)
+__device__ __forceinline__ void stage_piece(lds_u8 *piece, const uint4 cur, const uint4 hal, uint32_t lane)
 {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);
-    const uint32_t t0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 15);
-    const uint32_t t1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 31) + t0;
-    const uint32_t t2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 47) + t1;
-    const uint32_t row = lane >> 4;
-    return x + (row == 0u ? 0u : (row == 1u ? t0 : (row == 2u ? t1 : t2)));
+    *reinterpret_cast<lds_u128 *>(piece + 16u * lane) = u32x4_al{cur.x, cur.y, cur.z, cur.w};
+    if (lane < GEN_HALO / 16u) *reinterpret_cast<lds_u128 *>(piece + 1024u + 16u * lane) = u32x4_al{hal.x, hal.y, hal.z, hal.w};
+}
+
+// exact per-byte "== c" mask of 16 bytes (SWAR), 4 bits per dword
+__device__ __forceinline__ uint32_t eq_mask16(const uint4 v, uint32_t c)
+{
+    const uint32_t wv[4] = {v.x, v.y, v.z, v.w};
+    uint32_t m = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const uint32_t t = wv[q] ^ (c * 0x01010101u);
+        const uint32_t z = ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu);
+        m |= ((((z >> 7) * 0x01020408u) >> 24) & 0xFu) << (4 * q);
+    }
+    return m;
+}
+
+// the tabs of the lane's 16 bytes at b0 (one bit per byte, none at or behind the line's end); *nl_inside collects newlines
+__device__ __forceinline__ uint32_t tab_and_newline_masks(const uint4 cur, uint32_t b0, uint32_t lend, uint32_t *nl_inside)
+{
+    const uint32_t inl = b0 >= lend ? 0u : (lend - b0 >= 16u ? 0xFFFFu : ((1u << (lend - b0)) - 1u));
+    *nl_inside |= eq_mask16(cur, '\n') & inl;
+    return eq_mask16(cur, '\t') & inl;
+}
+
+// the columns that start in this piece, in order: list[i] = offset of the byte behind the i-th tab; returns how many
+__device__ __forceinline__ uint32_t list_columns(lds_u16 *list, uint32_t m, uint32_t lane)
+{
+    const uint32_t c = __popc(m);
+    uint32_t nf;
+    uint32_t at = wave_scan_sum_dpp(c, lane, &nf) - c, mm = m;
+    while (__builtin_amdgcn_ballot_w64(mm != 0u) != 0ull) {
+        const bool on = mm != 0u;
+        const uint32_t j = (uint32_t)__builtin_ctz(mm | 0x10000u);
+        list[on ? at : 1023u] = (uint16_t)(16u * lane + j + 1u);   // (slot 1023 is never a column's: a piece with 1024 tabs has its last one at offset 1023, written by an `on` lane)
+        at += on ? 1u : 0u;
+        mm &= mm - 1u;
+    }
+    return nf;
+}
+
+// byte p of the text: from the staged piece (and its halo), or from the text itself beyond the halo (rare long sub-fields)
+struct PieceReader {
+    const lds_u8 *piece;
+    const uint8_t *text;
+    uint32_t base, avail;
+    __device__ __forceinline__ uint32_t operator()(uint32_t p) const
+    {
+        const uint32_t o = p - base;
+        if (o < avail) return (uint32_t)piece[o];
+        return (uint32_t)text[p];
+    }
+};
+
+// skip gtidx sub-fields: p to the start of the GT sub-field; false when the column has none
+__device__ __forceinline__ bool skip_to_gt(const PieceReader &rd, uint32_t &p, uint32_t lend, uint32_t gtidx)
+{
+    for (uint32_t gsk = 0; gsk < gtidx; ++gsk) {
+        while (p < lend && rd(p) != ':' && rd(p) != '\t') ++p;
+        if (p < lend && rd(p) == ':') ++p;
+        else return false;
+    }
+    return true;
+}
+
+// the common column: GT reads "a|b" / "a/b" with a, b in {0, 1, .}, closed by ':', a tab or the line end.  Four bytes from
+// the staged piece (two aligned dwords, one funnel shift) through classify_field; the terminator is judged here
+__device__ __forceinline__ bool common_column(const PieceReader &rd, uint32_t p, uint32_t lend, uint32_t *hv)
+{
+    const bool inb = p - rd.base + 8u <= rd.avail;
+    const uint32_t o = inb ? p - rd.base : 0u;
+    const lds_u32 *w32 = reinterpret_cast<const lds_u32 *>(rd.piece);
+    uint32_t x = __builtin_amdgcn_alignbyte(w32[(o >> 2) + 1u], w32[o >> 2], o & 3u);
+    if (p + 3u >= lend) x = (x & 0x00FFFFFFu) | 0x09000000u;   // the line (and the text) ends behind the call
+    const FieldBits f = classify_field<false>(x);
+    const uint32_t yt = (x ^ FILL_FIELD) >> 24;                     // terminator: '\t', '\n' or ':'
+    const bool done = inb & (f.off == 0u) & ((yt == 0u) | (yt == 0x03u) | (yt == 0x33u)) & (p + 3u <= lend);
+    const uint32_t h0 = (f.exc & 1u) ? 0xF7u : (f.one & 1u), h1 = (f.exc >> 16) ? 0xF7u : (f.one >> 16);
+    *hv = h0 | (h1 << 8);
+    return done;
+}
+
+// Where a line's calls go in the bit-plane form (wave-uniform: the line's tile and bit are the same for every sample):
+// word = sample 0's dword of kind-plane 0, kstride = dwords between the kind-planes of a tile
+struct PlaneLine { uint8_t *word; uint64_t kstride; uint32_t pmask; };
+__device__ __forceinline__ PlaneLine plane_line(const PlanesGeom &pg, const TilePlace &at, uint8_t *P)
+{
+    const uint32_t tile = (uint32_t)(at.vin / PL_TILE), bit = (uint32_t)(at.vin % PL_TILE);
+    return {P + planes_piece(pg, at.vcol, tile, 0u, 0u) + ((bit >> 5) << 2), (uint64_t)pg.S_pad * 8ull, 1u << (bit & 31u)};
+}
+
+// (the bytes of calls beyond 0 / 1 / missing go to their place in G — 64-bit multiplies: only where needed)
+__device__ __forceinline__ void emit_planes(const PlaneLine &pl, const LayoutDev &lay, const TilePlace &at, bool act, uint32_t s, uint32_t hv,
+                                            int8_t *__restrict__ G, uint32_t *n_other)
+{
+    const uint32_t h0 = hv & 0xFFu, h1 = (hv >> 8) & 0xFFu;
+    // kind-planes of a tile: ONE of haplotype 0, ONE of haplotype 1, EXC of haplotype 0, EXC of haplotype 1
+    const bool bk[4] = {act && (h0 == 1u || h0 == 0xF7u), act && (h1 == 1u || h1 == 0xF7u), act && h0 > 1u, act && h1 > 1u};
+    uint32_t *pw = reinterpret_cast<uint32_t *>(pl.word + (uint64_t)s * 32ull);
+    if (bk[0]) atomicOr(pw, pl.pmask);
+    if (bk[1]) atomicOr(pw + pl.kstride, pl.pmask);
+    if (bk[2]) atomicOr(pw + 2ull * pl.kstride, pl.pmask);
+    if (bk[3]) atomicOr(pw + 3ull * pl.kstride, pl.pmask);
+    if (bk[2] && h0 != 0xF7u) {
+        ++*n_other;
+        if (G) G[matrix_at(lay, at.vcol, s, at.vin)] = (int8_t)h0;
+    }
+    if (bk[3] && h1 != 0xF7u) {
+        ++*n_other;
+        if (G) G[matrix_at(lay, at.vcol, s, at.vin) + 1ull] = (int8_t)h1;
+    }
+}
+
+__device__ __forceinline__ void wave_totals(DevCounters *cnt, uint32_t haploid, uint32_t malformed, uint32_t n_other, uint32_t lane)
+{
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        haploid += __shfl_down(haploid, d, 64);
+        n_other += __shfl_down(n_other, d, 64);
+    }
+    if (lane == 0) {
+        if (haploid) atomicAdd(&cnt->n_haploid, (unsigned long long)haploid);
+        if (malformed) atomicAdd(&cnt->n_malformed, (unsigned long long)malformed);
+        if (n_other) atomicAdd(&cnt->n_other, (unsigned long long)n_other);
+    }
 }
 
 // PLANES: the bit-plane form (k_encode_planes wrote zeros for every call of the lines this kernel owns; the bits are set
@@ -695,14 +832,10 @@ __device__ __forceinline__ uint32_t gen_scan_incl(uint32_t x, uint32_t lane)
 // the line was built and measured: 4.3 ms — a burst of sparse device-scope atomics hides worse than a trickle (in git
 // history: round 3).
 template <bool PLANES>
-__global__ __launch_bounds__(256) void k_encode_general(const uint8_t *__restrict__ text, uint64_t n,
-                                                        const uint32_t *__restrict__ k_soff,
-                                                        const uint32_t *__restrict__ k_lend,
-                                                        const uint32_t *__restrict__ k_meta,
-                                                        const uint32_t *__restrict__ redo_list,
-                                                        const uint64_t *__restrict__ d_cursor,
-                                                        LayoutDev lay, int8_t *__restrict__ G, uint8_t *__restrict__ P,
-                                                        DevCounters *cnt)
+__global__ __launch_bounds__(256) void k_encode_general(const uint8_t *__restrict__ text, uint64_t n, const uint32_t *__restrict__ k_soff,
+                                                        const uint32_t *__restrict__ k_lend, const uint32_t *__restrict__ k_meta,
+                                                        const uint32_t *__restrict__ redo_list, const uint64_t *__restrict__ d_cursor,
+                                                        LayoutDev lay, int8_t *__restrict__ G, uint8_t *__restrict__ P, DevCounters *cnt)
 {
     const uint64_t v_base = *d_cursor;
     const PlanesGeom pgeom = planes_geom(lay, 0u);
@@ -713,124 +846,44 @@ __global__ __launch_bounds__(256) void k_encode_general(const uint8_t *__restric
     const uint32_t S = lay.S;
     __shared__ __attribute__((aligned(16))) uint8_t sbuf[4][1024 + GEN_HALO];   // the piece (plus a halo), per wave
     __shared__ uint16_t slist[4][1024];                                          // where its columns start
-    // (the staged piece is always reached as sbuf[wq][...]: through a pointer variable the reader lambda below lost the LDS
-    // address space and every character was a flat_load — 915 global-load instructions per line, 520 us per line)
     const uint32_t wq = threadIdx.x >> 6;
-#define buf (sbuf[wq])
+    lds_u8 *piece = (lds_u8 *)sbuf[wq];
+    lds_u16 *list = (lds_u16 *)slist[wq];
     uint32_t haploid = 0, malformed = 0, n_other = 0;
     for (uint32_t idx = wave; idx < n_redo; idx += n_waves) {
         const uint32_t k = redo_list[idx];
         const uint32_t soff = k_soff[k], lend = k_lend[k], gtidx = (k_meta[k] >> 8) & 0xFFFu;
-        const uint64_t v = v_base + k;
-        if (!lay.ring && v >= lay.v_capacity) continue;
-        uint64_t vcol = v / lay.Vc;
-        const uint64_t vin = v - vcol * lay.Vc;
-        if (lay.ring) vcol %= lay.ring;
-        // bit-plane form: where this line's bit lives in every sample's piece of the tile (wave-uniform)
-        const uint64_t kstride = (uint64_t)pgeom.S_pad * 8ull;   // dwords between the kind-planes of a tile
-        uint8_t *pline = PLANES ? P + planes_piece(pgeom, vcol, (uint32_t)(vin / PL_TILE), 0u, 0u) + (((uint32_t)(vin % PL_TILE) >> 5) << 2) : nullptr;
-        const uint32_t pmask = 1u << ((uint32_t)(vin % PL_TILE) & 31u);
+        const TilePlace at = tile_place(lay, v_base, 0xFFFFFFFFu, 1u, k);   // the line's column: v_base + k
+        if (!at.live) continue;
+        const PlaneLine pline = PLANES ? plane_line(pgeom, at, P) : PlaneLine{nullptr, 0ull, 0u};
         const uint32_t rs = soff - 1u;  // the 9th tab: every sample field is preceded by a tab in [rs, lend)
         uint32_t tabs_before = 0, nl_inside = 0;
         // software pipeline: the piece in `cur` / `hal` was loaded one iteration ago
-        uint4 cur = gen_load16(text, n, (uint64_t)rs + 16u * lane);
-        uint4 hal = lane < GEN_HALO / 16u ? gen_load16(text, n, (uint64_t)rs + 1024u + 16u * lane) : make_uint4(0u, 0u, 0u, 0u);
+        uint4 cur = load16_or(text, n, (uint64_t)rs + 16u * lane, 0u);
+        uint4 hal = lane < GEN_HALO / 16u ? load16_or(text, n, (uint64_t)rs + 1024u + 16u * lane, 0u) : make_uint4(0u, 0u, 0u, 0u);
         for (uint32_t base = rs; base < lend; base += 1024u) {
             const uint32_t b0 = base + 16u * lane;
             const bool more = base + 1024u < lend;   // (wave-uniform)
             uint4 nx = make_uint4(0u, 0u, 0u, 0u), nh = nx;
             if (more) {
-                nx = gen_load16(text, n, (uint64_t)b0 + 1024u);
-                if (lane < GEN_HALO / 16u) nh = gen_load16(text, n, (uint64_t)base + 2048u + 16u * lane);
+                nx = load16_or(text, n, (uint64_t)b0 + 1024u, 0u);
+                if (lane < GEN_HALO / 16u) nh = load16_or(text, n, (uint64_t)base + 2048u + 16u * lane, 0u);
             }
-            *reinterpret_cast<uint4 *>(buf + 16u * lane) = cur;
-            if (lane < GEN_HALO / 16u) *reinterpret_cast<uint4 *>(buf + 1024u + 16u * lane) = hal;
-            // exact per-byte "== tab" mask (SWAR), 4 bits per dword; bytes at or behind the line's end do not count
-            uint32_t m = 0;
-            {
-                const uint32_t wv[4] = {cur.x, cur.y, cur.z, cur.w};
-                const uint32_t inl = b0 >= lend ? 0u : (lend - b0 >= 16u ? 0xFFFFu : ((1u << (lend - b0)) - 1u));
-                uint32_t nlm = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const uint32_t t = wv[q] ^ 0x09090909u;
-                    const uint32_t z = ~(((t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | t | 0x7F7F7F7Fu);
-                    m |= ((((z >> 7) * 0x01020408u) >> 24) & 0xFu) << (4 * q);
-                    const uint32_t tn = wv[q] ^ 0x0A0A0A0Au;
-                    const uint32_t zn = ~(((tn & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | tn | 0x7F7F7F7Fu);
-                    nlm |= ((((zn >> 7) * 0x01020408u) >> 24) & 0xFu) << (4 * q);
-                }
-                m &= inl;
-                nl_inside |= nlm & inl;   // a newline in front of the line's own
-            }
-            const uint32_t avail = lend - base < 1024u + GEN_HALO ? lend - base : 1024u + GEN_HALO;
-            // the staged piece through a pointer that CARRIES the LDS address space: as a generic pointer (or as one arm of a
-            // select against the global text) every character the reader below fetches became a flat_load
-            typedef __attribute__((address_space(3))) const uint8_t lds_u8;
-            lds_u8 *lbuf = (lds_u8 *)(uintptr_t)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)sbuf[wq];
-            auto rd = [&](uint32_t p) -> uint32_t {
-                const uint32_t o = p - base;
-                if (o < avail) return (uint32_t)lbuf[o];
-                return (uint32_t)text[p];  // beyond the halo: rare long sub-fields
-            };
-            // the columns that start in this piece, in order: slist[i] = offset of the byte behind the i-th tab
-            const uint32_t c = __popc(m);
-            const uint32_t inc = gen_scan_incl(c, lane);
-            const uint32_t nf = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-            {
-                uint32_t at = inc - c, mm = m;
-                while (__builtin_amdgcn_ballot_w64(mm != 0u) != 0ull) {
-                    const bool on = mm != 0u;
-                    const uint32_t j = (uint32_t)__builtin_ctz(mm | 0x10000u);
-                    slist[wq][on ? at : 1023u] = (uint16_t)(16u * lane + j + 1u);   // (slot 1023 is never a column's: a piece with 1024 tabs has its last one at offset 1023, written by an `on` lane)
-                    at += on ? 1u : 0u;
-                    mm &= mm - 1u;
-                }
-            }
-            // the lanes hand the staged piece and the column list to each other through LDS: the LDS executes a wave's
-            // accesses in order, and these two lines keep the COMPILER from moving a lane's read of another lane's slot in
-            // front of the stores above (no instruction is emitted; lz4bits.hip's BP_FENCE is the same pair)
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
+            stage_piece(piece, cur, hal, lane);
+            const uint32_t m = tab_and_newline_masks(cur, b0, lend, &nl_inside);
+            const PieceReader rd = {piece, text, base, lend - base < 1024u + GEN_HALO ? lend - base : 1024u + GEN_HALO};
+            const uint32_t nf = list_columns(list, m, lane);
+            gen_fence();
             for (uint32_t r0 = 0; r0 < nf; r0 += 64u) {   // (wave-uniform trip count)
                 const uint32_t i = r0 + lane;
                 const uint32_t s = tabs_before + i;
                 const bool act = i < nf && s < S;   // surplus columns are not decoded (the oracle ignores them too)
-                const uint32_t o0 = (uint32_t)slist[wq][i < 1024u ? i : 1023u];
+                const uint32_t o0 = (uint32_t)list[i < 1024u ? i : 1023u];
                 uint32_t p = base + (act ? o0 : 1u);
-                bool missing = false;
-                if (gtidx != 0u && act) {
-                    for (uint32_t gsk = 0; gsk < gtidx; ++gsk) {  // skip to the GT sub-field
-                        while (p < lend && rd(p) != ':' && rd(p) != '\t') ++p;
-                        if (p < lend && rd(p) == ':') ++p;
-                        else {
-                            missing = true;
-                            break;
-                        }
-                    }
-                }
-                uint32_t na = 2u, hv = 0xF7F7u;
-                bool done = false;
-                {
-                    // the common column: GT comes first and reads "a|b" / "a/b" with a, b in {0, 1, .}, closed by ':', a tab or
-                    // the line end.  Four bytes from the staged piece (two aligned dwords, one funnel shift), the same
-                    // branch-free classification as the tile kernel's second level.
-                    const bool inb = p - base + 8u <= avail;
-                    const uint32_t o = inb ? p - base : 0u;
-                    const uint32_t *w32 = reinterpret_cast<const uint32_t *>(sbuf[wq]);
-                    uint32_t x = __builtin_amdgcn_alignbyte(w32[(o >> 2) + 1u], w32[o >> 2], o & 3u);
-                    if (p + 3u >= lend) x = (x & 0x00FFFFFFu) | 0x09000000u;   // the line (and the text) ends behind the call
-                    const uint32_t y = x ^ 0x09307C30u;
-                    const uint32_t yt = y >> 24;                                    // terminator: '\t', '\n' or ':'
-                    const uint32_t t4 = y >> 4;
-                    const uint32_t e2 = t4 & 0x00010001u, o2 = (y | t4) & 0x00010001u;
-                    const uint32_t want = __umul24(e2, 30u) | (y & 0x00010001u & ~e2);
-                    const uint32_t z = y & 0x0000FF00u, zz = z ^ 0x00005300u;
-                    const uint32_t off = ((y & 0x00FF00FFu) ^ want) | (z < zz ? z : zz);
-                    done = inb & !missing & (off == 0u) & ((yt == 0u) | (yt == 0x03u) | (yt == 0x33u)) & (p + 3u <= lend);
-                    const uint32_t h0 = (e2 & 1u) ? 0xF7u : (o2 & 1u), h1 = (e2 >> 16) ? 0xF7u : (o2 >> 16);
-                    hv = done ? (h0 | (h1 << 8)) : 0xF7F7u;
-                }
+                const bool missing = gtidx != 0u && act && !skip_to_gt(rd, p, lend, gtidx);
+                uint32_t na = 2u, hv;
+                const bool done = common_column(rd, p, lend, &hv) & !missing;
+                if (!done) hv = 0xF7F7u;
                 if (__builtin_amdgcn_ballot_w64(act && !done && !missing) != 0ull) {   // (wave-uniform: some lane needs the byte walk)
                     if (act && !done && !missing) {
                         na = 1u;
@@ -840,101 +893,28 @@ __global__ __launch_bounds__(256) void k_encode_general(const uint8_t *__restric
                 }
                 if (act && missing) na = 1u;   // a column without the GT sub-field counts as one missing allele (parse_gt_bytes of nothing)
                 if (act && na == 1u) ++haploid;
-                auto g_off = [&]() -> uint64_t {   // the call's place in the int8 matrix (64-bit multiplies: only where it is needed)
-                    const uint32_t scol = lay.sc_log2 >= 31u ? 0u : (s >> lay.sc_log2);
-                    const uint32_t sin = s - scol * lay.Sc;
-                    return (((vcol * lay.n_sc + scol) * lay.Sc + sin) * lay.Vc + vin) * 2ull;
-                };
                 if (!PLANES) {
-                    if (act) *reinterpret_cast<uint16_t *>(G + g_off()) = (uint16_t)hv;
-                } else {
-                    const uint32_t h0 = hv & 0xFFu, h1 = (hv >> 8) & 0xFFu;
-                    // kind-planes of a tile: ONE of haplotype 0, ONE of haplotype 1, EXC of haplotype 0, EXC of haplotype 1
-                    const bool bk[4] = {act && (h0 == 1u || h0 == 0xF7u), act && (h1 == 1u || h1 == 0xF7u), act && h0 > 1u, act && h1 > 1u};
-#ifndef GEN_NO_SCATTER   // (development: timing of the column rounds alone; invalid planes)
-                    {
-                        // (pline: the line's tile and bit are the same for every sample — wave-uniform, computed once per line)
-                        uint32_t *pw = reinterpret_cast<uint32_t *>(pline + (uint64_t)s * 32ull);
-                        if (bk[0]) atomicOr(pw, pmask);
-                        if (bk[1]) atomicOr(pw + kstride, pmask);
-                        if (bk[2]) atomicOr(pw + 2ull * kstride, pmask);
-                        if (bk[3]) atomicOr(pw + 3ull * kstride, pmask);
-                    }
-#endif
-                    if (bk[2] && h0 != 0xF7u) {
-                        ++n_other;
-                        if (G) G[g_off()] = (int8_t)h0;
-                    }
-                    if (bk[3] && h1 != 0xF7u) {
-                        ++n_other;
-                        if (G) G[g_off() + 1ull] = (int8_t)h1;
-                    }
-                }
+                    if (act) *reinterpret_cast<uint16_t *>(G + matrix_at(lay, at.vcol, s, at.vin)) = (uint16_t)hv;
+                } else
+                    emit_planes(pline, lay, at, act, s, hv, G, &n_other);
             }
             tabs_before += nf;
             cur = nx;
             hal = nh;
-            __builtin_amdgcn_wave_barrier();   // ... and the next piece's stores behind this piece's reads
-            asm volatile("" ::: "memory");
+            gen_fence();
         }
         // fewer sample columns than the header declares; or a line end inside the line: a line shorter than any record
         // with S samples can be (its newline lay in the part the hopping index does not look at, index.hip)
         const bool broken = __builtin_amdgcn_ballot_w64(nl_inside != 0u) != 0ull;
         if ((tabs_before < S || broken) && lane == 0) ++malformed;
     }
-    // one atomic per wave
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        haploid += __shfl_down(haploid, d, 64);
-        n_other += __shfl_down(n_other, d, 64);
-    }
-    if (lane == 0) {
-        if (haploid) atomicAdd(&cnt->n_haploid, (unsigned long long)haploid);
-        if (malformed) atomicAdd(&cnt->n_malformed, (unsigned long long)malformed);
-        if (n_other) atomicAdd(&cnt->n_other, (unsigned long long)n_other);
-    }
+    wave_totals(cnt, haploid, malformed, n_other, lane);
 }
-#undef buf
 
 // -------------------------------------------------------------------------------------------------
-// zero columns [c0, c1) (variant index inside the chunk column) of rows [r0, r1) (sample index inside
-// the padded sample axis) of chunk column vcol
-__global__ __launch_bounds__(256) void k_zero_rect(LayoutDev lay, uint64_t vcol0, uint32_t r0, uint32_t r1,
-                                                   uint64_t c0, uint64_t c1, int8_t *__restrict__ G)
+// zero bytes [b0, b1) of a sample row of the int8 matrix in 16-byte segments, the workgroups of grid.x side by side
+__device__ __forceinline__ void zero_row_bytes(int8_t *row, uint64_t b0, uint64_t b1)
 {
-    const uint64_t vcol = vcol0 + blockIdx.z;   // one launch covers a range of chunk columns
-    const uint32_t r = r0 + blockIdx.y;
-    if (r >= r1) return;
-    const uint32_t scol = lay.sc_log2 >= 31u ? 0u : (r >> lay.sc_log2);
-    const uint32_t sin = r - scol * lay.Sc;
-    int8_t *row = G + (((vcol * lay.n_sc + scol) * lay.Sc + sin) * lay.Vc) * 2ull;
-    const uint64_t b0 = c0 * 2ull, b1 = c1 * 2ull;
-    // 16-byte segments
-    const uint64_t seg0 = b0 / 16ull, seg1 = (b1 + 15ull) / 16ull;
-    for (uint64_t sgm = seg0 + blockIdx.x * blockDim.x + threadIdx.x; sgm < seg1;
-         sgm += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t lo = sgm * 16ull, hi = lo + 16ull;
-        if (lo >= b0 && hi <= b1)
-            *reinterpret_cast<uint4 *>(row + lo) = make_uint4(0, 0, 0, 0);
-        else
-            for (uint64_t b = lo < b0 ? b0 : lo; b < (hi > b1 ? b1 : hi); ++b) row[b] = 0;
-    }
-}
-
-// cursor form of the tail padding: the kept count lives in device memory (asynchronous chains)
-__global__ __launch_bounds__(256) void k_zero_tail_cursor(LayoutDev lay, const uint64_t *__restrict__ d_cursor,
-                                                          int8_t *__restrict__ G)
-{
-    const uint64_t v_end = *d_cursor;
-    uint64_t vcol = v_end / lay.Vc;
-    const uint64_t c0 = v_end - vcol * lay.Vc;
-    if (c0 == 0) return;                       // the cursor sits on a column boundary: nothing is open
-    if (lay.ring) vcol %= lay.ring;
-    const uint32_t r = blockIdx.y;             // padded sample row
-    const uint32_t scol = lay.sc_log2 >= 31u ? 0u : (r >> lay.sc_log2);
-    const uint32_t sin = r - scol * lay.Sc;
-    int8_t *row = G + (((vcol * lay.n_sc + scol) * lay.Sc + sin) * lay.Vc) * 2ull;
-    const uint64_t b0 = r < lay.S ? c0 * 2ull : 0ull, b1 = lay.Vc * 2ull;   // sample padding rows: the whole row
     const uint64_t seg0 = b0 / 16ull, seg1 = (b1 + 15ull) / 16ull;
     for (uint64_t sgm = seg0 + blockIdx.x * blockDim.x + threadIdx.x; sgm < seg1; sgm += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t lo = sgm * 16ull, hi = lo + 16ull;
@@ -943,6 +923,26 @@ __global__ __launch_bounds__(256) void k_zero_tail_cursor(LayoutDev lay, const u
         else
             for (uint64_t b = lo < b0 ? b0 : lo; b < (hi > b1 ? b1 : hi); ++b) row[b] = 0;
     }
+}
+
+// zero columns [c0, c1) (variant index inside the chunk column) of rows [r0, r1) (sample index inside
+// the padded sample axis) of chunk column vcol
+__global__ __launch_bounds__(256) void k_zero_rect(LayoutDev lay, uint64_t vcol0, uint32_t r0, uint32_t r1, uint64_t c0, uint64_t c1, int8_t *__restrict__ G)
+{
+    const uint64_t vcol = vcol0 + blockIdx.z;   // one launch covers a range of chunk columns
+    const uint32_t r = r0 + blockIdx.y;
+    if (r >= r1) return;
+    zero_row_bytes(G + matrix_row(lay, vcol, r), c0 * 2ull, c1 * 2ull);
+}
+
+// cursor form of the tail padding: the kept count lives in device memory (asynchronous chains)
+__global__ __launch_bounds__(256) void k_zero_tail_cursor(LayoutDev lay, const uint64_t *__restrict__ d_cursor, int8_t *__restrict__ G)
+{
+    uint64_t vcol, c0;
+    column_of(lay, *d_cursor, &vcol, &c0);
+    if (c0 == 0) return;                       // the cursor sits on a column boundary: nothing is open
+    const uint32_t r = blockIdx.y;             // padded sample row
+    zero_row_bytes(G + matrix_row(lay, vcol, r), r < lay.S ? c0 * 2ull : 0ull, lay.Vc * 2ull);   // sample padding rows: the whole row
 }
 
 int launch_pad_tail_cursor(LayoutDev lay, const uint64_t *d_cursor, int8_t *d_G, hipStream_t st)
@@ -1035,11 +1035,9 @@ __global__ __launch_bounds__(256) void k_zero_planes_rect(LayoutDev lay, uint64_
 
 __global__ __launch_bounds__(256) void k_zero_planes_cursor(LayoutDev lay, const uint64_t *__restrict__ d_cursor, uint8_t *__restrict__ P)
 {
-    const uint64_t v_end = *d_cursor;
-    uint64_t vcol = v_end / lay.Vc;
-    const uint64_t c0 = v_end - vcol * lay.Vc;
+    uint64_t vcol, c0;
+    column_of(lay, *d_cursor, &vcol, &c0);
     if (c0 == 0) return;                       // the cursor sits on a column boundary: nothing is open
-    if (lay.ring) vcol %= lay.ring;
     zero_planes_rows(lay, vcol, 0u, lay.n_sc * lay.Sc, c0, lay.S, P);
 }
 
@@ -1088,10 +1086,7 @@ __global__ __launch_bounds__(256) void k_planes_expand(LayoutDev lay, PlanesGeom
     const uint64_t kstride = (uint64_t)pg.S_pad * 16ull;        // 16-bit words between kind-planes
     const uint16_t *pl = reinterpret_cast<const uint16_t *>(P + planes_piece(pg, col, tile, 0u, row)) + sub;
     const uint32_t o0 = pl[0], o1 = pl[kstride], e0 = pl[2ull * kstride], e1 = pl[3ull * kstride];
-    // byte offset of the block inside the int8 matrix (chunk-tiled layout: column, sample chunk, row in chunk)
-    const uint32_t scol = lay.sc_log2 >= 31u ? 0u : (row >> lay.sc_log2);
-    const uint32_t sin = row - scol * lay.Sc;
-    const uint64_t base = ((((col * lay.n_sc + scol) * lay.Sc + sin) * lay.Vc) + (uint64_t)bi * 4096ull + 16ull * t) * 2ull;
+    const uint64_t base = matrix_at(lay, col, row, (uint64_t)bi * 4096ull + 16ull * t);   // this thread's 16 variants of the block
     uint32_t w[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {

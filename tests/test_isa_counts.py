@@ -21,7 +21,13 @@ on an occupancy line (72 VGPRs at seven waves per SIMD, 64 at eight).  Its LDS i
 The same for csrc/index.hip: k_index_hop is a loop over inlined phases and k_parse_fixed a sequence of steps,
 and the four instantiations of the one and the other keep what they had as one function body each — here the scalar side
 counts too (the walk's state is wave-uniform and must stay in scalar registers: SGPRs and SGPR spills are part of the budget).
-The instruction lines of each body are printed beside profiles/r15_index_isa.txt."""
+The instruction lines of each body are printed beside profiles/r15_index_isa.txt.
+
+The same for csrc/encode.hip (DESIGN.md §3 "The encode kernels as named phases"): the three encode kernels are drivers over inlined phases, and they and the
+padding / expand kernels beside them keep what they had as one function body each, scalar side included (a tile's place and a
+line's place are wave-uniform); k_encode_planes sits two registers under the last count at which four workgroups share a CU.  The
+static LDS of the encode kernels is held exactly.  k_encode_general must still reach its staged piece through LDS byte reads
+and through no flat load (the address-space comments in encode.hip).  Body lines are printed beside profiles/r16_encode_isa.txt."""
 import os
 import re
 import shutil
@@ -77,6 +83,16 @@ LZ4_BUDGET = {(0, 5, False): (76, 0, 0), (8, 5, False): (64, 12, 48), (0, 6, Fal
 INDEX_BUDGET = {"k_index_hopILi5ELb1EE": (94, 106, 8, 0, 0, 0), "k_index_hopILi3ELb1EE": (57, 106, 2, 0, 0, 0),
                 "k_index_hopILi5ELb0EE": (52, 101, 0, 0, 0, 0), "k_index_hopILi3ELb0EE": (42, 89, 0, 0, 0, 0),
                 "k_parse_fixed": (83, 82, 0, 0, 0, 17432)}
+
+
+# kernel of encode.hip as it stands in the mangled name -> (VGPRs, SGPRs, SGPR spills, spilled VGPRs, scratch bytes, static LDS
+# bytes, non-empty body lines) before the encode kernels were cut into phases; the body lines are printed, not asserted
+ENCODE_BUDGET = {"k_encode_tiles": (78, 81, 0, 0, 0, 32768, 8902), "k_encode_planes": (127, 95, 0, 0, 0, 32768, 16434),
+                 "k_encode_generalILb1EE": (111, 106, 12, 0, 0, 12544, 2138), "k_encode_generalILb0EE": (108, 106, 0, 0, 0, 12544, 1959),
+                 "k_zero_rect": (28, 32, 0, 0, 0, 0, 233), "k_zero_tail_cursor": (28, 35, 0, 0, 0, 0, 539),
+                 "k_zero_planes_rect": (12, 22, 0, 0, 0, 0, 163), "k_zero_planes_cursor": (14, 33, 0, 0, 0, 0, 457),
+                 "k_planes_expand": (40, 40, 0, 0, 0, 0, 905)}
+ENCODE_GENERAL_FLAT_LOADS = 0    # flat_load instructions in either instantiation of k_encode_general before the pass
 
 
 def gfx950_asm(tmp_path_factory, stem):
@@ -214,3 +230,32 @@ def test_bytewise_coder_budget(lz4_asm, mw, effort, planes):
     assert meta["vgpr_spill_count"] <= vgpr_spills, meta["vgpr_spill_count"]
     assert meta["private_segment_fixed_size"] <= scratch, meta["private_segment_fixed_size"]
     assert meta["group_segment_fixed_size"] == 0, meta["group_segment_fixed_size"]
+
+
+@pytest.fixture(scope="module")
+def encode_asm(tmp_path_factory):
+    return gfx950_asm(tmp_path_factory, "encode")
+
+
+@pytest.mark.parametrize("kernel", sorted(ENCODE_BUDGET))
+def test_encode_budget(encode_asm, kernel):
+    meta = kernel_meta(encode_asm, kernel)
+    body = [ln for ln in kernel_body(encode_asm, kernel).splitlines() if ln.strip()]
+    budget, parent_lines = ENCODE_BUDGET[kernel][:6], ENCODE_BUDGET[kernel][6]
+    print(meta_line(kernel, meta) + f", {len(body)} lines of kernel body (before the pass: {parent_lines}; profiles/r16_encode_isa.txt)")
+    vgprs, sgprs, sgpr_spills, vgpr_spills, scratch, lds = budget
+    assert meta["vgpr_count"] <= vgprs, meta["vgpr_count"]
+    assert meta["sgpr_count"] <= sgprs, meta["sgpr_count"]
+    assert meta["sgpr_spill_count"] <= sgpr_spills, meta["sgpr_spill_count"]
+    assert meta["vgpr_spill_count"] <= vgpr_spills, meta["vgpr_spill_count"]
+    assert meta["private_segment_fixed_size"] <= scratch, meta["private_segment_fixed_size"]
+    assert meta["group_segment_fixed_size"] <= lds, meta["group_segment_fixed_size"]
+    if kernel.startswith("k_encode"):
+        assert meta["group_segment_fixed_size"] == lds, meta["group_segment_fixed_size"]
+
+
+@pytest.mark.parametrize("kernel", ["k_encode_generalILb1EE", "k_encode_generalILb0EE"])
+def test_general_kernel_reads_its_piece_from_lds(encode_asm, kernel):
+    body = kernel_body(encode_asm, kernel)
+    assert re.search(r"\bds_read_u8\b", body), kernel
+    assert len(re.findall(r"\bflat_load\w*", body)) <= ENCODE_GENERAL_FLAT_LOADS, kernel
